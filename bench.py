@@ -17,6 +17,10 @@ same frame.  Either launched by torch.distributed.run (RANK / WORLD_SIZE in the 
 torch or loaded the HIP library, so nothing that touched a GPU is ever re-executed -- relays rank 0's JSON
 line, and kills every rank and exits non-zero if one fails or the run exceeds its deadline.
 
+A plain run sets up (one GI pass), warms up, times --steps steps and prints the headline; --full adds every other
+figure and check of the line (stage times, kernel time, roofline, sweeps, HBM stress, CPU baseline, the N > 1 blocks).
+--dump-outputs DIR writes the frame of the last timed step.
+
 Prints one JSON line (rank 0).
 """
 import argparse
@@ -98,6 +102,14 @@ def parse():
                          "trace launch of the kernel trace then has the GPU to itself)")
     ap.add_argument("--timeout", type=float, default=float(os.environ.get("VCT_BENCH_TIMEOUT_S", "900")),
                     help="self-launched N > 1 run: seconds before the parent kills every rank and exits non-zero")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: per-stage GI pass times, the one-call GI pass, trace kernel time, "
+                         "the other frames-in-flight form, roofline / stage roofline, roughness sweep, exactness tax, HBM "
+                         "stress, CPU baseline, the multi_gpu block and the gathered-frame check (N > 1).  Without it a run "
+                         "sets up, warms up, times --steps steps and prints the headline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the frame of the last step (RGBA, float32 [height, width, 4]) "
+                         "as DIR/frame.npy (rank 0); above 64 MiB a fixed seeded sample of its pixels (dump_outputs)")
     return ap.parse_args()
 
 
@@ -278,56 +290,71 @@ def main():
         if inp["scene"] is not None:
             s = inp["scene"]
             ctx.upload_scene(s)         # triangles, frames, and (textured scenes) texture coordinates + maps
-            # 12 passes, every stage bracketed by events; reported = median of the last 5 (the first passes warm
-            # allocations and caches, bring the clocks up after the host-side scene set-up, and -- scenes with alpha-tested
-            # textures -- are the six passes in which the context samples both visibility forms before it keeps one)
-            passes = []
-            for _ in range(12):
-                ei = [ev() for _ in range(3)]
-                ei[0].record(); ctx.render_shadow_map(inp["light_vp"])        # DrawDepthTexture
-                ei[1].record(); ctx.render_gbuffer(inp["view_proj"])          # raster part of Render
-                ei[2].record()
-                e = [ev() for _ in range(4)]
-                e[0].record(); ctx.voxelize()
-                e[1].record(); ctx.inject_light()
-                e[2].record(); ctx.build_mips()
-                e[3].record()
+            if not args.full:
+                # the steps need the pass's products (brick chain, resident G-buffer), not its stage times: one pass
+                ctx.render_shadow_map(inp["light_vp"])
+                ctx.render_gbuffer(inp["view_proj"])
+                ctx.voxelize()
+                ctx.inject_light()
+                ctx.build_mips()
                 if args.bounces == 2:
-                    e.append(ev())
-                    ctx.bounce()                 # bounce kernel + mips of the bounce-1 chain
-                    e[4].record()
+                    ctx.bounce()
                 ctx.synchronize()
-                one = {"voxelize": e[0].elapsed_time(e[1]), "inject_resolve": e[1].elapsed_time(e[2]),
-                       "build_mips": e[2].elapsed_time(e[3]), "shadow_map_raster": ei[0].elapsed_time(ei[1]),
-                       "gbuffer_raster": ei[1].elapsed_time(ei[2])}
+            else:
+                # 12 passes, every stage bracketed by events; reported = median of the last 5 (the first passes warm
+                # allocations and caches, bring the clocks up after the host-side scene set-up, and -- scenes with alpha-tested
+                # textures -- are the six passes in which the context samples both visibility forms before it keeps one)
+                passes = []
+                for _ in range(12):
+                    ei = [ev() for _ in range(3)]
+                    ei[0].record(); ctx.render_shadow_map(inp["light_vp"])        # DrawDepthTexture
+                    ei[1].record(); ctx.render_gbuffer(inp["view_proj"])          # raster part of Render
+                    ei[2].record()
+                    e = [ev() for _ in range(4)]
+                    e[0].record(); ctx.voxelize()
+                    e[1].record(); ctx.inject_light()
+                    e[2].record(); ctx.build_mips()
+                    e[3].record()
+                    if args.bounces == 2:
+                        e.append(ev())
+                        ctx.bounce()                 # bounce kernel + mips of the bounce-1 chain
+                        e[4].record()
+                    ctx.synchronize()
+                    one = {"voxelize": e[0].elapsed_time(e[1]), "inject_resolve": e[1].elapsed_time(e[2]),
+                           "build_mips": e[2].elapsed_time(e[3]), "shadow_map_raster": ei[0].elapsed_time(ei[1]),
+                           "gbuffer_raster": ei[1].elapsed_time(ei[2])}
+                    if args.bounces == 2:
+                        one["bounce_and_mips"] = e[3].elapsed_time(e[4])
+                    passes.append(one)
+                gi = {k: float(np.median([q[k] for q in passes[-5:]])) for k in passes[-1]}
                 if args.bounces == 2:
-                    one["bounce_and_mips"] = e[3].elapsed_time(e[4])
-                passes.append(one)
-            gi = {k: float(np.median([q[k] for q in passes[-5:]])) for k in passes[-1]}
-            if args.bounces == 2:
-                gi["bounce_cone_steps"] = float(ctx.last_step_count())
-            if args.bounces != 2 and world == 1:
-                # the same six stages as ONE call (vct_gi_pass: G-buffer raster on a second stream beside the
-                # voxel stages) -- wall time of the whole pass, events around the calls, mean of 20 after 5 warm-ups
-                ctx.set_trace_timing(False)       # a frame loop: no timing events around the trace (include/vct.h)
-                for _ in range(5):
-                    ctx.gi_pass(inp["light_vp"], inp["view_proj"])
-                ef = [ev(), ev()]
-                ef[0].record()
-                for _ in range(20):
-                    ctx.gi_pass(inp["light_vp"], inp["view_proj"])
-                ef[1].record()
-                ctx.synchronize()
-                ctx.set_trace_timing(True)
-                gi_fused = ef[0].elapsed_time(ef[1]) / 20.0
-            stage_counts = ctx.stage_counts()
-            inp["planes"] = ctx.download_gbuffer()     # host copy only for the CPU baseline / checks
+                    gi["bounce_cone_steps"] = float(ctx.last_step_count())
+                if args.bounces != 2 and world == 1:
+                    # the same six stages as ONE call (vct_gi_pass: G-buffer raster on a second stream beside the
+                    # voxel stages) -- wall time of the whole pass, events around the calls, mean of 20 after 5 warm-ups
+                    ctx.set_trace_timing(False)       # a frame loop: no timing events around the trace (include/vct.h)
+                    for _ in range(5):
+                        ctx.gi_pass(inp["light_vp"], inp["view_proj"])
+                    ef = [ev(), ev()]
+                    ef[0].record()
+                    for _ in range(20):
+                        ctx.gi_pass(inp["light_vp"], inp["view_proj"])
+                    ef[1].record()
+                    ctx.synchronize()
+                    ctx.set_trace_timing(True)
+                    gi_fused = ef[0].elapsed_time(ef[1]) / 20.0
+                stage_counts = ctx.stage_counts()
+                inp["planes"] = ctx.download_gbuffer()     # host copy only for the CPU baseline / checks
         else:
             ctx.upload_volume(inp["volume"])
-            e = [ev(), ev()]
-            e[0].record(); ctx.build_mips(); e[1].record()
-            ctx.synchronize()
-            gi = {"voxelize": None, "inject_resolve": None, "build_mips": e[0].elapsed_time(e[1])}
+            if not args.full:
+                ctx.build_mips()
+                ctx.synchronize()
+            else:
+                e = [ev(), ev()]
+                e[0].record(); ctx.build_mips(); e[1].record()
+                ctx.synchronize()
+                gi = {"voxelize": None, "inject_resolve": None, "build_mips": e[0].elapsed_time(e[1])}
 
     # ---- slab of this rank ----
     # native (default for N > 1): vct_comm_init allocates two gather buffers per rank; vct_frame_step makes the
@@ -520,6 +547,16 @@ def main():
     for ev_ in gathered:                          # "previous gather" of the first use of each buffer
         ev_.record(ext_stream)
 
+    def last_frame():
+        """The RGBA16F frame (uint16 [h, w, 4]) of the last step, on rank 0 (None on the other ranks)."""
+        if not use_dist:
+            return ctx.download_frame()           # the frame (or frame target) of the selected slot: the last step's
+        if rank != 0:
+            return None
+        if native:
+            return ctx.comm_download_frame()
+        return fgs[(step_no[0] - 1) % len(fgs)].frame[:h].cpu().numpy().view(np.uint16)
+
     kernel_ms = []
     # Untimed pre-roll: the set-up above ends with ~40 ms of host work (G-buffer download for the CPU baseline, step
     # counts) during which the GPU idles and drops its clocks; the first ~25 launches after that run up to 18 % slow
@@ -540,52 +577,53 @@ def main():
     t_issue = time.perf_counter() - t0            # host time to ISSUE the steps (pacing overhead)
     fence()
     dt = time.perf_counter() - t0
-    # per-launch device time of the trace kernel: HIP events on the context's stream, collected
-    # in a second, untimed loop so the event reads do not serialise the timed region
-    fence()
-    # (one launch in flight at a time here, whatever --frames-in-flight: the duration of a launch that has the GPU to
-    # itself -- what rocprofv3 reports for the same launches and what the roofline block prices)
-    dt_one = None
-    if fif == 2:
-        ctx.select_frame_slot(0)
-        t1 = time.perf_counter()
-        for _ in range(args.steps):
-            if native:
-                ctx.frame_step()
-            else:
-                ctx.trace_resident()
+    frame = last_frame() if args.dump_outputs else None     # what the last timed step computed
+    dt_one = dt_two = None
+    if args.full:
+        # per-launch device time of the trace kernel: HIP events on the context's stream, collected
+        # in a second, untimed loop so the event reads do not serialise the timed region
         fence()
-        dt_one = time.perf_counter() - t1     # the same K steps on ONE stream: what frames_in_flight buys, same run
-    ctx.set_trace_timing(True)
-    for _ in range(min(args.steps, 20)):
-        ctx.trace_resident()
-        kernel_ms.append(ctx.last_trace_ms())
-    fence()
-    ctx.set_trace_timing(False)
-    dt_two = None
-    if fif == 1 and not use_dist and args.variant != 4 and args.frames_in_flight == 1 and not args.no_two_slots:
-        # ... and the other way round: the same K steps alternating between two frame slots, timed beside the headline
-        try:
-            ctx.set_frames_in_flight(2)
-            setup_slot1()
-            for k in range(PREROLL_STEPS + args.warmup):
-                ctx.select_frame_slot(k & 1); ctx.trace_resident()
-            fence()
-            t1 = time.perf_counter()
-            for k in range(args.steps):
-                ctx.select_frame_slot(k & 1); ctx.trace_resident()
-            fence()
-            dt_two = time.perf_counter() - t1
+        # (one launch in flight at a time here, whatever --frames-in-flight: the duration of a launch that has the GPU to
+        # itself -- what rocprofv3 reports for the same launches and what the roofline block prices)
+        if fif == 2:
             ctx.select_frame_slot(0)
-            ctx.set_frames_in_flight(1)
-        except vct.VctError as e:
-            print(f"[bench] two frames in flight unavailable ({e}); not measured", file=sys.stderr)
+            t1 = time.perf_counter()
+            for _ in range(args.steps):
+                if native:
+                    ctx.frame_step()
+                else:
+                    ctx.trace_resident()
+            fence()
+            dt_one = time.perf_counter() - t1     # the same K steps on ONE stream: what frames_in_flight buys, same run
+        ctx.set_trace_timing(True)
+        for _ in range(min(args.steps, 20)):
+            ctx.trace_resident()
+            kernel_ms.append(ctx.last_trace_ms())
+        fence()
+        ctx.set_trace_timing(False)
+        if fif == 1 and not use_dist and args.variant != 4 and args.frames_in_flight == 1 and not args.no_two_slots:
+            # ... and the other way round: the same K steps alternating between two frame slots, timed beside the headline
+            try:
+                ctx.set_frames_in_flight(2)
+                setup_slot1()
+                for k in range(PREROLL_STEPS + args.warmup):
+                    ctx.select_frame_slot(k & 1); ctx.trace_resident()
+                fence()
+                t1 = time.perf_counter()
+                for k in range(args.steps):
+                    ctx.select_frame_slot(k & 1); ctx.trace_resident()
+                fence()
+                dt_two = time.perf_counter() - t1
+                ctx.select_frame_slot(0)
+                ctx.set_frames_in_flight(1)
+            except vct.VctError as e:
+                print(f"[bench] two frames in flight unavailable ({e}); not measured", file=sys.stderr)
     ctx.set_trace_timing(True)
 
     # N > 1 lines explain themselves: what RCCL says the communicator is, every rank's slab kernel time, step count and
     # exchange-step time (untimed reads, after the timed region)
     multi = None
-    if use_dist and native:
+    if args.full and use_dist and native:
         info = ctx.comm_info()
         ctx.frame_step()
         mine = {"rank": rank, "rccl": info, "slab_kernel_ms": round(float(np.mean(kernel_ms)), 4),
@@ -606,7 +644,7 @@ def main():
     red_dev = "cpu"                               # control plane over gloo
     tmax = torch.tensor([dt], dtype=torch.float64, device=red_dev)
     steps_all = torch.tensor([steps_slab], dtype=torch.float64, device=red_dev)
-    kmax = torch.tensor([float(np.mean(kernel_ms))], dtype=torch.float64, device=red_dev)
+    kmax = torch.tensor([float(np.mean(kernel_ms)) if kernel_ms else 0.0], dtype=torch.float64, device=red_dev)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dist.all_reduce(steps_all, op=dist.ReduceOp.SUM)
@@ -616,7 +654,9 @@ def main():
     kernel_ms_avg = float(kmax.item())
 
     gather_ok = None
-    if use_dist:
+    if use_dist and not args.full and native:
+        ctx.comm_destroy()
+    elif use_dist and args.full:
         # acceptance check of SURVEY.md 8e, untimed: the gathered frame is bit-identical to the frame
         # one GPU traces alone
         if native:
@@ -640,49 +680,17 @@ def main():
                 alone = ctx.trace(inp["planes"])
             gather_ok = bool(np.array_equal(full, alone))
 
-    if rank == 0:
+    def full_figures():
+        """What --full adds to rank 0's line: the measurements and checks beside the headline (untimed, after it)."""
         npix = w * h
         cones = npix * 7
         ms_per_step = dt / args.steps * 1e3
-        value = cones / (dt / args.steps) / 1e6
         # roofline of the dominant kernel (trace) on this rank's launch
         alg_bytes = steps_slab * BYTES_PER_STEP + slab_px * BYTES_PER_PIXEL
         k_ms = float(np.mean(kernel_ms))
         alg_gbs = alg_bytes / (k_ms * 1e-3) / 1e9
         prof = pmc_profile(args, world)
         result = {
-            "metric": "Mcones/s (+ ms per GI pass), Sponza-class 256^3 @1080p" if (V, w, h) == (256, 1920, 1080)
-            else f"Mcones/s (+ ms per GI pass), Sponza-class {V}^3 @{w}x{h}",
-            "value": round(value, 1),
-            "unit": "Mcones/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "preroll_steps": PREROLL_STEPS,      # untimed, before the warm-up steps (clock ramp after the host-side set-up)
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic" if not args.obj else "user-supplied mesh",
-            "config": {"workload": f"{inp['label']}, {V}^3 RGBA8 brick chain, {w}x{h}, 6 diffuse + 1 "
-                                   f"specular cone/px, trace of a resident (GPU-rasterised) G-buffer",
-                       "voxel_dim": V, "width": w, "height": h, "cones_per_pixel": 7, "bounces": args.bounces,
-                       "anisotropic_mips": bool(args.anisotropic),
-                       "parallelism": ("single GPU" + (", 2 frames in flight (consecutive steps on alternate frame slots)" if fif == 2 else "")) if world == 1 else
-                       f"{world} screen-tile slabs ({args.slabs if native else 'equal'}) + 1 RCCL gather " +
-                       ("(native vct_frame_step" + (", direct slabs: no collective)" if direct else ")") if native
-                        else "(Python-paced step, torch.distributed gather)") +
-                       ("" if backend == "nccl" else f" [FUNCTIONAL TEST over {backend}, not a measurement]") +
-                       ("" if not native_fallback else f" [native communicator unavailable: {native_fallback}]"),
-                       "slabs": args.slabs if (native and use_dist) else ("equal" if use_dist else None),
-                       "trace_variant": args.variant, "footprint_records": bool(args.footprint_records),
-                       "comm_mode": None if world == 1 and not force_dist else ("direct slabs (experimental)" if direct and native else "rccl"),
-                       # compute units kept away from the trace for the gather's stream (VCT_COMM_RESERVED_CUS; 0: none)
-                       "comm_reserved_cus": ctx.stage_counts().get("comm_reserved_cus", 0),
-                       # visibility form of the G-buffer pass that was timed (chosen per context by timing both, DESIGN.md 3.4)
-                       "raster_form": {0: None, 1: "direct", 2: "tile-binned"}.get(ctx.stage_counts().get("raster_form", 0)),
-                       "slab_tile_rows": [b - a for a, b in slab_rows]},
             "frames_in_flight": {"n": fif, "slot_streams_overlap": ctx.frame_slot_streams_overlap() if fif == 2 else None,
                                  "ms_per_step_one_stream": None if dt_one is None else round(dt_one / args.steps * 1e3, 4),
                                  "ms_per_step_two_slots": None if dt_two is None else round(dt_two / args.steps * 1e3, 4),
@@ -695,9 +703,7 @@ def main():
             "trace_timing_events": "off in the timed steps and in gi_pass_one_call_ms (vct_set_trace_timing(0): the way a frame loop "
                                    "issues launches -- the two events vct_last_trace_ms reads cost a launch ~7 us of dispatch gaps); "
                                    "on for trace_kernel_ms, measured in its own loop",
-            "cone_steps_per_frame": total_steps,
             "gathered_frame_equals_single_gpu_frame": gather_ok,
-            "host_issue_us_per_step": round(t_issue / args.steps * 1e6, 2),
             "trace_kernel_ms": round(kernel_ms_avg, 4),
             "gi_pass_ms": {k: (None if v is None else round(v, 4)) for k, v in gi.items()}
             | {"trace": round(kernel_ms_avg, 4)},
@@ -777,11 +783,77 @@ def main():
             result["cpu_baseline"] = {"value": None, "unit": "Mcones/s", "cores": None, "kind": "port",
                                       "sample": "not timed at N > 1: the figure is the N = 1 line's cpu_baseline "
                                                 "(same workload, same host)"}
+        return result
+
+    if rank == 0:
+        npix = w * h
+        cones = npix * 7
+        ms_per_step = dt / args.steps * 1e3
+        value = cones / (dt / args.steps) / 1e6
+        if frame is not None:
+            dump_outputs(args.dump_outputs, vct.half_to_float(frame))
+        result = {
+            "metric": "Mcones/s (+ ms per GI pass), Sponza-class 256^3 @1080p" if (V, w, h) == (256, 1920, 1080)
+            else f"Mcones/s (+ ms per GI pass), Sponza-class {V}^3 @{w}x{h}",
+            "value": round(value, 1),
+            "unit": "Mcones/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "preroll_steps": PREROLL_STEPS,      # untimed, before the warm-up steps (clock ramp after the host-side set-up)
+            "ms_per_step": round(ms_per_step, 4),
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic" if not args.obj else "user-supplied mesh",
+            "config": {"workload": f"{inp['label']}, {V}^3 RGBA8 brick chain, {w}x{h}, 6 diffuse + 1 "
+                                   f"specular cone/px, trace of a resident (GPU-rasterised) G-buffer",
+                       "voxel_dim": V, "width": w, "height": h, "cones_per_pixel": 7, "bounces": args.bounces,
+                       "anisotropic_mips": bool(args.anisotropic),
+                       "parallelism": ("single GPU" + (", 2 frames in flight (consecutive steps on alternate frame slots)" if fif == 2 else "")) if world == 1 else
+                       f"{world} screen-tile slabs ({args.slabs if native else 'equal'}) + 1 RCCL gather " +
+                       ("(native vct_frame_step" + (", direct slabs: no collective)" if direct else ")") if native
+                        else "(Python-paced step, torch.distributed gather)") +
+                       ("" if backend == "nccl" else f" [FUNCTIONAL TEST over {backend}, not a measurement]") +
+                       ("" if not native_fallback else f" [native communicator unavailable: {native_fallback}]"),
+                       "slabs": args.slabs if (native and use_dist) else ("equal" if use_dist else None),
+                       "trace_variant": args.variant, "footprint_records": bool(args.footprint_records),
+                       "comm_mode": None if world == 1 and not force_dist else ("direct slabs (experimental)" if direct and native else "rccl"),
+                       # compute units kept away from the trace for the gather's stream (VCT_COMM_RESERVED_CUS; 0: none)
+                       "comm_reserved_cus": ctx.stage_counts().get("comm_reserved_cus", 0),
+                       # visibility form of the G-buffer pass that was timed (chosen per context by timing both, DESIGN.md 3.4)
+                       "raster_form": {0: None, 1: "direct", 2: "tile-binned"}.get(ctx.stage_counts().get("raster_form", 0)),
+                       "slab_tile_rows": [b - a for a, b in slab_rows]},
+            "frames_in_flight": {"n": fif, "slot_streams_overlap": ctx.frame_slot_streams_overlap() if fif == 2 else None},
+            "cone_steps_per_frame": total_steps,
+            "host_issue_us_per_step": round(t_issue / args.steps * 1e6, 2),
+        }
+        if args.full:
+            result.update(full_figures())
         print(json.dumps(result), flush=True)
     ctx.close()
     if world > 1 or force_dist:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(path, frame):
+    """--dump-outputs: the last step's frame as float32 [h, w, 4] in path/frame.npy.  A frame above 64 MiB (4K) is
+    written as a fixed sample instead: frame.npy [n, 4] of the pixels listed (row-major index, float64) in
+    frame_pixel_index.npy, drawn with seed 0 -- the same pixels for the same arguments in every run."""
+    os.makedirs(path, exist_ok=True)
+    frame = np.ascontiguousarray(frame, np.float32)
+    if frame.nbytes > DUMP_BYTES_MAX:
+        flat = frame.reshape(-1, 4)
+        n = DUMP_BYTES_MAX // (16 + 8) // 2                    # frame rows + their indices, within half the cap
+        idx = np.sort(np.random.default_rng(0).choice(flat.shape[0], n, replace=False))
+        np.save(os.path.join(path, "frame_pixel_index.npy"), idx.astype(np.float64))
+        frame = flat[idx]
+    np.save(os.path.join(path, "frame.npy"), frame)
 
 
 def hbm_stress(vct, device):

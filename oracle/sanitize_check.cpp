@@ -9,6 +9,7 @@
 #include <vector>
 
 #include <dirent.h>
+#include <unistd.h>
 
 #include <string>
 
@@ -132,7 +133,15 @@ int main() {
         vcth_scene_destroy(s);
     }
     // OBJ reader incl. error paths
-    const char* path = "/tmp/vct_sanitize_cube.obj";
+    // a file of this run's own ($TMPDIR or /tmp, unique name): a fixed path may belong to another user
+    const char* tmp = getenv("TMPDIR");
+    const std::string tmpl = std::string(tmp && *tmp ? tmp : "/tmp") + "/vct_sanitize_cube_XXXXXX.obj";
+    std::vector<char> pathbuf(tmpl.begin(), tmpl.end());
+    pathbuf.push_back('\0');
+    char* path = pathbuf.data();
+    const int fd = mkstemps(path, 4);
+    if (fd < 0) { printf("cannot create %s\n", path); return 1; }
+    close(fd);
     FILE* f = fopen(path, "w");
     fputs("v 0 0 0\nv 1 0 0\nv 1 1 0\nv 0 1 0\nvt 0 0\nvt 1 0\nvt 1 1\nvn 0 0 1\nusemtl m\nf 1/1/1 2/2/1 3/3/1 4\nf -4 -3 -2\n", f);
     fclose(f);
@@ -142,7 +151,9 @@ int main() {
     vcth_scene_destroy(o);
     if (vcth_scene_load_obj("/nonexistent.obj", err) != nullptr) return 1;
     f = fopen(path, "w"); fputs("v 0 0 0\nf 1 2 9\n", f); fclose(f);
-    if (vcth_scene_load_obj(path, err) != nullptr) return 1;
+    const bool bad_obj_loaded = vcth_scene_load_obj(path, err) != nullptr;
+    unlink(path);
+    if (bad_obj_loaded) return 1;
     // small helpers
     float out4[4];
     const float pos3[3] = {1.0f, -2.0f, 3.0f};

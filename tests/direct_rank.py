@@ -45,6 +45,10 @@ else:
         time.sleep(0.01)
     ident = open(idfile, "rb").read()
 ctx.comm_init(ident, rank, world)
+if late:
+    # the short deadline is for vct_comm_sync; set after the rendezvous, which it would otherwise bound as well (a root
+    # slower than 150 ms to create its rendezvous block then fails rank 1's vct_comm_init instead)
+    ctx.comm_set_timeout_ms(150)
 info = ctx.comm_info()
 assert info["nranks"] == world and info["rank"] == rank
 if die and rank == world - 1:

@@ -61,3 +61,22 @@ def test_pmc_replay_files_are_chosen_by_workload_and_gated_by_the_source_sha():
     assert n2["ok"] == a["ok"] and (not n2["ok"] or (n2["scale_by_steps"] and n2["hbm_bytes_per_launch"] is None))
     # another variant / a bounce / a user mesh never replay
     assert not bench.pmc_profile(args(variant=3), 1)["ok"] and not bench.pmc_profile(args(bounces=2), 1)["ok"]
+
+
+def test_dump_outputs_writes_the_frame_and_samples_a_large_one_the_same_way(tmp_path):
+    """--dump-outputs: a 1080p frame is written whole (float32 [h, w, 4]); one above 64 MiB (4K) as a fixed, seeded
+    sample with its row-major pixel indices, the same pixels in every run, within the 64 MiB of the contract."""
+    import numpy as np
+    small = np.random.default_rng(1).random((1080, 1920, 4), dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "s"), small)
+    got = np.load(tmp_path / "s" / "frame.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small)
+    assert not (tmp_path / "s" / "frame_pixel_index.npy").exists()
+    big = np.random.default_rng(2).random((2160, 3840, 4), dtype=np.float32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    fa, ia = np.load(tmp_path / "a" / "frame.npy"), np.load(tmp_path / "a" / "frame_pixel_index.npy")
+    assert ia.dtype == np.float64 and fa.dtype == np.float32 and fa.shape == (ia.size, 4)
+    assert np.array_equal(ia, np.load(tmp_path / "b" / "frame_pixel_index.npy"))
+    assert np.array_equal(fa, big.reshape(-1, 4)[ia.astype(np.int64)])
+    assert np.all(np.diff(ia) > 0) and fa.nbytes + ia.nbytes <= 64 << 20

@@ -133,7 +133,7 @@ def test_two_ranks_sharing_the_gpu_gather_the_single_gpu_frame():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29611", os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--steps", "3", "--warmup", "1", "--width", "320", "--height", "180",
-           "--voxel-dim", "64", "--scene-detail", "0.15", "--shadow-size", "512", "--cpu-seconds", "0", "--no-sweep"]
+           "--voxel-dim", "64", "--scene-detail", "0.15", "--shadow-size", "512", "--cpu-seconds", "0", "--no-sweep", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
@@ -188,7 +188,7 @@ def test_native_bench_loop_with_forced_one_rank_group():
     env = dict(os.environ, VCT_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29613")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--width", "320",
            "--height", "180", "--voxel-dim", "64", "--scene-detail", "0.15", "--shadow-size", "512",
-           "--cpu-seconds", "0", "--no-sweep"]
+           "--cpu-seconds", "0", "--no-sweep", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
@@ -199,7 +199,7 @@ def test_native_bench_loop_interleaved_with_forced_one_rank_group():
     env = dict(os.environ, VCT_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29614")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--width", "320",
            "--height", "180", "--voxel-dim", "64", "--scene-detail", "0.15", "--shadow-size", "512",
-           "--cpu-seconds", "0", "--no-sweep", "--slabs", "interleaved"]
+           "--cpu-seconds", "0", "--no-sweep", "--slabs", "interleaved", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
@@ -235,7 +235,7 @@ def test_bench_native_step_prints_exactly_one_json_line():
     env = dict(os.environ, VCT_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29541")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
                           "--cpu-seconds", "0", "--no-sweep", "--voxel-dim", "64", "--width", "320", "--height", "200",
-                          "--shadow-size", "512", "--scene-detail", "0.2"],
+                          "--shadow-size", "512", "--scene-detail", "0.2", "--full"],
                          capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.split("\n") if ln.strip()]
@@ -257,7 +257,7 @@ def test_bench_self_launches_its_ranks_without_a_launcher():
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
            "--width", "320", "--height", "180", "--voxel-dim", "64", "--scene-detail", "0.15", "--shadow-size", "512",
-           "--cpu-seconds", "0", "--no-sweep"]
+           "--cpu-seconds", "0", "--no-sweep", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.split("\n") if ln.strip()]
@@ -374,7 +374,7 @@ def test_bench_falls_back_when_the_native_communicator_cannot_form():
                MASTER_PORT="29617")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--width", "320",
            "--height", "180", "--voxel-dim", "64", "--scene-detail", "0.15", "--shadow-size", "512",
-           "--cpu-seconds", "0", "--no-sweep"]
+           "--cpu-seconds", "0", "--no-sweep", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.split("\n") if ln.strip()]
@@ -420,9 +420,9 @@ def test_direct_slabs_teardown_with_waits_still_queued(tmp_path):
     frame are still QUEUED behind long compute: vct_comm_destroy raises the abort word, drains both streams and only then
     closes the IPC mappings (round-5 advisor: a GPU memory fault otherwise); the context stays usable."""
     idfile, out = str(tmp_path / "id"), str(tmp_path / "out.npz")
-    env = dict(os.environ, VCT_COMM_TIMEOUT_MS="150")
+    # (direct_rank.py sets the communicator's 150 ms deadline itself, once the rendezvous is done)
     procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "direct_rank.py"), str(r), "2", idfile, out, "late"],
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env) for r in range(2)]
+                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for r in range(2)]
     logs = [p.communicate(timeout=300)[0] for p in procs]
     assert procs[1].returncode == 3, logs[1][-2000:]          # the expected error, not a fault / abort
     assert procs[0].returncode == 0, logs[0][-2000:]
@@ -456,7 +456,7 @@ def test_bench_native_loop_two_ranks_direct_slabs_on_one_gpu(slabs):
     env = dict(os.environ, VCT_COMM_MODE="direct", VCT_BENCH_BACKEND="gloo")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--width", "320",
            "--height", "180", "--voxel-dim", "64", "--scene-detail", "0.15", "--shadow-size", "512", "--cpu-seconds", "0",
-           "--no-sweep", "--slabs", slabs]
+           "--no-sweep", "--slabs", slabs, "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -446,3 +446,33 @@ def test_facade_demo_with_two_frames_in_flight_prints_the_same_checksum():
     assert dl1.returncode == 0 and dl2.returncode == 0, dl1.stdout + dl2.stdout + dl2.stderr
     # (the option really was taken -- vct_demo once paired its arguments two by two and lost it behind --dynamic-light)
     assert "2 frames in flight" in dl2.stdout and last(dl1.stdout) == last(dl2.stdout)
+
+
+def test_bench_plain_run_dumps_the_frame_of_its_last_step(tmp_path):
+    """bench.py without --full: the headline line only, and --dump-outputs writes the frame of the last timed step --
+    the same frame the --full run of the same arguments computes (its extra measurements run after the dump)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    base = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--width", "320",
+            "--height", "180", "--voxel-dim", "64", "--scene-detail", "0.15", "--shadow-size", "512"]
+    lines = {}
+    for form in ("plain", "full"):
+        extra = ["--full", "--cpu-seconds", "0", "--no-sweep"] if form == "full" else []
+        out = subprocess.run(base + extra + ["--dump-outputs", str(tmp_path / form)], capture_output=True, text=True,
+                             timeout=600, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        got = [ln for ln in out.stdout.split("\n") if ln.strip()]
+        assert len(got) == 1, got
+        lines[form] = json.loads(got[0])
+    plain, full = lines["plain"], lines["full"]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in plain and key in full, key
+    assert plain["steps"] == 3 and plain["ms_per_step"] > 0 and plain["value"] > 0
+    assert plain["metric"] == full["metric"] and plain["unit"] == full["unit"] == "Mcones/s"
+    assert "roofline" not in plain and "gi_pass_ms" not in plain and "roofline" in full and "gi_pass_ms" in full
+    a, b = np.load(tmp_path / "plain" / "frame.npy"), np.load(tmp_path / "full" / "frame.npy")
+    assert a.dtype == np.float32 and a.shape == (180, 320, 4) and np.isfinite(a).all() and (a != 0).any()
+    assert np.array_equal(a, b)

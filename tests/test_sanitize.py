@@ -30,7 +30,7 @@ def _sample_images(d):
 
 
 def test_oracle_and_host_library_are_clean_under_asan_ubsan(tmp_path):
-    env = dict(os.environ)
+    env = dict(os.environ, TMPDIR=str(tmp_path))        # the OBJ reader's scratch files
     if _sample_images(str(tmp_path)):
         env["VCT_SANITIZE_IMAGES"] = str(tmp_path)      # + 15,000 corrupted copies through the image decoders
     out = subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "sanitize"], capture_output=True,

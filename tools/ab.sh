@@ -31,7 +31,7 @@ if [ -n "$PYTEST" ]; then
 fi
 for round in $(seq 1 $ROUNDS); do for lib in $LIBS; do use $lib
   for args in "$@"; do
-    timeout 600 python bench.py $args --steps $STEPS --warmup 5 --cpu-seconds 0 --no-sweep 2>/dev/null | grep "^{" | \
+    timeout 600 python bench.py --full $args --steps $STEPS --warmup 5 --cpu-seconds 0 --no-sweep 2>/dev/null | grep "^{" | \
       python -c "
 import sys, json
 d = json.loads(sys.stdin.read())

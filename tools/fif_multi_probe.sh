@@ -9,9 +9,9 @@ print('$1', 'ms_per_step', d['ms_per_step'], 'one stream', d['frames_in_flight']
 for r in 1 2; do
 for f in 1 2; do
 for sl in equal interleaved; do
-VCT_BENCH_FORCE_DIST=1 python bench.py --height 136 --slabs $sl --cpu-seconds 0 --no-sweep --steps 200 --frames-in-flight $f 2>/dev/null | line "1-rank rccl slab-size $sl fif=$f"
+VCT_BENCH_FORCE_DIST=1 python bench.py --full --height 136 --slabs $sl --cpu-seconds 0 --no-sweep --steps 200 --frames-in-flight $f 2>/dev/null | line "1-rank rccl slab-size $sl fif=$f"
 done
-VCT_BENCH_FORCE_DIST=1 python bench.py --slabs balanced --cpu-seconds 0 --no-sweep --steps 50 --frames-in-flight $f 2>/dev/null | line "1-rank rccl whole frame fif=$f"
+VCT_BENCH_FORCE_DIST=1 python bench.py --full --slabs balanced --cpu-seconds 0 --no-sweep --steps 50 --frames-in-flight $f 2>/dev/null | line "1-rank rccl whole frame fif=$f"
 done; done
-VCT_COMM_MODE=direct VCT_BENCH_BACKEND=gloo python bench.py --gpus 2 --steps 20 --warmup 2 --cpu-seconds 0 --no-sweep --slabs balanced --frames-in-flight 2 2>/dev/null | line "2 ranks direct fif=2"
-VCT_COMM_MODE=direct VCT_BENCH_BACKEND=gloo python bench.py --gpus 2 --steps 20 --warmup 2 --cpu-seconds 0 --no-sweep --slabs interleaved --frames-in-flight 2 2>/dev/null | line "2 ranks direct interleaved fif=2"
+VCT_COMM_MODE=direct VCT_BENCH_BACKEND=gloo python bench.py --full --gpus 2 --steps 20 --warmup 2 --cpu-seconds 0 --no-sweep --slabs balanced --frames-in-flight 2 2>/dev/null | line "2 ranks direct fif=2"
+VCT_COMM_MODE=direct VCT_BENCH_BACKEND=gloo python bench.py --full --gpus 2 --steps 20 --warmup 2 --cpu-seconds 0 --no-sweep --slabs interleaved --frames-in-flight 2 2>/dev/null | line "2 ranks direct interleaved fif=2"

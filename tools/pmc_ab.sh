@@ -20,7 +20,7 @@ for name in "$@"; do
   i=0
   for PMC in "${GROUPS_[@]}"; do
     i=$((i+1))
-    timeout 300 rocprofv3 --pmc $PMC --output-format csv -d "$OUT/$name.p$i" -o pmc -- python3 $ROOT/bench.py --cpu-seconds 0 --no-sweep --steps 3 --warmup 1 > "$OUT/$name.p$i.log" 2>&1
+    timeout 300 rocprofv3 --pmc $PMC --output-format csv -d "$OUT/$name.p$i" -o pmc -- python3 $ROOT/bench.py --full --cpu-seconds 0 --no-sweep --steps 3 --warmup 1 > "$OUT/$name.p$i.log" 2>&1
     f=$(find "$OUT/$name.p$i" -name '*counter_collection.csv' | head -1)
     if [ -n "$f" ]; then
       python3 - "$f" >> "$OUT/$name.txt" <<'PY'

@@ -8,8 +8,8 @@ cd $ROOT
 tools/profile_gpu.sh $TAG
 tools/profile_configs.sh $TAG
 L=gpurun_out/${TAG}_lines; mkdir -p $L
-python bench.py --steps 20 --warmup 5 > $L/bench_default.json 2> $L/bench_default.err
-python bench.py --steps 10 --warmup 3 --scene bistro --voxel-dim 1024 --width 3840 --height 2160 --cpu-seconds 0 > $L/bench_c5.json 2> $L/bench_c5.err
+python bench.py --full --steps 20 --warmup 5 > $L/bench_default.json 2> $L/bench_default.err
+python bench.py --full --steps 10 --warmup 3 --scene bistro --voxel-dim 1024 --width 3840 --height 2160 --cpu-seconds 0 > $L/bench_c5.json 2> $L/bench_c5.err
 tools/raster_prof.sh $TAG > $L/raster_binned.txt 2>&1
 tools/raster_prof.sh ${TAG}d direct > $L/raster_direct.txt 2>&1
 tools/vox_pmc.sh ${TAG}_atrium > $L/vox_atrium.txt 2>&1

@@ -8,6 +8,6 @@ d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$1', 'ms_per_step', d['ms_per_step'], 'kernel', d['trace_kernel_ms'], 'gi one call', d.get('gi_pass_one_call_ms'), 'gi sum', d.get('gi_pass_total_ms'))"; }
 for r in 1 2; do
 for p in 0 1; do
-VCT_STREAM_PROBE=$p VCT_BENCH_FORCE_DIST=1 python bench.py --height 136 --slabs equal --cpu-seconds 0 --no-sweep --steps 200 2>/dev/null | line "slab-loop probe=$p"
-VCT_STREAM_PROBE=$p python bench.py --cpu-seconds 0 --no-sweep --frames-in-flight 1 2>/dev/null | line "whole-frame probe=$p"
+VCT_STREAM_PROBE=$p VCT_BENCH_FORCE_DIST=1 python bench.py --full --height 136 --slabs equal --cpu-seconds 0 --no-sweep --steps 200 2>/dev/null | line "slab-loop probe=$p"
+VCT_STREAM_PROBE=$p python bench.py --full --cpu-seconds 0 --no-sweep --frames-in-flight 1 2>/dev/null | line "whole-frame probe=$p"
 done; done

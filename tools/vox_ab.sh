@@ -11,7 +11,7 @@ for round in 1 2; do for lib in $LIBS; do use $lib
     echo "r$round $lib [$args] $(python tools/vox_bench.py $args 2>/dev/null | grep 'texture_mipmaps=1 shadow=True' | sed 's/  inject.*//')"
   done
   for args in "--scene atrium" "--scene bistro --voxel-dim 1024 --width 3840 --height 2160"; do
-    python bench.py $args --steps 5 --warmup 2 --cpu-seconds 0 --no-sweep 2>/dev/null | grep "^{" | python -c "
+    python bench.py --full $args --steps 5 --warmup 2 --cpu-seconds 0 --no-sweep 2>/dev/null | grep "^{" | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); g = d['gi_pass_ms']
 print('r$round $lib [$args] gi:', ' '.join(f'{k}={v}' for k, v in g.items()), 'total', d['gi_pass_total_ms'], 'one_call', d['gi_pass_one_call_ms'])"

@@ -261,6 +261,61 @@ int vct_set_frame_target(vct_ctx* ctx, void* rgba16f_dev);
 int vct_download_frame(vct_ctx* ctx, void* out_rgba16f_host);
 int vct_synchronize(vct_ctx* ctx);
 
+/* ---- lighting components and per-component outputs --------------------------------------------------
+ * The reference's orchestrator declares ShowDiffuse, ShowIndirectDiffuse, ShowSpecular, ShowIndirectSpecular and
+ * ShowAmbientOcclusion (R/Voxel_Cone_Tracing.h:51), the shader the matching uniforms (S/VoxelConeTracing.fs:36-39)
+ * and the ternaries that would apply them (fs:190,203,215, commented out there).  Here the mask applies them; with
+ * ind = the weighted 6-cone gather (fs:194-199) and sc = the specular cone (fs:218) the composite (fs:188-227) is
+ *   dd   = SHOW_DIFFUSE           ? shadow * cos_theta : 0       fs:190
+ *   occ  = SHOW_AMBIENT_OCCLUSION ? 1 - ind.a          : 1       fs:201
+ *   ird  = SHOW_INDIRECT_DIFFUSE  ? ind.rgb            : 0       fs:203 (after occlusion is formed)
+ *   D    = (dd + occ * ird) * albedo.rgb                         fs:205
+ *   ds   = SHOW_SPECULAR          ? spec * shadow      : 0       fs:215
+ *   socc = SHOW_AMBIENT_OCCLUSION ? 1 - sc.a           : 1       fs:221
+ *   irs  = SHOW_INDIRECT_SPECULAR ? sc.rgb             : 0       (the rule of fs:203)
+ *   S    = (irs + socc * ds) * specColor.rgb                     fs:223
+ *   A    = ambient * albedo.rgb * occ                            fs:225
+ *   out  = (A + D + S, albedo.a)                                 fs:227; discarded pixels keep the clear colour
+ * VCT_SHOW_ALL (the default) is the unmasked arithmetic in the same order: the same bits as before the mask existed.
+ * A cone group is marched only when something reads it: the six diffuse cones when INDIRECT_DIFFUSE or
+ * AMBIENT_OCCLUSION is shown or the indirect-diffuse output is on; the specular cone when INDIRECT_SPECULAR is shown,
+ * or AMBIENT_OCCLUSION and SPECULAR both are, or the indirect-specular output is on.  A skipped cone adds no steps
+ * to the step counts and leaves 0 steps and a zero vec4 in the debug outputs.
+ * The mask is host state like the ambient factor: it applies from the next trace launch of any kind on (screen
+ * traces, resident traces, the GI pass, a rank's frame step).  Bits above VCT_SHOW_ALL are VCT_ERR_INVALID, and so
+ * is a mask other than VCT_SHOW_ALL with config.trace_variant 1 .. 4 (measurement kernels without the mask). */
+enum {
+    VCT_SHOW_DIFFUSE = 1,
+    VCT_SHOW_INDIRECT_DIFFUSE = 2,
+    VCT_SHOW_SPECULAR = 4,
+    VCT_SHOW_INDIRECT_SPECULAR = 8,
+    VCT_SHOW_AMBIENT_OCCLUSION = 16,
+    VCT_SHOW_ALL = 31
+};
+int vct_set_lighting_components(vct_ctx* ctx, uint32_t mask);
+int vct_get_lighting_components(const vct_ctx* ctx, uint32_t* mask);
+
+/* Per-component outputs (no reference counterpart; for renderers that denoise, accumulate or composite the GI terms
+ * apart): RGBA16F full frames beside the frame, same addressing and the same f32 -> f16 rounding, raw values (the
+ * mask does not change them):
+ *   VCT_AOV_INDIRECT_DIFFUSE   inDirectDiffuse of fs:194-199 (the weighted gather of cones 0..5, rgba)
+ *   VCT_AOV_INDIRECT_SPECULAR  inDirectSpecular of fs:218 (the specular cone, rgba)
+ *   VCT_AOV_DIRECT             (shadow * cos_theta, spec * shadow, shadow, 1)
+ * Discarded pixels (albedo.a < 0.5) are (0,0,0,0) in every output; rows no trace has written keep their old
+ * content.  The set call allocates (which = 0: frees) the requested buffers for every frame slot, so launches
+ * allocate nothing; a second frame slot gets its own set.  Refused (VCT_ERR_INVALID) with config.trace_variant
+ * 1 .. 4 and on a context of a multi-GPU frame (after the communicator's init: outputs are not gathered). */
+enum {
+    VCT_AOV_INDIRECT_DIFFUSE = 1,
+    VCT_AOV_INDIRECT_SPECULAR = 2,
+    VCT_AOV_DIRECT = 4
+};
+int vct_set_aov_outputs(vct_ctx* ctx, uint32_t which);
+/* One output of the selected frame slot (one_bit: exactly one VCT_AOV_* bit): a host copy of width*height*4 halves
+ * (waits for the slot's stream), or its device pointer and size for zero-copy consumers. */
+int vct_download_aov(vct_ctx* ctx, uint32_t one_bit, void* out_rgba16f_host);
+int vct_get_aov_device(vct_ctx* ctx, uint32_t one_bit, void** rgba16f_dev, size_t* bytes);
+
 /* ---- two frames in flight (round 6) -----------------------------------------------------------------
  * The reference's Render() (VCT.h:146-190) issues GL commands; the driver starts frame k + 1 while frame k
  * drains -- nothing in R/main.cpp:77-94 waits for a frame.  A HIP stream does wait: each whole-frame trace

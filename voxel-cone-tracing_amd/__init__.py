@@ -26,6 +26,10 @@ GB_LINEAR, GB_TILED = 0, 1
 MEM_HOST, MEM_DEVICE = 0, 1
 VOX_CONSERVATIVE_AVG, VOX_REFERENCE = 0, 1
 ABI_VERSION = 7
+# lighting components (include/vct.h: the reference's Show* switches) and per-component outputs
+SHOW_DIFFUSE, SHOW_INDIRECT_DIFFUSE, SHOW_SPECULAR, SHOW_INDIRECT_SPECULAR, SHOW_AMBIENT_OCCLUSION = 1, 2, 4, 8, 16
+SHOW_ALL = 31
+AOV_INDIRECT_DIFFUSE, AOV_INDIRECT_SPECULAR, AOV_DIRECT = 1, 2, 4
 
 # every symbol include/vct.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
@@ -47,7 +51,8 @@ ABI_SYMBOLS = [
     "vct_comm_set_timeout_ms", "vct_last_row_steps", "vct_slab_partition_weighted", "vct_comm_set_slab_rows",
     "vct_get_stage_counts", "vct_comm_info", "vct_comm_last_gather_ms", "vct_set_footprint_records",
     "vct_set_frames_in_flight", "vct_get_frames_in_flight", "vct_select_frame_slot", "vct_selftest_texel_buffer",
-    "vct_set_trace_timing",
+    "vct_set_trace_timing", "vct_set_lighting_components", "vct_get_lighting_components", "vct_set_aov_outputs",
+    "vct_download_aov", "vct_get_aov_device",
 ]
 
 
@@ -141,6 +146,11 @@ _lib.vct_get_frames_in_flight.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.
 _lib.vct_select_frame_slot.argtypes = [C.c_void_p, C.c_int32]
 _lib.vct_set_trace_timing.argtypes = [C.c_void_p, C.c_int32]
 _lib.vct_selftest_texel_buffer.argtypes = [C.c_void_p, C.c_void_p]
+_lib.vct_set_lighting_components.argtypes = [C.c_void_p, C.c_uint32]
+_lib.vct_get_lighting_components.argtypes = [C.c_void_p, C.c_void_p]
+_lib.vct_set_aov_outputs.argtypes = [C.c_void_p, C.c_uint32]
+_lib.vct_download_aov.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+_lib.vct_get_aov_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
 _lib.vct_upload_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
 
 
@@ -249,6 +259,31 @@ class Context:
 
     def set_trace_variant(self, variant):
         self._ck(_lib.vct_set_trace_variant(self._h, int(variant)), "vct_set_trace_variant")
+
+    def set_lighting_components(self, mask):
+        """SHOW_* bits of the composite (the reference's Show* switches; default SHOW_ALL): from the next trace on."""
+        self._ck(_lib.vct_set_lighting_components(self._h, int(mask)), "vct_set_lighting_components")
+
+    def lighting_components(self):
+        v = C.c_uint32()
+        self._ck(_lib.vct_get_lighting_components(self._h, C.byref(v)), "vct_get_lighting_components")
+        return v.value
+
+    def set_aov_outputs(self, which):
+        """AOV_* bits: per-component RGBA16F frames beside the frame, for every frame slot (0 frees them)."""
+        self._ck(_lib.vct_set_aov_outputs(self._h, int(which)), "vct_set_aov_outputs")
+
+    def download_aov(self, bit):
+        """One per-component output (one AOV_* bit) of the selected slot: uint16 [h, w, 4] (fp16 bits)."""
+        out = np.zeros((self.cfg.height, self.cfg.width, 4), np.uint16)
+        self._ck(_lib.vct_download_aov(self._h, int(bit), _ptr(out)), "vct_download_aov")
+        return out
+
+    def aov_device(self, bit):
+        """(device pointer, bytes) of one per-component output of the selected slot (zero-copy consumers)."""
+        p, n = C.c_void_p(), C.c_size_t()
+        self._ck(_lib.vct_get_aov_device(self._h, int(bit), C.byref(p), C.byref(n)), "vct_get_aov_device")
+        return p.value, n.value
 
     # --- scene / volume
     def upload_triangles(self, pos, material, albedo):

@@ -226,7 +226,7 @@ int create_overlapping_stream(vct_ctx* c, hipStream_t base, hipStream_t* out, bo
 void slot_save(const vct_ctx* c, VctFrameSlot& s) {
     s.stream = c->stream; s.ev0 = c->ev0; s.ev1 = c->ev1;
     s.gb_tiled = c->gb_tiled; s.gb_current = c->gb_current; s.frame = c->frame; s.frame_target = c->frame_target;
-    s.tile_steps = c->tile_steps;
+    s.tile_steps = c->tile_steps; s.aov = c->aov;
     s.last_row0 = c->last_row0; s.last_row1 = c->last_row1; s.last_row_stride = c->last_row_stride;
     s.have_trace = c->have_trace; s.last_trace_compacted = c->last_trace_compacted; s.last_trace_timed = c->last_trace_timed;
     s.last_was_screen_trace = c->last_was_screen_trace; s.have_gbuffer = c->have_gbuffer;
@@ -234,7 +234,7 @@ void slot_save(const vct_ctx* c, VctFrameSlot& s) {
 void slot_load(vct_ctx* c, const VctFrameSlot& s) {
     c->stream = s.stream; c->ev0 = s.ev0; c->ev1 = s.ev1;
     c->gb_tiled = s.gb_tiled; c->gb_current = s.gb_current; c->frame = s.frame; c->frame_target = s.frame_target;
-    c->tile_steps = s.tile_steps;
+    c->tile_steps = s.tile_steps; c->aov = s.aov;
     c->last_row0 = s.last_row0; c->last_row1 = s.last_row1; c->last_row_stride = s.last_row_stride;
     c->have_trace = s.have_trace; c->last_trace_compacted = s.last_trace_compacted; c->last_trace_timed = s.last_trace_timed;
     c->last_was_screen_trace = s.last_was_screen_trace; c->have_gbuffer = s.have_gbuffer;
@@ -346,6 +346,20 @@ void fill_march_params(const vct_ctx* c, VctTraceParams& p, const uint32_t* chai
 #endif
 }
 
+// frames of a per-component output set (one per VCT_AOV_* bit that is on)
+size_t aov_frames(uint32_t which) { return (size_t)__builtin_popcount(which); }
+
+// VctTraceParams::comp of a launch with lighting components: the mask, the cone groups something reads (include/vct.h),
+// the outputs, and the bit that selects the COMP kernel
+uint32_t component_word(uint32_t mask, uint32_t aov_which) {
+    const bool diffuse = (mask & (VCT_SHOW_INDIRECT_DIFFUSE | VCT_SHOW_AMBIENT_OCCLUSION)) || (aov_which & VCT_AOV_INDIRECT_DIFFUSE);
+    const bool specular = (mask & VCT_SHOW_INDIRECT_SPECULAR) ||
+                          ((mask & VCT_SHOW_AMBIENT_OCCLUSION) && (mask & VCT_SHOW_SPECULAR)) ||
+                          (aov_which & VCT_AOV_INDIRECT_SPECULAR);
+    const uint32_t groups = (diffuse ? 1u : 0u) | (specular ? 2u : 0u);
+    return VCT_COMP_ON | (aov_which << VCT_COMP_AOV_SHIFT) | (groups << VCT_COMP_GROUPS_SHIFT) | (mask & VCT_SHOW_ALL);
+}
+
 // `out_base`: where the kernel writes (full-frame addressing); null = the caller's vct_set_frame_target or the
 // context-owned frame.  vct_frame_step passes its gather buffer here instead of re-pointing c->frame_target, which
 // on a non-root rank would leave a pointer BEFORE a one-slab allocation behind for every later full-frame call.
@@ -383,6 +397,15 @@ int launch_trace(vct_ctx* c, int row0, int row1, uint16_t* out_base = nullptr, i
     p.out = out_base ? out_base : (c->frame_target ? c->frame_target : c->frame);
     p.dbg_steps = c->cfg.debug_outputs ? c->dbg_steps : nullptr;
     p.dbg_cones = c->cfg.debug_outputs ? c->dbg_cones : nullptr;
+    // lighting components (include/vct.h): the COMP kernel only when the mask or an output asks for it.  A packed slab
+    // (interleaved ranks, whose contexts refuse outputs; the one-GPU self-test) writes no outputs.
+    const uint32_t aov_which = pack_rows ? 0u : c->aov_which;
+    if (c->show_mask != VCT_SHOW_ALL || aov_which) {
+        if (variant != 0)
+            return fail(c, VCT_ERR_INVALID, "lighting components / per-component outputs need the default trace kernel (config.trace_variant 0)");
+        p.comp = component_word(c->show_mask, aov_which);
+        p.aov = aov_which ? c->aov : nullptr;
+    }
 #if defined(VCT_STATS) && VCT_STATS
     HIP_TRY(c, hipMemsetAsync(c->stats, 0, 16 * sizeof(unsigned long long), c->stream));
 #endif
@@ -831,12 +854,13 @@ void vct_destroy(vct_ctx* c) {
     if (c->frames_in_flight > 1) {            // the slot that is not selected: its set is not in the context fields freed below
         VctFrameSlot& o = c->slots[1 - c->cur_slot];
         if (o.stream) (void)hipStreamSynchronize(o.stream);
-        void* ob[] = {o.gb_tiled, o.frame, o.tile_steps};
+        void* ob[] = {o.gb_tiled, o.frame, o.tile_steps, o.aov};
         for (void* b : ob) if (b) (void)hipFree(b);
         if (o.ev0) (void)hipEventDestroy(o.ev0);
         if (o.ev1) (void)hipEventDestroy(o.ev1);
         if (o.stream) (void)hipStreamDestroy(o.stream);
     }
+    if (c->aov) (void)hipFree(c->aov);
     if (c->ev_xslot) (void)hipEventDestroy(c->ev_xslot);
     void* bufs[] = {c->chain, c->cells, c->shadow_tiles, c->staging, c->gb_linear, c->gb_tiled, c->frame, c->dbg_steps,
                     c->dbg_cones, c->step_counter, c->tile_steps, c->stats, c->vt_pix, c->steps_dev, c->spread_lut, c->tri_pos,
@@ -904,6 +928,8 @@ int vct_set_trace_variant(vct_ctx* c, int32_t variant) {
     if (variant < 0 || variant > 4) return fail(c, VCT_ERR_INVALID, "vct_set_trace_variant: 0 .. 4");
     if (variant == 4 && c->frames_in_flight > 1)
         return fail(c, VCT_ERR_INVALID, "vct_set_trace_variant: variant 4 keeps per-context scratch (vct_set_frames_in_flight(ctx, 1) first)");
+    if (variant != 0 && (c->show_mask != VCT_SHOW_ALL || c->aov_which))
+        return fail(c, VCT_ERR_INVALID, "vct_set_trace_variant: variants 1 .. 4 have no lighting components (mask VCT_SHOW_ALL, no outputs first)");
     c->cfg.trace_variant = variant;
     return VCT_OK;
 }
@@ -1917,7 +1943,7 @@ int vct_set_frames_in_flight(vct_ctx* c, int32_t n) {
         // back to one frame: slot 0's set into the context, slot 1's released
         if (c->cur_slot != 0) { slot_save(c, c->slots[1]); slot_load(c, c->slots[0]); c->cur_slot = 0; }
         VctFrameSlot& o = c->slots[1];
-        void* ob[] = {o.gb_tiled, o.frame, o.tile_steps};
+        void* ob[] = {o.gb_tiled, o.frame, o.tile_steps, o.aov};
         for (void* b : ob) if (b) (void)hipFree(b);
         if (o.ev0) (void)hipEventDestroy(o.ev0);
         if (o.ev1) (void)hipEventDestroy(o.ev1);
@@ -1949,10 +1975,13 @@ int vct_set_frames_in_flight(vct_ctx* c, int32_t n) {
     if (e == hipSuccess) e = hipMemsetAsync(o.gb_tiled, 0, gb_tiled_floats(c) * sizeof(float), o.stream);
     if (e == hipSuccess) e = hipMemsetAsync(o.frame, 0, npix * 8, o.stream);
     if (e == hipSuccess) e = hipMemsetAsync(o.tile_steps, 0, nt * sizeof(uint32_t), o.stream);
+    const size_t aov_bytes = aov_frames(c->aov_which) * npix * 8;      // the slot's own per-component outputs
+    if (e == hipSuccess && aov_bytes) e = hipMalloc(&o.aov, aov_bytes);
+    if (e == hipSuccess && aov_bytes) e = hipMemsetAsync(o.aov, 0, aov_bytes, o.stream);
     if (e == hipSuccess && !c->ev_xslot) e = hipEventCreateWithFlags(&c->ev_xslot, hipEventDisableTiming);
     if (e == hipSuccess) e = hipStreamSynchronize(o.stream);
     if (e != hipSuccess) {
-        void* ob[] = {o.gb_tiled, o.frame, o.tile_steps};
+        void* ob[] = {o.gb_tiled, o.frame, o.tile_steps, o.aov};
         for (void* b : ob) if (b) (void)hipFree(b);
         if (o.ev0) (void)hipEventDestroy(o.ev0);
         if (o.ev1) (void)hipEventDestroy(o.ev1);
@@ -2197,6 +2226,81 @@ int vct_selftest_area_divide(vct_ctx* c, uint64_t seed, uint64_t count, uint64_t
 int vct_get_stream(vct_ctx* c, void** s) {
     if (!c || !s) return VCT_ERR_INVALID;
     *s = (void*)c->stream;
+    return VCT_OK;
+}
+
+// ---- lighting components (include/vct.h) -------------------------------------------------------------------------------
+int vct_set_lighting_components(vct_ctx* c, uint32_t mask) {
+    if (!c) return VCT_ERR_INVALID;
+    if (mask & ~(uint32_t)VCT_SHOW_ALL) return fail(c, VCT_ERR_INVALID, "vct_set_lighting_components: bits above VCT_SHOW_ALL");
+    if (mask != VCT_SHOW_ALL && c->cfg.trace_variant != 0)
+        return fail(c, VCT_ERR_INVALID, "vct_set_lighting_components: config.trace_variant 1 .. 4 has no lighting components");
+    c->show_mask = mask;
+    return VCT_OK;
+}
+
+int vct_get_lighting_components(const vct_ctx* c, uint32_t* mask) {
+    if (!c || !mask) return VCT_ERR_INVALID;
+    *mask = c->show_mask;
+    return VCT_OK;
+}
+
+int vct_set_aov_outputs(vct_ctx* c, uint32_t which) {
+    if (!c) return VCT_ERR_INVALID;
+    if (which & ~(uint32_t)(VCT_AOV_INDIRECT_DIFFUSE | VCT_AOV_INDIRECT_SPECULAR | VCT_AOV_DIRECT))
+        return fail(c, VCT_ERR_INVALID, "vct_set_aov_outputs: unknown output bits");
+    if (which && c->cfg.trace_variant != 0)
+        return fail(c, VCT_ERR_INVALID, "vct_set_aov_outputs: config.trace_variant 1 .. 4 has no per-component outputs");
+    if (which && c->comm)
+        return fail(c, VCT_ERR_INVALID, "vct_set_aov_outputs: a rank of a multi-GPU frame (per-component outputs are not gathered)");
+    if (which == c->aov_which) return VCT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    PIPE_TRY(vct_synchronize(c));            // the buffers being replaced may still be written
+    // every slot's set, allocated here and never in a launch; the selected slot's set lives in the context fields
+    const size_t bytes = aov_frames(which) * (size_t)c->cfg.width * c->cfg.height * 8;
+    uint16_t** sets[2] = {&c->aov, c->frames_in_flight > 1 ? &c->slots[1 - c->cur_slot].aov : nullptr};
+    uint16_t* fresh[2] = {nullptr, nullptr};
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 2 && e == hipSuccess; ++k) {
+        if (!sets[k] || !bytes) continue;
+        e = hipMalloc(&fresh[k], bytes);
+        if (e == hipSuccess) e = hipMemset(fresh[k], 0, bytes);
+    }
+    if (e != hipSuccess) {          // all or nothing: the old set stays
+        for (uint16_t* b : fresh) if (b) (void)hipFree(b);
+        return fail(c, e == hipErrorOutOfMemory ? VCT_ERR_NOMEM : VCT_ERR_DEVICE, std::string("vct_set_aov_outputs: ") + hipGetErrorString(e));
+    }
+    for (int k = 0; k < 2; ++k) {
+        if (!sets[k]) continue;
+        if (*sets[k]) (void)hipFree(*sets[k]);
+        *sets[k] = fresh[k];
+    }
+    c->aov_which = which;
+    return VCT_OK;
+}
+
+// the output `bit` of the selected slot: device address (null when the bit is not exactly one output that is on)
+static uint16_t* aov_of(const vct_ctx* c, uint32_t bit) {
+    if (bit == 0 || (bit & (bit - 1)) || !(c->aov_which & bit) || !c->aov) return nullptr;
+    return c->aov + aov_frames(c->aov_which & (bit - 1)) * (size_t)c->cfg.width * c->cfg.height * 4;
+}
+
+int vct_download_aov(vct_ctx* c, uint32_t bit, void* out) {
+    if (!c || !out) return VCT_ERR_INVALID;
+    const uint16_t* src = aov_of(c, bit);
+    if (!src) return fail(c, VCT_ERR_INVALID, "vct_download_aov: not one output that vct_set_aov_outputs turned on");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(out, src, (size_t)c->cfg.width * c->cfg.height * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return VCT_OK;
+}
+
+int vct_get_aov_device(vct_ctx* c, uint32_t bit, void** p, size_t* bytes) {
+    if (!c || !p) return VCT_ERR_INVALID;
+    uint16_t* src = aov_of(c, bit);
+    if (!src) return fail(c, VCT_ERR_INVALID, "vct_get_aov_device: not one output that vct_set_aov_outputs turned on");
+    *p = src;
+    if (bytes) *bytes = (size_t)c->cfg.width * c->cfg.height * 8;
     return VCT_OK;
 }
 

@@ -34,6 +34,7 @@ struct VctFrameSlot {
     uint16_t* frame = nullptr;
     uint16_t* frame_target = nullptr;
     uint32_t* tile_steps = nullptr;
+    uint16_t* aov = nullptr;            // per-component outputs of the slot (vct_set_aov_outputs): the frames that are on, in bit order
     int last_row0 = 0, last_row1 = 0, last_row_stride = 1;
     bool have_trace = false, last_trace_compacted = false, last_was_screen_trace = false, have_gbuffer = false;
     bool last_trace_timed = false;      // the slot's last march launch was bracketed by its timing events
@@ -67,6 +68,11 @@ struct vct_ctx {
     const float* gb_current = nullptr;   // tiled buffer the next resident trace reads
     uint16_t* frame = nullptr;        // RGBA16F [h][w][4]
     uint16_t* frame_target = nullptr; // caller-owned output (vct_set_frame_target) or null
+    // lighting components (vct_set_lighting_components): VCT_SHOW_* mask of the composite; per-component outputs
+    // (vct_set_aov_outputs): VCT_AOV_* bits, the selected slot's buffer (popcount(aov_which) frames, bit order)
+    uint32_t show_mask = VCT_SHOW_ALL;
+    uint32_t aov_which = 0;
+    uint16_t* aov = nullptr;
     uint8_t* dbg_steps = nullptr;
     float* dbg_cones = nullptr;
     unsigned long long* step_counter = nullptr;   // [VCT_STEP_COUNTERS] atomic bank of the bounce kernels (memset before each bounce)

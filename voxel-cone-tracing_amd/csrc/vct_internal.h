@@ -245,6 +245,9 @@ struct VctStep {       // 64 B: one s_load_dwordx16 per march step
     VctLevelRef l1, l2;
 };
 
+#define VCT_COMP_GROUPS_SHIFT 8
+#define VCT_COMP_AOV_SHIFT 16
+#define VCT_COMP_ON 0x80000000u
 struct VctTraceParams {
     const uint32_t* chain;              // Morton chain, RGBA8 packed
     uint32_t level_off[VCT_MAX_LEVELS]; // texel offsets
@@ -286,8 +289,17 @@ struct VctTraceParams {
     const uint32_t* brick_slot;
     const uint32_t* brick_prev;
     const uint32_t* bounce_seen;        // bricks the bounce chain showed when its mips were last built
-    uint32_t* bounce_out;
+    // bounce_out is written by the bounce kernels only, aov read by the screen trace only: they share the slot, so the
+    // screen trace's parameter block keeps its size (and the default kernels their code) with the lighting components
+    union {
+        uint32_t* bounce_out;
+        uint16_t* aov;                  // per-component outputs (below): the frames that are on, back to back in bit order
+    };
     uint32_t nbricks;
+    // Lighting components (vct_set_lighting_components / vct_set_aov_outputs; k_trace_tile_split<.., COMP = true>, launched
+    // when comp != 0): bits 0-4 the VCT_SHOW_* mask, bits 8-9 the cone groups marched (1: cones 0-5, 2: cone 6), bits
+    // 16-18 the VCT_AOV_* outputs written to `aov`, bit 31 set.  (It fills the padding in front of slot_brick.)
+    uint32_t comp;
     const uint32_t* slot_brick;         // [nslots] the bricks a fragment of the mesh can land in (the voxelizer's slots)
     uint32_t nslots;
     // anisotropic option: six directional chains (levels >= 1), Morton per level, each

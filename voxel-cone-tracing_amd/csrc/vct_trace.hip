@@ -43,6 +43,7 @@
 // (vct_capi.hip: divisor_verified).
 #include <hip/hip_fp16.h>
 
+#include "../../include/vct.h"
 #include "vct_internal.h"
 
 typedef int vct_v4i32 __attribute__((ext_vector_type(4)));
@@ -1299,7 +1300,10 @@ static_assert(VCT_SPLIT == 3 || VCT_SPLIT == 4 || VCT_SPLIT == 7, "VCT_SPLIT mus
 // spilling under the 80 of the default kernel)
 // CELLS: the per-lane sampler reads footprint records (p.cells_biased != null; vct_set_footprint_records) -- an
 // instantiation of its own, because the same code behind a run-time test cost the default kernel 2 % (0.608 -> 0.620 ms)
-template <bool WRAP, int FASTDIV, bool ANISO, bool COMPACT = false, bool CELLS = false, bool PRIO = false>
+// COMP: lighting components (p.comp; vct_set_lighting_components, vct_set_aov_outputs) -- a wave whose cone group
+// nothing reads marches nothing, the composite applies the VCT_SHOW_* mask, and the per-component outputs are stored
+// beside the frame.  An instantiation of its own for the same reason as CELLS: the default kernels carry none of it.
+template <bool WRAP, int FASTDIV, bool ANISO, bool COMPACT = false, bool CELLS = false, bool PRIO = false, bool COMP = false>
 __global__ void __launch_bounds__(64 * VCT_SPLIT, ANISO ? VCT_ANISO_MIN_WAVES : VCT_TRACE_MIN_WAVES)
 k_trace_tile_split(const VctTraceParams p) {
     __shared__ float4 lds_blk[VCT_SPLIT][ANISO ? 4 : 2][64];   // per wave: level-1 slab, level-2 slab (+ their "-axis" slabs)
@@ -1367,6 +1371,11 @@ k_trace_tile_split(const VctTraceParams p) {
     const bool in_frame = cvalid && (x < p.width) && (y < p.height);
     const bool alive = in_frame && !(VCT_GB(18) < 0.5f);            // trace.fs:171 discard
     int total = 0;
+    // COMP: a cone group nothing reads (march_groups bit 0: cones 0-5, bit 1: cone 6) is marched over 0 steps -- zero
+    // cones into LDS and the debug outputs, 0 steps, and the wave arrives at once.  The count is wave-uniform (the
+    // parameter word through readfirstlane), so the march loop is not entered on a scalar branch.
+    const uint32_t groups = COMP ? (uint32_t)__builtin_amdgcn_readfirstlane((int)p.comp) >> VCT_COMP_GROUPS_SHIFT : 3u;
+    const int n_diffuse = (groups & 1u) ? p.n_diffuse : 0, n_specular = (groups & 2u) ? p.n_specular : 0;
     if (wave < VCT_SPLIT - 1) {
         F3 start, k0, k1, k2;
         {
@@ -1391,7 +1400,7 @@ k_trace_tile_split(const VctTraceParams p) {
                                         k0.z * ddx + k1.z * ddy + k2.z * ddz));
             }
             ConeAcc acc3[3];
-            cone_march3<WRAP, FASTDIV, true>(p, alive, start, dirs, p.steps_diffuse, p.n_diffuse, blk, lb, acc3, ms);
+            cone_march3<WRAP, FASTDIV, true>(p, alive, start, dirs, p.steps_diffuse, n_diffuse, blk, lb, acc3, ms);
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
                 const int i = wave * 3 + j;
@@ -1413,7 +1422,7 @@ k_trace_tile_split(const VctTraceParams p) {
             dir = normalize3(dir);
             int st;
             const F4 c = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO>(p, alive, start, dir, p.steps_diffuse,
-                                                                p.n_diffuse, blk, lb, st, ms);
+                                                                n_diffuse, blk, lb, st, ms);
             total += st;
             lds_cone[i][lane] = make_float4(c.x, c.y, c.z, c.w);
             if (p.dbg_cones && alive) {
@@ -1437,7 +1446,7 @@ k_trace_tile_split(const VctTraceParams p) {
         const F3 Rd = normalize3(reflect3(f3(E.x * -1.0f, E.y * -1.0f, E.z * -1.0f), N));  // :217
         int st6;
         const F4 sc = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO>(p, alive, start, Rd, p.steps_specular,
-                                                             p.n_specular, blk, lb, st6, ms);
+                                                             n_specular, blk, lb, st6, ms);
         total += st6;
         lds_cone[6][lane] = make_float4(sc.x, sc.y, sc.z, sc.w);
         if (p.dbg_cones && alive) {
@@ -1483,18 +1492,29 @@ k_trace_tile_split(const VctTraceParams p) {
         const F3 L = normalize3(f3(p.light[0], p.light[1], p.light[2]));        // :179
         const F3 E = normalize3(f3(p.cam[0] - P.x, p.cam[1] - P.y, p.cam[2] - P.z));   // :181
         const float cos_theta = fmaxf(dot3(N, L), 0.0f);                        // :188
-        const float direct_diffuse = shadow * cos_theta;                        // :192
-        const float occlusion = 1.0f - ind[3];                                  // :201
-        const float dr = (direct_diffuse + occlusion * ind[0]) * alb_r;         // :205
-        const float dg = (direct_diffuse + occlusion * ind[1]) * alb_g;
-        const float db = (direct_diffuse + occlusion * ind[2]) * alb_b;
+        // COMP: the Show* ternaries (include/vct.h) as selects on the wave-uniform mask; VCT_SHOW_ALL selects every
+        // unmasked value, so the operations and their order are the default kernel's
+        const uint32_t comp = COMP ? (uint32_t)__builtin_amdgcn_readfirstlane((int)p.comp) : 0u;
+        const uint32_t show = COMP ? comp & (uint32_t)VCT_SHOW_ALL : (uint32_t)VCT_SHOW_ALL;
+        const bool s_dd = !COMP || (show & VCT_SHOW_DIFFUSE), s_ao = !COMP || (show & VCT_SHOW_AMBIENT_OCCLUSION);
+        const bool s_ird = !COMP || (show & VCT_SHOW_INDIRECT_DIFFUSE), s_ds = !COMP || (show & VCT_SHOW_SPECULAR);
+        const bool s_irs = !COMP || (show & VCT_SHOW_INDIRECT_SPECULAR);
+        const float raw_dd = shadow * cos_theta;
+        const float direct_diffuse = s_dd ? raw_dd : 0.0f;                      // :192 (:190)
+        const float occlusion = s_ao ? 1.0f - ind[3] : 1.0f;                    // :201
+        const float ird_r = s_ird ? ind[0] : 0.0f, ird_g = s_ird ? ind[1] : 0.0f, ird_b = s_ird ? ind[2] : 0.0f;   // :203
+        const float dr = (direct_diffuse + occlusion * ird_r) * alb_r;          // :205
+        const float dg = (direct_diffuse + occlusion * ird_g) * alb_g;
+        const float db = (direct_diffuse + occlusion * ird_b) * alb_b;
         const F3 R = normalize3(reflect3(f3(L.x * -1.0f, L.y * -1.0f, L.z * -1.0f), N));   // :212
         const float spec = powf(fmaxf(dot3(E, R), 0.0f), p.shininess);          // :213
-        const float direct_spec = spec * shadow;                                // :214
-        const float spec_occ = 1.0f - sc.w;                                     // :221
-        const float sr = (sc.x + spec_occ * direct_spec) * VCT_GB(19);          // :223
-        const float sg = (sc.y + spec_occ * direct_spec) * VCT_GB(20);
-        const float sb = (sc.z + spec_occ * direct_spec) * VCT_GB(21);
+        const float raw_ds = spec * shadow;
+        const float direct_spec = s_ds ? raw_ds : 0.0f;                         // :214 (:215)
+        const float spec_occ = s_ao ? 1.0f - sc.w : 1.0f;                       // :221
+        const float irs_r = s_irs ? sc.x : 0.0f, irs_g = s_irs ? sc.y : 0.0f, irs_b = s_irs ? sc.z : 0.0f;
+        const float sr = (irs_r + spec_occ * direct_spec) * VCT_GB(19);         // :223
+        const float sg = (irs_g + spec_occ * direct_spec) * VCT_GB(20);
+        const float sb = (irs_b + spec_occ * direct_spec) * VCT_GB(21);
         const float ar = p.ambient * alb_r * occlusion;                         // :225
         const float ag = p.ambient * alb_g * occlusion;
         const float ab = p.ambient * alb_b * occlusion;
@@ -1507,6 +1527,29 @@ k_trace_tile_split(const VctTraceParams p) {
         pk.x = pack_half2(o0, o1);
         pk.y = pack_half2(o2, o3);
         *reinterpret_cast<uint2*>(p.out + pixel_index(fresh_lane()) * 4) = pk;
+        if (COMP) {     // raw per-component values, one 8-byte store per output; discarded pixels get zeros
+            const uint32_t which = comp >> VCT_COMP_AOV_SHIFT;
+            const size_t frame_halves = (size_t)p.width * p.height * 4;
+            uint16_t* dst = p.aov + pixel_index(fresh_lane()) * 4;        // the outputs that are on, in bit order
+            uint2 q;
+            if (which & VCT_AOV_INDIRECT_DIFFUSE) {
+                q.x = alive ? pack_half2(ind[0], ind[1]) : 0u;
+                q.y = alive ? pack_half2(ind[2], ind[3]) : 0u;
+                *reinterpret_cast<uint2*>(dst) = q;
+                dst += frame_halves;
+            }
+            if (which & VCT_AOV_INDIRECT_SPECULAR) {
+                q.x = alive ? pack_half2(sc.x, sc.y) : 0u;
+                q.y = alive ? pack_half2(sc.z, sc.w) : 0u;
+                *reinterpret_cast<uint2*>(dst) = q;
+                dst += frame_halves;
+            }
+            if (which & VCT_AOV_DIRECT) {
+                q.x = alive ? pack_half2(raw_dd, raw_ds) : 0u;
+                q.y = alive ? pack_half2(shadow, 1.0f) : 0u;
+                *reinterpret_cast<uint2*>(dst) = q;
+            }
+        }
     }
 #undef VCT_GB
 }
@@ -1794,6 +1837,18 @@ hipError_t launch(const VctTraceParams& p, int blocks, hipStream_t s) {
     return hipGetLastError();
 }
 
+// the default kernel's dispatch: anisotropic chains, footprint records, whole-frame issue priority, or plain
+template <bool WRAP, int FASTDIV, bool COMP>
+void launch_split(const VctTraceParams& p, int blocks, hipStream_t s) {
+    if (p.aniso)
+        hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, true, false, false, false, COMP>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
+    else if (VCT_CELLS && WRAP && p.cells_biased)
+        hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, true, false, COMP>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
+    else if (VCT_LOAD_PRIO && !p.spec_prio)     // a whole frame (or most of one): issue priority around the samples' loads (sample_level)
+        hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, true, COMP>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
+    else hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, false, COMP>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
+}
+
 template <bool WRAP, int FASTDIV>
 hipError_t launch_v(const VctTraceParams& p, int variant, int ntiles, hipStream_t s) {
     if (!p.aniso && (variant == 1 || variant == 2)) {      // the anisotropic option exists in the default kernel only
@@ -1819,12 +1874,10 @@ hipError_t launch_v(const VctTraceParams& p, int variant, int ntiles, hipStream_
         hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, true>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
         return hipGetLastError();
     }
-    if (p.aniso) hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, true>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
-    else if (VCT_CELLS && WRAP && p.cells_biased)
-        hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, true>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
-    else if (VCT_LOAD_PRIO && !p.spec_prio)     // a whole frame (or most of one): issue priority around the samples' loads (sample_level)
-        hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, true>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
-    else hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
+    // lighting components (a mask other than VCT_SHOW_ALL, or per-component outputs): the COMP instantiation of the same
+    // branch; the host refuses them with variants 1 .. 4, so only the branches below need one
+    if (p.comp) launch_split<WRAP, FASTDIV, true>(p, blocks, s);
+    else launch_split<WRAP, FASTDIV, false>(p, blocks, s);
     return hipGetLastError();
 }
 

@@ -179,8 +179,10 @@ struct Voxel_Cone_Tracing {
     Model model;                                                             // VCT.h:48
     std::string model_path = "procedural:atrium";
 
+    // VCT.h:51 / S/VoxelConeTracing.fs:36-39: Render() hands them to the composite as the VCT_SHOW_* mask (include/vct.h;
+    // all true = VCT_SHOW_ALL, the unmasked frame), and cone groups nothing reads are not marched
     bool ShowDiffuse = true, ShowIndirectDiffuse = true, ShowSpecular = true,
-         ShowIndirectSpecular = true, ShowAmbientOcclusion = true;           // VCT.h:51 (never uploaded there either)
+         ShowIndirectSpecular = true, ShowAmbientOcclusion = true;
     float AmbientFactor = 0.1f;                                              // VCT.h:53
     // Multi-GPU (no reference counterpart, R/main.cpp drives one GL context): one process per GPU, each with
     // its own Voxel_Cone_Tracing; set Rank / World / Device and the 128-byte RCCL id (vct_comm_get_unique_id
@@ -286,9 +288,17 @@ struct Voxel_Cone_Tracing {
         DrawVoxelTexture();     // VCT.h:139
     }
 
+    // the five Show* switches as VCT_SHOW_* bits
+    uint32_t ShowMask() const {
+        return (ShowDiffuse ? (uint32_t)VCT_SHOW_DIFFUSE : 0u) | (ShowIndirectDiffuse ? (uint32_t)VCT_SHOW_INDIRECT_DIFFUSE : 0u) |
+               (ShowSpecular ? (uint32_t)VCT_SHOW_SPECULAR : 0u) | (ShowIndirectSpecular ? (uint32_t)VCT_SHOW_INDIRECT_SPECULAR : 0u) |
+               (ShowAmbientOcclusion ? (uint32_t)VCT_SHOW_AMBIENT_OCCLUSION : 0u);
+    }
+
     void Render() {
         if (!ctx || !model.scene) return;
         vct_set_ambient_factor(ctx, AmbientFactor);
+        if (!check(vct_set_lighting_components(ctx, ShowMask()), "vct_set_lighting_components")) return;
         const float cam[3] = {camera.position.x, camera.position.y, camera.position.z};   // VCT.h:167
         const float L[3] = {lightDirection.x, lightDirection.y, lightDirection.z};         // VCT.h:168
         vct_set_camera_position(ctx, cam);

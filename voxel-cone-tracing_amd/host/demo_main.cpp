@@ -6,7 +6,10 @@
 //
 //   vct_demo [--scene procedural:atrium|procedural:atrium-textured|procedural:bistro|procedural:cornell] [--voxels 128] [--size 1280x720]
 //            [--shadow 4096] [--frames 3] [--bounces 1|2] [--ppm out.ppm] [--gpus N] [--dynamic-light] [--frames-in-flight 1|2]
+//            [--show diffuse,indirect-diffuse,specular,indirect-specular,ao]
 //
+// --show LIST: the lighting components shown (the reference's Show* switches, VCT.h:51); the ones not listed are off.
+//   Default: all five.
 // --frames-in-flight 2: consecutive Render() calls alternate between two frame slots (Voxel_Cone_Tracing::FramesInFlight):
 //   frame k + 1 starts while frame k drains; same pixels, same checksum.
 // --dynamic-light: every Render() re-runs the whole GI pass (shadow map, voxelize, inject, mips, G-buffer, trace)
@@ -80,6 +83,7 @@ int main(int argc, char** argv) {
     const char* ppm = nullptr;
     bool dynamic_light = false;
     const char* idfile = nullptr;
+    const char* show = nullptr;
     for (int i = 1; i + 1 < argc; ++i) {
         if (!strcmp(argv[i], "--gpus")) gpus = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--rank")) rank = atoi(argv[++i]);
@@ -98,6 +102,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--bounces")) bounces = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--ppm")) ppm = argv[++i];
         else if (!strcmp(argv[i], "--frames-in-flight")) in_flight = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--show")) show = argv[++i];
     }
     GLFWwindow* window = nullptr;          // no window system on a compute node
 
@@ -117,6 +122,23 @@ int main(int argc, char** argv) {
     voxel_cone_tracing.Bounces = bounces;
     voxel_cone_tracing.DynamicLight = dynamic_light;       // every Render() = one whole GI pass (vct_gi_pass)
     voxel_cone_tracing.FramesInFlight = in_flight;
+    if (show) {                                             // --show: the listed Show* switches on, the others off
+        bool* flags[5] = {&voxel_cone_tracing.ShowDiffuse, &voxel_cone_tracing.ShowIndirectDiffuse, &voxel_cone_tracing.ShowSpecular,
+                          &voxel_cone_tracing.ShowIndirectSpecular, &voxel_cone_tracing.ShowAmbientOcclusion};
+        const char* names[5] = {"diffuse", "indirect-diffuse", "specular", "indirect-specular", "ao"};
+        for (bool* f : flags) *f = false;
+        const std::string list(show);
+        for (size_t p = 0; p <= list.size();) {
+            size_t q = list.find(',', p);
+            if (q == std::string::npos) q = list.size();
+            const std::string item = list.substr(p, q - p);
+            int k = 0;
+            while (k < 5 && item != names[k]) ++k;
+            if (k == 5 && !item.empty()) { fprintf(stderr, "--show: unknown component '%s'\n", item.c_str()); return 1; }
+            if (k < 5) *flags[k] = true;
+            p = q + 1;
+        }
+    }
     if (gpus > 0) {                                         // a rank of a multi-GPU run
         voxel_cone_tracing.Rank = rank;
         voxel_cone_tracing.World = gpus;

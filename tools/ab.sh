@@ -1,7 +1,7 @@
 #!/bin/bash
 # ON THE GPU BOX: interleaved A/B of library builds.  One script for what round 4 did with 27 one-off ones.
 #
-#   tools/build_ab.sh quad "-DVCT_QUAD_SHARE=1" base ""          # (here) variants into build/ab/<name>.so
+#   tools/build_ab.sh quad "-DVCT_SPLIT=4" base ""               # (here) variants into build/ab/<name>.so
 #   gpurun -- tools/ab.sh -t quad -l "tree quad base" -p "tests/test_gpu_parity.py tests/test_golden.py -k trace" \
 #             -r 3 -f trace_kernel_ms,value -- "--scene atrium" "--scene bistro --voxel-dim 1024 --width 3840 --height 2160"
 #

@@ -95,7 +95,7 @@ def main():
     fb = sorted((((n, c), i) for i, ((n, c), b) in enumerate(sized) if texel_loads(b) >= 6 and n >= 40), key=lambda x: x[1])
     coop = sorted((((n, c), i) for i, ((n, c), b) in enumerate(sized) if sum("ds_read_b128" in ln for ln in b) >= 8), key=lambda x: x[1])
     big = sorted(fb + coop)
-    # the march is unrolled by two (VCT_UNROLL2): two identical steps per loop body -- model the first
+    # the march is unrolled by two (cone_march): two identical steps per loop body -- model the first
     assert len(fb) in (2, 4) and len(coop) == len(fb), [x[0] for x in big]
     unrolled = len(fb) == 4
     fb, coop = fb[:2], coop[:2]

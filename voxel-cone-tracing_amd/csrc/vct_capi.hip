@@ -295,7 +295,7 @@ int refresh_steps(vct_ctx* c) {
         }
     }
     c->fast_div = ok;
-    // a table for the verified division carries what div_const<1> takes beside the reciprocal (VCT_DIV2: its low word)
+    // a table for the verified division carries what div_const<1> takes beside the reciprocal (its low word)
     // in the divisor's place; the IEEE-divide kernels of an unverified table keep the divisor
     if (ok) {
         for (VctStep& st : d) st.occ_den = vct_div_aux(st.occ_den, st.occ_rcp);
@@ -839,7 +839,7 @@ int vct_create(const vct_config* cfg, vct_ctx** out) {
         if (it->second) {
             vct_destroy(c);
             return fail(nullptr, VCT_ERR_DEVICE, "this device's typed-buffer loads do not convert UNORM8 to exactly c / 255 (" +
-                        std::to_string(it->second) + " of 4096 channel values differ): rebuild with -DVCT_HW_UNORM=0");
+                        std::to_string(it->second) + " of 4096 channel values differ)");
         }
     }
     *out = c;

@@ -207,12 +207,6 @@ __device__ __forceinline__ bool unpack_subtri(const SubTriRec& r, SubTri& s) {
 // 2^16 in magnitude: coordinates are multiples of 2^-8, pixel centres of 2^-1, so every product and partial sum is a
 // multiple of 2^-16 below 2^37 and fits a double's 53 bits.  Sub-triangles that reach further (near-clipped ones
 // projected far outside the frame) keep the general form, whose roundings the fast form could not reproduce.
-#ifndef VCT_SHADE_PREFETCH
-#define VCT_SHADE_PREFETCH 1
-#endif
-#ifndef VCT_FAST_COVER
-#define VCT_FAST_COVER 1      // 0: every sub-triangle takes the general form (A/B measurements)
-#endif
 struct FastEdges {
     double a[3], b[3], c[3], bias[3];
     double rcp;              // RN(1 / area)
@@ -242,7 +236,7 @@ __device__ __forceinline__ FastEdges slow_edges(const SubTri& s) {
     return f;
 }
 __device__ __forceinline__ void make_fast(const SubTri& s, FastEdges& f) {
-    f.ok = VCT_FAST_COVER != 0;
+    f.ok = true;
 #pragma unroll
     for (int k = 0; k < 3; ++k) f.ok = f.ok && fabs(s.sx[k]) < 65536.0 && fabs(s.sy[k]) < 65536.0;
 #pragma unroll
@@ -769,7 +763,7 @@ k_raster_mid(const RasterParams p, const int gblocks, const int wblocks) {
 //                 record) into each bin a record reaches.
 //   k_bin_raster  one workgroup per work item; wave w owns the 8x8-pixel quadrant w of the bin, LANE = PIXEL.  The
 //                 entries ARE the sort keys: opaque first, then alpha-tested front to back by a lower bound of the
-//                 sub-triangle's depth (bitonic in LDS, only when the slice has alpha-tested entries).  Records are
+//                 sub-triangle's depth (depth buckets in LDS, when the slice has alpha-tested entries or is long).  Records are
 //                 gathered into LDS 64 at a time by the whole workgroup (one round trip per chunk instead of one per
 //                 entry) and read back as broadcasts: the coverage test of 64 pixels is nine fp64 operations on
 //                 wave-uniform operands instead of a per-lane set-up.  A pixel's visibility word lives in ITS lane's
@@ -786,21 +780,12 @@ k_raster_mid(const RasterParams p, const int gblocks, const int wblocks) {
 #define VCT_BIN 16
 #define VCT_BIN_SHIFT 4
 #define VCT_BIN_SLICE 512           // entries per work item of k_bin_raster (LDS: 4 KiB of sort keys)
-#ifndef VCT_BIN_FILL_AGGREGATE
-#define VCT_BIN_FILL_AGGREGATE 1      // k_bin_fill: one returning atomic per distinct bin of a wave's 64 pairs
-#endif
-#ifndef VCT_BIN_BUCKET_ORDER
-#define VCT_BIN_BUCKET_ORDER 1        // k_bin_raster: slice entries bucketed by depth instead of sorted
-#endif
 #ifndef VCT_BIN_ORDER_MIN
 #define VCT_BIN_ORDER_MIN 16          // slices without alpha-tested entries are ordered too from this many entries on (front to back:
                                       // the hierarchical depth test rejects more; atrium 95 -> 62 us, depth-only street 300 -> 212)
 #endif
 #ifndef VCT_BIN_BUCKETS
 #define VCT_BIN_BUCKETS 32            // per class (opaque / alpha-tested); a multiple of 32
-#endif
-#ifndef VCT_BIN_COUNT_AGGREGATE
-#define VCT_BIN_COUNT_AGGREGATE 1     // k_bin_setup: the same for the counting atomics
 #endif
 #ifndef VCT_BIN_COUNT_AGG_ROUNDS
 #define VCT_BIN_COUNT_AGG_ROUNDS 8
@@ -1023,7 +1008,6 @@ k_bin_setup(const BinParams p) {
                         int bx = 0, by = 0;
                         for (int j = 0; j < nb; ++j) {
                             const uint32_t bin = (uint32_t)((by0 + by) * p.bins_x + bx0 + bx);
-#if VCT_BIN_COUNT_AGGREGATE
                             // the lanes still in this loop that count the same bin send ONE atomic (see k_bin_fill)
                             uint32_t want = ((binmask >> j) & 1u) ? bin : 0xffffffffu, add = 0u;
                             unsigned long long left = __builtin_amdgcn_ballot_w64(want != 0xffffffffu);
@@ -1038,9 +1022,6 @@ k_bin_setup(const BinParams p) {
                             }
                             if ((left >> lane) & 1ull) add = 1u;
                             if (add != 0u) atomicAdd(&p.bin_count[(size_t)bin * VCT_BIN_CSTRIDE], add);
-#else
-                            if ((binmask >> j) & 1u) atomicAdd(&p.bin_count[(size_t)bin * VCT_BIN_CSTRIDE], 1u);        // result unused: no round trip
-#endif
                             if (++bx == bw) { bx = 0; ++by; }
                         }
                     } else {
@@ -1175,17 +1156,13 @@ k_bin_fill(const BinParams p) {
         for (uint32_t k0 = 0u; k0 < total; k0 += 256u) {
             uint32_t at[4];
             uint2 ent[4];
-#if VCT_BIN_FILL_AGGREGATE
             uint32_t bin_of[4];
-#endif
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const uint32_t k = k0 + 64u * (uint32_t)u + (uint32_t)lane;
                 at[u] = p.entry_cap;
                 ent[u] = make_uint2(0u, 0u);
-#if VCT_BIN_FILL_AGGREGATE
                 bin_of[u] = 0xffffffffu;
-#endif
                 if (k < total) {
                     int lo = 0;
 #pragma unroll
@@ -1202,14 +1179,9 @@ k_bin_fill(const BinParams p) {
                     const int hw = ((int)(h.y >> 16) >> VCT_BIN_SHIFT) - hx0 + 1;
                     const int by = hy0 + (int)j / hw, bx = hx0 + (int)j % hw;
                     ent[u] = bin_entry(rec0 + (uint32_t)lo, h, bx, by, depth_only);
-#if VCT_BIN_FILL_AGGREGATE
                     bin_of[u] = (uint32_t)(by * p.bins_x + bx);
-#else
-                    at[u] = atomicAdd(&p.bin_cursor[(size_t)(by * p.bins_x + bx) * VCT_BIN_CSTRIDE], 1u);
-#endif
                 }
             }
-#if VCT_BIN_FILL_AGGREGATE
             // One returning atomic per DISTINCT bin of the wave's 64 pairs instead of one per pair (neighbouring triangles
             // land in the same bins; atomics on one address execute one after the other in the L2): the lanes of a bin
             // elect a leader and take consecutive slots behind what it reserved.  The leaders' atomics of the four rounds
@@ -1249,7 +1221,6 @@ k_bin_fill(const BinParams p) {
                 const uint32_t base = (uint32_t)__shfl((int)got[u], leader[u]);
                 if (bin_of[u] != 0xffffffffu) at[u] = base + rank[u];
             }
-#endif
 #pragma unroll
             for (int u = 0; u < 4; ++u) p.entries[at[u] < p.entry_cap ? at[u] : p.entry_cap] = ent[u];
         }
@@ -1373,15 +1344,11 @@ k_bin_raster(const BinParams p) {
     const int lx = (lane & 1) | ((lane >> 1) & 6), ly = ((lane >> 1) & 1) | ((lane >> 3) & 6);
     const uint4* rec16 = reinterpret_cast<const uint4*>(p.recs);
     for (uint32_t item = blockIdx.x; item < nitems; item += gridDim.x) {
-#if defined(VCT_BIN_REVERSE) && VCT_BIN_REVERSE
-        const uint4 it = p.items[nitems - 1u - item];       // order-sensitivity probe (profiles/experiments/README.md)
-#else
         const uint4 it = p.items[item];
-#endif
         const int bin = (int)it.x, n = (int)it.z;
         const uint32_t first = it.y;
         const int by = bin / p.bins_x, bx = bin - by * p.bins_x;
-        // ---- the slice's entries ARE the sort keys; sorted when the slice holds alpha-tested ones ----
+        // ---- the slice's entries ARE the sort keys; ordered when the slice holds alpha-tested ones ----
         int m = 1;
         while (m < n) m <<= 1;
         bool alpha_here = false;
@@ -1397,7 +1364,6 @@ k_bin_raster(const BinParams p) {
         mail[lane] = ~0ull;
         const bool any_alpha = __syncthreads_or(alpha_here ? 1 : 0) != 0;
         if ((any_alpha || n >= VCT_BIN_ORDER_MIN) && n > 1) {     // opaque first, then alpha-tested front to back
-#if VCT_BIN_BUCKET_ORDER
             // The order only has to be GOOD (what comes first hides what comes later; any order gives the same words):
             // instead of a bitonic network (28 barrier rounds for 128 keys, 45 for 512: a tenth of this kernel's time) the
             // keys are dealt into VCT_BIN_BUCKETS + VCT_BIN_BUCKETS buckets of their class' depth range -- five barriers.
@@ -1448,22 +1414,6 @@ k_bin_raster(const BinParams p) {
             __syncthreads();
             for (int i = (int)threadIdx.x; i < n; i += 256) s_kv[i] = tmp[i];
             // (the chunk loop starts with a barrier)
-#else
-#if defined(VCT_PROBE_SORT_TWICE)
-            for (int rep = 0; rep < 2; ++rep)       // timing probe: what the sort costs (sorted input, same network)
-#endif
-            for (int k = 2; k <= m; k <<= 1)
-                for (int j = k >> 1; j > 0; j >>= 1) {
-                    for (int i = (int)threadIdx.x; i < m; i += 256) {
-                        const int l = i ^ j;
-                        if (l > i) {
-                            const unsigned long long a = s_kv[i], b = s_kv[l];
-                            if ((a > b) == ((i & k) == 0)) { s_kv[i] = b; s_kv[l] = a; }
-                        }
-                    }
-                    __syncthreads();
-                }
-#endif
         }
         const int qx0 = (bx << VCT_BIN_SHIFT) + (wave & 1) * 8, qy0 = (by << VCT_BIN_SHIFT) + (wave >> 1) * 8;
         const int px = qx0 + lx, py = qy0 + ly;
@@ -1684,7 +1634,6 @@ k_gbuffer_shade(const ShadeParams p) {
         const int t = id >> 1, f = (id & 1) + 1;
         RVert in[3];
         load_clip_tri(p.r, t, in);
-#if VCT_SHADE_PREFETCH
         // Everything that depends on the triangle index only is requested NOW, ahead of the fp64 set-up: the four
         // per-vertex records (the position once more: the clip-space copy above is consumed by the set-up) and the
         // material index.  The kernel is a chain of dependent round trips (visibility word -> records -> material ->
@@ -1713,7 +1662,6 @@ k_gbuffer_shade(const ShadeParams p) {
 #pragma unroll
             for (int k = 0; k < 6; ++k) uv_early[k] = p.r.tex.uv[(size_t)t * 6 + k];
         }
-#endif
         const bool whole = unclipped(in);
         FanTri fan;
         SubTri s;
@@ -1739,12 +1687,7 @@ k_gbuffer_shade(const ShadeParams p) {
         // put the record into scratch).
 #pragma unroll
         for (int arr = 0; arr < 4; ++arr) {
-#if VCT_SHADE_PREFETCH
             const VctTri9 rec = recs4[arr];
-#else
-            const float* src = arr == 0 ? p.r.pos : (arr == 1 ? p.nrm : (arr == 2 ? p.tan : p.bit));
-            const VctTri9 rec = *reinterpret_cast<const VctTri9*>(src + (size_t)t * 9);
-#endif
 #pragma unroll
             for (int comp = 0; comp < 3; ++comp) {
                 const float a0 = rec.v[comp] * p.r.model_scale, a1 = rec.v[3 + comp] * p.r.model_scale,
@@ -1763,13 +1706,7 @@ k_gbuffer_shade(const ShadeParams p) {
                 g[3 * arr + comp] = (q0 * var[0] + q1 * var[1] + q2 * var[2]) * qs;
             }
         }
-#if VCT_SHADE_PREFETCH
         const int td = tex_early[0], tsp = tex_early[1], th = tex_early[2];
-#else
-        const int m = p.material[t];
-        const int td = TEX ? vct_tex_of(p.r.tex, m, 0) : -1, tsp = TEX ? vct_tex_of(p.r.tex, m, 1) : -1,
-                  th = TEX ? vct_tex_of(p.r.tex, m, 2) : -1;
-#endif
         float tcu = 0.0f, tcv = 0.0f;                                             // tex (trace.vs:36)
         float dq[4] = {0.0f, 0.0f, 0.0f, 0.0f};                                   // its quad differences (mip-mapped textures)
         if (TEX && (td >= 0 || tsp >= 0 || th >= 0)) {
@@ -1777,11 +1714,7 @@ k_gbuffer_shade(const ShadeParams p) {
             float vu[3], vv[3];
             if (whole) {
 #pragma unroll
-#if VCT_SHADE_PREFETCH
                 for (int k = 0; k < 3; ++k) { vu[k] = uv_early[2 * k]; vv[k] = uv_early[2 * k + 1]; }
-#else
-                for (int k = 0; k < 3; ++k) { vu[k] = uv[2 * k]; vv[k] = uv[2 * k + 1]; }
-#endif
             } else {
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
@@ -1846,22 +1779,14 @@ k_gbuffer_shade(const ShadeParams p) {
         g[12] = len > 0.0f ? ux * il : 0.0f;
         g[13] = len > 0.0f ? uy * il : 0.0f;
         g[14] = len > 0.0f ? uz * il : 0.0f;
-#if VCT_SHADE_PREFETCH
         const float* alb = alb_early;
-#else
-        const float* alb = p.albedo + 4 * (size_t)m;
-#endif
         if (TEX && td >= 0) {
             const float4 c = fetch(td, tcu, tcv);                                 // trace.fs:167
             g[15] = c.x; g[16] = c.y; g[17] = c.z; g[18] = c.w;
         } else {
             g[15] = alb[0]; g[16] = alb[1]; g[17] = alb[2]; g[18] = alb[3];
         }
-#if VCT_SHADE_PREFETCH
         float sp[3] = {sp_early[0], sp_early[1], sp_early[2]};
-#else
-        float sp[3] = {p.specular[3 * (size_t)m], p.specular[3 * (size_t)m + 1], p.specular[3 * (size_t)m + 2]};
-#endif
         if (TEX && tsp >= 0) {
             const float4 c = fetch(tsp, tcu, tcv);                                // trace.fs:209
             sp[0] = c.x; sp[1] = c.y; sp[2] = c.z;

@@ -38,7 +38,7 @@
 //   plain gather (phases of 2 + 2 + 4), the dilated coordinates from the anchor path's table, the +1
 //   neighbours derived by dilated increments.
 //
-// Both produce the same bits.  Divisions by wave-uniform constants use one FMA correction round
+// Both produce the same bits.  Divisions by wave-uniform constants use a two-term reciprocal product
 // instead of the 10-instruction IEEE sequence, for divisors the device has verified exhaustively
 // (vct_capi.hip: divisor_verified).
 #include <hip/hip_fp16.h>
@@ -76,7 +76,7 @@ __device__ __forceinline__ F3 reflect3(F3 I, F3 N) {
 
 // x / d for a wave-uniform divisor d: the IEEE division costs v_div_scale x2, v_rcp, 4 fma, v_div_fmas, v_div_fixup.
 // Rounds 1-3: q = x*r; e = fma(-d, q, x); q = fma(e, r, q) with r = RN(1/d) -- three instructions, one correction
-// round.  Round 4 (VCT_DIV2): t = x * r_lo; q = fma(x, r_hi, t) with r_hi = RN(1/d), r_lo = RN(1/d - r_hi) -- TWO
+// round.  Since round 4: t = x * r_lo; q = fma(x, r_hi, t) with r_hi = RN(1/d), r_lo = RN(1/d - r_hi) -- TWO
 // instructions: r_hi + r_lo is 1/d to ~48 bits, the fma adds the two products exactly and rounds once, so q is the
 // correctly rounded quotient unless x/d lies within ~2^-47 of a rounding boundary.  Neither form is correctly rounded
 // for every divisor, so both are used only for divisors the DEVICE has verified: before a step table is used,
@@ -95,23 +95,17 @@ __device__ __forceinline__ F3 reflect3(F3 I, F3 N) {
 //     non-zero trilinear weight is >= 2^-75, a non-zero texel >= 1/255, the level blend factors are
 //     0 or >= 2^-10 and oma >= 2^-5 (both checked on the host: vct_capi.hip refresh_steps).
 #define VCT_DIV_TINY 0x1p-100f
-// MODE 0: the IEEE division, 1: the verified form (two-term product, or one correction round without VCT_DIV2), 2: x * r alone -- NOT exact: only the opt-in "loose" trace
+// MODE 0: the IEEE division, 1: the verified form (two-term product), 2: x * r alone -- NOT exact: only the opt-in "loose" trace
 // variant that prices the exactness (config.trace_variant = 3, k_trace_tile_split<.., 2, ..>) uses it
-// `d`: the divisor -- or, for MODE 1 under VCT_DIV2, the low word r_lo of its reciprocal (the host puts it where the
+// `d`: the divisor -- or, for MODE 1, the low word r_lo of its reciprocal (the host puts it where the
 // divisor used to be: VctStep::occ_den, VctTraceParams::half_G_aux)
 template <int MODE>
 __device__ __forceinline__ float div_const(float x, float d, float r) {
     if (MODE == 0) return x / d;
     if (MODE == 2) return x * r;
-#if VCT_DIV2
     // x / d = x * (r_hi + r_lo) (1 + e), |e| < 2^-47: the one rounding of the fma is the rounding of the quotient unless
     // x / d lies within 2^-47 of a rounding boundary -- which the device rules out per divisor, over every fp32 x
     return fmaf(x, r, x * d);
-#else
-    const float q = x * r;
-    const float e = fmaf(-d, q, x);
-    return fmaf(e, r, q);
-#endif
 }
 
 // unorm8 -> float, bit-identical to (float)c / 255.0f for every c in [0,255]:
@@ -164,37 +158,16 @@ __device__ __forceinline__ uint32_t spread_byte(SpreadLut lut, int a, uint32_t m
     return *(SpreadLut)((const __attribute__((address_space(4))) char*)lut + off);
 }
 
-// EXPERIMENT / option (-DVCT_LUT=1 | 2 | 3; round 4): the exact unorm8 -> float decode through a
-// 256-entry table in LDS (1 KiB per workgroup, entry i = (float)i / 255.0f computed by the same two-term product) --
-// one SDWA byte-select shift + one ds_read_b32 per channel instead of cvt + mul + fma.  Bit 0: the cooperative
-// block's four decodes per lane, bit 1: the per-lane gather's 32.  Same bits either way; measurements in
-// profiles/experiments/README.md.
-#ifndef VCT_LUT
-#define VCT_LUT 0
-#endif
-typedef const __attribute__((address_space(3))) float* UnormLut;
 struct LaneBlock {      // this lane's texel inside the cooperative 4x4x4 block
     SpreadLut lut;              // (wave-uniform) the dilated-coordinate table
-    const uint32_t* lut_vec;    // the same table through a plain global pointer (per-lane gather: VCT_LANE_SPREAD_LUT)
-    const __attribute__((address_space(3))) uint32_t* lut_lds = nullptr;   // VCT_LANE_SPREAD_LUT == 2: a copy in LDS (split kernel)
+    const uint32_t* lut_vec;    // the same table through a plain global pointer (per-lane gather)
     int lane;
     uint32_t sbx, sby, sbz;     // texel-INDEX offsets: dilated (l&3), ((l>>2)&3)<<1, (l>>4)<<2
-    UnormLut unorm;             // VCT_LUT: the decode table in LDS
 };
-#if VCT_LUT
-#define VCT_LUT_DECL __shared__ float lds_unorm[256];
-// (called by every thread of the workgroup before its first barrier / before any sample)
-#define VCT_LUT_FILL(lb)                                                                                      \
-    for (uint32_t i_ = threadIdx.x; i_ < 256u; i_ += blockDim.x) lds_unorm[i_] = vct_unorm8_to_float(i_);     \
-    (lb).unorm = (UnormLut)lds_unorm;
-#else
-#define VCT_LUT_DECL
-#define VCT_LUT_FILL(lb) (lb).unorm = nullptr;
-#endif
+// the exact unorm8 -> float decode of one channel of a packed texel, where a texel is not read through the texture path
 template <int SHIFT, bool LOOSE = false>
-__device__ __forceinline__ float unorm8_of(UnormLut lut, uint32_t t, bool use_lut) {
+__device__ __forceinline__ float unorm8_of(uint32_t t) {
     if (LOOSE) return (float)((t >> SHIFT) & 0xffu) * 0x1.010102p-8f;     // one multiply: wrong in the last bit for 126 of the 256 bytes
-    if (use_lut) return lut[(t >> SHIFT) & 0xffu];
     return vct_unorm8_to_float((t >> SHIFT) & 0xffu);
 }
 
@@ -202,69 +175,6 @@ __device__ __forceinline__ float unorm8_of(UnormLut lut, uint32_t t, bool use_lu
 // SGPRs and flushed once per wave.  The production build compiles all of it away.
 #ifndef VCT_STATS
 #define VCT_STATS 0
-#endif
-#ifndef VCT_UNROLL2
-#define VCT_UNROLL2 1     // A/B: 0.6281 -> 0.6216 ms at 256^3, 2.659 -> 2.623 ms at 512^3 / 4K
-#endif
-#ifndef VCT_FRACT
-#define VCT_FRACT 0       // A/B (round 3, vector pipes binding): 0.6184 / 0.6210 ms without, 0.6194 / 0.6178 ms with: no gain (v_fract and
-                          // v_cvt_flr are 4-cycle operations: 8 cycles per axis against 4 + 2 + 4)
-#endif
-#ifndef VCT_HALF_GATHER
-#define VCT_HALF_GATHER 1     // gather + interpolate the lower z plane, then the upper one (half the texel registers live)
-#endif
-#ifndef VCT_CELLS
-#define VCT_CELLS 1           // footprint records (round 5; vct_set_footprint_records): a per-lane sample of a level >= 1 is ONE
-                              // 32-byte fetch of the footprint's 8 texels (vct_volume.hip k_build_cells) instead of eight 4-byte
-                              // ones from 2-4 cache lines.  Same bits.  Dense random 1024^3 chain + random G-buffer (the one
-                              // HBM-bound case): 5.61 -> 2.86 ms; cache-resident scenes: street at 1024^3 / 4K 2.72 -> 2.70 ms,
-                              // atrium 0.611 -> 0.613 (profiles/experiments/README.md).  Off unless the context asks for it.
-#endif
-#ifndef VCT_PAIR_LOAD
-#define VCT_PAIR_LOAD 0       // EXPERIMENT (round 5, review item 8): per-lane gather with the x-adjacent texel pair of an even x in one
-                              // 8-byte load (Morton order keeps (x, x+1) adjacent for even x); odd lanes fetch x + 1 with a masked
-                              // 4-byte load.  Same bits.  Result: profiles/experiments/README.md
-#endif
-#ifndef VCT_LANE_SPREAD_LUT
-#define VCT_LANE_SPREAD_LUT 1  // round 6: the per-lane gather's dilated coordinates by table look-up (profiles/experiments/README.md)
-#endif
-#ifndef VCT_HW_UNORM
-#define VCT_HW_UNORM 1         // round 6: texels are fetched through the texture path's typed-buffer load (RGBA8 UNORM, stride 4),
-                               // which returns a texel as four floats -- bit for bit (float)c / 255.0f for every byte
-                               // (tools/unorm_probe.hip) -- so the exact decode (cvt + mul + fma per channel) is not issued at all
-#endif
-#ifndef VCT_ANISO_HW
-#define VCT_ANISO_HW 0         // EXPERIMENT: the anisotropic sampler's directional blocks through typed loads too
-#endif
-#ifndef VCT_LANE_HYBRID
-#define VCT_LANE_HYBRID 0
-#endif
-#ifndef VCT_CELLS_HW
-#define VCT_CELLS_HW 0
-#endif
-#ifndef VCT_LANE_PAIRS
-#define VCT_LANE_PAIRS 0
-#endif
-#ifndef VCT_LANE_224
-#define VCT_LANE_224 1         // (A/B: 4 + 4 spills five registers at 72 VGPRs and runs 1-2.5 % slower; pairs only: slower on the street)
-#endif
-#ifndef VCT_LANE_RECOMPUTE_XY
-#define VCT_LANE_RECOMPUTE_XY 0
-#endif
-#ifndef VCT_QUARTER_GATHER
-#define VCT_QUARTER_GATHER 0
-#endif
-#ifndef VCT_LOAD_PRIO
-#define VCT_LOAD_PRIO 1        // (A/B, 4 interleaved rounds: kernel -1.7 %, one-stream step -1.3 %, vct_gi_pass -0.9 % on the atrium; street 4K -0.5 %)
-#endif
-#ifndef VCT_LOAD_PRIO_MODE
-#define VCT_LOAD_PRIO_MODE 1   // (A/B) 1: reset behind the load instructions; 2: cooperative path resets behind its LDS reads; 3: raised from the start of the march step
-#endif
-#ifndef VCT_CELLS_ARITH
-#define VCT_CELLS_ARITH 1      // the footprint-record instantiation keeps the arithmetic (it is memory bound: see sample_level)
-#endif
-#ifndef VCT_TWO_BLOCKS
-#define VCT_TWO_BLOCKS 0      // 1: a second cooperative block before the per-lane gather (profiles/experiments/README.md)
 #endif
 struct MarchStats {
     uint32_t wave_steps;       // march-loop iterations executed by the wave
@@ -275,7 +185,7 @@ struct MarchStats {
     uint32_t fallback_lanes;   // live lanes in those
     uint32_t fallback_fits;    // per-lane samples whose live footprints WOULD fit one 4x4x4 block (anchored at their minimum)
     uint32_t greedy_blocks, greedy_le2, greedy_le3, greedy_le4;   // blocks a greedy multi-anchor cover of them would need
-    uint32_t two_blocks;       // level samples served by two cooperative blocks (VCT_TWO_BLOCKS)
+    uint32_t two_blocks;       // (unused: the two-block experiment's counter, kept so that the layout stays)
     // round 5 (review item 3): would sharing inside smaller lane groups serve the per-lane samples?  Per per-lane sample:
     uint32_t quads_live;       // 2x2-pixel quads with a live lane
     uint32_t quads_fit333;     // ... whose live footprints span <= 1 texel per axis (their union fits a 3x3x3 block)
@@ -294,39 +204,21 @@ __device__ __forceinline__ F4 sample_level(const uint32_t* __restrict__ chain, c
                                            const char* __restrict__ cells = nullptr) {
     // `am` is ballot64(act), passed in so that compound predicates are ANDed as lane masks on the
     // scalar unit (a ballot of `x && y` costs a v_cndmask + v_cmp_ne pair to materialise the bool).
-    // Issue priority raised from here until the sample's loads are out (VCT_LOAD_PRIO, round 6): a wave that is forming
+    // Issue priority raised from here until the sample's loads are out (round 6): a wave that is forming
     // addresses gets its instructions ahead of the waves that are folding texels, so its loads leave earlier and more of
-    // their latency lies under the other waves' arithmetic.  PRIO is a template parameter: the launches of whole frames
+    // their latency lies under the other waves' arithmetic (A/B, 4 interleaved rounds: kernel -1.7 %, one-stream step
+    // -1.3 %, vct_gi_pass -0.9 % on the atrium; street 4K -0.5 %).  PRIO is a template parameter: the launches of whole frames
     // take the instantiation with it, slab launches the one without -- there the priority goes to the specular waves, the
     // tail of a short launch (spec_prio; 8-way slabs 0.0881 ms with that against 0.0900 with this).  The same choice behind
     // a wave-uniform flag cost the default kernel 60 B of scratch per lane.
-    if (VCT_LOAD_PRIO && PRIO) __builtin_amdgcn_s_setprio(1);
+    if (PRIO) __builtin_amdgcn_s_setprio(1);
     const int m = lv.m;
     const float fN = lv.fN;
     // ux * fN is exact (power of two), so the fused form is the oracle's (ux*fN) - 0.5f bit for bit
     const float u = fmaf(ux, fN, -0.5f), v = fmaf(uy, fN, -0.5f), w = fmaf(uz, fN, -0.5f);
-    float a, b, c;
-    int i0, j0, k0;
-#if VCT_FRACT
-    if (m != 0) {
-        // Footprint in two instructions per axis instead of three (v_floor + v_sub + v_cvt): v_fract_f32 and
-        // v_cvt_flr_i32_f32.  v_fract returns u - floor(u) except that it never returns 1.0 (it clamps to 1 - 2^-24),
-        // while the subtraction rounds up to 1.0 for u in [-2^-25, 0).  For N >= 2 such a u cannot occur here: u < 0
-        // means ux < 0.5 / N <= 0.25, and ux = fma(q, 0.5, 0.5) with |q| >= 0.5 there, so ux is a multiple of 2^-25
-        // (q's ulp is >= 2^-24 and the sum is exact), u = ux * N - 0.5 is a multiple of 2^-24, and 1 - |u| is
-        // representable: the subtraction is exact and equals v_fract.  The one-texel level (N = 1) keeps the
-        // subtraction.  Bit-exact in every parity test -- and no faster, twice (round 2, round 3): off by default.
-        a = __builtin_amdgcn_fractf(u); b = __builtin_amdgcn_fractf(v); c = __builtin_amdgcn_fractf(w);
-        asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(i0) : "v"(u));
-        asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(j0) : "v"(v));
-        asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(k0) : "v"(w));
-    } else
-#endif
-    {
-        const float fu = floorf(u), fv = floorf(v), fw = floorf(w);
-        a = u - fu; b = v - fv; c = w - fw;
-        i0 = (int)fu; j0 = (int)fv; k0 = (int)fw;
-    }
+    const float fu = floorf(u), fv = floorf(v), fw = floorf(w);
+    const float a = u - fu, b = v - fv, c = w - fw;
+    const int i0 = (int)fu, j0 = (int)fv, k0 = (int)fw;
     // Texels are addressed by their Morton INDEX inside the level (< 2^30): the dilated-integer arithmetic yields it
     // directly, and the level is a texel buffer whose structured load takes the index (no shift, no 64-bit address add).
     const uint32_t* __restrict__ base = chain + lv.off;
@@ -336,10 +228,6 @@ __device__ __forceinline__ F4 sample_level(const uint32_t* __restrict__ chain, c
     F4 r = {0.0f, 0.0f, 0.0f, 0.0f};
     bool coop = false;
     int ax = 0, ay = 0, az = 0, dx = 0, dy = 0, dz = 0;
-#if VCT_TWO_BLOCKS
-    bool two = false, mine = act, mine2 = false;   // mine: this lane's footprint lies in the block being fetched
-    int ex = 0, ey = 0, ez = 0;                    // second anchor - first anchor
-#endif
     if (COOP) {
         // anchor = footprint of the tile's centre pixel (lane 27) if it is live, else the first live lane
         const int src = ((am >> 27) & 1ull) ? 27 : (int)__ffsll((long long)am) - 1;
@@ -350,30 +238,8 @@ __device__ __forceinline__ F4 sample_level(const uint32_t* __restrict__ chain, c
         const uint32_t far = max(max((uint32_t)dx, (uint32_t)dy), (uint32_t)dz);
         const unsigned long long out = ballot64(far > 2u) & am;
         coop = out == 0ull;
-#if VCT_TWO_BLOCKS
-        if (!coop) {
-            // Second chance before the per-lane gather: a second block anchored at the first live lane the first one
-            // misses.  If the two blocks hold every live footprint, each is fetched cooperatively in turn and a lane
-            // gathers from the one that holds its footprint (any block that holds the 8 texels gives the same bits).
-            const int s2 = (int)__ffsll((long long)out) - 1;
-            ex = __builtin_amdgcn_readlane(dx, s2) - 1;
-            ey = __builtin_amdgcn_readlane(dy, s2) - 1;
-            ez = __builtin_amdgcn_readlane(dz, s2) - 1;
-            const uint32_t far2 = max(max((uint32_t)(dx - ex), (uint32_t)(dy - ey)), (uint32_t)(dz - ez));
-            two = (ballot64(far2 > 2u) & out) == 0ull;
-            coop = two;
-            mine = act && far <= 2u;
-            mine2 = act && far > 2u;
-        }
-#endif
     }
-#if VCT_TWO_BLOCKS
-    if (COOP && coop)
-#pragma unroll 1
-    for (int pass = 0;; ++pass) {
-#else
     if (COOP && coop) {
-#endif
         uint32_t idx;
         if (WRAP) {
             // scalar unit: dilate the anchor; vector unit: one dilated add per axis
@@ -390,66 +256,18 @@ __device__ __forceinline__ F4 sample_level(const uint32_t* __restrict__ chain, c
             const int z = min(max(az + (lb.lane >> 4), 0), m);
             idx = vct_morton3((uint32_t)x, (uint32_t)y, (uint32_t)z);
         }
-#if VCT_HW_UNORM && !VCT_LUT
         const float4 d = texel_f32(tb, idx);
-        if (VCT_LOAD_PRIO && PRIO && VCT_LOAD_PRIO_MODE != 2) __builtin_amdgcn_s_setprio(0);
+        if (PRIO) __builtin_amdgcn_s_setprio(0);
         // (channels are >= +0: the block is empty iff no channel has a bit set)
         const bool any_texel = ballot64((__float_as_uint(d.x) | __float_as_uint(d.y) | __float_as_uint(d.z) | __float_as_uint(d.w)) != 0u) != 0ull;
-#else
-        const uint32_t t = base[idx];
-        const bool any_texel = ballot64(t != 0u) != 0ull;
-#endif
         if (VCT_STATS) { if (any_texel) ++ms.coop_hit; else ++ms.coop_zero; }
-        if (VCT_LOAD_PRIO && PRIO && VCT_LOAD_PRIO_MODE == 2 && !any_texel) __builtin_amdgcn_s_setprio(0);
         if (any_texel) {     // all 64 texels zero: every footprint sums to exactly +0
-#if !(VCT_HW_UNORM && !VCT_LUT)
-            float4 d;
-            d.x = unorm8_of<0, LOOSE>(lb.unorm, t, (VCT_LUT & 1) != 0);
-            d.y = unorm8_of<8, LOOSE>(lb.unorm, t, (VCT_LUT & 1) != 0);
-            d.z = unorm8_of<16, LOOSE>(lb.unorm, t, (VCT_LUT & 1) != 0);
-            d.w = unorm8_of<24, LOOSE>(lb.unorm, t, (VCT_LUT & 1) != 0);
-#endif
             blk[lb.lane] = d;
             wave_sync();
-#if VCT_TWO_BLOCKS
-            if (mine) {
-#endif
             const int slot = act ? (dz * 4 + dy) * 4 + dx : 0;
             const float4* q = blk + slot;
             const float a0 = 1.0f - a, b0 = 1.0f - b, c0 = 1.0f - c;
             const float ab00 = a0 * b0, ab10 = a * b0, ab01 = a0 * b, ab11 = a * b;
-#if VCT_QUARTER_GATHER
-            {   // EXPERIMENT (round 6): two texels at a time -- 8 texel registers live instead of 16 (for 64 VGPRs / 8 waves per SIMD)
-                const float w0 = ab00 * c0, w1 = ab10 * c0;
-                { const float4 t0 = q[0], t1 = q[1];
-#define VCT_ACC(ch) r.ch = w0 * t0.ch; r.ch = fmaf(w1, t1.ch, r.ch);
-                VCT_ACC(x) VCT_ACC(y) VCT_ACC(z) VCT_ACC(w)
-#undef VCT_ACC
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                const float w2 = ab01 * c0, w3 = ab11 * c0;
-                { const float4 t2 = q[4], t3 = q[5];
-#define VCT_ACC(ch) r.ch = fmaf(w2, t2.ch, r.ch); r.ch = fmaf(w3, t3.ch, r.ch);
-                VCT_ACC(x) VCT_ACC(y) VCT_ACC(z) VCT_ACC(w)
-#undef VCT_ACC
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                const float w4 = ab00 * c, w5 = ab10 * c;
-                { const float4 t4 = q[16], t5 = q[17];
-#define VCT_ACC(ch) r.ch = fmaf(w4, t4.ch, r.ch); r.ch = fmaf(w5, t5.ch, r.ch);
-                VCT_ACC(x) VCT_ACC(y) VCT_ACC(z) VCT_ACC(w)
-#undef VCT_ACC
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                const float w6 = ab01 * c, w7 = ab11 * c;
-                { const float4 t6 = q[20], t7 = q[21];
-                wave_sync();
-#define VCT_ACC(ch) r.ch = fmaf(w6, t6.ch, r.ch); r.ch = fmaf(w7, t7.ch, r.ch);
-                VCT_ACC(x) VCT_ACC(y) VCT_ACC(z) VCT_ACC(w)
-#undef VCT_ACC
-                }
-            }
-#elif VCT_HALF_GATHER
             {   // lower z plane first, then the upper one: half the texel registers live at a time
                 const float4 t0 = q[0], t1 = q[1], t2 = q[4], t3 = q[5];
                 const float w0 = ab00 * c0, w1 = ab10 * c0, w2 = ab01 * c0, w3 = ab11 * c0;
@@ -466,32 +284,7 @@ __device__ __forceinline__ F4 sample_level(const uint32_t* __restrict__ chain, c
                 VCT_ACC(x) VCT_ACC(y) VCT_ACC(z) VCT_ACC(w)
 #undef VCT_ACC
             }
-#else
-            const float4 t0 = q[0], t1 = q[1], t2 = q[4], t3 = q[5];
-            const float4 t4 = q[16], t5 = q[17], t6 = q[20], t7 = q[21];
-            wave_sync();
-            if (VCT_LOAD_PRIO && PRIO && VCT_LOAD_PRIO_MODE == 2) __builtin_amdgcn_s_setprio(0);
-            const float w0 = ab00 * c0, w1 = ab10 * c0, w2 = ab01 * c0, w3 = ab11 * c0;
-            const float w4 = ab00 * c, w5 = ab10 * c, w6 = ab01 * c, w7 = ab11 * c;
-#define VCT_ACC(ch)                                                                           \
-    r.ch = w0 * t0.ch;                                                                        \
-    r.ch = fmaf(w1, t1.ch, r.ch); r.ch = fmaf(w2, t2.ch, r.ch); r.ch = fmaf(w3, t3.ch, r.ch); \
-    r.ch = fmaf(w4, t4.ch, r.ch); r.ch = fmaf(w5, t5.ch, r.ch); r.ch = fmaf(w6, t6.ch, r.ch); \
-    r.ch = fmaf(w7, t7.ch, r.ch);
-            VCT_ACC(x) VCT_ACC(y) VCT_ACC(z) VCT_ACC(w)
-#undef VCT_ACC
-#endif
-#if VCT_TWO_BLOCKS
-            }                              // a lane of the other block keeps what it has
-#endif
         }
-#if VCT_TWO_BLOCKS
-        if (!two || pass == 1) break;
-        if (VCT_STATS) ++ms.two_blocks;
-        ax += ex; ay += ey; az += ez;
-        dx -= ex; dy -= ey; dz -= ez;
-        mine = mine2;
-#endif
     } else {
       if (VCT_STATS) {
           ++ms.fallback; ms.fallback_lanes += (uint32_t)__popcll(am);
@@ -538,28 +331,20 @@ __device__ __forceinline__ F4 sample_level(const uint32_t* __restrict__ chain, c
       if (act) {
         uint32_t mx0, mx1, my0, my1, mz0, mz1;
         if (WRAP) {
-            // (the instantiation with footprint records serves volumes that do NOT fit the caches: every sample is a per-lane
-            // one and the memory pipe is what binds -- three more loads per sample cost it 1-3 %, VCT_CELLS_ARITH)
-            constexpr bool use_lut = VCT_LANE_SPREAD_LUT != 0 && !(CELLS && VCT_CELLS_ARITH);
-            if (use_lut) {
-            // the dilated coordinates from the table the anchor path reads with scalar loads -- here one 4-byte VECTOR load
-            // per axis (a 4 KiB table, cache resident) instead of ten vector instructions, half of them 4-cycle ones
-            const uint32_t m4 = (uint32_t)m << 2;
-            if (VCT_LANE_SPREAD_LUT == 2 && lb.lut_lds) {        // (A/B form: the table in LDS, filled per workgroup)
-                const __attribute__((address_space(3))) char* ll = (const __attribute__((address_space(3))) char*)lb.lut_lds;
-                mx0 = *(const __attribute__((address_space(3))) uint32_t*)(ll + (((uint32_t)i0 << 2) & m4)) >> 2;
-                my0 = *(const __attribute__((address_space(3))) uint32_t*)(ll + (((uint32_t)j0 << 2) & m4)) >> 1;
-                mz0 = *(const __attribute__((address_space(3))) uint32_t*)(ll + (((uint32_t)k0 << 2) & m4));
+            if (!CELLS) {
+                // the dilated coordinates from the table the anchor path reads with scalar loads -- here one 4-byte VECTOR
+                // load per axis (a 4 KiB table, cache resident) instead of ten vector instructions, half of them 4-cycle ones
+                const uint32_t m4 = (uint32_t)m << 2;
+                const char* lutb = (const char*)lb.lut_vec;      // (entries are spread3(i) << 2)
+                mx0 = *(const uint32_t*)(lutb + (((uint32_t)i0 << 2) & m4)) >> 2;
+                my0 = *(const uint32_t*)(lutb + (((uint32_t)j0 << 2) & m4)) >> 1;
+                mz0 = *(const uint32_t*)(lutb + (((uint32_t)k0 << 2) & m4));
             } else {
-            const char* lutb = (const char*)lb.lut_vec;      // (entries are spread3(i) << 2)
-            mx0 = *(const uint32_t*)(lutb + (((uint32_t)i0 << 2) & m4)) >> 2;
-            my0 = *(const uint32_t*)(lutb + (((uint32_t)j0 << 2) & m4)) >> 1;
-            mz0 = *(const uint32_t*)(lutb + (((uint32_t)k0 << 2) & m4));
-            }
-            } else {
-            mx0 = vct_spread3((uint32_t)i0 & (uint32_t)m);
-            my0 = vct_spread3((uint32_t)j0 & (uint32_t)m) << 1;
-            mz0 = vct_spread3((uint32_t)k0 & (uint32_t)m) << 2;
+                // (the instantiation with footprint records serves volumes that do NOT fit the caches: every sample is a
+                // per-lane one and the memory pipe is what binds -- the table's three loads per sample cost it 1-3 %)
+                mx0 = vct_spread3((uint32_t)i0 & (uint32_t)m);
+                my0 = vct_spread3((uint32_t)j0 & (uint32_t)m) << 1;
+                mz0 = vct_spread3((uint32_t)k0 & (uint32_t)m) << 2;
             }
             mx1 = ((mx0 | ~MX) + 1u) & MX;      // dilated increment, wraps at N
             my1 = ((my0 | ~MY) + 2u) & MY;
@@ -572,75 +357,12 @@ __device__ __forceinline__ F4 sample_level(const uint32_t* __restrict__ chain, c
             my0 = vct_spread3((uint32_t)cj0) << 1; my1 = vct_spread3((uint32_t)cj1) << 1;
             mz0 = vct_spread3((uint32_t)ck0) << 2; mz1 = vct_spread3((uint32_t)ck1) << 2;
         }
-        constexpr bool hw_texels = VCT_HW_UNORM && !VCT_LUT && !VCT_PAIR_LOAD && !(VCT_CELLS && CELLS);
-        if (VCT_CELLS_HW && VCT_HW_UNORM && VCT_CELLS && CELLS && WRAP && lv.off != 0u) {
-            // EXPERIMENT: the footprint record read as eight texels of a texel buffer laid over the records (decoded by the
-            // texture path; eight 4-byte requests into one 32-byte sector instead of two 16-byte ones + 32 decodes)
-            const vct_v4i32 cbuf = level_texel_buffer((const uint32_t*)(cells + ((size_t)lv.off << 5)));
-            const uint32_t ri = (mx0 | my0 | mz0) << 3;
+        if (!CELLS) {
+            // eight typed-buffer loads: every texel arrives as four floats.  Phases of 2 + 2 + 4 texels: the first phase is
+            // where most else is still live (both planes' addresses, all weight inputs), the last one where least is
+            // (A/B: 4 + 4 spills five registers at 72 VGPRs and runs 1-2.5 % slower; pairs only: slower on the street)
             const float a0 = 1.0f - a, b0 = 1.0f - b, c0 = 1.0f - c;
             const float ab00 = a0 * b0, ab10 = a * b0, ab01 = a0 * b, ab11 = a * b;
-            {
-                const float4 f0 = texel_f32(cbuf, ri), f1 = texel_f32(cbuf, ri + 1u), f2 = texel_f32(cbuf, ri + 2u), f3 = texel_f32(cbuf, ri + 3u);
-                const float w0 = ab00 * c0, w1 = ab10 * c0, w2 = ab01 * c0, w3 = ab11 * c0;
-#define VCT_ACC(ch) r.ch = w0 * f0.ch; r.ch = fmaf(w1, f1.ch, r.ch); r.ch = fmaf(w2, f2.ch, r.ch); r.ch = fmaf(w3, f3.ch, r.ch);
-                VCT_ACC(x) VCT_ACC(y) VCT_ACC(z) VCT_ACC(w)
-#undef VCT_ACC
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            {
-                const float4 f4 = texel_f32(cbuf, ri + 4u), f5 = texel_f32(cbuf, ri + 5u), f6 = texel_f32(cbuf, ri + 6u), f7 = texel_f32(cbuf, ri + 7u);
-                const float w4 = ab00 * c, w5 = ab10 * c, w6 = ab01 * c, w7 = ab11 * c;
-#define VCT_ACC(ch) r.ch = fmaf(w4, f4.ch, r.ch); r.ch = fmaf(w5, f5.ch, r.ch); r.ch = fmaf(w6, f6.ch, r.ch); r.ch = fmaf(w7, f7.ch, r.ch);
-                VCT_ACC(x) VCT_ACC(y) VCT_ACC(z) VCT_ACC(w)
-#undef VCT_ACC
-            }
-        } else
-        if (hw_texels) {
-            // eight typed-buffer loads: every texel arrives as four floats; one z plane at a time
-            const float a0 = 1.0f - a, b0 = 1.0f - b, c0 = 1.0f - c;
-            const float ab00 = a0 * b0, ab10 = a * b0, ab01 = a0 * b, ab11 = a * b;
-#if VCT_LANE_PAIRS
-            // two texels at a time (8 texel registers live): four dependent round trips, but no spill at 72 VGPRs
-            {
-                const uint32_t xy00 = mx0 | my0, xy10 = mx1 | my0;
-                const float4 f0 = texel_f32(tb, xy00 | mz0), f1 = texel_f32(tb, xy10 | mz0);
-                const float w0 = ab00 * c0, w1 = ab10 * c0;
-#define VCT_ACC(ch) r.ch = w0 * f0.ch; r.ch = fmaf(w1, f1.ch, r.ch);
-                VCT_ACC(x) VCT_ACC(y) VCT_ACC(z) VCT_ACC(w)
-#undef VCT_ACC
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            {
-                const uint32_t xy01 = mx0 | my1, xy11 = mx1 | my1;
-                const float4 f2 = texel_f32(tb, xy01 | mz0), f3 = texel_f32(tb, xy11 | mz0);
-                const float w2 = ab01 * c0, w3 = ab11 * c0;
-#define VCT_ACC(ch) r.ch = fmaf(w2, f2.ch, r.ch); r.ch = fmaf(w3, f3.ch, r.ch);
-                VCT_ACC(x) VCT_ACC(y) VCT_ACC(z) VCT_ACC(w)
-#undef VCT_ACC
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            {
-                const uint32_t xy00 = mx0 | my0, xy10 = mx1 | my0;
-                const float4 f4 = texel_f32(tb, xy00 | mz1), f5 = texel_f32(tb, xy10 | mz1);
-                const float w4 = ab00 * c, w5 = ab10 * c;
-#define VCT_ACC(ch) r.ch = fmaf(w4, f4.ch, r.ch); r.ch = fmaf(w5, f5.ch, r.ch);
-                VCT_ACC(x) VCT_ACC(y) VCT_ACC(z) VCT_ACC(w)
-#undef VCT_ACC
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            {
-                const uint32_t xy01 = mx0 | my1, xy11 = mx1 | my1;
-                const float4 f6 = texel_f32(tb, xy01 | mz1), f7 = texel_f32(tb, xy11 | mz1);
-                const float w6 = ab01 * c, w7 = ab11 * c;
-#define VCT_ACC(ch) r.ch = fmaf(w6, f6.ch, r.ch); r.ch = fmaf(w7, f7.ch, r.ch);
-                VCT_ACC(x) VCT_ACC(y) VCT_ACC(z) VCT_ACC(w)
-#undef VCT_ACC
-            }
-#else
-#if VCT_LANE_224
-            // phases of 2 + 2 + 4 texels: the first phase is where most else is still live (both planes' addresses, all weight
-            // inputs), the last one where least is
             {
                 const float4 f0 = texel_f32(tb, mx0 | my0 | mz0), f1 = texel_f32(tb, mx1 | my0 | mz0);
                 const float w0 = ab00 * c0, w1 = ab10 * c0;
@@ -657,123 +379,52 @@ __device__ __forceinline__ F4 sample_level(const uint32_t* __restrict__ chain, c
 #undef VCT_ACC
             }
             __builtin_amdgcn_sched_barrier(0);
-#if VCT_LANE_HYBRID
-            {   // EXPERIMENT: the upper plane through plain loads + the exact decode (4 B per lane and load through the data
-                // return path instead of 16): balances the vector pipes against the texture path on per-lane-heavy scenes
-                const uint32_t t4 = base[mx0 | my0 | mz1], t5 = base[mx1 | my0 | mz1];
-                const uint32_t t6 = base[mx0 | my1 | mz1], t7 = base[mx1 | my1 | mz1];
-                const float w4 = ab00 * c, w5 = ab10 * c, w6 = ab01 * c, w7 = ab11 * c;
-#define VCT_ACC(ch, sh) r.ch = fmaf(w4, vct_unorm8_to_float((t4 >> sh) & 0xffu), r.ch); r.ch = fmaf(w5, vct_unorm8_to_float((t5 >> sh) & 0xffu), r.ch); \
-                        r.ch = fmaf(w6, vct_unorm8_to_float((t6 >> sh) & 0xffu), r.ch); r.ch = fmaf(w7, vct_unorm8_to_float((t7 >> sh) & 0xffu), r.ch);
-                VCT_ACC(x, 0) VCT_ACC(y, 8) VCT_ACC(z, 16) VCT_ACC(w, 24)
-#undef VCT_ACC
-            }
-#else
             {
                 const float4 f4 = texel_f32(tb, mx0 | my0 | mz1), f5 = texel_f32(tb, mx1 | my0 | mz1);
                 const float4 f6 = texel_f32(tb, mx0 | my1 | mz1), f7 = texel_f32(tb, mx1 | my1 | mz1);
-                if (VCT_LOAD_PRIO && PRIO) __builtin_amdgcn_s_setprio(0);
+                if (PRIO) __builtin_amdgcn_s_setprio(0);
                 const float w4 = ab00 * c, w5 = ab10 * c, w6 = ab01 * c, w7 = ab11 * c;
 #define VCT_ACC(ch) r.ch = fmaf(w4, f4.ch, r.ch); r.ch = fmaf(w5, f5.ch, r.ch); r.ch = fmaf(w6, f6.ch, r.ch); r.ch = fmaf(w7, f7.ch, r.ch);
                 VCT_ACC(x) VCT_ACC(y) VCT_ACC(z) VCT_ACC(w)
 #undef VCT_ACC
             }
-#endif
-#elif VCT_LANE_RECOMPUTE_XY
-            // (the x|y parts are formed again for the upper plane instead of being kept across the lower one)
-            {
-                const float4 f0 = texel_f32(tb, mx0 | my0 | mz0), f1 = texel_f32(tb, mx1 | my0 | mz0);
-                const float4 f2 = texel_f32(tb, mx0 | my1 | mz0), f3 = texel_f32(tb, mx1 | my1 | mz0);
-                const float w0 = ab00 * c0, w1 = ab10 * c0, w2 = ab01 * c0, w3 = ab11 * c0;
-#define VCT_ACC(ch) r.ch = w0 * f0.ch; r.ch = fmaf(w1, f1.ch, r.ch); r.ch = fmaf(w2, f2.ch, r.ch); r.ch = fmaf(w3, f3.ch, r.ch);
-                VCT_ACC(x) VCT_ACC(y) VCT_ACC(z) VCT_ACC(w)
-#undef VCT_ACC
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            {
-                uint32_t x0 = mx0, x1 = mx1, y0 = my0, y1 = my1;
-                asm volatile("" : "+v"(x0), "+v"(x1), "+v"(y0), "+v"(y1));      // (no common subexpression with the lower plane)
-                const float4 f4 = texel_f32(tb, x0 | y0 | mz1), f5 = texel_f32(tb, x1 | y0 | mz1);
-                const float4 f6 = texel_f32(tb, x0 | y1 | mz1), f7 = texel_f32(tb, x1 | y1 | mz1);
-                const float w4 = ab00 * c, w5 = ab10 * c, w6 = ab01 * c, w7 = ab11 * c;
-#define VCT_ACC(ch) r.ch = fmaf(w4, f4.ch, r.ch); r.ch = fmaf(w5, f5.ch, r.ch); r.ch = fmaf(w6, f6.ch, r.ch); r.ch = fmaf(w7, f7.ch, r.ch);
-                VCT_ACC(x) VCT_ACC(y) VCT_ACC(z) VCT_ACC(w)
-#undef VCT_ACC
-            }
-#else
-            const uint32_t xy00 = mx0 | my0, xy10 = mx1 | my0, xy01 = mx0 | my1, xy11 = mx1 | my1;
-            {
-                const float4 f0 = texel_f32(tb, xy00 | mz0), f1 = texel_f32(tb, xy10 | mz0);
-                const float4 f2 = texel_f32(tb, xy01 | mz0), f3 = texel_f32(tb, xy11 | mz0);
-                const float w0 = ab00 * c0, w1 = ab10 * c0, w2 = ab01 * c0, w3 = ab11 * c0;
-#define VCT_ACC(ch) r.ch = w0 * f0.ch; r.ch = fmaf(w1, f1.ch, r.ch); r.ch = fmaf(w2, f2.ch, r.ch); r.ch = fmaf(w3, f3.ch, r.ch);
-                VCT_ACC(x) VCT_ACC(y) VCT_ACC(z) VCT_ACC(w)
-#undef VCT_ACC
-            }
-            __builtin_amdgcn_sched_barrier(0);      // (the upper plane's loads are issued after the lower plane is folded: 16 texel registers)
-            {
-                const float4 f4 = texel_f32(tb, xy00 | mz1), f5 = texel_f32(tb, xy10 | mz1);
-                const float4 f6 = texel_f32(tb, xy01 | mz1), f7 = texel_f32(tb, xy11 | mz1);
-                const float w4 = ab00 * c, w5 = ab10 * c, w6 = ab01 * c, w7 = ab11 * c;
-#define VCT_ACC(ch) r.ch = fmaf(w4, f4.ch, r.ch); r.ch = fmaf(w5, f5.ch, r.ch); r.ch = fmaf(w6, f6.ch, r.ch); r.ch = fmaf(w7, f7.ch, r.ch);
-                VCT_ACC(x) VCT_ACC(y) VCT_ACC(z) VCT_ACC(w)
-#undef VCT_ACC
-            }
-#endif
-#endif
         } else {
-        uint32_t t[8];
-#define VCT_TEXEL(o) (base[(o)])
-        if (VCT_CELLS && CELLS && WRAP && lv.off != 0u) {     // (CELLS instantiations are launched with records present)
-            // footprint record of the lower corner: the 8 texels as 32 contiguous bytes (levels >= 1; Morton index * 32
-            // = byte offset of the record, < 2^32 for every level but the first of a 2048^3 grid, which has none)
-            const char* cb = cells + ((size_t)lv.off << 5);
-            const uint32_t ro = (mx0 | my0 | mz0) << 5;
-            const uint4 lo = *(const uint4*)(cb + ro);
-            const uint4 hi = *(const uint4*)(cb + ro + 16u);
-            t[0] = lo.x; t[1] = lo.y; t[2] = lo.z; t[3] = lo.w;
-            t[4] = hi.x; t[5] = hi.y; t[6] = hi.z; t[7] = hi.w;
-        } else {
-#if VCT_PAIR_LOAD
-        if (WRAP && (MX & 1u)) {            // (not the one-texel level: its x + 1 wraps onto x)
-            const bool even = (mx0 & 1u) == 0u;
-            const uint32_t mxe = mx0 & ~1u;
-            const uint32_t yz[4] = {my0 | mz0, my1 | mz0, my0 | mz1, my1 | mz1};
+            // Footprint records (round 5; vct_set_footprint_records): a per-lane sample of a level >= 1 is ONE 32-byte fetch of
+            // the footprint's 8 texels (vct_volume.hip k_build_cells) instead of eight 4-byte ones from 2-4 cache lines.  Same
+            // bits.  Dense random 1024^3 chain + random G-buffer (the one HBM-bound case): 5.61 -> 2.86 ms; cache-resident
+            // scenes: street at 1024^3 / 4K 2.72 -> 2.70 ms, atrium 0.611 -> 0.613 (profiles/experiments/README.md).  Off
+            // unless the context asks for it.
+            uint32_t t[8];
+            if (WRAP && lv.off != 0u) {     // (CELLS instantiations are launched with records present)
+                // footprint record of the lower corner: the 8 texels as 32 contiguous bytes (levels >= 1; Morton index * 32
+                // = byte offset of the record, < 2^32 for every level but the first of a 2048^3 grid, which has none)
+                const char* cb = cells + ((size_t)lv.off << 5);
+                const uint32_t ro = (mx0 | my0 | mz0) << 5;
+                const uint4 lo = *(const uint4*)(cb + ro);
+                const uint4 hi = *(const uint4*)(cb + ro + 16u);
+                t[0] = lo.x; t[1] = lo.y; t[2] = lo.z; t[3] = lo.w;
+                t[4] = hi.x; t[5] = hi.y; t[6] = hi.z; t[7] = hi.w;
+            } else {
+                t[0] = base[mx0 | my0 | mz0]; t[1] = base[mx1 | my0 | mz0];
+                t[2] = base[mx0 | my1 | mz0]; t[3] = base[mx1 | my1 | mz0];
+                t[4] = base[mx0 | my0 | mz1]; t[5] = base[mx1 | my0 | mz1];
+                t[6] = base[mx0 | my1 | mz1]; t[7] = base[mx1 | my1 | mz1];
+            }
+            if (PRIO) __builtin_amdgcn_s_setprio(0);
+            const float a0 = 1.0f - a, b0 = 1.0f - b, c0 = 1.0f - c;
+            const float wg[8] = {(a0 * b0) * c0, (a * b0) * c0, (a0 * b) * c0, (a * b) * c0,
+                                 (a0 * b0) * c,  (a * b0) * c,  (a0 * b) * c,  (a * b) * c};
+            r.x = wg[0] * unorm8_of<0, LOOSE>(t[0]);
+            r.y = wg[0] * unorm8_of<8, LOOSE>(t[0]);
+            r.z = wg[0] * unorm8_of<16, LOOSE>(t[0]);
+            r.w = wg[0] * unorm8_of<24, LOOSE>(t[0]);
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const uint2 pr = *(const uint2*)(base + (mxe | yz[q]));       // (base: uint32_t*, index arithmetic)
-                uint32_t hi = pr.y;
-                if (!even) hi = VCT_TEXEL(mx1 | yz[q]);
-                t[2 * q] = even ? pr.x : pr.y;
-                t[2 * q + 1] = hi;
+            for (int i = 1; i < 8; ++i) {
+                r.x = fmaf(wg[i], unorm8_of<0, LOOSE>(t[i]), r.x);
+                r.y = fmaf(wg[i], unorm8_of<8, LOOSE>(t[i]), r.y);
+                r.z = fmaf(wg[i], unorm8_of<16, LOOSE>(t[i]), r.z);
+                r.w = fmaf(wg[i], unorm8_of<24, LOOSE>(t[i]), r.w);
             }
-        } else {
-#endif
-        t[0] = VCT_TEXEL(mx0 | my0 | mz0); t[1] = VCT_TEXEL(mx1 | my0 | mz0);
-        t[2] = VCT_TEXEL(mx0 | my1 | mz0); t[3] = VCT_TEXEL(mx1 | my1 | mz0);
-        t[4] = VCT_TEXEL(mx0 | my0 | mz1); t[5] = VCT_TEXEL(mx1 | my0 | mz1);
-        t[6] = VCT_TEXEL(mx0 | my1 | mz1); t[7] = VCT_TEXEL(mx1 | my1 | mz1);
-#if VCT_PAIR_LOAD
-        }
-#endif
-        }
-#undef VCT_TEXEL
-        if (VCT_LOAD_PRIO && PRIO) __builtin_amdgcn_s_setprio(0);
-        const float a0 = 1.0f - a, b0 = 1.0f - b, c0 = 1.0f - c;
-        const float wg[8] = {(a0 * b0) * c0, (a * b0) * c0, (a0 * b) * c0, (a * b) * c0,
-                             (a0 * b0) * c,  (a * b0) * c,  (a0 * b) * c,  (a * b) * c};
-        constexpr bool L = (VCT_LUT & 2) != 0;
-        r.x = wg[0] * unorm8_of<0, LOOSE>(lb.unorm, t[0], L);
-        r.y = wg[0] * unorm8_of<8, LOOSE>(lb.unorm, t[0], L);
-        r.z = wg[0] * unorm8_of<16, LOOSE>(lb.unorm, t[0], L);
-        r.w = wg[0] * unorm8_of<24, LOOSE>(lb.unorm, t[0], L);
-#pragma unroll
-        for (int i = 1; i < 8; ++i) {
-            r.x = fmaf(wg[i], unorm8_of<0, LOOSE>(lb.unorm, t[i], L), r.x);
-            r.y = fmaf(wg[i], unorm8_of<8, LOOSE>(lb.unorm, t[i], L), r.y);
-            r.z = fmaf(wg[i], unorm8_of<16, LOOSE>(lb.unorm, t[i], L), r.z);
-            r.w = fmaf(wg[i], unorm8_of<24, LOOSE>(lb.unorm, t[i], L), r.w);
-        }
         }
       }
     }
@@ -831,24 +482,12 @@ __device__ __forceinline__ F4 sample_aniso(const VctTraceParams& p, const VctLev
                                  (((saz | ~MZ) + lb.sbz) & MZ);
             const unsigned long long mneg[3] = {mx, my, mz};
             const bool lneg[3] = {ac.nx, ac.ny, ac.nz};
-#if VCT_HW_UNORM && VCT_ANISO_HW
-            // texels decoded by the texture path (sample_level): the up to six directional blocks arrive as float4s
-            float4 fpos[3], fneg[3];
-            const float4 zero4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {          // all block loads first (up to 6 in flight)
-                fpos[k] = mneg[k] != m ? texel_f32(level_texel_buffer(chain_of(2 * k) + lv.off), idx) : zero4;          // some lane is >= 0
-                fneg[k] = mneg[k] != 0ull ? texel_f32(level_texel_buffer(chain_of(2 * k + 1) + lv.off), idx) : zero4;   // some lane is < 0
-            }
-            auto bits4 = [](const float4& f) { return __float_as_uint(f.x) | __float_as_uint(f.y) | __float_as_uint(f.z) | __float_as_uint(f.w); };
-#else
             uint32_t tpos[3], tneg[3];
 #pragma unroll
             for (int k = 0; k < 3; ++k) {          // all block loads first (up to 6 in flight)
                 tpos[k] = mneg[k] != m ? (chain_of(2 * k) + lv.off)[idx] : 0u;          // some lane is >= 0
                 tneg[k] = mneg[k] != 0ull ? (chain_of(2 * k + 1) + lv.off)[idx] : 0u;   // some lane is < 0
             }
-#endif
             const int slot = act ? (dz * 4 + dy) * 4 + dx : 0;
             const float a0 = 1.0f - a, b0 = 1.0f - b, c0 = 1.0f - c;
             const float ab00 = a0 * b0, ab10 = a * b0, ab01 = a0 * b, ab11 = a * b;
@@ -859,11 +498,6 @@ __device__ __forceinline__ F4 sample_aniso(const VctTraceParams& p, const VctLev
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 F4 r = {0.0f, 0.0f, 0.0f, 0.0f};
-#if VCT_HW_UNORM && VCT_ANISO_HW
-                if (ballot64((bits4(fpos[k]) | bits4(fneg[k])) != 0u) != 0ull) {
-                    if (mneg[k] != m) blk[lb.lane] = fpos[k];
-                    if (mneg[k] != 0ull) alt[lb.lane] = fneg[k];
-#else
                 if (ballot64((tpos[k] | tneg[k]) != 0u) != 0ull) {
                     auto dec = [](uint32_t t) {
                         float4 d;
@@ -873,7 +507,6 @@ __device__ __forceinline__ F4 sample_aniso(const VctTraceParams& p, const VctLev
                     };
                     if (mneg[k] != m) blk[lb.lane] = dec(tpos[k]);
                     if (mneg[k] != 0ull) alt[lb.lane] = dec(tneg[k]);
-#endif
                     wave_sync();
                     const float4* q = (lneg[k] ? alt : blk) + slot;
                     const float4 t0 = q[0], t1 = q[1], t2 = q[4], t3v = q[5];
@@ -935,7 +568,6 @@ __device__ __forceinline__ VctStep load_step(StepTable t, int k) {
 //   sample:   textureLod = blend of the two levels (frac == 0: one level, decided in the table)
 //   composite: trace.fs:100 (colour), :101 (occlusion), :102 (alpha), front to back
 #define VCT_MARCH_STEP(st, act, live)                                                                        \
-        if (VCT_LOAD_PRIO && PRIO && VCT_LOAD_PRIO_MODE == 3) __builtin_amdgcn_s_setprio(1); \
         const float px = start.x + dir.x * st.dist; \
         const float py = start.y + dir.y * st.dist; \
         const float pz = start.z + dir.z * st.dist; \
@@ -977,8 +609,9 @@ __device__ __forceinline__ F4 cone_march(const VctTraceParams& p, bool alive, F3
         ac.nx = !(dir.x >= 0.0f); ac.ny = !(dir.y >= 0.0f); ac.nz = !(dir.z >= 0.0f);
     }
     const unsigned long long alive_mask = ballot64(alive);
-    if constexpr (VCT_UNROLL2 && !ANISO) {
-    // Two steps per loop iteration (not the anisotropic march: its body, twice, spills and ran 7x slower), the table entries ping-pong between two register sets: the entry of step k + 1 is
+    if constexpr (!ANISO) {
+    // Two steps per loop iteration (A/B: 0.6281 -> 0.6216 ms at 256^3, 2.659 -> 2.623 ms at 512^3 / 4K; not the anisotropic
+    // march: its body, twice, spills and ran 7x slower), the table entries ping-pong between two register sets: the entry of step k + 1 is
     // requested while step k is marched and is never copied (the rotating form below moves 12 SGPRs per step, and
     // the scalar pipe is the march's second bound).
     // (the step body goes through a lambda here: measured 2 % faster than the macro expanded in place, while the
@@ -1021,47 +654,6 @@ __device__ __forceinline__ F4 cone_march(const VctTraceParams& p, bool alive, F3
     return {cr, cg, cb, occ};
 }
 
-// EXPERIMENT (-DVCT_LOCKSTEP=1; round 3): the three diffuse cones of a wave marched in lockstep -- one
-// table entry, one set of level constants per step for all three, three independent dependency chains.  Same bits.
-// Result on MI355X: see profiles/experiments/README.md (the per-step work that is shared is scalar -- the table load
-// and ~8 SALU of loop control -- while every vector instruction of a step depends on the cone's own position; the
-// carried state triples: three accumulator sets + three directions).
-#ifndef VCT_LOCKSTEP
-#define VCT_LOCKSTEP 0
-#endif
-struct ConeAcc { float cr, cg, cb, alpha, occ; int steps; };
-template <bool WRAP, int FASTDIV, bool COOP>
-__device__ __forceinline__ void cone_march3(const VctTraceParams& p, bool alive, F3 start, const F3 dirs[3],
-                                            const VctStep* tab_global, int n, float4* __restrict__ blk,
-                                            const LaneBlock& lb, ConeAcc out[3], MarchStats& ms) {
-    constexpr bool ANISO = false, CELLS = false, PRIO = false;
-    const StepTable tab = (StepTable)tab_global;
-    AnisoCone ac = {0.0f, 0.0f, 0.0f, false, false, false};
-    ConeAcc c0 = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0}, c1 = c0, c2 = c0;
-    const unsigned long long alive_mask = ballot64(alive);
-    auto one = [&](const VctStep& st, const F3 dir, ConeAcc& c) -> bool {
-        float cr = c.cr, cg = c.cg, cb = c.cb, alpha = c.alpha, occ = c.occ;
-        int steps = c.steps;
-        const bool act = alive && (alpha < p.max_alpha);
-        const unsigned long long live = ballot64(alpha < p.max_alpha) & alive_mask;
-        if (live == 0ull) return false;
-        if (VCT_STATS) { ++ms.wave_steps; ms.lane_steps += (uint32_t)__popcll(live); }
-        VCT_MARCH_STEP(st, act, live)
-        c.cr = cr; c.cg = cg; c.cb = cb; c.alpha = alpha; c.occ = occ; c.steps = steps;
-        return true;
-    };
-    VctStep nxt = load_step(tab, 0);
-    for (int k = 0; k < n; ++k) {
-        const VctStep st = nxt;
-        nxt = load_step(tab, k + 1 < n ? k + 1 : k);
-        const bool a = one(st, dirs[0], c0);
-        const bool b = one(st, dirs[1], c1);
-        const bool c = one(st, dirs[2], c2);
-        if (!(a || b || c)) break;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2;
-}
-
 __device__ __forceinline__ uint32_t pack_half2(float a, float b) {
     const __half ha = __float2half_rn(a), hb = __float2half_rn(b);
     return (uint32_t)__half_as_ushort(ha) | ((uint32_t)__half_as_ushort(hb) << 16);
@@ -1086,28 +678,18 @@ __constant__ float kConeDirs[18] = {0.0f, 0.0f, 1.0f,
                                     -0.823639f, 0.267617f, 0.5f};            // trace.fs:49-57
 __constant__ float kConeWeights[6] = {0.25f, 0.15f, 0.15f, 0.15f, 0.15f, 0.15f};   // trace.fs:48
 
-#ifndef VCT_XCD_MAP
-#define VCT_XCD_MAP 16   // measured: 0 (round-robin) 0.764 ms, 1 (contiguous) 0.797, 16: 0.756, 60: 0.779, 240: 0.758
-#endif
 // Workgroups are dealt to XCDs round-robin by the dispatcher (block b -> XCD b % 8); the tile order is
 // remapped so that every XCD works on short runs of neighbouring tiles (neighbouring tiles march
 // through neighbouring voxels and share that XCD's L2) while the runs of all XCDs interleave over
 // the frame -- one long contiguous run per XCD loses more to imbalance between cheap and expensive
-// screen regions than it gains in locality (profiles/r01h_ab_xcd_map.txt).
+// screen regions than it gains in locality (profiles/r01h_ab_xcd_map.txt).  Run length measured: none
+// (round-robin) 0.764 ms, one contiguous run per XCD 0.797, 16: 0.756, 60: 0.779, 240: 0.758.
 __device__ __forceinline__ int xcd_remap(int b, int nblocks) {
-#if VCT_XCD_MAP == 0
-    (void)nblocks;
-    return b;                                                    // tiles dealt round-robin to the XCDs
-#elif VCT_XCD_MAP == 1
-    const int per_xcd = nblocks >> 3;                            // one contiguous run of tiles per XCD
-    return (b & 7) * per_xcd + (b >> 3);
-#else
-    // runs of VCT_XCD_MAP consecutive blocks per XCD: a permutation inside every full group of
+    // runs of 16 consecutive blocks per XCD: a permutation inside every full group of
     // 8*run blocks; the last partial group keeps identity
-    const int run = VCT_XCD_MAP, group = 8 * run;
+    const int run = 16, group = 8 * run;
     const int g = b / group, local = b - g * group;
     return (g + 1) * group <= nblocks ? g * group + (local & 7) * run + (local >> 3) : b;
-#endif
 }
 
 // tiles (waves) per workgroup: single-wave workgroups dispatch with the finest granularity, which
@@ -1129,17 +711,12 @@ template <bool WRAP, int FASTDIV, bool COOP>
 __global__ void __launch_bounds__(64 * VCT_WAVES_PER_BLOCK, VCT_TRACE_MIN_WAVES)
 k_trace_tile(const VctTraceParams p) {
     __shared__ float4 lds_blk[VCT_WAVES_PER_BLOCK][2][64];
-    VCT_LUT_DECL
     const int lane = threadIdx.x & 63;
     // wave-uniform by construction; readfirstlane tells the compiler, so tile indices, the tile's
     // G-buffer base and the LDS slab base live in SGPRs
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     float4* blk = &lds_blk[wave][0][0];
     LaneBlock lb;
-    VCT_LUT_FILL(lb)
-#if VCT_LUT
-    __syncthreads();
-#endif
 
     const int ntiles = (p.tile_row1 - p.tile_row0) * p.tiles_x;
     const int vb = xcd_remap((int)blockIdx.x, (int)gridDim.x);
@@ -1313,14 +890,7 @@ k_trace_tile_split(const VctTraceParams p) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     float4* blk = &lds_blk[wave][0][0];
-    VCT_LUT_DECL
     LaneBlock lb;
-    VCT_LUT_FILL(lb)
-#if VCT_LANE_SPREAD_LUT == 2
-    __shared__ uint32_t lds_spread[1024];
-    for (uint32_t i_ = threadIdx.x; i_ < 1024u; i_ += blockDim.x) lds_spread[i_] = p.spread_lut[i_];
-    lb.lut_lds = (const __attribute__((address_space(3))) uint32_t*)lds_spread;
-#endif
     if (threadIdx.x == 0) { lds_done = 0; lds_steps = 0; }
     __syncthreads();
 
@@ -1389,31 +959,6 @@ k_trace_tile_split(const VctTraceParams p) {
             k2 = f3(c2.x * inv_det, c2.y * inv_det, c2.z * inv_det);
             start = f3(P.x + Nw.x * p.vs, P.y + Nw.y * p.vs, P.z + Nw.z * p.vs);       // :92
         }
-#if VCT_LOCKSTEP && VCT_SPLIT == 3
-        if (!ANISO) {
-            F3 dirs[3];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const int i = wave * 3 + j;
-                const float ddx = kConeDirs[3 * i], ddy = kConeDirs[3 * i + 1], ddz = kConeDirs[3 * i + 2];
-                dirs[j] = normalize3(f3(k0.x * ddx + k1.x * ddy + k2.x * ddz, k0.y * ddx + k1.y * ddy + k2.y * ddz,
-                                        k0.z * ddx + k1.z * ddy + k2.z * ddz));
-            }
-            ConeAcc acc3[3];
-            cone_march3<WRAP, FASTDIV, true>(p, alive, start, dirs, p.steps_diffuse, n_diffuse, blk, lb, acc3, ms);
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const int i = wave * 3 + j;
-                total += acc3[j].steps;
-                lds_cone[i][lane] = make_float4(acc3[j].cr, acc3[j].cg, acc3[j].cb, acc3[j].occ);
-                if (p.dbg_cones && alive) {
-                    float* d = p.dbg_cones + pixel_index(fresh_lane()) * 28 + 4 * i;
-                    d[0] = acc3[j].cr; d[1] = acc3[j].cg; d[2] = acc3[j].cb; d[3] = acc3[j].occ;
-                }
-                if (p.dbg_steps && in_frame) p.dbg_steps[pixel_index(fresh_lane()) * 7 + i] = (uint8_t)acc3[j].steps;
-            }
-        } else
-#endif
 #pragma unroll 1
         for (int i = wave * VCT_CONES_PER_WAVE; i < wave * VCT_CONES_PER_WAVE + VCT_CONES_PER_WAVE; ++i) {      // :196-199
             const float ddx = kConeDirs[3 * i], ddy = kConeDirs[3 * i + 1], ddz = kConeDirs[3 * i + 2];
@@ -1626,10 +1171,7 @@ __device__ __forceinline__ void bounce_voxels(const VctTraceParams& p, bool aliv
     const int lane = threadIdx.x & 63;                                       \
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); \
     float4* blk = &lds_blk[wave][0][0];                                      \
-    VCT_LUT_DECL                                                             \
     LaneBlock lb;                                                            \
-    VCT_LUT_FILL(lb)                                                         \
-    if (VCT_LUT) __syncthreads();                                            \
     lb.lane = lane;                                                          \
     lb.lut = (SpreadLut)p.spread_lut; lb.lut_vec = p.spread_lut;                                        \
     lb.sbx = vct_spread3((uint32_t)lane & 3u);                               \
@@ -1842,9 +1384,9 @@ template <bool WRAP, int FASTDIV, bool COMP>
 void launch_split(const VctTraceParams& p, int blocks, hipStream_t s) {
     if (p.aniso)
         hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, true, false, false, false, COMP>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
-    else if (VCT_CELLS && WRAP && p.cells_biased)
+    else if (WRAP && p.cells_biased)
         hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, true, false, COMP>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
-    else if (VCT_LOAD_PRIO && !p.spec_prio)     // a whole frame (or most of one): issue priority around the samples' loads (sample_level)
+    else if (!p.spec_prio)     // a whole frame (or most of one): issue priority around the samples' loads (sample_level)
         hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, true, COMP>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
     else hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, false, COMP>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
 }

@@ -113,9 +113,6 @@ __device__ __forceinline__ int pcf25(const uint32_t* __restrict__ words, uint32_
         // a window.
         if (tiles) {
             const int v = vct_pcf_tile_verdict(tiles, S, col0, row0, cur);
-#if defined(VCT_PROBE_TILE_ALWAYS)
-            return v >= 0 ? v : 12;          // timing probe only (wrong results): every window decided by the tiles
-#endif
             if (v >= 0) return v;
         }
         // One pass over the window: decode in place and take the smallest / largest decoded word on the way (the decode is
@@ -336,13 +333,10 @@ struct PassTri {
     float alb[3];
     uint32_t nrm[3];    // biased quantised face normal (voxel attributes)
 };
-#ifndef VCT_VOX_PREFETCH
-#define VCT_VOX_PREFETCH 0     // EXPERIMENT (round 5): the next fragment's triangle requested one iteration ahead (list entry two ahead)
-#endif
 template <bool ATTR, bool FALB>
-__device__ __forceinline__ void setup_pass(const VctVoxParams& p, int t, PassTri& r, const VctTri9* pre = nullptr) {
+__device__ __forceinline__ void setup_pass(const VctVoxParams& p, int t, PassTri& r) {
     if (p.shadow) {
-        const VctTri9 rec = pre ? *pre : *reinterpret_cast<const VctTri9*>(p.pos + (size_t)t * 9);     // three wide loads, not nine
+        const VctTri9 rec = *reinterpret_cast<const VctTri9*>(p.pos + (size_t)t * 9);     // three wide loads, not nine
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const float* q = rec.v + 3 * k;
@@ -637,14 +631,6 @@ k_voxelize_bricks(const VctVoxParams p) {
             bb = p.frag_bary[first + f];
             if (FALB) fa = falb[first + f];
         }
-#if VCT_VOX_PREFETCH
-        // two list entries and one triangle ahead: the triangle fetch (dependent on the list entry) leaves the chain of
-        // dependent round trips of an iteration, which is then the PCF window alone
-        uint32_t e1 = 0u;
-        if (f + blockDim.x < n) e1 = p.frag_sorted[first + f + blockDim.x];
-        VctTri9 rec = {};
-        if (p.shadow && f < n) rec = *reinterpret_cast<const VctTri9*>(p.pos + (size_t)(e >> 9) * 9);
-#endif
         for (uint32_t v = threadIdx.x; v < 512u * 2u; v += blockDim.x) acc[v] = 0ull;
         if (ATTR) for (uint32_t v = threadIdx.x; v < 512u * 3u; v += blockDim.x) acc_attr[v] = 0ull;
         __syncthreads();
@@ -653,30 +639,14 @@ k_voxelize_bricks(const VctVoxParams p) {
             uint32_t e_next = 0u;
             float2 bb_next = bb;
             VctF3 fa_next = fa;
-#if VCT_VOX_PREFETCH
-            e_next = e1;
-            uint32_t e2 = 0u;
-            if (fn + blockDim.x < n) e2 = p.frag_sorted[first + fn + blockDim.x];
-            VctTri9 rec_next = rec;
-            if (fn < n) {
-                if (p.shadow) rec_next = *reinterpret_cast<const VctTri9*>(p.pos + (size_t)(e_next >> 9) * 9);
-                bb_next = p.frag_bary[first + fn];
-                if (FALB) fa_next = falb[first + fn];
-            }
-#else
             if (fn < n) {
                 e_next = p.frag_sorted[first + fn];
                 bb_next = p.frag_bary[first + fn];
                 if (FALB) fa_next = falb[first + fn];
             }
-#endif
             const uint32_t local = e & 511u;
             PassTri r;
-#if VCT_VOX_PREFETCH
-            setup_pass<ATTR, FALB>(p, (int)(e >> 9), r, &rec);
-#else
             setup_pass<ATTR, FALB>(p, (int)(e >> 9), r);
-#endif
             const FragValue fv = frag_eval(p, r, bb.x, bb.y, FALB ? fa.v : r.alb);
             atomicAdd(&acc[2 * local], (unsigned long long)fv.r | ((unsigned long long)fv.g << 32));       // ds_add_u64
             atomicAdd(&acc[2 * local + 1], (unsigned long long)fv.b | (1ull << 32));
@@ -686,9 +656,6 @@ k_voxelize_bricks(const VctVoxParams p) {
                 atomicAdd(&acc_attr[3 * local + 2], (unsigned long long)r.nrm[1] | ((unsigned long long)r.nrm[2] << 32));
             }
             f = fn; e = e_next; bb = bb_next; fa = fa_next;
-#if VCT_VOX_PREFETCH
-            e1 = e2; rec = rec_next;
-#endif
         }
         __syncthreads();
         if (mi == 0xffffffffu) {

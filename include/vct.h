@@ -435,12 +435,14 @@ int vct_last_step_count(vct_ctx* ctx, uint64_t* steps);
  * blocks, [11..15] reserved. */
 int vct_last_trace_stats(vct_ctx* ctx, uint64_t out[16]);
 /* Work-item counts behind the per-stage byte figures of bench.py (`stage_roofline`): [0] triangles uploaded,
- * [1] conservative fragments of the mesh at this grid size (the voxelizer's brick-sorted list), [2] reserved,
- * [3] brick slots = 8^3 bricks a fragment of the mesh can land in, [4] bricks level 0 shows after the last
- * resolve, [5] compute units reserved for the communication stream (VCT_COMM_RESERVED_CUS; 0 = none), [6] form of the
- * last main-draw visibility pass (0 none yet, 1 direct, 2 tile-binned: chosen per context by timing),
- * [7] work items of the voxelize pass (brick slots, the heavy ones cut into chunks of 4096 fragments).  Synchronises
- * the stream. */
+ * [1] conservative fragments of the mesh at this grid size (the voxelizer's brick-sorted list), [2] division form of
+ * the last march launch (screen trace, slab, frame step or bounce): 0 none yet, 1 the IEEE divide, 2 the verified
+ * two-term product (every divisor of the step tables is in the shipped table or passed the device check, 1 - max_alpha
+ * >= 2^-5, every two-level blend fraction in [2^-10, 1 - 2^-10]), 3 trace_variant 3's x * r, [3] brick slots =
+ * 8^3 bricks a fragment of the mesh can land in, [4] bricks level 0 shows after the last resolve, [5] compute
+ * units reserved for the communication stream (VCT_COMM_RESERVED_CUS; 0 = none), [6] form of the last main-draw
+ * visibility pass (0 none yet, 1 direct, 2 tile-binned: chosen per context by timing), [7] work items
+ * of the voxelize pass (brick slots, the heavy ones cut into chunks of 4096 fragments).  Synchronises the stream. */
 int vct_get_stage_counts(vct_ctx* ctx, uint64_t out[8]);
 /* Device time of the last trace kernel launch in milliseconds (HIP events on the ctx stream). */
 int vct_last_trace_ms(vct_ctx* ctx, float* ms);

@@ -307,16 +307,17 @@ int vcto_max_steps(const vcto_params* p, float tan_half, float* last_lod) {
 }  // extern "C" (reopened below)
 
 namespace {
+// steps: the per-cone counts as cone_trace returns them (a cone may take more than 255 steps)
 int shade_pixel(const vcto_params* p, const uint8_t* chain, const uint8_t* aniso, const float gb[23],
-                float out[4], uint8_t steps[7], float cones[28]) {
+                float out[4], int steps[7], float cones[28]) {
     const float* alb = gb + VCTO_GB_ALBEDO;
-    uint8_t st[7] = {0, 0, 0, 0, 0, 0, 0};
+    int st[7] = {0, 0, 0, 0, 0, 0, 0};
     float cn[28];
     memset(cn, 0, sizeof(cn));
     if (alb[3] < 0.5f) {                                       // trace.fs:171 discard
         const float c = p->ambient_factor < 0.5f ? 0.5f : 1.0f;   // VCT.h:156-159
         out[0] = c; out[1] = c; out[2] = c; out[3] = 1.0f;
-        if (steps) memcpy(steps, st, 7);
+        if (steps) memcpy(steps, st, sizeof(st));
         if (cones) memcpy(cones, cn, sizeof(cn));
         return 0;
     }
@@ -344,7 +345,7 @@ int shade_pixel(const vcto_params* p, const uint8_t* chain, const uint8_t* aniso
                   k0.z * d[0] + k1.z * d[1] + k2.z * d[2]};
         dir = normalize(dir);
         float c[4];
-        st[i] = (uint8_t)cone_trace(p, chain, P, Nw, dir, p->tan_diffuse, c, aniso);
+        st[i] = cone_trace(p, chain, P, Nw, dir, p->tan_diffuse, c, aniso);
         for (int ch = 0; ch < 4; ++ch) {
             cn[4 * i + ch] = c[ch];
             ind[ch] = fmaf(kConeWeights[i], c[ch], ind[ch]);
@@ -361,7 +362,7 @@ int shade_pixel(const vcto_params* p, const uint8_t* chain, const uint8_t* aniso
     const float direct_spec = spec * shadow;                               // :214
     const V3 Rd = normalize(reflect(mul(E, -1.0f), N));                    // :217
     float s[4];
-    st[6] = (uint8_t)cone_trace(p, chain, P, Nw, Rd, p->tan_specular, s, aniso);  // :218
+    st[6] = cone_trace(p, chain, P, Nw, Rd, p->tan_specular, s, aniso);  // :218
     for (int ch = 0; ch < 4; ++ch) cn[24 + ch] = s[ch];
     const float spec_occ = 1.0f - s[3];                                    // :221
     const float sr = (s[0] + spec_occ * direct_spec) * sc[0];              // :223
@@ -376,17 +377,23 @@ int shade_pixel(const vcto_params* p, const uint8_t* chain, const uint8_t* aniso
     out[1] = ag + dg + sg;
     out[2] = ab + db + sb;
     out[3] = alb[3];
-    if (steps) memcpy(steps, st, 7);
+    if (steps) memcpy(steps, st, sizeof(st));
     if (cones) memcpy(cones, cn, sizeof(cn));
     return 1;
 }
+// the per-cone byte counts of the outputs saturate at 255 (the GPU's debug outputs refuse tables that long); totals add
+// up the full counts
+uint8_t sat_u8(int n) { return (uint8_t)(n > 255 ? 255 : n); }
 }  // namespace
 
 extern "C" {
 
 int vcto_shade_pixel(const vcto_params* p, const uint8_t* chain, const float gb[23], float out[4],
                      uint8_t steps[7], float cones[28]) {
-    return shade_pixel(p, chain, nullptr, gb, out, steps, cones);
+    int st[7];
+    const int r = shade_pixel(p, chain, nullptr, gb, out, st, cones);
+    if (steps) for (int k = 0; k < 7; ++k) steps[k] = sat_u8(st[k]);
+    return r;
 }
 
 uint16_t vcto_f32_to_f16(float f) {
@@ -437,13 +444,13 @@ uint64_t vcto_trace_aniso(const vcto_params* p, const uint8_t* chain, const uint
         uint64_t t = 0;
         for (size_t i = lo; i < hi; ++i) {
             float gb[23], o[4], cn[28];
-            uint8_t st[7];
+            int st[7];
             for (int k = 0; k < 23; ++k) gb[k] = planes[(size_t)k * npix + i];
             shade_pixel(p, chain, aniso, gb, o, st, cn);
-            for (int k = 0; k < 7; ++k) t += st[k];
+            for (int k = 0; k < 7; ++k) t += (uint64_t)st[k];
             if (out32f) memcpy(out32f + 4 * i, o, 16);
             if (out16f) for (int k = 0; k < 4; ++k) out16f[4 * i + k] = vcto_f32_to_f16(o[k]);
-            if (steps) memcpy(steps + 7 * i, st, 7);
+            if (steps) for (int k = 0; k < 7; ++k) steps[7 * i + k] = sat_u8(st[k]);
             if (cones) memcpy(cones + 28 * i, cn, sizeof(cn));
         }
         *total = t;

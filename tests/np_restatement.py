@@ -82,3 +82,16 @@ def cone(levels, V, G, P, Nw, d, tan_half, max_distance=75.0, max_alpha=0.95):
         dist = dist + diam
         steps += 1
     return np.concatenate([col, [occ]]).astype(f32), steps
+
+
+def max_steps(V, G, tan_half, max_distance):
+    """Steps of a cone that nothing stops before max_distance (the loop of trace.fs:94-104 without the alpha test), in
+    fp32 scalars.  Returns (steps, lod of the last step)."""
+    vs = f32(G) / f32(V)
+    dist, lod, steps = vs, f32(0), 0
+    while dist < f32(max_distance):
+        diam = max(vs, f32(2.0) * f32(tan_half) * dist)
+        lod = np.log2(diam / vs, dtype=f32)
+        dist = f32(dist + diam)
+        steps += 1
+    return steps, float(lod)

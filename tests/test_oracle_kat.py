@@ -406,3 +406,84 @@ def test_zslab_voxelization_equals_the_slices_of_the_whole_volume():
     assert (full[..., 3] > 0).sum() > 500
     for z0, z1 in ((0, 32), (0, 7), (9, 20), (31, 32)):
         assert np.array_equal(pyoracle.voxelize_conservative_zslab(p, sc, z0, z1), full[z0:z1])
+
+
+# Non-default march constants (vct_config fields / setters; the reference hard-codes them in trace.fs:43-44,198,218 and
+# VCT.h:17): grid size, distance limit, opacity limit and apertures, each at the values where the step table changes
+# shape -- no step (max_distance <= G/V), one step, cones that leave the grid several times (4 G), no march at all
+# (max_alpha 0), only distance ends a cone (1.0), blend fractions just above 0 (0.5 (1 + 2^-11)), integer LODs (0.5),
+# the top level within a few steps (2.0), long tables of small steps (0.01).
+MARCH_G = [100.0, 37.5, 600.0]
+MARCH_APERTURES = [0.5, 0.5 * (1 + 2.0 ** -11), 2.0, 0.01]
+MARCH_ALPHAS = [0.0, 0.5, 0.97, 1.0]
+
+
+def march_distances(G, V):
+    vs = np.float32(G) / np.float32(V)
+    return [float(vs), float(np.nextafter(vs, np.float32(np.inf))), 4.0 * G]
+
+
+@pytest.mark.parametrize("G", MARCH_G)
+@pytest.mark.parametrize("tan", MARCH_APERTURES)
+def test_max_steps_against_restatement_across_constants(oracle, G, tan):
+    V = 16
+    for md in march_distances(G, V) + [G * 0.5, 75.0]:
+        p = oracle.default_params(V, G=G, max_distance=md)
+        n, lod = oracle.max_steps(p, tan)
+        want_n, want_lod = npr.max_steps(V, G, tan, md)
+        assert n == want_n, (md, n, want_n)
+        assert abs(lod - want_lod) <= 1e-6 * max(1.0, abs(want_lod))
+    p = oracle.default_params(V, G=G, max_distance=march_distances(G, V)[0])
+    assert oracle.max_steps(p, tan)[0] == 0                     # dist = G/V is not < max_distance
+    p = oracle.default_params(V, G=G, max_distance=march_distances(G, V)[1])
+    assert oracle.max_steps(p, tan)[0] == 1
+
+
+@pytest.mark.parametrize("G", MARCH_G)
+@pytest.mark.parametrize("tan", MARCH_APERTURES)
+def test_against_numpy_restatement_across_constants(oracle, G, tan):
+    """The oracle's cone (C++, fma) against the numpy restatement (lerps, no fma) away from the reference's constants,
+    GL_REPEAT: same step counts for almost all cones, and the same vec4 within 2e-5 where they agree."""
+    V = 16
+    chain = oracle.build_mips(synth.noise_volume(V, seed=3, occupancy=0.1))
+    levels = npr.levels_from_chain(chain, V)
+    r = np.random.default_rng(int(G * 8) + int(tan * 1e4))
+    n = equal = 0
+    for md in march_distances(G, V):
+        for ma in MARCH_ALPHAS:
+            p = oracle.default_params(V, G=G, max_distance=md, max_alpha=ma)
+            for _ in range(4):
+                P = r.uniform(-0.6 * G, 0.6 * G, 3).astype(np.float32)   # some outside the grid (wrap)
+                nw = r.normal(size=3)
+                nw = (nw / np.linalg.norm(nw)).astype(np.float32)
+                d = r.normal(size=3)
+                d = (d / np.linalg.norm(d)).astype(np.float32)
+                a, sa = oracle.cone(p, chain, P, nw * np.float32(0.05), d, tan)
+                b, sb = npr.cone(levels, V, G, P, nw * np.float32(0.05), d, tan, max_distance=md, max_alpha=ma)
+                n += 1
+                if ma == 0.0 or md == march_distances(G, V)[0]:
+                    assert sa == sb == 0 and not a.any()
+                if sa == sb:
+                    equal += 1
+                    assert np.abs(a - b).max() < 2e-5, (md, ma, sa)
+                assert sa <= oracle.max_steps(p, tan)[0]
+    assert equal >= n - 1, (equal, n)
+
+
+def test_trace_total_counts_cones_longer_than_255_steps(oracle):
+    """vcto_trace's total adds up the full per-cone counts; the per-cone bytes saturate at 255."""
+    V = 16
+    chain = uniform_chain(oracle, V, (0, 0, 0, 0))              # nothing stops a cone before max_distance
+    p = oracle.default_params(V, max_distance=3000.0, tan_specular=0.001)
+    nd, _ = oracle.max_steps(p, p.tan_diffuse)
+    ns, _ = oracle.max_steps(p, p.tan_specular)
+    assert ns > 255 > nd
+    g = frame(3)
+    g[0:3] = np.array([[1.0, -3.0, 20.0], [2.0, 2.5, -7.0], [3.0, 9.0, 1.0]])
+    g[18, 2] = 0.0                                               # one discarded pixel: no cones
+    r = oracle.trace(p, chain, g, nthreads=2)
+    assert r["total_steps"] == 2 * (6 * nd + ns)
+    assert np.all(r["steps"][:2, :6] == nd) and np.all(r["steps"][:2, 6] == 255)
+    assert not r["steps"][2].any()
+    a, sa = oracle.cone(p, chain, g[0:3, 0], g[3:6, 0], np.array([0, 1, 0], np.float32), p.tan_specular)
+    assert sa == ns and not a.any()

@@ -217,6 +217,12 @@ class Context:
         self.cfg = Config()
         _lib.vct_get_config(self._h, C.byref(self.cfg))
 
+    def current_config(self):
+        """The configuration as the setters have left it (`cfg` is the one the context was created with)."""
+        cfg = Config()
+        self._ck(_lib.vct_get_config(self._h, C.byref(cfg)), "vct_get_config")
+        return cfg
+
     def close(self):
         if self._h:
             _lib.vct_destroy(self._h)
@@ -571,7 +577,7 @@ class Context:
     def stage_counts(self):
         v = (C.c_uint64 * 8)()
         self._ck(_lib.vct_get_stage_counts(self._h, v), "vct_get_stage_counts")
-        return dict(zip(("triangles", "vox_candidates", "reserved", "accumulator_bricks", "touched_bricks",
+        return dict(zip(("triangles", "vox_candidates", "march_division", "accumulator_bricks", "touched_bricks",
                          "comm_reserved_cus", "raster_form", "vox_items"), (int(x) for x in v)))
 
     def set_trace_timing(self, on=True):

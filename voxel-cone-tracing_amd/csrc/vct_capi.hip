@@ -420,6 +420,7 @@ int launch_trace(vct_ctx* c, int row0, int row1, uint16_t* out_base = nullptr, i
     HIP_TRY(c, vct_launch_trace(p, variant, c->stream));       // an empty row range (a rank without rows) launches nothing
     if (c->time_traces) HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
     c->last_trace_timed = c->time_traces;
+    c->last_march_form = (variant == 3 && !p.aniso) ? 3 : (c->fast_div ? 2 : 1);      // (vct_launch_trace's dispatch)
     c->last_row0 = row0;
     c->last_row1 = row1;
     c->last_row_stride = row_stride > 1 ? row_stride : 1;
@@ -725,6 +726,11 @@ int vct_create(const vct_config* cfg, vct_ctx** out) {
         return fail(nullptr, VCT_ERR_INVALID, "voxel_dim must be a power of two in [8,1024]");
     if (cfg->width <= 0 || cfg->height <= 0 || !(cfg->grid_world_size > 0.0f))
         return fail(nullptr, VCT_ERR_INVALID, "bad frame size or grid size");
+    // the checks of the setters (vct_set_cone_apertures, vct_set_trace_variant) for the same fields
+    if (!(cfg->tan_diffuse > 0.0f) || !(cfg->tan_specular > 0.0f))
+        return fail(nullptr, VCT_ERR_INVALID, "aperture must be > 0");
+    if (cfg->trace_variant < 0 || cfg->trace_variant > 4)
+        return fail(nullptr, VCT_ERR_INVALID, "trace_variant: 0 .. 4");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(nullptr, VCT_ERR_NO_DEVICE,
@@ -1624,6 +1630,7 @@ int vct_bounce(vct_ctx* c) {
     HIP_TRY(c, vct_launch_bounce(p, c->stream));
     if (c->time_traces) HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
     c->last_trace_timed = c->time_traces;
+    c->last_march_form = c->fast_div ? 2 : 1;
     HIP_TRY(c, vct_launch_build_mips(c->chain_b, c->cfg.voxel_dim, b_sparse ? c->brick_prev : nullptr,
                                      b_sparse ? c->mip_seen_b : nullptr, c->stream));
     // the directional chains always describe the chain the trace reads (the bounce itself gathers
@@ -2091,7 +2098,7 @@ int vct_get_stage_counts(vct_ctx* c, uint64_t out[8]) {
     memset(out, 0, 8 * sizeof(uint64_t));
     out[0] = (uint64_t)c->ntri;
     out[1] = c->n_frags;
-    out[2] = 0;
+    out[2] = (uint64_t)c->last_march_form;       // division form of the last march launch: 0 none, 1 IEEE, 2 product, 3 x * r
     out[3] = c->nslots;
     out[5] = (uint64_t)c->reserved_cus;          // compute units kept for the communication stream (VCT_COMM_RESERVED_CUS)
     out[6] = (uint64_t)c->last_raster_form;      // visibility form of the last main-draw pass: 1 direct, 2 tile-binned

@@ -84,6 +84,7 @@ struct vct_ctx {
     int n_diffuse = 0, n_specular = 0;
     bool steps_dirty = true;
     bool fast_div = false;            // set by refresh_steps: constant divisors admit the FMA division
+    int last_march_form = 0;          // division of the last march launch: 1 IEEE, 2 verified product, 3 x * r (vct_get_stage_counts [2])
     int last_row0 = 0, last_row1 = 0;
     int last_row_stride = 1;          // the last screen trace took every last_row_stride-th tile row of [last_row0, last_row1)
     bool have_trace = false;

@@ -408,17 +408,25 @@ def test_rank_context_with_two_frames_in_flight(vct):
 
 
 def test_second_slot_is_released(vct):
-    """Enabling and disabling the second slot leaves no memory behind (190 MB per 1080p slot would add up)."""
+    """Enabling and disabling the second slot leaves no memory behind (190 MB per 1080p slot would add up), its raster
+    scratch included: every second slot rasterises a G-buffer before it goes."""
     import torch
     ctx, sc = make(vct, 1920, 1080, 32)
+    vp = cameras(sc, 1920, 1080, 1)[0][1]
+    ctx.render_shadow_map(sc.light_view_proj((0.0, 1.0, 0.25)))
+    ctx.render_gbuffer(vp)                           # shared state (shadow map, alpha classes) exists before the baseline
     torch.cuda.synchronize()
     free0 = torch.cuda.mem_get_info()[0]
     for _ in range(3):
         ctx.set_frames_in_flight(2)
         assert free0 - torch.cuda.mem_get_info()[0] > 150 << 20
+        ctx.select_frame_slot(1)
+        ctx.render_gbuffer(vp)                       # allocates slot 1's raster scratch
         ctx.set_frames_in_flight(1)
     assert abs(free0 - torch.cuda.mem_get_info()[0]) < 8 << 20
     ctx.set_frames_in_flight(2)
+    ctx.select_frame_slot(1)
+    ctx.render_gbuffer(vp)
     ctx.close()                                      # destroy with the second slot alive
     torch.cuda.synchronize()
     assert torch.cuda.mem_get_info()[0] >= free0 - (8 << 20)

@@ -157,11 +157,11 @@ int divisor_verified(vct_ctx* c, float d, bool* ok) {
         auto it = cache.find(bits);
         if (it != cache.end()) { *ok = it->second; return VCT_OK; }
     }
-    HIP_TRY(c, hipMemsetAsync(c->stats, 0, 2 * sizeof(unsigned long long), c->stream));
-    HIP_TRY(c, vct_launch_divide_selftest(d, c->stats, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->stats, 0, 2 * sizeof(unsigned long long), cur(c).stream));
+    HIP_TRY(c, vct_launch_divide_selftest(d, c->stats, cur(c).stream));
     unsigned long long bad = 1;
-    HIP_TRY(c, hipMemcpyAsync(&bad, c->stats, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&bad, c->stats, sizeof(bad), hipMemcpyDeviceToHost, cur(c).stream));
+    HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     *ok = bad == 0ull;
     std::lock_guard<std::mutex> g(cache_lock);
     cache[bits] = *ok;
@@ -223,30 +223,14 @@ int create_overlapping_stream(vct_ctx* c, hipStream_t base, hipStream_t* out, bo
     return rc;
 }
 
-void slot_save(const vct_ctx* c, VctFrameSlot& s) {
-    s.stream = c->stream; s.ev0 = c->ev0; s.ev1 = c->ev1;
-    s.gb_tiled = c->gb_tiled; s.gb_current = c->gb_current; s.frame = c->frame; s.frame_target = c->frame_target;
-    s.tile_steps = c->tile_steps; s.aov = c->aov;
-    s.last_row0 = c->last_row0; s.last_row1 = c->last_row1; s.last_row_stride = c->last_row_stride;
-    s.have_trace = c->have_trace; s.last_trace_compacted = c->last_trace_compacted; s.last_trace_timed = c->last_trace_timed;
-    s.last_was_screen_trace = c->last_was_screen_trace; s.have_gbuffer = c->have_gbuffer;
-}
-void slot_load(vct_ctx* c, const VctFrameSlot& s) {
-    c->stream = s.stream; c->ev0 = s.ev0; c->ev1 = s.ev1;
-    c->gb_tiled = s.gb_tiled; c->gb_current = s.gb_current; c->frame = s.frame; c->frame_target = s.frame_target;
-    c->tile_steps = s.tile_steps; c->aov = s.aov;
-    c->last_row0 = s.last_row0; c->last_row1 = s.last_row1; c->last_row_stride = s.last_row_stride;
-    c->have_trace = s.have_trace; c->last_trace_compacted = s.last_trace_compacted; c->last_trace_timed = s.last_trace_timed;
-    c->last_was_screen_trace = s.last_was_screen_trace; c->have_gbuffer = s.have_gbuffer;
-}
 // A stage that WRITES state both slots read (shadow map, chain, accumulators): on the GPU it waits for everything the
 // other slot has in flight, and the next slot switch makes the other stream wait for it (produced_since_switch).
 int pipeline_join(vct_ctx* c) {
     if (c->frames_in_flight < 2) return VCT_OK;
     c->produced_since_switch = true;
     if (c->joined_since_switch) return VCT_OK;      // (vct_ctx.h: nothing new can be on the other stream)
-    HIP_TRY(c, hipEventRecord(c->ev_xslot, c->slots[1 - c->cur_slot].stream));
-    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_xslot, 0));
+    HIP_TRY(c, hipEventRecord(c->ev_xslot, other(c).stream));
+    HIP_TRY(c, hipStreamWaitEvent(cur(c).stream, c->ev_xslot, 0));
     c->joined_since_switch = true;
     return VCT_OK;
 }
@@ -255,7 +239,7 @@ int pipeline_drain(vct_ctx* c) {
     if (c->frames_in_flight < 2) return VCT_OK;
     c->produced_since_switch = true;
     if (c->drained_since_switch) return VCT_OK;
-    HIP_TRY(c, hipStreamSynchronize(c->slots[1 - c->cur_slot].stream));
+    HIP_TRY(c, hipStreamSynchronize(other(c).stream));
     c->drained_since_switch = c->joined_since_switch = true;      // (a finished stream needs no GPU-side wait either)
     return VCT_OK;
 }
@@ -302,10 +286,10 @@ int refresh_steps(vct_ctx* c) {
         for (VctStep& st : s) st.occ_den = vct_div_aux(st.occ_den, st.occ_rcp);
     }
     HIP_TRY(c, hipMemcpyAsync(c->steps_dev, d.data(), d.size() * sizeof(VctStep),
-                              hipMemcpyHostToDevice, c->stream));
+                              hipMemcpyHostToDevice, cur(c).stream));
     HIP_TRY(c, hipMemcpyAsync(c->steps_dev + VCT_MAX_STEPS, s.data(), s.size() * sizeof(VctStep),
-                              hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));   // d, s go out of scope
+                              hipMemcpyHostToDevice, cur(c).stream));
+    HIP_TRY(c, hipStreamSynchronize(cur(c).stream));   // d, s go out of scope
     c->steps_dirty = false;
     return VCT_OK;
 }
@@ -340,7 +324,7 @@ void fill_march_params(const vct_ctx* c, VctTraceParams& p, const uint32_t* chai
     p.n_diffuse = c->n_diffuse;
     p.n_specular = c->n_specular;
     p.step_counter = c->step_counter;
-    p.tile_steps = c->tile_steps;
+    p.tile_steps = cur(c).tile_steps;
 #if defined(VCT_STATS) && VCT_STATS
     p.stats = c->stats;
 #endif
@@ -361,7 +345,7 @@ uint32_t component_word(uint32_t mask, uint32_t aov_which) {
 }
 
 // `out_base`: where the kernel writes (full-frame addressing); null = the caller's vct_set_frame_target or the
-// context-owned frame.  vct_frame_step passes its gather buffer here instead of re-pointing c->frame_target, which
+// context-owned frame.  vct_frame_step passes its gather buffer here instead of re-pointing the frame target, which
 // on a non-root rank would leave a pointer BEFORE a one-slab allocation behind for every later full-frame call.
 int launch_trace(vct_ctx* c, int row0, int row1, uint16_t* out_base = nullptr, int row_stride = 1, bool pack_rows = false) {
     // the reference rebuilds the mips right after every voxelization (VCT.h:248); tracing a chain whose
@@ -390,11 +374,11 @@ int launch_trace(vct_ctx* c, int row0, int row1, uint16_t* out_base = nullptr, i
         return fail(c, VCT_ERR_INVALID, "interleaved tile rows need the default trace kernel (config.trace_variant 0 or 3)");
     p.spec_prio = ((row1 - row0) / (row_stride > 1 ? row_stride : 1)) * 2 <= tiles_y(c) ? 1 : 0;
     const int variant = c->cfg.trace_variant;
-    p.gbuf = c->gb_current;
+    p.gbuf = cur(c).gb_current;
     p.aniso = c->cfg.anisotropic_mips ? c->aniso : nullptr;
     p.aniso_alt_slab = 128;     // k_trace_tile_split<ANISO>: slabs [level 1][level 2][-axis of 1][-axis of 2]
     p.aniso_stride = (uint32_t)(c->chain_texels - (size_t)c->cfg.voxel_dim * c->cfg.voxel_dim * c->cfg.voxel_dim);
-    p.out = out_base ? out_base : (c->frame_target ? c->frame_target : c->frame);
+    p.out = out_base ? out_base : (cur(c).frame_target ? cur(c).frame_target : cur(c).frame);
     p.dbg_steps = c->cfg.debug_outputs ? c->dbg_steps : nullptr;
     p.dbg_cones = c->cfg.debug_outputs ? c->dbg_cones : nullptr;
     // lighting components (include/vct.h): the COMP kernel only when the mask or an output asks for it.  A packed slab
@@ -404,29 +388,29 @@ int launch_trace(vct_ctx* c, int row0, int row1, uint16_t* out_base = nullptr, i
         if (variant != 0)
             return fail(c, VCT_ERR_INVALID, "lighting components / per-component outputs need the default trace kernel (config.trace_variant 0)");
         p.comp = component_word(c->show_mask, aov_which);
-        p.aov = aov_which ? c->aov : nullptr;
+        p.aov = aov_which ? cur(c).aov : nullptr;
     }
 #if defined(VCT_STATS) && VCT_STATS
-    HIP_TRY(c, hipMemsetAsync(c->stats, 0, 16 * sizeof(unsigned long long), c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->stats, 0, 16 * sizeof(unsigned long long), cur(c).stream));
 #endif
     if (variant == 4 && !c->cfg.anisotropic_mips) {       // live-pixel compaction (experiment): list + counter, zeroed per launch
         const size_t nt = (size_t)tiles_x(c) * tiles_y(c);
         if (!c->vt_pix) HIP_TRY(c, hipMalloc(&c->vt_pix, (nt * 64 + 4) * sizeof(uint32_t)));
         p.vt_pix = c->vt_pix;
         p.vt_count = c->vt_pix + nt * 64;
-        HIP_TRY(c, hipMemsetAsync(p.vt_count, 0, sizeof(uint32_t), c->stream));
+        HIP_TRY(c, hipMemsetAsync(p.vt_count, 0, sizeof(uint32_t), cur(c).stream));
     }
-    if (c->time_traces) HIP_TRY(c, hipEventRecord(c->ev0, c->stream));      // (vct_set_trace_timing)
-    HIP_TRY(c, vct_launch_trace(p, variant, c->stream));       // an empty row range (a rank without rows) launches nothing
-    if (c->time_traces) HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
-    c->last_trace_timed = c->time_traces;
+    if (c->time_traces) HIP_TRY(c, hipEventRecord(cur(c).ev0, cur(c).stream));      // (vct_set_trace_timing)
+    HIP_TRY(c, vct_launch_trace(p, variant, cur(c).stream));       // an empty row range (a rank without rows) launches nothing
+    if (c->time_traces) HIP_TRY(c, hipEventRecord(cur(c).ev1, cur(c).stream));
+    cur(c).last_trace_timed = c->time_traces;
     c->last_march_form = (variant == 3 && !p.aniso) ? 3 : (c->fast_div ? 2 : 1);      // (vct_launch_trace's dispatch)
-    c->last_row0 = row0;
-    c->last_row1 = row1;
-    c->last_row_stride = row_stride > 1 ? row_stride : 1;
-    c->have_trace = true;
-    c->last_was_screen_trace = true;
-    c->last_trace_compacted = variant == 4 && !c->cfg.anisotropic_mips;
+    cur(c).last_row0 = row0;
+    cur(c).last_row1 = row1;
+    cur(c).last_row_stride = row_stride > 1 ? row_stride : 1;
+    cur(c).have_trace = true;
+    cur(c).last_was_screen_trace = true;
+    cur(c).last_trace_compacted = variant == 4 && !c->cfg.anisotropic_mips;
     return VCT_OK;
 }
 
@@ -548,19 +532,19 @@ int build_voxel_slots(vct_ctx* c, const uint2* frags, uint32_t nfrags) {
     POOL_TRY(hipMalloc(&mark, (size_t)nbricks * sizeof(uint32_t)));
     POOL_TRY(hipMalloc(&slot, (size_t)nbricks * sizeof(uint32_t)));
     POOL_TRY(hipMalloc(&count, sizeof(uint32_t)));
-    POOL_TRY(hipMemsetAsync(mark, 0, (size_t)nbricks * sizeof(uint32_t), c->stream));
+    POOL_TRY(hipMemsetAsync(mark, 0, (size_t)nbricks * sizeof(uint32_t), cur(c).stream));
     if (!c->ref_big) POOL_TRY(hipMalloc(&c->ref_big, ((size_t)c->ntri + 1) * sizeof(int32_t)));
-    POOL_TRY(vct_launch_frag_mark(frags, nfrags, mark, c->stream));                  // north-star mode's fragments
+    POOL_TRY(vct_launch_frag_mark(frags, nfrags, mark, cur(c).stream));                  // north-star mode's fragments
     VctVoxParams p = vox_params(c);
     p.mark_only = 1;
     p.brick_mark = mark;
     p.shadow = nullptr;
     glm_voxel_projections(c, p.proj);
-    POOL_TRY(vct_launch_voxelize_reference(p, c->ref_big + 1, c->ref_big, c->stream));   // reference mode's (mark only)
-    POOL_TRY(vct_launch_assign_slots(mark, slot, count, nbricks, c->stream));
+    POOL_TRY(vct_launch_voxelize_reference(p, c->ref_big + 1, c->ref_big, cur(c).stream));   // reference mode's (mark only)
+    POOL_TRY(vct_launch_assign_slots(mark, slot, count, nbricks, cur(c).stream));
     uint32_t nslots = 0;
-    POOL_TRY(hipMemcpyAsync(&nslots, count, sizeof(nslots), hipMemcpyDeviceToHost, c->stream));
-    POOL_TRY(hipStreamSynchronize(c->stream));
+    POOL_TRY(hipMemcpyAsync(&nslots, count, sizeof(nslots), hipMemcpyDeviceToHost, cur(c).stream));
+    POOL_TRY(hipStreamSynchronize(cur(c).stream));
     // counting sort of the fragments by slot: per-slot counts -> offsets (host prefix sum: once per mesh) -> scatter
     const size_t ns = nslots ? nslots : 1u;
     POOL_TRY(hipMalloc(&cnt, ns * sizeof(uint32_t)));
@@ -568,26 +552,26 @@ int build_voxel_slots(vct_ctx* c, const uint2* frags, uint32_t nfrags) {
     POOL_TRY(hipMalloc(&first, (ns + 1) * sizeof(uint32_t)));
     POOL_TRY(hipMalloc(&slot_brick, ns * sizeof(uint32_t)));
     POOL_TRY(hipMalloc(&sorted, (size_t)(nfrags ? nfrags : 1u) * sizeof(uint32_t)));
-    POOL_TRY(hipMemsetAsync(cnt, 0, ns * sizeof(uint32_t), c->stream));
-    POOL_TRY(hipMemsetAsync(cursor, 0, ns * sizeof(uint32_t), c->stream));
-    POOL_TRY(hipMemsetAsync(slot_brick, 0, ns * sizeof(uint32_t), c->stream));
-    POOL_TRY(vct_launch_slot_bricks(slot, nbricks, slot_brick, c->stream));      // every slot names its brick
-    POOL_TRY(vct_launch_frag_count(frags, nfrags, slot, cnt, c->stream));
+    POOL_TRY(hipMemsetAsync(cnt, 0, ns * sizeof(uint32_t), cur(c).stream));
+    POOL_TRY(hipMemsetAsync(cursor, 0, ns * sizeof(uint32_t), cur(c).stream));
+    POOL_TRY(hipMemsetAsync(slot_brick, 0, ns * sizeof(uint32_t), cur(c).stream));
+    POOL_TRY(vct_launch_slot_bricks(slot, nbricks, slot_brick, cur(c).stream));      // every slot names its brick
+    POOL_TRY(vct_launch_frag_count(frags, nfrags, slot, cnt, cur(c).stream));
     std::vector<uint32_t> hcnt(ns, 0u), hfirst(ns + 1, 0u);
-    POOL_TRY(hipMemcpyAsync(hcnt.data(), cnt, ns * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    POOL_TRY(hipStreamSynchronize(c->stream));
+    POOL_TRY(hipMemcpyAsync(hcnt.data(), cnt, ns * sizeof(uint32_t), hipMemcpyDeviceToHost, cur(c).stream));
+    POOL_TRY(hipStreamSynchronize(cur(c).stream));
     for (size_t i = 0; i < ns; ++i) hfirst[i + 1] = hfirst[i] + hcnt[i];
-    POOL_TRY(hipMemcpyAsync(first, hfirst.data(), (ns + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    POOL_TRY(vct_launch_frag_scatter(frags, nfrags, slot, first, cursor, sorted, slot_brick, c->stream));
+    POOL_TRY(hipMemcpyAsync(first, hfirst.data(), (ns + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, cur(c).stream));
+    POOL_TRY(vct_launch_frag_scatter(frags, nfrags, slot, first, cursor, sorted, slot_brick, cur(c).stream));
     // the barycentrics of every fragment (geometry only): the pass reads them instead of re-deriving the triangle set-up
     POOL_TRY(hipMalloc(&bary, (size_t)(nfrags ? nfrags : 1u) * sizeof(float2)));
     {
         VctVoxParams q = vox_params(c);
         q.frag_sorted = sorted; q.slot_first = first; q.slot_brick = slot_brick; q.nslots = nslots;
-        POOL_TRY(vct_launch_frag_geom(q, bary, nullptr, c->stream));
+        POOL_TRY(vct_launch_frag_geom(q, bary, nullptr, cur(c).stream));
         if (c->cfg.voxel_attributes) {
             POOL_TRY(hipMalloc(&tri_nrm, (size_t)(c->ntri > 0 ? c->ntri : 1) * 3 * sizeof(uint32_t)));
-            POOL_TRY(vct_launch_tri_nrm(q, tri_nrm, c->stream));
+            POOL_TRY(vct_launch_tri_nrm(q, tri_nrm, cur(c).stream));
         }
     }
     // Work items of the pass, the heaviest slots first, slots above VCT_VOX_CHUNK fragments cut into chunks.  Fragments
@@ -616,39 +600,39 @@ int build_voxel_slots(vct_ctx* c, const uint2* frags, uint32_t nfrags) {
         }
     const uint32_t nitems = (uint32_t)(hitems.size() / 4);
     POOL_TRY(hipMalloc(&items, (size_t)(nitems ? nitems : 1u) * 16));
-    if (nitems) POOL_TRY(hipMemcpyAsync(items, hitems.data(), (size_t)nitems * 16, hipMemcpyHostToDevice, c->stream));
+    if (nitems) POOL_TRY(hipMemcpyAsync(items, hitems.data(), (size_t)nitems * 16, hipMemcpyHostToDevice, cur(c).stream));
     const size_t nm = nmulti ? nmulti : 1u;
     POOL_TRY(hipMalloc(&acc2, nm * 512 * 2 * sizeof(unsigned long long)));
-    POOL_TRY(hipMemsetAsync(acc2, 0, nm * 512 * 2 * sizeof(unsigned long long), c->stream));
+    POOL_TRY(hipMemsetAsync(acc2, 0, nm * 512 * 2 * sizeof(unsigned long long), cur(c).stream));
     POOL_TRY(hipMalloc(&multi_slot, nm * sizeof(uint32_t)));
-    if (nmulti) POOL_TRY(hipMemcpyAsync(multi_slot, hmulti.data(), (size_t)nmulti * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    if (nmulti) POOL_TRY(hipMemcpyAsync(multi_slot, hmulti.data(), (size_t)nmulti * sizeof(uint32_t), hipMemcpyHostToDevice, cur(c).stream));
     if (c->cfg.voxel_attributes) {
         POOL_TRY(hipMalloc(&acc2_attr, nm * 512 * 3 * sizeof(unsigned long long)));
-        POOL_TRY(hipMemsetAsync(acc2_attr, 0, nm * 512 * 3 * sizeof(unsigned long long), c->stream));
+        POOL_TRY(hipMemsetAsync(acc2_attr, 0, nm * 512 * 3 * sizeof(unsigned long long), cur(c).stream));
     }
     // staging pool of a pass (+ attributes): written in full by every pass, never cleared
     const size_t pool_vox = ns * 512;
     POOL_TRY(hipMalloc(&stage, pool_vox * 4));
-    POOL_TRY(hipMemsetAsync(stage, 0, pool_vox * 4, c->stream));
+    POOL_TRY(hipMemsetAsync(stage, 0, pool_vox * 4, cur(c).stream));
     if (c->cfg.voxel_attributes) {
         POOL_TRY(hipMalloc(&stage_albedo, pool_vox * 4));
         POOL_TRY(hipMalloc(&stage_normal, pool_vox * 4));
         POOL_TRY(hipMalloc(&attr_albedo, pool_vox * 4));
         POOL_TRY(hipMalloc(&attr_normal, pool_vox * 4));
-        POOL_TRY(hipMemsetAsync(stage_albedo, 0, pool_vox * 4, c->stream));
-        POOL_TRY(hipMemsetAsync(stage_normal, 0, pool_vox * 4, c->stream));
-        POOL_TRY(hipMemsetAsync(attr_albedo, 0, pool_vox * 4, c->stream));
-        POOL_TRY(hipMemsetAsync(attr_normal, 0, pool_vox * 4, c->stream));
+        POOL_TRY(hipMemsetAsync(stage_albedo, 0, pool_vox * 4, cur(c).stream));
+        POOL_TRY(hipMemsetAsync(stage_normal, 0, pool_vox * 4, cur(c).stream));
+        POOL_TRY(hipMemsetAsync(attr_albedo, 0, pool_vox * 4, cur(c).stream));
+        POOL_TRY(hipMemsetAsync(attr_normal, 0, pool_vox * 4, cur(c).stream));
     }
     const size_t flag_bytes = (size_t)nbricks * sizeof(uint32_t);
     uint32_t** flags[] = {&c->brick_flags, &c->brick_prev, &c->mip_seen};
     for (uint32_t** f : flags)
         if (!*f) {
             POOL_TRY(hipMalloc(f, flag_bytes));
-            POOL_TRY(hipMemsetAsync(*f, 0, flag_bytes, c->stream));
+            POOL_TRY(hipMemsetAsync(*f, 0, flag_bytes, cur(c).stream));
         }
-    POOL_TRY(hipMemsetAsync(c->brick_flags, 0, flag_bytes, c->stream));
-    POOL_TRY(hipStreamSynchronize(c->stream));
+    POOL_TRY(hipMemsetAsync(c->brick_flags, 0, flag_bytes, cur(c).stream));
+    POOL_TRY(hipStreamSynchronize(cur(c).stream));
 #undef POOL_TRY
     (void)hipFree(mark); (void)hipFree(count); (void)hipFree(cnt); (void)hipFree(cursor);
     c->attr_albedo = attr_albedo; c->attr_normal = attr_normal;
@@ -659,6 +643,51 @@ int build_voxel_slots(vct_ctx* c, const uint2* frags, uint32_t nfrags) {
     c->stage = stage; c->stage_albedo = stage_albedo; c->stage_normal = stage_normal;
     c->vox_items = items; c->n_vox_items = nitems; c->vox_acc2 = acc2; c->vox_acc2_attr = acc2_attr; c->vox_multi_slot = multi_slot; c->n_vox_multi = nmulti;
     return VCT_OK;
+}
+
+// ---- lifetime of raster scratch and frame slots (vct_ctx.h) ------------------------------------------------------------
+// Frees every buffer of the scratch and resets it: the next pass allocates and clears what it needs.
+void raster_release(VctRasterScratch& r) {
+    void* bufs[] = {r.lists, r.recs, r.counts, r.items, r.bin_recs, r.bin_entries, r.bin_count, r.bin_items, r.bin_huge, r.vis};
+    for (void* b : bufs) if (b) (void)hipFree(b);
+    r = VctRasterScratch();
+}
+// Frees the buffers sized by the mesh's triangle count (a new mesh: the next pass allocates them for it).
+void raster_release_mesh(VctRasterScratch& r) {
+    void** bufs[] = {(void**)&r.lists, &r.recs, &r.bin_recs, (void**)&r.bin_entries, (void**)&r.bin_items};
+    for (void** b : bufs) if (*b) { (void)hipFree(*b); *b = nullptr; }
+    r.bin_rec_cap = r.bin_entry_cap = r.bin_item_cap = 0u;
+}
+
+// A slot on `stream`, which it owns from here on: timing events, G-buffer, frame, per-tile step counts and the
+// per-component outputs that are on, zeroed on that stream.  A failure leaves a partial slot for slot_release.
+hipError_t slot_create(vct_ctx* c, VctFrameSlot& s, hipStream_t stream) {
+    const size_t npix = (size_t)c->cfg.width * c->cfg.height, nt = (size_t)tiles_x(c) * tiles_y(c);
+    const size_t aov_bytes = aov_frames(c->aov_which) * npix * 8;
+    s.stream = stream;
+    hipError_t e = hipEventCreate(&s.ev0);
+    if (e == hipSuccess) e = hipEventCreate(&s.ev1);
+    if (e == hipSuccess) e = hipMalloc(&s.gb_tiled, gb_tiled_floats(c) * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(&s.frame, npix * 8);
+    if (e == hipSuccess) e = hipMalloc(&s.tile_steps, nt * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemsetAsync(s.gb_tiled, 0, gb_tiled_floats(c) * sizeof(float), stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s.frame, 0, npix * 8, stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s.tile_steps, 0, nt * sizeof(uint32_t), stream);
+    if (e == hipSuccess && aov_bytes) e = hipMalloc(&s.aov, aov_bytes);
+    if (e == hipSuccess && aov_bytes) e = hipMemsetAsync(s.aov, 0, aov_bytes, stream);
+    s.gb_current = s.gb_tiled;
+    return e;
+}
+// Waits for the slot's stream, then frees everything the slot owns (its stream and raster scratch too) and resets it.
+void slot_release(VctFrameSlot& s) {
+    if (s.stream) (void)hipStreamSynchronize(s.stream);
+    void* bufs[] = {s.gb_tiled, s.frame, s.tile_steps, s.aov};
+    for (void* b : bufs) if (b) (void)hipFree(b);
+    raster_release(s.raster);
+    if (s.ev0) (void)hipEventDestroy(s.ev0);
+    if (s.ev1) (void)hipEventDestroy(s.ev1);
+    if (s.stream) (void)hipStreamDestroy(s.stream);
+    s = VctFrameSlot();
 }
 
 }  // namespace
@@ -753,6 +782,7 @@ int vct_create(const vct_config* cfg, vct_ctx** out) {
     } while (0)
     CREATE_TRY(hipSetDevice(dev));
     {
+        hipStream_t stream = nullptr;
         // VCT_STREAM_PRIORITY = high | low: experiments with two contexts sharing a GPU (tools/overlap_probe.py)
         int lo = 0, hi = 0;
         const char* pr = getenv("VCT_STREAM_PRIORITY");
@@ -764,14 +794,13 @@ int vct_create(const vct_config* cfg, vct_ctx** out) {
         CREATE_TRY(hipGetDeviceProperties(&prop, dev));
         if (c->reserved_cus < 0 || c->reserved_cus >= prop.multiProcessorCount) c->reserved_cus = 0;
         if (c->reserved_cus > 0)
-            CREATE_TRY(vct_create_masked_stream(&c->stream, dev, 0, prop.multiProcessorCount - c->reserved_cus));
+            CREATE_TRY(vct_create_masked_stream(&stream, dev, 0, prop.multiProcessorCount - c->reserved_cus));
         else if (pr && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess)
-            CREATE_TRY(hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, pr[0] == 'h' ? hi : lo));
+            CREATE_TRY(hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, pr[0] == 'h' ? hi : lo));
         else
-            CREATE_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+            CREATE_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        CREATE_TRY(slot_create(c, c->slots[0], stream));      // slot 0: the context's stream
     }
-    CREATE_TRY(hipEventCreate(&c->ev0));
-    CREATE_TRY(hipEventCreate(&c->ev1));
     {
         // VCT_RASTER_PATH=binned | direct: the tile-binned visibility (round 4) or the direct form of rounds 2-3 (one
         // device-scope atomicMin per covered pixel) for both raster passes -- same results.  Unset: chosen per scene by
@@ -791,26 +820,17 @@ int vct_create(const vct_config* cfg, vct_ctx** out) {
     c->nlev = vct_ilog2(V) + 1;
     c->chain_texels = vct_chain_texels(V);
     CREATE_TRY(hipMalloc(&c->chain, c->chain_texels * 4));
-    CREATE_TRY(hipMemsetAsync(c->chain, 0, c->chain_texels * 4, c->stream));   // VCT.h:115-119
+    CREATE_TRY(hipMemsetAsync(c->chain, 0, c->chain_texels * 4, cur(c).stream));   // VCT.h:115-119
     const size_t npix = (size_t)cfg->width * cfg->height;
-    CREATE_TRY(hipMalloc(&c->gb_tiled, gb_tiled_floats(c) * sizeof(float)));
-    CREATE_TRY(hipMemsetAsync(c->gb_tiled, 0, gb_tiled_floats(c) * sizeof(float), c->stream));
     if (cfg->anisotropic_mips) {
         const size_t n = 6 * (c->chain_texels - (size_t)V * V * V);
         CREATE_TRY(hipMalloc(&c->aniso, n * 4));
-        CREATE_TRY(hipMemsetAsync(c->aniso, 0, n * 4, c->stream));
+        CREATE_TRY(hipMemsetAsync(c->aniso, 0, n * 4, cur(c).stream));
     }
-    CREATE_TRY(hipMalloc(&c->frame, npix * 8));
-    CREATE_TRY(hipMemsetAsync(c->frame, 0, npix * 8, c->stream));
     CREATE_TRY(hipMalloc(&c->step_counter, VCT_STEP_COUNTERS * sizeof(unsigned long long)));
-    CREATE_TRY(hipMemsetAsync(c->step_counter, 0, VCT_STEP_COUNTERS * sizeof(unsigned long long), c->stream));
-    {
-        const size_t nw = (size_t)tiles_x(c) * tiles_y(c);
-        CREATE_TRY(hipMalloc(&c->tile_steps, nw * sizeof(uint32_t)));
-        CREATE_TRY(hipMemsetAsync(c->tile_steps, 0, nw * sizeof(uint32_t), c->stream));
-    }
+    CREATE_TRY(hipMemsetAsync(c->step_counter, 0, VCT_STEP_COUNTERS * sizeof(unsigned long long), cur(c).stream));
     CREATE_TRY(hipMalloc(&c->stats, 16 * sizeof(unsigned long long)));
-    CREATE_TRY(hipMemsetAsync(c->stats, 0, 16 * sizeof(unsigned long long), c->stream));
+    CREATE_TRY(hipMemsetAsync(c->stats, 0, 16 * sizeof(unsigned long long), cur(c).stream));
     CREATE_TRY(hipMalloc(&c->steps_dev, 2 * VCT_MAX_STEPS * sizeof(VctStep)));
     {
         std::vector<uint32_t> lut(1024);
@@ -821,14 +841,13 @@ int vct_create(const vct_config* cfg, vct_ctx** out) {
     if (cfg->debug_outputs) {
         CREATE_TRY(hipMalloc(&c->dbg_steps, npix * 7));
         CREATE_TRY(hipMalloc(&c->dbg_cones, npix * 28 * sizeof(float)));
-        CREATE_TRY(hipMemsetAsync(c->dbg_steps, 0, npix * 7, c->stream));
-        CREATE_TRY(hipMemsetAsync(c->dbg_cones, 0, npix * 28 * sizeof(float), c->stream));
+        CREATE_TRY(hipMemsetAsync(c->dbg_steps, 0, npix * 7, cur(c).stream));
+        CREATE_TRY(hipMemsetAsync(c->dbg_cones, 0, npix * 28 * sizeof(float), cur(c).stream));
     }
-    CREATE_TRY(hipStreamSynchronize(c->stream));
+    CREATE_TRY(hipStreamSynchronize(cur(c).stream));
 #undef CREATE_TRY
     memset(c->light_vp, 0, sizeof(c->light_vp));
     c->light_vp[0] = c->light_vp[5] = c->light_vp[10] = c->light_vp[15] = 1.0f;
-    c->gb_current = c->gb_tiled;
     {
         // once per process and device: the texture path's UNORM8 conversion must be the exact decode the trace kernels
         // count on (it is on gfx950).  No other path is compiled in: a device where it is not fails here, loudly.
@@ -856,39 +875,21 @@ void vct_destroy(vct_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     vct_comm_release(c);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->frames_in_flight > 1) {            // the slot that is not selected: its set is not in the context fields freed below
-        VctFrameSlot& o = c->slots[1 - c->cur_slot];
-        if (o.stream) (void)hipStreamSynchronize(o.stream);
-        void* ob[] = {o.gb_tiled, o.frame, o.tile_steps, o.aov};
-        for (void* b : ob) if (b) (void)hipFree(b);
-        if (o.ev0) (void)hipEventDestroy(o.ev0);
-        if (o.ev1) (void)hipEventDestroy(o.ev1);
-        if (o.stream) (void)hipStreamDestroy(o.stream);
-    }
-    if (c->aov) (void)hipFree(c->aov);
+    for (int k = 0; k < c->frames_in_flight; ++k) slot_release(c->slots[k]);
+    raster_release(c->shadow_raster);
     if (c->ev_xslot) (void)hipEventDestroy(c->ev_xslot);
-    void* bufs[] = {c->chain, c->cells, c->shadow_tiles, c->staging, c->gb_linear, c->gb_tiled, c->frame, c->dbg_steps,
-                    c->dbg_cones, c->step_counter, c->tile_steps, c->stats, c->vt_pix, c->steps_dev, c->spread_lut, c->tri_pos,
+    void* bufs[] = {c->chain, c->cells, c->shadow_tiles, c->staging, c->gb_linear, c->dbg_steps,
+                    c->dbg_cones, c->step_counter, c->stats, c->vt_pix, c->steps_dev, c->spread_lut, c->tri_pos,
                     c->tri_mat, c->tri_alpha, c->mat_albedo, c->shadow, c->acc, c->brick_slot, c->frag_sorted, c->slot_first, c->slot_brick, c->vox_items, c->vox_acc2, c->vox_acc2_attr, c->vox_multi_slot, c->stage,
                     c->stage_albedo, c->stage_normal, c->plan, c->frag_bary, c->frag_alb, c->tri_qnrm,
                     c->aniso, c->ref_big, c->brick_flags, c->brick_prev, c->mip_seen, c->mip_seen_b, c->bounce_list, c->brick_over, c->chain_b, c->attr_albedo, c->attr_normal,
-                    c->tri_nrm, c->tri_tan, c->tri_bit, c->mat_specular, c->tri_uv, c->tex_texels, c->tex_desc, c->mat_tex, c->vis[0], c->vis[1], c->raster_lists[0], c->raster_lists[1], c->raster_lists[2],
-                    c->raster_counts[0], c->raster_counts[1], c->raster_counts[2], c->raster_items[0], c->raster_items[1], c->raster_items[2],
-                    c->raster_recs[0], c->raster_recs[1], c->raster_recs[2]};
+                    c->tri_nrm, c->tri_tan, c->tri_bit, c->mat_specular, c->tri_uv, c->tex_texels, c->tex_desc, c->mat_tex};
     for (void* b : bufs) if (b) (void)hipFree(b);
-    for (int k = 0; k < 3; ++k) {
-        void* bb[] = {c->bin_recs[k], c->bin_entries[k], c->bin_count[k], c->bin_items[k], c->bin_huge[k]};
-        for (void* b : bb) if (b) (void)hipFree(b);
-    }
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     if (c->ev_shadow) (void)hipEventDestroy(c->ev_shadow);
     for (int k = 0; k < 8; ++k) if (c->ev_auto[k]) (void)hipEventDestroy(c->ev_auto[k]);
     if (c->aux_stream) { (void)hipStreamSynchronize(c->aux_stream); (void)hipStreamDestroy(c->aux_stream); }
-    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
 
@@ -957,13 +958,8 @@ int vct_upload_triangles(vct_ctx* c, const float* pos, const int32_t* material, 
     if (c->tri_alpha) { (void)hipFree(c->tri_alpha); c->tri_alpha = nullptr; }
     c->tri_alpha_dirty = true;
     if (c->mat_albedo) { (void)hipFree(c->mat_albedo); c->mat_albedo = nullptr; }
-    for (int k = 0; k < 3; ++k) {
-        if (c->raster_lists[k]) { (void)hipFree(c->raster_lists[k]); c->raster_lists[k] = nullptr; }   // sized by ntri
-        if (c->raster_recs[k]) { (void)hipFree(c->raster_recs[k]); c->raster_recs[k] = nullptr; }
-        void** bb[] = {&c->bin_recs[k], (void**)&c->bin_entries[k], (void**)&c->bin_items[k]};
-        for (void** b : bb) if (*b) { (void)hipFree(*b); *b = nullptr; }
-        c->bin_rec_cap[k] = c->bin_entry_cap[k] = c->bin_item_cap[k] = 0u;
-    }
+    raster_release_mesh(c->shadow_raster);
+    for (VctFrameSlot& sl : c->slots) raster_release_mesh(sl.raster);
     c->auto_state = 0; c->auto_choice = -1;       // the raster form is measured again for the new mesh
     drop_voxel_plan(c);     // before anything below can fail: the old plan indexes the old mesh
     float** frames[4] = {&c->tri_nrm, &c->tri_tan, &c->tri_bit, &c->tri_uv};       // belong to the old mesh
@@ -977,11 +973,11 @@ int vct_upload_triangles(vct_ctx* c, const float* pos, const int32_t* material, 
     HIP_TRY(c, hipMalloc(&c->mat_albedo, (size_t)nmat * 4 * sizeof(float)));
     if (!c->plan) HIP_TRY(c, hipMalloc(&c->plan, 4 * sizeof(uint32_t)));
     HIP_TRY(c, hipMemcpyAsync(c->tri_pos, pos, (size_t)ntri * 9 * sizeof(float),
-                              hipMemcpyHostToDevice, c->stream));
+                              hipMemcpyHostToDevice, cur(c).stream));
     HIP_TRY(c, hipMemcpyAsync(c->tri_mat, material, (size_t)ntri * sizeof(int32_t),
-                              hipMemcpyHostToDevice, c->stream));
+                              hipMemcpyHostToDevice, cur(c).stream));
     HIP_TRY(c, hipMemcpyAsync(c->mat_albedo, albedo, (size_t)nmat * 4 * sizeof(float),
-                              hipMemcpyHostToDevice, c->stream));
+                              hipMemcpyHostToDevice, cur(c).stream));
     c->ntri = ntri;
     c->nmat = nmat;
     // Voxelization plan (geometry only): the exact conservative fragments of every triangle -- count, allocate, fill;
@@ -997,15 +993,15 @@ int vct_upload_triangles(vct_ctx* c, const float* pos, const int32_t* material, 
     };
 #define PLAN_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return plan_fail(e_, #expr); } while (0)
     PLAN_TRY(hipMalloc(&big_tmp, (size_t)ntri * sizeof(int32_t)));
-    PLAN_TRY(hipMemsetAsync(c->plan, 0, 4 * sizeof(uint32_t), c->stream));
-    PLAN_TRY(vct_launch_vox_plan(p, c->plan, nullptr, big_tmp, false, c->stream));
-    PLAN_TRY(hipMemcpyAsync(counts, c->plan, sizeof(counts), hipMemcpyDeviceToHost, c->stream));
-    PLAN_TRY(hipStreamSynchronize(c->stream));
+    PLAN_TRY(hipMemsetAsync(c->plan, 0, 4 * sizeof(uint32_t), cur(c).stream));
+    PLAN_TRY(vct_launch_vox_plan(p, c->plan, nullptr, big_tmp, false, cur(c).stream));
+    PLAN_TRY(hipMemcpyAsync(counts, c->plan, sizeof(counts), hipMemcpyDeviceToHost, cur(c).stream));
+    PLAN_TRY(hipStreamSynchronize(cur(c).stream));
     const uint32_t n_small = counts[0];
     const int n_big = (int)counts[1];
-    PLAN_TRY(vct_launch_vox_plan_big(p, big_tmp, n_big, c->plan, nullptr, false, c->stream));
-    PLAN_TRY(hipMemcpyAsync(counts, c->plan, sizeof(counts), hipMemcpyDeviceToHost, c->stream));
-    PLAN_TRY(hipStreamSynchronize(c->stream));
+    PLAN_TRY(vct_launch_vox_plan_big(p, big_tmp, n_big, c->plan, nullptr, false, cur(c).stream));
+    PLAN_TRY(hipMemcpyAsync(counts, c->plan, sizeof(counts), hipMemcpyDeviceToHost, cur(c).stream));
+    PLAN_TRY(hipStreamSynchronize(cur(c).stream));
     const unsigned long long total = (unsigned long long)n_small + counts[2];
     // counts[3]: one of the 32-bit device counters wrapped while counting (k_vox_plan / k_vox_plan_big flag it) -- the
     // totals above would then look small
@@ -1015,10 +1011,10 @@ int vct_upload_triangles(vct_ctx* c, const float* pos, const int32_t* material, 
     }
     PLAN_TRY(hipMalloc(&frags, (size_t)(total ? total : 1ull) * sizeof(uint2)));
     const uint32_t restart[4] = {0u, 0u, n_small, 0u};          // small triangles fill [0, n_small), the big ones behind
-    PLAN_TRY(hipMemcpyAsync(c->plan, restart, sizeof(restart), hipMemcpyHostToDevice, c->stream));
-    PLAN_TRY(vct_launch_vox_plan(p, c->plan, frags, nullptr, true, c->stream));
-    PLAN_TRY(vct_launch_vox_plan_big(p, big_tmp, n_big, c->plan, frags, true, c->stream));
-    PLAN_TRY(hipStreamSynchronize(c->stream));
+    PLAN_TRY(hipMemcpyAsync(c->plan, restart, sizeof(restart), hipMemcpyHostToDevice, cur(c).stream));
+    PLAN_TRY(vct_launch_vox_plan(p, c->plan, frags, nullptr, true, cur(c).stream));
+    PLAN_TRY(vct_launch_vox_plan_big(p, big_tmp, n_big, c->plan, frags, true, cur(c).stream));
+    PLAN_TRY(hipStreamSynchronize(cur(c).stream));
 #undef PLAN_TRY
     (void)hipFree(big_tmp);
     big_tmp = nullptr;
@@ -1043,11 +1039,11 @@ int vct_upload_shadow_map(vct_ctx* c, const float* depth, int32_t size, const fl
     float* tmp = nullptr;
     HIP_TRY(c, hipMalloc(&c->shadow, n * sizeof(uint32_t)));
     hipError_t e = hipMalloc(&tmp, n * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpyAsync(tmp, depth, n * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = vct_launch_shadow_encode(tmp, c->shadow, n, 0u, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(tmp, depth, n * sizeof(float), hipMemcpyHostToDevice, cur(c).stream);
+    if (e == hipSuccess) e = vct_launch_shadow_encode(tmp, c->shadow, n, 0u, cur(c).stream);
     if (e == hipSuccess) e = hipMalloc(&c->shadow_tiles, shadow_tile_count(size) * sizeof(uint2));
-    if (e == hipSuccess) e = vct_launch_shadow_minmax(c->shadow, 0u, size, c->shadow_tiles, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = vct_launch_shadow_minmax(c->shadow, 0u, size, c->shadow_tiles, cur(c).stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(cur(c).stream);
     if (tmp) (void)hipFree(tmp);
     if (e != hipSuccess) {
         (void)hipFree(c->shadow); c->shadow = nullptr;
@@ -1063,20 +1059,17 @@ int vct_upload_shadow_map(vct_ctx* c, const float* depth, int32_t size, const fl
 
 // ---- raster input stages ------------------------------------------------------------------
 
-// Scratch of one raster pass on stream `s`: `pixels` 64-bit visibility words (main draw) or 32-bit ones (depth_only).
-// scratch set of the main draw: [1], or [2] in the second frame slot (vct_ctx.h)
-static int raster_set_of(const vct_ctx* c) { return c->frames_in_flight > 1 && c->cur_slot == 1 ? 2 : 1; }
-
-static int raster_args(vct_ctx* c, int side_w, int side_h, bool depth_only, bool binned, hipStream_t s, VctRasterArgs& a) {
+// Scratch `r` of one raster pass on stream `s`: `pixels` 64-bit visibility words (main draw) or 32-bit ones (depth_only,
+// the shadow-map words).
+static int raster_args(vct_ctx* c, VctRasterScratch& r, int side_w, int side_h, bool depth_only, bool binned, hipStream_t s,
+                       VctRasterArgs& a) {
     if (!c->tri_pos) return fail(c, VCT_ERR_INVALID, "no triangles uploaded");
     const size_t pixels = (size_t)side_w * side_h;
-    const int k = depth_only ? 0 : raster_set_of(c);
-    const int vs = k == 2 ? 1 : 0;                 // visibility words of this frame slot
-    if (!depth_only && c->vis_words[vs] < pixels) {
-        if (c->vis[vs]) { (void)hipFree(c->vis[vs]); c->vis[vs] = nullptr; c->vis_words[vs] = 0; }
-        HIP_TRY(c, hipMalloc(&c->vis[vs], pixels * sizeof(unsigned long long)));
-        c->vis_words[vs] = pixels;
-        c->raster_dirty[k] = true;
+    if (!depth_only && r.vis_words < pixels) {
+        if (r.vis) { (void)hipFree(r.vis); r.vis = nullptr; r.vis_words = 0; }
+        HIP_TRY(c, hipMalloc(&r.vis, pixels * sizeof(unsigned long long)));
+        r.vis_words = pixels;
+        r.dirty = true;
     }
     const uint32_t bins = (uint32_t)(((size_t)side_w + 15) / 16 * (((size_t)side_h + 15) / 16));
     if (binned) {
@@ -1089,69 +1082,69 @@ static int raster_args(vct_ctx* c, int side_w, int side_h, bool depth_only, bool
         const uint32_t want_recs = (uint32_t)c->ntri + 4096u;
         const size_t want_ent_sz = (size_t)c->ntri * 4 + (size_t)bins * 4 + 65536;
         const uint32_t want_ent = (uint32_t)(want_ent_sz < 0x7fffffffull ? want_ent_sz : 0x7fffffffull);
-        if (c->bin_rec_cap[k] < want_recs) {
-            if (c->bin_recs[k]) { (void)hipFree(c->bin_recs[k]); c->bin_recs[k] = nullptr; c->bin_rec_cap[k] = 0u; }
-            HIP_TRY(c, hipMalloc(&c->bin_recs[k], (size_t)want_recs * 160));
-            c->bin_rec_cap[k] = want_recs;
+        if (r.bin_rec_cap < want_recs) {
+            if (r.bin_recs) { (void)hipFree(r.bin_recs); r.bin_recs = nullptr; r.bin_rec_cap = 0u; }
+            HIP_TRY(c, hipMalloc(&r.bin_recs, (size_t)want_recs * 160));
+            r.bin_rec_cap = want_recs;
         }
-        if (c->bin_entry_cap[k] < want_ent) {
-            if (c->bin_entries[k]) { (void)hipFree(c->bin_entries[k]); c->bin_entries[k] = nullptr; c->bin_entry_cap[k] = 0u; }
-            HIP_TRY(c, hipMalloc(&c->bin_entries[k], ((size_t)want_ent + 1) * sizeof(uint2)));      // + the spare entry k_bin_fill's idle lanes write
-            c->bin_entry_cap[k] = want_ent;
+        if (r.bin_entry_cap < want_ent) {
+            if (r.bin_entries) { (void)hipFree(r.bin_entries); r.bin_entries = nullptr; r.bin_entry_cap = 0u; }
+            HIP_TRY(c, hipMalloc(&r.bin_entries, ((size_t)want_ent + 1) * sizeof(uint2)));      // + the spare entry k_bin_fill's idle lanes write
+            r.bin_entry_cap = want_ent;
         }
-        const uint32_t want_items = bins + c->bin_entry_cap[k] / 512u + 1u;      // sum over bins of ceil(entries / slice)
-        if (c->bin_item_cap[k] < want_items) {
-            if (c->bin_items[k]) { (void)hipFree(c->bin_items[k]); c->bin_items[k] = nullptr; c->bin_item_cap[k] = 0u; }
-            HIP_TRY(c, hipMalloc(&c->bin_items[k], (size_t)want_items * sizeof(uint4)));
-            c->bin_item_cap[k] = want_items;
+        const uint32_t want_items = bins + r.bin_entry_cap / 512u + 1u;      // sum over bins of ceil(entries / slice)
+        if (r.bin_item_cap < want_items) {
+            if (r.bin_items) { (void)hipFree(r.bin_items); r.bin_items = nullptr; r.bin_item_cap = 0u; }
+            HIP_TRY(c, hipMalloc(&r.bin_items, (size_t)want_items * sizeof(uint4)));
+            r.bin_item_cap = want_items;
         }
-        if (c->bin_bins[k] < bins) {
-            if (c->bin_count[k]) { (void)hipFree(c->bin_count[k]); c->bin_count[k] = nullptr; c->bin_bins[k] = 0u; }
-            HIP_TRY(c, hipMalloc(&c->bin_count[k], (size_t)bins * 2 * VCT_BIN_CSTRIDE * sizeof(uint32_t)));
-            c->bin_bins[k] = bins;
-            c->raster_dirty[k] = true;
+        if (r.bin_bins < bins) {
+            if (r.bin_count) { (void)hipFree(r.bin_count); r.bin_count = nullptr; r.bin_bins = 0u; }
+            HIP_TRY(c, hipMalloc(&r.bin_count, (size_t)bins * 2 * VCT_BIN_CSTRIDE * sizeof(uint32_t)));
+            r.bin_bins = bins;
+            r.dirty = true;
         }
-        if (!c->bin_huge[k]) {
-            HIP_TRY(c, hipMalloc(&c->bin_huge[k], (size_t)(VCT_BIN_HUGE_CAP + 16 + 32) * sizeof(uint32_t)));
-            c->raster_dirty[k] = true;
+        if (!r.bin_huge) {
+            HIP_TRY(c, hipMalloc(&r.bin_huge, (size_t)(VCT_BIN_HUGE_CAP + 16 + 32) * sizeof(uint32_t)));
+            r.dirty = true;
         }
     } else {
-        if (!c->raster_lists[k]) HIP_TRY(c, hipMalloc(&c->raster_lists[k], (size_t)c->ntri * 4 * sizeof(int32_t)));
-        if (!c->raster_recs[k]) HIP_TRY(c, hipMalloc(&c->raster_recs[k], (size_t)c->ntri * 2 * 96));
-        if (!c->raster_counts[k]) { HIP_TRY(c, hipMalloc(&c->raster_counts[k], 8 * sizeof(uint32_t))); c->raster_dirty[k] = true; }
+        if (!r.lists) HIP_TRY(c, hipMalloc(&r.lists, (size_t)c->ntri * 4 * sizeof(int32_t)));
+        if (!r.recs) HIP_TRY(c, hipMalloc(&r.recs, (size_t)c->ntri * 2 * 96));
+        if (!r.counts) { HIP_TRY(c, hipMalloc(&r.counts, 8 * sizeof(uint32_t))); r.dirty = true; }
         // tile work items: 16x16-pixel pieces of large triangles; pixels/16 entries is ~16x the typical
         // demand (sum of visible bounding boxes ~ a few frames' worth of pixels); overflow is handled
         const size_t want_items = pixels / 16 + 4096;
-        if (c->raster_item_capacity[k] < want_items) {
-            if (c->raster_items[k]) { (void)hipFree(c->raster_items[k]); c->raster_items[k] = nullptr; }
-            HIP_TRY(c, hipMalloc(&c->raster_items[k], want_items * sizeof(uint2)));
-            c->raster_item_capacity[k] = (uint32_t)want_items;
+        if (r.item_capacity < want_items) {
+            if (r.items) { (void)hipFree(r.items); r.items = nullptr; }
+            HIP_TRY(c, hipMalloc(&r.items, want_items * sizeof(uint2)));
+            r.item_capacity = (uint32_t)want_items;
         }
     }
-    if (c->raster_dirty[k]) {   // first pass, resized buffers, or a pass that failed half way: clear this kind's state once
+    if (r.dirty) {   // first pass, resized buffers, or a pass that failed half way: clear this kind's state once
         if (depth_only) c->shadow_passes = 0u;      // the shadow words restart their epoch cycle with a memset (below)
-        else HIP_TRY(c, hipMemsetAsync(c->vis[vs], 0xff, c->vis_words[vs] * sizeof(unsigned long long), s));
+        else HIP_TRY(c, hipMemsetAsync(r.vis, 0xff, r.vis_words * sizeof(unsigned long long), s));
         if (binned) {
-            HIP_TRY(c, hipMemsetAsync(c->bin_count[k], 0, (size_t)c->bin_bins[k] * 2 * VCT_BIN_CSTRIDE * sizeof(uint32_t), s));
-            HIP_TRY(c, hipMemsetAsync(c->bin_huge[k] + VCT_BIN_HUGE_CAP, 0, (16 + 32) * sizeof(uint32_t), s));
+            HIP_TRY(c, hipMemsetAsync(r.bin_count, 0, (size_t)r.bin_bins * 2 * VCT_BIN_CSTRIDE * sizeof(uint32_t), s));
+            HIP_TRY(c, hipMemsetAsync(r.bin_huge + VCT_BIN_HUGE_CAP, 0, (16 + 32) * sizeof(uint32_t), s));
         } else {
-            HIP_TRY(c, hipMemsetAsync(c->raster_counts[k], 0, 8 * sizeof(uint32_t), s));
+            HIP_TRY(c, hipMemsetAsync(r.counts, 0, 8 * sizeof(uint32_t), s));
         }
-        c->raster_dirty[k] = false;
+        r.dirty = false;
     }
     memset(&a, 0, sizeof(a));
     a.binned = binned ? 1 : 0;
     if (binned) {
-        a.bin_recs = c->bin_recs[k]; a.bin_rec_cap = c->bin_rec_cap[k];
-        a.bin_entries = c->bin_entries[k]; a.bin_entry_cap = c->bin_entry_cap[k];
+        a.bin_recs = r.bin_recs; a.bin_rec_cap = r.bin_rec_cap;
+        a.bin_entries = r.bin_entries; a.bin_entry_cap = r.bin_entry_cap;
         if (c->bin_test_caps[0] && c->bin_test_caps[0] < a.bin_rec_cap) a.bin_rec_cap = c->bin_test_caps[0];
         if (c->bin_test_caps[1] && c->bin_test_caps[1] < a.bin_entry_cap) a.bin_entry_cap = c->bin_test_caps[1];
-        a.bin_count = c->bin_count[k]; a.bin_cursor = c->bin_count[k] + (size_t)c->bin_bins[k] * VCT_BIN_CSTRIDE;
-        a.bin_items = c->bin_items[k]; a.bin_item_cap = c->bin_item_cap[k];
-        a.bin_huge = c->bin_huge[k]; a.bin_huge_cap = VCT_BIN_HUGE_CAP;
-        a.bin_ctr = c->bin_huge[k] + VCT_BIN_HUGE_CAP + 8 * c->bin_set[k];
-        a.bin_next_ctr = c->bin_huge[k] + VCT_BIN_HUGE_CAP + 8 * (c->bin_set[k] ^ 1);
-        c->bin_set[k] ^= 1;
+        a.bin_count = r.bin_count; a.bin_cursor = r.bin_count + (size_t)r.bin_bins * VCT_BIN_CSTRIDE;
+        a.bin_items = r.bin_items; a.bin_item_cap = r.bin_item_cap;
+        a.bin_huge = r.bin_huge; a.bin_huge_cap = VCT_BIN_HUGE_CAP;
+        a.bin_ctr = r.bin_huge + VCT_BIN_HUGE_CAP + 8 * r.bin_set;
+        a.bin_next_ctr = r.bin_huge + VCT_BIN_HUGE_CAP + 8 * (r.bin_set ^ 1);
+        r.bin_set ^= 1;
     }
     a.pos = c->tri_pos;
     a.nrm = c->tri_nrm; a.tan = c->tri_tan; a.bit = c->tri_bit;
@@ -1160,23 +1153,23 @@ static int raster_args(vct_ctx* c, int side_w, int side_h, bool depth_only, bool
     a.specular = c->mat_specular;
     a.ntri = c->ntri;
     a.model_scale = c->cfg.model_scale;
-    a.vis = c->vis[vs];
+    a.vis = r.vis;
     a.vis32 = nullptr;          // vct_render_shadow_map points it at the shadow-map words
     a.vis32_ebase = 0u;
     if (!binned) {
-        a.items = c->raster_items[k];
+        a.items = r.items;
         // [wave, group, item, -]: the wave and group counters are one 8-byte-aligned pair, k_raster_vis reserves both
         // lists of a workgroup with a single 64-bit atomic
-        uint32_t* cur = c->raster_counts[k] + 4 * c->raster_set[k];
-        a.wave_list = c->raster_lists[k];
-        a.wave_count = cur;
-        a.group_list = c->raster_lists[k] + (size_t)c->ntri * 2;
-        a.group_count = cur + 1;
-        a.item_count = cur + 2;
-        a.next_counts = c->raster_counts[k] + 4 * (c->raster_set[k] ^ 1);
-        a.recs = c->raster_recs[k];
-        c->raster_set[k] ^= 1;
-        a.item_capacity = c->raster_item_capacity[k];
+        uint32_t* ctr = r.counts + 4 * r.set;
+        a.wave_list = r.lists;
+        a.wave_count = ctr;
+        a.group_list = r.lists + (size_t)c->ntri * 2;
+        a.group_count = ctr + 1;
+        a.item_count = ctr + 2;
+        a.next_counts = r.counts + 4 * (r.set ^ 1);
+        a.recs = r.recs;
+        r.set ^= 1;
+        a.item_capacity = r.item_capacity;
     }
     a.tex = textures_of(c);
     if (!depth_only) {          // the main draw's alpha-test class per triangle: once per mesh / texture set
@@ -1205,13 +1198,13 @@ int vct_upload_mesh_attributes(vct_ctx* c, const float* normal, const float* tan
     for (int k = 0; k < 3; ++k) {
         if (*dst[k]) { (void)hipFree(*dst[k]); *dst[k] = nullptr; }
         HIP_TRY(c, hipMalloc(dst[k], bytes));
-        HIP_TRY(c, hipMemcpyAsync(*dst[k], src[k], bytes, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(*dst[k], src[k], bytes, hipMemcpyHostToDevice, cur(c).stream));
     }
     if (c->mat_specular) { (void)hipFree(c->mat_specular); c->mat_specular = nullptr; }
     HIP_TRY(c, hipMalloc(&c->mat_specular, (size_t)c->nmat * 3 * sizeof(float)));
     HIP_TRY(c, hipMemcpyAsync(c->mat_specular, specular, (size_t)c->nmat * 3 * sizeof(float),
-                              hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+                              hipMemcpyHostToDevice, cur(c).stream));
+    HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     return VCT_OK;
 }
 
@@ -1226,8 +1219,8 @@ int vct_upload_mesh_uvs(vct_ctx* c, const float* uv) {
     c->tri_alpha_dirty = true;          // textures take effect once the coordinates are there
     c->frag_alb_dirty = true;
     HIP_TRY(c, hipMalloc(&c->tri_uv, bytes));
-    HIP_TRY(c, hipMemcpyAsync(c->tri_uv, uv, bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->tri_uv, uv, bytes, hipMemcpyHostToDevice, cur(c).stream));
+    HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     return VCT_OK;
 }
 
@@ -1287,17 +1280,17 @@ int vct_upload_textures(vct_ctx* c, const uint8_t* const* rgba8, const int32_t* 
     for (int32_t i = 0; i < ntex; ++i) {
         const VctTexDesc& d = desc[(size_t)i];
         HIP_TRY(c, hipMemcpyAsync(c->tex_texels + d.off, rgba8[i], (size_t)width[i] * height[i] * 4,
-                                  hipMemcpyHostToDevice, c->stream));
+                                  hipMemcpyHostToDevice, cur(c).stream));
         for (int k = 1; k < d.nlev; ++k) {
             const int pw = d.w >> (k - 1) > 1 ? d.w >> (k - 1) : 1, ph = d.h >> (k - 1) > 1 ? d.h >> (k - 1) : 1;
             const int w = d.w >> k > 1 ? d.w >> k : 1, h = d.h >> k > 1 ? d.h >> k : 1;
             HIP_TRY(c, vct_launch_tex_mip(c->tex_texels + d.off + d.lvl[k - 1], pw, ph, c->tex_texels + d.off + d.lvl[k],
-                                          w, h, c->stream));
+                                          w, h, cur(c).stream));
         }
     }
-    HIP_TRY(c, hipMemcpyAsync(c->tex_desc, desc.data(), (size_t)ntex * sizeof(VctTexDesc), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->mat_tex, mat_tex, (size_t)c->nmat * 3 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->tex_desc, desc.data(), (size_t)ntex * sizeof(VctTexDesc), hipMemcpyHostToDevice, cur(c).stream));
+    HIP_TRY(c, hipMemcpyAsync(c->mat_tex, mat_tex, (size_t)c->nmat * 3 * sizeof(int32_t), hipMemcpyHostToDevice, cur(c).stream));
+    HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     c->ntex = ntex;
     for (int32_t m = 0; m < c->nmat; ++m)         // a diffuse map with non-opaque texels: its fragments are alpha-tested
         if (mat_tex[3 * m] >= 0 && (desc[(size_t)mat_tex[3 * m]].flags & 1u)) c->has_alpha_textures = true;
@@ -1332,25 +1325,25 @@ int vct_render_shadow_map(vct_ctx* c, const float light_vp[16]) {
     // uninitialised table would decide PCF windows wrongly, without one the consumers just fetch every window (advisor, round 5).
     auto drop_tiles = [&]() { if (c->shadow_tiles) { (void)hipFree(c->shadow_tiles); c->shadow_tiles = nullptr; } };
     VctRasterArgs a;
-    int rc = raster_args(c, S, S, true, c->raster_mode == 2, c->stream, a);
+    int rc = raster_args(c, c->shadow_raster, S, S, true, c->raster_mode == 2, cur(c).stream, a);
     if (rc) { drop_tiles(); return rc; }
     // The pass's atomicMin words ARE the map (vct_internal.h "shadow map words"): epoch 3, 2, 1, 0, then one memset
     // and 3 again -- a new pass overwrites older epochs by itself, readers see them as depth 1.0.
     const uint32_t epoch = 3u - (c->shadow_passes & 3u);
     if (epoch == 3u) {
-        const hipError_t em = hipMemsetAsync(c->shadow, 0xff, (size_t)S * S * sizeof(uint32_t), c->stream);
+        const hipError_t em = hipMemsetAsync(c->shadow, 0xff, (size_t)S * S * sizeof(uint32_t), cur(c).stream);
         if (em != hipSuccess) { drop_tiles(); HIP_TRY(c, em); }
     }
     a.vis32 = c->shadow;
     a.vis32_ebase = VCT_SHADOW_EPOCH(epoch);
     memcpy(c->light_vp, light_vp, 64);
-    const hipError_t e = vct_launch_shadow_raster(a, light_vp, S, c->stream);
-    if (e != hipSuccess) { c->raster_dirty[0] = true; drop_tiles(); HIP_TRY(c, e); }
+    const hipError_t e = vct_launch_shadow_raster(a, light_vp, S, cur(c).stream);
+    if (e != hipSuccess) { c->shadow_raster.dirty = true; drop_tiles(); HIP_TRY(c, e); }
     c->shadow_ebase = a.vis32_ebase;
     ++c->shadow_passes;
     // depth bounds per (dilated) 8 x 8 tile of the new map: the PCF consumers (voxelizer, G-buffer shade) decide most windows on them
     if (c->shadow_tiles) {
-        const hipError_t et = vct_launch_shadow_minmax(c->shadow, c->shadow_ebase, S, c->shadow_tiles, c->stream);
+        const hipError_t et = vct_launch_shadow_minmax(c->shadow, c->shadow_ebase, S, c->shadow_tiles, cur(c).stream);
         if (et != hipSuccess) { drop_tiles(); HIP_TRY(c, et); }
     }
     return VCT_OK;
@@ -1363,9 +1356,9 @@ int vct_download_shadow_map(vct_ctx* c, float* depth) {
     const size_t n = (size_t)c->shadow_size * c->shadow_size;
     float* tmp = nullptr;
     HIP_TRY(c, hipMalloc(&tmp, n * sizeof(float)));
-    hipError_t e = vct_launch_shadow_decode(c->shadow, tmp, n, c->shadow_ebase, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(depth, tmp, n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    hipError_t e = vct_launch_shadow_decode(c->shadow, tmp, n, c->shadow_ebase, cur(c).stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(depth, tmp, n * sizeof(float), hipMemcpyDeviceToHost, cur(c).stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(cur(c).stream);
     (void)hipFree(tmp);
     HIP_TRY(c, e);
     return VCT_OK;
@@ -1380,8 +1373,8 @@ static int render_gbuffer_rows_on(vct_ctx* c, const float view_proj[16], int32_t
     if (row0 < 0 || row1 > tiles_y(c) || row0 > row1)
         return fail(c, VCT_ERR_INVALID, "vct_render_gbuffer_rows: tile-row range outside the frame");
     HIP_TRY(c, hipSetDevice(c->device));
-    // (two frames in flight: each frame slot has raster scratch of its own -- raster_set_of -- so this pass waits for
-    // nothing of the other slot's frame)
+    // (two frames in flight: each frame slot has raster scratch of its own, so this pass waits for nothing of the other
+    // slot's frame)
     // the form of the visibility stage (vct_ctx.h raster_mode)
     bool binned = c->raster_mode == 2;
     // Automatic choice: six passes -- direct (warm-up: the first pass after an upload pays for cold caches), direct timed,
@@ -1409,7 +1402,8 @@ static int render_gbuffer_rows_on(vct_ctx* c, const float view_proj[16], int32_t
     }
     const bool sampling = c->raster_mode == 0 && c->has_alpha_textures && c->auto_choice < 0 && row1 > row0 && c->auto_state < 6;
     VctRasterArgs a;
-    int rc = raster_args(c, c->cfg.width, c->cfg.height, false, binned, s, a);
+    VctRasterScratch& r = cur(c).raster;
+    int rc = raster_args(c, r, c->cfg.width, c->cfg.height, false, binned, s, a);
     if (rc) return rc;
     if (slot >= 0) HIP_TRY(c, hipEventRecord(c->ev_auto[2 * slot], s));
     hipError_t e = vct_launch_gbuffer_visibility(a, view_proj, c->cfg.width, c->cfg.height, row0, row1, s);
@@ -1418,25 +1412,25 @@ static int render_gbuffer_rows_on(vct_ctx* c, const float view_proj[16], int32_t
     if (e == hipSuccess && shadow_ready) e = hipStreamWaitEvent(s, shadow_ready, 0);
     if (e == hipSuccess)
         e = vct_launch_gbuffer_shade(a, view_proj, c->cfg.width, c->cfg.height, row0, row1, c->shadow, c->shadow_ebase,
-                                     c->shadow_size, c->shadow_tiles, c->light_vp, c->gb_tiled, s);
-    if (e != hipSuccess) { c->raster_dirty[raster_set_of(c)] = true; HIP_TRY(c, e); }
-    c->gb_current = c->gb_tiled;
+                                     c->shadow_size, c->shadow_tiles, c->light_vp, cur(c).gb_tiled, s);
+    if (e != hipSuccess) { r.dirty = true; HIP_TRY(c, e); }
+    cur(c).gb_current = cur(c).gb_tiled;
     c->last_raster_form = binned ? 2 : 1;
-    c->last_row0 = row0;
-    c->last_row1 = row1;
-    c->last_row_stride = 1;
-    c->have_gbuffer = true;
+    cur(c).last_row0 = row0;
+    cur(c).last_row1 = row1;
+    cur(c).last_row_stride = 1;
+    cur(c).have_gbuffer = true;
 #if defined(VCT_BIN_STATS) && VCT_BIN_STATS
     if (binned && getenv("VCT_BIN_STATS_DUMP")) {       // instrumented builds only (tools/r04_binstats.sh)
         uint32_t st[48];
         HIP_TRY(c, hipStreamSynchronize(s));
-        HIP_TRY(c, hipMemcpy(st, c->bin_huge[1] + VCT_BIN_HUGE_CAP, sizeof(st), hipMemcpyDeviceToHost));
-        const uint32_t* cur = st + 8 * (c->bin_set[1] ^ 1);
-        fprintf(stderr, "binstats: entries %u records %u items %u huge %u | ", cur[0], cur[1], cur[2], cur[4]);
+        HIP_TRY(c, hipMemcpy(st, r.bin_huge + VCT_BIN_HUGE_CAP, sizeof(st), hipMemcpyDeviceToHost));
+        const uint32_t* ctr = st + 8 * (r.bin_set ^ 1);
+        fprintf(stderr, "binstats: entries %u records %u items %u huge %u | ", ctr[0], ctr[1], ctr[2], ctr[4]);
         // (the adopted form of k_bin_raster only counts its alpha-queue flushes and the fragments they fetched; the
         // per-step counters of the earlier forms are in profiles/experiments/README.md)
         fprintf(stderr, "alpha_queue_flushes %u fragments_fetched %u\n", st[16 + 7], st[16 + 8]);
-        HIP_TRY(c, hipMemset(c->bin_huge[1] + VCT_BIN_HUGE_CAP + 16, 0, 32 * sizeof(uint32_t)));
+        HIP_TRY(c, hipMemset(r.bin_huge + VCT_BIN_HUGE_CAP + 16, 0, 32 * sizeof(uint32_t)));
     }
 #endif
     return VCT_OK;
@@ -1444,7 +1438,7 @@ static int render_gbuffer_rows_on(vct_ctx* c, const float view_proj[16], int32_t
 
 int vct_render_gbuffer_rows(vct_ctx* c, const float view_proj[16], int32_t row0, int32_t row1) {
     if (!c) return VCT_ERR_INVALID;
-    return render_gbuffer_rows_on(c, view_proj, row0, row1, c->stream);
+    return render_gbuffer_rows_on(c, view_proj, row0, row1, cur(c).stream);
 }
 
 int vct_render_gbuffer(vct_ctx* c, const float view_proj[16]) {
@@ -1457,9 +1451,9 @@ int vct_download_gbuffer(vct_ctx* c, float* planes) {
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t n = (size_t)c->cfg.width * c->cfg.height * VCT_GB_NPLANES;
     if (!c->gb_linear) HIP_TRY(c, hipMalloc(&c->gb_linear, n * sizeof(float)));
-    HIP_TRY(c, vct_launch_untile_gbuffer(c->gb_current, c->gb_linear, c->cfg.width, c->cfg.height, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(planes, c->gb_linear, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, vct_launch_untile_gbuffer(cur(c).gb_current, c->gb_linear, c->cfg.width, c->cfg.height, cur(c).stream));
+    HIP_TRY(c, hipMemcpyAsync(planes, c->gb_linear, n * sizeof(float), hipMemcpyDeviceToHost, cur(c).stream));
+    HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     return VCT_OK;
 }
 
@@ -1477,29 +1471,29 @@ int vct_voxelize(vct_ctx* c, int32_t mode) {
     const size_t nbricks = (size_t)c->cfg.voxel_dim * c->cfg.voxel_dim * c->cfg.voxel_dim / 512;
     if (mode == VCT_VOX_REFERENCE && !c->acc) {       // reference mode's accumulators: allocated on first use, zeroed once
         HIP_TRY(c, hipMalloc(&c->acc, pool_vox * 16));
-        HIP_TRY(c, hipMemsetAsync(c->acc, 0, pool_vox * 16, c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->acc, 0, pool_vox * 16, cur(c).stream));
     }
     if (c->acc_pending) {   // a pass that was never resolved: discard it
-        if (c->acc_mode == VCT_VOX_REFERENCE && c->acc) HIP_TRY(c, hipMemsetAsync(c->acc, 0, pool_vox * 16, c->stream));
-        HIP_TRY(c, hipMemsetAsync(c->brick_flags, 0, nbricks * sizeof(uint32_t), c->stream));
+        if (c->acc_mode == VCT_VOX_REFERENCE && c->acc) HIP_TRY(c, hipMemsetAsync(c->acc, 0, pool_vox * 16, cur(c).stream));
+        HIP_TRY(c, hipMemsetAsync(c->brick_flags, 0, nbricks * sizeof(uint32_t), cur(c).stream));
     }
     VctVoxParams p = vox_params(c);
     p.mode = mode;
     if (mode == VCT_VOX_REFERENCE) {
         glm_voxel_projections(c, p.proj);
-        HIP_TRY(c, vct_launch_voxelize_reference(p, c->ref_big + 1, c->ref_big, c->stream));
+        HIP_TRY(c, vct_launch_voxelize_reference(p, c->ref_big + 1, c->ref_big, cur(c).stream));
     } else {
         if (p.tex.texels && c->n_frags) {
             // every fragment's albedo (texture fetch or material colour): independent of the light, so evaluated once per
             // change of the textures / texture coordinates, not once per pass
             if (!c->frag_alb) { HIP_TRY(c, hipMalloc(&c->frag_alb, (size_t)c->n_frags * 3 * sizeof(float))); c->frag_alb_dirty = true; }
             if (c->frag_alb_dirty) {
-                HIP_TRY(c, vct_launch_frag_geom(p, nullptr, c->frag_alb, c->stream));
+                HIP_TRY(c, vct_launch_frag_geom(p, nullptr, c->frag_alb, cur(c).stream));
                 c->frag_alb_dirty = false;
             }
             p.frag_alb = c->frag_alb;
         }
-        HIP_TRY(c, vct_launch_voxelize(p, c->stream));      // one workgroup per brick: LDS accumulation + resolve into the staging pool
+        HIP_TRY(c, vct_launch_voxelize(p, cur(c).stream));      // one workgroup per brick: LDS accumulation + resolve into the staging pool
     }
     c->acc_pending = true;
     c->acc_mode = mode;
@@ -1513,7 +1507,7 @@ int vct_inject_light(vct_ctx* c) {
     PIPE_TRY(pipeline_join(c));       // level 0 is rewritten: the other slot's trace may still read the chain
     HIP_TRY(c, vct_launch_resolve(c->acc, c->brick_slot, c->chain, c->brick_flags, c->brick_prev, c->cfg.voxel_dim,
                                   c->level0_dirty, nullptr, c->attr_albedo, c->attr_normal,
-                                  c->acc_mode == VCT_VOX_REFERENCE, c->stage, c->stage_albedo, c->stage_normal, c->stream));
+                                  c->acc_mode == VCT_VOX_REFERENCE, c->stage, c->stage_albedo, c->stage_normal, cur(c).stream));
     c->acc_pending = false;
     c->level0_dirty = false;
     c->use_chain_b = false;
@@ -1532,7 +1526,7 @@ static int build_cells(vct_ctx* c) {
         const hipError_t e = hipMalloc(&c->cells, (c->chain_texels - V3) * 32);
         if (e != hipSuccess) { c->cells = nullptr; return fail(c, VCT_ERR_NOMEM, std::string("footprint records: ") + hipGetErrorString(e)); }
     }
-    HIP_TRY(c, vct_launch_build_cells(c->chain, c->cells, c->cfg.voxel_dim, c->stream));
+    HIP_TRY(c, vct_launch_build_cells(c->chain, c->cells, c->cfg.voxel_dim, cur(c).stream));
     c->cells_valid = true;
     return VCT_OK;
 }
@@ -1545,7 +1539,7 @@ int vct_set_footprint_records(vct_ctx* c, int32_t on) {
     if (!c->want_cells) {
         c->cells_valid = false;
         if (c->cells) {
-            HIP_TRY(c, hipStreamSynchronize(c->stream));      // a trace in flight may still read them
+            HIP_TRY(c, hipStreamSynchronize(cur(c).stream));      // a trace in flight may still read them
             (void)hipFree(c->cells);
             c->cells = nullptr;
         }
@@ -1567,11 +1561,11 @@ int vct_build_mips(vct_ctx* c) {
     if (!sparse && c->mip_seen && c->brick_prev)      // dense build: afterwards every brick is "seen" as it is now
         HIP_TRY(c, hipMemcpyAsync(c->mip_seen, c->brick_prev,
                                   ((size_t)c->cfg.voxel_dim * c->cfg.voxel_dim * c->cfg.voxel_dim / 512) * sizeof(uint32_t),
-                                  hipMemcpyDeviceToDevice, c->stream));
+                                  hipMemcpyDeviceToDevice, cur(c).stream));
     HIP_TRY(c, vct_launch_build_mips(c->chain, c->cfg.voxel_dim, sparse ? c->brick_prev : nullptr,
-                                     sparse ? c->mip_seen : nullptr, c->stream));
+                                     sparse ? c->mip_seen : nullptr, cur(c).stream));
     if (!sparse) c->chain_sparse_ready = tracked;
-    if (c->aniso) HIP_TRY(c, vct_launch_build_mips_aniso(c->chain, c->aniso, c->cfg.voxel_dim, c->stream));
+    if (c->aniso) HIP_TRY(c, vct_launch_build_mips_aniso(c->chain, c->aniso, c->cfg.voxel_dim, cur(c).stream));
     c->mips_valid = true;
     c->use_chain_b = false;
     return build_cells(c);
@@ -1597,19 +1591,19 @@ int vct_bounce(vct_ctx* c) {
     bool b_sparse = c->chain_b != nullptr;
     if (!c->chain_b) {
         HIP_TRY(c, hipMalloc(&c->chain_b, c->chain_texels * 4));
-        HIP_TRY(c, hipMemsetAsync(c->chain_b, 0, c->chain_texels * 4, c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->chain_b, 0, c->chain_texels * 4, cur(c).stream));
         HIP_TRY(c, hipMalloc(&c->mip_seen_b, nbricks * sizeof(uint32_t)));
-        HIP_TRY(c, hipMemsetAsync(c->mip_seen_b, 0, nbricks * sizeof(uint32_t), c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->mip_seen_b, 0, nbricks * sizeof(uint32_t), cur(c).stream));
         b_sparse = true;     // zero-filled chain + empty "seen" set: the sparse form is valid from the start
         // occupied-voxel list: surfaces occupy ~1 % of a grid; V^3/8 entries is a generous bound and
         // bricks that do not fit are handled by the per-brick kernel
         c->bounce_list_cap = (uint32_t)(nvox / 8);
         HIP_TRY(c, hipMalloc(&c->bounce_list, ((size_t)c->bounce_list_cap + 1) * sizeof(uint32_t)));
         HIP_TRY(c, hipMalloc(&c->brick_over, nbricks * sizeof(uint32_t)));
-        HIP_TRY(c, hipMemsetAsync(c->brick_over, 0, nbricks * sizeof(uint32_t), c->stream));   // k_bounce_bricks resets what it serves
+        HIP_TRY(c, hipMemsetAsync(c->brick_over, 0, nbricks * sizeof(uint32_t), cur(c).stream));   // k_bounce_bricks resets what it serves
     }
     // only the counter: the list itself needs no clear (the one brick that can straddle its end marks its tail empty)
-    HIP_TRY(c, hipMemsetAsync(c->bounce_list, 0, sizeof(uint32_t), c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->bounce_list, 0, sizeof(uint32_t), cur(c).stream));
     VctTraceParams p;
     fill_march_params(c, p, c->chain);
     p.attr_albedo = c->attr_albedo;
@@ -1625,20 +1619,20 @@ int vct_bounce(vct_ctx* c) {
     p.bounce_list = c->bounce_list + 1;
     p.bounce_list_cap = c->bounce_list_cap;
     p.brick_over = c->brick_over;
-    HIP_TRY(c, hipMemsetAsync(c->step_counter, 0, VCT_STEP_COUNTERS * sizeof(unsigned long long), c->stream));
-    if (c->time_traces) HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-    HIP_TRY(c, vct_launch_bounce(p, c->stream));
-    if (c->time_traces) HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
-    c->last_trace_timed = c->time_traces;
+    HIP_TRY(c, hipMemsetAsync(c->step_counter, 0, VCT_STEP_COUNTERS * sizeof(unsigned long long), cur(c).stream));
+    if (c->time_traces) HIP_TRY(c, hipEventRecord(cur(c).ev0, cur(c).stream));
+    HIP_TRY(c, vct_launch_bounce(p, cur(c).stream));
+    if (c->time_traces) HIP_TRY(c, hipEventRecord(cur(c).ev1, cur(c).stream));
+    cur(c).last_trace_timed = c->time_traces;
     c->last_march_form = c->fast_div ? 2 : 1;
     HIP_TRY(c, vct_launch_build_mips(c->chain_b, c->cfg.voxel_dim, b_sparse ? c->brick_prev : nullptr,
-                                     b_sparse ? c->mip_seen_b : nullptr, c->stream));
+                                     b_sparse ? c->mip_seen_b : nullptr, cur(c).stream));
     // the directional chains always describe the chain the trace reads (the bounce itself gathers
     // from the isotropic bounce-0 chain, like the oracle's vcto_bounce)
-    if (c->aniso) HIP_TRY(c, vct_launch_build_mips_aniso(c->chain_b, c->aniso, c->cfg.voxel_dim, c->stream));
+    if (c->aniso) HIP_TRY(c, vct_launch_build_mips_aniso(c->chain_b, c->aniso, c->cfg.voxel_dim, cur(c).stream));
     c->use_chain_b = true;
-    c->have_trace = true;      // step counter / event pair now describe the bounce launch
-    c->last_was_screen_trace = false;
+    cur(c).have_trace = true;      // step counter / event pair now describe the bounce launch
+    cur(c).last_was_screen_trace = false;
     return VCT_OK;
 }
 
@@ -1657,10 +1651,10 @@ int vct_download_voxel_attributes(vct_ctx* c, uint8_t* albedo, uint8_t* normal) 
     uint32_t* dense = nullptr;          // pooled [slot][512] -> dense Morton volume -> linear staging
     HIP_TRY(c, hipMalloc(&dense, n * 4));
     for (int k = 0; k < 2; ++k) {
-        hipError_t e = vct_launch_unpool(src[k], c->brick_slot, dense, (uint32_t)(n / 512), c->stream);
-        if (e == hipSuccess) e = vct_launch_morton_to_linear(dense, c->staging, V, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(dst[k], c->staging, n * 4, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        hipError_t e = vct_launch_unpool(src[k], c->brick_slot, dense, (uint32_t)(n / 512), cur(c).stream);
+        if (e == hipSuccess) e = vct_launch_morton_to_linear(dense, c->staging, V, cur(c).stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(dst[k], c->staging, n * 4, hipMemcpyDeviceToHost, cur(c).stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(cur(c).stream);
         if (e != hipSuccess) { (void)hipFree(dense); HIP_TRY(c, e); }
     }
     (void)hipFree(dense);
@@ -1690,9 +1684,9 @@ static int upload_levels(vct_ctx* c, const uint8_t* lin, int nlevels) {
     for (int l = 0; l < nlevels; ++l) {
         const int N = V >> l;
         const size_t off = (size_t)vct_level_offset(V, l), n = (size_t)N * N * N;
-        HIP_TRY(c, hipMemcpyAsync(c->staging, lin + off * 4, n * 4, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, vct_launch_linear_to_morton(c->staging, c->chain + off, N, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->staging, lin + off * 4, n * 4, hipMemcpyHostToDevice, cur(c).stream));
+        HIP_TRY(c, vct_launch_linear_to_morton(c->staging, c->chain + off, N, cur(c).stream));
+        HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     }
     return VCT_OK;
 }
@@ -1708,7 +1702,7 @@ int vct_upload_chain_rgba8(vct_ctx* c, const uint8_t* chain) {
     if (!chain) return fail(c, VCT_ERR_INVALID, "vct_upload_chain_rgba8: null chain");
     int rc = upload_levels(c, chain, c->nlev);
     if (rc) return rc;
-    if (c->aniso) HIP_TRY(c, vct_launch_build_mips_aniso(c->chain, c->aniso, c->cfg.voxel_dim, c->stream));
+    if (c->aniso) HIP_TRY(c, vct_launch_build_mips_aniso(c->chain, c->aniso, c->cfg.voxel_dim, cur(c).stream));
     return build_cells(c);
 }
 
@@ -1724,9 +1718,9 @@ int vct_download_aniso_rgba8(vct_ctx* c, uint8_t* out) {
         for (int l = 1; l < c->nlev; ++l) {
             const int N = V >> l;
             const size_t off = (size_t)vct_level_offset(V, l) - V3, n = (size_t)N * N * N;
-            HIP_TRY(c, vct_launch_morton_to_linear(c->aniso + d * stride + off, c->staging, N, c->stream));
-            HIP_TRY(c, hipMemcpyAsync(out + (d * stride + off) * 4, c->staging, n * 4, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            HIP_TRY(c, vct_launch_morton_to_linear(c->aniso + d * stride + off, c->staging, N, cur(c).stream));
+            HIP_TRY(c, hipMemcpyAsync(out + (d * stride + off) * 4, c->staging, n * 4, hipMemcpyDeviceToHost, cur(c).stream));
+            HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
         }
     return VCT_OK;
 }
@@ -1742,9 +1736,9 @@ int vct_download_chain_rgba8(vct_ctx* c, uint8_t* chain) {
         const int N = V >> l;
         const size_t off = (size_t)vct_level_offset(V, l), n = (size_t)N * N * N;
         const uint32_t* active = c->use_chain_b ? c->chain_b : c->chain;
-        HIP_TRY(c, vct_launch_morton_to_linear(active + off, c->staging, N, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(chain + off * 4, c->staging, n * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, vct_launch_morton_to_linear(active + off, c->staging, N, cur(c).stream));
+        HIP_TRY(c, hipMemcpyAsync(chain + off * 4, c->staging, n * 4, hipMemcpyDeviceToHost, cur(c).stream));
+        HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     }
     return VCT_OK;
 }
@@ -1758,11 +1752,11 @@ static int bind_gbuffer(vct_ctx* c, const vct_gbuffer* gb) {
     const size_t npix = (size_t)c->cfg.width * c->cfg.height;
     if (gb->layout == VCT_GB_TILED) {
         if (gb->location == VCT_MEM_DEVICE) {
-            c->gb_current = gb->planes;     // zero-copy: trace reads the caller's HBM buffer
+            cur(c).gb_current = gb->planes;     // zero-copy: trace reads the caller's HBM buffer
         } else {
-            HIP_TRY(c, hipMemcpyAsync(c->gb_tiled, gb->planes, gb_tiled_floats(c) * sizeof(float),
-                                      hipMemcpyHostToDevice, c->stream));
-            c->gb_current = c->gb_tiled;
+            HIP_TRY(c, hipMemcpyAsync(cur(c).gb_tiled, gb->planes, gb_tiled_floats(c) * sizeof(float),
+                                      hipMemcpyHostToDevice, cur(c).stream));
+            cur(c).gb_current = cur(c).gb_tiled;
         }
         return VCT_OK;
     }
@@ -1771,11 +1765,11 @@ static int bind_gbuffer(vct_ctx* c, const vct_gbuffer* gb) {
     if (gb->location == VCT_MEM_HOST) {
         if (!c->gb_linear) HIP_TRY(c, hipMalloc(&c->gb_linear, npix * VCT_GB_NPLANES * sizeof(float)));
         HIP_TRY(c, hipMemcpyAsync(c->gb_linear, gb->planes, npix * VCT_GB_NPLANES * sizeof(float),
-                                  hipMemcpyHostToDevice, c->stream));
+                                  hipMemcpyHostToDevice, cur(c).stream));
         src = c->gb_linear;
     }
-    HIP_TRY(c, vct_launch_tile_gbuffer(src, c->gb_tiled, c->cfg.width, c->cfg.height, c->stream));
-    c->gb_current = c->gb_tiled;
+    HIP_TRY(c, vct_launch_tile_gbuffer(src, cur(c).gb_tiled, c->cfg.width, c->cfg.height, cur(c).stream));
+    cur(c).gb_current = cur(c).gb_tiled;
     return VCT_OK;
 }
 
@@ -1787,7 +1781,7 @@ int vct_trace_slab(vct_ctx* c, const vct_gbuffer* gb, int32_t row0, int32_t row1
     HIP_TRY(c, hipSetDevice(c->device));
     int rc = bind_gbuffer(c, gb);
     if (rc) return rc;
-    c->have_gbuffer = true;
+    cur(c).have_gbuffer = true;
     rc = launch_trace(c, row0, row1);
     if (rc) return rc;
     if (out) {
@@ -1795,14 +1789,14 @@ int vct_trace_slab(vct_ctx* c, const vct_gbuffer* gb, int32_t row0, int32_t row1
         const int y1 = row1 * VCT_TILE < c->cfg.height ? row1 * VCT_TILE : c->cfg.height;
         if (y1 > y0) {
             const size_t off = (size_t)y0 * c->cfg.width * 8, bytes = (size_t)(y1 - y0) * c->cfg.width * 8;
-            const char* src = (const char*)(c->frame_target ? c->frame_target : c->frame);
+            const char* src = (const char*)(cur(c).frame_target ? cur(c).frame_target : cur(c).frame);
             HIP_TRY(c, hipMemcpyAsync((char*)out + off, src + off, bytes,
                                       out_location == VCT_MEM_DEVICE ? hipMemcpyDeviceToDevice
                                                                      : hipMemcpyDeviceToHost,
-                                      c->stream));
+                                      cur(c).stream));
         }
     }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     return VCT_OK;
 }
 
@@ -1813,23 +1807,23 @@ int vct_trace(vct_ctx* c, const vct_gbuffer* gb, void* out, int32_t out_location
 
 int vct_trace_current(vct_ctx* c, void* out, int32_t out_location) {
     if (!c) return VCT_ERR_INVALID;
-    if (!c->have_gbuffer) return fail(c, VCT_ERR_INVALID, "vct_trace_current: no G-buffer resident yet");
+    if (!cur(c).have_gbuffer) return fail(c, VCT_ERR_INVALID, "vct_trace_current: no G-buffer resident yet");
     HIP_TRY(c, hipSetDevice(c->device));
     int rc = launch_trace(c, 0, tiles_y(c));
     if (rc) return rc;
     if (out) {
-        const char* src = (const char*)(c->frame_target ? c->frame_target : c->frame);
+        const char* src = (const char*)(cur(c).frame_target ? cur(c).frame_target : cur(c).frame);
         HIP_TRY(c, hipMemcpyAsync(out, src, (size_t)c->cfg.width * c->cfg.height * 8,
                                   out_location == VCT_MEM_DEVICE ? hipMemcpyDeviceToDevice
-                                                                 : hipMemcpyDeviceToHost, c->stream));
+                                                                 : hipMemcpyDeviceToHost, cur(c).stream));
     }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     return VCT_OK;
 }
 
 int vct_trace_resident_rows(vct_ctx* c, int32_t row0, int32_t row1) {
     if (!c) return VCT_ERR_INVALID;
-    if (!c->have_gbuffer) return fail(c, VCT_ERR_INVALID, "vct_trace_resident_rows: no G-buffer resident yet");
+    if (!cur(c).have_gbuffer) return fail(c, VCT_ERR_INVALID, "vct_trace_resident_rows: no G-buffer resident yet");
     if (row0 < 0 || row1 > tiles_y(c) || row0 > row1)
         return fail(c, VCT_ERR_INVALID, "vct_trace_resident_rows: tile-row range outside the frame");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1838,7 +1832,7 @@ int vct_trace_resident_rows(vct_ctx* c, int32_t row0, int32_t row1) {
 
 int vct_trace_resident_strided(vct_ctx* c, int32_t row0, int32_t row1, int32_t stride) {
     if (!c) return VCT_ERR_INVALID;
-    if (!c->have_gbuffer) return fail(c, VCT_ERR_INVALID, "vct_trace_resident_strided: no G-buffer resident yet");
+    if (!cur(c).have_gbuffer) return fail(c, VCT_ERR_INVALID, "vct_trace_resident_strided: no G-buffer resident yet");
     if (row0 < 0 || row1 > tiles_y(c) || row0 > row1 || stride < 1)
         return fail(c, VCT_ERR_INVALID, "vct_trace_resident_strided: tile-row range outside the frame or stride < 1");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1847,9 +1841,9 @@ int vct_trace_resident_strided(vct_ctx* c, int32_t row0, int32_t row1, int32_t s
 
 int vct_trace_resident(vct_ctx* c) {
     if (!c) return VCT_ERR_INVALID;
-    if (!c->have_gbuffer) return fail(c, VCT_ERR_INVALID, "vct_trace_resident: no G-buffer resident yet");
+    if (!cur(c).have_gbuffer) return fail(c, VCT_ERR_INVALID, "vct_trace_resident: no G-buffer resident yet");
     HIP_TRY(c, hipSetDevice(c->device));
-    return launch_trace(c, c->last_row0, c->last_row1, nullptr, c->last_row_stride, false);
+    return launch_trace(c, cur(c).last_row0, cur(c).last_row1, nullptr, cur(c).last_row_stride, false);
 }
 
 int vct_gi_pass(vct_ctx* c, const float light_vp[16], const float view_proj[16], int32_t mode) {
@@ -1870,10 +1864,10 @@ int vct_gi_pass(vct_ctx* c, const float light_vp[16], const float view_proj[16],
             if (rc1 == VCT_OK) rc1 = vct_voxelize(c, mode);
             if (rc1 == VCT_OK) rc1 = vct_inject_light(c);
             if (rc1 == VCT_OK) rc1 = vct_build_mips(c);
-            if (rc1 == VCT_OK) rc1 = render_gbuffer_rows_on(c, view_proj, row0, row1, c->stream);
+            if (rc1 == VCT_OK) rc1 = render_gbuffer_rows_on(c, view_proj, row0, row1, cur(c).stream);
             if (rc1) return rc1;
             if (rank_ctx) return vct_frame_step(c);
-            return launch_trace(c, c->last_row0, c->last_row1, nullptr, c->last_row_stride, false);
+            return launch_trace(c, cur(c).last_row0, cur(c).last_row1, nullptr, cur(c).last_row_stride, false);
         }
     }
     if (!c->aux_stream) {
@@ -1883,7 +1877,7 @@ int vct_gi_pass(vct_ctx* c, const float light_vp[16], const float view_proj[16],
             HIP_TRY(c, vct_create_masked_stream(&c->aux_stream, c->device, 0, prop.multiProcessorCount - c->reserved_cus));
         } else {
             bool ov = false;      // a stream that shares the context stream's hardware queue would run the two halves in sequence
-            PIPE_TRY(create_overlapping_stream(c, c->stream, &c->aux_stream, &ov));
+            PIPE_TRY(create_overlapping_stream(c, cur(c).stream, &c->aux_stream, &ov));
         }
     }
     if (!c->ev_fork) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
@@ -1891,43 +1885,43 @@ int vct_gi_pass(vct_ctx* c, const float light_vp[16], const float view_proj[16],
     if (!c->ev_join) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
     // fork at once: the main draw's VISIBILITY raster needs nothing of this pass (it has its own lists and words);
     // only its shading kernel reads the shadow map (PCF term), so that alone waits for the shadow pass
-    HIP_TRY(c, hipEventRecord(c->ev_fork, c->stream));                 // everything issued before this call is done
+    HIP_TRY(c, hipEventRecord(c->ev_fork, cur(c).stream));                 // everything issued before this call is done
     HIP_TRY(c, hipStreamWaitEvent(c->aux_stream, c->ev_fork, 0));
     int rc = vct_render_shadow_map(c, light_vp);                       // allocates / sizes the shadow map first
     if (rc) return rc;
-    HIP_TRY(c, hipEventRecord(c->ev_shadow, c->stream));
+    HIP_TRY(c, hipEventRecord(c->ev_shadow, cur(c).stream));
     rc = render_gbuffer_rows_on(c, view_proj, row0, row1, c->aux_stream, c->ev_shadow);
     // join before anything else can fail: later work on the context's stream must see the G-buffer
     const hipError_t ej = hipEventRecord(c->ev_join, c->aux_stream);
     if (rc == VCT_OK) rc = vct_voxelize(c, mode);
     if (rc == VCT_OK) rc = vct_inject_light(c);
     if (rc == VCT_OK) rc = vct_build_mips(c);
-    if (ej == hipSuccess) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
+    if (ej == hipSuccess) HIP_TRY(c, hipStreamWaitEvent(cur(c).stream, c->ev_join, 0));
     else HIP_TRY(c, ej);
     if (rc) return rc;
     if (rank_ctx) return vct_frame_step(c);
-    return launch_trace(c, c->last_row0, c->last_row1, nullptr, c->last_row_stride, false);
+    return launch_trace(c, cur(c).last_row0, cur(c).last_row1, nullptr, cur(c).last_row_stride, false);
 }
 
 int vct_download_frame(vct_ctx* c, void* out) {
     if (!c || !out) return VCT_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
-    const char* src = (const char*)(c->frame_target ? c->frame_target : c->frame);
-    HIP_TRY(c, hipMemcpyAsync(out, src, (size_t)c->cfg.width * c->cfg.height * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const char* src = (const char*)(cur(c).frame_target ? cur(c).frame_target : cur(c).frame);
+    HIP_TRY(c, hipMemcpyAsync(out, src, (size_t)c->cfg.width * c->cfg.height * 8, hipMemcpyDeviceToHost, cur(c).stream));
+    HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     return VCT_OK;
 }
 
 int vct_set_frame_target(vct_ctx* c, void* dev) {
     if (!c) return VCT_ERR_INVALID;
-    c->frame_target = (uint16_t*)dev;
+    cur(c).frame_target = (uint16_t*)dev;
     return VCT_OK;
 }
 
 int vct_synchronize(vct_ctx* c) {
     if (!c) return VCT_ERR_INVALID;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->frames_in_flight > 1) HIP_TRY(c, hipStreamSynchronize(c->slots[1 - c->cur_slot].stream));      // every frame in flight
+    HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
+    if (c->frames_in_flight > 1) HIP_TRY(c, hipStreamSynchronize(other(c).stream));      // every frame in flight
     return VCT_OK;
 }
 
@@ -1947,58 +1941,24 @@ int vct_set_frames_in_flight(vct_ctx* c, int32_t n) {
     if (c->comm) PIPE_TRY(vct_comm_sync(c));      // (deadline-bounded: a frame step in flight may wait for a peer)
     PIPE_TRY(vct_synchronize(c));
     if (n == 1) {
-        // back to one frame: slot 0's set into the context, slot 1's released
-        if (c->cur_slot != 0) { slot_save(c, c->slots[1]); slot_load(c, c->slots[0]); c->cur_slot = 0; }
-        VctFrameSlot& o = c->slots[1];
-        void* ob[] = {o.gb_tiled, o.frame, o.tile_steps, o.aov};
-        for (void* b : ob) if (b) (void)hipFree(b);
-        if (o.ev0) (void)hipEventDestroy(o.ev0);
-        if (o.ev1) (void)hipEventDestroy(o.ev1);
-        if (o.stream) (void)hipStreamDestroy(o.stream);
-        o = VctFrameSlot();
-        // ... and its raster scratch set (vct_ctx.h: set [2], visibility words [1])
-        void** sc[] = {(void**)&c->raster_lists[2], &c->raster_recs[2], (void**)&c->raster_counts[2], (void**)&c->raster_items[2],
-                       &c->bin_recs[2], (void**)&c->bin_entries[2], (void**)&c->bin_count[2], (void**)&c->bin_items[2],
-                       (void**)&c->bin_huge[2], (void**)&c->vis[1]};
-        for (void** q : sc) if (*q) { (void)hipFree(*q); *q = nullptr; }
-        c->raster_item_capacity[2] = c->bin_rec_cap[2] = c->bin_entry_cap[2] = c->bin_bins[2] = c->bin_item_cap[2] = 0u;
-        c->vis_words[1] = 0;
-        c->raster_dirty[2] = true;
-        c->raster_set[2] = c->bin_set[2] = 0;
+        // back to one frame: slot 0 selected first, then slot 1 released with its raster scratch
+        c->cur_slot = 0;
+        slot_release(c->slots[1]);
         c->frames_in_flight = 1;
         c->produced_since_switch = c->joined_since_switch = c->drained_since_switch = false;
         return VCT_OK;
     }
     // a second slot: its own stream, timing events, G-buffer, frame and per-tile step counts (190 MB + 17 MB at 1080p)
-    VctFrameSlot o;
-    const size_t npix = (size_t)c->cfg.width * c->cfg.height, nt = (size_t)tiles_x(c) * tiles_y(c);
-    // the slot's stream: one that demonstrably runs beside the context's stream (create_overlapping_stream)
-    PIPE_TRY(create_overlapping_stream(c, c->stream, &o.stream, &c->slot_streams_overlap));
-    hipError_t e = hipEventCreate(&o.ev0);
-    if (e == hipSuccess) e = hipEventCreate(&o.ev1);
-    if (e == hipSuccess) e = hipMalloc(&o.gb_tiled, gb_tiled_floats(c) * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&o.frame, npix * 8);
-    if (e == hipSuccess) e = hipMalloc(&o.tile_steps, nt * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemsetAsync(o.gb_tiled, 0, gb_tiled_floats(c) * sizeof(float), o.stream);
-    if (e == hipSuccess) e = hipMemsetAsync(o.frame, 0, npix * 8, o.stream);
-    if (e == hipSuccess) e = hipMemsetAsync(o.tile_steps, 0, nt * sizeof(uint32_t), o.stream);
-    const size_t aov_bytes = aov_frames(c->aov_which) * npix * 8;      // the slot's own per-component outputs
-    if (e == hipSuccess && aov_bytes) e = hipMalloc(&o.aov, aov_bytes);
-    if (e == hipSuccess && aov_bytes) e = hipMemsetAsync(o.aov, 0, aov_bytes, o.stream);
+    // on a stream that demonstrably runs beside the context's stream (create_overlapping_stream)
+    hipStream_t stream = nullptr;
+    PIPE_TRY(create_overlapping_stream(c, c->slots[0].stream, &stream, &c->slot_streams_overlap));
+    hipError_t e = slot_create(c, c->slots[1], stream);
     if (e == hipSuccess && !c->ev_xslot) e = hipEventCreateWithFlags(&c->ev_xslot, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipStreamSynchronize(o.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e != hipSuccess) {
-        void* ob[] = {o.gb_tiled, o.frame, o.tile_steps, o.aov};
-        for (void* b : ob) if (b) (void)hipFree(b);
-        if (o.ev0) (void)hipEventDestroy(o.ev0);
-        if (o.ev1) (void)hipEventDestroy(o.ev1);
-        if (o.stream) (void)hipStreamDestroy(o.stream);
+        slot_release(c->slots[1]);
         return fail(c, e == hipErrorOutOfMemory ? VCT_ERR_NOMEM : VCT_ERR_DEVICE, std::string("vct_set_frames_in_flight: ") + hipGetErrorString(e));
     }
-    o.gb_current = o.gb_tiled;
-    c->slots[1] = o;
-    slot_save(c, c->slots[0]);
-    c->cur_slot = 0;
     c->frames_in_flight = 2;
     c->produced_since_switch = c->joined_since_switch = c->drained_since_switch = false;
     return VCT_OK;
@@ -2020,13 +1980,11 @@ int vct_select_frame_slot(vct_ctx* c, int32_t slot) {
     HIP_TRY(c, hipSetDevice(c->device));
     bool waited = false;
     if (c->produced_since_switch) {      // shared state was written on this slot's stream: the other stream's next work follows it
-        HIP_TRY(c, hipEventRecord(c->ev_xslot, c->stream));
+        HIP_TRY(c, hipEventRecord(c->ev_xslot, cur(c).stream));
         HIP_TRY(c, hipStreamWaitEvent(c->slots[slot].stream, c->ev_xslot, 0));
         c->produced_since_switch = false;
         waited = true;
     }
-    slot_save(c, c->slots[c->cur_slot]);
-    slot_load(c, c->slots[slot]);
     c->cur_slot = slot;
     // the stream left behind may hold work the next producer must follow -- unless the wait above already put the selected
     // stream behind all of it (the stream left behind receives nothing more until it is selected again)
@@ -2038,7 +1996,7 @@ int vct_select_frame_slot(vct_ctx* c, int32_t slot) {
 int vct_download_steps(vct_ctx* c, uint8_t* steps) {
     if (!c || !steps) return VCT_ERR_INVALID;
     if (!c->dbg_steps) return fail(c, VCT_ERR_INVALID, "context created without debug_outputs");
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     HIP_TRY(c, hipMemcpy(steps, c->dbg_steps, (size_t)c->cfg.width * c->cfg.height * 7,
                          hipMemcpyDeviceToHost));
     return VCT_OK;
@@ -2047,7 +2005,7 @@ int vct_download_steps(vct_ctx* c, uint8_t* steps) {
 int vct_download_cones(vct_ctx* c, float* cones) {
     if (!c || !cones) return VCT_ERR_INVALID;
     if (!c->dbg_cones) return fail(c, VCT_ERR_INVALID, "context created without debug_outputs");
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     HIP_TRY(c, hipMemcpy(cones, c->dbg_cones, (size_t)c->cfg.width * c->cfg.height * 28 * sizeof(float),
                          hipMemcpyDeviceToHost));
     return VCT_OK;
@@ -2057,14 +2015,14 @@ int vct_download_cones(vct_ctx* c, float* cones) {
 static int row_steps(vct_ctx* c, std::vector<uint64_t>& rows) {
     const int tx = tiles_x(c), ty = tiles_y(c);
     rows.assign((size_t)ty, 0);
-    const int r0 = c->last_row0, r1 = c->last_row1;
+    const int r0 = cur(c).last_row0, r1 = cur(c).last_row1;
     if (r1 <= r0) return VCT_OK;
     const size_t per_row = (size_t)tx;
     std::vector<uint32_t> v(per_row * (size_t)(r1 - r0));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(v.data(), c->tile_steps + per_row * (size_t)r0, v.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
+    HIP_TRY(c, hipMemcpy(v.data(), cur(c).tile_steps + per_row * (size_t)r0, v.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (int r = r0; r < r1; ++r) {
-        if ((r - r0) % c->last_row_stride) continue;          // an interleaved launch: the other rows belong to other ranks
+        if ((r - r0) % cur(c).last_row_stride) continue;          // an interleaved launch: the other rows belong to other ranks
         uint64_t sum = 0;
         const uint32_t* q = v.data() + per_row * (size_t)(r - r0);
         for (size_t i = 0; i < per_row; ++i) sum += q[i];
@@ -2075,16 +2033,16 @@ static int row_steps(vct_ctx* c, std::vector<uint64_t>& rows) {
 
 int vct_last_step_count(vct_ctx* c, uint64_t* steps) {
     if (!c || !steps) return VCT_ERR_INVALID;
-    if (!c->have_trace) return fail(c, VCT_ERR_INVALID, "no trace has run");
+    if (!cur(c).have_trace) return fail(c, VCT_ERR_INVALID, "no trace has run");
     HIP_TRY(c, hipSetDevice(c->device));
     uint64_t sum = 0;
-    if (c->last_was_screen_trace) {
+    if (cur(c).last_was_screen_trace) {
         std::vector<uint64_t> rows;
         const int rc = row_steps(c, rows);
         if (rc) return rc;
         for (uint64_t r : rows) sum += r;
     } else {        // a bounce: its kernels add into the atomic bank
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
         unsigned long long v[VCT_STEP_COUNTERS];
         HIP_TRY(c, hipMemcpy(v, c->step_counter, sizeof(v), hipMemcpyDeviceToHost));
         for (int i = 0; i < VCT_STEP_COUNTERS; ++i) sum += v[i];
@@ -2107,7 +2065,7 @@ int vct_get_stage_counts(vct_ctx* c, uint64_t out[8]) {
         HIP_TRY(c, hipSetDevice(c->device));
         const size_t nbricks = (size_t)c->cfg.voxel_dim * c->cfg.voxel_dim * c->cfg.voxel_dim / 512;
         std::vector<uint32_t> flags(nbricks);
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
         HIP_TRY(c, hipMemcpy(flags.data(), c->brick_prev, nbricks * sizeof(uint32_t), hipMemcpyDeviceToHost));
         uint64_t n = 0;
         for (uint32_t f : flags) n += f != 0u;
@@ -2118,11 +2076,11 @@ int vct_get_stage_counts(vct_ctx* c, uint64_t out[8]) {
 
 int vct_last_row_steps(vct_ctx* c, uint64_t* rows, int32_t nrows) {
     if (!c || !rows) return VCT_ERR_INVALID;
-    if (!c->have_trace || !c->last_was_screen_trace)
+    if (!cur(c).have_trace || !cur(c).last_was_screen_trace)
         return fail(c, VCT_ERR_INVALID, "vct_last_row_steps: the last march was not a screen trace");
     if (nrows != tiles_y(c)) return fail(c, VCT_ERR_INVALID, "vct_last_row_steps: nrows must be the frame's tile rows, ceil(height / 8)");
     // trace_variant 4 stores its step counts per VIRTUAL tile of the compaction list: only their total means anything
-    if (c->last_trace_compacted)
+    if (cur(c).last_trace_compacted)
         return fail(c, VCT_ERR_INVALID, "vct_last_row_steps: the last trace was compacted (config.trace_variant 4): no per-row histogram");
     HIP_TRY(c, hipSetDevice(c->device));
     std::vector<uint64_t> v;
@@ -2135,8 +2093,8 @@ int vct_last_row_steps(vct_ctx* c, uint64_t* rows, int32_t nrows) {
 int vct_last_trace_stats(vct_ctx* c, uint64_t out[16]) {
     if (!c || !out) return VCT_ERR_INVALID;
 #if defined(VCT_STATS) && VCT_STATS
-    if (!c->have_trace) return fail(c, VCT_ERR_INVALID, "no trace has run");
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (!cur(c).have_trace) return fail(c, VCT_ERR_INVALID, "no trace has run");
+    HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     HIP_TRY(c, hipMemcpy(out, c->stats, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return VCT_OK;
 #else
@@ -2153,11 +2111,11 @@ int vct_set_trace_timing(vct_ctx* c, int32_t on) {
 
 int vct_last_trace_ms(vct_ctx* c, float* ms) {
     if (!c || !ms) return VCT_ERR_INVALID;
-    if (!c->have_trace) return fail(c, VCT_ERR_INVALID, "no trace has run");
-    if (!c->last_trace_timed)
+    if (!cur(c).have_trace) return fail(c, VCT_ERR_INVALID, "no trace has run");
+    if (!cur(c).last_trace_timed)
         return fail(c, VCT_ERR_INVALID, "vct_last_trace_ms: the last trace was issued with timing off (vct_set_trace_timing)");
-    HIP_TRY(c, hipEventSynchronize(c->ev1));
-    HIP_TRY(c, hipEventElapsedTime(ms, c->ev0, c->ev1));
+    HIP_TRY(c, hipEventSynchronize(cur(c).ev1));
+    HIP_TRY(c, hipEventElapsedTime(ms, cur(c).ev0, cur(c).ev1));
     return VCT_OK;
 }
 
@@ -2166,11 +2124,11 @@ int vct_selftest_const_divide(vct_ctx* c, float d, uint64_t* mismatches) {
     if (!divisor_ok(d)) return fail(c, VCT_ERR_INVALID, "divisor outside the set the FMA division is proven for");
     HIP_TRY(c, hipSetDevice(c->device));
     // scratch = the statistics words (never the step-counter bank: vct_last_step_count sums that)
-    HIP_TRY(c, hipMemsetAsync(c->stats, 0, 2 * sizeof(unsigned long long), c->stream));
-    HIP_TRY(c, vct_launch_divide_selftest(d, c->stats, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->stats, 0, 2 * sizeof(unsigned long long), cur(c).stream));
+    HIP_TRY(c, vct_launch_divide_selftest(d, c->stats, cur(c).stream));
     unsigned long long v[2] = {0, 0};
-    HIP_TRY(c, hipMemcpyAsync(v, c->stats, sizeof(v), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpyAsync(v, c->stats, sizeof(v), hipMemcpyDeviceToHost, cur(c).stream));
+    HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     *mismatches = v[0];
     if (v[0]) {      // not a failure of the call: leave one offending x readable for diagnosis
         char msg[96];
@@ -2195,12 +2153,12 @@ int vct_selftest_texel_buffer(vct_ctx* c, uint64_t* mismatches) {
     }
     uint32_t* d = nullptr;
     HIP_TRY(c, hipMalloc(&d, h.size() * sizeof(uint32_t)));
-    hipError_t e = hipMemcpyAsync(d, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(c->stats, 0, 2 * sizeof(unsigned long long), c->stream);
-    if (e == hipSuccess) e = vct_launch_texel_buffer_selftest(d, (uint32_t)h.size(), c->stats, c->stream);
+    hipError_t e = hipMemcpyAsync(d, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice, cur(c).stream);
+    if (e == hipSuccess) e = hipMemsetAsync(c->stats, 0, 2 * sizeof(unsigned long long), cur(c).stream);
+    if (e == hipSuccess) e = vct_launch_texel_buffer_selftest(d, (uint32_t)h.size(), c->stats, cur(c).stream);
     unsigned long long v[2] = {0, 0};
-    if (e == hipSuccess) e = hipMemcpyAsync(v, c->stats, sizeof(v), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(v, c->stats, sizeof(v), hipMemcpyDeviceToHost, cur(c).stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(cur(c).stream);
     (void)hipFree(d);
     HIP_TRY(c, e);
     *mismatches = v[0];
@@ -2215,11 +2173,11 @@ int vct_selftest_texel_buffer(vct_ctx* c, uint64_t* mismatches) {
 int vct_selftest_area_divide(vct_ctx* c, uint64_t seed, uint64_t count, uint64_t* mismatches) {
     if (!c || !mismatches) return VCT_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemsetAsync(c->stats, 0, 2 * sizeof(unsigned long long), c->stream));
-    HIP_TRY(c, vct_launch_area_divide_selftest(seed, count, c->stats, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->stats, 0, 2 * sizeof(unsigned long long), cur(c).stream));
+    HIP_TRY(c, vct_launch_area_divide_selftest(seed, count, c->stats, cur(c).stream));
     unsigned long long v[2] = {0, 0};
-    HIP_TRY(c, hipMemcpyAsync(v, c->stats, sizeof(v), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpyAsync(v, c->stats, sizeof(v), hipMemcpyDeviceToHost, cur(c).stream));
+    HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     *mismatches = v[0];
     if (v[0]) {
         char msg[96];
@@ -2232,7 +2190,7 @@ int vct_selftest_area_divide(vct_ctx* c, uint64_t seed, uint64_t count, uint64_t
 
 int vct_get_stream(vct_ctx* c, void** s) {
     if (!c || !s) return VCT_ERR_INVALID;
-    *s = (void*)c->stream;
+    *s = (void*)cur(c).stream;
     return VCT_OK;
 }
 
@@ -2263,24 +2221,21 @@ int vct_set_aov_outputs(vct_ctx* c, uint32_t which) {
     if (which == c->aov_which) return VCT_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     PIPE_TRY(vct_synchronize(c));            // the buffers being replaced may still be written
-    // every slot's set, allocated here and never in a launch; the selected slot's set lives in the context fields
+    // every live slot's set, allocated here and never in a launch
     const size_t bytes = aov_frames(which) * (size_t)c->cfg.width * c->cfg.height * 8;
-    uint16_t** sets[2] = {&c->aov, c->frames_in_flight > 1 ? &c->slots[1 - c->cur_slot].aov : nullptr};
     uint16_t* fresh[2] = {nullptr, nullptr};
     hipError_t e = hipSuccess;
-    for (int k = 0; k < 2 && e == hipSuccess; ++k) {
-        if (!sets[k] || !bytes) continue;
+    for (int k = 0; k < c->frames_in_flight && bytes && e == hipSuccess; ++k) {
         e = hipMalloc(&fresh[k], bytes);
         if (e == hipSuccess) e = hipMemset(fresh[k], 0, bytes);
     }
-    if (e != hipSuccess) {          // all or nothing: the old set stays
+    if (e != hipSuccess) {          // all or nothing: the old sets stay
         for (uint16_t* b : fresh) if (b) (void)hipFree(b);
         return fail(c, e == hipErrorOutOfMemory ? VCT_ERR_NOMEM : VCT_ERR_DEVICE, std::string("vct_set_aov_outputs: ") + hipGetErrorString(e));
     }
-    for (int k = 0; k < 2; ++k) {
-        if (!sets[k]) continue;
-        if (*sets[k]) (void)hipFree(*sets[k]);
-        *sets[k] = fresh[k];
+    for (int k = 0; k < c->frames_in_flight; ++k) {
+        if (c->slots[k].aov) (void)hipFree(c->slots[k].aov);
+        c->slots[k].aov = fresh[k];
     }
     c->aov_which = which;
     return VCT_OK;
@@ -2288,8 +2243,8 @@ int vct_set_aov_outputs(vct_ctx* c, uint32_t which) {
 
 // the output `bit` of the selected slot: device address (null when the bit is not exactly one output that is on)
 static uint16_t* aov_of(const vct_ctx* c, uint32_t bit) {
-    if (bit == 0 || (bit & (bit - 1)) || !(c->aov_which & bit) || !c->aov) return nullptr;
-    return c->aov + aov_frames(c->aov_which & (bit - 1)) * (size_t)c->cfg.width * c->cfg.height * 4;
+    if (bit == 0 || (bit & (bit - 1)) || !(c->aov_which & bit) || !cur(c).aov) return nullptr;
+    return cur(c).aov + aov_frames(c->aov_which & (bit - 1)) * (size_t)c->cfg.width * c->cfg.height * 4;
 }
 
 int vct_download_aov(vct_ctx* c, uint32_t bit, void* out) {
@@ -2297,8 +2252,8 @@ int vct_download_aov(vct_ctx* c, uint32_t bit, void* out) {
     const uint16_t* src = aov_of(c, bit);
     if (!src) return fail(c, VCT_ERR_INVALID, "vct_download_aov: not one output that vct_set_aov_outputs turned on");
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(out, src, (size_t)c->cfg.width * c->cfg.height * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out, src, (size_t)c->cfg.width * c->cfg.height * 8, hipMemcpyDeviceToHost, cur(c).stream));
+    HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     return VCT_OK;
 }
 
@@ -2313,7 +2268,7 @@ int vct_get_aov_device(vct_ctx* c, uint32_t bit, void** p, size_t* bytes) {
 
 int vct_get_frame_device(vct_ctx* c, void** p, size_t* bytes) {
     if (!c || !p) return VCT_ERR_INVALID;
-    *p = c->frame_target ? c->frame_target : c->frame;
+    *p = cur(c).frame_target ? cur(c).frame_target : cur(c).frame;
     if (bytes) *bytes = (size_t)c->cfg.width * c->cfg.height * 8;
     return VCT_OK;
 }

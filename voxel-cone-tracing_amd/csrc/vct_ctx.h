@@ -15,37 +15,69 @@ struct vct_comm;      // multi-GPU state (vct_multi.hip)
 // (k_raster_mid 658 us instead of 60 beside a trace), and RCCL's gather kernel is such a queue.
 hipError_t vct_create_masked_stream(hipStream_t* s, int device, int first_cu, int last_cu);
 
+// Scratch of one kind of raster pass (vct_capi.hip raster_args).  Between passes every visibility word is all-ones and
+// the counter set of the next pass is zero: the kernels re-establish both themselves (vct_raster.hip run_visibility), so
+// a pass launches no memset.  `dirty` (a launch failed, or nothing is initialised yet) makes the next pass clear
+// everything once.  The shadow pass and the main draw have scratch of their own, so that the main draw's visibility
+// raster can run on the second stream WHILE the shadow map is rasterised (vct_gi_pass); the shadow pass writes the
+// shadow-map words and leaves `vis` unused.
+struct VctRasterScratch {
+    // direct form
+    int32_t* lists = nullptr;           // [2*ntri] wave list, [2*ntri] group list
+    void* recs = nullptr;               // [2*ntri] 96-byte set-up records handed from k_raster_vis to k_raster_mid
+    uint32_t* counts = nullptr;         // two sets of [tile work items, wave list, group list, pad]
+    int set = 0;                        // the counter set the next pass uses
+    uint2* items = nullptr;
+    uint32_t item_capacity = 0;
+    // tile-binned form (vct_raster.hip), see VctRasterArgs
+    void* bin_recs = nullptr;
+    uint32_t bin_rec_cap = 0;
+    uint2* bin_entries = nullptr;
+    uint32_t bin_entry_cap = 0;
+    uint32_t* bin_count = nullptr;      // count + cursor, [2 * bins * VCT_BIN_CSTRIDE]
+    uint32_t bin_bins = 0;
+    uint4* bin_items = nullptr;
+    uint32_t bin_item_cap = 0;
+    uint32_t* bin_huge = nullptr;       // huge list [VCT_BIN_HUGE_CAP] + two counter sets [16] behind it
+    int bin_set = 0;
+    unsigned long long* vis = nullptr;  // 64-bit visibility words of the main draw
+    size_t vis_words = 0;
+    bool dirty = true;
+};
+
 // Two frames in flight (vct_set_frames_in_flight, round 6).  A whole-frame trace launch pays ~20 us of ramp and drain
 // (the last generation of workgroups leaves compute units idle, tools/quant_probe.py) plus the dispatch gap to the next
 // kernel of its stream: 4-5 % of a 0.61 ms frame.  A renderer that starts frame k + 1 on a second stream while frame k
 // drains gets that back (tools/pipe_probe.py: trace 0.626 -> 0.598 ms per frame, Render() 0.773 -> 0.738 at
 // configs[1]) -- what the reference's GL driver does with consecutive frames of its command queue.  What a frame owns
-// -- stream, G-buffer, output frame, per-tile step counts, timing events, "last launch" bookkeeping -- exists once per
-// SLOT; vct_select_frame_slot swaps a slot's set into the context fields of the same names, so every entry point works
-// on the selected slot unchanged; the main draw's raster scratch exists per slot too (set [2] below), so a frame's
-// G-buffer pass needs nothing of the other frame's.  Everything else (chain, shadow map, mesh) is shared, ordered by
-// events: a stage that WRITES shared state (uploads, shadow map, inject, mips, bounce) waits for everything the other
-// slot has in flight (pipeline_join), and the next slot switch makes the other stream wait for that stage.
+// exists once per SLOT, below; every entry point works on the selected slot (cur(c)).  The main draw's raster scratch is
+// part of the slot, so frame k + 1's G-buffer pass needs nothing of frame k's and the two overlap.  Everything else
+// (chain, shadow map, mesh) is shared, ordered by events: a stage that WRITES shared state (uploads, shadow map, inject,
+// mips, bounce) waits for everything the other slot has in flight (pipeline_join), and the next slot switch makes the
+// other stream wait for that stage.  Slot 0's stream is the context's stream.
 struct VctFrameSlot {
     hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    float* gb_tiled = nullptr;
-    const float* gb_current = nullptr;
-    uint16_t* frame = nullptr;
-    uint16_t* frame_target = nullptr;
-    uint32_t* tile_steps = nullptr;
-    uint16_t* aov = nullptr;            // per-component outputs of the slot (vct_set_aov_outputs): the frames that are on, in bit order
-    int last_row0 = 0, last_row1 = 0, last_row_stride = 1;
-    bool have_trace = false, last_trace_compacted = false, last_was_screen_trace = false, have_gbuffer = false;
-    bool last_trace_timed = false;      // the slot's last march launch was bracketed by its timing events
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // timing events of the march launches (vct_last_trace_ms)
+    float* gb_tiled = nullptr;          // [tiles][23][64]
+    const float* gb_current = nullptr;  // tiled buffer the next resident trace reads
+    uint16_t* frame = nullptr;          // RGBA16F [h][w][4]
+    uint16_t* frame_target = nullptr;   // caller-owned output (vct_set_frame_target) or null
+    uint32_t* tile_steps = nullptr;     // [tiles] executed steps per 8x8 tile of the screen trace
+    uint16_t* aov = nullptr;            // per-component outputs (vct_set_aov_outputs): popcount(aov_which) frames, bit order
+    int last_row0 = 0, last_row1 = 0;
+    int last_row_stride = 1;            // the last screen trace took every last_row_stride-th tile row of [last_row0, last_row1)
+    bool have_trace = false;
+    bool last_trace_timed = false;      // the last march launch was bracketed by the timing events
+    bool last_trace_compacted = false;  // ... of trace_variant 4: counts per virtual tile, no per-row histogram
+    bool last_was_screen_trace = false; // the step counters hold a screen trace (indexed by tile row), not a bounce
+    bool have_gbuffer = false;          // a G-buffer is resident (uploaded by vct_trace or rendered)
+    VctRasterScratch raster;            // the main draw's
 };
 
 struct vct_ctx {
     vct_config cfg;
     int device = 0;
-    hipStream_t stream = nullptr;
     int reserved_cus = 0;             // VCT_COMM_RESERVED_CUS at vct_create: CUs kept for the communication stream
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::string err;
 
     uint32_t* chain = nullptr;        // Morton chain (bounce 0: direct light)
@@ -64,19 +96,13 @@ struct vct_ctx {
     int nlev = 0;
 
     float* gb_linear = nullptr;       // [23][w*h] staging
-    float* gb_tiled = nullptr;        // [tiles][23][64]
-    const float* gb_current = nullptr;   // tiled buffer the next resident trace reads
-    uint16_t* frame = nullptr;        // RGBA16F [h][w][4]
-    uint16_t* frame_target = nullptr; // caller-owned output (vct_set_frame_target) or null
     // lighting components (vct_set_lighting_components): VCT_SHOW_* mask of the composite; per-component outputs
-    // (vct_set_aov_outputs): VCT_AOV_* bits, the selected slot's buffer (popcount(aov_which) frames, bit order)
+    // (vct_set_aov_outputs): VCT_AOV_* bits, one buffer per frame slot (VctFrameSlot::aov)
     uint32_t show_mask = VCT_SHOW_ALL;
     uint32_t aov_which = 0;
-    uint16_t* aov = nullptr;
     uint8_t* dbg_steps = nullptr;
     float* dbg_cones = nullptr;
     unsigned long long* step_counter = nullptr;   // [VCT_STEP_COUNTERS] atomic bank of the bounce kernels (memset before each bounce)
-    uint32_t* tile_steps = nullptr;               // [tiles] executed steps per 8x8 tile of the screen trace
     unsigned long long* stats = nullptr;      // [8] march statistics of instrumented builds (VCT_STATS)
     uint32_t* vt_pix = nullptr;       // trace_variant 4: compaction list [tiles][64] + the virtual-tile counter behind it
     VctStep* steps_dev = nullptr;     // [2][VCT_MAX_STEPS]
@@ -85,16 +111,10 @@ struct vct_ctx {
     bool steps_dirty = true;
     bool fast_div = false;            // set by refresh_steps: constant divisors admit the FMA division
     int last_march_form = 0;          // division of the last march launch: 1 IEEE, 2 verified product, 3 x * r (vct_get_stage_counts [2])
-    int last_row0 = 0, last_row1 = 0;
-    int last_row_stride = 1;          // the last screen trace took every last_row_stride-th tile row of [last_row0, last_row1)
-    bool have_trace = false;
     // vct_set_trace_timing: bracket every march launch with the two timing events vct_last_trace_ms reads.  On by default
     // (every entry point keeps working); a frame loop switches it off -- the two events cost a launch ~7 us of dispatch
     // gaps on this GPU (one-stream step 0.549 -> 0.542 ms, a 1/8 slab's 0.12 ms step the same 7 us).
-    bool time_traces = true, last_trace_timed = false;
-    bool last_trace_compacted = false;    // ... of trace_variant 4: counts per virtual tile, no per-row histogram
-    bool last_was_screen_trace = false;   // the step counters hold a screen trace (indexed by tile row), not a bounce
-    bool have_gbuffer = false;        // a G-buffer is resident (uploaded by vct_trace or rendered)
+    bool time_traces = true;
 
     float cam[3] = {0.0f, 4.0f, 0.0f};        // VCT.h:8
     float light[3] = {0.0f, 1.0f, 0.25f};     // VCT.h:14
@@ -122,23 +142,7 @@ struct vct_ctx {
     VctTexDesc* tex_desc = nullptr;
     int32_t* mat_tex = nullptr;
     int32_t ntex = 0;
-    // raster scratch.  Between passes every visibility word is all-ones and the counter set of the next pass is
-    // zero: the kernels re-establish both themselves (vct_raster.hip run_visibility), so a pass launches no memset.
-    // `raster_dirty` (a launch failed, or nothing is initialised yet) makes the next pass clear everything once.
-    // Scratch SETS: [0] the shadow pass, [1] the main draw, [2] the main draw of the second frame slot (two frames in flight:
-    // frame k + 1's G-buffer pass then needs nothing of frame k's and the two overlap, vct_capi.hip raster_set_of)
-    unsigned long long* vis[2] = {nullptr, nullptr};   // 64-bit words of the main draw, per frame slot
-    size_t vis_words[2] = {0, 0};
-    // lists / counters / tile items exist twice, [0] for the shadow pass and [1] for the main draw, so that the main
-    // draw's visibility raster can run on the second stream WHILE the shadow map is rasterised (vct_gi_pass)
-    int32_t* raster_lists[3] = {nullptr, nullptr, nullptr};     // [2*ntri] wave list, [2*ntri] group list
-    void* raster_recs[3] = {nullptr, nullptr, nullptr};         // [2*ntri] 96-byte set-up records handed from k_raster_vis to k_raster_mid
-    uint32_t* raster_counts[3] = {nullptr, nullptr, nullptr};   // two sets of [tile work items, wave list, group list, pad]
-    int raster_set[3] = {0, 0, 0};                        // the counter set the next pass of that kind uses
-    bool raster_dirty[3] = {true, true, true};
-    uint2* raster_items[3] = {nullptr, nullptr, nullptr};
-    uint32_t raster_item_capacity[3] = {0, 0, 0};
-    // tile-binned visibility (vct_raster.hip): scratch per pass kind ([0] shadow pass, [1] main draw), see VctRasterArgs
+    VctRasterScratch shadow_raster;    // scratch of the shadow pass (the main draw's is per frame slot)
     // Which form the MAIN draw's visibility takes (the shadow pass is opaque and sparse: the direct form won every
     // measurement).  raster_mode 0 = auto: scenes without alpha-tested textures keep the direct form; otherwise the first
     // pass runs direct, the second -- over the same tile rows -- binned, both between events, and the faster one is kept
@@ -151,16 +155,6 @@ struct vct_ctx {
     int auto_choice = -1;                              // -1 undecided, 0 direct, 1 binned
     hipEvent_t ev_auto[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // begin / end of the four timed samples
     bool has_alpha_textures = false;
-    void* bin_recs[3] = {nullptr, nullptr, nullptr};
-    uint32_t bin_rec_cap[3] = {0, 0, 0};
-    uint2* bin_entries[3] = {nullptr, nullptr, nullptr};
-    uint32_t bin_entry_cap[3] = {0, 0, 0};
-    uint32_t* bin_count[3] = {nullptr, nullptr, nullptr};       // count + cursor, [2 * bins * VCT_BIN_CSTRIDE]
-    uint32_t bin_bins[3] = {0, 0, 0};
-    uint4* bin_items[3] = {nullptr, nullptr, nullptr};
-    uint32_t bin_item_cap[3] = {0, 0, 0};
-    uint32_t* bin_huge[3] = {nullptr, nullptr, nullptr};        // huge list [VCT_BIN_HUGE_CAP] + two counter sets [16] behind it
-    int bin_set[3] = {0, 0, 0};
     // second stream: vct_gi_pass runs the G-buffer raster beside the voxel stages
     hipStream_t aux_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_shadow = nullptr, ev_join = nullptr;
@@ -203,7 +197,7 @@ struct vct_ctx {
     int32_t* ref_big = nullptr;        // reference mode: triangles left to the workgroup pass (+ counter)
     bool level0_dirty = false;         // level 0 was written by an upload: next resolve is dense
     vct_comm* comm = nullptr;          // multi-GPU slabs + gather (vct_comm_init)
-    // frame slots (see VctFrameSlot): slots[cur_slot] is STALE while selected -- its live values are the context fields
+    // frame slots (see VctFrameSlot): slots [0, frames_in_flight) are live, slots[cur_slot] is selected
     int frames_in_flight = 1;          // 1 or 2
     int cur_slot = 0;
     VctFrameSlot slots[2];
@@ -215,6 +209,11 @@ struct vct_ctx {
     // in a row -- paid five cross-queue waits per pass for nothing (0.860 ms against 0.817 on one slot).
     bool joined_since_switch = false, drained_since_switch = false;
 };
+
+// the selected frame slot, and the other one (meaningful with two frames in flight)
+inline VctFrameSlot& cur(vct_ctx* c) { return c->slots[c->cur_slot]; }
+inline const VctFrameSlot& cur(const vct_ctx* c) { return c->slots[c->cur_slot]; }
+inline VctFrameSlot& other(vct_ctx* c) { return c->slots[1 - c->cur_slot]; }
 
 // shared helpers (vct_capi.hip)
 int vct_fail(vct_ctx* c, int code, const std::string& msg);

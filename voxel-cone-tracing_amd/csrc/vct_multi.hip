@@ -246,8 +246,8 @@ static void comm_free(vct_comm* m) {
 void vct_comm_release(vct_ctx* c) {
     if (!c || !c->comm) return;
     // (frame slots may have been added or switched since vct_comm_init: the streams that carry this communicator's work NOW)
-    c->comm->ctx_stream = c->stream;
-    c->comm->ctx_stream2 = c->frames_in_flight > 1 ? c->slots[1 - c->cur_slot].stream : nullptr;
+    c->comm->ctx_stream = cur(c).stream;
+    c->comm->ctx_stream2 = c->frames_in_flight > 1 ? other(c).stream : nullptr;
     comm_free(c->comm);
     c->comm = nullptr;
 }
@@ -405,10 +405,10 @@ int vct_comm_init(vct_ctx* c, const void* id128, int32_t rank, int32_t world) {
         // the exchange step is meant to run beside the next frame's trace: a stream that shares the context stream's hardware
         // queue would run behind it instead (round 6: HIP hands out four queues; RCCL and torch hold streams of their own)
         bool ov = false;
-        e = vct_create_overlapping_stream(c, c->stream, &m->comm_stream, &ov) == VCT_OK ? hipSuccess : hipErrorUnknown;
+        e = vct_create_overlapping_stream(c, cur(c).stream, &m->comm_stream, &ov) == VCT_OK ? hipSuccess : hipErrorUnknown;
         m->comm_stream_overlaps = ov;
     }
-    m->ctx_stream = c->stream;
+    m->ctx_stream = cur(c).stream;
     if (direct && e == hipSuccess) {
         int khz = 0;
         if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->device) == hipSuccess && khz > 0) m->wall_khz = khz;
@@ -423,15 +423,15 @@ int vct_comm_init(vct_ctx* c, const void* id128, int32_t rank, int32_t world) {
             // are allocated fine-grained (advisor, round 5); no fallback -- a coarse-grained frame could be silently stale.
             e = direct ? hipExtMallocWithFlags((void**)&m->buf[k], m->buf_halves * 2, hipDeviceMallocFinegrained)
                        : hipMalloc(&m->buf[k], m->buf_halves * 2);
-            if (e == hipSuccess) e = hipMemsetAsync(m->buf[k], 0, m->buf_halves * 2, c->stream);
+            if (e == hipSuccess) e = hipMemsetAsync(m->buf[k], 0, m->buf_halves * 2, cur(c).stream);
         }
         if (e == hipSuccess) e = hipEventCreateWithFlags(&m->traced[k], hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&m->gathered[k], hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreate(&m->g0[k]);
         if (e == hipSuccess) e = hipEventCreate(&m->g1[k]);
-        if (e == hipSuccess) e = hipEventRecord(m->gathered[k], c->stream);      // "previous gather" of the first use
+        if (e == hipSuccess) e = hipEventRecord(m->gathered[k], cur(c).stream);      // "previous gather" of the first use
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(cur(c).stream);
     if (e != hipSuccess) {
         comm_free(m);
         return vct_fail(c, e == hipErrorOutOfMemory ? VCT_ERR_NOMEM : VCT_ERR_DEVICE,
@@ -555,7 +555,7 @@ int vct_frame_step(vct_ctx* c) {
     vct_comm* m = c->comm;
     if (!m) return vct_fail(c, VCT_ERR_INVALID, "vct_frame_step: call vct_comm_init first");
     if (m->broken || (!m->comm && !m->direct)) return vct_fail(c, VCT_ERR_DEVICE, "vct_frame_step: the communicator was aborted (vct_comm_destroy, then vct_comm_init again)");
-    if (!c->have_gbuffer) return vct_fail(c, VCT_ERR_INVALID, "vct_frame_step: no G-buffer resident yet");
+    if (!cur(c).have_gbuffer) return vct_fail(c, VCT_ERR_INVALID, "vct_frame_step: no G-buffer resident yet");
     HIP_TRY(c, hipSetDevice(c->device));
     const int k = (int)(m->frames & 1ull);
     // This rank's slab inside buffer k.  The kernel addresses the full frame, so it gets the slab's address minus the
@@ -563,7 +563,7 @@ int vct_frame_step(vct_ctx* c) {
     // that address lies before the allocation).  Root: the frame buffer itself (slab 0 at offset 0, in-place gather).
     uint16_t* slab = m->buf[k];
     const size_t first_row_halves = (size_t)m->row0 * VCT_TILE * c->cfg.width * 4;
-    HIP_TRY(c, hipStreamWaitEvent(c->stream, m->gathered[k], 0));    // buffer k is free once its last gather is done
+    HIP_TRY(c, hipStreamWaitEvent(cur(c).stream, m->gathered[k], 0));    // buffer k is free once its last gather is done
     const bool uneven = !m->starts.empty();
     if (m->direct) {
         // direct slabs (see DirectShm): flags instead of a collective, the slab stored straight into the root's frame
@@ -571,15 +571,15 @@ int vct_frame_step(vct_ctx* c) {
         const long long ticks = (long long)m->timeout_ms * m->wall_khz;        // wall_clock64 ticks per ms = its rate in kHz
         const size_t row_halves = (size_t)VCT_TILE * c->cfg.width * 4;
         if (m->rank == 0) {
-            hipLaunchKernelGGL(k_flag_set, dim3(1), dim3(1), 0, c->stream, &m->shm_dev->release[k], gen - 1u);
+            hipLaunchKernelGGL(k_flag_set, dim3(1), dim3(1), 0, cur(c).stream, &m->shm_dev->release[k], gen - 1u);
             HIP_TRY(c, hipGetLastError());
             uint16_t* base = uneven ? m->buf[k] : slab - first_row_halves;
             const int rc = m->interleaved ? vct_launch_trace_rows(c, m->row0, m->row1, slab, m->world, true)
                                           : vct_launch_trace_rows(c, m->row0, m->row1, base);
             if (rc) return rc;
-            const hipStream_t cs = m->same_stream ? c->stream : m->comm_stream;
+            const hipStream_t cs = m->same_stream ? cur(c).stream : m->comm_stream;
             if (!m->same_stream) {
-                HIP_TRY(c, hipEventRecord(m->traced[k], c->stream));
+                HIP_TRY(c, hipEventRecord(m->traced[k], cur(c).stream));
                 HIP_TRY(c, hipStreamWaitEvent(m->comm_stream, m->traced[k], 0));
             }
             HIP_TRY(c, hipEventRecord(m->g0[k], cs));
@@ -596,7 +596,7 @@ int vct_frame_step(vct_ctx* c) {
             HIP_TRY(c, hipEventRecord(m->g1[k], cs));
             HIP_TRY(c, hipEventRecord(m->gathered[k], cs));
         } else {
-            hipLaunchKernelGGL(k_flag_wait, dim3(1), dim3(64), 0, c->stream, &m->shm_dev->release[k], 1, 1, gen - 1u,
+            hipLaunchKernelGGL(k_flag_wait, dim3(1), dim3(64), 0, cur(c).stream, &m->shm_dev->release[k], 1, 1, gen - 1u,
                                &m->shm_dev->timed_out, ticks, m->abort_dev);
             HIP_TRY(c, hipGetLastError());
             // where this rank's slab lives in the root's buffer k: packed slab `rank` (equal / interleaved) or its own rows
@@ -604,11 +604,11 @@ int vct_frame_step(vct_ctx* c) {
             const int rc = m->interleaved ? vct_launch_trace_rows(c, m->row0, m->row1, peer_slab, m->world, true)
                                           : vct_launch_trace_rows(c, m->row0, m->row1, peer_slab - first_row_halves);
             if (rc) return rc;
-            HIP_TRY(c, hipEventRecord(m->g0[k], c->stream));
-            hipLaunchKernelGGL(k_flag_set, dim3(1), dim3(1), 0, c->stream, &m->shm_dev->done[k][m->rank], gen);
+            HIP_TRY(c, hipEventRecord(m->g0[k], cur(c).stream));
+            hipLaunchKernelGGL(k_flag_set, dim3(1), dim3(1), 0, cur(c).stream, &m->shm_dev->done[k][m->rank], gen);
             HIP_TRY(c, hipGetLastError());
-            HIP_TRY(c, hipEventRecord(m->g1[k], c->stream));
-            HIP_TRY(c, hipEventRecord(m->gathered[k], c->stream));
+            HIP_TRY(c, hipEventRecord(m->g1[k], cur(c).stream));
+            HIP_TRY(c, hipEventRecord(m->gathered[k], cur(c).stream));
         }
         m->last = k;
         ++m->frames;
@@ -619,9 +619,9 @@ int vct_frame_step(vct_ctx* c) {
     const int rc = m->interleaved ? vct_launch_trace_rows(c, m->row0, m->row1, slab, m->world, true)
                                   : vct_launch_trace_rows(c, m->row0, m->row1, out_base);     // an empty slab launches nothing
     if (rc) return rc;
-    const hipStream_t cs = m->same_stream ? c->stream : m->comm_stream;
+    const hipStream_t cs = m->same_stream ? cur(c).stream : m->comm_stream;
     if (!m->same_stream) {
-        HIP_TRY(c, hipEventRecord(m->traced[k], c->stream));
+        HIP_TRY(c, hipEventRecord(m->traced[k], cur(c).stream));
         HIP_TRY(c, hipStreamWaitEvent(m->comm_stream, m->traced[k], 0));
     }
     Rccl* r = rccl();
@@ -675,7 +675,7 @@ int vct_comm_sync(vct_ctx* c) {
     HIP_TRY(c, hipSetDevice(c->device));
     // BOTH streams are polled under the deadline: with frames issued back to back the context stream itself waits on
     // gathered[k] (vct_frame_step), i.e. behind a collective a dead peer never finishes -- a blocking
-    // hipStreamSynchronize(c->stream) here would hang before the deadline loop was ever reached.
+    // hipStreamSynchronize of the context stream here would hang before the deadline loop was ever reached.
     // After the abort below the stuck collective's kernel ends, its event completes and both streams drain.
     // Compute queued on the context's stream in front of the exchange (several 4K / 1024^3 GI passes, a first-use divisor
     // self-test) is not communication: it gets a deadline of its own -- the last step's "slab traced" event -- and the
@@ -693,10 +693,10 @@ int vct_comm_sync(vct_ctx* c) {
     const auto t0 = std::chrono::steady_clock::now();
     int spins = 0;
     while (true) {
-        hipError_t qc = hipStreamQuery(c->stream);
+        hipError_t qc = hipStreamQuery(cur(c).stream);
         if (qc != hipSuccess && qc != hipErrorNotReady) HIP_TRY(c, qc);
         if (qc == hipSuccess && c->frames_in_flight > 1) {      // two frames in flight: the other slot's stream carries steps too
-            qc = hipStreamQuery(c->slots[1 - c->cur_slot].stream);
+            qc = hipStreamQuery(other(c).stream);
             if (qc != hipSuccess && qc != hipErrorNotReady) HIP_TRY(c, qc);
         }
         const hipError_t q = hipStreamQuery(m->comm_stream);
@@ -785,7 +785,7 @@ int vct_comm_download_frame(vct_ctx* c, void* out) {
 // compared with the frame one launch traces.  *mismatches = pixels that differ (0 expected).
 int vct_selftest_interleaved(vct_ctx* c, int32_t world, uint64_t* mismatches) {
     if (!c || !mismatches || world < 1) return VCT_ERR_INVALID;
-    if (!c->have_gbuffer) return vct_fail(c, VCT_ERR_INVALID, "vct_selftest_interleaved: no G-buffer resident yet");
+    if (!cur(c).have_gbuffer) return vct_fail(c, VCT_ERR_INVALID, "vct_selftest_interleaved: no G-buffer resident yet");
     HIP_TRY(c, hipSetDevice(c->device));
     const int w = c->cfg.width, h = c->cfg.height, ty = vct_tiles_y(c);
     const int per = (ty + world - 1) / world;
@@ -795,18 +795,18 @@ int vct_selftest_interleaved(vct_ctx* c, int32_t world, uint64_t* mismatches) {
     if (hipMalloc(&gathered, slab_pixels * world * 8) != hipSuccess || hipMalloc(&il, npix * 8) != hipSuccess ||
         hipMalloc(&plain, npix * 8) != hipSuccess)
         return done(vct_fail(c, VCT_ERR_NOMEM, "vct_selftest_interleaved: out of memory"));
-    hipError_t e = hipMemsetAsync(gathered, 0, slab_pixels * world * 8, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(plain, 0, npix * 8, c->stream);
+    hipError_t e = hipMemsetAsync(gathered, 0, slab_pixels * world * 8, cur(c).stream);
+    if (e == hipSuccess) e = hipMemsetAsync(plain, 0, npix * 8, cur(c).stream);
     if (e != hipSuccess) return done(vct_fail(c, VCT_ERR_DEVICE, hipGetErrorString(e)));
     for (int r = 0; r < world; ++r) {
         const int rc = vct_launch_trace_rows(c, r < ty ? r : ty, ty, (uint16_t*)(gathered + slab_pixels * r), world, true);
         if (rc) return done(rc);
     }
-    hipLaunchKernelGGL(k_deinterleave, dim3(2048), dim3(256), 0, c->stream, gathered, il, w, h, world, slab_pixels);
+    hipLaunchKernelGGL(k_deinterleave, dim3(2048), dim3(256), 0, cur(c).stream, gathered, il, w, h, world, slab_pixels);
     int rc = vct_launch_trace_rows(c, 0, ty, (uint16_t*)plain);
     if (rc) return done(rc);
     std::vector<uint2> a(npix), b(npix);
-    e = hipStreamSynchronize(c->stream);
+    e = hipStreamSynchronize(cur(c).stream);
     if (e == hipSuccess) e = hipMemcpy(a.data(), il, npix * 8, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(b.data(), plain, npix * 8, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return done(vct_fail(c, VCT_ERR_DEVICE, hipGetErrorString(e)));

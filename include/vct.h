@@ -140,7 +140,20 @@ int vct_set_footprint_records(vct_ctx* ctx, int32_t on);
 
 /* Scene upload -- replaces Model/Mesh VBO setup (R/Mesh.h:49-82) for the two attributes the
  * voxelizer reads (vox.vs:3-4).  pos: [ntri][3][3] model-space fp32; material: [ntri];
- * albedo: [nmat][4] flat per-material albedo (stands in for DiffuseTexture, vox.fs:56). */
+ * albedo: [nmat][4] flat per-material albedo (stands in for DiffuseTexture, vox.fs:56).
+ *
+ * Vertex contract.  Every coordinate v of pos must be finite and satisfy, with the product formed in fp32,
+ *     |v * config.model_scale| <= VCT_VERTEX_LIMIT_GRIDS * config.grid_world_size        (2^20 grid widths).
+ * Where the bound comes from: the voxelizer turns a scaled coordinate x into the voxel coordinate
+ * g = (x / G + 0.5) * V and takes (int)floorf(g) for its bounding boxes before clamping to the grid (csrc/vct_voxelize.hip
+ * setup_tri, ref_setup).  That conversion is only defined for |g| < 2^31 (the GPU saturates, C++ on the host does
+ * not), and V <= 1024 = 2^10: |x| / G <= 2^20 gives |g| <= (2^20 + 0.5) * 2^10 < 2^31 with a factor 2 to spare for
+ * the fp32 roundings on the way.  Inside the bound every stage (voxelizer, shadow and G-buffer raster) computes,
+ * bit for bit, what the CPU checkers of oracle/ compute; a mesh outside it is refused here with VCT_ERR_INVALID and
+ * a message (vct_last_error), and the context keeps the mesh it had.  The raster stages have no bound of their own
+ * on the vertices: their integer conversions happen after the near clip, on doubles, are clamped to the frame, and
+ * saturate, for any finite clip coordinates the caller's matrix produces from an in-contract vertex. */
+#define VCT_VERTEX_LIMIT_GRIDS 1048576.0f
 int vct_upload_triangles(vct_ctx* ctx, const float* pos, const int32_t* material, int32_t ntri,
                          const float* albedo, int32_t nmat);
 /* Shadow map produced by the depth pass (VCT.h:192-211): size*size fp32 depths in [0,1] plus the

@@ -95,10 +95,13 @@ void raster_triangle(const RVert in[3], int nvar, bool cull_back, int W, int H, 
             b0 = (float)(f[0] / iarea);
             b1 = (float)(f[1] / iarea);
         };
-        const int x0 = std::max(0, (int)floor(std::min({sx[0], sx[1], sx[2]})));
-        const int x1 = std::min(W - 1, (int)floor(std::max({sx[0], sx[1], sx[2]})));
-        const int y0 = std::max(0, (int)floor(std::min({sy[0], sy[1], sy[2]})));
-        const int y1 = std::min(H - 1, (int)floor(std::max({sy[0], sy[1], sy[2]})));
+        // clamped as doubles BEFORE the conversion: a near-clipped triangle can project beyond 2^31 pixels, where
+        // (int) of a double is undefined in C++ (the GPU's conversion saturates, which is this clamp)
+        auto pix = [](double v, int n) { return (int)floor(std::min(std::max(v, -1.0), (double)n)); };
+        const int x0 = std::max(0, pix(std::min({sx[0], sx[1], sx[2]}), W));
+        const int x1 = std::min(W - 1, pix(std::max({sx[0], sx[1], sx[2]}), W));
+        const int y0 = std::max(0, pix(std::min({sy[0], sy[1], sy[2]}), H));
+        const int y1 = std::min(H - 1, pix(std::max({sy[0], sy[1], sy[2]}), H));
         for (int py = y0; py <= y1; ++py)
             for (int px = x0; px <= x1; ++px) {
                 const double cx = (double)px + 0.5, cy = (double)py + 0.5;

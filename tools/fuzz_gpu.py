@@ -81,9 +81,15 @@ while time.time() < t_end:
     depth = (np.round(depth.astype(np.float64) * (2 ** 24 - 1)) / (2 ** 24 - 1)).astype(np.float32)
     vp = np.array([[1 / 120.0, 0, 0, 0], [0, 0, -1 / 120.0, 0], [0, -1 / 100.0, 0, 0], [0, 0, 0, 1]], np.float32)
     use_shadow = r.random() < 0.7
-    p = oracle.default_params(V)
-    scn = oracle.make_scene(pos, mat, alb, shadow_depth=depth if use_shadow else None, light_vp=vp if use_shadow else None)
-    with vct.Context(vct.default_config(voxel_dim=V, width=8, height=8, voxel_attributes=1)) as ctx:
+    # the scene scales: the mesh is rescaled with them so that it still fills the grid, and the light's matrix sees
+    # the rescaled world as before
+    vms = float(r.choice([0.05, 0.05, 1.0, 0.0137])); vG = float(r.choice([150.0, 150.0, 100.0, 317.3]))
+    pos = (pos.astype(np.float64) * (0.05 / vms) * (vG / 150.0)).astype(np.float32)
+    vp[:, :3] /= np.float32(vG / 150.0)
+    p = oracle.default_params(V, G=vG)
+    scn = oracle.make_scene(pos, mat, alb, vms, shadow_depth=depth if use_shadow else None, light_vp=vp if use_shadow else None)
+    with vct.Context(vct.default_config(voxel_dim=V, width=8, height=8, voxel_attributes=1, model_scale=vms,
+                                        grid_world_size=vG)) as ctx:
         ctx.upload_triangles(pos, mat, alb)
         if use_shadow: ctx.upload_shadow_map(depth, vp)       # (an uploaded map always carries its tile bounds)
         ctx.voxelize(vct.VOX_REFERENCE); ctx.inject_light(); ctx.build_mips()
@@ -114,8 +120,12 @@ while time.time() < t_end:
     cam = sc.default_camera(position=tuple(r.uniform(-40, 40, 3)), yaw=float(r.uniform(-180, 180)),
                             pitch=float(r.uniform(-60, 60)), zoom=float(r.uniform(20, 45)))
     mips = bool(r.integers(0, 2))          # material textures mip-mapped (the default) or level 0 only
-    dref, lvp_row = raster_oracle.shadow_map(sc, scene, lightd, S)
-    gref = raster_oracle.gbuffer(sc, scene, cam, w, h, dref, lvp_row, mipmaps=mips)
+    # model_scale with the mesh rescaled against it (the world, and with it camera and light, stay where they are);
+    # grid_world_size only reaches the raster stages through the configuration
+    rms = float(r.choice([0.05, 0.05, 1.0, 0.0137])); rG = float(r.choice([150.0, 150.0, 100.0, 317.3]))
+    scene.pos = (scene.pos.astype(np.float64) * (0.05 / rms)).astype(np.float32)
+    dref, lvp_row = raster_oracle.shadow_map(sc, scene, lightd, S, model_scale=rms)
+    gref = raster_oracle.gbuffer(sc, scene, cam, w, h, dref, lvp_row, mipmaps=mips, model_scale=rms)
     # the form of the visibility stage: direct, tile-binned (both passes), or chosen by the library (round 4)
     path = [None, "direct", "binned", "binned"][int(r.integers(0, 4))]
     os.environ.pop("VCT_RASTER_PATH", None)
@@ -125,7 +135,8 @@ while time.time() < t_end:
     if tiles: os.environ["VCT_SHADOW_TILES"] = tiles
     counts["tiles_" + str(tiles)] = counts.get("tiles_" + str(tiles), 0) + 1
     counts["raster_" + str(path)] = counts.get("raster_" + str(path), 0) + 1
-    with vct.Context(vct.default_config(voxel_dim=16, width=w, height=h, shadow_map_size=S,
+    with vct.Context(vct.default_config(voxel_dim=16, width=w, height=h, shadow_map_size=S, model_scale=rms,
+                                        grid_world_size=rG,
                                         texture_mipmaps=1 if mips else 0)) as ctx:
         os.environ.pop("VCT_RASTER_PATH", None)
         ctx.upload_scene(scene)
@@ -144,7 +155,7 @@ while time.time() < t_end:
         ctx.render_gbuffer_rows(sc.camera_view_proj(cam, w, h), r0, r1)
         cam2 = sc.default_camera(position=tuple(r.uniform(-40, 40, 3)), yaw=float(r.uniform(-180, 180)),
                                  pitch=float(r.uniform(-60, 60)), zoom=float(r.uniform(20, 45)))
-        gref2 = raster_oracle.gbuffer(sc, scene, cam2, w, h, dref, lvp_row, mipmaps=mips)
+        gref2 = raster_oracle.gbuffer(sc, scene, cam2, w, h, dref, lvp_row, mipmaps=mips, model_scale=rms)
         ctx.render_shadow_map(sc.light_view_proj(lightd))
         if not np.array_equal(ctx.download_shadow_map().view(np.uint32), dref.view(np.uint32)): fail("shadow raster (2nd pass)", seed)
         slots = r.random() < 0.5           # round 6: the second pose in the context's second frame slot (two frames in flight)

@@ -951,6 +951,21 @@ int vct_upload_triangles(vct_ctx* c, const float* pos, const int32_t* material, 
     for (int32_t i = 0; i < ntri; ++i)
         if (material[i] < 0 || material[i] >= nmat)
             return fail(c, VCT_ERR_INVALID, "vct_upload_triangles: material index out of range");
+    // The vertex contract of include/vct.h, checked before anything of the current mesh is touched: a refused mesh
+    // leaves the context as it was.  The product is formed in fp32, as every kernel forms it; !(x <= lim) is also
+    // true for NaN and the infinities.
+    {
+        const float ms = c->cfg.model_scale, lim = VCT_VERTEX_LIMIT_GRIDS * c->cfg.grid_world_size;
+        const size_t nfloat = (size_t)ntri * 9;
+        for (size_t i = 0; i < nfloat; ++i)
+            if (!(fabsf(pos[i] * ms) <= lim)) {
+                char msg[256];
+                snprintf(msg, sizeof msg, "vct_upload_triangles: vertex %zu of triangle %zu (%g, times model_scale %g) is not "
+                         "finite or beyond 2^20 grid widths (%g): outside the vertex contract of vct.h",
+                         (i / 3) % 3, i / 9, (double)pos[i], (double)ms, (double)lim);
+                return fail(c, VCT_ERR_INVALID, msg);
+            }
+    }
     HIP_TRY(c, hipSetDevice(c->device));
     PIPE_TRY(pipeline_drain(c));
     if (c->tri_pos) { (void)hipFree(c->tri_pos); c->tri_pos = nullptr; }

@@ -833,6 +833,78 @@ def test_contexts_release_all_hbm(vct):
     assert free0 - free1 < 8 << 20, (free0, free1)     # nothing accumulates (a context here holds > 100 MB)
 
 
+def test_replacing_scene_data_on_a_live_context_releases_the_old(vct):
+    """ONE context whose triangles, mesh attributes, texture coordinates, textures (attach, detach, attach) and
+    uploaded shadow map are replaced round after round, with a full voxelize -> inject -> mips -> G-buffer -> trace
+    in between: whatever an upload replaces goes back at once, not only when the context is destroyed.  The data is
+    sized so that EACH replaced kind, leaked on its own, would exceed the bound over the measured rounds (asserted
+    below from the buffers' sizes, before the memory is looked at)."""
+    import torch
+    from voxel_cone_tracing_amd import scene as sc
+    bound, rounds = 8 << 20, 8
+    light = (0.0, 1.0, 0.25)
+    scenes = [sc.Scene(sc.ATRIUM_TEXTURED, 0.5, 1234), sc.Scene(sc.ATRIUM_TEXTURED, 0.4, 77)]
+    assert scenes[0].ntri != scenes[1].ntri and all(s.textures for s in scenes)
+    rng = np.random.default_rng(5)
+    depths = [rng.random((S, S), dtype=np.float32) for S in (1024, 1536)]
+    lvp_row = np.asarray(sc.light_view_proj(light), np.float32).reshape(4, 4).T
+    view_proj = sc.camera_view_proj(sc.default_camera(position=(0.0, 0.0, 58.0)), 64, 48)
+    plan_bytes = {}
+
+    with vct.Context(vct.default_config(voxel_dim=128, width=64, height=48, shadow_map_size=256,
+                                        voxel_attributes=1)) as ctx:
+        ctx.set_light_direction(light)
+
+        def one_round(i):
+            s = scenes[i % 2]
+            ctx.upload_triangles(s.pos, s.material, s.albedo)
+            for _ in range(3):                                      # the second and third replace the one before
+                ctx.upload_mesh_attributes(*s.frames(), s.specular)
+                ctx.upload_mesh_uvs(s.uv)
+            ctx.upload_textures(s.textures, s.mat_tex)              # replaces the previous round's texels
+            ctx.upload_textures([], s.mat_tex)                      # detach (ntex = 0)
+            ctx.upload_textures(s.textures, s.mat_tex)
+            ctx.upload_shadow_map(depths[(i + 1) % 2], lvp_row)
+            ctx.upload_shadow_map(depths[i % 2], lvp_row)
+            ctx.voxelize(); ctx.inject_light(); ctx.build_mips()
+            ctx.render_gbuffer(view_proj)
+            frame = ctx.trace_current()
+            assert np.isfinite(vct.half_to_float(frame.reshape(-1, 4))).all()
+            n = ctx.stage_counts()
+            # the plan's pools (stage + 2 staged and 2 resolved attributes, 512 RGBA8 voxels per slot each) and its
+            # sorted fragments with their barycentrics
+            plan_bytes[i % 2] = n["accumulator_bricks"] * 512 * 4 * 5 + n["vox_candidates"] * 12
+
+        for i in range(2):                           # both meshes once: runtime pools, lazily allocated scratch
+            one_round(i)
+        ctx.synchronize()
+        torch.cuda.synchronize()
+        free0, _ = torch.cuda.mem_get_info()
+        for i in range(2, 2 + rounds):
+            one_round(i)
+        ctx.synchronize()
+        torch.cuda.synchronize()
+        free1, _ = torch.cuda.mem_get_info()
+
+        # what ONE kind would hold after the measured rounds if its replacement leaked (lower bounds: the smaller
+        # mesh, the smaller map, level 0 of the textures only)
+        ntri = min(s.ntri for s in scenes)
+        leak = {
+            "uploaded shadow map (2 replacements per round)": rounds * 2 * depths[0].size * 4,
+            "triangle positions": rounds * ntri * 36,
+            "one of normal / tangent / bitangent (2 replacements per round)": rounds * 2 * ntri * 36,
+            "texture coordinates (2 replacements per round)": rounds * 2 * ntri * 24,
+            "texels (2 replacements per round)": rounds * 2 * min(sum(t.nbytes for t in s.textures) for s in scenes),
+            "voxelization plan": rounds * min(plan_bytes.values()),
+            "mesh-sized raster lists and records": rounds * ntri * (16 + 192),
+        }
+        for kind, held in leak.items():
+            print(f"a leaked {kind} would hold {held} bytes")
+            assert held > bound, (kind, held)
+        print(f"live-context replacement: free before {free0}, after {free1}, held {free0 - free1} bytes")
+        assert free0 - free1 < bound, (free0, free1)
+
+
 def test_extreme_sizes(vct, oracle):
     """Smallest grid (8^3: one brick, 4 levels), 1x1 and 1xN frames, all pixels discarded."""
     V = 8

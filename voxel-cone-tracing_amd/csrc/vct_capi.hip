@@ -12,6 +12,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "vct_ctx.h"
@@ -157,10 +158,10 @@ int divisor_verified(vct_ctx* c, float d, bool* ok) {
         auto it = cache.find(bits);
         if (it != cache.end()) { *ok = it->second; return VCT_OK; }
     }
-    HIP_TRY(c, hipMemsetAsync(c->stats, 0, 2 * sizeof(unsigned long long), cur(c).stream));
-    HIP_TRY(c, vct_launch_divide_selftest(d, c->stats, cur(c).stream));
+    HIP_TRY(c, hipMemsetAsync(c->stats.get(), 0, 2 * sizeof(unsigned long long), cur(c).stream));
+    HIP_TRY(c, vct_launch_divide_selftest(d, c->stats.get(), cur(c).stream));
     unsigned long long bad = 1;
-    HIP_TRY(c, hipMemcpyAsync(&bad, c->stats, sizeof(bad), hipMemcpyDeviceToHost, cur(c).stream));
+    HIP_TRY(c, hipMemcpyAsync(&bad, c->stats.get(), sizeof(bad), hipMemcpyDeviceToHost, cur(c).stream));
     HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     *ok = bad == 0ull;
     std::lock_guard<std::mutex> g(cache_lock);
@@ -184,15 +185,15 @@ __global__ void k_stamp(unsigned long long* out) { out[1] = wall_clock64(); }
 int streams_overlap(vct_ctx* c, hipStream_t base, hipStream_t cand, bool* overlap) {
     int khz = 0;
     if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->device) != hipSuccess || khz <= 0) khz = 100000;
-    HIP_TRY(c, hipMemsetAsync(c->stats, 0, 2 * sizeof(unsigned long long), base));
+    HIP_TRY(c, hipMemsetAsync(c->stats.get(), 0, 2 * sizeof(unsigned long long), base));
     HIP_TRY(c, hipStreamSynchronize(base));
-    hipLaunchKernelGGL(k_spin_stamp, dim3(1), dim3(1), 0, base, (long long)khz * 3 / 10, c->stats);      // 0.3 ms
-    hipLaunchKernelGGL(k_stamp, dim3(1), dim3(1), 0, cand, c->stats);
+    hipLaunchKernelGGL(k_spin_stamp, dim3(1), dim3(1), 0, base, (long long)khz * 3 / 10, c->stats.get());      // 0.3 ms
+    hipLaunchKernelGGL(k_stamp, dim3(1), dim3(1), 0, cand, c->stats.get());
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(base));
     HIP_TRY(c, hipStreamSynchronize(cand));
     unsigned long long v[2] = {0, 0};
-    HIP_TRY(c, hipMemcpy(v, c->stats, sizeof(v), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(v, c->stats.get(), sizeof(v), hipMemcpyDeviceToHost));
     *overlap = v[1] != 0ull && v[1] < v[0];
     return VCT_OK;
 }
@@ -285,9 +286,9 @@ int refresh_steps(vct_ctx* c) {
         for (VctStep& st : d) st.occ_den = vct_div_aux(st.occ_den, st.occ_rcp);
         for (VctStep& st : s) st.occ_den = vct_div_aux(st.occ_den, st.occ_rcp);
     }
-    HIP_TRY(c, hipMemcpyAsync(c->steps_dev, d.data(), d.size() * sizeof(VctStep),
+    HIP_TRY(c, hipMemcpyAsync(c->steps_dev.get(), d.data(), d.size() * sizeof(VctStep),
                               hipMemcpyHostToDevice, cur(c).stream));
-    HIP_TRY(c, hipMemcpyAsync(c->steps_dev + VCT_MAX_STEPS, s.data(), s.size() * sizeof(VctStep),
+    HIP_TRY(c, hipMemcpyAsync(c->steps_dev.get() + VCT_MAX_STEPS, s.data(), s.size() * sizeof(VctStep),
                               hipMemcpyHostToDevice, cur(c).stream));
     HIP_TRY(c, hipStreamSynchronize(cur(c).stream));   // d, s go out of scope
     c->steps_dirty = false;
@@ -315,18 +316,18 @@ void fill_march_params(const vct_ctx* c, VctTraceParams& p, const uint32_t* chai
     p.fast_div = c->fast_div ? 1 : 0;
     p.max_alpha = c->cfg.max_alpha;
     p.wrap_repeat = c->cfg.wrap_repeat;
-    p.spread_lut = c->spread_lut;
+    p.spread_lut = c->spread_lut.get();
     // records of `c->chain` only (the bounce chain has none), biased by the first level's offset
-    p.cells_biased = (c->cells_valid && chain == c->chain)
-                         ? (const char*)c->cells - ((size_t)vct_level_offset(c->cfg.voxel_dim, 1) << 5) : nullptr;
-    p.steps_diffuse = c->steps_dev;
-    p.steps_specular = c->steps_dev + VCT_MAX_STEPS;
+    p.cells_biased = (c->cells_valid && chain == c->chain.get())
+                         ? (const char*)c->cells.get() - ((size_t)vct_level_offset(c->cfg.voxel_dim, 1) << 5) : nullptr;
+    p.steps_diffuse = c->steps_dev.get();
+    p.steps_specular = c->steps_dev.get() + VCT_MAX_STEPS;
     p.n_diffuse = c->n_diffuse;
     p.n_specular = c->n_specular;
-    p.step_counter = c->step_counter;
-    p.tile_steps = cur(c).tile_steps;
+    p.step_counter = c->step_counter.get();
+    p.tile_steps = cur(c).tile_steps.get();
 #if defined(VCT_STATS) && VCT_STATS
-    p.stats = c->stats;
+    p.stats = c->stats.get();
 #endif
 }
 
@@ -357,7 +358,7 @@ int launch_trace(vct_ctx* c, int row0, int row1, uint16_t* out_base = nullptr, i
     if (c->cfg.debug_outputs && (c->n_diffuse > 255 || c->n_specular > 255))
         return fail(c, VCT_ERR_INVALID, "debug_outputs keeps per-cone step counts as uint8: this aperture needs more than 255 steps");
     VctTraceParams p;
-    fill_march_params(c, p, c->use_chain_b ? c->chain_b : c->chain);
+    fill_march_params(c, p, c->use_chain_b ? c->chain_b.get() : c->chain.get());
     for (int i = 0; i < 3; ++i) { p.cam[i] = c->cam[i]; p.light[i] = c->light[i]; }
     p.ambient = c->cfg.ambient_factor;
     p.shininess = c->cfg.shininess;
@@ -375,12 +376,12 @@ int launch_trace(vct_ctx* c, int row0, int row1, uint16_t* out_base = nullptr, i
     p.spec_prio = ((row1 - row0) / (row_stride > 1 ? row_stride : 1)) * 2 <= tiles_y(c) ? 1 : 0;
     const int variant = c->cfg.trace_variant;
     p.gbuf = cur(c).gb_current;
-    p.aniso = c->cfg.anisotropic_mips ? c->aniso : nullptr;
+    p.aniso = c->cfg.anisotropic_mips ? c->aniso.get() : nullptr;
     p.aniso_alt_slab = 128;     // k_trace_tile_split<ANISO>: slabs [level 1][level 2][-axis of 1][-axis of 2]
     p.aniso_stride = (uint32_t)(c->chain_texels - (size_t)c->cfg.voxel_dim * c->cfg.voxel_dim * c->cfg.voxel_dim);
-    p.out = out_base ? out_base : (cur(c).frame_target ? cur(c).frame_target : cur(c).frame);
-    p.dbg_steps = c->cfg.debug_outputs ? c->dbg_steps : nullptr;
-    p.dbg_cones = c->cfg.debug_outputs ? c->dbg_cones : nullptr;
+    p.out = out_base ? out_base : (cur(c).frame_target ? cur(c).frame_target : cur(c).frame.get());
+    p.dbg_steps = c->cfg.debug_outputs ? c->dbg_steps.get() : nullptr;
+    p.dbg_cones = c->cfg.debug_outputs ? c->dbg_cones.get() : nullptr;
     // lighting components (include/vct.h): the COMP kernel only when the mask or an output asks for it.  A packed slab
     // (interleaved ranks, whose contexts refuse outputs; the one-GPU self-test) writes no outputs.
     const uint32_t aov_which = pack_rows ? 0u : c->aov_which;
@@ -388,16 +389,16 @@ int launch_trace(vct_ctx* c, int row0, int row1, uint16_t* out_base = nullptr, i
         if (variant != 0)
             return fail(c, VCT_ERR_INVALID, "lighting components / per-component outputs need the default trace kernel (config.trace_variant 0)");
         p.comp = component_word(c->show_mask, aov_which);
-        p.aov = aov_which ? cur(c).aov : nullptr;
+        p.aov = aov_which ? cur(c).aov.get() : nullptr;
     }
 #if defined(VCT_STATS) && VCT_STATS
-    HIP_TRY(c, hipMemsetAsync(c->stats, 0, 16 * sizeof(unsigned long long), cur(c).stream));
+    HIP_TRY(c, hipMemsetAsync(c->stats.get(), 0, 16 * sizeof(unsigned long long), cur(c).stream));
 #endif
     if (variant == 4 && !c->cfg.anisotropic_mips) {       // live-pixel compaction (experiment): list + counter, zeroed per launch
         const size_t nt = (size_t)tiles_x(c) * tiles_y(c);
-        if (!c->vt_pix) HIP_TRY(c, hipMalloc(&c->vt_pix, (nt * 64 + 4) * sizeof(uint32_t)));
-        p.vt_pix = c->vt_pix;
-        p.vt_count = c->vt_pix + nt * 64;
+        HIP_TRY(c, c->vt_pix.reserve(nt * 64 + 4));
+        p.vt_pix = c->vt_pix.get();
+        p.vt_count = c->vt_pix.get() + nt * 64;
         HIP_TRY(c, hipMemsetAsync(p.vt_count, 0, sizeof(uint32_t), cur(c).stream));
     }
     if (c->time_traces) HIP_TRY(c, hipEventRecord(cur(c).ev0, cur(c).stream));      // (vct_set_trace_timing)
@@ -418,48 +419,50 @@ int launch_trace(vct_ctx* c, int row0, int row1, uint16_t* out_base = nullptr, i
 VctTextures textures_of(const vct_ctx* c) {
     VctTextures t;
     memset(&t, 0, sizeof(t));
-    if (c->tex_texels && c->tri_uv && c->mat_tex) {
-        t.texels = c->tex_texels; t.desc = c->tex_desc; t.mat_tex = c->mat_tex; t.uv = c->tri_uv; t.ntex = c->ntex;
+    const VctMesh& m = c->mesh;
+    if (m.tex_texels && m.tri_uv && m.mat_tex) {
+        t.texels = m.tex_texels.get(); t.desc = m.tex_desc.get(); t.mat_tex = m.mat_tex.get(); t.uv = m.tri_uv.get(); t.ntex = m.ntex;
         t.mips = c->cfg.texture_mipmaps ? 1 : 0;
     }
     return t;
 }
 
-VctVoxParams vox_params(const vct_ctx* c) {
+// parameters of the voxelizer kernels: the context's mesh and shadow map, and the buffers of plan `v`
+VctVoxParams vox_params(const vct_ctx* c, const VctVoxelPlan& v) {
     VctVoxParams p;
     memset(&p, 0, sizeof(p));
     p.V = c->cfg.voxel_dim;
     p.G = c->cfg.grid_world_size;
     p.model_scale = c->cfg.model_scale;
-    p.pos = c->tri_pos;
-    p.material = c->tri_mat;
-    p.albedo = c->mat_albedo;
-    p.ntri = c->ntri;
-    p.shadow = c->shadow;
-    p.shadow_tiles = c->shadow ? c->shadow_tiles : nullptr;
+    p.pos = c->mesh.tri_pos.get();
+    p.material = c->mesh.tri_mat.get();
+    p.albedo = c->mesh.mat_albedo.get();
+    p.ntri = c->mesh.ntri;
+    p.shadow = c->shadow.get();
+    p.shadow_tiles = c->shadow ? c->shadow_tiles.get() : nullptr;
     p.shadow_ebase = c->shadow_ebase;
     p.shadow_size = c->shadow_size;
     memcpy(p.light_vp, c->light_vp, 64);
-    p.acc = c->acc;
-    p.brick_slot = c->brick_slot;
-    p.frag_sorted = c->frag_sorted;
-    p.frag_bary = c->frag_bary;
+    p.acc = v.acc.get();
+    p.brick_slot = v.brick_slot.get();
+    p.frag_sorted = v.frag_sorted.get();
+    p.frag_bary = v.frag_bary.get();
     p.frag_alb = nullptr;       // vct_voxelize attaches it (scenes with textures)
-    p.tri_qnrm = c->tri_qnrm;
-    p.slot_first = c->slot_first;
-    p.slot_brick = c->slot_brick;
-    p.items = (const uint4*)c->vox_items;
-    p.nitems = c->n_vox_items;
-    p.chunk = c->vox_chunk;
-    p.acc2 = c->vox_acc2;
-    p.acc2_attr = c->vox_acc2_attr;
-    p.multi_slot = c->vox_multi_slot;
-    p.nmulti = c->n_vox_multi;
-    p.nslots = c->nslots;
-    p.stage = c->stage;
-    p.stage_albedo = c->stage_albedo;
-    p.stage_normal = c->stage_normal;
-    p.brick_flags = c->brick_flags;
+    p.tri_qnrm = v.tri_qnrm.get();
+    p.slot_first = v.slot_first.get();
+    p.slot_brick = v.slot_brick.get();
+    p.items = v.items.get();
+    p.nitems = v.n_items;
+    p.chunk = v.chunk;
+    p.acc2 = v.acc2.get();
+    p.acc2_attr = v.acc2_attr.get();
+    p.multi_slot = v.multi_slot.get();
+    p.nmulti = v.n_multi;
+    p.nslots = v.nslots;
+    p.stage = v.stage.get();
+    p.stage_albedo = v.stage_albedo.get();
+    p.stage_normal = v.stage_normal.get();
+    p.brick_flags = c->brick_flags.get();
     p.tex = textures_of(c);
     return p;
 }
@@ -477,101 +480,62 @@ void glm_voxel_projections(const vct_ctx* c, float proj[48]) {
     }
 }
 
-// Drops the voxelization plan of the previous mesh (slots, sorted fragments, work items, staging pool, pooled
-// attributes, reference-mode accumulators and big-triangle list): everything indexed by the OLD mesh's triangles or
-// slots.  Called by vct_upload_triangles BEFORE any step that can fail, so that a failed upload leaves the context
-// without a plan (vct_voxelize then refuses) instead of with the old mesh's plan over the new mesh's triangles.
-// Level 0 / brick_prev keep describing what the chain shows.
-void drop_voxel_plan(vct_ctx* c) {
-    void** old[] = {(void**)&c->acc, (void**)&c->attr_albedo, (void**)&c->attr_normal, (void**)&c->brick_slot,
-                    (void**)&c->frag_sorted, (void**)&c->slot_first, (void**)&c->slot_brick, (void**)&c->stage,
-                    (void**)&c->stage_albedo, (void**)&c->stage_normal, (void**)&c->vox_items, (void**)&c->vox_acc2,
-                    (void**)&c->vox_acc2_attr, (void**)&c->vox_multi_slot, (void**)&c->ref_big, (void**)&c->frag_bary,
-                    (void**)&c->frag_alb, (void**)&c->tri_qnrm};
-    for (void** q : old) if (*q) { (void)hipFree(*q); *q = nullptr; }
-    c->frag_alb_dirty = true;
-    c->nslots = 0;
-    c->n_frags = 0;
-    c->n_vox_items = 0;
-    c->n_vox_multi = 0;
-    c->acc_pending = false;
-    c->attrs_valid = false;     // the pooled attributes are indexed by the NEW mesh's slots: nothing resolved into them yet
-}
-
 // Per-mesh brick slots.  The bricks a fragment of this mesh can land in depend only on geometry, V and G (not on the
 // light, the shadow map or the textures), so they are found ONCE per upload -- from the conservative voxelizer's
 // fragment list `frags` and a mark-only run of the reference-mode voxelizer -- and every marked brick gets a slot; the
 // fragment list is then sorted by slot (counting sort) and the staging pool of the north-star pass is allocated (+ the
-// voxel attributes when config.voxel_attributes).  Everything is allocated into locals and committed only when every
-// allocation succeeded, so a failed hipMalloc leaves the context without a plan (vct_voxelize then reports it) instead
-// of half-initialised.
+// voxel attributes when config.voxel_attributes).  Everything is built in a local plan that becomes the context's as the
+// last statement, so a failure on the way leaves the context with the empty plan vct_upload_triangles gave it
+// (vct_voxelize then reports it) instead of a half-initialised one.
 int build_voxel_slots(vct_ctx* c, const uint2* frags, uint32_t nfrags) {
     const size_t nvox = (size_t)c->cfg.voxel_dim * c->cfg.voxel_dim * c->cfg.voxel_dim;
     const uint32_t nbricks = (uint32_t)(nvox / 512);
-    drop_voxel_plan(c);         // (vct_upload_triangles already did, before its first fallible step)
-    uint32_t *mark = nullptr, *slot = nullptr, *count = nullptr, *cnt = nullptr, *cursor = nullptr;
-    uint32_t *sorted = nullptr, *first = nullptr, *slot_brick = nullptr, *stage = nullptr, *stage_albedo = nullptr,
-             *stage_normal = nullptr, *attr_albedo = nullptr, *attr_normal = nullptr, *multi_slot = nullptr, *tri_nrm = nullptr;
-    float2* bary = nullptr;
-    void* items = nullptr;
-    unsigned long long *acc2 = nullptr, *acc2_attr = nullptr;
-    auto cleanup = [&]() {
-        void* tmp[] = {mark, slot, count, cnt, cursor, sorted, first, slot_brick, stage, stage_albedo, stage_normal,
-                       attr_albedo, attr_normal, multi_slot, items, acc2, acc2_attr, bary, tri_nrm};
-        for (void* q : tmp) if (q) (void)hipFree(q);
-    };
-#define POOL_TRY(expr)                                                                                  \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) {                                                                         \
-            cleanup();                                                                                  \
-            return fail(c, e_ == hipErrorOutOfMemory ? VCT_ERR_NOMEM : VCT_ERR_DEVICE,                  \
-                        std::string(#expr) + ": " + hipGetErrorString(e_));                             \
-        }                                                                                               \
-    } while (0)
-    POOL_TRY(hipMalloc(&mark, (size_t)nbricks * sizeof(uint32_t)));
-    POOL_TRY(hipMalloc(&slot, (size_t)nbricks * sizeof(uint32_t)));
-    POOL_TRY(hipMalloc(&count, sizeof(uint32_t)));
-    POOL_TRY(hipMemsetAsync(mark, 0, (size_t)nbricks * sizeof(uint32_t), cur(c).stream));
-    if (!c->ref_big) POOL_TRY(hipMalloc(&c->ref_big, ((size_t)c->ntri + 1) * sizeof(int32_t)));
-    POOL_TRY(vct_launch_frag_mark(frags, nfrags, mark, cur(c).stream));                  // north-star mode's fragments
-    VctVoxParams p = vox_params(c);
+    const int32_t ntri = c->mesh.ntri;
+    VctVoxelPlan v;
+    VctBuf<uint32_t> mark, count, cnt, cursor;
+    VctVoxParams p = vox_params(c, v);       // the mesh alone: the mark-only run reads nothing of a plan
+    HIP_TRY(c, mark.alloc(nbricks));
+    HIP_TRY(c, v.brick_slot.alloc(nbricks));
+    HIP_TRY(c, count.alloc(1));
+    HIP_TRY(c, hipMemsetAsync(mark.get(), 0, (size_t)nbricks * sizeof(uint32_t), cur(c).stream));
+    HIP_TRY(c, v.ref_big.alloc((size_t)ntri + 1));
+    HIP_TRY(c, vct_launch_frag_mark(frags, nfrags, mark.get(), cur(c).stream));                  // north-star mode's fragments
     p.mark_only = 1;
-    p.brick_mark = mark;
+    p.brick_mark = mark.get();
     p.shadow = nullptr;
     glm_voxel_projections(c, p.proj);
-    POOL_TRY(vct_launch_voxelize_reference(p, c->ref_big + 1, c->ref_big, cur(c).stream));   // reference mode's (mark only)
-    POOL_TRY(vct_launch_assign_slots(mark, slot, count, nbricks, cur(c).stream));
-    uint32_t nslots = 0;
-    POOL_TRY(hipMemcpyAsync(&nslots, count, sizeof(nslots), hipMemcpyDeviceToHost, cur(c).stream));
-    POOL_TRY(hipStreamSynchronize(cur(c).stream));
+    HIP_TRY(c, vct_launch_voxelize_reference(p, v.ref_big.get() + 1, v.ref_big.get(), cur(c).stream));   // reference mode's (mark only)
+    HIP_TRY(c, vct_launch_assign_slots(mark.get(), v.brick_slot.get(), count.get(), nbricks, cur(c).stream));
+    HIP_TRY(c, hipMemcpyAsync(&v.nslots, count.get(), sizeof(v.nslots), hipMemcpyDeviceToHost, cur(c).stream));
+    HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     // counting sort of the fragments by slot: per-slot counts -> offsets (host prefix sum: once per mesh) -> scatter
-    const size_t ns = nslots ? nslots : 1u;
-    POOL_TRY(hipMalloc(&cnt, ns * sizeof(uint32_t)));
-    POOL_TRY(hipMalloc(&cursor, ns * sizeof(uint32_t)));
-    POOL_TRY(hipMalloc(&first, (ns + 1) * sizeof(uint32_t)));
-    POOL_TRY(hipMalloc(&slot_brick, ns * sizeof(uint32_t)));
-    POOL_TRY(hipMalloc(&sorted, (size_t)(nfrags ? nfrags : 1u) * sizeof(uint32_t)));
-    POOL_TRY(hipMemsetAsync(cnt, 0, ns * sizeof(uint32_t), cur(c).stream));
-    POOL_TRY(hipMemsetAsync(cursor, 0, ns * sizeof(uint32_t), cur(c).stream));
-    POOL_TRY(hipMemsetAsync(slot_brick, 0, ns * sizeof(uint32_t), cur(c).stream));
-    POOL_TRY(vct_launch_slot_bricks(slot, nbricks, slot_brick, cur(c).stream));      // every slot names its brick
-    POOL_TRY(vct_launch_frag_count(frags, nfrags, slot, cnt, cur(c).stream));
+    const size_t ns = v.nslots ? v.nslots : 1u;
+    HIP_TRY(c, cnt.alloc(ns));
+    HIP_TRY(c, cursor.alloc(ns));
+    HIP_TRY(c, v.slot_first.alloc(ns + 1));
+    HIP_TRY(c, v.slot_brick.alloc(ns));
+    HIP_TRY(c, v.frag_sorted.alloc(nfrags ? nfrags : 1u));
+    v.n_frags = nfrags;
+    HIP_TRY(c, hipMemsetAsync(cnt.get(), 0, ns * sizeof(uint32_t), cur(c).stream));
+    HIP_TRY(c, hipMemsetAsync(cursor.get(), 0, ns * sizeof(uint32_t), cur(c).stream));
+    HIP_TRY(c, hipMemsetAsync(v.slot_brick.get(), 0, ns * sizeof(uint32_t), cur(c).stream));
+    HIP_TRY(c, vct_launch_slot_bricks(v.brick_slot.get(), nbricks, v.slot_brick.get(), cur(c).stream));      // every slot names its brick
+    HIP_TRY(c, vct_launch_frag_count(frags, nfrags, v.brick_slot.get(), cnt.get(), cur(c).stream));
     std::vector<uint32_t> hcnt(ns, 0u), hfirst(ns + 1, 0u);
-    POOL_TRY(hipMemcpyAsync(hcnt.data(), cnt, ns * sizeof(uint32_t), hipMemcpyDeviceToHost, cur(c).stream));
-    POOL_TRY(hipStreamSynchronize(cur(c).stream));
+    HIP_TRY(c, hipMemcpyAsync(hcnt.data(), cnt.get(), ns * sizeof(uint32_t), hipMemcpyDeviceToHost, cur(c).stream));
+    HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     for (size_t i = 0; i < ns; ++i) hfirst[i + 1] = hfirst[i] + hcnt[i];
-    POOL_TRY(hipMemcpyAsync(first, hfirst.data(), (ns + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, cur(c).stream));
-    POOL_TRY(vct_launch_frag_scatter(frags, nfrags, slot, first, cursor, sorted, slot_brick, cur(c).stream));
+    HIP_TRY(c, hipMemcpyAsync(v.slot_first.get(), hfirst.data(), (ns + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, cur(c).stream));
+    HIP_TRY(c, vct_launch_frag_scatter(frags, nfrags, v.brick_slot.get(), v.slot_first.get(), cursor.get(), v.frag_sorted.get(),
+                                       v.slot_brick.get(), cur(c).stream));
     // the barycentrics of every fragment (geometry only): the pass reads them instead of re-deriving the triangle set-up
-    POOL_TRY(hipMalloc(&bary, (size_t)(nfrags ? nfrags : 1u) * sizeof(float2)));
+    HIP_TRY(c, v.frag_bary.alloc(nfrags ? nfrags : 1u));
     {
-        VctVoxParams q = vox_params(c);
-        q.frag_sorted = sorted; q.slot_first = first; q.slot_brick = slot_brick; q.nslots = nslots;
-        POOL_TRY(vct_launch_frag_geom(q, bary, nullptr, cur(c).stream));
+        const VctVoxParams q = vox_params(c, v);      // the sorted fragments and their slots
+        HIP_TRY(c, vct_launch_frag_geom(q, v.frag_bary.get(), nullptr, cur(c).stream));
         if (c->cfg.voxel_attributes) {
-            POOL_TRY(hipMalloc(&tri_nrm, (size_t)(c->ntri > 0 ? c->ntri : 1) * 3 * sizeof(uint32_t)));
-            POOL_TRY(vct_launch_tri_nrm(q, tri_nrm, cur(c).stream));
+            HIP_TRY(c, v.tri_qnrm.alloc((size_t)(ntri > 0 ? ntri : 1) * 3));
+            HIP_TRY(c, vct_launch_tri_nrm(q, v.tri_qnrm.get(), cur(c).stream));
         }
     }
     // Work items of the pass, the heaviest slots first, slots above VCT_VOX_CHUNK fragments cut into chunks.  Fragments
@@ -585,105 +549,81 @@ int build_voxel_slots(vct_ctx* c, const uint2* frags, uint32_t nfrags) {
     std::vector<uint32_t> hitems;
     hitems.reserve(ns * 4 + 64);
     std::vector<uint32_t> hmulti;
-    uint32_t nmulti = 0;
-    const uint32_t CH = VCT_VOX_CHUNK;
-    c->vox_chunk = CH;
-    if (nslots)
+    const uint32_t CH = v.chunk;
+    if (v.nslots)
         for (uint32_t sl : order) {
             const uint32_t chunks = hcnt[sl] ? (hcnt[sl] + CH - 1u) / CH : 1u;
-            const uint32_t mi = chunks > 1u ? nmulti++ : 0xffffffffu;
+            const uint32_t mi = chunks > 1u ? v.n_multi++ : 0xffffffffu;
             if (chunks > 1u) hmulti.push_back(sl);
             for (uint32_t ch = 0; ch < chunks; ++ch) {      // (slot, first fragment, fragments, multi index or ~0)
                 const uint32_t nfr = hcnt[sl] - ch * CH < CH ? hcnt[sl] - ch * CH : CH;
                 hitems.push_back(sl); hitems.push_back(hfirst[sl] + ch * CH); hitems.push_back(nfr); hitems.push_back(mi);
             }
         }
-    const uint32_t nitems = (uint32_t)(hitems.size() / 4);
-    POOL_TRY(hipMalloc(&items, (size_t)(nitems ? nitems : 1u) * 16));
-    if (nitems) POOL_TRY(hipMemcpyAsync(items, hitems.data(), (size_t)nitems * 16, hipMemcpyHostToDevice, cur(c).stream));
-    const size_t nm = nmulti ? nmulti : 1u;
-    POOL_TRY(hipMalloc(&acc2, nm * 512 * 2 * sizeof(unsigned long long)));
-    POOL_TRY(hipMemsetAsync(acc2, 0, nm * 512 * 2 * sizeof(unsigned long long), cur(c).stream));
-    POOL_TRY(hipMalloc(&multi_slot, nm * sizeof(uint32_t)));
-    if (nmulti) POOL_TRY(hipMemcpyAsync(multi_slot, hmulti.data(), (size_t)nmulti * sizeof(uint32_t), hipMemcpyHostToDevice, cur(c).stream));
+    v.n_items = (uint32_t)(hitems.size() / 4);
+    HIP_TRY(c, v.items.alloc(v.n_items ? v.n_items : 1u));
+    if (v.n_items) HIP_TRY(c, hipMemcpyAsync(v.items.get(), hitems.data(), (size_t)v.n_items * 16, hipMemcpyHostToDevice, cur(c).stream));
+    const size_t nm = v.n_multi ? v.n_multi : 1u;
+    HIP_TRY(c, v.acc2.alloc(nm * 512 * 2));
+    HIP_TRY(c, hipMemsetAsync(v.acc2.get(), 0, nm * 512 * 2 * sizeof(unsigned long long), cur(c).stream));
+    HIP_TRY(c, v.multi_slot.alloc(nm));
+    if (v.n_multi) HIP_TRY(c, hipMemcpyAsync(v.multi_slot.get(), hmulti.data(), (size_t)v.n_multi * sizeof(uint32_t), hipMemcpyHostToDevice, cur(c).stream));
     if (c->cfg.voxel_attributes) {
-        POOL_TRY(hipMalloc(&acc2_attr, nm * 512 * 3 * sizeof(unsigned long long)));
-        POOL_TRY(hipMemsetAsync(acc2_attr, 0, nm * 512 * 3 * sizeof(unsigned long long), cur(c).stream));
+        HIP_TRY(c, v.acc2_attr.alloc(nm * 512 * 3));
+        HIP_TRY(c, hipMemsetAsync(v.acc2_attr.get(), 0, nm * 512 * 3 * sizeof(unsigned long long), cur(c).stream));
     }
     // staging pool of a pass (+ attributes): written in full by every pass, never cleared
     const size_t pool_vox = ns * 512;
-    POOL_TRY(hipMalloc(&stage, pool_vox * 4));
-    POOL_TRY(hipMemsetAsync(stage, 0, pool_vox * 4, cur(c).stream));
+    HIP_TRY(c, v.stage.alloc(pool_vox));
+    HIP_TRY(c, hipMemsetAsync(v.stage.get(), 0, pool_vox * 4, cur(c).stream));
     if (c->cfg.voxel_attributes) {
-        POOL_TRY(hipMalloc(&stage_albedo, pool_vox * 4));
-        POOL_TRY(hipMalloc(&stage_normal, pool_vox * 4));
-        POOL_TRY(hipMalloc(&attr_albedo, pool_vox * 4));
-        POOL_TRY(hipMalloc(&attr_normal, pool_vox * 4));
-        POOL_TRY(hipMemsetAsync(stage_albedo, 0, pool_vox * 4, cur(c).stream));
-        POOL_TRY(hipMemsetAsync(stage_normal, 0, pool_vox * 4, cur(c).stream));
-        POOL_TRY(hipMemsetAsync(attr_albedo, 0, pool_vox * 4, cur(c).stream));
-        POOL_TRY(hipMemsetAsync(attr_normal, 0, pool_vox * 4, cur(c).stream));
+        VctBuf<uint32_t>* pools[] = {&v.stage_albedo, &v.stage_normal, &v.attr_albedo, &v.attr_normal};
+        for (VctBuf<uint32_t>* b : pools) HIP_TRY(c, b->alloc(pool_vox));
+        for (VctBuf<uint32_t>* b : pools) HIP_TRY(c, hipMemsetAsync(b->get(), 0, pool_vox * 4, cur(c).stream));
     }
+    // (these describe the chain, not the mesh: allocated with the first plan, kept from then on)
     const size_t flag_bytes = (size_t)nbricks * sizeof(uint32_t);
-    uint32_t** flags[] = {&c->brick_flags, &c->brick_prev, &c->mip_seen};
-    for (uint32_t** f : flags)
+    VctBuf<uint32_t>* flags[] = {&c->brick_flags, &c->brick_prev, &c->mip_seen};
+    for (VctBuf<uint32_t>* f : flags)
         if (!*f) {
-            POOL_TRY(hipMalloc(f, flag_bytes));
-            POOL_TRY(hipMemsetAsync(*f, 0, flag_bytes, cur(c).stream));
+            HIP_TRY(c, f->alloc(nbricks));
+            HIP_TRY(c, hipMemsetAsync(f->get(), 0, flag_bytes, cur(c).stream));
         }
-    POOL_TRY(hipMemsetAsync(c->brick_flags, 0, flag_bytes, cur(c).stream));
-    POOL_TRY(hipStreamSynchronize(cur(c).stream));
-#undef POOL_TRY
-    (void)hipFree(mark); (void)hipFree(count); (void)hipFree(cnt); (void)hipFree(cursor);
-    c->attr_albedo = attr_albedo; c->attr_normal = attr_normal;
-    c->brick_slot = slot;
-    c->nslots = nslots;
-    c->frag_sorted = sorted; c->n_frags = nfrags; c->slot_first = first; c->slot_brick = slot_brick;
-    c->frag_bary = bary; c->tri_qnrm = tri_nrm; c->frag_alb_dirty = true;
-    c->stage = stage; c->stage_albedo = stage_albedo; c->stage_normal = stage_normal;
-    c->vox_items = items; c->n_vox_items = nitems; c->vox_acc2 = acc2; c->vox_acc2_attr = acc2_attr; c->vox_multi_slot = multi_slot; c->n_vox_multi = nmulti;
+    HIP_TRY(c, hipMemsetAsync(c->brick_flags.get(), 0, flag_bytes, cur(c).stream));
+    HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
+    c->vox = std::move(v);
     return VCT_OK;
 }
 
 // ---- lifetime of raster scratch and frame slots (vct_ctx.h) ------------------------------------------------------------
-// Frees every buffer of the scratch and resets it: the next pass allocates and clears what it needs.
-void raster_release(VctRasterScratch& r) {
-    void* bufs[] = {r.lists, r.recs, r.counts, r.items, r.bin_recs, r.bin_entries, r.bin_count, r.bin_items, r.bin_huge, r.vis};
-    for (void* b : bufs) if (b) (void)hipFree(b);
-    r = VctRasterScratch();
-}
 // Frees the buffers sized by the mesh's triangle count (a new mesh: the next pass allocates them for it).
 void raster_release_mesh(VctRasterScratch& r) {
-    void** bufs[] = {(void**)&r.lists, &r.recs, &r.bin_recs, (void**)&r.bin_entries, (void**)&r.bin_items};
-    for (void** b : bufs) if (*b) { (void)hipFree(*b); *b = nullptr; }
-    r.bin_rec_cap = r.bin_entry_cap = r.bin_item_cap = 0u;
+    r.lists.reset(); r.recs.reset(); r.bin_recs.reset(); r.bin_entries.reset(); r.bin_items.reset();
 }
 
 // A slot on `stream`, which it owns from here on: timing events, G-buffer, frame, per-tile step counts and the
 // per-component outputs that are on, zeroed on that stream.  A failure leaves a partial slot for slot_release.
 hipError_t slot_create(vct_ctx* c, VctFrameSlot& s, hipStream_t stream) {
     const size_t npix = (size_t)c->cfg.width * c->cfg.height, nt = (size_t)tiles_x(c) * tiles_y(c);
-    const size_t aov_bytes = aov_frames(c->aov_which) * npix * 8;
+    const size_t aov_halves = aov_frames(c->aov_which) * npix * 4;
     s.stream = stream;
     hipError_t e = hipEventCreate(&s.ev0);
     if (e == hipSuccess) e = hipEventCreate(&s.ev1);
-    if (e == hipSuccess) e = hipMalloc(&s.gb_tiled, gb_tiled_floats(c) * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&s.frame, npix * 8);
-    if (e == hipSuccess) e = hipMalloc(&s.tile_steps, nt * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemsetAsync(s.gb_tiled, 0, gb_tiled_floats(c) * sizeof(float), stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s.frame, 0, npix * 8, stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s.tile_steps, 0, nt * sizeof(uint32_t), stream);
-    if (e == hipSuccess && aov_bytes) e = hipMalloc(&s.aov, aov_bytes);
-    if (e == hipSuccess && aov_bytes) e = hipMemsetAsync(s.aov, 0, aov_bytes, stream);
-    s.gb_current = s.gb_tiled;
+    if (e == hipSuccess) e = s.gb_tiled.alloc(gb_tiled_floats(c));
+    if (e == hipSuccess) e = s.frame.alloc(npix * 4);
+    if (e == hipSuccess) e = s.tile_steps.alloc(nt);
+    if (e == hipSuccess) e = hipMemsetAsync(s.gb_tiled.get(), 0, gb_tiled_floats(c) * sizeof(float), stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s.frame.get(), 0, npix * 8, stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s.tile_steps.get(), 0, nt * sizeof(uint32_t), stream);
+    if (e == hipSuccess && aov_halves) e = s.aov.alloc(aov_halves);
+    if (e == hipSuccess && aov_halves) e = hipMemsetAsync(s.aov.get(), 0, aov_halves * 2, stream);
+    s.gb_current = s.gb_tiled.get();
     return e;
 }
-// Waits for the slot's stream, then frees everything the slot owns (its stream and raster scratch too) and resets it.
+// Waits for the slot's stream, destroys its events and the stream, and resets the slot: the fresh slot that takes its
+// place frees the memory (its raster scratch too).
 void slot_release(VctFrameSlot& s) {
     if (s.stream) (void)hipStreamSynchronize(s.stream);
-    void* bufs[] = {s.gb_tiled, s.frame, s.tile_steps, s.aov};
-    for (void* b : bufs) if (b) (void)hipFree(b);
-    raster_release(s.raster);
     if (s.ev0) (void)hipEventDestroy(s.ev0);
     if (s.ev1) (void)hipEventDestroy(s.ev1);
     if (s.stream) (void)hipStreamDestroy(s.stream);
@@ -819,30 +759,30 @@ int vct_create(const vct_config* cfg, vct_ctx** out) {
     const int V = cfg->voxel_dim;
     c->nlev = vct_ilog2(V) + 1;
     c->chain_texels = vct_chain_texels(V);
-    CREATE_TRY(hipMalloc(&c->chain, c->chain_texels * 4));
-    CREATE_TRY(hipMemsetAsync(c->chain, 0, c->chain_texels * 4, cur(c).stream));   // VCT.h:115-119
+    CREATE_TRY(c->chain.alloc(c->chain_texels));
+    CREATE_TRY(hipMemsetAsync(c->chain.get(), 0, c->chain_texels * 4, cur(c).stream));   // VCT.h:115-119
     const size_t npix = (size_t)cfg->width * cfg->height;
     if (cfg->anisotropic_mips) {
         const size_t n = 6 * (c->chain_texels - (size_t)V * V * V);
-        CREATE_TRY(hipMalloc(&c->aniso, n * 4));
-        CREATE_TRY(hipMemsetAsync(c->aniso, 0, n * 4, cur(c).stream));
+        CREATE_TRY(c->aniso.alloc(n));
+        CREATE_TRY(hipMemsetAsync(c->aniso.get(), 0, n * 4, cur(c).stream));
     }
-    CREATE_TRY(hipMalloc(&c->step_counter, VCT_STEP_COUNTERS * sizeof(unsigned long long)));
-    CREATE_TRY(hipMemsetAsync(c->step_counter, 0, VCT_STEP_COUNTERS * sizeof(unsigned long long), cur(c).stream));
-    CREATE_TRY(hipMalloc(&c->stats, 16 * sizeof(unsigned long long)));
-    CREATE_TRY(hipMemsetAsync(c->stats, 0, 16 * sizeof(unsigned long long), cur(c).stream));
-    CREATE_TRY(hipMalloc(&c->steps_dev, 2 * VCT_MAX_STEPS * sizeof(VctStep)));
+    CREATE_TRY(c->step_counter.alloc(VCT_STEP_COUNTERS));
+    CREATE_TRY(hipMemsetAsync(c->step_counter.get(), 0, VCT_STEP_COUNTERS * sizeof(unsigned long long), cur(c).stream));
+    CREATE_TRY(c->stats.alloc(16));
+    CREATE_TRY(hipMemsetAsync(c->stats.get(), 0, 16 * sizeof(unsigned long long), cur(c).stream));
+    CREATE_TRY(c->steps_dev.alloc(2 * VCT_MAX_STEPS));
     {
         std::vector<uint32_t> lut(1024);
         for (uint32_t i = 0; i < 1024u; ++i) lut[i] = vct_spread3(i) << 2;
-        CREATE_TRY(hipMalloc(&c->spread_lut, lut.size() * sizeof(uint32_t)));
-        CREATE_TRY(hipMemcpy(c->spread_lut, lut.data(), lut.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        CREATE_TRY(c->spread_lut.alloc(lut.size()));
+        CREATE_TRY(hipMemcpy(c->spread_lut.get(), lut.data(), lut.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     if (cfg->debug_outputs) {
-        CREATE_TRY(hipMalloc(&c->dbg_steps, npix * 7));
-        CREATE_TRY(hipMalloc(&c->dbg_cones, npix * 28 * sizeof(float)));
-        CREATE_TRY(hipMemsetAsync(c->dbg_steps, 0, npix * 7, cur(c).stream));
-        CREATE_TRY(hipMemsetAsync(c->dbg_cones, 0, npix * 28 * sizeof(float), cur(c).stream));
+        CREATE_TRY(c->dbg_steps.alloc(npix * 7));
+        CREATE_TRY(c->dbg_cones.alloc(npix * 28));
+        CREATE_TRY(hipMemsetAsync(c->dbg_steps.get(), 0, npix * 7, cur(c).stream));
+        CREATE_TRY(hipMemsetAsync(c->dbg_cones.get(), 0, npix * 28 * sizeof(float), cur(c).stream));
     }
     CREATE_TRY(hipStreamSynchronize(cur(c).stream));
 #undef CREATE_TRY
@@ -875,21 +815,12 @@ void vct_destroy(vct_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     vct_comm_release(c);
+    // every stream that can still read a buffer is waited for before the context's members free their memory
     for (int k = 0; k < c->frames_in_flight; ++k) slot_release(c->slots[k]);
-    raster_release(c->shadow_raster);
-    if (c->ev_xslot) (void)hipEventDestroy(c->ev_xslot);
-    void* bufs[] = {c->chain, c->cells, c->shadow_tiles, c->staging, c->gb_linear, c->dbg_steps,
-                    c->dbg_cones, c->step_counter, c->stats, c->vt_pix, c->steps_dev, c->spread_lut, c->tri_pos,
-                    c->tri_mat, c->tri_alpha, c->mat_albedo, c->shadow, c->acc, c->brick_slot, c->frag_sorted, c->slot_first, c->slot_brick, c->vox_items, c->vox_acc2, c->vox_acc2_attr, c->vox_multi_slot, c->stage,
-                    c->stage_albedo, c->stage_normal, c->plan, c->frag_bary, c->frag_alb, c->tri_qnrm,
-                    c->aniso, c->ref_big, c->brick_flags, c->brick_prev, c->mip_seen, c->mip_seen_b, c->bounce_list, c->brick_over, c->chain_b, c->attr_albedo, c->attr_normal,
-                    c->tri_nrm, c->tri_tan, c->tri_bit, c->mat_specular, c->tri_uv, c->tex_texels, c->tex_desc, c->mat_tex};
-    for (void* b : bufs) if (b) (void)hipFree(b);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    if (c->ev_shadow) (void)hipEventDestroy(c->ev_shadow);
-    for (int k = 0; k < 8; ++k) if (c->ev_auto[k]) (void)hipEventDestroy(c->ev_auto[k]);
     if (c->aux_stream) { (void)hipStreamSynchronize(c->aux_stream); (void)hipStreamDestroy(c->aux_stream); }
+    hipEvent_t events[] = {c->ev_xslot, c->ev_fork, c->ev_join, c->ev_shadow};
+    for (hipEvent_t ev : events) if (ev) (void)hipEventDestroy(ev);
+    for (int k = 0; k < 8; ++k) if (c->ev_auto[k]) (void)hipEventDestroy(c->ev_auto[k]);
     delete c;
 }
 
@@ -968,74 +899,63 @@ int vct_upload_triangles(vct_ctx* c, const float* pos, const int32_t* material, 
     }
     HIP_TRY(c, hipSetDevice(c->device));
     PIPE_TRY(pipeline_drain(c));
-    if (c->tri_pos) { (void)hipFree(c->tri_pos); c->tri_pos = nullptr; }
-    if (c->tri_mat) { (void)hipFree(c->tri_mat); c->tri_mat = nullptr; }
-    if (c->tri_alpha) { (void)hipFree(c->tri_alpha); c->tri_alpha = nullptr; }
-    c->tri_alpha_dirty = true;
-    if (c->mat_albedo) { (void)hipFree(c->mat_albedo); c->mat_albedo = nullptr; }
+    VctMesh& m = c->mesh;
+    m.tri_pos.reset(); m.tri_mat.reset(); m.tri_alpha.reset(); m.mat_albedo.reset();
+    m.tri_alpha_dirty = true;
     raster_release_mesh(c->shadow_raster);
     for (VctFrameSlot& sl : c->slots) raster_release_mesh(sl.raster);
     c->auto_state = 0; c->auto_choice = -1;       // the raster form is measured again for the new mesh
-    drop_voxel_plan(c);     // before anything below can fail: the old plan indexes the old mesh
-    float** frames[4] = {&c->tri_nrm, &c->tri_tan, &c->tri_bit, &c->tri_uv};       // belong to the old mesh
-    for (float** f : frames) if (*f) { (void)hipFree(*f); *f = nullptr; }
-    if (c->mat_tex) { (void)hipFree(c->mat_tex); c->mat_tex = nullptr; }           // indexed by the old materials
+    // Everything indexed by the OLD mesh's triangles or slots goes BEFORE anything below can fail, so that a failed upload
+    // leaves the context without a plan (vct_voxelize then refuses) instead of with the old mesh's plan over the new
+    // mesh's triangles.  Level 0 / brick_prev keep describing what the chain shows.
+    c->vox = VctVoxelPlan();
+    m.tri_nrm.reset(); m.tri_tan.reset(); m.tri_bit.reset(); m.tri_uv.reset();       // belong to the old mesh
+    m.mat_tex.reset();                                                                // indexed by the old materials
     if (ntri >= (1 << 23))
         return fail(c, VCT_ERR_INVALID, "vct_upload_triangles: more than 2^23 - 1 triangles (the voxelizer's fragment "
                                         "entries carry 23 bits of triangle index)");
-    HIP_TRY(c, hipMalloc(&c->tri_pos, (size_t)ntri * 9 * sizeof(float)));
-    HIP_TRY(c, hipMalloc(&c->tri_mat, (size_t)ntri * sizeof(int32_t)));
-    HIP_TRY(c, hipMalloc(&c->mat_albedo, (size_t)nmat * 4 * sizeof(float)));
-    if (!c->plan) HIP_TRY(c, hipMalloc(&c->plan, 4 * sizeof(uint32_t)));
-    HIP_TRY(c, hipMemcpyAsync(c->tri_pos, pos, (size_t)ntri * 9 * sizeof(float),
+    HIP_TRY(c, m.tri_pos.alloc((size_t)ntri * 9));
+    HIP_TRY(c, m.tri_mat.alloc((size_t)ntri));
+    HIP_TRY(c, m.mat_albedo.alloc((size_t)nmat * 4));
+    HIP_TRY(c, c->plan.reserve(4));
+    HIP_TRY(c, hipMemcpyAsync(m.tri_pos.get(), pos, (size_t)ntri * 9 * sizeof(float),
                               hipMemcpyHostToDevice, cur(c).stream));
-    HIP_TRY(c, hipMemcpyAsync(c->tri_mat, material, (size_t)ntri * sizeof(int32_t),
+    HIP_TRY(c, hipMemcpyAsync(m.tri_mat.get(), material, (size_t)ntri * sizeof(int32_t),
                               hipMemcpyHostToDevice, cur(c).stream));
-    HIP_TRY(c, hipMemcpyAsync(c->mat_albedo, albedo, (size_t)nmat * 4 * sizeof(float),
+    HIP_TRY(c, hipMemcpyAsync(m.mat_albedo.get(), albedo, (size_t)nmat * 4 * sizeof(float),
                               hipMemcpyHostToDevice, cur(c).stream));
-    c->ntri = ntri;
-    c->nmat = nmat;
+    m.ntri = ntri;
+    m.nmat = nmat;
     // Voxelization plan (geometry only): the exact conservative fragments of every triangle -- count, allocate, fill;
     // triangles with a huge bounding box are enumerated by a workgroup each -- then sorted by brick (build_voxel_slots).
-    VctVoxParams p = vox_params(c);
+    const VctVoxParams p = vox_params(c, c->vox);
     uint32_t counts[4] = {0, 0, 0, 0};
-    int32_t* big_tmp = nullptr;
-    uint2* frags = nullptr;
-    auto plan_fail = [&](hipError_t e, const char* what) {
-        if (big_tmp) (void)hipFree(big_tmp);
-        if (frags) (void)hipFree(frags);
-        return fail(c, e == hipErrorOutOfMemory ? VCT_ERR_NOMEM : VCT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
-    };
-#define PLAN_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return plan_fail(e_, #expr); } while (0)
-    PLAN_TRY(hipMalloc(&big_tmp, (size_t)ntri * sizeof(int32_t)));
-    PLAN_TRY(hipMemsetAsync(c->plan, 0, 4 * sizeof(uint32_t), cur(c).stream));
-    PLAN_TRY(vct_launch_vox_plan(p, c->plan, nullptr, big_tmp, false, cur(c).stream));
-    PLAN_TRY(hipMemcpyAsync(counts, c->plan, sizeof(counts), hipMemcpyDeviceToHost, cur(c).stream));
-    PLAN_TRY(hipStreamSynchronize(cur(c).stream));
+    uint32_t* plan = c->plan.get();
+    VctBuf<int32_t> big_tmp;
+    VctBuf<uint2> frags;
+    HIP_TRY(c, big_tmp.alloc((size_t)ntri));
+    HIP_TRY(c, hipMemsetAsync(plan, 0, 4 * sizeof(uint32_t), cur(c).stream));
+    HIP_TRY(c, vct_launch_vox_plan(p, plan, nullptr, big_tmp.get(), false, cur(c).stream));
+    HIP_TRY(c, hipMemcpyAsync(counts, plan, sizeof(counts), hipMemcpyDeviceToHost, cur(c).stream));
+    HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     const uint32_t n_small = counts[0];
     const int n_big = (int)counts[1];
-    PLAN_TRY(vct_launch_vox_plan_big(p, big_tmp, n_big, c->plan, nullptr, false, cur(c).stream));
-    PLAN_TRY(hipMemcpyAsync(counts, c->plan, sizeof(counts), hipMemcpyDeviceToHost, cur(c).stream));
-    PLAN_TRY(hipStreamSynchronize(cur(c).stream));
+    HIP_TRY(c, vct_launch_vox_plan_big(p, big_tmp.get(), n_big, plan, nullptr, false, cur(c).stream));
+    HIP_TRY(c, hipMemcpyAsync(counts, plan, sizeof(counts), hipMemcpyDeviceToHost, cur(c).stream));
+    HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     const unsigned long long total = (unsigned long long)n_small + counts[2];
     // counts[3]: one of the 32-bit device counters wrapped while counting (k_vox_plan / k_vox_plan_big flag it) -- the
     // totals above would then look small
-    if (total >= (1ull << 32) || counts[3] != 0u) {
-        (void)hipFree(big_tmp);
+    if (total >= (1ull << 32) || counts[3] != 0u)
         return fail(c, VCT_ERR_INVALID, "vct_upload_triangles: the mesh has 2^32 or more conservative fragments at this grid size");
-    }
-    PLAN_TRY(hipMalloc(&frags, (size_t)(total ? total : 1ull) * sizeof(uint2)));
+    HIP_TRY(c, frags.alloc((size_t)(total ? total : 1ull)));
     const uint32_t restart[4] = {0u, 0u, n_small, 0u};          // small triangles fill [0, n_small), the big ones behind
-    PLAN_TRY(hipMemcpyAsync(c->plan, restart, sizeof(restart), hipMemcpyHostToDevice, cur(c).stream));
-    PLAN_TRY(vct_launch_vox_plan(p, c->plan, frags, nullptr, true, cur(c).stream));
-    PLAN_TRY(vct_launch_vox_plan_big(p, big_tmp, n_big, c->plan, frags, true, cur(c).stream));
-    PLAN_TRY(hipStreamSynchronize(cur(c).stream));
-#undef PLAN_TRY
-    (void)hipFree(big_tmp);
-    big_tmp = nullptr;
-    const int rc = build_voxel_slots(c, frags, (uint32_t)total);
-    (void)hipFree(frags);
-    return rc;
+    HIP_TRY(c, hipMemcpyAsync(plan, restart, sizeof(restart), hipMemcpyHostToDevice, cur(c).stream));
+    HIP_TRY(c, vct_launch_vox_plan(p, plan, frags.get(), nullptr, true, cur(c).stream));
+    HIP_TRY(c, vct_launch_vox_plan_big(p, big_tmp.get(), n_big, plan, frags.get(), true, cur(c).stream));
+    HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
+    big_tmp.reset();
+    return build_voxel_slots(c, frags.get(), (uint32_t)total);
 }
 
 static size_t shadow_tile_count(int S) { const size_t nb = ((size_t)S + 7) >> 3; return nb * nb; }
@@ -1044,27 +964,27 @@ int vct_upload_shadow_map(vct_ctx* c, const float* depth, int32_t size, const fl
     if (!c) return VCT_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
     PIPE_TRY(pipeline_drain(c));
-    if (c->shadow) { (void)hipFree(c->shadow); c->shadow = nullptr; c->shadow_size = 0; }
-    if (c->shadow_tiles) { (void)hipFree(c->shadow_tiles); c->shadow_tiles = nullptr; }
+    c->shadow.reset();
+    c->shadow_tiles.reset();
+    c->shadow_size = 0;
     if (!depth) return VCT_OK;
     if (size <= 0 || !light_vp) return fail(c, VCT_ERR_INVALID, "vct_upload_shadow_map: bad size");
     // the map lives as shadow-map words (vct_internal.h): depths clamped to [0, 1] like a GL depth texture, epoch 0;
-    // a later vct_render_shadow_map starts a fresh epoch cycle over this buffer (shadow_passes = 0: memset first)
+    // a later vct_render_shadow_map starts a fresh epoch cycle over this buffer (shadow_passes = 0: memset first).
+    // Built in locals: a failure leaves the context without a map.
     const size_t n = (size_t)size * size;
-    float* tmp = nullptr;
-    HIP_TRY(c, hipMalloc(&c->shadow, n * sizeof(uint32_t)));
-    hipError_t e = hipMalloc(&tmp, n * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpyAsync(tmp, depth, n * sizeof(float), hipMemcpyHostToDevice, cur(c).stream);
-    if (e == hipSuccess) e = vct_launch_shadow_encode(tmp, c->shadow, n, 0u, cur(c).stream);
-    if (e == hipSuccess) e = hipMalloc(&c->shadow_tiles, shadow_tile_count(size) * sizeof(uint2));
-    if (e == hipSuccess) e = vct_launch_shadow_minmax(c->shadow, 0u, size, c->shadow_tiles, cur(c).stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(cur(c).stream);
-    if (tmp) (void)hipFree(tmp);
-    if (e != hipSuccess) {
-        (void)hipFree(c->shadow); c->shadow = nullptr;
-        if (c->shadow_tiles) { (void)hipFree(c->shadow_tiles); c->shadow_tiles = nullptr; }
-        HIP_TRY(c, e);
-    }
+    VctBuf<uint32_t> words;
+    VctBuf<float> tmp;
+    VctBuf<uint2> tiles;
+    HIP_TRY(c, words.alloc(n));
+    HIP_TRY(c, tmp.alloc(n));
+    HIP_TRY(c, hipMemcpyAsync(tmp.get(), depth, n * sizeof(float), hipMemcpyHostToDevice, cur(c).stream));
+    HIP_TRY(c, vct_launch_shadow_encode(tmp.get(), words.get(), n, 0u, cur(c).stream));
+    HIP_TRY(c, tiles.alloc(shadow_tile_count(size)));
+    HIP_TRY(c, vct_launch_shadow_minmax(words.get(), 0u, size, tiles.get(), cur(c).stream));
+    HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
+    c->shadow = std::move(words);
+    c->shadow_tiles = std::move(tiles);
     c->shadow_size = size;
     c->shadow_ebase = 0u;
     c->shadow_passes = 0u;
@@ -1078,14 +998,10 @@ int vct_upload_shadow_map(vct_ctx* c, const float* depth, int32_t size, const fl
 // the shadow-map words).
 static int raster_args(vct_ctx* c, VctRasterScratch& r, int side_w, int side_h, bool depth_only, bool binned, hipStream_t s,
                        VctRasterArgs& a) {
-    if (!c->tri_pos) return fail(c, VCT_ERR_INVALID, "no triangles uploaded");
+    if (!c->mesh.tri_pos) return fail(c, VCT_ERR_INVALID, "no triangles uploaded");
     const size_t pixels = (size_t)side_w * side_h;
-    if (!depth_only && r.vis_words < pixels) {
-        if (r.vis) { (void)hipFree(r.vis); r.vis = nullptr; r.vis_words = 0; }
-        HIP_TRY(c, hipMalloc(&r.vis, pixels * sizeof(unsigned long long)));
-        r.vis_words = pixels;
-        r.dirty = true;
-    }
+    const VctMesh& m = c->mesh;
+    if (!depth_only) HIP_TRY(c, r.vis.reserve(pixels, &r.dirty));
     const uint32_t bins = (uint32_t)(((size_t)side_w + 15) / 16 * (((size_t)side_h + 15) / 16));
     if (binned) {
         // Scratch of the tile-binned form (vct_raster.hip).  One 160-byte record per visible sub-triangle (back faces are
@@ -1094,107 +1010,82 @@ static int raster_args(vct_ctx* c, VctRasterScratch& r, int side_w, int side_h, 
         // Bistro-class street at 4K -- plus the bins' counters.  Whatever does not fit takes the huge list or is
         // rasterised in place (k_bin_setup), so these are sizes, not limits.  ~200 B per triangle and pass kind,
         // replicated per rank of a multi-GPU frame.
-        const uint32_t want_recs = (uint32_t)c->ntri + 4096u;
-        const size_t want_ent_sz = (size_t)c->ntri * 4 + (size_t)bins * 4 + 65536;
+        const uint32_t want_recs = (uint32_t)m.ntri + 4096u;
+        const size_t want_ent_sz = (size_t)m.ntri * 4 + (size_t)bins * 4 + 65536;
         const uint32_t want_ent = (uint32_t)(want_ent_sz < 0x7fffffffull ? want_ent_sz : 0x7fffffffull);
-        if (r.bin_rec_cap < want_recs) {
-            if (r.bin_recs) { (void)hipFree(r.bin_recs); r.bin_recs = nullptr; r.bin_rec_cap = 0u; }
-            HIP_TRY(c, hipMalloc(&r.bin_recs, (size_t)want_recs * 160));
-            r.bin_rec_cap = want_recs;
-        }
-        if (r.bin_entry_cap < want_ent) {
-            if (r.bin_entries) { (void)hipFree(r.bin_entries); r.bin_entries = nullptr; r.bin_entry_cap = 0u; }
-            HIP_TRY(c, hipMalloc(&r.bin_entries, ((size_t)want_ent + 1) * sizeof(uint2)));      // + the spare entry k_bin_fill's idle lanes write
-            r.bin_entry_cap = want_ent;
-        }
-        const uint32_t want_items = bins + r.bin_entry_cap / 512u + 1u;      // sum over bins of ceil(entries / slice)
-        if (r.bin_item_cap < want_items) {
-            if (r.bin_items) { (void)hipFree(r.bin_items); r.bin_items = nullptr; r.bin_item_cap = 0u; }
-            HIP_TRY(c, hipMalloc(&r.bin_items, (size_t)want_items * sizeof(uint4)));
-            r.bin_item_cap = want_items;
-        }
-        if (r.bin_bins < bins) {
-            if (r.bin_count) { (void)hipFree(r.bin_count); r.bin_count = nullptr; r.bin_bins = 0u; }
-            HIP_TRY(c, hipMalloc(&r.bin_count, (size_t)bins * 2 * VCT_BIN_CSTRIDE * sizeof(uint32_t)));
-            r.bin_bins = bins;
-            r.dirty = true;
-        }
-        if (!r.bin_huge) {
-            HIP_TRY(c, hipMalloc(&r.bin_huge, (size_t)(VCT_BIN_HUGE_CAP + 16 + 32) * sizeof(uint32_t)));
-            r.dirty = true;
-        }
+        HIP_TRY(c, r.bin_recs.reserve((size_t)want_recs * 160));
+        HIP_TRY(c, r.bin_entries.reserve((size_t)want_ent + 1));      // + the spare entry k_bin_fill's idle lanes write
+        // sum over bins of ceil(entries / slice)
+        HIP_TRY(c, r.bin_items.reserve(bins + (r.bin_entries.size() - 1) / 512u + 1u));
+        HIP_TRY(c, r.bin_count.reserve((size_t)bins * 2 * VCT_BIN_CSTRIDE, &r.dirty));
+        HIP_TRY(c, r.bin_huge.reserve((size_t)(VCT_BIN_HUGE_CAP + 16 + 32), &r.dirty));
     } else {
-        if (!r.lists) HIP_TRY(c, hipMalloc(&r.lists, (size_t)c->ntri * 4 * sizeof(int32_t)));
-        if (!r.recs) HIP_TRY(c, hipMalloc(&r.recs, (size_t)c->ntri * 2 * 96));
-        if (!r.counts) { HIP_TRY(c, hipMalloc(&r.counts, 8 * sizeof(uint32_t))); r.dirty = true; }
+        HIP_TRY(c, r.lists.reserve((size_t)m.ntri * 4));
+        HIP_TRY(c, r.recs.reserve((size_t)m.ntri * 2 * 96));
+        HIP_TRY(c, r.counts.reserve(8, &r.dirty));
         // tile work items: 16x16-pixel pieces of large triangles; pixels/16 entries is ~16x the typical
         // demand (sum of visible bounding boxes ~ a few frames' worth of pixels); overflow is handled
-        const size_t want_items = pixels / 16 + 4096;
-        if (r.item_capacity < want_items) {
-            if (r.items) { (void)hipFree(r.items); r.items = nullptr; }
-            HIP_TRY(c, hipMalloc(&r.items, want_items * sizeof(uint2)));
-            r.item_capacity = (uint32_t)want_items;
-        }
+        HIP_TRY(c, r.items.reserve(pixels / 16 + 4096));
     }
     if (r.dirty) {   // first pass, resized buffers, or a pass that failed half way: clear this kind's state once
         if (depth_only) c->shadow_passes = 0u;      // the shadow words restart their epoch cycle with a memset (below)
-        else HIP_TRY(c, hipMemsetAsync(r.vis, 0xff, r.vis_words * sizeof(unsigned long long), s));
+        else HIP_TRY(c, hipMemsetAsync(r.vis.get(), 0xff, r.vis.size() * sizeof(unsigned long long), s));
         if (binned) {
-            HIP_TRY(c, hipMemsetAsync(r.bin_count, 0, (size_t)r.bin_bins * 2 * VCT_BIN_CSTRIDE * sizeof(uint32_t), s));
-            HIP_TRY(c, hipMemsetAsync(r.bin_huge + VCT_BIN_HUGE_CAP, 0, (16 + 32) * sizeof(uint32_t), s));
+            HIP_TRY(c, hipMemsetAsync(r.bin_count.get(), 0, r.bin_count.size() * sizeof(uint32_t), s));
+            HIP_TRY(c, hipMemsetAsync(r.bin_huge.get() + VCT_BIN_HUGE_CAP, 0, (16 + 32) * sizeof(uint32_t), s));
         } else {
-            HIP_TRY(c, hipMemsetAsync(r.counts, 0, 8 * sizeof(uint32_t), s));
+            HIP_TRY(c, hipMemsetAsync(r.counts.get(), 0, 8 * sizeof(uint32_t), s));
         }
         r.dirty = false;
     }
     memset(&a, 0, sizeof(a));
     a.binned = binned ? 1 : 0;
     if (binned) {
-        a.bin_recs = r.bin_recs; a.bin_rec_cap = r.bin_rec_cap;
-        a.bin_entries = r.bin_entries; a.bin_entry_cap = r.bin_entry_cap;
+        a.bin_recs = r.bin_recs.get(); a.bin_rec_cap = (uint32_t)(r.bin_recs.size() / 160);
+        a.bin_entries = r.bin_entries.get(); a.bin_entry_cap = (uint32_t)(r.bin_entries.size() - 1);
         if (c->bin_test_caps[0] && c->bin_test_caps[0] < a.bin_rec_cap) a.bin_rec_cap = c->bin_test_caps[0];
         if (c->bin_test_caps[1] && c->bin_test_caps[1] < a.bin_entry_cap) a.bin_entry_cap = c->bin_test_caps[1];
-        a.bin_count = r.bin_count; a.bin_cursor = r.bin_count + (size_t)r.bin_bins * VCT_BIN_CSTRIDE;
-        a.bin_items = r.bin_items; a.bin_item_cap = r.bin_item_cap;
-        a.bin_huge = r.bin_huge; a.bin_huge_cap = VCT_BIN_HUGE_CAP;
-        a.bin_ctr = r.bin_huge + VCT_BIN_HUGE_CAP + 8 * r.bin_set;
-        a.bin_next_ctr = r.bin_huge + VCT_BIN_HUGE_CAP + 8 * (r.bin_set ^ 1);
+        a.bin_count = r.bin_count.get(); a.bin_cursor = r.bin_count.get() + r.bin_count.size() / 2;
+        a.bin_items = r.bin_items.get(); a.bin_item_cap = (uint32_t)r.bin_items.size();
+        a.bin_huge = r.bin_huge.get(); a.bin_huge_cap = VCT_BIN_HUGE_CAP;
+        a.bin_ctr = r.bin_huge.get() + VCT_BIN_HUGE_CAP + 8 * r.bin_set;
+        a.bin_next_ctr = r.bin_huge.get() + VCT_BIN_HUGE_CAP + 8 * (r.bin_set ^ 1);
         r.bin_set ^= 1;
     }
-    a.pos = c->tri_pos;
-    a.nrm = c->tri_nrm; a.tan = c->tri_tan; a.bit = c->tri_bit;
-    a.material = c->tri_mat;
-    a.albedo = c->mat_albedo;
-    a.specular = c->mat_specular;
-    a.ntri = c->ntri;
+    a.pos = m.tri_pos.get();
+    a.nrm = m.tri_nrm.get(); a.tan = m.tri_tan.get(); a.bit = m.tri_bit.get();
+    a.material = m.tri_mat.get();
+    a.albedo = m.mat_albedo.get();
+    a.specular = m.mat_specular.get();
+    a.ntri = m.ntri;
     a.model_scale = c->cfg.model_scale;
-    a.vis = r.vis;
+    a.vis = r.vis.get();
     a.vis32 = nullptr;          // vct_render_shadow_map points it at the shadow-map words
     a.vis32_ebase = 0u;
     if (!binned) {
-        a.items = r.items;
+        a.items = r.items.get();
         // [wave, group, item, -]: the wave and group counters are one 8-byte-aligned pair, k_raster_vis reserves both
         // lists of a workgroup with a single 64-bit atomic
-        uint32_t* ctr = r.counts + 4 * r.set;
-        a.wave_list = r.lists;
+        uint32_t* ctr = r.counts.get() + 4 * r.set;
+        a.wave_list = r.lists.get();
         a.wave_count = ctr;
-        a.group_list = r.lists + (size_t)c->ntri * 2;
+        a.group_list = r.lists.get() + (size_t)m.ntri * 2;
         a.group_count = ctr + 1;
         a.item_count = ctr + 2;
-        a.next_counts = r.counts + 4 * (r.set ^ 1);
-        a.recs = r.recs;
+        a.next_counts = r.counts.get() + 4 * (r.set ^ 1);
+        a.recs = r.recs.get();
         r.set ^= 1;
-        a.item_capacity = r.item_capacity;
+        a.item_capacity = (uint32_t)r.items.size();
     }
     a.tex = textures_of(c);
     if (!depth_only) {          // the main draw's alpha-test class per triangle: once per mesh / texture set
-        if (!c->tri_alpha) { HIP_TRY(c, hipMalloc(&c->tri_alpha, (size_t)c->ntri * sizeof(int32_t))); c->tri_alpha_dirty = true; }
-        if (c->tri_alpha_dirty) {
-            HIP_TRY(c, vct_launch_tri_alpha(a, c->tri_alpha, s));
-            c->tri_alpha_dirty = false;
+        HIP_TRY(c, c->mesh.tri_alpha.reserve((size_t)m.ntri, &c->mesh.tri_alpha_dirty));
+        if (m.tri_alpha_dirty) {
+            HIP_TRY(c, vct_launch_tri_alpha(a, m.tri_alpha.get(), s));
+            c->mesh.tri_alpha_dirty = false;
             c->produced_since_switch = true;      // (shared by both frame slots: the other slot's next pass follows this one)
         }
-        a.tri_alpha = c->tri_alpha;
+        a.tri_alpha = m.tri_alpha.get();
     }
     return VCT_OK;
 }
@@ -1204,20 +1095,18 @@ int vct_upload_mesh_attributes(vct_ctx* c, const float* normal, const float* tan
     if (!c) return VCT_ERR_INVALID;
     if (!normal || !tangent || !bitangent || !specular)
         return fail(c, VCT_ERR_INVALID, "vct_upload_mesh_attributes: null input");
-    if (!c->tri_pos) return fail(c, VCT_ERR_INVALID, "vct_upload_mesh_attributes: call vct_upload_triangles first");
+    if (!c->mesh.tri_pos) return fail(c, VCT_ERR_INVALID, "vct_upload_mesh_attributes: call vct_upload_triangles first");
     HIP_TRY(c, hipSetDevice(c->device));
     PIPE_TRY(pipeline_drain(c));
-    float** dst[3] = {&c->tri_nrm, &c->tri_tan, &c->tri_bit};
+    VctBuf<float>* dst[3] = {&c->mesh.tri_nrm, &c->mesh.tri_tan, &c->mesh.tri_bit};
     const float* src[3] = {normal, tangent, bitangent};
-    const size_t bytes = (size_t)c->ntri * 9 * sizeof(float);
+    const size_t n = (size_t)c->mesh.ntri * 9;
     for (int k = 0; k < 3; ++k) {
-        if (*dst[k]) { (void)hipFree(*dst[k]); *dst[k] = nullptr; }
-        HIP_TRY(c, hipMalloc(dst[k], bytes));
-        HIP_TRY(c, hipMemcpyAsync(*dst[k], src[k], bytes, hipMemcpyHostToDevice, cur(c).stream));
+        HIP_TRY(c, dst[k]->alloc(n));
+        HIP_TRY(c, hipMemcpyAsync(dst[k]->get(), src[k], n * sizeof(float), hipMemcpyHostToDevice, cur(c).stream));
     }
-    if (c->mat_specular) { (void)hipFree(c->mat_specular); c->mat_specular = nullptr; }
-    HIP_TRY(c, hipMalloc(&c->mat_specular, (size_t)c->nmat * 3 * sizeof(float)));
-    HIP_TRY(c, hipMemcpyAsync(c->mat_specular, specular, (size_t)c->nmat * 3 * sizeof(float),
+    HIP_TRY(c, c->mesh.mat_specular.alloc((size_t)c->mesh.nmat * 3));
+    HIP_TRY(c, hipMemcpyAsync(c->mesh.mat_specular.get(), specular, (size_t)c->mesh.nmat * 3 * sizeof(float),
                               hipMemcpyHostToDevice, cur(c).stream));
     HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     return VCT_OK;
@@ -1226,15 +1115,14 @@ int vct_upload_mesh_attributes(vct_ctx* c, const float* normal, const float* tan
 int vct_upload_mesh_uvs(vct_ctx* c, const float* uv) {
     if (!c) return VCT_ERR_INVALID;
     if (!uv) return fail(c, VCT_ERR_INVALID, "vct_upload_mesh_uvs: null input");
-    if (!c->tri_pos) return fail(c, VCT_ERR_INVALID, "vct_upload_mesh_uvs: call vct_upload_triangles first");
+    if (!c->mesh.tri_pos) return fail(c, VCT_ERR_INVALID, "vct_upload_mesh_uvs: call vct_upload_triangles first");
     HIP_TRY(c, hipSetDevice(c->device));
     PIPE_TRY(pipeline_drain(c));
-    if (c->tri_uv) { (void)hipFree(c->tri_uv); c->tri_uv = nullptr; }
-    const size_t bytes = (size_t)c->ntri * 6 * sizeof(float);
-    c->tri_alpha_dirty = true;          // textures take effect once the coordinates are there
-    c->frag_alb_dirty = true;
-    HIP_TRY(c, hipMalloc(&c->tri_uv, bytes));
-    HIP_TRY(c, hipMemcpyAsync(c->tri_uv, uv, bytes, hipMemcpyHostToDevice, cur(c).stream));
+    const size_t n = (size_t)c->mesh.ntri * 6;
+    c->mesh.tri_alpha_dirty = true;          // textures take effect once the coordinates are there
+    c->vox.frag_alb_dirty = true;
+    HIP_TRY(c, c->mesh.tri_uv.alloc(n));
+    HIP_TRY(c, hipMemcpyAsync(c->mesh.tri_uv.get(), uv, n * sizeof(float), hipMemcpyHostToDevice, cur(c).stream));
     HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     return VCT_OK;
 }
@@ -1242,16 +1130,15 @@ int vct_upload_mesh_uvs(vct_ctx* c, const float* uv) {
 int vct_upload_textures(vct_ctx* c, const uint8_t* const* rgba8, const int32_t* width, const int32_t* height,
                         int32_t ntex, const int32_t* mat_tex) {
     if (!c) return VCT_ERR_INVALID;
-    if (!c->tri_pos) return fail(c, VCT_ERR_INVALID, "vct_upload_textures: call vct_upload_triangles first");
+    if (!c->mesh.tri_pos) return fail(c, VCT_ERR_INVALID, "vct_upload_textures: call vct_upload_triangles first");
     HIP_TRY(c, hipSetDevice(c->device));
     PIPE_TRY(pipeline_drain(c));
-    if (c->tex_texels) { (void)hipFree(c->tex_texels); c->tex_texels = nullptr; }
-    if (c->tex_desc) { (void)hipFree(c->tex_desc); c->tex_desc = nullptr; }
-    if (c->mat_tex) { (void)hipFree(c->mat_tex); c->mat_tex = nullptr; }
-    c->ntex = 0;
-    c->tri_alpha_dirty = true;
-    c->frag_alb_dirty = true;
-    c->has_alpha_textures = false;
+    VctMesh& m = c->mesh;
+    m.tex_texels.reset(); m.tex_desc.reset(); m.mat_tex.reset();
+    m.ntex = 0;
+    m.tri_alpha_dirty = true;
+    c->vox.frag_alb_dirty = true;
+    m.has_alpha_textures = false;
     c->auto_state = 0; c->auto_choice = -1;
     if (ntex == 0) return VCT_OK;                     // detach: flat colours again
     if (ntex < 0 || !rgba8 || !width || !height || !mat_tex)
@@ -1278,7 +1165,7 @@ int vct_upload_textures(vct_ctx* c, const uint8_t* const* rgba8, const int32_t* 
         d.flags = flags;
         d.nlev = 1;
         if (c->cfg.texture_mipmaps)
-            for (int m = width[i] > height[i] ? width[i] : height[i]; m > 1; m >>= 1) ++d.nlev;
+            for (int side = width[i] > height[i] ? width[i] : height[i]; side > 1; side >>= 1) ++d.nlev;
         size_t off = 0;
         for (int k = 0; k < d.nlev; ++k) {
             d.lvl[k] = (uint32_t)off;
@@ -1287,28 +1174,28 @@ int vct_upload_textures(vct_ctx* c, const uint8_t* const* rgba8, const int32_t* 
         total += off;
         if (total > 0xffffffffull) return fail(c, VCT_ERR_INVALID, "vct_upload_textures: more than 2^32 texels");
     }
-    for (int32_t m = 0; m < c->nmat * 3; ++m)
-        if (mat_tex[m] >= ntex) return fail(c, VCT_ERR_INVALID, "vct_upload_textures: texture index out of range");
-    HIP_TRY(c, hipMalloc(&c->tex_texels, total * 4));
-    HIP_TRY(c, hipMalloc(&c->tex_desc, (size_t)ntex * sizeof(VctTexDesc)));
-    HIP_TRY(c, hipMalloc(&c->mat_tex, (size_t)c->nmat * 3 * sizeof(int32_t)));
+    for (int32_t k = 0; k < m.nmat * 3; ++k)
+        if (mat_tex[k] >= ntex) return fail(c, VCT_ERR_INVALID, "vct_upload_textures: texture index out of range");
+    HIP_TRY(c, m.tex_texels.alloc(total));
+    HIP_TRY(c, m.tex_desc.alloc((size_t)ntex));
+    HIP_TRY(c, m.mat_tex.alloc((size_t)m.nmat * 3));
+    uint32_t* texels = m.tex_texels.get();
     for (int32_t i = 0; i < ntex; ++i) {
         const VctTexDesc& d = desc[(size_t)i];
-        HIP_TRY(c, hipMemcpyAsync(c->tex_texels + d.off, rgba8[i], (size_t)width[i] * height[i] * 4,
+        HIP_TRY(c, hipMemcpyAsync(texels + d.off, rgba8[i], (size_t)width[i] * height[i] * 4,
                                   hipMemcpyHostToDevice, cur(c).stream));
         for (int k = 1; k < d.nlev; ++k) {
             const int pw = d.w >> (k - 1) > 1 ? d.w >> (k - 1) : 1, ph = d.h >> (k - 1) > 1 ? d.h >> (k - 1) : 1;
             const int w = d.w >> k > 1 ? d.w >> k : 1, h = d.h >> k > 1 ? d.h >> k : 1;
-            HIP_TRY(c, vct_launch_tex_mip(c->tex_texels + d.off + d.lvl[k - 1], pw, ph, c->tex_texels + d.off + d.lvl[k],
-                                          w, h, cur(c).stream));
+            HIP_TRY(c, vct_launch_tex_mip(texels + d.off + d.lvl[k - 1], pw, ph, texels + d.off + d.lvl[k], w, h, cur(c).stream));
         }
     }
-    HIP_TRY(c, hipMemcpyAsync(c->tex_desc, desc.data(), (size_t)ntex * sizeof(VctTexDesc), hipMemcpyHostToDevice, cur(c).stream));
-    HIP_TRY(c, hipMemcpyAsync(c->mat_tex, mat_tex, (size_t)c->nmat * 3 * sizeof(int32_t), hipMemcpyHostToDevice, cur(c).stream));
+    HIP_TRY(c, hipMemcpyAsync(m.tex_desc.get(), desc.data(), (size_t)ntex * sizeof(VctTexDesc), hipMemcpyHostToDevice, cur(c).stream));
+    HIP_TRY(c, hipMemcpyAsync(m.mat_tex.get(), mat_tex, (size_t)m.nmat * 3 * sizeof(int32_t), hipMemcpyHostToDevice, cur(c).stream));
     HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
-    c->ntex = ntex;
-    for (int32_t m = 0; m < c->nmat; ++m)         // a diffuse map with non-opaque texels: its fragments are alpha-tested
-        if (mat_tex[3 * m] >= 0 && (desc[(size_t)mat_tex[3 * m]].flags & 1u)) c->has_alpha_textures = true;
+    m.ntex = ntex;
+    for (int32_t k = 0; k < m.nmat; ++k)               // a diffuse map with non-opaque texels: its fragments are alpha-tested
+        if (mat_tex[3 * k] >= 0 && (desc[(size_t)mat_tex[3 * k]].flags & 1u)) m.has_alpha_textures = true;
     return VCT_OK;
 }
 
@@ -1320,25 +1207,25 @@ int vct_render_shadow_map(vct_ctx* c, const float light_vp[16]) {
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->shadow && c->shadow_size == S) PIPE_TRY(pipeline_join(c)); else PIPE_TRY(pipeline_drain(c));   // (re)allocation: host wait
     if (c->shadow && c->shadow_size != S) {
-        (void)hipFree(c->shadow); c->shadow = nullptr; c->shadow_size = 0;
-        if (c->shadow_tiles) { (void)hipFree(c->shadow_tiles); c->shadow_tiles = nullptr; }
+        c->shadow.reset(); c->shadow_size = 0;
+        c->shadow_tiles.reset();
     }
     if (!c->shadow) {
-        HIP_TRY(c, hipMalloc(&c->shadow, (size_t)S * S * sizeof(uint32_t)));
+        HIP_TRY(c, c->shadow.alloc((size_t)S * S));
         c->shadow_passes = 0u;
     }
     // Tile bounds of the map (vct_launch_shadow_minmax) cost one more pass over it (~0.03 ms at 4096^2) and save the PCF
     // consumers their window fetches away from shadow boundaries: 14-28 % of the voxelize pass (street: 0.536 -> 0.461 ms at
     // 1024^3, 0.176 -> 0.126 at 256^3; atrium 0.033 -> 0.031).  Built where that repays the pass: meshes of >= 4 M
     // voxel fragments (VCT_SHADOW_TILES=0 / 1 in the environment: never / always).  Results are identical either way.
-    bool want_tiles = c->n_frags >= 4000000u;
+    bool want_tiles = c->vox.n_frags >= 4000000u;
     if (const char* st = getenv("VCT_SHADOW_TILES")) want_tiles = st[0] == '1';
-    if (want_tiles && !c->shadow_tiles) HIP_TRY(c, hipMalloc(&c->shadow_tiles, shadow_tile_count(S) * sizeof(uint2)));
-    if (!want_tiles && c->shadow_tiles) { (void)hipFree(c->shadow_tiles); c->shadow_tiles = nullptr; }
+    if (want_tiles && !c->shadow_tiles) HIP_TRY(c, c->shadow_tiles.alloc(shadow_tile_count(S)));
+    if (!want_tiles) c->shadow_tiles.reset();
     c->shadow_size = S;
     // A pass that fails from here on leaves a map (the old one, or a partly written one) but NO tile bounds: a stale or
     // uninitialised table would decide PCF windows wrongly, without one the consumers just fetch every window (advisor, round 5).
-    auto drop_tiles = [&]() { if (c->shadow_tiles) { (void)hipFree(c->shadow_tiles); c->shadow_tiles = nullptr; } };
+    auto drop_tiles = [&]() { c->shadow_tiles.reset(); };
     VctRasterArgs a;
     int rc = raster_args(c, c->shadow_raster, S, S, true, c->raster_mode == 2, cur(c).stream, a);
     if (rc) { drop_tiles(); return rc; }
@@ -1346,10 +1233,10 @@ int vct_render_shadow_map(vct_ctx* c, const float light_vp[16]) {
     // and 3 again -- a new pass overwrites older epochs by itself, readers see them as depth 1.0.
     const uint32_t epoch = 3u - (c->shadow_passes & 3u);
     if (epoch == 3u) {
-        const hipError_t em = hipMemsetAsync(c->shadow, 0xff, (size_t)S * S * sizeof(uint32_t), cur(c).stream);
+        const hipError_t em = hipMemsetAsync(c->shadow.get(), 0xff, (size_t)S * S * sizeof(uint32_t), cur(c).stream);
         if (em != hipSuccess) { drop_tiles(); HIP_TRY(c, em); }
     }
-    a.vis32 = c->shadow;
+    a.vis32 = c->shadow.get();
     a.vis32_ebase = VCT_SHADOW_EPOCH(epoch);
     memcpy(c->light_vp, light_vp, 64);
     const hipError_t e = vct_launch_shadow_raster(a, light_vp, S, cur(c).stream);
@@ -1358,7 +1245,7 @@ int vct_render_shadow_map(vct_ctx* c, const float light_vp[16]) {
     ++c->shadow_passes;
     // depth bounds per (dilated) 8 x 8 tile of the new map: the PCF consumers (voxelizer, G-buffer shade) decide most windows on them
     if (c->shadow_tiles) {
-        const hipError_t et = vct_launch_shadow_minmax(c->shadow, c->shadow_ebase, S, c->shadow_tiles, cur(c).stream);
+        const hipError_t et = vct_launch_shadow_minmax(c->shadow.get(), c->shadow_ebase, S, c->shadow_tiles.get(), cur(c).stream);
         if (et != hipSuccess) { drop_tiles(); HIP_TRY(c, et); }
     }
     return VCT_OK;
@@ -1369,13 +1256,11 @@ int vct_download_shadow_map(vct_ctx* c, float* depth) {
     if (!c->shadow) return fail(c, VCT_ERR_INVALID, "no shadow map");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t n = (size_t)c->shadow_size * c->shadow_size;
-    float* tmp = nullptr;
-    HIP_TRY(c, hipMalloc(&tmp, n * sizeof(float)));
-    hipError_t e = vct_launch_shadow_decode(c->shadow, tmp, n, c->shadow_ebase, cur(c).stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(depth, tmp, n * sizeof(float), hipMemcpyDeviceToHost, cur(c).stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(cur(c).stream);
-    (void)hipFree(tmp);
-    HIP_TRY(c, e);
+    VctBuf<float> tmp;
+    HIP_TRY(c, tmp.alloc(n));
+    HIP_TRY(c, vct_launch_shadow_decode(c->shadow.get(), tmp.get(), n, c->shadow_ebase, cur(c).stream));
+    HIP_TRY(c, hipMemcpyAsync(depth, tmp.get(), n * sizeof(float), hipMemcpyDeviceToHost, cur(c).stream));
+    HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     return VCT_OK;
 }
 
@@ -1384,7 +1269,7 @@ int vct_download_shadow_map(vct_ctx* c, float* depth) {
 static int render_gbuffer_rows_on(vct_ctx* c, const float view_proj[16], int32_t row0, int32_t row1, hipStream_t s,
                                   hipEvent_t shadow_ready = nullptr) {
     if (!view_proj) return fail(c, VCT_ERR_INVALID, "vct_render_gbuffer: null matrix");
-    if (!c->tri_nrm) return fail(c, VCT_ERR_INVALID, "vct_render_gbuffer: call vct_upload_mesh_attributes first");
+    if (!c->mesh.tri_nrm) return fail(c, VCT_ERR_INVALID, "vct_render_gbuffer: call vct_upload_mesh_attributes first");
     if (row0 < 0 || row1 > tiles_y(c) || row0 > row1)
         return fail(c, VCT_ERR_INVALID, "vct_render_gbuffer_rows: tile-row range outside the frame");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1398,7 +1283,7 @@ static int render_gbuffer_rows_on(vct_ctx* c, const float view_proj[16], int32_t
     // warm binned pass: biased towards the binned form -- advisor, round 4.)  Results are identical either way.
     static const struct { int form, slot; } kAutoSeq[6] = {{0, -1}, {0, 0}, {1, -1}, {1, 1}, {0, 2}, {1, 3}};
     int slot = -1;              // >= 0: this pass is timed sample `slot`
-    if (c->raster_mode == 0 && c->has_alpha_textures) {
+    if (c->raster_mode == 0 && c->mesh.has_alpha_textures) {
         if (c->auto_state == 6 && c->auto_choice < 0 && hipEventQuery(c->ev_auto[7]) == hipSuccess) {
             float t[4] = {0.0f, 0.0f, 0.0f, 0.0f};
             bool ok = true;
@@ -1415,7 +1300,7 @@ static int render_gbuffer_rows_on(vct_ctx* c, const float view_proj[16], int32_t
             c->auto_rows[0] = row0; c->auto_rows[1] = row1;
         } else if (c->auto_state >= 6) binned = true;        // all sampled, the last event still pending: stay on the last form
     }
-    const bool sampling = c->raster_mode == 0 && c->has_alpha_textures && c->auto_choice < 0 && row1 > row0 && c->auto_state < 6;
+    const bool sampling = c->raster_mode == 0 && c->mesh.has_alpha_textures && c->auto_choice < 0 && row1 > row0 && c->auto_state < 6;
     VctRasterArgs a;
     VctRasterScratch& r = cur(c).raster;
     int rc = raster_args(c, r, c->cfg.width, c->cfg.height, false, binned, s, a);
@@ -1426,10 +1311,10 @@ static int render_gbuffer_rows_on(vct_ctx* c, const float view_proj[16], int32_t
     if (sampling && e == hipSuccess) ++c->auto_state;
     if (e == hipSuccess && shadow_ready) e = hipStreamWaitEvent(s, shadow_ready, 0);
     if (e == hipSuccess)
-        e = vct_launch_gbuffer_shade(a, view_proj, c->cfg.width, c->cfg.height, row0, row1, c->shadow, c->shadow_ebase,
-                                     c->shadow_size, c->shadow_tiles, c->light_vp, cur(c).gb_tiled, s);
+        e = vct_launch_gbuffer_shade(a, view_proj, c->cfg.width, c->cfg.height, row0, row1, c->shadow.get(), c->shadow_ebase,
+                                     c->shadow_size, c->shadow_tiles.get(), c->light_vp, cur(c).gb_tiled.get(), s);
     if (e != hipSuccess) { r.dirty = true; HIP_TRY(c, e); }
-    cur(c).gb_current = cur(c).gb_tiled;
+    cur(c).gb_current = cur(c).gb_tiled.get();
     c->last_raster_form = binned ? 2 : 1;
     cur(c).last_row0 = row0;
     cur(c).last_row1 = row1;
@@ -1439,13 +1324,13 @@ static int render_gbuffer_rows_on(vct_ctx* c, const float view_proj[16], int32_t
     if (binned && getenv("VCT_BIN_STATS_DUMP")) {       // instrumented builds only (tools/r04_binstats.sh)
         uint32_t st[48];
         HIP_TRY(c, hipStreamSynchronize(s));
-        HIP_TRY(c, hipMemcpy(st, r.bin_huge + VCT_BIN_HUGE_CAP, sizeof(st), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(st, r.bin_huge.get() + VCT_BIN_HUGE_CAP, sizeof(st), hipMemcpyDeviceToHost));
         const uint32_t* ctr = st + 8 * (r.bin_set ^ 1);
         fprintf(stderr, "binstats: entries %u records %u items %u huge %u | ", ctr[0], ctr[1], ctr[2], ctr[4]);
         // (the adopted form of k_bin_raster only counts its alpha-queue flushes and the fragments they fetched; the
         // per-step counters of the earlier forms are in profiles/experiments/README.md)
         fprintf(stderr, "alpha_queue_flushes %u fragments_fetched %u\n", st[16 + 7], st[16 + 8]);
-        HIP_TRY(c, hipMemset(r.bin_huge + VCT_BIN_HUGE_CAP + 16, 0, 32 * sizeof(uint32_t)));
+        HIP_TRY(c, hipMemset(r.bin_huge.get() + VCT_BIN_HUGE_CAP + 16, 0, 32 * sizeof(uint32_t)));
     }
 #endif
     return VCT_OK;
@@ -1465,9 +1350,9 @@ int vct_download_gbuffer(vct_ctx* c, float* planes) {
     if (!c || !planes) return VCT_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t n = (size_t)c->cfg.width * c->cfg.height * VCT_GB_NPLANES;
-    if (!c->gb_linear) HIP_TRY(c, hipMalloc(&c->gb_linear, n * sizeof(float)));
-    HIP_TRY(c, vct_launch_untile_gbuffer(cur(c).gb_current, c->gb_linear, c->cfg.width, c->cfg.height, cur(c).stream));
-    HIP_TRY(c, hipMemcpyAsync(planes, c->gb_linear, n * sizeof(float), hipMemcpyDeviceToHost, cur(c).stream));
+    HIP_TRY(c, c->gb_linear.reserve(n));
+    HIP_TRY(c, vct_launch_untile_gbuffer(cur(c).gb_current, c->gb_linear.get(), c->cfg.width, c->cfg.height, cur(c).stream));
+    HIP_TRY(c, hipMemcpyAsync(planes, c->gb_linear.get(), n * sizeof(float), hipMemcpyDeviceToHost, cur(c).stream));
     HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     return VCT_OK;
 }
@@ -1476,58 +1361,61 @@ int vct_voxelize(vct_ctx* c, int32_t mode) {
     if (!c) return VCT_ERR_INVALID;
     if (mode != VCT_VOX_CONSERVATIVE_AVG && mode != VCT_VOX_REFERENCE)
         return fail(c, VCT_ERR_INVALID, "vct_voxelize: unknown mode");
-    if (!c->tri_pos) return fail(c, VCT_ERR_INVALID, "vct_voxelize: no triangles uploaded");
+    if (!c->mesh.tri_pos) return fail(c, VCT_ERR_INVALID, "vct_voxelize: no triangles uploaded");
     HIP_TRY(c, hipSetDevice(c->device));
     PIPE_TRY(pipeline_join(c));       // the staging pool is shared: the other slot's resolve may still read the previous pass
-    if (!c->brick_slot || !c->stage || (mode == VCT_VOX_REFERENCE && !c->ref_big))
+    if (!c->vox.brick_slot || !c->vox.stage || (mode == VCT_VOX_REFERENCE && !c->vox.ref_big))
         return fail(c, VCT_ERR_NOMEM, "vct_voxelize: the voxelization plan of this mesh could not be allocated "
                                       "(vct_upload_triangles reported it)");
-    const size_t pool_vox = (size_t)(c->nslots ? c->nslots : 1u) * 512;
+    const size_t pool_vox = (size_t)(c->vox.nslots ? c->vox.nslots : 1u) * 512;
     const size_t nbricks = (size_t)c->cfg.voxel_dim * c->cfg.voxel_dim * c->cfg.voxel_dim / 512;
-    if (mode == VCT_VOX_REFERENCE && !c->acc) {       // reference mode's accumulators: allocated on first use, zeroed once
-        HIP_TRY(c, hipMalloc(&c->acc, pool_vox * 16));
-        HIP_TRY(c, hipMemsetAsync(c->acc, 0, pool_vox * 16, cur(c).stream));
+    VctVoxelPlan& v = c->vox;
+    if (mode == VCT_VOX_REFERENCE && !v.acc) {       // reference mode's accumulators: allocated on first use, zeroed once
+        HIP_TRY(c, v.acc.alloc(pool_vox * 2));
+        HIP_TRY(c, hipMemsetAsync(v.acc.get(), 0, pool_vox * 16, cur(c).stream));
     }
-    if (c->acc_pending) {   // a pass that was never resolved: discard it
-        if (c->acc_mode == VCT_VOX_REFERENCE && c->acc) HIP_TRY(c, hipMemsetAsync(c->acc, 0, pool_vox * 16, cur(c).stream));
-        HIP_TRY(c, hipMemsetAsync(c->brick_flags, 0, nbricks * sizeof(uint32_t), cur(c).stream));
+    if (v.acc_pending) {   // a pass that was never resolved: discard it
+        if (c->acc_mode == VCT_VOX_REFERENCE && v.acc) HIP_TRY(c, hipMemsetAsync(v.acc.get(), 0, pool_vox * 16, cur(c).stream));
+        HIP_TRY(c, hipMemsetAsync(c->brick_flags.get(), 0, nbricks * sizeof(uint32_t), cur(c).stream));
     }
-    VctVoxParams p = vox_params(c);
+    VctVoxParams p = vox_params(c, v);
     p.mode = mode;
     if (mode == VCT_VOX_REFERENCE) {
         glm_voxel_projections(c, p.proj);
-        HIP_TRY(c, vct_launch_voxelize_reference(p, c->ref_big + 1, c->ref_big, cur(c).stream));
+        HIP_TRY(c, vct_launch_voxelize_reference(p, v.ref_big.get() + 1, v.ref_big.get(), cur(c).stream));
     } else {
-        if (p.tex.texels && c->n_frags) {
+        if (p.tex.texels && v.n_frags) {
             // every fragment's albedo (texture fetch or material colour): independent of the light, so evaluated once per
             // change of the textures / texture coordinates, not once per pass
-            if (!c->frag_alb) { HIP_TRY(c, hipMalloc(&c->frag_alb, (size_t)c->n_frags * 3 * sizeof(float))); c->frag_alb_dirty = true; }
-            if (c->frag_alb_dirty) {
-                HIP_TRY(c, vct_launch_frag_geom(p, nullptr, c->frag_alb, cur(c).stream));
-                c->frag_alb_dirty = false;
+            HIP_TRY(c, v.frag_alb.reserve((size_t)v.n_frags * 3, &v.frag_alb_dirty));
+            if (v.frag_alb_dirty) {
+                HIP_TRY(c, vct_launch_frag_geom(p, nullptr, v.frag_alb.get(), cur(c).stream));
+                v.frag_alb_dirty = false;
             }
-            p.frag_alb = c->frag_alb;
+            p.frag_alb = v.frag_alb.get();
         }
         HIP_TRY(c, vct_launch_voxelize(p, cur(c).stream));      // one workgroup per brick: LDS accumulation + resolve into the staging pool
     }
-    c->acc_pending = true;
+    v.acc_pending = true;
     c->acc_mode = mode;
     return VCT_OK;
 }
 
 int vct_inject_light(vct_ctx* c) {
     if (!c) return VCT_ERR_INVALID;
-    if (!c->acc_pending) return fail(c, VCT_ERR_INVALID, "vct_inject_light: call vct_voxelize first");
+    if (!c->vox.acc_pending) return fail(c, VCT_ERR_INVALID, "vct_inject_light: call vct_voxelize first");
     HIP_TRY(c, hipSetDevice(c->device));
     PIPE_TRY(pipeline_join(c));       // level 0 is rewritten: the other slot's trace may still read the chain
-    HIP_TRY(c, vct_launch_resolve(c->acc, c->brick_slot, c->chain, c->brick_flags, c->brick_prev, c->cfg.voxel_dim,
-                                  c->level0_dirty, nullptr, c->attr_albedo, c->attr_normal,
-                                  c->acc_mode == VCT_VOX_REFERENCE, c->stage, c->stage_albedo, c->stage_normal, cur(c).stream));
-    c->acc_pending = false;
+    const VctVoxelPlan& v = c->vox;
+    HIP_TRY(c, vct_launch_resolve(v.acc.get(), v.brick_slot.get(), c->chain.get(), c->brick_flags.get(), c->brick_prev.get(),
+                                  c->cfg.voxel_dim, c->level0_dirty, nullptr, v.attr_albedo.get(), v.attr_normal.get(),
+                                  c->acc_mode == VCT_VOX_REFERENCE, v.stage.get(), v.stage_albedo.get(), v.stage_normal.get(),
+                                  cur(c).stream));
+    c->vox.acc_pending = false;
     c->level0_dirty = false;
     c->use_chain_b = false;
     c->mips_valid = false;
-    c->attrs_valid = c->attr_normal != nullptr && c->acc_mode == VCT_VOX_CONSERVATIVE_AVG;
+    c->vox.attrs_valid = c->vox.attr_normal && c->acc_mode == VCT_VOX_CONSERVATIVE_AVG;
     return VCT_OK;
 }
 
@@ -1538,10 +1426,10 @@ static int build_cells(vct_ctx* c) {
     if (!c->want_cells || c->nlev < 2) return VCT_OK;
     const size_t V3 = (size_t)c->cfg.voxel_dim * c->cfg.voxel_dim * c->cfg.voxel_dim;
     if (!c->cells) {
-        const hipError_t e = hipMalloc(&c->cells, (c->chain_texels - V3) * 32);
-        if (e != hipSuccess) { c->cells = nullptr; return fail(c, VCT_ERR_NOMEM, std::string("footprint records: ") + hipGetErrorString(e)); }
+        const hipError_t e = c->cells.alloc((c->chain_texels - V3) * 2);
+        if (e != hipSuccess) { return fail(c, VCT_ERR_NOMEM, std::string("footprint records: ") + hipGetErrorString(e)); }
     }
-    HIP_TRY(c, vct_launch_build_cells(c->chain, c->cells, c->cfg.voxel_dim, cur(c).stream));
+    HIP_TRY(c, vct_launch_build_cells(c->chain.get(), c->cells.get(), c->cfg.voxel_dim, cur(c).stream));
     c->cells_valid = true;
     return VCT_OK;
 }
@@ -1555,8 +1443,7 @@ int vct_set_footprint_records(vct_ctx* c, int32_t on) {
         c->cells_valid = false;
         if (c->cells) {
             HIP_TRY(c, hipStreamSynchronize(cur(c).stream));      // a trace in flight may still read them
-            (void)hipFree(c->cells);
-            c->cells = nullptr;
+            c->cells.reset();
         }
         return VCT_OK;
     }
@@ -1574,13 +1461,13 @@ int vct_build_mips(vct_ctx* c) {
     const bool tracked = c->brick_prev && c->mip_seen && !c->level0_dirty;
     const bool sparse = tracked && c->chain_sparse_ready;
     if (!sparse && c->mip_seen && c->brick_prev)      // dense build: afterwards every brick is "seen" as it is now
-        HIP_TRY(c, hipMemcpyAsync(c->mip_seen, c->brick_prev,
+        HIP_TRY(c, hipMemcpyAsync(c->mip_seen.get(), c->brick_prev.get(),
                                   ((size_t)c->cfg.voxel_dim * c->cfg.voxel_dim * c->cfg.voxel_dim / 512) * sizeof(uint32_t),
                                   hipMemcpyDeviceToDevice, cur(c).stream));
-    HIP_TRY(c, vct_launch_build_mips(c->chain, c->cfg.voxel_dim, sparse ? c->brick_prev : nullptr,
-                                     sparse ? c->mip_seen : nullptr, cur(c).stream));
+    HIP_TRY(c, vct_launch_build_mips(c->chain.get(), c->cfg.voxel_dim, sparse ? c->brick_prev.get() : nullptr,
+                                     sparse ? c->mip_seen.get() : nullptr, cur(c).stream));
     if (!sparse) c->chain_sparse_ready = tracked;
-    if (c->aniso) HIP_TRY(c, vct_launch_build_mips_aniso(c->chain, c->aniso, c->cfg.voxel_dim, cur(c).stream));
+    if (c->aniso) HIP_TRY(c, vct_launch_build_mips_aniso(c->chain.get(), c->aniso.get(), c->cfg.voxel_dim, cur(c).stream));
     c->mips_valid = true;
     c->use_chain_b = false;
     return build_cells(c);
@@ -1588,11 +1475,11 @@ int vct_build_mips(vct_ctx* c) {
 
 int vct_bounce(vct_ctx* c) {
     if (!c) return VCT_ERR_INVALID;
-    if (!c->cfg.voxel_attributes || !c->attr_normal)
+    if (!c->cfg.voxel_attributes || !c->vox.attr_normal)
         return fail(c, VCT_ERR_INVALID, "vct_bounce: needs config.voxel_attributes = 1 and a voxelize + inject pass");
-    if (c->acc_pending || !c->mips_valid)
+    if (c->vox.acc_pending || !c->mips_valid)
         return fail(c, VCT_ERR_INVALID, "vct_bounce: call vct_inject_light and vct_build_mips first");
-    if (!c->attrs_valid)      // a new mesh was uploaded since: level 0 / brick_prev describe the OLD mesh, the slots the new one
+    if (!c->vox.attrs_valid)      // a new mesh was uploaded since: level 0 / brick_prev describe the OLD mesh, the slots the new one
         return fail(c, VCT_ERR_INVALID, "vct_bounce: the voxel attributes belong to a mesh uploaded after the last "
                                         "vct_inject_light (voxelize + inject + mips again first)");
     if (c->level0_dirty || c->acc_mode != VCT_VOX_CONSERVATIVE_AVG)
@@ -1603,48 +1490,47 @@ int vct_bounce(vct_ctx* c) {
     if (rc) return rc;
     const size_t nvox = (size_t)c->cfg.voxel_dim * c->cfg.voxel_dim * c->cfg.voxel_dim;
     const size_t nbricks = nvox / 512;
-    bool b_sparse = c->chain_b != nullptr;
+    bool b_sparse = (bool)c->chain_b;
     if (!c->chain_b) {
-        HIP_TRY(c, hipMalloc(&c->chain_b, c->chain_texels * 4));
-        HIP_TRY(c, hipMemsetAsync(c->chain_b, 0, c->chain_texels * 4, cur(c).stream));
-        HIP_TRY(c, hipMalloc(&c->mip_seen_b, nbricks * sizeof(uint32_t)));
-        HIP_TRY(c, hipMemsetAsync(c->mip_seen_b, 0, nbricks * sizeof(uint32_t), cur(c).stream));
+        HIP_TRY(c, c->chain_b.alloc(c->chain_texels));
+        HIP_TRY(c, hipMemsetAsync(c->chain_b.get(), 0, c->chain_texels * 4, cur(c).stream));
+        HIP_TRY(c, c->mip_seen_b.alloc(nbricks));
+        HIP_TRY(c, hipMemsetAsync(c->mip_seen_b.get(), 0, nbricks * sizeof(uint32_t), cur(c).stream));
         b_sparse = true;     // zero-filled chain + empty "seen" set: the sparse form is valid from the start
         // occupied-voxel list: surfaces occupy ~1 % of a grid; V^3/8 entries is a generous bound and
         // bricks that do not fit are handled by the per-brick kernel
-        c->bounce_list_cap = (uint32_t)(nvox / 8);
-        HIP_TRY(c, hipMalloc(&c->bounce_list, ((size_t)c->bounce_list_cap + 1) * sizeof(uint32_t)));
-        HIP_TRY(c, hipMalloc(&c->brick_over, nbricks * sizeof(uint32_t)));
-        HIP_TRY(c, hipMemsetAsync(c->brick_over, 0, nbricks * sizeof(uint32_t), cur(c).stream));   // k_bounce_bricks resets what it serves
+        HIP_TRY(c, c->bounce_list.alloc(nvox / 8 + 1));      // (+ the counter word in front)
+        HIP_TRY(c, c->brick_over.alloc(nbricks));
+        HIP_TRY(c, hipMemsetAsync(c->brick_over.get(), 0, nbricks * sizeof(uint32_t), cur(c).stream));   // k_bounce_bricks resets what it serves
     }
     // only the counter: the list itself needs no clear (the one brick that can straddle its end marks its tail empty)
-    HIP_TRY(c, hipMemsetAsync(c->bounce_list, 0, sizeof(uint32_t), cur(c).stream));
+    HIP_TRY(c, hipMemsetAsync(c->bounce_list.get(), 0, sizeof(uint32_t), cur(c).stream));
     VctTraceParams p;
-    fill_march_params(c, p, c->chain);
-    p.attr_albedo = c->attr_albedo;
-    p.attr_normal = c->attr_normal;
-    p.brick_slot = c->brick_slot;
-    p.brick_prev = c->brick_prev;
-    p.bounce_seen = c->mip_seen_b;
-    p.bounce_out = c->chain_b;
+    fill_march_params(c, p, c->chain.get());
+    p.attr_albedo = c->vox.attr_albedo.get();
+    p.attr_normal = c->vox.attr_normal.get();
+    p.brick_slot = c->vox.brick_slot.get();
+    p.brick_prev = c->brick_prev.get();
+    p.bounce_seen = c->mip_seen_b.get();
+    p.bounce_out = c->chain_b.get();
     p.nbricks = (uint32_t)(nvox / 512);
-    p.slot_brick = c->slot_brick;
-    p.nslots = c->nslots;
-    p.bounce_list_count = c->bounce_list;
-    p.bounce_list = c->bounce_list + 1;
-    p.bounce_list_cap = c->bounce_list_cap;
-    p.brick_over = c->brick_over;
-    HIP_TRY(c, hipMemsetAsync(c->step_counter, 0, VCT_STEP_COUNTERS * sizeof(unsigned long long), cur(c).stream));
+    p.slot_brick = c->vox.slot_brick.get();
+    p.nslots = c->vox.nslots;
+    p.bounce_list_count = c->bounce_list.get();
+    p.bounce_list = c->bounce_list.get() + 1;
+    p.bounce_list_cap = (uint32_t)(c->bounce_list.size() - 1);
+    p.brick_over = c->brick_over.get();
+    HIP_TRY(c, hipMemsetAsync(c->step_counter.get(), 0, VCT_STEP_COUNTERS * sizeof(unsigned long long), cur(c).stream));
     if (c->time_traces) HIP_TRY(c, hipEventRecord(cur(c).ev0, cur(c).stream));
     HIP_TRY(c, vct_launch_bounce(p, cur(c).stream));
     if (c->time_traces) HIP_TRY(c, hipEventRecord(cur(c).ev1, cur(c).stream));
     cur(c).last_trace_timed = c->time_traces;
     c->last_march_form = c->fast_div ? 2 : 1;
-    HIP_TRY(c, vct_launch_build_mips(c->chain_b, c->cfg.voxel_dim, b_sparse ? c->brick_prev : nullptr,
-                                     b_sparse ? c->mip_seen_b : nullptr, cur(c).stream));
+    HIP_TRY(c, vct_launch_build_mips(c->chain_b.get(), c->cfg.voxel_dim, b_sparse ? c->brick_prev.get() : nullptr,
+                                     b_sparse ? c->mip_seen_b.get() : nullptr, cur(c).stream));
     // the directional chains always describe the chain the trace reads (the bounce itself gathers
     // from the isotropic bounce-0 chain, like the oracle's vcto_bounce)
-    if (c->aniso) HIP_TRY(c, vct_launch_build_mips_aniso(c->chain_b, c->aniso, c->cfg.voxel_dim, cur(c).stream));
+    if (c->aniso) HIP_TRY(c, vct_launch_build_mips_aniso(c->chain_b.get(), c->aniso.get(), c->cfg.voxel_dim, cur(c).stream));
     c->use_chain_b = true;
     cur(c).have_trace = true;      // step counter / event pair now describe the bounce launch
     cur(c).last_was_screen_trace = false;
@@ -1653,35 +1539,28 @@ int vct_bounce(vct_ctx* c) {
 
 int vct_download_voxel_attributes(vct_ctx* c, uint8_t* albedo, uint8_t* normal) {
     if (!c || !albedo || !normal) return VCT_ERR_INVALID;
-    if (!c->attr_albedo) return fail(c, VCT_ERR_INVALID, "no voxel attributes (config.voxel_attributes, vct_voxelize + vct_inject_light)");
+    if (!c->vox.attr_albedo) return fail(c, VCT_ERR_INVALID, "no voxel attributes (config.voxel_attributes, vct_voxelize + vct_inject_light)");
     HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->staging) {
-        const size_t n = (size_t)c->cfg.voxel_dim * c->cfg.voxel_dim * c->cfg.voxel_dim;
-        HIP_TRY(c, hipMalloc(&c->staging, n * 4));
-    }
     const int V = c->cfg.voxel_dim;
     const size_t n = (size_t)V * V * V;
-    const uint32_t* src[2] = {c->attr_albedo, c->attr_normal};
+    HIP_TRY(c, c->staging.reserve(n));
+    const uint32_t* src[2] = {c->vox.attr_albedo.get(), c->vox.attr_normal.get()};
     uint8_t* dst[2] = {albedo, normal};
-    uint32_t* dense = nullptr;          // pooled [slot][512] -> dense Morton volume -> linear staging
-    HIP_TRY(c, hipMalloc(&dense, n * 4));
+    VctBuf<uint32_t> dense;             // pooled [slot][512] -> dense Morton volume -> linear staging
+    HIP_TRY(c, dense.alloc(n));
     for (int k = 0; k < 2; ++k) {
-        hipError_t e = vct_launch_unpool(src[k], c->brick_slot, dense, (uint32_t)(n / 512), cur(c).stream);
-        if (e == hipSuccess) e = vct_launch_morton_to_linear(dense, c->staging, V, cur(c).stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(dst[k], c->staging, n * 4, hipMemcpyDeviceToHost, cur(c).stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(cur(c).stream);
-        if (e != hipSuccess) { (void)hipFree(dense); HIP_TRY(c, e); }
+        HIP_TRY(c, vct_launch_unpool(src[k], c->vox.brick_slot.get(), dense.get(), (uint32_t)(n / 512), cur(c).stream));
+        HIP_TRY(c, vct_launch_morton_to_linear(dense.get(), c->staging.get(), V, cur(c).stream));
+        HIP_TRY(c, hipMemcpyAsync(dst[k], c->staging.get(), n * 4, hipMemcpyDeviceToHost, cur(c).stream));
+        HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     }
-    (void)hipFree(dense);
     return VCT_OK;
 }
 
 // ---- volume up/download -----------------------------------------------------------------
 
 static int ensure_staging(vct_ctx* c) {
-    if (c->staging) return VCT_OK;
-    const size_t n = (size_t)c->cfg.voxel_dim * c->cfg.voxel_dim * c->cfg.voxel_dim;
-    HIP_TRY(c, hipMalloc(&c->staging, n * 4));
+    HIP_TRY(c, c->staging.reserve((size_t)c->cfg.voxel_dim * c->cfg.voxel_dim * c->cfg.voxel_dim));
     return VCT_OK;
 }
 
@@ -1699,8 +1578,8 @@ static int upload_levels(vct_ctx* c, const uint8_t* lin, int nlevels) {
     for (int l = 0; l < nlevels; ++l) {
         const int N = V >> l;
         const size_t off = (size_t)vct_level_offset(V, l), n = (size_t)N * N * N;
-        HIP_TRY(c, hipMemcpyAsync(c->staging, lin + off * 4, n * 4, hipMemcpyHostToDevice, cur(c).stream));
-        HIP_TRY(c, vct_launch_linear_to_morton(c->staging, c->chain + off, N, cur(c).stream));
+        HIP_TRY(c, hipMemcpyAsync(c->staging.get(), lin + off * 4, n * 4, hipMemcpyHostToDevice, cur(c).stream));
+        HIP_TRY(c, vct_launch_linear_to_morton(c->staging.get(), c->chain.get() + off, N, cur(c).stream));
         HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     }
     return VCT_OK;
@@ -1717,7 +1596,7 @@ int vct_upload_chain_rgba8(vct_ctx* c, const uint8_t* chain) {
     if (!chain) return fail(c, VCT_ERR_INVALID, "vct_upload_chain_rgba8: null chain");
     int rc = upload_levels(c, chain, c->nlev);
     if (rc) return rc;
-    if (c->aniso) HIP_TRY(c, vct_launch_build_mips_aniso(c->chain, c->aniso, c->cfg.voxel_dim, cur(c).stream));
+    if (c->aniso) HIP_TRY(c, vct_launch_build_mips_aniso(c->chain.get(), c->aniso.get(), c->cfg.voxel_dim, cur(c).stream));
     return build_cells(c);
 }
 
@@ -1733,8 +1612,8 @@ int vct_download_aniso_rgba8(vct_ctx* c, uint8_t* out) {
         for (int l = 1; l < c->nlev; ++l) {
             const int N = V >> l;
             const size_t off = (size_t)vct_level_offset(V, l) - V3, n = (size_t)N * N * N;
-            HIP_TRY(c, vct_launch_morton_to_linear(c->aniso + d * stride + off, c->staging, N, cur(c).stream));
-            HIP_TRY(c, hipMemcpyAsync(out + (d * stride + off) * 4, c->staging, n * 4, hipMemcpyDeviceToHost, cur(c).stream));
+            HIP_TRY(c, vct_launch_morton_to_linear(c->aniso.get() + d * stride + off, c->staging.get(), N, cur(c).stream));
+            HIP_TRY(c, hipMemcpyAsync(out + (d * stride + off) * 4, c->staging.get(), n * 4, hipMemcpyDeviceToHost, cur(c).stream));
             HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
         }
     return VCT_OK;
@@ -1750,9 +1629,9 @@ int vct_download_chain_rgba8(vct_ctx* c, uint8_t* chain) {
     for (int l = 0; l < c->nlev; ++l) {
         const int N = V >> l;
         const size_t off = (size_t)vct_level_offset(V, l), n = (size_t)N * N * N;
-        const uint32_t* active = c->use_chain_b ? c->chain_b : c->chain;
-        HIP_TRY(c, vct_launch_morton_to_linear(active + off, c->staging, N, cur(c).stream));
-        HIP_TRY(c, hipMemcpyAsync(chain + off * 4, c->staging, n * 4, hipMemcpyDeviceToHost, cur(c).stream));
+        const uint32_t* active = c->use_chain_b ? c->chain_b.get() : c->chain.get();
+        HIP_TRY(c, vct_launch_morton_to_linear(active + off, c->staging.get(), N, cur(c).stream));
+        HIP_TRY(c, hipMemcpyAsync(chain + off * 4, c->staging.get(), n * 4, hipMemcpyDeviceToHost, cur(c).stream));
         HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     }
     return VCT_OK;
@@ -1769,22 +1648,22 @@ static int bind_gbuffer(vct_ctx* c, const vct_gbuffer* gb) {
         if (gb->location == VCT_MEM_DEVICE) {
             cur(c).gb_current = gb->planes;     // zero-copy: trace reads the caller's HBM buffer
         } else {
-            HIP_TRY(c, hipMemcpyAsync(cur(c).gb_tiled, gb->planes, gb_tiled_floats(c) * sizeof(float),
+            HIP_TRY(c, hipMemcpyAsync(cur(c).gb_tiled.get(), gb->planes, gb_tiled_floats(c) * sizeof(float),
                                       hipMemcpyHostToDevice, cur(c).stream));
-            cur(c).gb_current = cur(c).gb_tiled;
+            cur(c).gb_current = cur(c).gb_tiled.get();
         }
         return VCT_OK;
     }
     if (gb->layout != VCT_GB_LINEAR) return fail(c, VCT_ERR_INVALID, "vct_trace: unknown G-buffer layout");
     const float* src = gb->planes;
     if (gb->location == VCT_MEM_HOST) {
-        if (!c->gb_linear) HIP_TRY(c, hipMalloc(&c->gb_linear, npix * VCT_GB_NPLANES * sizeof(float)));
-        HIP_TRY(c, hipMemcpyAsync(c->gb_linear, gb->planes, npix * VCT_GB_NPLANES * sizeof(float),
+        HIP_TRY(c, c->gb_linear.reserve(npix * VCT_GB_NPLANES));
+        HIP_TRY(c, hipMemcpyAsync(c->gb_linear.get(), gb->planes, npix * VCT_GB_NPLANES * sizeof(float),
                                   hipMemcpyHostToDevice, cur(c).stream));
-        src = c->gb_linear;
+        src = c->gb_linear.get();
     }
-    HIP_TRY(c, vct_launch_tile_gbuffer(src, cur(c).gb_tiled, c->cfg.width, c->cfg.height, cur(c).stream));
-    cur(c).gb_current = cur(c).gb_tiled;
+    HIP_TRY(c, vct_launch_tile_gbuffer(src, cur(c).gb_tiled.get(), c->cfg.width, c->cfg.height, cur(c).stream));
+    cur(c).gb_current = cur(c).gb_tiled.get();
     return VCT_OK;
 }
 
@@ -1804,7 +1683,7 @@ int vct_trace_slab(vct_ctx* c, const vct_gbuffer* gb, int32_t row0, int32_t row1
         const int y1 = row1 * VCT_TILE < c->cfg.height ? row1 * VCT_TILE : c->cfg.height;
         if (y1 > y0) {
             const size_t off = (size_t)y0 * c->cfg.width * 8, bytes = (size_t)(y1 - y0) * c->cfg.width * 8;
-            const char* src = (const char*)(cur(c).frame_target ? cur(c).frame_target : cur(c).frame);
+            const char* src = (const char*)(cur(c).frame_target ? cur(c).frame_target : cur(c).frame.get());
             HIP_TRY(c, hipMemcpyAsync((char*)out + off, src + off, bytes,
                                       out_location == VCT_MEM_DEVICE ? hipMemcpyDeviceToDevice
                                                                      : hipMemcpyDeviceToHost,
@@ -1827,7 +1706,7 @@ int vct_trace_current(vct_ctx* c, void* out, int32_t out_location) {
     int rc = launch_trace(c, 0, tiles_y(c));
     if (rc) return rc;
     if (out) {
-        const char* src = (const char*)(cur(c).frame_target ? cur(c).frame_target : cur(c).frame);
+        const char* src = (const char*)(cur(c).frame_target ? cur(c).frame_target : cur(c).frame.get());
         HIP_TRY(c, hipMemcpyAsync(out, src, (size_t)c->cfg.width * c->cfg.height * 8,
                                   out_location == VCT_MEM_DEVICE ? hipMemcpyDeviceToDevice
                                                                  : hipMemcpyDeviceToHost, cur(c).stream));
@@ -1921,7 +1800,7 @@ int vct_gi_pass(vct_ctx* c, const float light_vp[16], const float view_proj[16],
 int vct_download_frame(vct_ctx* c, void* out) {
     if (!c || !out) return VCT_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
-    const char* src = (const char*)(cur(c).frame_target ? cur(c).frame_target : cur(c).frame);
+    const char* src = (const char*)(cur(c).frame_target ? cur(c).frame_target : cur(c).frame.get());
     HIP_TRY(c, hipMemcpyAsync(out, src, (size_t)c->cfg.width * c->cfg.height * 8, hipMemcpyDeviceToHost, cur(c).stream));
     HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     return VCT_OK;
@@ -2012,7 +1891,7 @@ int vct_download_steps(vct_ctx* c, uint8_t* steps) {
     if (!c || !steps) return VCT_ERR_INVALID;
     if (!c->dbg_steps) return fail(c, VCT_ERR_INVALID, "context created without debug_outputs");
     HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
-    HIP_TRY(c, hipMemcpy(steps, c->dbg_steps, (size_t)c->cfg.width * c->cfg.height * 7,
+    HIP_TRY(c, hipMemcpy(steps, c->dbg_steps.get(), (size_t)c->cfg.width * c->cfg.height * 7,
                          hipMemcpyDeviceToHost));
     return VCT_OK;
 }
@@ -2021,7 +1900,7 @@ int vct_download_cones(vct_ctx* c, float* cones) {
     if (!c || !cones) return VCT_ERR_INVALID;
     if (!c->dbg_cones) return fail(c, VCT_ERR_INVALID, "context created without debug_outputs");
     HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
-    HIP_TRY(c, hipMemcpy(cones, c->dbg_cones, (size_t)c->cfg.width * c->cfg.height * 28 * sizeof(float),
+    HIP_TRY(c, hipMemcpy(cones, c->dbg_cones.get(), (size_t)c->cfg.width * c->cfg.height * 28 * sizeof(float),
                          hipMemcpyDeviceToHost));
     return VCT_OK;
 }
@@ -2035,7 +1914,7 @@ static int row_steps(vct_ctx* c, std::vector<uint64_t>& rows) {
     const size_t per_row = (size_t)tx;
     std::vector<uint32_t> v(per_row * (size_t)(r1 - r0));
     HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
-    HIP_TRY(c, hipMemcpy(v.data(), cur(c).tile_steps + per_row * (size_t)r0, v.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(v.data(), cur(c).tile_steps.get() + per_row * (size_t)r0, v.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (int r = r0; r < r1; ++r) {
         if ((r - r0) % cur(c).last_row_stride) continue;          // an interleaved launch: the other rows belong to other ranks
         uint64_t sum = 0;
@@ -2059,7 +1938,7 @@ int vct_last_step_count(vct_ctx* c, uint64_t* steps) {
     } else {        // a bounce: its kernels add into the atomic bank
         HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
         unsigned long long v[VCT_STEP_COUNTERS];
-        HIP_TRY(c, hipMemcpy(v, c->step_counter, sizeof(v), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(v, c->step_counter.get(), sizeof(v), hipMemcpyDeviceToHost));
         for (int i = 0; i < VCT_STEP_COUNTERS; ++i) sum += v[i];
     }
     *steps = sum;
@@ -2069,19 +1948,19 @@ int vct_last_step_count(vct_ctx* c, uint64_t* steps) {
 int vct_get_stage_counts(vct_ctx* c, uint64_t out[8]) {
     if (!c || !out) return VCT_ERR_INVALID;
     memset(out, 0, 8 * sizeof(uint64_t));
-    out[0] = (uint64_t)c->ntri;
-    out[1] = c->n_frags;
+    out[0] = (uint64_t)c->mesh.ntri;
+    out[1] = c->vox.n_frags;
     out[2] = (uint64_t)c->last_march_form;       // division form of the last march launch: 0 none, 1 IEEE, 2 product, 3 x * r
-    out[3] = c->nslots;
+    out[3] = c->vox.nslots;
     out[5] = (uint64_t)c->reserved_cus;          // compute units kept for the communication stream (VCT_COMM_RESERVED_CUS)
     out[6] = (uint64_t)c->last_raster_form;      // visibility form of the last main-draw pass: 1 direct, 2 tile-binned
-    out[7] = (uint64_t)c->n_vox_items;           // work items of the voxelize pass (slots, heavy ones cut into chunks)
+    out[7] = (uint64_t)c->vox.n_items;           // work items of the voxelize pass (slots, heavy ones cut into chunks)
     if (c->brick_prev) {
         HIP_TRY(c, hipSetDevice(c->device));
         const size_t nbricks = (size_t)c->cfg.voxel_dim * c->cfg.voxel_dim * c->cfg.voxel_dim / 512;
         std::vector<uint32_t> flags(nbricks);
         HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
-        HIP_TRY(c, hipMemcpy(flags.data(), c->brick_prev, nbricks * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(flags.data(), c->brick_prev.get(), nbricks * sizeof(uint32_t), hipMemcpyDeviceToHost));
         uint64_t n = 0;
         for (uint32_t f : flags) n += f != 0u;
         out[4] = n;
@@ -2110,7 +1989,7 @@ int vct_last_trace_stats(vct_ctx* c, uint64_t out[16]) {
 #if defined(VCT_STATS) && VCT_STATS
     if (!cur(c).have_trace) return fail(c, VCT_ERR_INVALID, "no trace has run");
     HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
-    HIP_TRY(c, hipMemcpy(out, c->stats, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(out, c->stats.get(), 16 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return VCT_OK;
 #else
     return fail(c, VCT_ERR_INVALID, "vct_last_trace_stats: this library was built without -DVCT_STATS=1 "
@@ -2139,10 +2018,10 @@ int vct_selftest_const_divide(vct_ctx* c, float d, uint64_t* mismatches) {
     if (!divisor_ok(d)) return fail(c, VCT_ERR_INVALID, "divisor outside the set the FMA division is proven for");
     HIP_TRY(c, hipSetDevice(c->device));
     // scratch = the statistics words (never the step-counter bank: vct_last_step_count sums that)
-    HIP_TRY(c, hipMemsetAsync(c->stats, 0, 2 * sizeof(unsigned long long), cur(c).stream));
-    HIP_TRY(c, vct_launch_divide_selftest(d, c->stats, cur(c).stream));
+    HIP_TRY(c, hipMemsetAsync(c->stats.get(), 0, 2 * sizeof(unsigned long long), cur(c).stream));
+    HIP_TRY(c, vct_launch_divide_selftest(d, c->stats.get(), cur(c).stream));
     unsigned long long v[2] = {0, 0};
-    HIP_TRY(c, hipMemcpyAsync(v, c->stats, sizeof(v), hipMemcpyDeviceToHost, cur(c).stream));
+    HIP_TRY(c, hipMemcpyAsync(v, c->stats.get(), sizeof(v), hipMemcpyDeviceToHost, cur(c).stream));
     HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     *mismatches = v[0];
     if (v[0]) {      // not a failure of the call: leave one offending x readable for diagnosis
@@ -2166,16 +2045,14 @@ int vct_selftest_texel_buffer(vct_ctx* c, uint64_t* mismatches) {
         const uint32_t ch[4] = {o0, o1, o2, b};
         h[i] = ch[(0 + 3 - k) & 3] | (ch[(1 + 3 - k) & 3] << 8) | (ch[(2 + 3 - k) & 3] << 16) | (ch[(3 + 3 - k) & 3] << 24);
     }
-    uint32_t* d = nullptr;
-    HIP_TRY(c, hipMalloc(&d, h.size() * sizeof(uint32_t)));
-    hipError_t e = hipMemcpyAsync(d, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice, cur(c).stream);
-    if (e == hipSuccess) e = hipMemsetAsync(c->stats, 0, 2 * sizeof(unsigned long long), cur(c).stream);
-    if (e == hipSuccess) e = vct_launch_texel_buffer_selftest(d, (uint32_t)h.size(), c->stats, cur(c).stream);
+    VctBuf<uint32_t> d;
+    HIP_TRY(c, d.alloc(h.size()));
+    HIP_TRY(c, hipMemcpyAsync(d.get(), h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice, cur(c).stream));
+    HIP_TRY(c, hipMemsetAsync(c->stats.get(), 0, 2 * sizeof(unsigned long long), cur(c).stream));
+    HIP_TRY(c, vct_launch_texel_buffer_selftest(d.get(), (uint32_t)h.size(), c->stats.get(), cur(c).stream));
     unsigned long long v[2] = {0, 0};
-    if (e == hipSuccess) e = hipMemcpyAsync(v, c->stats, sizeof(v), hipMemcpyDeviceToHost, cur(c).stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(cur(c).stream);
-    (void)hipFree(d);
-    HIP_TRY(c, e);
+    HIP_TRY(c, hipMemcpyAsync(v, c->stats.get(), sizeof(v), hipMemcpyDeviceToHost, cur(c).stream));
+    HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     *mismatches = v[0];
     if (v[0]) {
         char msg[128];
@@ -2188,10 +2065,10 @@ int vct_selftest_texel_buffer(vct_ctx* c, uint64_t* mismatches) {
 int vct_selftest_area_divide(vct_ctx* c, uint64_t seed, uint64_t count, uint64_t* mismatches) {
     if (!c || !mismatches) return VCT_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemsetAsync(c->stats, 0, 2 * sizeof(unsigned long long), cur(c).stream));
-    HIP_TRY(c, vct_launch_area_divide_selftest(seed, count, c->stats, cur(c).stream));
+    HIP_TRY(c, hipMemsetAsync(c->stats.get(), 0, 2 * sizeof(unsigned long long), cur(c).stream));
+    HIP_TRY(c, vct_launch_area_divide_selftest(seed, count, c->stats.get(), cur(c).stream));
     unsigned long long v[2] = {0, 0};
-    HIP_TRY(c, hipMemcpyAsync(v, c->stats, sizeof(v), hipMemcpyDeviceToHost, cur(c).stream));
+    HIP_TRY(c, hipMemcpyAsync(v, c->stats.get(), sizeof(v), hipMemcpyDeviceToHost, cur(c).stream));
     HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
     *mismatches = v[0];
     if (v[0]) {
@@ -2238,20 +2115,15 @@ int vct_set_aov_outputs(vct_ctx* c, uint32_t which) {
     PIPE_TRY(vct_synchronize(c));            // the buffers being replaced may still be written
     // every live slot's set, allocated here and never in a launch
     const size_t bytes = aov_frames(which) * (size_t)c->cfg.width * c->cfg.height * 8;
-    uint16_t* fresh[2] = {nullptr, nullptr};
+    VctBuf<uint16_t> fresh[2];
     hipError_t e = hipSuccess;
     for (int k = 0; k < c->frames_in_flight && bytes && e == hipSuccess; ++k) {
-        e = hipMalloc(&fresh[k], bytes);
-        if (e == hipSuccess) e = hipMemset(fresh[k], 0, bytes);
+        e = fresh[k].alloc(bytes / 2);
+        if (e == hipSuccess) e = hipMemset(fresh[k].get(), 0, bytes);
     }
-    if (e != hipSuccess) {          // all or nothing: the old sets stay
-        for (uint16_t* b : fresh) if (b) (void)hipFree(b);
+    if (e != hipSuccess)            // all or nothing: the old sets stay
         return fail(c, e == hipErrorOutOfMemory ? VCT_ERR_NOMEM : VCT_ERR_DEVICE, std::string("vct_set_aov_outputs: ") + hipGetErrorString(e));
-    }
-    for (int k = 0; k < c->frames_in_flight; ++k) {
-        if (c->slots[k].aov) (void)hipFree(c->slots[k].aov);
-        c->slots[k].aov = fresh[k];
-    }
+    for (int k = 0; k < c->frames_in_flight; ++k) c->slots[k].aov = std::move(fresh[k]);
     c->aov_which = which;
     return VCT_OK;
 }
@@ -2259,7 +2131,7 @@ int vct_set_aov_outputs(vct_ctx* c, uint32_t which) {
 // the output `bit` of the selected slot: device address (null when the bit is not exactly one output that is on)
 static uint16_t* aov_of(const vct_ctx* c, uint32_t bit) {
     if (bit == 0 || (bit & (bit - 1)) || !(c->aov_which & bit) || !cur(c).aov) return nullptr;
-    return cur(c).aov + aov_frames(c->aov_which & (bit - 1)) * (size_t)c->cfg.width * c->cfg.height * 4;
+    return cur(c).aov.get() + aov_frames(c->aov_which & (bit - 1)) * (size_t)c->cfg.width * c->cfg.height * 4;
 }
 
 int vct_download_aov(vct_ctx* c, uint32_t bit, void* out) {
@@ -2283,7 +2155,7 @@ int vct_get_aov_device(vct_ctx* c, uint32_t bit, void** p, size_t* bytes) {
 
 int vct_get_frame_device(vct_ctx* c, void** p, size_t* bytes) {
     if (!c || !p) return VCT_ERR_INVALID;
-    *p = cur(c).frame_target ? cur(c).frame_target : cur(c).frame;
+    *p = cur(c).frame_target ? cur(c).frame_target : cur(c).frame.get();
     if (bytes) *bytes = (size_t)c->cfg.width * c->cfg.height * 8;
     return VCT_OK;
 }

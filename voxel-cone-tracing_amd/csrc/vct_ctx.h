@@ -15,6 +15,46 @@ struct vct_comm;      // multi-GPU state (vct_multi.hip)
 // (k_raster_mid 658 us instead of 60 beside a trace), and RCCL's gather kernel is such a queue.
 hipError_t vct_create_masked_stream(hipStream_t* s, int device, int first_cu, int last_cu);
 
+// Device memory with an owner.  Every buffer of the context is one of these, as a member of the struct whose lifetime
+// it shares, so that dropping the struct (assigning a fresh one, leaving a scope on an error, delete) is what frees it:
+// no list of pointers to keep in step.  size() counts elements.  Kernel parameter structs take get().
+template <class T>
+class VctBuf {
+    T* p_ = nullptr;
+    size_t n_ = 0;
+
+public:
+    VctBuf() = default;
+    VctBuf(const VctBuf&) = delete;
+    VctBuf& operator=(const VctBuf&) = delete;
+    VctBuf(VctBuf&& o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr; o.n_ = 0; }
+    VctBuf& operator=(VctBuf&& o) noexcept {
+        if (this != &o) { reset(); p_ = o.p_; n_ = o.n_; o.p_ = nullptr; o.n_ = 0; }
+        return *this;
+    }
+    ~VctBuf() { reset(); }
+    void reset() {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr;
+        n_ = 0;
+    }
+    hipError_t alloc(size_t n) {      // the old contents go first; a failure leaves the buffer empty
+        reset();
+        const hipError_t e = hipMalloc(&p_, n * sizeof(T));
+        if (e == hipSuccess) n_ = n; else p_ = nullptr;
+        return e;
+    }
+    // grow-only scratch: at least n elements, contents undefined after growing (*grew is set, never cleared)
+    hipError_t reserve(size_t n, bool* grew = nullptr) {
+        if (n <= n_) return hipSuccess;
+        if (grew) *grew = true;
+        return alloc(n);
+    }
+    T* get() const { return p_; }
+    size_t size() const { return n_; }
+    explicit operator bool() const { return p_ != nullptr; }
+};
+
 // Scratch of one kind of raster pass (vct_capi.hip raster_args).  Between passes every visibility word is all-ones and
 // the counter set of the next pass is zero: the kernels re-establish both themselves (vct_raster.hip run_visibility), so
 // a pass launches no memset.  `dirty` (a launch failed, or nothing is initialised yet) makes the next pass clear
@@ -23,25 +63,19 @@ hipError_t vct_create_masked_stream(hipStream_t* s, int device, int first_cu, in
 // shadow-map words and leaves `vis` unused.
 struct VctRasterScratch {
     // direct form
-    int32_t* lists = nullptr;           // [2*ntri] wave list, [2*ntri] group list
-    void* recs = nullptr;               // [2*ntri] 96-byte set-up records handed from k_raster_vis to k_raster_mid
-    uint32_t* counts = nullptr;         // two sets of [tile work items, wave list, group list, pad]
+    VctBuf<int32_t> lists;              // [2*ntri] wave list, [2*ntri] group list
+    VctBuf<char> recs;                  // [2*ntri] 96-byte set-up records handed from k_raster_vis to k_raster_mid
+    VctBuf<uint32_t> counts;            // two sets of [tile work items, wave list, group list, pad]
     int set = 0;                        // the counter set the next pass uses
-    uint2* items = nullptr;
-    uint32_t item_capacity = 0;
+    VctBuf<uint2> items;
     // tile-binned form (vct_raster.hip), see VctRasterArgs
-    void* bin_recs = nullptr;
-    uint32_t bin_rec_cap = 0;
-    uint2* bin_entries = nullptr;
-    uint32_t bin_entry_cap = 0;
-    uint32_t* bin_count = nullptr;      // count + cursor, [2 * bins * VCT_BIN_CSTRIDE]
-    uint32_t bin_bins = 0;
-    uint4* bin_items = nullptr;
-    uint32_t bin_item_cap = 0;
-    uint32_t* bin_huge = nullptr;       // huge list [VCT_BIN_HUGE_CAP] + two counter sets [16] behind it
+    VctBuf<char> bin_recs;              // 160-byte records
+    VctBuf<uint2> bin_entries;          // capacity + the spare entry k_bin_fill's idle lanes write
+    VctBuf<uint32_t> bin_count;         // count + cursor, [2 * bins * VCT_BIN_CSTRIDE]
+    VctBuf<uint4> bin_items;
+    VctBuf<uint32_t> bin_huge;          // huge list [VCT_BIN_HUGE_CAP] + two counter sets [16] behind it
     int bin_set = 0;
-    unsigned long long* vis = nullptr;  // 64-bit visibility words of the main draw
-    size_t vis_words = 0;
+    VctBuf<unsigned long long> vis;     // 64-bit visibility words of the main draw
     bool dirty = true;
 };
 
@@ -58,12 +92,12 @@ struct VctRasterScratch {
 struct VctFrameSlot {
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;  // timing events of the march launches (vct_last_trace_ms)
-    float* gb_tiled = nullptr;          // [tiles][23][64]
-    const float* gb_current = nullptr;  // tiled buffer the next resident trace reads
-    uint16_t* frame = nullptr;          // RGBA16F [h][w][4]
-    uint16_t* frame_target = nullptr;   // caller-owned output (vct_set_frame_target) or null
-    uint32_t* tile_steps = nullptr;     // [tiles] executed steps per 8x8 tile of the screen trace
-    uint16_t* aov = nullptr;            // per-component outputs (vct_set_aov_outputs): popcount(aov_which) frames, bit order
+    VctBuf<float> gb_tiled;             // [tiles][23][64]
+    const float* gb_current = nullptr;  // tiled buffer the next resident trace reads: gb_tiled or the caller's (not owned)
+    VctBuf<uint16_t> frame;             // RGBA16F [h][w][4]
+    uint16_t* frame_target = nullptr;   // caller-owned output (vct_set_frame_target) or null (not owned)
+    VctBuf<uint32_t> tile_steps;        // [tiles] executed steps per 8x8 tile of the screen trace
+    VctBuf<uint16_t> aov;               // per-component outputs (vct_set_aov_outputs): popcount(aov_which) frames, bit order
     int last_row0 = 0, last_row1 = 0;
     int last_row_stride = 1;            // the last screen trace took every last_row_stride-th tile row of [last_row0, last_row1)
     bool have_trace = false;
@@ -74,39 +108,91 @@ struct VctFrameSlot {
     VctRasterScratch raster;            // the main draw's
 };
 
+// The mesh and its texture set (vct_upload_triangles, vct_upload_mesh_attributes / _uvs, vct_upload_textures).
+struct VctMesh {
+    VctBuf<float> tri_pos;
+    VctBuf<int32_t> tri_mat;
+    VctBuf<int32_t> tri_alpha;        // [ntri] alpha-test class per triangle (main draw), rebuilt when the mesh / textures change
+    bool tri_alpha_dirty = true;
+    VctBuf<float> mat_albedo;
+    int32_t ntri = 0, nmat = 0;
+    // raster input stages
+    VctBuf<float> tri_nrm, tri_tan, tri_bit;
+    VctBuf<float> mat_specular;
+    // material textures (vct_upload_textures) + texture coordinates (vct_upload_mesh_uvs)
+    VctBuf<float> tri_uv;
+    VctBuf<uint32_t> tex_texels;
+    VctBuf<VctTexDesc> tex_desc;
+    VctBuf<int32_t> mat_tex;
+    int32_t ntex = 0;
+    bool has_alpha_textures = false;
+};
+
+// Voxelization plan of the current mesh (geometry only; built by vct_upload_triangles): everything indexed by the mesh's
+// triangles or brick slots -- the conservative fragments sorted by brick slot, the staging pool a pass resolves into,
+// the pooled attributes, sparse-resolve state.  A new mesh starts from a fresh plan; a context whose upload failed has
+// an empty one (vct_voxelize refuses).
+struct VctVoxelPlan {
+    VctBuf<unsigned long long> acc;    // reference mode only, allocated on first use: [nslots][512][2] ((triangle + 1) << 32 | rgb)
+    VctBuf<uint32_t> attr_albedo;      // [nslots][512] resolved mean albedo (cfg.voxel_attributes)
+    VctBuf<uint32_t> attr_normal;      // [nslots][512] resolved mean normal (biased)
+    bool attrs_valid = false;          // attr_albedo / attr_normal hold a resolve of THIS mesh's pools (vct_bounce needs it)
+    VctBuf<uint32_t> brick_slot;       // [V^3/512] brick -> slot or VCT_NO_SLOT
+    uint32_t nslots = 0;
+    VctBuf<uint32_t> frag_sorted;      // [n_frags] triangle << 9 | voxel inside the brick
+    VctBuf<float2> frag_bary;          // [n_frags] the fragment's barycentrics (geometry only: once per mesh, k_frag_geom)
+    VctBuf<float> frag_alb;            // [n_frags][3] the fragment's albedo (scenes with textures); built by the first
+    bool frag_alb_dirty = true;        //   voxelize pass after the texture coordinates / textures changed
+    VctBuf<uint32_t> tri_qnrm;         // [ntri][3] quantised face normals (config.voxel_attributes)
+    uint32_t n_frags = 0;
+    VctBuf<uint32_t> slot_first;       // [nslots + 1]
+    VctBuf<uint32_t> slot_brick;       // [nslots]
+    VctBuf<uint4> items;               // [n_items] work items of the voxelize pass (VctVoxParams::items)
+    uint32_t n_items = 0;
+    uint32_t chunk = VCT_VOX_CHUNK;
+    VctBuf<unsigned long long> acc2;   // HBM accumulators of the multi-chunk slots (+ attributes): chunks add, k_vox_resolve_multi resolves and re-zeroes
+    VctBuf<unsigned long long> acc2_attr;
+    VctBuf<uint32_t> multi_slot;       // [n_multi] slot of every multi-chunk slot
+    uint32_t n_multi = 0;
+    VctBuf<uint32_t> stage;            // [nslots][512] RGBA8 of the pending north-star pass
+    VctBuf<uint32_t> stage_albedo;     // [nslots][512] (cfg.voxel_attributes)
+    VctBuf<uint32_t> stage_normal;
+    VctBuf<int32_t> ref_big;           // reference mode: triangles left to the workgroup pass (+ counter)
+    bool acc_pending = false;          // accumulators hold an unresolved voxelize pass
+};
+
+// Every device buffer below is a VctBuf member of the context or of one of its parts (VctMesh, VctVoxelPlan,
+// VctFrameSlot, VctRasterScratch): vct_destroy waits for the streams and deletes the context, the members free the rest.
 struct vct_ctx {
     vct_config cfg;
     int device = 0;
     int reserved_cus = 0;             // VCT_COMM_RESERVED_CUS at vct_create: CUs kept for the communication stream
     std::string err;
 
-    uint32_t* chain = nullptr;        // Morton chain (bounce 0: direct light)
-    uint32_t* chain_b = nullptr;      // second chain (bounce 1), allocated by vct_bounce
+    VctBuf<uint32_t> chain;           // Morton chain (bounce 0: direct light)
+    VctBuf<uint32_t> chain_b;         // second chain (bounce 1), allocated by vct_bounce
     bool use_chain_b = false;         // the trace reads chain_b until the next vct_inject_light
-    uint32_t* attr_albedo = nullptr;  // [V^3] resolved mean albedo, Morton order
-    uint32_t* attr_normal = nullptr;  // [V^3] resolved mean normal (biased), Morton order
     bool mips_valid = true;           // levels >= 1 describe level 0 (a fresh chain is all zero)
     bool want_cells = false;          // vct_set_footprint_records / VCT_FOOTPRINT_RECORDS=1
-    uint4* cells = nullptr;           // footprint records of the levels >= 1 of `chain` (32 B per texel of those levels)
+    VctBuf<uint4> cells;              // footprint records of the levels >= 1 of `chain` (32 B per texel of those levels)
     bool cells_valid = false;         // ... rebuilt by vct_build_mips / vct_upload_chain_rgba8
-    bool attrs_valid = false;         // attr_albedo / attr_normal hold a resolve of the CURRENT mesh's pools (vct_bounce needs it)
-    uint32_t* aniso = nullptr;        // [6][chain_texels - V^3] directional chains (cfg.anisotropic_mips)
+    VctBuf<uint32_t> aniso;           // [6][chain_texels - V^3] directional chains (cfg.anisotropic_mips)
     size_t chain_texels = 0;
-    uint32_t* staging = nullptr;      // linear staging for up/downloads (size of level 0)
+    VctBuf<uint32_t> staging;         // linear staging for up/downloads (size of level 0)
     int nlev = 0;
 
-    float* gb_linear = nullptr;       // [23][w*h] staging
+    VctBuf<float> gb_linear;          // [23][w*h] staging
     // lighting components (vct_set_lighting_components): VCT_SHOW_* mask of the composite; per-component outputs
     // (vct_set_aov_outputs): VCT_AOV_* bits, one buffer per frame slot (VctFrameSlot::aov)
     uint32_t show_mask = VCT_SHOW_ALL;
     uint32_t aov_which = 0;
-    uint8_t* dbg_steps = nullptr;
-    float* dbg_cones = nullptr;
-    unsigned long long* step_counter = nullptr;   // [VCT_STEP_COUNTERS] atomic bank of the bounce kernels (memset before each bounce)
-    unsigned long long* stats = nullptr;      // [8] march statistics of instrumented builds (VCT_STATS)
-    uint32_t* vt_pix = nullptr;       // trace_variant 4: compaction list [tiles][64] + the virtual-tile counter behind it
-    VctStep* steps_dev = nullptr;     // [2][VCT_MAX_STEPS]
-    uint32_t* spread_lut = nullptr;   // [1024] spread3(i) << 2 (vct_trace.hip: dilated anchor coordinates by scalar load)
+    VctBuf<uint8_t> dbg_steps;
+    VctBuf<float> dbg_cones;
+    VctBuf<unsigned long long> step_counter;   // [VCT_STEP_COUNTERS] atomic bank of the bounce kernels (memset before each bounce)
+    VctBuf<unsigned long long> stats;  // [16] march statistics of instrumented builds (VCT_STATS); scratch of the self-tests
+    VctBuf<uint32_t> vt_pix;          // trace_variant 4: compaction list [tiles][64] + the virtual-tile counter behind it
+    VctBuf<VctStep> steps_dev;        // [2][VCT_MAX_STEPS]
+    VctBuf<uint32_t> spread_lut;      // [1024] spread3(i) << 2 (vct_trace.hip: dilated anchor coordinates by scalar load)
     int n_diffuse = 0, n_specular = 0;
     bool steps_dirty = true;
     bool fast_div = false;            // set by refresh_steps: constant divisors admit the FMA division
@@ -119,29 +205,12 @@ struct vct_ctx {
     float cam[3] = {0.0f, 4.0f, 0.0f};        // VCT.h:8
     float light[3] = {0.0f, 1.0f, 0.25f};     // VCT.h:14
 
-    // scene
-    float* tri_pos = nullptr;
-    int32_t* tri_mat = nullptr;
-    int32_t* tri_alpha = nullptr;     // [ntri] alpha-test class per triangle (main draw), rebuilt when the mesh / textures change
-    bool tri_alpha_dirty = true;
-    float* mat_albedo = nullptr;
-    int32_t ntri = 0, nmat = 0;
-    uint32_t* shadow = nullptr;       // shadow-map words (vct_internal.h vct_shadow_depth), shadow_size^2
+    VctMesh mesh;
+    VctBuf<uint32_t> shadow;          // shadow-map words (vct_internal.h vct_shadow_depth), shadow_size^2
     int32_t shadow_size = 0;
     uint32_t shadow_ebase = 0;        // epoch base of the words the map currently shows
-    uint2* shadow_tiles = nullptr;    // decoded (min, max) per dilated 8 x 8 tile of the current map (vct_launch_shadow_minmax)
+    VctBuf<uint2> shadow_tiles;       // decoded (min, max) per dilated 8 x 8 tile of the current map (vct_launch_shadow_minmax)
     uint32_t shadow_passes = 0;       // shadow passes rasterised into this buffer since its last memset
-    // raster input stages
-    float* tri_nrm = nullptr;
-    float* tri_tan = nullptr;
-    float* tri_bit = nullptr;
-    float* mat_specular = nullptr;
-    // material textures (vct_upload_textures) + texture coordinates (vct_upload_mesh_uvs)
-    float* tri_uv = nullptr;
-    uint32_t* tex_texels = nullptr;
-    VctTexDesc* tex_desc = nullptr;
-    int32_t* mat_tex = nullptr;
-    int32_t ntex = 0;
     VctRasterScratch shadow_raster;    // scratch of the shadow pass (the main draw's is per frame slot)
     // Which form the MAIN draw's visibility takes (the shadow pass is opaque and sparse: the direct form won every
     // measurement).  raster_mode 0 = auto: scenes without alpha-tested textures keep the direct form; otherwise the first
@@ -154,47 +223,22 @@ struct vct_ctx {
     int auto_state = 0;                                // position in the sampling sequence (vct_capi.hip kAutoSeq); 6: all sampled
     int auto_choice = -1;                              // -1 undecided, 0 direct, 1 binned
     hipEvent_t ev_auto[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // begin / end of the four timed samples
-    bool has_alpha_textures = false;
     // second stream: vct_gi_pass runs the G-buffer raster beside the voxel stages
     hipStream_t aux_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_shadow = nullptr, ev_join = nullptr;
     float light_vp[16];
-    unsigned long long* acc = nullptr;         // reference mode only, allocated on first use: [nslots][512][2] ((triangle + 1) << 32 | rgb)
-    uint32_t* brick_slot = nullptr;            // [V^3/512] brick -> slot or VCT_NO_SLOT
-    uint32_t nslots = 0;
-    // voxelization plan (geometry only; built by vct_upload_triangles): the mesh's conservative fragments sorted by
-    // brick slot, and the staging pool a pass resolves into; sparse-resolve state
-    uint32_t* frag_sorted = nullptr;   // [n_frags] triangle << 9 | voxel inside the brick
-    float2* frag_bary = nullptr;       // [n_frags] the fragment's barycentrics (geometry only: once per mesh, k_frag_geom)
-    float* frag_alb = nullptr;         // [n_frags][3] the fragment's albedo (scenes with textures); built by the first
-    bool frag_alb_dirty = true;        //   voxelize pass after the texture coordinates / textures changed
-    uint32_t* tri_qnrm = nullptr;      // [ntri][3] quantised face normals (config.voxel_attributes)
-    uint32_t n_frags = 0;
-    uint32_t* slot_first = nullptr;    // [nslots + 1]
-    uint32_t* slot_brick = nullptr;    // [nslots]
-    void* vox_items = nullptr;         // [n_vox_items] uint4 work items of the voxelize pass (VctVoxParams::items)
-    uint32_t n_vox_items = 0;
-    uint32_t vox_chunk = VCT_VOX_CHUNK;
-    unsigned long long* vox_acc2 = nullptr;       // HBM accumulators of the multi-chunk slots (+ attributes): chunks add, k_vox_resolve_multi resolves and re-zeroes
-    unsigned long long* vox_acc2_attr = nullptr;
-    uint32_t* vox_multi_slot = nullptr;          // [n_vox_multi] slot of every multi-chunk slot
-    uint32_t n_vox_multi = 0;
-    uint32_t* stage = nullptr;         // [nslots][512] RGBA8 of the pending north-star pass
-    uint32_t* stage_albedo = nullptr;  // [nslots][512] (cfg.voxel_attributes)
-    uint32_t* stage_normal = nullptr;
-    uint32_t* plan = nullptr;          // [4] device counters used while planning
-    uint32_t* brick_flags = nullptr;   // [V^3/512] touched in the pending pass
-    uint32_t* brick_prev = nullptr;    // [V^3/512] touched in the pass level 0 currently shows
-    uint32_t* mip_seen = nullptr;      // [V^3/512] bricks non-empty when the chain's mips were last built
-    uint32_t* mip_seen_b = nullptr;    // same for the bounce chain
-    uint32_t* bounce_list = nullptr;   // occupied-voxel list of the bounce (+1 counter word in front)
-    uint32_t bounce_list_cap = 0;
-    uint32_t* brick_over = nullptr;
+    VctVoxelPlan vox;
+    VctBuf<uint32_t> plan;             // [4] device counters used while planning
+    // these describe the chain, not the mesh: they survive a mesh change
+    VctBuf<uint32_t> brick_flags;      // [V^3/512] touched in the pending pass
+    VctBuf<uint32_t> brick_prev;       // [V^3/512] touched in the pass level 0 currently shows
+    VctBuf<uint32_t> mip_seen;         // [V^3/512] bricks non-empty when the chain's mips were last built
+    VctBuf<uint32_t> mip_seen_b;       // same for the bounce chain
+    VctBuf<uint32_t> bounce_list;      // counter word + occupied-voxel list of the bounce
+    VctBuf<uint32_t> brick_over;
     bool chain_sparse_ready = true;    // bricks outside mip_seen have all-zero ancestors (true for a fresh, zero-filled
                                        // chain; an upload clears it until a dense mip build over a resolved level 0)
-    bool acc_pending = false;          // accumulators hold an unresolved voxelize pass
-    int acc_mode = 0;                  // vct_voxelize_mode of that pass
-    int32_t* ref_big = nullptr;        // reference mode: triangles left to the workgroup pass (+ counter)
+    int acc_mode = 0;                  // vct_voxelize_mode of the pending (or last resolved) pass
     bool level0_dirty = false;         // level 0 was written by an upload: next resolve is dense
     vct_comm* comm = nullptr;          // multi-GPU slabs + gather (vct_comm_init)
     // frame slots (see VctFrameSlot): slots [0, frames_in_flight) are live, slots[cur_slot] is selected

@@ -790,30 +790,28 @@ int vct_selftest_interleaved(vct_ctx* c, int32_t world, uint64_t* mismatches) {
     const int w = c->cfg.width, h = c->cfg.height, ty = vct_tiles_y(c);
     const int per = (ty + world - 1) / world;
     const size_t slab_pixels = (size_t)per * VCT_TILE * w, npix = (size_t)w * h;
-    uint2 *gathered = nullptr, *il = nullptr, *plain = nullptr;
-    auto done = [&](int rc) { if (gathered) (void)hipFree(gathered); if (il) (void)hipFree(il); if (plain) (void)hipFree(plain); return rc; };
-    if (hipMalloc(&gathered, slab_pixels * world * 8) != hipSuccess || hipMalloc(&il, npix * 8) != hipSuccess ||
-        hipMalloc(&plain, npix * 8) != hipSuccess)
-        return done(vct_fail(c, VCT_ERR_NOMEM, "vct_selftest_interleaved: out of memory"));
-    hipError_t e = hipMemsetAsync(gathered, 0, slab_pixels * world * 8, cur(c).stream);
-    if (e == hipSuccess) e = hipMemsetAsync(plain, 0, npix * 8, cur(c).stream);
-    if (e != hipSuccess) return done(vct_fail(c, VCT_ERR_DEVICE, hipGetErrorString(e)));
+    VctBuf<uint2> gathered, il, plain;
+    if (gathered.alloc(slab_pixels * world) != hipSuccess || il.alloc(npix) != hipSuccess || plain.alloc(npix) != hipSuccess)
+        return vct_fail(c, VCT_ERR_NOMEM, "vct_selftest_interleaved: out of memory");
+    hipError_t e = hipMemsetAsync(gathered.get(), 0, slab_pixels * world * 8, cur(c).stream);
+    if (e == hipSuccess) e = hipMemsetAsync(plain.get(), 0, npix * 8, cur(c).stream);
+    if (e != hipSuccess) return vct_fail(c, VCT_ERR_DEVICE, hipGetErrorString(e));
     for (int r = 0; r < world; ++r) {
-        const int rc = vct_launch_trace_rows(c, r < ty ? r : ty, ty, (uint16_t*)(gathered + slab_pixels * r), world, true);
-        if (rc) return done(rc);
+        const int rc = vct_launch_trace_rows(c, r < ty ? r : ty, ty, (uint16_t*)(gathered.get() + slab_pixels * r), world, true);
+        if (rc) return rc;
     }
-    hipLaunchKernelGGL(k_deinterleave, dim3(2048), dim3(256), 0, cur(c).stream, gathered, il, w, h, world, slab_pixels);
-    int rc = vct_launch_trace_rows(c, 0, ty, (uint16_t*)plain);
-    if (rc) return done(rc);
+    hipLaunchKernelGGL(k_deinterleave, dim3(2048), dim3(256), 0, cur(c).stream, gathered.get(), il.get(), w, h, world, slab_pixels);
+    int rc = vct_launch_trace_rows(c, 0, ty, (uint16_t*)plain.get());
+    if (rc) return rc;
     std::vector<uint2> a(npix), b(npix);
     e = hipStreamSynchronize(cur(c).stream);
-    if (e == hipSuccess) e = hipMemcpy(a.data(), il, npix * 8, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(b.data(), plain, npix * 8, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return done(vct_fail(c, VCT_ERR_DEVICE, hipGetErrorString(e)));
+    if (e == hipSuccess) e = hipMemcpy(a.data(), il.get(), npix * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(b.data(), plain.get(), npix * 8, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return vct_fail(c, VCT_ERR_DEVICE, hipGetErrorString(e));
     uint64_t bad = 0;
     for (size_t i = 0; i < npix; ++i) bad += (a[i].x != b[i].x || a[i].y != b[i].y) ? 1u : 0u;
     *mismatches = bad;
-    return done(VCT_OK);
+    return VCT_OK;
 }
 
 }  // extern "C"

@@ -370,11 +370,11 @@ int launch_trace(vct_ctx* c, int row0, int row1, uint16_t* out_base = nullptr, i
     p.tile_row1 = row1;
     p.row_stride = row_stride;
     p.pack_rows = pack_rows ? 1 : 0;
-    p.ntiles = ((row1 - row0 + (row_stride > 1 ? row_stride : 1) - 1) / (row_stride > 1 ? row_stride : 1)) * tiles_x(c);
-    if ((row_stride > 1 || pack_rows) && (c->cfg.trace_variant == 1 || c->cfg.trace_variant == 2 || c->cfg.trace_variant == 4))
-        return fail(c, VCT_ERR_INVALID, "interleaved tile rows need the default trace kernel (config.trace_variant 0 or 3)");
-    p.spec_prio = ((row1 - row0) / (row_stride > 1 ? row_stride : 1)) * 2 <= tiles_y(c) ? 1 : 0;
     const int variant = c->cfg.trace_variant;
+    if ((row_stride > 1 || pack_rows) && !vct_variant_takes_row_subsets(variant))
+        return fail(c, VCT_ERR_INVALID, "interleaved tile rows need the default trace kernel (config.trace_variant 0 or 3)");
+    const int rstride = row_stride > 1 ? row_stride : 1;
+    p.spec_prio = ((row1 - row0) / rstride) * 2 <= tiles_y(c) ? 1 : 0;
     p.gbuf = cur(c).gb_current;
     p.aniso = c->cfg.anisotropic_mips ? c->aniso.get() : nullptr;
     p.aniso_alt_slab = 128;     // k_trace_tile_split<ANISO>: slabs [level 1][level 2][-axis of 1][-axis of 2]
@@ -402,13 +402,12 @@ int launch_trace(vct_ctx* c, int row0, int row1, uint16_t* out_base = nullptr, i
         HIP_TRY(c, hipMemsetAsync(p.vt_count, 0, sizeof(uint32_t), cur(c).stream));
     }
     if (c->time_traces) HIP_TRY(c, hipEventRecord(cur(c).ev0, cur(c).stream));      // (vct_set_trace_timing)
-    HIP_TRY(c, vct_launch_trace(p, variant, cur(c).stream));       // an empty row range (a rank without rows) launches nothing
+    HIP_TRY(c, vct_launch_trace(p, variant, cur(c).stream, &c->last_march_form));       // an empty row range (a rank without rows) launches nothing
     if (c->time_traces) HIP_TRY(c, hipEventRecord(cur(c).ev1, cur(c).stream));
     cur(c).last_trace_timed = c->time_traces;
-    c->last_march_form = (variant == 3 && !p.aniso) ? 3 : (c->fast_div ? 2 : 1);      // (vct_launch_trace's dispatch)
     cur(c).last_row0 = row0;
     cur(c).last_row1 = row1;
-    cur(c).last_row_stride = row_stride > 1 ? row_stride : 1;
+    cur(c).last_row_stride = rstride;
     cur(c).have_trace = true;
     cur(c).last_was_screen_trace = true;
     cur(c).last_trace_compacted = variant == 4 && !c->cfg.anisotropic_mips;

@@ -265,7 +265,7 @@ struct VctTraceParams {
     // (0 / 1: all of them); pack_rows = 1 writes traced row j to pixel rows 8j .. 8j+7 of `out` (a rank's packed slab of
     // an interleaved frame) instead of the row's own place in the frame.  k_trace_tile_split only.
     int32_t row_stride, pack_rows;
-    int32_t ntiles;                     // tiles of this launch (rows traced x tiles_x)
+    int32_t ntiles;                     // tiles of this launch (rows traced x tiles_x): set by vct_launch_trace
     int32_t spec_prio;                  // 1: the specular waves raise their issue priority (slab launches, vct_trace.hip)
     const float* gbuf;                  // tiled [tile][23][64]
     uint16_t* out;                      // RGBA16F [h][w][4]
@@ -429,7 +429,11 @@ hipError_t vct_launch_gbuffer_shade(const VctRasterArgs& a, const float view_pro
 hipError_t vct_launch_tri_alpha(const VctRasterArgs& a, int32_t* out, hipStream_t s);
 hipError_t vct_launch_tex_mip(const uint32_t* parent, int pw, int ph, uint32_t* level, int w, int h, hipStream_t s);
 hipError_t vct_launch_untile_gbuffer(const float* tiled, float* planes_linear, int w, int h, hipStream_t s);
-hipError_t vct_launch_trace(const VctTraceParams& p, int variant, hipStream_t s);
+// strided (row_stride > 1) and packed tile rows are read by k_trace_tile_split's own tiles only: not by the one-wave
+// kernel (variants 1, 2) nor by the compaction's virtual tiles (4)
+static inline bool vct_variant_takes_row_subsets(int variant) { return variant == 0 || variant == 3; }
+// sets p.ntiles on its own copy; march_form: the division form dispatched (vct_trace.hip)
+hipError_t vct_launch_trace(const VctTraceParams& p, int variant, hipStream_t s, int* march_form = nullptr);
 hipError_t vct_launch_divide_selftest(float d, unsigned long long* mismatches, hipStream_t s);
 // typed-buffer texel loads (RGBA8 UNORM -> four floats in the texture path) against the exact decode, n texels
 hipError_t vct_launch_texel_buffer_selftest(const uint32_t* texels, uint32_t n, unsigned long long* out, hipStream_t s);

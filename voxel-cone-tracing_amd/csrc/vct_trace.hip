@@ -678,6 +678,138 @@ __constant__ float kConeDirs[18] = {0.0f, 0.0f, 1.0f,
                                     -0.823639f, 0.267617f, 0.5f};            // trace.fs:49-57
 __constant__ float kConeWeights[6] = {0.25f, 0.15f, 0.15f, 0.15f, 0.15f, 0.15f};   // trace.fs:48
 
+// ---- tile-level building blocks: what the tile kernels and the bounce do outside the march, written once --------
+// Each performs the oracle's fp32 operations in the oracle's order.  The ones that read the G-buffer read it through
+// the pointer they are given, where they are called: the callers stage those reads around the marches (k_trace_tile).
+__device__ __forceinline__ LaneBlock make_lane_block(const VctTraceParams& p, int lane) {
+    LaneBlock lb;
+    lb.lane = lane;
+    lb.lut = (SpreadLut)p.spread_lut; lb.lut_vec = p.spread_lut;
+    lb.sbx = vct_spread3((uint32_t)lane & 3u);
+    lb.sby = vct_spread3(((uint32_t)lane >> 2) & 3u) << 1;
+    lb.sbz = vct_spread3((uint32_t)lane >> 4) << 2;
+    return lb;
+}
+// plane k of this lane's pixel; `gb` = the tile's G-buffer + the pixel's index inside the tile
+__device__ __forceinline__ float gb_plane(const float* gb, int k) { return gb[k * VCT_TILE_PIX]; }
+__device__ __forceinline__ F3 gb_planes3(const float* gb, int k) { return f3(gb_plane(gb, k), gb_plane(gb, k + 1), gb_plane(gb, k + 2)); }
+__device__ __forceinline__ F3 cone_start(F3 P, F3 N, float vs) {                   // trace.fs:92
+    return f3(P.x + N.x * vs, P.y + N.y * vs, P.z + N.z * vs);
+}
+// planes 0-11: the cones' start point and the frame k0, k1, k2 their directions are combined in
+__device__ __forceinline__ void cone_frame_from_gbuffer(const float* gb, float vs, F3& start, F3& k0, F3& k1, F3& k2) {
+    const F3 P = gb_planes3(gb, 0), Nw = gb_planes3(gb, 3), T = gb_planes3(gb, 6), B = gb_planes3(gb, 9);
+    // trace.fs:175: inverse(transpose(mat3(T,B,N))) = columns (BxN, NxT, TxB) / det
+    const F3 c0 = cross3(B, Nw), c1 = cross3(Nw, T), c2 = cross3(T, B);
+    const float inv_det = div_rn(1.0f, dot3(T, c0));
+    k0 = f3(c0.x * inv_det, c0.y * inv_det, c0.z * inv_det);
+    k1 = f3(c1.x * inv_det, c1.y * inv_det, c1.z * inv_det);
+    k2 = f3(c2.x * inv_det, c2.y * inv_det, c2.z * inv_det);
+    start = cone_start(P, Nw, vs);
+}
+// direction of diffuse cone i in the frame (b0, b1, b2)                             trace.fs:196-199
+__device__ __forceinline__ F3 cone_dir(F3 b0, F3 b1, F3 b2, int i) {
+    const float* d = &kConeDirs[3 * i];
+    const float ddx = d[0], ddy = d[1], ddz = d[2];
+    return normalize3(f3(b0.x * ddx + b1.x * ddy + b2.x * ddz, b0.y * ddx + b1.y * ddy + b2.y * ddz,
+                         b0.z * ddx + b1.z * ddy + b2.z * ddz));
+}
+// the weighted sum of the diffuse cones: an fma chain over cones 0..5, in that order (V4: F4, or the float4 parked in LDS)
+template <class V4>
+__device__ __forceinline__ F4 fold_cone(F4 ind, int i, V4 c) {
+    const float wgt = kConeWeights[i];
+    return {fmaf(wgt, c.x, ind.x), fmaf(wgt, c.y, ind.y), fmaf(wgt, c.z, ind.z), fmaf(wgt, c.w, ind.w)};
+}
+// the specular cone runs along reflect(-E, N) with the bump normal N (planes 12-14)     trace.fs:217-218
+__device__ __forceinline__ F3 specular_dir(F3 P, F3 N, const float cam[3]) {
+    const F3 E = normalize3(f3(cam[0] - P.x, cam[1] - P.y, cam[2] - P.z));              // :181
+    return normalize3(reflect3(f3(E.x * -1.0f, E.y * -1.0f, E.z * -1.0f), N));          // :217
+}
+// config.debug_outputs: cone i's raw vec4 and step count.  `pixel()` re-derives the pixel's index per store (see k_trace_tile)
+template <class Pixel>
+__device__ __forceinline__ void store_debug_cone(const VctTraceParams& p, Pixel pixel, int i, F4 c, int st,
+                                                 bool alive, bool in_frame) {
+    if (p.dbg_cones && alive) {
+        float* d = p.dbg_cones + pixel() * 28 + 4 * i;
+        d[0] = c.x; d[1] = c.y; d[2] = c.z; d[3] = c.w;
+    }
+    if (p.dbg_steps && in_frame) p.dbg_steps[pixel() * 7 + i] = (uint8_t)st;
+}
+// a discarded pixel keeps the clear colour (alpha 1)                                VCT.h:156-159
+__device__ __forceinline__ float clear_colour(const VctTraceParams& p) { return p.ambient < 0.5f ? 0.5f : 1.0f; }
+
+// The composite of one pixel inside the frame from its gathered diffuse cones `ind` and its specular cone `sc`, read
+// from planes 0-2 and 12-22 of `gb`                                                trace.fs:179-227
+// COMP: the Show* ternaries (include/vct.h) as selects on the wave-uniform mask, and the per-component outputs.
+// VCT_SHOW_ALL selects every unmasked value, and without COMP every select is decided here: the operations and their
+// order are the same in all three cases.
+template <bool COMP, class V4, class Pixel>
+__device__ __forceinline__ void composite(const VctTraceParams& p, const float* gb, F4 ind, V4 sc,
+                                          bool alive, Pixel pixel) {
+    const F3 P = gb_planes3(gb, 0), N = gb_planes3(gb, 12);
+    const float alb_r = gb_plane(gb, 15), alb_g = gb_plane(gb, 16), alb_b = gb_plane(gb, 17), alb_a = gb_plane(gb, 18);
+    const float shadow = gb_plane(gb, 22);
+    const F3 L = normalize3(f3(p.light[0], p.light[1], p.light[2]));        // :179
+    const F3 E = normalize3(f3(p.cam[0] - P.x, p.cam[1] - P.y, p.cam[2] - P.z));   // :181
+    const float cos_theta = fmaxf(dot3(N, L), 0.0f);                        // :188
+    const uint32_t comp = COMP ? (uint32_t)__builtin_amdgcn_readfirstlane((int)p.comp) : 0u;
+    const uint32_t show = COMP ? comp & (uint32_t)VCT_SHOW_ALL : (uint32_t)VCT_SHOW_ALL;
+    const bool s_dd = !COMP || (show & VCT_SHOW_DIFFUSE), s_ao = !COMP || (show & VCT_SHOW_AMBIENT_OCCLUSION);
+    const bool s_ird = !COMP || (show & VCT_SHOW_INDIRECT_DIFFUSE), s_ds = !COMP || (show & VCT_SHOW_SPECULAR);
+    const bool s_irs = !COMP || (show & VCT_SHOW_INDIRECT_SPECULAR);
+    const float raw_dd = shadow * cos_theta;
+    const float direct_diffuse = s_dd ? raw_dd : 0.0f;                      // :192 (:190)
+    const float occlusion = s_ao ? 1.0f - ind.w : 1.0f;                    // :201
+    const float ird_r = s_ird ? ind.x : 0.0f, ird_g = s_ird ? ind.y : 0.0f, ird_b = s_ird ? ind.z : 0.0f;   // :203
+    const float dr = (direct_diffuse + occlusion * ird_r) * alb_r;          // :205
+    const float dg = (direct_diffuse + occlusion * ird_g) * alb_g;
+    const float db = (direct_diffuse + occlusion * ird_b) * alb_b;
+    const F3 R = normalize3(reflect3(f3(L.x * -1.0f, L.y * -1.0f, L.z * -1.0f), N));   // :212
+    const float spec = powf(fmaxf(dot3(E, R), 0.0f), p.shininess);          // :213
+    const float raw_ds = spec * shadow;
+    const float direct_spec = s_ds ? raw_ds : 0.0f;                         // :214 (:215)
+    const float spec_occ = s_ao ? 1.0f - sc.w : 1.0f;                       // :221
+    const float irs_r = s_irs ? sc.x : 0.0f, irs_g = s_irs ? sc.y : 0.0f, irs_b = s_irs ? sc.z : 0.0f;
+    const float sr = (irs_r + spec_occ * direct_spec) * gb_plane(gb, 19);   // :223
+    const float sg = (irs_g + spec_occ * direct_spec) * gb_plane(gb, 20);
+    const float sb = (irs_b + spec_occ * direct_spec) * gb_plane(gb, 21);
+    const float ar = p.ambient * alb_r * occlusion;                         // :225
+    const float ag = p.ambient * alb_g * occlusion;
+    const float ab = p.ambient * alb_b * occlusion;
+    float o0 = ar + dr + sr, o1 = ag + dg + sg, o2 = ab + db + sb, o3 = alb_a;   // :227
+    if (!alive) {
+        const float cc = clear_colour(p);
+        o0 = cc; o1 = cc; o2 = cc; o3 = 1.0f;
+    }
+    uint2 pk;
+    pk.x = pack_half2(o0, o1);
+    pk.y = pack_half2(o2, o3);
+    *reinterpret_cast<uint2*>(p.out + pixel() * 4) = pk;
+    if (COMP) {     // raw per-component values, one 8-byte store per output; discarded pixels get zeros
+        const uint32_t which = comp >> VCT_COMP_AOV_SHIFT;
+        const size_t frame_halves = (size_t)p.width * p.height * 4;
+        uint16_t* dst = p.aov + pixel() * 4;        // the outputs that are on, in bit order
+        uint2 q;
+        if (which & VCT_AOV_INDIRECT_DIFFUSE) {
+            q.x = alive ? pack_half2(ind.x, ind.y) : 0u;
+            q.y = alive ? pack_half2(ind.z, ind.w) : 0u;
+            *reinterpret_cast<uint2*>(dst) = q;
+            dst += frame_halves;
+        }
+        if (which & VCT_AOV_INDIRECT_SPECULAR) {
+            q.x = alive ? pack_half2(sc.x, sc.y) : 0u;
+            q.y = alive ? pack_half2(sc.z, sc.w) : 0u;
+            *reinterpret_cast<uint2*>(dst) = q;
+            dst += frame_halves;
+        }
+        if (which & VCT_AOV_DIRECT) {
+            q.x = alive ? pack_half2(raw_dd, raw_ds) : 0u;
+            q.y = alive ? pack_half2(shadow, 1.0f) : 0u;
+            *reinterpret_cast<uint2*>(dst) = q;
+        }
+    }
+}
+
 // Workgroups are dealt to XCDs round-robin by the dispatcher (block b -> XCD b % 8); the tile order is
 // remapped so that every XCD works on short runs of neighbouring tiles (neighbouring tiles march
 // through neighbouring voxels and share that XCD's L2) while the runs of all XCDs interleave over
@@ -704,9 +836,7 @@ __device__ __forceinline__ int xcd_remap(int b, int nblocks) {
 #endif
 
 // One wave per tile, lane = pixel, the 7 cones in sequence; VCT_WAVES_PER_BLOCK horizontally
-// adjacent tiles per workgroup.  Workgroups are dealt to XCDs round-robin by the dispatcher (block b -> XCD b % 8), so
-// the tile order is remapped to give every XCD one contiguous run of tiles: neighbouring tiles
-// march through neighbouring voxels and share that XCD's L2.
+// adjacent tiles per workgroup, in the tile order of xcd_remap.
 template <bool WRAP, int FASTDIV, bool COOP>
 __global__ void __launch_bounds__(64 * VCT_WAVES_PER_BLOCK, VCT_TRACE_MIN_WAVES)
 k_trace_tile(const VctTraceParams p) {
@@ -716,18 +846,13 @@ k_trace_tile(const VctTraceParams p) {
     // G-buffer base and the LDS slab base live in SGPRs
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     float4* blk = &lds_blk[wave][0][0];
-    LaneBlock lb;
 
     const int ntiles = (p.tile_row1 - p.tile_row0) * p.tiles_x;
     const int vb = xcd_remap((int)blockIdx.x, (int)gridDim.x);
     const int ti = vb * VCT_WAVES_PER_BLOCK + wave;
     if (ti >= ntiles) return;
 
-    lb.lane = lane;
-    lb.lut = (SpreadLut)p.spread_lut; lb.lut_vec = p.spread_lut;
-    lb.sbx = vct_spread3((uint32_t)lane & 3u);     
-    lb.sby = vct_spread3(((uint32_t)lane >> 2) & 3u) << 1;
-    lb.sbz = vct_spread3((uint32_t)lane >> 4) << 2;
+    const LaneBlock lb = make_lane_block(p, lane);
     MarchStats ms = {};
 
     const int tile = p.tile_row0 * p.tiles_x + ti;
@@ -736,7 +861,8 @@ k_trace_tile(const VctTraceParams p) {
     // integer ops) rather than carried in 64-bit VGPR pairs across the march loops, where they
     // would be spilled to scratch under the 80-VGPR budget.
     auto fresh_lane = [&]() { int l = lane; asm volatile("" : "+v"(l)); return l; };
-    auto pixel_index = [&](int l) {
+    auto pixel_index = [&]() {
+        const int l = fresh_lane();
         return (size_t)(ty * VCT_TILE + (l >> 3)) * p.width + (tx * VCT_TILE + (l & 7));
     };
     auto gbuf_ptr = [&](int l) {
@@ -747,106 +873,35 @@ k_trace_tile(const VctTraceParams p) {
     // once up front: the 23 planes are only L1/L2 re-reads, while every VGPR kept live across the
     // march loops costs occupancy, and resident waves are what hides the sampler's latency chain.
     const float* gb = gbuf_ptr(lane);
-#define VCT_GB(k) gb[(k) * VCT_TILE_PIX]
     const bool in_frame = (x < p.width) && (y < p.height);
-    const bool alive = in_frame && !(VCT_GB(18) < 0.5f);            // trace.fs:171 discard
+    const bool alive = in_frame && !(gb_plane(gb, 18) < 0.5f);      // trace.fs:171 discard
 
     F3 start, k0, k1, k2;
-    {
-        const F3 P = f3(VCT_GB(0), VCT_GB(1), VCT_GB(2)), Nw = f3(VCT_GB(3), VCT_GB(4), VCT_GB(5));
-        const F3 T = f3(VCT_GB(6), VCT_GB(7), VCT_GB(8)), B = f3(VCT_GB(9), VCT_GB(10), VCT_GB(11));
-        // trace.fs:175: inverse(transpose(mat3(T,B,N))) = columns (BxN, NxT, TxB) / det
-        const F3 c0 = cross3(B, Nw), c1 = cross3(Nw, T), c2 = cross3(T, B);
-        const float inv_det = div_rn(1.0f, dot3(T, c0));
-        k0 = f3(c0.x * inv_det, c0.y * inv_det, c0.z * inv_det);
-        k1 = f3(c1.x * inv_det, c1.y * inv_det, c1.z * inv_det);
-        k2 = f3(c2.x * inv_det, c2.y * inv_det, c2.z * inv_det);
-        start = f3(P.x + Nw.x * p.vs, P.y + Nw.y * p.vs, P.z + Nw.z * p.vs);       // :92
-    }
+    cone_frame_from_gbuffer(gb, p.vs, start, k0, k1, k2);
 
-    float ind[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    F4 ind = {0.0f, 0.0f, 0.0f, 0.0f};
     int total = 0;
 #pragma unroll 1
     for (int i = 0; i < 6; ++i) {                                           // :196-199
-        const float ddx = kConeDirs[3 * i], ddy = kConeDirs[3 * i + 1], ddz = kConeDirs[3 * i + 2];
-        F3 dir = f3(k0.x * ddx + k1.x * ddy + k2.x * ddz, k0.y * ddx + k1.y * ddy + k2.y * ddz,
-                    k0.z * ddx + k1.z * ddy + k2.z * ddz);
-        dir = normalize3(dir);
         int st;
-        const F4 c = cone_march<WRAP, FASTDIV, COOP>(p, alive, start, dir, p.steps_diffuse,
+        const F4 c = cone_march<WRAP, FASTDIV, COOP>(p, alive, start, cone_dir(k0, k1, k2, i), p.steps_diffuse,
                                                      p.n_diffuse, blk, lb, st, ms);
         total += st;
-        const float wgt = kConeWeights[i];
-        ind[0] = fmaf(wgt, c.x, ind[0]);
-        ind[1] = fmaf(wgt, c.y, ind[1]);
-        ind[2] = fmaf(wgt, c.z, ind[2]);
-        ind[3] = fmaf(wgt, c.w, ind[3]);
-        if (p.dbg_cones && alive) {
-            float* d = p.dbg_cones + pixel_index(fresh_lane()) * 28 + 4 * i;
-            d[0] = c.x; d[1] = c.y; d[2] = c.z; d[3] = c.w;
-        }
-        if (p.dbg_steps && in_frame) p.dbg_steps[pixel_index(fresh_lane()) * 7 + i] = (uint8_t)st;
+        ind = fold_cone(ind, i, c);
+        store_debug_cone(p, pixel_index, i, c, st, alive, in_frame);
     }
 
-    // stage 2: specular cone along reflect(-E, N) with the bump normal           trace.fs:217-218
-    const float* gb2 = gbuf_ptr(fresh_lane());   // a fresh pointer: re-read instead of keeping planes live
-#undef VCT_GB
-#define VCT_GB(k) gb2[(k) * VCT_TILE_PIX]
-    F4 sc;
-    {
-        const F3 P = f3(VCT_GB(0), VCT_GB(1), VCT_GB(2));
-        const F3 N = f3(VCT_GB(12), VCT_GB(13), VCT_GB(14));
-        const F3 E = normalize3(f3(p.cam[0] - P.x, p.cam[1] - P.y, p.cam[2] - P.z));   // :181
-        const F3 Rd = normalize3(reflect3(f3(E.x * -1.0f, E.y * -1.0f, E.z * -1.0f), N));  // :217
-        int st6;
-        sc = cone_march<WRAP, FASTDIV, COOP>(p, alive, start, Rd, p.steps_specular, p.n_specular,
-                                             blk, lb, st6, ms);
-        total += st6;
-        if (p.dbg_cones && alive) {
-            float* d = p.dbg_cones + pixel_index(fresh_lane()) * 28 + 24;
-            d[0] = sc.x; d[1] = sc.y; d[2] = sc.z; d[3] = sc.w;
-        }
-        if (p.dbg_steps && in_frame) p.dbg_steps[pixel_index(fresh_lane()) * 7 + 6] = (uint8_t)st6;
-    }
+    // stage 2: the specular cone, from a fresh pointer: re-read instead of keeping planes live
+    const float* gb2 = gbuf_ptr(fresh_lane());
+    const F3 Rd = specular_dir(gb_planes3(gb2, 0), gb_planes3(gb2, 12), p.cam);
+    int st6;
+    const F4 sc = cone_march<WRAP, FASTDIV, COOP>(p, alive, start, Rd, p.steps_specular, p.n_specular, blk, lb, st6, ms);
+    total += st6;
+    store_debug_cone(p, pixel_index, 6, sc, st6, alive, in_frame);
 
-    // stage 3: composite                                                          trace.fs:179-227
+    // stage 3: composite
     const float* gb3 = gbuf_ptr(fresh_lane());
-#undef VCT_GB
-#define VCT_GB(k) gb3[(k) * VCT_TILE_PIX]
-    if (in_frame) {
-        const F3 P = f3(VCT_GB(0), VCT_GB(1), VCT_GB(2));
-        const F3 N = f3(VCT_GB(12), VCT_GB(13), VCT_GB(14));
-        const float alb_r = VCT_GB(15), alb_g = VCT_GB(16), alb_b = VCT_GB(17), alb_a = VCT_GB(18);
-        const float shadow = VCT_GB(22);
-        const F3 L = normalize3(f3(p.light[0], p.light[1], p.light[2]));        // :179
-        const F3 E = normalize3(f3(p.cam[0] - P.x, p.cam[1] - P.y, p.cam[2] - P.z));   // :181
-        const float cos_theta = fmaxf(dot3(N, L), 0.0f);                        // :188
-        const float direct_diffuse = shadow * cos_theta;                        // :192
-        const float occlusion = 1.0f - ind[3];                                  // :201
-        const float dr = (direct_diffuse + occlusion * ind[0]) * alb_r;         // :205
-        const float dg = (direct_diffuse + occlusion * ind[1]) * alb_g;
-        const float db = (direct_diffuse + occlusion * ind[2]) * alb_b;
-        const F3 R = normalize3(reflect3(f3(L.x * -1.0f, L.y * -1.0f, L.z * -1.0f), N));   // :212
-        const float spec = powf(fmaxf(dot3(E, R), 0.0f), p.shininess);          // :213
-        const float direct_spec = spec * shadow;                                // :214
-        const float spec_occ = 1.0f - sc.w;                                     // :221
-        const float sr = (sc.x + spec_occ * direct_spec) * VCT_GB(19);          // :223
-        const float sg = (sc.y + spec_occ * direct_spec) * VCT_GB(20);
-        const float sb = (sc.z + spec_occ * direct_spec) * VCT_GB(21);
-        const float ar = p.ambient * alb_r * occlusion;                         // :225
-        const float ag = p.ambient * alb_g * occlusion;
-        const float ab = p.ambient * alb_b * occlusion;
-        float o0 = ar + dr + sr, o1 = ag + dg + sg, o2 = ab + db + sb, o3 = alb_a;   // :227
-        if (!alive) {                                                           // VCT.h:156-159
-            const float cc = p.ambient < 0.5f ? 0.5f : 1.0f;
-            o0 = cc; o1 = cc; o2 = cc; o3 = 1.0f;
-        }
-        uint2 pk;
-        pk.x = pack_half2(o0, o1);
-        pk.y = pack_half2(o2, o3);
-        *reinterpret_cast<uint2*>(p.out + pixel_index(fresh_lane()) * 4) = pk;
-    }
-#undef VCT_GB
+    if (in_frame) composite<false>(p, gb3, ind, sc, alive, pixel_index);
     // executed-step count: wave reduction, stored into the tile's slot (a plain store: no atomic, nothing to clear)
     for (int off = 32; off > 0; off >>= 1) total += __shfl_xor(total, off);
     if (lane == 0) p.tile_steps[tile] = (uint32_t)total;
@@ -890,7 +945,6 @@ k_trace_tile_split(const VctTraceParams p) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     float4* blk = &lds_blk[wave][0][0];
-    LaneBlock lb;
     if (threadIdx.x == 0) { lds_done = 0; lds_steps = 0; }
     __syncthreads();
 
@@ -909,11 +963,7 @@ k_trace_tile_split(const VctTraceParams p) {
         cpix = p.vt_pix[(size_t)ti * 64 + lane];
     }
 
-    lb.lane = lane;
-    lb.lut = (SpreadLut)p.spread_lut; lb.lut_vec = p.spread_lut;
-    lb.sbx = vct_spread3((uint32_t)lane & 3u);     
-    lb.sby = vct_spread3(((uint32_t)lane >> 2) & 3u) << 1;
-    lb.sbz = vct_spread3((uint32_t)lane >> 4) << 2;
+    const LaneBlock lb = make_lane_block(p, lane);
     MarchStats ms = {};
 
     // (interleaved slabs: traced row j of the launch is tile row row0 + j * stride; the plain launch pays no second division)
@@ -929,7 +979,8 @@ k_trace_tile_split(const VctTraceParams p) {
     const int oy = p.pack_rows ? (p.row_stride > 1 ? lrow : ty - p.tile_row0) : ty;
     const int plane_ = compact ? (int)(cpix & 63u) : lane;        // this lane's pixel inside its tile
     auto fresh_lane = [&]() { int l = plane_; asm volatile("" : "+v"(l)); return l; };
-    auto pixel_index = [&](int l) {
+    auto pixel_index = [&]() {
+        const int l = fresh_lane();
         return (size_t)(oy * VCT_TILE + (l >> 3)) * p.width + (tx * VCT_TILE + (l & 7));
     };
     auto gbuf_ptr = [&](int l) {
@@ -937,9 +988,8 @@ k_trace_tile_split(const VctTraceParams p) {
     };
     const int x = tx * VCT_TILE + (plane_ & 7), y = ty * VCT_TILE + (plane_ >> 3);
     const float* gb = gbuf_ptr(plane_);
-#define VCT_GB(k) gb[(k) * VCT_TILE_PIX]
     const bool in_frame = cvalid && (x < p.width) && (y < p.height);
-    const bool alive = in_frame && !(VCT_GB(18) < 0.5f);            // trace.fs:171 discard
+    const bool alive = in_frame && !(gb_plane(gb, 18) < 0.5f);      // trace.fs:171 discard
     int total = 0;
     // COMP: a cone group nothing reads (march_groups bit 0: cones 0-5, bit 1: cone 6) is marched over 0 steps -- zero
     // cones into LDS and the debug outputs, 0 steps, and the wave arrives at once.  The count is wave-uniform (the
@@ -948,33 +998,15 @@ k_trace_tile_split(const VctTraceParams p) {
     const int n_diffuse = (groups & 1u) ? p.n_diffuse : 0, n_specular = (groups & 2u) ? p.n_specular : 0;
     if (wave < VCT_SPLIT - 1) {
         F3 start, k0, k1, k2;
-        {
-            const F3 P = f3(VCT_GB(0), VCT_GB(1), VCT_GB(2)), Nw = f3(VCT_GB(3), VCT_GB(4), VCT_GB(5));
-            const F3 T = f3(VCT_GB(6), VCT_GB(7), VCT_GB(8)), B = f3(VCT_GB(9), VCT_GB(10), VCT_GB(11));
-            // trace.fs:175: inverse(transpose(mat3(T,B,N))) = columns (BxN, NxT, TxB) / det
-            const F3 c0 = cross3(B, Nw), c1 = cross3(Nw, T), c2 = cross3(T, B);
-            const float inv_det = div_rn(1.0f, dot3(T, c0));
-            k0 = f3(c0.x * inv_det, c0.y * inv_det, c0.z * inv_det);
-            k1 = f3(c1.x * inv_det, c1.y * inv_det, c1.z * inv_det);
-            k2 = f3(c2.x * inv_det, c2.y * inv_det, c2.z * inv_det);
-            start = f3(P.x + Nw.x * p.vs, P.y + Nw.y * p.vs, P.z + Nw.z * p.vs);       // :92
-        }
+        cone_frame_from_gbuffer(gb, p.vs, start, k0, k1, k2);
 #pragma unroll 1
         for (int i = wave * VCT_CONES_PER_WAVE; i < wave * VCT_CONES_PER_WAVE + VCT_CONES_PER_WAVE; ++i) {      // :196-199
-            const float ddx = kConeDirs[3 * i], ddy = kConeDirs[3 * i + 1], ddz = kConeDirs[3 * i + 2];
-            F3 dir = f3(k0.x * ddx + k1.x * ddy + k2.x * ddz, k0.y * ddx + k1.y * ddy + k2.y * ddz,
-                        k0.z * ddx + k1.z * ddy + k2.z * ddz);
-            dir = normalize3(dir);
             int st;
-            const F4 c = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO>(p, alive, start, dir, p.steps_diffuse,
-                                                                n_diffuse, blk, lb, st, ms);
+            const F4 c = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO>(p, alive, start, cone_dir(k0, k1, k2, i),
+                                                                p.steps_diffuse, n_diffuse, blk, lb, st, ms);
             total += st;
             lds_cone[i][lane] = make_float4(c.x, c.y, c.z, c.w);
-            if (p.dbg_cones && alive) {
-                float* d = p.dbg_cones + pixel_index(fresh_lane()) * 28 + 4 * i;
-                d[0] = c.x; d[1] = c.y; d[2] = c.z; d[3] = c.w;
-            }
-            if (p.dbg_steps && in_frame) p.dbg_steps[pixel_index(fresh_lane()) * 7 + i] = (uint8_t)st;
+            store_debug_cone(p, pixel_index, i, c, st, alive, in_frame);
         }
     } else {
         // the specular wave is the longest of a tile (29 march steps against 21) and the last ones of a launch are its
@@ -983,22 +1015,14 @@ k_trace_tile_split(const VctTraceParams p) {
         // 0.111 ms max), costs 0.5 % on the whole frame: the host sets it for launches of at most half the frame.
         // (the PRIO instantiation -- whole frames -- sets and resets the priority around every sample's loads instead)
         if (!PRIO && p.spec_prio) __builtin_amdgcn_s_setprio(1);
-        // specular cone along reflect(-E, N) with the bump normal                 trace.fs:217-218
-        const F3 P = f3(VCT_GB(0), VCT_GB(1), VCT_GB(2)), Nw = f3(VCT_GB(3), VCT_GB(4), VCT_GB(5));
-        const F3 N = f3(VCT_GB(12), VCT_GB(13), VCT_GB(14));
-        const F3 start = f3(P.x + Nw.x * p.vs, P.y + Nw.y * p.vs, P.z + Nw.z * p.vs);
-        const F3 E = normalize3(f3(p.cam[0] - P.x, p.cam[1] - P.y, p.cam[2] - P.z));   // :181
-        const F3 Rd = normalize3(reflect3(f3(E.x * -1.0f, E.y * -1.0f, E.z * -1.0f), N));  // :217
+        const F3 P = gb_planes3(gb, 0), Nw = gb_planes3(gb, 3), N = gb_planes3(gb, 12);
+        const F3 start = cone_start(P, Nw, p.vs);
         int st6;
-        const F4 sc = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO>(p, alive, start, Rd, p.steps_specular,
-                                                             n_specular, blk, lb, st6, ms);
+        const F4 sc = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO>(p, alive, start, specular_dir(P, N, p.cam),
+                                                             p.steps_specular, n_specular, blk, lb, st6, ms);
         total += st6;
         lds_cone[6][lane] = make_float4(sc.x, sc.y, sc.z, sc.w);
-        if (p.dbg_cones && alive) {
-            float* d = p.dbg_cones + pixel_index(fresh_lane()) * 28 + 24;
-            d[0] = sc.x; d[1] = sc.y; d[2] = sc.z; d[3] = sc.w;
-        }
-        if (p.dbg_steps && in_frame) p.dbg_steps[pixel_index(fresh_lane()) * 7 + 6] = (uint8_t)st6;
+        store_debug_cone(p, pixel_index, 6, sc, st6, alive, in_frame);
     }
     for (int off = 32; off > 0; off >>= 1) total += __shfl_xor(total, off);
     if (lane == 0) atomicAdd(&lds_steps, total);          // LDS: the last arriver below stores the tile's total
@@ -1014,89 +1038,14 @@ k_trace_tile_split(const VctTraceParams p) {
     __threadfence_block();
     if (lane == 0) p.tile_steps[tile0] = (uint32_t)lds_steps;     // one plain store per tile: no global atomic, nothing to clear
 
-    // composite by the last wave                                                   trace.fs:179-227
+    // the last wave gathers the diffuse cones in the oracle's order and composites
     const float* gb3 = gbuf_ptr(fresh_lane());
-#undef VCT_GB
-#define VCT_GB(k) gb3[(k) * VCT_TILE_PIX]
     if (in_frame) {
-        float ind[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        F4 ind = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            const float4 c = lds_cone[i][lane];
-            const float wgt = kConeWeights[i];
-            ind[0] = fmaf(wgt, c.x, ind[0]);
-            ind[1] = fmaf(wgt, c.y, ind[1]);
-            ind[2] = fmaf(wgt, c.z, ind[2]);
-            ind[3] = fmaf(wgt, c.w, ind[3]);
-        }
-        const float4 sc = lds_cone[6][lane];
-        const F3 P = f3(VCT_GB(0), VCT_GB(1), VCT_GB(2));
-        const F3 N = f3(VCT_GB(12), VCT_GB(13), VCT_GB(14));
-        const float alb_r = VCT_GB(15), alb_g = VCT_GB(16), alb_b = VCT_GB(17), alb_a = VCT_GB(18);
-        const float shadow = VCT_GB(22);
-        const F3 L = normalize3(f3(p.light[0], p.light[1], p.light[2]));        // :179
-        const F3 E = normalize3(f3(p.cam[0] - P.x, p.cam[1] - P.y, p.cam[2] - P.z));   // :181
-        const float cos_theta = fmaxf(dot3(N, L), 0.0f);                        // :188
-        // COMP: the Show* ternaries (include/vct.h) as selects on the wave-uniform mask; VCT_SHOW_ALL selects every
-        // unmasked value, so the operations and their order are the default kernel's
-        const uint32_t comp = COMP ? (uint32_t)__builtin_amdgcn_readfirstlane((int)p.comp) : 0u;
-        const uint32_t show = COMP ? comp & (uint32_t)VCT_SHOW_ALL : (uint32_t)VCT_SHOW_ALL;
-        const bool s_dd = !COMP || (show & VCT_SHOW_DIFFUSE), s_ao = !COMP || (show & VCT_SHOW_AMBIENT_OCCLUSION);
-        const bool s_ird = !COMP || (show & VCT_SHOW_INDIRECT_DIFFUSE), s_ds = !COMP || (show & VCT_SHOW_SPECULAR);
-        const bool s_irs = !COMP || (show & VCT_SHOW_INDIRECT_SPECULAR);
-        const float raw_dd = shadow * cos_theta;
-        const float direct_diffuse = s_dd ? raw_dd : 0.0f;                      // :192 (:190)
-        const float occlusion = s_ao ? 1.0f - ind[3] : 1.0f;                    // :201
-        const float ird_r = s_ird ? ind[0] : 0.0f, ird_g = s_ird ? ind[1] : 0.0f, ird_b = s_ird ? ind[2] : 0.0f;   // :203
-        const float dr = (direct_diffuse + occlusion * ird_r) * alb_r;          // :205
-        const float dg = (direct_diffuse + occlusion * ird_g) * alb_g;
-        const float db = (direct_diffuse + occlusion * ird_b) * alb_b;
-        const F3 R = normalize3(reflect3(f3(L.x * -1.0f, L.y * -1.0f, L.z * -1.0f), N));   // :212
-        const float spec = powf(fmaxf(dot3(E, R), 0.0f), p.shininess);          // :213
-        const float raw_ds = spec * shadow;
-        const float direct_spec = s_ds ? raw_ds : 0.0f;                         // :214 (:215)
-        const float spec_occ = s_ao ? 1.0f - sc.w : 1.0f;                       // :221
-        const float irs_r = s_irs ? sc.x : 0.0f, irs_g = s_irs ? sc.y : 0.0f, irs_b = s_irs ? sc.z : 0.0f;
-        const float sr = (irs_r + spec_occ * direct_spec) * VCT_GB(19);         // :223
-        const float sg = (irs_g + spec_occ * direct_spec) * VCT_GB(20);
-        const float sb = (irs_b + spec_occ * direct_spec) * VCT_GB(21);
-        const float ar = p.ambient * alb_r * occlusion;                         // :225
-        const float ag = p.ambient * alb_g * occlusion;
-        const float ab = p.ambient * alb_b * occlusion;
-        float o0 = ar + dr + sr, o1 = ag + dg + sg, o2 = ab + db + sb, o3 = alb_a;   // :227
-        if (!alive) {                                                           // VCT.h:156-159
-            const float cc = p.ambient < 0.5f ? 0.5f : 1.0f;
-            o0 = cc; o1 = cc; o2 = cc; o3 = 1.0f;
-        }
-        uint2 pk;
-        pk.x = pack_half2(o0, o1);
-        pk.y = pack_half2(o2, o3);
-        *reinterpret_cast<uint2*>(p.out + pixel_index(fresh_lane()) * 4) = pk;
-        if (COMP) {     // raw per-component values, one 8-byte store per output; discarded pixels get zeros
-            const uint32_t which = comp >> VCT_COMP_AOV_SHIFT;
-            const size_t frame_halves = (size_t)p.width * p.height * 4;
-            uint16_t* dst = p.aov + pixel_index(fresh_lane()) * 4;        // the outputs that are on, in bit order
-            uint2 q;
-            if (which & VCT_AOV_INDIRECT_DIFFUSE) {
-                q.x = alive ? pack_half2(ind[0], ind[1]) : 0u;
-                q.y = alive ? pack_half2(ind[2], ind[3]) : 0u;
-                *reinterpret_cast<uint2*>(dst) = q;
-                dst += frame_halves;
-            }
-            if (which & VCT_AOV_INDIRECT_SPECULAR) {
-                q.x = alive ? pack_half2(sc.x, sc.y) : 0u;
-                q.y = alive ? pack_half2(sc.z, sc.w) : 0u;
-                *reinterpret_cast<uint2*>(dst) = q;
-                dst += frame_halves;
-            }
-            if (which & VCT_AOV_DIRECT) {
-                q.x = alive ? pack_half2(raw_dd, raw_ds) : 0u;
-                q.y = alive ? pack_half2(shadow, 1.0f) : 0u;
-                *reinterpret_cast<uint2*>(dst) = q;
-            }
-        }
+        for (int i = 0; i < 6; ++i) ind = fold_cone(ind, i, lds_cone[i][lane]);
+        composite<COMP>(p, gb3, ind, lds_cone[6][lane], alive, pixel_index);
     }
-#undef VCT_GB
 }
 
 __device__ __forceinline__ uint32_t to_unorm8_dev(float f) {     // [GL] float -> unorm8, round to nearest
@@ -1135,29 +1084,21 @@ __device__ __forceinline__ void bounce_voxels(const VctTraceParams& p, bool aliv
     const F3 helper = fabsf(nrm.y) < 0.9f ? f3(0.0f, 1.0f, 0.0f) : f3(1.0f, 0.0f, 0.0f);
     const F3 t = normalize3(cross3(helper, nrm));
     const F3 bt = cross3(nrm, t);
-    const F3 start = f3(P.x + nrm.x * p.vs, P.y + nrm.y * p.vs, P.z + nrm.z * p.vs);
-    float ind[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    const F3 start = cone_start(P, nrm, p.vs);
+    F4 ind = {0.0f, 0.0f, 0.0f, 0.0f};
     int total = 0;
 #pragma unroll 1
     for (int c = 0; c < 6; ++c) {
-        const float ddx = kConeDirs[3 * c], ddy = kConeDirs[3 * c + 1], ddz = kConeDirs[3 * c + 2];
-        F3 dir = f3(t.x * ddx + bt.x * ddy + nrm.x * ddz, t.y * ddx + bt.y * ddy + nrm.y * ddz,
-                    t.z * ddx + bt.z * ddy + nrm.z * ddz);
-        dir = normalize3(dir);
         int st;
-        const F4 cone = march(alive, start, dir, st);
+        const F4 cone = march(alive, start, cone_dir(t, bt, nrm, c), st);
         total += st;
-        const float wgt = kConeWeights[c];
-        ind[0] = fmaf(wgt, cone.x, ind[0]);
-        ind[1] = fmaf(wgt, cone.y, ind[1]);
-        ind[2] = fmaf(wgt, cone.z, ind[2]);
-        ind[3] = fmaf(wgt, cone.w, ind[3]);
+        ind = fold_cone(ind, c, cone);
     }
     if (alive) {
-        const float occlusion = 1.0f - ind[3];
-        const uint32_t r = to_unorm8_dev(unorm8(src & 0xffu) + unorm8(aq & 0xffu) * (occlusion * ind[0]));
-        const uint32_t g = to_unorm8_dev(unorm8((src >> 8) & 0xffu) + unorm8((aq >> 8) & 0xffu) * (occlusion * ind[1]));
-        const uint32_t bl = to_unorm8_dev(unorm8((src >> 16) & 0xffu) + unorm8((aq >> 16) & 0xffu) * (occlusion * ind[2]));
+        const float occlusion = 1.0f - ind.w;
+        const uint32_t r = to_unorm8_dev(unorm8(src & 0xffu) + unorm8(aq & 0xffu) * (occlusion * ind.x));
+        const uint32_t g = to_unorm8_dev(unorm8((src >> 8) & 0xffu) + unorm8((aq >> 8) & 0xffu) * (occlusion * ind.y));
+        const uint32_t bl = to_unorm8_dev(unorm8((src >> 16) & 0xffu) + unorm8((aq >> 16) & 0xffu) * (occlusion * ind.z));
         p.bounce_out[vox] = r | (g << 8) | (bl << 16) | (src & 0xff000000u);
     } else {
         total = 0;
@@ -1171,12 +1112,7 @@ __device__ __forceinline__ void bounce_voxels(const VctTraceParams& p, bool aliv
     const int lane = threadIdx.x & 63;                                       \
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); \
     float4* blk = &lds_blk[wave][0][0];                                      \
-    LaneBlock lb;                                                            \
-    lb.lane = lane;                                                          \
-    lb.lut = (SpreadLut)p.spread_lut; lb.lut_vec = p.spread_lut;                                        \
-    lb.sbx = vct_spread3((uint32_t)lane & 3u);                               \
-    lb.sby = vct_spread3(((uint32_t)lane >> 2) & 3u) << 1;                   \
-    lb.sbz = vct_spread3((uint32_t)lane >> 4) << 2;                          \
+    const LaneBlock lb = make_lane_block(p, lane);                           \
     MarchStats ms = {};
 
 // compaction of one brick into `list` (LDS); returns the number of occupied voxels
@@ -1348,7 +1284,7 @@ k_compact_tiles(const VctTraceParams p) {
             const float a = p.gbuf[(size_t)tiles[k] * (VCT_GB_NPLANES * VCT_TILE_PIX) + 18 * VCT_TILE_PIX + lane];
             live = in_frame && !(a < 0.5f);
             if (in_frame && !live) {
-                const float cc = p.ambient < 0.5f ? 0.5f : 1.0f;
+                const float cc = clear_colour(p);
                 uint2 pk;
                 pk.x = pack_half2(cc, cc);
                 pk.y = pack_half2(cc, 1.0f);
@@ -1391,8 +1327,10 @@ void launch_split(const VctTraceParams& p, int blocks, hipStream_t s) {
     else hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, false, COMP>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
 }
 
+// `loose`: vct_launch_trace's decision to run variant 3's kernel
 template <bool WRAP, int FASTDIV>
-hipError_t launch_v(const VctTraceParams& p, int variant, int ntiles, hipStream_t s) {
+hipError_t launch_v(const VctTraceParams& p, int variant, bool loose, hipStream_t s) {
+    const int ntiles = p.ntiles;
     if (!p.aniso && (variant == 1 || variant == 2)) {      // the anisotropic option exists in the default kernel only
         const int nblocks = (ntiles + VCT_WAVES_PER_BLOCK - 1) / VCT_WAVES_PER_BLOCK;
         const int blocks = ((nblocks + 7) / 8) * 8;     // whole rounds of the 8 XCDs
@@ -1408,7 +1346,7 @@ hipError_t launch_v(const VctTraceParams& p, int variant, int ntiles, hipStream_
     }
     // variant 3: the default kernel with the one-multiply decode and reciprocal-multiply divisions -- never the default,
     // not bit-exact; it exists to price the exactness (bench.py exactness_tax)
-    if (variant == 3 && !p.aniso) {
+    if (loose) {
         hipLaunchKernelGGL((k_trace_tile_split<WRAP, 2, false>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
         return hipGetLastError();
     }
@@ -1495,16 +1433,24 @@ hipError_t vct_launch_bounce(const VctTraceParams& p, hipStream_t s) {
     return p.fast_div ? launch_bounce<false, true>(p, s) : launch_bounce<false, false>(p, s);
 }
 
-// variant 0 (default): cooperative sampler, each tile split over 3 waves; 2: cooperative sampler, one
-// wave per tile; 1: per-lane sampler only, one wave per tile.
-hipError_t vct_launch_trace(const VctTraceParams& p, int variant, hipStream_t s) {
+// The screen trace of tile rows [tile_row0, tile_row1) (every row_stride-th of them).  variant = config.trace_variant
+// (include/vct.h): 0 (default) the cooperative sampler with each tile split over 3 waves; 1 the per-lane sampler only and
+// 2 the cooperative sampler, one wave per tile (k_trace_tile; with anisotropic chains both run the default kernel);
+// 3 the default kernel with reciprocal-multiply divisions and the one-multiply decode, not bit-exact (with anisotropic
+// chains: the default kernel); 4 the default kernel over the live-pixel compaction (p.vt_pix set by the caller).
+// p.ntiles is set here.  *march_form (optional) receives the division form of the launch as vct_get_stage_counts reports
+// it -- 1 IEEE, 2 the verified product, 3 variant 3's x * r -- also for an empty row range, which launches nothing.
+hipError_t vct_launch_trace(const VctTraceParams& params, int variant, hipStream_t s, int* march_form) {
+    VctTraceParams p = params;
     const int rstride = p.row_stride > 1 ? p.row_stride : 1;
-    const int ntiles = ((p.tile_row1 - p.tile_row0 + rstride - 1) / rstride) * p.tiles_x;
-    if (ntiles <= 0) return hipSuccess;
-    if ((rstride > 1 || p.pack_rows) && (variant == 1 || variant == 2 || variant == 4)) return hipErrorInvalidValue;   // the default kernel only
+    p.ntiles = ((p.tile_row1 - p.tile_row0 + rstride - 1) / rstride) * p.tiles_x;
+    const bool loose = variant == 3 && !p.aniso;
+    if (march_form) *march_form = loose ? 3 : (p.fast_div ? 2 : 1);
+    if (p.ntiles <= 0) return hipSuccess;
+    if ((rstride > 1 || p.pack_rows) && !vct_variant_takes_row_subsets(variant)) return hipErrorInvalidValue;
     if (p.wrap_repeat)
-        return p.fast_div ? launch_v<true, true>(p, variant, ntiles, s)
-                          : launch_v<true, false>(p, variant, ntiles, s);
-    return p.fast_div ? launch_v<false, true>(p, variant, ntiles, s)
-                      : launch_v<false, false>(p, variant, ntiles, s);
+        return p.fast_div ? launch_v<true, true>(p, variant, loose, s)
+                          : launch_v<true, false>(p, variant, loose, s);
+    return p.fast_div ? launch_v<false, true>(p, variant, loose, s)
+                      : launch_v<false, false>(p, variant, loose, s);
 }

@@ -35,6 +35,81 @@ __device__ __forceinline__ void xform4(const float* m, float x, float y, float z
     for (int r = 0; r < 4; ++r) out[r] = m[r] * x + m[4 + r] * y + m[8 + r] * z + m[12 + r];
 }
 
+// ---- wave idioms (64 lanes; called by the whole wave, wave_group_by_key by any set of lanes) ----
+// this lane's rank among the set bits of a ballot mask: the number of set bits below it
+__device__ __forceinline__ uint32_t lane_rank(unsigned long long m) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+// inclusive prefix sum over the wave's lanes; lane 63 holds the total
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane) {
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t t = __shfl_up(v, off);
+        if (lane >= off) v += t;
+    }
+    return v;
+}
+// One leader per distinct key among the wave's valid lanes (keys below 0xffffffff), so that lanes bound for one
+// address send ONE atomic: `count` is the size of the group on its leader and 0 on its other lanes, `leader` and `rank`
+// place a lane behind what its leader reserved.  At most ROUNDS distinct keys are grouped, and the election stops
+// after two groups of one in a row (no crowding here: it would cost more than the atomics it saves); lanes left over
+// are leaders of themselves.
+struct KeyGroup { uint32_t count, rank; int leader; };
+template <int ROUNDS>
+__device__ __forceinline__ KeyGroup wave_group_by_key(uint32_t key, bool valid, int lane) {
+    const uint32_t want = valid ? key : 0xffffffffu;
+    KeyGroup g;
+    g.count = 0u; g.rank = 0u; g.leader = lane;
+    unsigned long long left = __builtin_amdgcn_ballot_w64(valid);
+    int singles = 0;
+    for (int round = 0; round < ROUNDS && left != 0ull && singles < 2; ++round) {
+        const int l = (int)__ffsll((long long)left) - 1;
+        const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)want, l);
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(want == b);
+        if (want == b) { g.leader = l; g.rank = lane_rank(m); }
+        if (lane == l) g.count = (uint32_t)__popcll(m);
+        singles = (m & (m - 1ull)) == 0ull ? singles + 1 : 0;
+        left &= ~m;
+    }
+    if ((left >> lane) & 1ull) g.count = 1u;
+    return g;
+}
+// One 64-bit atomic reserves room in two lists at once for the whole wave: `lo_add` / `hi_add` (wave-uniform) go to
+// the low / high word of `counter` (neither can carry into the other: the callers' lists are bounded well below 2^32),
+// the old values come back as the wave's bases.
+struct Reserve2 { uint32_t lo, hi; };
+__device__ __forceinline__ Reserve2 wave_reserve2(uint32_t* counter, uint32_t lo_add, uint32_t hi_add, int lane) {
+    unsigned long long base = 0ull;
+    if ((lo_add | hi_add) != 0u) {       // wave-uniform
+        if (lane == 0) base = atomicAdd(reinterpret_cast<unsigned long long*>(counter),
+                                        (unsigned long long)lo_add | ((unsigned long long)hi_add << 32));
+        base = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32)) << 32) |
+               (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
+    }
+    Reserve2 r;
+    r.lo = (uint32_t)base; r.hi = (uint32_t)(base >> 32);
+    return r;
+}
+// The same for a workgroup of four waves, with ONE atomic: the waves pool their counts in LDS, thread 0 reserves for
+// all, every wave gets its own bases.  Two barriers: every thread of the workgroup calls it.
+__device__ __forceinline__ Reserve2 block_reserve2(uint32_t* counter, uint32_t lo_add, uint32_t hi_add,
+                                                   uint32_t (*lds_cnt)[2], unsigned long long* lds_base) {
+    const int wv = (int)(threadIdx.x >> 6);
+    if ((threadIdx.x & 63) == 0) { lds_cnt[wv][0] = lo_add; lds_cnt[wv][1] = hi_add; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t tl = 0u, th = 0u;
+        for (int w = 0; w < 4; ++w) { tl += lds_cnt[w][0]; th += lds_cnt[w][1]; }
+        *lds_base = (tl | th) ? atomicAdd(reinterpret_cast<unsigned long long*>(counter),
+                                          (unsigned long long)tl | ((unsigned long long)th << 32)) : 0ull;
+    }
+    __syncthreads();
+    const unsigned long long base = *lds_base;
+    Reserve2 r;
+    r.lo = (uint32_t)base; r.hi = (uint32_t)(base >> 32);
+    for (int w = 0; w < wv; ++w) { r.lo += lds_cnt[w][0]; r.hi += lds_cnt[w][1]; }
+    return r;
+}
+
 // Near-plane clip (z >= -w) of a clip-space triangle.  A polygon vertex is lerp(in[a], in[b], t) (b < 0: a copy
 // of in[a]); every varying is interpolated the same way.  Nothing here is indexed at run time: a run-time index
 // puts the polygon into scratch memory, and with more than ~120 B of scratch per lane the runtime allocates the
@@ -199,7 +274,6 @@ __device__ __forceinline__ bool unpack_subtri(const SubTriRec& r, SubTri& s) {
     return true;
 }
 
-// pixel-centre coverage + barycentrics; returns false when the pixel is not covered
 // The three edge functions as plane equations, for the list consumers' inner loops: e_k(cx, cy) = a_k*cx + b_k*cy + c_k
 // with the top-left rule folded into c_k (an edge that does not own its boundary gets c_k - 2^-16, so that "inside" is
 // e'_k >= 0 for every edge; bias_k restores e_k for the barycentrics).  EXACT -- the same real numbers as the
@@ -235,6 +309,15 @@ __device__ __forceinline__ FastEdges slow_edges(const SubTri& s) {
     f.rcp = 1.0 / s.area;
     return f;
 }
+// top-left rule: does the edge of direction (dx, dy) own the pixel centres that lie exactly on it?
+__device__ __forceinline__ bool top_left(double dx, double dy) { return (dy > 0.0) || (dy == 0.0 && dx < 0.0); }
+// Edge function k (opposite vertex k) at (cx, cy) in the general form -- the difference of products the oracle states
+// -- and the edge's direction.
+__device__ __forceinline__ double edge_general(const SubTri& s, int k, double cx, double cy, double& dx, double& dy) {
+    const int i = (k + 1) % 3, j = (k + 2) % 3;
+    dx = (s.sx[j] - s.sx[i]) * s.sgn; dy = (s.sy[j] - s.sy[i]) * s.sgn;
+    return dx * (cy - s.sy[i]) - dy * (cx - s.sx[i]);
+}
 __device__ __forceinline__ void make_fast(const SubTri& s, FastEdges& f) {
     f.ok = true;
 #pragma unroll
@@ -243,8 +326,7 @@ __device__ __forceinline__ void make_fast(const SubTri& s, FastEdges& f) {
     for (int k = 0; k < 3; ++k) {
         const int i = (k + 1) % 3, j = (k + 2) % 3;
         const double dx = (s.sx[j] - s.sx[i]) * s.sgn, dy = (s.sy[j] - s.sy[i]) * s.sgn;
-        const bool top_left = (dy > 0.0) || (dy == 0.0 && dx < 0.0);
-        f.bias[k] = top_left ? 0.0 : 0x1p-16;
+        f.bias[k] = top_left(dx, dy) ? 0.0 : 0x1p-16;
         f.a[k] = -dy;
         f.b[k] = dx;
         f.c[k] = (dy * s.sx[i] - dx * s.sy[i]) - f.bias[k];
@@ -252,40 +334,67 @@ __device__ __forceinline__ void make_fast(const SubTri& s, FastEdges& f) {
     f.rcp = 1.0 / s.area;
 }
 
+// Edge functions of the sub-triangle at the centre of pixel (px, py): inside?, and the first two (unbiased) for the
+// barycentrics.  Pixels outside the triangle get their values too: in the binned form they are the helper invocations
+// of the alpha test's texture fetch.
+template <bool FAST>
+__device__ __forceinline__ bool edges_at(const SubTri& s, const FastEdges& f, int px, int py, double& e0, double& e1) {
+    const double cx = (double)px + 0.5, cy = (double)py + 0.5;
+    double e[3];
+    bool in = true;
+    if (FAST) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) e[k] = fma(f.a[k], cx, fma(f.b[k], cy, f.c[k]));
+        in = !(e[0] < 0.0 || e[1] < 0.0 || e[2] < 0.0);
+        // (an edge function that is exactly zero may come out as +0 here and as -0 in the general form, or the other
+        // way round.  The plane-equation form is only used for visibility, whose results are the depth -- normalised in
+        // depth_from_edges, and a zero product never changes a non-zero sum -- and the alpha test, which a zero's sign
+        // cannot change either; k_gbuffer_shade, whose interpolated attributes DO keep the sign of a zero, uses the
+        // general form.)
+        e0 = e[0] + f.bias[0];
+        e1 = e[1] + f.bias[1];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            double dx, dy;
+            e[k] = edge_general(s, k, cx, cy, dx, dy);
+            if (e[k] < 0.0 || (e[k] == 0.0 && !top_left(dx, dy))) in = false;
+        }
+        e0 = e[0];
+        e1 = e[1];
+    }
+    return in;
+}
+// barycentrics and depth from the first two edge functions; false: the depth is outside [0, 1)
+__device__ __forceinline__ bool depth_from_edges(double e0, double e1, double area, double rcp, const float sz[3],
+                                                 float& b0, float& b1, float& b2, float& z) {
+    b0 = (float)div_area(e0, area, rcp);
+    b1 = (float)div_area(e1, area, rcp);
+    b2 = 1.0f - b0 - b1;
+    z = b0 * sz[0] + b1 * sz[1] + b2 * sz[2];
+    z = z + 0.0f;      // -0 -> +0: depth is ordered through its bit pattern
+    // far-plane clip (and NaN); z == 1 can never pass "LESS" against a depth buffer cleared to 1
+    return z >= 0.0f && z < 1.0f;
+}
 // pixel-centre coverage + barycentrics; returns false when the pixel is not covered
 template <bool FAST>
 __device__ __forceinline__ bool cover(const SubTri& s, const FastEdges& f, int px, int py, float& b0, float& b1,
                                       float& b2, float& z, double& e0, double& e1) {
-    const double cx = (double)px + 0.5, cy = (double)py + 0.5;
-    double e[3];
     if (FAST) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) e[k] = fma(f.a[k], cx, fma(f.b[k], cy, f.c[k]));
-        if (e[0] < 0.0 || e[1] < 0.0 || e[2] < 0.0) return false;
-        // (an edge function that is exactly zero may come out as +0 here and as -0 in the general form, or the other
-        // way round.  The plane-equation form is only used by plot(), whose results are the depth -- normalised below,
-        // and a zero product never changes a non-zero sum -- and the alpha test, which a zero's sign cannot change
-        // either; k_gbuffer_shade, whose interpolated attributes DO keep the sign of a zero, uses the general form.)
-        e[0] += f.bias[0];
-        e[1] += f.bias[1];
+        if (!edges_at<true>(s, f, px, py, e0, e1)) return false;
     } else {
+        // edges_at<false> with a return at the first edge that fails: the in-place loops of the direct form spend many
+        // of their pixels outside the triangle, and k_gbuffer_shade keeps the code it had
+        const double cx = (double)px + 0.5, cy = (double)py + 0.5;
+        double e[3], dx, dy;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const int a = (k + 1) % 3, b = (k + 2) % 3;
-            const double dx = (s.sx[b] - s.sx[a]) * s.sgn, dy = (s.sy[b] - s.sy[a]) * s.sgn;
-            e[k] = dx * (cy - s.sy[a]) - dy * (cx - s.sx[a]);
-            const bool top_left = (dy > 0.0) || (dy == 0.0 && dx < 0.0);
-            if (e[k] < 0.0 || (e[k] == 0.0 && !top_left)) return false;
+            e[k] = edge_general(s, k, cx, cy, dx, dy);
+            if (e[k] < 0.0 || (e[k] == 0.0 && !top_left(dx, dy))) return false;
         }
+        e0 = e[0]; e1 = e[1];
     }
-    b0 = (float)div_area(e[0], s.area, f.rcp);
-    b1 = (float)div_area(e[1], s.area, f.rcp);
-    e0 = e[0]; e1 = e[1];
-    b2 = 1.0f - b0 - b1;
-    z = b0 * s.sz[0] + b1 * s.sz[1] + b2 * s.sz[2];
-    z = z + 0.0f;      // -0 -> +0: depth is ordered through its bit pattern below
-    // far-plane clip (and NaN); z == 1 can never pass "LESS" against a depth buffer cleared to 1
-    return z >= 0.0f && z < 1.0f;
+    return depth_from_edges(e0, e1, s.area, f.rcp, s.sz, b0, b1, b2, z);
 }
 
 // vct_selftest_area_divide: div_area next to the IEEE division on `count` pseudo-random (x, area) pairs -- integers of
@@ -330,13 +439,9 @@ __device__ __forceinline__ void interp2_from(const SubTri& s, double q0, double 
 __device__ __forceinline__ void interp2_at(const SubTri& s, double rcp, int qx, int qy, const float a[3],
                                            const float b[3], float& oa, float& ob) {
     const double cx = (double)qx + 0.5, cy = (double)qy + 0.5;
-    double f[2];
+    double f[2], dx, dy;
 #pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const int i = (k + 1) % 3, j = (k + 2) % 3;
-        const double dx = (s.sx[j] - s.sx[i]) * s.sgn, dy = (s.sy[j] - s.sy[i]) * s.sgn;
-        f[k] = dx * (cy - s.sy[i]) - dy * (cx - s.sx[i]);
-    }
+    for (int k = 0; k < 2; ++k) f[k] = edge_general(s, k, cx, cy, dx, dy);
     interp2_from(s, div_area(f[0], s.area, rcp), div_area(f[1], s.area, rcp), a, b, oa, ob);
 }
 
@@ -389,10 +494,7 @@ __device__ __forceinline__ void load_clip_tri(const RasterParams& p, int t, RVer
 #endif
 #define VCT_RTILE 16             // larger: cut into 16x16-pixel work items by the wave that met the triangle
 
-// Decides how fragments of triangle t are alpha-tested and, for the per-fragment case, loads the texture
-// coordinates of the sub-triangle's three vertices (fan == null: the unclipped triangle; otherwise the vertices
-// of the near-clipped polygon's fan sub-triangle, interpolated like every other varying).
-// what setup_alpha derives per triangle: alpha_mode | (texture + 1) << 2
+// how the fragments of triangle t are alpha-tested: alpha_mode | (texture + 1) << 2
 __device__ __forceinline__ int alpha_class(const RasterParams& p, int t) {
     const int m = p.material[t];
     const int td = vct_tex_of(p.tex, m, 0);
@@ -406,6 +508,9 @@ k_tri_alpha(const RasterParams p, int32_t* __restrict__ out) {
     if (t < p.ntri) out[t] = alpha_class(p, t);
 }
 
+// Sets the sub-triangle's alpha test from the triangle's class and, for the per-fragment case, loads the texture
+// coordinates of its three vertices (fan == null: the unclipped triangle; otherwise the vertices of the near-clipped
+// polygon's fan sub-triangle, interpolated like every other varying).
 // `pre`: the triangle's word of tri_alpha when the caller has already loaded it (>= 0), else -1
 __device__ __forceinline__ void setup_alpha(const RasterParams& p, int t, const FanTri* fan, SubTri& s, int pre = -1) {
     if (!p.material) return;
@@ -487,8 +592,54 @@ __device__ __forceinline__ TileBox tile_box(const SubTri& s) {
     return t;
 }
 
-// forward: the sub-triangle of a list entry, rebuilt from the mesh
-__device__ __forceinline__ bool rebuild_subtri(const RasterParams& p, int id, SubTri& s);
+// the pixels [x0, x1] x [y0, y1] of sub-triangle `id`, one after the other, by the calling lane (general form)
+__device__ __forceinline__ void plot_box(const RasterParams& p, const SubTri& s, int x0, int x1, int y0, int y1, int id) {
+    const FastEdges fe = slow_edges(s);
+    for (int py = y0; py <= y1; ++py)
+        for (int px = x0; px <= x1; ++px) plot<false>(p, s, fe, px, py, (unsigned long long)(uint32_t)id);
+}
+
+// The per-triangle front end of every stage that sets a triangle up: clip-space vertices, the near-clipped polygon
+// (a fan of at most two sub-triangles; an unclipped triangle is the one sub-triangle of a polygon with n = 3 whose
+// vertices are not used) and the alpha class.
+struct TriFront {
+    RVert in[3];
+    ClipPoly poly;
+    bool whole;          // no vertex behind the near plane
+    int acls;            // the triangle's word of tri_alpha, -1: not loaded
+};
+// (!valid: no triangle, n = 0)
+__device__ __forceinline__ void tri_front(const RasterParams& p, int t, bool valid, TriFront& f) {
+    f.poly.n = 0;
+    f.whole = false;
+    f.acls = -1;
+    if (valid) {
+        if (p.material && p.tri_alpha) f.acls = p.tri_alpha[t];      // requested with the positions
+        load_clip_tri(p, t, f.in);
+        f.whole = unclipped(f.in);
+        f.poly.n = 3;
+        if (!f.whole) clip_near(f.in, f.poly);
+    }
+    if (f.whole || !valid) {
+        f.poly.p0.v.c[0] = f.poly.p0.v.c[1] = f.poly.p0.v.c[2] = f.poly.p0.v.c[3] = 0.0f;
+        f.poly.p0.a = 0; f.poly.p0.b = -1; f.poly.p0.t = 0.0f;
+        f.poly.p1 = f.poly.p0; f.poly.p2 = f.poly.p0; f.poly.p3 = f.poly.p0;
+    }
+}
+// set-up of fan sub-triangle i (1 or 2; i + 1 < poly.n) of triangle t, with its alpha test
+__device__ __forceinline__ void front_subtri(const RasterParams& p, int t, const TriFront& f, int i, SubTri& s) {
+    const FanTri fan = fan_tri(f.poly, i);
+    if (f.whole) setup_subtri(&f.in[0], &f.in[1], &f.in[2], p.W, p.H, p.ys0, p.ys1, s);
+    else setup_subtri(&fan.v[0].v, &fan.v[1].v, &fan.v[2].v, p.W, p.H, p.ys0, p.ys1, s);
+    if (s.ok) setup_alpha(p, t, f.whole ? nullptr : &fan, s, f.acls);
+}
+// the sub-triangle of a list entry, rebuilt from the mesh
+__device__ __forceinline__ bool rebuild_subtri(const RasterParams& p, int id, SubTri& s) {
+    TriFront f;
+    tri_front(p, id >> 1, true, f);
+    front_subtri(p, id >> 1, f, (id & 1) + 1, s);
+    return s.ok;
+}
 
 // A huge sub-triangle met by one lane of k_raster_vis is cut into 16x16-pixel work items by the whole wave:
 // one atomic reserves the item range, the 64 lanes write the items (a full-screen Cornell wall at 1080p is
@@ -508,23 +659,9 @@ __device__ __forceinline__ void emit_big_wave(const RasterParams& p, int id, int
             p.items[slot] = make_uint2((uint32_t)id, ((uint32_t)ty << 16) | (uint32_t)tx);
             continue;
         }
-        const int x0 = max(s.x0, tx * VCT_RTILE), x1 = min(s.x1, tx * VCT_RTILE + VCT_RTILE - 1);
-        const int y0 = max(s.y0, ty * VCT_RTILE), y1 = min(s.y1, ty * VCT_RTILE + VCT_RTILE - 1);
-        const FastEdges fe = slow_edges(s);
-        for (int py = y0; py <= y1; ++py)
-            for (int px = x0; px <= x1; ++px) plot<false>(p, s, fe, px, py, (unsigned long long)(uint32_t)id);
+        plot_box(p, s, max(s.x0, tx * VCT_RTILE), min(s.x1, tx * VCT_RTILE + VCT_RTILE - 1),
+                 max(s.y0, ty * VCT_RTILE), min(s.y1, ty * VCT_RTILE + VCT_RTILE - 1), id);
     }
-}
-
-// Wave-aggregated list append, called by all 64 lanes: the slot of this lane's entry (meaningful where `pred`).
-__device__ __forceinline__ uint32_t wave_append(uint32_t* counter, bool pred, int lane) {
-    const unsigned long long m = __builtin_amdgcn_ballot_w64(pred);
-    if (m == 0ull) return 0u;
-    const int leader = (int)__ffsll((long long)m) - 1;
-    uint32_t base = 0u;
-    if (lane == leader) base = atomicAdd(counter, (uint32_t)__popcll(m));
-    base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
-    return base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 
 // one thread per triangle: clip, cull, classify; tiny sub-triangles are rasterised inline, huge ones are cut into
@@ -540,23 +677,8 @@ k_raster_vis(const RasterParams p) {
     const int lane = threadIdx.x & 63;
     if (t == 0) { p.next_counts[0] = 0u; p.next_counts[1] = 0u; p.next_counts[2] = 0u; }
     const bool valid = t < p.ntri;          // no early return: the wave cooperates on huge triangles below
-    RVert in[3];
-    ClipPoly poly;
-    poly.n = 0;
-    bool whole = false;
-    int acls = -1;
-    if (valid) {
-        if (p.material && p.tri_alpha) acls = p.tri_alpha[t];      // requested with the positions
-        load_clip_tri(p, t, in);
-        whole = unclipped(in);
-        poly.n = 3;
-        if (!whole) clip_near(in, poly);
-    }
-    if (whole || !valid) {
-        poly.p0.v.c[0] = poly.p0.v.c[1] = poly.p0.v.c[2] = poly.p0.v.c[3] = 0.0f;
-        poly.p0.a = 0; poly.p0.b = -1; poly.p0.t = 0.0f;
-        poly.p1 = poly.p0; poly.p2 = poly.p0; poly.p3 = poly.p0;
-    }
+    TriFront tf;
+    tri_front(p, t, valid, tf);
     unsigned long long big1 = 0ull, big2 = 0ull;
 #pragma unroll
     for (int f = 1; f <= 2; ++f) {          // a near-clipped triangle is at most a quad: two sub-triangles
@@ -564,18 +686,13 @@ k_raster_vis(const RasterParams p) {
         const int id = t * 2 + (f - 1);
         SubTriRec rec;
         rec.alpha_tex = 0;
-        if (valid && f + 1 < poly.n) {
+        if (valid && f + 1 < tf.poly.n) {
             SubTri s;
-            const FanTri fan = fan_tri(poly, f);
-            if (whole) setup_subtri(&in[0], &in[1], &in[2], p.W, p.H, p.ys0, p.ys1, s);
-            else setup_subtri(&fan.v[0].v, &fan.v[1].v, &fan.v[2].v, p.W, p.H, p.ys0, p.ys1, s);
-            if (s.ok) setup_alpha(p, t, whole ? nullptr : &fan, s, acls);
+            front_subtri(p, t, tf, f, s);
             if (s.ok && s.alpha_mode != 1) {
                 const long long box = (long long)(s.x1 - s.x0 + 1) * (s.y1 - s.y0 + 1);
                 if (box <= VCT_RASTER_SMALL) {
-                    const FastEdges fe = slow_edges(s);
-                    for (int py = s.y0; py <= s.y1; ++py)
-                        for (int px = s.x0; px <= s.x1; ++px) plot<false>(p, s, fe, px, py, (unsigned long long)(uint32_t)id);
+                    plot_box(p, s, s.x0, s.x1, s.y0, s.y1, id);
                 } else if (box <= VCT_RASTER_GROUP) {
                     to_group = true;
                     pack_subtri(s, rec);
@@ -593,29 +710,12 @@ k_raster_vis(const RasterParams p) {
         // (round 3, found on the second bounce's list).  Now the workgroup's four waves pool their counts in LDS and
         // ONE 64-bit atomic reserves both lists for all 256 triangles (wave count low, group count high: neither can
         // carry, the lists hold at most 2 * ntri entries).  The second sub-triangle exists only for near-clipped
-        // triangles: rare, it keeps the per-wave append.
-        uint32_t gslot, wslot;
-        if (f == 1) {
-            const unsigned long long mg = __builtin_amdgcn_ballot_w64(to_group), mw = __builtin_amdgcn_ballot_w64(to_wave);
-            const int wv = (int)(threadIdx.x >> 6);
-            if (lane == 0) { lds_cnt[wv][0] = (uint32_t)__popcll(mg); lds_cnt[wv][1] = (uint32_t)__popcll(mw); }
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                uint32_t tg = 0u, tw = 0u;
-                for (int w = 0; w < 4; ++w) { tg += lds_cnt[w][0]; tw += lds_cnt[w][1]; }
-                lds_base = (tg | tw) ? atomicAdd(reinterpret_cast<unsigned long long*>(p.wave_count),
-                                                 (unsigned long long)tw | ((unsigned long long)tg << 32)) : 0ull;
-            }
-            __syncthreads();
-            const unsigned long long base = lds_base;
-            uint32_t gb = (uint32_t)(base >> 32), wb = (uint32_t)base;
-            for (int w = 0; w < wv; ++w) { gb += lds_cnt[w][0]; wb += lds_cnt[w][1]; }
-            gslot = gb + __builtin_amdgcn_mbcnt_hi((uint32_t)(mg >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mg, 0u));
-            wslot = wb + __builtin_amdgcn_mbcnt_hi((uint32_t)(mw >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mw, 0u));
-        } else {
-            gslot = wave_append(p.group_count, to_group, lane);
-            wslot = wave_append(p.wave_count, to_wave, lane);
-        }
+        // triangles: rare, it keeps a per-wave reservation.
+        const unsigned long long mg = __builtin_amdgcn_ballot_w64(to_group), mw = __builtin_amdgcn_ballot_w64(to_wave);
+        const uint32_t ng = (uint32_t)__popcll(mg), nw = (uint32_t)__popcll(mw);
+        const Reserve2 base = f == 1 ? block_reserve2(p.wave_count, nw, ng, lds_cnt, &lds_base)
+                                     : wave_reserve2(p.wave_count, nw, ng, lane);
+        const uint32_t gslot = base.hi + lane_rank(mg), wslot = base.lo + lane_rank(mw);
         if (to_group) { p.group_list[gslot] = (int32_t)id; p.recs[gslot] = rec; }
         if (to_wave) { p.wave_list[wslot] = (int32_t)id; p.recs[(size_t)2 * p.ntri - 1 - wslot] = rec; }
         if (f == 1) big1 = __builtin_amdgcn_ballot_w64(big); else big2 = __builtin_amdgcn_ballot_w64(big);
@@ -639,21 +739,29 @@ k_raster_vis(const RasterParams p) {
     }
 }
 
-__device__ __forceinline__ bool rebuild_subtri(const RasterParams& p, int id, SubTri& s) {
-    const int t = id >> 1, f = (id & 1) + 1;
-    RVert in[3];
-    load_clip_tri(p, t, in);
-    if (unclipped(in)) {
-        setup_subtri(&in[0], &in[1], &in[2], p.W, p.H, p.ys0, p.ys1, s);
-        if (s.ok) setup_alpha(p, t, nullptr, s);
-        return s.ok;
+// One listed sub-triangle by LANES lanes (`l`: this lane among them), which stride its bounding box; `rec`: its set-up
+// record in p.recs.
+template <int LANES>
+__device__ __forceinline__ void raster_listed(const RasterParams& p, int id, size_t rec, int l) {
+    SubTri s;
+    if (!unpack_subtri(p.recs[rec], s) && !rebuild_subtri(p, id, s)) return;
+    const int bw = s.x1 - s.x0 + 1;
+    const int box = bw * (s.y1 - s.y0 + 1);
+    FastEdges fe;
+    make_fast(s, fe);
+    // the box is walked in strides of LANES without a division per pixel: (x, y) advance by (LANES % bw, LANES / bw)
+    const int qs = LANES / bw, rs = LANES - qs * bw;
+    int x = l % bw, y = l / bw;
+    if (fe.ok) {
+        for (int i = l; i < box; i += LANES) {
+            plot<true>(p, s, fe, s.x0 + x, s.y0 + y, (unsigned long long)(uint32_t)id);
+            x += rs; y += qs;
+            if (x >= bw) { x -= bw; ++y; }
+        }
+    } else {
+        for (int i = l; i < box; i += LANES)
+            plot<false>(p, s, fe, s.x0 + i % bw, s.y0 + i / bw, (unsigned long long)(uint32_t)id);
     }
-    ClipPoly poly;
-    clip_near(in, poly);
-    const FanTri fan = fan_tri(poly, f);
-    setup_subtri(&fan.v[0].v, &fan.v[1].v, &fan.v[2].v, p.W, p.H, p.ys0, p.ys1, s);
-    if (s.ok) setup_alpha(p, t, &fan, s);
-    return s.ok;
 }
 
 // The three list consumers in ONE launch (they are independent of each other, and a dependent dispatch costs
@@ -673,28 +781,8 @@ k_raster_mid(const RasterParams p, const int gblocks, const int wblocks) {
         const uint32_t n = *p.group_count;
         const int l16 = threadIdx.x & 15;
         const uint32_t ngroups = ((uint32_t)gblocks * blockDim.x) >> 4;
-        for (uint32_t g = ((uint32_t)b * blockDim.x + threadIdx.x) >> 4; g < n; g += ngroups) {
-            const int id = p.group_list[g];
-            SubTri s;
-            if (!unpack_subtri(p.recs[g], s) && !rebuild_subtri(p, id, s)) continue;
-            const int bw = s.x1 - s.x0 + 1;
-            const int box = bw * (s.y1 - s.y0 + 1);
-            FastEdges fe;
-            make_fast(s, fe);
-            // the box is walked in strides of 16 without a division per pixel: (x, y) advance by (16 % bw, 16 / bw)
-            const int qs = 16 / bw, rs = 16 - qs * bw;
-            int x = l16 % bw, y = l16 / bw;
-            if (fe.ok) {
-                for (int i = l16; i < box; i += 16) {
-                    plot<true>(p, s, fe, s.x0 + x, s.y0 + y, (unsigned long long)(uint32_t)id);
-                    x += rs; y += qs;
-                    if (x >= bw) { x -= bw; ++y; }
-                }
-            } else {
-                for (int i = l16; i < box; i += 16)
-                    plot<false>(p, s, fe, s.x0 + i % bw, s.y0 + i / bw, (unsigned long long)(uint32_t)id);
-            }
-        }
+        for (uint32_t g = ((uint32_t)b * blockDim.x + threadIdx.x) >> 4; g < n; g += ngroups)
+            raster_listed<16>(p, p.group_list[g], g, l16);
         return;
     }
     b -= gblocks;
@@ -702,27 +790,8 @@ k_raster_mid(const RasterParams p, const int gblocks, const int wblocks) {
         const uint32_t n = *p.wave_count;
         const int lane = threadIdx.x & 63;
         const uint32_t nwaves = ((uint32_t)wblocks * blockDim.x) >> 6;
-        for (uint32_t w = ((uint32_t)b * blockDim.x + threadIdx.x) >> 6; w < n; w += nwaves) {
-            const int id = p.wave_list[w];
-            SubTri s;
-            if (!unpack_subtri(p.recs[(size_t)2 * p.ntri - 1 - w], s) && !rebuild_subtri(p, id, s)) continue;
-            const int bw = s.x1 - s.x0 + 1;
-            const int box = bw * (s.y1 - s.y0 + 1);
-            FastEdges fe;
-            make_fast(s, fe);
-            const int qs = 64 / bw, rs = 64 - qs * bw;
-            int x = lane % bw, y = lane / bw;
-            if (fe.ok) {
-                for (int i = lane; i < box; i += 64) {
-                    plot<true>(p, s, fe, s.x0 + x, s.y0 + y, (unsigned long long)(uint32_t)id);
-                    x += rs; y += qs;
-                    if (x >= bw) { x -= bw; ++y; }
-                }
-            } else {
-                for (int i = lane; i < box; i += 64)
-                    plot<false>(p, s, fe, s.x0 + i % bw, s.y0 + i / bw, (unsigned long long)(uint32_t)id);
-            }
-        }
+        for (uint32_t w = ((uint32_t)b * blockDim.x + threadIdx.x) >> 6; w < n; w += nwaves)
+            raster_listed<64>(p, p.wave_list[w], (size_t)2 * p.ntri - 1 - w, lane);
         return;
     }
     b -= wblocks;
@@ -861,6 +930,21 @@ __device__ __forceinline__ void pack_binrec(const SubTri& s, const FastEdges& fe
     const float lb = (lo > -2.0f && lo < 2.0f) ? lo - 4e-6f : 0.0f;
     r.zmin_bits = lb > 0.0f ? __float_as_uint(lb) : 0u;
 }
+// FastEdges::bias[k] of a record, from its flags
+__device__ __forceinline__ double binrec_bias(uint32_t flags, int k) { return ((flags >> (28 + k)) & 1u) ? 0x1p-16 : 0.0; }
+
+// the bins a bounding box overlaps: the first one, bins per row, bins in all (row by row)
+struct BinBox { int bx0, by0, bw, nb; };
+__device__ __forceinline__ BinBox bin_box(int x0, int x1, int y0, int y1) {
+    BinBox b;
+    b.bx0 = x0 >> VCT_BIN_SHIFT; b.by0 = y0 >> VCT_BIN_SHIFT;
+    b.bw = (x1 >> VCT_BIN_SHIFT) - b.bx0 + 1;
+    b.nb = b.bw * ((y1 >> VCT_BIN_SHIFT) - b.by0 + 1);
+    return b;
+}
+__device__ __forceinline__ BinBox bin_box(uint32_t xx, uint32_t yy) {       // of a record's xx, yy
+    return bin_box((int)(xx & 0xffffu), (int)(xx >> 16), (int)(yy & 0xffffu), (int)(yy >> 16));
+}
 
 // Which of the (at most VCT_BIN_INLINE) bins of its bounding box does the sub-triangle itself reach?  A bin is dropped
 // when one edge function is negative on every pixel centre of the bin's part of the box -- its largest value over that
@@ -894,29 +978,14 @@ k_bin_setup(const BinParams p) {
     __shared__ uint32_t lds_cnt[4][2];
     __shared__ unsigned long long lds_base;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    const int lane = threadIdx.x & 63, wv = (int)(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
     if (t == 0) {
 #pragma unroll
         for (int k = 0; k < 8; ++k) p.next_ctr[k] = 0u;
     }
     const bool valid = t < p.r.ntri;
-    RVert in[3];
-    ClipPoly poly;
-    poly.n = 0;
-    bool whole = false;
-    int acls = -1;
-    if (valid) {
-        if (p.r.material && p.r.tri_alpha) acls = p.r.tri_alpha[t];      // requested with the positions
-        load_clip_tri(p.r, t, in);
-        whole = unclipped(in);
-        poly.n = 3;
-        if (!whole) clip_near(in, poly);
-    }
-    if (whole || !valid) {
-        poly.p0.v.c[0] = poly.p0.v.c[1] = poly.p0.v.c[2] = poly.p0.v.c[3] = 0.0f;
-        poly.p0.a = 0; poly.p0.b = -1; poly.p0.t = 0.0f;
-        poly.p1 = poly.p0; poly.p2 = poly.p0; poly.p3 = poly.p0;
-    }
+    TriFront tf;
+    tri_front(p.r, t, valid, tf);
     // sub-triangles whose bins the wave counts together (more than VCT_BIN_INLINE): first bin, bins per row | bins
     unsigned long long coop[2] = {0ull, 0ull};
     uint32_t coop_b0[2] = {0u, 0u}, coop_wn[2] = {0u, 0u};
@@ -927,19 +996,12 @@ k_bin_setup(const BinParams p) {
         bool have = false;
         SubTri s;
         s.ok = false;
-        if (valid && f + 1 < poly.n) {
-            const FanTri fan = fan_tri(poly, f);
-            if (whole) setup_subtri(&in[0], &in[1], &in[2], p.r.W, p.r.H, p.r.ys0, p.r.ys1, s);
-            else setup_subtri(&fan.v[0].v, &fan.v[1].v, &fan.v[2].v, p.r.W, p.r.H, p.r.ys0, p.r.ys1, s);
-            if (s.ok) setup_alpha(p.r, t, whole ? nullptr : &fan, s, acls);
+        if (valid && f + 1 < tf.poly.n) {
+            front_subtri(p.r, t, tf, f, s);
             have = s.ok && s.alpha_mode != 1;
         }
-        int bx0 = 0, by0 = 0, bw = 0, nb = 0;
-        if (have) {
-            bx0 = s.x0 >> VCT_BIN_SHIFT; by0 = s.y0 >> VCT_BIN_SHIFT;
-            bw = (s.x1 >> VCT_BIN_SHIFT) - bx0 + 1;
-            nb = bw * ((s.y1 >> VCT_BIN_SHIFT) - by0 + 1);
-        }
+        const BinBox bb = have ? bin_box(s.x0, s.x1, s.y0, s.y1) : BinBox{0, 0, 0, 0};
+        const int bx0 = bb.bx0, by0 = bb.by0, bw = bb.bw, nb = bb.nb;
         FastEdges fe;
         fe.ok = false;
         uint32_t binmask = 0xffffffffu;
@@ -956,39 +1018,11 @@ k_bin_setup(const BinParams p) {
         // after the other (~11 ns each): one 64-bit atomic per WORKGROUP (entries low, records high) for the first
         // sub-triangle; the second exists for near-clipped triangles only and keeps a per-wave reservation.
         const unsigned long long mh = __builtin_amdgcn_ballot_w64(have);
-        uint32_t incl = np;
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t v = __shfl_up(incl, off);
-            if (lane >= off) incl += v;
-        }
-        const uint32_t wave_ent = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-        uint32_t rslot, eslot;
-        if (f == 1) {
-            if (lane == 0) { lds_cnt[wv][0] = wave_ent; lds_cnt[wv][1] = (uint32_t)__popcll(mh); }
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                uint32_t te = 0u, tr = 0u;
-                for (int w = 0; w < 4; ++w) { te += lds_cnt[w][0]; tr += lds_cnt[w][1]; }
-                lds_base = (te | tr) ? atomicAdd(reinterpret_cast<unsigned long long*>(p.ctr),
-                                                 (unsigned long long)te | ((unsigned long long)tr << 32)) : 0ull;
-            }
-            __syncthreads();
-            const unsigned long long base = lds_base;
-            uint32_t eb = (uint32_t)base, rb = (uint32_t)(base >> 32);
-            for (int w = 0; w < wv; ++w) { eb += lds_cnt[w][0]; rb += lds_cnt[w][1]; }
-            eslot = eb + incl - np;
-            rslot = rb + __builtin_amdgcn_mbcnt_hi((uint32_t)(mh >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mh, 0u));
-        } else {
-            unsigned long long base = 0ull;
-            if (mh != 0ull) {       // wave-uniform
-                if (lane == 0) base = atomicAdd(reinterpret_cast<unsigned long long*>(p.ctr),
-                                                (unsigned long long)wave_ent | ((unsigned long long)__popcll(mh) << 32));
-                base = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32)) << 32) |
-                       (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
-            }
-            eslot = (uint32_t)base + incl - np;
-            rslot = (uint32_t)(base >> 32) + __builtin_amdgcn_mbcnt_hi((uint32_t)(mh >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mh, 0u));
-        }
+        const uint32_t incl = wave_incl_scan(np, lane);
+        const uint32_t wave_ent = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63), wave_rec = (uint32_t)__popcll(mh);
+        const Reserve2 base = f == 1 ? block_reserve2(p.ctr, wave_ent, wave_rec, lds_cnt, &lds_base)
+                                     : wave_reserve2(p.ctr, wave_ent, wave_rec, lane);
+        const uint32_t eslot = base.lo + incl - np, rslot = base.hi + lane_rank(mh);
         bool wave_bins = false;
         if (have) {
             if (rslot >= p.rec_cap) {
@@ -1009,18 +1043,7 @@ k_bin_setup(const BinParams p) {
                         for (int j = 0; j < nb; ++j) {
                             const uint32_t bin = (uint32_t)((by0 + by) * p.bins_x + bx0 + bx);
                             // the lanes still in this loop that count the same bin send ONE atomic (see k_bin_fill)
-                            uint32_t want = ((binmask >> j) & 1u) ? bin : 0xffffffffu, add = 0u;
-                            unsigned long long left = __builtin_amdgcn_ballot_w64(want != 0xffffffffu);
-                            int singles = 0;
-                            for (int round = 0; round < VCT_BIN_COUNT_AGG_ROUNDS && left != 0ull && singles < 2; ++round) {
-                                const int l = (int)__ffsll((long long)left) - 1;
-                                const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)want, l);
-                                const unsigned long long m = __builtin_amdgcn_ballot_w64(want == b);
-                                if (lane == l) add = (uint32_t)__popcll(m);
-                                singles = (m & (m - 1ull)) == 0ull ? singles + 1 : 0;
-                                left &= ~m;
-                            }
-                            if ((left >> lane) & 1ull) add = 1u;
+                            const uint32_t add = wave_group_by_key<VCT_BIN_COUNT_AGG_ROUNDS>(bin, (binmask >> j) & 1u, lane).count;
                             if (add != 0u) atomicAdd(&p.bin_count[(size_t)bin * VCT_BIN_CSTRIDE], add);
                             if (++bx == bw) { bx = 0; ++by; }
                         }
@@ -1058,9 +1081,7 @@ k_bin_setup(const BinParams p) {
         SubTri s;
         if (!rebuild_subtri(p.r, t * 2 + k, s)) continue;
         p.ctr[5] = 1u;
-        const FastEdges fe = slow_edges(s);
-        for (int py = s.y0; py <= s.y1; ++py)
-            for (int px = s.x0; px <= s.x1; ++px) plot<false>(p.r, s, fe, px, py, (unsigned long long)(uint32_t)(t * 2 + k));
+        plot_box(p.r, s, s.x0, s.x1, s.y0, s.y1, t * 2 + k);
     }
 }
 
@@ -1081,20 +1102,10 @@ k_bin_alloc(const BinParams p) {
     }
     // a bin without entries still gets one item while the huge list is not empty (a Cornell wall covers every bin)
     const uint32_t ni = n ? (n + VCT_BIN_SLICE - 1u) / VCT_BIN_SLICE : ((nhuge && rows) ? 1u : 0u);
-    uint32_t in_n = n, in_i = ni;
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t a = __shfl_up(in_n, off), b = __shfl_up(in_i, off);
-        if (lane >= off) { in_n += a; in_i += b; }
-    }
+    const uint32_t in_n = wave_incl_scan(n, lane), in_i = wave_incl_scan(ni, lane);
     const uint32_t tot_n = (uint32_t)__builtin_amdgcn_readlane((int)in_n, 63), tot_i = (uint32_t)__builtin_amdgcn_readlane((int)in_i, 63);
-    unsigned long long base = 0ull;
-    if (tot_i != 0u) {
-        if (lane == 0) base = atomicAdd(reinterpret_cast<unsigned long long*>(p.ctr + 2),
-                                        (unsigned long long)tot_i | ((unsigned long long)tot_n << 32));
-        base = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32)) << 32) |
-               (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
-    }
-    const uint32_t ebase = (uint32_t)(base >> 32) + in_n - n, ibase = (uint32_t)base + in_i - ni;
+    const Reserve2 base = wave_reserve2(p.ctr + 2, tot_i, tot_n, lane);       // (entries only come with items)
+    const uint32_t ebase = base.hi + in_n - n, ibase = base.lo + in_i - ni;
     if (bin < nbins) p.bin_cursor[(size_t)bin * VCT_BIN_CSTRIDE] = ebase;
     for (uint32_t sl = 0; sl < ni; ++sl) {
         const uint32_t at = ibase + sl;
@@ -1134,17 +1145,11 @@ k_bin_fill(const BinParams p) {
         uint32_t msk = 0u;
         if (rec < nrec) { q = *reinterpret_cast<const uint4*>(&p.recs[rec].flags); msk = p.recs[rec].binmask; }
         const bool binned = (q.x & VCT_BINREC_BINNED) != 0u;
-        const int bx0 = (int)(q.y & 0xffffu) >> VCT_BIN_SHIFT, by0 = (int)(q.z & 0xffffu) >> VCT_BIN_SHIFT;
-        const int bw = ((int)(q.y >> 16) >> VCT_BIN_SHIFT) - bx0 + 1;
-        const uint32_t nbox = (uint32_t)(bw * (((int)(q.z >> 16) >> VCT_BIN_SHIFT) - by0 + 1));
+        const uint32_t nbox = (uint32_t)bin_box(q.y, q.z).nb;
         // a record of at most VCT_BIN_INLINE bins has an entry in the bins of its mask, a larger one in every bin of its box
         const uint32_t nb = !binned ? 0u : (nbox <= VCT_BIN_INLINE ? (uint32_t)__popc(msk) : nbox);
         if (nbox > VCT_BIN_INLINE) msk = 0u;           // 0: "every bin"
-        uint32_t incl = nb;
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t v = __shfl_up(incl, off);
-            if (lane >= off) incl += v;
-        }
+        const uint32_t incl = wave_incl_scan(nb, lane);
         const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
         s_pre[wv][lane] = incl;                        // inclusive: pair k belongs to the first lane with incl > k
         s_hdr[wv][lane] = q;
@@ -1175,9 +1180,8 @@ k_bin_fill(const BinParams p) {
                         for (uint32_t i = 0; i < j; ++i) hm &= hm - 1u;
                         j = (uint32_t)__ffs((int)hm) - 1u;
                     }
-                    const int hx0 = (int)(h.y & 0xffffu) >> VCT_BIN_SHIFT, hy0 = (int)(h.z & 0xffffu) >> VCT_BIN_SHIFT;
-                    const int hw = ((int)(h.y >> 16) >> VCT_BIN_SHIFT) - hx0 + 1;
-                    const int by = hy0 + (int)j / hw, bx = hx0 + (int)j % hw;
+                    const BinBox hb = bin_box(h.y, h.z);
+                    const int by = hb.by0 + (int)j / hb.bw, bx = hb.bx0 + (int)j % hb.bw;
                     ent[u] = bin_entry(rec0 + (uint32_t)lo, h, bx, by, depth_only);
                     bin_of[u] = (uint32_t)(by * p.bins_x + bx);
                 }
@@ -1186,74 +1190,25 @@ k_bin_fill(const BinParams p) {
             // land in the same bins; atomics on one address execute one after the other in the L2): the lanes of a bin
             // elect a leader and take consecutive slots behind what it reserved.  The leaders' atomics of the four rounds
             // are all issued before any result is used.
-            int leader[4];
-            uint32_t rank[4], cnt[4];
+            // (where every pair of the wave has a bin of its own -- large triangles at 4K -- the election stops early)
+            KeyGroup grp[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                leader[u] = lane; rank[u] = 0u; cnt[u] = 0u;
-                unsigned long long left = __builtin_amdgcn_ballot_w64(bin_of[u] != 0xffffffffu);
-                // (at most VCT_BIN_FILL_AGG_ROUNDS distinct bins are grouped, and the election stops after two groups of one
-                // in a row; pairs left over take their own atomic: where every pair of the wave has a bin of its own --
-                // large triangles at 4K -- the election would cost more than the atomics it saves)
-                int singles = 0;
-                for (int round = 0; round < VCT_BIN_FILL_AGG_ROUNDS && left != 0ull && singles < 2; ++round) {
-                    const int l = (int)__ffsll((long long)left) - 1;
-                    const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)bin_of[u], l);
-                    const unsigned long long m = __builtin_amdgcn_ballot_w64(bin_of[u] == b);
-                    if (bin_of[u] == b) {
-                        leader[u] = l;
-                        rank[u] = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                    }
-                    if (lane == l) cnt[u] = (uint32_t)__popcll(m);
-                    singles = (m & (m - 1ull)) == 0ull ? singles + 1 : 0;     // two groups of one in a row: no crowding here
-                    left &= ~m;
-                }
-                if ((left >> lane) & 1ull) cnt[u] = 1u;       // not grouped: leader of itself
-            }
+            for (int u = 0; u < 4; ++u) grp[u] = wave_group_by_key<VCT_BIN_FILL_AGG_ROUNDS>(bin_of[u], bin_of[u] != 0xffffffffu, lane);
             uint32_t got[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 got[u] = 0u;
-                if (cnt[u] != 0u) got[u] = atomicAdd(&p.bin_cursor[(size_t)bin_of[u] * VCT_BIN_CSTRIDE], cnt[u]);
+                if (grp[u].count != 0u) got[u] = atomicAdd(&p.bin_cursor[(size_t)bin_of[u] * VCT_BIN_CSTRIDE], grp[u].count);
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                const uint32_t base = (uint32_t)__shfl((int)got[u], leader[u]);
-                if (bin_of[u] != 0xffffffffu) at[u] = base + rank[u];
+                const uint32_t base = (uint32_t)__shfl((int)got[u], grp[u].leader);
+                if (bin_of[u] != 0xffffffffu) at[u] = base + grp[u].rank;
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) p.entries[at[u] < p.entry_cap ? at[u] : p.entry_cap] = ent[u];
         }
     }
-}
-
-// edge functions of the sub-triangle at this lane's pixel centre: inside?, and the first two (unbiased) for the
-// barycentrics -- the arithmetic of cover<FAST>, split so that lanes outside the triangle keep their values too
-// (they are the helper invocations of the alpha test's texture fetch)
-template <bool FAST>
-__device__ __forceinline__ bool edges_at(const SubTri& s, const FastEdges& f, int px, int py, double& e0, double& e1) {
-    const double cx = (double)px + 0.5, cy = (double)py + 0.5;
-    double e[3];
-    bool in = true;
-    if (FAST) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) e[k] = fma(f.a[k], cx, fma(f.b[k], cy, f.c[k]));
-        in = !(e[0] < 0.0 || e[1] < 0.0 || e[2] < 0.0);
-        e0 = e[0] + f.bias[0];
-        e1 = e[1] + f.bias[1];
-    } else {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const int a = (k + 1) % 3, b = (k + 2) % 3;
-            const double dx = (s.sx[b] - s.sx[a]) * s.sgn, dy = (s.sy[b] - s.sy[a]) * s.sgn;
-            e[k] = dx * (cy - s.sy[a]) - dy * (cx - s.sx[a]);
-            const bool top_left = (dy > 0.0) || (dy == 0.0 && dx < 0.0);
-            if (e[k] < 0.0 || (e[k] == 0.0 && !top_left)) in = false;
-        }
-        e0 = e[0];
-        e1 = e[1];
-    }
-    return in;
 }
 
 __device__ __forceinline__ float dpp_quad_x(float v) {      // the value of lane ^ 1 (quad_perm [1,0,3,2])
@@ -1396,11 +1351,7 @@ k_bin_raster(const BinParams p) {
 #pragma unroll
                 for (int h = 0; h < 2 * VCT_BIN_BUCKETS; h += 64) {
                     const uint32_t v = s_bk[h + lane];
-                    uint32_t incl = v;
-                    for (int off = 1; off < 64; off <<= 1) {
-                        const uint32_t t = __shfl_up(incl, off);
-                        if (lane >= off) incl += t;
-                    }
+                    const uint32_t incl = wave_incl_scan(v, lane);
                     s_bk[h + lane] = carry + incl - v;
                     carry += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
                 }
@@ -1464,12 +1415,12 @@ k_bin_raster(const BinParams p) {
                 const float* F = reinterpret_cast<const float*>(R) + 22;   // sz[3], iw[3], tu[3], tv[3], id
                 bool in;
                 double e0, e1;
-                if (flags >> 31) {       // plane equations (every coordinate below 2^16)
+                if (flags >> 31) {       // plane equations (every coordinate below 2^16): edges_at<true> on the LDS broadcasts
                     const double f0 = fma(D[0], cx, fma(D[3], cy, D[6])), f1 = fma(D[1], cx, fma(D[4], cy, D[7]));
                     const double f2 = fma(D[2], cx, fma(D[5], cy, D[8]));
                     in = !(f0 < 0.0 || f1 < 0.0 || f2 < 0.0);
-                    e0 = f0 + (((flags >> 28) & 1u) ? 0x1p-16 : 0.0);
-                    e1 = f1 + (((flags >> 29) & 1u) ? 0x1p-16 : 0.0);
+                    e0 = f0 + binrec_bias(flags, 0);
+                    e1 = f1 + binrec_bias(flags, 1);
                 } else {                 // the general form on the snapped coordinates (sx in ea, sy in eb)
                     SubTri s;
                     FastEdges fe;
@@ -1480,12 +1431,8 @@ k_bin_raster(const BinParams p) {
                 }
                 const bool cov = in && open;
                 if (__builtin_amdgcn_ballot_w64(cov) == 0ull) continue;
-                const double area = D[9], rcp = D[10];
-                const float b0 = (float)div_area(e0, area, rcp), b1 = (float)div_area(e1, area, rcp);
-                const float b2 = 1.0f - b0 - b1;
-                float z = b0 * F[0] + b1 * F[1] + b2 * F[2];
-                z = z + 0.0f;
-                bool pass = cov && z >= 0.0f && z < 1.0f;
+                float b0, b1, b2, z;
+                bool pass = depth_from_edges(e0, e1, D[9], D[10], F, b0, b1, b2, z) && cov;
                 if (DEPTH_ONLY) {
                     const unsigned long long word = (unsigned long long)__float_as_uint(z);
                     pass = pass && word < best;
@@ -1509,7 +1456,7 @@ k_bin_raster(const BinParams p) {
                             best = min(best, lds_peek(&mail[lane]));
                         }
                         if (pass) {
-                            const int at = qn + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mp >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mp, 0u));
+                            const int at = qn + (int)lane_rank(mp);
                             Q.word[at] = word;
                             Q.uv[at][0] = u; Q.uv[at][1] = v;
                             Q.uv[at][2] = ux - u; Q.uv[at][3] = vx - v; Q.uv[at][4] = uy - u; Q.uv[at][5] = vy - v;
@@ -1662,6 +1609,8 @@ k_gbuffer_shade(const ShadeParams p) {
 #pragma unroll
             for (int k = 0; k < 6; ++k) uv_early[k] = p.r.tex.uv[(size_t)t * 6 + k];
         }
+        // (not tri_front / front_subtri: the loads above must stay between load_clip_tri and the set-up, and with the
+        // polygon filled by selects this kernel's textured instantiation takes six more VGPRs)
         const bool whole = unclipped(in);
         FanTri fan;
         SubTri s;

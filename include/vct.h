@@ -329,6 +329,53 @@ int vct_set_aov_outputs(vct_ctx* ctx, uint32_t which);
 int vct_download_aov(vct_ctx* ctx, uint32_t one_bit, void* out_rgba16f_host);
 int vct_get_aov_device(vct_ctx* ctx, uint32_t one_bit, void** rgba16f_dev, size_t* bytes);
 
+/* ---- half-rate diffuse gather -------------------------------------------------------------------------
+ * No reference counterpart (S/VoxelConeTracing.fs:194-199 marches the six diffuse cones of every fragment), so the
+ * definition is this build's.  The six diffuse cones are most of a frame's steps, their aperture is 60 degrees and they
+ * start one voxel off the surface: their gather varies slowly over a surface.  rate = 2 marches them for one pixel per
+ * 2x2 quad and reconstructs the others with a depth- and normal-aware filter; rate = 1 (default) is the trace as it was,
+ * bit for bit.  The specular cone stays at full rate.  Rate 2, all of it fp32, plain multiplies, adds and compares in
+ * the written order, nothing fused, one IEEE division at the end:
+ *   Coarse grid  cw = ceil(w / 2) by ch = ceil(h / 2); coarse sample (cx, cy) covers the pixels (2 cx + i, 2 cy + j).
+ *   Anchor       of a quad: the first pixel in the order (0,0), (1,0), (0,1), (1,1) = (i, j) that is inside the frame
+ *                and not discarded (albedo.a >= 0.5).  No such pixel: no sample.  The anchor's six cones are marched as
+ *                rate 1 marches them for that pixel and ind is their gather (fs:194-199): the same bits as at rate 1.
+ *   Candidates   of a live pixel p = (x, y) that is no anchor, in this order, with integer weights:
+ *                  0  its own quad (x >> 1, y >> 1)                                   9
+ *                  1  the horizontal neighbour, (x >> 1) + (x & 1 ? +1 : -1)          3
+ *                  2  the vertical neighbour, chosen the same way in y                3
+ *                  3  the diagonal of the two                                         1
+ *                A candidate outside the coarse grid or without a sample is rejected.
+ *   Acceptance   with n_p, n_k the raw VCT_GB_NORMAL planes of p and of candidate k's anchor, P_p, P_k their positions,
+ *                vs = grid_world_size / voxel_dim, dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z and
+ *                  dn = dot(n_p, n_k)   d = dot(P_k - P_p, n_p)   l_p = dot(n_p, n_p)   l_k = dot(n_k, n_k):
+ *                  dn > 0
+ *                  dn*dn >= VCT_DIFFUSE_RATE_NORMAL_COS2 * (l_p * l_k)                 normals within ~25.7 degrees
+ *                  d*d  <= (VCT_DIFFUSE_RATE_PLANE_TOL * (vs*vs)) * l_p                anchor within vs / 2 of p's tangent plane
+ *   Interpolate  w_k = the weight of an accepted candidate, else 0; W = sum w_k (0 .. 16).  W > 0: per channel
+ *                  S = ((w_0*I_0 + w_1*I_1) + w_2*I_2) + w_3*I_3   (a rejected term is +0),   ind_p = S / (float)W.
+ *   Fill         W == 0: p marches its own six cones, like an anchor.
+ * The composite above runs per pixel with ind_p in place of the pixel's own gather; VCT_AOV_INDIRECT_DIFFUSE holds
+ * ind_p.  The skip rule is unchanged: when nothing reads the diffuse group, no coarse or fill cone is marched.
+ * vct_set_diffuse_rate is host state like the lighting mask: it applies from the next vct_trace, vct_trace_current,
+ * vct_trace_resident (at rate 2: the whole frame) or vct_gi_pass on.  Rate 2 allocates its buffers (24 B per pixel +
+ * 17 B per quad) for every frame slot and rate 1 frees them, so launches allocate nothing.  VCT_ERR_INVALID: a rate
+ * other than 1 or 2; rate 2 with config.trace_variant 1 .. 4, config.anisotropic_mips, footprint records or on a context of
+ * a multi-GPU frame (and each of those while rate 2 is set); at rate 2 vct_trace_slab, vct_trace_resident_rows,
+ * vct_trace_resident_strided and vct_last_row_steps.  vct_last_step_count counts every executed step (coarse, fill,
+ * specular), vct_last_trace_ms brackets all launches of the pass.  With config.debug_outputs, steps and cones 0..5 of
+ * a pixel hold its own march if it is an anchor or a fill pixel and zeros if it was interpolated.
+ * vct_get_diffuse_rate (either pointer may be NULL): the rate, and the pixels whose diffuse cones the selected slot's last
+ * trace marched (anchors + fill pixels; 0 after a rate-1 trace or when the group was skipped).  Waits for the slot's stream. */
+#define VCT_DIFFUSE_RATE_NORMAL_COS2 0.8125f    /* 13/16 */
+#define VCT_DIFFUSE_RATE_PLANE_TOL 0.25f        /* (1/2)^2 */
+int vct_set_diffuse_rate(vct_ctx* ctx, int32_t rate);
+int vct_get_diffuse_rate(const vct_ctx* ctx, int32_t* rate, uint64_t* marched_pixels);
+/* Device time of the four launches of the selected slot's last rate-2 pass -- coarse march, resolve, fill march, specular
+ * trace + composite -- in milliseconds.  Needs trace timing on (vct_set_trace_timing) and a pass that marched the
+ * diffuse group; waits for it. */
+int vct_last_diffuse_rate_ms(vct_ctx* ctx, float ms[4]);
+
 /* ---- two frames in flight (round 6) -----------------------------------------------------------------
  * The reference's Render() (VCT.h:146-190) issues GL commands; the driver starts frame k + 1 while frame k
  * drains -- nothing in R/main.cpp:77-94 waits for a frame.  A HIP stream does wait: each whole-frame trace

@@ -52,7 +52,7 @@ ABI_SYMBOLS = [
     "vct_get_stage_counts", "vct_comm_info", "vct_comm_last_gather_ms", "vct_set_footprint_records",
     "vct_set_frames_in_flight", "vct_get_frames_in_flight", "vct_select_frame_slot", "vct_selftest_texel_buffer",
     "vct_set_trace_timing", "vct_set_lighting_components", "vct_get_lighting_components", "vct_set_aov_outputs",
-    "vct_download_aov", "vct_get_aov_device",
+    "vct_download_aov", "vct_get_aov_device", "vct_set_diffuse_rate", "vct_get_diffuse_rate", "vct_last_diffuse_rate_ms",
 ]
 
 
@@ -151,6 +151,9 @@ _lib.vct_get_lighting_components.argtypes = [C.c_void_p, C.c_void_p]
 _lib.vct_set_aov_outputs.argtypes = [C.c_void_p, C.c_uint32]
 _lib.vct_download_aov.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
 _lib.vct_get_aov_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+_lib.vct_set_diffuse_rate.argtypes = [C.c_void_p, C.c_int32]
+_lib.vct_get_diffuse_rate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.vct_last_diffuse_rate_ms.argtypes = [C.c_void_p, C.c_void_p]
 _lib.vct_upload_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
 
 
@@ -290,6 +293,23 @@ class Context:
         p, n = C.c_void_p(), C.c_size_t()
         self._ck(_lib.vct_get_aov_device(self._h, int(bit), C.byref(p), C.byref(n)), "vct_get_aov_device")
         return p.value, n.value
+
+    def set_diffuse_rate(self, rate):
+        """1 (default): every pixel marches its six diffuse cones; 2: one pixel per 2x2 quad does and the others take a
+        depth- and normal-aware mean of the nearest four (include/vct.h).  From the next whole-frame trace on."""
+        self._ck(_lib.vct_set_diffuse_rate(self._h, int(rate)), "vct_set_diffuse_rate")
+
+    def diffuse_rate(self):
+        """(rate, pixels whose diffuse cones the last trace marched: anchors + fill pixels; 0 at rate 1).  Waits."""
+        r, n = C.c_int32(), C.c_uint64()
+        self._ck(_lib.vct_get_diffuse_rate(self._h, C.byref(r), C.byref(n)), "vct_get_diffuse_rate")
+        return r.value, n.value
+
+    def last_diffuse_rate_ms(self):
+        """Device ms of the last rate-2 pass's launches: (coarse march, resolve, fill march, specular trace + composite)."""
+        v = (C.c_float * 4)()
+        self._ck(_lib.vct_last_diffuse_rate_ms(self._h, v), "vct_last_diffuse_rate_ms")
+        return tuple(float(x) for x in v)
 
     # --- scene / volume
     def upload_triangles(self, pos, material, albedo):

@@ -385,7 +385,24 @@ int launch_trace(vct_ctx* c, int row0, int row1, uint16_t* out_base = nullptr, i
     // lighting components (include/vct.h): the COMP kernel only when the mask or an output asks for it.  A packed slab
     // (interleaved ranks, whose contexts refuse outputs; the one-GPU self-test) writes no outputs.
     const uint32_t aov_which = pack_rows ? 0u : c->aov_which;
-    if (c->show_mask != VCT_SHOW_ALL || aov_which) {
+    // half-rate diffuse gather (include/vct.h): whole frames only; the pass composites in the COMP kernel whatever the mask
+    // (VCT_SHOW_ALL there is the unmasked arithmetic), and when nothing reads the diffuse group it is rate 1's launch
+    const bool half = c->diffuse_rate == 2;
+    bool half_march = false;
+    if (half) {
+        if (row0 != 0 || row1 != tiles_y(c) || row_stride > 1 || pack_rows)
+            return fail(c, VCT_ERR_INVALID, "trace: diffuse rate 2 traces whole frames only (no slabs, tile-row ranges or interleaved rows)");
+        if (variant != 0 || c->cfg.anisotropic_mips || c->want_cells || c->comm || !cur(c).dr_ind)
+            return fail(c, VCT_ERR_INVALID, "trace: diffuse rate 2 needs the default trace kernel on a single-GPU context");
+        p.comp = component_word(c->show_mask, aov_which);
+        p.aov = aov_which ? cur(c).aov.get() : nullptr;
+        half_march = ((p.comp >> VCT_COMP_GROUPS_SHIFT) & 1u) != 0u;
+        if (half_march) {
+            p.dr_ind = cur(c).dr_ind.get(); p.dr_coarse = cur(c).dr_coarse.get(); p.dr_anchor = cur(c).dr_anchor.get();
+            p.dr_list = cur(c).dr_list.get(); p.dr_ctr = cur(c).dr_ctr.get();
+            p.dr_waves = c->diffuse_rate_waves;
+        }
+    } else if (c->show_mask != VCT_SHOW_ALL || aov_which) {
         if (variant != 0)
             return fail(c, VCT_ERR_INVALID, "lighting components / per-component outputs need the default trace kernel (config.trace_variant 0)");
         p.comp = component_word(c->show_mask, aov_which);
@@ -402,9 +419,11 @@ int launch_trace(vct_ctx* c, int row0, int row1, uint16_t* out_base = nullptr, i
         HIP_TRY(c, hipMemsetAsync(p.vt_count, 0, sizeof(uint32_t), cur(c).stream));
     }
     if (c->time_traces) HIP_TRY(c, hipEventRecord(cur(c).ev0, cur(c).stream));      // (vct_set_trace_timing)
-    HIP_TRY(c, vct_launch_trace(p, variant, cur(c).stream, &c->last_march_form));       // an empty row range (a rank without rows) launches nothing
+    HIP_TRY(c, vct_launch_trace(p, variant, cur(c).stream, &c->last_march_form,       // an empty row range (a rank without rows) launches nothing
+                                half_march && c->time_traces ? cur(c).dr_ev : nullptr));
     if (c->time_traces) HIP_TRY(c, hipEventRecord(cur(c).ev1, cur(c).stream));
     cur(c).last_trace_timed = c->time_traces;
+    cur(c).last_trace_half = half_march;
     cur(c).last_row0 = row0;
     cur(c).last_row1 = row1;
     cur(c).last_row_stride = rstride;
@@ -602,6 +621,34 @@ void raster_release_mesh(VctRasterScratch& r) {
 
 // A slot on `stream`, which it owns from here on: timing events, G-buffer, frame, per-tile step counts and the
 // per-component outputs that are on, zeroed on that stream.  A failure leaves a partial slot for slot_release.
+// the buffers and events of the half-rate diffuse gather (vct_set_diffuse_rate(ctx, 2)), zeroed on `stream`
+void slot_free_half_rate(VctFrameSlot& s) {
+    s.dr_ind.reset(); s.dr_coarse.reset(); s.dr_anchor.reset(); s.dr_list.reset(); s.dr_ctr.reset();
+    for (hipEvent_t& ev : s.dr_ev) {
+        if (ev) (void)hipEventDestroy(ev);
+        ev = nullptr;
+    }
+    s.last_trace_half = false;
+}
+hipError_t slot_alloc_half_rate(const vct_ctx* c, VctFrameSlot& s, hipStream_t stream) {
+    const size_t npix = (size_t)c->cfg.width * c->cfg.height;
+    const size_t nquad = (size_t)((c->cfg.width + 1) / 2) * ((c->cfg.height + 1) / 2);
+    hipError_t e = s.dr_ind.alloc(npix);
+    if (e == hipSuccess) e = s.dr_coarse.alloc(nquad);
+    if (e == hipSuccess) e = s.dr_anchor.alloc(nquad);
+    if (e == hipSuccess) e = s.dr_list.alloc(npix);
+    if (e == hipSuccess) e = s.dr_ctr.alloc(VCT_DR_CTR_WORDS);
+    if (e == hipSuccess) e = hipMemsetAsync(s.dr_ind.get(), 0, npix * sizeof(float4), stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s.dr_coarse.get(), 0, nquad * sizeof(float4), stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s.dr_anchor.get(), 0xff, nquad, stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s.dr_list.get(), 0, npix * sizeof(uint32_t), stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s.dr_ctr.get(), 0, VCT_DR_CTR_WORDS * sizeof(unsigned long long), stream);
+    for (hipEvent_t& ev : s.dr_ev)
+        if (e == hipSuccess && !ev) e = hipEventCreate(&ev);
+    if (e != hipSuccess) slot_free_half_rate(s);
+    return e;
+}
+
 hipError_t slot_create(vct_ctx* c, VctFrameSlot& s, hipStream_t stream) {
     const size_t npix = (size_t)c->cfg.width * c->cfg.height, nt = (size_t)tiles_x(c) * tiles_y(c);
     const size_t aov_halves = aov_frames(c->aov_which) * npix * 4;
@@ -616,6 +663,7 @@ hipError_t slot_create(vct_ctx* c, VctFrameSlot& s, hipStream_t stream) {
     if (e == hipSuccess) e = hipMemsetAsync(s.tile_steps.get(), 0, nt * sizeof(uint32_t), stream);
     if (e == hipSuccess && aov_halves) e = s.aov.alloc(aov_halves);
     if (e == hipSuccess && aov_halves) e = hipMemsetAsync(s.aov.get(), 0, aov_halves * 2, stream);
+    if (e == hipSuccess && c->diffuse_rate == 2) e = slot_alloc_half_rate(c, s, stream);
     s.gb_current = s.gb_tiled.get();
     return e;
 }
@@ -625,6 +673,7 @@ void slot_release(VctFrameSlot& s) {
     if (s.stream) (void)hipStreamSynchronize(s.stream);
     if (s.ev0) (void)hipEventDestroy(s.ev0);
     if (s.ev1) (void)hipEventDestroy(s.ev1);
+    slot_free_half_rate(s);
     if (s.stream) (void)hipStreamDestroy(s.stream);
     s = VctFrameSlot();
 }
@@ -867,6 +916,8 @@ int vct_set_trace_variant(vct_ctx* c, int32_t variant) {
         return fail(c, VCT_ERR_INVALID, "vct_set_trace_variant: variant 4 keeps per-context scratch (vct_set_frames_in_flight(ctx, 1) first)");
     if (variant != 0 && (c->show_mask != VCT_SHOW_ALL || c->aov_which))
         return fail(c, VCT_ERR_INVALID, "vct_set_trace_variant: variants 1 .. 4 have no lighting components (mask VCT_SHOW_ALL, no outputs first)");
+    if (variant != 0 && c->diffuse_rate == 2)
+        return fail(c, VCT_ERR_INVALID, "vct_set_trace_variant: variants 1 .. 4 have no half-rate diffuse gather (vct_set_diffuse_rate(ctx, 1) first)");
     c->cfg.trace_variant = variant;
     return VCT_OK;
 }
@@ -1435,6 +1486,8 @@ static int build_cells(vct_ctx* c) {
 
 int vct_set_footprint_records(vct_ctx* c, int32_t on) {
     if (!c) return VCT_ERR_INVALID;
+    if (on && c->diffuse_rate == 2)
+        return fail(c, VCT_ERR_INVALID, "vct_set_footprint_records: the half-rate diffuse gather has no footprint-record kernels (vct_set_diffuse_rate(ctx, 1) first)");
     HIP_TRY(c, hipSetDevice(c->device));
     c->want_cells = on != 0;
     PIPE_TRY(pipeline_drain(c));
@@ -1638,6 +1691,12 @@ int vct_download_chain_rgba8(vct_ctx* c, uint8_t* chain) {
 
 // ---- trace -------------------------------------------------------------------------------
 
+// the rows of the last screen trace again (vct_trace_resident, vct_gi_pass) -- at diffuse rate 2 the whole frame
+static int launch_trace_last_rows(vct_ctx* c) {
+    if (c->diffuse_rate == 2) return launch_trace(c, 0, tiles_y(c));
+    return launch_trace(c, cur(c).last_row0, cur(c).last_row1, nullptr, cur(c).last_row_stride, false);
+}
+
 static int bind_gbuffer(vct_ctx* c, const vct_gbuffer* gb) {
     if (!gb || !gb->planes) return fail(c, VCT_ERR_INVALID, "vct_trace: null G-buffer");
     if (gb->width != c->cfg.width || gb->height != c->cfg.height)
@@ -1666,9 +1725,16 @@ static int bind_gbuffer(vct_ctx* c, const vct_gbuffer* gb) {
     return VCT_OK;
 }
 
+static int trace_rows(vct_ctx* c, const vct_gbuffer* gb, int32_t row0, int32_t row1, void* out, int32_t out_location);
+
 int vct_trace_slab(vct_ctx* c, const vct_gbuffer* gb, int32_t row0, int32_t row1, void* out,
                    int32_t out_location) {
     if (!c) return VCT_ERR_INVALID;
+    if (c->diffuse_rate == 2) return fail(c, VCT_ERR_INVALID, "vct_trace_slab: diffuse rate 2 traces whole frames only (vct_trace)");
+    return trace_rows(c, gb, row0, row1, out, out_location);
+}
+
+static int trace_rows(vct_ctx* c, const vct_gbuffer* gb, int32_t row0, int32_t row1, void* out, int32_t out_location) {
     if (row0 < 0 || row1 > tiles_y(c) || row0 > row1)
         return fail(c, VCT_ERR_INVALID, "vct_trace_slab: tile-row range outside the frame");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1695,7 +1761,7 @@ int vct_trace_slab(vct_ctx* c, const vct_gbuffer* gb, int32_t row0, int32_t row1
 
 int vct_trace(vct_ctx* c, const vct_gbuffer* gb, void* out, int32_t out_location) {
     if (!c) return VCT_ERR_INVALID;
-    return vct_trace_slab(c, gb, 0, tiles_y(c), out, out_location);
+    return trace_rows(c, gb, 0, tiles_y(c), out, out_location);
 }
 
 int vct_trace_current(vct_ctx* c, void* out, int32_t out_location) {
@@ -1716,6 +1782,7 @@ int vct_trace_current(vct_ctx* c, void* out, int32_t out_location) {
 
 int vct_trace_resident_rows(vct_ctx* c, int32_t row0, int32_t row1) {
     if (!c) return VCT_ERR_INVALID;
+    if (c->diffuse_rate == 2) return fail(c, VCT_ERR_INVALID, "vct_trace_resident_rows: diffuse rate 2 traces whole frames only (vct_trace_resident)");
     if (!cur(c).have_gbuffer) return fail(c, VCT_ERR_INVALID, "vct_trace_resident_rows: no G-buffer resident yet");
     if (row0 < 0 || row1 > tiles_y(c) || row0 > row1)
         return fail(c, VCT_ERR_INVALID, "vct_trace_resident_rows: tile-row range outside the frame");
@@ -1725,6 +1792,7 @@ int vct_trace_resident_rows(vct_ctx* c, int32_t row0, int32_t row1) {
 
 int vct_trace_resident_strided(vct_ctx* c, int32_t row0, int32_t row1, int32_t stride) {
     if (!c) return VCT_ERR_INVALID;
+    if (c->diffuse_rate == 2) return fail(c, VCT_ERR_INVALID, "vct_trace_resident_strided: diffuse rate 2 traces whole frames only (vct_trace_resident)");
     if (!cur(c).have_gbuffer) return fail(c, VCT_ERR_INVALID, "vct_trace_resident_strided: no G-buffer resident yet");
     if (row0 < 0 || row1 > tiles_y(c) || row0 > row1 || stride < 1)
         return fail(c, VCT_ERR_INVALID, "vct_trace_resident_strided: tile-row range outside the frame or stride < 1");
@@ -1736,7 +1804,7 @@ int vct_trace_resident(vct_ctx* c) {
     if (!c) return VCT_ERR_INVALID;
     if (!cur(c).have_gbuffer) return fail(c, VCT_ERR_INVALID, "vct_trace_resident: no G-buffer resident yet");
     HIP_TRY(c, hipSetDevice(c->device));
-    return launch_trace(c, cur(c).last_row0, cur(c).last_row1, nullptr, cur(c).last_row_stride, false);
+    return launch_trace_last_rows(c);
 }
 
 int vct_gi_pass(vct_ctx* c, const float light_vp[16], const float view_proj[16], int32_t mode) {
@@ -1760,7 +1828,7 @@ int vct_gi_pass(vct_ctx* c, const float light_vp[16], const float view_proj[16],
             if (rc1 == VCT_OK) rc1 = render_gbuffer_rows_on(c, view_proj, row0, row1, cur(c).stream);
             if (rc1) return rc1;
             if (rank_ctx) return vct_frame_step(c);
-            return launch_trace(c, cur(c).last_row0, cur(c).last_row1, nullptr, cur(c).last_row_stride, false);
+            return launch_trace_last_rows(c);
         }
     }
     if (!c->aux_stream) {
@@ -1793,7 +1861,7 @@ int vct_gi_pass(vct_ctx* c, const float light_vp[16], const float view_proj[16],
     else HIP_TRY(c, ej);
     if (rc) return rc;
     if (rank_ctx) return vct_frame_step(c);
-    return launch_trace(c, cur(c).last_row0, cur(c).last_row1, nullptr, cur(c).last_row_stride, false);
+    return launch_trace_last_rows(c);
 }
 
 int vct_download_frame(vct_ctx* c, void* out) {
@@ -1934,6 +2002,11 @@ int vct_last_step_count(vct_ctx* c, uint64_t* steps) {
         const int rc = row_steps(c, rows);
         if (rc) return rc;
         for (uint64_t r : rows) sum += r;
+        if (cur(c).last_trace_half) {       // + the coarse and the fill march of a half-rate pass (the stream is idle by now)
+            std::vector<unsigned long long> v(VCT_DR_COUNTERS);
+            HIP_TRY(c, hipMemcpy(v.data(), cur(c).dr_ctr.get(), v.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+            for (unsigned long long w : v) sum += w;
+        }
     } else {        // a bounce: its kernels add into the atomic bank
         HIP_TRY(c, hipStreamSynchronize(cur(c).stream));
         unsigned long long v[VCT_STEP_COUNTERS];
@@ -1972,6 +2045,8 @@ int vct_last_row_steps(vct_ctx* c, uint64_t* rows, int32_t nrows) {
     if (!cur(c).have_trace || !cur(c).last_was_screen_trace)
         return fail(c, VCT_ERR_INVALID, "vct_last_row_steps: the last march was not a screen trace");
     if (nrows != tiles_y(c)) return fail(c, VCT_ERR_INVALID, "vct_last_row_steps: nrows must be the frame's tile rows, ceil(height / 8)");
+    if (c->diffuse_rate == 2 || cur(c).last_trace_half)
+        return fail(c, VCT_ERR_INVALID, "vct_last_row_steps: diffuse rate 2 keeps no per-row histogram (its marches are not per tile row)");
     // trace_variant 4 stores its step counts per VIRTUAL tile of the compaction list: only their total means anything
     if (cur(c).last_trace_compacted)
         return fail(c, VCT_ERR_INVALID, "vct_last_row_steps: the last trace was compacted (config.trace_variant 4): no per-row histogram");
@@ -2149,6 +2224,73 @@ int vct_get_aov_device(vct_ctx* c, uint32_t bit, void** p, size_t* bytes) {
     if (!src) return fail(c, VCT_ERR_INVALID, "vct_get_aov_device: not one output that vct_set_aov_outputs turned on");
     *p = src;
     if (bytes) *bytes = (size_t)c->cfg.width * c->cfg.height * 8;
+    return VCT_OK;
+}
+
+// ---- half-rate diffuse gather (include/vct.h) ---------------------------------------------------------------------------
+int vct_set_diffuse_rate(vct_ctx* c, int32_t rate) {
+    if (!c) return VCT_ERR_INVALID;
+    if (rate != 1 && rate != 2) return fail(c, VCT_ERR_INVALID, "vct_set_diffuse_rate: 1 or 2");
+    if (rate == 2) {
+        if (c->cfg.trace_variant != 0)
+            return fail(c, VCT_ERR_INVALID, "vct_set_diffuse_rate: config.trace_variant 1 .. 4 has no half-rate diffuse gather");
+        if (c->cfg.anisotropic_mips)
+            return fail(c, VCT_ERR_INVALID, "vct_set_diffuse_rate: config.anisotropic_mips has no half-rate diffuse gather");
+        if (c->want_cells)
+            return fail(c, VCT_ERR_INVALID, "vct_set_diffuse_rate: footprint records are on (vct_set_footprint_records(ctx, 0) first)");
+        if (c->comm)
+            return fail(c, VCT_ERR_INVALID, "vct_set_diffuse_rate: a rank of a multi-GPU frame traces slabs (rate 2 traces whole frames only)");
+    }
+    if (rate == c->diffuse_rate) return VCT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    PIPE_TRY(vct_synchronize(c));            // buffers about to go may still be read
+    if (rate == 2) {
+        // every live slot's set, allocated here and never in a launch; all or nothing
+        hipError_t e = hipSuccess;
+        for (int k = 0; k < c->frames_in_flight && e == hipSuccess; ++k) {
+            e = slot_alloc_half_rate(c, c->slots[k], c->slots[k].stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->slots[k].stream);
+        }
+        if (e != hipSuccess) {
+            for (int k = 0; k < c->frames_in_flight; ++k) slot_free_half_rate(c->slots[k]);
+            return fail(c, e == hipErrorOutOfMemory ? VCT_ERR_NOMEM : VCT_ERR_DEVICE, std::string("vct_set_diffuse_rate: ") + hipGetErrorString(e));
+        }
+        const char* w = getenv("VCT_DIFFUSE_RATE_WAVES");      // A/B of the march's workgroup shape
+        c->diffuse_rate_waves = w && w[0] == '2' ? 2 : 1;
+    } else {
+        for (int k = 0; k < c->frames_in_flight; ++k) slot_free_half_rate(c->slots[k]);
+    }
+    c->diffuse_rate = rate;
+    return VCT_OK;
+}
+
+int vct_get_diffuse_rate(const vct_ctx* c, int32_t* rate, uint64_t* marched_pixels) {
+    if (!c) return VCT_ERR_INVALID;
+    if (rate) *rate = c->diffuse_rate;
+    if (marched_pixels) {
+        *marched_pixels = 0;
+        if (cur(c).have_trace && cur(c).last_trace_half && cur(c).dr_ctr) {
+            std::vector<unsigned long long> v(VCT_DR_COUNTERS);
+            hipError_t e = hipSetDevice(c->device);
+            if (e == hipSuccess) e = hipStreamSynchronize(cur(c).stream);
+            if (e == hipSuccess)
+                e = hipMemcpy(v.data(), cur(c).dr_ctr.get() + VCT_DR_COUNTERS, v.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+            if (e != hipSuccess) return fail(const_cast<vct_ctx*>(c), VCT_ERR_DEVICE, std::string("vct_get_diffuse_rate: ") + hipGetErrorString(e));
+            for (unsigned long long w : v) *marched_pixels += w;
+        }
+    }
+    return VCT_OK;
+}
+
+int vct_last_diffuse_rate_ms(vct_ctx* c, float ms[4]) {
+    if (!c || !ms) return VCT_ERR_INVALID;
+    if (!cur(c).have_trace || !cur(c).last_trace_half || !cur(c).last_was_screen_trace)
+        return fail(c, VCT_ERR_INVALID, "vct_last_diffuse_rate_ms: the last trace was no rate-2 pass that marched the diffuse group");
+    if (!cur(c).last_trace_timed)
+        return fail(c, VCT_ERR_INVALID, "vct_last_diffuse_rate_ms: the last trace was issued with timing off (vct_set_trace_timing)");
+    HIP_TRY(c, hipEventSynchronize(cur(c).ev1));
+    const hipEvent_t ev[5] = {cur(c).ev0, cur(c).dr_ev[0], cur(c).dr_ev[1], cur(c).dr_ev[2], cur(c).ev1};
+    for (int i = 0; i < 4; ++i) HIP_TRY(c, hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
     return VCT_OK;
 }
 

@@ -98,6 +98,14 @@ struct VctFrameSlot {
     uint16_t* frame_target = nullptr;   // caller-owned output (vct_set_frame_target) or null (not owned)
     VctBuf<uint32_t> tile_steps;        // [tiles] executed steps per 8x8 tile of the screen trace
     VctBuf<uint16_t> aov;               // per-component outputs (vct_set_aov_outputs): popcount(aov_which) frames, bit order
+    // half-rate diffuse gather (vct_set_diffuse_rate(ctx, 2); vct_internal.h VctTraceParams::dr_*), present at rate 2 only
+    VctBuf<float4> dr_ind;              // [h][w]
+    VctBuf<float4> dr_coarse;           // [ch][cw]
+    VctBuf<uint8_t> dr_anchor;          // [ch][cw]
+    VctBuf<uint32_t> dr_list;           // [w * h]
+    VctBuf<unsigned long long> dr_ctr;  // [VCT_DR_CTR_WORDS]
+    hipEvent_t dr_ev[3] = {nullptr, nullptr, nullptr};   // between the pass's four launches (vct_last_diffuse_rate_ms)
+    bool last_trace_half = false;       // the last screen trace was a half-rate pass: dr_ctr holds its marches' counts
     int last_row0 = 0, last_row1 = 0;
     int last_row_stride = 1;            // the last screen trace took every last_row_stride-th tile row of [last_row0, last_row1)
     bool have_trace = false;
@@ -186,6 +194,8 @@ struct vct_ctx {
     // (vct_set_aov_outputs): VCT_AOV_* bits, one buffer per frame slot (VctFrameSlot::aov)
     uint32_t show_mask = VCT_SHOW_ALL;
     uint32_t aov_which = 0;
+    int diffuse_rate = 1;             // vct_set_diffuse_rate: 1, or 2 = the half-rate diffuse gather
+    int diffuse_rate_waves = 1;       // waves per 64 marched points of its marches (VCT_DIFFUSE_RATE_WAVES=2: A/B)
     VctBuf<uint8_t> dbg_steps;
     VctBuf<float> dbg_cones;
     VctBuf<unsigned long long> step_counter;   // [VCT_STEP_COUNTERS] atomic bank of the bounce kernels (memset before each bounce)

@@ -276,11 +276,23 @@ struct VctTraceParams {
     unsigned long long* stats;          // [8] wave-level march counters (builds with -DVCT_STATS=1 only)
     // second bounce (k_bounce): per-voxel attributes (pooled like the accumulators: [slot][512]), touched-brick
     // flags, output level 0
-    const uint32_t* attr_albedo;
-    const uint32_t* attr_normal;
-    const uint32_t* brick_slot;
-    const uint32_t* brick_prev;
-    const uint32_t* bounce_seen;        // bricks the bounce chain showed when its mips were last built
+    // The five of them are read by the bounce kernels only and the dr_* beside them by the screen trace only (half-rate
+    // diffuse gather: vct_set_diffuse_rate(ctx, 2), include/vct.h; vct_trace.hip k_point_march / k_diffuse_resolve /
+    // k_trace_tile_split<.., HALF = true>; dr_ind != null in a screen trace's parameters selects it).  They share their
+    // slots for the reason bounce_out and aov do.
+    union { const uint32_t* attr_albedo;
+            float4* dr_ind; };          // [h][w] the gather every pixel's composite takes (anchor, interpolated or fill)
+    union { const uint32_t* attr_normal;
+            float4* dr_coarse; };       // [ch][cw] the gather of each 2x2 quad's anchor, cw = ceil(w / 2), ch = ceil(h / 2)
+    union { const uint32_t* brick_slot;
+            uint8_t* dr_anchor; };      // [ch][cw] the anchor's place in its quad, j * 2 + i, or VCT_DR_NO_ANCHOR
+    union { const uint32_t* brick_prev;
+            uint32_t* dr_list; };       // [w * h] fill pixels (y * w + x) in no particular order
+    // bounce_seen: bricks the bounce chain showed when its mips were last built
+    // dr_ctr: counters of one half-rate pass, zeroed by its first launch: [0, VCT_DR_COUNTERS) executed steps of the coarse
+    // and the listed march, [VCT_DR_COUNTERS, 2 VCT_DR_COUNTERS) pixels they marched, [2 VCT_DR_COUNTERS] entries of dr_list
+    union { const uint32_t* bounce_seen;
+            unsigned long long* dr_ctr; };
     // bounce_out is written by the bounce kernels only, aov read by the screen trace only: they share the slot, so the
     // screen trace's parameter block keeps its size (and the default kernels their code) with the lighting components
     union {
@@ -301,7 +313,8 @@ struct VctTraceParams {
     uint32_t aniso_alt_slab;            // float4 offset from a level's LDS slab to its second ("-axis") slab
     uint32_t* bounce_list;              // global list of occupied voxels (Morton indices), brick by brick
     uint32_t* bounce_list_count;
-    uint32_t bounce_list_cap;
+    union { uint32_t bounce_list_cap;
+            int32_t dr_waves; };        // (half-rate pass) waves per 64 marched points: 1, or 2 with three cones each
     uint32_t* brick_over;               // bricks whose voxels did not fit the list
     // Live-pixel compaction (config.trace_variant = 4; vct_trace.hip k_compact_tiles): the live pixels (albedo.a >= 0.5)
     // of every 16x16-pixel super-tile packed into whole waves.  vt_pix[v * 64 + lane] = tile << 6 | pixel of the tile
@@ -309,6 +322,9 @@ struct VctTraceParams {
     uint32_t* vt_pix;
     uint32_t* vt_count;
 };
+#define VCT_DR_NO_ANCHOR 0xffu
+#define VCT_DR_COUNTERS 256             // (power of two) a bank, for the reason VCT_STEP_COUNTERS is one
+#define VCT_DR_CTR_WORDS (2 * VCT_DR_COUNTERS + 1)
 
 #ifndef VCT_VOX_CHUNK
 #define VCT_VOX_CHUNK 4096u       // most fragments one work item (workgroup) of the voxelize pass takes (vct_capi.hip build_voxel_slots)
@@ -433,7 +449,9 @@ hipError_t vct_launch_untile_gbuffer(const float* tiled, float* planes_linear, i
 // kernel (variants 1, 2) nor by the compaction's virtual tiles (4)
 static inline bool vct_variant_takes_row_subsets(int variant) { return variant == 0 || variant == 3; }
 // sets p.ntiles on its own copy; march_form: the division form dispatched (vct_trace.hip)
-hipError_t vct_launch_trace(const VctTraceParams& p, int variant, hipStream_t s, int* march_form = nullptr);
+// marks (optional, half-rate passes only): three events recorded between the pass's four launches
+hipError_t vct_launch_trace(const VctTraceParams& p, int variant, hipStream_t s, int* march_form = nullptr,
+                            const hipEvent_t* marks = nullptr);
 hipError_t vct_launch_divide_selftest(float d, unsigned long long* mismatches, hipStream_t s);
 // typed-buffer texel loads (RGBA8 UNORM -> four floats in the texture path) against the exact decode, n texels
 hipError_t vct_launch_texel_buffer_selftest(const uint32_t* texels, uint32_t n, unsigned long long* out, hipStream_t s);

@@ -382,6 +382,7 @@ int vct_comm_init(vct_ctx* c, const void* id128, int32_t rank, int32_t world) {
     if (!id128 || world <= 0 || rank < 0 || rank >= world) return vct_fail(c, VCT_ERR_INVALID, "vct_comm_init: bad rank / world / id");
     if (c->comm) return vct_fail(c, VCT_ERR_INVALID, "vct_comm_init: already initialised (vct_comm_destroy first)");
     if (c->aov_which) return vct_fail(c, VCT_ERR_INVALID, "vct_comm_init: per-component outputs are on (they are not gathered)");
+    if (c->diffuse_rate == 2) return vct_fail(c, VCT_ERR_INVALID, "vct_comm_init: diffuse rate 2 traces whole frames only (vct_set_diffuse_rate(ctx, 1) first)");
     const char* mode = getenv("VCT_COMM_MODE");
     const bool direct = mode && mode[0] == 'd';       // direct slabs: no RCCL (see DirectShm)
     Rccl* r = direct ? nullptr : rccl();

@@ -11,7 +11,8 @@
 //
 // Kernels in this file: k_trace_tile_split (default: an 8x8 screen tile = 3 waves -- cones 0-2, cones
 // 3-5, specular -- with an LDS hand-off and a last-arriver composite), k_trace_tile (one wave per
-// tile; A/B variants), k_bounce_list/_march/_bricks (second bounce, same march), k_divide_selftest.
+// tile; A/B variants), k_bounce_list/_march/_bricks (second bounce, same march), k_point_march + k_diffuse_resolve (half-rate
+// diffuse gather, same march), k_divide_selftest.
 //
 // Mapping: lane = pixel of the tile, a wave marches its cones one after the other.  The kernel
 // was VALU-issue bound from round 1 (profiles/r01a: 995 M VALU wave-instructions per 1080p frame, half of the
@@ -935,7 +936,11 @@ static_assert(VCT_SPLIT == 3 || VCT_SPLIT == 4 || VCT_SPLIT == 7, "VCT_SPLIT mus
 // COMP: lighting components (p.comp; vct_set_lighting_components, vct_set_aov_outputs) -- a wave whose cone group
 // nothing reads marches nothing, the composite applies the VCT_SHOW_* mask, and the per-component outputs are stored
 // beside the frame.  An instantiation of its own for the same reason as CELLS: the default kernels carry none of it.
-template <bool WRAP, int FASTDIV, bool ANISO, bool COMPACT = false, bool CELLS = false, bool PRIO = false, bool COMP = false>
+// HALF: the last launch of a half-rate pass (vct_set_diffuse_rate(ctx, 2); "Half-rate diffuse gather" below): the diffuse
+// waves march nothing and leave the debug outputs to the launches in front of this one, and the composite takes the
+// pixel's gather from p.dr_ind instead of the cones in LDS.  Instantiated with COMP and PRIO only (whole frames).
+template <bool WRAP, int FASTDIV, bool ANISO, bool COMPACT = false, bool CELLS = false, bool PRIO = false, bool COMP = false,
+          bool HALF = false>
 __global__ void __launch_bounds__(64 * VCT_SPLIT, ANISO ? VCT_ANISO_MIN_WAVES : VCT_TRACE_MIN_WAVES)
 k_trace_tile_split(const VctTraceParams p) {
     __shared__ float4 lds_blk[VCT_SPLIT][ANISO ? 4 : 2][64];   // per wave: level-1 slab, level-2 slab (+ their "-axis" slabs)
@@ -996,7 +1001,9 @@ k_trace_tile_split(const VctTraceParams p) {
     // parameter word through readfirstlane), so the march loop is not entered on a scalar branch.
     const uint32_t groups = COMP ? (uint32_t)__builtin_amdgcn_readfirstlane((int)p.comp) >> VCT_COMP_GROUPS_SHIFT : 3u;
     const int n_diffuse = (groups & 1u) ? p.n_diffuse : 0, n_specular = (groups & 2u) ? p.n_specular : 0;
-    if (wave < VCT_SPLIT - 1) {
+    if (HALF && wave < VCT_SPLIT - 1) {
+        // 0 steps: the wave arrives at once (the skip mechanism of COMP, without its zero cones)
+    } else if (wave < VCT_SPLIT - 1) {
         F3 start, k0, k1, k2;
         cone_frame_from_gbuffer(gb, p.vs, start, k0, k1, k2);
 #pragma unroll 1
@@ -1042,9 +1049,204 @@ k_trace_tile_split(const VctTraceParams p) {
     const float* gb3 = gbuf_ptr(fresh_lane());
     if (in_frame) {
         F4 ind = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (HALF) {
+            const float4 v = p.dr_ind[pixel_index()];
+            ind = {v.x, v.y, v.z, v.w};
+        } else {
 #pragma unroll
-        for (int i = 0; i < 6; ++i) ind = fold_cone(ind, i, lds_cone[i][lane]);
+            for (int i = 0; i < 6; ++i) ind = fold_cone(ind, i, lds_cone[i][lane]);
+        }
         composite<COMP>(p, gb3, ind, lds_cone[6][lane], alive, pixel_index);
+    }
+}
+
+// ---- Half-rate diffuse gather (include/vct.h vct_set_diffuse_rate) ------------------------------------------------------
+// The six diffuse cones are 63 % of a frame's steps and their gather varies slowly over a surface: at rate 2 one pixel
+// per 2x2 quad -- its ANCHOR -- marches them, the other pixels take the 9:3:3:1 mean of the (up to) four nearest
+// anchors' gathers that lie on their surface, and a pixel none of them serves marches its own (a FILL pixel).  Four
+// launches on the slot's stream:
+//   k_point_march<.., LISTED = false>   lane = one quad of an 8x8 block of quads: finds the anchor, marches its cones
+//   k_diffuse_resolve                   lane = one pixel: acceptance test, interpolation, fill list (one append per wave)
+//   k_point_march<.., LISTED = true>    lane = one entry of the fill list, over the list's device-side count
+//   k_trace_tile_split<.., HALF = true> specular cone + composite with the gather of p.dr_ind
+// The marches are cone_march with rate 1's inputs, so cones and gather of a marched pixel are rate 1's, bit for bit.
+__device__ __forceinline__ const float* gb_of_pixel(const VctTraceParams& p, int x, int y) {
+    return p.gbuf + (size_t)((y >> 3) * p.tiles_x + (x >> 3)) * (VCT_GB_NPLANES * VCT_TILE_PIX) + (((y & 7) << 3) | (x & 7));
+}
+// (a.x*b.x + a.y*b.y) + a.z*b.z, every operation rounded on its own (include/vct.h: no fused operation)
+__device__ __forceinline__ float dot3_rn(F3 a, F3 b) {
+    return __fadd_rn(__fadd_rn(__fmul_rn(a.x, b.x), __fmul_rn(a.y, b.y)), __fmul_rn(a.z, b.z));
+}
+// this lane's place among the lanes of mask m below it
+__device__ __forceinline__ uint32_t lane_rank(unsigned long long m) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
+#ifndef VCT_POINT_MIN_WAVES
+#define VCT_POINT_MIN_WAVES 5     // the cone frame and the running gather stay live across the marches: as the bounce (6 spills 12-22 registers)
+#endif
+// WAVES = 1: one wave marches the six cones of its 64 points (the shape of k_bounce_march); 2: a workgroup of two waves
+// with cones 0-2 and 3-5, the second hands its three over in LDS and the first folds all six in the oracle's order.
+template <bool WRAP, int FASTDIV, bool LISTED, int WAVES>
+__global__ void __launch_bounds__(64 * WAVES, VCT_POINT_MIN_WAVES)
+k_point_march(const VctTraceParams p) {
+    __shared__ float4 lds_blk[WAVES][2][64];
+    __shared__ float4 lds_cone[WAVES == 2 ? 3 : 1][64];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    float4* blk = &lds_blk[wave][0][0];
+    const LaneBlock lb = make_lane_block(p, lane);
+    MarchStats ms = {};
+    const int cw = (p.width + 1) >> 1, ch = (p.height + 1) >> 1;
+    const int bxn = (cw + 7) >> 3;
+    const uint32_t nfill = LISTED ? (uint32_t)p.dr_ctr[2 * VCT_DR_COUNTERS] : 0u;
+    const uint32_t nitems = LISTED ? (nfill + 63u) >> 6 : (uint32_t)(bxn * ((ch + 7) >> 3));       // workgroup-uniform
+    unsigned long long wave_steps = 0;
+    uint32_t wave_marched = 0u;
+    for (uint32_t it = blockIdx.x; it < nitems; it += gridDim.x) {
+        // the point of this lane: pixel (x, y); a lane without one reads pixel 0 and its result is discarded
+        int x = 0, y = 0;
+        bool alive = false;
+        uint32_t code = VCT_DR_NO_ANCHOR;
+        const int by = LISTED ? 0 : (int)it / bxn, bx = LISTED ? 0 : (int)it - by * bxn;
+        const int cx = bx * 8 + (lane & 7), cy = by * 8 + (lane >> 3);          // (coarse march: this lane's quad)
+        if (!LISTED) {
+            if (cx < cw && cy < ch) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {          // (0,0), (1,0), (0,1), (1,1): the first pixel that is not discarded
+                    const int px = 2 * cx + (k & 1), py = 2 * cy + (k >> 1);
+                    if (!alive && px < p.width && py < p.height && !(gb_plane(gb_of_pixel(p, px, py), 18) < 0.5f)) {
+                        alive = true; x = px; y = py; code = (uint32_t)k;
+                    }
+                }
+            }
+        } else {
+            const uint32_t e = it * 64u + (uint32_t)lane;
+            if (e < nfill) {
+                const uint32_t pix = p.dr_list[e];
+                y = (int)(pix / (uint32_t)p.width); x = (int)(pix - (uint32_t)y * (uint32_t)p.width);
+                alive = true;
+            }
+        }
+        const float* gb = gb_of_pixel(p, x, y);
+        auto pixel_index = [&]() { return (size_t)y * p.width + x; };
+        F3 start, k0, k1, k2;
+        cone_frame_from_gbuffer(gb, p.vs, start, k0, k1, k2);
+        F4 ind = {0.0f, 0.0f, 0.0f, 0.0f};
+        int total = 0;
+        const int first = WAVES == 2 ? wave * 3 : 0;
+#pragma unroll 1
+        for (int i = first; i < first + 6 / WAVES; ++i) {
+            int st;
+            const F4 c = cone_march<WRAP, FASTDIV, true>(p, alive, start, cone_dir(k0, k1, k2, i), p.steps_diffuse, p.n_diffuse,
+                                                         blk, lb, st, ms);
+            total += st;
+            bool handed = false;
+            if constexpr (WAVES == 2) {
+                if (wave == 1) { lds_cone[i - 3][lane] = make_float4(c.x, c.y, c.z, c.w); handed = true; }
+            }
+            if (!handed) ind = fold_cone(ind, i, c);
+            store_debug_cone(p, pixel_index, i, c, st, alive, alive);
+        }
+        if constexpr (WAVES == 2) {
+            __syncthreads();
+            if (wave == 0)
+                for (int i = 3; i < 6; ++i) ind = fold_cone(ind, i, lds_cone[i - 3][lane]);
+        }
+        if (wave == 0) {
+            const float4 v = make_float4(ind.x, ind.y, ind.z, ind.w);
+            if (LISTED) {
+                if (alive) p.dr_ind[pixel_index()] = v;
+            } else if (cx < cw && cy < ch) {
+                p.dr_coarse[(size_t)cy * cw + cx] = v;          // (no anchor: no sample -- zeros nobody reads)
+                p.dr_anchor[(size_t)cy * cw + cx] = (uint8_t)code;
+            }
+            wave_marched += (uint32_t)__popcll(ballot64(alive));
+        }
+        if (WAVES == 2) __syncthreads();          // lds_cone is written again by the next round
+        for (int off = 32; off > 0; off >>= 1) total += __shfl_xor(total, off);
+        wave_steps += (unsigned long long)total;
+    }
+    if (lane == 0) {
+        const uint32_t slot = (blockIdx.x * WAVES + wave) & (VCT_DR_COUNTERS - 1);
+        if (wave_steps) atomicAdd(p.dr_ctr + slot, wave_steps);
+        if (wave_marched) atomicAdd(p.dr_ctr + VCT_DR_COUNTERS + slot, (unsigned long long)wave_marched);
+    }
+    flush_stats(p, ms, lane);
+}
+
+// One wave per 8x8 tile, lane = pixel.  An anchor copies its quad's sample; any other live pixel tests the four
+// candidates of include/vct.h in their order and interpolates, or -- no candidate accepted -- joins the fill list.
+__global__ void __launch_bounds__(256)
+k_diffuse_resolve(const VctTraceParams p) {
+    const int lane = threadIdx.x & 63;
+    const int tile = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    if (tile >= p.tiles_x * p.tiles_y) return;
+    const int ty = tile / p.tiles_x, tx = tile - ty * p.tiles_x;
+    const int x = tx * VCT_TILE + (lane & 7), y = ty * VCT_TILE + (lane >> 3);
+    const float* gb = p.gbuf + (size_t)tile * (VCT_GB_NPLANES * VCT_TILE_PIX) + lane;
+    const bool in_frame = x < p.width && y < p.height;
+    const bool alive = in_frame && !(gb_plane(gb, 18) < 0.5f);
+    const int cw = (p.width + 1) >> 1, ch = (p.height + 1) >> 1;
+    const size_t pix = (size_t)y * p.width + x;
+    bool marched = false, fill = false;
+    if (alive) {
+        const int qx = x >> 1, qy = y >> 1;
+        if ((uint32_t)p.dr_anchor[(size_t)qy * cw + qx] == (uint32_t)(((y & 1) << 1) | (x & 1))) {
+            marched = true;
+            p.dr_ind[pix] = p.dr_coarse[(size_t)qy * cw + qx];
+        } else {
+            const F3 Pp = gb_planes3(gb, 0), np_ = gb_planes3(gb, 3);
+            const float lp = dot3_rn(np_, np_);
+            const float plane_tol = __fmul_rn(__fmul_rn(VCT_DIFFUSE_RATE_PLANE_TOL, __fmul_rn(p.vs, p.vs)), lp);
+            const int sx = (x & 1) ? 1 : -1, sy = (y & 1) ? 1 : -1;
+            float4 S = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            int W = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {          // own quad 9, horizontal neighbour 3, vertical neighbour 3, diagonal 1
+                const int ccx = qx + ((k & 1) ? sx : 0), ccy = qy + ((k & 2) ? sy : 0);
+                const float wgt = k == 0 ? 9.0f : (k == 3 ? 1.0f : 3.0f);
+                float4 t = make_float4(0.0f, 0.0f, 0.0f, 0.0f);          // a rejected candidate contributes +0
+                if (ccx >= 0 && ccx < cw && ccy >= 0 && ccy < ch) {
+                    const uint32_t code = p.dr_anchor[(size_t)ccy * cw + ccx];
+                    if (code != VCT_DR_NO_ANCHOR) {
+                        const float* ga = gb_of_pixel(p, 2 * ccx + (int)(code & 1u), 2 * ccy + (int)(code >> 1));
+                        const F3 Pk = gb_planes3(ga, 0), nk = gb_planes3(ga, 3);
+                        const float dn = dot3_rn(np_, nk), lk = dot3_rn(nk, nk);
+                        const float d = dot3_rn(f3(__fsub_rn(Pk.x, Pp.x), __fsub_rn(Pk.y, Pp.y), __fsub_rn(Pk.z, Pp.z)), np_);
+                        if (dn > 0.0f && __fmul_rn(dn, dn) >= __fmul_rn(VCT_DIFFUSE_RATE_NORMAL_COS2, __fmul_rn(lp, lk)) &&
+                            __fmul_rn(d, d) <= plane_tol) {
+                            const float4 I = p.dr_coarse[(size_t)ccy * cw + ccx];
+                            W += k == 0 ? 9 : (k == 3 ? 1 : 3);
+                            t = make_float4(__fmul_rn(wgt, I.x), __fmul_rn(wgt, I.y), __fmul_rn(wgt, I.z), __fmul_rn(wgt, I.w));
+                        }
+                    }
+                }
+                if (k == 0) S = t;
+                else S = make_float4(__fadd_rn(S.x, t.x), __fadd_rn(S.y, t.y), __fadd_rn(S.z, t.z), __fadd_rn(S.w, t.w));
+            }
+            if (W > 0) {
+                const float fW = (float)W;
+                p.dr_ind[pix] = make_float4(div_rn(S.x, fW), div_rn(S.y, fW), div_rn(S.z, fW), div_rn(S.w, fW));
+            } else {
+                marched = fill = true;
+            }
+        }
+    }
+    // debug outputs: a pixel that marches nothing of its own shows 0 steps and zero cones 0..5
+    if (in_frame && !marched) {
+        if (p.dbg_steps)
+            for (int i = 0; i < 6; ++i) p.dbg_steps[pix * 7 + i] = 0;
+        if (p.dbg_cones && alive)
+            for (int i = 0; i < 24; ++i) p.dbg_cones[pix * 28 + i] = 0.0f;
+    }
+    // the fill list: one reservation per wave
+    const unsigned long long m = ballot64(fill);
+    if (m != 0ull) {
+        uint32_t base = 0u;
+        if (lane == 0) base = (uint32_t)atomicAdd(p.dr_ctr + 2 * VCT_DR_COUNTERS, (unsigned long long)__popcll(m));
+        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+        if (fill) p.dr_list[base + lane_rank(m)] = (uint32_t)pix;
     }
 }
 
@@ -1327,9 +1529,37 @@ void launch_split(const VctTraceParams& p, int blocks, hipStream_t s) {
     else hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, false, COMP>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
 }
 
+// the four launches of a half-rate pass (p.dr_ind set: whole frame, default kernel, p.comp on); marks: see vct_launch_trace
+template <bool WRAP, int FASTDIV, int WAVES>
+void launch_point_march(const VctTraceParams& p, bool listed, int blocks, hipStream_t s) {
+    if (listed) hipLaunchKernelGGL((k_point_march<WRAP, FASTDIV, true, WAVES>), dim3(blocks), dim3(64 * WAVES), 0, s, p);
+    else hipLaunchKernelGGL((k_point_march<WRAP, FASTDIV, false, WAVES>), dim3(blocks), dim3(64 * WAVES), 0, s, p);
+}
+template <bool WRAP, int FASTDIV>
+hipError_t launch_half_rate(const VctTraceParams& p, int blocks, hipStream_t s, const hipEvent_t* marks) {
+    auto mark = [&](int i) { return marks ? hipEventRecord(marks[i], s) : hipSuccess; };
+    hipError_t e = hipMemsetAsync(p.dr_ctr, 0, VCT_DR_CTR_WORDS * sizeof(unsigned long long), s);
+    if (e != hipSuccess) return e;
+    const int cw = (p.width + 1) >> 1, ch = (p.height + 1) >> 1;
+    const int coarse_blocks = ((cw + 7) >> 3) * ((ch + 7) >> 3);
+    if (p.dr_waves == 2) launch_point_march<WRAP, FASTDIV, 2>(p, false, coarse_blocks, s);
+    else launch_point_march<WRAP, FASTDIV, 1>(p, false, coarse_blocks, s);
+    if ((e = hipGetLastError()) != hipSuccess || (e = mark(0)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_diffuse_resolve, dim3((p.tiles_x * p.tiles_y + 3) / 4), dim3(256), 0, s, p);
+    if ((e = hipGetLastError()) != hipSuccess || (e = mark(1)) != hipSuccess) return e;
+    // over the list's device-side count: enough workgroups for a frame of fill pixels, at most the bounce's grid
+    const long long full = ((long long)p.width * p.height + 63) / 64;
+    const int listed_blocks = (int)(full < 256 * 24 ? full : 256 * 24);
+    if (p.dr_waves == 2) launch_point_march<WRAP, FASTDIV, 2>(p, true, listed_blocks, s);
+    else launch_point_march<WRAP, FASTDIV, 1>(p, true, listed_blocks, s);
+    if ((e = hipGetLastError()) != hipSuccess || (e = mark(2)) != hipSuccess) return e;
+    hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, true, true, true>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
+    return hipGetLastError();
+}
+
 // `loose`: vct_launch_trace's decision to run variant 3's kernel
 template <bool WRAP, int FASTDIV>
-hipError_t launch_v(const VctTraceParams& p, int variant, bool loose, hipStream_t s) {
+hipError_t launch_v(const VctTraceParams& p, int variant, bool loose, hipStream_t s, const hipEvent_t* marks) {
     const int ntiles = p.ntiles;
     if (!p.aniso && (variant == 1 || variant == 2)) {      // the anisotropic option exists in the default kernel only
         const int nblocks = (ntiles + VCT_WAVES_PER_BLOCK - 1) / VCT_WAVES_PER_BLOCK;
@@ -1356,6 +1586,7 @@ hipError_t launch_v(const VctTraceParams& p, int variant, bool loose, hipStream_
     }
     // lighting components (a mask other than VCT_SHOW_ALL, or per-component outputs): the COMP instantiation of the same
     // branch; the host refuses them with variants 1 .. 4, so only the branches below need one
+    if (p.dr_ind) return launch_half_rate<WRAP, FASTDIV>(p, blocks, s, marks);
     if (p.comp) launch_split<WRAP, FASTDIV, true>(p, blocks, s);
     else launch_split<WRAP, FASTDIV, false>(p, blocks, s);
     return hipGetLastError();
@@ -1440,7 +1671,10 @@ hipError_t vct_launch_bounce(const VctTraceParams& p, hipStream_t s) {
 // chains: the default kernel); 4 the default kernel over the live-pixel compaction (p.vt_pix set by the caller).
 // p.ntiles is set here.  *march_form (optional) receives the division form of the launch as vct_get_stage_counts reports
 // it -- 1 IEEE, 2 the verified product, 3 variant 3's x * r -- also for an empty row range, which launches nothing.
-hipError_t vct_launch_trace(const VctTraceParams& params, int variant, hipStream_t s, int* march_form) {
+// p.dr_ind set: a half-rate pass (vct_set_diffuse_rate(ctx, 2)) -- coarse march, resolve, listed march, then the trace
+// kernel that composites; whole frames of the default kernel with p.comp on only.  marks (optional): three events
+// recorded between those four launches.
+hipError_t vct_launch_trace(const VctTraceParams& params, int variant, hipStream_t s, int* march_form, const hipEvent_t* marks) {
     VctTraceParams p = params;
     const int rstride = p.row_stride > 1 ? p.row_stride : 1;
     p.ntiles = ((p.tile_row1 - p.tile_row0 + rstride - 1) / rstride) * p.tiles_x;
@@ -1448,9 +1682,12 @@ hipError_t vct_launch_trace(const VctTraceParams& params, int variant, hipStream
     if (march_form) *march_form = loose ? 3 : (p.fast_div ? 2 : 1);
     if (p.ntiles <= 0) return hipSuccess;
     if ((rstride > 1 || p.pack_rows) && !vct_variant_takes_row_subsets(variant)) return hipErrorInvalidValue;
+    if (p.dr_ind && (variant != 0 || p.aniso || p.cells_biased || !p.comp || rstride > 1 || p.pack_rows || p.tile_row0 != 0 ||
+                     p.tile_row1 != p.tiles_y))
+        return hipErrorInvalidValue;
     if (p.wrap_repeat)
-        return p.fast_div ? launch_v<true, true>(p, variant, loose, s)
-                          : launch_v<true, false>(p, variant, loose, s);
-    return p.fast_div ? launch_v<false, true>(p, variant, loose, s)
-                      : launch_v<false, false>(p, variant, loose, s);
+        return p.fast_div ? launch_v<true, true>(p, variant, loose, s, marks)
+                          : launch_v<true, false>(p, variant, loose, s, marks);
+    return p.fast_div ? launch_v<false, true>(p, variant, loose, s, marks)
+                      : launch_v<false, false>(p, variant, loose, s, marks);
 }

@@ -205,6 +205,11 @@ struct Voxel_Cone_Tracing {
     // (vct_set_trace_timing: those were most of the gap a second slot hides): configs[1] 0.70 -> 0.69 ms per Render(),
     // erratic at configs[4].  Frames that are whole GI passes (DynamicLight) stay on one slot.  Set before init.
     int FramesInFlight = 1;
+    // 2: the six diffuse cones are marched for one pixel per 2x2 quad and the others take a depth- and normal-aware mean
+    // of the nearest four (vct_set_diffuse_rate, include/vct.h: no reference counterpart -- the shader marches them per
+    // fragment); pixels on edges and thin geometry march their own.  1 (default): every pixel, the reference's frame.
+    // Handed over by every Render(), like the Show* switches.  Not on a rank of a multi-GPU run.
+    int DiffuseRate = 1;
     int Bounces = 1;    // 2 = re-inject the lit voxels once (the "2 bounces" of the reference's README.md:16,
                         // which its code does not implement: VCT.h:138-139 injects once); set before init
 
@@ -299,6 +304,7 @@ struct Voxel_Cone_Tracing {
         if (!ctx || !model.scene) return;
         vct_set_ambient_factor(ctx, AmbientFactor);
         if (!check(vct_set_lighting_components(ctx, ShowMask()), "vct_set_lighting_components")) return;
+        if (!check(vct_set_diffuse_rate(ctx, DiffuseRate), "vct_set_diffuse_rate")) return;
         const float cam[3] = {camera.position.x, camera.position.y, camera.position.z};   // VCT.h:167
         const float L[3] = {lightDirection.x, lightDirection.y, lightDirection.z};         // VCT.h:168
         vct_set_camera_position(ctx, cam);
@@ -332,7 +338,9 @@ struct Voxel_Cone_Tracing {
             return;
         }
         if (!check(vct_render_gbuffer(ctx, vp), "vct_render_gbuffer")) return;
-        if (!check(vct_trace_resident_rows(ctx, 0, (screen_height + 7) / 8), "vct_trace_resident_rows")) return;
+        if (DiffuseRate == 2) {                                  // whole frames only: no tile-row call at rate 2
+            if (!check(vct_trace_resident(ctx), "vct_trace_resident")) return;
+        } else if (!check(vct_trace_resident_rows(ctx, 0, (screen_height + 7) / 8), "vct_trace_resident_rows")) return;
         frame_on_host = false;
     }
 

@@ -6,8 +6,10 @@
 //
 //   vct_demo [--scene procedural:atrium|procedural:atrium-textured|procedural:bistro|procedural:cornell] [--voxels 128] [--size 1280x720]
 //            [--shadow 4096] [--frames 3] [--bounces 1|2] [--ppm out.ppm] [--gpus N] [--dynamic-light] [--frames-in-flight 1|2]
-//            [--show diffuse,indirect-diffuse,specular,indirect-specular,ao]
+//            [--show diffuse,indirect-diffuse,specular,indirect-specular,ao] [--diffuse-rate 1|2]
 //
+// --diffuse-rate 2: the six diffuse cones at half screen rate with a depth- and normal-aware upsampling
+//   (Voxel_Cone_Tracing::DiffuseRate, vct_set_diffuse_rate); single GPU only.  Default 1.
 // --show LIST: the lighting components shown (the reference's Show* switches, VCT.h:51); the ones not listed are off.
 //   Default: all five.
 // --frames-in-flight 2: consecutive Render() calls alternate between two frame slots (Voxel_Cone_Tracing::FramesInFlight):
@@ -78,7 +80,7 @@ static int launch_ranks(int gpus, int argc, char** argv) {
 
 int main(int argc, char** argv) {
     int w = SCREEN_WIDTH, h = SCREEN_HEIGHT, frames = 3, voxels = 128, shadow = 4096, bounces = 1;
-    int gpus = 0, rank = -1, in_flight = 1;
+    int gpus = 0, rank = -1, in_flight = 1, diffuse_rate = 1;
     const char* scene = "procedural:atrium";
     const char* ppm = nullptr;
     bool dynamic_light = false;
@@ -103,6 +105,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--ppm")) ppm = argv[++i];
         else if (!strcmp(argv[i], "--frames-in-flight")) in_flight = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--show")) show = argv[++i];
+        else if (!strcmp(argv[i], "--diffuse-rate")) diffuse_rate = atoi(argv[++i]);
     }
     GLFWwindow* window = nullptr;          // no window system on a compute node
 
@@ -122,6 +125,7 @@ int main(int argc, char** argv) {
     voxel_cone_tracing.Bounces = bounces;
     voxel_cone_tracing.DynamicLight = dynamic_light;       // every Render() = one whole GI pass (vct_gi_pass)
     voxel_cone_tracing.FramesInFlight = in_flight;
+    voxel_cone_tracing.DiffuseRate = diffuse_rate;
     if (show) {                                             // --show: the listed Show* switches on, the others off
         bool* flags[5] = {&voxel_cone_tracing.ShowDiffuse, &voxel_cone_tracing.ShowIndirectDiffuse, &voxel_cone_tracing.ShowSpecular,
                           &voxel_cone_tracing.ShowIndirectSpecular, &voxel_cone_tracing.ShowAmbientOcclusion};

@@ -599,6 +599,49 @@ def test_heavy_bricks_are_cut_into_chunks(vct, oracle, with_shadow):
         assert np.array_equal(ctx.download_chain(), chain0)
 
 
+@pytest.mark.parametrize("with_shadow", [False, True])
+def test_heavy_textured_bricks_with_attributes_are_cut_into_chunks(vct, oracle, with_shadow):
+    """The same crowding with stored per-fragment albedos (a mip-mapped diffuse texture, per-triangle coordinates) AND
+    voxel attributes: the k_voxelize_bricks<ATTR, FALB> instantiation leaving through the multi-chunk exit into
+    k_vox_resolve_multi<true>.  V = 16 is 2 x 2 x 2 bricks; 3,000 triangles put ~9,200 fragments into one of them (three
+    chunks; counted with the oracle).  Material 4 keeps its flat colour.  Twice in a row: the HBM sums must return to zero."""
+    V = 16
+    r = np.random.default_rng(5)
+    ntri = 3000
+    c = np.array([[[-300.0, 150.0, 420.0]]]) + r.normal(scale=60.0, size=(ntri, 1, 3))
+    pos = (c + r.normal(scale=70.0, size=(ntri, 3, 3))).astype(np.float32)
+    mat = r.integers(0, 5, ntri).astype(np.int32)
+    alb = r.uniform(0.1, 1.0, (5, 4)).astype(np.float32)
+    uv = r.uniform(-1.0, 2.0, (ntri, 6)).astype(np.float32)
+    tex = r.integers(0, 256, (4, 4, 4), dtype=np.uint8)
+    tex[..., 3] = 255
+    mat_tex = np.full((5, 3), -1, np.int32)
+    mat_tex[:4, 0] = 0
+    depth, vp = light_setup(128, 9) if with_shadow else (None, None)
+    p = oracle.default_params(V)
+    sc = oracle.make_scene(pos, mat, alb, shadow_depth=depth, light_vp=vp, uv=uv, mat_tex=mat_tex, textures=[tex],
+                           mipmaps=True)
+    l0, want_alb, want_nrm = oracle.voxelize_conservative_attr(p, sc)
+    fragments = oracle.voxelize_conservative(p, sc, want_acc=True)[1][..., 3].astype(np.int64)
+    assert fragments.reshape(2, 8, 2, 8, 2, 8).sum(axis=(1, 3, 5)).max() > 4096          # a brick above the chunk limit
+    flat = oracle.voxelize_conservative_attr(p, oracle.make_scene(pos, mat, alb, shadow_depth=depth, light_vp=vp))
+    assert (flat[0] != l0).any() and (flat[1] != want_alb).any()                         # the texture matters
+    chain0 = oracle.build_mips(l0)
+    with make_ctx(vct, V, 8, 8, voxel_attributes=1, texture_mipmaps=1) as ctx:
+        ctx.upload_triangles(pos, mat, alb)
+        ctx.upload_mesh_uvs(uv)
+        ctx.upload_textures([tex], mat_tex)
+        if with_shadow:
+            ctx.upload_shadow_map(depth, vp)
+        counts = ctx.stage_counts()
+        assert counts["vox_items"] > counts["accumulator_bricks"]                        # a slot of several work items
+        for _ in range(2):
+            ctx.voxelize(); ctx.inject_light(); ctx.build_mips()
+            assert np.array_equal(ctx.download_chain(), chain0)
+            got_alb, got_nrm = ctx.voxel_attributes()
+            assert np.array_equal(got_alb, want_alb) and np.array_equal(got_nrm, want_nrm)
+
+
 def test_second_bounce_dense_scene_overflows_the_voxel_list(vct, oracle):
     """More than 1/8 of the grid occupied: the compacted list of occupied voxels (capacity V^3 / 8) overflows and the
     bricks that did not fit are marched brick by brick (k_bounce_bricks).  Same level 0, chain and step count."""

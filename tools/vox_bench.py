@@ -42,26 +42,3 @@ for mips in (1, 0):
     print(f"V={V} texture_mipmaps={mips} shadow={shadow}: voxelize {best[0]:.4f} ms  inject {best[1]:.4f} ms  mips {best[2]:.4f} ms   "
           f"fragments {c['vox_candidates']}  bricks {c['touched_bricks']}  triangles {c['triangles']}  items {c.get('vox_items')}")
   del ctx
-raise SystemExit(0)
-
-
-def ev():
-    return torch.cuda.Event(enable_timing=True)
-
-
-for shadow in (True, False):
-    if shadow:
-        ctx.render_shadow_map(inp["light_vp"])
-    else:
-        ctx.upload_shadow_map(None, None)
-    best = None
-    with torch.cuda.stream(st):
-        for _ in range(8):
-            e = [ev() for _ in range(4)]
-            e[0].record(); ctx.voxelize(); e[1].record(); ctx.inject_light(); e[2].record(); ctx.build_mips(); e[3].record()
-            ctx.synchronize()
-            t = [e[i].elapsed_time(e[i + 1]) for i in range(3)]
-            best = t if best is None else [min(a, b) for a, b in zip(best, t)]
-    c = ctx.stage_counts()
-    print(f"V={V} shadow={shadow}: voxelize {best[0]:.4f} ms  inject {best[1]:.4f} ms  mips {best[2]:.4f} ms   "
-          f"fragments {c['vox_candidates']}  bricks {c['touched_bricks']}  triangles {c['triangles']}")

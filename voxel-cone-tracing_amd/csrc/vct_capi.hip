@@ -471,7 +471,6 @@ VctVoxParams vox_params(const vct_ctx* c, const VctVoxelPlan& v) {
     p.slot_brick = v.slot_brick.get();
     p.items = v.items.get();
     p.nitems = v.n_items;
-    p.chunk = v.chunk;
     p.acc2 = v.acc2.get();
     p.acc2_attr = v.acc2_attr.get();
     p.multi_slot = v.multi_slot.get();
@@ -1429,7 +1428,6 @@ int vct_voxelize(vct_ctx* c, int32_t mode) {
         HIP_TRY(c, hipMemsetAsync(c->brick_flags.get(), 0, nbricks * sizeof(uint32_t), cur(c).stream));
     }
     VctVoxParams p = vox_params(c, v);
-    p.mode = mode;
     if (mode == VCT_VOX_REFERENCE) {
         glm_voxel_projections(c, p.proj);
         HIP_TRY(c, vct_launch_voxelize_reference(p, v.ref_big.get() + 1, v.ref_big.get(), cur(c).stream));
@@ -1457,10 +1455,15 @@ int vct_inject_light(vct_ctx* c) {
     HIP_TRY(c, hipSetDevice(c->device));
     PIPE_TRY(pipeline_join(c));       // level 0 is rewritten: the other slot's trace may still read the chain
     const VctVoxelPlan& v = c->vox;
-    HIP_TRY(c, vct_launch_resolve(v.acc.get(), v.brick_slot.get(), c->chain.get(), c->brick_flags.get(), c->brick_prev.get(),
-                                  c->cfg.voxel_dim, c->level0_dirty, nullptr, v.attr_albedo.get(), v.attr_normal.get(),
-                                  c->acc_mode == VCT_VOX_REFERENCE, v.stage.get(), v.stage_albedo.get(), v.stage_normal.get(),
-                                  cur(c).stream));
+    VctResolveArgs a;
+    memset(&a, 0, sizeof(a));
+    a.level0 = c->chain.get(); a.flags = c->brick_flags.get(); a.prev = c->brick_prev.get(); a.brick_slot = v.brick_slot.get();
+    if (c->acc_mode == VCT_VOX_REFERENCE) a.acc = v.acc.get();
+    else {
+        a.stage = v.stage.get(); a.stage_albedo = v.stage_albedo.get(); a.stage_normal = v.stage_normal.get();
+        a.attr_albedo = v.attr_albedo.get(); a.attr_normal = v.attr_normal.get();
+    }
+    HIP_TRY(c, vct_launch_resolve(a, c->cfg.voxel_dim, c->level0_dirty, cur(c).stream));
     c->vox.acc_pending = false;
     c->level0_dirty = false;
     c->use_chain_b = false;

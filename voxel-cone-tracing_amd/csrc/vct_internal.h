@@ -366,7 +366,6 @@ struct VctVoxParams {
     // [multi][512][3]); a second small kernel resolves those slots (multi_slot[multi]) and re-zeroes the accumulators.
     const uint4* items;        // [nitems] (slot, first fragment, fragments, index among the multi-chunk slots or ~0)
     uint32_t nitems;
-    uint32_t chunk;            // fragments per work item
     unsigned long long* acc2;
     unsigned long long* acc2_attr;
     const uint32_t* multi_slot;
@@ -376,8 +375,23 @@ struct VctVoxParams {
     uint32_t* stage_normal;
     uint32_t* brick_flags;     // [V^3 / 512] raised for bricks written by a pass, consumed by the sparse resolve
     float proj[48];            // ProjX, ProjY, ProjZ (VCT.h:128-134), column-major; reference mode only
-    int32_t mode;
     VctTextures tex;           // diffuse textures + texture coordinates (vox.fs:56); texels == null: flat colours
+};
+
+// what the sparse resolve of vct_inject_light reads and writes (vct_voxelize.hip k_resolve_sparse)
+struct VctResolveArgs {
+    uint32_t* level0;                // [V^3] Morton
+    uint32_t* flags;                 // [V^3 / 512] bricks written by the pass (consumed) ...
+    uint32_t* prev;                  // ... and by the pass before it (updated)
+    const uint32_t* brick_slot;      // [V^3 / 512]
+    // north-star mode: the staging pool of the pass, [nslots][512] each; the attribute pair is null without
+    // config.voxel_attributes and is copied into the context's pooled attributes.  stage == null: reference mode
+    const uint32_t* stage;
+    const uint32_t* stage_albedo;
+    const uint32_t* stage_normal;
+    uint32_t* attr_albedo;
+    uint32_t* attr_normal;
+    unsigned long long* acc;         // reference mode: [nslots][512][2] last-writer words (re-zeroed)
 };
 
 // inputs of the raster stages (vct_raster.hip); all device pointers
@@ -478,10 +492,7 @@ hipError_t vct_launch_frag_scatter(const uint2* frags, uint32_t n, const uint32_
 hipError_t vct_launch_voxelize(const VctVoxParams& p, hipStream_t s);
 hipError_t vct_launch_frag_geom(const VctVoxParams& p, float2* bary, float* frag_alb, hipStream_t s);
 hipError_t vct_launch_tri_nrm(const VctVoxParams& p, uint32_t* tri_nrm, hipStream_t s);
-hipError_t vct_launch_resolve(unsigned long long* acc, const uint32_t* brick_slot, uint32_t* level0, uint32_t* flags,
-                              uint32_t* prev, int V, bool dense, unsigned long long* acc_attr,
-                              uint32_t* attr_albedo, uint32_t* attr_normal, bool reference, const uint32_t* stage,
-                              const uint32_t* stage_albedo, const uint32_t* stage_normal, hipStream_t s);
+hipError_t vct_launch_resolve(const VctResolveArgs& a, int V, bool dense, hipStream_t s);
 // mark[b] != 0 -> slot[b] = next free slot (order irrelevant), else VCT_NO_SLOT; *count = slots handed out
 hipError_t vct_launch_assign_slots(const uint32_t* mark, uint32_t* slot, uint32_t* count, uint32_t nbricks, hipStream_t s);
 hipError_t vct_launch_slot_bricks(const uint32_t* slot, uint32_t nbricks, uint32_t* slot_brick, hipStream_t s);

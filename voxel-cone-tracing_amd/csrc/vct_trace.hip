@@ -1250,13 +1250,6 @@ k_diffuse_resolve(const VctTraceParams p) {
     }
 }
 
-__device__ __forceinline__ uint32_t to_unorm8_dev(float f) {     // [GL] float -> unorm8, round to nearest
-    const float s = f * 255.0f + 0.5f;
-    if (!(s > 0.0f)) return 0u;
-    if (s >= 255.0f) return 255u;
-    return (uint32_t)(int)s;
-}
-
 // Second bounce (oracle/vct_oracle.h vcto_bounce), three kernels:
 //   k_bounce_list   one wave per touched 8^3 brick (found through the voxelizer's slot table): copies the brick
 //                   into the bounce chain (untouched voxels keep their bounce-0 value), compacts its occupied
@@ -1298,9 +1291,9 @@ __device__ __forceinline__ void bounce_voxels(const VctTraceParams& p, bool aliv
     }
     if (alive) {
         const float occlusion = 1.0f - ind.w;
-        const uint32_t r = to_unorm8_dev(unorm8(src & 0xffu) + unorm8(aq & 0xffu) * (occlusion * ind.x));
-        const uint32_t g = to_unorm8_dev(unorm8((src >> 8) & 0xffu) + unorm8((aq >> 8) & 0xffu) * (occlusion * ind.y));
-        const uint32_t bl = to_unorm8_dev(unorm8((src >> 16) & 0xffu) + unorm8((aq >> 16) & 0xffu) * (occlusion * ind.z));
+        const uint32_t r = vct_float_to_unorm8(unorm8(src & 0xffu) + unorm8(aq & 0xffu) * (occlusion * ind.x));
+        const uint32_t g = vct_float_to_unorm8(unorm8((src >> 8) & 0xffu) + unorm8((aq >> 8) & 0xffu) * (occlusion * ind.y));
+        const uint32_t bl = vct_float_to_unorm8(unorm8((src >> 16) & 0xffu) + unorm8((aq >> 16) & 0xffu) * (occlusion * ind.z));
         p.bounce_out[vox] = r | (g << 8) | (bl << 16) | (src & 0xff000000u);
     } else {
         total = 0;

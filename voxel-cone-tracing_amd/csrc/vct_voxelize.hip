@@ -2,29 +2,34 @@
 //
 // Replaces the reference's voxelization draw (VCT.h:213-245): S/Voxelization.vs:15-22 (world
 // position, shadow coordinate), S/Voxelization.gs:22-51 (dominant axis), S/Voxelization.fs:18-89
-// (PCF, voxel index, imageStore of albedo*shadow).  North-star mode: conservative triangle /
-// voxel-box overlap (Schwarz & Seidel 2010) instead of pixel-centre raster, and instead of the
-// racy last-writer imageStore every fragment adds its unorm8 value into per-voxel 64-bit integer
-// accumulators (sumR|sumG, sumB|count), which is exact and order-independent; vct_launch_resolve
-// turns them into the rounded mean.  fp32 operation order mirrors the scalar oracle
-// (compile with -ffp-contract=off).
+// (PCF, voxel index, imageStore of albedo*shadow).  fp32 operation order mirrors the scalar oracle
+// (compile with -ffp-contract=off).  Two modes:
 //
-// Work distribution (north-star mode): BRICK-parallel, no global atomics.  Which voxels a triangle overlaps depends
-// only on geometry, V and G, so the fragment list is built ONCE when the triangles are uploaded (k_vox_plan*: exact
-// conservative overlap, entries (triangle, Morton voxel)) and sorted by 8^3 brick (counting sort: k_frag_count /
-// k_frag_scatter).  What a fragment contributes apart from the light -- its barycentrics on its triangle and its albedo
-// (the mip-mapped diffuse fetch of vox.fs:56, or the material's colour) -- is evaluated once as well (k_frag_geom, round 4)
-// and stored per sorted fragment.  A voxelize pass -- e.g. after the light moved -- is then one workgroup per touched
-// brick (k_voxelize_bricks): its threads read their fragments' stored values, transform the triangle's vertices by the
-// light matrix, run the 25-tap PCF and add albedo * shadow into the brick's 512 accumulators IN LDS (64-bit ds_add: the exact, order-independent "atomic RGBA average"), then the same workgroup
-// resolves the rounded means and writes the brick's 2 KiB of texels -- coalesced, once.  Rounds 1-2 accumulated with
-// two device-scope 64-bit atomics per fragment into per-brick pools in HBM and resolved in a second kernel: 0.098 +
-// 0.018 ms at configs[1], bound by the atomic unit.  All fragments of a brick lie within 8 voxels of each other, so
-// their 25-tap shadow windows overlap: coherent fetches.
+// North-star mode: conservative triangle / voxel-box overlap (Schwarz & Seidel 2010) instead of pixel-centre raster,
+// and the exact, order-independent rounded mean of the fragments of a voxel instead of the racy last-writer imageStore.
+//   plan      Which voxels a triangle overlaps depends only on geometry, V and G, so the fragment list is built ONCE when
+//             the triangles are uploaded (k_vox_plan / k_vox_plan_big: entries (triangle, Morton voxel)).
+//   sort      Counting sort of the list by 8^3 brick; every brick the mesh can touch gets a SLOT (k_frag_mark,
+//             k_assign_slots, k_frag_count, k_frag_scatter, k_slot_bricks).
+//   constants What a fragment contributes apart from the light -- its barycentrics on its triangle and its albedo (the
+//             mip-mapped diffuse fetch of vox.fs:56; scenes with textures only) -- is stored per sorted fragment
+//             (k_frag_geom), and the quantised face normals per triangle (k_tri_nrm).
+//   LDS pass  A voxelize pass -- e.g. after the light moved -- is one workgroup per work item = up to VCT_VOX_CHUNK
+//             fragments of one slot (k_voxelize_bricks): its threads read their fragments' stored values, transform the
+//             triangle's vertices by the light matrix, run the 25-tap PCF and add unorm8(albedo * shadow) into the
+//             brick's 512 accumulators IN LDS (64-bit ds_add of sumR|sumG, sumB|count); the same workgroup resolves the
+//             rounded means and writes the brick's 2 KiB of texels into the slot's place in a STAGING pool -- coalesced,
+//             once, no global atomics.  Only the chunks of a slot above VCT_VOX_CHUNK meet in HBM accumulators, resolved
+//             by k_vox_resolve_multi.  All fragments of a brick lie within 8 voxels of each other, so their 25-tap shadow
+//             windows overlap: coherent fetches.
+//   resolve   vct_inject_light's sparse resolve (k_resolve_sparse) copies the staged slots of touched bricks into level 0
+//             and clears bricks that are no longer covered: vct_voxelize evaluates the light, vct_inject_light makes it
+//             visible.
+// Reference mode: the shaders as written (k_voxelize_reference*), last writer by atomicMax into per-slot words in HBM,
+// unpacked by the same sparse resolve.
 //
-// The texels of a pass go to a staging pool (one 2 KiB slot per brick the mesh can touch); vct_inject_light's sparse
-// resolve (k_resolve_sparse) copies the slots of touched bricks into level 0 and clears bricks that are no longer
-// covered -- vct_voxelize evaluates the light, vct_inject_light makes it visible, as before.
+// Both modes share the triangle front end (load_world_tri, shadow_coords, dominant_axis), the material (material_colour,
+// load_material, interp_uv, quad_duv, frag_albedo) and the fragment value (shadow_factor, lit_rgb8): DESIGN.md 3.2.
 #include "vct_internal.h"
 
 namespace {
@@ -160,14 +165,93 @@ __device__ __forceinline__ int pcf25(const uint32_t* __restrict__ words, uint32_
     return count;
 }
 
-__device__ __forceinline__ uint32_t to_unorm8(float f) {
-    const float s = f * 255.0f + 0.5f;
-    if (!(s > 0.0f)) return 0u;
-    if (s >= 255.0f) return 255u;
-    return (uint32_t)(int)s;
+// vox.fs:46: the PCF factor of a fragment with barycentrics (b0, b1, b2) on a triangle whose vertices have the shadow
+// coordinates dc; 1 without a shadow map
+__device__ __forceinline__ float shadow_factor(const VctVoxParams& p, const F3 dc[3], float b0, float b1, float b2) {
+    if (!p.shadow) return 1.0f;
+    const F3 c = {b0 * dc[0].x + b1 * dc[1].x + b2 * dc[2].x,
+                  b0 * dc[0].y + b1 * dc[1].y + b2 * dc[2].y,
+                  b0 * dc[0].z + b1 * dc[1].z + b2 * dc[2].z};
+    return __fdiv_rn((float)pcf25(p.shadow, p.shadow_ebase, p.shadow_size, c, 0.002f, p.shadow_tiles), 25.0f);
+}
+// vox.fs:88: unorm8(albedo * shadow), a channel per word
+struct Rgb8 { uint32_t r, g, b; };
+__device__ __forceinline__ Rgb8 lit_rgb8(const float alb[3], float sh) {
+    return {vct_float_to_unorm8(alb[0] * sh), vct_float_to_unorm8(alb[1] * sh), vct_float_to_unorm8(alb[2] * sh)};
 }
 
-struct TriSetup {
+// ---- the triangle front end of both modes -------------------------------------------------------------------------
+// vox.vs:21: world-space vertices (the record as three wide loads, not nine)
+__device__ __forceinline__ void load_world_tri(const VctVoxParams& p, int t, F3 w[3]) {
+    const VctTri9 rec = *reinterpret_cast<const VctTri9*>(p.pos + (size_t)t * 9);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float* q = rec.v + 3 * k;
+        w[k] = {q[0] * p.model_scale, q[1] * p.model_scale, q[2] * p.model_scale};
+    }
+}
+// vox.vs:18-19: the vertices in the light's clip space, as shadow-map coordinates
+__device__ __forceinline__ void shadow_coords(const VctVoxParams& p, const F3 w[3], F3 dc[3]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const F3 d = xform_point(p.light_vp, w[k]);
+        dc[k] = {d.x * 0.5f + 0.5f, d.y * 0.5f + 0.5f, d.z * 0.5f + 0.5f};
+    }
+}
+// vox.gs:24-39: 1 / 2 / 3 = the face normal is longest along x / y / z
+__device__ __forceinline__ int dominant_axis(const F3 w[3]) {
+    const F3 e1 = sub3(w[0], w[1]), e2 = sub3(w[2], w[0]);
+    const F3 nn = cross3(e1, e2);
+    const float len = __builtin_sqrtf(dot3(nn, nn));
+    const float nx = fabsf(__fdiv_rn(nn.x, len)), ny = fabsf(__fdiv_rn(nn.y, len)),
+                nz = fabsf(__fdiv_rn(nn.z, len));
+    if (nx >= ny && nx >= nz) return 1;
+    if (ny >= nx && ny >= nz) return 2;
+    return 3;
+}
+
+// What a fragment's albedo comes from: the material's colour, or its diffuse texture at the triangle's coordinates
+struct TriMaterial {
+    float alb[3];
+    float uv[3][2];     // TexCoord per vertex (vox.vs:17)
+    int tex;            // diffuse texture of the triangle's material or -1 (flat colour)
+};
+__device__ __forceinline__ void material_colour(const VctVoxParams& p, int t, float alb[3]) {
+    const float* c = p.albedo + 4 * (size_t)p.material[t];
+    alb[0] = c[0]; alb[1] = c[1]; alb[2] = c[2];
+}
+__device__ __forceinline__ void load_material(const VctVoxParams& p, int t, TriMaterial& r) {
+    material_colour(p, t, r.alb);
+    r.tex = vct_tex_of(p.tex, p.material[t], 0);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        r.uv[k][0] = r.tex >= 0 ? p.tex.uv[(size_t)t * 6 + 2 * k] : 0.0f;
+        r.uv[k][1] = r.tex >= 0 ? p.tex.uv[(size_t)t * 6 + 2 * k + 1] : 0.0f;
+    }
+}
+// the texture coordinate at barycentrics (c0, c1, c2)
+struct UV { float u, v; };
+__device__ __forceinline__ UV interp_uv(const TriMaterial& r, float c0, float c1, float c2) {
+    return {c0 * r.uv[0][0] + c1 * r.uv[1][0] + c2 * r.uv[2][0], c0 * r.uv[0][1] + c1 * r.uv[1][1] + c2 * r.uv[2][1]};
+}
+// texture() derivatives: the differences of the coordinate between the fragment (m) and its neighbours along the two
+// raster axes (x, y), on this triangle (mip-mapped textures; oracle/vct_oracle.h vcto_scene)
+__device__ __forceinline__ void quad_duv(UV m, UV x, UV y, float duv[4]) {
+    duv[0] = x.u - m.u; duv[1] = x.v - m.v; duv[2] = y.u - m.u; duv[3] = y.v - m.v;
+}
+// vox.fs:56: the fragment's albedo -- texture(DiffuseTexture, uv) with uv interpolated by the fragment's
+// barycentrics, or the flat material colour when the material has no diffuse texture
+__device__ __forceinline__ void frag_albedo(const VctVoxParams& p, const TriMaterial& r, float b0, float b1, float b2,
+                                            const float duv[4], float alb[3]) {
+    alb[0] = r.alb[0]; alb[1] = r.alb[1]; alb[2] = r.alb[2];
+    if (r.tex >= 0) {
+        const UV q = interp_uv(r, b0, b1, b2);
+        const float4 c = vct_tex_sample_lod(p.tex, r.tex, q.u, q.v, duv[0], duv[1], duv[2], duv[3]);
+        alb[0] = c.x; alb[1] = c.y; alb[2] = c.z;
+    }
+}
+
+struct TriSetup : TriMaterial {
     F3 g[3];     // voxel-space vertices
     F3 dc[3];    // shadow coordinates
     F3 n;
@@ -176,60 +260,26 @@ struct TriSetup {
     float de[3][3];
     int lo[3], hi[3];
     int ua, ub;
-    float area;
-    float alb[3];
-    float uv[3][2];     // TexCoord per vertex (vox.vs:17)
-    int tex;            // diffuse texture of the triangle's material or -1 (flat colour)
+    float area;         // twice the signed area of the in-plane triangle
     bool valid;
 };
-
-// vox.fs:56: the fragment's albedo -- texture(DiffuseTexture, uv) with uv interpolated by the fragment's
-// barycentrics, or the flat material colour when the material has no diffuse texture
-// duv: quad differences of the coordinate in the voxelization raster (mip-mapped textures; oracle/vct_oracle.h vcto_scene)
-template <class Setup>
-__device__ __forceinline__ void frag_albedo(const VctVoxParams& p, const Setup& r, float b0, float b1, float b2,
-                                            const float duv[4], float alb[3]) {
-    alb[0] = r.alb[0]; alb[1] = r.alb[1]; alb[2] = r.alb[2];
-    if (r.tex >= 0) {
-        const float u = b0 * r.uv[0][0] + b1 * r.uv[1][0] + b2 * r.uv[2][0];
-        const float v = b0 * r.uv[0][1] + b1 * r.uv[1][1] + b2 * r.uv[2][1];
-        const float4 c = vct_tex_sample_lod(p.tex, r.tex, u, v, duv[0], duv[1], duv[2], duv[3]);
-        alb[0] = c.x; alb[1] = c.y; alb[2] = c.z;
-    }
-}
-template <class Setup>
-__device__ __forceinline__ void load_tex_setup(const VctVoxParams& p, int t, Setup& r) {
-    r.tex = vct_tex_of(p.tex, p.material[t], 0);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        r.uv[k][0] = r.tex >= 0 ? p.tex.uv[(size_t)t * 6 + 2 * k] : 0.0f;
-        r.uv[k][1] = r.tex >= 0 ? p.tex.uv[(size_t)t * 6 + 2 * k + 1] : 0.0f;
-    }
+// the vertices in the plane the triangle is projected to (perpendicular to its dominant axis)
+struct InPlane { float x[3], y[3]; };
+__device__ __forceinline__ InPlane in_plane(const TriSetup& r) {
+    return {{comp(r.g[0], r.ua), comp(r.g[1], r.ua), comp(r.g[2], r.ua)},
+            {comp(r.g[0], r.ub), comp(r.g[1], r.ub), comp(r.g[2], r.ub)}};
 }
 
 __device__ __forceinline__ void setup_tri(const VctVoxParams& p, int t, TriSetup& r) {
     F3 w[3];
     const float fV = (float)p.V;
-    const VctTri9 rec = *reinterpret_cast<const VctTri9*>(p.pos + (size_t)t * 9);     // three wide loads, not nine
+    load_world_tri(p, t, w);
+    shadow_coords(p, w, r.dc);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float* q = rec.v + 3 * k;
-        w[k] = {q[0] * p.model_scale, q[1] * p.model_scale, q[2] * p.model_scale};   // vox.vs:21
-        const F3 d = xform_point(p.light_vp, w[k]);                                  // vox.vs:18
-        r.dc[k] = {d.x * 0.5f + 0.5f, d.y * 0.5f + 0.5f, d.z * 0.5f + 0.5f};          // vox.vs:19
+    for (int k = 0; k < 3; ++k)
         r.g[k] = {(__fdiv_rn(w[k].x, p.G) + 0.5f) * fV, (__fdiv_rn(w[k].y, p.G) + 0.5f) * fV,
                   (__fdiv_rn(w[k].z, p.G) + 0.5f) * fV};
-    }
-    // vox.gs:24-39 dominant axis
-    const F3 e1 = sub3(w[0], w[1]), e2 = sub3(w[2], w[0]);
-    F3 nn = cross3(e1, e2);
-    const float len = __builtin_sqrtf(dot3(nn, nn));
-    const float nx = fabsf(__fdiv_rn(nn.x, len)), ny = fabsf(__fdiv_rn(nn.y, len)),
-                nz = fabsf(__fdiv_rn(nn.z, len));
-    int axis;
-    if (nx >= ny && nx >= nz) axis = 1;
-    else if (ny >= nx && ny >= nz) axis = 2;
-    else axis = 3;
+    const int axis = dominant_axis(w);
 
     const F3 e[3] = {sub3(r.g[1], r.g[0]), sub3(r.g[2], r.g[1]), sub3(r.g[0], r.g[2])};
     r.n = cross3(e[0], e[1]);
@@ -262,13 +312,9 @@ __device__ __forceinline__ void setup_tri(const VctVoxParams& p, int t, TriSetup
     }
     r.ua = axis == 1 ? 1 : 0;
     r.ub = axis == 3 ? 1 : 2;
-    const float ax0 = comp(r.g[0], r.ua), ay0 = comp(r.g[0], r.ub);
-    const float ax1 = comp(r.g[1], r.ua), ay1 = comp(r.g[1], r.ub);
-    const float ax2 = comp(r.g[2], r.ua), ay2 = comp(r.g[2], r.ub);
-    r.area = (ax1 - ax0) * (ay2 - ay0) - (ax2 - ax0) * (ay1 - ay0);
-    const float* alb = p.albedo + 4 * (size_t)p.material[t];
-    r.alb[0] = alb[0]; r.alb[1] = alb[1]; r.alb[2] = alb[2];
-    load_tex_setup(p, t, r);
+    const InPlane a = in_plane(r);
+    r.area = (a.x[1] - a.x[0]) * (a.y[2] - a.y[0]) - (a.x[2] - a.x[0]) * (a.y[1] - a.y[0]);
+    load_material(p, t, r);
 }
 
 __device__ __forceinline__ bool overlap(const TriSetup& c, int i, int j, int k) {
@@ -285,6 +331,18 @@ __device__ __forceinline__ bool overlap(const TriSetup& c, int i, int j, int k) 
     return true;
 }
 
+// the centre of voxel (i, j, k) in that plane
+struct PlanePoint { float x, y; };
+__device__ __forceinline__ PlanePoint voxel_centre(const TriSetup& r, int i, int j, int k) {
+    const F3 ctr = {(float)i + 0.5f, (float)j + 0.5f, (float)k + 0.5f};
+    return {comp(ctr, r.ua), comp(ctr, r.ub)};
+}
+// (no reference code for this mode) the UNCLAMPED barycentrics of in-plane point q, from area cross products
+__device__ __forceinline__ void area_bary(const TriSetup& r, PlanePoint q, float& c0, float& c1) {
+    const InPlane a = in_plane(r);
+    c0 = __fdiv_rn((a.x[1] - q.x) * (a.y[2] - q.y) - (a.x[2] - q.x) * (a.y[1] - q.y), r.area);
+    c1 = __fdiv_rn((a.x[2] - q.x) * (a.y[0] - q.y) - (a.x[0] - q.x) * (a.y[2] - q.y), r.area);
+}
 // The barycentrics of the conservative fragment of triangle set-up `r` at voxel (i, j, k) (vox.fs has none: the oracle's
 // north-star mode evaluates the triangle at the voxel centre projected along the dominant axis, clamped into the
 // triangle), and -- for mip-mapped textures -- the differences of the texture coordinate one voxel further along each
@@ -292,37 +350,20 @@ __device__ __forceinline__ bool overlap(const TriSetup& c, int i, int j, int k) 
 // per fragment; the voxelize pass reads them back (round 4: the pass used to re-derive the whole triangle set-up --
 // nine IEEE divisions, the dominant axis, the in-plane area -- for every fragment, ~300 of its ~1,200 instructions).
 __device__ __forceinline__ void frag_bary(const TriSetup& r, int i, int j, int k, float& b0, float& b1) {
-    const F3 ctr = {(float)i + 0.5f, (float)j + 0.5f, (float)k + 0.5f};
-    const float cx = comp(ctr, r.ua), cy = comp(ctr, r.ub);
-    const float ax0 = comp(r.g[0], r.ua), ay0 = comp(r.g[0], r.ub);
-    const float ax1 = comp(r.g[1], r.ua), ay1 = comp(r.g[1], r.ub);
-    const float ax2 = comp(r.g[2], r.ua), ay2 = comp(r.g[2], r.ub);
-    b0 = __fdiv_rn((ax1 - cx) * (ay2 - cy) - (ax2 - cx) * (ay1 - cy), r.area);
-    b1 = __fdiv_rn((ax2 - cx) * (ay0 - cy) - (ax0 - cx) * (ay2 - cy), r.area);
+    area_bary(r, voxel_centre(r, i, j, k), b0, b1);
     b0 = fminf(fmaxf(b0, 0.0f), 1.0f);
     b1 = fminf(fmaxf(b1, 0.0f), 1.0f);
     const float sum = b0 + b1;
     if (sum > 1.0f) { b0 = __fdiv_rn(b0, sum); b1 = __fdiv_rn(b1, sum); }
 }
 __device__ __forceinline__ void frag_duv(const TriSetup& r, int i, int j, int k, float duv[4]) {
-    const F3 ctr = {(float)i + 0.5f, (float)j + 0.5f, (float)k + 0.5f};
-    const float cx = comp(ctr, r.ua), cy = comp(ctr, r.ub);
-    const float ax0 = comp(r.g[0], r.ua), ay0 = comp(r.g[0], r.ub);
-    const float ax1 = comp(r.g[1], r.ua), ay1 = comp(r.g[1], r.ub);
-    const float ax2 = comp(r.g[2], r.ua), ay2 = comp(r.g[2], r.ub);
-    // (no reference code for this mode) the UNCLAMPED barycentrics one voxel further along each in-plane axis
-    auto uv_at = [&](float qx, float qy, float& ou, float& ov) {
-        const float c0 = __fdiv_rn((ax1 - qx) * (ay2 - qy) - (ax2 - qx) * (ay1 - qy), r.area);
-        const float c1 = __fdiv_rn((ax2 - qx) * (ay0 - qy) - (ax0 - qx) * (ay2 - qy), r.area);
-        const float c2 = 1.0f - c0 - c1;
-        ou = c0 * r.uv[0][0] + c1 * r.uv[1][0] + c2 * r.uv[2][0];
-        ov = c0 * r.uv[0][1] + c1 * r.uv[1][1] + c2 * r.uv[2][1];
+    const PlanePoint c = voxel_centre(r, i, j, k);
+    auto uv_at = [&](float qx, float qy) {
+        float c0, c1;
+        area_bary(r, {qx, qy}, c0, c1);
+        return interp_uv(r, c0, c1, 1.0f - c0 - c1);
     };
-    float mu, mv, xu, xv, yu, yv;
-    uv_at(cx, cy, mu, mv);
-    uv_at(cx + 1.0f, cy, xu, xv);
-    uv_at(cx, cy + 1.0f, yu, yv);
-    duv[0] = xu - mu; duv[1] = xv - mv; duv[2] = yu - mu; duv[3] = yv - mv;
+    quad_duv(uv_at(c.x, c.y), uv_at(c.x + 1.0f, c.y), uv_at(c.x, c.y + 1.0f), duv);
 }
 
 // What a voxelize pass still needs of a fragment's triangle: the shadow coordinates of its vertices (they follow the
@@ -335,20 +376,12 @@ struct PassTri {
 };
 template <bool ATTR, bool FALB>
 __device__ __forceinline__ void setup_pass(const VctVoxParams& p, int t, PassTri& r) {
-    if (p.shadow) {
-        const VctTri9 rec = *reinterpret_cast<const VctTri9*>(p.pos + (size_t)t * 9);     // three wide loads, not nine
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float* q = rec.v + 3 * k;
-            const F3 w = {q[0] * p.model_scale, q[1] * p.model_scale, q[2] * p.model_scale};   // vox.vs:21
-            const F3 d = xform_point(p.light_vp, w);                                          // vox.vs:18
-            r.dc[k] = {d.x * 0.5f + 0.5f, d.y * 0.5f + 0.5f, d.z * 0.5f + 0.5f};               // vox.vs:19
-        }
+    if (p.shadow) {       // (the positions are not touched without a shadow map)
+        F3 w[3];
+        load_world_tri(p, t, w);
+        shadow_coords(p, w, r.dc);
     }
-    if (!FALB) {
-        const float* alb = p.albedo + 4 * (size_t)p.material[t];
-        r.alb[0] = alb[0]; r.alb[1] = alb[1]; r.alb[2] = alb[2];
-    }
+    if (!FALB) material_colour(p, t, r.alb);
     if (ATTR) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) r.nrm[k] = p.tri_qnrm[(size_t)t * 3 + k];
@@ -357,20 +390,11 @@ __device__ __forceinline__ void setup_pass(const VctVoxParams& p, int t, PassTri
 
 // One conservative fragment of triangle `r` with barycentrics (b0, b1) and albedo alb: the vox.fs:88 value
 // unorm8(albedo * PCF / 25) and, for the second bounce, the fragment's albedo (unorm8) -- vox.fs:18-56.
-struct FragValue { uint32_t r, g, b, ar, ag, ab; };
+struct FragValue { Rgb8 lit, alb; };
 __device__ __forceinline__ FragValue frag_eval(const VctVoxParams& p, const PassTri& r, float b0, float b1, const float alb[3]) {
     const float b2 = fmaxf(1.0f - b0 - b1, 0.0f);
-    float sh = 1.0f;
-    if (p.shadow) {
-        const F3 dc = {b0 * r.dc[0].x + b1 * r.dc[1].x + b2 * r.dc[2].x,
-                       b0 * r.dc[0].y + b1 * r.dc[1].y + b2 * r.dc[2].y,
-                       b0 * r.dc[0].z + b1 * r.dc[1].z + b2 * r.dc[2].z};
-        sh = __fdiv_rn((float)pcf25(p.shadow, p.shadow_ebase, p.shadow_size, dc, 0.002f, p.shadow_tiles), 25.0f);   // vox.fs:46
-    }
-    FragValue f;
-    f.r = to_unorm8(alb[0] * sh); f.g = to_unorm8(alb[1] * sh); f.b = to_unorm8(alb[2] * sh);   // vox.fs:88
-    f.ar = to_unorm8(alb[0]); f.ag = to_unorm8(alb[1]); f.ab = to_unorm8(alb[2]);                // the fragment's albedo
-    return f;
+    const float sh = shadow_factor(p, r.dc, b0, b1, b2);
+    return {lit_rgb8(alb, sh), lit_rgb8(alb, 1.0f)};       // (x * 1.0f is x, bit for bit)
 }
 
 __device__ __forceinline__ uint32_t resolve_voxel(ulonglong2 a) {
@@ -399,6 +423,13 @@ __device__ __forceinline__ long long tri_candidates(const TriSetup& r) {
 // (plan[0] = fragments of the small triangles, plan[1] = big triangles, listed in big_list: bounding box > VCT_VOX_BIG
 // voxels, enumerated by a workgroup each, k_vox_plan_big); WRITE = true: the entries.  Entry order is
 // irrelevant (integer accumulation), so workgroups claim ranges with one atomic each.
+template <class F>
+__device__ __forceinline__ void for_each_overlap(const TriSetup& r, F f) {      // f(i, j, k) per overlapped voxel of the box
+    for (int k = r.lo[2]; k <= r.hi[2]; ++k)
+        for (int j = r.lo[1]; j <= r.hi[1]; ++j)
+            for (int i = r.lo[0]; i <= r.hi[0]; ++i)
+                if (overlap(r, i, j, k)) f(i, j, k);
+}
 template <bool WRITE>
 __global__ void __launch_bounds__(256)
 k_vox_plan(const VctVoxParams p, uint32_t* plan, uint2* frags, int32_t* big_list) {
@@ -408,18 +439,11 @@ k_vox_plan(const VctVoxParams p, uint32_t* plan, uint2* frags, int32_t* big_list
     uint32_t chunks = 0;
     bool big = false;
     TriSetup r;
-    int nx = 0, ny = 0, nz = 0;
     if (t < p.ntri) {
         setup_tri(p, t, r);
         const long long cnt = tri_candidates(r);
         if (cnt > VCT_VOX_BIG) big = true;
-        else if (cnt > 0) {
-            nx = r.hi[0] - r.lo[0] + 1; ny = r.hi[1] - r.lo[1] + 1; nz = r.hi[2] - r.lo[2] + 1;
-            for (int k = 0; k < nz; ++k)
-                for (int j = 0; j < ny; ++j)
-                    for (int i = 0; i < nx; ++i)
-                        if (overlap(r, r.lo[0] + i, r.lo[1] + j, r.lo[2] + k)) ++chunks;
-        }
+        else if (cnt > 0) for_each_overlap(r, [&](int, int, int) { ++chunks; });
     }
     // workgroup exclusive scan of `chunks`
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -443,12 +467,9 @@ k_vox_plan(const VctVoxParams p, uint32_t* plan, uint2* frags, int32_t* big_list
     if (big && !WRITE) big_list[atomicAdd(&plan[1], 1u)] = t;      // (capacity ntri: the count pass lists them)
     if (WRITE && chunks) {
         uint32_t at = block_base + wave_base + incl - chunks;
-        for (int k = 0; k < nz; ++k)
-            for (int j = 0; j < ny; ++j)
-                for (int i = 0; i < nx; ++i)
-                    if (overlap(r, r.lo[0] + i, r.lo[1] + j, r.lo[2] + k))
-                        frags[at++] = make_uint2((uint32_t)t, vct_morton3((uint32_t)(r.lo[0] + i), (uint32_t)(r.lo[1] + j),
-                                                                          (uint32_t)(r.lo[2] + k)));
+        for_each_overlap(r, [&](int i, int j, int k) {
+            frags[at++] = make_uint2((uint32_t)t, vct_morton3((uint32_t)i, (uint32_t)j, (uint32_t)k));
+        });
     }
 }
 
@@ -553,11 +574,7 @@ k_tri_nrm(const VctVoxParams p, uint32_t* __restrict__ tri_nrm) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= p.ntri) return;
     F3 w[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float* q = p.pos + (size_t)t * 9 + 3 * k;
-        w[k] = {q[0] * p.model_scale, q[1] * p.model_scale, q[2] * p.model_scale};
-    }
+    load_world_tri(p, t, w);
     const F3 fn = cross3(sub3(w[1], w[0]), sub3(w[2], w[0]));
     const float fl = __builtin_sqrtf(dot3(fn, fn));
     const float fc[3] = {__fdiv_rn(fn.x, fl), __fdiv_rn(fn.y, fl), __fdiv_rn(fn.z, fl)};
@@ -648,11 +665,11 @@ k_voxelize_bricks(const VctVoxParams p) {
             PassTri r;
             setup_pass<ATTR, FALB>(p, (int)(e >> 9), r);
             const FragValue fv = frag_eval(p, r, bb.x, bb.y, FALB ? fa.v : r.alb);
-            atomicAdd(&acc[2 * local], (unsigned long long)fv.r | ((unsigned long long)fv.g << 32));       // ds_add_u64
-            atomicAdd(&acc[2 * local + 1], (unsigned long long)fv.b | (1ull << 32));
+            atomicAdd(&acc[2 * local], (unsigned long long)fv.lit.r | ((unsigned long long)fv.lit.g << 32));       // ds_add_u64
+            atomicAdd(&acc[2 * local + 1], (unsigned long long)fv.lit.b | (1ull << 32));
             if (ATTR) {
-                atomicAdd(&acc_attr[3 * local], (unsigned long long)fv.ar | ((unsigned long long)fv.ag << 32));
-                atomicAdd(&acc_attr[3 * local + 1], (unsigned long long)fv.ab | ((unsigned long long)r.nrm[0] << 32));
+                atomicAdd(&acc_attr[3 * local], (unsigned long long)fv.alb.r | ((unsigned long long)fv.alb.g << 32));
+                atomicAdd(&acc_attr[3 * local + 1], (unsigned long long)fv.alb.b | ((unsigned long long)r.nrm[0] << 32));
                 atomicAdd(&acc_attr[3 * local + 2], (unsigned long long)r.nrm[1] | ((unsigned long long)r.nrm[2] << 32));
             }
             f = fn; e = e_next; bb = bb_next; fa = fa_next;
@@ -724,34 +741,20 @@ k_vox_resolve_multi(const VctVoxParams p, const uint32_t* __restrict__ multi_slo
 // = unorm8(albedo * PCF/25), a = 1, and "imageStore: last writer wins".  The reference's store order
 // is a race; the deterministic reading the oracle uses -- the last triangle in submission order
 // wins -- is an order-independent 64-bit atomicMax on (triangle + 1) << 32 | rgb.
-struct RefSetup {
+struct RefSetup : TriMaterial {
     float wx[3], wy[3], wz[3];
     F3 dc[3];
     float area, sgn;
     int x0, x1, y0, y1, axis;
-    float alb[3];
-    float uv[3][2];
-    int tex;
     bool ok;
 };
 
 __device__ __forceinline__ void ref_setup(const VctVoxParams& p, int t, RefSetup& r) {
     F3 w[3];
     const float fV = (float)p.V;
-    for (int k = 0; k < 3; ++k) {
-        const float* q = p.pos + (size_t)t * 9 + 3 * k;
-        w[k] = {q[0] * p.model_scale, q[1] * p.model_scale, q[2] * p.model_scale};   // vox.vs:21
-        const F3 d = xform_point(p.light_vp, w[k]);                                  // vox.vs:18
-        r.dc[k] = {d.x * 0.5f + 0.5f, d.y * 0.5f + 0.5f, d.z * 0.5f + 0.5f};          // vox.vs:19
-    }
-    const F3 e1 = sub3(w[0], w[1]), e2 = sub3(w[2], w[0]);                            // vox.gs:24-25
-    const F3 nn = cross3(e1, e2);
-    const float len = __builtin_sqrtf(dot3(nn, nn));
-    const float nx = fabsf(__fdiv_rn(nn.x, len)), ny = fabsf(__fdiv_rn(nn.y, len)),
-                nz = fabsf(__fdiv_rn(nn.z, len));
-    if (nx >= ny && nx >= nz) r.axis = 1;                                             // vox.gs:34-39
-    else if (ny >= nx && ny >= nz) r.axis = 2;
-    else r.axis = 3;
+    load_world_tri(p, t, w);
+    shadow_coords(p, w, r.dc);
+    r.axis = dominant_axis(w);
     const float* proj = p.proj + 16 * (r.axis - 1);
     for (int k = 0; k < 3; ++k) {
         const F3 ndc = xform_point(proj, w[k]);                                       // vox.gs:47 (w = 1)
@@ -767,9 +770,7 @@ __device__ __forceinline__ void ref_setup(const VctVoxParams& p, int t, RefSetup
     r.x1 = min((int)floorf(fmaxf(fmaxf(r.wx[0], r.wx[1]), r.wx[2])), p.V - 1);
     r.y0 = max((int)floorf(fminf(fminf(r.wy[0], r.wy[1]), r.wy[2])), 0);
     r.y1 = min((int)floorf(fmaxf(fmaxf(r.wy[0], r.wy[1]), r.wy[2])), p.V - 1);
-    const float* alb = p.albedo + 4 * (size_t)p.material[t];
-    r.alb[0] = alb[0]; r.alb[1] = alb[1]; r.alb[2] = alb[2];
-    load_tex_setup(p, t, r);
+    load_material(p, t, r);
 }
 
 __device__ __forceinline__ void ref_fragment(const VctVoxParams& p, const RefSetup& r, int t, int px, int py) {
@@ -794,18 +795,12 @@ __device__ __forceinline__ void ref_fragment(const VctVoxParams& p, const RefSet
     if (vx < 0 || vy < 0 || vz < 0 || vx >= V || vy >= V || vz >= V) return;          // [GL] store dropped
     const uint32_t vox = vct_morton3((uint32_t)vx, (uint32_t)vy, (uint32_t)vz);
     if (p.mark_only) { p.brick_mark[vox >> 9] = 1u; return; }
-    float sh = 1.0f;
-    if (p.shadow) {
-        const F3 dc = {l0 * r.dc[0].x + l1 * r.dc[1].x + l2 * r.dc[2].x,
-                       l0 * r.dc[0].y + l1 * r.dc[1].y + l2 * r.dc[2].y,
-                       l0 * r.dc[0].z + l1 * r.dc[1].z + l2 * r.dc[2].z};
-        sh = __fdiv_rn((float)pcf25(p.shadow, p.shadow_ebase, p.shadow_size, dc, 0.002f, p.shadow_tiles), 25.0f);    // vox.fs:46
-    }
+    const float sh = shadow_factor(p, r.dc, l0, l1, l2);
     float alb[3];
     float duv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     if (r.tex >= 0 && p.tex.mips) {
-        // texture() derivatives: the neighbouring pixel centres of the fragment's 2x2 quad, on this triangle
-        auto uv_at = [&](int qx, int qy, float& ou, float& ov) {
+        // the neighbouring pixel centres of the fragment's 2x2 quad; unclamped barycentrics from the signed edge functions
+        auto uv_at = [&](int qx, int qy) {
             const float nx = (float)qx + 0.5f, ny = (float)qy + 0.5f;
             float f[2];
 #pragma unroll
@@ -814,21 +809,15 @@ __device__ __forceinline__ void ref_fragment(const VctVoxParams& p, const RefSet
                 const float dx = (r.wx[b] - r.wx[a]) * r.sgn, dy = (r.wy[b] - r.wy[a]) * r.sgn;
                 f[k] = dx * (ny - r.wy[a]) - dy * (nx - r.wx[a]);
             }
-            const float c0 = __fdiv_rn(f[0], r.area), c1 = __fdiv_rn(f[1], r.area), c2 = 1.0f - c0 - c1;
-            ou = c0 * r.uv[0][0] + c1 * r.uv[1][0] + c2 * r.uv[2][0];
-            ov = c0 * r.uv[0][1] + c1 * r.uv[1][1] + c2 * r.uv[2][1];
+            const float c0 = __fdiv_rn(f[0], r.area), c1 = __fdiv_rn(f[1], r.area);
+            return interp_uv(r, c0, c1, 1.0f - c0 - c1);
         };
-        float mu, mv, xu, xv, yu, yv;
-        uv_at(px, py, mu, mv);
-        uv_at(px ^ 1, py, xu, xv);
-        uv_at(px, py ^ 1, yu, yv);
-        duv[0] = xu - mu; duv[1] = xv - mv; duv[2] = yu - mu; duv[3] = yv - mv;
+        quad_duv(uv_at(px, py), uv_at(px ^ 1, py), uv_at(px, py ^ 1), duv);
     }
     frag_albedo(p, r, l0, l1, l2, duv, alb);                                          // vox.fs:56
-    const unsigned long long rgb = to_unorm8(alb[0] * sh) | (to_unorm8(alb[1] * sh) << 8) |
-                                   (to_unorm8(alb[2] * sh) << 16);                   // vox.fs:88
+    const Rgb8 c = lit_rgb8(alb, sh);
     atomicMax(p.acc + 2 * ((size_t)p.brick_slot[vox >> 9] * 512 + (vox & 511u)),
-              ((unsigned long long)(uint32_t)(t + 1) << 32) | rgb);
+              ((unsigned long long)(uint32_t)(t + 1) << 32) | c.r | (c.g << 8) | (c.b << 16));
     p.brick_flags[vox >> 9] = 1u;
 }
 
@@ -863,17 +852,12 @@ k_voxelize_reference_big(const VctVoxParams p, const int32_t* big_list, const in
     }
 }
 
-// accumulators -> RGBA8 level 0 (Morton), rounded mean, a = 255 where any fragment landed.
-// One wave per 8^3 brick (512 voxels, one contiguous 8 KiB run of accumulators); bricks that were
-// touched neither in this pass nor in the previous one are skipped unless `dense`.
+// A pass's result -> RGBA8 level 0 (Morton) for the bricks that were touched in this pass or in the previous one (all
+// bricks if `dense`), one wave per 8^3 brick.  Three cases: the mesh has no slot for the brick (level 0 is empty there);
+// north-star mode: the brick's staged texels (+ voxel attributes) are copied; reference mode: the last writer's colour
+// is unpacked from the slot's words, which go back to zero.
 __global__ void __launch_bounds__(256)
-k_resolve_sparse(unsigned long long* __restrict__ acc, const uint32_t* __restrict__ brick_slot,
-                 uint32_t* __restrict__ level0,
-                 uint32_t* __restrict__ flags, uint32_t* __restrict__ prev, uint32_t nbricks,
-                 uint32_t brick_voxels, int dense, unsigned long long* __restrict__ acc_attr,
-                 uint32_t* __restrict__ attr_albedo, uint32_t* __restrict__ attr_normal, int reference,
-                 const uint32_t* __restrict__ stage, const uint32_t* __restrict__ stage_albedo,
-                 const uint32_t* __restrict__ stage_normal, int scan64) {
+k_resolve_sparse(const VctResolveArgs a, uint32_t nbricks, int dense, int scan64) {
     const int lane = threadIdx.x & 63;
     const uint32_t waves = (gridDim.x * blockDim.x) >> 6;
     // The flags are read 64 bricks at a time, one brick per lane, and the wave then serves the flagged ones one after the
@@ -889,57 +873,34 @@ k_resolve_sparse(unsigned long long* __restrict__ acc, const uint32_t* __restric
     for (uint32_t c = (blockIdx.x * blockDim.x + threadIdx.x) >> 6; c < nchunks; c += waves) {
       const uint32_t mine = scan64 ? (uint32_t)lane * nchunks + c : c;
       const bool in = mine < nbricks && (scan64 || lane == 0);
-      const uint32_t now_l = in ? flags[mine] : 0u, before_l = in ? prev[mine] : 0u;
+      const uint32_t now_l = in ? a.flags[mine] : 0u, before_l = in ? a.prev[mine] : 0u;
       for (unsigned long long todo = __builtin_amdgcn_ballot_w64(in && (dense || (now_l | before_l) != 0u)); todo != 0ull;
            todo &= todo - 1ull) {
         const int src = (int)__ffsll((long long)todo) - 1;
         const uint32_t b = scan64 ? (uint32_t)src * nchunks + c : c;
         const uint32_t now = (uint32_t)__builtin_amdgcn_readlane((int)now_l, src);
-        uint32_t* l0 = level0 + (size_t)b * brick_voxels;
-        const uint32_t slot = brick_slot[b];
+        uint32_t* l0 = a.level0 + (size_t)b * 512;
+        const uint32_t slot = a.brick_slot[b];
         if (slot == VCT_NO_SLOT) {        // no fragment of this mesh can land here: level 0 is empty
-            for (uint32_t v = lane; v < brick_voxels; v += 64) l0[v] = 0u;
-            if (lane == 0) { prev[b] = 0u; flags[b] = 0u; }
+            for (uint32_t v = lane; v < 512u; v += 64) l0[v] = 0u;
+            if (lane == 0) { a.prev[b] = 0u; a.flags[b] = 0u; }
             continue;
         }
-        if (stage) {        // north-star mode: k_voxelize_bricks already resolved the brick into its staging slot
-            for (uint32_t v = lane; v < brick_voxels; v += 64) {
-                const size_t vox = (size_t)slot * brick_voxels + v;
-                l0[v] = stage[vox];
-                if (stage_albedo) { attr_albedo[vox] = stage_albedo[vox]; attr_normal[vox] = stage_normal[vox]; }
+        if (a.stage) {        // north-star mode: k_voxelize_bricks already resolved the brick into its staging slot
+            for (uint32_t v = lane; v < 512u; v += 64) {
+                const size_t vox = (size_t)slot * 512 + v;
+                l0[v] = a.stage[vox];
+                if (a.stage_albedo) { a.attr_albedo[vox] = a.stage_albedo[vox]; a.attr_normal[vox] = a.stage_normal[vox]; }
             }
-            if (lane == 0) { prev[b] = now; flags[b] = 0u; }
-            continue;
-        }
-        ulonglong2* a2 = reinterpret_cast<ulonglong2*>(acc) + (size_t)slot * brick_voxels;
-        for (uint32_t v = lane; v < brick_voxels; v += 64) {
-            const ulonglong2 a = a2[v];
-            if (reference) {        // (triangle + 1) << 32 | rgb of the last triangle that stored here
-                l0[v] = a.x ? ((uint32_t)a.x & 0xffffffu) | 0xff000000u : 0u;
-                if (a.x) a2[v] = make_ulonglong2(0ull, 0ull);
-                continue;
-            }
-            l0[v] = resolve_voxel(a);
-            if (a.y) a2[v] = make_ulonglong2(0ull, 0ull);
-            if (acc_attr) {
-                const size_t vox = (size_t)slot * brick_voxels + v;       // attributes are pooled like the accumulators
-                unsigned long long* q = acc_attr + 3 * vox;
-                const uint32_t c = (uint32_t)(a.y >> 32);
-                uint32_t alb = 0u, nrm = 0u;
-                if (c) {
-                    const unsigned long long q0 = q[0], q1 = q[1], q2 = q[2];
-                    const uint32_t h = c >> 1;
-                    alb = (((uint32_t)q0 + h) / c) | ((((uint32_t)(q0 >> 32) + h) / c) << 8) |
-                          ((((uint32_t)q1 + h) / c) << 16) | 0xff000000u;
-                    nrm = (((uint32_t)(q1 >> 32) + h) / c) | ((((uint32_t)q2 + h) / c) << 8) |
-                          ((((uint32_t)(q2 >> 32) + h) / c) << 16) | 0xff000000u;
-                    q[0] = 0ull; q[1] = 0ull; q[2] = 0ull;
-                }
-                attr_albedo[vox] = alb;
-                attr_normal[vox] = nrm;
+        } else {              // reference mode: (triangle + 1) << 32 | rgb of the last triangle that stored here
+            ulonglong2* w = reinterpret_cast<ulonglong2*>(a.acc) + (size_t)slot * 512;
+            for (uint32_t v = lane; v < 512u; v += 64) {
+                const unsigned long long last = w[v].x;
+                l0[v] = last ? ((uint32_t)last & 0xffffffu) | 0xff000000u : 0u;
+                if (last) w[v] = make_ulonglong2(0ull, 0ull);
             }
         }
-        if (lane == 0) { prev[b] = now; flags[b] = 0u; }
+        if (lane == 0) { a.prev[b] = now; a.flags[b] = 0u; }
       }
     }
 }
@@ -976,24 +937,23 @@ k_unpool(const uint32_t* __restrict__ pooled, const uint32_t* __restrict__ brick
 
 }  // namespace
 
+// blocks of a grid-stride launch over n units of work: n, at most cap, at least one
+static unsigned capped_grid(size_t n, size_t cap) { return (unsigned)(n < cap ? (n ? n : 1) : cap); }
+
 hipError_t vct_launch_assign_slots(const uint32_t* mark, uint32_t* slot, uint32_t* count, uint32_t nbricks, hipStream_t s) {
     hipError_t e = hipMemsetAsync(count, 0, sizeof(uint32_t), s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_assign_slots, dim3((nbricks + 255) / 256 < 4096 ? (nbricks + 255) / 256 : 4096), dim3(256), 0, s,
-                       mark, slot, count, nbricks);
+    hipLaunchKernelGGL(k_assign_slots, dim3(capped_grid((nbricks + 255) / 256, 4096)), dim3(256), 0, s, mark, slot, count, nbricks);
     return hipGetLastError();
 }
 
 hipError_t vct_launch_slot_bricks(const uint32_t* slot, uint32_t nbricks, uint32_t* slot_brick, hipStream_t s) {
-    hipLaunchKernelGGL(k_slot_bricks, dim3((nbricks + 255) / 256 < 4096 ? (nbricks + 255) / 256 : 4096), dim3(256), 0, s,
-                       slot, nbricks, slot_brick);
+    hipLaunchKernelGGL(k_slot_bricks, dim3(capped_grid((nbricks + 255) / 256, 4096)), dim3(256), 0, s, slot, nbricks, slot_brick);
     return hipGetLastError();
 }
 
 hipError_t vct_launch_unpool(const uint32_t* pooled, const uint32_t* brick_slot, uint32_t* dense, uint32_t nbricks, hipStream_t s) {
-    size_t blocks = ((size_t)nbricks + 3) / 4;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    hipLaunchKernelGGL(k_unpool, dim3((unsigned)blocks), dim3(256), 0, s, pooled, brick_slot, dense, nbricks);
+    hipLaunchKernelGGL(k_unpool, dim3(capped_grid(((size_t)nbricks + 3) / 4, 256 * 32)), dim3(256), 0, s, pooled, brick_slot, dense, nbricks);
     return hipGetLastError();
 }
 
@@ -1009,16 +969,13 @@ hipError_t vct_launch_vox_plan(const VctVoxParams& p, uint32_t* plan, uint2* fra
 hipError_t vct_launch_vox_plan_big(const VctVoxParams& p, const int32_t* big_list, int n_big, uint32_t* plan, uint2* frags,
                                    bool write, hipStream_t s) {
     if (n_big <= 0) return hipSuccess;
-    const dim3 grid(n_big < 256 * 8 ? n_big : 256 * 8), block(256);
+    const dim3 grid(capped_grid((size_t)n_big, 256 * 8)), block(256);
     if (write) hipLaunchKernelGGL(k_vox_plan_big<true>, grid, block, 0, s, p, big_list, n_big, plan, frags);
     else hipLaunchKernelGGL(k_vox_plan_big<false>, grid, block, 0, s, p, big_list, n_big, plan, frags);
     return hipGetLastError();
 }
 
-static unsigned frag_blocks(uint32_t n) {
-    const size_t b = ((size_t)n + 255) / 256;
-    return (unsigned)(b < 256 * 32 ? (b ? b : 1) : 256 * 32);
-}
+static unsigned frag_blocks(uint32_t n) { return capped_grid(((size_t)n + 255) / 256, 256 * 32); }
 hipError_t vct_launch_frag_mark(const uint2* frags, uint32_t n, uint32_t* mark, hipStream_t s) {
     if (!n) return hipSuccess;
     hipLaunchKernelGGL(k_frag_mark, dim3(frag_blocks(n)), dim3(256), 0, s, frags, n, mark);
@@ -1039,7 +996,7 @@ hipError_t vct_launch_frag_scatter(const uint2* frags, uint32_t n, const uint32_
 
 hipError_t vct_launch_frag_geom(const VctVoxParams& p, float2* bary, float* falb, hipStream_t s) {
     if (p.nslots == 0u || (!bary && !falb)) return hipSuccess;
-    const dim3 grid(p.nslots < 256u * 64u ? p.nslots : 256u * 64u), block(256);
+    const dim3 grid(capped_grid(p.nslots, 256 * 64)), block(256);
     VctF3* fa = reinterpret_cast<VctF3*>(falb);
     if (bary && falb) hipLaunchKernelGGL((k_frag_geom<true, true>), grid, block, 0, s, p, bary, fa);
     else if (bary) hipLaunchKernelGGL((k_frag_geom<true, false>), grid, block, 0, s, p, bary, fa);
@@ -1067,7 +1024,7 @@ hipError_t vct_launch_voxelize_reference(const VctVoxParams& p, int32_t* big_lis
 
 hipError_t vct_launch_voxelize(const VctVoxParams& p, hipStream_t s) {
     if (p.nslots == 0u || p.nitems == 0u) return hipSuccess;
-    const unsigned blocks = p.nitems < 256u * 64u ? p.nitems : 256u * 64u;
+    const unsigned blocks = capped_grid(p.nitems, 256 * 64);
     const bool attr = p.stage_albedo != nullptr, falb = p.frag_alb != nullptr;
     const unsigned threads = p.nitems >= VCT_VOX_TINY_BLOCK_ITEMS ? 64u : (p.nitems >= VCT_VOX_SMALL_BLOCK_ITEMS ? 128u : 256u);
     if (attr && falb) hipLaunchKernelGGL((k_voxelize_bricks<true, true>), dim3(blocks), dim3(threads), 0, s, p);
@@ -1076,23 +1033,16 @@ hipError_t vct_launch_voxelize(const VctVoxParams& p, hipStream_t s) {
     else hipLaunchKernelGGL((k_voxelize_bricks<false, false>), dim3(blocks), dim3(threads), 0, s, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || p.nmulti == 0u) return e;
-    const unsigned mblocks = p.nmulti < 256u * 16u ? p.nmulti : 256u * 16u;
+    const unsigned mblocks = capped_grid(p.nmulti, 256 * 16);
     if (p.stage_albedo) hipLaunchKernelGGL(k_vox_resolve_multi<true>, dim3(mblocks), dim3(256), 0, s, p, p.multi_slot, p.nmulti);
     else hipLaunchKernelGGL(k_vox_resolve_multi<false>, dim3(mblocks), dim3(256), 0, s, p, p.multi_slot, p.nmulti);
     return hipGetLastError();
 }
 
-hipError_t vct_launch_resolve(unsigned long long* acc, const uint32_t* brick_slot, uint32_t* level0, uint32_t* flags,
-                              uint32_t* prev, int V, bool dense, unsigned long long* acc_attr,
-                              uint32_t* attr_albedo, uint32_t* attr_normal, bool reference, const uint32_t* stage,
-                              const uint32_t* stage_albedo, const uint32_t* stage_normal, hipStream_t s) {
-    const uint32_t brick_voxels = V >= 8 ? 512u : (uint32_t)(V * V * V);
-    const uint32_t nbricks = (uint32_t)(((size_t)V * V * V) / brick_voxels);
-    size_t blocks = ((size_t)nbricks + 3) / 4;      // 4 waves per workgroup, one brick per wave
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    hipLaunchKernelGGL(k_resolve_sparse, dim3((unsigned)blocks), dim3(256), 0, s, acc, brick_slot, level0, flags,
-                       prev, nbricks, brick_voxels, dense ? 1 : 0, reference ? nullptr : acc_attr, attr_albedo,
-                       attr_normal, reference ? 1 : 0, reference ? nullptr : stage, reference ? nullptr : stage_albedo,
-                       reference ? nullptr : stage_normal, nbricks > 524288u ? 1 : 0);
+hipError_t vct_launch_resolve(const VctResolveArgs& a, int V, bool dense, hipStream_t s) {
+    const uint32_t nbricks = (uint32_t)(((size_t)V * V * V) / 512);
+    // 4 waves per workgroup, one brick per wave
+    hipLaunchKernelGGL(k_resolve_sparse, dim3(capped_grid(((size_t)nbricks + 3) / 4, 256 * 32)), dim3(256), 0, s, a, nbricks,
+                       dense ? 1 : 0, nbricks > 524288u ? 1 : 0);
     return hipGetLastError();
 }

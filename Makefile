@@ -6,7 +6,7 @@ CSRC := $(PKG)/csrc
 # -fno-slp-vectorize: packed fp32 (v_pk_fma_f32 ...) issues at half rate on gfx950, so SLP packing buys
 #   nothing and costs v_mov shuffles (trace kernel 1.01 -> 0.87 ms, profiles/r01c).
 HIPFLAGS := -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fno-slp-vectorize -fPIC -Wall -Wno-unused-function
-OBJS := $(CSRC)/vct_capi.o $(CSRC)/vct_trace.o $(CSRC)/vct_volume.o $(CSRC)/vct_voxelize.o $(CSRC)/vct_raster.o $(CSRC)/vct_multi.o
+OBJS := $(CSRC)/vct_capi.o $(CSRC)/vct_api_scene.o $(CSRC)/vct_api_raster.o $(CSRC)/vct_api_voxel.o $(CSRC)/vct_api_trace.o $(CSRC)/vct_trace.o $(CSRC)/vct_volume.o $(CSRC)/vct_voxelize.o $(CSRC)/vct_raster.o $(CSRC)/vct_multi.o
 LIB := $(PKG)/libvct_amd.so
 
 HOSTLIB := $(PKG)/libvct_host.so

@@ -1,7 +1,7 @@
 """The cone march away from the reference's constants: grid size, distance and opacity limits, apertures and the shading
 constants (vct_config fields and setters), against the CPU oracle under the same parameters.
 
-The march has two families of kernels.  refresh_steps (csrc/vct_capi.hip) picks the verified two-term product for its
+The march has two families of kernels.  vct_refresh_steps (csrc/vct_api_trace.hip) picks the verified two-term product for its
 constant divisions only when every divisor passes the device's exhaustive check, 1 - max_alpha >= 2^-5 and every blend
 fraction lies in [2^-10, 1 - 2^-10]; anything else runs the IEEE-divide instantiations (FASTDIV = 0).  Every test here
 asserts which form ran (vct_get_stage_counts [2]), from a restatement of that rule.  Bars as in test_gpu_parity.py:
@@ -66,7 +66,7 @@ def volume(seed=5, occupancy=0.12, Vd=V):
     return synth.noise_volume(Vd, seed=seed, occupancy=occupancy)
 
 
-# ---- restatement of refresh_steps / build_steps (csrc/vct_capi.hip) -------------------------------------------------
+# ---- restatement of vct_refresh_steps / build_steps (csrc/vct_api_trace.hip) -------------------------------------------------
 def step_table(Vd, G, tan, md):
     """[(dist, occlusion divisor, two levels, blend fraction, lod)] of one cone group, fp32 as build_steps."""
     vs = f32(G) / f32(Vd)

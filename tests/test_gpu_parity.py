@@ -378,6 +378,50 @@ def test_stale_mips_are_refused_and_upload_then_sparse_builds_stay_correct(vct, 
         assert ctx.last_step_count() == steps       # the self-test does not disturb the step counters
 
 
+def test_chain_state_walks_bounce_upload_dense_and_sparse_builds(vct, oracle):
+    """One context through the chain's transitions in an order no other test uses; after each, the chain the
+    trace and the download read is the right one and holds the right bits.  bounce -> uploaded chain ->
+    uploaded level 0 (stale mips refused) -> build -> voxelize + inject + build (by design still dense: the
+    upload's ancestors are only known to be gone after a dense build over a RESOLVED level 0) -> the same
+    again (by design sparse) -> bounce into the existing second chain.  All bit-exact.  Which form a build
+    took is not observable through the ABI and not asserted: a sparse build where a dense one was due would
+    leave the upload's ancestors behind and fail the comparison, a dense one where sparse was due passes."""
+    V, w, h = 16, 16, 8
+    pos, mat, alb = random_scene(40, seed=7)
+    p = oracle.default_params(V)
+    l0, want_alb, want_nrm = oracle.voxelize_conservative_attr(p, oracle.make_scene(pos, mat, alb))
+    chain0 = oracle.build_mips(l0)
+    l1, _ = oracle.bounce(p, chain0, want_alb, want_nrm, nthreads=8)
+    chain1 = oracle.build_mips(l1)
+    assert (l0[..., 3] > 0).any() and (l1 != l0).any()
+    planes = synth.random_gbuffer(w * h, seed=6)
+    rng = np.random.default_rng(8)
+    junk_chain = rng.integers(0, 256, (vct.chain_texels(V), 4), dtype=np.uint8)
+    junk = rng.integers(0, 256, (V, V, V, 4), dtype=np.uint8)
+    with make_ctx(vct, V, w, h, voxel_attributes=1) as ctx:
+        ctx.upload_triangles(pos, mat, alb)
+        ctx.voxelize(); ctx.inject_light(); ctx.build_mips(); ctx.bounce()
+        got = ctx.download_chain()
+        assert np.array_equal(got, chain1)
+        check_frame(vct, oracle, ctx, got, planes, w, h)            # the trace reads the bounce chain
+        ctx.upload_chain(junk_chain)                                # ... and the uploaded chain after an upload
+        assert np.array_equal(ctx.download_chain(), junk_chain)
+        check_frame(vct, oracle, ctx, junk_chain, planes, w, h)
+        ctx.upload_volume(junk)
+        with pytest.raises(vct.VctError, match="level 0 changed since the last vct_build_mips"):
+            ctx.trace(planes)
+        ctx.build_mips()                                            # dense: level 0 is an upload
+        want = oracle.build_mips(junk)
+        assert np.array_equal(ctx.download_chain(), want)
+        check_frame(vct, oracle, ctx, want, planes, w, h)
+        for form in ("dense over the resolved level 0", "sparse"):
+            ctx.voxelize(); ctx.inject_light(); ctx.build_mips()
+            assert np.array_equal(ctx.download_chain(), chain0), form
+        ctx.bounce()                                                # the second chain exists: its sparse update
+        assert np.array_equal(ctx.download_chain(), chain1)
+        check_frame(vct, oracle, ctx, chain1, planes, w, h)
+
+
 def test_texel_buffer_conversion_is_the_exact_decode(vct):
     """Round 6: the trace kernels take the four floats the texture path returns for an RGBA8 UNORM texel (typed-buffer
     load) instead of decoding the bytes -- [GL] value = byte / 255.  Every byte value in every channel

@@ -1,5 +1,5 @@
 #!/bin/bash
-# ON THE GPU BOX: does probing for streams that really overlap (VCT_STREAM_PROBE, vct_capi.hip create_overlapping_stream) change
+# ON THE GPU BOX: does probing for streams that really overlap (VCT_STREAM_PROBE, vct_capi.hip vct_create_overlapping_stream) change
 # (a) the native multi-GPU step loop with a 1-rank communicator on a frame the size of an 8-way slab, (b) vct_gi_pass?
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 line() { python -c "

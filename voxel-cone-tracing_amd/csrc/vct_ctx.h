@@ -2,7 +2,13 @@
 #ifndef VCT_CTX_H_
 #define VCT_CTX_H_
 
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
 #include <string>
+#include <vector>
 
 #include "../../include/vct.h"
 #include "vct_internal.h"
@@ -55,7 +61,37 @@ public:
     explicit operator bool() const { return p_ != nullptr; }
 };
 
-// Scratch of one kind of raster pass (vct_capi.hip raster_args).  Between passes every visibility word is all-ones and
+// An event / a stream with an owner, like VctBuf.  Destroying a stream does not wait for it: whoever drops one with work in flight waits first.
+template <class H, hipError_t (*Create)(H*, unsigned), hipError_t (*Destroy)(H)>
+class VctHandle {
+    H h_ = nullptr;
+
+public:
+    VctHandle() = default;
+    VctHandle(const VctHandle&) = delete;
+    VctHandle& operator=(const VctHandle&) = delete;
+    VctHandle(VctHandle&& o) noexcept : h_(o.release()) {}
+    VctHandle& operator=(VctHandle&& o) noexcept { if (this != &o) adopt(o.release()); return *this; }
+    ~VctHandle() { reset(); }
+    void reset() { adopt(nullptr); }
+    hipError_t create(unsigned flags = 0) {      // the old one goes first; a failure leaves none
+        reset();
+        const hipError_t e = Create(&h_, flags);
+        if (e != hipSuccess) h_ = nullptr;
+        return e;
+    }
+    void adopt(H h) {      // one made another way (a stream with a priority or a CU mask): owned from here on
+        if (h_) (void)Destroy(h_);
+        h_ = h;
+    }
+    H release() { H h = h_; h_ = nullptr; return h; }
+    H get() const { return h_; }
+    explicit operator bool() const { return h_ != nullptr; }
+};
+using VctEvent = VctHandle<hipEvent_t, hipEventCreateWithFlags, hipEventDestroy>;
+using VctStream = VctHandle<hipStream_t, hipStreamCreateWithFlags, hipStreamDestroy>;
+
+// Scratch of one kind of raster pass (vct_api_raster.hip raster_args).  Between passes every visibility word is all-ones and
 // the counter set of the next pass is zero: the kernels re-establish both themselves (vct_raster.hip run_visibility), so
 // a pass launches no memset.  `dirty` (a launch failed, or nothing is initialised yet) makes the next pass clear
 // everything once.  The shadow pass and the main draw have scratch of their own, so that the main draw's visibility
@@ -77,6 +113,8 @@ struct VctRasterScratch {
     int bin_set = 0;
     VctBuf<unsigned long long> vis;     // 64-bit visibility words of the main draw
     bool dirty = true;
+    // frees the buffers sized by the mesh's triangle count (a new mesh: the next pass allocates them for it)
+    void release_mesh() { lists.reset(); recs.reset(); bin_recs.reset(); bin_entries.reset(); bin_items.reset(); }
 };
 
 // Two frames in flight (vct_set_frames_in_flight, round 6).  A whole-frame trace launch pays ~20 us of ramp and drain
@@ -90,8 +128,8 @@ struct VctRasterScratch {
 // mips, bounce) waits for everything the other slot has in flight (pipeline_join), and the next slot switch makes the
 // other stream wait for that stage.  Slot 0's stream is the context's stream.
 struct VctFrameSlot {
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // timing events of the march launches (vct_last_trace_ms)
+    VctStream stream;
+    VctEvent ev0, ev1;                  // timing events of the march launches (vct_last_trace_ms)
     VctBuf<float> gb_tiled;             // [tiles][23][64]
     const float* gb_current = nullptr;  // tiled buffer the next resident trace reads: gb_tiled or the caller's (not owned)
     VctBuf<uint16_t> frame;             // RGBA16F [h][w][4]
@@ -104,7 +142,7 @@ struct VctFrameSlot {
     VctBuf<uint8_t> dr_anchor;          // [ch][cw]
     VctBuf<uint32_t> dr_list;           // [w * h]
     VctBuf<unsigned long long> dr_ctr;  // [VCT_DR_CTR_WORDS]
-    hipEvent_t dr_ev[3] = {nullptr, nullptr, nullptr};   // between the pass's four launches (vct_last_diffuse_rate_ms)
+    VctEvent dr_ev[3];                  // between the pass's four launches (vct_last_diffuse_rate_ms)
     bool last_trace_half = false;       // the last screen trace was a half-rate pass: dr_ctr holds its marches' counts
     int last_row0 = 0, last_row1 = 0;
     int last_row_stride = 1;            // the last screen trace took every last_row_stride-th tile row of [last_row0, last_row1)
@@ -114,6 +152,16 @@ struct VctFrameSlot {
     bool last_was_screen_trace = false; // the step counters hold a screen trace (indexed by tile row), not a bounce
     bool have_gbuffer = false;          // a G-buffer is resident (uploaded by vct_trace or rendered)
     VctRasterScratch raster;            // the main draw's
+
+    // where a trace writes and a download reads: the caller's target or the slot's own frame
+    uint16_t* frame_out() const { return frame_target ? frame_target : frame.get(); }
+    // the buffers and events of the half-rate gather for a w x h frame, zeroed on the slot's stream; a failure leaves none
+    hipError_t alloc_half_rate(int w, int h);      // (vct_capi.hip)
+    void free_half_rate() {
+        dr_ind.reset(); dr_coarse.reset(); dr_anchor.reset(); dr_list.reset(); dr_ctr.reset();
+        for (VctEvent& ev : dr_ev) ev.reset();
+        last_trace_half = false;
+    }
 };
 
 // The mesh and its texture set (vct_upload_triangles, vct_upload_mesh_attributes / _uvs, vct_upload_textures).
@@ -169,26 +217,107 @@ struct VctVoxelPlan {
     bool acc_pending = false;          // accumulators hold an unresolved voxelize pass
 };
 
-// Every device buffer below is a VctBuf member of the context or of one of its parts (VctMesh, VctVoxelPlan,
-// VctFrameSlot, VctRasterScratch): vct_destroy waits for the streams and deletes the context, the members free the rest.
+// The voxel volume: the Morton mip chain the trace reads and which of its parts are current.  The flags change only in
+// the functions named after what happened to the chain; entry points read them.  All of it survives a mesh change.
+struct VctChain {
+    int V = 0, nlev = 0;
+    size_t chain_texels = 0;
+    VctBuf<uint32_t> chain;           // Morton chain (bounce 0: direct light)
+    VctBuf<uint32_t> chain_b;         // second chain (bounce 1), allocated by vct_bounce
+    VctBuf<uint32_t> aniso;           // [6][chain_texels - V^3] directional chains (cfg.anisotropic_mips)
+    bool want_cells = false;          // vct_set_footprint_records / VCT_FOOTPRINT_RECORDS=1
+    VctBuf<uint4> cells;              // footprint records of the levels >= 1 of `chain` (32 B per texel of those levels)
+    VctBuf<uint32_t> staging;         // linear staging for up/downloads (size of level 0)
+    VctBuf<uint32_t> brick_flags;     // [V^3/512] touched in the pending pass
+    VctBuf<uint32_t> brick_prev;      // [V^3/512] touched in the pass level 0 currently shows
+    VctBuf<uint32_t> mip_seen;        // [V^3/512] bricks non-empty when the chain's mips were last built
+    VctBuf<uint32_t> mip_seen_b;      // same for the bounce chain
+    bool use_chain_b = false;         // the trace reads chain_b until the next vct_inject_light
+    bool mips_valid = true;           // levels >= 1 describe level 0 (a fresh chain is all zero)
+    bool cells_valid = false;         // `cells` describe the levels >= 1 of `chain`
+    bool level0_dirty = false;        // level 0 was written by an upload: next resolve is dense
+    bool chain_sparse_ready = true;   // bricks outside mip_seen have all-zero ancestors (true for a fresh, zero-filled
+                                      // chain; an upload clears it until a dense mip build over a resolved level 0)
+
+    const uint32_t* active() const { return use_chain_b ? chain_b.get() : chain.get(); }      // the chain the trace reads
+    size_t nvox() const { return (size_t)V * V * V; }
+    size_t nbricks() const { return nvox() / 512; }
+    bool tracked() const { return brick_prev && mip_seen && !level0_dirty; }      // level 0 mirrors brick_prev: a resolve's output, not an upload's
+    // the sparse mip build reduces only bricks that hold something now (brick_prev) or did at the last build (mip_seen)
+    bool sparse_mips_ok() const { return tracked() && chain_sparse_ready; }
+    void level0_uploaded(bool with_levels) {      // the next resolve and mip build are dense
+        use_chain_b = false; mips_valid = with_levels; cells_valid = false; level0_dirty = true; chain_sparse_ready = false;
+    }
+    void level0_resolved() { level0_dirty = false; use_chain_b = false; mips_valid = false; }      // vct_inject_light
+    void mips_reduced(bool sparse) { if (!sparse) chain_sparse_ready = tracked(); }      // a dense build over a tracked level 0 makes the sparse form valid again
+    void mips_built() { mips_valid = true; use_chain_b = false; }      // ... and the directional chains followed
+    void bounce_done() { use_chain_b = true; }
+    void records_valid(bool v) { cells_valid = v; }      // built; or freed / about to be rebuilt
+};
+
+// The shadow map: its words ARE the shadow pass's atomicMin words (vct_internal.h "shadow map words"), written under epoch
+// 3, 2, 1, 0, then one memset and 3 again -- a new pass overwrites older epochs by itself, readers see them as depth 1.0.
+struct VctShadowMap {
+    VctBuf<uint32_t> words;           // size^2 (vct_internal.h vct_shadow_depth)
+    int32_t size = 0;
+    uint32_t ebase = 0;               // epoch base of the words the map currently shows
+    VctBuf<uint2> tiles;              // decoded (min, max) per dilated 8 x 8 tile of the current map (vct_launch_shadow_minmax)
+    uint32_t passes = 0;              // shadow passes rasterised into `words` since their last memset
+    VctRasterScratch raster;          // scratch of the shadow pass (the main draw's is per frame slot)
+    float light_vp[16] = {1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f};
+
+    void drop() { words.reset(); tiles.reset(); size = 0; }
+    void restart_epochs() { passes = 0u; }      // fresh or cleared words: the next pass starts with the memset
+    uint32_t next_epoch(bool* memset_due) const { *memset_due = (passes & 3u) == 0u; return 3u - (passes & 3u); }
+    void pass_done(uint32_t epoch) { ebase = VCT_SHADOW_EPOCH(epoch); ++passes; }
+    // a pass that fails leaves a map but NO tile bounds: a stale table would decide PCF windows wrongly, without one every window is fetched
+    int pass_result(int rc) { if (rc) tiles.reset(); return rc; }
+};
+
+// Which form the MAIN draw's visibility takes (the shadow pass is opaque and sparse: the direct form won every measurement).
+// mode 0 = auto: scenes without alpha-tested textures keep the direct form; otherwise six passes over the same tile rows are
+// sampled (vct_api_raster.hip kAutoSeq) and the faster form is kept until the mesh or the textures change.  1 / 2 = VCT_RASTER_PATH=direct / binned.
+struct VctRasterForm {
+    int mode = 0;
+    int state = 0;                    // position in the sampling sequence; 6: all sampled
+    int choice = -1;                  // -1 undecided, 0 direct, 1 binned
+    int rows[2] = {0, 0};             // tile rows of the sampled passes
+    bool in_sequence = false;         // the pass pick() was last asked about is the sequence's next
+    VctEvent ev[8];                   // begin / end of the four timed samples
+    int last_form = 0;                // form of the last main-draw visibility pass: 1 direct, 2 tile-binned (vct_get_stage_counts [6])
+    uint32_t bin_test_caps[2] = {0u, 0u};   // VCT_BIN_TEST_CAPS="records,entries": capacities REPORTED to the binned kernels (tests of the overflow paths)
+
+    void restart() { state = 0; choice = -1; }      // a new mesh or texture set: measured again
+    // the form of a pass over tile rows [row0, row1) (*binned), and the timed sample it is (0 .. 3) or -1
+    int pick(int row0, int row1, bool has_alpha_textures, bool* binned);      // (vct_api_raster.hip)
+    void launched() { if (in_sequence) ++state; }      // after the pass's visibility launch (and its end event) succeeded
+};
+
+// vct_gi_pass runs the G-buffer raster on a second stream beside the voxel stages: created on first use.
+struct VctForkJoin {
+    VctStream aux;
+    VctEvent ev_fork, ev_shadow, ev_join;
+};
+
+// Ordering between the two frame slots' streams.  The other slot's stream receives work only while its slot is selected,
+// so ONE join (drain) per selection orders (waits for) everything it holds: later producers of the same selection skip theirs.
+// vct_gi_pass -- five producers in a row -- paid five cross-queue waits per pass for nothing (0.860 ms against 0.817 on one slot).
+struct VctSlotOrder {
+    VctEvent ev;                      // scratch event of the cross-slot waits
+    bool streams_overlap = false;     // the second slot's stream was SEEN to run beside the first (vct_capi.hip streams_overlap)
+    bool produced = false;            // a stage that writes shared state ran on the selected slot's stream since the last switch
+    bool joined = false, drained = false;      // ... and the other slot's stream was joined / drained since then
+    void note_producer() { produced = true; }      // the next slot switch makes the other stream wait for this stream
+    void reset() { produced = joined = drained = false; }
+};
+
 struct vct_ctx {
     vct_config cfg;
     int device = 0;
     int reserved_cus = 0;             // VCT_COMM_RESERVED_CUS at vct_create: CUs kept for the communication stream
     std::string err;
 
-    VctBuf<uint32_t> chain;           // Morton chain (bounce 0: direct light)
-    VctBuf<uint32_t> chain_b;         // second chain (bounce 1), allocated by vct_bounce
-    bool use_chain_b = false;         // the trace reads chain_b until the next vct_inject_light
-    bool mips_valid = true;           // levels >= 1 describe level 0 (a fresh chain is all zero)
-    bool want_cells = false;          // vct_set_footprint_records / VCT_FOOTPRINT_RECORDS=1
-    VctBuf<uint4> cells;              // footprint records of the levels >= 1 of `chain` (32 B per texel of those levels)
-    bool cells_valid = false;         // ... rebuilt by vct_build_mips / vct_upload_chain_rgba8
-    VctBuf<uint32_t> aniso;           // [6][chain_texels - V^3] directional chains (cfg.anisotropic_mips)
-    size_t chain_texels = 0;
-    VctBuf<uint32_t> staging;         // linear staging for up/downloads (size of level 0)
-    int nlev = 0;
-
+    VctChain vol;
     VctBuf<float> gb_linear;          // [23][w*h] staging
     // lighting components (vct_set_lighting_components): VCT_SHOW_* mask of the composite; per-component outputs
     // (vct_set_aov_outputs): VCT_AOV_* bits, one buffer per frame slot (VctFrameSlot::aov)
@@ -205,7 +334,7 @@ struct vct_ctx {
     VctBuf<uint32_t> spread_lut;      // [1024] spread3(i) << 2 (vct_trace.hip: dilated anchor coordinates by scalar load)
     int n_diffuse = 0, n_specular = 0;
     bool steps_dirty = true;
-    bool fast_div = false;            // set by refresh_steps: constant divisors admit the FMA division
+    bool fast_div = false;            // set by vct_refresh_steps: constant divisors admit the FMA division
     int last_march_form = 0;          // division of the last march launch: 1 IEEE, 2 verified product, 3 x * r (vct_get_stage_counts [2])
     // vct_set_trace_timing: bracket every march launch with the two timing events vct_last_trace_ms reads.  On by default
     // (every entry point keeps working); a frame loop switches it off -- the two events cost a launch ~7 us of dispatch
@@ -216,52 +345,20 @@ struct vct_ctx {
     float light[3] = {0.0f, 1.0f, 0.25f};     // VCT.h:14
 
     VctMesh mesh;
-    VctBuf<uint32_t> shadow;          // shadow-map words (vct_internal.h vct_shadow_depth), shadow_size^2
-    int32_t shadow_size = 0;
-    uint32_t shadow_ebase = 0;        // epoch base of the words the map currently shows
-    VctBuf<uint2> shadow_tiles;       // decoded (min, max) per dilated 8 x 8 tile of the current map (vct_launch_shadow_minmax)
-    uint32_t shadow_passes = 0;       // shadow passes rasterised into this buffer since its last memset
-    VctRasterScratch shadow_raster;    // scratch of the shadow pass (the main draw's is per frame slot)
-    // Which form the MAIN draw's visibility takes (the shadow pass is opaque and sparse: the direct form won every
-    // measurement).  raster_mode 0 = auto: scenes without alpha-tested textures keep the direct form; otherwise the first
-    // pass runs direct, the second -- over the same tile rows -- binned, both between events, and the faster one is kept
-    // until the mesh or the textures change.  1 / 2 = VCT_RASTER_PATH=direct / binned (both passes), for A/B runs.
-    int raster_mode = 0;
-    int auto_rows[2] = {0, 0};         // tile rows of the timed sample pair
-    int last_raster_form = 0;          // form of the last main-draw visibility pass: 1 direct, 2 tile-binned (vct_get_stage_counts [6])
-    uint32_t bin_test_caps[2] = {0u, 0u};   // VCT_BIN_TEST_CAPS="records,entries": capacities REPORTED to the binned kernels (tests of the overflow paths)
-    int auto_state = 0;                                // position in the sampling sequence (vct_capi.hip kAutoSeq); 6: all sampled
-    int auto_choice = -1;                              // -1 undecided, 0 direct, 1 binned
-    hipEvent_t ev_auto[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // begin / end of the four timed samples
-    // second stream: vct_gi_pass runs the G-buffer raster beside the voxel stages
-    hipStream_t aux_stream = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_shadow = nullptr, ev_join = nullptr;
-    float light_vp[16];
+    VctShadowMap shadow;
+    VctRasterForm raster_form;
+    VctForkJoin fork;
     VctVoxelPlan vox;
     VctBuf<uint32_t> plan;             // [4] device counters used while planning
-    // these describe the chain, not the mesh: they survive a mesh change
-    VctBuf<uint32_t> brick_flags;      // [V^3/512] touched in the pending pass
-    VctBuf<uint32_t> brick_prev;       // [V^3/512] touched in the pass level 0 currently shows
-    VctBuf<uint32_t> mip_seen;         // [V^3/512] bricks non-empty when the chain's mips were last built
-    VctBuf<uint32_t> mip_seen_b;       // same for the bounce chain
     VctBuf<uint32_t> bounce_list;      // counter word + occupied-voxel list of the bounce
     VctBuf<uint32_t> brick_over;
-    bool chain_sparse_ready = true;    // bricks outside mip_seen have all-zero ancestors (true for a fresh, zero-filled
-                                       // chain; an upload clears it until a dense mip build over a resolved level 0)
     int acc_mode = 0;                  // vct_voxelize_mode of the pending (or last resolved) pass
-    bool level0_dirty = false;         // level 0 was written by an upload: next resolve is dense
     vct_comm* comm = nullptr;          // multi-GPU slabs + gather (vct_comm_init)
     // frame slots (see VctFrameSlot): slots [0, frames_in_flight) are live, slots[cur_slot] is selected
     int frames_in_flight = 1;          // 1 or 2
     int cur_slot = 0;
     VctFrameSlot slots[2];
-    hipEvent_t ev_xslot = nullptr;     // scratch event of the cross-slot waits
-    bool slot_streams_overlap = false; // the second slot's stream was SEEN to run beside the first (vct_capi.hip streams_overlap)
-    bool produced_since_switch = false;   // a stage that writes shared state ran on the selected slot's stream since the last switch
-    // The other slot's stream receives work only while its slot is selected, so ONE join (drain) per selection orders
-    // (waits for) everything it holds: later producers of the same selection skip theirs.  vct_gi_pass -- five producers
-    // in a row -- paid five cross-queue waits per pass for nothing (0.860 ms against 0.817 on one slot).
-    bool joined_since_switch = false, drained_since_switch = false;
+    VctSlotOrder xslot;
 };
 
 // the selected frame slot, and the other one (meaningful with two frames in flight)
@@ -269,16 +366,34 @@ inline VctFrameSlot& cur(vct_ctx* c) { return c->slots[c->cur_slot]; }
 inline const VctFrameSlot& cur(const vct_ctx* c) { return c->slots[c->cur_slot]; }
 inline VctFrameSlot& other(vct_ctx* c) { return c->slots[1 - c->cur_slot]; }
 
-// shared helpers (vct_capi.hip)
+inline int vct_tiles_x(const vct_ctx* c) { return (c->cfg.width + VCT_TILE - 1) / VCT_TILE; }
+inline int vct_tiles_y(const vct_ctx* c) { return (c->cfg.height + VCT_TILE - 1) / VCT_TILE; }
+inline bool vct_rows_in_frame(const vct_ctx* c, int row0, int row1) { return row0 >= 0 && row1 <= vct_tiles_y(c) && row0 <= row1; }
+inline size_t vct_gb_tiled_floats(const vct_ctx* c) { return (size_t)vct_tiles_x(c) * vct_tiles_y(c) * VCT_GB_NPLANES * VCT_TILE_PIX; }
+inline size_t vct_aov_frames(uint32_t which) { return (size_t)__builtin_popcount(which); }      // one frame per VCT_AOV_* bit that is on
+
+// ---- what more than one translation unit needs, by the file that defines it: vct_capi.hip ----
 int vct_fail(vct_ctx* c, int code, const std::string& msg);
-// trace kernel on the context stream, asynchronous; out_base (full-frame addressing) overrides the frame target when not null
-// row_stride > 1: only every row_stride-th tile row from row0 on; pack_rows: those rows back to back in out_base (interleaved slabs)
-int vct_launch_trace_rows(vct_ctx* c, int row0, int row1, uint16_t* out_base = nullptr, int row_stride = 1, bool pack_rows = false);
-// a new stream that was SEEN to run beside `base` (HIP shares a few hardware queues between a process' streams; two
-// streams on one queue execute in order): vct_capi.hip create_overlapping_stream
 int vct_create_overlapping_stream(vct_ctx* c, hipStream_t base, hipStream_t* out, bool* overlaps);
-int vct_tiles_x(const vct_ctx* c);
-int vct_tiles_y(const vct_ctx* c);
+// a stage that WRITES state both slots read waits on the GPU for all the other slot has in flight; the next slot switch makes the other stream wait for it
+int vct_pipeline_join(vct_ctx* c);
+// Uploads free and reallocate buffers the other slot's kernels may still read: the host waits for that slot.
+int vct_pipeline_drain(vct_ctx* c);
+// vct_api_scene.hip: textures are used once both the maps and the texture coordinates are there
+VctTextures vct_textures_of(const vct_ctx* c);
+// vct_api_raster.hip: `shadow_ready` not null: the visibility raster is issued at once, only the shading kernel (it reads the shadow map) waits for it
+int vct_render_gbuffer_rows_on(vct_ctx* c, const float view_proj[16], int32_t row0, int32_t row1, hipStream_t s, hipEvent_t shadow_ready = nullptr);
+// vct_api_voxel.hip: parameters of the voxelizer kernels (the context's mesh and shadow map, the buffers of plan `v`); the reference's ProjX/Y/Z
+VctVoxParams vct_vox_params(const vct_ctx* c, const VctVoxelPlan& v);
+void vct_glm_voxel_projections(const vct_ctx* c, float proj[48]);
+// vct_api_trace.hip: the step tables on the device follow the config; everything the march needs (screen trace and bounce)
+int vct_refresh_steps(vct_ctx* c);
+void vct_fill_march_params(const vct_ctx* c, VctTraceParams& p, const uint32_t* chain);
+// asynchronous, on the slot's stream.  row_stride > 1: only every row_stride-th tile row from row0 on; pack_rows: those rows back to back in out_base (interleaved slabs)
+int vct_launch_trace_rows(vct_ctx* c, int row0, int row1, uint16_t* out_base = nullptr, int row_stride = 1, bool pack_rows = false);
+// vct_multi.hip: slab of the attached communicator (false: none attached); its release
+bool vct_comm_rows(const vct_ctx* c, int* row0, int* row1);
+void vct_comm_release(vct_ctx* c);
 
 #define HIP_TRY(c, expr)                                                                     \
     do {                                                                                     \
@@ -287,5 +402,6 @@ int vct_tiles_y(const vct_ctx* c);
             return vct_fail((c), e_ == hipErrorOutOfMemory ? VCT_ERR_NOMEM : VCT_ERR_DEVICE, \
                             std::string(#expr) + ": " + hipGetErrorString(e_));              \
     } while (0)
+#define PIPE_TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
 
 #endif

@@ -246,13 +246,13 @@ static void comm_free(vct_comm* m) {
 void vct_comm_release(vct_ctx* c) {
     if (!c || !c->comm) return;
     // (frame slots may have been added or switched since vct_comm_init: the streams that carry this communicator's work NOW)
-    c->comm->ctx_stream = cur(c).stream;
-    c->comm->ctx_stream2 = c->frames_in_flight > 1 ? other(c).stream : nullptr;
+    c->comm->ctx_stream = cur(c).stream.get();
+    c->comm->ctx_stream2 = c->frames_in_flight > 1 ? other(c).stream.get() : nullptr;
     comm_free(c->comm);
     c->comm = nullptr;
 }
 
-// slab of the attached communicator (vct_capi.hip: vct_gi_pass on a rank context); false when there is none
+// slab of the attached communicator (vct_api_trace.hip: vct_gi_pass on a rank context); false when there is none
 bool vct_comm_rows(const vct_ctx* c, int* row0, int* row1) {
     if (!c || !c->comm) return false;
     *row0 = c->comm->row0;
@@ -406,10 +406,10 @@ int vct_comm_init(vct_ctx* c, const void* id128, int32_t rank, int32_t world) {
         // the exchange step is meant to run beside the next frame's trace: a stream that shares the context stream's hardware
         // queue would run behind it instead (round 6: HIP hands out four queues; RCCL and torch hold streams of their own)
         bool ov = false;
-        e = vct_create_overlapping_stream(c, cur(c).stream, &m->comm_stream, &ov) == VCT_OK ? hipSuccess : hipErrorUnknown;
+        e = vct_create_overlapping_stream(c, cur(c).stream.get(), &m->comm_stream, &ov) == VCT_OK ? hipSuccess : hipErrorUnknown;
         m->comm_stream_overlaps = ov;
     }
-    m->ctx_stream = cur(c).stream;
+    m->ctx_stream = cur(c).stream.get();
     if (direct && e == hipSuccess) {
         int khz = 0;
         if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->device) == hipSuccess && khz > 0) m->wall_khz = khz;
@@ -424,15 +424,15 @@ int vct_comm_init(vct_ctx* c, const void* id128, int32_t rank, int32_t world) {
             // are allocated fine-grained (advisor, round 5); no fallback -- a coarse-grained frame could be silently stale.
             e = direct ? hipExtMallocWithFlags((void**)&m->buf[k], m->buf_halves * 2, hipDeviceMallocFinegrained)
                        : hipMalloc(&m->buf[k], m->buf_halves * 2);
-            if (e == hipSuccess) e = hipMemsetAsync(m->buf[k], 0, m->buf_halves * 2, cur(c).stream);
+            if (e == hipSuccess) e = hipMemsetAsync(m->buf[k], 0, m->buf_halves * 2, cur(c).stream.get());
         }
         if (e == hipSuccess) e = hipEventCreateWithFlags(&m->traced[k], hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&m->gathered[k], hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreate(&m->g0[k]);
         if (e == hipSuccess) e = hipEventCreate(&m->g1[k]);
-        if (e == hipSuccess) e = hipEventRecord(m->gathered[k], cur(c).stream);      // "previous gather" of the first use
+        if (e == hipSuccess) e = hipEventRecord(m->gathered[k], cur(c).stream.get());      // "previous gather" of the first use
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(cur(c).stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(cur(c).stream.get());
     if (e != hipSuccess) {
         comm_free(m);
         return vct_fail(c, e == hipErrorOutOfMemory ? VCT_ERR_NOMEM : VCT_ERR_DEVICE,
@@ -564,7 +564,7 @@ int vct_frame_step(vct_ctx* c) {
     // that address lies before the allocation).  Root: the frame buffer itself (slab 0 at offset 0, in-place gather).
     uint16_t* slab = m->buf[k];
     const size_t first_row_halves = (size_t)m->row0 * VCT_TILE * c->cfg.width * 4;
-    HIP_TRY(c, hipStreamWaitEvent(cur(c).stream, m->gathered[k], 0));    // buffer k is free once its last gather is done
+    HIP_TRY(c, hipStreamWaitEvent(cur(c).stream.get(), m->gathered[k], 0));    // buffer k is free once its last gather is done
     const bool uneven = !m->starts.empty();
     if (m->direct) {
         // direct slabs (see DirectShm): flags instead of a collective, the slab stored straight into the root's frame
@@ -572,15 +572,15 @@ int vct_frame_step(vct_ctx* c) {
         const long long ticks = (long long)m->timeout_ms * m->wall_khz;        // wall_clock64 ticks per ms = its rate in kHz
         const size_t row_halves = (size_t)VCT_TILE * c->cfg.width * 4;
         if (m->rank == 0) {
-            hipLaunchKernelGGL(k_flag_set, dim3(1), dim3(1), 0, cur(c).stream, &m->shm_dev->release[k], gen - 1u);
+            hipLaunchKernelGGL(k_flag_set, dim3(1), dim3(1), 0, cur(c).stream.get(), &m->shm_dev->release[k], gen - 1u);
             HIP_TRY(c, hipGetLastError());
             uint16_t* base = uneven ? m->buf[k] : slab - first_row_halves;
             const int rc = m->interleaved ? vct_launch_trace_rows(c, m->row0, m->row1, slab, m->world, true)
                                           : vct_launch_trace_rows(c, m->row0, m->row1, base);
             if (rc) return rc;
-            const hipStream_t cs = m->same_stream ? cur(c).stream : m->comm_stream;
+            const hipStream_t cs = m->same_stream ? cur(c).stream.get() : m->comm_stream;
             if (!m->same_stream) {
-                HIP_TRY(c, hipEventRecord(m->traced[k], cur(c).stream));
+                HIP_TRY(c, hipEventRecord(m->traced[k], cur(c).stream.get()));
                 HIP_TRY(c, hipStreamWaitEvent(m->comm_stream, m->traced[k], 0));
             }
             HIP_TRY(c, hipEventRecord(m->g0[k], cs));
@@ -597,7 +597,7 @@ int vct_frame_step(vct_ctx* c) {
             HIP_TRY(c, hipEventRecord(m->g1[k], cs));
             HIP_TRY(c, hipEventRecord(m->gathered[k], cs));
         } else {
-            hipLaunchKernelGGL(k_flag_wait, dim3(1), dim3(64), 0, cur(c).stream, &m->shm_dev->release[k], 1, 1, gen - 1u,
+            hipLaunchKernelGGL(k_flag_wait, dim3(1), dim3(64), 0, cur(c).stream.get(), &m->shm_dev->release[k], 1, 1, gen - 1u,
                                &m->shm_dev->timed_out, ticks, m->abort_dev);
             HIP_TRY(c, hipGetLastError());
             // where this rank's slab lives in the root's buffer k: packed slab `rank` (equal / interleaved) or its own rows
@@ -605,11 +605,11 @@ int vct_frame_step(vct_ctx* c) {
             const int rc = m->interleaved ? vct_launch_trace_rows(c, m->row0, m->row1, peer_slab, m->world, true)
                                           : vct_launch_trace_rows(c, m->row0, m->row1, peer_slab - first_row_halves);
             if (rc) return rc;
-            HIP_TRY(c, hipEventRecord(m->g0[k], cur(c).stream));
-            hipLaunchKernelGGL(k_flag_set, dim3(1), dim3(1), 0, cur(c).stream, &m->shm_dev->done[k][m->rank], gen);
+            HIP_TRY(c, hipEventRecord(m->g0[k], cur(c).stream.get()));
+            hipLaunchKernelGGL(k_flag_set, dim3(1), dim3(1), 0, cur(c).stream.get(), &m->shm_dev->done[k][m->rank], gen);
             HIP_TRY(c, hipGetLastError());
-            HIP_TRY(c, hipEventRecord(m->g1[k], cur(c).stream));
-            HIP_TRY(c, hipEventRecord(m->gathered[k], cur(c).stream));
+            HIP_TRY(c, hipEventRecord(m->g1[k], cur(c).stream.get()));
+            HIP_TRY(c, hipEventRecord(m->gathered[k], cur(c).stream.get()));
         }
         m->last = k;
         ++m->frames;
@@ -620,9 +620,9 @@ int vct_frame_step(vct_ctx* c) {
     const int rc = m->interleaved ? vct_launch_trace_rows(c, m->row0, m->row1, slab, m->world, true)
                                   : vct_launch_trace_rows(c, m->row0, m->row1, out_base);     // an empty slab launches nothing
     if (rc) return rc;
-    const hipStream_t cs = m->same_stream ? cur(c).stream : m->comm_stream;
+    const hipStream_t cs = m->same_stream ? cur(c).stream.get() : m->comm_stream;
     if (!m->same_stream) {
-        HIP_TRY(c, hipEventRecord(m->traced[k], cur(c).stream));
+        HIP_TRY(c, hipEventRecord(m->traced[k], cur(c).stream.get()));
         HIP_TRY(c, hipStreamWaitEvent(m->comm_stream, m->traced[k], 0));
     }
     Rccl* r = rccl();
@@ -694,10 +694,10 @@ int vct_comm_sync(vct_ctx* c) {
     const auto t0 = std::chrono::steady_clock::now();
     int spins = 0;
     while (true) {
-        hipError_t qc = hipStreamQuery(cur(c).stream);
+        hipError_t qc = hipStreamQuery(cur(c).stream.get());
         if (qc != hipSuccess && qc != hipErrorNotReady) HIP_TRY(c, qc);
         if (qc == hipSuccess && c->frames_in_flight > 1) {      // two frames in flight: the other slot's stream carries steps too
-            qc = hipStreamQuery(other(c).stream);
+            qc = hipStreamQuery(other(c).stream.get());
             if (qc != hipSuccess && qc != hipErrorNotReady) HIP_TRY(c, qc);
         }
         const hipError_t q = hipStreamQuery(m->comm_stream);
@@ -794,18 +794,18 @@ int vct_selftest_interleaved(vct_ctx* c, int32_t world, uint64_t* mismatches) {
     VctBuf<uint2> gathered, il, plain;
     if (gathered.alloc(slab_pixels * world) != hipSuccess || il.alloc(npix) != hipSuccess || plain.alloc(npix) != hipSuccess)
         return vct_fail(c, VCT_ERR_NOMEM, "vct_selftest_interleaved: out of memory");
-    hipError_t e = hipMemsetAsync(gathered.get(), 0, slab_pixels * world * 8, cur(c).stream);
-    if (e == hipSuccess) e = hipMemsetAsync(plain.get(), 0, npix * 8, cur(c).stream);
+    hipError_t e = hipMemsetAsync(gathered.get(), 0, slab_pixels * world * 8, cur(c).stream.get());
+    if (e == hipSuccess) e = hipMemsetAsync(plain.get(), 0, npix * 8, cur(c).stream.get());
     if (e != hipSuccess) return vct_fail(c, VCT_ERR_DEVICE, hipGetErrorString(e));
     for (int r = 0; r < world; ++r) {
         const int rc = vct_launch_trace_rows(c, r < ty ? r : ty, ty, (uint16_t*)(gathered.get() + slab_pixels * r), world, true);
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(k_deinterleave, dim3(2048), dim3(256), 0, cur(c).stream, gathered.get(), il.get(), w, h, world, slab_pixels);
+    hipLaunchKernelGGL(k_deinterleave, dim3(2048), dim3(256), 0, cur(c).stream.get(), gathered.get(), il.get(), w, h, world, slab_pixels);
     int rc = vct_launch_trace_rows(c, 0, ty, (uint16_t*)plain.get());
     if (rc) return rc;
     std::vector<uint2> a(npix), b(npix);
-    e = hipStreamSynchronize(cur(c).stream);
+    e = hipStreamSynchronize(cur(c).stream.get());
     if (e == hipSuccess) e = hipMemcpy(a.data(), il.get(), npix * 8, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(b.data(), plain.get(), npix * 8, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return vct_fail(c, VCT_ERR_DEVICE, hipGetErrorString(e));

@@ -376,6 +376,60 @@ int vct_get_diffuse_rate(const vct_ctx* ctx, int32_t* rate, uint64_t* marched_pi
  * diffuse group; waits for it. */
 int vct_last_diffuse_rate_ms(vct_ctx* ctx, float ms[4]);
 
+/* ---- voxel view -----------------------------------------------------------------------------------------
+ * No reference counterpart (the reference has no way to look at its VoxelTexture), so the definition is this build's.
+ * Every pixel's ray is walked cell by cell through ONE level of a chain -- or through a per-voxel attribute -- and
+ * composited front to back with the march's own rule (S/VoxelConeTracing.fs:100,102): at level 0 of an injected chain
+ * alpha is 0 or 1 and the view shows the first occupied voxel, at coarse levels it shows what the cones see.  It is how
+ * one picks grid_world_size and voxel_dim, sees light leaking through thin walls, a mesh falling out of the grid, a
+ * bounce that did nothing or a level that has gone opaque -- without a 4.57 GiB download at 1024^3.
+ * All of it fp32, multiplies, adds and compares in the written order, nothing fused, IEEE divisions.  w x h the frame,
+ * V the grid, L the level, N = V >> L, G = grid_world_size, m = inv_view_proj (column-major), row 0 the bottom row:
+ *   Ray      of pixel (x, y): nx = (2 (x + 0.5)) / w - 1, ny likewise with h; for nz = -1 and nz = +1
+ *              r_i = ((m[i] nx + m[4 + i] ny) + m[8 + i] nz) + m[12 + i],  i = 0 .. 3,     point = r_xyz / r_w.
+ *            o = the near point (nz = -1), d = far - near (not normalised).  A non-finite o or d, or d = 0: a miss.
+ *   Grid     units: g_a = (o_a / G + 0.5) N,  e_a = (d_a / G) N,  inv_a = 1 / e_a where e_a != 0.
+ *   Entry    per axis with e_a != 0 the pair (0 - g_a) inv_a, (N - g_a) inv_a, smaller first; t_in = max(0, the smaller
+ *            ones), t_out = min(the larger ones) -- folded over x, y, z in that order from 0 and +inf, each step keeping
+ *            what it has unless the next value compares greater (smaller).  An axis with e_a = 0 gives no pair and is a
+ *            miss unless 0 <= g_a < N.  A miss unless t_in < t_out.
+ *            Start cell c_a = (int)min(max(floor(g_a + t_in e_a), 0), N - 1), the clamps taken on the float.
+ *   Walk     the next plane of axis a is b_a = c_a + (e_a > 0 ? 1 : 0) and its parameter t_a = ((float)b_a - g_a) inv_a
+ *            (+inf for e_a = 0): a function of the integer plane index alone, never accumulated.  Visit the cell; step
+ *            the axis with the smallest t_a by +1 (e_a > 0) or -1 (start with x; y replaces it if t_y < t_x; z replaces
+ *            that if t_z is smaller still: ties go x before y before z); stop when the cell leaves [0, N)^3.
+ *   Visit    T = the texel of cell (c_x, c_y, c_z), each byte c as c / 255.0f;  oma = 1 - A;
+ *            C_rgb = C_rgb + oma T_rgb;  A = A + oma T_a;  stop after a visit that leaves A >= config.max_alpha.
+ *            (A texel with alpha 0 and rgb != 0 -- uploaded volumes can hold them -- still adds its colour.)
+ *   Output   (C_r, C_g, C_b, A) from C = 0, A = 0; a miss is (0, 0, 0, 0).
+ * The kernel skips empty space and still writes this frame bit for bit.  A zero parent texel proves nothing about its
+ * children (the mips requantise) and the voxelizer's brick flags know nothing of uploaded chains, so it keeps one bit per
+ * 8^3 block of the viewed level, "some texel word != 0" (a 64-bit word per 32^3 region: 256 KiB at 1024^3), rebuilt by
+ * a small kernel in front of the first view after the chain or the attributes changed; inside an empty block it walks
+ * the cells with no fetch.  VCT_VOXVIEW_SKIP=0 in the environment takes the instantiation without it (A/B).
+ * vct_render_voxels writes the selected frame slot's RGBA16F frame -- same addressing and f32 -> f16 rounding as the
+ * trace, vct_set_frame_target honoured -- so vct_download_frame and vct_get_frame_device show it.  Asynchronous on the
+ * slot's stream; ordered against the stages that write the chain exactly as a resident trace is (it reads shared state
+ * and writes slot state only: the frame and the slot's occupancy words).  It leaves the G-buffer, the step counts, the
+ * per-component outputs and vct_last_trace_ms alone, works with every config.trace_variant, with two frame slots, with
+ * config.anisotropic_mips (it shows the isotropic chain) and with footprint records (it ignores them).
+ * inv_view_proj: the column-major fp32 inverse of the matrix vct_render_gbuffer takes (the caller inverts; the facade
+ * and the Python binding invert in double and round once).
+ * VCT_ERR_INVALID: a NULL context or matrix; a non-finite matrix element; an unknown source; a level outside
+ * [0, levels); ALBEDO / NORMAL without config.voxel_attributes, with level != 0 or before a mesh was uploaded; a level
+ * >= 1 of a chain whose level 0 changed since the last vct_build_mips (the rule of the trace); a context of a multi-GPU
+ * frame. */
+enum {
+    VCT_VOXVIEW_CURRENT = 0,    /* the chain the trace reads now (the bounce chain after vct_bounce, else radiance) */
+    VCT_VOXVIEW_RADIANCE = 1,   /* the bounce-0 radiance chain, whatever the trace reads */
+    VCT_VOXVIEW_ALBEDO = 2,     /* per-voxel mean albedo   (config.voxel_attributes = 1, level 0 only) */
+    VCT_VOXVIEW_NORMAL = 3      /* per-voxel biased normal (config.voxel_attributes = 1, level 0 only) */
+};
+int vct_render_voxels(vct_ctx* ctx, const float inv_view_proj[16], int32_t source, int32_t level);
+/* Device time of the walk kernel of the selected slot's last view in milliseconds (the occupancy rebuild, when one was
+ * due, runs in front of the bracket).  Needs trace timing on (vct_set_trace_timing) when the view was issued; waits. */
+int vct_last_voxel_view_ms(vct_ctx* ctx, float* ms);
+
 /* ---- two frames in flight (round 6) -----------------------------------------------------------------
  * The reference's Render() (VCT.h:146-190) issues GL commands; the driver starts frame k + 1 while frame k
  * drains -- nothing in R/main.cpp:77-94 waits for a frame.  A HIP stream does wait: each whole-frame trace

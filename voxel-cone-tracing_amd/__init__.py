@@ -30,6 +30,8 @@ ABI_VERSION = 7
 SHOW_DIFFUSE, SHOW_INDIRECT_DIFFUSE, SHOW_SPECULAR, SHOW_INDIRECT_SPECULAR, SHOW_AMBIENT_OCCLUSION = 1, 2, 4, 8, 16
 SHOW_ALL = 31
 AOV_INDIRECT_DIFFUSE, AOV_INDIRECT_SPECULAR, AOV_DIRECT = 1, 2, 4
+# sources of the voxel view (Context.render_voxels)
+VOXVIEW_CURRENT, VOXVIEW_RADIANCE, VOXVIEW_ALBEDO, VOXVIEW_NORMAL = 0, 1, 2, 3
 
 # every symbol include/vct.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
@@ -53,6 +55,7 @@ ABI_SYMBOLS = [
     "vct_set_frames_in_flight", "vct_get_frames_in_flight", "vct_select_frame_slot", "vct_selftest_texel_buffer",
     "vct_set_trace_timing", "vct_set_lighting_components", "vct_get_lighting_components", "vct_set_aov_outputs",
     "vct_download_aov", "vct_get_aov_device", "vct_set_diffuse_rate", "vct_get_diffuse_rate", "vct_last_diffuse_rate_ms",
+    "vct_render_voxels", "vct_last_voxel_view_ms",
 ]
 
 
@@ -154,6 +157,8 @@ _lib.vct_get_aov_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void
 _lib.vct_set_diffuse_rate.argtypes = [C.c_void_p, C.c_int32]
 _lib.vct_get_diffuse_rate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.vct_last_diffuse_rate_ms.argtypes = [C.c_void_p, C.c_void_p]
+_lib.vct_render_voxels.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
+_lib.vct_last_voxel_view_ms.argtypes = [C.c_void_p, C.c_void_p]
 _lib.vct_upload_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
 
 
@@ -532,6 +537,19 @@ class Context:
         out = np.zeros((self.cfg.height, self.cfg.width, 4), np.uint16)
         self._ck(_lib.vct_download_frame(self._h, _ptr(out)), "vct_download_frame")
         return out
+
+    def render_voxels(self, inv_view_proj, source=VOXVIEW_CURRENT, level=0):
+        """Voxel view (include/vct.h): ray-march `level` of a chain (VOXVIEW_CURRENT / _RADIANCE) or a voxel attribute
+        (VOXVIEW_ALBEDO / _NORMAL) into the selected slot's frame.  inv_view_proj: column-major float32[16], e.g.
+        scene.invert_matrix(scene.camera_view_proj(cam, w, h)).  Asynchronous; download_frame() returns the view."""
+        m = np.ascontiguousarray(inv_view_proj, np.float32).reshape(16)
+        self._ck(_lib.vct_render_voxels(self._h, _ptr(m), int(source), int(level)), "vct_render_voxels")
+
+    def last_voxel_view_ms(self):
+        """Device ms of the walk kernel of the selected slot's last voxel view (trace timing must have been on)."""
+        v = C.c_float()
+        self._ck(_lib.vct_last_voxel_view_ms(self._h, C.byref(v)), "vct_last_voxel_view_ms")
+        return v.value
 
     def set_frame_target(self, dev_ptr):
         """Kernel output goes to caller-owned HBM (full-frame addressing); None restores the default."""

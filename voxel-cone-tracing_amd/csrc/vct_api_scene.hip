@@ -127,6 +127,7 @@ int build_voxel_slots(vct_ctx* c, const uint2* frags, uint32_t nfrags) {
     HIP_TRY(c, hipMemsetAsync(c->vol.brick_flags.get(), 0, flag_bytes, cur(c).stream.get()));
     HIP_TRY(c, hipStreamSynchronize(cur(c).stream.get()));
     c->vox = std::move(v);
+    c->vol.touched();      // fresh (zeroed) attribute pools and slots: a voxel view of the attributes rebuilds its occupancy
     return VCT_OK;
 }
 
@@ -169,6 +170,7 @@ int vct_upload_triangles(vct_ctx* c, const float* pos, const int32_t* material, 
     // leaves the context without a plan (vct_voxelize then refuses) instead of with the old mesh's plan over the new
     // mesh's triangles.  Level 0 / brick_prev keep describing what the chain shows.
     c->vox = VctVoxelPlan();
+    c->vol.touched();
     m.tri_nrm.reset(); m.tri_tan.reset(); m.tri_bit.reset(); m.tri_uv.reset();       // belong to the old mesh
     m.mat_tex.reset();                                                                // indexed by the old materials
     if (ntri >= (1 << 23))

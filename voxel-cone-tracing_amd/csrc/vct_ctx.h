@@ -151,6 +151,13 @@ struct VctFrameSlot {
     bool last_trace_compacted = false;  // ... of trace_variant 4: counts per virtual tile, no per-row histogram
     bool last_was_screen_trace = false; // the step counters hold a screen trace (indexed by tile row), not a bounce
     bool have_gbuffer = false;          // a G-buffer is resident (uploaded by vct_trace or rendered)
+    // voxel view (vct_render_voxels): the occupancy words of the level it last showed -- slot state, so that a view writes
+    // nothing the other slot reads -- and what they were built from; rebuilt when either differs
+    VctBuf<unsigned long long> vv_occ;
+    const uint32_t* vv_texels = nullptr;
+    uint64_t vv_gen = 0;
+    VctEvent vv_ev0, vv_ev1;            // timing events of the view's walk (vct_last_voxel_view_ms)
+    bool have_view = false, last_view_timed = false;
     VctRasterScratch raster;            // the main draw's
 
     // where a trace writes and a download reads: the caller's target or the slot's own frame
@@ -236,6 +243,7 @@ struct VctChain {
     bool mips_valid = true;           // levels >= 1 describe level 0 (a fresh chain is all zero)
     bool cells_valid = false;         // `cells` describe the levels >= 1 of `chain`
     bool level0_dirty = false;        // level 0 was written by an upload: next resolve is dense
+    uint64_t gen = 1;                 // counts the changes of anything a voxel view can show (chains, pooled attributes)
     bool chain_sparse_ready = true;   // bricks outside mip_seen have all-zero ancestors (true for a fresh, zero-filled
                                       // chain; an upload clears it until a dense mip build over a resolved level 0)
 
@@ -245,13 +253,14 @@ struct VctChain {
     bool tracked() const { return brick_prev && mip_seen && !level0_dirty; }      // level 0 mirrors brick_prev: a resolve's output, not an upload's
     // the sparse mip build reduces only bricks that hold something now (brick_prev) or did at the last build (mip_seen)
     bool sparse_mips_ok() const { return tracked() && chain_sparse_ready; }
+    void touched() { ++gen; }
     void level0_uploaded(bool with_levels) {      // the next resolve and mip build are dense
-        use_chain_b = false; mips_valid = with_levels; cells_valid = false; level0_dirty = true; chain_sparse_ready = false;
+        touched(); use_chain_b = false; mips_valid = with_levels; cells_valid = false; level0_dirty = true; chain_sparse_ready = false;
     }
-    void level0_resolved() { level0_dirty = false; use_chain_b = false; mips_valid = false; }      // vct_inject_light
+    void level0_resolved() { touched(); level0_dirty = false; use_chain_b = false; mips_valid = false; }      // vct_inject_light
     void mips_reduced(bool sparse) { if (!sparse) chain_sparse_ready = tracked(); }      // a dense build over a tracked level 0 makes the sparse form valid again
-    void mips_built() { mips_valid = true; use_chain_b = false; }      // ... and the directional chains followed
-    void bounce_done() { use_chain_b = true; }
+    void mips_built() { touched(); mips_valid = true; use_chain_b = false; }      // ... and the directional chains followed
+    void bounce_done() { touched(); use_chain_b = true; }
     void records_valid(bool v) { cells_valid = v; }      // built; or freed / about to be rebuilt
 };
 

@@ -502,4 +502,20 @@ hipError_t vct_launch_voxelize_reference(const VctVoxParams& p, int32_t* big_lis
                                          hipStream_t s);
 hipError_t vct_launch_bounce(const VctTraceParams& p, hipStream_t s);
 
+// the voxel view (include/vct.h "voxel view", vct_voxview.hip)
+struct VctVoxViewParams {
+    const uint32_t* texels;            // the viewed level (Morton), or the pooled attribute [slot][512] when brick_slot is set
+    const uint32_t* brick_slot;        // [V^3 / 512] brick -> slot of a pooled attribute; null: `texels` is a level of a chain
+    unsigned long long* occ;           // occupancy words, [occ_dim^3]: one bit per 8^3 block, one word per 32^3 region
+    int32_t N;                         // cells per side of the viewed level, V >> level
+    int32_t occ_dim;                   // max(1, N / 32)
+    float G, max_alpha;
+    float m[16];                       // column-major inverse view-projection
+    int32_t width, height, tiles_x, tiles_y;
+    uint16_t* out;                     // RGBA16F [h][w][4]
+};
+hipError_t vct_launch_voxview_occupancy(const VctVoxViewParams& p, hipStream_t s);
+// skip = false: the instantiation without the occupancy look-ups (every block is fetched): the A/B arm of the measurements
+hipError_t vct_launch_voxview(const VctVoxViewParams& p, bool skip, hipStream_t s);
+
 #endif

@@ -46,11 +46,8 @@
 
 #include "../../include/vct.h"
 #include "vct_internal.h"
+#include "vct_texel.h"
 
-typedef int vct_v4i32 __attribute__((ext_vector_type(4)));
-typedef float vct_v4f32 __attribute__((ext_vector_type(4)));
-__device__ vct_v4f32 vct_struct_buffer_load_format_v4f32(vct_v4i32 rsrc, int vindex, int voffset, int soffset, int aux)
-    __asm("llvm.amdgcn.struct.buffer.load.format.v4f32");
 
 namespace {
 
@@ -114,24 +111,7 @@ __device__ __forceinline__ float div_const(float x, float d, float r) {
 // (checked exhaustively in tests/test_abi.py::test_unorm8_decode_exact).
 __device__ __forceinline__ float unorm8(uint32_t c) { return vct_unorm8_to_float(c); }
 
-// A level of the chain as a TEXEL BUFFER: buffer resource with stride 4 and format 8_8_8_8 UNORM; the structured load takes
-// the texel's Morton INDEX (a 4 GiB level -- 1024^3 level 0 -- is addressed in full; the raw byte-offset form fails its
-// range check on that level's last texel) and returns the four channels converted by the texture path.  Declared like
-// composable_kernel declares its buffer loads, so that the compiler tracks the load's completion itself.
-// (vct_v4i32 / vct_v4f32 / vct_struct_buffer_load_format_v4f32: declared in front of this namespace)
-__device__ __forceinline__ vct_v4i32 level_texel_buffer(const uint32_t* level_base) {
-    const uint64_t a = (uint64_t)level_base;
-    vct_v4i32 r;
-    r.x = __builtin_amdgcn_readfirstlane((int)(uint32_t)a);
-    r.y = __builtin_amdgcn_readfirstlane((int)(((uint32_t)(a >> 32) & 0xffffu) | (4u << 16)));     // base[47:32] | stride 4
-    r.z = 0x40000000;                   // records: no level has more than 2^30 texels
-    r.w = 0x50fac;                      // DST_SEL x,y,z,w = R,G,B,A | NUM_FORMAT_UNORM << 12 | DATA_FORMAT_8_8_8_8 << 15
-    return r;
-}
-__device__ __forceinline__ float4 texel_f32(vct_v4i32 rsrc, uint32_t index) {
-    const vct_v4f32 v = vct_struct_buffer_load_format_v4f32(rsrc, (int)index, 0, 0, 0);
-    return make_float4(v.x, v.y, v.z, v.w);
-}
+// level_texel_buffer / texel_f32 (a level of the chain as an RGBA8 UNORM texel buffer) and pack_half2: vct_texel.h
 
 // LDS operations of one wave execute in order, so a slab written and then read by the lanes of
 // the same wave needs no s_barrier -- only the compiler must not reorder across this point.
@@ -653,11 +633,6 @@ __device__ __forceinline__ F4 cone_march(const VctTraceParams& p, bool alive, F3
     }
     steps_out = steps;
     return {cr, cg, cb, occ};
-}
-
-__device__ __forceinline__ uint32_t pack_half2(float a, float b) {
-    const __half ha = __float2half_rn(a), hb = __float2half_rn(b);
-    return (uint32_t)__half_as_ushort(ha) | ((uint32_t)__half_as_ushort(hb) << 16);
 }
 
 __device__ __forceinline__ void flush_stats(const VctTraceParams& p, const MarchStats& ms, int lane) {

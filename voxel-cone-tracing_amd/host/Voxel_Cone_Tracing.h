@@ -12,6 +12,7 @@
 //   DrawVoxelTexture()         VCT.h:213-250  -> vct_voxelize + vct_inject_light + vct_build_mips
 //   Render()                   VCT.h:146-190  -> vct_render_gbuffer (GPU raster of the main draw's vertex and
 //                                                non-cone fragment work) + vct_trace_current -> RGBA16F frame
+//                                                (ShowVoxels: vct_render_voxels instead, the voxel view)
 // Every stage runs on the GPU and a frame never leaves HBM until Frame() is read.
 //
 // Differences a caller can observe, all forced by running headless on a compute GPU:
@@ -210,6 +211,13 @@ struct Voxel_Cone_Tracing {
     // fragment); pixels on edges and thin geometry march their own.  1 (default): every pixel, the reference's frame.
     // Handed over by every Render(), like the Show* switches.  Not on a rank of a multi-GPU run.
     int DiffuseRate = 1;
+    // Voxel view (vct_render_voxels, include/vct.h: no reference counterpart): with ShowVoxels on, Render() skips the
+    // G-buffer raster and the trace and ray-marches level VoxelViewLevel of VoxelViewSource (a VCT_VOXVIEW_* value) into
+    // the frame with the camera's matrix -- Frame() shows the voxels.  Handed over by every Render().  Not on a rank of a
+    // multi-GPU run.
+    bool ShowVoxels = false;
+    int VoxelViewSource = VCT_VOXVIEW_CURRENT;
+    int VoxelViewLevel = 0;
     int Bounces = 1;    // 2 = re-inject the lit voxels once (the "2 bounces" of the reference's README.md:16,
                         // which its code does not implement: VCT.h:138-139 injects once); set before init
 
@@ -324,6 +332,13 @@ struct Voxel_Cone_Tracing {
         int32_t slots = 1;
         if (!whole_pass && vct_get_frames_in_flight(ctx, &slots, nullptr, nullptr) == VCT_OK && slots == 2)
             if (!check(vct_select_frame_slot(ctx, (int32_t)(frame_no++ & 1u)), "vct_select_frame_slot")) return;
+        if (ShowVoxels) {                                        // the voxel view instead of raster + trace
+            float inv[16];
+            if (vcth_invert_matrix(vp, inv) != 0) { last_status = VCT_ERR_INVALID; printf("ERROR::VCT::Render: singular view-projection\n"); return; }
+            if (!check(vct_render_voxels(ctx, inv, VoxelViewSource, VoxelViewLevel), "vct_render_voxels")) return;
+            frame_on_host = false;
+            return;
+        }
         if (rank_ctx) {                                          // multi-GPU: this rank's slab, one gather
             if (!check(vct_render_gbuffer_rows(ctx, vp, row0, row1), "vct_render_gbuffer_rows")) return;
             if (!check(vct_frame_step(ctx), "vct_frame_step")) return;

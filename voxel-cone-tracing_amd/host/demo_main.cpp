@@ -7,7 +7,13 @@
 //   vct_demo [--scene procedural:atrium|procedural:atrium-textured|procedural:bistro|procedural:cornell] [--voxels 128] [--size 1280x720]
 //            [--shadow 4096] [--frames 3] [--bounces 1|2] [--ppm out.ppm] [--gpus N] [--dynamic-light] [--frames-in-flight 1|2]
 //            [--show diffuse,indirect-diffuse,specular,indirect-specular,ao] [--diffuse-rate 1|2]
+//            [--voxels [current|radiance|albedo|normal[:level]]]
 //
+// --voxels SOURCE[:LEVEL]: the voxel view instead of the traced frame (Voxel_Cone_Tracing::ShowVoxels,
+//   vct_render_voxels): every Render() ray-marches LEVEL (default 0) of the chain the trace reads (current, the default
+//   when --voxels stands alone), the bounce-0 radiance chain, or the per-voxel albedo / normal (level 0; they need
+//   --bounces 2, which keeps the attributes).  cone_steps and trace_ms then print 0 and view_ms the walk's device time.
+//   (--voxels followed by a NUMBER keeps its older meaning, the grid size.)
 // --diffuse-rate 2: the six diffuse cones at half screen rate with a depth- and normal-aware upsampling
 //   (Voxel_Cone_Tracing::DiffuseRate, vct_set_diffuse_rate); single GPU only.  Default 1.
 // --show LIST: the lighting components shown (the reference's Show* switches, VCT.h:51); the ones not listed are off.
@@ -86,6 +92,8 @@ int main(int argc, char** argv) {
     bool dynamic_light = false;
     const char* idfile = nullptr;
     const char* show = nullptr;
+    bool show_voxels = false;
+    int view_source = VCT_VOXVIEW_CURRENT, view_level = 0;
     for (int i = 1; i + 1 < argc; ++i) {
         if (!strcmp(argv[i], "--gpus")) gpus = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--rank")) rank = atoi(argv[++i]);
@@ -95,6 +103,21 @@ int main(int argc, char** argv) {
     // (options with a value consume it; --dynamic-light has none and may stand anywhere)
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--dynamic-light")) { dynamic_light = true; continue; }
+        if (!strcmp(argv[i], "--voxels") && !(i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9')) {
+            show_voxels = true;                             // the voxel view: SOURCE[:LEVEL] may follow
+            if (i + 1 < argc && strncmp(argv[i + 1], "--", 2)) {
+                const std::string v(argv[++i]);
+                const size_t colon = v.find(':');
+                const std::string src = v.substr(0, colon);
+                const char* names[4] = {"current", "radiance", "albedo", "normal"};
+                int k = 0;
+                while (k < 4 && src != names[k]) ++k;
+                if (k == 4) { fprintf(stderr, "--voxels: unknown source '%s'\n", src.c_str()); return 1; }
+                view_source = k;
+                if (colon != std::string::npos) view_level = atoi(v.c_str() + colon + 1);
+            }
+            continue;
+        }
         if (i + 1 >= argc) break;
         if (!strcmp(argv[i], "--scene")) scene = argv[++i];
         else if (!strcmp(argv[i], "--voxels")) voxels = atoi(argv[++i]);
@@ -126,6 +149,9 @@ int main(int argc, char** argv) {
     voxel_cone_tracing.DynamicLight = dynamic_light;       // every Render() = one whole GI pass (vct_gi_pass)
     voxel_cone_tracing.FramesInFlight = in_flight;
     voxel_cone_tracing.DiffuseRate = diffuse_rate;
+    voxel_cone_tracing.ShowVoxels = show_voxels;
+    voxel_cone_tracing.VoxelViewSource = view_source;
+    voxel_cone_tracing.VoxelViewLevel = view_level;
     if (show) {                                             // --show: the listed Show* switches on, the others off
         bool* flags[5] = {&voxel_cone_tracing.ShowDiffuse, &voxel_cone_tracing.ShowIndirectDiffuse, &voxel_cone_tracing.ShowSpecular,
                           &voxel_cone_tracing.ShowIndirectSpecular, &voxel_cone_tracing.ShowAmbientOcclusion};
@@ -212,9 +238,14 @@ int main(int argc, char** argv) {
     uint64_t sum = 1469598103934665603ull;                  // FNV-1a over the RGBA16F halves
     for (size_t i = 0; i < n; ++i) { sum ^= fr[i]; sum *= 1099511628211ull; }
     uint64_t steps = 0;
-    vct_last_step_count(voxel_cone_tracing.ctx, &steps);
-    float ms = 0.0f;
-    if (gpus <= 0) vct_last_trace_ms(voxel_cone_tracing.ctx, &ms);      // (a rank's slab steps were not timed: 0)
+    float ms = 0.0f, view_ms = 0.0f;
+    if (show_voxels) {                                      // a view marches no cones
+        vct_last_voxel_view_ms(voxel_cone_tracing.ctx, &view_ms);
+        printf("voxel view: source=%d level=%d view_ms=%.3f\n", view_source, view_level, view_ms);
+    } else {
+        vct_last_step_count(voxel_cone_tracing.ctx, &steps);
+        if (gpus <= 0) vct_last_trace_ms(voxel_cone_tracing.ctx, &ms);      // (a rank's slab steps were not timed: 0)
+    }
     printf("frames=%d size=%dx%d voxels=%d cone_steps=%llu trace_ms=%.3f fnv1a=%016llx\n", frames, w, h,
            voxels, (unsigned long long)steps, ms, (unsigned long long)sum);
     if (ppm) {

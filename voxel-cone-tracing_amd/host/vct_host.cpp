@@ -1002,6 +1002,34 @@ void vcth_camera_view_proj(const vcth_camera* cam, int32_t width, int32_t height
     memcpy(out_vp, vp.m, 64);
 }
 
+int32_t vcth_invert_matrix(const float m[16], float out_inv[16]) {
+    double a[4][8];      // [row][m | identity]; m[col * 4 + row]
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) { a[r][c] = (double)m[c * 4 + r]; a[r][4 + c] = r == c ? 1.0 : 0.0; }
+    for (int k = 0; k < 4; ++k) {
+        int piv = k;
+        for (int r = k + 1; r < 4; ++r)
+            if (fabs(a[r][k]) > fabs(a[piv][k])) piv = r;
+        if (!(fabs(a[piv][k]) > 0.0) || !std::isfinite(a[piv][k])) return -1;
+        for (int c = 0; c < 8; ++c) std::swap(a[k][c], a[piv][c]);
+        const double d = a[k][k];
+        for (int c = 0; c < 8; ++c) a[k][c] /= d;
+        for (int r = 0; r < 4; ++r) {
+            if (r == k) continue;
+            const double f = a[r][k];
+            for (int c = 0; c < 8; ++c) a[r][c] -= f * a[k][c];
+        }
+    }
+    float inv[16];
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) {
+            inv[c * 4 + r] = (float)a[r][4 + c];
+            if (!std::isfinite(inv[c * 4 + r])) return -1;
+        }
+    memcpy(out_inv, inv, sizeof(inv));
+    return 0;
+}
+
 void vcth_light_view_proj(const float L[3], float out_vp[16]) {
     const M4 v = look_at({L[0], L[1], L[2]}, {0, 0, 0}, {0, 1, 0});     // VCT.h:84
     const M4 p = ortho(-120, 120, -120, 120, -100, 100);                // VCT.h:85

@@ -67,6 +67,9 @@ void vcth_scene_get(const vcth_scene* s, float* pos, int32_t* material, float* a
 void vcth_scene_get_frames(const vcth_scene* s, float* normal, float* tangent, float* bitangent);
 /* VCT.h:161-163: perspective(radians(Zoom), w/h, near, far) * camera.GetViewMatrix(), column-major. */
 void vcth_camera_view_proj(const vcth_camera* cam, int32_t width, int32_t height, float out_vp[16]);
+/* The inverse of a column-major 4x4 matrix, computed in double (Gauss-Jordan, partial pivoting) and rounded to fp32 once:
+ * what vct_render_voxels takes for the matrix above.  Returns 0, or -1 for a singular or non-finite matrix (out untouched). */
+int32_t vcth_invert_matrix(const float m[16], float out_inv[16]);
 
 /* VCT.h:84-86: DepthViewProjectionMatrix = ortho(-120,120,-120,120,-100,100) * lookAt(L,0,+Y),
  * column-major. */

@@ -30,6 +30,7 @@ _lib.vcth_scene_get.argtypes = [C.c_void_p] * 5
 _lib.vcth_light_view_proj.argtypes = [C.c_void_p, C.c_void_p]
 _lib.vcth_scene_get_frames.argtypes = [C.c_void_p] * 4
 _lib.vcth_camera_view_proj.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+_lib.vcth_invert_matrix.argtypes = [C.c_void_p, C.c_void_p]
 _lib.vcth_scene_save.argtypes = [C.c_void_p, C.c_char_p]
 _lib.vcth_scene_load_cache.restype = C.c_void_p
 _lib.vcth_scene_load_cache.argtypes = [C.c_char_p, C.c_char_p]
@@ -76,6 +77,16 @@ def camera_view_proj(cam, w, h):
     vp = np.zeros(16, np.float32)
     _lib.vcth_camera_view_proj(C.byref(cam), w, h, vp.ctypes.data)
     return vp
+
+
+def invert_matrix(m_colmajor):
+    """Inverse of a column-major 4x4 matrix (float32[16]), computed in double and rounded once: what
+    Context.render_voxels takes for a camera_view_proj matrix.  Raises ValueError for a singular matrix."""
+    m = np.ascontiguousarray(m_colmajor, np.float32).reshape(16)
+    inv = np.zeros(16, np.float32)
+    if _lib.vcth_invert_matrix(m.ctypes.data, inv.ctypes.data) != 0:
+        raise ValueError("singular or non-finite matrix")
+    return inv
 
 
 def light_view_proj(light_dir):

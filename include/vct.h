@@ -60,6 +60,36 @@ typedef enum vct_mem {
     VCT_MEM_DEVICE = 1
 } vct_mem;
 
+/* G-buffer contract (what vct_trace and its kin accept in `planes`; nothing validates it -- a pass over the planes would
+ * cost a frame's worth of reads).
+ *
+ * Position bound.  For every pixel that is not discarded and whose planes 0-5 are finite, on every axis c, evaluated in
+ * exact arithmetic with vs = grid_world_size / voxel_dim:
+ *     |Position_c| + |Normal_world_c| * vs + config.max_distance <= VCT_GBUFFER_LIMIT_GRIDS * config.grid_world_size.
+ * Where the bound comes from: a cone samples the positions p = Position + Normal_world * vs + dir * d with |dir| = 1 and
+ * d < max_distance (trace.fs:92,98), the left side bounds |p_c|, and the sampler turns p into the texel coordinate
+ * u = (p / G + 0.5) * N - 0.5 of a level of N <= voxel_dim <= 2^10 texels and takes (int)floorf(u) (csrc/vct_trace.hip
+ * sample_level, oracle/vct_oracle.cpp tri_sample).  That conversion is only defined for |u| < 2^31 (the GPU saturates,
+ * C++ on the host does not: with GL_REPEAT the two would read texel N - 1 and texel 0, with clamp opposite edges):
+ * |p_c| / G <= 2^20 gives |u| <= (2^20 + 0.5) * 2^10 + 0.5 < 2^31 with a factor 2 to spare for the fp32 roundings on
+ * the way -- the figure of the vertex contract (VCT_VERTEX_LIMIT_GRIDS), here with the cone's reach inside it.  Inside the
+ * bound frame, per-cone steps and raw cones are the CPU oracle's; outside it the result of that pixel is unspecified
+ * (no address leaves the chain: every texel index is masked or clamped).
+ *
+ * Otherwise every plane may hold any fp32 value, NaN and +-inf included:
+ *   - a tangent frame whose determinant dot(T, B x N) is 0, underflows, overflows or is not finite, a camera position
+ *     equal to Position (trace.fs:181 normalises cam - Position) and NaN or infinite inputs give NaN cone directions.
+ *     Such a cone takes one step (trace.fs:94 holds once, then its alpha is NaN) and returns NaN; the pixel's rgb is
+ *     NaN or inf, ITS rgb only: no other pixel of the frame, of the step counts or of the debug outputs changes.
+ *     max(x, 0) in trace.fs:188,213 is C's fmaxf: a NaN dot product gives 0 there.
+ *   - albedo.a = NaN counts as NOT discarded: trace.fs:171 discards on `albedo.a < 0.5`, which NaN fails.  The pixel is
+ *     traced and its output alpha is NaN.  -0.0 and the float below 0.5 are discarded, 0.5 is not.
+ *   - colours and the shadow term are plain factors: negative values, values above 1 and values whose product leaves
+ *     fp16 (|x| >= 65520 rounds to inf) are composited as the shader's arithmetic has them.
+ *   - lanes of a TILED buffer outside the frame (ragged width / height) may hold anything: they are never read into a
+ *     result and never steer the sampler. */
+#define VCT_GBUFFER_LIMIT_GRIDS 1048576.0f
+
 typedef struct vct_gbuffer {
     const float* planes;
     int32_t width, height;

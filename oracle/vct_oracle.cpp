@@ -60,7 +60,11 @@ void tri_sample(const vcto_params* p, const uint8_t* chain, int level, float ux,
     const float u = ux * fN - 0.5f, v = uy * fN - 0.5f, w = uz * fN - 0.5f;
     const float fu = floorf(u), fv = floorf(v), fw = floorf(w);
     const float a = u - fu, b = v - fv, c = w - fw;
-    int i0 = (int)fu, j0 = (int)fv, k0 = (int)fw;
+    // (int) of a float is defined for |f| < 2^31 only.  A NaN or infinite coordinate is inside the G-buffer contract
+    // (include/vct.h): its weights are NaN, so the sample is NaN whichever texels are read -- texel 0 here.  A finite
+    // coordinate beyond 2^31 is outside the contract; it reads texel 0 too instead of being undefined.
+    auto texel = [](float f) { return (f >= -2147483648.0f && f < 2147483648.0f) ? (int)f : 0; };
+    int i0 = texel(fu), j0 = texel(fv), k0 = texel(fw);
     int i1 = i0 + 1, j1 = j0 + 1, k1 = k0 + 1;
     if (p->wrap_repeat) {
         const int m = N - 1;

@@ -2,7 +2,8 @@
 and of the per-component outputs, from G-buffer planes and per-pixel raw cones (oracle.trace(..., want_cones=True)).
 
 fp32 throughout, in the kernel's operation order; the 6-cone gather is an fma chain (fs:194-199), emulated in fp64
-(the product of two fp32 values is exact there).  With SHOW_ALL it is the oracle's composite (tests pin that)."""
+(the product of two fp32 values is exact there).  With SHOW_ALL it is the oracle's composite (tests pin that).
+max(x, 0) is C's fmaxf as in the oracle and the kernel: a NaN dot product (P == camera, a NaN normal) gives 0."""
 import numpy as np
 
 SHOW_DIFFUSE, SHOW_INDIRECT_DIFFUSE, SHOW_SPECULAR, SHOW_INDIRECT_SPECULAR, SHOW_AMBIENT_OCCLUSION = 1, 2, 4, 8, 16
@@ -61,14 +62,14 @@ def composite(planes, cones, cam, light, ambient=0.1, shininess=20.0, mask=SHOW_
         sc = cones[:, 6, :]
         L = _normalize([f32(light[0]), f32(light[1]), f32(light[2])])                       # :179
         E = _normalize([f32(cam[0]) - P[0], f32(cam[1]) - P[1], f32(cam[2]) - P[2]])        # :181
-        cos_theta = np.maximum(_dot(N, L), f32(0.0))                                         # :188
+        cos_theta = np.fmax(_dot(N, L), f32(0.0))                                            # :188
         raw_dd = shadow * cos_theta
         dd = raw_dd if mask & SHOW_DIFFUSE else np.zeros_like(raw_dd)                        # :190
         occ = f32(1.0) - ind[:, 3] if mask & SHOW_AMBIENT_OCCLUSION else np.ones_like(raw_dd)   # :201
         ird = ind[:, :3] if mask & SHOW_INDIRECT_DIFFUSE else np.zeros_like(ind[:, :3])      # :203
         D = [(dd + occ * ird[:, c]) * alb[c] for c in range(3)]                              # :205
         R = _normalize(_reflect([-L[0], -L[1], -L[2]], N))                                   # :212
-        spec = np.power(np.maximum(_dot(E, R), f32(0.0)), f32(shininess)).astype(np.float32)   # :213
+        spec = np.power(np.fmax(_dot(E, R), f32(0.0)), f32(shininess)).astype(np.float32)   # :213
         raw_ds = spec * shadow
         ds = raw_ds if mask & SHOW_SPECULAR else np.zeros_like(raw_ds)                       # :215
         socc = f32(1.0) - sc[:, 3] if mask & SHOW_AMBIENT_OCCLUSION else np.ones_like(raw_dd)   # :221
@@ -106,7 +107,8 @@ def marched_steps(steps, mask, aov=0):
 
 def to_f16_bits(x):
     """Round-to-nearest-even fp32 -> fp16 bits (numpy's cast: the rounding of the kernel's pack and the oracle)."""
-    return np.asarray(x, np.float32).astype(np.float16).view(np.uint16)
+    with np.errstate(over="ignore"):          # a value that rounds to 65520 or more becomes inf, as in the kernel's pack
+        return np.asarray(x, np.float32).astype(np.float16).view(np.uint16)
 
 
 def header_constants(path):

@@ -582,13 +582,23 @@ __device__ __forceinline__ F4 cone_march(const VctTraceParams& p, bool alive, F3
                                          float4* __restrict__ blk, const LaneBlock& lb,
                                          int& steps_out, MarchStats& ms) {
     const StepTable tab = (StepTable)tab_global;
-    float cr = 0.0f, cg = 0.0f, cb = 0.0f, alpha = 0.0f, occ = 0.0f;
+    float cr = 0.0f, cg = 0.0f, cb = 0.0f, occ = 0.0f;
     int steps = 0;
     AnisoCone ac = {0.0f, 0.0f, 0.0f, false, false, false};
     if (ANISO) {
         ac.wx = dir.x * dir.x; ac.wy = dir.y * dir.y; ac.wz = dir.z * dir.z;
         ac.nx = !(dir.x >= 0.0f); ac.ny = !(dir.y >= 0.0f); ac.nz = !(dir.z >= 0.0f);
     }
+    // A lane whose sample position is not finite (start or direction NaN / inf: a degenerate tangent frame, the camera on
+    // the surface point -- include/vct.h "G-buffer contract") has NaN filter weights at every step, so the oracle's first
+    // sample is NaN whatever the texels hold and its march ends there: one step, (NaN, NaN, NaN, NaN).  The cooperative
+    // sampler skips the weights when its block is all zero and would hand such a lane +0 and let it march on, so these
+    // lanes start with alpha = NaN: trace.fs:94's alpha < max_alpha never holds for them, they take no part in the march
+    // and get the oracle's result below.  (x * 0 is NaN for NaN and inf, else +-0, and the chain ends in + 0.0f, so a
+    // finite position gives exactly +0 whatever its size: nothing here can overflow.  A position that is finite at the
+    // first step stays finite inside the contract: |dir| <= 1, dist < max_distance.)
+    const float wx = start.x + dir.x * p.vs, wy = start.y + dir.y * p.vs, wz = start.z + dir.z * p.vs;      // step 0: dist = vs
+    float alpha = fmaf(wx, 0.0f, fmaf(wy, 0.0f, fmaf(wz, 0.0f, 0.0f)));
     const unsigned long long alive_mask = ballot64(alive);
     if constexpr (!ANISO) {
     // Two steps per loop iteration (A/B: 0.6281 -> 0.6216 ms at 256^3, 2.659 -> 2.623 ms at 512^3 / 4K; not the anisotropic
@@ -630,6 +640,12 @@ __device__ __forceinline__ F4 cone_march(const VctTraceParams& p, bool alive, F3
         nxt = load_step(tab, k + 1 < n ? k + 1 : k);
         VCT_MARCH_STEP(st, act, live)
     }
+    }
+    // a lane that never marched because it started with alpha = NaN: in the oracle trace.fs:94 holds once (its alpha starts
+    // at 0), the sample is NaN, and then alpha is NaN
+    if (alive && steps == 0 && alpha != alpha && n > 0 && 0.0f < p.max_alpha) {
+        cr = cg = cb = occ = __builtin_nanf("");
+        steps = 1;
     }
     steps_out = steps;
     return {cr, cg, cb, occ};

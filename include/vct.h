@@ -460,6 +460,57 @@ int vct_render_voxels(vct_ctx* ctx, const float inv_view_proj[16], int32_t sourc
  * due, runs in front of the bracket).  Needs trace timing on (vct_set_trace_timing) when the view was issued; waits. */
 int vct_last_voxel_view_ms(vct_ctx* ctx, float* ms);
 
+/* ---- point queries: gathers and single cones at caller-given points ------------------------------------------
+ * No reference counterpart (the reference lights only what its one camera sees).  What light arrives at a point that is
+ * no pixel of the G-buffer -- a light probe, a lightmap texel, a particle, another camera's reflection point, a caller's
+ * own AO cone -- is the march of S/VoxelConeTracing.fs with the point's values in place of the fragment's:
+ *   Gather  (vct_gather_points) point i is a fragment with Position_world = position, Normal_world = normal (as planes
+ *           3-5 hold it: model-scaled, not normalised), Tangent_world = tangent, BiTangent_world = bitangent.
+ *           out_gather[i] = the vec4 inDirectDiffuse of fs:194-199 before fs:201: the frame of fs:175
+ *           (inverse(transpose(mat3(T, B, N))), as the screen trace forms it), six Voxel_Cone_Tracing calls at
+ *           config.tan_diffuse along normalize(frame * ConeVectors[k]), folded as ind = fma(Weights[k], cone_k, ind)
+ *           over k = 0 .. 5 from 0.  out_cones[i][k] / out_steps[i][k] (either may be NULL): the six raw vec4s and their
+ *           executed step counts, as vct_download_cones / vct_download_steps hold columns 0-5 of a pixel.
+ *   Cone    (vct_cone_points) out_cone[i] = Voxel_Cone_Tracing(direction, tan) of fs:82-107 with
+ *           startPos = position + normal * voxelWorldSize (fs:92) and tan = config.tan_diffuse (aperture 0) or
+ *           config.tan_specular (aperture 1), the two apertures of vct_set_cone_apertures and their step tables.
+ *           direction is used as given: normalising is the caller's job (fs:196,217 normalise before the call).
+ * Bit for bit what the CPU oracle computes for the same values, and what the screen trace computes for a pixel that holds
+ * them.  A query reads the chain the trace reads at that moment (GL_REPEAT or clamp; the bounce chain after vct_bounce)
+ * and always takes the exact march: config.trace_variant does not apply, footprint records are not used (same bits).
+ * Point contract: the G-buffer contract restated.  Per axis c, in exact arithmetic, vs = grid_world_size / voxel_dim,
+ *     |position_c| + |normal_c| * vs + config.max_distance * max(1, |direction|) <= VCT_GBUFFER_LIMIT_GRIDS * grid_world_size
+ * (|direction| = 1 for a gather).  Otherwise every field may hold any fp32 value: a point whose start or direction is
+ * not finite (NaN or inf fields, a tangent frame with determinant 0) gets the oracle's result -- one step, NaN -- and
+ * changes no other point; no address is formed from a coordinate that was not masked or clamped.
+ * pts and every out pointer live where `location` (vct_mem) says and need 4-byte alignment only.  VCT_MEM_DEVICE: the
+ * work is queued on the selected frame slot's stream and the call returns at once (vct_synchronize); the memory must stay
+ * valid until then.  VCT_MEM_HOST: the call returns when the outputs are written.  A query reads shared state only, so
+ * with two frame slots it is ordered against the stages that write the chain exactly as a resident trace is.
+ * flags: VCT_QUERY_SORT_CELLS -- results are a pure function of each point, so the library may march the points in any
+ * order: with the flag it marches them ordered by the 4-voxel cell of their start point (non-finite points last) and
+ * writes every result at the caller's index.  Same outputs, bit for bit; it pays when neighbouring points are far apart
+ * in the list (a shuffled lightmap, particles), because 64 consecutive points share their texel fetches only when
+ * they are neighbours in space.  Points already in spatial order (probe grids, lightmap rows) need no flag.
+ * n = 0 succeeds and does nothing.  VCT_ERR_INVALID, nothing touched: n < 0 or n > VCT_POINT_QUERY_MAX; NULL pts or
+ * out_gather / out_cone with n > 0; a location or aperture that is not one of the above; unknown flag bits; step counts
+ * wanted with an aperture of more than 255 steps; config.anisotropic_mips (out of scope: queries read the isotropic chain
+ * only); a chain whose level 0 changed since the last vct_build_mips (the rule of the trace). */
+typedef struct vct_gather_point { float position[3], normal[3], tangent[3], bitangent[3]; } vct_gather_point; /* 48 B */
+typedef struct vct_cone_point { float position[3], normal[3], direction[3]; } vct_cone_point;                 /* 36 B */
+#define VCT_QUERY_SORT_CELLS 1u
+#define VCT_POINT_QUERY_MAX (1 << 26)
+int vct_gather_points(vct_ctx* ctx, const vct_gather_point* pts, int32_t n, int32_t location, float* out_gather,
+                      float* out_cones, uint8_t* out_steps, uint32_t flags);
+int vct_cone_points(vct_ctx* ctx, const vct_cone_point* pts, int32_t n, int32_t location, int32_t aperture,
+                    float* out_cone, uint8_t* out_steps, uint32_t flags);
+/* The selected slot's last query: out[0] points, out[1] executed steps, out[2] kind (0 gather, 1 cone), out[3] 1 if the
+ * points were marched in sorted order.  Waits for the slot's stream. */
+int vct_last_point_query(vct_ctx* ctx, uint64_t out[4]);
+/* Device time of that query's march kernel alone (not the sort, not the copies) in milliseconds, from the library's
+ * events; needs trace timing on (vct_set_trace_timing) when the query was issued and n > 0.  Waits for it. */
+int vct_last_point_query_ms(vct_ctx* ctx, float* ms);
+
 /* ---- two frames in flight (round 6) -----------------------------------------------------------------
  * The reference's Render() (VCT.h:146-190) issues GL commands; the driver starts frame k + 1 while frame k
  * drains -- nothing in R/main.cpp:77-94 waits for a frame.  A HIP stream does wait: each whole-frame trace
@@ -580,7 +631,7 @@ int vct_last_step_count(vct_ctx* ctx, uint64_t* steps);
 int vct_last_trace_stats(vct_ctx* ctx, uint64_t out[16]);
 /* Work-item counts behind the per-stage byte figures of bench.py (`stage_roofline`): [0] triangles uploaded,
  * [1] conservative fragments of the mesh at this grid size (the voxelizer's brick-sorted list), [2] division form of
- * the last march launch (screen trace, slab, frame step or bounce): 0 none yet, 1 the IEEE divide, 2 the verified
+ * the last march launch (screen trace, slab, frame step, bounce or point query): 0 none yet, 1 the IEEE divide, 2 the verified
  * two-term product (every divisor of the step tables is in the shipped table or passed the device check, 1 - max_alpha
  * >= 2^-5, every two-level blend fraction in [2^-10, 1 - 2^-10]), 3 trace_variant 3's x * r, [3] brick slots =
  * 8^3 bricks a fragment of the mesh can land in, [4] bricks level 0 shows after the last resolve, [5] compute

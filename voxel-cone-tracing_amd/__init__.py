@@ -32,6 +32,10 @@ SHOW_ALL = 31
 AOV_INDIRECT_DIFFUSE, AOV_INDIRECT_SPECULAR, AOV_DIRECT = 1, 2, 4
 # sources of the voxel view (Context.render_voxels)
 VOXVIEW_CURRENT, VOXVIEW_RADIANCE, VOXVIEW_ALBEDO, VOXVIEW_NORMAL = 0, 1, 2, 3
+# point queries (Context.gather_points / cone_points)
+QUERY_SORT_CELLS = 1
+POINT_QUERY_MAX = 1 << 26
+APERTURE_DIFFUSE, APERTURE_SPECULAR = 0, 1
 
 # every symbol include/vct.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
@@ -56,6 +60,7 @@ ABI_SYMBOLS = [
     "vct_set_trace_timing", "vct_set_lighting_components", "vct_get_lighting_components", "vct_set_aov_outputs",
     "vct_download_aov", "vct_get_aov_device", "vct_set_diffuse_rate", "vct_get_diffuse_rate", "vct_last_diffuse_rate_ms",
     "vct_render_voxels", "vct_last_voxel_view_ms",
+    "vct_gather_points", "vct_cone_points", "vct_last_point_query", "vct_last_point_query_ms",
 ]
 
 
@@ -159,6 +164,10 @@ _lib.vct_get_diffuse_rate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.vct_last_diffuse_rate_ms.argtypes = [C.c_void_p, C.c_void_p]
 _lib.vct_render_voxels.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
 _lib.vct_last_voxel_view_ms.argtypes = [C.c_void_p, C.c_void_p]
+_lib.vct_gather_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+_lib.vct_cone_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32]
+_lib.vct_last_point_query.argtypes = [C.c_void_p, C.c_void_p]
+_lib.vct_last_point_query_ms.argtypes = [C.c_void_p, C.c_void_p]
 _lib.vct_upload_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
 
 
@@ -549,6 +558,64 @@ class Context:
         """Device ms of the walk kernel of the selected slot's last voxel view (trace timing must have been on)."""
         v = C.c_float()
         self._ck(_lib.vct_last_voxel_view_ms(self._h, C.byref(v)), "vct_last_voxel_view_ms")
+        return v.value
+
+    # --- point queries (include/vct.h): gathers and single cones at caller-given points
+    def gather_points(self, points, want_cones=False, want_steps=False, sort=False, n=None, out_device_ptr=None,
+                      cones_device_ptr=None, steps_device_ptr=None):
+        """The six-cone diffuse gather at caller-given points.  points: float32 [n, 12] numpy = position, normal (model-scaled,
+        as G-buffer planes 3-5), tangent, bitangent per point; returns the gather float32 [n, 4], or a tuple (gather[, cones
+        [n, 6, 4]][, steps uint8 [n, 6]]) with want_cones / want_steps.  sort: QUERY_SORT_CELLS (same results; for lists
+        that are not in spatial order).  Device form, for torch tensors: points = an int device pointer, n = the point
+        count, out_device_ptr (and optionally cones_device_ptr / steps_device_ptr) = device pointers of the outputs; the
+        work is queued on the slot's stream and None is returned (synchronize())."""
+        flags = QUERY_SORT_CELLS if sort else 0
+        if isinstance(points, int):
+            if n is None or out_device_ptr is None:
+                raise VctError("gather_points: a device pointer needs n and out_device_ptr")
+            self._ck(_lib.vct_gather_points(self._h, _ptr(points), int(n), MEM_DEVICE, _ptr(out_device_ptr), _ptr(cones_device_ptr),
+                                            _ptr(steps_device_ptr), flags), "vct_gather_points")
+            return None
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 12)
+        n = pts.shape[0]
+        out = np.zeros((n, 4), np.float32)
+        cones = np.zeros((n, 6, 4), np.float32) if want_cones else None
+        steps = np.zeros((n, 6), np.uint8) if want_steps else None
+        self._ck(_lib.vct_gather_points(self._h, _ptr(pts), n, MEM_HOST, _ptr(out), _ptr(cones), _ptr(steps), flags),
+                 "vct_gather_points")
+        res = (out,) + ((cones,) if want_cones else ()) + ((steps,) if want_steps else ())
+        return res[0] if len(res) == 1 else res
+
+    def cone_points(self, points, aperture=APERTURE_DIFFUSE, want_steps=False, sort=False, n=None, out_device_ptr=None,
+                    steps_device_ptr=None):
+        """One cone per point.  points: float32 [n, 9] = position, normal, direction (used as given: normalise it yourself);
+        aperture: APERTURE_DIFFUSE / APERTURE_SPECULAR (set_cone_apertures).  Returns float32 [n, 4] (and steps uint8 [n]
+        with want_steps).  Device form as gather_points."""
+        flags = QUERY_SORT_CELLS if sort else 0
+        if isinstance(points, int):
+            if n is None or out_device_ptr is None:
+                raise VctError("cone_points: a device pointer needs n and out_device_ptr")
+            self._ck(_lib.vct_cone_points(self._h, _ptr(points), int(n), MEM_DEVICE, int(aperture), _ptr(out_device_ptr),
+                                          _ptr(steps_device_ptr), flags), "vct_cone_points")
+            return None
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 9)
+        n = pts.shape[0]
+        out = np.zeros((n, 4), np.float32)
+        steps = np.zeros(n, np.uint8) if want_steps else None
+        self._ck(_lib.vct_cone_points(self._h, _ptr(pts), n, MEM_HOST, int(aperture), _ptr(out), _ptr(steps), flags),
+                 "vct_cone_points")
+        return (out, steps) if want_steps else out
+
+    def last_point_query(self):
+        """(points, executed steps, kind: 0 gather / 1 cone, 1 if marched in sorted order) of the slot's last query.  Waits."""
+        v = (C.c_uint64 * 4)()
+        self._ck(_lib.vct_last_point_query(self._h, v), "vct_last_point_query")
+        return tuple(int(x) for x in v)
+
+    def last_point_query_ms(self):
+        """Device ms of the march kernel of the slot's last point query (trace timing must have been on)."""
+        v = C.c_float()
+        self._ck(_lib.vct_last_point_query_ms(self._h, C.byref(v)), "vct_last_point_query_ms")
         return v.value
 
     def set_frame_target(self, dev_ptr):

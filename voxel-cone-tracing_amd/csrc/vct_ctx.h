@@ -117,6 +117,23 @@ struct VctRasterScratch {
     void release_mesh() { lists.reset(); recs.reset(); bin_recs.reset(); bin_entries.reset(); bin_items.reset(); }
 };
 
+// What a frame slot keeps for point queries (include/vct.h "point queries", vct_api_query.hip): staging for host-located
+// points and outputs, the sort's scratch, the step counters and the timing events of the march.  Everything is created
+// by the first query that needs it, grows on demand and is never shrunk; a query that fails leaves what it had grown (the
+// owner frees it with the slot).  Work of a query on these buffers is ordered by the slot's stream.
+struct VctPointQuery {
+    VctBuf<float> pts;                  // staged points of a host-located query
+    VctBuf<float> out, out_cones;       // staged results [n][4], [n][6][4]
+    VctBuf<uint8_t> out_steps;          // [n][6] / [n]
+    VctBuf<uint32_t> keys, index;       // VCT_QUERY_SORT_CELLS: two (key, index) buffer pairs of the radix sort, [2][n] each
+    VctBuf<char> sort_tmp;              // the device sort's temporary storage
+    VctBuf<unsigned long long> ctr;     // [VCT_DR_COUNTERS] executed steps of the last query (zeroed by its launch)
+    VctEvent ev0, ev1;                  // around the march kernel (vct_last_point_query_ms)
+    bool have = false, timed = false, sorted = false;
+    uint64_t n = 0;
+    int kind = 0;
+};
+
 // Two frames in flight (vct_set_frames_in_flight, round 6).  A whole-frame trace launch pays ~20 us of ramp and drain
 // (the last generation of workgroups leaves compute units idle, tools/quant_probe.py) plus the dispatch gap to the next
 // kernel of its stream: 4-5 % of a 0.61 ms frame.  A renderer that starts frame k + 1 on a second stream while frame k
@@ -159,6 +176,7 @@ struct VctFrameSlot {
     VctEvent vv_ev0, vv_ev1;            // timing events of the view's walk (vct_last_voxel_view_ms)
     bool have_view = false, last_view_timed = false;
     VctRasterScratch raster;            // the main draw's
+    VctPointQuery query;                // point queries issued on this slot
 
     // where a trace writes and a download reads: the caller's target or the slot's own frame
     uint16_t* frame_out() const { return frame_target ? frame_target : frame.get(); }

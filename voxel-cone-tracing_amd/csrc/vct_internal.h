@@ -326,6 +326,26 @@ struct VctTraceParams {
 #define VCT_DR_COUNTERS 256             // (power of two) a bank, for the reason VCT_STEP_COUNTERS is one
 #define VCT_DR_CTR_WORDS (2 * VCT_DR_COUNTERS + 1)
 
+// Point queries (include/vct.h "point queries"; vct_trace.hip k_query_march): what a query launch needs beside the march's
+// part of VctTraceParams (vct_fill_march_params), as a second kernel argument -- VctTraceParams keeps its layout.
+#define VCT_QUERY_GATHER 0
+#define VCT_QUERY_CONE 1
+#define VCT_QUERY_KEY_BITS 28           // sort key: bits 0-2 octant, 3-26 Morton code of the start point's cell, bit 27 non-finite
+struct VctQueryArgs {
+    const float* pts;                   // [n] vct_gather_point (12 floats) or vct_cone_point (9 floats), 4-byte aligned
+    const uint32_t* index;              // [n] the order the points are marched in (VCT_QUERY_SORT_CELLS) or null: as given
+    float* out;                         // [n][4] gather / cone, at the caller's index
+    float* out_cones;                   // [n][6][4] or null (gather)
+    uint8_t* out_steps;                 // [n][6] (gather) / [n] (cone) or null
+    unsigned long long* ctr;            // [VCT_DR_COUNTERS] partial sums of executed steps (zero at launch)
+    uint32_t n;
+    int32_t specular;                   // (cone) 1: the specular step table, 0: the diffuse one
+};
+// marches q.n points; kind: VCT_QUERY_GATHER / _CONE.  p: vct_fill_march_params' fields only
+hipError_t vct_launch_query(const VctTraceParams& p, const VctQueryArgs& q, int kind, hipStream_t s);
+// keys[i] = sort key of point i (VCT_QUERY_KEY_BITS bits), index[i] = i
+hipError_t vct_launch_query_keys(const VctTraceParams& p, const VctQueryArgs& q, int kind, uint32_t* keys, uint32_t* index, hipStream_t s);
+
 #ifndef VCT_VOX_CHUNK
 #define VCT_VOX_CHUNK 4096u       // most fragments one work item (workgroup) of the voxelize pass takes (vct_capi.hip build_voxel_slots)
 #endif

@@ -12,7 +12,7 @@
 // Kernels in this file: k_trace_tile_split (default: an 8x8 screen tile = 3 waves -- cones 0-2, cones
 // 3-5, specular -- with an LDS hand-off and a last-arriver composite), k_trace_tile (one wave per
 // tile; A/B variants), k_bounce_list/_march/_bricks (second bounce, same march), k_point_march + k_diffuse_resolve (half-rate
-// diffuse gather, same march), k_divide_selftest.
+// diffuse gather, same march), k_query_march + k_query_keys (point queries, same march), k_divide_selftest.
 //
 // Mapping: lane = pixel of the tile, a wave marches its cones one after the other.  The kernel
 // was VALU-issue bound from round 1 (profiles/r01a: 995 M VALU wave-instructions per 1080p frame, half of the
@@ -688,9 +688,9 @@ __device__ __forceinline__ F3 gb_planes3(const float* gb, int k) { return f3(gb_
 __device__ __forceinline__ F3 cone_start(F3 P, F3 N, float vs) {                   // trace.fs:92
     return f3(P.x + N.x * vs, P.y + N.y * vs, P.z + N.z * vs);
 }
-// planes 0-11: the cones' start point and the frame k0, k1, k2 their directions are combined in
-__device__ __forceinline__ void cone_frame_from_gbuffer(const float* gb, float vs, F3& start, F3& k0, F3& k1, F3& k2) {
-    const F3 P = gb_planes3(gb, 0), Nw = gb_planes3(gb, 3), T = gb_planes3(gb, 6), B = gb_planes3(gb, 9);
+// the cones' start point and the frame k0, k1, k2 their directions are combined in, from a fragment's Position_world,
+// Normal_world, Tangent_world and BiTangent_world (G-buffer planes 0-11, or a caller's gather point)
+__device__ __forceinline__ void cone_frame(F3 P, F3 Nw, F3 T, F3 B, float vs, F3& start, F3& k0, F3& k1, F3& k2) {
     // trace.fs:175: inverse(transpose(mat3(T,B,N))) = columns (BxN, NxT, TxB) / det
     const F3 c0 = cross3(B, Nw), c1 = cross3(Nw, T), c2 = cross3(T, B);
     const float inv_det = div_rn(1.0f, dot3(T, c0));
@@ -698,6 +698,10 @@ __device__ __forceinline__ void cone_frame_from_gbuffer(const float* gb, float v
     k1 = f3(c1.x * inv_det, c1.y * inv_det, c1.z * inv_det);
     k2 = f3(c2.x * inv_det, c2.y * inv_det, c2.z * inv_det);
     start = cone_start(P, Nw, vs);
+}
+__device__ __forceinline__ void cone_frame_from_gbuffer(const float* gb, float vs, F3& start, F3& k0, F3& k1, F3& k2) {
+    const F3 P = gb_planes3(gb, 0), Nw = gb_planes3(gb, 3), T = gb_planes3(gb, 6), B = gb_planes3(gb, 9);
+    cone_frame(P, Nw, T, B, vs, start, k0, k1, k2);
 }
 // direction of diffuse cone i in the frame (b0, b1, b2)                             trace.fs:196-199
 __device__ __forceinline__ F3 cone_dir(F3 b0, F3 b1, F3 b2, int i) {
@@ -1166,6 +1170,107 @@ k_point_march(const VctTraceParams p) {
     flush_stats(p, ms, lane);
 }
 
+// ---- Point queries (include/vct.h "point queries": vct_gather_points, vct_cone_points) ---------------------------------------
+// The march of the screen trace for points the caller names: light probes, lightmap texels, particles.  One wave per 64
+// consecutive entries of the (possibly permuted: q.index) list, lane = point, a fixed grid striding over the items as
+// k_point_march<LISTED> does.  KIND = VCT_QUERY_GATHER: cone_frame on the point's own T, B, N, P, six diffuse cones, the
+// fold of fold_cone in cone order -- the arithmetic of a pixel of k_trace_tile*, so the same bits.  VCT_QUERY_CONE: one
+// cone along the caller's direction from cone_start(P, N), with the diffuse or the specular step table.  DEBUG: the raw
+// cones and / or per-cone step counts are wanted too.
+// The cooperative block serves waves whose points are neighbours in space (a lightmap in row order, a sorted list), the
+// per-lane gather the others: sample_level's own decision, per sample.  A record is 48 (36) bytes at 4-byte alignment and
+// arrives as dwordx4 loads (VctTri9's reason); results leave as one dwordx4 store per vec4.  Address safety: a point is
+// addressed by an entry index < n (or the library's own permutation of those); coordinates reach memory only through
+// sample_level's masked / clamped texel indices.  Tail lanes (n not a multiple of 64) re-read the last point, march as
+// `alive = false` and store nothing.
+struct __attribute__((packed, aligned(4))) VctFloats12 { float v[12]; };
+struct __attribute__((packed, aligned(4))) VctFloats4 { float v[4]; };
+__device__ __forceinline__ void store_vec4(float* dst, F4 c) {
+    VctFloats4 o;
+    o.v[0] = c.x; o.v[1] = c.y; o.v[2] = c.z; o.v[3] = c.w;
+    *(VctFloats4*)dst = o;
+}
+template <bool WRAP, int FASTDIV, int KIND, bool DEBUG>
+__global__ void __launch_bounds__(64, VCT_POINT_MIN_WAVES)
+k_query_march(const VctTraceParams p, const VctQueryArgs q) {
+    __shared__ float4 lds_blk[2][64];
+    const int lane = (int)threadIdx.x;
+    float4* blk = &lds_blk[0][0];
+    const LaneBlock lb = make_lane_block(p, lane);
+    MarchStats ms = {};
+    const uint32_t nitems = (q.n + 63u) >> 6;          // (the host launches nothing for n = 0)
+    unsigned long long wave_steps = 0;
+    for (uint32_t it = blockIdx.x; it < nitems; it += gridDim.x) {
+        const uint32_t e = it * 64u + (uint32_t)lane;
+        const bool alive = e < q.n;
+        const uint32_t entry = alive ? e : q.n - 1u;
+        const size_t i = q.index ? q.index[entry] : entry;          // the caller's index of this lane's point
+        int total = 0;
+        if constexpr (KIND == VCT_QUERY_GATHER) {
+            const VctFloats12 r = *(const VctFloats12*)(q.pts + i * 12);
+            F3 start, k0, k1, k2;
+            cone_frame(f3(r.v[0], r.v[1], r.v[2]), f3(r.v[3], r.v[4], r.v[5]), f3(r.v[6], r.v[7], r.v[8]),
+                       f3(r.v[9], r.v[10], r.v[11]), p.vs, start, k0, k1, k2);
+            F4 ind = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll 1
+            for (int c = 0; c < 6; ++c) {
+                int st;
+                const F4 v = cone_march<WRAP, FASTDIV, true>(p, alive, start, cone_dir(k0, k1, k2, c), p.steps_diffuse, p.n_diffuse,
+                                                             blk, lb, st, ms);
+                total += st;
+                ind = fold_cone(ind, c, v);
+                if (DEBUG && alive) {
+                    if (q.out_cones) store_vec4(q.out_cones + (i * 6 + (size_t)c) * 4, v);
+                    if (q.out_steps) q.out_steps[i * 6 + (size_t)c] = (uint8_t)st;
+                }
+            }
+            if (alive) store_vec4(q.out + i * 4, ind);
+        } else {
+            const VctTri9 r = *(const VctTri9*)(q.pts + i * 9);
+            const F3 start = cone_start(f3(r.v[0], r.v[1], r.v[2]), f3(r.v[3], r.v[4], r.v[5]), p.vs);
+            const VctStep* tab = q.specular ? p.steps_specular : p.steps_diffuse;          // (wave-uniform)
+            const int nsteps = q.specular ? p.n_specular : p.n_diffuse;
+            const F4 v = cone_march<WRAP, FASTDIV, true>(p, alive, start, f3(r.v[6], r.v[7], r.v[8]), tab, nsteps, blk, lb, total, ms);
+            if (alive) {
+                store_vec4(q.out + i * 4, v);
+                if (DEBUG) q.out_steps[i] = (uint8_t)total;
+            }
+        }
+        for (int off = 32; off > 0; off >>= 1) total += __shfl_xor(total, off);
+        wave_steps += (unsigned long long)total;
+    }
+    if (lane == 0 && wave_steps) atomicAdd(q.ctr + (blockIdx.x & (VCT_DR_COUNTERS - 1)), wave_steps);
+    flush_stats(p, ms, lane);
+}
+
+// Sort key of VCT_QUERY_SORT_CELLS: the Morton code of the 4-voxel cell of the point's start position, folded into the grid
+// as the sampler folds a coordinate (REPEAT: modulo, else clamped), over the octant of the direction the march leaves in
+// (gather: the normal; cone: the direction).  Non-finite points sort last.  The key orders the march and nothing else:
+// results do not depend on it.
+template <bool WRAP, int KIND>
+__global__ void __launch_bounds__(256)
+k_query_keys(const VctTraceParams p, const VctQueryArgs q, uint32_t* keys, uint32_t* index) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= q.n) return;
+    const float* r = q.pts + (size_t)i * (KIND == VCT_QUERY_GATHER ? 12 : 9);
+    const F3 start = cone_start(f3(r[0], r[1], r[2]), f3(r[3], r[4], r[5]), p.vs);
+    const F3 d = KIND == VCT_QUERY_GATHER ? f3(r[3], r[4], r[5]) : f3(r[6], r[7], r[8]);
+    const int cells = p.V >> 2;          // per axis (V >= 8: at least 2)
+    auto cell = [&](float x) {
+        const float u = fmaf(x / p.half_G, 0.5f, 0.5f) * (float)cells;
+        const int c = (int)fminf(fmaxf(floorf(u), -0x1p30f), 0x1p30f);
+        return (uint32_t)(WRAP ? c & (cells - 1) : min(max(c, 0), cells - 1));
+    };
+    uint32_t key = 1u << (VCT_QUERY_KEY_BITS - 1);
+    const float probe = (start.x + start.y + start.z) * 0.0f + (d.x + d.y + d.z) * 0.0f;      // NaN iff something is not finite
+    if (probe == probe) {
+        const uint32_t oct = (d.x < 0.0f ? 1u : 0u) | (d.y < 0.0f ? 2u : 0u) | (d.z < 0.0f ? 4u : 0u);
+        key = (vct_morton3(cell(start.x), cell(start.y), cell(start.z)) << 3) | oct;
+    }
+    keys[i] = key;
+    index[i] = i;
+}
+
 // One wave per 8x8 tile, lane = pixel.  An anchor copies its quad's sample; any other live pixel tests the four
 // candidates of include/vct.h in their order and interpolates, or -- no candidate accepted -- joins the fill list.
 __global__ void __launch_bounds__(256)
@@ -1621,6 +1726,43 @@ hipError_t vct_launch_texel_buffer_selftest(const uint32_t* texels, uint32_t n, 
 hipError_t vct_launch_divide_selftest(float d, unsigned long long* mismatches, hipStream_t s) {
     const float r = 1.0f / d;
     hipLaunchKernelGGL(k_divide_selftest, dim3(256 * 16), dim3(256), 0, s, d, r, vct_div_aux(d, r), mismatches);
+    return hipGetLastError();
+}
+
+// Point queries: always the exact march (FASTDIV 0 or 1 as the step tables were built), isotropic chain, no footprint records.
+template <bool WRAP, int FASTDIV>
+hipError_t launch_query(const VctTraceParams& p, const VctQueryArgs& q, int kind, hipStream_t s) {
+    const uint32_t nitems = (q.n + 63u) >> 6;
+    const dim3 grid(nitems < 256u * 24u ? nitems : 256u * 24u), block(64);          // at most the bounce's grid
+    const bool debug = q.out_cones || q.out_steps;
+    if (kind == VCT_QUERY_GATHER) {
+        if (debug) hipLaunchKernelGGL((k_query_march<WRAP, FASTDIV, VCT_QUERY_GATHER, true>), grid, block, 0, s, p, q);
+        else hipLaunchKernelGGL((k_query_march<WRAP, FASTDIV, VCT_QUERY_GATHER, false>), grid, block, 0, s, p, q);
+    } else {
+        if (debug) hipLaunchKernelGGL((k_query_march<WRAP, FASTDIV, VCT_QUERY_CONE, true>), grid, block, 0, s, p, q);
+        else hipLaunchKernelGGL((k_query_march<WRAP, FASTDIV, VCT_QUERY_CONE, false>), grid, block, 0, s, p, q);
+    }
+    return hipGetLastError();
+}
+
+hipError_t vct_launch_query(const VctTraceParams& p, const VctQueryArgs& q, int kind, hipStream_t s) {
+    if (q.n == 0u) return hipSuccess;
+    if (p.aniso || p.cells_biased || (kind != VCT_QUERY_GATHER && kind != VCT_QUERY_CONE)) return hipErrorInvalidValue;
+    if (p.wrap_repeat) return p.fast_div ? launch_query<true, 1>(p, q, kind, s) : launch_query<true, 0>(p, q, kind, s);
+    return p.fast_div ? launch_query<false, 1>(p, q, kind, s) : launch_query<false, 0>(p, q, kind, s);
+}
+
+hipError_t vct_launch_query_keys(const VctTraceParams& p, const VctQueryArgs& q, int kind, uint32_t* keys, uint32_t* index, hipStream_t s) {
+    if (q.n == 0u) return hipSuccess;
+    const dim3 grid((q.n + 255u) / 256u), block(256);
+    const bool gather = kind == VCT_QUERY_GATHER;
+    if (p.wrap_repeat) {
+        if (gather) hipLaunchKernelGGL((k_query_keys<true, VCT_QUERY_GATHER>), grid, block, 0, s, p, q, keys, index);
+        else hipLaunchKernelGGL((k_query_keys<true, VCT_QUERY_CONE>), grid, block, 0, s, p, q, keys, index);
+    } else {
+        if (gather) hipLaunchKernelGGL((k_query_keys<false, VCT_QUERY_GATHER>), grid, block, 0, s, p, q, keys, index);
+        else hipLaunchKernelGGL((k_query_keys<false, VCT_QUERY_CONE>), grid, block, 0, s, p, q, keys, index);
+    }
     return hipGetLastError();
 }
 

@@ -400,6 +400,24 @@ struct Voxel_Cone_Tracing {
         return FrameRGBA16F.data();
     }
 
+    // Point queries (vct_gather_points / vct_cone_points, include/vct.h: no reference counterpart -- the reference lights
+    // only what its camera sees): the six-cone diffuse gather, or one cone, at points the caller names (light probes,
+    // lightmap texels, particles), from the volume the last DrawVoxelTexture() built.  Host pointers; the call returns when
+    // the outputs are written.  sort_cells: VCT_QUERY_SORT_CELLS, for lists that are not in spatial order (same results).
+    // vcth_frame_from_normal makes a tangent frame for a point that has only a normal.
+    bool GatherPoints(const vct_gather_point* points, int32_t n, float* out_gather, float* out_cones = nullptr,
+                      uint8_t* out_steps = nullptr, bool sort_cells = false) {
+        if (!ctx) return false;
+        return check(vct_gather_points(ctx, points, n, VCT_MEM_HOST, out_gather, out_cones, out_steps,
+                                       sort_cells ? VCT_QUERY_SORT_CELLS : 0u), "vct_gather_points");
+    }
+    bool ConePoints(const vct_cone_point* points, int32_t n, int32_t aperture, float* out_cone, uint8_t* out_steps = nullptr,
+                    bool sort_cells = false) {
+        if (!ctx) return false;
+        return check(vct_cone_points(ctx, points, n, VCT_MEM_HOST, aperture, out_cone, out_steps,
+                                     sort_cells ? VCT_QUERY_SORT_CELLS : 0u), "vct_cone_points");
+    }
+
 private:
     bool check(int rc, const char* what) {
         last_status = rc;

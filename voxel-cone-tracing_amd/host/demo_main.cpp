@@ -7,8 +7,13 @@
 //   vct_demo [--scene procedural:atrium|procedural:atrium-textured|procedural:bistro|procedural:cornell] [--voxels 128] [--size 1280x720]
 //            [--shadow 4096] [--frames 3] [--bounces 1|2] [--ppm out.ppm] [--gpus N] [--dynamic-light] [--frames-in-flight 1|2]
 //            [--show diffuse,indirect-diffuse,specular,indirect-specular,ao] [--diffuse-rate 1|2]
-//            [--voxels [current|radiance|albedo|normal[:level]]]
+//            [--voxels [current|radiance|albedo|normal[:level]]] [--ambient-cubes NX,NY,NZ FILE] [--dump-chain FILE]
 //
+// --ambient-cubes NX,NY,NZ FILE: after the frames, an irradiance volume -- an NX x NY x NZ grid of probes over the scene's
+//   bounds, six axis-aligned gathers each (+x, -x, +y, -y, +z, -z: an ambient cube), through
+//   Voxel_Cone_Tracing::GatherPoints (vct_gather_points).  FILE receives raw fp32 [nz][ny][nx][6][4] (rgb + occlusion),
+//   FILE.points the [nz][ny][nx][6] vct_gather_point records that were sent.  Single GPU only.
+// --dump-chain FILE: the mip chain the trace reads, as vct_download_chain_rgba8 returns it.
 // --voxels SOURCE[:LEVEL]: the voxel view instead of the traced frame (Voxel_Cone_Tracing::ShowVoxels,
 //   vct_render_voxels): every Render() ray-marches LEVEL (default 0) of the chain the trace reads (current, the default
 //   when --voxels stands alone), the bounce-0 radiance chain, or the per-voxel albedo / normal (level 0; they need
@@ -92,6 +97,9 @@ int main(int argc, char** argv) {
     bool dynamic_light = false;
     const char* idfile = nullptr;
     const char* show = nullptr;
+    const char* cubes_file = nullptr;
+    const char* chain_file = nullptr;
+    int cubes[3] = {0, 0, 0};
     bool show_voxels = false;
     int view_source = VCT_VOXVIEW_CURRENT, view_level = 0;
     for (int i = 1; i + 1 < argc; ++i) {
@@ -129,6 +137,15 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--frames-in-flight")) in_flight = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--show")) show = argv[++i];
         else if (!strcmp(argv[i], "--diffuse-rate")) diffuse_rate = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--dump-chain")) chain_file = argv[++i];
+        else if (!strcmp(argv[i], "--ambient-cubes") && i + 2 < argc) {
+            if (sscanf(argv[++i], "%d,%d,%d", &cubes[0], &cubes[1], &cubes[2]) != 3 || cubes[0] < 1 || cubes[1] < 1 || cubes[2] < 1 ||
+                (long long)cubes[0] * cubes[1] * cubes[2] * 6 > VCT_POINT_QUERY_MAX) {
+                fprintf(stderr, "--ambient-cubes: NX,NY,NZ FILE with positive counts\n");
+                return 1;
+            }
+            cubes_file = argv[++i];
+        }
     }
     GLFWwindow* window = nullptr;          // no window system on a compute node
 
@@ -248,6 +265,58 @@ int main(int argc, char** argv) {
     }
     printf("frames=%d size=%dx%d voxels=%d cone_steps=%llu trace_ms=%.3f fnv1a=%016llx\n", frames, w, h,
            voxels, (unsigned long long)steps, ms, (unsigned long long)sum);
+    if (cubes_file && gpus <= 0) {
+        // the irradiance-volume use of the point queries: probes at the cell centres of a grid over the scene's bounds
+        Model& model = voxel_cone_tracing.model;
+        const int32_t ntri = vcth_scene_num_triangles(model.scene), nmat = vcth_scene_num_materials(model.scene);
+        std::vector<float> pos((size_t)ntri * 9), albedo((size_t)nmat * 4), specular((size_t)nmat * 3);
+        std::vector<int32_t> material((size_t)ntri);
+        vcth_scene_get(model.scene, pos.data(), material.data(), albedo.data(), specular.data());
+        vct_config cfg;
+        vct_get_config(voxel_cone_tracing.ctx, &cfg);
+        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (size_t i = 0; i < pos.size(); ++i) {
+            const float v = pos[i] * cfg.model_scale;
+            lo[i % 3] = fminf(lo[i % 3], v); hi[i % 3] = fmaxf(hi[i % 3], v);
+        }
+        std::vector<vct_gather_point> pts;
+        for (int z = 0; z < cubes[2]; ++z)
+            for (int y = 0; y < cubes[1]; ++y)
+                for (int x = 0; x < cubes[0]; ++x)
+                    for (int face = 0; face < 6; ++face) {
+                        vct_gather_point p;
+                        const int cell[3] = {x, y, z};
+                        for (int a = 0; a < 3; ++a) {
+                            p.position[a] = lo[a] + (hi[a] - lo[a]) * ((float)cell[a] + 0.5f) / (float)cubes[a];
+                            p.normal[a] = a == face / 2 ? (face & 1 ? -1.0f : 1.0f) : 0.0f;      // unit: the cones start one voxel off the probe
+                        }
+                        vcth_frame_from_normal(p.normal, 1.0f, p.tangent, p.bitangent);
+                        pts.push_back(p);
+                    }
+        std::vector<float> out(pts.size() * 4);
+        if (!voxel_cone_tracing.GatherPoints(pts.data(), (int32_t)pts.size(), out.data())) return 7;
+        uint64_t q[4] = {0, 0, 0, 0};
+        float qms = 0.0f;
+        vct_last_point_query(voxel_cone_tracing.ctx, q);
+        vct_last_point_query_ms(voxel_cone_tracing.ctx, &qms);
+        printf("ambient cubes: %dx%dx%d probes, %llu gathers, cone_steps=%llu march_ms=%.3f\n", cubes[0], cubes[1], cubes[2],
+               (unsigned long long)q[0], (unsigned long long)q[1], qms);
+        FILE* fp = fopen(cubes_file, "wb");
+        if (!fp || fwrite(out.data(), sizeof(float), out.size(), fp) != out.size()) return 4;
+        fclose(fp);
+        fp = fopen((std::string(cubes_file) + ".points").c_str(), "wb");
+        if (!fp || fwrite(pts.data(), sizeof(vct_gather_point), pts.size(), fp) != pts.size()) return 4;
+        fclose(fp);
+    }
+    if (chain_file && gpus <= 0) {
+        vct_config cfg;
+        vct_get_config(voxel_cone_tracing.ctx, &cfg);
+        std::vector<uint8_t> chain(vct_chain_texels(cfg.voxel_dim) * 4);
+        if (vct_download_chain_rgba8(voxel_cone_tracing.ctx, chain.data()) != VCT_OK) return 7;
+        FILE* fp = fopen(chain_file, "wb");
+        if (!fp || fwrite(chain.data(), 1, chain.size(), fp) != chain.size()) return 4;
+        fclose(fp);
+    }
     if (ppm) {
         FILE* fp = fopen(ppm, "wb");
         if (!fp) return 4;

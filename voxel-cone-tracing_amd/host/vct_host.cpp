@@ -1030,6 +1030,24 @@ int32_t vcth_invert_matrix(const float m[16], float out_inv[16]) {
     return 0;
 }
 
+void vcth_frame_from_normal(const float n[3], float scale, float t[3], float b[3]) {
+    for (int i = 0; i < 3; ++i) t[i] = b[i] = 0.0f;
+    const double ax = fabs((double)n[0]), ay = fabs((double)n[1]), az = fabs((double)n[2]);
+    const double m = ax > ay ? (ax > az ? ax : az) : (ay > az ? ay : az);
+    if (!(ax + ay + az > 0.0) || !(ax + ay + az < 1.1e39)) return;      // zero, NaN or infinite (three floats cannot overflow a double)
+    double u[3] = {(double)n[0] / m, (double)n[1] / m, (double)n[2] / m};      // largest component +-1: 1 <= |u| <= sqrt(3)
+    const double lu = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+    for (double& v : u) v /= lu;
+    // helper axis: y unless n runs mostly along y, then x -- never within 45 degrees of n, so |h x u| >= sin(45 degrees)
+    double c[3];
+    if (ay >= ax && ay >= az) { c[0] = 0.0; c[1] = -u[2]; c[2] = u[1]; }       // (1, 0, 0) x u
+    else { c[0] = u[2]; c[1] = 0.0; c[2] = -u[0]; }                            // (0, 1, 0) x u
+    const double lc = sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
+    for (double& v : c) v /= lc;
+    const double d[3] = {u[1] * c[2] - u[2] * c[1], u[2] * c[0] - u[0] * c[2], u[0] * c[1] - u[1] * c[0]};      // u x t: t x (u x t) = u
+    for (int i = 0; i < 3; ++i) { t[i] = (float)(c[i] * (double)scale); b[i] = (float)(d[i] * (double)scale); }
+}
+
 void vcth_light_view_proj(const float L[3], float out_vp[16]) {
     const M4 v = look_at({L[0], L[1], L[2]}, {0, 0, 0}, {0, 1, 0});     // VCT.h:84
     const M4 p = ortho(-120, 120, -120, 120, -100, 100);                // VCT.h:85

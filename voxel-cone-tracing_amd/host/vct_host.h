@@ -70,6 +70,12 @@ void vcth_camera_view_proj(const vcth_camera* cam, int32_t width, int32_t height
 /* The inverse of a column-major 4x4 matrix, computed in double (Gauss-Jordan, partial pivoting) and rounded to fp32 once:
  * what vct_render_voxels takes for the matrix above.  Returns 0, or -1 for a singular or non-finite matrix (out untouched). */
 int32_t vcth_invert_matrix(const float m[16], float out_inv[16]);
+/* A tangent frame for callers of vct_gather_points that have only a normal (light probes, particles): t and b are
+ * orthogonal to n and to each other, of length `scale`, with dot(cross(t, b), n) > 0 -- the orientation of the frames the
+ * scenes of this library carry.  Computed in double from n scaled by its largest component, so any finite non-zero n
+ * works (never NaN, no overflow, no underflow); the helper axis is chosen by a branch on n's dominant axis.  n = 0 or a
+ * non-finite n gives t = b = 0. */
+void vcth_frame_from_normal(const float n[3], float scale, float t[3], float b[3]);
 
 /* VCT.h:84-86: DepthViewProjectionMatrix = ortho(-120,120,-120,120,-100,100) * lookAt(L,0,+Y),
  * column-major. */

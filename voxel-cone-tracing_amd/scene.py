@@ -31,6 +31,8 @@ _lib.vcth_light_view_proj.argtypes = [C.c_void_p, C.c_void_p]
 _lib.vcth_scene_get_frames.argtypes = [C.c_void_p] * 4
 _lib.vcth_camera_view_proj.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
 _lib.vcth_invert_matrix.argtypes = [C.c_void_p, C.c_void_p]
+_lib.vcth_frame_from_normal.restype = None
+_lib.vcth_frame_from_normal.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
 _lib.vcth_scene_save.argtypes = [C.c_void_p, C.c_char_p]
 _lib.vcth_scene_load_cache.restype = C.c_void_p
 _lib.vcth_scene_load_cache.argtypes = [C.c_char_p, C.c_char_p]
@@ -87,6 +89,15 @@ def invert_matrix(m_colmajor):
     if _lib.vcth_invert_matrix(m.ctypes.data, inv.ctypes.data) != 0:
         raise ValueError("singular or non-finite matrix")
     return inv
+
+
+def frame_from_normal(normal, scale=1.0):
+    """(tangent, bitangent), float32[3] each, of length `scale`: a right-handed frame around `normal` for
+    Context.gather_points at a point that has only a normal (a light probe, a particle)."""
+    n = np.ascontiguousarray(normal, np.float32).reshape(3)
+    t, b = np.zeros(3, np.float32), np.zeros(3, np.float32)
+    _lib.vcth_frame_from_normal(n.ctypes.data, float(scale), t.ctypes.data, b.ctypes.data)
+    return t, b
 
 
 def light_view_proj(light_dir):

@@ -627,8 +627,13 @@ int vct_last_step_count(vct_ctx* ctx, uint64_t* steps);
  * all zero (skipped), [3] served through the cooperative block, [4] served by the per-lane gather,
  * [5] live lanes in [4], [6] those of [4] whose live footprints would fit one block anchored at their minimum,
  * [7] blocks a greedy multi-anchor cover of [4] needs in total, [8..10] those of [4] it covers with <= 2 / 3 / 4
- * blocks, [11..15] reserved. */
-int vct_last_trace_stats(vct_ctx* ctx, uint64_t out[16]);
+ * blocks, [11..15] quad / quadrant sharing statistics of [4] (tools/trace_stats.py).
+ * [16..31] block reuse of the default trace kernel, four counters per (kind of wave, level of the step) in the order
+ * diffuse first level, diffuse second, specular first, specular second: cooperative samples for which a slab of the
+ * wave held a block of the sample's level; those whose live footprints all lay inside that block (served from it
+ * without a fetch); those of them whose block was all zero; candidates whose anchor equalled the one a fresh block
+ * would have taken. */
+int vct_last_trace_stats(vct_ctx* ctx, uint64_t out[32]);
 /* Work-item counts behind the per-stage byte figures of bench.py (`stage_roofline`): [0] triangles uploaded,
  * [1] conservative fragments of the mesh at this grid size (the voxelizer's brick-sorted list), [2] division form of
  * the last march launch (screen trace, slab, frame step, bounce or point query): 0 none yet, 1 the IEEE divide, 2 the verified

@@ -54,7 +54,9 @@ def main():
         ctx.trace_resident()
         ctx.synchronize()
         st = ctx.last_trace_stats()
-        samples = st["coop_zero"] + st["coop_hit"] + st["fallback"]
+        # (a sample served from a block already in LDS fetches nothing: it is counted under reuse_hits_* alone)
+        reused = sum(st[f"reuse_hits_{wave}_{level}"] for wave in ("diffuse", "specular") for level in ("first", "second"))
+        samples = st["coop_zero"] + st["coop_hit"] + st["fallback"] + reused
         st.update({
             "tan_specular": ts,
             "cone_steps": ctx.last_step_count(),
@@ -63,6 +65,7 @@ def main():
             "level_samples": samples,
             "frac_coop_zero": round(st["coop_zero"] / max(samples, 1), 4),
             "frac_coop_gather": round(st["coop_hit"] / max(samples, 1), 4),
+            "frac_coop_reused": round(reused / max(samples, 1), 4),
             "frac_per_lane": round(st["fallback"] / max(samples, 1), 4),
             "per_lane_mean_live_lanes": round(st["fallback_lanes"] / max(st["fallback"], 1), 2),
             # of the per-lane samples' live 2x2 quads / 4x4 quadrants: how many could share one small block
@@ -70,6 +73,22 @@ def main():
             "frac_quads_same_cell": round(st["quads_same"] / max(st["quads_live"], 1), 4),
             "frac_quadrants_fit_4x4x4": round(st["quadrants_fit444"] / max(st["quadrants_live"], 1), 4),
         })
+        # block reuse (vct_trace.hip BlockDesc): shares of the cooperative samples (zero + gathered + reused)
+        coop = st["coop_zero"] + st["coop_hit"]
+        reuse = {}
+        for wave in ("diffuse", "specular", "all"):
+            for c in ("candidates", "hits", "hits_zero", "equal_anchor"):
+                reuse[f"{wave}_{c}"] = sum(st[f"reuse_{c}_{wv}_{level}"] for wv in ("diffuse", "specular")
+                                           for level in ("first", "second") if wave in ("all", wv))
+        coop += reuse["all_hits"]
+        st["cooperative_samples"] = coop
+        for wave in ("diffuse", "specular", "all"):
+            cand = max(reuse[f"{wave}_candidates"], 1)
+            st[f"reuse_{wave}_hits_per_candidate"] = round(reuse[f"{wave}_hits"] / cand, 4)
+        st["reuse_candidates_per_coop_sample"] = round(reuse["all_candidates"] / max(coop, 1), 4)
+        st["reuse_hits_per_coop_sample"] = round(reuse["all_hits"] / max(coop, 1), 4)
+        st["reuse_hits_zero_per_coop_sample"] = round(reuse["all_hits_zero"] / max(coop, 1), 4)
+        st["reuse_equal_anchor_per_coop_sample"] = round(reuse["all_equal_anchor"] / max(coop, 1), 4)
         out["launches"].append(st)
     print(json.dumps(out, indent=1))
     ctx.close()

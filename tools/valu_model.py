@@ -4,21 +4,19 @@
     tools/valu_model.py  [--write]
 
 Compiles csrc/vct_trace.hip to gfx950 assembly, takes the specular march loop of
-k_trace_tile_split<true,1,false,false,false,true> (the whole-frame instantiation; the diffuse loop has the same body), splits it at its labels into
-  head      position, three constant divisions, level-1 coordinates, anchor, coverage test
-  coop      cooperative block: Morton offset, load, decode, LDS slab, 8-texel gather, interpolation
-  fallback  per-lane gather
-  l2head    level-2 coordinates, anchor, coverage test
-  tail      level blend + front-to-back composite
-and prices every VALU instruction with the issue cost MEASURED for its class on this GPU
+k_trace_tile_split<true,1,false,false,false,true,false,false> (the whole-frame instantiation; the diffuse loop has the
+same body), splits it at its labels into basic blocks, tells the blocks of a level sample apart by what they hold
+(coordinates, fit test against the held block, reuse, fresh anchor, fetch, LDS write, gather, zero result, per-lane
+gather: see main) and prices every VALU instruction with the issue cost MEASURED for its class on this GPU
 (tools/valu_bench.hip at 8 waves per SIMD, gpurun_out/valu_bench.txt; classes it does not cover are priced as
-4-cycle ops).  The segments are weighted with the measured path frequencies (profiles/r02i_trace_stats.json:
-cooperative gather / empty block / per-lane = 75.5 / 10.9 / 13.7 % of the level samples).
+4-cycle ops).  Each block is weighted with the frequency at which the instrumented build executes it
+(profiles/r07_reuse_stats.json: tools/trace_stats.py on the default workload).
 
 Output: VALU instructions and issue cycles per wave-step and the mean issue cycles per instruction -- the factor
 bench.py uses for `roofline.valu_pipe_busy_model` (profiles/valu_model.json, keyed by the kernel-source sha).
 The segmentation relies on the block layout the compiler currently emits; the script checks the instruction
-counts it finds against the per-wave-step count of the PMC profile and refuses to write on a mismatch > 8 %.
+counts it finds (plus the tile's work outside the march) against the per-wave-step count of the PMC profile and refuses
+to write on a mismatch > 8 %.
 """
 import json
 import os
@@ -35,7 +33,6 @@ sys.path.insert(0, ROOT)
 COST = {"fma": 2.42, "mul": 2.20, "add": 2.18, "logic2": 2.25, "cvt": 3.95, "floor": 3.95, "int3": 4.0, "max": 3.96,
         "cndmask": 2.4, "readlane": 4.0, "cmp": 2.4, "mov": 2.3, "mul_lo": 4.0, "other": 4.0}
 SALU_CYCLES = 4.0       # s_add / s_and / s_mul / s_lshl: 4.17 "cycles @2.4 GHz" at 1, 4 and 8 waves per SIMD
-P_HIT, P_ZERO, P_FALLBACK = 0.7546, 0.1087, 0.1367
 
 
 def classify(op):
@@ -69,7 +66,7 @@ def main():
                         "-fno-slp-vectorize", "-fPIC", "-Wno-unused-function", "-S", "--cuda-device-only", "-o", out, src],
                        check=True, capture_output=True)
         text = open(out).read()
-    m = re.search(r"^_ZN12_GLOBAL__N_118k_trace_tile_splitILb1ELi1ELb0ELb0ELb0ELb1EEEv14VctTraceParams:.*?\.end_amdhsa_kernel", text, re.S | re.M)
+    m = re.search(r"^_ZN12_GLOBAL__N_118k_trace_tile_splitILb1ELi1ELb0ELb0ELb0ELb1ELb0ELb0EEEv14VctTraceParams:.*?\.end_amdhsa_kernel", text, re.S | re.M)
     body = m.group(0).split("\n")
     # the specular march = the largest depth-1 inner loop (the diffuse march, inside the cone loop, is depth 2 and has the
     # same body; small depth-1 loops, if any, are prologue code)
@@ -86,60 +83,71 @@ def main():
             blocks.append(cur); cur = []
         cur.append(ln)
     blocks.append(cur)
-    sized = [(price(b), b) for b in blocks]
-    # by construction: two per-lane blocks (eight texel loads each) and two cooperative blocks (eight ds_read_b128 each), one
-    # pair per level.  (Round 6: texels arrive decoded through typed-buffer loads -- ~76 and ~52 VALU; before: ~190 and ~70
-    # with global_load_dword + cvt / mul / fma.)
-    def texel_loads(b):
-        return sum(1 for ln in b if "buffer_load_format_xyzw" in ln or re.match(r"\s+global_load_dword\s", ln))
-    fb = sorted((((n, c), i) for i, ((n, c), b) in enumerate(sized) if texel_loads(b) >= 6 and n >= 40), key=lambda x: x[1])
-    coop = sorted((((n, c), i) for i, ((n, c), b) in enumerate(sized) if sum("ds_read_b128" in ln for ln in b) >= 8), key=lambda x: x[1])
-    big = sorted(fb + coop)
+    # Round 7 (block reuse): a level sample is a chain of small blocks, told apart by what they hold, each executed
+    # with the frequency the instrumented build measured for it (profiles/r07_reuse_stats.json, default apertures):
+    #   coords   level coordinates (the first level's block also holds the step's position and constant divisions)
+    #   cand     fit test against the held block            -- samples with a candidate
+    #   hit      LDS offset of a reused block               -- samples served from the held block
+    #   anchor   anchor + fit test of a fresh block         -- samples not served from the held block
+    #   fetch    dilated index, typed load, zero ballot     -- cooperative samples that fetch
+    #   write    ds_write of the block, LDS offset          -- ... whose block is not all zero
+    #   gather   8 ds_read_b128 + the trilinear fold        -- reused or fetched, block not all zero
+    #   zero     the four v_mov of a sample that is +0      -- priced as executed whenever the gather is not
+    #   lane     per-lane gather (8 typed loads) and its preamble
+    # Everything else (blend, composite, loop control) is executed once per step.
+    stats = json.load(open(os.path.join(ROOT, "profiles", "r07_reuse_stats.json")))["launches"][0]
+    n_s = float(stats["level_samples"])
+    reused = sum(stats[f"reuse_hits_{w}_{l}"] for w in ("diffuse", "specular") for l in ("first", "second"))
+    reused_zero = sum(stats[f"reuse_hits_zero_{w}_{l}"] for w in ("diffuse", "specular") for l in ("first", "second"))
+    cands = sum(stats[f"reuse_candidates_{w}_{l}"] for w in ("diffuse", "specular") for l in ("first", "second"))
+    f_hit, f_cand, f_lane = reused / n_s, cands / n_s, stats["fallback"] / n_s
+    f_fetch, f_write = (stats["coop_zero"] + stats["coop_hit"]) / n_s, stats["coop_hit"] / n_s
+    f_gather = f_write + (reused - reused_zero) / n_s
+    freq = {"coords": 1.0, "cand": f_cand, "hit": f_hit, "anchor": 1.0 - f_hit, "fetch": f_fetch, "write": f_write,
+            "gather": f_gather, "zero": 1.0 - f_gather, "lane": f_lane, "step": 1.0}
+    second = n_s / stats["wave_steps"] - 1.0          # level samples per wave-step: the second level only where two_levels
+
+    def kind(b):
+        t = "\n".join(b)
+        loads = sum(1 for ln in b if "buffer_load_format_xyzw" in ln)
+        nv = price(b)[0]
+        if loads >= 6: return "lane"
+        if t.count("ds_read_b128") >= 8: return "gather"
+        if "ds_write_b128" in t: return "write"
+        if loads == 1: return "fetch"
+        if "v_readlane" in t: return "anchor"
+        if "v_max3_u32" in t: return "cand"
+        if "v_floor" in t: return "coords"
+        if "s_setprio 0" in t: return "hit"
+        if "s_setprio 1" in t and nv <= 6: return "lane"      # (the per-lane path's preamble)
+        if nv == 4 and all("v_mov_b32" in ln for ln in b if re.match(r"\s+v_", ln)): return "zero"
+        return "step"
+    kinds = [kind(b) for b in blocks]
     # the march is unrolled by two (cone_march): two identical steps per loop body -- model the first
-    assert len(fb) in (2, 4) and len(coop) == len(fb), [x[0] for x in big]
-    unrolled = len(fb) == 4
-    fb, coop = fb[:2], coop[:2]
-    big = sorted(fb + coop)
-    n_fb, c_fb = fb[0][0]
-    n_coop, c_coop = coop[0][0]
-    # the cooperative path starts in the block before (Morton offset, load, all-zero test): that prefix alone is the
-    # cost of an empty block
-    (n_zero, c_zero), _ = sized[coop[0][1] - 1]
-    assert n_zero < 20, n_zero
-    n_coop += n_zero; c_coop += c_zero
-    # head = everything before the first big block; l2head = between the level-1 and level-2 sample code
-    first = min(i for _, i in big)
-    n_head, c_head = price([ln for _, b in sized[:first] for ln in b])
-    l1 = sorted(i for _, i in big)[:2]
-    l2 = sorted(i for _, i in big)[2:]
-    mid = [ln for (_, b) in sized[max(l1) + 1:min(l2)] for ln in b]
-    n_mid_all, c_mid_all = price(mid)
-    rest = sized[max(l2) + 1:]
-    if unrolled:        # the first step ends where the second one's head (position + coordinates, >= 30 VALU) begins
-        cut = next(i for i, ((n, _), _) in enumerate(rest) if n >= 30)
-        rest = rest[:cut]
-    tail = [ln for (_, b) in rest for ln in b]
-    n_tail_all, c_tail_all = price(tail)
-    # blocks between / after the samples also hold the zero-block paths (4 v_mov each): they are priced in full,
-    # which overstates l2head / tail by a few instructions
-    def sample(k):
-        return (P_HIT * (n_coop, c_coop)[k] + P_ZERO * (n_zero, c_zero)[k] + P_FALLBACK * (n_fb, c_fb)[k])
-    n_step = n_head + n_mid_all + n_tail_all + 2 * sample(0)
-    c_step = c_head + c_mid_all + c_tail_all + 2 * sample(1)
-    res = {"segments": {"head": [n_head, round(c_head, 1)], "coop": [n_coop, round(c_coop, 1)],
-                        "fallback": [n_fb, round(c_fb, 1)], "between_levels": [n_mid_all, round(c_mid_all, 1)],
-                        "tail": [n_tail_all, round(c_tail_all, 1)]},
+    heads = [i for i, (k, b) in enumerate(zip(kinds, blocks)) if k == "coords" and price(b)[0] >= 20]
+    assert len(heads) == 2 and kinds.count("lane") >= 4 and kinds.count("gather") == 4, kinds
+    first_step = range(heads[0] - 1 if heads[0] > 0 else 0, heads[1] - 1)
+    seg = {}
+    n_step = c_step = 0.0
+    level = 0
+    for i in first_step:
+        k = kinds[i]
+        if k == "coords": level += 1
+        wgt = freq[k] * (second if (level == 2 and k != "step") else 1.0)
+        n, c = price(blocks[i])
+        n_step += wgt * n; c_step += wgt * c
+        e = seg.setdefault(k, [0, 0.0]); e[0] += n; e[1] = round(e[1] + c, 1)
+    res = {"segments": seg, "segment_frequencies": {k: round(v, 4) for k, v in freq.items()},
+           "second_level_samples_per_wave_step": round(second, 4),
            "valu_per_wave_step_model": round(n_step, 1), "issue_cycles_per_wave_step_model": round(c_step, 1),
            "model_issue_cycles_per_valu_instr": round(c_step / n_step, 3),
-           "path_frequencies": {"coop_gather": P_HIT, "empty_block": P_ZERO, "per_lane": P_FALLBACK},
            "cost_table_cycles": COST}
     import bench
     res["kernel_source_sha16"] = bench.kernel_source_sha()
     tt = os.path.join(ROOT, "profiles", "trace_traffic.json")
     if os.path.exists(tt):
         t = json.load(open(tt))
-        stats = json.load(open(os.path.join(ROOT, "profiles", "r02i_trace_stats.json")))["launches"][0]
-        measured = t["wave_instructions_per_launch"]["valu"] / stats["wave_steps"]
+        measured = t["wave_instructions_per_launch"]["valu"] / stats["wave_steps"]      # (the r07 statistics' wave steps)
         res["valu_per_wave_step_pmc"] = round(measured, 1)
         res["pipe_busy_model"] = round(t["wave_instructions_per_launch"]["valu"] * res["model_issue_cycles_per_valu_instr"]
                                        / 1024.0 / t["gpu_cycles_per_launch"], 3)
@@ -147,7 +155,11 @@ def main():
         res["salu_issue_cycles_per_instr"] = SALU_CYCLES
         res["salu_pipe_busy_model"] = round(t["wave_instructions_per_launch"]["salu"] * SALU_CYCLES
                                             / 1024.0 / t["gpu_cycles_per_launch"], 3)
-        ok = abs(measured - n_step) / measured < 0.08
+        # the PMC count also holds what a tile executes outside the march -- prologue, per-cone set-up, composite: about
+        # 1,700 VALU wave-instructions per tile of the default 1080p frame's 240 x 135 tiles
+        outside = 1700.0 * 240 * 135 / stats["wave_steps"]
+        res["valu_per_wave_step_outside_march"] = round(outside, 1)
+        ok = abs(measured - (n_step + outside)) / measured < 0.08
     else:
         ok = False
     print(json.dumps(res, indent=1))

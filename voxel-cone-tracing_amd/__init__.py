@@ -672,11 +672,14 @@ class Context:
 
     def last_trace_stats(self):
         """Instrumented builds (-DVCT_STATS=1) only: dict of wave-level march counters."""
-        v = (C.c_uint64 * 16)()
+        v = (C.c_uint64 * 32)()
         self._ck(_lib.vct_last_trace_stats(self._h, v), "vct_last_trace_stats")
         keys = ("wave_steps", "lane_steps", "coop_zero", "coop_hit", "fallback", "fallback_lanes", "fallback_fits",
                 "greedy_blocks", "greedy_le2", "greedy_le3", "greedy_le4", "quads_live", "quads_fit333", "quads_same",
                 "quadrants_live", "quadrants_fit444")
+        # block reuse: per kind of wave and level of the step (include/vct.h)
+        keys += tuple(f"reuse_{c}_{wave}_{level}" for wave in ("diffuse", "specular") for level in ("first", "second")
+                      for c in ("candidates", "hits", "hits_zero", "equal_anchor"))
         return dict(zip(keys, (int(x) for x in v)))
 
     def stage_counts(self):

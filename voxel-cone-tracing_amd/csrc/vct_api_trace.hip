@@ -257,7 +257,7 @@ int vct_launch_trace_rows(vct_ctx* c, int row0, int row1, uint16_t* out_base, in
         p.aov = aov_which ? cur(c).aov.get() : nullptr;
     }
 #if defined(VCT_STATS) && VCT_STATS
-    HIP_TRY(c, hipMemsetAsync(c->stats.get(), 0, 16 * sizeof(unsigned long long), cur(c).stream.get()));
+    HIP_TRY(c, hipMemsetAsync(c->stats.get(), 0, 32 * sizeof(unsigned long long), cur(c).stream.get()));
 #endif
     if (compacting) {       // live-pixel compaction (experiment): list + counter, zeroed per launch
         const size_t nt = (size_t)vct_tiles_x(c) * vct_tiles_y(c);
@@ -567,12 +567,12 @@ int vct_last_row_steps(vct_ctx* c, uint64_t* rows, int32_t nrows) {
     return VCT_OK;
 }
 
-int vct_last_trace_stats(vct_ctx* c, uint64_t out[16]) {
+int vct_last_trace_stats(vct_ctx* c, uint64_t out[32]) {
     if (!c || !out) return VCT_ERR_INVALID;
 #if defined(VCT_STATS) && VCT_STATS
     if (!cur(c).have_trace) return vct_fail(c, VCT_ERR_INVALID, "no trace has run");
     HIP_TRY(c, hipStreamSynchronize(cur(c).stream.get()));
-    HIP_TRY(c, hipMemcpy(out, c->stats.get(), 16 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(out, c->stats.get(), 32 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return VCT_OK;
 #else
     return vct_fail(c, VCT_ERR_INVALID, "vct_last_trace_stats: this library was built without -DVCT_STATS=1 "

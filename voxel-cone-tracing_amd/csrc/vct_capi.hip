@@ -121,8 +121,8 @@ int create_resources(vct_ctx* c) {
     }
     HIP_TRY(c, c->step_counter.alloc(VCT_STEP_COUNTERS));
     HIP_TRY(c, hipMemsetAsync(c->step_counter.get(), 0, VCT_STEP_COUNTERS * sizeof(unsigned long long), cur(c).stream.get()));
-    HIP_TRY(c, c->stats.alloc(16));
-    HIP_TRY(c, hipMemsetAsync(c->stats.get(), 0, 16 * sizeof(unsigned long long), cur(c).stream.get()));
+    HIP_TRY(c, c->stats.alloc(32));
+    HIP_TRY(c, hipMemsetAsync(c->stats.get(), 0, 32 * sizeof(unsigned long long), cur(c).stream.get()));
     HIP_TRY(c, c->steps_dev.alloc(2 * VCT_MAX_STEPS));
     {
         std::vector<uint32_t> lut(1024);

@@ -355,7 +355,7 @@ struct vct_ctx {
     VctBuf<uint8_t> dbg_steps;
     VctBuf<float> dbg_cones;
     VctBuf<unsigned long long> step_counter;   // [VCT_STEP_COUNTERS] atomic bank of the bounce kernels (memset before each bounce)
-    VctBuf<unsigned long long> stats;  // [16] march statistics of instrumented builds (VCT_STATS); scratch of the self-tests
+    VctBuf<unsigned long long> stats;  // [32] march statistics of instrumented builds (VCT_STATS); scratch of the self-tests
     VctBuf<uint32_t> vt_pix;          // trace_variant 4: compaction list [tiles][64] + the virtual-tile counter behind it
     VctBuf<VctStep> steps_dev;        // [2][VCT_MAX_STEPS]
     VctBuf<uint32_t> spread_lut;      // [1024] spread3(i) << 2 (vct_trace.hip: dilated anchor coordinates by scalar load)

@@ -273,7 +273,7 @@ struct VctTraceParams {
     float* dbg_cones;                   // [npix][7][4] or null
     unsigned long long* step_counter;   // [VCT_STEP_COUNTERS] bounce kernels: partial sums of executed steps (zero at launch)
     uint32_t* tile_steps;               // [tiles] screen trace: executed steps of each tile (stored, not added)
-    unsigned long long* stats;          // [8] wave-level march counters (builds with -DVCT_STATS=1 only)
+    unsigned long long* stats;          // [32] wave-level march counters (builds with -DVCT_STATS=1 only)
     // second bounce (k_bounce): per-voxel attributes (pooled like the accumulators: [slot][512]), touched-brick
     // flags, output level 0
     // The five of them are read by the bounce kernels only and the dr_* beside them by the screen trace only (half-rate

@@ -173,7 +173,61 @@ struct MarchStats {
     uint32_t quads_same;       // ... whose live footprints are one and the same 2x2x2 cell
     uint32_t quadrants_live;   // 4x4-pixel quadrants with a live lane
     uint32_t quadrants_fit444; // ... whose live footprints fit a 4x4x4 block of their own
+    // round 7: block reuse (BlockDesc below), per cooperative sample, [first / second level of the step]:
+    //   0 candidates: the second slab holds a block of this level          1 hits: every live footprint lies inside it
+    //   2 hits whose block was all zero      3 candidates whose anchor equals the one a fresh block would take
+    uint32_t reuse[2][4];
 };
+
+// Block reuse (round 7).  A march step usually samples a level the wave sampled one step earlier, at most a texel or two
+// further on: a diffuse cone's LOD grows 1.1 per step, so the lower level of a step is the upper level of the step before;
+// a specular cone stays on one pair of levels for several steps.  A 4x4x4 block covers three footprint origins per axis
+// and a coherent tile's 64 footprints span one or two, so the block fetched then usually still holds every texel the
+// new sample reads.  The wave therefore keeps a descriptor -- wave-uniform, four SGPRs -- of the block in its SECOND
+// slab (blk + 64, the one the upper level of a step fills); a cooperative sample of either level whose live footprints
+// all lie inside that block gathers from it and skips the table loads, the index arithmetic, the load, the zero ballot
+// and the LDS write.  A block's texels are a function of (level, anchor + s mod N) alone, so a lane whose offsets
+// against ANY anchor lie in 0..2 reads the eight texel values it reads from a block anchored at the centre lane's
+// footprint (sample_level's rule): same bits.
+// The chain does not change during a launch, so the descriptor lives across the cones of a wave; it starts invalid.
+// (A descriptor for each slab would also serve the lower level of a specular step, but its four SGPRs more put the
+// default kernel into scratch and made it slower than without reuse: profiles/experiments/README.md, round 7.)
+// -DVCT_REUSE=0 builds the kernels without the path: kept for A/B builds (tools/build_ab.sh), like VCT_STATS.
+#ifndef VCT_REUSE
+#define VCT_REUSE 1
+#endif
+#define VCT_NO_BLOCK 0xfffffff0u     // BlockDesc::id of a slab that holds nothing (no level starts there)
+struct BlockDesc {
+    // the level (VctLevelRef::off: a multiple of 8, every level in front of it holds a power of 8 texels >= 8) | 1 when
+    // the block is in the slab; without the bit the block is all zero and the slab holds nothing.  Or VCT_NO_BLOCK.
+    uint32_t id;
+    int ax, ay, az;     // anchor, in the sampler's unreduced integer coordinates
+};
+__device__ __forceinline__ BlockDesc no_block() { return {VCT_NO_BLOCK, 0, 0, 0}; }
+
+// the trilinear fold of a lane's 8 texels out of a block in LDS; q = the lane's lower corner in the slab
+__device__ __forceinline__ F4 gather_block(const float4* q, float a, float b, float c) {
+    F4 r;
+    const float a0 = 1.0f - a, b0 = 1.0f - b, c0 = 1.0f - c;
+    const float ab00 = a0 * b0, ab10 = a * b0, ab01 = a0 * b, ab11 = a * b;
+    {   // lower z plane first, then the upper one: half the texel registers live at a time
+        const float4 t0 = q[0], t1 = q[1], t2 = q[4], t3 = q[5];
+        const float w0 = ab00 * c0, w1 = ab10 * c0, w2 = ab01 * c0, w3 = ab11 * c0;
+#define VCT_ACC(ch) r.ch = w0 * t0.ch; r.ch = fmaf(w1, t1.ch, r.ch); r.ch = fmaf(w2, t2.ch, r.ch); r.ch = fmaf(w3, t3.ch, r.ch);
+        VCT_ACC(x) VCT_ACC(y) VCT_ACC(z) VCT_ACC(w)
+#undef VCT_ACC
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    {
+        const float4 t4 = q[16], t5 = q[17], t6 = q[20], t7 = q[21];
+        wave_sync();
+        const float w4 = ab00 * c, w5 = ab10 * c, w6 = ab01 * c, w7 = ab11 * c;
+#define VCT_ACC(ch) r.ch = fmaf(w4, t4.ch, r.ch); r.ch = fmaf(w5, t5.ch, r.ch); r.ch = fmaf(w6, t6.ch, r.ch); r.ch = fmaf(w7, t7.ch, r.ch);
+        VCT_ACC(x) VCT_ACC(y) VCT_ACC(z) VCT_ACC(w)
+#undef VCT_ACC
+    }
+    return r;
+}
 
 // [GL] tri(level): trilinear, texel centres, REPEAT (or clamp).  `level` is wave-uniform; must be
 // called in wave-uniform control flow with at least one lane `act`.  Lanes without `act` help
@@ -246,25 +300,7 @@ __device__ __forceinline__ F4 sample_level(const uint32_t* __restrict__ chain, c
             blk[lb.lane] = d;
             wave_sync();
             const int slot = act ? (dz * 4 + dy) * 4 + dx : 0;
-            const float4* q = blk + slot;
-            const float a0 = 1.0f - a, b0 = 1.0f - b, c0 = 1.0f - c;
-            const float ab00 = a0 * b0, ab10 = a * b0, ab01 = a0 * b, ab11 = a * b;
-            {   // lower z plane first, then the upper one: half the texel registers live at a time
-                const float4 t0 = q[0], t1 = q[1], t2 = q[4], t3 = q[5];
-                const float w0 = ab00 * c0, w1 = ab10 * c0, w2 = ab01 * c0, w3 = ab11 * c0;
-#define VCT_ACC(ch) r.ch = w0 * t0.ch; r.ch = fmaf(w1, t1.ch, r.ch); r.ch = fmaf(w2, t2.ch, r.ch); r.ch = fmaf(w3, t3.ch, r.ch);
-                VCT_ACC(x) VCT_ACC(y) VCT_ACC(z) VCT_ACC(w)
-#undef VCT_ACC
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            {
-                const float4 t4 = q[16], t5 = q[17], t6 = q[20], t7 = q[21];
-                wave_sync();
-                const float w4 = ab00 * c, w5 = ab10 * c, w6 = ab01 * c, w7 = ab11 * c;
-#define VCT_ACC(ch) r.ch = fmaf(w4, t4.ch, r.ch); r.ch = fmaf(w5, t5.ch, r.ch); r.ch = fmaf(w6, t6.ch, r.ch); r.ch = fmaf(w7, t7.ch, r.ch);
-                VCT_ACC(x) VCT_ACC(y) VCT_ACC(z) VCT_ACC(w)
-#undef VCT_ACC
-            }
+            r = gather_block(blk + slot, a, b, c);
         }
     } else {
       if (VCT_STATS) {
@@ -412,6 +448,96 @@ __device__ __forceinline__ F4 sample_level(const uint32_t* __restrict__ chain, c
     return r;
 }
 
+// The same sample with block reuse (BlockDesc above): cooperative, exact, no footprint records.  `blk` is the wave's
+// FIRST slab whichever level of the step this is; SLAB says which slab this sample fills (0: blk, 1: blk + 64) and
+// `held` describes the block in the second one.
+template <bool WRAP, bool LOOSE, bool PRIO, int SLAB>
+__device__ __forceinline__ F4 sample_level_reuse(const uint32_t* __restrict__ chain, const VctLevelRef lv,
+                                                 float ux, float uy, float uz, bool act, unsigned long long am,
+                                                 float4* __restrict__ blk, const LaneBlock& lb, MarchStats& ms,
+                                                 BlockDesc& held) {
+    // (GL_REPEAT only: k_trace_tile_split switches the path off in clamp mode)
+    if (PRIO) __builtin_amdgcn_s_setprio(1);
+    const int m = lv.m;
+    const float fN = lv.fN;
+    const float u = fmaf(ux, fN, -0.5f), v = fmaf(uy, fN, -0.5f), w = fmaf(uz, fN, -0.5f);
+    const float fu = floorf(u), fv = floorf(v), fw = floorf(w);
+    const float a = u - fu, b = v - fv, c = w - fw;
+    const int i0 = (int)fu, j0 = (int)fv, k0 = (int)fw;
+    // how the sample is served -- an integer, not flags: wave-uniform integers stay in one SGPR, while booleans merged
+    // across branches become lane masks.  0: by no block (yet), 1: by an all-zero block, 2: by the block of the wave's
+    // slabs in which this lane's footprint starts at float4 `at`
+    int mode = 0, at = 0;
+    // the second slab holds a block of this level: compared on the scalar unit, a sample without one pays nothing more
+    if ((held.id & ~1u) == lv.off) {
+        const BlockDesc cd = held;
+        const int dx = i0 - cd.ax, dy = j0 - cd.ay, dz = k0 - cd.az;
+        const uint32_t far = max(max((uint32_t)dx, (uint32_t)dy), (uint32_t)dz);
+        const unsigned long long out = ballot64(far > 2u) & am;
+        if (VCT_STATS) {
+            const int src = ((am >> 27) & 1ull) ? 27 : (int)__ffsll((long long)am) - 1;
+            ++ms.reuse[SLAB][0];
+            if (out == 0ull) { ++ms.reuse[SLAB][1]; if (!(cd.id & 1u)) ++ms.reuse[SLAB][2]; }
+            if (__builtin_amdgcn_readlane(i0, src) - 1 == cd.ax && __builtin_amdgcn_readlane(j0, src) - 1 == cd.ay &&
+                __builtin_amdgcn_readlane(k0, src) - 1 == cd.az) ++ms.reuse[SLAB][3];
+        }
+        if (out == 0ull) {
+            // every live footprint lies inside it: the block is in LDS already, or known to be all zero -- nothing to fetch
+            if (PRIO) __builtin_amdgcn_s_setprio(0);
+            mode = 1 + (int)(cd.id & 1u);
+            at = (act ? (dz * 4 + dy) * 4 + dx : 0) + 64;
+        }
+    }
+    if (mode == 0) {
+        // sample_level's cooperative block, into this sample's slab
+        const int src = ((am >> 27) & 1ull) ? 27 : (int)__ffsll((long long)am) - 1;
+        const int ax = __builtin_amdgcn_readlane(i0, src) - 1;
+        const int ay = __builtin_amdgcn_readlane(j0, src) - 1;
+        const int az = __builtin_amdgcn_readlane(k0, src) - 1;
+        const int dx = i0 - ax, dy = j0 - ay, dz = k0 - az;
+        const uint32_t far = max(max((uint32_t)dx, (uint32_t)dy), (uint32_t)dz);
+        const unsigned long long out = ballot64(far > 2u) & am;
+        if (out == 0ull) {
+            const uint32_t MX = lv.mask_x, MY = MX << 1, MZ = MX << 2;
+            // (GL_REPEAT only: in clamp mode the kernels sample without reuse)
+            const uint32_t m4 = (uint32_t)m << 2;
+            const uint32_t sax = spread_byte(lb.lut, ax, m4) >> 2;
+            const uint32_t say = spread_byte(lb.lut, ay, m4) >> 1;
+            const uint32_t saz = spread_byte(lb.lut, az, m4);
+            const uint32_t idx = (((sax | ~MX) + lb.sbx) & MX) | (((say | ~MY) + lb.sby) & MY) |
+                                 (((saz | ~MZ) + lb.sbz) & MZ);
+            const float4 d = texel_f32(level_texel_buffer(chain + lv.off), idx);
+            if (PRIO) __builtin_amdgcn_s_setprio(0);
+            const unsigned long long any_texel = ballot64((__float_as_uint(d.x) | __float_as_uint(d.y) | __float_as_uint(d.z) | __float_as_uint(d.w)) != 0u);
+            if (VCT_STATS) { if (any_texel != 0ull) ++ms.coop_hit; else ++ms.coop_zero; }
+            mode = any_texel != 0ull ? 2 : 1;
+            if (SLAB == 1) held = {lv.off | (uint32_t)(mode - 1), ax, ay, az};
+            if (mode == 2) {
+                blk[SLAB * 64 + lb.lane] = d;
+                wave_sync();
+                at = (act ? (dz * 4 + dy) * 4 + dx : 0) + SLAB * 64;
+            }
+        }
+    }
+    if (mode == 2) return gather_block(blk + at, a, b, c);
+    if (mode == 1) return {0.0f, 0.0f, 0.0f, 0.0f};     // all 64 texels zero: every footprint sums to exactly +0
+    // incoherent footprints: the per-lane gather, which leaves the slabs and the descriptor alone
+    return sample_level<WRAP, false, LOOSE, false, PRIO>(chain, lv, ux, uy, uz, act, am, blk, lb, ms);
+}
+
+// level SLAB (0: first, 1: second) of a march step, with or without block reuse; `blk` is the wave's first slab
+template <bool WRAP, bool COOP, bool LOOSE, bool CELLS, bool PRIO, bool REUSE, int SLAB>
+__device__ __forceinline__ F4 sample_step_level(const VctTraceParams& p, const VctLevelRef lv, float ux, float uy, float uz,
+                                                bool act, unsigned long long am, float4* __restrict__ blk,
+                                                const LaneBlock& lb, MarchStats& ms, BlockDesc& held) {
+    if constexpr (REUSE) {
+        static_assert(WRAP && COOP && !CELLS, "block reuse: cooperative sampler, GL_REPEAT, no footprint records");
+        return sample_level_reuse<WRAP, LOOSE, PRIO, SLAB>(p.chain, lv, ux, uy, uz, act, am, blk, lb, ms, held);
+    } else {
+        return sample_level<WRAP, COOP, LOOSE, CELLS, PRIO>(p.chain, lv, ux, uy, uz, act, am, blk + SLAB * 64, lb, ms, p.cells_biased);
+    }
+}
+
 // Anisotropic option (oracle/vct_oracle.h "anisotropic (directional) mip volumes"): a level >= 1 is
 // sampled from the three directional chains the cone direction faces, weighted by dir^2.  The chain
 // of an axis depends on the sign of that direction component, which is per lane: when the live
@@ -556,10 +682,10 @@ __device__ __forceinline__ VctStep load_step(StepTable t, int k) {
         const float uy = fmaf(div_const<FASTDIV>(py, p.half_G_aux, p.half_G_rcp), 0.5f, 0.5f); \
         const float uz = fmaf(div_const<FASTDIV>(pz, p.half_G_aux, p.half_G_rcp), 0.5f, 0.5f); \
         F4 vc = (ANISO && st.level >= 1) ? sample_aniso<WRAP, COOP>(p, st.l1, ux, uy, uz, act, live, blk, lb, ac, ms) \
-                                         : sample_level<WRAP, COOP, FASTDIV == 2, CELLS, PRIO>(p.chain, st.l1, ux, uy, uz, act, live, blk, lb, ms, p.cells_biased); \
+                                         : sample_step_level<WRAP, COOP, FASTDIV == 2, CELLS, PRIO, REUSE, 0>(p, st.l1, ux, uy, uz, act, live, blk, lb, ms, held); \
         if (st.two_levels) { \
             const F4 t2 = ANISO ? sample_aniso<WRAP, COOP>(p, st.l2, ux, uy, uz, act, live, blk + 64, lb, ac, ms) \
-                                : sample_level<WRAP, COOP, FASTDIV == 2, CELLS, PRIO>(p.chain, st.l2, ux, uy, uz, act, live, blk + 64, lb, ms, p.cells_biased); \
+                                : sample_step_level<WRAP, COOP, FASTDIV == 2, CELLS, PRIO, REUSE, 1>(p, st.l2, ux, uy, uz, act, live, blk, lb, ms, held); \
             const float g = st.omf;      /* 1 - frac, from the table */ \
             vc.x = fmaf(st.frac, t2.x, g * vc.x); \
             vc.y = fmaf(st.frac, t2.y, g * vc.y); \
@@ -576,11 +702,12 @@ __device__ __forceinline__ VctStep load_step(StepTable t, int k) {
             ++steps; \
         }
 
-template <bool WRAP, int FASTDIV, bool COOP, bool ANISO = false, bool CELLS = false, bool PRIO = false>
+// REUSE: `held` describes the block in the wave's second slab (BlockDesc); the caller keeps it across the cones of a wave
+template <bool WRAP, int FASTDIV, bool COOP, bool ANISO, bool CELLS, bool PRIO, bool REUSE>
 __device__ __forceinline__ F4 cone_march(const VctTraceParams& p, bool alive, F3 start, F3 dir,
                                          const VctStep* tab_global, int n,
                                          float4* __restrict__ blk, const LaneBlock& lb,
-                                         int& steps_out, MarchStats& ms) {
+                                         int& steps_out, MarchStats& ms, BlockDesc& held) {
     const StepTable tab = (StepTable)tab_global;
     float cr = 0.0f, cg = 0.0f, cb = 0.0f, occ = 0.0f;
     int steps = 0;
@@ -651,8 +778,21 @@ __device__ __forceinline__ F4 cone_march(const VctTraceParams& p, bool alive, F3
     return {cr, cg, cb, occ};
 }
 
-__device__ __forceinline__ void flush_stats(const VctTraceParams& p, const MarchStats& ms, int lane) {
+// the march without block reuse
+template <bool WRAP, int FASTDIV, bool COOP, bool ANISO = false, bool CELLS = false, bool PRIO = false>
+__device__ __forceinline__ F4 cone_march(const VctTraceParams& p, bool alive, F3 start, F3 dir,
+                                         const VctStep* tab_global, int n,
+                                         float4* __restrict__ blk, const LaneBlock& lb,
+                                         int& steps_out, MarchStats& ms) {
+    BlockDesc none = no_block();
+    return cone_march<WRAP, FASTDIV, COOP, ANISO, CELLS, PRIO, false>(p, alive, start, dir, tab_global, n, blk, lb, steps_out, ms, none);
+}
+
+// `specular`: the wave marches the specular cone (the reuse counters are kept per kind of wave)
+__device__ __forceinline__ void flush_stats(const VctTraceParams& p, const MarchStats& ms, int lane, bool specular = false) {
     if (VCT_STATS && p.stats && lane == 0) {
+        for (int i = 0; i < 8; ++i)
+            if (ms.reuse[i >> 2][i & 3]) atomicAdd(p.stats + 16 + (specular ? 8 : 0) + i, (unsigned long long)ms.reuse[i >> 2][i & 3]);
         const uint32_t v[16] = {ms.wave_steps, ms.lane_steps, ms.coop_zero, ms.coop_hit, ms.fallback,
                                 ms.fallback_lanes, ms.fallback_fits, ms.greedy_blocks, ms.greedy_le2, ms.greedy_le3,
                                 ms.greedy_le4, ms.quads_live, ms.quads_fit333, ms.quads_same, ms.quadrants_live,
@@ -965,6 +1105,10 @@ k_trace_tile_split(const VctTraceParams p) {
 
     const LaneBlock lb = make_lane_block(p, lane);
     MarchStats ms = {};
+    // block reuse (BlockDesc): the plain, PRIO, COMP, HALF and loose instantiations under GL_REPEAT; the others -- and
+    // clamp mode, where the descriptor costs the kernel 12 B of scratch per lane -- sample as before
+    constexpr bool REUSE = VCT_REUSE && WRAP && !ANISO && !CELLS && !COMPACT;
+    BlockDesc held = no_block();
 
     // (interleaved slabs: traced row j of the launch is tile row row0 + j * stride; the plain launch pays no second division)
     int lrow = 0, tile0 = p.tile_row0 * p.tiles_x + ti;           // tile0: where the wave's step count is stored
@@ -1004,8 +1148,8 @@ k_trace_tile_split(const VctTraceParams p) {
 #pragma unroll 1
         for (int i = wave * VCT_CONES_PER_WAVE; i < wave * VCT_CONES_PER_WAVE + VCT_CONES_PER_WAVE; ++i) {      // :196-199
             int st;
-            const F4 c = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO>(p, alive, start, cone_dir(k0, k1, k2, i),
-                                                                p.steps_diffuse, n_diffuse, blk, lb, st, ms);
+            const F4 c = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO, REUSE>(p, alive, start, cone_dir(k0, k1, k2, i),
+                                                                       p.steps_diffuse, n_diffuse, blk, lb, st, ms, held);
             total += st;
             lds_cone[i][lane] = make_float4(c.x, c.y, c.z, c.w);
             store_debug_cone(p, pixel_index, i, c, st, alive, in_frame);
@@ -1020,15 +1164,15 @@ k_trace_tile_split(const VctTraceParams p) {
         const F3 P = gb_planes3(gb, 0), Nw = gb_planes3(gb, 3), N = gb_planes3(gb, 12);
         const F3 start = cone_start(P, Nw, p.vs);
         int st6;
-        const F4 sc = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO>(p, alive, start, specular_dir(P, N, p.cam),
-                                                             p.steps_specular, n_specular, blk, lb, st6, ms);
+        const F4 sc = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO, REUSE>(p, alive, start, specular_dir(P, N, p.cam),
+                                                                    p.steps_specular, n_specular, blk, lb, st6, ms, held);
         total += st6;
         lds_cone[6][lane] = make_float4(sc.x, sc.y, sc.z, sc.w);
         store_debug_cone(p, pixel_index, 6, sc, st6, alive, in_frame);
     }
     for (int off = 32; off > 0; off >>= 1) total += __shfl_xor(total, off);
     if (lane == 0) atomicAdd(&lds_steps, total);          // LDS: the last arriver below stores the tile's total
-    flush_stats(p, ms, lane);
+    flush_stats(p, ms, lane, wave == VCT_SPLIT - 1);
 
     // arrival: LDS operations of a wave are performed in order, so the cone values are in LDS before
     // the count is raised; whoever raises it to VCT_SPLIT sees all of them

@@ -511,6 +511,55 @@ int vct_last_point_query(vct_ctx* ctx, uint64_t out[4]);
  * events; needs trace timing on (vct_set_trace_timing) when the query was issued and n > 0.  Waits for it. */
 int vct_last_point_query_ms(vct_ctx* ctx, float* ms);
 
+/* ---- emissive materials: area lights in the voxel chain and the frame -------------------------------------------------
+ * No reference counterpart (the reference's only light is the directional one behind the shadow map: S/Voxelization.fs:88
+ * stores albedo * PCF, S/VoxelConeTracing.fs:188-227 adds ambient + direct + cones), so the definition is this build's.
+ * A surface that emits is written into radiance level 0 and becomes an area light for everything that reads the chain --
+ * screen trace, half-rate gather, vct_bounce, voxel view, point queries, anisotropic chains, footprint records, all
+ * unchanged -- and is added to the frame for the pixels that see it.
+ *   Material emission  emission[nmat][3], fp32 RGB, one per material of the uploaded mesh; flat (no emission textures).
+ *   Level 0            (VCT_VOX_CONSERVATIVE_AVG) for a voxel with at least one conservative fragment:
+ *                        L  = the texel the voxelizer produces without emission: the rounded mean of
+ *                             unorm8(albedo * PCF / 25) over the voxel's fragments;
+ *                        Em = the same rounded mean over the same fragments of unorm8(emission[material] * 1.0f): no shadow
+ *                             term, no texture; the clamping float -> unorm8 conversion saturates values above 1;
+ *                        texel.rgb = min(255, L.rgb + Em.rgb) per byte, texel.a = 255.
+ *                      Voxels without fragments stay 0.  The two terms are quantised apart and added with saturation -- not
+ *                      unorm8(albedo * shadow + emission) -- because Em depends on neither the light, the shadow map nor
+ *                      the textures: like the fragments' barycentrics it is computed once per (mesh, table), into an
+ *                      EMISSION POOL of one staged RGBA8 brick (2 KiB) per brick slot, by the voxelize pass's own kernel
+ *                      with the table in place of the albedo; vct_inject_light adds the pool's brick to every brick it
+ *                      copies (one more coalesced 2 KiB read per touched brick).  The voxel attributes are unchanged.
+ *   Frame              every frame slot has three fp32 PIXEL-EMISSION PLANES E[3][h*w].  For a pixel that is not discarded
+ *                      out.rgb = ((A + D) + S) + E: one fp32 add per channel, last, A, D, S formed as above; out.a, discarded
+ *                      pixels (clear colour) and the per-component outputs are unchanged; the VCT_SHOW_* mask does not gate
+ *                      E.  E may hold any fp32 value: a NaN changes its own pixel's rgb only.  No planes: no add, the
+ *                      frame as it was, bit for bit (and the trace kernels without lighting components are launched).
+ * vct_upload_emission: call after vct_upload_triangles, with the nmat of that call.  NULL detaches, so does a new
+ * vct_upload_triangles, and so does a table whose values are all zero: no pool, no planes, no cost.  VCT_ERR_INVALID,
+ * the context keeping the table it had: no mesh uploaded; a value that is NaN, infinite or below 0; config.trace_variant
+ * 1 .. 4 (the rule of the lighting components: those kernels have no planes; and vct_set_trace_variant refuses 1 .. 4
+ * while planes are attached).  Allocates the pool (2 KiB per brick slot) and zeroed planes (12 B per pixel) for every
+ * frame slot -- a later second slot gets its own -- so that a launch allocates nothing; a detach frees them.  It takes effect
+ * with the next vct_voxelize + vct_inject_light (+ vct_build_mips), exactly as a moved light does ("level 0 changed since
+ * the last vct_build_mips" applies unchanged); a pass voxelized before a detach and injected after it is injected without
+ * emission.  vct_voxelize(ctx, VCT_VOX_REFERENCE) with emission attached is VCT_ERR_INVALID: that mode is the shaders as
+ * written.  With emission attached vct_render_gbuffer, vct_render_gbuffer_rows and vct_gi_pass also write the selected
+ * slot's planes (both visibility forms): emission[material of the visible triangle] where a surface is visible, 0 where
+ * none is; the rows form touches its tile rows only.
+ * vct_set_pixel_emission: planes of the selected frame slot for callers that bring their own G-buffer; layout
+ * VCT_GB_LINEAR [3][h*w] or VCT_GB_TILED [tile][3][64], location a vct_mem.  The planes are copied into the slot's own
+ * (HOST: done when the call returns; DEVICE: on the slot's stream).  NULL detaches them (with material emission attached
+ * the slot keeps planes, zeroed until the next G-buffer pass writes them; a G-buffer pass overwrites a caller's planes too).
+ * Every launch that composites takes the selected slot's planes: vct_trace and its slab, resident, row and strided forms,
+ * vct_trace_current, a rank's vct_frame_step, the half-rate pass and vct_gi_pass.  Point queries and the voxel view
+ * need none.
+ * An emitter-only scene needs no switch: a shadow map of all-zero depths (vct_upload_shadow_map) puts every fragment and
+ * every pixel in shadow, level 0 is then Em exactly and the direct terms of the frame are 0. */
+int vct_upload_emission(vct_ctx* ctx, const float* emission /* [nmat][3] */);
+int vct_set_pixel_emission(vct_ctx* ctx, const float* planes, int32_t layout, int32_t location);
+int vct_download_pixel_emission(vct_ctx* ctx, float* planes /* linear [3][h*w] */);
+
 /* ---- two frames in flight (round 6) -----------------------------------------------------------------
  * The reference's Render() (VCT.h:146-190) issues GL commands; the driver starts frame k + 1 while frame k
  * drains -- nothing in R/main.cpp:77-94 waits for a frame.  A HIP stream does wait: each whole-frame trace

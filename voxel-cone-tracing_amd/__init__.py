@@ -61,6 +61,7 @@ ABI_SYMBOLS = [
     "vct_download_aov", "vct_get_aov_device", "vct_set_diffuse_rate", "vct_get_diffuse_rate", "vct_last_diffuse_rate_ms",
     "vct_render_voxels", "vct_last_voxel_view_ms",
     "vct_gather_points", "vct_cone_points", "vct_last_point_query", "vct_last_point_query_ms",
+    "vct_upload_emission", "vct_set_pixel_emission", "vct_download_pixel_emission",
 ]
 
 
@@ -168,6 +169,9 @@ _lib.vct_gather_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
 _lib.vct_cone_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32]
 _lib.vct_last_point_query.argtypes = [C.c_void_p, C.c_void_p]
 _lib.vct_last_point_query_ms.argtypes = [C.c_void_p, C.c_void_p]
+_lib.vct_upload_emission.argtypes = [C.c_void_p, C.c_void_p]
+_lib.vct_set_pixel_emission.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
+_lib.vct_download_pixel_emission.argtypes = [C.c_void_p, C.c_void_p]
 _lib.vct_upload_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
 
 
@@ -332,6 +336,41 @@ class Context:
         albedo = np.ascontiguousarray(albedo, np.float32).reshape(-1, 4)
         self._ck(_lib.vct_upload_triangles(self._h, _ptr(pos), _ptr(material), pos.shape[0],
                                            _ptr(albedo), albedo.shape[0]), "vct_upload_triangles")
+        self._nmat = albedo.shape[0]            # what upload_emission checks its table against (the C side reads nmat rows)
+
+    def upload_emission(self, emission):
+        """Material emission [nmat, 3] (fp32 RGB, finite, >= 0) of the uploaded mesh; None or an all-zero table detaches.
+        Shows in the chain after the next voxelize + inject_light (+ build_mips), in the frame after the next G-buffer pass."""
+        if emission is None:
+            self._ck(_lib.vct_upload_emission(self._h, None), "vct_upload_emission")
+            return
+        emission = np.ascontiguousarray(emission, np.float32).reshape(-1, 3)
+        nmat = getattr(self, "_nmat", None)
+        if nmat is not None and emission.shape[0] != nmat:
+            raise VctError(f"upload_emission: {emission.shape[0]} rows, the uploaded mesh has {nmat} materials")
+        self._ck(_lib.vct_upload_emission(self._h, _ptr(emission)), "vct_upload_emission")
+
+    def set_pixel_emission(self, planes, layout=GB_LINEAR):
+        """Pixel-emission planes of the selected frame slot: a float32 array (linear [3, h*w] or tiled [tiles, 3, 64]) or
+        an int device pointer; None detaches.  Every following trace adds them to the frame's rgb."""
+        if planes is None:
+            self._ck(_lib.vct_set_pixel_emission(self._h, None, GB_LINEAR, MEM_HOST), "vct_set_pixel_emission")
+            return
+        if isinstance(planes, int):
+            self._ck(_lib.vct_set_pixel_emission(self._h, _ptr(planes), layout, MEM_DEVICE), "vct_set_pixel_emission")
+            return
+        planes = np.ascontiguousarray(planes, np.float32)
+        want = 3 * self.cfg.width * self.cfg.height if layout == GB_LINEAR else \
+            ((self.cfg.width + 7) // 8) * ((self.cfg.height + 7) // 8) * 3 * 64
+        if planes.size != want:
+            raise VctError(f"set_pixel_emission: {planes.size} floats, this layout of the frame has {want}")
+        self._ck(_lib.vct_set_pixel_emission(self._h, _ptr(planes), layout, MEM_HOST), "vct_set_pixel_emission")
+
+    def download_pixel_emission(self):
+        """The selected slot's pixel-emission planes, float32 [3, h*w] (linear)."""
+        out = np.zeros((3, self.cfg.width * self.cfg.height), np.float32)
+        self._ck(_lib.vct_download_pixel_emission(self._h, _ptr(out)), "vct_download_pixel_emission")
+        return out
 
     def upload_shadow_map(self, depth, light_vp_rowmajor):
         if depth is None:
@@ -379,6 +418,8 @@ class Context:
         if scene.textures:
             self.upload_mesh_uvs(scene.uv)
             self.upload_textures(scene.textures, scene.mat_tex)
+        if getattr(scene, "emission", None) is not None and np.any(scene.emission):
+            self.upload_emission(scene.emission)       # Ke of the MTL file (an all-zero table would only detach)
 
     def render_shadow_map(self, light_vp_colmajor):
         m = np.ascontiguousarray(light_vp_colmajor, np.float32).reshape(16)

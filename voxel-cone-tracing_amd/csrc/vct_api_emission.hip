@@ -1,0 +1,134 @@
+// vct_api_emission.hip -- the C ABI of emissive materials (include/vct.h "emissive materials"): the material table with
+// its emission pool, and the pixel-emission planes of a frame slot.
+#include "vct_ctx.h"
+#include "vct_emission_check.h"
+
+// No material emission from here on: the table, the pool and every slot's planes that the table (not the caller) attached.
+// The caller has made sure nothing in flight reads them (vct_pipeline_drain + the selected stream, or a hipFree's own wait).
+void vct_emission_detach(vct_ctx* c) {
+    c->mesh.mat_emission.reset();
+    c->vox.emis_pool.reset();
+    c->vox.emis_dirty = true;
+    c->vox.pass_emis = false;
+    for (VctFrameSlot& sl : c->slots)
+        if (!sl.emis_user) sl.emis.reset();
+}
+
+// zeroed planes for a slot that has none, on the slot's stream
+hipError_t vct_emission_planes(const vct_ctx* c, VctFrameSlot& s) {
+    if (s.emis) return hipSuccess;
+    hipError_t e = s.emis.alloc(vct_emis_tiled_floats(c));
+    if (e == hipSuccess) e = hipMemsetAsync(s.emis.get(), 0, vct_emis_tiled_floats(c) * sizeof(float), s.stream.get());
+    if (e != hipSuccess) s.emis.reset();
+    return e;
+}
+
+// c->gb_linear is ONE staging buffer for both frame slots (bind_gbuffer, vct_download_gbuffer and the two calls below use it
+// on the selected slot's stream): before this slot's work overwrites it the host waits for whatever the other slot's stream
+// still has in flight -- that may be a tile kernel reading it.  Only a host-located linear hand-over or a download pays this.
+static int staging_free(vct_ctx* c) {
+    if (c->frames_in_flight > 1) HIP_TRY(c, hipStreamSynchronize(other(c).stream.get()));
+    return VCT_OK;
+}
+
+extern "C" {
+
+int vct_upload_emission(vct_ctx* c, const float* emission) {
+    if (!c) return VCT_ERR_INVALID;
+    if (!c->mesh.tri_pos) return vct_fail(c, VCT_ERR_INVALID, "vct_upload_emission: call vct_upload_triangles first");
+    const int32_t nmat = c->mesh.nmat;
+    size_t bad = 0;
+    const int verdict = emission ? vct_emission_check(emission, nmat, &bad) : VCT_EMISSION_ZERO;
+    if (verdict == VCT_EMISSION_BAD) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "vct_upload_emission: channel %zu of material %zu (%g) is not finite or below 0",
+                 bad % 3, bad / 3, (double)emission[bad]);
+        return vct_fail(c, VCT_ERR_INVALID, msg);
+    }
+    if (verdict == VCT_EMISSION_OK && c->cfg.trace_variant != 0)
+        return vct_fail(c, VCT_ERR_INVALID, "vct_upload_emission: config.trace_variant 1 .. 4 has no pixel-emission planes");
+    HIP_TRY(c, hipSetDevice(c->device));
+    PIPE_TRY(vct_pipeline_drain(c));
+    HIP_TRY(c, hipStreamSynchronize(cur(c).stream.get()));
+    if (verdict == VCT_EMISSION_ZERO) {       // NULL or all zero: detached -- no pool, no planes, no cost
+        vct_emission_detach(c);
+        return VCT_OK;
+    }
+    // all or nothing: the table and the pool in locals, planes only for slots that have none (released again on a failure)
+    std::vector<float> padded((size_t)nmat * 4);
+    vct_emission_pad(emission, nmat, padded.data());
+    VctBuf<float> table;
+    VctBuf<uint32_t> pool;
+    bool fresh_planes[2] = {false, false};
+    hipError_t e = table.alloc(padded.size());
+    if (e == hipSuccess) e = hipMemcpy(table.get(), padded.data(), padded.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess && !c->vox.emis_pool) e = pool.alloc((size_t)(c->vox.nslots ? c->vox.nslots : 1u) * 512);
+    for (int k = 0; k < c->frames_in_flight && e == hipSuccess; ++k) {
+        fresh_planes[k] = !c->slots[k].emis;
+        e = vct_emission_planes(c, c->slots[k]);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->slots[k].stream.get());
+    }
+    if (e != hipSuccess) {
+        for (int k = 0; k < 2; ++k)
+            if (fresh_planes[k]) c->slots[k].emis.reset();
+        return vct_fail(c, e == hipErrorOutOfMemory ? VCT_ERR_NOMEM : VCT_ERR_DEVICE, std::string("vct_upload_emission: ") + hipGetErrorString(e));
+    }
+    c->mesh.mat_emission = std::move(table);
+    if (pool) c->vox.emis_pool = std::move(pool);
+    c->vox.emis_dirty = true;       // the next north-star pass rebuilds the pool from this table
+    return VCT_OK;
+}
+
+int vct_set_pixel_emission(vct_ctx* c, const float* planes, int32_t layout, int32_t location) {
+    if (!c) return VCT_ERR_INVALID;
+    VctFrameSlot& s = cur(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!planes) {       // detach the caller's planes; with material emission the slot keeps planes, zeroed until the next G-buffer pass
+        s.emis_user = false;
+        if (!s.emis) return VCT_OK;
+        if (c->mesh.mat_emission) {
+            HIP_TRY(c, hipMemsetAsync(s.emis.get(), 0, vct_emis_tiled_floats(c) * sizeof(float), s.stream.get()));
+        } else {
+            HIP_TRY(c, hipStreamSynchronize(s.stream.get()));      // a trace in flight may still read them
+            s.emis.reset();
+        }
+        return VCT_OK;
+    }
+    if (layout != VCT_GB_LINEAR && layout != VCT_GB_TILED) return vct_fail(c, VCT_ERR_INVALID, "vct_set_pixel_emission: unknown layout");
+    if (location != VCT_MEM_HOST && location != VCT_MEM_DEVICE) return vct_fail(c, VCT_ERR_INVALID, "vct_set_pixel_emission: unknown location");
+    if (c->cfg.trace_variant != 0)
+        return vct_fail(c, VCT_ERR_INVALID, "vct_set_pixel_emission: config.trace_variant 1 .. 4 has no pixel-emission planes");
+    HIP_TRY(c, vct_emission_planes(c, s));
+    const size_t npix = (size_t)c->cfg.width * c->cfg.height;
+    if (layout == VCT_GB_TILED) {
+        HIP_TRY(c, hipMemcpyAsync(s.emis.get(), planes, vct_emis_tiled_floats(c) * sizeof(float),
+                                  location == VCT_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s.stream.get()));
+    } else {
+        const float* src = planes;
+        if (location == VCT_MEM_HOST) {
+            PIPE_TRY(staging_free(c));
+            HIP_TRY(c, c->gb_linear.reserve(npix * VCT_GB_NPLANES));
+            HIP_TRY(c, hipMemcpyAsync(c->gb_linear.get(), planes, npix * VCT_EMIS_NPLANES * sizeof(float), hipMemcpyHostToDevice, s.stream.get()));
+            src = c->gb_linear.get();
+        }
+        HIP_TRY(c, vct_launch_tile_emission(src, s.emis.get(), c->cfg.width, c->cfg.height, s.stream.get()));
+    }
+    s.emis_user = true;
+    if (location == VCT_MEM_HOST) HIP_TRY(c, hipStreamSynchronize(s.stream.get()));      // the caller's memory is free again
+    return VCT_OK;
+}
+
+int vct_download_pixel_emission(vct_ctx* c, float* planes) {
+    if (!c || !planes) return VCT_ERR_INVALID;
+    if (!cur(c).emis) return vct_fail(c, VCT_ERR_INVALID, "vct_download_pixel_emission: no pixel-emission planes (vct_upload_emission, vct_set_pixel_emission)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t npix = (size_t)c->cfg.width * c->cfg.height;
+    PIPE_TRY(staging_free(c));
+    HIP_TRY(c, c->gb_linear.reserve(npix * VCT_GB_NPLANES));
+    HIP_TRY(c, vct_launch_untile_emission(cur(c).emis.get(), c->gb_linear.get(), c->cfg.width, c->cfg.height, cur(c).stream.get()));
+    HIP_TRY(c, hipMemcpyAsync(planes, c->gb_linear.get(), npix * VCT_EMIS_NPLANES * sizeof(float), hipMemcpyDeviceToHost, cur(c).stream.get()));
+    HIP_TRY(c, hipStreamSynchronize(cur(c).stream.get()));
+    return VCT_OK;
+}
+
+}  // extern "C"

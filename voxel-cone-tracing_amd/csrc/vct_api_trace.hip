@@ -184,14 +184,15 @@ void vct_fill_march_params(const vct_ctx* c, VctTraceParams& p, const uint32_t* 
 }
 
 // VctTraceParams::comp of a launch with lighting components: the mask, the cone groups something reads (include/vct.h),
-// the outputs, and the bit that selects the COMP kernel
-uint32_t component_word(uint32_t mask, uint32_t aov_which) {
+// the outputs, whether the launch has pixel-emission planes, and the bit that selects the COMP kernel
+uint32_t component_word(uint32_t mask, uint32_t aov_which, bool emission) {
     const bool diffuse = (mask & (VCT_SHOW_INDIRECT_DIFFUSE | VCT_SHOW_AMBIENT_OCCLUSION)) || (aov_which & VCT_AOV_INDIRECT_DIFFUSE);
     const bool specular = (mask & VCT_SHOW_INDIRECT_SPECULAR) ||
                           ((mask & VCT_SHOW_AMBIENT_OCCLUSION) && (mask & VCT_SHOW_SPECULAR)) ||
                           (aov_which & VCT_AOV_INDIRECT_SPECULAR);
     const uint32_t groups = (diffuse ? 1u : 0u) | (specular ? 2u : 0u);
-    return VCT_COMP_ON | (aov_which << VCT_COMP_AOV_SHIFT) | (groups << VCT_COMP_GROUPS_SHIFT) | (mask & VCT_SHOW_ALL);
+    return VCT_COMP_ON | (emission ? VCT_COMP_EMISSION : 0u) | (aov_which << VCT_COMP_AOV_SHIFT) | (groups << VCT_COMP_GROUPS_SHIFT) |
+           (mask & VCT_SHOW_ALL);
 }
 
 // `out_base`: where the kernel writes (full-frame addressing); null = the caller's vct_set_frame_target or the
@@ -237,12 +238,17 @@ int vct_launch_trace_rows(vct_ctx* c, int row0, int row1, uint16_t* out_base, in
     // (VCT_SHOW_ALL there is the unmasked arithmetic), and when nothing reads the diffuse group it is rate 1's launch
     const bool half = c->diffuse_rate == 2;
     bool half_march = false;
+    // pixel-emission planes of the slot (include/vct.h "emissive materials"): the composite adds them, in the COMP kernel
+    const float* pix_emis = cur(c).emis.get();
+    if (pix_emis && variant != 0)
+        return vct_fail(c, VCT_ERR_INVALID, "pixel-emission planes need the default trace kernel (config.trace_variant 0)");
+    p.pix_emis = pix_emis;
     if (half) {
         if (row0 != 0 || row1 != vct_tiles_y(c) || row_stride > 1 || pack_rows)
             return vct_fail(c, VCT_ERR_INVALID, "trace: diffuse rate 2 traces whole frames only (no slabs, tile-row ranges or interleaved rows)");
         if (variant != 0 || c->cfg.anisotropic_mips || c->vol.want_cells || c->comm || !cur(c).dr_ind)
             return vct_fail(c, VCT_ERR_INVALID, "trace: diffuse rate 2 needs the default trace kernel on a single-GPU context");
-        p.comp = component_word(c->show_mask, aov_which);
+        p.comp = component_word(c->show_mask, aov_which, pix_emis != nullptr);
         p.aov = aov_which ? cur(c).aov.get() : nullptr;
         half_march = ((p.comp >> VCT_COMP_GROUPS_SHIFT) & 1u) != 0u;
         if (half_march) {
@@ -250,10 +256,10 @@ int vct_launch_trace_rows(vct_ctx* c, int row0, int row1, uint16_t* out_base, in
             p.dr_list = cur(c).dr_list.get(); p.dr_ctr = cur(c).dr_ctr.get();
             p.dr_waves = c->diffuse_rate_waves;
         }
-    } else if (c->show_mask != VCT_SHOW_ALL || aov_which) {
+    } else if (c->show_mask != VCT_SHOW_ALL || aov_which || pix_emis) {
         if (variant != 0)
             return vct_fail(c, VCT_ERR_INVALID, "lighting components / per-component outputs need the default trace kernel (config.trace_variant 0)");
-        p.comp = component_word(c->show_mask, aov_which);
+        p.comp = component_word(c->show_mask, aov_which, pix_emis != nullptr);
         p.aov = aov_which ? cur(c).aov.get() : nullptr;
     }
 #if defined(VCT_STATS) && VCT_STATS

@@ -107,6 +107,9 @@ int vct_voxelize(vct_ctx* c, int32_t mode) {
     if (!c) return VCT_ERR_INVALID;
     if (mode != VCT_VOX_CONSERVATIVE_AVG && mode != VCT_VOX_REFERENCE) return vct_fail(c, VCT_ERR_INVALID, "vct_voxelize: unknown mode");
     if (!c->mesh.tri_pos) return vct_fail(c, VCT_ERR_INVALID, "vct_voxelize: no triangles uploaded");
+    if (mode == VCT_VOX_REFERENCE && c->mesh.mat_emission)
+        return vct_fail(c, VCT_ERR_INVALID, "vct_voxelize: VCT_VOX_REFERENCE is the reference's shaders as written and has no emission "
+                                        "(vct_upload_emission(ctx, NULL) first)");
     HIP_TRY(c, hipSetDevice(c->device));
     PIPE_TRY(vct_pipeline_join(c));       // the staging pool is shared: the other slot's resolve may still read the previous pass
     if (!c->vox.brick_slot || !c->vox.stage || (mode == VCT_VOX_REFERENCE && !c->vox.ref_big))
@@ -127,6 +130,22 @@ int vct_voxelize(vct_ctx* c, int32_t mode) {
         vct_glm_voxel_projections(c, p.proj);
         HIP_TRY(c, vct_launch_voxelize_reference(p, v.ref_big.get() + 1, v.ref_big.get(), cur(c).stream.get()));
     } else {
+        v.pass_emis = false;
+        if (c->mesh.mat_emission && v.emis_pool) {
+            // Emission pool: the brick pass itself over the same sorted fragments with the emission table as the colour
+            // table, no shadow map (PCF = 1) and no per-fragment albedo, resolved into the pool instead of the staging
+            // slots -- multi-chunk slots through the same accumulators, which their resolve leaves zero for the pass
+            // below.  Once per (mesh, table).  It raises the brick flags of exactly the slots the pass below raises.
+            if (v.emis_dirty) {
+                VctVoxParams q = p;
+                q.albedo = c->mesh.mat_emission.get();
+                q.shadow = nullptr; q.shadow_tiles = nullptr;
+                q.stage = v.emis_pool.get(); q.stage_albedo = nullptr; q.stage_normal = nullptr;
+                HIP_TRY(c, vct_launch_voxelize(q, cur(c).stream.get()));
+                v.emis_dirty = false;
+            }
+            v.pass_emis = true;
+        }
         if (p.tex.texels && v.n_frags) {
             // every fragment's albedo (texture fetch or material colour): independent of the light, so evaluated once per
             // change of the textures / texture coordinates, not once per pass
@@ -157,6 +176,7 @@ int vct_inject_light(vct_ctx* c) {
     else {
         a.stage = v.stage.get(); a.stage_albedo = v.stage_albedo.get(); a.stage_normal = v.stage_normal.get();
         a.attr_albedo = v.attr_albedo.get(); a.attr_normal = v.attr_normal.get();
+        if (v.pass_emis && v.emis_pool) a.emis = v.emis_pool.get();
     }
     HIP_TRY(c, vct_launch_resolve(a, c->cfg.voxel_dim, c->vol.level0_dirty, cur(c).stream.get()));
     c->vox.acc_pending = false;

@@ -153,6 +153,11 @@ struct VctFrameSlot {
     uint16_t* frame_target = nullptr;   // caller-owned output (vct_set_frame_target) or null (not owned)
     VctBuf<uint32_t> tile_steps;        // [tiles] executed steps per 8x8 tile of the screen trace
     VctBuf<uint16_t> aov;               // per-component outputs (vct_set_aov_outputs): popcount(aov_which) frames, bit order
+    // pixel-emission planes (include/vct.h "emissive materials"), tiled [tiles][3][64]: present while material emission is
+    // attached (the G-buffer pass writes them) or the caller set planes of its own on this slot (emis_user); a trace
+    // launch with planes adds them in the composite
+    VctBuf<float> emis;
+    bool emis_user = false;             // vct_set_pixel_emission attached them: a detach of the material table leaves them alone
     // half-rate diffuse gather (vct_set_diffuse_rate(ctx, 2); vct_internal.h VctTraceParams::dr_*), present at rate 2 only
     VctBuf<float4> dr_ind;              // [h][w]
     VctBuf<float4> dr_coarse;           // [ch][cw]
@@ -200,6 +205,7 @@ struct VctMesh {
     // raster input stages
     VctBuf<float> tri_nrm, tri_tan, tri_bit;
     VctBuf<float> mat_specular;
+    VctBuf<float> mat_emission;       // [nmat][4] (rgb, 0) material emission (vct_upload_emission), or none: no emission attached
     // material textures (vct_upload_textures) + texture coordinates (vct_upload_mesh_uvs)
     VctBuf<float> tri_uv;
     VctBuf<uint32_t> tex_texels;
@@ -240,6 +246,13 @@ struct VctVoxelPlan {
     VctBuf<uint32_t> stage_normal;
     VctBuf<int32_t> ref_big;           // reference mode: triangles left to the workgroup pass (+ counter)
     bool acc_pending = false;          // accumulators hold an unresolved voxelize pass
+    // Emission pool (include/vct.h "emissive materials"): one staged RGBA8 brick per slot like `stage`, holding the
+    // rounded mean of unorm8(emission[material]) over each voxel's fragments.  Light-independent: allocated by
+    // vct_upload_emission, built by the first north-star pass after the mesh or the table changed (emis_dirty), added to
+    // the staged texels by the resolve of every pass voxelized with it (pass_emis).
+    VctBuf<uint32_t> emis_pool;        // [nslots][512]
+    bool emis_dirty = true;
+    bool pass_emis = false;            // the pending (or last resolved) north-star pass was voxelized with the pool built
 };
 
 // The voxel volume: the Morton mip chain the trace reads and which of its parts are current.  The flags change only in
@@ -397,6 +410,7 @@ inline int vct_tiles_x(const vct_ctx* c) { return (c->cfg.width + VCT_TILE - 1) 
 inline int vct_tiles_y(const vct_ctx* c) { return (c->cfg.height + VCT_TILE - 1) / VCT_TILE; }
 inline bool vct_rows_in_frame(const vct_ctx* c, int row0, int row1) { return row0 >= 0 && row1 <= vct_tiles_y(c) && row0 <= row1; }
 inline size_t vct_gb_tiled_floats(const vct_ctx* c) { return (size_t)vct_tiles_x(c) * vct_tiles_y(c) * VCT_GB_NPLANES * VCT_TILE_PIX; }
+inline size_t vct_emis_tiled_floats(const vct_ctx* c) { return (size_t)vct_tiles_x(c) * vct_tiles_y(c) * VCT_EMIS_NPLANES * VCT_TILE_PIX; }
 inline size_t vct_aov_frames(uint32_t which) { return (size_t)__builtin_popcount(which); }      // one frame per VCT_AOV_* bit that is on
 
 // ---- what more than one translation unit needs, by the file that defines it: vct_capi.hip ----
@@ -418,6 +432,10 @@ int vct_refresh_steps(vct_ctx* c);
 void vct_fill_march_params(const vct_ctx* c, VctTraceParams& p, const uint32_t* chain);
 // asynchronous, on the slot's stream.  row_stride > 1: only every row_stride-th tile row from row0 on; pack_rows: those rows back to back in out_base (interleaved slabs)
 int vct_launch_trace_rows(vct_ctx* c, int row0, int row1, uint16_t* out_base = nullptr, int row_stride = 1, bool pack_rows = false);
+// vct_api_emission.hip: drops the material emission table, its pool and the planes it attached (a new mesh, a NULL or all-zero
+// table); zeroed pixel-emission planes for a slot that has none, on the slot's stream
+void vct_emission_detach(vct_ctx* c);
+hipError_t vct_emission_planes(const vct_ctx* c, VctFrameSlot& s);
 // vct_multi.hip: slab of the attached communicator (false: none attached); its release
 bool vct_comm_rows(const vct_ctx* c, int* row0, int* row1);
 void vct_comm_release(vct_ctx* c);

@@ -240,6 +240,7 @@ struct VctStep {       // 64 B: one s_load_dwordx16 per march step
 #define VCT_COMP_GROUPS_SHIFT 8
 #define VCT_COMP_AOV_SHIFT 16
 #define VCT_COMP_ON 0x80000000u
+#define VCT_COMP_EMISSION 0x40000000u   // the launch has pixel-emission planes (VctTraceParams::pix_emis): the composite adds them
 struct VctTraceParams {
     const uint32_t* chain;              // Morton chain, RGBA8 packed
     uint32_t level_off[VCT_MAX_LEVELS]; // texel offsets
@@ -302,7 +303,7 @@ struct VctTraceParams {
     uint32_t nbricks;
     // Lighting components (vct_set_lighting_components / vct_set_aov_outputs; k_trace_tile_split<.., COMP = true>, launched
     // when comp != 0): bits 0-4 the VCT_SHOW_* mask, bits 8-9 the cone groups marched (1: cones 0-5, 2: cone 6), bits
-    // 16-18 the VCT_AOV_* outputs written to `aov`, bit 31 set.  (It fills the padding in front of slot_brick.)
+    // 16-18 the VCT_AOV_* outputs written to `aov`, bit 30 VCT_COMP_EMISSION, bit 31 set.  (It fills the padding in front of slot_brick.)
     uint32_t comp;
     const uint32_t* slot_brick;         // [nslots] the bricks a fragment of the mesh can land in (the voxelizer's slots)
     uint32_t nslots;
@@ -315,7 +316,9 @@ struct VctTraceParams {
     uint32_t* bounce_list_count;
     union { uint32_t bounce_list_cap;
             int32_t dr_waves; };        // (half-rate pass) waves per 64 marched points: 1, or 2 with three cones each
-    uint32_t* brick_over;               // bricks whose voxels did not fit the list
+    // brick_over is the bounce kernels', pix_emis the screen trace's: one slot, for the reason bounce_out and aov share theirs
+    union { uint32_t* brick_over;       // bricks whose voxels did not fit the list
+            const float* pix_emis; };   // pixel-emission planes, tiled [tile][3][64] (include/vct.h "emissive materials"); read when comp has VCT_COMP_EMISSION
     // Live-pixel compaction (config.trace_variant = 4; vct_trace.hip k_compact_tiles): the live pixels (albedo.a >= 0.5)
     // of every 16x16-pixel super-tile packed into whole waves.  vt_pix[v * 64 + lane] = tile << 6 | pixel of the tile
     // (all ones: no pixel), vt_count[0] = virtual tiles.  Null: lane = pixel of the launched tile.
@@ -412,6 +415,9 @@ struct VctResolveArgs {
     uint32_t* attr_albedo;
     uint32_t* attr_normal;
     unsigned long long* acc;         // reference mode: [nslots][512][2] last-writer words (re-zeroed)
+    // north-star mode with emissive materials: the emission pool, [nslots][512] RGBA8 like `stage`, added to the staged
+    // texel per byte with saturation (include/vct.h "emissive materials"); null: the staged texel as it is
+    const uint32_t* emis;
 };
 
 // inputs of the raster stages (vct_raster.hip); all device pointers
@@ -424,6 +430,7 @@ struct VctRasterArgs {
     const int32_t* tri_alpha;    // [ntri] alpha-test class of the triangle (vct_raster.hip k_tri_alpha) or null
     const float* albedo;         // [nmat][4]
     const float* specular;       // [nmat][3]
+    const float* emission;       // [nmat][4] material emission (rgb, pad) or null (G-buffer shade: the pixel-emission planes)
     int32_t ntri;
     float model_scale;
     // Visibility words: 64-bit (depth | id) of the main draw, W*H; 32-bit depth-only of the shadow pass, S*S.
@@ -474,11 +481,15 @@ hipError_t vct_launch_gbuffer_visibility(const VctRasterArgs& a, const float vie
                                          hipStream_t s);
 hipError_t vct_launch_gbuffer_shade(const VctRasterArgs& a, const float view_proj[16], int W, int H, int row0, int row1,
                                     const uint32_t* shadow, uint32_t shadow_ebase, int shadow_size, const uint2* shadow_tiles,
-                                    const float light_vp[16], float* tiled, hipStream_t s);
+                                    const float light_vp[16], float* tiled, float* emis_tiled, hipStream_t s);
 // one level of a texture's mip chain from its parent (pw x ph -> w x h), glGenerateMipmap restated as in the oracle
 hipError_t vct_launch_tri_alpha(const VctRasterArgs& a, int32_t* out, hipStream_t s);
 hipError_t vct_launch_tex_mip(const uint32_t* parent, int pw, int ph, uint32_t* level, int w, int h, hipStream_t s);
 hipError_t vct_launch_untile_gbuffer(const float* tiled, float* planes_linear, int w, int h, hipStream_t s);
+// the same for the three pixel-emission planes: tiled [tile][3][64] <-> linear [3][h*w]
+#define VCT_EMIS_NPLANES 3
+hipError_t vct_launch_untile_emission(const float* tiled, float* planes_linear, int w, int h, hipStream_t s);
+hipError_t vct_launch_tile_emission(const float* planes_linear, float* tiled, int w, int h, hipStream_t s);
 // strided (row_stride > 1) and packed tile rows are read by k_trace_tile_split's own tiles only: not by the one-wave
 // kernel (variants 1, 2) nor by the compaction's virtual tiles (4)
 static inline bool vct_variant_takes_row_subsets(int variant) { return variant == 0 || variant == 3; }

@@ -1529,6 +1529,10 @@ struct ShadeParams {
     float* tiled;                // [tile][23][64]
     int32_t tiles_x;
     int32_t tile0, tile1;        // tiles [tile0, tile1) are shaded (whole tile rows)
+    // emissive materials (include/vct.h): the material table [nmat][4] and the slot's pixel-emission planes
+    // [tile][3][64]; emis_tiled == null: no emission attached, nothing read or written
+    const float* emission;
+    float* emis_tiled;
 };
 
 // [GL] bilinear clamp-to-edge fetch with the operation order of host/vct_host.cpp shadow_fetch
@@ -1571,6 +1575,7 @@ k_gbuffer_shade(const ShadeParams p) {
     float g[VCT_GB_NPLANES];
 #pragma unroll
     for (int k = 0; k < VCT_GB_NPLANES; ++k) g[k] = 0.0f;
+    float em[3] = {0.0f, 0.0f, 0.0f};       // pixel emission: the visible triangle's material's, 0 where no surface is
     unsigned long long v = ~0ull;
     if (px < W && py < H) {
         v = p.r.vis[(size_t)py * W + px];
@@ -1598,6 +1603,10 @@ k_gbuffer_shade(const ShadeParams p) {
                                     p.albedo[4 * (size_t)m_early + 2], p.albedo[4 * (size_t)m_early + 3]};
         const float sp_early[3] = {p.specular[3 * (size_t)m_early], p.specular[3 * (size_t)m_early + 1],
                                    p.specular[3 * (size_t)m_early + 2]};
+        if (p.emis_tiled) {       // (wave-uniform: a kernel argument) ... and its emission, with them
+#pragma unroll
+            for (int k = 0; k < 3; ++k) em[k] = p.emission[4 * (size_t)m_early + k];
+        }
         // ... and, in a scene with textures, the material's three texture indices and the triangle's texture coordinates
         // (round 4: they used to be asked for after the set-up -- material -> indices -> descriptor -> texels was four
         // dependent round trips behind it, now two)
@@ -1846,6 +1855,11 @@ k_gbuffer_shade(const ShadeParams p) {
     }
 #pragma unroll
     for (int k = 0; k < VCT_GB_NPLANES; ++k) out[k * VCT_TILE_PIX] = g[k];
+    if (p.emis_tiled) {
+        float* eo = p.emis_tiled + (size_t)tile * (VCT_EMIS_NPLANES * VCT_TILE_PIX) + lane;
+#pragma unroll
+        for (int k = 0; k < VCT_EMIS_NPLANES; ++k) eo[k * VCT_TILE_PIX] = em[k];
+    }
 }
 
 // glGenerateMipmap (R/Model.h:168) for one level: rounded mean of the 2x2 parent texels, indices clamped to the parent
@@ -1866,10 +1880,11 @@ k_tex_mip(const uint32_t* __restrict__ parent, int pw, int ph, uint32_t* __restr
 }
 
 // tiled [tile][23][64] -> linear planes [23][h*w] (downloads / tests)
+template <int NPLANES>      // 23: the G-buffer; 3: the pixel-emission planes
 __global__ void k_untile_gbuffer(const float* __restrict__ tiled, float* __restrict__ planes, int w, int h,
                                  int tiles_x) {
     const size_t npix = (size_t)w * h;
-    const size_t total = npix * VCT_GB_NPLANES;
+    const size_t total = npix * NPLANES;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
          i += (size_t)gridDim.x * blockDim.x) {
         const int plane = (int)(i / npix);
@@ -1877,7 +1892,7 @@ __global__ void k_untile_gbuffer(const float* __restrict__ tiled, float* __restr
         const int y = (int)(pix / w), x = (int)(pix - (size_t)y * w);
         const size_t tile = (size_t)(y / VCT_TILE) * tiles_x + x / VCT_TILE;
         const int lane = (y % VCT_TILE) * VCT_TILE + (x % VCT_TILE);
-        planes[i] = tiled[(tile * VCT_GB_NPLANES + plane) * VCT_TILE_PIX + lane];
+        planes[i] = tiled[(tile * NPLANES + plane) * VCT_TILE_PIX + lane];
     }
 }
 
@@ -2038,7 +2053,7 @@ hipError_t vct_launch_gbuffer_visibility(const VctRasterArgs& a, const float vie
 
 hipError_t vct_launch_gbuffer_shade(const VctRasterArgs& a, const float view_proj[16], int W, int H, int row0, int row1,
                                     const uint32_t* shadow, uint32_t shadow_ebase, int shadow_size, const uint2* shadow_tiles,
-                                    const float light_vp[16], float* tiled, hipStream_t s) {
+                                    const float light_vp[16], float* tiled, float* emis_tiled, hipStream_t s) {
     ShadeParams p = make_shade(a, view_proj, W, H, row0, row1);
     p.shadow_tiles = shadow ? shadow_tiles : nullptr;
     p.nrm = a.nrm; p.tan = a.tan; p.bit = a.bit;
@@ -2046,6 +2061,8 @@ hipError_t vct_launch_gbuffer_shade(const VctRasterArgs& a, const float view_pro
     p.shadow = shadow; p.shadow_ebase = shadow_ebase; p.shadow_size = shadow_size;
     for (int i = 0; i < 16; ++i) p.light_vp[i] = light_vp[i];
     p.tiled = tiled;
+    p.emission = a.emission;
+    p.emis_tiled = a.emission ? emis_tiled : nullptr;
     p.tiles_x = (W + VCT_TILE - 1) / VCT_TILE;
     p.tile0 = row0 * p.tiles_x;
     p.tile1 = row1 * p.tiles_x;
@@ -2078,7 +2095,13 @@ hipError_t vct_launch_tex_mip(const uint32_t* parent, int pw, int ph, uint32_t* 
 
 hipError_t vct_launch_untile_gbuffer(const float* tiled, float* planes_linear, int w, int h, hipStream_t s) {
     const int tx = (w + VCT_TILE - 1) / VCT_TILE;
-    hipLaunchKernelGGL(k_untile_gbuffer, dim3(256 * 8), dim3(256), 0, s, tiled, planes_linear, w, h, tx);
+    hipLaunchKernelGGL(k_untile_gbuffer<VCT_GB_NPLANES>, dim3(256 * 8), dim3(256), 0, s, tiled, planes_linear, w, h, tx);
+    return hipGetLastError();
+}
+
+hipError_t vct_launch_untile_emission(const float* tiled, float* planes_linear, int w, int h, hipStream_t s) {
+    const int tx = (w + VCT_TILE - 1) / VCT_TILE;
+    hipLaunchKernelGGL(k_untile_gbuffer<VCT_EMIS_NPLANES>, dim3(256 * 8), dim3(256), 0, s, tiled, planes_linear, w, h, tx);
     return hipGetLastError();
 }
 

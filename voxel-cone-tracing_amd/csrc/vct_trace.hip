@@ -879,9 +879,11 @@ __device__ __forceinline__ float clear_colour(const VctTraceParams& p) { return 
 // COMP: the Show* ternaries (include/vct.h) as selects on the wave-uniform mask, and the per-component outputs.
 // VCT_SHOW_ALL selects every unmasked value, and without COMP every select is decided here: the operations and their
 // order are the same in all three cases.
-template <bool COMP, class V4, class Pixel>
+// COMP with VCT_COMP_EMISSION in the mask word (wave-uniform): out.rgb = ((A + D) + S) + E, one fp32 add per channel, last,
+// E from the launch's pixel-emission planes at em_offset() = tile * 192 + lane (include/vct.h "emissive materials").
+template <bool COMP, class V4, class Pixel, class EmOffset>
 __device__ __forceinline__ void composite(const VctTraceParams& p, const float* gb, F4 ind, V4 sc,
-                                          bool alive, Pixel pixel) {
+                                          bool alive, Pixel pixel, EmOffset em_offset) {
     const F3 P = gb_planes3(gb, 0), N = gb_planes3(gb, 12);
     const float alb_r = gb_plane(gb, 15), alb_g = gb_plane(gb, 16), alb_b = gb_plane(gb, 17), alb_a = gb_plane(gb, 18);
     const float shadow = gb_plane(gb, 22);
@@ -913,6 +915,10 @@ __device__ __forceinline__ void composite(const VctTraceParams& p, const float* 
     const float ag = p.ambient * alb_g * occlusion;
     const float ab = p.ambient * alb_b * occlusion;
     float o0 = ar + dr + sr, o1 = ag + dg + sg, o2 = ab + db + sb, o3 = alb_a;   // :227
+    if (COMP && (comp & VCT_COMP_EMISSION)) {
+        const float* em = p.pix_emis + em_offset();
+        o0 = o0 + em[0]; o1 = o1 + em[VCT_TILE_PIX]; o2 = o2 + em[2 * VCT_TILE_PIX];
+    }
     if (!alive) {
         const float cc = clear_colour(p);
         o0 = cc; o1 = cc; o2 = cc; o3 = 1.0f;
@@ -1037,7 +1043,7 @@ k_trace_tile(const VctTraceParams p) {
 
     // stage 3: composite
     const float* gb3 = gbuf_ptr(fresh_lane());
-    if (in_frame) composite<false>(p, gb3, ind, sc, alive, pixel_index);
+    if (in_frame) composite<false>(p, gb3, ind, sc, alive, pixel_index, [] { return (size_t)0; });
     // executed-step count: wave reduction, stored into the tile's slot (a plain store: no atomic, nothing to clear)
     for (int off = 32; off > 0; off >>= 1) total += __shfl_xor(total, off);
     if (lane == 0) p.tile_steps[tile] = (uint32_t)total;
@@ -1195,7 +1201,8 @@ k_trace_tile_split(const VctTraceParams p) {
 #pragma unroll
             for (int i = 0; i < 6; ++i) ind = fold_cone(ind, i, lds_cone[i][lane]);
         }
-        composite<COMP>(p, gb3, ind, lds_cone[6][lane], alive, pixel_index);
+        composite<COMP>(p, gb3, ind, lds_cone[6][lane], alive, pixel_index,
+                        [&]() { return (size_t)tile * (VCT_EMIS_NPLANES * VCT_TILE_PIX) + fresh_lane(); });
     }
 }
 

@@ -166,16 +166,17 @@ k_mip_aniso(const uint32_t* __restrict__ level0, uint32_t* __restrict__ aniso, u
 }
 
 // planes [23][h*w] -> tiled [tile][23][64]; pixels outside the frame are zero (albedo.a = 0).
+template <int NPLANES>      // 23: the G-buffer; 3: the pixel-emission planes
 __global__ void k_tile_gbuffer(const float* __restrict__ planes, float* __restrict__ tiled, int w,
                                int h, int tiles_x, int tiles_y) {
-    const size_t total = (size_t)tiles_x * tiles_y * VCT_GB_NPLANES * VCT_TILE_PIX;
+    const size_t total = (size_t)tiles_x * tiles_y * NPLANES * VCT_TILE_PIX;
     const size_t npix = (size_t)w * h;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
          i += (size_t)gridDim.x * blockDim.x) {
         const int lane = (int)(i & 63);
         const size_t r = i >> 6;
-        const int plane = (int)(r % VCT_GB_NPLANES);
-        const size_t tile = r / VCT_GB_NPLANES;
+        const int plane = (int)(r % NPLANES);
+        const size_t tile = r / NPLANES;
         const int ty = (int)(tile / tiles_x), tx = (int)(tile - (size_t)ty * tiles_x);
         const int x = tx * VCT_TILE + (lane & 7), y = ty * VCT_TILE + (lane >> 3);
         float v = 0.0f;
@@ -268,7 +269,15 @@ hipError_t vct_launch_tile_gbuffer(const float* planes_linear, float* tiled, int
                                    hipStream_t s) {
     const int tx = (w + VCT_TILE - 1) / VCT_TILE, ty = (h + VCT_TILE - 1) / VCT_TILE;
     const size_t n = (size_t)tx * ty * VCT_GB_NPLANES * VCT_TILE_PIX;
-    hipLaunchKernelGGL(k_tile_gbuffer, dim3(grid_for(n, 256)), dim3(256), 0, s, planes_linear, tiled,
+    hipLaunchKernelGGL(k_tile_gbuffer<VCT_GB_NPLANES>, dim3(grid_for(n, 256)), dim3(256), 0, s, planes_linear, tiled,
+                       w, h, tx, ty);
+    return hipGetLastError();
+}
+
+hipError_t vct_launch_tile_emission(const float* planes_linear, float* tiled, int w, int h, hipStream_t s) {
+    const int tx = (w + VCT_TILE - 1) / VCT_TILE, ty = (h + VCT_TILE - 1) / VCT_TILE;
+    const size_t n = (size_t)tx * ty * VCT_EMIS_NPLANES * VCT_TILE_PIX;
+    hipLaunchKernelGGL(k_tile_gbuffer<VCT_EMIS_NPLANES>, dim3(grid_for(n, 256)), dim3(256), 0, s, planes_linear, tiled,
                        w, h, tx, ty);
     return hipGetLastError();
 }

@@ -852,9 +852,21 @@ k_voxelize_reference_big(const VctVoxParams p, const int32_t* big_list, const in
     }
 }
 
+// Per-byte saturating add of two RGBA8 words (emissive materials: staged texel + emission-pool texel).  Even and odd
+// bytes are added apart, each in a 16-bit field, so a byte's carry lands in the gap above it instead of in its
+// neighbour; a field whose bit 8 is set overflowed and its byte becomes 255.
+__device__ __forceinline__ uint32_t add_sat_rgba8(uint32_t a, uint32_t b) {
+    const uint32_t even = (a & 0x00ff00ffu) + (b & 0x00ff00ffu);
+    const uint32_t odd = ((a >> 8) & 0x00ff00ffu) + ((b >> 8) & 0x00ff00ffu);
+    const uint32_t even_s = (even | (((even >> 8) & 0x00010001u) * 0xffu)) & 0x00ff00ffu;
+    const uint32_t odd_s = (odd | (((odd >> 8) & 0x00010001u) * 0xffu)) & 0x00ff00ffu;
+    return even_s | (odd_s << 8);
+}
+
 // A pass's result -> RGBA8 level 0 (Morton) for the bricks that were touched in this pass or in the previous one (all
 // bricks if `dense`), one wave per 8^3 brick.  Three cases: the mesh has no slot for the brick (level 0 is empty there);
-// north-star mode: the brick's staged texels (+ voxel attributes) are copied; reference mode: the last writer's colour
+// north-star mode: the brick's staged texels (+ voxel attributes) are copied -- plus, with emissive materials, the
+// emission pool's brick per byte with saturation (a.emis, wave-uniform: one more coalesced 2 KiB read); reference mode: the last writer's colour
 // is unpacked from the slot's words, which go back to zero.
 __global__ void __launch_bounds__(256)
 k_resolve_sparse(const VctResolveArgs a, uint32_t nbricks, int dense, int scan64) {
@@ -889,7 +901,7 @@ k_resolve_sparse(const VctResolveArgs a, uint32_t nbricks, int dense, int scan64
         if (a.stage) {        // north-star mode: k_voxelize_bricks already resolved the brick into its staging slot
             for (uint32_t v = lane; v < 512u; v += 64) {
                 const size_t vox = (size_t)slot * 512 + v;
-                l0[v] = a.stage[vox];
+                l0[v] = a.emis ? add_sat_rgba8(a.stage[vox], a.emis[vox]) : a.stage[vox];
                 if (a.stage_albedo) { a.attr_albedo[vox] = a.stage_albedo[vox]; a.attr_normal[vox] = a.stage_normal[vox]; }
             }
         } else {              // reference mode: (triangle + 1) << 32 | rgb of the last triangle that stored here

@@ -218,6 +218,13 @@ struct Voxel_Cone_Tracing {
     bool ShowVoxels = false;
     int VoxelViewSource = VCT_VOXVIEW_CURRENT;
     int VoxelViewLevel = 0;
+    // Emissive materials (vct_upload_emission, include/vct.h: no reference counterpart -- the reference's only light is the
+    // directional one): fp32 RGB per material of the model, filled from the MTL file's Ke by init; SetEmission changes
+    // it.  The next Render() uploads a changed table and rebuilds the volume from it (DrawVoxelTexture, or the whole GI
+    // pass under DynamicLight), as a changed lightDirection is picked up under DynamicLight.  Not with
+    // ReferenceVoxelization (that mode is the reference's shaders as written).
+    std::vector<float> Emission;                     // [materials][3]
+    bool emission_dirty = false;
     int Bounces = 1;    // 2 = re-inject the lit voxels once (the "2 bounces" of the reference's README.md:16,
                         // which its code does not implement: VCT.h:138-139 injects once); set before init
 
@@ -297,8 +304,29 @@ struct Voxel_Cone_Tracing {
             if (!check(vct_upload_textures(ctx, ptr.data(), tw.data(), th.data(), ntex, mat_tex.data()),
                        "vct_upload_textures")) return;
         }
+        // Ke of the MTL file, unless SetEmission was called before init for this many materials
+        if (Emission.size() != (size_t)nmat * 3) {
+            Emission.assign((size_t)nmat * 3, 0.0f);
+            vcth_scene_get_emission(model.scene, Emission.data());
+        }
+        if (!UploadEmission()) return;
         DrawDepthTexture();     // VCT.h:138
         DrawVoxelTexture();     // VCT.h:139
+    }
+
+    // Emission of one material, or the whole table ([materials][3]); picked up by the next Render().
+    bool SetEmission(int material, float r, float g, float b) {
+        if (material < 0 || (size_t)material * 3 + 2 >= Emission.size()) return false;
+        float* e = &Emission[(size_t)material * 3];
+        e[0] = r; e[1] = g; e[2] = b;
+        emission_dirty = true;
+        return true;
+    }
+    bool SetEmission(const float* table, size_t materials) {
+        if (!table || (ctx && materials * 3 != Emission.size())) return false;
+        Emission.assign(table, table + materials * 3);
+        emission_dirty = true;
+        return true;
     }
 
     // the five Show* switches as VCT_SHOW_* bits
@@ -313,6 +341,11 @@ struct Voxel_Cone_Tracing {
         vct_set_ambient_factor(ctx, AmbientFactor);
         if (!check(vct_set_lighting_components(ctx, ShowMask()), "vct_set_lighting_components")) return;
         if (!check(vct_set_diffuse_rate(ctx, DiffuseRate), "vct_set_diffuse_rate")) return;
+        if (emission_dirty) {                                    // a changed table: upload, and rebuild the volume from it
+            if (!UploadEmission()) return;
+            if (!DynamicLight || Bounces >= 2) DrawVoxelTexture();      // (a whole GI pass below rebuilds it anyway)
+            if (last_status != VCT_OK) return;
+        }
         const float cam[3] = {camera.position.x, camera.position.y, camera.position.z};   // VCT.h:167
         const float L[3] = {lightDirection.x, lightDirection.y, lightDirection.z};         // VCT.h:168
         vct_set_camera_position(ctx, cam);
@@ -419,6 +452,11 @@ struct Voxel_Cone_Tracing {
     }
 
 private:
+    bool UploadEmission() {
+        // a refused table stays pending: every Render() reports the refusal until SetEmission hands over a valid one
+        emission_dirty = !check(vct_upload_emission(ctx, Emission.empty() ? nullptr : Emission.data()), "vct_upload_emission");
+        return !emission_dirty;
+    }
     bool check(int rc, const char* what) {
         last_status = rc;
         if (rc != VCT_OK) printf("ERROR::VCT::%s: %s\n", what, vct_last_error(ctx));

@@ -8,7 +8,11 @@
 //            [--shadow 4096] [--frames 3] [--bounces 1|2] [--ppm out.ppm] [--gpus N] [--dynamic-light] [--frames-in-flight 1|2]
 //            [--show diffuse,indirect-diffuse,specular,indirect-specular,ao] [--diffuse-rate 1|2]
 //            [--voxels [current|radiance|albedo|normal[:level]]] [--ambient-cubes NX,NY,NZ FILE] [--dump-chain FILE]
+//            [--emission MATERIAL=R,G,B[;MATERIAL=R,G,B...]]
 //
+// --emission LIST: emission (fp32 RGB) of the listed material indices, over whatever the scene's MTL file gave them
+//   (Voxel_Cone_Tracing::SetEmission, vct_upload_emission): the surfaces become area lights in the volume and are added
+//   to the pixels that see them.  The procedural street (procedural:bistro) keeps its lamps in material 10: --emission "10=1,0.9,0.7" lights them.
 // --ambient-cubes NX,NY,NZ FILE: after the frames, an irradiance volume -- an NX x NY x NZ grid of probes over the scene's
 //   bounds, six axis-aligned gathers each (+x, -x, +y, -y, +z, -z: an ambient cube), through
 //   Voxel_Cone_Tracing::GatherPoints (vct_gather_points).  FILE receives raw fp32 [nz][ny][nx][6][4] (rgb + occlusion),
@@ -99,6 +103,7 @@ int main(int argc, char** argv) {
     const char* show = nullptr;
     const char* cubes_file = nullptr;
     const char* chain_file = nullptr;
+    const char* emission = nullptr;
     int cubes[3] = {0, 0, 0};
     bool show_voxels = false;
     int view_source = VCT_VOXVIEW_CURRENT, view_level = 0;
@@ -138,6 +143,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--show")) show = argv[++i];
         else if (!strcmp(argv[i], "--diffuse-rate")) diffuse_rate = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--dump-chain")) chain_file = argv[++i];
+        else if (!strcmp(argv[i], "--emission")) emission = argv[++i];
         else if (!strcmp(argv[i], "--ambient-cubes") && i + 2 < argc) {
             if (sscanf(argv[++i], "%d,%d,%d", &cubes[0], &cubes[1], &cubes[2]) != 3 || cubes[0] < 1 || cubes[1] < 1 || cubes[2] < 1 ||
                 (long long)cubes[0] * cubes[1] * cubes[2] * 6 > VCT_POINT_QUERY_MAX) {
@@ -208,6 +214,21 @@ int main(int argc, char** argv) {
     }
     voxel_cone_tracing.init_voxel_cone_tracing();           // R/main.cpp:68
     if (voxel_cone_tracing.last_status != VCT_OK) return 2;
+
+    if (emission) {                                         // --emission: per-material overrides, picked up by the first Render()
+        for (const char* q = emission; *q;) {
+            int m = -1, used = 0;
+            float r = 0.0f, g = 0.0f, b = 0.0f;
+            if (sscanf(q, "%d=%f,%f,%f%n", &m, &r, &g, &b, &used) != 4 || !voxel_cone_tracing.SetEmission(m, r, g, b)) {
+                fprintf(stderr, "--emission: MATERIAL=R,G,B[;...] with material indices below %zu (at '%s')\n",
+                        voxel_cone_tracing.Emission.size() / 3, q);
+                return 1;
+            }
+            q += used;
+            if (*q == ';') ++q;
+            else if (*q) { fprintf(stderr, "--emission: ';' expected at '%s'\n", q); return 1; }
+        }
+    }
 
     float delta_time = 0.05f;
     voxel_cone_tracing.Render();                            // frame 0 pays first-launch costs

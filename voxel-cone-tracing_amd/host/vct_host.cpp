@@ -80,7 +80,10 @@ inline void xform(const float* m, V3 p, float out[4]) {
     for (int r = 0; r < 4; ++r) out[r] = m[r] * p.x + m[4 + r] * p.y + m[8 + r] * p.z + m[12 + r];
 }
 
-struct Material { float albedo[4]; float spec[3]; int tex[3] = {-1, -1, -1}; };   // tex: diffuse, specular, height
+struct Material {
+    float albedo[4]; float spec[3]; int tex[3] = {-1, -1, -1};      // tex: diffuse, specular, height
+    float emission[3] = {0.0f, 0.0f, 0.0f};                         // Ke of the MTL file; the procedural scenes emit nothing
+};
 struct Texture { int w = 0, h = 0; std::vector<uint8_t> rgba; };
 
 }  // namespace
@@ -768,6 +771,8 @@ vcth_scene* vcth_scene_load_obj(const char* path, char* error) {
                 mats[(size_t)cur].albedo[0] = a; mats[(size_t)cur].albedo[1] = b; mats[(size_t)cur].albedo[2] = c;
             } else if (cur >= 0 && sscanf(line, " Ks %f %f %f", &a, &b, &c) == 3) {
                 mats[(size_t)cur].spec[0] = a; mats[(size_t)cur].spec[1] = b; mats[(size_t)cur].spec[2] = c;
+            } else if (cur >= 0 && sscanf(line, " Ke %f %f %f", &a, &b, &c) == 3) {
+                mats[(size_t)cur].emission[0] = a; mats[(size_t)cur].emission[1] = b; mats[(size_t)cur].emission[2] = c;
             } else if (cur >= 0 && sscanf(line, " d %f", &a) == 1) mats[(size_t)cur].albedo[3] = a;
             else if (cur >= 0) {
                 // map_Kd -> DiffuseTexture, map_Ks -> SpecularTexture, map_bump / bump -> HeightTexture
@@ -923,6 +928,15 @@ int vcth_scene_save(const vcth_scene* s, const char* path) {
         const int32_t wh[2] = {t.w, t.h};
         ok = ok && fwrite(wh, 4, 2, f) == 2 && put(f, t.rgba);
     }
+    // material emission [nmat][3]: a trailing block, written only when something emits -- a cache without it (every
+    // cache written before emission existed) loads with zero emission, and an older reader stops in front of it
+    std::vector<float> me;
+    bool emits = false;
+    for (const Material& m : s->materials) {
+        me.insert(me.end(), m.emission, m.emission + 3);
+        emits = emits || m.emission[0] != 0.0f || m.emission[1] != 0.0f || m.emission[2] != 0.0f;
+    }
+    if (emits) ok = ok && put(f, me);
     ok = (fclose(f) == 0) && ok;
     return ok ? 0 : -1;
 }
@@ -949,6 +963,16 @@ vcth_scene* vcth_scene_load_cache(const char* path, char* error) {
         t.w = wh[0]; t.h = wh[1];
         if (ok) s->textures.push_back(t);
     }
+    std::vector<float> me;      // the optional trailing emission block (vcth_scene_save): absent = zero emission
+    uint64_t me_n = 0;
+    const size_t me_head = ok ? fread(&me_n, 1, 8, f) : 0;      // 0 bytes: the file ends here, no block
+    if (me_head == 8) {
+        ok = me_n == mt.size();      // [nmat][3], like the texture indices
+        me.resize(ok ? me_n : 0);
+        ok = ok && fread(me.data(), sizeof(float), me_n, f) == me_n;
+    } else if (me_head != 0) {
+        ok = false;
+    }
     fclose(f);
     const size_t ntri = s->mat.size(), nmat = mt.size() / 3;
     ok = ok && s->pos.size() == ntri * 9 && s->nrm.size() == ntri * 9 && s->tan.size() == ntri * 9 &&
@@ -961,6 +985,7 @@ vcth_scene* vcth_scene_load_cache(const char* path, char* error) {
         memcpy(mm.albedo, &mf[m * 7], 16);
         memcpy(mm.spec, &mf[m * 7 + 4], 12);
         memcpy(mm.tex, &mt[m * 3], 12);
+        if (!me.empty()) memcpy(mm.emission, &me[m * 3], 12);
         s->materials.push_back(mm);
     }
     return s;
@@ -977,6 +1002,10 @@ void vcth_scene_get(const vcth_scene* s, float* pos, int32_t* material, float* a
         if (albedo) memcpy(albedo + 4 * i, s->materials[i].albedo, 16);
         if (specular) memcpy(specular + 3 * i, s->materials[i].spec, 12);
     }
+}
+
+void vcth_scene_get_emission(const vcth_scene* s, float* emission) {
+    for (size_t i = 0; s && emission && i < s->materials.size(); ++i) memcpy(emission + 3 * i, s->materials[i].emission, 12);
 }
 
 void vcth_scene_get_frames(const vcth_scene* s, float* normal, float* tangent, float* bitangent) {

@@ -62,6 +62,9 @@ int32_t vcth_scene_num_materials(const vcth_scene* s);
 /* pos [ntri*9], material [ntri], albedo [nmat*4], specular [nmat*3]; any may be NULL. */
 void vcth_scene_get(const vcth_scene* s, float* pos, int32_t* material, float* albedo,
                     float* specular);
+/* Material emission [nmat*3]: Ke of the MTL file (what vct_upload_emission takes); zero for the procedural scenes and
+ * for materials without Ke. */
+void vcth_scene_get_emission(const vcth_scene* s, float* emission);
 
 /* Per-vertex frame (R/Mesh.h:12-19): normal, tangent, bitangent [ntri*9] each; any may be NULL. */
 void vcth_scene_get_frames(const vcth_scene* s, float* normal, float* tangent, float* bitangent);

@@ -41,6 +41,7 @@ _lib.vcth_scene_num_textures.argtypes = [C.c_void_p]
 _lib.vcth_scene_texture_info.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
 _lib.vcth_scene_get_texture.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
 _lib.vcth_scene_get_material_textures.argtypes = [C.c_void_p, C.c_void_p]
+_lib.vcth_scene_get_emission.argtypes = [C.c_void_p, C.c_void_p]
 
 
 _lib.vcth_image_load.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
@@ -131,6 +132,8 @@ class Scene:
         self.specular = np.zeros((self.nmat, 3), np.float32)
         _lib.vcth_scene_get(self._h, self.pos.ctypes.data, self.material.ctypes.data,
                             self.albedo.ctypes.data, self.specular.ctypes.data)
+        self.emission = np.zeros((self.nmat, 3), np.float32)         # Ke of the MTL file; the procedural scenes emit nothing
+        _lib.vcth_scene_get_emission(self._h, self.emission.ctypes.data)
         self.uv = np.zeros((self.ntri, 6), np.float32)
         _lib.vcth_scene_get_uvs(self._h, self.uv.ctypes.data)
         self.mat_tex = np.full((self.nmat, 3), -1, np.int32)       # diffuse / specular / height texture or -1

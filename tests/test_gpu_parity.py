@@ -714,6 +714,35 @@ def test_second_bounce_dense_scene_overflows_the_voxel_list(vct, oracle):
             ctx.voxelize(); ctx.inject_light(); ctx.build_mips()
 
 
+def test_second_bounce_in_clamp_mode_list_and_overflow(vct, oracle):
+    """The second bounce with wrap_repeat = 0 and the default march constants (the verified-product division):
+    k_bounce_march<false, 1> over the voxel list and k_bounce_bricks<false, 1> over the bricks that did not fit it -- the
+    dense 16^3 scene of the test above, whose voxels next to the grid's faces march cones out of the volume, where clamp
+    and REPEAT differ.  Level 0, chain and step count bit-equal to the oracle's, and not those of REPEAT."""
+    V = 16
+    r = np.random.default_rng(77)
+    ntri = 1500
+    c = r.uniform(-1400, 1400, (ntri, 1, 3))
+    pos = (c + r.normal(scale=260.0, size=(ntri, 3, 3))).astype(np.float32)
+    mat = r.integers(0, 3, ntri).astype(np.int32)
+    alb = r.uniform(0.2, 0.9, (3, 4)).astype(np.float32)
+    p = oracle.default_params(V, wrap_repeat=0)
+    l0, want_alb, want_nrm = oracle.voxelize_conservative_attr(p, oracle.make_scene(pos, mat, alb))
+    assert int((l0[..., 3] > 0).sum()) > V ** 3 // 8                               # the list cannot hold them all
+    chain0 = oracle.build_mips(l0)
+    want_l1, want_steps = oracle.bounce(p, chain0, want_alb, want_nrm, nthreads=8)
+    repeat_l1, _ = oracle.bounce(oracle.default_params(V), chain0, want_alb, want_nrm, nthreads=8)
+    assert (want_l1 != repeat_l1).any()
+    with make_ctx(vct, V, 8, 8, voxel_attributes=1, wrap_repeat=0) as ctx:
+        ctx.upload_triangles(pos, mat, alb)
+        ctx.voxelize(); ctx.inject_light(); ctx.build_mips()
+        assert np.array_equal(ctx.download_chain(), chain0)
+        ctx.bounce()
+        assert ctx.stage_counts()["march_division"] == 2                           # the verified product, not the IEEE divide
+        assert ctx.last_step_count() == want_steps
+        assert np.array_equal(ctx.download_chain(), oracle.build_mips(want_l1))
+
+
 @pytest.mark.parametrize("w,h", [(1, 1), (9, 3)])
 def test_smallest_grid_and_frames(vct, oracle, w, h):
     """voxel_dim = 8 (the minimum: one brick, 4 levels, the coarse levels of every cone step are the one-texel level)

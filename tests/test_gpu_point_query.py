@@ -183,6 +183,27 @@ def test_division_forms_and_march_constants(vct, oracle, chain, which, wrap):
         assert mp.form_of(ctx) == form
 
 
+@pytest.mark.parametrize("wrap", [1, 0])
+def test_gather_without_debug_outputs_under_the_ieee_divide(vct, oracle, chain, wrap):
+    """k_query_march<WRAP, 0, GATHER, false>: the gather alone (no cones, no step counts asked for) with a grid size whose
+    divisors the device rejects.  No debug outputs exist in this instantiation, so the bar is on what it writes: every
+    gather float bit-equal to the oracle's and the executed-step total equal to the sum of the oracle's per-cone counts.
+    193 points: three full waves and a tail of one lane; a coherent patch (cooperative blocks) and a scatter (per-lane)."""
+    consts, form = MARCH["rejected_G"]
+    cfg = dict(pc.config(wrap_repeat=wrap), **consts)
+    pts = np.concatenate([pc.scatter()[:100], pc.patch()[:93]])
+    pts[:, 0:3] *= f32(cfg["grid_world_size"] / pc.G)
+    with vct.Context(vct.default_config(**cfg)) as ctx:
+        ctx.upload_chain(chain)
+        ref = pq.gather(oracle, mp.params(oracle, ctx), chain, pts)
+        got = ctx.gather_points(pts)
+        assert mp.form_of(ctx) == form
+        pq.assert_floats_match(got, ref["gather"], "gather without debug outputs")
+        n, steps, kind, was_sorted = ctx.last_point_query()
+        assert (n, kind, was_sorted) == (pts.shape[0], 0, 0)
+        assert steps == int(ref["steps"].astype(np.int64).sum())
+
+
 # ---- 4. GPU against GPU: the screen trace's own cones -----------------------------------------------------------------------
 def specular_dirs(planes, cam):
     """csrc/vct_trace.hip specular_dir in fp32: normalize(reflect(-E, N)), E = normalize(cam - P), N = planes 12-14."""

@@ -44,6 +44,8 @@
 // (vct_capi.hip: divisor_verified).
 #include <hip/hip_fp16.h>
 
+#include <type_traits>
+
 #include "../../include/vct.h"
 #include "vct_internal.h"
 #include "vct_texel.h"
@@ -125,6 +127,12 @@ __device__ __forceinline__ void wave_sync() {
 __device__ __forceinline__ unsigned long long ballot64(bool pred) {
     return __builtin_amdgcn_ballot_w64(pred);
 }
+// the sum of v over the 64 lanes, in every lane (the waves' executed-step counts; the self-test's mismatch count)
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
 
 // Dilated anchor coordinates come from a table: computing spread3() of three scalars took 41 scalar-unit instructions
 // per level sample, and the scalar pipe issues one instruction per 4 cycles per SIMD (tools/valu_bench.hip: s_add /
@@ -179,6 +187,63 @@ struct MarchStats {
     uint32_t reuse[2][4];
 };
 
+// ---- the pieces the three samplers below share: written once, the oracle's operations in the oracle's order ---------
+// A lane's trilinear footprint in a level: lower corner (unreduced integer coordinates) and filter fractions.
+struct Footprint { int i0, j0, k0; float a, b, c; };
+__device__ __forceinline__ Footprint footprint_of(const VctLevelRef lv, float ux, float uy, float uz) {
+    const float fN = lv.fN;
+    // ux * fN is exact (power of two), so the fused form is the oracle's (ux*fN) - 0.5f bit for bit
+    const float u = fmaf(ux, fN, -0.5f), v = fmaf(uy, fN, -0.5f), w = fmaf(uz, fN, -0.5f);
+    const float fu = floorf(u), fv = floorf(v), fw = floorf(w);
+    const float a = u - fu, b = v - fv, c = w - fw;
+    return {(int)fu, (int)fv, (int)fw, a, b, c};
+}
+// The cooperative 4x4x4 block is anchored one texel below the footprint of the tile's centre pixel (lane 27) if that
+// lane is live, else of the first live lane.  `am` = ballot of the live lanes, not empty.
+struct Anchor { int x, y, z; };
+__device__ __forceinline__ int anchor_lane(unsigned long long am) {
+    return ((am >> 27) & 1ull) ? 27 : (int)__ffsll((long long)am) - 1;
+}
+__device__ __forceinline__ Anchor anchor_of(const Footprint& f, int src) {
+    return {__builtin_amdgcn_readlane(f.i0, src) - 1, __builtin_amdgcn_readlane(f.j0, src) - 1,
+            __builtin_amdgcn_readlane(f.k0, src) - 1};
+}
+// Where this lane's footprint starts inside the block at `an`, and the live lanes whose footprint does not lie inside
+// it (an offset outside 0..2, negative ones included: the compare is unsigned).  `out` == 0: the block serves the wave.
+struct BlockFit { int dx, dy, dz; unsigned long long out; };
+__device__ __forceinline__ BlockFit block_fit(const Footprint& f, const Anchor an, unsigned long long am) {
+    const int dx = f.i0 - an.x, dy = f.j0 - an.y, dz = f.k0 - an.z;
+    const uint32_t far = max(max((uint32_t)dx, (uint32_t)dy), (uint32_t)dz);
+    return {dx, dy, dz, ballot64(far > 2u) & am};
+}
+// Index inside the level of the block texel this lane fetches: texel (l&3, (l>>2)&3, l>>4) of the block at `an`.
+// Texels are addressed by their Morton INDEX inside the level (< 2^30): the dilated-integer arithmetic yields it
+// directly, and the level is a texel buffer whose structured load takes the index (no shift, no 64-bit address add).
+template <bool WRAP>
+__device__ __forceinline__ uint32_t block_texel_index(const VctLevelRef lv, const Anchor an, const LaneBlock& lb) {
+    if (WRAP) {
+        // scalar unit: dilate the anchor; vector unit: one dilated add per axis
+        const uint32_t MX = lv.mask_x, MY = MX << 1, MZ = MX << 2;
+        const uint32_t m4 = (uint32_t)lv.m << 2;
+        // (the table holds spread3(i) << 2: the scalar unit shifts it into place -- one shift for two of the axes, as before)
+        const uint32_t sax = spread_byte(lb.lut, an.x, m4) >> 2;
+        const uint32_t say = spread_byte(lb.lut, an.y, m4) >> 1;
+        const uint32_t saz = spread_byte(lb.lut, an.z, m4);
+        return (((sax | ~MX) + lb.sbx) & MX) | (((say | ~MY) + lb.sby) & MY) | (((saz | ~MZ) + lb.sbz) & MZ);
+    } else {
+        const int x = min(max(an.x + (lb.lane & 3), 0), lv.m);
+        const int y = min(max(an.y + ((lb.lane >> 2) & 3), 0), lv.m);
+        const int z = min(max(an.z + (lb.lane >> 4), 0), lv.m);
+        return vct_morton3((uint32_t)x, (uint32_t)y, (uint32_t)z);
+    }
+}
+// float4 of a slab at which a lane's footprint starts (gather_block's q); a lane that is not live reads the block's first
+__device__ __forceinline__ int block_slot(bool act, int dx, int dy, int dz) { return act ? (dz * 4 + dy) * 4 + dx : 0; }
+// (channels are >= +0: the block is empty iff no channel of any lane's texel has a bit set)
+__device__ __forceinline__ unsigned long long block_texel_mask(const float4 d) {
+    return ballot64((__float_as_uint(d.x) | __float_as_uint(d.y) | __float_as_uint(d.z) | __float_as_uint(d.w)) != 0u);
+}
+
 // Block reuse (round 7).  A march step usually samples a level the wave sampled one step earlier, at most a texel or two
 // further on: a diffuse cone's LOD grows 1.1 per step, so the lower level of a step is the upper level of the step before;
 // a specular cone stays on one pair of levels for several steps.  A 4x4x4 block covers three footprint origins per axis
@@ -201,9 +266,9 @@ struct BlockDesc {
     // the level (VctLevelRef::off: a multiple of 8, every level in front of it holds a power of 8 texels >= 8) | 1 when
     // the block is in the slab; without the bit the block is all zero and the slab holds nothing.  Or VCT_NO_BLOCK.
     uint32_t id;
-    int ax, ay, az;     // anchor, in the sampler's unreduced integer coordinates
+    Anchor an;          // in the sampler's unreduced integer coordinates
 };
-__device__ __forceinline__ BlockDesc no_block() { return {VCT_NO_BLOCK, 0, 0, 0}; }
+__device__ __forceinline__ BlockDesc no_block() { return {VCT_NO_BLOCK, {0, 0, 0}}; }
 
 // the trilinear fold of a lane's 8 texels out of a block in LDS; q = the lane's lower corner in the slab
 __device__ __forceinline__ F4 gather_block(const float4* q, float a, float b, float c) {
@@ -229,9 +294,56 @@ __device__ __forceinline__ F4 gather_block(const float4* q, float a, float b, fl
     return r;
 }
 
+// VCT_STATS only: the census of a per-lane sample -- would one block anchored at the live footprints' minimum serve it,
+// how many blocks a greedy multi-anchor cover needs, and whether sharing inside 2x2-pixel quads or 4x4-pixel quadrants
+// would (MarchStats: fallback*, greedy*, quads*, quadrants*).
+__device__ __forceinline__ void per_lane_census(MarchStats& ms, const Footprint& f, bool act, unsigned long long am, int lane) {
+    const int i0 = f.i0, j0 = f.j0, k0 = f.k0;
+    ++ms.fallback; ms.fallback_lanes += (uint32_t)__popcll(am);
+    int lo[3] = {act ? i0 : 0x7fffffff, act ? j0 : 0x7fffffff, act ? k0 : 0x7fffffff};
+    int hi[3] = {act ? i0 : -0x7fffffff, act ? j0 : -0x7fffffff, act ? k0 : -0x7fffffff};
+    for (int off = 32; off > 0; off >>= 1)
+        for (int q = 0; q < 3; ++q) { lo[q] = min(lo[q], __shfl_xor(lo[q], off)); hi[q] = max(hi[q], __shfl_xor(hi[q], off)); }
+    if (hi[0] - lo[0] <= 2 && hi[1] - lo[1] <= 2 && hi[2] - lo[2] <= 2) ++ms.fallback_fits;
+    // greedy cover: blocks anchored at the first lane not yet covered
+    unsigned long long pending = am;
+    int nb = 0;
+    while (pending != 0ull && nb < 16) {
+        const BlockFit fit = block_fit(f, anchor_of(f, (int)__ffsll((long long)pending) - 1), ~0ull);
+        pending &= fit.out;
+        ++nb;
+    }
+    // the same range test inside 2x2-pixel quads (lanes l, l^1, l^8, l^9) and 4x4-pixel quadrants (+ l^2, l^16, ...)
+    int qlo[3] = {act ? i0 : 0x7fffffff, act ? j0 : 0x7fffffff, act ? k0 : 0x7fffffff};
+    int qhi[3] = {act ? i0 : -0x7fffffff, act ? j0 : -0x7fffffff, act ? k0 : -0x7fffffff};
+    bool qany = act;
+    auto widen = [&](int off) {
+        for (int q = 0; q < 3; ++q) { qlo[q] = min(qlo[q], __shfl_xor(qlo[q], off)); qhi[q] = max(qhi[q], __shfl_xor(qhi[q], off)); }
+        qany = qany || (__shfl_xor((int)qany, off) != 0);
+    };
+    widen(1); widen(8);
+    const int span2 = max(max(qhi[0] - qlo[0], qhi[1] - qlo[1]), qhi[2] - qlo[2]);
+    const bool lead2 = (lane & 9) == 0;                      // one lane per quad
+    ms.quads_live += (uint32_t)__popcll(ballot64(lead2 && qany));
+    ms.quads_fit333 += (uint32_t)__popcll(ballot64(lead2 && qany && span2 <= 1));
+    ms.quads_same += (uint32_t)__popcll(ballot64(lead2 && qany && span2 == 0));
+    widen(2); widen(16);
+    const int span4 = max(max(qhi[0] - qlo[0], qhi[1] - qlo[1]), qhi[2] - qlo[2]);
+    const bool lead4 = (lane & 27) == 0;                     // one lane per quadrant
+    ms.quadrants_live += (uint32_t)__popcll(ballot64(lead4 && qany));
+    ms.quadrants_fit444 += (uint32_t)__popcll(ballot64(lead4 && qany && span4 <= 2));
+    ms.greedy_blocks += (uint32_t)nb;
+    if (nb <= 2) ++ms.greedy_le2;
+    if (nb <= 3) ++ms.greedy_le3;
+    if (nb <= 4) ++ms.greedy_le4;
+}
+
 // [GL] tri(level): trilinear, texel centres, REPEAT (or clamp).  `level` is wave-uniform; must be
 // called in wave-uniform control flow with at least one lane `act`.  Lanes without `act` help
 // fetch the block and return garbage-free zeros / unused values.
+// Over the shared pieces above: the choice between the cooperative block (COOP, every live footprint inside the block
+// at the anchor) and the per-lane gather, the per-lane gather itself (texel loads in phases of 2 + 2 + 4, or one
+// footprint record with CELLS), and where the issue priority (PRIO) is raised and dropped.
 template <bool WRAP, bool COOP, bool LOOSE = false, bool CELLS = false, bool PRIO = false>
 __device__ __forceinline__ F4 sample_level(const uint32_t* __restrict__ chain, const VctLevelRef lv,
                                            float ux, float uy, float uz, bool act, unsigned long long am,
@@ -248,103 +360,28 @@ __device__ __forceinline__ F4 sample_level(const uint32_t* __restrict__ chain, c
     // a wave-uniform flag cost the default kernel 60 B of scratch per lane.
     if (PRIO) __builtin_amdgcn_s_setprio(1);
     const int m = lv.m;
-    const float fN = lv.fN;
-    // ux * fN is exact (power of two), so the fused form is the oracle's (ux*fN) - 0.5f bit for bit
-    const float u = fmaf(ux, fN, -0.5f), v = fmaf(uy, fN, -0.5f), w = fmaf(uz, fN, -0.5f);
-    const float fu = floorf(u), fv = floorf(v), fw = floorf(w);
-    const float a = u - fu, b = v - fv, c = w - fw;
-    const int i0 = (int)fu, j0 = (int)fv, k0 = (int)fw;
-    // Texels are addressed by their Morton INDEX inside the level (< 2^30): the dilated-integer arithmetic yields it
-    // directly, and the level is a texel buffer whose structured load takes the index (no shift, no 64-bit address add).
+    const Footprint f = footprint_of(lv, ux, uy, uz);
+    const float a = f.a, b = f.b, c = f.c;
+    const int i0 = f.i0, j0 = f.j0, k0 = f.k0;
     const uint32_t* __restrict__ base = chain + lv.off;
     const uint32_t MX = lv.mask_x, MY = MX << 1, MZ = MX << 2;
     const vct_v4i32 tb = level_texel_buffer(base);
 
     F4 r = {0.0f, 0.0f, 0.0f, 0.0f};
-    bool coop = false;
-    int ax = 0, ay = 0, az = 0, dx = 0, dy = 0, dz = 0;
-    if (COOP) {
-        // anchor = footprint of the tile's centre pixel (lane 27) if it is live, else the first live lane
-        const int src = ((am >> 27) & 1ull) ? 27 : (int)__ffsll((long long)am) - 1;
-        ax = __builtin_amdgcn_readlane(i0, src) - 1;
-        ay = __builtin_amdgcn_readlane(j0, src) - 1;
-        az = __builtin_amdgcn_readlane(k0, src) - 1;
-        dx = i0 - ax; dy = j0 - ay; dz = k0 - az;
-        const uint32_t far = max(max((uint32_t)dx, (uint32_t)dy), (uint32_t)dz);
-        const unsigned long long out = ballot64(far > 2u) & am;
-        coop = out == 0ull;
-    }
-    if (COOP && coop) {
-        uint32_t idx;
-        if (WRAP) {
-            // scalar unit: dilate the anchor; vector unit: one dilated add per axis
-            const uint32_t m4 = (uint32_t)m << 2;
-            // (the table holds spread3(i) << 2: the scalar unit shifts it into place -- one shift for two of the axes, as before)
-            const uint32_t sax = spread_byte(lb.lut, ax, m4) >> 2;
-            const uint32_t say = spread_byte(lb.lut, ay, m4) >> 1;
-            const uint32_t saz = spread_byte(lb.lut, az, m4);
-            idx = (((sax | ~MX) + lb.sbx) & MX) | (((say | ~MY) + lb.sby) & MY) |
-                  (((saz | ~MZ) + lb.sbz) & MZ);
-        } else {
-            const int x = min(max(ax + (lb.lane & 3), 0), m);
-            const int y = min(max(ay + ((lb.lane >> 2) & 3), 0), m);
-            const int z = min(max(az + (lb.lane >> 4), 0), m);
-            idx = vct_morton3((uint32_t)x, (uint32_t)y, (uint32_t)z);
-        }
-        const float4 d = texel_f32(tb, idx);
+    const Anchor an = anchor_of(f, anchor_lane(am));          // (without COOP nothing reads these two: compiled away)
+    const BlockFit fit = block_fit(f, an, am);
+    if (COOP && fit.out == 0ull) {
+        const float4 d = texel_f32(tb, block_texel_index<WRAP>(lv, an, lb));
         if (PRIO) __builtin_amdgcn_s_setprio(0);
-        // (channels are >= +0: the block is empty iff no channel has a bit set)
-        const bool any_texel = ballot64((__float_as_uint(d.x) | __float_as_uint(d.y) | __float_as_uint(d.z) | __float_as_uint(d.w)) != 0u) != 0ull;
+        const bool any_texel = block_texel_mask(d) != 0ull;
         if (VCT_STATS) { if (any_texel) ++ms.coop_hit; else ++ms.coop_zero; }
         if (any_texel) {     // all 64 texels zero: every footprint sums to exactly +0
             blk[lb.lane] = d;
             wave_sync();
-            const int slot = act ? (dz * 4 + dy) * 4 + dx : 0;
-            r = gather_block(blk + slot, a, b, c);
+            r = gather_block(blk + block_slot(act, fit.dx, fit.dy, fit.dz), a, b, c);
         }
     } else {
-      if (VCT_STATS) {
-          ++ms.fallback; ms.fallback_lanes += (uint32_t)__popcll(am);
-          int lo[3] = {act ? i0 : 0x7fffffff, act ? j0 : 0x7fffffff, act ? k0 : 0x7fffffff};
-          int hi[3] = {act ? i0 : -0x7fffffff, act ? j0 : -0x7fffffff, act ? k0 : -0x7fffffff};
-          for (int off = 32; off > 0; off >>= 1)
-              for (int q = 0; q < 3; ++q) { lo[q] = min(lo[q], __shfl_xor(lo[q], off)); hi[q] = max(hi[q], __shfl_xor(hi[q], off)); }
-          if (hi[0] - lo[0] <= 2 && hi[1] - lo[1] <= 2 && hi[2] - lo[2] <= 2) ++ms.fallback_fits;
-          // greedy cover: blocks anchored at the first lane not yet covered
-          unsigned long long pending = am;
-          int nb = 0;
-          while (pending != 0ull && nb < 16) {
-              const int src = (int)__ffsll((long long)pending) - 1;
-              const int bx = __builtin_amdgcn_readlane(i0, src) - 1, by = __builtin_amdgcn_readlane(j0, src) - 1,
-                        bz = __builtin_amdgcn_readlane(k0, src) - 1;
-              const bool in = (uint32_t)(i0 - bx) <= 2u && (uint32_t)(j0 - by) <= 2u && (uint32_t)(k0 - bz) <= 2u;
-              pending &= ~ballot64(in);
-              ++nb;
-          }
-          // the same range test inside 2x2-pixel quads (lanes l, l^1, l^8, l^9) and 4x4-pixel quadrants (+ l^2, l^16, ...)
-          int qlo[3] = {act ? i0 : 0x7fffffff, act ? j0 : 0x7fffffff, act ? k0 : 0x7fffffff};
-          int qhi[3] = {act ? i0 : -0x7fffffff, act ? j0 : -0x7fffffff, act ? k0 : -0x7fffffff};
-          bool qany = act;
-          auto widen = [&](int off) {
-              for (int q = 0; q < 3; ++q) { qlo[q] = min(qlo[q], __shfl_xor(qlo[q], off)); qhi[q] = max(qhi[q], __shfl_xor(qhi[q], off)); }
-              qany = qany || (__shfl_xor((int)qany, off) != 0);
-          };
-          widen(1); widen(8);
-          const int span2 = max(max(qhi[0] - qlo[0], qhi[1] - qlo[1]), qhi[2] - qlo[2]);
-          const bool lead2 = (lb.lane & 9) == 0;                      // one lane per quad
-          ms.quads_live += (uint32_t)__popcll(ballot64(lead2 && qany));
-          ms.quads_fit333 += (uint32_t)__popcll(ballot64(lead2 && qany && span2 <= 1));
-          ms.quads_same += (uint32_t)__popcll(ballot64(lead2 && qany && span2 == 0));
-          widen(2); widen(16);
-          const int span4 = max(max(qhi[0] - qlo[0], qhi[1] - qlo[1]), qhi[2] - qlo[2]);
-          const bool lead4 = (lb.lane & 27) == 0;                     // one lane per quadrant
-          ms.quadrants_live += (uint32_t)__popcll(ballot64(lead4 && qany));
-          ms.quadrants_fit444 += (uint32_t)__popcll(ballot64(lead4 && qany && span4 <= 2));
-          ms.greedy_blocks += (uint32_t)nb;
-          if (nb <= 2) ++ms.greedy_le2;
-          if (nb <= 3) ++ms.greedy_le3;
-          if (nb <= 4) ++ms.greedy_le4;
-      }
+      if (VCT_STATS) per_lane_census(ms, f, act, am, lb.lane);
       if (act) {
         uint32_t mx0, mx1, my0, my1, mz0, mz1;
         if (WRAP) {
@@ -451,6 +488,8 @@ __device__ __forceinline__ F4 sample_level(const uint32_t* __restrict__ chain, c
 // The same sample with block reuse (BlockDesc above): cooperative, exact, no footprint records.  `blk` is the wave's
 // FIRST slab whichever level of the step this is; SLAB says which slab this sample fills (0: blk, 1: blk + 64) and
 // `held` describes the block in the second one.
+// Over the shared pieces: the fit test runs against the held block first and against a fresh anchor only when that
+// fails, and a fresh block of the second slab becomes the held one.
 template <bool WRAP, bool LOOSE, bool PRIO, int SLAB>
 __device__ __forceinline__ F4 sample_level_reuse(const uint32_t* __restrict__ chain, const VctLevelRef lv,
                                                  float ux, float uy, float uz, bool act, unsigned long long am,
@@ -458,12 +497,7 @@ __device__ __forceinline__ F4 sample_level_reuse(const uint32_t* __restrict__ ch
                                                  BlockDesc& held) {
     // (GL_REPEAT only: k_trace_tile_split switches the path off in clamp mode)
     if (PRIO) __builtin_amdgcn_s_setprio(1);
-    const int m = lv.m;
-    const float fN = lv.fN;
-    const float u = fmaf(ux, fN, -0.5f), v = fmaf(uy, fN, -0.5f), w = fmaf(uz, fN, -0.5f);
-    const float fu = floorf(u), fv = floorf(v), fw = floorf(w);
-    const float a = u - fu, b = v - fv, c = w - fw;
-    const int i0 = (int)fu, j0 = (int)fv, k0 = (int)fw;
+    const Footprint f = footprint_of(lv, ux, uy, uz);
     // how the sample is served -- an integer, not flags: wave-uniform integers stay in one SGPR, while booleans merged
     // across branches become lane masks.  0: by no block (yet), 1: by an all-zero block, 2: by the block of the wave's
     // slabs in which this lane's footprint starts at float4 `at`
@@ -471,55 +505,40 @@ __device__ __forceinline__ F4 sample_level_reuse(const uint32_t* __restrict__ ch
     // the second slab holds a block of this level: compared on the scalar unit, a sample without one pays nothing more
     if ((held.id & ~1u) == lv.off) {
         const BlockDesc cd = held;
-        const int dx = i0 - cd.ax, dy = j0 - cd.ay, dz = k0 - cd.az;
-        const uint32_t far = max(max((uint32_t)dx, (uint32_t)dy), (uint32_t)dz);
-        const unsigned long long out = ballot64(far > 2u) & am;
+        const BlockFit fit = block_fit(f, cd.an, am);
         if (VCT_STATS) {
-            const int src = ((am >> 27) & 1ull) ? 27 : (int)__ffsll((long long)am) - 1;
+            const Anchor fresh = anchor_of(f, anchor_lane(am));
             ++ms.reuse[SLAB][0];
-            if (out == 0ull) { ++ms.reuse[SLAB][1]; if (!(cd.id & 1u)) ++ms.reuse[SLAB][2]; }
-            if (__builtin_amdgcn_readlane(i0, src) - 1 == cd.ax && __builtin_amdgcn_readlane(j0, src) - 1 == cd.ay &&
-                __builtin_amdgcn_readlane(k0, src) - 1 == cd.az) ++ms.reuse[SLAB][3];
+            if (fit.out == 0ull) { ++ms.reuse[SLAB][1]; if (!(cd.id & 1u)) ++ms.reuse[SLAB][2]; }
+            if (fresh.x == cd.an.x && fresh.y == cd.an.y && fresh.z == cd.an.z) ++ms.reuse[SLAB][3];
         }
-        if (out == 0ull) {
+        if (fit.out == 0ull) {
             // every live footprint lies inside it: the block is in LDS already, or known to be all zero -- nothing to fetch
             if (PRIO) __builtin_amdgcn_s_setprio(0);
             mode = 1 + (int)(cd.id & 1u);
-            at = (act ? (dz * 4 + dy) * 4 + dx : 0) + 64;
+            at = block_slot(act, fit.dx, fit.dy, fit.dz) + 64;
         }
     }
     if (mode == 0) {
         // sample_level's cooperative block, into this sample's slab
-        const int src = ((am >> 27) & 1ull) ? 27 : (int)__ffsll((long long)am) - 1;
-        const int ax = __builtin_amdgcn_readlane(i0, src) - 1;
-        const int ay = __builtin_amdgcn_readlane(j0, src) - 1;
-        const int az = __builtin_amdgcn_readlane(k0, src) - 1;
-        const int dx = i0 - ax, dy = j0 - ay, dz = k0 - az;
-        const uint32_t far = max(max((uint32_t)dx, (uint32_t)dy), (uint32_t)dz);
-        const unsigned long long out = ballot64(far > 2u) & am;
-        if (out == 0ull) {
-            const uint32_t MX = lv.mask_x, MY = MX << 1, MZ = MX << 2;
-            // (GL_REPEAT only: in clamp mode the kernels sample without reuse)
-            const uint32_t m4 = (uint32_t)m << 2;
-            const uint32_t sax = spread_byte(lb.lut, ax, m4) >> 2;
-            const uint32_t say = spread_byte(lb.lut, ay, m4) >> 1;
-            const uint32_t saz = spread_byte(lb.lut, az, m4);
-            const uint32_t idx = (((sax | ~MX) + lb.sbx) & MX) | (((say | ~MY) + lb.sby) & MY) |
-                                 (((saz | ~MZ) + lb.sbz) & MZ);
+        const Anchor an = anchor_of(f, anchor_lane(am));
+        const BlockFit fit = block_fit(f, an, am);
+        if (fit.out == 0ull) {
+            const uint32_t idx = block_texel_index<true>(lv, an, lb);
             const float4 d = texel_f32(level_texel_buffer(chain + lv.off), idx);
             if (PRIO) __builtin_amdgcn_s_setprio(0);
-            const unsigned long long any_texel = ballot64((__float_as_uint(d.x) | __float_as_uint(d.y) | __float_as_uint(d.z) | __float_as_uint(d.w)) != 0u);
+            const unsigned long long any_texel = block_texel_mask(d);
             if (VCT_STATS) { if (any_texel != 0ull) ++ms.coop_hit; else ++ms.coop_zero; }
             mode = any_texel != 0ull ? 2 : 1;
-            if (SLAB == 1) held = {lv.off | (uint32_t)(mode - 1), ax, ay, az};
+            if (SLAB == 1) held = {lv.off | (uint32_t)(mode - 1), an};
             if (mode == 2) {
                 blk[SLAB * 64 + lb.lane] = d;
                 wave_sync();
-                at = (act ? (dz * 4 + dy) * 4 + dx : 0) + SLAB * 64;
+                at = block_slot(act, fit.dx, fit.dy, fit.dz) + SLAB * 64;
             }
         }
     }
-    if (mode == 2) return gather_block(blk + at, a, b, c);
+    if (mode == 2) return gather_block(blk + at, f.a, f.b, f.c);
     if (mode == 1) return {0.0f, 0.0f, 0.0f, 0.0f};     // all 64 texels zero: every footprint sums to exactly +0
     // incoherent footprints: the per-lane gather, which leaves the slabs and the descriptor alone
     return sample_level<WRAP, false, LOOSE, false, PRIO>(chain, lv, ux, uy, uz, act, am, blk, lb, ms);
@@ -543,6 +562,11 @@ __device__ __forceinline__ F4 sample_step_level(const VctTraceParams& p, const V
 // of an axis depends on the sign of that direction component, which is per lane: when the live
 // lanes disagree the axis is sampled once per sign with the lanes split by mask (rare: a tile's
 // cones are near-parallel), so sample_level always sees a wave-uniform chain.
+// Over the shared pieces (footprint_of, anchor_of, block_fit, block_texel_index, block_slot, gather_block) its
+// cooperative GL_REPEAT path adds: one set-up for all six chains, which share their geometry; per axis one or two
+// block loads by the lanes' signs, decoded into the slab of the sign (blk, or blk + p.aniso_alt_slab); and the dir^2
+// weighting of the three gathers.  Footprints that do not fit one block, clamp mode and the per-lane sampler go
+// through sample_level once per axis and sign.
 struct AnisoCone {
     float wx, wy, wz;       // dir.x^2, dir.y^2, dir.z^2
     bool nx, ny, nz;        // component not >= 0: the chain pre-integrated towards -axis
@@ -559,34 +583,14 @@ __device__ __forceinline__ F4 sample_aniso(const VctTraceParams& p, const VctLev
     F4 tx, ty, tz;
     bool done = false;
     if (COOP && WRAP) {
-        // The six directional chains have the same geometry, so coordinates, anchor, cooperative
-        // test, Morton index, LDS slot and trilinear weights are computed once for all of them; only
-        // the texel, its decode and the 8-texel gather are per chain.  An axis whose live lanes
-        // disagree on the sign (cones along a coordinate axis have components ~0 of either sign)
-        // fetches both of its chains into two slabs and every lane gathers from the one its sign
-        // selects.
-        const int mm = lv.m;
-        const float fN = lv.fN;
-        const float u = fmaf(ux, fN, -0.5f), v = fmaf(uy, fN, -0.5f), w = fmaf(uz, fN, -0.5f);
-        const float fu = floorf(u), fv = floorf(v), fw = floorf(w);
-        const float a = u - fu, b = v - fv, c = w - fw;
-        const int i0 = (int)fu, j0 = (int)fv, k0 = (int)fw;
-        const int src = ((m >> 27) & 1ull) ? 27 : (int)__ffsll((long long)m) - 1;
-        const int ax = __builtin_amdgcn_readlane(i0, src) - 1;
-        const int ay = __builtin_amdgcn_readlane(j0, src) - 1;
-        const int az = __builtin_amdgcn_readlane(k0, src) - 1;
-        const int dx = i0 - ax, dy = j0 - ay, dz = k0 - az;
-        const uint32_t far = max(max((uint32_t)dx, (uint32_t)dy), (uint32_t)dz);
-        if ((ballot64(far > 2u) & m) == 0ull) {
+        // An axis whose live lanes disagree on the sign (cones along a coordinate axis have components ~0 of either
+        // sign) fetches both of its chains into two slabs and every lane gathers from the one its sign selects.
+        const Footprint f = footprint_of(lv, ux, uy, uz);
+        const Anchor an = anchor_of(f, anchor_lane(m));
+        const BlockFit fit = block_fit(f, an, m);
+        if (fit.out == 0ull) {
             done = true;
-            const uint32_t MX = lv.mask_x, MY = MX << 1, MZ = MX << 2;      // texel indices, as in sample_level
-            const uint32_t m4 = (uint32_t)mm << 2;
-            const SpreadLut lut = (SpreadLut)p.spread_lut;
-            const uint32_t sax = spread_byte(lut, ax, m4) >> 2;
-            const uint32_t say = spread_byte(lut, ay, m4) >> 1;
-            const uint32_t saz = spread_byte(lut, az, m4);
-            const uint32_t idx = (((sax | ~MX) + lb.sbx) & MX) | (((say | ~MY) + lb.sby) & MY) |
-                                 (((saz | ~MZ) + lb.sbz) & MZ);
+            const uint32_t idx = block_texel_index<true>(lv, an, lb);
             const unsigned long long mneg[3] = {mx, my, mz};
             const bool lneg[3] = {ac.nx, ac.ny, ac.nz};
             uint32_t tpos[3], tneg[3];
@@ -595,11 +599,7 @@ __device__ __forceinline__ F4 sample_aniso(const VctTraceParams& p, const VctLev
                 tpos[k] = mneg[k] != m ? (chain_of(2 * k) + lv.off)[idx] : 0u;          // some lane is >= 0
                 tneg[k] = mneg[k] != 0ull ? (chain_of(2 * k + 1) + lv.off)[idx] : 0u;   // some lane is < 0
             }
-            const int slot = act ? (dz * 4 + dy) * 4 + dx : 0;
-            const float a0 = 1.0f - a, b0 = 1.0f - b, c0 = 1.0f - c;
-            const float ab00 = a0 * b0, ab10 = a * b0, ab01 = a0 * b, ab11 = a * b;
-            const float w0 = ab00 * c0, w1 = ab10 * c0, w2 = ab01 * c0, w3 = ab11 * c0;
-            const float w4 = ab00 * c, w5 = ab10 * c, w6 = ab01 * c, w7 = ab11 * c;
+            const int slot = block_slot(act, fit.dx, fit.dy, fit.dz);
             float4* alt = p.aniso_alt_slab ? blk + p.aniso_alt_slab : blk;      // slab of the "towards -axis" chain
             F4 out3[3];
 #pragma unroll
@@ -615,17 +615,7 @@ __device__ __forceinline__ F4 sample_aniso(const VctTraceParams& p, const VctLev
                     if (mneg[k] != m) blk[lb.lane] = dec(tpos[k]);
                     if (mneg[k] != 0ull) alt[lb.lane] = dec(tneg[k]);
                     wave_sync();
-                    const float4* q = (lneg[k] ? alt : blk) + slot;
-                    const float4 t0 = q[0], t1 = q[1], t2 = q[4], t3v = q[5];
-                    const float4 t4 = q[16], t5 = q[17], t6 = q[20], t7 = q[21];
-                    wave_sync();
-#define VCT_ACC(ch)                                                                            \
-    r.ch = w0 * t0.ch;                                                                         \
-    r.ch = fmaf(w1, t1.ch, r.ch); r.ch = fmaf(w2, t2.ch, r.ch); r.ch = fmaf(w3, t3v.ch, r.ch); \
-    r.ch = fmaf(w4, t4.ch, r.ch); r.ch = fmaf(w5, t5.ch, r.ch); r.ch = fmaf(w6, t6.ch, r.ch);  \
-    r.ch = fmaf(w7, t7.ch, r.ch);
-                    VCT_ACC(x) VCT_ACC(y) VCT_ACC(z) VCT_ACC(w)
-#undef VCT_ACC
+                    r = gather_block((lneg[k] ? alt : blk) + slot, f.a, f.b, f.c);
                 }
                 out3[k] = r;
             }
@@ -856,6 +846,22 @@ __device__ __forceinline__ F4 fold_cone(F4 ind, int i, V4 c) {
     const float wgt = kConeWeights[i];
     return {fmaf(wgt, c.x, ind.x), fmaf(wgt, c.y, ind.y), fmaf(wgt, c.z, ind.z), fmaf(wgt, c.w, ind.w)};
 }
+// The diffuse gather of one point: the six cones of the frame (b0, b1, b2), one after the other, folded in cone order.
+// march(dir, st) marches one cone and leaves its step count in st; per_cone(i, cone, st) is the caller's business with
+// cone i (debug outputs).  `total` grows by the lane's executed steps.                            trace.fs:196-199
+template <class March, class PerCone>
+__device__ __forceinline__ F4 gather_six_cones(F3 b0, F3 b1, F3 b2, int& total, March march, PerCone per_cone) {
+    F4 ind = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll 1
+    for (int i = 0; i < 6; ++i) {
+        int st;
+        const F4 c = march(cone_dir(b0, b1, b2, i), st);
+        total += st;
+        ind = fold_cone(ind, i, c);
+        per_cone(i, c, st);
+    }
+    return ind;
+}
 // the specular cone runs along reflect(-E, N) with the bump normal N (planes 12-14)     trace.fs:217-218
 __device__ __forceinline__ F3 specular_dir(F3 P, F3 N, const float cam[3]) {
     const F3 E = normalize3(f3(cam[0] - P.x, cam[1] - P.y, cam[2] - P.z));              // :181
@@ -1021,17 +1027,10 @@ k_trace_tile(const VctTraceParams p) {
     F3 start, k0, k1, k2;
     cone_frame_from_gbuffer(gb, p.vs, start, k0, k1, k2);
 
-    F4 ind = {0.0f, 0.0f, 0.0f, 0.0f};
     int total = 0;
-#pragma unroll 1
-    for (int i = 0; i < 6; ++i) {                                           // :196-199
-        int st;
-        const F4 c = cone_march<WRAP, FASTDIV, COOP>(p, alive, start, cone_dir(k0, k1, k2, i), p.steps_diffuse,
-                                                     p.n_diffuse, blk, lb, st, ms);
-        total += st;
-        ind = fold_cone(ind, i, c);
-        store_debug_cone(p, pixel_index, i, c, st, alive, in_frame);
-    }
+    const F4 ind = gather_six_cones(k0, k1, k2, total,
+        [&](F3 dir, int& st) { return cone_march<WRAP, FASTDIV, COOP>(p, alive, start, dir, p.steps_diffuse, p.n_diffuse, blk, lb, st, ms); },
+        [&](int i, F4 c, int st) { store_debug_cone(p, pixel_index, i, c, st, alive, in_frame); });
 
     // stage 2: the specular cone, from a fresh pointer: re-read instead of keeping planes live
     const float* gb2 = gbuf_ptr(fresh_lane());
@@ -1045,7 +1044,7 @@ k_trace_tile(const VctTraceParams p) {
     const float* gb3 = gbuf_ptr(fresh_lane());
     if (in_frame) composite<false>(p, gb3, ind, sc, alive, pixel_index, [] { return (size_t)0; });
     // executed-step count: wave reduction, stored into the tile's slot (a plain store: no atomic, nothing to clear)
-    for (int off = 32; off > 0; off >>= 1) total += __shfl_xor(total, off);
+    total = wave_sum(total);
     if (lane == 0) p.tile_steps[tile] = (uint32_t)total;
     flush_stats(p, ms, lane);
 }
@@ -1176,7 +1175,7 @@ k_trace_tile_split(const VctTraceParams p) {
         lds_cone[6][lane] = make_float4(sc.x, sc.y, sc.z, sc.w);
         store_debug_cone(p, pixel_index, 6, sc, st6, alive, in_frame);
     }
-    for (int off = 32; off > 0; off >>= 1) total += __shfl_xor(total, off);
+    total = wave_sum(total);
     if (lane == 0) atomicAdd(&lds_steps, total);          // LDS: the last arriver below stores the tile's total
     flush_stats(p, ms, lane, wave == VCT_SPLIT - 1);
 
@@ -1310,6 +1309,7 @@ k_point_march(const VctTraceParams p) {
             wave_marched += (uint32_t)__popcll(ballot64(alive));
         }
         if (WAVES == 2) __syncthreads();          // lds_cone is written again by the next round
+        // (spelt out, not wave_sum: through the helper the 16 instantiations hoist the lane arithmetic in another order)
         for (int off = 32; off > 0; off >>= 1) total += __shfl_xor(total, off);
         wave_steps += (unsigned long long)total;
     }
@@ -1362,6 +1362,8 @@ k_query_march(const VctTraceParams p, const VctQueryArgs q) {
             F3 start, k0, k1, k2;
             cone_frame(f3(r.v[0], r.v[1], r.v[2]), f3(r.v[3], r.v[4], r.v[5]), f3(r.v[6], r.v[7], r.v[8]),
                        f3(r.v[9], r.v[10], r.v[11]), p.vs, start, k0, k1, k2);
+            // (spelt out, not gather_six_cones: through the helper the sorted ambient-cube gather measured 0.8 % slower
+            // than the loop, outside the loop's own spread -- profiles/experiments/r13_trace_one_copy_ab.txt)
             F4 ind = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll 1
             for (int c = 0; c < 6; ++c) {
@@ -1387,8 +1389,7 @@ k_query_march(const VctTraceParams p, const VctQueryArgs q) {
                 if (DEBUG) q.out_steps[i] = (uint8_t)total;
             }
         }
-        for (int off = 32; off > 0; off >>= 1) total += __shfl_xor(total, off);
-        wave_steps += (unsigned long long)total;
+        wave_steps += (unsigned long long)wave_sum(total);
     }
     if (lane == 0 && wave_steps) atomicAdd(q.ctr + (blockIdx.x & (VCT_DR_COUNTERS - 1)), wave_steps);
     flush_stats(p, ms, lane);
@@ -1507,9 +1508,9 @@ k_diffuse_resolve(const VctTraceParams p) {
 //                   same cone_march as the screen trace (voxels of a locally flat surface trace
 //                   near-parallel cones, so the cooperative sampler applies);
 //   k_bounce_bricks the same march per brick, only for bricks that did not fit the list.
-template <class March>
+template <bool WRAP, int FASTDIV>
 __device__ __forceinline__ void bounce_voxels(const VctTraceParams& p, bool alive, size_t vox, int& total_out,
-                                              March march) {
+                                              float4* __restrict__ blk, const LaneBlock& lb, MarchStats& ms) {
     const uint32_t* __restrict__ level0 = p.chain;          // level 0 starts the chain
     const float fV = (float)p.V;
     // attributes are pooled per touched brick; lanes without a voxel (alive == false) may point at a brick that
@@ -1527,15 +1528,10 @@ __device__ __forceinline__ void bounce_voxels(const VctTraceParams& p, bool aliv
     const F3 t = normalize3(cross3(helper, nrm));
     const F3 bt = cross3(nrm, t);
     const F3 start = cone_start(P, nrm, p.vs);
-    F4 ind = {0.0f, 0.0f, 0.0f, 0.0f};
     int total = 0;
-#pragma unroll 1
-    for (int c = 0; c < 6; ++c) {
-        int st;
-        const F4 cone = march(alive, start, cone_dir(t, bt, nrm, c), st);
-        total += st;
-        ind = fold_cone(ind, c, cone);
-    }
+    const F4 ind = gather_six_cones(t, bt, nrm, total,
+        [&](F3 dir, int& st) { return cone_march<WRAP, FASTDIV, true>(p, alive, start, dir, p.steps_diffuse, p.n_diffuse, blk, lb, st, ms); },
+        [](int, F4, int) {});
     if (alive) {
         const float occlusion = 1.0f - ind.w;
         const uint32_t r = vct_float_to_unorm8(unorm8(src & 0xffu) + unorm8(aq & 0xffu) * (occlusion * ind.x));
@@ -1545,8 +1541,7 @@ __device__ __forceinline__ void bounce_voxels(const VctTraceParams& p, bool aliv
     } else {
         total = 0;
     }
-    for (int off = 32; off > 0; off >>= 1) total += __shfl_xor(total, off);
-    total_out = total;
+    total_out = wave_sum(total);
 }
 
 #define VCT_BOUNCE_SETUP                                                     \
@@ -1656,9 +1651,7 @@ k_bounce_march(const VctTraceParams p) {
         const uint32_t first = __builtin_amdgcn_readfirstlane(e);
         const size_t vox = alive ? e : (first != 0xffffffffu ? first : 0u);
         int total;
-        bounce_voxels(p, alive, vox, total, [&](bool al, F3 start, F3 dir, int& st) {
-            return cone_march<WRAP, FASTDIV, true>(p, al, start, dir, p.steps_diffuse, p.n_diffuse, blk, lb, st, ms);
-        });
+        bounce_voxels<WRAP, FASTDIV>(p, alive, vox, total, blk, lb, ms);
         wave_steps += (unsigned long long)total;
     }
     if (lane == 0 && wave_steps)
@@ -1688,9 +1681,7 @@ k_bounce_bricks(const VctTraceParams p) {
                 const bool alive = base + lane < n;
                 const size_t vox = (size_t)b * 512 + (alive ? list[base + lane] : list[base]);
                 int total;
-                bounce_voxels(p, alive, vox, total, [&](bool al, F3 start, F3 dir, int& st) {
-                    return cone_march<WRAP, FASTDIV, true>(p, al, start, dir, p.steps_diffuse, p.n_diffuse, blk, lb, st, ms);
-                });
+                bounce_voxels<WRAP, FASTDIV>(p, alive, vox, total, blk, lb, ms);
                 wave_steps += (unsigned long long)total;
             }
             wave_sync();
@@ -1750,6 +1741,20 @@ k_compact_tiles(const VctTraceParams p) {
     for (int i = total + lane; i < nvt * 64; i += 64) p.vt_pix[(size_t)base * 64 + i] = 0xffffffffu;
 }
 
+// ---- launch dispatch: run-time parameters to template arguments, written once -----------------------------------------
+// f(std::true_type{}) or f(std::false_type{}): a run-time flag as a type, so that a generic lambda can name the
+// instantiation it launches (decltype(tag)::value)
+template <class F>
+auto with_flag(bool flag, F f) { return flag ? f(std::true_type{}) : f(std::false_type{}); }
+// f(WRAP tag, FASTDIV tag) of a launch: GL_REPEAT or clamp (p.wrap_repeat), and the division form of the march the step
+// tables were built for -- 1 the verified two-term product (p.fast_div), 0 the IEEE divide (div_const)
+template <class F>
+auto with_march_mode(const VctTraceParams& p, F f) {
+    return with_flag(p.wrap_repeat != 0, [&](auto wrap) {
+        return with_flag(p.fast_div != 0, [&](auto fast) { return f(wrap, std::integral_constant<int, decltype(fast)::value ? 1 : 0>{}); });
+    });
+}
+
 template <bool WRAP, int FASTDIV, bool COOP>
 hipError_t launch(const VctTraceParams& p, int blocks, hipStream_t s) {
     hipLaunchKernelGGL((k_trace_tile<WRAP, FASTDIV, COOP>), dim3(blocks),
@@ -1760,13 +1765,20 @@ hipError_t launch(const VctTraceParams& p, int blocks, hipStream_t s) {
 // the default kernel's dispatch: anisotropic chains, footprint records, whole-frame issue priority, or plain
 template <bool WRAP, int FASTDIV, bool COMP>
 void launch_split(const VctTraceParams& p, int blocks, hipStream_t s) {
-    if (p.aniso)
-        hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, true, false, false, false, COMP>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
-    else if (WRAP && p.cells_biased)
-        hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, true, false, COMP>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
-    else if (!p.spec_prio)     // a whole frame (or most of one): issue priority around the samples' loads (sample_level)
-        hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, true, COMP>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
-    else hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, false, COMP>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
+    const dim3 grid(blocks), block(64 * VCT_SPLIT);
+    if (p.aniso) {
+        hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, true, false, false, false, COMP>), grid, block, 0, s, p);
+        return;
+    }
+    if constexpr (WRAP) {     // the sampler reads footprint records under GL_REPEAT only: clamp mode has no such kernel
+        if (p.cells_biased) {
+            hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, true, false, COMP>), grid, block, 0, s, p);
+            return;
+        }
+    }
+    if (!p.spec_prio)     // a whole frame (or most of one): issue priority around the samples' loads (sample_level)
+        hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, true, COMP>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, false, COMP>), grid, block, 0, s, p);
 }
 
 // the four launches of a half-rate pass (p.dr_ind set: whole frame, default kernel, p.comp on); marks: see vct_launch_trace
@@ -1827,8 +1839,7 @@ hipError_t launch_v(const VctTraceParams& p, int variant, bool loose, hipStream_
     // lighting components (a mask other than VCT_SHOW_ALL, or per-component outputs): the COMP instantiation of the same
     // branch; the host refuses them with variants 1 .. 4, so only the branches below need one
     if (p.dr_ind) return launch_half_rate<WRAP, FASTDIV>(p, blocks, s, marks);
-    if (p.comp) launch_split<WRAP, FASTDIV, true>(p, blocks, s);
-    else launch_split<WRAP, FASTDIV, false>(p, blocks, s);
+    with_flag(p.comp != 0, [&](auto comp) { launch_split<WRAP, FASTDIV, decltype(comp)::value>(p, blocks, s); });
     return hipGetLastError();
 }
 
@@ -1848,7 +1859,7 @@ k_divide_selftest(float d, float r, float aux, unsigned long long* mismatches) {
         const float got = div_const<1>(x, aux, r);
         if (__float_as_uint(got) != __float_as_uint(want)) { ++bad; mismatches[1] = i; }
     }
-    for (int off = 32; off > 0; off >>= 1) bad += __shfl_xor(bad, off);
+    bad = wave_sum(bad);
     if ((threadIdx.x & 63) == 0 && bad) atomicAdd(mismatches, bad);
 }
 
@@ -1885,35 +1896,32 @@ template <bool WRAP, int FASTDIV>
 hipError_t launch_query(const VctTraceParams& p, const VctQueryArgs& q, int kind, hipStream_t s) {
     const uint32_t nitems = (q.n + 63u) >> 6;
     const dim3 grid(nitems < 256u * 24u ? nitems : 256u * 24u), block(64);          // at most the bounce's grid
-    const bool debug = q.out_cones || q.out_steps;
-    if (kind == VCT_QUERY_GATHER) {
-        if (debug) hipLaunchKernelGGL((k_query_march<WRAP, FASTDIV, VCT_QUERY_GATHER, true>), grid, block, 0, s, p, q);
-        else hipLaunchKernelGGL((k_query_march<WRAP, FASTDIV, VCT_QUERY_GATHER, false>), grid, block, 0, s, p, q);
-    } else {
-        if (debug) hipLaunchKernelGGL((k_query_march<WRAP, FASTDIV, VCT_QUERY_CONE, true>), grid, block, 0, s, p, q);
-        else hipLaunchKernelGGL((k_query_march<WRAP, FASTDIV, VCT_QUERY_CONE, false>), grid, block, 0, s, p, q);
-    }
+    with_flag(kind == VCT_QUERY_GATHER, [&](auto gather) {
+        with_flag(q.out_cones || q.out_steps, [&](auto debug) {
+            constexpr int KIND = decltype(gather)::value ? VCT_QUERY_GATHER : VCT_QUERY_CONE;
+            hipLaunchKernelGGL((k_query_march<WRAP, FASTDIV, KIND, decltype(debug)::value>), grid, block, 0, s, p, q);
+        });
+    });
     return hipGetLastError();
 }
 
 hipError_t vct_launch_query(const VctTraceParams& p, const VctQueryArgs& q, int kind, hipStream_t s) {
     if (q.n == 0u) return hipSuccess;
     if (p.aniso || p.cells_biased || (kind != VCT_QUERY_GATHER && kind != VCT_QUERY_CONE)) return hipErrorInvalidValue;
-    if (p.wrap_repeat) return p.fast_div ? launch_query<true, 1>(p, q, kind, s) : launch_query<true, 0>(p, q, kind, s);
-    return p.fast_div ? launch_query<false, 1>(p, q, kind, s) : launch_query<false, 0>(p, q, kind, s);
+    return with_march_mode(p, [&](auto wrap, auto fastdiv) {
+        return launch_query<decltype(wrap)::value, decltype(fastdiv)::value>(p, q, kind, s);
+    });
 }
 
 hipError_t vct_launch_query_keys(const VctTraceParams& p, const VctQueryArgs& q, int kind, uint32_t* keys, uint32_t* index, hipStream_t s) {
     if (q.n == 0u) return hipSuccess;
     const dim3 grid((q.n + 255u) / 256u), block(256);
-    const bool gather = kind == VCT_QUERY_GATHER;
-    if (p.wrap_repeat) {
-        if (gather) hipLaunchKernelGGL((k_query_keys<true, VCT_QUERY_GATHER>), grid, block, 0, s, p, q, keys, index);
-        else hipLaunchKernelGGL((k_query_keys<true, VCT_QUERY_CONE>), grid, block, 0, s, p, q, keys, index);
-    } else {
-        if (gather) hipLaunchKernelGGL((k_query_keys<false, VCT_QUERY_GATHER>), grid, block, 0, s, p, q, keys, index);
-        else hipLaunchKernelGGL((k_query_keys<false, VCT_QUERY_CONE>), grid, block, 0, s, p, q, keys, index);
-    }
+    with_flag(p.wrap_repeat != 0, [&](auto wrap) {     // (the keys divide by no table constant: one kernel for both forms)
+        with_flag(kind == VCT_QUERY_GATHER, [&](auto gather) {
+            constexpr int KIND = decltype(gather)::value ? VCT_QUERY_GATHER : VCT_QUERY_CONE;
+            hipLaunchKernelGGL((k_query_keys<decltype(wrap)::value, KIND>), grid, block, 0, s, p, q, keys, index);
+        });
+    });
     return hipGetLastError();
 }
 
@@ -1937,8 +1945,7 @@ hipError_t launch_bounce(const VctTraceParams& p, hipStream_t s) {
 
 hipError_t vct_launch_bounce(const VctTraceParams& p, hipStream_t s) {
     if (p.nbricks == 0) return hipSuccess;
-    if (p.wrap_repeat) return p.fast_div ? launch_bounce<true, true>(p, s) : launch_bounce<true, false>(p, s);
-    return p.fast_div ? launch_bounce<false, true>(p, s) : launch_bounce<false, false>(p, s);
+    return with_march_mode(p, [&](auto wrap, auto fastdiv) { return launch_bounce<decltype(wrap)::value, decltype(fastdiv)::value>(p, s); });
 }
 
 // The screen trace of tile rows [tile_row0, tile_row1) (every row_stride-th of them).  variant = config.trace_variant
@@ -1962,9 +1969,7 @@ hipError_t vct_launch_trace(const VctTraceParams& params, int variant, hipStream
     if (p.dr_ind && (variant != 0 || p.aniso || p.cells_biased || !p.comp || rstride > 1 || p.pack_rows || p.tile_row0 != 0 ||
                      p.tile_row1 != p.tiles_y))
         return hipErrorInvalidValue;
-    if (p.wrap_repeat)
-        return p.fast_div ? launch_v<true, true>(p, variant, loose, s, marks)
-                          : launch_v<true, false>(p, variant, loose, s, marks);
-    return p.fast_div ? launch_v<false, true>(p, variant, loose, s, marks)
-                      : launch_v<false, false>(p, variant, loose, s, marks);
+    return with_march_mode(p, [&](auto wrap, auto fastdiv) {
+        return launch_v<decltype(wrap)::value, decltype(fastdiv)::value>(p, variant, loose, s, marks);
+    });
 }

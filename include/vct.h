@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define VCT_ABI_VERSION 7
+#define VCT_ABI_VERSION 8
 
 typedef enum vct_status {
     VCT_OK = 0,
@@ -559,6 +559,64 @@ int vct_last_point_query_ms(vct_ctx* ctx, float* ms);
 int vct_upload_emission(vct_ctx* ctx, const float* emission /* [nmat][3] */);
 int vct_set_pixel_emission(vct_ctx* ctx, const float* planes, int32_t layout, int32_t location);
 int vct_download_pixel_emission(vct_ctx* ctx, float* planes /* linear [3][h*w] */);
+
+/* ---- per-material gloss: specular cone aperture and shininess by class ------------------------------------------------
+ * The reference hard-codes one gloss for every surface (S/VoxelConeTracing.fs:213 pow(.., 20), :218 aperture 0.07, with
+ * 0.105 left in a comment); config.tan_specular / config.shininess are that pair, one per context.  With gloss classes a
+ * polished floor, a brushed rail and a plaster wall reflect differently in ONE frame.
+ *   Gloss class        vct_gloss_class { tan_specular, shininess }, at most VCT_GLOSS_CLASSES_MAX = 8 per context.  For a
+ *                      pixel of class k the specular cone is Voxel_Cone_Tracing(reflect dir, classes[k].tan_specular) of
+ *                      fs:82-107,217-218 and `spec` of fs:213 is pow(max(dot(E,R),0), classes[k].shininess).  Nothing else
+ *                      of fs:165-227 changes, nor do the VCT_SHOW_* ternaries, the per-component outputs or the emission
+ *                      add.  The six diffuse cones, the voxel chain and the bounce know nothing of gloss.
+ *   Class of a pixel   every frame slot has a PIXEL-GLOSS PLANE of one byte per pixel, tiled [tile][64] on the device like
+ *                      the emission planes.  A byte b means class (b < nclasses ? b : 0): the plane is never used unclamped
+ *                      to form an address, lanes outside a ragged frame may hold anything, and discarded pixels keep the
+ *                      clear colour whatever their byte.
+ * A small set of classes (not a per-pixel float aperture) keeps what the march is built on: one wave-uniform step table
+ * per aperture.  The specular wave of a tile marches once per class present among its live pixels, the other lanes
+ * masked off; a pixel is marched exactly once, with its class's table, so its cone is the oracle's cone for that
+ * aperture bit for bit and does not depend on its neighbours' classes.
+ * vct_set_gloss_classes: builds one step table per class with the builder of config.tan_specular's table (VCT_MAX_STEPS
+ * applies; with config.debug_outputs a table of more than 255 steps is refused) and allocates a zeroed plane for every
+ * frame slot -- a later second slot gets its own.  NULL or nclasses = 0 detaches: tables and planes are freed and the
+ * frame is again the frame of config.tan_specular / config.shininess, bit for bit, from the kernels launched today.
+ * While classes are attached those two config values are not used by screen traces (they still serve vct_cone_points
+ * aperture 1).  The context's one division verdict (vct_get_stage_counts [2]) covers the diffuse table, the specular
+ * table and every class table: one unverifiable divisor in any of them puts all march launches on the IEEE divide.  The
+ * first use of a new divisor pays the existing device check (about 2 ms, synchronous, cached per process).
+ * Contract: tan_specular finite and > 0, shininess finite and >= 0, 1 <= nclasses <= 8.  VCT_ERR_INVALID, the context
+ * keeping what it had: a value outside the contract; config.trace_variant 1 .. 4 (and vct_set_trace_variant refuses
+ * 1 .. 4 while classes are attached); config.anisotropic_mips; footprint records on (and vct_set_footprint_records(on)
+ * while classes are attached) -- the rule of the half-rate gather, so only the default kernel has a gloss form.
+ * vct_get_gloss_classes: the attached table (*nclasses = 0: none) and the march steps of each class's table; any of the
+ * three outputs may be NULL.
+ * vct_upload_material_gloss: mat_class[nmat], one class byte per material of the uploaded mesh; call after
+ * vct_upload_triangles, with the nmat of that call.  NULL detaches, and so does a new vct_upload_triangles.  With it
+ * attached (and classes attached, so that the slot has a plane) vct_render_gbuffer, vct_render_gbuffer_rows and
+ * vct_gi_pass write the selected slot's plane, in both visibility forms and in the flat and textured shade kernels:
+ * mat_class[material of the visible triangle] where a surface is visible, 0 where none is; the rows form touches its
+ * tile rows only.  A value >= nclasses is stored as given and read under the clamp rule above.
+ * vct_set_pixel_gloss / vct_download_pixel_gloss: the selected slot's plane for callers that bring their own G-buffer;
+ * layout VCT_GB_LINEAR [h*w] or VCT_GB_TILED [tile][64], location a vct_mem; copy semantics and stream ordering are
+ * those of vct_set_pixel_emission.  NULL zeroes the plane.  Both need classes attached (there is no plane otherwise).
+ * Every launch that marches the specular cone of a G-buffer takes the selected slot's plane: vct_trace and its slab,
+ * resident, rows and strided forms, vct_trace_current, the last launch of a half-rate pass, vct_gi_pass and a rank's
+ * vct_frame_step (each rank's G-buffer pass fills its own rows: nothing new travels between ranks).
+ * Point queries: vct_cone_points accepts aperture = VCT_APERTURE_GLOSS(k), k < nclasses, and marches with class k's
+ * table; any other value above 1 is VCT_ERR_INVALID.  Gathers are unchanged.
+ * vct_last_step_count, vct_last_row_steps and the debug outputs count and hold what was executed: column 6 of a pixel
+ * is its own class's march.
+ * Out of scope, both follow-ups: mapping an MTL file's Ns to an aperture and quantising a scene's materials into eight
+ * classes (that needs a definition nothing here can be checked against), and gloss textures. */
+#define VCT_GLOSS_CLASSES_MAX 8
+#define VCT_APERTURE_GLOSS(k) (2 + (k))
+typedef struct vct_gloss_class { float tan_specular, shininess; } vct_gloss_class;
+int vct_set_gloss_classes(vct_ctx* ctx, const vct_gloss_class* classes, int32_t nclasses);
+int vct_get_gloss_classes(const vct_ctx* ctx, vct_gloss_class out[8], int32_t* nclasses, int32_t steps[8]);
+int vct_upload_material_gloss(vct_ctx* ctx, const uint8_t* mat_class /* [nmat] */);
+int vct_set_pixel_gloss(vct_ctx* ctx, const uint8_t* classes, int32_t layout, int32_t location);
+int vct_download_pixel_gloss(vct_ctx* ctx, uint8_t* out /* linear [h*w] */);
 
 /* ---- two frames in flight (round 6) -----------------------------------------------------------------
  * The reference's Render() (VCT.h:146-190) issues GL commands; the driver starts frame k + 1 while frame k

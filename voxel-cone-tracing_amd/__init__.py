@@ -25,7 +25,7 @@ GB_PLANES = 23
 GB_LINEAR, GB_TILED = 0, 1
 MEM_HOST, MEM_DEVICE = 0, 1
 VOX_CONSERVATIVE_AVG, VOX_REFERENCE = 0, 1
-ABI_VERSION = 7
+ABI_VERSION = 8
 # lighting components (include/vct.h: the reference's Show* switches) and per-component outputs
 SHOW_DIFFUSE, SHOW_INDIRECT_DIFFUSE, SHOW_SPECULAR, SHOW_INDIRECT_SPECULAR, SHOW_AMBIENT_OCCLUSION = 1, 2, 4, 8, 16
 SHOW_ALL = 31
@@ -36,6 +36,14 @@ VOXVIEW_CURRENT, VOXVIEW_RADIANCE, VOXVIEW_ALBEDO, VOXVIEW_NORMAL = 0, 1, 2, 3
 QUERY_SORT_CELLS = 1
 POINT_QUERY_MAX = 1 << 26
 APERTURE_DIFFUSE, APERTURE_SPECULAR = 0, 1
+# per-material gloss (Context.set_gloss_classes)
+GLOSS_CLASSES_MAX = 8
+
+
+def APERTURE_GLOSS(k):
+    """aperture of cone_points that marches with gloss class k's step table (include/vct.h VCT_APERTURE_GLOSS)"""
+    return 2 + int(k)
+
 
 # every symbol include/vct.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
@@ -62,6 +70,8 @@ ABI_SYMBOLS = [
     "vct_render_voxels", "vct_last_voxel_view_ms",
     "vct_gather_points", "vct_cone_points", "vct_last_point_query", "vct_last_point_query_ms",
     "vct_upload_emission", "vct_set_pixel_emission", "vct_download_pixel_emission",
+    "vct_set_gloss_classes", "vct_get_gloss_classes", "vct_upload_material_gloss", "vct_set_pixel_gloss",
+    "vct_download_pixel_gloss",
 ]
 
 
@@ -75,6 +85,10 @@ class Config(C.Structure):
         ("wrap_repeat", C.c_int32), ("debug_outputs", C.c_int32), ("trace_variant", C.c_int32),
         ("voxel_attributes", C.c_int32), ("anisotropic_mips", C.c_int32), ("texture_mipmaps", C.c_int32),
     ]
+
+
+class GlossClass(C.Structure):
+    _fields_ = [("tan_specular", C.c_float), ("shininess", C.c_float)]
 
 
 class GBuffer(C.Structure):
@@ -172,6 +186,11 @@ _lib.vct_last_point_query_ms.argtypes = [C.c_void_p, C.c_void_p]
 _lib.vct_upload_emission.argtypes = [C.c_void_p, C.c_void_p]
 _lib.vct_set_pixel_emission.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
 _lib.vct_download_pixel_emission.argtypes = [C.c_void_p, C.c_void_p]
+_lib.vct_set_gloss_classes.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+_lib.vct_get_gloss_classes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.vct_upload_material_gloss.argtypes = [C.c_void_p, C.c_void_p]
+_lib.vct_set_pixel_gloss.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
+_lib.vct_download_pixel_gloss.argtypes = [C.c_void_p, C.c_void_p]
 _lib.vct_upload_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
 
 
@@ -370,6 +389,61 @@ class Context:
         """The selected slot's pixel-emission planes, float32 [3, h*w] (linear)."""
         out = np.zeros((3, self.cfg.width * self.cfg.height), np.float32)
         self._ck(_lib.vct_download_pixel_emission(self._h, _ptr(out)), "vct_download_pixel_emission")
+        return out
+
+    # --- per-material gloss (include/vct.h "per-material gloss")
+    def set_gloss_classes(self, classes):
+        """Gloss classes [(tan_specular, shininess), ...], 1 .. 8 of them; None or an empty list detaches.  Every frame
+        slot gets a zeroed pixel-gloss plane: class 0 everywhere until a G-buffer pass or set_pixel_gloss writes it."""
+        if classes is None or len(classes) == 0:
+            self._ck(_lib.vct_set_gloss_classes(self._h, None, 0), "vct_set_gloss_classes")
+            return
+        a = np.ascontiguousarray(classes, np.float32).reshape(-1, 2)
+        self._ck(_lib.vct_set_gloss_classes(self._h, _ptr(a), a.shape[0]), "vct_set_gloss_classes")
+
+    def get_gloss_classes(self):
+        """(classes float32 [n, 2], march steps int32 [n]) of the attached table; n = 0: none attached."""
+        out, n, steps = np.zeros((GLOSS_CLASSES_MAX, 2), np.float32), C.c_int32(), np.zeros(GLOSS_CLASSES_MAX, np.int32)
+        self._ck(_lib.vct_get_gloss_classes(self._h, _ptr(out), C.byref(n), _ptr(steps)), "vct_get_gloss_classes")
+        return out[:n.value].copy(), steps[:n.value].copy()
+
+    def upload_material_gloss(self, mat_class):
+        """Gloss class per material of the uploaded mesh, uint8 [nmat]; None detaches.  The G-buffer passes then write the
+        selected slot's pixel-gloss plane."""
+        if mat_class is None:
+            self._ck(_lib.vct_upload_material_gloss(self._h, None), "vct_upload_material_gloss")
+            return
+        m = np.ascontiguousarray(mat_class)
+        if m.dtype != np.uint8:
+            if m.size and (m.min() < 0 or m.max() > 255):
+                raise VctError("upload_material_gloss: classes are bytes (0 .. 255)")
+            m = m.astype(np.uint8)
+        m = m.reshape(-1)
+        nmat = getattr(self, "_nmat", None)
+        if nmat is not None and m.shape[0] != nmat:
+            raise VctError(f"upload_material_gloss: {m.shape[0]} entries, the uploaded mesh has {nmat} materials")
+        self._ck(_lib.vct_upload_material_gloss(self._h, _ptr(m)), "vct_upload_material_gloss")
+
+    def set_pixel_gloss(self, classes, layout=GB_LINEAR):
+        """Pixel-gloss plane of the selected frame slot: a uint8 array (linear [h*w] or tiled [tiles, 64]) or an int device
+        pointer; None zeroes the plane.  Needs gloss classes attached."""
+        if classes is None:
+            self._ck(_lib.vct_set_pixel_gloss(self._h, None, GB_LINEAR, MEM_HOST), "vct_set_pixel_gloss")
+            return
+        if isinstance(classes, int):
+            self._ck(_lib.vct_set_pixel_gloss(self._h, _ptr(classes), layout, MEM_DEVICE), "vct_set_pixel_gloss")
+            return
+        classes = np.ascontiguousarray(classes, np.uint8)
+        want = self.cfg.width * self.cfg.height if layout == GB_LINEAR else \
+            ((self.cfg.width + 7) // 8) * ((self.cfg.height + 7) // 8) * 64
+        if classes.size != want:
+            raise VctError(f"set_pixel_gloss: {classes.size} bytes, this layout of the frame has {want}")
+        self._ck(_lib.vct_set_pixel_gloss(self._h, _ptr(classes), layout, MEM_HOST), "vct_set_pixel_gloss")
+
+    def download_pixel_gloss(self):
+        """The selected slot's pixel-gloss plane, uint8 [h*w] (linear), bytes as stored (unclamped)."""
+        out = np.zeros(self.cfg.width * self.cfg.height, np.uint8)
+        self._ck(_lib.vct_download_pixel_gloss(self._h, _ptr(out)), "vct_download_pixel_gloss")
         return out
 
     def upload_shadow_map(self, depth, light_vp_rowmajor):
@@ -630,7 +704,7 @@ class Context:
     def cone_points(self, points, aperture=APERTURE_DIFFUSE, want_steps=False, sort=False, n=None, out_device_ptr=None,
                     steps_device_ptr=None):
         """One cone per point.  points: float32 [n, 9] = position, normal, direction (used as given: normalise it yourself);
-        aperture: APERTURE_DIFFUSE / APERTURE_SPECULAR (set_cone_apertures).  Returns float32 [n, 4] (and steps uint8 [n]
+        aperture: APERTURE_DIFFUSE / APERTURE_SPECULAR (set_cone_apertures) or APERTURE_GLOSS(k) (set_gloss_classes).  Returns float32 [n, 4] (and steps uint8 [n]
         with want_steps).  Device form as gather_points."""
         flags = QUERY_SORT_CELLS if sort else 0
         if isinstance(points, int):

@@ -39,6 +39,14 @@ int run_query(vct_ctx* c, const char* who, int kind, const void* pts, int32_t n,
               float* out_cones, uint8_t* out_steps, uint32_t flags) {
     if (!c) return VCT_ERR_INVALID;
     auto refuse = [&](const char* why) { return vct_fail(c, VCT_ERR_INVALID, std::string(who) + ": " + why); };
+    // VCT_APERTURE_GLOSS(k), k < nclasses (include/vct.h "per-material gloss"): class k's step table in the specular
+    // table's place -- wave-uniform as before, one query has one aperture.  From here on it counts as aperture 1.
+    int gloss_class = -1;
+    if (kind == VCT_QUERY_CONE && aperture >= 2) {
+        if (aperture - 2 >= c->gloss.n) return refuse("aperture is neither 0 (diffuse), 1 (specular) nor VCT_APERTURE_GLOSS(k) of an attached class");
+        gloss_class = aperture - 2;
+        aperture = 1;
+    }
     if (const char* why = vct_query_check_args(kind, pts, n, location, aperture, out, false, 0, flags)) return refuse(why);
     if (n > 0 && out_cones && ((uintptr_t)out_cones & 3u)) return refuse("points and outputs need 4-byte alignment");
     if (c->cfg.anisotropic_mips)
@@ -49,7 +57,7 @@ int run_query(vct_ctx* c, const char* who, int kind, const void* pts, int32_t n,
     PIPE_TRY(vct_refresh_steps(c));
     const bool specular = kind == VCT_QUERY_CONE && aperture == 1;
     if (const char* why = vct_query_check_args(kind, pts, n, location, aperture, out, out_steps != nullptr,
-                                               specular ? c->n_specular : c->n_diffuse, flags))
+                                               gloss_class >= 0 ? c->gloss.nsteps[gloss_class] : (specular ? c->n_specular : c->n_diffuse), flags))
         return refuse(why);
 
     VctPointQuery& Q = cur(c).query;
@@ -65,6 +73,7 @@ int run_query(vct_ctx* c, const char* who, int kind, const void* pts, int32_t n,
     VctTraceParams p;
     vct_fill_march_params(c, p, c->vol.active());
     p.cells_biased = nullptr;      // same bits without the footprint records
+    if (gloss_class >= 0) { p.steps_specular = &c->gloss.table.get()->steps[gloss_class][0]; p.n_specular = c->gloss.nsteps[gloss_class]; }
     VctQueryArgs q;
     memset(&q, 0, sizeof(q));
     q.n = (uint32_t)n;

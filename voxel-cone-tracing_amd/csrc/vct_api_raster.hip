@@ -67,6 +67,7 @@ static int raster_args(vct_ctx* c, VctRasterScratch& r, int side_w, int side_h, 
     a.albedo = m.mat_albedo.get();
     a.specular = m.mat_specular.get();
     a.emission = depth_only ? nullptr : m.mat_emission.get();
+    a.mat_gloss = depth_only ? nullptr : m.mat_gloss.get();
     a.ntri = m.ntri;
     a.model_scale = c->cfg.model_scale;
     a.vis = r.vis.get();
@@ -166,7 +167,7 @@ int vct_render_gbuffer_rows_on(vct_ctx* c, const float view_proj[16], int32_t ro
     if (e == hipSuccess && shadow_ready) e = hipStreamWaitEvent(s, shadow_ready, 0);
     if (e == hipSuccess)
         e = vct_launch_gbuffer_shade(a, view_proj, c->cfg.width, c->cfg.height, row0, row1, c->shadow.words.get(), c->shadow.ebase,
-                                     c->shadow.size, c->shadow.tiles.get(), c->shadow.light_vp, cur(c).gb_tiled.get(), cur(c).emis.get(), s);
+                                     c->shadow.size, c->shadow.tiles.get(), c->shadow.light_vp, cur(c).gb_tiled.get(), cur(c).emis.get(), cur(c).gloss.get(), s);
     if (e != hipSuccess) { r.dirty = true; HIP_TRY(c, e); }
     cur(c).gb_current = cur(c).gb_tiled.get();
     form.last_form = binned ? 2 : 1;

@@ -171,6 +171,7 @@ int vct_upload_triangles(vct_ctx* c, const float* pos, const int32_t* material, 
     // mesh's triangles.  Level 0 / brick_prev keep describing what the chain shows.
     c->vox = VctVoxelPlan();
     vct_emission_detach(c);         // the table is indexed by the old materials, the pool by the old slots
+    vct_material_gloss_detach(c);   // the class map too
     c->vol.touched();
     m.tri_nrm.reset(); m.tri_tan.reset(); m.tri_bit.reset(); m.tri_uv.reset();       // belong to the old mesh
     m.mat_tex.reset();                                                                // indexed by the old materials

@@ -1,4 +1,6 @@
 // vct_api_trace.hip -- the C ABI's cone trace: step tables, march parameters, every vct_trace* entry point, vct_gi_pass, outputs, counts, self-tests.
+#include <stddef.h>
+
 #include <algorithm>
 #include <map>
 #include <mutex>
@@ -6,12 +8,10 @@
 #include "vct_ctx.h"
 #include "vct_divisors.h"
 
-namespace {
-
 // The step sequence of trace.fs:90-104, evaluated with the reference's operation order:
 //   dist = vs; while (dist < MAX) { diameter = max(vs, 2*t*dist); lod = log2(diameter/vs); ...
 //   dist += diameter; }   and the [GL] textureLod level selection for that lod.
-int build_steps(const vct_config& cfg, float tan_half, std::vector<VctStep>& out) {
+int vct_build_steps(const vct_config& cfg, float tan_half, std::vector<VctStep>& out) {
     out.clear();
     const int maxl = vct_ilog2(cfg.voxel_dim);
     const float vs = cfg.grid_world_size / (float)cfg.voxel_dim;
@@ -57,6 +57,8 @@ int build_steps(const vct_config& cfg, float tan_half, std::vector<VctStep>& out
     }
     return 0;
 }
+
+namespace {
 
 // The two result words of a self-test kernel (mismatches, one example), through the statistics words as scratch (never the
 // step-counter bank: vct_last_step_count sums that).
@@ -115,8 +117,13 @@ int vct_refresh_steps(vct_ctx* c) {
     if (!c->steps_dirty) return VCT_OK;
     PIPE_TRY(vct_pipeline_drain(c));      // the other slot's trace may still read the table that is rewritten below
     std::vector<VctStep> d, s;
-    if (build_steps(c->cfg, c->cfg.tan_diffuse, d) || build_steps(c->cfg, c->cfg.tan_specular, s))
+    if (vct_build_steps(c->cfg, c->cfg.tan_diffuse, d) || vct_build_steps(c->cfg, c->cfg.tan_specular, s))
         return vct_fail(c, VCT_ERR_INVALID, "cone aperture needs more than VCT_MAX_STEPS march steps");
+    // the tables of the gloss classes (include/vct.h "per-material gloss"): built like `s`, under the same verdict
+    std::vector<VctStep> g[VCT_GLOSS_CLASSES_MAX];
+    for (int k = 0; k < c->gloss.n; ++k)
+        if (vct_build_steps(c->cfg, c->gloss.cls[k].tan_specular, g[k]))      // (vct_set_gloss_classes built it once already)
+            return vct_fail(c, VCT_ERR_INVALID, "a gloss class's aperture needs more than VCT_MAX_STEPS march steps");
     c->n_diffuse = (int)d.size();
     c->n_specular = (int)s.size();
     // preconditions of the kernel's FMA division (vct_trace.hip div_const): admissible divisors, and
@@ -129,10 +136,14 @@ int vct_refresh_steps(vct_ctx* c) {
     };
     for (const VctStep& st : d) ok = ok && divisor_ok(st.occ_den) && blend_ok(st);
     for (const VctStep& st : s) ok = ok && divisor_ok(st.occ_den) && blend_ok(st);
+    for (int k = 0; k < c->gloss.n; ++k)
+        for (const VctStep& st : g[k]) ok = ok && divisor_ok(st.occ_den) && blend_ok(st);
     if (ok) {      // every divisor of the tables passes the device's exhaustive check of the kernel's division
         std::vector<float> divs = {c->cfg.grid_world_size * 0.5f};
         for (const VctStep& st : d) divs.push_back(st.occ_den);
         for (const VctStep& st : s) divs.push_back(st.occ_den);
+        for (int k = 0; k < c->gloss.n; ++k)
+            for (const VctStep& st : g[k]) divs.push_back(st.occ_den);
         for (float dv : divs) {
             bool good = false;
             PIPE_TRY(divisor_verified(c, dv, &good));
@@ -145,10 +156,26 @@ int vct_refresh_steps(vct_ctx* c) {
     if (ok) {
         for (VctStep& st : d) st.occ_den = vct_div_aux(st.occ_den, st.occ_rcp);
         for (VctStep& st : s) st.occ_den = vct_div_aux(st.occ_den, st.occ_rcp);
+        for (int k = 0; k < c->gloss.n; ++k)
+            for (VctStep& st : g[k]) st.occ_den = vct_div_aux(st.occ_den, st.occ_rcp);
     }
     HIP_TRY(c, hipMemcpyAsync(c->steps_dev.get(), d.data(), d.size() * sizeof(VctStep), hipMemcpyHostToDevice, cur(c).stream.get()));
     HIP_TRY(c, hipMemcpyAsync(c->steps_dev.get() + VCT_MAX_STEPS, s.data(), s.size() * sizeof(VctStep),
                               hipMemcpyHostToDevice, cur(c).stream.get()));
+    if (c->gloss.n) {      // the class headers, then each class's table
+        VctGlossTable* t = c->gloss.table.get();
+        struct { int32_t nclasses, pad0[3], nsteps[8]; float shininess[8]; } head = {};
+        head.nclasses = c->gloss.n;
+        for (int k = 0; k < c->gloss.n; ++k) {
+            head.nsteps[k] = c->gloss.nsteps[k] = (int)g[k].size();
+            head.shininess[k] = c->gloss.cls[k].shininess;
+        }
+        static_assert(sizeof(head) <= offsetof(VctGlossTable, steps), "the headers fit in front of the tables");
+        HIP_TRY(c, hipMemcpyAsync(t, &head, sizeof(head), hipMemcpyHostToDevice, cur(c).stream.get()));
+        for (int k = 0; k < c->gloss.n; ++k)
+            HIP_TRY(c, hipMemcpyAsync(&t->steps[k][0], g[k].data(), g[k].size() * sizeof(VctStep), hipMemcpyHostToDevice, cur(c).stream.get()));
+        HIP_TRY(c, hipStreamSynchronize(cur(c).stream.get()));   // head goes out of scope
+    }
     HIP_TRY(c, hipStreamSynchronize(cur(c).stream.get()));   // d, s go out of scope
     c->steps_dirty = false;
     return VCT_OK;
@@ -243,6 +270,12 @@ int vct_launch_trace_rows(vct_ctx* c, int row0, int row1, uint16_t* out_base, in
     if (pix_emis && variant != 0)
         return vct_fail(c, VCT_ERR_INVALID, "pixel-emission planes need the default trace kernel (config.trace_variant 0)");
     p.pix_emis = pix_emis;
+    // gloss classes (include/vct.h "per-material gloss"): the slot's plane and the class tables, in the COMP kernel's
+    // GLOSS form; config.shininess and the specular table are then not read by this launch
+    const uint8_t* pix_gloss = c->gloss.n ? cur(c).gloss.get() : nullptr;
+    if (pix_gloss && (variant != 0 || c->cfg.anisotropic_mips || c->vol.want_cells))
+        return vct_fail(c, VCT_ERR_INVALID, "gloss classes need the default trace kernel (config.trace_variant 0, no anisotropic mips, no footprint records)");
+    if (pix_gloss) { p.gloss = c->gloss.table.get(); p.pix_gloss = pix_gloss; }
     if (half) {
         if (row0 != 0 || row1 != vct_tiles_y(c) || row_stride > 1 || pack_rows)
             return vct_fail(c, VCT_ERR_INVALID, "trace: diffuse rate 2 traces whole frames only (no slabs, tile-row ranges or interleaved rows)");
@@ -256,7 +289,7 @@ int vct_launch_trace_rows(vct_ctx* c, int row0, int row1, uint16_t* out_base, in
             p.dr_list = cur(c).dr_list.get(); p.dr_ctr = cur(c).dr_ctr.get();
             p.dr_waves = c->diffuse_rate_waves;
         }
-    } else if (c->show_mask != VCT_SHOW_ALL || aov_which || pix_emis) {
+    } else if (c->show_mask != VCT_SHOW_ALL || aov_which || pix_emis || pix_gloss) {
         if (variant != 0)
             return vct_fail(c, VCT_ERR_INVALID, "lighting components / per-component outputs need the default trace kernel (config.trace_variant 0)");
         p.comp = component_word(c->show_mask, aov_which, pix_emis != nullptr);

@@ -203,6 +203,8 @@ int vct_set_footprint_records(vct_ctx* c, int32_t on) {
     if (!c) return VCT_ERR_INVALID;
     if (on && c->diffuse_rate == 2)
         return vct_fail(c, VCT_ERR_INVALID, "vct_set_footprint_records: the half-rate diffuse gather has no footprint-record kernels (vct_set_diffuse_rate(ctx, 1) first)");
+    if (on && c->gloss.n)
+        return vct_fail(c, VCT_ERR_INVALID, "vct_set_footprint_records: gloss classes have no footprint-record kernels (vct_set_gloss_classes(ctx, NULL, 0) first)");
     HIP_TRY(c, hipSetDevice(c->device));
     c->vol.want_cells = on != 0;
     PIPE_TRY(vct_pipeline_drain(c));

@@ -62,6 +62,7 @@ hipError_t slot_create(vct_ctx* c, VctFrameSlot& s, hipStream_t stream) {
     if (e == hipSuccess && aov_halves) e = hipMemsetAsync(s.aov.get(), 0, aov_halves * 2, stream);
     if (e == hipSuccess && c->diffuse_rate == 2) e = s.alloc_half_rate(c->cfg.width, c->cfg.height);
     if (e == hipSuccess && c->mesh.mat_emission) e = vct_emission_planes(c, s);      // material emission is attached: every slot has planes
+    if (e == hipSuccess && c->gloss.n) e = vct_gloss_plane(c, s);      // gloss classes are attached: every slot has a plane
     s.gb_current = s.gb_tiled.get();
     return e;
 }
@@ -344,6 +345,8 @@ int vct_set_trace_variant(vct_ctx* c, int32_t variant) {
         return vct_fail(c, VCT_ERR_INVALID, "vct_set_trace_variant: variants 1 .. 4 have no half-rate diffuse gather (vct_set_diffuse_rate(ctx, 1) first)");
     if (variant != 0 && (c->slots[0].emis || c->slots[1].emis))
         return vct_fail(c, VCT_ERR_INVALID, "vct_set_trace_variant: variants 1 .. 4 have no pixel-emission planes (detach the emission first)");
+    if (variant != 0 && c->gloss.n)
+        return vct_fail(c, VCT_ERR_INVALID, "vct_set_trace_variant: variants 1 .. 4 have no gloss classes (vct_set_gloss_classes(ctx, NULL, 0) first)");
     c->cfg.trace_variant = variant;
     return VCT_OK;
 }

@@ -158,6 +158,9 @@ struct VctFrameSlot {
     // launch with planes adds them in the composite
     VctBuf<float> emis;
     bool emis_user = false;             // vct_set_pixel_emission attached them: a detach of the material table leaves them alone
+    // pixel-gloss plane (include/vct.h "per-material gloss"), tiled [tiles][64]: present while gloss classes are attached;
+    // a trace launch with a plane marches each pixel's specular cone with its class's table
+    VctBuf<uint8_t> gloss;
     // half-rate diffuse gather (vct_set_diffuse_rate(ctx, 2); vct_internal.h VctTraceParams::dr_*), present at rate 2 only
     VctBuf<float4> dr_ind;              // [h][w]
     VctBuf<float4> dr_coarse;           // [ch][cw]
@@ -206,6 +209,7 @@ struct VctMesh {
     VctBuf<float> tri_nrm, tri_tan, tri_bit;
     VctBuf<float> mat_specular;
     VctBuf<float> mat_emission;       // [nmat][4] (rgb, 0) material emission (vct_upload_emission), or none: no emission attached
+    VctBuf<uint8_t> mat_gloss;        // [nmat] gloss class per material (vct_upload_material_gloss), or none
     // material textures (vct_upload_textures) + texture coordinates (vct_upload_mesh_uvs)
     VctBuf<float> tri_uv;
     VctBuf<uint32_t> tex_texels;
@@ -351,6 +355,16 @@ struct VctSlotOrder {
     void reset() { produced = joined = drained = false; }
 };
 
+// Gloss classes (include/vct.h "per-material gloss", vct_api_gloss.hip): the attached table, the march steps of each
+// class's step table, and the device copy of both with the tables (vct_internal.h VctGlossTable).  n == 0: none attached.
+// vct_refresh_steps rebuilds the device copy with the diffuse and the specular table, under the same division verdict.
+struct VctGloss {
+    int n = 0;
+    vct_gloss_class cls[VCT_GLOSS_CLASSES_MAX] = {};
+    int nsteps[VCT_GLOSS_CLASSES_MAX] = {};
+    VctBuf<VctGlossTable> table;      // one element
+};
+
 struct vct_ctx {
     vct_config cfg;
     int device = 0;
@@ -373,6 +387,7 @@ struct vct_ctx {
     VctBuf<VctStep> steps_dev;        // [2][VCT_MAX_STEPS]
     VctBuf<uint32_t> spread_lut;      // [1024] spread3(i) << 2 (vct_trace.hip: dilated anchor coordinates by scalar load)
     int n_diffuse = 0, n_specular = 0;
+    VctGloss gloss;
     bool steps_dirty = true;
     bool fast_div = false;            // set by vct_refresh_steps: constant divisors admit the FMA division
     int last_march_form = 0;          // division of the last march launch: 1 IEEE, 2 verified product, 3 x * r (vct_get_stage_counts [2])
@@ -411,6 +426,7 @@ inline int vct_tiles_y(const vct_ctx* c) { return (c->cfg.height + VCT_TILE - 1)
 inline bool vct_rows_in_frame(const vct_ctx* c, int row0, int row1) { return row0 >= 0 && row1 <= vct_tiles_y(c) && row0 <= row1; }
 inline size_t vct_gb_tiled_floats(const vct_ctx* c) { return (size_t)vct_tiles_x(c) * vct_tiles_y(c) * VCT_GB_NPLANES * VCT_TILE_PIX; }
 inline size_t vct_emis_tiled_floats(const vct_ctx* c) { return (size_t)vct_tiles_x(c) * vct_tiles_y(c) * VCT_EMIS_NPLANES * VCT_TILE_PIX; }
+inline size_t vct_gloss_tiled_bytes(const vct_ctx* c) { return (size_t)vct_tiles_x(c) * vct_tiles_y(c) * VCT_TILE_PIX; }
 inline size_t vct_aov_frames(uint32_t which) { return (size_t)__builtin_popcount(which); }      // one frame per VCT_AOV_* bit that is on
 
 // ---- what more than one translation unit needs, by the file that defines it: vct_capi.hip ----
@@ -429,6 +445,8 @@ VctVoxParams vct_vox_params(const vct_ctx* c, const VctVoxelPlan& v);
 void vct_glm_voxel_projections(const vct_ctx* c, float proj[48]);
 // vct_api_trace.hip: the step tables on the device follow the config; everything the march needs (screen trace and bounce)
 int vct_refresh_steps(vct_ctx* c);
+// the step sequence of one aperture (trace.fs:90-104); -1: more than VCT_MAX_STEPS steps, or a march that would not end
+int vct_build_steps(const vct_config& cfg, float tan_half, std::vector<VctStep>& out);
 void vct_fill_march_params(const vct_ctx* c, VctTraceParams& p, const uint32_t* chain);
 // asynchronous, on the slot's stream.  row_stride > 1: only every row_stride-th tile row from row0 on; pack_rows: those rows back to back in out_base (interleaved slabs)
 int vct_launch_trace_rows(vct_ctx* c, int row0, int row1, uint16_t* out_base = nullptr, int row_stride = 1, bool pack_rows = false);
@@ -436,6 +454,9 @@ int vct_launch_trace_rows(vct_ctx* c, int row0, int row1, uint16_t* out_base = n
 // table); zeroed pixel-emission planes for a slot that has none, on the slot's stream
 void vct_emission_detach(vct_ctx* c);
 hipError_t vct_emission_planes(const vct_ctx* c, VctFrameSlot& s);
+// vct_api_gloss.hip: a zeroed pixel-gloss plane for a slot that has none, on the slot's stream; drops the material map (a new mesh)
+hipError_t vct_gloss_plane(const vct_ctx* c, VctFrameSlot& s);
+void vct_material_gloss_detach(vct_ctx* c);
 // vct_multi.hip: slab of the attached communicator (false: none attached); its release
 bool vct_comm_rows(const vct_ctx* c, int* row0, int* row1);
 void vct_comm_release(vct_ctx* c);

@@ -237,6 +237,20 @@ struct VctStep {       // 64 B: one s_load_dwordx16 per march step
     VctLevelRef l1, l2;
 };
 
+// Gloss classes on the device (include/vct.h "per-material gloss"): the class headers -- count, march steps and Phong
+// exponent of each class -- in front of one step table per class, each built as the specular table is.  One allocation
+// behind one pointer of VctTraceParams: the specular wave reads a header entry and a table through the constant address
+// space with a wave-uniform class index (scalar loads, as it reads steps_specular), the composite reads its lane's
+// exponent with one vector load.
+struct VctGlossTable {
+    int32_t nclasses;
+    int32_t pad0[3];
+    int32_t nsteps[8];
+    float shininess[8];
+    int32_t pad1[12];                   // the tables start 128 B in
+    VctStep steps[8][VCT_MAX_STEPS];
+};
+
 #define VCT_COMP_GROUPS_SHIFT 8
 #define VCT_COMP_AOV_SHIFT 16
 #define VCT_COMP_ON 0x80000000u
@@ -312,8 +326,13 @@ struct VctTraceParams {
     const uint32_t* aniso;
     uint32_t aniso_stride;
     uint32_t aniso_alt_slab;            // float4 offset from a level's LDS slab to its second ("-axis") slab
-    uint32_t* bounce_list;              // global list of occupied voxels (Morton indices), brick by brick
-    uint32_t* bounce_list_count;
+    // bounce_list / bounce_list_count are the bounce kernels', gloss / pix_gloss the screen trace's (include/vct.h
+    // "per-material gloss"; k_trace_tile_split<.., GLOSS = true>, launched when pix_gloss != null): they share their slots
+    // for the reason bounce_out and aov do
+    union { uint32_t* bounce_list;      // global list of occupied voxels (Morton indices), brick by brick
+            const VctGlossTable* gloss; };   // the class headers and one step table per class
+    union { uint32_t* bounce_list_count;
+            const uint8_t* pix_gloss; };     // pixel-gloss plane, tiled [tile][64]: a byte b means class (b < nclasses ? b : 0)
     union { uint32_t bounce_list_cap;
             int32_t dr_waves; };        // (half-rate pass) waves per 64 marched points: 1, or 2 with three cones each
     // brick_over is the bounce kernels', pix_emis the screen trace's: one slot, for the reason bounce_out and aov share theirs
@@ -431,6 +450,7 @@ struct VctRasterArgs {
     const float* albedo;         // [nmat][4]
     const float* specular;       // [nmat][3]
     const float* emission;       // [nmat][4] material emission (rgb, pad) or null (G-buffer shade: the pixel-emission planes)
+    const uint8_t* mat_gloss;    // [nmat] gloss class per material or null (G-buffer shade: the pixel-gloss plane)
     int32_t ntri;
     float model_scale;
     // Visibility words: 64-bit (depth | id) of the main draw, W*H; 32-bit depth-only of the shadow pass, S*S.
@@ -481,7 +501,7 @@ hipError_t vct_launch_gbuffer_visibility(const VctRasterArgs& a, const float vie
                                          hipStream_t s);
 hipError_t vct_launch_gbuffer_shade(const VctRasterArgs& a, const float view_proj[16], int W, int H, int row0, int row1,
                                     const uint32_t* shadow, uint32_t shadow_ebase, int shadow_size, const uint2* shadow_tiles,
-                                    const float light_vp[16], float* tiled, float* emis_tiled, hipStream_t s);
+                                    const float light_vp[16], float* tiled, float* emis_tiled, uint8_t* gloss_tiled, hipStream_t s);
 // one level of a texture's mip chain from its parent (pw x ph -> w x h), glGenerateMipmap restated as in the oracle
 hipError_t vct_launch_tri_alpha(const VctRasterArgs& a, int32_t* out, hipStream_t s);
 hipError_t vct_launch_tex_mip(const uint32_t* parent, int pw, int ph, uint32_t* level, int w, int h, hipStream_t s);
@@ -490,6 +510,9 @@ hipError_t vct_launch_untile_gbuffer(const float* tiled, float* planes_linear, i
 #define VCT_EMIS_NPLANES 3
 hipError_t vct_launch_untile_emission(const float* tiled, float* planes_linear, int w, int h, hipStream_t s);
 hipError_t vct_launch_tile_emission(const float* planes_linear, float* tiled, int w, int h, hipStream_t s);
+// the one-byte pixel-gloss plane: tiled [tile][64] <-> linear [h*w] (pixels outside the frame are tiled as 0)
+hipError_t vct_launch_untile_gloss(const uint8_t* tiled, uint8_t* linear, int w, int h, hipStream_t s);
+hipError_t vct_launch_tile_gloss(const uint8_t* linear, uint8_t* tiled, int w, int h, hipStream_t s);
 // strided (row_stride > 1) and packed tile rows are read by k_trace_tile_split's own tiles only: not by the one-wave
 // kernel (variants 1, 2) nor by the compaction's virtual tiles (4)
 static inline bool vct_variant_takes_row_subsets(int variant) { return variant == 0 || variant == 3; }

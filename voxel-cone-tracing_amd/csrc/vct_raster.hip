@@ -1533,6 +1533,10 @@ struct ShadeParams {
     // [tile][3][64]; emis_tiled == null: no emission attached, nothing read or written
     const float* emission;
     float* emis_tiled;
+    // per-material gloss (include/vct.h): the class byte per material [nmat] and the slot's pixel-gloss plane [tile][64];
+    // gloss_tiled == null: nothing read or written
+    const uint8_t* mat_gloss;
+    uint8_t* gloss_tiled;
 };
 
 // [GL] bilinear clamp-to-edge fetch with the operation order of host/vct_host.cpp shadow_fetch
@@ -1576,6 +1580,7 @@ k_gbuffer_shade(const ShadeParams p) {
 #pragma unroll
     for (int k = 0; k < VCT_GB_NPLANES; ++k) g[k] = 0.0f;
     float em[3] = {0.0f, 0.0f, 0.0f};       // pixel emission: the visible triangle's material's, 0 where no surface is
+    uint32_t gloss = 0u;                    // pixel gloss class: the same
     unsigned long long v = ~0ull;
     if (px < W && py < H) {
         v = p.r.vis[(size_t)py * W + px];
@@ -1607,6 +1612,7 @@ k_gbuffer_shade(const ShadeParams p) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) em[k] = p.emission[4 * (size_t)m_early + k];
         }
+        if (p.gloss_tiled) gloss = p.mat_gloss[m_early];
         // ... and, in a scene with textures, the material's three texture indices and the triangle's texture coordinates
         // (round 4: they used to be asked for after the set-up -- material -> indices -> descriptor -> texels was four
         // dependent round trips behind it, now two)
@@ -1860,6 +1866,7 @@ k_gbuffer_shade(const ShadeParams p) {
 #pragma unroll
         for (int k = 0; k < VCT_EMIS_NPLANES; ++k) eo[k * VCT_TILE_PIX] = em[k];
     }
+    if (p.gloss_tiled) p.gloss_tiled[(size_t)tile * VCT_TILE_PIX + lane] = (uint8_t)gloss;
 }
 
 // glGenerateMipmap (R/Model.h:168) for one level: rounded mean of the 2x2 parent texels, indices clamped to the parent
@@ -2053,7 +2060,7 @@ hipError_t vct_launch_gbuffer_visibility(const VctRasterArgs& a, const float vie
 
 hipError_t vct_launch_gbuffer_shade(const VctRasterArgs& a, const float view_proj[16], int W, int H, int row0, int row1,
                                     const uint32_t* shadow, uint32_t shadow_ebase, int shadow_size, const uint2* shadow_tiles,
-                                    const float light_vp[16], float* tiled, float* emis_tiled, hipStream_t s) {
+                                    const float light_vp[16], float* tiled, float* emis_tiled, uint8_t* gloss_tiled, hipStream_t s) {
     ShadeParams p = make_shade(a, view_proj, W, H, row0, row1);
     p.shadow_tiles = shadow ? shadow_tiles : nullptr;
     p.nrm = a.nrm; p.tan = a.tan; p.bit = a.bit;
@@ -2063,6 +2070,8 @@ hipError_t vct_launch_gbuffer_shade(const VctRasterArgs& a, const float view_pro
     p.tiled = tiled;
     p.emission = a.emission;
     p.emis_tiled = a.emission ? emis_tiled : nullptr;
+    p.mat_gloss = a.mat_gloss;
+    p.gloss_tiled = a.mat_gloss ? gloss_tiled : nullptr;
     p.tiles_x = (W + VCT_TILE - 1) / VCT_TILE;
     p.tile0 = row0 * p.tiles_x;
     p.tile1 = row1 * p.tiles_x;

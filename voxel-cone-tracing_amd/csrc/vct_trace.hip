@@ -10,7 +10,8 @@
 // per-cone step counts and the raw cone vec4s are bit-identical; compile with -ffp-contract=off.
 //
 // Kernels in this file: k_trace_tile_split (default: an 8x8 screen tile = 3 waves -- cones 0-2, cones
-// 3-5, specular -- with an LDS hand-off and a last-arriver composite), k_trace_tile (one wave per
+// 3-5, specular -- with an LDS hand-off and a last-arriver composite; its GLOSS forms march the specular cone once per
+// gloss class present in the tile), k_trace_tile (one wave per
 // tile; A/B variants), k_bounce_list/_march/_bricks (second bounce, same march), k_point_march + k_diffuse_resolve (half-rate
 // diffuse gather, same march), k_query_march + k_query_keys (point queries, same march), k_divide_selftest.
 //
@@ -887,9 +888,10 @@ __device__ __forceinline__ float clear_colour(const VctTraceParams& p) { return 
 // order are the same in all three cases.
 // COMP with VCT_COMP_EMISSION in the mask word (wave-uniform): out.rgb = ((A + D) + S) + E, one fp32 add per channel, last,
 // E from the launch's pixel-emission planes at em_offset() = tile * 192 + lane (include/vct.h "emissive materials").
+// `shininess`: the exponent of :213 -- p.shininess, or the lane's gloss class's (k_trace_tile_split<.., GLOSS = true>).
 template <bool COMP, class V4, class Pixel, class EmOffset>
 __device__ __forceinline__ void composite(const VctTraceParams& p, const float* gb, F4 ind, V4 sc,
-                                          bool alive, Pixel pixel, EmOffset em_offset) {
+                                          bool alive, Pixel pixel, EmOffset em_offset, float shininess) {
     const F3 P = gb_planes3(gb, 0), N = gb_planes3(gb, 12);
     const float alb_r = gb_plane(gb, 15), alb_g = gb_plane(gb, 16), alb_b = gb_plane(gb, 17), alb_a = gb_plane(gb, 18);
     const float shadow = gb_plane(gb, 22);
@@ -909,7 +911,7 @@ __device__ __forceinline__ void composite(const VctTraceParams& p, const float* 
     const float dg = (direct_diffuse + occlusion * ird_g) * alb_g;
     const float db = (direct_diffuse + occlusion * ird_b) * alb_b;
     const F3 R = normalize3(reflect3(f3(L.x * -1.0f, L.y * -1.0f, L.z * -1.0f), N));   // :212
-    const float spec = powf(fmaxf(dot3(E, R), 0.0f), p.shininess);          // :213
+    const float spec = powf(fmaxf(dot3(E, R), 0.0f), shininess);            // :213
     const float raw_ds = spec * shadow;
     const float direct_spec = s_ds ? raw_ds : 0.0f;                         // :214 (:215)
     const float spec_occ = s_ao ? 1.0f - sc.w : 1.0f;                       // :221
@@ -1042,7 +1044,7 @@ k_trace_tile(const VctTraceParams p) {
 
     // stage 3: composite
     const float* gb3 = gbuf_ptr(fresh_lane());
-    if (in_frame) composite<false>(p, gb3, ind, sc, alive, pixel_index, [] { return (size_t)0; });
+    if (in_frame) composite<false>(p, gb3, ind, sc, alive, pixel_index, [] { return (size_t)0; }, p.shininess);
     // executed-step count: wave reduction, stored into the tile's slot (a plain store: no atomic, nothing to clear)
     total = wave_sum(total);
     if (lane == 0) p.tile_steps[tile] = (uint32_t)total;
@@ -1079,10 +1081,20 @@ static_assert(VCT_SPLIT == 3 || VCT_SPLIT == 4 || VCT_SPLIT == 7, "VCT_SPLIT mus
 // HALF: the last launch of a half-rate pass (vct_set_diffuse_rate(ctx, 2); "Half-rate diffuse gather" below): the diffuse
 // waves march nothing and leave the debug outputs to the launches in front of this one, and the composite takes the
 // pixel's gather from p.dr_ind instead of the cones in LDS.  Instantiated with COMP and PRIO only (whole frames).
+// GLOSS: gloss classes (include/vct.h "per-material gloss"; p.pix_gloss, p.gloss): the specular wave marches once per class
+// present among its live lanes, each time with that class's step table and the other lanes masked off, and the composite
+// takes the lane's Phong exponent from the class headers.  Instantiated with COMP, for the plain, PRIO and HALF forms.
+typedef const __attribute__((address_space(4))) VctGlossTable* GlossTable;
+// the lane's class: its byte of the tile's plane under the clamp rule -- never an index before the clamp
+__device__ __forceinline__ int gloss_class_of(const VctTraceParams& p, int tile, int pix, int nclasses) {
+    const int b = (int)p.pix_gloss[(size_t)tile * VCT_TILE_PIX + pix];
+    return b < nclasses ? b : 0;
+}
 template <bool WRAP, int FASTDIV, bool ANISO, bool COMPACT = false, bool CELLS = false, bool PRIO = false, bool COMP = false,
-          bool HALF = false>
+          bool HALF = false, bool GLOSS = false>
 __global__ void __launch_bounds__(64 * VCT_SPLIT, ANISO ? VCT_ANISO_MIN_WAVES : VCT_TRACE_MIN_WAVES)
 k_trace_tile_split(const VctTraceParams p) {
+    static_assert(!GLOSS || (COMP && !ANISO && !COMPACT && !CELLS), "gloss classes: the default kernel's COMP forms only");
     __shared__ float4 lds_blk[VCT_SPLIT][ANISO ? 4 : 2][64];   // per wave: level-1 slab, level-2 slab (+ their "-axis" slabs)
     __shared__ float4 lds_cone[7][64];
     __shared__ int lds_done;
@@ -1168,12 +1180,39 @@ k_trace_tile_split(const VctTraceParams p) {
         if (!PRIO && p.spec_prio) __builtin_amdgcn_s_setprio(1);
         const F3 P = gb_planes3(gb, 0), Nw = gb_planes3(gb, 3), N = gb_planes3(gb, 12);
         const F3 start = cone_start(P, Nw, p.vs);
+        if constexpr (GLOSS) {
+            // One march per class present among the live lanes: the class of the first remaining lane, wave-uniform, picks
+            // the table and its step count by scalar loads; the lanes of that class march, write their cone and leave the
+            // mask.  A lane marches exactly once, so nothing depends on the order of the classes.  `held` stays live across
+            // the marches: it describes a block by (level, anchor) alone, every sample tests its own footprints against it,
+            // and between two marches nothing writes the wave's slabs (the first slab is refilled by every sample that
+            // reads it, the second only together with the descriptor).
+            const GlossTable gt = (GlossTable)p.gloss;
+            const int cls = gloss_class_of(p, tile, plane_, gt->nclasses);
+            const F3 dir = specular_dir(P, N, p.cam);
+            if (!alive) {       // what a lane that marches nothing gets from the one march of the other forms
+                lds_cone[6][lane] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (p.dbg_steps && in_frame) p.dbg_steps[pixel_index() * 7 + 6] = 0;
+            }
+            for (unsigned long long rest = ballot64(alive); rest != 0ull;) {
+                const int k = __builtin_amdgcn_readlane(cls, (int)__ffsll((long long)rest) - 1);
+                const bool mine = alive && cls == k;
+                int st;
+                const F4 sc = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO, REUSE>(p, mine, start, dir, &p.gloss->steps[k][0],
+                                                                            (groups & 2u) ? gt->nsteps[k] : 0, blk, lb, st, ms, held);
+                total += st;          // (0 for the lanes that did not march)
+                if (mine) lds_cone[6][lane] = make_float4(sc.x, sc.y, sc.z, sc.w);
+                store_debug_cone(p, pixel_index, 6, sc, st, mine, mine);
+                rest &= ~ballot64(mine);
+            }
+        } else {
         int st6;
         const F4 sc = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO, REUSE>(p, alive, start, specular_dir(P, N, p.cam),
                                                                     p.steps_specular, n_specular, blk, lb, st6, ms, held);
         total += st6;
         lds_cone[6][lane] = make_float4(sc.x, sc.y, sc.z, sc.w);
         store_debug_cone(p, pixel_index, 6, sc, st6, alive, in_frame);
+        }
     }
     total = wave_sum(total);
     if (lane == 0) atomicAdd(&lds_steps, total);          // LDS: the last arriver below stores the tile's total
@@ -1200,8 +1239,13 @@ k_trace_tile_split(const VctTraceParams p) {
 #pragma unroll
             for (int i = 0; i < 6; ++i) ind = fold_cone(ind, i, lds_cone[i][lane]);
         }
+        float shininess = p.shininess;
+        if constexpr (GLOSS) {
+            const GlossTable gt = (GlossTable)p.gloss;
+            shininess = p.gloss->shininess[gloss_class_of(p, tile, fresh_lane(), gt->nclasses)];
+        }
         composite<COMP>(p, gb3, ind, lds_cone[6][lane], alive, pixel_index,
-                        [&]() { return (size_t)tile * (VCT_EMIS_NPLANES * VCT_TILE_PIX) + fresh_lane(); });
+                        [&]() { return (size_t)tile * (VCT_EMIS_NPLANES * VCT_TILE_PIX) + fresh_lane(); }, shininess);
     }
 }
 
@@ -1766,6 +1810,14 @@ hipError_t launch(const VctTraceParams& p, int blocks, hipStream_t s) {
 template <bool WRAP, int FASTDIV, bool COMP>
 void launch_split(const VctTraceParams& p, int blocks, hipStream_t s) {
     const dim3 grid(blocks), block(64 * VCT_SPLIT);
+    if constexpr (COMP) {     // gloss classes (the host launches them with p.comp on, and refuses them beside the two options below)
+        if (p.pix_gloss) {
+            if (!p.spec_prio)
+                hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, true, true, false, true>), grid, block, 0, s, p);
+            else hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, false, true, false, true>), grid, block, 0, s, p);
+            return;
+        }
+    }
     if (p.aniso) {
         hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, true, false, false, false, COMP>), grid, block, 0, s, p);
         return;
@@ -1805,7 +1857,9 @@ hipError_t launch_half_rate(const VctTraceParams& p, int blocks, hipStream_t s, 
     if (p.dr_waves == 2) launch_point_march<WRAP, FASTDIV, 2>(p, true, listed_blocks, s);
     else launch_point_march<WRAP, FASTDIV, 1>(p, true, listed_blocks, s);
     if ((e = hipGetLastError()) != hipSuccess || (e = mark(2)) != hipSuccess) return e;
-    hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, true, true, true>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
+    if (p.pix_gloss)
+        hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, true, true, true, true>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
+    else hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, true, true, true>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
     return hipGetLastError();
 }
 
@@ -1966,6 +2020,7 @@ hipError_t vct_launch_trace(const VctTraceParams& params, int variant, hipStream
     if (march_form) *march_form = loose ? 3 : (p.fast_div ? 2 : 1);
     if (p.ntiles <= 0) return hipSuccess;
     if ((rstride > 1 || p.pack_rows) && !vct_variant_takes_row_subsets(variant)) return hipErrorInvalidValue;
+    if (p.pix_gloss && (variant != 0 || p.aniso || p.cells_biased || !p.comp || !p.gloss)) return hipErrorInvalidValue;
     if (p.dr_ind && (variant != 0 || p.aniso || p.cells_biased || !p.comp || rstride > 1 || p.pack_rows || p.tile_row0 != 0 ||
                      p.tile_row1 != p.tiles_y))
         return hipErrorInvalidValue;

@@ -225,6 +225,14 @@ struct Voxel_Cone_Tracing {
     // ReferenceVoxelization (that mode is the reference's shaders as written).
     std::vector<float> Emission;                     // [materials][3]
     bool emission_dirty = false;
+    // Per-material gloss (vct_set_gloss_classes / vct_upload_material_gloss, include/vct.h: the reference hard-codes one
+    // aperture and one shininess for every surface): up to VCT_GLOSS_CLASSES_MAX classes and a class per material of the
+    // model (all 0 after init).  SetGlossClasses / SetGloss change them; the next Render() hands them over and its
+    // G-buffer pass writes the classes of the visible materials -- no volume rebuild, the voxels know nothing of gloss.
+    // An empty class list (the default) is the reference's frame.
+    std::vector<vct_gloss_class> GlossClasses;
+    std::vector<uint8_t> Gloss;                      // [materials]
+    bool gloss_dirty = false;
     int Bounces = 1;    // 2 = re-inject the lit voxels once (the "2 bounces" of the reference's README.md:16,
                         // which its code does not implement: VCT.h:138-139 injects once); set before init
 
@@ -310,6 +318,8 @@ struct Voxel_Cone_Tracing {
             vcth_scene_get_emission(model.scene, Emission.data());
         }
         if (!UploadEmission()) return;
+        if (Gloss.size() != (size_t)nmat) Gloss.assign((size_t)nmat, 0);
+        if (!GlossClasses.empty() && !UploadGloss()) return;
         DrawDepthTexture();     // VCT.h:138
         DrawVoxelTexture();     // VCT.h:139
     }
@@ -326,6 +336,21 @@ struct Voxel_Cone_Tracing {
         if (!table || (ctx && materials * 3 != Emission.size())) return false;
         Emission.assign(table, table + materials * 3);
         emission_dirty = true;
+        return true;
+    }
+
+    // The gloss classes (1 .. VCT_GLOSS_CLASSES_MAX; none: detached), and the class of one material; picked up by the next
+    // Render().  Before init SetGloss knows no materials and refuses.
+    bool SetGlossClasses(const vct_gloss_class* classes, size_t n) {
+        if (n > (size_t)VCT_GLOSS_CLASSES_MAX || (n && !classes)) return false;
+        GlossClasses.assign(classes, classes + n);
+        gloss_dirty = true;
+        return true;
+    }
+    bool SetGloss(int material, int gloss_class) {
+        if (material < 0 || (size_t)material >= Gloss.size() || gloss_class < 0 || gloss_class > 255) return false;
+        Gloss[(size_t)material] = (uint8_t)gloss_class;
+        gloss_dirty = true;
         return true;
     }
 
@@ -346,6 +371,7 @@ struct Voxel_Cone_Tracing {
             if (!DynamicLight || Bounces >= 2) DrawVoxelTexture();      // (a whole GI pass below rebuilds it anyway)
             if (last_status != VCT_OK) return;
         }
+        if (gloss_dirty && !UploadGloss()) return;              // changed classes: the G-buffer pass below writes them
         const float cam[3] = {camera.position.x, camera.position.y, camera.position.z};   // VCT.h:167
         const float L[3] = {lightDirection.x, lightDirection.y, lightDirection.z};         // VCT.h:168
         vct_set_camera_position(ctx, cam);
@@ -456,6 +482,13 @@ private:
         // a refused table stays pending: every Render() reports the refusal until SetEmission hands over a valid one
         emission_dirty = !check(vct_upload_emission(ctx, Emission.empty() ? nullptr : Emission.data()), "vct_upload_emission");
         return !emission_dirty;
+    }
+    bool UploadGloss() {
+        // refused classes stay pending, like a refused emission table
+        const bool on = !GlossClasses.empty();
+        gloss_dirty = !check(vct_set_gloss_classes(ctx, on ? GlossClasses.data() : nullptr, (int32_t)GlossClasses.size()), "vct_set_gloss_classes") ||
+                      !check(vct_upload_material_gloss(ctx, on && !Gloss.empty() ? Gloss.data() : nullptr), "vct_upload_material_gloss");
+        return !gloss_dirty;
     }
     bool check(int rc, const char* what) {
         last_status = rc;

@@ -9,7 +9,13 @@
 //            [--show diffuse,indirect-diffuse,specular,indirect-specular,ao] [--diffuse-rate 1|2]
 //            [--voxels [current|radiance|albedo|normal[:level]]] [--ambient-cubes NX,NY,NZ FILE] [--dump-chain FILE]
 //            [--emission MATERIAL=R,G,B[;MATERIAL=R,G,B...]]
+//            [--gloss-classes TAN,SHIN[;TAN,SHIN...] --gloss MATERIAL=CLASS[;MATERIAL=CLASS...]]
 //
+// --gloss-classes LIST --gloss LIST: per-material gloss (Voxel_Cone_Tracing::SetGlossClasses / SetGloss,
+//   vct_set_gloss_classes): up to 8 classes of (specular cone aperture as tan of the half angle, Phong exponent) and the
+//   class of the listed material indices (the others are class 0).  --gloss-classes "0.07,20;0.2,4" --gloss "2=1" gives
+//   material 2 the wide, dull reflection and leaves the rest as the reference has them.  Both lists are checked before a
+//   GPU is touched; a material index the scene does not have is refused after the scene is loaded.
 // --emission LIST: emission (fp32 RGB) of the listed material indices, over whatever the scene's MTL file gave them
 //   (Voxel_Cone_Tracing::SetEmission, vct_upload_emission): the surfaces become area lights in the volume and are added
 //   to the pixels that see them.  The procedural street (procedural:bistro) keeps its lamps in material 10: --emission "10=1,0.9,0.7" lights them.
@@ -48,6 +54,7 @@
 #include <vector>
 
 #include "Voxel_Cone_Tracing.h"
+#include "vct_demo_options.h"
 
 static const int SCREEN_WIDTH = 1280;
 static const int SCREEN_HEIGHT = 720;
@@ -104,6 +111,8 @@ int main(int argc, char** argv) {
     const char* cubes_file = nullptr;
     const char* chain_file = nullptr;
     const char* emission = nullptr;
+    const char* gloss_classes_arg = nullptr;
+    const char* gloss_arg = nullptr;
     int cubes[3] = {0, 0, 0};
     bool show_voxels = false;
     int view_source = VCT_VOXVIEW_CURRENT, view_level = 0;
@@ -144,6 +153,8 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--diffuse-rate")) diffuse_rate = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--dump-chain")) chain_file = argv[++i];
         else if (!strcmp(argv[i], "--emission")) emission = argv[++i];
+        else if (!strcmp(argv[i], "--gloss-classes")) gloss_classes_arg = argv[++i];
+        else if (!strcmp(argv[i], "--gloss")) gloss_arg = argv[++i];
         else if (!strcmp(argv[i], "--ambient-cubes") && i + 2 < argc) {
             if (sscanf(argv[++i], "%d,%d,%d", &cubes[0], &cubes[1], &cubes[2]) != 3 || cubes[0] < 1 || cubes[1] < 1 || cubes[2] < 1 ||
                 (long long)cubes[0] * cubes[1] * cubes[2] * 6 > VCT_POINT_QUERY_MAX) {
@@ -151,6 +162,21 @@ int main(int argc, char** argv) {
                 return 1;
             }
             cubes_file = argv[++i];
+        }
+    }
+    std::vector<vct_gloss_class> gloss_classes;             // --gloss-classes / --gloss: both lists before a GPU is touched
+    std::vector<std::pair<int, int>> gloss_of;
+    if (gloss_classes_arg) {
+        if (const char* at = vct_demo_parse_gloss_classes(gloss_classes_arg, gloss_classes)) {
+            fprintf(stderr, "--gloss-classes: TAN,SHIN[;...], 1 to %d classes, TAN > 0 and SHIN >= 0 (at '%s')\n", VCT_GLOSS_CLASSES_MAX, at);
+            return 1;
+        }
+    }
+    if (gloss_arg) {
+        if (!gloss_classes_arg) { fprintf(stderr, "--gloss: needs --gloss-classes\n"); return 1; }
+        if (const char* at = vct_demo_parse_gloss(gloss_arg, (int)gloss_classes.size(), gloss_of)) {
+            fprintf(stderr, "--gloss: MATERIAL=CLASS[;...] with classes below %zu (at '%s')\n", gloss_classes.size(), at);
+            return 1;
         }
     }
     GLFWwindow* window = nullptr;          // no window system on a compute node
@@ -228,6 +254,15 @@ int main(int argc, char** argv) {
             if (*q == ';') ++q;
             else if (*q) { fprintf(stderr, "--emission: ';' expected at '%s'\n", q); return 1; }
         }
+    }
+
+    if (!gloss_classes.empty()) {                           // picked up by the first Render()
+        voxel_cone_tracing.SetGlossClasses(gloss_classes.data(), gloss_classes.size());
+        for (const std::pair<int, int>& g : gloss_of)
+            if (!voxel_cone_tracing.SetGloss(g.first, g.second)) {
+                fprintf(stderr, "--gloss: material %d: the scene has %zu materials\n", g.first, voxel_cone_tracing.Gloss.size());
+                return 1;
+            }
     }
 
     float delta_time = 0.05f;

@@ -618,6 +618,45 @@ int vct_upload_material_gloss(vct_ctx* ctx, const uint8_t* mat_class /* [nmat] *
 int vct_set_pixel_gloss(vct_ctx* ctx, const uint8_t* classes, int32_t layout, int32_t location);
 int vct_download_pixel_gloss(vct_ctx* ctx, uint8_t* out /* linear [h*w] */);
 
+/* ---- sky light: open cones gather a spherical-harmonic environment ------------------------------------------------------
+ * The march of S/VoxelConeTracing.fs:94-104 drops the unoccluded remainder 1 - alpha of a cone: a cone that reaches open
+ * air returns black, and the flat ambientFactor term is all that stands in for the sky.  With a SKY attached that
+ * remainder gathers the sky's radiance along the cone.
+ *   Sky                a context holds at most one: nine real spherical-harmonic coefficients per colour channel,
+ *                      float sh[9][3], in the orthonormal real basis in WORLD axes.  Index i = l(l+1)+m goes with the
+ *                      polynomials 1, y, z, x, xy, yz, 3z^2-1, xz, x^2-y^2 of the unit direction d = (x, y, z).
+ *   Folding            on the host, poly[i][c] = (float)(K_i * (double)sh[i][c]) with K_0 = sqrt(1/4pi) =
+ *                      0.28209479177387814, K_1..3 = sqrt(3/4pi) = 0.4886025119029199, K_4,5,7 = sqrt(15/4pi) =
+ *                      1.0925484305920792, K_6 = sqrt(5/16pi) = 0.31539156525252005, K_8 = sqrt(15/16pi) =
+ *                      0.5462742152960396.  The device sees only poly.
+ *   Radiance           of a direction, per channel, in fp32, in exactly this order:
+ *                        s = p0; s = fmaf(p1,y,s); s = fmaf(p2,z,s); s = fmaf(p3,x,s);
+ *                        s = fmaf(p4,x*y,s); s = fmaf(p5,y*z,s); s = fmaf(p6,fmaf(3.0f*z,z,-1.0f),s);
+ *                        s = fmaf(p7,x*z,s); s = fmaf(p8,fmaf(x,x,-(y*y)),s);   sky = fmaxf(s, 0.0f)
+ *                      (a second-order series can dip below zero where the sky it approximates does not: the clamp).
+ *   A marched cone     with alpha the value the loop test of fs:94 saw last and d the normalised direction the march
+ *                      used, becomes   T = fmaxf(1.0f - alpha, 0.0f);   rgb_c = fmaf(T, sky_c(d), rgb_c).
+ * The occlusion component and the step count do not change.  This holds however the loop ended: alpha bound, distance
+ * bound, or a table of zero steps -- then the cone is the sky.  A pixel or point that is not alive keeps the zero cone; a
+ * cone group that the lighting-component mask skips is not marched and gets no sky; a cone whose march is NaN stays NaN.
+ * Nothing else of the fragment shader changes: the gather, both occlusion factors, the composite and the per-component
+ * outputs read the cones as they now are.  The sky is context state, not frame-slot state.
+ * It applies to the screen trace at diffuse rate 1 and 2, with and without gloss classes, in slab, rows and strided
+ * launches, and to vct_gather_points and vct_cone_points (every aperture; the caller's direction is used as given).
+ * It does NOT apply to vct_bounce (the bounce chain is pinned by its own reference), to the voxel view, or to discarded
+ * pixels: they keep the clear colour, the trace has no ray for them.
+ * vct_set_sky: NULL detaches; a table whose values are all +0 or -0 counts as detached.  Detached, the frame is the
+ * frame without this section, bit for bit, from the kernels launched before it existed.  A NaN or infinite value gives
+ * VCT_ERR_INVALID and leaves the state as it was.  Also VCT_ERR_INVALID, the context keeping what it had:
+ * config.trace_variant 1 .. 4 (and vct_set_trace_variant refuses 1 .. 4 while a sky is attached);
+ * config.anisotropic_mips; footprint records on (and vct_set_footprint_records(on) while a sky is attached) -- the rule
+ * of gloss classes and the half-rate gather, so only the default kernel has a sky form.  The call waits for work in
+ * flight; the next launch of either frame slot sees the new sky.
+ * vct_get_sky: the coefficients as given, their folded form, and whether a sky is attached (zeros and 0 when none is);
+ * any of the three outputs may be NULL. */
+int vct_set_sky(vct_ctx* ctx, const float sh[9][3]);
+int vct_get_sky(const vct_ctx* ctx, float sh[9][3], float poly[9][3], int32_t* attached);
+
 /* ---- two frames in flight (round 6) -----------------------------------------------------------------
  * The reference's Render() (VCT.h:146-190) issues GL commands; the driver starts frame k + 1 while frame k
  * drains -- nothing in R/main.cpp:77-94 waits for a frame.  A HIP stream does wait: each whole-frame trace

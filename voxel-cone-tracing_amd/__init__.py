@@ -72,6 +72,7 @@ ABI_SYMBOLS = [
     "vct_upload_emission", "vct_set_pixel_emission", "vct_download_pixel_emission",
     "vct_set_gloss_classes", "vct_get_gloss_classes", "vct_upload_material_gloss", "vct_set_pixel_gloss",
     "vct_download_pixel_gloss",
+    "vct_set_sky", "vct_get_sky",
 ]
 
 
@@ -191,6 +192,8 @@ _lib.vct_get_gloss_classes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_v
 _lib.vct_upload_material_gloss.argtypes = [C.c_void_p, C.c_void_p]
 _lib.vct_set_pixel_gloss.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
 _lib.vct_download_pixel_gloss.argtypes = [C.c_void_p, C.c_void_p]
+_lib.vct_set_sky.argtypes = [C.c_void_p, C.c_void_p]
+_lib.vct_get_sky.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.vct_upload_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
 
 
@@ -445,6 +448,26 @@ class Context:
         out = np.zeros(self.cfg.width * self.cfg.height, np.uint8)
         self._ck(_lib.vct_download_pixel_gloss(self._h, _ptr(out)), "vct_download_pixel_gloss")
         return out
+
+    # --- sky light (include/vct.h "sky light")
+    def set_sky(self, sh):
+        """The context's sky: float32 [9, 3] real spherical-harmonic coefficients (orthonormal basis, world axes, index
+        l(l+1)+m) per colour channel.  None detaches, and so does a table of zeros; a NaN or infinite value is refused and
+        the sky in force stays."""
+        if sh is None:
+            self._ck(_lib.vct_set_sky(self._h, None), "vct_set_sky")
+            return
+        a = np.ascontiguousarray(sh, np.float32)
+        if a.shape != (9, 3):
+            raise VctError(f"set_sky: shape {a.shape}, a sky is float32 [9, 3]")
+        self._ck(_lib.vct_set_sky(self._h, _ptr(a)), "vct_set_sky")
+
+    def sky(self):
+        """(sh float32 [9, 3], poly float32 [9, 3], attached bool): the coefficients as given, their folded polynomial form
+        (what the kernels read), and whether a sky is attached (zeros and False when none is)."""
+        sh, poly, on = np.zeros((9, 3), np.float32), np.zeros((9, 3), np.float32), C.c_int32()
+        self._ck(_lib.vct_get_sky(self._h, _ptr(sh), _ptr(poly), C.byref(on)), "vct_get_sky")
+        return sh, poly, bool(on.value)
 
     def upload_shadow_map(self, depth, light_vp_rowmajor):
         if depth is None:

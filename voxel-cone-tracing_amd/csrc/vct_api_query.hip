@@ -73,6 +73,7 @@ int run_query(vct_ctx* c, const char* who, int kind, const void* pts, int32_t n,
     VctTraceParams p;
     vct_fill_march_params(c, p, c->vol.active());
     p.cells_biased = nullptr;      // same bits without the footprint records
+    p.sky = c->sky.dev();          // sky light: the SKY forms of k_query_march (include/vct.h "sky light")
     if (gloss_class >= 0) { p.steps_specular = &c->gloss.table.get()->steps[gloss_class][0]; p.n_specular = c->gloss.nsteps[gloss_class]; }
     VctQueryArgs q;
     memset(&q, 0, sizeof(q));

@@ -276,6 +276,11 @@ int vct_launch_trace_rows(vct_ctx* c, int row0, int row1, uint16_t* out_base, in
     if (pix_gloss && (variant != 0 || c->cfg.anisotropic_mips || c->vol.want_cells))
         return vct_fail(c, VCT_ERR_INVALID, "gloss classes need the default trace kernel (config.trace_variant 0, no anisotropic mips, no footprint records)");
     if (pix_gloss) { p.gloss = c->gloss.table.get(); p.pix_gloss = pix_gloss; }
+    // sky light (include/vct.h "sky light"): the context's folded coefficients, in the COMP kernel's SKY form
+    const float* sky = c->sky.dev();
+    if (sky && (variant != 0 || c->cfg.anisotropic_mips || c->vol.want_cells))
+        return vct_fail(c, VCT_ERR_INVALID, "sky light needs the default trace kernel (config.trace_variant 0, no anisotropic mips, no footprint records)");
+    p.sky = sky;
     if (half) {
         if (row0 != 0 || row1 != vct_tiles_y(c) || row_stride > 1 || pack_rows)
             return vct_fail(c, VCT_ERR_INVALID, "trace: diffuse rate 2 traces whole frames only (no slabs, tile-row ranges or interleaved rows)");
@@ -289,7 +294,7 @@ int vct_launch_trace_rows(vct_ctx* c, int row0, int row1, uint16_t* out_base, in
             p.dr_list = cur(c).dr_list.get(); p.dr_ctr = cur(c).dr_ctr.get();
             p.dr_waves = c->diffuse_rate_waves;
         }
-    } else if (c->show_mask != VCT_SHOW_ALL || aov_which || pix_emis || pix_gloss) {
+    } else if (c->show_mask != VCT_SHOW_ALL || aov_which || pix_emis || pix_gloss || sky) {
         if (variant != 0)
             return vct_fail(c, VCT_ERR_INVALID, "lighting components / per-component outputs need the default trace kernel (config.trace_variant 0)");
         p.comp = component_word(c->show_mask, aov_which, pix_emis != nullptr);

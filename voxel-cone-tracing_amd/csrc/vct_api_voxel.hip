@@ -205,6 +205,8 @@ int vct_set_footprint_records(vct_ctx* c, int32_t on) {
         return vct_fail(c, VCT_ERR_INVALID, "vct_set_footprint_records: the half-rate diffuse gather has no footprint-record kernels (vct_set_diffuse_rate(ctx, 1) first)");
     if (on && c->gloss.n)
         return vct_fail(c, VCT_ERR_INVALID, "vct_set_footprint_records: gloss classes have no footprint-record kernels (vct_set_gloss_classes(ctx, NULL, 0) first)");
+    if (on && c->sky.attached)
+        return vct_fail(c, VCT_ERR_INVALID, "vct_set_footprint_records: sky light has no footprint-record kernels (vct_set_sky(ctx, NULL) first)");
     HIP_TRY(c, hipSetDevice(c->device));
     c->vol.want_cells = on != 0;
     PIPE_TRY(vct_pipeline_drain(c));

@@ -347,6 +347,8 @@ int vct_set_trace_variant(vct_ctx* c, int32_t variant) {
         return vct_fail(c, VCT_ERR_INVALID, "vct_set_trace_variant: variants 1 .. 4 have no pixel-emission planes (detach the emission first)");
     if (variant != 0 && c->gloss.n)
         return vct_fail(c, VCT_ERR_INVALID, "vct_set_trace_variant: variants 1 .. 4 have no gloss classes (vct_set_gloss_classes(ctx, NULL, 0) first)");
+    if (variant != 0 && c->sky.attached)
+        return vct_fail(c, VCT_ERR_INVALID, "vct_set_trace_variant: variants 1 .. 4 have no sky light (vct_set_sky(ctx, NULL) first)");
     c->cfg.trace_variant = variant;
     return VCT_OK;
 }

@@ -365,6 +365,18 @@ struct VctGloss {
     VctBuf<VctGlossTable> table;      // one element
 };
 
+// Sky light (include/vct.h "sky light", vct_api_sky.hip): the attached coefficients as given, their folded polynomial
+// form (vct_sky_check.h vct_sky_fold), and the device copy of the latter that the SKY kernels read.  Context state: every
+// frame slot and every point query sees the same sky.
+#define VCT_SKY_DEV_FLOATS 32           // 27 coefficients, padded to whole 32-byte scalar loads
+struct VctSky {
+    bool attached = false;
+    float sh[27] = {};
+    float poly[27] = {};
+    VctBuf<float> poly_dev;           // [VCT_SKY_DEV_FLOATS]
+    const float* dev() const { return attached ? poly_dev.get() : nullptr; }
+};
+
 struct vct_ctx {
     vct_config cfg;
     int device = 0;
@@ -388,6 +400,7 @@ struct vct_ctx {
     VctBuf<uint32_t> spread_lut;      // [1024] spread3(i) << 2 (vct_trace.hip: dilated anchor coordinates by scalar load)
     int n_diffuse = 0, n_specular = 0;
     VctGloss gloss;
+    VctSky sky;
     bool steps_dirty = true;
     bool fast_div = false;            // set by vct_refresh_steps: constant divisors admit the FMA division
     int last_march_form = 0;          // division of the last march launch: 1 IEEE, 2 verified product, 3 x * r (vct_get_stage_counts [2])

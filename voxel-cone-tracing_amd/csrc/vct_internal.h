@@ -319,7 +319,11 @@ struct VctTraceParams {
     // when comp != 0): bits 0-4 the VCT_SHOW_* mask, bits 8-9 the cone groups marched (1: cones 0-5, 2: cone 6), bits
     // 16-18 the VCT_AOV_* outputs written to `aov`, bit 30 VCT_COMP_EMISSION, bit 31 set.  (It fills the padding in front of slot_brick.)
     uint32_t comp;
-    const uint32_t* slot_brick;         // [nslots] the bricks a fragment of the mesh can land in (the voxelizer's slots)
+    // slot_brick is the bounce kernels', sky the screen trace's and the point queries' (include/vct.h "sky light"; the SKY
+    // forms of k_trace_tile_split, k_point_march and k_query_march, launched when sky != null): one slot, for the reason
+    // bounce_out and aov share theirs
+    union { const uint32_t* slot_brick; // [nslots] the bricks a fragment of the mesh can land in (the voxelizer's slots)
+            const float* sky; };        // [9][3] folded polynomial coefficients of the attached sky (vct_sky_check.h vct_sky_fold)
     uint32_t nslots;
     // anisotropic option: six directional chains (levels >= 1), Morton per level, each
     // `aniso_stride` texels; level k of a direction at texel offset level_off[k] - level_off[1]

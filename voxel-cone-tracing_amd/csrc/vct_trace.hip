@@ -693,12 +693,54 @@ __device__ __forceinline__ VctStep load_step(StepTable t, int k) {
             ++steps; \
         }
 
+// Sky light (include/vct.h "sky light"; p.sky: the folded polynomial coefficients [9][3]): what a marched cone adds behind
+// its loop -- the part 1 - alpha of its footprint that reached open air, times the sky's radiance along the cone.  The
+// chain is csrc/vct_sky_check.h vct_sky_eval's, operation for operation.  The 27 coefficients are wave-uniform scalar
+// loads through the constant address space, issued here and not held across the march; of the march only `alpha` and the
+// direction outlive the loop.  fmaxf is maxNum: a NaN sum gives 0, a NaN alpha T = 0, and fmaf(T, sky, NaN) stays NaN.
+typedef const __attribute__((address_space(4))) float* SkyPoly;
+__device__ __forceinline__ void sky_epilogue(const VctTraceParams& p, bool alive, F3 d, float alpha, float& cr, float& cg, float& cb) {
+    // (the pointer and the direction through empty asm: where one direction serves several marches -- the class loop of the
+    // GLOSS forms -- the loads and the five products are loop-invariant, and hoisted they live across every march: 4 VGPRs
+    // and the 8th wave of the HALF form, 6 more spilled SGPRs and 8 B of scratch in the PRIO form)
+    SkyPoly q = (SkyPoly)p.sky;
+    float x = d.x, y = d.y, z = d.z;
+    asm volatile("" : "+s"(q), "+v"(x), "+v"(y), "+v"(z));
+    const float xy = x * y, yz = y * z, zz = fmaf(3.0f * z, z, -1.0f), xz = x * z, xxyy = fmaf(x, x, -(y * y));
+    const float T = fmaxf(1.0f - alpha, 0.0f);
+    float sky[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float s = q[c];
+        s = fmaf(q[3 + c], y, s);
+        s = fmaf(q[6 + c], z, s);
+        s = fmaf(q[9 + c], x, s);
+        s = fmaf(q[12 + c], xy, s);
+        s = fmaf(q[15 + c], yz, s);
+        s = fmaf(q[18 + c], zz, s);
+        s = fmaf(q[21 + c], xz, s);
+        s = fmaf(q[24 + c], xxyy, s);
+        sky[c] = fmaxf(s, 0.0f);
+    }
+    if (alive) {          // a lane that is not alive keeps the zero cone
+        cr = fmaf(T, sky[0], cr);
+        cg = fmaf(T, sky[1], cg);
+        cb = fmaf(T, sky[2], cb);
+    }
+}
+
 // REUSE: `held` describes the block in the wave's second slab (BlockDesc); the caller keeps it across the cones of a wave
-template <bool WRAP, int FASTDIV, bool COOP, bool ANISO, bool CELLS, bool PRIO, bool REUSE>
+// SKY: VCT_SKY_INSIDE the sky epilogue above, behind the loops; VCT_SKY_ALPHA the alpha the epilogue would take goes to
+// *alpha_out and the caller applies it (the class loop of the GLOSS forms: once per lane, behind the loop).  The loop body
+// is the same in all three.
+#define VCT_SKY_NONE 0
+#define VCT_SKY_INSIDE 1
+#define VCT_SKY_ALPHA 2
+template <bool WRAP, int FASTDIV, bool COOP, bool ANISO, bool CELLS, bool PRIO, bool REUSE, int SKY = VCT_SKY_NONE>
 __device__ __forceinline__ F4 cone_march(const VctTraceParams& p, bool alive, F3 start, F3 dir,
                                          const VctStep* tab_global, int n,
                                          float4* __restrict__ blk, const LaneBlock& lb,
-                                         int& steps_out, MarchStats& ms, BlockDesc& held) {
+                                         int& steps_out, MarchStats& ms, BlockDesc& held, float* alpha_out = nullptr) {
     const StepTable tab = (StepTable)tab_global;
     float cr = 0.0f, cg = 0.0f, cb = 0.0f, occ = 0.0f;
     int steps = 0;
@@ -761,22 +803,27 @@ __device__ __forceinline__ F4 cone_march(const VctTraceParams& p, bool alive, F3
     }
     // a lane that never marched because it started with alpha = NaN: in the oracle trace.fs:94 holds once (its alpha starts
     // at 0), the sample is NaN, and then alpha is NaN
+    // (SKY: what trace.fs:94 saw last -- a lane that took no step has the oracle's initial 0, also where this march started
+    // it with NaN; if the patch below applies, the cone is NaN whatever T is)
+    [[maybe_unused]] const float alpha_seen = steps == 0 ? 0.0f : alpha;
     if (alive && steps == 0 && alpha != alpha && n > 0 && 0.0f < p.max_alpha) {
         cr = cg = cb = occ = __builtin_nanf("");
         steps = 1;
     }
+    if constexpr (SKY == VCT_SKY_INSIDE) sky_epilogue(p, alive, dir, alpha_seen, cr, cg, cb);
+    if constexpr (SKY == VCT_SKY_ALPHA) *alpha_out = alpha_seen;
     steps_out = steps;
     return {cr, cg, cb, occ};
 }
 
 // the march without block reuse
-template <bool WRAP, int FASTDIV, bool COOP, bool ANISO = false, bool CELLS = false, bool PRIO = false>
+template <bool WRAP, int FASTDIV, bool COOP, bool ANISO = false, bool CELLS = false, bool PRIO = false, int SKY = VCT_SKY_NONE>
 __device__ __forceinline__ F4 cone_march(const VctTraceParams& p, bool alive, F3 start, F3 dir,
                                          const VctStep* tab_global, int n,
                                          float4* __restrict__ blk, const LaneBlock& lb,
                                          int& steps_out, MarchStats& ms) {
     BlockDesc none = no_block();
-    return cone_march<WRAP, FASTDIV, COOP, ANISO, CELLS, PRIO, false>(p, alive, start, dir, tab_global, n, blk, lb, steps_out, ms, none);
+    return cone_march<WRAP, FASTDIV, COOP, ANISO, CELLS, PRIO, false, SKY>(p, alive, start, dir, tab_global, n, blk, lb, steps_out, ms, none);
 }
 
 // `specular`: the wave marches the specular cone (the reuse counters are kept per kind of wave)
@@ -1084,6 +1131,9 @@ static_assert(VCT_SPLIT == 3 || VCT_SPLIT == 4 || VCT_SPLIT == 7, "VCT_SPLIT mus
 // GLOSS: gloss classes (include/vct.h "per-material gloss"; p.pix_gloss, p.gloss): the specular wave marches once per class
 // present among its live lanes, each time with that class's step table and the other lanes masked off, and the composite
 // takes the lane's Phong exponent from the class headers.  Instantiated with COMP, for the plain, PRIO and HALF forms.
+// SKY: sky light (include/vct.h "sky light"; p.sky): every marched cone adds what its open remainder gathers from the
+// sky -- cone_march<.., VCT_SKY_INSIDE>, or, with GLOSS, one sky_epilogue per lane behind the class loop.  Instantiated
+// with COMP, for the plain, PRIO and HALF forms, each with and without GLOSS.
 typedef const __attribute__((address_space(4))) VctGlossTable* GlossTable;
 // the lane's class: its byte of the tile's plane under the clamp rule -- never an index before the clamp
 __device__ __forceinline__ int gloss_class_of(const VctTraceParams& p, int tile, int pix, int nclasses) {
@@ -1091,10 +1141,11 @@ __device__ __forceinline__ int gloss_class_of(const VctTraceParams& p, int tile,
     return b < nclasses ? b : 0;
 }
 template <bool WRAP, int FASTDIV, bool ANISO, bool COMPACT = false, bool CELLS = false, bool PRIO = false, bool COMP = false,
-          bool HALF = false, bool GLOSS = false>
+          bool HALF = false, bool GLOSS = false, bool SKY = false>
 __global__ void __launch_bounds__(64 * VCT_SPLIT, ANISO ? VCT_ANISO_MIN_WAVES : VCT_TRACE_MIN_WAVES)
 k_trace_tile_split(const VctTraceParams p) {
     static_assert(!GLOSS || (COMP && !ANISO && !COMPACT && !CELLS), "gloss classes: the default kernel's COMP forms only");
+    static_assert(!SKY || (COMP && !ANISO && !COMPACT && !CELLS), "sky light: the default kernel's COMP forms only");
     __shared__ float4 lds_blk[VCT_SPLIT][ANISO ? 4 : 2][64];   // per wave: level-1 slab, level-2 slab (+ their "-axis" slabs)
     __shared__ float4 lds_cone[7][64];
     __shared__ int lds_done;
@@ -1157,6 +1208,9 @@ k_trace_tile_split(const VctTraceParams p) {
     // parameter word through readfirstlane), so the march loop is not entered on a scalar branch.
     const uint32_t groups = COMP ? (uint32_t)__builtin_amdgcn_readfirstlane((int)p.comp) >> VCT_COMP_GROUPS_SHIFT : 3u;
     const int n_diffuse = (groups & 1u) ? p.n_diffuse : 0, n_specular = (groups & 2u) ? p.n_specular : 0;
+    // SKY: a table of 0 steps is a cone that is all sky, so a group nothing reads must not look like one: its lanes go
+    // into the march as not alive (the zero cone, 0 steps -- what the 0-step march gives without a sky)
+    const bool march_d = SKY ? alive && (groups & 1u) != 0u : alive, march_s = SKY ? alive && (groups & 2u) != 0u : alive;
     if (HALF && wave < VCT_SPLIT - 1) {
         // 0 steps: the wave arrives at once (the skip mechanism of COMP, without its zero cones)
     } else if (wave < VCT_SPLIT - 1) {
@@ -1165,7 +1219,7 @@ k_trace_tile_split(const VctTraceParams p) {
 #pragma unroll 1
         for (int i = wave * VCT_CONES_PER_WAVE; i < wave * VCT_CONES_PER_WAVE + VCT_CONES_PER_WAVE; ++i) {      // :196-199
             int st;
-            const F4 c = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO, REUSE>(p, alive, start, cone_dir(k0, k1, k2, i),
+            const F4 c = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO, REUSE, SKY ? VCT_SKY_INSIDE : VCT_SKY_NONE>(p, march_d, start, cone_dir(k0, k1, k2, i),
                                                                        p.steps_diffuse, n_diffuse, blk, lb, st, ms, held);
             total += st;
             lds_cone[i][lane] = make_float4(c.x, c.y, c.z, c.w);
@@ -1194,20 +1248,33 @@ k_trace_tile_split(const VctTraceParams p) {
                 lds_cone[6][lane] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                 if (p.dbg_steps && in_frame) p.dbg_steps[pixel_index() * 7 + 6] = 0;
             }
+            [[maybe_unused]] float sky_alpha = 0.0f;       // SKY: what the lane's own march saw last
             for (unsigned long long rest = ballot64(alive); rest != 0ull;) {
                 const int k = __builtin_amdgcn_readlane(cls, (int)__ffsll((long long)rest) - 1);
                 const bool mine = alive && cls == k;
                 int st;
-                const F4 sc = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO, REUSE>(p, mine, start, dir, &p.gloss->steps[k][0],
-                                                                            (groups & 2u) ? gt->nsteps[k] : 0, blk, lb, st, ms, held);
+                float a = 0.0f;
+                const F4 sc = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO, REUSE, SKY ? VCT_SKY_ALPHA : VCT_SKY_NONE>(
+                    p, mine && march_s, start, dir, &p.gloss->steps[k][0], (groups & 2u) ? gt->nsteps[k] : 0, blk, lb, st, ms, held, &a);
                 total += st;          // (0 for the lanes that did not march)
                 if (mine) lds_cone[6][lane] = make_float4(sc.x, sc.y, sc.z, sc.w);
-                store_debug_cone(p, pixel_index, 6, sc, st, mine, mine);
+                if (SKY && mine) sky_alpha = a;
+                store_debug_cone(p, pixel_index, 6, sc, st, mine && !SKY, mine);      // (SKY: the cone is stored below)
                 rest &= ~ballot64(mine);
+            }
+            if constexpr (SKY) {
+                // the sky once per lane, behind the class loop, from the alpha its own march handed out: inside the march
+                // (as in every other form) the epilogue costs the clamp-mode GLOSS kernels 4 VGPRs -- the 8th wave of the
+                // HALF form -- and the PRIO one 8 B of scratch.  Same chain, same operands, same bits.
+                const float4 v = lds_cone[6][lane];
+                F4 sc = {v.x, v.y, v.z, v.w};
+                sky_epilogue(p, march_s, dir, sky_alpha, sc.x, sc.y, sc.z);
+                lds_cone[6][lane] = make_float4(sc.x, sc.y, sc.z, sc.w);
+                store_debug_cone(p, pixel_index, 6, sc, 0, alive, false);
             }
         } else {
         int st6;
-        const F4 sc = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO, REUSE>(p, alive, start, specular_dir(P, N, p.cam),
+        const F4 sc = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO, REUSE, SKY ? VCT_SKY_INSIDE : VCT_SKY_NONE>(p, march_s, start, specular_dir(P, N, p.cam),
                                                                     p.steps_specular, n_specular, blk, lb, st6, ms, held);
         total += st6;
         lds_cone[6][lane] = make_float4(sc.x, sc.y, sc.z, sc.w);
@@ -1276,7 +1343,7 @@ __device__ __forceinline__ uint32_t lane_rank(unsigned long long m) {
 #endif
 // WAVES = 1: one wave marches the six cones of its 64 points (the shape of k_bounce_march); 2: a workgroup of two waves
 // with cones 0-2 and 3-5, the second hands its three over in LDS and the first folds all six in the oracle's order.
-template <bool WRAP, int FASTDIV, bool LISTED, int WAVES>
+template <bool WRAP, int FASTDIV, bool LISTED, int WAVES, bool SKY = false>
 __global__ void __launch_bounds__(64 * WAVES, VCT_POINT_MIN_WAVES)
 k_point_march(const VctTraceParams p) {
     __shared__ float4 lds_blk[WAVES][2][64];
@@ -1327,8 +1394,8 @@ k_point_march(const VctTraceParams p) {
 #pragma unroll 1
         for (int i = first; i < first + 6 / WAVES; ++i) {
             int st;
-            const F4 c = cone_march<WRAP, FASTDIV, true>(p, alive, start, cone_dir(k0, k1, k2, i), p.steps_diffuse, p.n_diffuse,
-                                                         blk, lb, st, ms);
+            const F4 c = cone_march<WRAP, FASTDIV, true, false, false, false, SKY ? VCT_SKY_INSIDE : VCT_SKY_NONE>(p, alive, start, cone_dir(k0, k1, k2, i), p.steps_diffuse,
+                                                                                   p.n_diffuse, blk, lb, st, ms);
             total += st;
             bool handed = false;
             if constexpr (WAVES == 2) {
@@ -1385,7 +1452,7 @@ __device__ __forceinline__ void store_vec4(float* dst, F4 c) {
     o.v[0] = c.x; o.v[1] = c.y; o.v[2] = c.z; o.v[3] = c.w;
     *(VctFloats4*)dst = o;
 }
-template <bool WRAP, int FASTDIV, int KIND, bool DEBUG>
+template <bool WRAP, int FASTDIV, int KIND, bool DEBUG, bool SKY = false>
 __global__ void __launch_bounds__(64, VCT_POINT_MIN_WAVES)
 k_query_march(const VctTraceParams p, const VctQueryArgs q) {
     __shared__ float4 lds_blk[2][64];
@@ -1412,8 +1479,8 @@ k_query_march(const VctTraceParams p, const VctQueryArgs q) {
 #pragma unroll 1
             for (int c = 0; c < 6; ++c) {
                 int st;
-                const F4 v = cone_march<WRAP, FASTDIV, true>(p, alive, start, cone_dir(k0, k1, k2, c), p.steps_diffuse, p.n_diffuse,
-                                                             blk, lb, st, ms);
+                const F4 v = cone_march<WRAP, FASTDIV, true, false, false, false, SKY ? VCT_SKY_INSIDE : VCT_SKY_NONE>(p, alive, start, cone_dir(k0, k1, k2, c), p.steps_diffuse,
+                                                                                       p.n_diffuse, blk, lb, st, ms);
                 total += st;
                 ind = fold_cone(ind, c, v);
                 if (DEBUG && alive) {
@@ -1427,7 +1494,8 @@ k_query_march(const VctTraceParams p, const VctQueryArgs q) {
             const F3 start = cone_start(f3(r.v[0], r.v[1], r.v[2]), f3(r.v[3], r.v[4], r.v[5]), p.vs);
             const VctStep* tab = q.specular ? p.steps_specular : p.steps_diffuse;          // (wave-uniform)
             const int nsteps = q.specular ? p.n_specular : p.n_diffuse;
-            const F4 v = cone_march<WRAP, FASTDIV, true>(p, alive, start, f3(r.v[6], r.v[7], r.v[8]), tab, nsteps, blk, lb, total, ms);
+            const F4 v = cone_march<WRAP, FASTDIV, true, false, false, false, SKY ? VCT_SKY_INSIDE : VCT_SKY_NONE>(p, alive, start, f3(r.v[6], r.v[7], r.v[8]), tab, nsteps, blk, lb,
+                                                                                   total, ms);
             if (alive) {
                 store_vec4(q.out + i * 4, v);
                 if (DEBUG) q.out_steps[i] = (uint8_t)total;
@@ -1810,7 +1878,16 @@ hipError_t launch(const VctTraceParams& p, int blocks, hipStream_t s) {
 template <bool WRAP, int FASTDIV, bool COMP>
 void launch_split(const VctTraceParams& p, int blocks, hipStream_t s) {
     const dim3 grid(blocks), block(64 * VCT_SPLIT);
-    if constexpr (COMP) {     // gloss classes (the host launches them with p.comp on, and refuses them beside the two options below)
+    if constexpr (COMP) {     // sky light and gloss classes (the host launches them with p.comp on, and refuses them beside the two options below)
+        if (p.sky) {
+            with_flag(p.pix_gloss != nullptr, [&](auto gloss) {
+                with_flag(!p.spec_prio, [&](auto prio) {
+                    hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, decltype(prio)::value, true, false,
+                                                           decltype(gloss)::value, true>), grid, block, 0, s, p);
+                });
+            });
+            return;
+        }
         if (p.pix_gloss) {
             if (!p.spec_prio)
                 hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, true, true, false, true>), grid, block, 0, s, p);
@@ -1836,6 +1913,11 @@ void launch_split(const VctTraceParams& p, int blocks, hipStream_t s) {
 // the four launches of a half-rate pass (p.dr_ind set: whole frame, default kernel, p.comp on); marks: see vct_launch_trace
 template <bool WRAP, int FASTDIV, int WAVES>
 void launch_point_march(const VctTraceParams& p, bool listed, int blocks, hipStream_t s) {
+    if (p.sky) {          // sky light: the marches of a half-rate pass add it as rate 1's do
+        if (listed) hipLaunchKernelGGL((k_point_march<WRAP, FASTDIV, true, WAVES, true>), dim3(blocks), dim3(64 * WAVES), 0, s, p);
+        else hipLaunchKernelGGL((k_point_march<WRAP, FASTDIV, false, WAVES, true>), dim3(blocks), dim3(64 * WAVES), 0, s, p);
+        return;
+    }
     if (listed) hipLaunchKernelGGL((k_point_march<WRAP, FASTDIV, true, WAVES>), dim3(blocks), dim3(64 * WAVES), 0, s, p);
     else hipLaunchKernelGGL((k_point_march<WRAP, FASTDIV, false, WAVES>), dim3(blocks), dim3(64 * WAVES), 0, s, p);
 }
@@ -1857,7 +1939,12 @@ hipError_t launch_half_rate(const VctTraceParams& p, int blocks, hipStream_t s, 
     if (p.dr_waves == 2) launch_point_march<WRAP, FASTDIV, 2>(p, true, listed_blocks, s);
     else launch_point_march<WRAP, FASTDIV, 1>(p, true, listed_blocks, s);
     if ((e = hipGetLastError()) != hipSuccess || (e = mark(2)) != hipSuccess) return e;
-    if (p.pix_gloss)
+    if (p.sky)
+        with_flag(p.pix_gloss != nullptr, [&](auto gloss) {
+            hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, true, true, true, decltype(gloss)::value, true>),
+                               dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
+        });
+    else if (p.pix_gloss)
         hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, true, true, true, true>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
     else hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, true, true, true>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
     return hipGetLastError();
@@ -1953,7 +2040,8 @@ hipError_t launch_query(const VctTraceParams& p, const VctQueryArgs& q, int kind
     with_flag(kind == VCT_QUERY_GATHER, [&](auto gather) {
         with_flag(q.out_cones || q.out_steps, [&](auto debug) {
             constexpr int KIND = decltype(gather)::value ? VCT_QUERY_GATHER : VCT_QUERY_CONE;
-            hipLaunchKernelGGL((k_query_march<WRAP, FASTDIV, KIND, decltype(debug)::value>), grid, block, 0, s, p, q);
+            if (p.sky) hipLaunchKernelGGL((k_query_march<WRAP, FASTDIV, KIND, decltype(debug)::value, true>), grid, block, 0, s, p, q);
+            else hipLaunchKernelGGL((k_query_march<WRAP, FASTDIV, KIND, decltype(debug)::value>), grid, block, 0, s, p, q);
         });
     });
     return hipGetLastError();
@@ -2021,6 +2109,7 @@ hipError_t vct_launch_trace(const VctTraceParams& params, int variant, hipStream
     if (p.ntiles <= 0) return hipSuccess;
     if ((rstride > 1 || p.pack_rows) && !vct_variant_takes_row_subsets(variant)) return hipErrorInvalidValue;
     if (p.pix_gloss && (variant != 0 || p.aniso || p.cells_biased || !p.comp || !p.gloss)) return hipErrorInvalidValue;
+    if (p.sky && (variant != 0 || p.aniso || p.cells_biased || !p.comp)) return hipErrorInvalidValue;
     if (p.dr_ind && (variant != 0 || p.aniso || p.cells_biased || !p.comp || rstride > 1 || p.pack_rows || p.tile_row0 != 0 ||
                      p.tile_row1 != p.tiles_y))
         return hipErrorInvalidValue;

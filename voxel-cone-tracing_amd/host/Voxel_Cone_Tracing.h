@@ -233,6 +233,11 @@ struct Voxel_Cone_Tracing {
     std::vector<vct_gloss_class> GlossClasses;
     std::vector<uint8_t> Gloss;                      // [materials]
     bool gloss_dirty = false;
+    // Sky light (vct_set_sky, include/vct.h: the reference's cones return black from open air): nine spherical-harmonic
+    // coefficients per channel, all zero (the default) is no sky and the reference's frame.  SetSky / SetSkyGradient change
+    // them; the next Render() hands them over -- no volume rebuild, the voxels know nothing of the sky.
+    float Sky[9][3] = {};
+    bool sky_dirty = false;
     int Bounces = 1;    // 2 = re-inject the lit voxels once (the "2 bounces" of the reference's README.md:16,
                         // which its code does not implement: VCT.h:138-139 injects once); set before init
 
@@ -354,6 +359,18 @@ struct Voxel_Cone_Tracing {
         return true;
     }
 
+    // The sky: coefficients as vct_set_sky takes them (NULL: none), or the three colours of a gradient about `up` (NULL: +y)
+    // through vcth_sky_gradient; picked up by the next Render().
+    void SetSky(const float sh[9][3]) {
+        if (sh) memcpy(Sky, sh, sizeof(Sky));
+        else memset(Sky, 0, sizeof(Sky));
+        sky_dirty = true;
+    }
+    void SetSkyGradient(const float zenith[3], const float horizon[3], const float ground[3], const float up[3] = nullptr) {
+        vcth_sky_gradient(zenith, horizon, ground, up, Sky);
+        sky_dirty = true;
+    }
+
     // the five Show* switches as VCT_SHOW_* bits
     uint32_t ShowMask() const {
         return (ShowDiffuse ? (uint32_t)VCT_SHOW_DIFFUSE : 0u) | (ShowIndirectDiffuse ? (uint32_t)VCT_SHOW_INDIRECT_DIFFUSE : 0u) |
@@ -372,6 +389,10 @@ struct Voxel_Cone_Tracing {
             if (last_status != VCT_OK) return;
         }
         if (gloss_dirty && !UploadGloss()) return;              // changed classes: the G-buffer pass below writes them
+        if (sky_dirty) {                                        // a refused sky stays pending, like a refused emission table
+            sky_dirty = !check(vct_set_sky(ctx, Sky), "vct_set_sky");
+            if (sky_dirty) return;
+        }
         const float cam[3] = {camera.position.x, camera.position.y, camera.position.z};   // VCT.h:167
         const float L[3] = {lightDirection.x, lightDirection.y, lightDirection.z};         // VCT.h:168
         vct_set_camera_position(ctx, cam);

@@ -10,7 +10,13 @@
 //            [--voxels [current|radiance|albedo|normal[:level]]] [--ambient-cubes NX,NY,NZ FILE] [--dump-chain FILE]
 //            [--emission MATERIAL=R,G,B[;MATERIAL=R,G,B...]]
 //            [--gloss-classes TAN,SHIN[;TAN,SHIN...] --gloss MATERIAL=CLASS[;MATERIAL=CLASS...]]
+//            [--sky-gradient ZR,ZG,ZB;HR,HG,HB;GR,GG,GB[;UX,UY,UZ] | --sky-sh FILE]
 //
+// --sky-gradient COLOURS / --sky-sh FILE: sky light (Voxel_Cone_Tracing::SetSkyGradient / SetSky, vct_set_sky): what a
+//   cone gathers from the part of its footprint that reaches open air.  The gradient form takes a zenith, a horizon and a
+//   ground colour and an optional up vector (+y) and lights with their second-order spherical-harmonic projection
+//   (vcth_sky_gradient); the file form takes the 27 coefficients sh[i][c] themselves.  --sky-gradient
+//   "0.3,0.5,1.0;0.8,0.8,0.8;0.1,0.1,0.1" is a blue sky over a dark floor.  Both are checked before a GPU is touched.
 // --gloss-classes LIST --gloss LIST: per-material gloss (Voxel_Cone_Tracing::SetGlossClasses / SetGloss,
 //   vct_set_gloss_classes): up to 8 classes of (specular cone aperture as tan of the half angle, Phong exponent) and the
 //   class of the listed material indices (the others are class 0).  --gloss-classes "0.07,20;0.2,4" --gloss "2=1" gives
@@ -113,6 +119,8 @@ int main(int argc, char** argv) {
     const char* emission = nullptr;
     const char* gloss_classes_arg = nullptr;
     const char* gloss_arg = nullptr;
+    const char* sky_gradient_arg = nullptr;
+    const char* sky_sh_arg = nullptr;
     int cubes[3] = {0, 0, 0};
     bool show_voxels = false;
     int view_source = VCT_VOXVIEW_CURRENT, view_level = 0;
@@ -155,6 +163,8 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--emission")) emission = argv[++i];
         else if (!strcmp(argv[i], "--gloss-classes")) gloss_classes_arg = argv[++i];
         else if (!strcmp(argv[i], "--gloss")) gloss_arg = argv[++i];
+        else if (!strcmp(argv[i], "--sky-gradient")) sky_gradient_arg = argv[++i];
+        else if (!strcmp(argv[i], "--sky-sh")) sky_sh_arg = argv[++i];
         else if (!strcmp(argv[i], "--ambient-cubes") && i + 2 < argc) {
             if (sscanf(argv[++i], "%d,%d,%d", &cubes[0], &cubes[1], &cubes[2]) != 3 || cubes[0] < 1 || cubes[1] < 1 || cubes[2] < 1 ||
                 (long long)cubes[0] * cubes[1] * cubes[2] * 6 > VCT_POINT_QUERY_MAX) {
@@ -178,6 +188,20 @@ int main(int argc, char** argv) {
             fprintf(stderr, "--gloss: MATERIAL=CLASS[;...] with classes below %zu (at '%s')\n", gloss_classes.size(), at);
             return 1;
         }
+    }
+    float sky_sh[9][3] = {};                                // --sky-gradient / --sky-sh: before a GPU is touched
+    if (sky_gradient_arg && sky_sh_arg) { fprintf(stderr, "--sky-gradient and --sky-sh: one sky per context\n"); return 1; }
+    if (sky_gradient_arg) {
+        float zenith[3], horizon[3], ground[3], up[3];
+        if (const char* at = vct_demo_parse_sky_gradient(sky_gradient_arg, zenith, horizon, ground, up)) {
+            fprintf(stderr, "--sky-gradient: ZR,ZG,ZB;HR,HG,HB;GR,GG,GB[;UX,UY,UZ], finite numbers, up not zero (at '%s')\n", at);
+            return 1;
+        }
+        vcth_sky_gradient(zenith, horizon, ground, up, sky_sh);
+    }
+    if (sky_sh_arg && !vct_demo_read_sky_sh(sky_sh_arg, sky_sh)) {
+        fprintf(stderr, "--sky-sh: %s does not hold 27 finite numbers\n", sky_sh_arg);
+        return 1;
     }
     GLFWwindow* window = nullptr;          // no window system on a compute node
 
@@ -264,6 +288,8 @@ int main(int argc, char** argv) {
                 return 1;
             }
     }
+
+    if (sky_gradient_arg || sky_sh_arg) voxel_cone_tracing.SetSky(sky_sh);      // picked up by the first Render()
 
     float delta_time = 0.05f;
     voxel_cone_tracing.Render();                            // frame 0 pays first-launch costs

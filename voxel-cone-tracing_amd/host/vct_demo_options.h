@@ -43,4 +43,43 @@ static inline const char* vct_demo_parse_gloss(const char* list, int nclasses, s
     return out.empty() ? list : nullptr;
 }
 
+// --sky-gradient ZR,ZG,ZB;HR,HG,HB;GR,GG,GB[;UX,UY,UZ]: zenith, horizon and ground colour (finite) and an optional up
+// vector (finite, not zero; +y when left out), for vcth_sky_gradient.  Returns null or the offending place.
+static inline const char* vct_demo_parse_sky_gradient(const char* list, float zenith[3], float horizon[3], float ground[3], float up[3]) {
+    float* const dst[4] = {zenith, horizon, ground, up};
+    up[0] = 0.0f; up[1] = 1.0f; up[2] = 0.0f;
+    const char* q = list;
+    int k = 0;
+    for (; k < 4 && *q; ++k) {
+        float v[3] = {0.0f, 0.0f, 0.0f};
+        int used = 0;
+        if (sscanf(q, "%f,%f,%f%n", &v[0], &v[1], &v[2], &used) != 3) return q;
+        for (int i = 0; i < 3; ++i)
+            if (v[i] != v[i] || isinf(v[i])) return q;
+        if (k == 3 && v[0] == 0.0f && v[1] == 0.0f && v[2] == 0.0f) return q;
+        for (int i = 0; i < 3; ++i) dst[k][i] = v[i];
+        q += used;
+        if (*q == ';') { if (!q[1]) return q; ++q; }
+        else if (*q) return q;
+    }
+    return (k < 3 || *q) ? q : nullptr;
+}
+
+// --sky-sh FILE: 27 numbers separated by white space, sh[i][c] with the channel running fastest (the table of vct_set_sky);
+// finite, and nothing but white space behind them.  Returns false when the file is unreadable or is not that.
+static inline bool vct_demo_read_sky_sh(const char* path, float sh[9][3]) {
+    FILE* f = fopen(path, "r");
+    if (!f) return false;
+    bool ok = true;
+    for (int i = 0; i < 27 && ok; ++i) {
+        float v = 0.0f;
+        ok = fscanf(f, "%f", &v) == 1 && v == v && !isinf(v);
+        sh[i / 3][i % 3] = v;
+    }
+    char extra;
+    if (ok && fscanf(f, " %c", &extra) == 1) ok = false;
+    fclose(f);
+    return ok;
+}
+
 #endif

@@ -1077,6 +1077,38 @@ void vcth_frame_from_normal(const float n[3], float scale, float t[3], float b[3
     for (int i = 0; i < 3; ++i) { t[i] = (float)(c[i] * (double)scale); b[i] = (float)(d[i] * (double)scale); }
 }
 
+void vcth_sky_gradient(const float zenith[3], const float horizon[3], const float ground[3], const float up[3], float sh[9][3]) {
+    const double PI = 3.14159265358979323846;
+    const double K0 = 0.28209479177387814, K1 = 0.4886025119029199, K4 = 1.0925484305920792, K6 = 0.31539156525252005,
+                 K8 = 0.5462742152960396;
+    // unit up, scaled by its largest component first (vcth_frame_from_normal's reason); zero or non-finite: +y
+    double u[3] = {0.0, 1.0, 0.0};
+    if (up) {
+        const double ax = fabs((double)up[0]), ay = fabs((double)up[1]), az = fabs((double)up[2]);
+        const double m = ax > ay ? (ax > az ? ax : az) : (ay > az ? ay : az);
+        if (ax + ay + az > 0.0 && ax + ay + az < 1.1e39) {
+            for (int i = 0; i < 3; ++i) u[i] = (double)up[i] / m;
+            const double lu = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+            for (double& v : u) v /= lu;
+        }
+    }
+    const double x = u[0], y = u[1], z = u[2];
+    // Y_lm(up) in index order l(l+1)+m, and sqrt(4 pi / (2l + 1)) of each band
+    const double Y[9] = {K0, K1 * y, K1 * z, K1 * x, K4 * x * y, K4 * y * z, K6 * (3.0 * z * z - 1.0), K4 * x * z, K8 * (x * x - y * y)};
+    const double band[3] = {sqrt(4.0 * PI), sqrt(4.0 * PI / 3.0), sqrt(4.0 * PI / 5.0)};
+    for (int c = 0; c < 3; ++c) {
+        const double zc = (double)zenith[c], h = (double)horizon[c], g = (double)ground[c];
+        // zonal coefficients of L(t) = h + (z - h) max(t, 0) + (g - h) max(-t, 0) about `up`: a_l = 2 pi int L(t) Y_l0(t) dt
+        const double a[3] = {sqrt(4.0 * PI) * (h + (zc - h) / 4.0 + (g - h) / 4.0),
+                             K1 * 2.0 * PI * ((zc - h) - (g - h)) / 3.0,
+                             K6 * 2.0 * PI * (zc + g - 2.0 * h) / 4.0};
+        for (int i = 0; i < 9; ++i) {
+            const int l = i == 0 ? 0 : (i < 4 ? 1 : 2);
+            sh[i][c] = (float)(band[l] * a[l] * Y[i]);
+        }
+    }
+}
+
 void vcth_light_view_proj(const float L[3], float out_vp[16]) {
     const M4 v = look_at({L[0], L[1], L[2]}, {0, 0, 0}, {0, 1, 0});     // VCT.h:84
     const M4 p = ortho(-120, 120, -120, 120, -100, 100);                // VCT.h:85

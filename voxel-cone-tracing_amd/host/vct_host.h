@@ -79,6 +79,14 @@ int32_t vcth_invert_matrix(const float m[16], float out_inv[16]);
  * works (never NaN, no overflow, no underflow); the helper axis is chosen by a branch on n's dominant axis.  n = 0 or a
  * non-finite n gives t = b = 0. */
 void vcth_frame_from_normal(const float n[3], float scale, float t[3], float b[3]);
+/* A sky for vct_set_sky (include/vct.h "sky light") from three colours: the nine-coefficient projection, per channel, of
+ *   L(d) = horizon + (zenith - horizon) * max(t, 0) + (ground - horizon) * max(-t, 0),   t = dot(d, up) / |up|
+ * computed in double from the closed form -- zonal coefficients a_0 = sqrt(4 pi) (h + (z - h) / 4 + (g - h) / 4),
+ * a_1 = K_1 2 pi ((z - h) - (g - h)) / 3, a_2 = K_6 2 pi (z + g - 2 h) / 4, rotated to `up` by
+ * L_lm = sqrt(4 pi / (2l + 1)) a_l Y_lm(up) -- and rounded to float once.  The sky the library then lights with is that
+ * second-order series, NOT the gradient itself: it is smooth across the horizon and overshoots the three colours a
+ * little (equal colours are reproduced exactly).  up = NULL, zero or non-finite counts as +y. */
+void vcth_sky_gradient(const float zenith[3], const float horizon[3], const float ground[3], const float up[3], float sh[9][3]);
 
 /* VCT.h:84-86: DepthViewProjectionMatrix = ortho(-120,120,-120,120,-100,100) * lookAt(L,0,+Y),
  * column-major. */

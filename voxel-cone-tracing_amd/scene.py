@@ -33,6 +33,8 @@ _lib.vcth_camera_view_proj.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_voi
 _lib.vcth_invert_matrix.argtypes = [C.c_void_p, C.c_void_p]
 _lib.vcth_frame_from_normal.restype = None
 _lib.vcth_frame_from_normal.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
+_lib.vcth_sky_gradient.restype = None
+_lib.vcth_sky_gradient.argtypes = [C.c_void_p] * 5
 _lib.vcth_scene_save.argtypes = [C.c_void_p, C.c_char_p]
 _lib.vcth_scene_load_cache.restype = C.c_void_p
 _lib.vcth_scene_load_cache.argtypes = [C.c_char_p, C.c_char_p]
@@ -99,6 +101,16 @@ def frame_from_normal(normal, scale=1.0):
     t, b = np.zeros(3, np.float32), np.zeros(3, np.float32)
     _lib.vcth_frame_from_normal(n.ctypes.data, float(scale), t.ctypes.data, b.ctypes.data)
     return t, b
+
+
+def sky_gradient(zenith, horizon, ground, up=None):
+    """float32 [9, 3] for Context.set_sky: the second-order spherical-harmonic projection of a sky that runs from `horizon`
+    to `zenith` towards `up` (+y when None) and to `ground` away from it.  The sky is that series, not the gradient."""
+    z, h, g = (np.ascontiguousarray(v, np.float32).reshape(3) for v in (zenith, horizon, ground))
+    u = None if up is None else np.ascontiguousarray(up, np.float32).reshape(3)
+    sh = np.zeros((9, 3), np.float32)
+    _lib.vcth_sky_gradient(z.ctypes.data, h.ctypes.data, g.ctypes.data, None if u is None else u.ctypes.data, sh.ctypes.data)
+    return sh
 
 
 def light_view_proj(light_dir):

@@ -66,7 +66,7 @@ def main():
                         "-fno-slp-vectorize", "-fPIC", "-Wno-unused-function", "-S", "--cuda-device-only", "-o", out, src],
                        check=True, capture_output=True)
         text = open(out).read()
-    m = re.search(r"^_ZN12_GLOBAL__N_118k_trace_tile_splitILb1ELi1ELb0ELb0ELb0ELb1ELb0ELb0EEEv14VctTraceParams:.*?\.end_amdhsa_kernel", text, re.S | re.M)
+    m = re.search(r"^_ZN12_GLOBAL__N_118k_trace_tile_splitILb1ELi1ELb0ELb0ELb0ELb1ELb0ELb0ELb0ELb0EEEv14VctTraceParams:.*?\.end_amdhsa_kernel", text, re.S | re.M)
     body = m.group(0).split("\n")
     # the specular march = the largest depth-1 inner loop (the diffuse march, inside the cone loop, is depth 2 and has the
     # same body; small depth-1 loops, if any, are prologue code)
@@ -156,8 +156,9 @@ def main():
         res["salu_pipe_busy_model"] = round(t["wave_instructions_per_launch"]["salu"] * SALU_CYCLES
                                             / 1024.0 / t["gpu_cycles_per_launch"], 3)
         # the PMC count also holds what a tile executes outside the march -- prologue, per-cone set-up, composite: about
-        # 1,700 VALU wave-instructions per tile of the default 1080p frame's 240 x 135 tiles
-        outside = 1700.0 * 240 * 135 / stats["wave_steps"]
+        # 1,530 VALU wave-instructions per tile (1,700 before the tile's divisions, the light vector and
+        # the second E left the waves: -170 per tile by SQ_INSTS_VALU) of the default 1080p frame's 240 x 135 tiles
+        outside = 1530.0 * 240 * 135 / stats["wave_steps"]
         res["valu_per_wave_step_outside_march"] = round(outside, 1)
         ok = abs(measured - (n_step + outside)) / measured < 0.08
     else:

@@ -265,6 +265,7 @@ struct VctTraceParams {
     int32_t fast_div;                   // 1: every constant divisor admits the FMA-corrected division
     float cam[3];
     float light[3];
+    float light_unit[3];                // normalize(light), the composite's L (vct_tilediv.h vct_light_unit): set by vct_launch_trace
     float ambient, shininess, max_alpha;
     int32_t wrap_repeat;
     const uint32_t* spread_lut;         // [1024] spread3(i) << 2: dilated byte offsets of an x coordinate (scalar loads)
@@ -282,6 +283,7 @@ struct VctTraceParams {
     int32_t row_stride, pack_rows;
     int32_t ntiles;                     // tiles of this launch (rows traced x tiles_x): set by vct_launch_trace
     int32_t spec_prio;                  // 1: the specular waves raise their issue priority (slab launches, vct_trace.hip)
+    uint32_t tile_mul, tile_shift;      // tile / tiles_x without a division (vct_tilediv.h): set by vct_launch_trace
     const float* gbuf;                  // tiled [tile][23][64]
     uint16_t* out;                      // RGBA16F [h][w][4]
     uint8_t* dbg_steps;                 // [npix][7] or null

@@ -50,6 +50,7 @@
 #include "../../include/vct.h"
 #include "vct_internal.h"
 #include "vct_texel.h"
+#include "vct_tilediv.h"
 
 
 namespace {
@@ -911,9 +912,16 @@ __device__ __forceinline__ F4 gather_six_cones(F3 b0, F3 b1, F3 b2, int& total, 
     return ind;
 }
 // the specular cone runs along reflect(-E, N) with the bump normal N (planes 12-14)     trace.fs:217-218
-__device__ __forceinline__ F3 specular_dir(F3 P, F3 N, const float cam[3]) {
-    const F3 E = normalize3(f3(cam[0] - P.x, cam[1] - P.y, cam[2] - P.z));              // :181
+// E, the unit vector from the point to the camera (:181), is the composite's too (:213): the one copy of its arithmetic
+__device__ __forceinline__ F3 eye_dir(F3 P, const float cam[3]) {
+    return normalize3(f3(cam[0] - P.x, cam[1] - P.y, cam[2] - P.z));                    // :181
+}
+__device__ __forceinline__ F3 specular_dir(F3 E, F3 N) {
     return normalize3(reflect3(f3(E.x * -1.0f, E.y * -1.0f, E.z * -1.0f), N));          // :217
+}
+// tile / tiles_x, both below 2^31, by the launch's multiplier and shift (vct_tilediv.h; set by vct_launch_trace)
+__device__ __forceinline__ int tile_row_of(const VctTraceParams& p, int tile) {
+    return (int)vct_tilediv((uint32_t)tile, (uint32_t)p.tiles_x, p.tile_mul, p.tile_shift);
 }
 // config.debug_outputs: cone i's raw vec4 and step count.  `pixel()` re-derives the pixel's index per store (see k_trace_tile)
 template <class Pixel>
@@ -928,8 +936,9 @@ __device__ __forceinline__ void store_debug_cone(const VctTraceParams& p, Pixel 
 // a discarded pixel keeps the clear colour (alpha 1)                                VCT.h:156-159
 __device__ __forceinline__ float clear_colour(const VctTraceParams& p) { return p.ambient < 0.5f ? 0.5f : 1.0f; }
 
-// The composite of one pixel inside the frame from its gathered diffuse cones `ind` and its specular cone `sc`, read
-// from planes 0-2 and 12-22 of `gb`                                                trace.fs:179-227
+// The composite of one pixel inside the frame from its gathered diffuse cones `ind`, its specular cone `sc` and its eye
+// vector E (eye_dir: the specular cone's set-up has it already), read from planes 12-22 of `gb`        trace.fs:179-227
+// L = normalize(LightDirection) is the launch's: p.light_unit, the same bits from the host (vct_tilediv.h).
 // COMP: the Show* ternaries (include/vct.h) as selects on the wave-uniform mask, and the per-component outputs.
 // VCT_SHOW_ALL selects every unmasked value, and without COMP every select is decided here: the operations and their
 // order are the same in all three cases.
@@ -937,13 +946,12 @@ __device__ __forceinline__ float clear_colour(const VctTraceParams& p) { return 
 // E from the launch's pixel-emission planes at em_offset() = tile * 192 + lane (include/vct.h "emissive materials").
 // `shininess`: the exponent of :213 -- p.shininess, or the lane's gloss class's (k_trace_tile_split<.., GLOSS = true>).
 template <bool COMP, class V4, class Pixel, class EmOffset>
-__device__ __forceinline__ void composite(const VctTraceParams& p, const float* gb, F4 ind, V4 sc,
+__device__ __forceinline__ void composite(const VctTraceParams& p, const float* gb, F4 ind, V4 sc, F3 E,
                                           bool alive, Pixel pixel, EmOffset em_offset, float shininess) {
-    const F3 P = gb_planes3(gb, 0), N = gb_planes3(gb, 12);
+    const F3 N = gb_planes3(gb, 12);
     const float alb_r = gb_plane(gb, 15), alb_g = gb_plane(gb, 16), alb_b = gb_plane(gb, 17), alb_a = gb_plane(gb, 18);
     const float shadow = gb_plane(gb, 22);
-    const F3 L = normalize3(f3(p.light[0], p.light[1], p.light[2]));        // :179
-    const F3 E = normalize3(f3(p.cam[0] - P.x, p.cam[1] - P.y, p.cam[2] - P.z));   // :181
+    const F3 L = f3(p.light_unit[0], p.light_unit[1], p.light_unit[2]);    // :179
     const float cos_theta = fmaxf(dot3(N, L), 0.0f);                        // :188
     const uint32_t comp = COMP ? (uint32_t)__builtin_amdgcn_readfirstlane((int)p.comp) : 0u;
     const uint32_t show = COMP ? comp & (uint32_t)VCT_SHOW_ALL : (uint32_t)VCT_SHOW_ALL;
@@ -1053,7 +1061,7 @@ k_trace_tile(const VctTraceParams p) {
     MarchStats ms = {};
 
     const int tile = p.tile_row0 * p.tiles_x + ti;
-    const int ty = tile / p.tiles_x, tx = tile - ty * p.tiles_x;
+    const int ty = tile_row_of(p, tile), tx = tile - ty * p.tiles_x;
     // Pixel / G-buffer addresses are re-derived from the lane id wherever they are needed (a few
     // integer ops) rather than carried in 64-bit VGPR pairs across the march loops, where they
     // would be spilled to scratch under the 80-VGPR budget.
@@ -1083,15 +1091,15 @@ k_trace_tile(const VctTraceParams p) {
 
     // stage 2: the specular cone, from a fresh pointer: re-read instead of keeping planes live
     const float* gb2 = gbuf_ptr(fresh_lane());
-    const F3 Rd = specular_dir(gb_planes3(gb2, 0), gb_planes3(gb2, 12), p.cam);
+    const F3 Rd = specular_dir(eye_dir(gb_planes3(gb2, 0), p.cam), gb_planes3(gb2, 12));
     int st6;
     const F4 sc = cone_march<WRAP, FASTDIV, COOP>(p, alive, start, Rd, p.steps_specular, p.n_specular, blk, lb, st6, ms);
     total += st6;
     store_debug_cone(p, pixel_index, 6, sc, st6, alive, in_frame);
 
-    // stage 3: composite
+    // stage 3: composite (E again from planes 0-2: three L1 re-reads, against three registers live across the march)
     const float* gb3 = gbuf_ptr(fresh_lane());
-    if (in_frame) composite<false>(p, gb3, ind, sc, alive, pixel_index, [] { return (size_t)0; }, p.shininess);
+    if (in_frame) composite<false>(p, gb3, ind, sc, eye_dir(gb_planes3(gb3, 0), p.cam), alive, pixel_index, [] { return (size_t)0; }, p.shininess);
     // executed-step count: wave reduction, stored into the tile's slot (a plain store: no atomic, nothing to clear)
     total = wave_sum(total);
     if (lane == 0) p.tile_steps[tile] = (uint32_t)total;
@@ -1148,12 +1156,15 @@ k_trace_tile_split(const VctTraceParams p) {
     static_assert(!SKY || (COMP && !ANISO && !COMPACT && !CELLS), "sky light: the default kernel's COMP forms only");
     __shared__ float4 lds_blk[VCT_SPLIT][ANISO ? 4 : 2][64];   // per wave: level-1 slab, level-2 slab (+ their "-axis" slabs)
     __shared__ float4 lds_cone[7][64];
-    __shared__ int lds_done;
-    __shared__ int lds_steps;          // executed steps of the tile's waves, summed here; the last arriver stores the total
+    // Arrival word: bits 28-31 count the waves that have arrived, bits 0-27 sum their executed steps -- one returning
+    // atomic per wave raises both, and the last arriver stores the total.  A tile executes at most 64 lanes x (6 diffuse
+    // cones + 8 gloss classes) x VCT_MAX_STEPS steps, and VCT_SPLIT arrivals fit four bits:
+    static_assert(64ull * (6 + 8) * VCT_MAX_STEPS < (1ull << 28) && VCT_SPLIT < 16, "the arrival word holds count and step total");
+    __shared__ uint32_t lds_arrive;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     float4* blk = &lds_blk[wave][0][0];
-    if (threadIdx.x == 0) { lds_done = 0; lds_steps = 0; }
+    if (threadIdx.x == 0) lds_arrive = 0u;
     __syncthreads();
 
     const int ntiles = p.ntiles;          // (host-computed: a division here is ~40 instructions per wave -- 1 % of the frame)
@@ -1181,12 +1192,12 @@ k_trace_tile_split(const VctTraceParams p) {
     // (interleaved slabs: traced row j of the launch is tile row row0 + j * stride; the plain launch pays no second division)
     int lrow = 0, tile0 = p.tile_row0 * p.tiles_x + ti;           // tile0: where the wave's step count is stored
     if (p.row_stride > 1) {
-        lrow = ti / p.tiles_x;
+        lrow = tile_row_of(p, ti);
         tile0 = (p.tile_row0 + lrow * p.row_stride) * p.tiles_x + (ti - lrow * p.tiles_x);
     }
     const bool cvalid = !compact || cpix != 0xffffffffu;
     const int tile = compact ? (cvalid ? (int)(cpix >> 6) : 0) : tile0;
-    const int ty = tile / p.tiles_x, tx = tile - ty * p.tiles_x;
+    const int ty = tile_row_of(p, tile), tx = tile - ty * p.tiles_x;
     // tile row of the output (a packed slab holds its rows back to back)
     const int oy = p.pack_rows ? (p.row_stride > 1 ? lrow : ty - p.tile_row0) : ty;
     const int plane_ = compact ? (int)(cpix & 63u) : lane;        // this lane's pixel inside its tile
@@ -1234,6 +1245,10 @@ k_trace_tile_split(const VctTraceParams p) {
         if (!PRIO && p.spec_prio) __builtin_amdgcn_s_setprio(1);
         const F3 P = gb_planes3(gb, 0), Nw = gb_planes3(gb, 3), N = gb_planes3(gb, 12);
         const F3 start = cone_start(P, Nw, p.vs);
+        // E is the composite's too: this wave hands it over in its own first slab -- no LDS of its own -- once its marches
+        // are over and nothing reads its slabs again, in every form of this arm, also the 0-step ones of COMP and HALF
+        const F3 E = eye_dir(P, p.cam);
+        auto hand_over = [&](F3 e) { blk[lane] = make_float4(e.x, e.y, e.z, 0.0f); };
         if constexpr (GLOSS) {
             // One march per class present among the live lanes: the class of the first remaining lane, wave-uniform, picks
             // the table and its step count by scalar loads; the lanes of that class march, write their cone and leave the
@@ -1243,8 +1258,8 @@ k_trace_tile_split(const VctTraceParams p) {
             // reads it, the second only together with the descriptor).
             const GlossTable gt = (GlossTable)p.gloss;
             const int cls = gloss_class_of(p, tile, plane_, gt->nclasses);
-            const F3 dir = specular_dir(P, N, p.cam);
-            if (!alive) {       // what a lane that marches nothing gets from the one march of the other forms
+            const F3 dir = specular_dir(E, N);
+            if (!alive) {     // what a lane that marches nothing gets from the one march of the other forms
                 lds_cone[6][lane] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                 if (p.dbg_steps && in_frame) p.dbg_steps[pixel_index() * 7 + 6] = 0;
             }
@@ -1272,28 +1287,32 @@ k_trace_tile_split(const VctTraceParams p) {
                 lds_cone[6][lane] = make_float4(sc.x, sc.y, sc.z, sc.w);
                 store_debug_cone(p, pixel_index, 6, sc, 0, alive, false);
             }
+            // (E again from planes 0-2, L1 re-reads: live across the class loop it costs the clamp-mode GLOSS kernels 3 VGPRs
+            // -- the 8th wave of the HALF forms, 16 B of scratch in the PRIO ones)
+            hand_over(eye_dir(gb_planes3(gbuf_ptr(fresh_lane()), 0), p.cam));
         } else {
         int st6;
-        const F4 sc = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO, REUSE, SKY ? VCT_SKY_INSIDE : VCT_SKY_NONE>(p, march_s, start, specular_dir(P, N, p.cam),
+        const F4 sc = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO, REUSE, SKY ? VCT_SKY_INSIDE : VCT_SKY_NONE>(p, march_s, start, specular_dir(E, N),
                                                                     p.steps_specular, n_specular, blk, lb, st6, ms, held);
         total += st6;
         lds_cone[6][lane] = make_float4(sc.x, sc.y, sc.z, sc.w);
         store_debug_cone(p, pixel_index, 6, sc, st6, alive, in_frame);
+        hand_over(E);
         }
     }
     total = wave_sum(total);
-    if (lane == 0) atomicAdd(&lds_steps, total);          // LDS: the last arriver below stores the tile's total
     flush_stats(p, ms, lane, wave == VCT_SPLIT - 1);
 
-    // arrival: LDS operations of a wave are performed in order, so the cone values are in LDS before
-    // the count is raised; whoever raises it to VCT_SPLIT sees all of them
+    // arrival: LDS operations of a wave are performed in order, so the cone values (and E) are in LDS before the
+    // word is raised; whoever raises its count to VCT_SPLIT sees all of them
     __threadfence_block();
-    int arrived = 0;
-    if (lane == 0) arrived = atomicAdd(&lds_done, 1);
-    arrived = __builtin_amdgcn_readfirstlane(arrived);
-    if (arrived != VCT_SPLIT - 1) return;
+    uint32_t before = 0u;
+    if (lane == 0) before = atomicAdd(&lds_arrive, (uint32_t)total + (1u << 28));
+    before = (uint32_t)__builtin_amdgcn_readfirstlane((int)before);
+    if ((before >> 28) != VCT_SPLIT - 1) return;
     __threadfence_block();
-    if (lane == 0) p.tile_steps[tile0] = (uint32_t)lds_steps;     // one plain store per tile: no global atomic, nothing to clear
+    // one plain store per tile: no global atomic, nothing to clear
+    if (lane == 0) p.tile_steps[tile0] = (before + (uint32_t)total) & 0x0fffffffu;
 
     // the last wave gathers the diffuse cones in the oracle's order and composites
     const float* gb3 = gbuf_ptr(fresh_lane());
@@ -1311,7 +1330,8 @@ k_trace_tile_split(const VctTraceParams p) {
             const GlossTable gt = (GlossTable)p.gloss;
             shininess = p.gloss->shininess[gloss_class_of(p, tile, fresh_lane(), gt->nclasses)];
         }
-        composite<COMP>(p, gb3, ind, lds_cone[6][lane], alive, pixel_index,
+        const float4 e = lds_blk[VCT_SPLIT - 1][0][lane];
+        composite<COMP>(p, gb3, ind, lds_cone[6][lane], f3(e.x, e.y, e.z), alive, pixel_index,
                         [&]() { return (size_t)tile * (VCT_EMIS_NPLANES * VCT_TILE_PIX) + fresh_lane(); }, shininess);
     }
 }
@@ -2095,7 +2115,7 @@ hipError_t vct_launch_bounce(const VctTraceParams& p, hipStream_t s) {
 // 2 the cooperative sampler, one wave per tile (k_trace_tile; with anisotropic chains both run the default kernel);
 // 3 the default kernel with reciprocal-multiply divisions and the one-multiply decode, not bit-exact (with anisotropic
 // chains: the default kernel); 4 the default kernel over the live-pixel compaction (p.vt_pix set by the caller).
-// p.ntiles is set here.  *march_form (optional) receives the division form of the launch as vct_get_stage_counts reports
+// p.ntiles, p.tile_mul, p.tile_shift and p.light_unit are set here.  *march_form (optional) receives the division form of the launch as vct_get_stage_counts reports
 // it -- 1 IEEE, 2 the verified product, 3 variant 3's x * r -- also for an empty row range, which launches nothing.
 // p.dr_ind set: a half-rate pass (vct_set_diffuse_rate(ctx, 2)) -- coarse march, resolve, listed march, then the trace
 // kernel that composites; whole frames of the default kernel with p.comp on only.  marks (optional): three events
@@ -2104,6 +2124,12 @@ hipError_t vct_launch_trace(const VctTraceParams& params, int variant, hipStream
     VctTraceParams p = params;
     const int rstride = p.row_stride > 1 ? p.row_stride : 1;
     p.ntiles = ((p.tile_row1 - p.tile_row0 + rstride - 1) / rstride) * p.tiles_x;
+    // what else is the same for every tile of the launch (vct_tilediv.h): the division by tiles_x as a multiplier and a
+    // shift -- (0, 0) where the host cannot certify them: the kernels divide -- and the composite's unit light vector
+    const VctTileDiv td = vct_tilediv_make(p.tiles_x > 0 ? (uint32_t)p.tiles_x : 0u);
+    p.tile_mul = td.mul;
+    p.tile_shift = td.shift;
+    vct_light_unit(p.light, p.light_unit);
     const bool loose = variant == 3 && !p.aniso;
     if (march_form) *march_form = loose ? 3 : (p.fast_div ? 2 : 1);
     if (p.ntiles <= 0) return hipSuccess;

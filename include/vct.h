@@ -657,6 +657,83 @@ int vct_download_pixel_gloss(vct_ctx* ctx, uint8_t* out /* linear [h*w] */);
 int vct_set_sky(vct_ctx* ctx, const float sh[9][3]);
 int vct_get_sky(const vct_ctx* ctx, float sh[9][3], float poly[9][3], int32_t* attached);
 
+/* ---- G-buffer import: a renderer's depth, normal and colour buffers --------------------------------------------------
+ * A deferred renderer keeps a depth or position target, one or two normal targets, RGBA8 colours and perhaps a
+ * material-id target; the trace reads 23 fp32 planes, tiled.  The import is the conversion between the two as a stage
+ * of the library: one kernel reads the caller's compact buffers and writes the selected frame slot's resident tiled
+ * G-buffer; vct_trace_current / vct_trace_resident and their rows forms follow as after vct_render_gbuffer.
+ *   Inputs             linear, row-major, tightly packed, of the context's width x height, every non-NULL pointer where
+ *                      `location` (a vct_mem) says.  Each needs the alignment of its scalar only: 4 B, or 2 B for the
+ *                      F16 and SNORM16 formats.  Frame pixel (x, y), row 0 at the bottom, reads element
+ *                      (FLIP_Y ? h-1-y : y) * w + x of every input.
+ *   Arithmetic         all fp32: multiplies, adds and compares in the written order, nothing fused, IEEE / and sqrtf.
+ *   Surface            DEPTH_F32: none iff depth == depth_clear or depth is NaN.  POSITION_F32X4: none iff w == 0 (w is
+ *                      otherwise unused).  POSITION_F32X3: always.  A pixel without a surface gets +0 in all 23 planes
+ *                      (the trace discards it) and, with `material`, emission 0 and class 0.
+ *   Position           planes 0-2.  F32X3 / F32X4 as given.  DEPTH_F32, with the frame's x and y whatever FLIP_Y says:
+ *                        nx = (2(x + 0.5))/w - 1;  ny = (2(y + 0.5))/h - 1;  nz = DEPTH_ZERO_TO_ONE ? depth : 2*depth - 1;
+ *                        r_i = ((m[i] nx + m[4+i] ny) + m[8+i] nz) + m[12+i];   P = r_xyz / r_w
+ *                      with m = inv_view_proj, column-major: the voxel view's formula.
+ *   Decode             F16 to fp32 is exact; UNORM8 is c / 255.0f; SNORM16 is max(s, -32767) / 32767.0f.  Octahedral
+ *                      e = (ex, ey): v = (ex, ey, (1 - |ex|) - |ey|), and if v.z < 0 then
+ *                      v.x = (1 - |ey|) * (ex >= 0 ? 1 : -1), v.y = (1 - |ex|) * (ey >= 0 ? 1 : -1).
+ *   unit(v)            l = sqrtf((v.x*v.x + v.y*v.y) + v.z*v.z);  l > 0 ? v * (1.0f / l) : 0.
+ *   Frame              u = unit(normal);  k = (|u.y| >= |u.x| and |u.y| >= |u.z|) ? (0, -u.z, u.y) : (u.z, 0, -u.x);
+ *                      t = unit(k);  b = (u.y*t.z - u.z*t.y, u.z*t.x - u.x*t.z, u.x*t.y - u.y*t.x): the construction of
+ *                      vcth_frame_from_normal in fp32.  Planes 3-5 = u * normal_scale, 6-8 = t * normal_scale,
+ *                      9-11 = b * normal_scale, 12-14 = unit(shading normal), or u without one.  A zero or non-finite
+ *                      normal flows through as this arithmetic has it; the G-buffer contract above says what the trace
+ *                      does with such a pixel.
+ *   Colours            planes 15-17 = albedo rgb; 18 = albedo a, or 1.0f with OPAQUE; 19-21 = specular rgb as given, or
+ *                      specular_constant (the .rrra rule of trace.fs:210 is a texture quirk and is not applied).
+ *   Shadow             plane 22 = shadow[element] where given.  Otherwise, with a shadow map in the context, the value
+ *                      the G-buffer pass writes for a fragment at this Position under the map's stored light matrix (PCF
+ *                      count * 0.111f; the same device function) -- except that a pixel for which any of the four
+ *                      light-space coordinates is NaN or infinite gets 0 and fetches nothing; every other coordinate
+ *                      reaches a texel index only through the PCF's clamps.  Without a map: 25.0f * 0.111f.
+ *   Material ids       with `material` and a material emission table attached, the slot's pixel-emission planes get
+ *                      emission[id], and 0 for id >= nmat or no surface; with `material`, gloss classes and a material
+ *                      gloss map attached, the slot's pixel-gloss plane gets mat_class[id] under the same rule.  Without
+ *                      `material` both are left exactly as they are.
+ * The import writes the selected slot's OWN tiled buffer and makes it the resident G-buffer, also where the last
+ * vct_trace had bound a caller's tiled buffer zero-copy.  The rows form writes tile rows [tile_row0, tile_row1) only
+ * (a rank of a multi-GPU frame imports its slab); other rows keep what that buffer held.  VCT_MEM_DEVICE: queued on
+ * the slot's stream, returns at once, the inputs must stay valid until the stream has passed it.  VCT_MEM_HOST: staged
+ * through buffers the slot owns; returns when the planes are written.  The import reads shared state only (the shadow
+ * map, the tables) and is ordered against their writers as the G-buffer pass is.
+ * vct_last_gbuffer_import_ms: device time of the import kernel alone; needs vct_set_trace_timing on when the import was
+ * issued (VCT_ERR_INVALID otherwise, and before the slot's first import); waits.
+ * VCT_ERR_INVALID, nothing touched: NULL ctx or descriptor; NULL position, normal or albedo; an unknown format (of
+ * specular only with a specular buffer), location or flag bit; DEPTH_F32 with a non-finite inv_view_proj element;
+ * normal_scale not finite or <= 0; specular NULL with a non-finite specular_constant; a tile-row range outside the frame.
+ * Out of scope: pitched or tiled inputs and graphics-API interop handles, UNORM8 and 10:10:10:2 normals, sRGB decode
+ * (pass linear colours), velocity and history buffers. */
+enum { VCT_IMPORT_POSITION_F32X3 = 0, VCT_IMPORT_POSITION_F32X4 = 1, VCT_IMPORT_DEPTH_F32 = 2 };
+enum { VCT_IMPORT_NORMAL_F32X3 = 0, VCT_IMPORT_NORMAL_F16X4 = 1, VCT_IMPORT_NORMAL_OCT_SNORM16X2 = 2 };
+enum { VCT_IMPORT_COLOR_UNORM8X4 = 0, VCT_IMPORT_COLOR_F16X4 = 1, VCT_IMPORT_COLOR_F32X4 = 2 };
+#define VCT_IMPORT_FLIP_Y 1u             /* row 0 of every input is the TOP row (the library's row 0 is the bottom row) */
+#define VCT_IMPORT_DEPTH_ZERO_TO_ONE 2u  /* nz = depth (D3D / Vulkan clip space) instead of 2 * depth - 1 (GL) */
+#define VCT_IMPORT_OPAQUE 4u             /* plane 18 = 1.0f wherever there is a surface; albedo.a is not read as alpha */
+typedef struct vct_gbuffer_import {
+    const void* position;        /* required */
+    const void* normal;          /* required: the geometric normal (planes 3-11 are derived from it) */
+    const void* shading_normal;  /* optional, normal_format too: plane 12-14; NULL = normal */
+    const void* albedo;          /* required */
+    const void* specular;        /* optional; NULL = specular_constant */
+    const float* shadow;         /* optional fp32 [h*w]; NULL = the library's PCF (above) */
+    const uint16_t* material;    /* optional [h*w] */
+    int32_t position_format, normal_format, albedo_format, specular_format;
+    int32_t location;            /* vct_mem: where EVERY non-NULL pointer above lives */
+    uint32_t flags;
+    float inv_view_proj[16];     /* DEPTH_F32 only: column-major, as vct_render_voxels takes it */
+    float depth_clear;           /* DEPTH_F32 only */
+    float normal_scale;          /* length given to planes 3-11; 1 = the cone starts one voxel off the surface */
+    float specular_constant[3];
+} vct_gbuffer_import;
+int vct_import_gbuffer(vct_ctx* ctx, const vct_gbuffer_import* in);
+int vct_import_gbuffer_rows(vct_ctx* ctx, const vct_gbuffer_import* in, int32_t tile_row0, int32_t tile_row1);
+int vct_last_gbuffer_import_ms(vct_ctx* ctx, float* ms);
+
 /* ---- two frames in flight (round 6) -----------------------------------------------------------------
  * The reference's Render() (VCT.h:146-190) issues GL commands; the driver starts frame k + 1 while frame k
  * drains -- nothing in R/main.cpp:77-94 waits for a frame.  A HIP stream does wait: each whole-frame trace

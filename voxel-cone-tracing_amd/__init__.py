@@ -38,6 +38,11 @@ POINT_QUERY_MAX = 1 << 26
 APERTURE_DIFFUSE, APERTURE_SPECULAR = 0, 1
 # per-material gloss (Context.set_gloss_classes)
 GLOSS_CLASSES_MAX = 8
+# G-buffer import (Context.import_gbuffer): input formats and flags of include/vct.h "G-buffer import"
+IMPORT_POSITION_F32X3, IMPORT_POSITION_F32X4, IMPORT_DEPTH_F32 = 0, 1, 2
+IMPORT_NORMAL_F32X3, IMPORT_NORMAL_F16X4, IMPORT_NORMAL_OCT_SNORM16X2 = 0, 1, 2
+IMPORT_COLOR_UNORM8X4, IMPORT_COLOR_F16X4, IMPORT_COLOR_F32X4 = 0, 1, 2
+IMPORT_FLIP_Y, IMPORT_DEPTH_ZERO_TO_ONE, IMPORT_OPAQUE = 1, 2, 4
 
 
 def APERTURE_GLOSS(k):
@@ -73,6 +78,7 @@ ABI_SYMBOLS = [
     "vct_set_gloss_classes", "vct_get_gloss_classes", "vct_upload_material_gloss", "vct_set_pixel_gloss",
     "vct_download_pixel_gloss",
     "vct_set_sky", "vct_get_sky",
+    "vct_import_gbuffer", "vct_import_gbuffer_rows", "vct_last_gbuffer_import_ms",
 ]
 
 
@@ -95,6 +101,16 @@ class GlossClass(C.Structure):
 class GBuffer(C.Structure):
     _fields_ = [("planes", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32),
                 ("layout", C.c_int32), ("location", C.c_int32)]
+
+
+class GBufferImport(C.Structure):
+    """vct_gbuffer_import of include/vct.h"""
+    _fields_ = [("position", C.c_void_p), ("normal", C.c_void_p), ("shading_normal", C.c_void_p),
+                ("albedo", C.c_void_p), ("specular", C.c_void_p), ("shadow", C.c_void_p), ("material", C.c_void_p),
+                ("position_format", C.c_int32), ("normal_format", C.c_int32), ("albedo_format", C.c_int32),
+                ("specular_format", C.c_int32), ("location", C.c_int32), ("flags", C.c_uint32),
+                ("inv_view_proj", C.c_float * 16), ("depth_clear", C.c_float), ("normal_scale", C.c_float),
+                ("specular_constant", C.c_float * 3)]
 
 
 class VctError(RuntimeError):
@@ -194,6 +210,9 @@ _lib.vct_set_pixel_gloss.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int3
 _lib.vct_download_pixel_gloss.argtypes = [C.c_void_p, C.c_void_p]
 _lib.vct_set_sky.argtypes = [C.c_void_p, C.c_void_p]
 _lib.vct_get_sky.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.vct_import_gbuffer.argtypes = [C.c_void_p, C.c_void_p]
+_lib.vct_import_gbuffer_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
+_lib.vct_last_gbuffer_import_ms.argtypes = [C.c_void_p, C.c_void_p]
 _lib.vct_upload_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
 
 
@@ -468,6 +487,81 @@ class Context:
         sh, poly, on = np.zeros((9, 3), np.float32), np.zeros((9, 3), np.float32), C.c_int32()
         self._ck(_lib.vct_get_sky(self._h, _ptr(sh), _ptr(poly), C.byref(on)), "vct_get_sky")
         return sh, poly, bool(on.value)
+
+    # --- G-buffer import (include/vct.h "G-buffer import")
+    @staticmethod
+    def _import_format(what, a, npix, given):
+        """The format of one input: as given, or inferred from a numpy array's dtype and element count."""
+        if given is not None:
+            return int(given)
+        if a is None:
+            return 0
+        if isinstance(a, int):
+            raise VctError(f"import_gbuffer: {what} is a device pointer: name its format")
+        per = a.size / npix
+        table = {"position": {("float32", 3): IMPORT_POSITION_F32X3, ("float32", 4): IMPORT_POSITION_F32X4,
+                              ("float32", 1): IMPORT_DEPTH_F32},
+                 "normal": {("float32", 3): IMPORT_NORMAL_F32X3, ("float16", 4): IMPORT_NORMAL_F16X4,
+                            ("int16", 2): IMPORT_NORMAL_OCT_SNORM16X2},
+                 "colour": {("uint8", 4): IMPORT_COLOR_UNORM8X4, ("float16", 4): IMPORT_COLOR_F16X4,
+                            ("float32", 4): IMPORT_COLOR_F32X4}}[what if what in ("position", "normal") else "colour"]
+        fmt = table.get((a.dtype.name, per))
+        if fmt is None:
+            raise VctError(f"import_gbuffer: {what} is {a.dtype.name} x {per:g} per pixel, which is none of its formats")
+        return fmt
+
+    def import_gbuffer(self, position, normal, albedo, shading_normal=None, specular=None, shadow=None, material=None,
+                       position_format=None, normal_format=None, albedo_format=None, specular_format=None, flags=0,
+                       inv_view_proj=None, depth_clear=1.0, normal_scale=1.0, specular_constant=(0.0, 0.0, 0.0), rows=None):
+        """A renderer's buffers into the selected slot's resident G-buffer; trace_current() / trace_resident() follow.
+        Every input is a numpy array (host memory) or an int device pointer, all of one kind: position float32 [h*w, 3],
+        [h*w, 4] or depth [h*w]; normal (and shading_normal) float32 x 3, float16 x 4 or octahedral int16 x 2; albedo and
+        specular uint8, float16 or float32 x 4; shadow float32 [h*w]; material uint16 [h*w].  Formats are inferred from
+        numpy inputs and must be named (IMPORT_*) for device pointers.  flags: IMPORT_FLIP_Y | IMPORT_DEPTH_ZERO_TO_ONE |
+        IMPORT_OPAQUE.  inv_view_proj: column-major float32[16], depth inputs only.  rows = (tile_row0, tile_row1): only
+        those tile rows are written.  Device inputs are queued on the slot's stream; host inputs return when written."""
+        npix = self.cfg.width * self.cfg.height
+        named = dict(position=position, normal=normal, shading_normal=shading_normal, albedo=albedo, specular=specular,
+                     shadow=shadow, material=material)
+        given = {k: v for k, v in named.items() if v is not None}
+        kinds = {isinstance(v, int) for v in given.values()}
+        if len(kinds) > 1:
+            raise VctError("import_gbuffer: every input lives where `location` says: all numpy arrays or all device pointers")
+        device = kinds == {True}
+        if not device:
+            fixed = dict(shadow=np.float32, material=np.uint16)
+            for k, v in given.items():
+                v = np.ascontiguousarray(v, fixed.get(k))
+                if k in fixed and v.size != npix:
+                    raise VctError(f"import_gbuffer: {k} has {v.size} elements, the frame has {npix} pixels")
+                given[k] = v
+        d = GBufferImport()
+        d.position_format = self._import_format("position", given.get("position"), npix, position_format)
+        d.normal_format = self._import_format("normal", given.get("normal"), npix, normal_format)
+        if not device and "shading_normal" in given and \
+                self._import_format("normal", given["shading_normal"], npix, normal_format) != d.normal_format:
+            raise VctError("import_gbuffer: shading_normal has normal's format")
+        d.albedo_format = self._import_format("albedo", given.get("albedo"), npix, albedo_format)
+        d.specular_format = self._import_format("specular", given.get("specular"), npix, specular_format)
+        for k in named:
+            v = given.get(k)
+            setattr(d, k, None if v is None else (v if device else v.ctypes.data))
+        d.location = MEM_DEVICE if device else MEM_HOST
+        d.flags = int(flags)
+        if inv_view_proj is not None:
+            d.inv_view_proj[:] = [float(x) for x in np.asarray(inv_view_proj, np.float32).reshape(16)]
+        d.depth_clear, d.normal_scale = float(depth_clear), float(normal_scale)
+        d.specular_constant[:] = [float(x) for x in specular_constant]
+        if rows is None:
+            self._ck(_lib.vct_import_gbuffer(self._h, C.byref(d)), "vct_import_gbuffer")
+        else:
+            self._ck(_lib.vct_import_gbuffer_rows(self._h, C.byref(d), int(rows[0]), int(rows[1])), "vct_import_gbuffer_rows")
+
+    def last_gbuffer_import_ms(self):
+        """Device ms of the kernel of the selected slot's last G-buffer import (trace timing must have been on)."""
+        v = C.c_float()
+        self._ck(_lib.vct_last_gbuffer_import_ms(self._h, C.byref(v)), "vct_last_gbuffer_import_ms")
+        return v.value
 
     def upload_shadow_map(self, depth, light_vp_rowmajor):
         if depth is None:

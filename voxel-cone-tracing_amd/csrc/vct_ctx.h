@@ -134,6 +134,16 @@ struct VctPointQuery {
     int kind = 0;
 };
 
+// What a frame slot keeps for the G-buffer import (include/vct.h "G-buffer import", vct_api_import.hip): device staging
+// for a host-located import -- one buffer, every input at an offset of its own, grown on demand and never shrunk -- and
+// the timing events around the import kernel.  Work on them is ordered by the slot's stream; a host-located import
+// returns only when the stream has passed its kernel, so the staging is free again at every entry.
+struct VctGBufferImport {
+    VctBuf<char> stage;
+    VctEvent ev0, ev1;                  // around k_gbuffer_import (vct_last_gbuffer_import_ms)
+    bool have = false, timed = false;
+};
+
 // Two frames in flight (vct_set_frames_in_flight, round 6).  A whole-frame trace launch pays ~20 us of ramp and drain
 // (the last generation of workgroups leaves compute units idle, tools/quant_probe.py) plus the dispatch gap to the next
 // kernel of its stream: 4-5 % of a 0.61 ms frame.  A renderer that starts frame k + 1 on a second stream while frame k
@@ -185,6 +195,7 @@ struct VctFrameSlot {
     bool have_view = false, last_view_timed = false;
     VctRasterScratch raster;            // the main draw's
     VctPointQuery query;                // point queries issued on this slot
+    VctGBufferImport gb_import;         // G-buffer imports issued on this slot
 
     // where a trace writes and a download reads: the caller's target or the slot's own frame
     uint16_t* frame_out() const { return frame_target ? frame_target : frame.get(); }

@@ -578,4 +578,23 @@ hipError_t vct_launch_voxview_occupancy(const VctVoxViewParams& p, hipStream_t s
 // skip = false: the instantiation without the occupancy look-ups (every block is fetched): the A/B arm of the measurements
 hipError_t vct_launch_voxview(const VctVoxViewParams& p, bool skip, hipStream_t s);
 
+// the G-buffer import (include/vct.h "G-buffer import", k_gbuffer_import in vct_raster.hip)
+struct vct_gbuffer_import;
+struct VctImportArgs {
+    const vct_gbuffer_import* desc;    // a checked descriptor (vct_import_check.h) whose pointers are device pointers
+    int32_t W, H, row0, row1;          // the frame; tile rows [row0, row1) are written
+    const uint32_t* shadow;            // the context's shadow-map words or null, as vct_launch_gbuffer_shade takes them
+    uint32_t shadow_ebase;
+    int32_t shadow_size;
+    const uint2* shadow_tiles;
+    const float* light_vp;             // [16]
+    float* tiled;                      // [tile][23][64]
+    const float* emission;             // [nmat][4] with emis_tiled [tile][3][64], or both null: the planes are not written
+    float* emis_tiled;
+    const uint8_t* mat_gloss;          // [nmat] with gloss_tiled [tile][64], or both null
+    uint8_t* gloss_tiled;
+    int32_t nmat;
+};
+hipError_t vct_launch_gbuffer_import(const VctImportArgs& a, hipStream_t s);
+
 #endif

@@ -8,6 +8,8 @@
 //               (:110-128 with a flat height map), material colours (:167,:209-210), the 25-tap PCF
 //               shadow term with its 0.111 scale (:132-163).  Output: the tiled 23-plane G-buffer
 //               k_trace_tile reads, written in place -- a frame never leaves HBM.
+//   import      the same 23 planes from a renderer's own depth / normal / colour buffers instead of a
+//               raster (include/vct.h "G-buffer import"): k_gbuffer_import, with the shade kernel's PCF.
 //
 // Rasterisation rules are those of the CPU rasteriser in oracle/vct_oracle_raster.cpp (the checker of these
 // stages): near-plane clip, window coordinates snapped to 1/256 pixel, edge functions in double
@@ -25,6 +27,7 @@
 #include <string.h>
 
 #include "vct_internal.h"
+#include "vct_import_check.h"
 
 namespace {
 
@@ -1552,6 +1555,105 @@ __device__ __forceinline__ float shadow_fetch(const uint32_t* __restrict__ words
     return (1.0f - a) * (1.0f - b) * d00 + a * (1.0f - b) * d10 + (1.0f - a) * b * d01 + a * b * d11;
 }
 
+// Plane 22 of a fragment whose light-space coordinates are d (trace.vs:28): the 5 x 5 PCF of trace.fs:140-158 over the
+// shadow-map words, count x 0.111f.  One copy for k_gbuffer_shade and k_gbuffer_import.
+__device__ __forceinline__ float pcf_shadow(const uint32_t* __restrict__ words, uint32_t ebase, int shadow_size,
+                                            const uint2* __restrict__ tiles, const float d[4]) {
+    const float cx = d[0] * 0.5f + 0.5f, cy = d[1] * 0.5f + 0.5f, cz = d[2] * 0.5f + 0.5f;
+    const float cur = __fdiv_rn(cz, d[3]) - 0.002f;
+    const float step = __fdiv_rn(1.0f, (float)shadow_size);
+    // The 25 taps sit one texel apart: when every tap's upper texel index equals the next
+    // tap's lower one on both axes (checked per lane) the shared 6x6 window is loaded once
+    // and each tap is evaluated with its own exact fractions; otherwise tap by tap.
+    const int S = shadow_size;
+    const float fS = (float)S, top = (float)(S - 1);
+    int xi0[5], xi1[5], yj0[5], yj1[5];
+    float xa[5], yb[5];
+    bool regular = true;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        const float ux = (cx + step * (float)(k - 2)) * fS - 0.5f, uy = (cy + step * (float)(k - 2)) * fS - 0.5f;
+        const float fx = floorf(ux), fy = floorf(uy);
+        xa[k] = ux - fx; yb[k] = uy - fy;
+        const float fx1 = fx + 1.0f, fy1 = fy + 1.0f;
+        xi0[k] = fx < 0.0f ? 0 : (fx > top ? S - 1 : (int)fx);
+        xi1[k] = fx1 < 0.0f ? 0 : (fx1 > top ? S - 1 : (int)fx1);
+        yj0[k] = fy < 0.0f ? 0 : (fy > top ? S - 1 : (int)fy);
+        yj1[k] = fy1 < 0.0f ? 0 : (fy1 > top ? S - 1 : (int)fy1);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) regular = regular && xi1[k] == xi0[k + 1] && yj1[k] == yj0[k + 1];
+    float cnt = 0.0f;
+    if (regular) {
+        int col[6], row[6];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) { col[k] = xi0[k]; row[k] = yj0[k]; }
+        col[5] = xi1[4]; row[5] = yj1[4];
+        const bool wide = col[5] - col[0] == 5;     // six consecutive texels per row: one dwordx4 + one dwordx2 (VctWords6)
+        auto tap_row = [&](int y, const float r0[6], const float r1[6]) __attribute__((always_inline)) {
+#pragma unroll
+            for (int x = 0; x < 5; ++x) {
+                const float a = xa[x], b = yb[y];
+                const float tap = (1.0f - a) * (1.0f - b) * r0[x] + a * (1.0f - b) * r0[x + 1] +
+                                  (1.0f - a) * b * r1[x] + a * b * r1[x + 1];
+                if (cur <= tap) cnt += 1.0f;
+            }
+        };
+        int tile_verdict = -1;
+        if (wide && tiles) tile_verdict = vct_pcf_tile_verdict(tiles, S, (uint32_t)col[0], (uint32_t)row[0], cur);
+        if (tile_verdict >= 0) {
+            cnt = (float)tile_verdict;      // the tiles the window lies in bound it: no window fetch
+        } else if (wide) {
+            // all six rows in flight at once (round 3: the rows used to be fetched one after the other, two
+            // live at a time to save registers -- six dependent round trips per pixel were the price, 36 of
+            // the pass's 188 us); the taps are counted, so their order is free
+            VctWords6 w[6];
+#pragma unroll
+            for (int y = 0; y < 6; ++y) w[y] = *reinterpret_cast<const VctWords6*>(words + (size_t)row[y] * S + col[0]);
+            uint32_t wmin = 0xffffffffu, wmax = 0u;
+#pragma unroll
+            for (int y = 0; y < 6; ++y)
+#pragma unroll
+                for (int i = 0; i < 6; ++i) { wmin = min(wmin, w[y].v[i]); wmax = max(wmax, w[y].v[i]); }
+            const int verdict = vct_pcf_window_verdict(wmin, wmax, ebase, cur);      // vct_internal.h "PCF short cut"
+            if (verdict >= 0) {
+                cnt = (float)verdict;
+            } else {
+                float r0[6], r1[6];
+#pragma unroll
+                for (int i = 0; i < 6; ++i) r0[i] = vct_shadow_depth(w[0].v[i], ebase);
+#pragma unroll
+                for (int y = 0; y < 5; ++y) {
+#pragma unroll
+                    for (int i = 0; i < 6; ++i) r1[i] = vct_shadow_depth(w[y + 1].v[i], ebase);
+                    tap_row(y, r0, r1);
+#pragma unroll
+                    for (int i = 0; i < 6; ++i) r0[i] = r1[i];
+                }
+            }
+        } else {       // a window at a clamped border: texel by texel, two rows live at a time
+            float r0[6], r1[6];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) r0[i] = vct_shadow_depth(words[(size_t)row[0] * S + col[i]], ebase);
+#pragma unroll
+            for (int y = 0; y < 5; ++y) {
+#pragma unroll
+                for (int i = 0; i < 6; ++i) r1[i] = vct_shadow_depth(words[(size_t)row[y + 1] * S + col[i]], ebase);
+                tap_row(y, r0, r1);
+#pragma unroll
+                for (int i = 0; i < 6; ++i) r0[i] = r1[i];
+            }
+        }
+    } else {
+        for (int x = -2; x <= 2; ++x)
+            for (int y = -2; y <= 2; ++y) {
+                const float ox = step * (float)x, oy = step * (float)y;       // trace.fs:147
+                if (cur <= shadow_fetch(words, ebase, shadow_size, cx + ox, cy + oy)) cnt += 1.0f;
+            }
+    }
+    return cnt * 0.111f;                                                      // trace.fs:158
+}
+
 // one thread per pixel, 64 threads = one 8x8 tile of the tiled G-buffer
 #ifndef VCT_SHADE_MIN_BLOCKS
 #define VCT_SHADE_MIN_BLOCKS 4       // waves per SIMD (round 2, dword PCF loads, G-buffer pass in us: 5: 204, 7: 201, 8: 212); the wide row loads of round 3 need register tuples: 7 spills
@@ -1763,99 +1865,7 @@ k_gbuffer_shade(const ShadeParams p) {
         if (p.shadow) {
             float d[4];
             xform4(p.light_vp, g[0], g[1], g[2], d);                              // trace.vs:28
-            const float cx = d[0] * 0.5f + 0.5f, cy = d[1] * 0.5f + 0.5f, cz = d[2] * 0.5f + 0.5f;
-            const float cur = __fdiv_rn(cz, d[3]) - 0.002f;
-            const float step = __fdiv_rn(1.0f, (float)p.shadow_size);
-            // The 25 taps sit one texel apart: when every tap's upper texel index equals the next
-            // tap's lower one on both axes (checked per lane) the shared 6x6 window is loaded once
-            // and each tap is evaluated with its own exact fractions; otherwise tap by tap.
-            const int S = p.shadow_size;
-            const float fS = (float)S, top = (float)(S - 1);
-            int xi0[5], xi1[5], yj0[5], yj1[5];
-            float xa[5], yb[5];
-            bool regular = true;
-#pragma unroll
-            for (int k = 0; k < 5; ++k) {
-                const float ux = (cx + step * (float)(k - 2)) * fS - 0.5f, uy = (cy + step * (float)(k - 2)) * fS - 0.5f;
-                const float fx = floorf(ux), fy = floorf(uy);
-                xa[k] = ux - fx; yb[k] = uy - fy;
-                const float fx1 = fx + 1.0f, fy1 = fy + 1.0f;
-                xi0[k] = fx < 0.0f ? 0 : (fx > top ? S - 1 : (int)fx);
-                xi1[k] = fx1 < 0.0f ? 0 : (fx1 > top ? S - 1 : (int)fx1);
-                yj0[k] = fy < 0.0f ? 0 : (fy > top ? S - 1 : (int)fy);
-                yj1[k] = fy1 < 0.0f ? 0 : (fy1 > top ? S - 1 : (int)fy1);
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) regular = regular && xi1[k] == xi0[k + 1] && yj1[k] == yj0[k + 1];
-            float cnt = 0.0f;
-            if (regular) {
-                int col[6], row[6];
-#pragma unroll
-                for (int k = 0; k < 5; ++k) { col[k] = xi0[k]; row[k] = yj0[k]; }
-                col[5] = xi1[4]; row[5] = yj1[4];
-                const bool wide = col[5] - col[0] == 5;     // six consecutive texels per row: one dwordx4 + one dwordx2 (VctWords6)
-                auto tap_row = [&](int y, const float r0[6], const float r1[6]) __attribute__((always_inline)) {
-#pragma unroll
-                    for (int x = 0; x < 5; ++x) {
-                        const float a = xa[x], b = yb[y];
-                        const float tap = (1.0f - a) * (1.0f - b) * r0[x] + a * (1.0f - b) * r0[x + 1] +
-                                          (1.0f - a) * b * r1[x] + a * b * r1[x + 1];
-                        if (cur <= tap) cnt += 1.0f;
-                    }
-                };
-                int tile_verdict = -1;
-                if (wide && p.shadow_tiles) tile_verdict = vct_pcf_tile_verdict(p.shadow_tiles, S, (uint32_t)col[0], (uint32_t)row[0], cur);
-                if (tile_verdict >= 0) {
-                    cnt = (float)tile_verdict;      // the tiles the window lies in bound it: no window fetch
-                } else if (wide) {
-                    // all six rows in flight at once (round 3: the rows used to be fetched one after the other, two
-                    // live at a time to save registers -- six dependent round trips per pixel were the price, 36 of
-                    // the pass's 188 us); the taps are counted, so their order is free
-                    VctWords6 w[6];
-#pragma unroll
-                    for (int y = 0; y < 6; ++y) w[y] = *reinterpret_cast<const VctWords6*>(p.shadow + (size_t)row[y] * S + col[0]);
-                    uint32_t wmin = 0xffffffffu, wmax = 0u;
-#pragma unroll
-                    for (int y = 0; y < 6; ++y)
-#pragma unroll
-                        for (int i = 0; i < 6; ++i) { wmin = min(wmin, w[y].v[i]); wmax = max(wmax, w[y].v[i]); }
-                    const int verdict = vct_pcf_window_verdict(wmin, wmax, p.shadow_ebase, cur);      // vct_internal.h "PCF short cut"
-                    if (verdict >= 0) {
-                        cnt = (float)verdict;
-                    } else {
-                        float r0[6], r1[6];
-#pragma unroll
-                        for (int i = 0; i < 6; ++i) r0[i] = vct_shadow_depth(w[0].v[i], p.shadow_ebase);
-#pragma unroll
-                        for (int y = 0; y < 5; ++y) {
-#pragma unroll
-                            for (int i = 0; i < 6; ++i) r1[i] = vct_shadow_depth(w[y + 1].v[i], p.shadow_ebase);
-                            tap_row(y, r0, r1);
-#pragma unroll
-                            for (int i = 0; i < 6; ++i) r0[i] = r1[i];
-                        }
-                    }
-                } else {       // a window at a clamped border: texel by texel, two rows live at a time
-                    float r0[6], r1[6];
-#pragma unroll
-                    for (int i = 0; i < 6; ++i) r0[i] = vct_shadow_depth(p.shadow[(size_t)row[0] * S + col[i]], p.shadow_ebase);
-#pragma unroll
-                    for (int y = 0; y < 5; ++y) {
-#pragma unroll
-                        for (int i = 0; i < 6; ++i) r1[i] = vct_shadow_depth(p.shadow[(size_t)row[y + 1] * S + col[i]], p.shadow_ebase);
-                        tap_row(y, r0, r1);
-#pragma unroll
-                        for (int i = 0; i < 6; ++i) r0[i] = r1[i];
-                    }
-                }
-            } else {
-                for (int x = -2; x <= 2; ++x)
-                    for (int y = -2; y <= 2; ++y) {
-                        const float ox = step * (float)x, oy = step * (float)y;       // trace.fs:147
-                        if (cur <= shadow_fetch(p.shadow, p.shadow_ebase, p.shadow_size, cx + ox, cy + oy)) cnt += 1.0f;
-                    }
-            }
-            shadow = cnt * 0.111f;                                                // trace.fs:158
+            shadow = pcf_shadow(p.shadow, p.shadow_ebase, p.shadow_size, p.shadow_tiles, d);
         }
         g[22] = shadow;
     }
@@ -1867,6 +1877,70 @@ k_gbuffer_shade(const ShadeParams p) {
         for (int k = 0; k < VCT_EMIS_NPLANES; ++k) eo[k * VCT_TILE_PIX] = em[k];
     }
     if (p.gloss_tiled) p.gloss_tiled[(size_t)tile * VCT_TILE_PIX + lane] = (uint8_t)gloss;
+}
+
+// ---- G-buffer import (include/vct.h "G-buffer import") ----
+struct ImportParams {
+    vct_gbuffer_import d;        // formats, flags and constants are wave-uniform: the kernel branches on them
+    int32_t W, H;
+    int32_t tiles_x;
+    int32_t tile0, tile1;        // tiles [tile0, tile1) are written (whole tile rows)
+    const uint32_t* shadow;      // PCF only: as ShadeParams
+    uint32_t shadow_ebase;
+    int32_t shadow_size;
+    const uint2* shadow_tiles;
+    float light_vp[16];
+    float* tiled;                // [tile][23][64]
+    const float* emission;       // [nmat][4]; emis_tiled == null: nothing read or written
+    float* emis_tiled;
+    const uint8_t* mat_gloss;    // [nmat]; gloss_tiled == null: nothing read or written
+    uint8_t* gloss_tiled;
+    int32_t nmat;
+};
+
+// One wave per 8x8 tile, lane = pixel, four tiles adjacent in x per workgroup (k_gbuffer_shade's indexing): the
+// 32-pixel row segments a workgroup reads are whole cache lines, every plane store is the 256 contiguous bytes
+// [tile][plane][64].  The per-pixel arithmetic is vct_import_check.h's.  PCF: the context has a shadow map and the
+// caller gave no shadow plane -- the only template parameter, so that the other form does not carry the PCF's registers.
+template <bool PCF>
+__global__ void __launch_bounds__(256)
+k_gbuffer_import(const ImportParams p) {
+    const int W = p.W, H = p.H;
+    const int tile = p.tile0 + blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (tile >= p.tile1) return;
+    const int ty = tile / p.tiles_x, tx = tile - ty * p.tiles_x;
+    const int px = tx * VCT_TILE + (lane & 7), py = ty * VCT_TILE + (lane >> 3);
+    const bool inside = px < W && py < H;       // lanes outside a ragged frame read nothing and write zeros
+    float g[VCT_GB_NPLANES];
+#pragma unroll
+    for (int k = 0; k < VCT_GB_NPLANES; ++k) g[k] = 0.0f;
+    bool surface = false;
+    if (inside) surface = vct_import_pixel(p.d, W, H, px, py, g);
+    if (PCF && surface) {
+        float d[4];
+        xform4(p.light_vp, g[0], g[1], g[2], d);
+        // a caller's position need not be finite: such a pixel is unlit and fetches nothing; every finite coordinate
+        // reaches a texel index only through the PCF's own clamps
+        const bool finite = vct_import_finite(d[0]) && vct_import_finite(d[1]) && vct_import_finite(d[2]) && vct_import_finite(d[3]);
+        float shadow = 0.0f;
+        if (finite) shadow = pcf_shadow(p.shadow, p.shadow_ebase, p.shadow_size, p.shadow_tiles, d);
+        g[22] = shadow;
+    }
+    float* out = p.tiled + (size_t)tile * (VCT_GB_NPLANES * VCT_TILE_PIX) + lane;
+#pragma unroll
+    for (int k = 0; k < VCT_GB_NPLANES; ++k) out[k * VCT_TILE_PIX] = g[k];
+    if (p.emis_tiled || p.gloss_tiled) {        // (wave-uniform: kernel arguments) material ids
+        uint32_t id = (uint32_t)p.nmat;
+        if (surface) id = p.d.material[(size_t)((p.d.flags & VCT_IMPORT_FLIP_Y) ? H - 1 - py : py) * (size_t)W + (size_t)px];
+        const bool known = id < (uint32_t)p.nmat;
+        if (p.emis_tiled) {
+            float* eo = p.emis_tiled + (size_t)tile * (VCT_EMIS_NPLANES * VCT_TILE_PIX) + lane;
+#pragma unroll
+            for (int k = 0; k < VCT_EMIS_NPLANES; ++k) eo[k * VCT_TILE_PIX] = known ? p.emission[4 * (size_t)id + k] : 0.0f;
+        }
+        if (p.gloss_tiled) p.gloss_tiled[(size_t)tile * VCT_TILE_PIX + lane] = known ? p.mat_gloss[id] : (uint8_t)0;
+    }
 }
 
 // glGenerateMipmap (R/Model.h:168) for one level: rounded mean of the 2x2 parent texels, indices clamped to the parent
@@ -2080,6 +2154,34 @@ hipError_t vct_launch_gbuffer_shade(const VctRasterArgs& a, const float view_pro
     const int per_block = VCT_SHADE_BLOCK / 64;       // tiles (waves) per workgroup
     if (a.tex.texels) hipLaunchKernelGGL(k_gbuffer_shade<true>, dim3((tiles + per_block - 1) / per_block), dim3(VCT_SHADE_BLOCK), 0, s, p);
     else hipLaunchKernelGGL(k_gbuffer_shade<false>, dim3((tiles + per_block - 1) / per_block), dim3(VCT_SHADE_BLOCK), 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t vct_launch_gbuffer_import(const VctImportArgs& a, hipStream_t s) {
+    ImportParams p;
+    memset(&p, 0, sizeof(p));
+    p.d = *a.desc;
+    p.W = a.W; p.H = a.H;
+    p.tiles_x = (a.W + VCT_TILE - 1) / VCT_TILE;
+    p.tile0 = a.row0 * p.tiles_x;
+    p.tile1 = a.row1 * p.tiles_x;
+    const bool pcf = a.shadow && !a.desc->shadow;
+    if (pcf) {
+        p.shadow = a.shadow; p.shadow_ebase = a.shadow_ebase; p.shadow_size = a.shadow_size; p.shadow_tiles = a.shadow_tiles;
+        for (int i = 0; i < 16; ++i) p.light_vp[i] = a.light_vp[i];
+    }
+    p.tiled = a.tiled;
+    const bool ids = a.desc->material != nullptr;
+    p.emission = a.emission;
+    p.emis_tiled = ids && a.emission ? a.emis_tiled : nullptr;
+    p.mat_gloss = a.mat_gloss;
+    p.gloss_tiled = ids && a.mat_gloss ? a.gloss_tiled : nullptr;
+    p.nmat = a.nmat;
+    const int tiles = p.tile1 - p.tile0;
+    if (tiles <= 0) return hipSuccess;
+    const int per_block = VCT_SHADE_BLOCK / 64;       // tiles (waves) per workgroup
+    if (pcf) hipLaunchKernelGGL(k_gbuffer_import<true>, dim3((tiles + per_block - 1) / per_block), dim3(VCT_SHADE_BLOCK), 0, s, p);
+    else hipLaunchKernelGGL(k_gbuffer_import<false>, dim3((tiles + per_block - 1) / per_block), dim3(VCT_SHADE_BLOCK), 0, s, p);
     return hipGetLastError();
 }
 

@@ -378,25 +378,50 @@ struct Voxel_Cone_Tracing {
                (ShowAmbientOcclusion ? (uint32_t)VCT_SHOW_AMBIENT_OCCLUSION : 0u);
     }
 
-    void Render() {
-        if (!ctx || !model.scene) return;
+    // What every frame hands over before it is drawn: the switches, changed tables, the camera and the light.
+    bool HandOverFrameState() {
         vct_set_ambient_factor(ctx, AmbientFactor);
-        if (!check(vct_set_lighting_components(ctx, ShowMask()), "vct_set_lighting_components")) return;
-        if (!check(vct_set_diffuse_rate(ctx, DiffuseRate), "vct_set_diffuse_rate")) return;
+        if (!check(vct_set_lighting_components(ctx, ShowMask()), "vct_set_lighting_components")) return false;
+        if (!check(vct_set_diffuse_rate(ctx, DiffuseRate), "vct_set_diffuse_rate")) return false;
         if (emission_dirty) {                                    // a changed table: upload, and rebuild the volume from it
-            if (!UploadEmission()) return;
+            if (!UploadEmission()) return false;
             if (!DynamicLight || Bounces >= 2) DrawVoxelTexture();      // (a whole GI pass below rebuilds it anyway)
-            if (last_status != VCT_OK) return;
+            if (last_status != VCT_OK) return false;
         }
-        if (gloss_dirty && !UploadGloss()) return;              // changed classes: the G-buffer pass below writes them
+        if (gloss_dirty && !UploadGloss()) return false;        // changed classes: the G-buffer pass below writes them
         if (sky_dirty) {                                        // a refused sky stays pending, like a refused emission table
             sky_dirty = !check(vct_set_sky(ctx, Sky), "vct_set_sky");
-            if (sky_dirty) return;
+            if (sky_dirty) return false;
         }
         const float cam[3] = {camera.position.x, camera.position.y, camera.position.z};   // VCT.h:167
         const float L[3] = {lightDirection.x, lightDirection.y, lightDirection.z};         // VCT.h:168
         vct_set_camera_position(ctx, cam);
         vct_set_light_direction(ctx, L);
+        return true;
+    }
+
+    // A frame from the caller's own buffers instead of the model's raster (vct_import_gbuffer, include/vct.h "G-buffer
+    // import"; no reference counterpart): what Render() hands over, the import into the selected frame slot -- this
+    // rank's slab of tile rows on a multi-GPU run -- and the trace.  Frame() returns it.  The volume is the model's.
+    void ImportGBuffer(const vct_gbuffer_import& in) {
+        if (!ctx) return;
+        if (!HandOverFrameState()) return;
+        int32_t row0 = 0, row1 = 0;
+        if (vct_comm_slab(ctx, &row0, &row1) == VCT_OK) {
+            if (!check(vct_import_gbuffer_rows(ctx, &in, row0, row1), "vct_import_gbuffer_rows")) return;
+            if (!check(vct_frame_step(ctx), "vct_frame_step")) return;
+        } else {
+            if (!check(vct_import_gbuffer(ctx, &in), "vct_import_gbuffer")) return;
+            if (!check(vct_trace_resident(ctx), "vct_trace_resident")) return;
+        }
+        frame_on_host = false;
+    }
+
+    void Render() {
+        if (!ctx || !model.scene) return;
+        if (!HandOverFrameState()) return;
+        const float cam[3] = {camera.position.x, camera.position.y, camera.position.z};   // VCT.h:167
+        const float L[3] = {lightDirection.x, lightDirection.y, lightDirection.z};         // VCT.h:168
         vcth_camera hc;
         memcpy(hc.position, cam, sizeof(cam));
         hc.yaw = camera.Yaw; hc.pitch = camera.Pitch; hc.zoom = camera.Zoom;

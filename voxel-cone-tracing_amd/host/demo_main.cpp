@@ -10,8 +10,13 @@
 //            [--voxels [current|radiance|albedo|normal[:level]]] [--ambient-cubes NX,NY,NZ FILE] [--dump-chain FILE]
 //            [--emission MATERIAL=R,G,B[;MATERIAL=R,G,B...]]
 //            [--gloss-classes TAN,SHIN[;TAN,SHIN...] --gloss MATERIAL=CLASS[;MATERIAL=CLASS...]]
-//            [--sky-gradient ZR,ZG,ZB;HR,HG,HB;GR,GG,GB[;UX,UY,UZ] | --sky-sh FILE]
+//            [--sky-gradient ZR,ZG,ZB;HR,HG,HB;GR,GG,GB[;UX,UY,UZ] | --sky-sh FILE] [--reimport]
 //
+// --reimport: after the frames, the G-buffer the library rasterised is read back and packed on the host into what a deferred
+//   renderer keeps -- position F32X3, geometric and shading normals as F16X4, albedo and specular as UNORM8, the shadow
+//   plane -- then imported (Voxel_Cone_Tracing::ImportGBuffer, vct_import_gbuffer) and traced, and the relative L2
+//   between the two frames is printed: the cost of fp16 normals, 8-bit colours and a synthesised tangent frame.
+//   Single GPU only.
 // --sky-gradient COLOURS / --sky-sh FILE: sky light (Voxel_Cone_Tracing::SetSkyGradient / SetSky, vct_set_sky): what a
 //   cone gathers from the part of its footprint that reaches open air.  The gradient form takes a zenith, a horizon and a
 //   ground colour and an optional up vector (+y) and lights with their second-order spherical-harmonic projection
@@ -74,6 +79,28 @@ static float half_to_float(uint16_t h) {
     return s ? -f : f;
 }
 
+// round to nearest even; overflow to infinity, NaN stays NaN
+static uint16_t float_to_half(float f) {
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    const uint16_t sign = (uint16_t)((u >> 16) & 0x8000u);
+    u &= 0x7fffffffu;
+    if (u >= 0x7f800000u) return (uint16_t)(sign | (u > 0x7f800000u ? 0x7e00u : 0x7c00u));
+    if (u >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);                 // rounds to 65536 or more
+    if (u < 0x33000001u) return sign;                                       // at most half the smallest subnormal
+    if (u < 0x38800000u) {                                                  // subnormal half: m * 2^-24
+        const uint32_t shift = 126u - (u >> 23), mant = (u & 0x7fffffu) | 0x800000u;
+        const uint32_t q = mant >> shift, rem = mant & ((1u << shift) - 1u), halfway = 1u << (shift - 1u);
+        return (uint16_t)(sign | (q + (rem > halfway || (rem == halfway && (q & 1u)) ? 1u : 0u)));
+    }
+    const uint32_t q = (u - 0x38000000u) >> 13, rem = u & 0x1fffu;
+    return (uint16_t)(sign | (q + (rem > 0x1000u || (rem == 0x1000u && (q & 1u)) ? 1u : 0u)));
+}
+
+static uint8_t float_to_unorm8(float v) {
+    return (uint8_t)(!(v > 0.0f) ? 0 : (v >= 1.0f ? 255 : (int)(v * 255.0f + 0.5f)));
+}
+
 // parent of a multi-GPU run: start one child per rank (fork + exec of this binary; the parent never
 // initialises a GPU) and wait for them
 static int launch_ranks(int gpus, int argc, char** argv) {
@@ -111,7 +138,7 @@ int main(int argc, char** argv) {
     int gpus = 0, rank = -1, in_flight = 1, diffuse_rate = 1;
     const char* scene = "procedural:atrium";
     const char* ppm = nullptr;
-    bool dynamic_light = false;
+    bool dynamic_light = false, reimport = false;
     const char* idfile = nullptr;
     const char* show = nullptr;
     const char* cubes_file = nullptr;
@@ -133,6 +160,7 @@ int main(int argc, char** argv) {
     // (options with a value consume it; --dynamic-light has none and may stand anywhere)
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--dynamic-light")) { dynamic_light = true; continue; }
+        if (!strcmp(argv[i], "--reimport")) { reimport = true; continue; }
         if (!strcmp(argv[i], "--voxels") && !(i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9')) {
             show_voxels = true;                             // the voxel view: SOURCE[:LEVEL] may follow
             if (i + 1 < argc && strncmp(argv[i + 1], "--", 2)) {
@@ -347,6 +375,53 @@ int main(int argc, char** argv) {
     }
     printf("frames=%d size=%dx%d voxels=%d cone_steps=%llu trace_ms=%.3f fnv1a=%016llx\n", frames, w, h,
            voxels, (unsigned long long)steps, ms, (unsigned long long)sum);
+    if (reimport && gpus <= 0 && !show_voxels) {
+        // the renderer "that brings its own G-buffer": the rasterised planes, packed as a deferred renderer keeps them
+        const size_t npix = (size_t)w * h;
+        const std::vector<uint16_t> native(fr, fr + n);
+        std::vector<float> planes(npix * VCT_GB_PLANES);
+        if (vct_download_gbuffer(voxel_cone_tracing.ctx, planes.data()) != VCT_OK) return 7;
+        vct_config cfg;
+        vct_get_config(voxel_cone_tracing.ctx, &cfg);
+        std::vector<float> position(npix * 3);
+        std::vector<uint16_t> normal(npix * 4), shading(npix * 4);
+        std::vector<uint8_t> albedo(npix * 4), specular(npix * 4);
+        for (size_t i = 0; i < npix; ++i) {
+            for (int c = 0; c < 3; ++c) {
+                position[i * 3 + c] = planes[(VCT_GB_POSITION + c) * npix + i];
+                normal[i * 4 + c] = float_to_half(planes[(VCT_GB_NORMAL + c) * npix + i]);
+                shading[i * 4 + c] = float_to_half(planes[(VCT_GB_BUMP_N + c) * npix + i]);
+                specular[i * 4 + c] = float_to_unorm8(planes[(VCT_GB_SPECULAR + c) * npix + i]);
+            }
+            for (int c = 0; c < 4; ++c) albedo[i * 4 + c] = float_to_unorm8(planes[(VCT_GB_ALBEDO + c) * npix + i]);
+            normal[i * 4 + 3] = shading[i * 4 + 3] = 0;
+            specular[i * 4 + 3] = 255;
+        }
+        vct_gbuffer_import in;
+        memset(&in, 0, sizeof in);
+        in.position = position.data(); in.position_format = VCT_IMPORT_POSITION_F32X3;
+        in.normal = normal.data(); in.shading_normal = shading.data(); in.normal_format = VCT_IMPORT_NORMAL_F16X4;
+        in.albedo = albedo.data(); in.albedo_format = VCT_IMPORT_COLOR_UNORM8X4;
+        in.specular = specular.data(); in.specular_format = VCT_IMPORT_COLOR_UNORM8X4;
+        in.shadow = planes.data() + (size_t)VCT_GB_SHADOW * npix;
+        in.location = VCT_MEM_HOST;
+        in.normal_scale = cfg.model_scale;                  // the length the raster gives planes 3-11 (ModelMatrix = scale)
+        voxel_cone_tracing.ImportGBuffer(in);
+        if (voxel_cone_tracing.last_status != VCT_OK) return 3;
+        const uint16_t* again = voxel_cone_tracing.Frame();
+        if (!again) return 3;
+        double num = 0.0, den = 0.0;
+        for (size_t i = 0; i < n; ++i) {
+            const double a = half_to_float(again[i]), b = half_to_float(native[i]);
+            if (!(fabs(a) < INFINITY) || !(fabs(b) < INFINITY)) continue;
+            num += (a - b) * (a - b); den += b * b;
+        }
+        float import_ms = 0.0f;
+        vct_last_gbuffer_import_ms(voxel_cone_tracing.ctx, &import_ms);
+        printf("reimport: position f32x3, normals f16x4, colours unorm8: frame relative L2 %.3e against the rasterised G-buffer, import_ms=%.3f\n",
+               den > 0.0 ? sqrt(num / den) : 0.0, import_ms);
+        fr = again;
+    }
     if (cubes_file && gpus <= 0) {
         // the irradiance-volume use of the point queries: probes at the cell centres of a grid over the scene's bounds
         Model& model = voxel_cone_tracing.model;

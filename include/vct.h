@@ -734,6 +734,83 @@ int vct_import_gbuffer(vct_ctx* ctx, const vct_gbuffer_import* in);
 int vct_import_gbuffer_rows(vct_ctx* ctx, const vct_gbuffer_import* in, int32_t tile_row0, int32_t tile_row1);
 int vct_last_gbuffer_import_ms(vct_ctx* ctx, float* ms);
 
+/* ---- local lights: point and spot lights in the chain and the frame ---------------------------------------------------
+ * No reference counterpart (its only light is the directional one), so the definition is this build's.  A context holds
+ * up to VCT_LIGHTS_MAX point and spot lights.  They add a direct diffuse term to radiance level 0 -- and so light
+ * everything that reads the chain: screen trace at both diffuse rates, vct_bounce, voxel view, point queries,
+ * anisotropic chains, footprint records, all unchanged -- and a direct diffuse and specular term to the frame.  They cast
+ * NO shadows: a light is bounded by its radius and gated by the surface normal.
+ * All arithmetic is fp32; multiplies, adds and compares in the written order, nothing fused; / and sqrtf are IEEE, fmaxf
+ * and fminf are C's (a NaN operand gives the other one); dot(a,b) = (a.x*b.x + a.y*b.y) + a.z*b.z.
+ *   Folding            on the host, once per vct_set_lights; the device sees  R2 = radius*radius,
+ *                      S2 = source_radius*source_radius,  a = unit(direction) (the import's unit(v)),
+ *                      inv_cone = 1.0f / (cos_inner - cos_outer).
+ *   Light j            at a point P with unit normal n:
+ *                        d = position - P;  r2 = dot(d, d);  in = r2 < R2   (false for NaN)
+ *                        l = d / sqrtf(r2)   (per component; r2 = 0 gives NaN, which the fmaxf below turn into 0)
+ *                        q = r2 / R2;  w = fmaxf(1.0f - q*q, 0.0f);  att = (w*w) / fmaxf(r2, S2)
+ *                        spot = 1.0f for a point light; for a SPOT: c = dot(a, l) * -1.0f;
+ *                               t = fminf(fmaxf((c - cos_outer) * inv_cone, 0.0f), 1.0f);  spot = t*t
+ *                        nl = fmaxf(dot(n, l), 0.0f);   k_j = in ? (att * spot) * nl : +0.0f
+ *                        Dsum_c = Dsum_c + color_c * k_j      over j = 0 .. n-1 in order, from +0
+ *                      A light out of range adds exactly +0, so the kernels skip lights for a whole brick or tile when
+ *                      `in` is false for every point of it; the bits are those of the plain loop.
+ *   Level 0            (config.voxel_attributes = 1, VCT_VOX_CONSERVATIVE_AVG) after vct_inject_light has written a brick
+ *                      -- the saturating emission add included -- for every voxel whose attribute-albedo alpha byte is 255:
+ *                      P = the voxel centre (((float)i + 0.5f) / V - 0.5f) * G per axis, as vct_bounce forms it; n = the
+ *                      stored normal's bytes - 128, normalised as vct_bounce does; alb_c = the attribute albedo byte / 255;
+ *                        texel_c = unorm8 of (texel_c / 255 + alb_c * Dsum_c)   for c = r, g, b (round to nearest,
+ *                      clamped: the form of the bounce's write-back); alpha untouched.  A voxel whose stored normal is zero
+ *                      (thin geometry whose face normals cancel) has n = NaN, nl = 0 and takes no local light.  Voxels
+ *                      without fragments stay 0; the voxel attributes are unchanged.  The term does not depend on the
+ *                      shadow map.
+ *   Frame              every frame slot gets three fp32 LIT PLANES, tiled [tile][3][64] like the emission planes.  Right
+ *                      before every launch that composites a G-buffer -- vct_trace and its slab, resident, rows and strided
+ *                      forms, vct_trace_current, the last launch of a half-rate pass, vct_gi_pass, a rank's vct_frame_step --
+ *                      one kernel fills them for the tile rows [row0, row1) of that launch (a strided launch: every row of
+ *                      the range) from the G-buffer that launch reads.  For a pixel that is not discarded, with P = planes
+ *                      0-2, N = planes 12-14, Ev = normalize(camera - P) as the composite forms E, Dsum as above with n = N,
+ *                      and per light with the same in, att, spot:
+ *                        R = (2.0f * dot(N, l)) * N - l;   sp = powf(fmaxf(dot(Ev, R), 0.0f), shin)
+ *                        Ssum_c = Ssum_c + color_c * (in ? (att * spot) * sp : +0)
+ *                      (shin = config.shininess, or the pixel's gloss class's under the clamp rule of the gloss plane),
+ *                        Lit_c = (SHOW_DIFFUSE ? Dsum_c * albedo_c : 0) + (SHOW_SPECULAR ? Ssum_c * specColor_c : 0)
+ *                        plane_c = E_c + Lit_c      (E the slot's pixel-emission plane; Lit_c alone when there is none)
+ *                      with the VCT_SHOW_* mask of that launch.  Discarded pixels and lanes outside a ragged frame get +0.
+ *                      The launch takes the lit planes in the place of the pixel-emission planes: the composite's last add
+ *                      reads ((A + D) + S) + (E + Lit).  The per-component outputs are unchanged.
+ * vct_set_lights: NULL or n = 0 detaches.  Waits for work in flight; allocates the device table and zeroed lit planes
+ * (12 B per pixel) for every frame slot -- a later second slot gets its own -- so that a launch allocates nothing.  The
+ * voxel side takes effect with the next vct_voxelize + vct_inject_light (+ vct_build_mips), exactly as a moved
+ * directional light does; the frame side with the next composite launch.  Detached, every kernel launched is the one
+ * launched without this section and every frame, chain and plane is bit for bit what it was.  VCT_ERR_INVALID, the
+ * context keeping what it had: n < 0 or n > VCT_LIGHTS_MAX; a non-finite field; radius <= 0, source_radius <= 0 or a
+ * negative colour; for a SPOT a zero-length axis or not -1 <= cos_outer < cos_inner <= 1; unknown flag bits;
+ * config.voxel_attributes = 0; config.trace_variant 1 .. 4 (and vct_set_trace_variant refuses 1 .. 4 while lights are
+ * attached).  direction, cos_outer and cos_inner of a point light are checked for finiteness only.
+ * vct_voxelize(ctx, VCT_VOX_REFERENCE) with lights attached is VCT_ERR_INVALID, as with emission.
+ * vct_get_lights: the attached lights as given (*n = 0: none); either output may be NULL.
+ * vct_download_pixel_lights: the lit planes of the selected slot's last composite launch with lights attached;
+ * VCT_ERR_INVALID before one.  Rows outside that launch's range hold what earlier launches left (zero at first).
+ * vct_last_lights_ms: device time of [0] the voxel kernel of the last vct_inject_light and [1] the pixel kernel of the
+ * selected slot's last composite launch; needs lights attached and vct_set_trace_timing on when both were issued
+ * (VCT_ERR_INVALID otherwise, and before either has run); waits.
+ * Out of scope: shadows of local lights (cube or spot shadow maps, occlusion cones through the chain); two-sided voxels
+ * for thin cards whose stored normals cancel; area and tube lights other than through emission; IES profiles; more than
+ * 64 lights or clustered light lists; lights in VCT_VOX_REFERENCE mode. */
+#define VCT_LIGHTS_MAX 64
+#define VCT_LIGHT_SPOT 1u
+typedef struct vct_light {            /* 56 B */
+    float position[3];  float radius;         /* world units; the light reaches nothing at distance >= radius */
+    float color[3];     float source_radius;  /* the factor at distance 1; inverse-square falloff is clamped below source_radius */
+    float direction[3]; float cos_outer;      /* SPOT only: axis (need not be unit), cosines of the outer / inner half angle */
+    float cos_inner;    uint32_t flags;       /* 0 = point light, VCT_LIGHT_SPOT */
+} vct_light;
+int vct_set_lights(vct_ctx* ctx, const vct_light* lights, int32_t n);      /* NULL or n = 0 detaches */
+int vct_get_lights(const vct_ctx* ctx, vct_light out[VCT_LIGHTS_MAX], int32_t* n);
+int vct_download_pixel_lights(vct_ctx* ctx, float* planes /* linear [3][h*w] */);
+int vct_last_lights_ms(vct_ctx* ctx, float ms[2]);   /* [0] voxel kernel of the last inject, [1] pixel kernel of the slot's last composite launch */
+
 /* ---- two frames in flight (round 6) -----------------------------------------------------------------
  * The reference's Render() (VCT.h:146-190) issues GL commands; the driver starts frame k + 1 while frame k
  * drains -- nothing in R/main.cpp:77-94 waits for a frame.  A HIP stream does wait: each whole-frame trace

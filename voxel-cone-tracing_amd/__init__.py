@@ -79,6 +79,7 @@ ABI_SYMBOLS = [
     "vct_download_pixel_gloss",
     "vct_set_sky", "vct_get_sky",
     "vct_import_gbuffer", "vct_import_gbuffer_rows", "vct_last_gbuffer_import_ms",
+    "vct_set_lights", "vct_get_lights", "vct_download_pixel_lights", "vct_last_lights_ms",
 ]
 
 
@@ -96,6 +97,27 @@ class Config(C.Structure):
 
 class GlossClass(C.Structure):
     _fields_ = [("tan_specular", C.c_float), ("shininess", C.c_float)]
+
+
+LIGHTS_MAX = 64
+LIGHT_SPOT = 1
+
+
+class Light(C.Structure):
+    """vct_light of include/vct.h (56 B)"""
+    _fields_ = [("position", C.c_float * 3), ("radius", C.c_float), ("color", C.c_float * 3), ("source_radius", C.c_float),
+                ("direction", C.c_float * 3), ("cos_outer", C.c_float), ("cos_inner", C.c_float), ("flags", C.c_uint32)]
+
+
+def point_light(position, color, radius, source_radius):
+    """A point light as Context.set_lights takes it."""
+    return dict(position=tuple(position), color=tuple(color), radius=radius, source_radius=source_radius)
+
+
+def spot_light(position, color, radius, source_radius, direction, cos_inner, cos_outer):
+    """A spot light: axis `direction` (any length), cosines of the inner / outer half angle."""
+    return dict(position=tuple(position), color=tuple(color), radius=radius, source_radius=source_radius,
+                direction=tuple(direction), cos_inner=cos_inner, cos_outer=cos_outer, flags=LIGHT_SPOT)
 
 
 class GBuffer(C.Structure):
@@ -213,6 +235,10 @@ _lib.vct_get_sky.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.vct_import_gbuffer.argtypes = [C.c_void_p, C.c_void_p]
 _lib.vct_import_gbuffer_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
 _lib.vct_last_gbuffer_import_ms.argtypes = [C.c_void_p, C.c_void_p]
+_lib.vct_set_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+_lib.vct_get_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.vct_download_pixel_lights.argtypes = [C.c_void_p, C.c_void_p]
+_lib.vct_last_lights_ms.argtypes = [C.c_void_p, C.c_void_p]
 _lib.vct_upload_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
 
 
@@ -562,6 +588,55 @@ class Context:
         v = C.c_float()
         self._ck(_lib.vct_last_gbuffer_import_ms(self._h, C.byref(v)), "vct_last_gbuffer_import_ms")
         return v.value
+
+    # --- local lights (include/vct.h "local lights")
+    @staticmethod
+    def _light(d):
+        """One vct_light from a Light or a dict of its fields (point_light / spot_light build such dicts)."""
+        if isinstance(d, Light):
+            return d
+        l = Light()
+        for k in ("position", "color", "direction"):
+            v = [float(x) for x in d.get(k, (0.0, 0.0, 0.0))]
+            if len(v) != 3:
+                raise VctError(f"set_lights: {k} has three components")
+            getattr(l, k)[:] = v
+        l.radius, l.source_radius = float(d["radius"]), float(d["source_radius"])
+        l.cos_outer, l.cos_inner = float(d.get("cos_outer", 0.0)), float(d.get("cos_inner", 0.0))
+        l.flags = int(d.get("flags", 0))
+        return l
+
+    def set_lights(self, lights):
+        """The context's point and spot lights: a sequence of at most LIGHTS_MAX Light structures or dicts of their fields
+        (point_light(), spot_light()).  None or an empty sequence detaches.  The voxel chain takes them with the next
+        voxelize + inject_light (+ build_mips), the frame with the next composite launch.  Needs voxel_attributes = 1."""
+        if lights is None or len(lights) == 0:
+            self._ck(_lib.vct_set_lights(self._h, None, 0), "vct_set_lights")
+            return
+        if len(lights) > LIGHTS_MAX:
+            raise VctError(f"set_lights: {len(lights)} lights, a context takes at most {LIGHTS_MAX}")
+        arr = (Light * len(lights))(*[self._light(d) for d in lights])
+        self._ck(_lib.vct_set_lights(self._h, C.cast(arr, C.c_void_p), len(lights)), "vct_set_lights")
+
+    def lights(self):
+        """The attached lights as a list of Light structures (empty: none attached)."""
+        out, n = (Light * LIGHTS_MAX)(), C.c_int32()
+        self._ck(_lib.vct_get_lights(self._h, C.cast(out, C.c_void_p), C.byref(n)), "vct_get_lights")
+        return [out[i] for i in range(n.value)]
+
+    def download_pixel_lights(self):
+        """The selected slot's lit planes (pixel emission + the local lights' direct terms) as its last composite launch
+        left them, float32 [3, h*w] (linear)."""
+        out = np.zeros((3, self.cfg.width * self.cfg.height), np.float32)
+        self._ck(_lib.vct_download_pixel_lights(self._h, _ptr(out)), "vct_download_pixel_lights")
+        return out
+
+    def last_lights_ms(self):
+        """(voxel kernel of the last inject_light, pixel kernel of the selected slot's last composite launch), device ms;
+        trace timing must have been on for both."""
+        v = (C.c_float * 2)()
+        self._ck(_lib.vct_last_lights_ms(self._h, v), "vct_last_lights_ms")
+        return v[0], v[1]
 
     def upload_shadow_map(self, depth, light_vp_rowmajor):
         if depth is None:

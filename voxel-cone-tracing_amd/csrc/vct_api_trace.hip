@@ -269,6 +269,13 @@ int vct_launch_trace_rows(vct_ctx* c, int row0, int row1, uint16_t* out_base, in
     const float* pix_emis = cur(c).emis.get();
     if (pix_emis && variant != 0)
         return vct_fail(c, VCT_ERR_INVALID, "pixel-emission planes need the default trace kernel (config.trace_variant 0)");
+    // local lights (include/vct.h "local lights"): the slot's lit planes -- filled below, right in front of the launch, with
+    // E + Lit -- take the planes' place
+    const float* lit = c->lights.n ? cur(c).lit.get() : nullptr;
+    if (lit && variant != 0)
+        return vct_fail(c, VCT_ERR_INVALID, "local lights need the default trace kernel (config.trace_variant 0)");
+    const float* slot_emis = pix_emis;
+    if (lit) pix_emis = lit;
     p.pix_emis = pix_emis;
     // gloss classes (include/vct.h "per-material gloss"): the slot's plane and the class tables, in the COMP kernel's
     // GLOSS form; config.shininess and the specular table are then not read by this launch
@@ -309,6 +316,25 @@ int vct_launch_trace_rows(vct_ctx* c, int row0, int row1, uint16_t* out_base, in
         p.vt_pix = c->vt_pix.get();
         p.vt_count = c->vt_pix.get() + nt * 64;
         HIP_TRY(c, hipMemsetAsync(p.vt_count, 0, sizeof(uint32_t), cur(c).stream.get()));
+    }
+    if (lit) {
+        VctLightPixArgs la;
+        memset(&la, 0, sizeof(la));
+        la.lights = c->lights.table.get(); la.nlights = c->lights.n;
+        la.width = c->cfg.width; la.height = c->cfg.height; la.tiles_x = vct_tiles_x(c);
+        la.row0 = row0; la.row1 = row1;      // (a strided launch: every row of the range)
+        for (int i = 0; i < 3; ++i) la.cam[i] = c->cam[i];
+        la.shininess = c->cfg.shininess;
+        la.show = c->show_mask;
+        la.gbuf = cur(c).gb_current; la.emis = slot_emis; la.pix_gloss = pix_gloss;
+        la.nclasses = c->gloss.n;
+        for (int k = 0; k < c->gloss.n; ++k) la.class_shininess[k] = c->gloss.cls[k].shininess;
+        la.lit = cur(c).lit.get();
+        if (c->time_traces) HIP_TRY(c, hipEventRecord(cur(c).lit_ev0.get(), cur(c).stream.get()));
+        HIP_TRY(c, vct_launch_light_pixels(la, cur(c).stream.get()));
+        if (c->time_traces) HIP_TRY(c, hipEventRecord(cur(c).lit_ev1.get(), cur(c).stream.get()));
+        cur(c).have_lit = true;
+        cur(c).lit_timed = c->time_traces;
     }
     if (c->time_traces) HIP_TRY(c, hipEventRecord(cur(c).ev0.get(), cur(c).stream.get()));      // (vct_set_trace_timing)
     const hipEvent_t marks[3] = {cur(c).dr_ev[0].get(), cur(c).dr_ev[1].get(), cur(c).dr_ev[2].get()};

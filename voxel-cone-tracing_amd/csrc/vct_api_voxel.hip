@@ -110,6 +110,9 @@ int vct_voxelize(vct_ctx* c, int32_t mode) {
     if (mode == VCT_VOX_REFERENCE && c->mesh.mat_emission)
         return vct_fail(c, VCT_ERR_INVALID, "vct_voxelize: VCT_VOX_REFERENCE is the reference's shaders as written and has no emission "
                                         "(vct_upload_emission(ctx, NULL) first)");
+    if (mode == VCT_VOX_REFERENCE && c->lights.n)
+        return vct_fail(c, VCT_ERR_INVALID, "vct_voxelize: VCT_VOX_REFERENCE is the reference's shaders as written and has no local lights "
+                                        "(vct_set_lights(ctx, NULL, 0) first)");
     HIP_TRY(c, hipSetDevice(c->device));
     PIPE_TRY(vct_pipeline_join(c));       // the staging pool is shared: the other slot's resolve may still read the previous pass
     if (!c->vox.brick_slot || !c->vox.stage || (mode == VCT_VOX_REFERENCE && !c->vox.ref_big))
@@ -179,6 +182,20 @@ int vct_inject_light(vct_ctx* c) {
         if (v.pass_emis && v.emis_pool) a.emis = v.emis_pool.get();
     }
     HIP_TRY(c, vct_launch_resolve(a, c->cfg.voxel_dim, c->vol.level0_dirty, cur(c).stream.get()));
+    // local lights (include/vct.h "local lights"): their direct term into the bricks the resolve has just written
+    if (c->lights.n && c->acc_mode == VCT_VOX_CONSERVATIVE_AVG && v.attr_albedo) {
+        VctLightVoxArgs la;
+        memset(&la, 0, sizeof(la));
+        la.lights = c->lights.table.get(); la.nlights = c->lights.n;
+        la.V = c->cfg.voxel_dim; la.G = c->cfg.grid_world_size;
+        la.level0 = c->vol.chain.get(); la.attr_albedo = v.attr_albedo.get(); la.attr_normal = v.attr_normal.get();
+        la.slot_brick = v.slot_brick.get(); la.brick_prev = c->vol.brick_prev.get(); la.nslots = v.nslots;
+        if (c->time_traces) HIP_TRY(c, hipEventRecord(c->lights.ev0.get(), cur(c).stream.get()));      // (vct_set_trace_timing)
+        HIP_TRY(c, vct_launch_light_voxels(la, cur(c).stream.get()));
+        if (c->time_traces) HIP_TRY(c, hipEventRecord(c->lights.ev1.get(), cur(c).stream.get()));
+        c->lights.vox_have = true;
+        c->lights.vox_timed = c->time_traces;
+    }
     c->vox.acc_pending = false;
     c->vol.level0_resolved();
     c->vox.attrs_valid = c->vox.attr_normal && c->acc_mode == VCT_VOX_CONSERVATIVE_AVG;

@@ -63,6 +63,7 @@ hipError_t slot_create(vct_ctx* c, VctFrameSlot& s, hipStream_t stream) {
     if (e == hipSuccess && c->diffuse_rate == 2) e = s.alloc_half_rate(c->cfg.width, c->cfg.height);
     if (e == hipSuccess && c->mesh.mat_emission) e = vct_emission_planes(c, s);      // material emission is attached: every slot has planes
     if (e == hipSuccess && c->gloss.n) e = vct_gloss_plane(c, s);      // gloss classes are attached: every slot has a plane
+    if (e == hipSuccess && c->lights.n) e = vct_lights_planes(c, s);      // local lights are attached: every slot has lit planes
     s.gb_current = s.gb_tiled.get();
     return e;
 }
@@ -349,6 +350,8 @@ int vct_set_trace_variant(vct_ctx* c, int32_t variant) {
         return vct_fail(c, VCT_ERR_INVALID, "vct_set_trace_variant: variants 1 .. 4 have no gloss classes (vct_set_gloss_classes(ctx, NULL, 0) first)");
     if (variant != 0 && c->sky.attached)
         return vct_fail(c, VCT_ERR_INVALID, "vct_set_trace_variant: variants 1 .. 4 have no sky light (vct_set_sky(ctx, NULL) first)");
+    if (variant != 0 && c->lights.n)
+        return vct_fail(c, VCT_ERR_INVALID, "vct_set_trace_variant: variants 1 .. 4 have no local lights (vct_set_lights(ctx, NULL, 0) first)");
     c->cfg.trace_variant = variant;
     return VCT_OK;
 }

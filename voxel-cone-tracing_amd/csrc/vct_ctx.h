@@ -12,6 +12,7 @@
 
 #include "../../include/vct.h"
 #include "vct_internal.h"
+#include "vct_lights_check.h"
 
 struct vct_comm;      // multi-GPU state (vct_multi.hip)
 
@@ -171,6 +172,11 @@ struct VctFrameSlot {
     // pixel-gloss plane (include/vct.h "per-material gloss"), tiled [tiles][64]: present while gloss classes are attached;
     // a trace launch with a plane marches each pixel's specular cone with its class's table
     VctBuf<uint8_t> gloss;
+    // lit planes (include/vct.h "local lights"), tiled [tiles][3][64]: present while lights are attached; every composite
+    // launch fills the rows it takes (k_light_pixels) and passes them in the place of the pixel-emission planes
+    VctBuf<float> lit;
+    VctEvent lit_ev0, lit_ev1;          // around k_light_pixels (vct_last_lights_ms [1])
+    bool have_lit = false, lit_timed = false;      // a launch has filled them; ... bracketed by the timing events
     // half-rate diffuse gather (vct_set_diffuse_rate(ctx, 2); vct_internal.h VctTraceParams::dr_*), present at rate 2 only
     VctBuf<float4> dr_ind;              // [h][w]
     VctBuf<float4> dr_coarse;           // [ch][cw]
@@ -388,6 +394,17 @@ struct VctSky {
     const float* dev() const { return attached ? poly_dev.get() : nullptr; }
 };
 
+// Local lights (include/vct.h "local lights", vct_api_lights.hip): the attached lights as given and the device copy of
+// their folded form (vct_lights_check.h VctLightDev) that both kernels read.  n == 0: none attached.  Context state:
+// every frame slot and the voxel chain see the same lights.
+struct VctLights {
+    int n = 0;
+    vct_light given[VCT_LIGHTS_MAX] = {};
+    VctBuf<VctLightDev> table;        // [VCT_LIGHTS_MAX]
+    VctEvent ev0, ev1;                // around k_light_voxels (vct_last_lights_ms [0])
+    bool vox_have = false, vox_timed = false;
+};
+
 struct vct_ctx {
     vct_config cfg;
     int device = 0;
@@ -412,6 +429,7 @@ struct vct_ctx {
     int n_diffuse = 0, n_specular = 0;
     VctGloss gloss;
     VctSky sky;
+    VctLights lights;
     bool steps_dirty = true;
     bool fast_div = false;            // set by vct_refresh_steps: constant divisors admit the FMA division
     int last_march_form = 0;          // division of the last march launch: 1 IEEE, 2 verified product, 3 x * r (vct_get_stage_counts [2])
@@ -481,6 +499,8 @@ hipError_t vct_emission_planes(const vct_ctx* c, VctFrameSlot& s);
 // vct_api_gloss.hip: a zeroed pixel-gloss plane for a slot that has none, on the slot's stream; drops the material map (a new mesh)
 hipError_t vct_gloss_plane(const vct_ctx* c, VctFrameSlot& s);
 void vct_material_gloss_detach(vct_ctx* c);
+// vct_api_lights.hip: zeroed lit planes and their timing events for a slot that has none, on the slot's stream
+hipError_t vct_lights_planes(const vct_ctx* c, VctFrameSlot& s);
 // vct_multi.hip: slab of the attached communicator (false: none attached); its release
 bool vct_comm_rows(const vct_ctx* c, int* row0, int* row1);
 void vct_comm_release(vct_ctx* c);

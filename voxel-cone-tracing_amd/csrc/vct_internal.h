@@ -597,4 +597,37 @@ struct VctImportArgs {
 };
 hipError_t vct_launch_gbuffer_import(const VctImportArgs& a, hipStream_t s);
 
+// local lights (include/vct.h "local lights", vct_lights.hip): the folded table (vct_lights_check.h VctLightDev, 64 B per
+// light) is read at wave-uniform indices by both kernels
+struct VctLightDev;
+struct VctLightVoxArgs {
+    const VctLightDev* lights;         // [nlights]
+    int32_t nlights;                   // 1 .. VCT_LIGHTS_MAX
+    int32_t V;
+    float G;
+    uint32_t* level0;                  // [V^3] Morton; bricks the last resolve wrote (brick_prev) are updated in place
+    const uint32_t* attr_albedo;       // [nslots][512] the pooled voxel attributes of that resolve
+    const uint32_t* attr_normal;
+    const uint32_t* slot_brick;        // [nslots]
+    const uint32_t* brick_prev;        // [V^3 / 512]
+    uint32_t nslots;
+};
+struct VctLightPixArgs {
+    const VctLightDev* lights;
+    int32_t nlights;
+    int32_t width, height, tiles_x;
+    int32_t row0, row1;                // tile rows filled
+    float cam[3];
+    float shininess;                   // config.shininess; with a gloss plane, class_shininess[class of the pixel]
+    uint32_t show;                     // VCT_SHOW_* mask of the launch that follows
+    const float* gbuf;                 // tiled [tile][23][64]
+    const float* emis;                 // tiled [tile][3][64] pixel-emission planes or null
+    const uint8_t* pix_gloss;          // tiled [tile][64] or null
+    int32_t nclasses;
+    float class_shininess[8];
+    float* lit;                        // tiled [tile][3][64]
+};
+hipError_t vct_launch_light_voxels(const VctLightVoxArgs& a, hipStream_t s);
+hipError_t vct_launch_light_pixels(const VctLightPixArgs& a, hipStream_t s);
+
 #endif

@@ -238,6 +238,13 @@ struct Voxel_Cone_Tracing {
     // them; the next Render() hands them over -- no volume rebuild, the voxels know nothing of the sky.
     float Sky[9][3] = {};
     bool sky_dirty = false;
+    // Local lights (vct_set_lights, include/vct.h "local lights": the reference has the directional light only): up to
+    // VCT_LIGHTS_MAX point and spot lights, lighting the voxels and the frame, without shadows.  SetLights changes them;
+    // the next Render() hands them over and rebuilds the volume, as it does for a changed emission table.  They need the
+    // voxels' albedo and normal: set VoxelAttributes (or Bounces = 2) before init.
+    std::vector<vct_light> Lights;
+    bool lights_dirty = false;
+    bool VoxelAttributes = false;                    // config.voxel_attributes without a second bounce; set before init
     int Bounces = 1;    // 2 = re-inject the lit voxels once (the "2 bounces" of the reference's README.md:16,
                         // which its code does not implement: VCT.h:138-139 injects once); set before init
 
@@ -267,7 +274,7 @@ struct Voxel_Cone_Tracing {
         cfg.height = screen_height;
         cfg.shadow_map_size = (int32_t)ShadowMapSize;
         cfg.ambient_factor = AmbientFactor;
-        cfg.voxel_attributes = Bounces >= 2 ? 1 : 0;
+        cfg.voxel_attributes = (Bounces >= 2 || VoxelAttributes) ? 1 : 0;
         cfg.device = Device;
         if (!check(vct_create(&cfg, &ctx), "vct_create")) return;
         if (World > 1 || Rank != 0 || CommId[0] || CommId[1])
@@ -359,6 +366,14 @@ struct Voxel_Cone_Tracing {
         return true;
     }
 
+    // The local lights ([n], n <= VCT_LIGHTS_MAX; NULL or 0: none); picked up by the next Render().
+    bool SetLights(const vct_light* lights, size_t n) {
+        if (n > (size_t)VCT_LIGHTS_MAX || (n && !lights)) return false;
+        Lights.assign(lights, lights + n);
+        lights_dirty = true;
+        return true;
+    }
+
     // The sky: coefficients as vct_set_sky takes them (NULL: none), or the three colours of a gradient about `up` (NULL: +y)
     // through vcth_sky_gradient; picked up by the next Render().
     void SetSky(const float sh[9][3]) {
@@ -386,6 +401,12 @@ struct Voxel_Cone_Tracing {
         if (emission_dirty) {                                    // a changed table: upload, and rebuild the volume from it
             if (!UploadEmission()) return false;
             if (!DynamicLight || Bounces >= 2) DrawVoxelTexture();      // (a whole GI pass below rebuilds it anyway)
+            if (last_status != VCT_OK) return false;
+        }
+        if (lights_dirty) {                                      // refused lights stay pending, like a refused emission table
+            lights_dirty = !check(vct_set_lights(ctx, Lights.empty() ? nullptr : Lights.data(), (int32_t)Lights.size()), "vct_set_lights");
+            if (lights_dirty) return false;
+            if (!DynamicLight || Bounces >= 2) DrawVoxelTexture();      // the voxels take them with the next voxelize + inject
             if (last_status != VCT_OK) return false;
         }
         if (gloss_dirty && !UploadGloss()) return false;        // changed classes: the G-buffer pass below writes them

@@ -11,7 +11,13 @@
 //            [--emission MATERIAL=R,G,B[;MATERIAL=R,G,B...]]
 //            [--gloss-classes TAN,SHIN[;TAN,SHIN...] --gloss MATERIAL=CLASS[;MATERIAL=CLASS...]]
 //            [--sky-gradient ZR,ZG,ZB;HR,HG,HB;GR,GG,GB[;UX,UY,UZ] | --sky-sh FILE] [--reimport]
+//            [--light X,Y,Z;R,G,B;RADIUS;SRC[;DX,DY,DZ;INNER_DEG;OUTER_DEG]]...
 //
+// --light SPEC (repeatable, up to 64): a local light (Voxel_Cone_Tracing::SetLights, vct_set_lights) in world units: a point
+//   light at X,Y,Z of colour R,G,B (the factor at distance 1) that reaches RADIUS and whose inverse-square falloff is
+//   clamped below SRC; with an axis and the inner and outer half angle in degrees, a spot light.  The lights enter the
+//   voxels (the context is then created with voxel attributes) and the frame; they cast no shadows.
+//   --light "0,8,0;40,30,20;25;0.5" hangs a warm lamp 8 units above the origin.  Checked before a GPU is touched.
 // --reimport: after the frames, the G-buffer the library rasterised is read back and packed on the host into what a deferred
 //   renderer keeps -- position F32X3, geometric and shading normals as F16X4, albedo and specular as UNORM8, the shadow
 //   plane -- then imported (Voxel_Cone_Tracing::ImportGBuffer, vct_import_gbuffer) and traced, and the relative L2
@@ -148,6 +154,7 @@ int main(int argc, char** argv) {
     const char* gloss_arg = nullptr;
     const char* sky_gradient_arg = nullptr;
     const char* sky_sh_arg = nullptr;
+    std::vector<const char*> light_args;
     int cubes[3] = {0, 0, 0};
     bool show_voxels = false;
     int view_source = VCT_VOXVIEW_CURRENT, view_level = 0;
@@ -193,6 +200,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--gloss")) gloss_arg = argv[++i];
         else if (!strcmp(argv[i], "--sky-gradient")) sky_gradient_arg = argv[++i];
         else if (!strcmp(argv[i], "--sky-sh")) sky_sh_arg = argv[++i];
+        else if (!strcmp(argv[i], "--light") && i + 1 < argc) light_args.push_back(argv[++i]);
         else if (!strcmp(argv[i], "--ambient-cubes") && i + 2 < argc) {
             if (sscanf(argv[++i], "%d,%d,%d", &cubes[0], &cubes[1], &cubes[2]) != 3 || cubes[0] < 1 || cubes[1] < 1 || cubes[2] < 1 ||
                 (long long)cubes[0] * cubes[1] * cubes[2] * 6 > VCT_POINT_QUERY_MAX) {
@@ -216,6 +224,17 @@ int main(int argc, char** argv) {
             fprintf(stderr, "--gloss: MATERIAL=CLASS[;...] with classes below %zu (at '%s')\n", gloss_classes.size(), at);
             return 1;
         }
+    }
+    std::vector<vct_light> lights;                          // --light: every one before a GPU is touched
+    if (light_args.size() > (size_t)VCT_LIGHTS_MAX) { fprintf(stderr, "--light: at most %d lights\n", VCT_LIGHTS_MAX); return 1; }
+    for (const char* spec : light_args) {
+        vct_light l;
+        if (const char* at = vct_demo_parse_light(spec, l)) {
+            fprintf(stderr, "--light: X,Y,Z;R,G,B;RADIUS;SRC[;DX,DY,DZ;INNER_DEG;OUTER_DEG], finite numbers, colour >= 0, radii > 0, "
+                            "axis not zero, 0 <= inner < outer <= 180 (at '%s')\n", at);
+            return 1;
+        }
+        lights.push_back(l);
     }
     float sky_sh[9][3] = {};                                // --sky-gradient / --sky-sh: before a GPU is touched
     if (sky_gradient_arg && sky_sh_arg) { fprintf(stderr, "--sky-gradient and --sky-sh: one sky per context\n"); return 1; }
@@ -247,6 +266,7 @@ int main(int argc, char** argv) {
     voxel_cone_tracing.ShadowMapSize = (unsigned)shadow;
     voxel_cone_tracing.model_path = scene;
     voxel_cone_tracing.Bounces = bounces;
+    voxel_cone_tracing.VoxelAttributes = !lights.empty();   // --light: the lights read the voxels' albedo and normal
     voxel_cone_tracing.DynamicLight = dynamic_light;       // every Render() = one whole GI pass (vct_gi_pass)
     voxel_cone_tracing.FramesInFlight = in_flight;
     voxel_cone_tracing.DiffuseRate = diffuse_rate;
@@ -318,6 +338,7 @@ int main(int argc, char** argv) {
     }
 
     if (sky_gradient_arg || sky_sh_arg) voxel_cone_tracing.SetSky(sky_sh);      // picked up by the first Render()
+    if (!lights.empty()) voxel_cone_tracing.SetLights(lights.data(), lights.size());
 
     float delta_time = 0.05f;
     voxel_cone_tracing.Render();                            // frame 0 pays first-launch costs

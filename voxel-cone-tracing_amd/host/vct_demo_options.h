@@ -82,4 +82,48 @@ static inline bool vct_demo_read_sky_sh(const char* path, float sh[9][3]) {
     return ok;
 }
 
+// --light X,Y,Z;R,G,B;RADIUS;SRC[;DX,DY,DZ;INNER_DEG;OUTER_DEG]: one point light -- position and colour, the radius it
+// reaches and its source radius -- or, with the three further fields, a spot light: axis and the inner and outer half angle
+// in degrees (0 <= inner < outer <= 180).  The values are checked against the contract of vct_set_lights.  Returns null
+// or the place in the text where it stops making sense.
+static inline const char* vct_demo_parse_light(const char* text, vct_light& out) {
+    out = vct_light{};
+    const char* q = text;
+    int used = 0;
+    auto sep = [&]() { if (*q != ';' || !q[1]) return false; ++q; return true; };
+    auto finite = [](float v) { return v == v && !isinf(v); };
+    if (sscanf(q, "%f,%f,%f%n", &out.position[0], &out.position[1], &out.position[2], &used) != 3) return q;
+    q += used;
+    if (!sep()) return q;
+    if (sscanf(q, "%f,%f,%f%n", &out.color[0], &out.color[1], &out.color[2], &used) != 3) return q;
+    for (int i = 0; i < 3; ++i)
+        if (!finite(out.position[i]) || !finite(out.color[i]) || out.color[i] < 0.0f) return q;
+    q += used;
+    if (!sep()) return q;
+    if (sscanf(q, "%f%n", &out.radius, &used) != 1 || !finite(out.radius) || !(out.radius > 0.0f)) return q;
+    q += used;
+    if (!sep()) return q;
+    if (sscanf(q, "%f%n", &out.source_radius, &used) != 1 || !finite(out.source_radius) || !(out.source_radius > 0.0f)) return q;
+    q += used;
+    if (!*q) return nullptr;                       // a point light
+    if (!sep()) return q;
+    if (sscanf(q, "%f,%f,%f%n", &out.direction[0], &out.direction[1], &out.direction[2], &used) != 3) return q;
+    const float len = sqrtf((out.direction[0] * out.direction[0] + out.direction[1] * out.direction[1]) + out.direction[2] * out.direction[2]);
+    if (!finite(len) || !(len > 0.0f)) return q;
+    q += used;
+    if (!sep()) return q;
+    float inner = 0.0f, outer = 0.0f;
+    if (sscanf(q, "%f%n", &inner, &used) != 1 || !finite(inner)) return q;
+    q += used;
+    if (!sep()) return q;
+    if (sscanf(q, "%f%n", &outer, &used) != 1 || !finite(outer) || !(0.0f <= inner && inner < outer && outer <= 180.0f)) return q;
+    q += used;
+    if (*q) return q;
+    out.cos_inner = cosf(inner * 0.017453292519943295f);
+    out.cos_outer = cosf(outer * 0.017453292519943295f);
+    if (!(out.cos_outer < out.cos_inner)) return text;      // angles too close to tell apart in fp32
+    out.flags = VCT_LIGHT_SPOT;
+    return nullptr;
+}
+
 #endif

@@ -468,3 +468,70 @@ def test_bench_native_loop_two_ranks_direct_slabs_on_one_gpu(slabs):
     assert mg["rccl_nranks"] == 2 and [p["rank"] for p in mg["per_rank"]] == [0, 1]
     assert all(p["slab_kernel_ms"] > 0 and p["slab_cone_steps"] > 0 for p in mg["per_rank"])
     assert sum(p["slab_cone_steps"] for p in mg["per_rank"]) == d["cone_steps_per_frame"]
+
+
+def test_comm_init_refused_after_its_allocations_leaves_the_context_as_it_was(vct, monkeypatch):
+    """Direct slabs refuse more than 64 ranks only in the rendezvous, when the root's frame buffers, events, stream and
+    abort word already exist: all of them go with the failed call, nothing is attached, and the context goes on to
+    trace, to form a (1-rank RCCL) communicator and to gather the same frame."""
+    ctx, vp = small_pipeline(vct)
+    ctx.render_gbuffer(vp)
+    want = ctx.trace_current()
+    monkeypatch.setenv("VCT_COMM_MODE", "direct")
+    with pytest.raises(vct.VctError, match="at most 64 ranks"):
+        ctx.comm_init(vct.comm_unique_id(), 0, 65)
+    with pytest.raises(vct.VctError):
+        ctx.frame_step()                                  # nothing attached
+    assert np.array_equal(ctx.trace_current(), want)
+    monkeypatch.delenv("VCT_COMM_MODE")
+    ctx.comm_init(vct.comm_unique_id(), 0, 1)
+    ctx.frame_step(); ctx.frame_step()
+    assert np.array_equal(ctx.comm_download_frame(), want)
+    ctx.comm_destroy()
+    ctx.close()
+
+
+def test_comm_init_that_times_out_in_the_rendezvous_leaves_the_context_as_it_was(vct, monkeypatch):
+    """Rank 1 of 2 with no root anywhere: the rendezvous gives up at the communicator's deadline (the 30 s are a cap
+    against a hang, not a measurement), the context still traces its frame and accepts the next vct_comm_init."""
+    ctx, vp = small_pipeline(vct)
+    ctx.render_gbuffer(vp)
+    want = ctx.trace_current()
+    monkeypatch.setenv("VCT_COMM_MODE", "direct")
+    monkeypatch.setenv("VCT_COMM_TIMEOUT_MS", "300")
+    t0 = time.time()
+    with pytest.raises(vct.VctError, match="never appeared"):
+        ctx.comm_init(vct.comm_unique_id(), 1, 2)
+    assert time.time() - t0 < 30.0
+    assert np.array_equal(ctx.trace_current(), want)
+    ctx.comm_init(vct.comm_unique_id(), 0, 1)             # not "already initialised"
+    ctx.comm_destroy()
+    ctx.close()
+
+
+def test_direct_slabs_one_process_through_all_slab_forms_twice(vct, monkeypatch):
+    """A direct-mode communicator of ONE rank -- rendezvous block, fine-grained frame buffers, flag kernels, no peer --
+    through equal slabs, explicit boundaries and interleaved rows, destroyed and built again on the same context: every
+    frame is the single-context frame, and the rendezvous block exists exactly while the communicator does."""
+    ctx, vp = small_pipeline(vct)
+    ctx.render_gbuffer(vp)
+    want = ctx.trace_current()
+    ty = (120 + 7) // 8
+    monkeypatch.setenv("VCT_COMM_MODE", "direct")
+    for cycle in range(2):
+        ident = vct.comm_unique_id()
+        block = "/dev/shm/vct_" + ident[:12].hex()
+        ctx.comm_init(ident, 0, 1)
+        assert os.path.exists(block)
+        for form in ("equal", "boundaries", "interleaved"):
+            if form == "boundaries":
+                ctx.comm_set_slab_rows([0, ty])
+            elif form == "interleaved":
+                ctx.comm_set_interleaved(True)
+            for _ in range(3):                            # both buffers, reuse of the first
+                ctx.frame_step()
+            assert np.array_equal(ctx.comm_download_frame(), want), (cycle, form)
+        ctx.comm_destroy()
+        assert not os.path.exists(block)
+    assert np.array_equal(ctx.trace_current(), want)
+    ctx.close()

@@ -57,6 +57,8 @@ public:
         if (grew) *grew = true;
         return alloc(n);
     }
+    // n elements allocated another way (fine-grained memory) that hipFree releases: owned from here on
+    void adopt(T* p, size_t n) { reset(); p_ = p; n_ = n; }
     T* get() const { return p_; }
     size_t size() const { return n_; }
     explicit operator bool() const { return p_ != nullptr; }

@@ -19,6 +19,10 @@
 // RCCL is loaded lazily (dlopen) so single-GPU users of libvct_amd.so never pay for it and the library
 // carries no link-time dependency on a particular librccl build (a Python process that already loaded
 // torch's bundled RCCL reuses that one).
+//
+// Everything a communicator holds has an owner (vct_comm; RcclComm and DirectRendezvous for what vct_ctx.h has none for),
+// and vct_frame_step is ONE skeleton for the RCCL path, the direct-mode root and the direct-mode peer: they differ in
+// where the slab goes and in the exchange_* functions.
 #include <dlfcn.h>
 #include <fcntl.h>
 #include <string.h>
@@ -27,6 +31,7 @@
 #include <unistd.h>
 
 #include <chrono>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -150,14 +155,130 @@ __global__ void k_flag_set(uint32_t* flag, uint32_t v) {
     __hip_atomic_store(flag, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// True once pred() holds, false when timeout_ms since t0 passed first (pred is asked before the clock).  spin_first: 2000
+// yields, then 200 us sleeps -- what is usually over within microseconds; otherwise 1 ms sleeps -- processes still starting.
+template <class Pred>
+bool wait_until(Pred pred, long long timeout_ms, bool spin_first, std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now()) {
+    for (int spins = 0; !pred();) {
+        if (std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count() > timeout_ms) return false;
+        if (spin_first && ++spins < 2000) std::this_thread::yield();
+        else std::this_thread::sleep_for(std::chrono::microseconds(spin_first ? 200 : 1000));
+    }
+    return true;
+}
+
+// VCT_COMM_MODE=direct: direct slabs, no RCCL (see DirectShm)
+bool direct_mode() { const char* mode = getenv("VCT_COMM_MODE"); return mode && mode[0] == 'd'; }
+
+// The RCCL communicator with an owner: destroyed with it, unless it was aborted first -- one that may be half way through
+// a collective the peers will never finish (ncclCommAbort frees its resources without waiting for them).  (`h` is set by
+// ncclCommInitRank alone, so the loader found every entry point used here.)
+struct RcclComm {
+    ncclComm_t h = nullptr;
+    RcclComm() = default;
+    RcclComm(const RcclComm&) = delete;
+    RcclComm& operator=(const RcclComm&) = delete;
+    ~RcclComm() { if (h) (void)rccl()->CommDestroy(h); }
+    bool abort() { const bool had = h != nullptr; if (had) (void)rccl()->CommAbort(h); h = nullptr; return had; }
+};
+
+// What one process holds of the direct mode's rendezvous (see DirectShm): the shared block -- mapped, page-locked and
+// visible to this rank's GPU --, a rank's mappings of the root's two frame buffers, the block's name (the root unlinks
+// it) and this process' abort word.  Kernels use all of it: whoever drops it has drained their streams (~vct_comm).
+struct DirectRendezvous {
+    char name[48] = {0};
+    bool root = false;
+    DirectShm* shm = nullptr;          // host mapping of the rendezvous block
+    bool registered = false;           // ... page-locked (hipHostRegister)
+    DirectShm* shm_dev = nullptr;      // the same block as this rank's GPU sees it
+    uint16_t* peer_frame[2] = {nullptr, nullptr};      // ranks > 0: the root's frame buffers, mapped
+    uint32_t* abort_host = nullptr;    // this process' abort word (page-locked, mapped): k_flag_wait gives up when it is set
+    uint32_t* abort_dev = nullptr;
+
+    DirectRendezvous() = default;
+    DirectRendezvous(const DirectRendezvous&) = delete;
+    DirectRendezvous& operator=(const DirectRendezvous&) = delete;
+    ~DirectRendezvous() {      // in this order: the frame mappings, the block, its name, the abort word
+        for (uint16_t* p : peer_frame) if (p) (void)hipIpcCloseMemHandle(p);
+        if (shm) { if (registered) (void)hipHostUnregister(shm); munmap(shm, sizeof(DirectShm)); }
+        if (root && name[0]) shm_unlink(name);
+        if (abort_host) (void)hipHostFree(abort_host);
+    }
+    hipError_t create_abort_word() {
+        hipError_t e = hipHostMalloc((void**)&abort_host, sizeof(uint32_t), hipHostMallocMapped);
+        if (e == hipSuccess) { *abort_host = 0u; e = hipHostGetDevicePointer((void**)&abort_dev, abort_host, 0); }
+        return e;
+    }
+    void raise_abort() { if (abort_host) __atomic_store_n(abort_host, 1u, __ATOMIC_RELEASE); }
+    // The rendezvous: shared block, the root's IPC handles (of `root_frame`), every rank's mapping.  The host-side
+    // waits share ONE deadline, the communicator's timeout from t0 on.  A failure leaves what it got to the destructor.
+    int attach(vct_ctx* c, const void* id128, int rank, int world, int timeout_ms, const VctBuf<uint16_t> root_frame[2]) {
+        if (world > VCT_DIRECT_MAX_RANKS) return vct_fail(c, VCT_ERR_INVALID, "direct slabs: at most 64 ranks");
+        const unsigned char* id = (const unsigned char*)id128;
+        snprintf(name, sizeof(name), "/vct_%02x%02x%02x%02x%02x%02x%02x%02x%02x%02x%02x%02x", id[0], id[1], id[2], id[3],
+                 id[4], id[5], id[6], id[7], id[8], id[9], id[10], id[11]);
+        root = rank == 0;
+        const auto t0 = std::chrono::steady_clock::now();
+        auto wait = [&](auto pred) { return wait_until(pred, timeout_ms, false, t0); };
+        int fd = -1;
+        if (root) {
+            shm_unlink(name);
+            fd = shm_open(name, O_CREAT | O_EXCL | O_RDWR, 0600);
+            if (fd < 0 || ftruncate(fd, sizeof(DirectShm)) != 0) { if (fd >= 0) close(fd); return vct_fail(c, VCT_ERR_DEVICE, "direct slabs: cannot create the rendezvous block"); }
+        } else {
+            if (!wait([&] { return (fd = shm_open(name, O_RDWR, 0600)) >= 0; }))
+                return vct_fail(c, VCT_ERR_DEVICE, "direct slabs: the root's rendezvous block never appeared");
+            struct stat st;
+            if (!wait([&] { return fstat(fd, &st) != 0 || (size_t)st.st_size >= sizeof(DirectShm); })) {      // created, not sized yet
+                close(fd);
+                return vct_fail(c, VCT_ERR_DEVICE, "direct slabs: rendezvous block not sized");
+            }
+        }
+        void* p = mmap(nullptr, sizeof(DirectShm), PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
+        close(fd);
+        if (p == MAP_FAILED) return vct_fail(c, VCT_ERR_DEVICE, "direct slabs: mmap failed");
+        shm = (DirectShm*)p;
+        hipError_t e = hipHostRegister(p, sizeof(DirectShm), hipHostRegisterMapped | hipHostRegisterPortable);
+        registered = e == hipSuccess;
+        if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&shm_dev, p, 0);
+        if (e != hipSuccess) return vct_fail(c, VCT_ERR_DEVICE, std::string("direct slabs: hipHostRegister: ") + hipGetErrorString(e));
+        if (root) {
+            shm->world = (uint32_t)world;
+            for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipIpcGetMemHandle(&shm->frame[k], root_frame[k].get());
+            if (e != hipSuccess) return vct_fail(c, VCT_ERR_DEVICE, std::string("direct slabs: hipIpcGetMemHandle: ") + hipGetErrorString(e));
+            shm->magic = 0x56435444u;
+            __atomic_store_n(&shm->handles_ready, 1u, __ATOMIC_RELEASE);
+            for (int r = 1; r < world; ++r)
+                if (!wait([&] { return __atomic_load_n(&shm->attached[r], __ATOMIC_ACQUIRE) != 0u; }))
+                    return vct_fail(c, VCT_ERR_DEVICE, "direct slabs: rank " + std::to_string(r) + " never attached");
+        } else {
+            if (!wait([&] { return __atomic_load_n(&shm->handles_ready, __ATOMIC_ACQUIRE) != 0u; }))
+                return vct_fail(c, VCT_ERR_DEVICE, "direct slabs: the root never published its frame buffers");
+            for (int k = 0; k < 2 && e == hipSuccess; ++k)
+                e = hipIpcOpenMemHandle((void**)&peer_frame[k], shm->frame[k], hipIpcMemLazyEnablePeerAccess);
+            if (e != hipSuccess) return vct_fail(c, VCT_ERR_DEVICE, std::string("direct slabs: hipIpcOpenMemHandle: ") + hipGetErrorString(e));
+            __atomic_store_n(&shm->attached[rank], 1u, __ATOMIC_RELEASE);
+        }
+        return VCT_OK;
+    }
+};
+
 }  // namespace
 
+// The ORDER of the owning members is the teardown order read backwards, and a correctness requirement: ~vct_comm drains
+// the streams, then the rendezvous goes (IPC mappings, hipHostUnregister + munmap, shm_unlink on the root, abort word),
+// then the RCCL communicator, then buffers and events, and last of all the communication stream.
 struct vct_comm {
-    ncclComm_t comm = nullptr;
+    VctStream comm_stream;
+    VctEvent traced[2], gathered[2];
+    VctEvent g0[2], g1[2];             // timing: around the frame's exchange step
+    VctBuf<uint16_t> buf[2];           // root: the frame (world padded slabs); others: this rank's slab (none in direct mode)
+    VctBuf<uint16_t> il_frame[2];      // root only, see `interleaved`
+    RcclComm comm;
+    DirectRendezvous rv;               // direct slabs (VCT_COMM_MODE=direct): no RCCL communicator; see DirectShm above
     int rank = 0, world = 1;
     int row0 = 0, row1 = 0;            // tile rows of this rank's slab
-    int rows_per_rank = 0;             // padded slab height in tile rows of the EQUAL partition (the gather's sendcount)
-    size_t slab_halves = 0;            // halves per padded equal slab
+    size_t slab_halves = 0;            // halves per padded slab of the EQUAL partition (the gather's sendcount)
     // load-aware partition (vct_comm_set_slab_rows): tile-row boundaries of every rank, [world + 1]; empty = the equal
     // partition above.  Uneven slabs travel by grouped ncclSend / ncclRecv straight to their rows of the root's frame.
     std::vector<int> starts;
@@ -165,82 +286,57 @@ struct vct_comm {
     // frame, so the slabs cost the same BY CONSTRUCTION (no histogram, no feedback rounds).  A rank traces its rows back
     // to back into its padded slab, the slabs travel with the one equal-count ncclGather, and the root de-interleaves
     // them into `il_frame` (one 8-byte copy per pixel on the communication stream, behind the gather).
+    bool interleaved = false;
     // VCT_COMM_STREAM=same: the gather is issued on the context's stream right behind the trace instead of on the
     // communication stream behind an event (profiles/experiments/README.md "gather beside the next trace")
     bool same_stream = false;
-    bool comm_stream_overlaps = false;     // the communication stream was seen to run beside the context's stream
-    bool interleaved = false;
-    uint16_t* il_frame[2] = {nullptr, nullptr};      // root only
-    size_t buf_halves = 0;             // allocation of each gather buffer
-    hipStream_t comm_stream = nullptr;
-    uint16_t* buf[2] = {nullptr, nullptr};   // root: the frame (world padded slabs); others: this rank's slab
-    hipEvent_t traced[2] = {nullptr, nullptr}, gathered[2] = {nullptr, nullptr};
-    hipEvent_t g0[2] = {nullptr, nullptr}, g1[2] = {nullptr, nullptr};     // timing: around the frame's exchange step
     unsigned long long frames = 0;     // steps issued
     int last = -1;                     // buffer of the last issued step
-    // direct slabs (VCT_COMM_MODE=direct): no RCCL communicator; see DirectShm above
     bool direct = false;
-    char shm_name[48] = {0};
-    DirectShm* shm = nullptr;          // host mapping of the rendezvous block
-    DirectShm* shm_dev = nullptr;      // the same block as this rank's GPU sees it
-    uint16_t* peer_frame[2] = {nullptr, nullptr};      // ranks > 0: the root's frame buffers, mapped
     hipStream_t ctx_stream = nullptr;  // the context's stream (direct mode queues flag kernels and peer stores on it: drained at teardown)
     hipStream_t ctx_stream2 = nullptr; // ... and the other frame slot's, when the context runs two frames in flight
-    uint32_t* abort_host = nullptr;    // this process' abort word (page-locked, mapped): k_flag_wait gives up when it is set
-    uint32_t* abort_dev = nullptr;
     long long wall_khz = 100000;       // wall_clock64 rate of this device (hipDeviceAttributeWallClockRate)
     int timeout_ms = 60000;            // vct_comm_sync gives up after this long and aborts the communicator
     bool broken = false;               // the communicator was aborted (a peer died or hung): only vct_comm_destroy is left
+
+    ~vct_comm() {
+        if (direct) {
+            // Direct slabs: flag waits and the trace kernels that store into the root's mapped frame may still be QUEUED
+            // (a host-side deadline fires before a wait that sits behind long compute has even started).  They must have
+            // left the GPU before the mappings they use go away -- so: raise the abort word (every wait of this process
+            // returns at its next poll; each is deadline-bounded anyway), drain BOTH streams, and only then close the IPC
+            // handles and unregister the block.  Cannot hang: nothing left in the queues waits on a peer.
+            rv.raise_abort();
+            if (ctx_stream) (void)hipStreamSynchronize(ctx_stream);
+            if (ctx_stream2) (void)hipStreamSynchronize(ctx_stream2);
+            if (comm_stream) (void)hipStreamSynchronize(comm_stream.get());
+        } else if (comm_stream && !broken) {
+            (void)hipStreamSynchronize(comm_stream.get());
+        }
+        if (broken) comm.abort();      // (not destroyed: that would wait for the peers.  Direct slabs have none.)
+    }
+    // direct slabs, step f: its generation, and the flag waits' deadline in wall_clock64 ticks (ticks per ms = the rate in kHz)
+    uint32_t gen() const { return (uint32_t)(frames >> 1) + 1u; }
+    long long ticks() const { return (long long)timeout_ms * wall_khz; }
 };
 
 // An RCCL call failed: the communicator may be half way through a collective the peers will never finish, so it
-// is aborted (ncclCommAbort frees its resources without waiting for them) and the context keeps only the error.
+// is aborted and the context keeps only the error.
 static int comm_fail(vct_ctx* c, vct_comm* m, const std::string& what, ncclResult_t r) {
     std::string msg = what + ": " + (rccl()->GetErrorString ? rccl()->GetErrorString(r) : "RCCL error");
-    if (m && m->comm && rccl()->CommAbort) { (void)rccl()->CommAbort(m->comm); m->comm = nullptr; msg += " (communicator aborted)"; }
-    if (m) m->broken = true;
+    if (m->comm.abort()) msg += " (communicator aborted)";
+    m->broken = true;
     return vct_fail(c, VCT_ERR_DEVICE, msg);
 }
 
-#define NCCL_TRY(c, m, expr)                                              \
-    do {                                                                  \
-        ncclResult_t r_ = (expr);                                         \
-        if (r_ != ncclSuccess) return comm_fail((c), (m), #expr, r_);     \
-    } while (0)
+static size_t row_halves(const vct_ctx* c) { return (size_t)VCT_TILE * c->cfg.width * 4; }      // RGBA16F halves of one tile row
+static int launched(vct_ctx* c) { HIP_TRY(c, hipGetLastError()); return VCT_OK; }      // what the launch just issued came to
 
-static void comm_free(vct_comm* m) {
-    if (!m) return;
-    if (m->direct) {
-        // Direct slabs: flag waits and the trace kernels that store into the root's mapped frame may still be QUEUED
-        // (a host-side deadline fires before a wait that sits behind long compute has even started).  They must have
-        // left the GPU before the mappings they use go away -- so: raise the abort word (every wait of this process
-        // returns at its next poll; each is deadline-bounded anyway), drain BOTH streams, and only then close the IPC
-        // handles and unregister the block.  Cannot hang: nothing left in the queues waits on a peer.
-        if (m->abort_host) __atomic_store_n(m->abort_host, 1u, __ATOMIC_RELEASE);
-        if (m->ctx_stream) (void)hipStreamSynchronize(m->ctx_stream);
-        if (m->ctx_stream2) (void)hipStreamSynchronize(m->ctx_stream2);
-        if (m->comm_stream) (void)hipStreamSynchronize(m->comm_stream);
-        for (int k = 0; k < 2; ++k) if (m->peer_frame[k]) (void)hipIpcCloseMemHandle(m->peer_frame[k]);
-        if (m->shm) { (void)hipHostUnregister(m->shm); munmap(m->shm, sizeof(DirectShm)); }
-        if (m->rank == 0 && m->shm_name[0]) shm_unlink(m->shm_name);
-        if (m->abort_host) (void)hipHostFree(m->abort_host);
-    } else if (m->comm_stream && !m->broken) {
-        (void)hipStreamSynchronize(m->comm_stream);
-    }
-    if (m->comm) {
-        if (m->broken && rccl()->CommAbort) (void)rccl()->CommAbort(m->comm);
-        else if (rccl()->CommDestroy) (void)rccl()->CommDestroy(m->comm);
-    }
-    for (int k = 0; k < 2; ++k) {
-        if (m->il_frame[k]) (void)hipFree(m->il_frame[k]);
-        if (m->buf[k]) (void)hipFree(m->buf[k]);
-        if (m->traced[k]) (void)hipEventDestroy(m->traced[k]);
-        if (m->gathered[k]) (void)hipEventDestroy(m->gathered[k]);
-        if (m->g0[k]) (void)hipEventDestroy(m->g0[k]);
-        if (m->g1[k]) (void)hipEventDestroy(m->g1[k]);
-    }
-    if (m->comm_stream) (void)hipStreamDestroy(m->comm_stream);
-    delete m;
+// the root's de-interleave of `world` gathered slabs into a frame (k_deinterleave), on stream s
+static int launch_deinterleave(vct_ctx* c, hipStream_t s, const void* gathered, void* frame, int world, size_t slab_pixels) {
+    hipLaunchKernelGGL(k_deinterleave, dim3(2048), dim3(256), 0, s, (const uint2*)gathered, (uint2*)frame, c->cfg.width,
+                       c->cfg.height, world, slab_pixels);
+    return launched(c);
 }
 
 void vct_comm_release(vct_ctx* c) {
@@ -248,7 +344,7 @@ void vct_comm_release(vct_ctx* c) {
     // (frame slots may have been added or switched since vct_comm_init: the streams that carry this communicator's work NOW)
     c->comm->ctx_stream = cur(c).stream.get();
     c->comm->ctx_stream2 = c->frames_in_flight > 1 ? other(c).stream.get() : nullptr;
-    comm_free(c->comm);
+    delete c->comm;
     c->comm = nullptr;
 }
 
@@ -303,8 +399,7 @@ int vct_slab_partition_weighted(const uint64_t* row_cost, int32_t tile_rows, int
 
 int vct_comm_get_unique_id(void* id128) {
     if (!id128) return VCT_ERR_INVALID;
-    const char* mode = getenv("VCT_COMM_MODE");
-    if (mode && mode[0] == 'd') {              // direct slabs never touch RCCL: any 128 unpredictable bytes name the rendezvous
+    if (direct_mode()) {              // direct slabs never touch RCCL: any 128 unpredictable bytes name the rendezvous
         FILE* fp = fopen("/dev/urandom", "rb");
         const bool ok = fp && fread(id128, 1, 128, fp) == 128;
         if (fp) fclose(fp);
@@ -318,141 +413,82 @@ int vct_comm_get_unique_id(void* id128) {
     return VCT_OK;
 }
 
-// Rendezvous of the direct mode: shared block, the root's IPC handles, every rank's mapping.  Host-side waits are
-// bounded by the communicator's timeout.
-static int direct_attach(vct_ctx* c, vct_comm* m, const void* id128) {
-    if (m->world > VCT_DIRECT_MAX_RANKS) return vct_fail(c, VCT_ERR_INVALID, "direct slabs: at most 64 ranks");
-    const unsigned char* id = (const unsigned char*)id128;
-    snprintf(m->shm_name, sizeof(m->shm_name), "/vct_%02x%02x%02x%02x%02x%02x%02x%02x%02x%02x%02x%02x", id[0], id[1], id[2], id[3],
-             id[4], id[5], id[6], id[7], id[8], id[9], id[10], id[11]);
-    const auto t0 = std::chrono::steady_clock::now();
-    auto expired = [&]() { return std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count() > m->timeout_ms; };
-    int fd = -1;
-    if (m->rank == 0) {
-        shm_unlink(m->shm_name);
-        fd = shm_open(m->shm_name, O_CREAT | O_EXCL | O_RDWR, 0600);
-        if (fd < 0 || ftruncate(fd, sizeof(DirectShm)) != 0) { if (fd >= 0) close(fd); return vct_fail(c, VCT_ERR_DEVICE, "direct slabs: cannot create the rendezvous block"); }
-    } else {
-        while ((fd = shm_open(m->shm_name, O_RDWR, 0600)) < 0) {
-            if (expired()) return vct_fail(c, VCT_ERR_DEVICE, "direct slabs: the root's rendezvous block never appeared");
-            std::this_thread::sleep_for(std::chrono::milliseconds(2));
-        }
-        struct stat st;
-        while (fstat(fd, &st) == 0 && (size_t)st.st_size < sizeof(DirectShm)) {      // created, not sized yet
-            if (expired()) { close(fd); return vct_fail(c, VCT_ERR_DEVICE, "direct slabs: rendezvous block not sized"); }
-            std::this_thread::sleep_for(std::chrono::milliseconds(1));
-        }
-    }
-    void* p = mmap(nullptr, sizeof(DirectShm), PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
-    close(fd);
-    if (p == MAP_FAILED) return vct_fail(c, VCT_ERR_DEVICE, "direct slabs: mmap failed");
-    m->shm = (DirectShm*)p;
-    hipError_t e = hipHostRegister(p, sizeof(DirectShm), hipHostRegisterMapped | hipHostRegisterPortable);
-    if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&m->shm_dev, p, 0);
-    if (e != hipSuccess) { munmap(p, sizeof(DirectShm)); m->shm = nullptr; return vct_fail(c, VCT_ERR_DEVICE, std::string("direct slabs: hipHostRegister: ") + hipGetErrorString(e)); }
-    if (m->rank == 0) {
-        m->shm->world = (uint32_t)m->world;
-        for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipIpcGetMemHandle(&m->shm->frame[k], m->buf[k]);
-        if (e != hipSuccess) return vct_fail(c, VCT_ERR_DEVICE, std::string("direct slabs: hipIpcGetMemHandle: ") + hipGetErrorString(e));
-        m->shm->magic = 0x56435444u;
-        __atomic_store_n(&m->shm->handles_ready, 1u, __ATOMIC_RELEASE);
-        for (int r = 1; r < m->world; ++r)
-            while (!__atomic_load_n(&m->shm->attached[r], __ATOMIC_ACQUIRE)) {
-                if (expired()) return vct_fail(c, VCT_ERR_DEVICE, "direct slabs: rank " + std::to_string(r) + " never attached");
-                std::this_thread::sleep_for(std::chrono::milliseconds(1));
-            }
-    } else {
-        while (!__atomic_load_n(&m->shm->handles_ready, __ATOMIC_ACQUIRE)) {
-            if (expired()) return vct_fail(c, VCT_ERR_DEVICE, "direct slabs: the root never published its frame buffers");
-            std::this_thread::sleep_for(std::chrono::milliseconds(1));
-        }
-        for (int k = 0; k < 2 && e == hipSuccess; ++k)
-            e = hipIpcOpenMemHandle((void**)&m->peer_frame[k], m->shm->frame[k], hipIpcMemLazyEnablePeerAccess);
-        if (e != hipSuccess) return vct_fail(c, VCT_ERR_DEVICE, std::string("direct slabs: hipIpcOpenMemHandle: ") + hipGetErrorString(e));
-        __atomic_store_n(&m->shm->attached[m->rank], 1u, __ATOMIC_RELEASE);
-    }
-    return VCT_OK;
-}
-
 // All or nothing: the communicator is built into a local object and attached to the context only when every
-// allocation and ncclCommInitRank succeeded; on any failure everything is released and the context is as before
-// (a retry is possible, vct_frame_step keeps refusing).
+// allocation and the rendezvous / ncclCommInitRank succeeded; on any failure the local object goes with the scope and
+// the context is as before (a retry is possible, vct_frame_step keeps refusing).
 int vct_comm_init(vct_ctx* c, const void* id128, int32_t rank, int32_t world) {
     if (!c) return VCT_ERR_INVALID;
     if (!id128 || world <= 0 || rank < 0 || rank >= world) return vct_fail(c, VCT_ERR_INVALID, "vct_comm_init: bad rank / world / id");
     if (c->comm) return vct_fail(c, VCT_ERR_INVALID, "vct_comm_init: already initialised (vct_comm_destroy first)");
     if (c->aov_which) return vct_fail(c, VCT_ERR_INVALID, "vct_comm_init: per-component outputs are on (they are not gathered)");
     if (c->diffuse_rate == 2) return vct_fail(c, VCT_ERR_INVALID, "vct_comm_init: diffuse rate 2 traces whole frames only (vct_set_diffuse_rate(ctx, 1) first)");
-    const char* mode = getenv("VCT_COMM_MODE");
-    const bool direct = mode && mode[0] == 'd';       // direct slabs: no RCCL (see DirectShm)
+    const bool direct = direct_mode();
     Rccl* r = direct ? nullptr : rccl();
     if (r && !r->err.empty()) return vct_fail(c, VCT_ERR_DEVICE, r->err);
     HIP_TRY(c, hipSetDevice(c->device));
-    vct_comm* m = new vct_comm();
+    std::unique_ptr<vct_comm> m(new vct_comm());
     m->rank = rank;
     m->world = world;
     m->direct = direct;
-    vct_slab_partition(c->cfg.height, world, rank, &m->row0, &m->row1, &m->rows_per_rank);
-    m->slab_halves = (size_t)m->rows_per_rank * VCT_TILE * c->cfg.width * 4;
-    m->buf_halves = rank == 0 ? m->slab_halves * world : m->slab_halves;
+    int rows_per_rank = 0;
+    vct_slab_partition(c->cfg.height, world, rank, &m->row0, &m->row1, &rows_per_rank);
+    m->slab_halves = (size_t)rows_per_rank * row_halves(c);
+    const size_t buf_halves = rank == 0 ? m->slab_halves * world : m->slab_halves;      // allocation of each gather buffer
     if (const char* t = getenv("VCT_COMM_TIMEOUT_MS")) { const int v = atoi(t); if (v > 0) m->timeout_ms = v; }
     if (const char* t = getenv("VCT_COMM_STREAM")) m->same_stream = t[0] == 's';
     hipError_t e;
+    hipStream_t cs = nullptr;
     if (c->reserved_cus > 0) {       // the CUs the context's streams leave alone (VCT_COMM_RESERVED_CUS)
         hipDeviceProp_t prop;
         e = hipGetDeviceProperties(&prop, c->device);
-        if (e == hipSuccess) e = vct_create_masked_stream(&m->comm_stream, c->device, prop.multiProcessorCount - c->reserved_cus, prop.multiProcessorCount);
+        if (e == hipSuccess) e = vct_create_masked_stream(&cs, c->device, prop.multiProcessorCount - c->reserved_cus, prop.multiProcessorCount);
     } else {
         // the exchange step is meant to run beside the next frame's trace: a stream that shares the context stream's hardware
         // queue would run behind it instead (round 6: HIP hands out four queues; RCCL and torch hold streams of their own)
-        bool ov = false;
-        e = vct_create_overlapping_stream(c, cur(c).stream.get(), &m->comm_stream, &ov) == VCT_OK ? hipSuccess : hipErrorUnknown;
-        m->comm_stream_overlaps = ov;
+        bool overlaps = false;
+        e = vct_create_overlapping_stream(c, cur(c).stream.get(), &cs, &overlaps) == VCT_OK ? hipSuccess : hipErrorUnknown;
     }
+    m->comm_stream.adopt(cs);
     m->ctx_stream = cur(c).stream.get();
     if (direct && e == hipSuccess) {
         int khz = 0;
         if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->device) == hipSuccess && khz > 0) m->wall_khz = khz;
-        e = hipHostMalloc((void**)&m->abort_host, sizeof(uint32_t), hipHostMallocMapped);
-        if (e == hipSuccess) { *m->abort_host = 0u; e = hipHostGetDevicePointer((void**)&m->abort_dev, m->abort_host, 0); }
+        e = m->rv.create_abort_word();
     }
     for (int k = 0; k < 2 && e == hipSuccess; ++k) {
-        if (!(direct && rank != 0)) {        // (a rank of the direct mode owns no slab buffer: it writes the root's)
+        if (direct && rank == 0) {
             // Direct mode: peers store into the root's frame over IPC / xGMI and the root's next kernel reads it with only
             // a kernel-boundary acquire, which need not invalidate lines of LOCAL coarse-grained memory that the root's L2
             // kept from an earlier frame.  Fine-grained memory is not cached that way, so the frame buffers peers write
             // are allocated fine-grained (advisor, round 5); no fallback -- a coarse-grained frame could be silently stale.
-            e = direct ? hipExtMallocWithFlags((void**)&m->buf[k], m->buf_halves * 2, hipDeviceMallocFinegrained)
-                       : hipMalloc(&m->buf[k], m->buf_halves * 2);
-            if (e == hipSuccess) e = hipMemsetAsync(m->buf[k], 0, m->buf_halves * 2, cur(c).stream.get());
+            uint16_t* p = nullptr;
+            e = hipExtMallocWithFlags((void**)&p, buf_halves * 2, hipDeviceMallocFinegrained);
+            if (e == hipSuccess) m->buf[k].adopt(p, buf_halves);
+        } else if (!direct) {        // (a rank of the direct mode owns no slab buffer: it writes the root's)
+            e = m->buf[k].alloc(buf_halves);
         }
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&m->traced[k], hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&m->gathered[k], hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreate(&m->g0[k]);
-        if (e == hipSuccess) e = hipEventCreate(&m->g1[k]);
-        if (e == hipSuccess) e = hipEventRecord(m->gathered[k], cur(c).stream.get());      // "previous gather" of the first use
+        if (e == hipSuccess && m->buf[k]) e = hipMemsetAsync(m->buf[k].get(), 0, buf_halves * 2, cur(c).stream.get());
+        if (e == hipSuccess) e = m->traced[k].create(hipEventDisableTiming);
+        if (e == hipSuccess) e = m->gathered[k].create(hipEventDisableTiming);
+        if (e == hipSuccess) e = m->g0[k].create();
+        if (e == hipSuccess) e = m->g1[k].create();
+        if (e == hipSuccess) e = hipEventRecord(m->gathered[k].get(), cur(c).stream.get());      // "previous gather" of the first use
     }
     if (e == hipSuccess) e = hipStreamSynchronize(cur(c).stream.get());
-    if (e != hipSuccess) {
-        comm_free(m);
-        return vct_fail(c, e == hipErrorOutOfMemory ? VCT_ERR_NOMEM : VCT_ERR_DEVICE,
-                        std::string("vct_comm_init: ") + hipGetErrorString(e));
-    }
+    if (e != hipSuccess)
+        return vct_fail(c, e == hipErrorOutOfMemory ? VCT_ERR_NOMEM : VCT_ERR_DEVICE, std::string("vct_comm_init: ") + hipGetErrorString(e));
     if (direct) {
-        const int rc = direct_attach(c, m, id128);
-        if (rc) { comm_free(m); return rc; }
-        c->comm = m;
-        return VCT_OK;
+        PIPE_TRY(m->rv.attach(c, id128, rank, world, m->timeout_ms, m->buf));
+    } else {
+        ncclUniqueId id;
+        memcpy(id.internal, id128, 128);
+        const ncclResult_t nr = r->CommInitRank(&m->comm.h, world, id, rank);
+        if (nr != ncclSuccess) {
+            m->comm.h = nullptr;          // nothing to destroy: ncclCommInitRank failed
+            return vct_fail(c, VCT_ERR_DEVICE, std::string("ncclCommInitRank: ") + r->GetErrorString(nr));
+        }
     }
-    ncclUniqueId id;
-    memcpy(id.internal, id128, 128);
-    const ncclResult_t nr = r->CommInitRank(&m->comm, world, id, rank);
-    if (nr != ncclSuccess) {
-        m->comm = nullptr;          // nothing to destroy: ncclCommInitRank failed
-        comm_free(m);
-        return vct_fail(c, VCT_ERR_DEVICE, std::string("ncclCommInitRank: ") + r->GetErrorString(nr));
-    }
-    c->comm = m;
+    c->comm = m.release();
     return VCT_OK;
 }
 
@@ -493,8 +529,7 @@ int vct_comm_set_slab_rows(vct_ctx* c, const int32_t* starts) {
             if (starts[r + 1] < starts[r]) return vct_fail(c, VCT_ERR_INVALID, "vct_comm_set_slab_rows: boundaries must not decrease");
     }
     HIP_TRY(c, hipSetDevice(c->device));
-    int rc = vct_comm_sync(c);
-    if (rc) return rc;
+    PIPE_TRY(vct_comm_sync(c));
     m->interleaved = false;
     if (!starts) {
         m->starts.clear();
@@ -504,18 +539,15 @@ int vct_comm_set_slab_rows(vct_ctx* c, const int32_t* starts) {
         m->row0 = starts[m->rank];
         m->row1 = starts[m->rank + 1];
     }
-    const size_t need = m->rank == 0 ? m->buf_halves : (size_t)(m->row1 - m->row0) * VCT_TILE * c->cfg.width * 4;
-    if (need > m->buf_halves && !m->direct) {        // (direct slabs: a rank owns no buffer, it writes the root's frame)
-        uint16_t* nb[2] = {nullptr, nullptr};
-        for (int k = 0; k < 2; ++k) {
-            const hipError_t e = hipMalloc(&nb[k], need * 2);
-            if (e != hipSuccess) {
-                if (nb[0]) (void)hipFree(nb[0]);
-                return vct_fail(c, VCT_ERR_NOMEM, std::string("vct_comm_set_slab_rows: ") + hipGetErrorString(e));
-            }
+    // (the root's frame never grows; direct slabs: a rank owns no buffer, it writes the root's frame)
+    const size_t need = (size_t)(m->row1 - m->row0) * row_halves(c);
+    if (m->rank != 0 && !m->direct && need > m->buf[0].size()) {
+        VctBuf<uint16_t> nb[2];
+        for (VctBuf<uint16_t>& b : nb) {
+            const hipError_t e = b.alloc(need);
+            if (e != hipSuccess) return vct_fail(c, VCT_ERR_NOMEM, std::string("vct_comm_set_slab_rows: ") + hipGetErrorString(e));
         }
-        for (int k = 0; k < 2; ++k) { (void)hipFree(m->buf[k]); m->buf[k] = nb[k]; }
-        m->buf_halves = need;
+        for (int k = 0; k < 2; ++k) m->buf[k] = std::move(nb[k]);
     }
     m->last = -1;
     return VCT_OK;
@@ -528,14 +560,13 @@ int vct_comm_set_interleaved(vct_ctx* c, int32_t on) {
     vct_comm* m = c->comm;
     if (!m || m->broken) return vct_fail(c, VCT_ERR_INVALID, "vct_comm_set_interleaved: no usable communicator (vct_comm_init)");
     HIP_TRY(c, hipSetDevice(c->device));
-    int rc = vct_comm_sync(c);
-    if (rc) return rc;
+    PIPE_TRY(vct_comm_sync(c));
     // the root's de-interleave target first: a failed allocation leaves this rank's state untouched.  (The other
     // ranks cannot see the root's failure: on VCT_ERR_NOMEM the caller must destroy the communicator on every rank.)
     if (on && m->rank == 0)
-        for (int k = 0; k < 2; ++k)
-            if (!m->il_frame[k]) {
-                const hipError_t e = hipMalloc(&m->il_frame[k], (size_t)c->cfg.width * c->cfg.height * 8);
+        for (VctBuf<uint16_t>& f : m->il_frame)
+            if (!f) {
+                const hipError_t e = f.alloc((size_t)c->cfg.width * c->cfg.height * 4);
                 if (e != hipSuccess) return vct_fail(c, VCT_ERR_NOMEM, std::string("vct_comm_set_interleaved: ") + hipGetErrorString(e));
             }
     m->starts.clear();
@@ -550,115 +581,93 @@ int vct_comm_set_interleaved(vct_ctx* c, int32_t on) {
     return VCT_OK;
 }
 
-// One frame: trace this rank's slab into gather buffer k and start its gather.  Asynchronous.
+// ---- the exchange of one frame step: what runs on the exchange stream `cs` between the step's g0 and g1 events ---------
+
+// the direct mode's flag kernels (see DirectShm)
+static int flag_set(vct_ctx* c, hipStream_t s, uint32_t* flag, uint32_t v) {
+    hipLaunchKernelGGL(k_flag_set, dim3(1), dim3(1), 0, s, flag, v);
+    return launched(c);
+}
+static int flag_wait(vct_ctx* c, vct_comm* m, hipStream_t s, const uint32_t* flags, int n, uint32_t want) {
+    hipLaunchKernelGGL(k_flag_wait, dim3(1), dim3(64), 0, s, flags, n, 1, want, &m->rv.shm_dev->timed_out, m->ticks(), m->rv.abort_dev);
+    return launched(c);
+}
+
+static int exchange_rccl(vct_ctx* c, vct_comm* m, int k, hipStream_t cs) {
+    Rccl* r = rccl();
+    uint16_t* slab = m->buf[k].get();
+    if (m->starts.empty()) {
+        // ONE collective per frame, equal (padded) or interleaved slabs alike.  Root: in place (its slab already sits at
+        // offset rank * sendcount = 0).
+        const ncclResult_t nr = r->Gather(slab, m->rank == 0 ? slab : nullptr, m->slab_halves, ncclFloat16, 0, m->comm.h, cs);
+        return nr == ncclSuccess ? VCT_OK : comm_fail(c, m, "ncclGather", nr);
+    }
+    // load-aware slabs differ in size: one fused group of point-to-point transfers, each slab straight to its
+    // rows of the root's frame (what ncclGather is made of inside RCCL, with per-rank counts)
+    ncclResult_t gr = r->GroupStart();
+    if (gr != ncclSuccess) return comm_fail(c, m, "ncclGroupStart", gr);
+    if (m->rank == 0) {
+        for (int peer = 1; peer < m->world && gr == ncclSuccess; ++peer) {
+            const size_t n = (size_t)(m->starts[peer + 1] - m->starts[peer]) * row_halves(c);
+            if (n) gr = r->Recv(slab + (size_t)m->starts[peer] * row_halves(c), n, ncclFloat16, peer, m->comm.h, cs);
+        }
+    } else {
+        const size_t n = (size_t)(m->row1 - m->row0) * row_halves(c);
+        if (n) gr = r->Send(slab, n, ncclFloat16, 0, m->comm.h, cs);
+    }
+    const ncclResult_t ge = r->GroupEnd();
+    if (gr != ncclSuccess) return comm_fail(c, m, "ncclSend/ncclRecv", gr);
+    if (ge != ncclSuccess) return comm_fail(c, m, "ncclGroupEnd", ge);
+    return VCT_OK;
+}
+
+static int exchange_direct_root(vct_ctx* c, vct_comm* m, int k, hipStream_t cs) {
+    return m->world > 1 ? flag_wait(c, m, cs, &m->rv.shm_dev->done[k][1], m->world - 1, m->gen()) : VCT_OK;
+}
+
+static int exchange_direct_peer(vct_ctx* c, vct_comm* m, int k, hipStream_t cs) {
+    return flag_set(c, cs, &m->rv.shm_dev->done[k][m->rank], m->gen());
+}
+
+// One frame: trace this rank's slab into gather buffer k and start its exchange.  Asynchronous.
 int vct_frame_step(vct_ctx* c) {
     if (!c) return VCT_ERR_INVALID;
     vct_comm* m = c->comm;
     if (!m) return vct_fail(c, VCT_ERR_INVALID, "vct_frame_step: call vct_comm_init first");
-    if (m->broken || (!m->comm && !m->direct)) return vct_fail(c, VCT_ERR_DEVICE, "vct_frame_step: the communicator was aborted (vct_comm_destroy, then vct_comm_init again)");
+    if (m->broken || (!m->comm.h && !m->direct)) return vct_fail(c, VCT_ERR_DEVICE, "vct_frame_step: the communicator was aborted (vct_comm_destroy, then vct_comm_init again)");
     if (!cur(c).have_gbuffer) return vct_fail(c, VCT_ERR_INVALID, "vct_frame_step: no G-buffer resident yet");
     HIP_TRY(c, hipSetDevice(c->device));
     const int k = (int)(m->frames & 1ull);
-    // This rank's slab inside buffer k.  The kernel addresses the full frame, so it gets the slab's address minus the
+    const hipStream_t ts = cur(c).stream.get();
+    const bool peer = m->direct && m->rank != 0;      // stores its slab straight into the root's mapped frame
+    HIP_TRY(c, hipStreamWaitEvent(ts, m->gathered[k].get(), 0));    // buffer k is free once its last gather is done
+    if (m->direct)      // the root releases buffer k (it is past frame f - 2), a peer waits for that
+        PIPE_TRY(peer ? flag_wait(c, m, ts, &m->rv.shm_dev->release[k], 1, m->gen() - 1u)
+                      : flag_set(c, ts, &m->rv.shm_dev->release[k], m->gen() - 1u));
+    // This rank's slab: the start of its own buffer k (the root's slab always begins at tile row 0: the frame buffer
+    // itself, in-place gather), or its place in the root's mapped buffer k -- packed slab `rank` (equal / interleaved)
+    // or its own rows.  Contiguous slabs: the kernel addresses the full frame, so it gets the slab's address minus the
     // slab's first row as its output base -- passed to the launch, never stored in the context (on a non-root rank
-    // that address lies before the allocation).  Root: the frame buffer itself (slab 0 at offset 0, in-place gather).
-    uint16_t* slab = m->buf[k];
-    const size_t first_row_halves = (size_t)m->row0 * VCT_TILE * c->cfg.width * 4;
-    HIP_TRY(c, hipStreamWaitEvent(cur(c).stream.get(), m->gathered[k], 0));    // buffer k is free once its last gather is done
-    const bool uneven = !m->starts.empty();
-    if (m->direct) {
-        // direct slabs (see DirectShm): flags instead of a collective, the slab stored straight into the root's frame
-        const uint32_t gen = (uint32_t)(m->frames >> 1) + 1u;
-        const long long ticks = (long long)m->timeout_ms * m->wall_khz;        // wall_clock64 ticks per ms = its rate in kHz
-        const size_t row_halves = (size_t)VCT_TILE * c->cfg.width * 4;
-        if (m->rank == 0) {
-            hipLaunchKernelGGL(k_flag_set, dim3(1), dim3(1), 0, cur(c).stream.get(), &m->shm_dev->release[k], gen - 1u);
-            HIP_TRY(c, hipGetLastError());
-            uint16_t* base = uneven ? m->buf[k] : slab - first_row_halves;
-            const int rc = m->interleaved ? vct_launch_trace_rows(c, m->row0, m->row1, slab, m->world, true)
-                                          : vct_launch_trace_rows(c, m->row0, m->row1, base);
-            if (rc) return rc;
-            const hipStream_t cs = m->same_stream ? cur(c).stream.get() : m->comm_stream;
-            if (!m->same_stream) {
-                HIP_TRY(c, hipEventRecord(m->traced[k], cur(c).stream.get()));
-                HIP_TRY(c, hipStreamWaitEvent(m->comm_stream, m->traced[k], 0));
-            }
-            HIP_TRY(c, hipEventRecord(m->g0[k], cs));
-            if (m->world > 1) {
-                hipLaunchKernelGGL(k_flag_wait, dim3(1), dim3(64), 0, cs, &m->shm_dev->done[k][1], m->world - 1, 1, gen,
-                                   &m->shm_dev->timed_out, ticks, m->abort_dev);
-                HIP_TRY(c, hipGetLastError());
-            }
-            if (m->interleaved) {
-                hipLaunchKernelGGL(k_deinterleave, dim3(2048), dim3(256), 0, cs, (const uint2*)m->buf[k],
-                                   (uint2*)m->il_frame[k], c->cfg.width, c->cfg.height, m->world, m->slab_halves / 4);
-                HIP_TRY(c, hipGetLastError());
-            }
-            HIP_TRY(c, hipEventRecord(m->g1[k], cs));
-            HIP_TRY(c, hipEventRecord(m->gathered[k], cs));
-        } else {
-            hipLaunchKernelGGL(k_flag_wait, dim3(1), dim3(64), 0, cur(c).stream.get(), &m->shm_dev->release[k], 1, 1, gen - 1u,
-                               &m->shm_dev->timed_out, ticks, m->abort_dev);
-            HIP_TRY(c, hipGetLastError());
-            // where this rank's slab lives in the root's buffer k: packed slab `rank` (equal / interleaved) or its own rows
-            uint16_t* peer_slab = m->peer_frame[k] + (uneven ? (size_t)m->starts[m->rank] * row_halves : (size_t)m->rank * m->slab_halves);
-            const int rc = m->interleaved ? vct_launch_trace_rows(c, m->row0, m->row1, peer_slab, m->world, true)
-                                          : vct_launch_trace_rows(c, m->row0, m->row1, peer_slab - first_row_halves);
-            if (rc) return rc;
-            HIP_TRY(c, hipEventRecord(m->g0[k], cur(c).stream.get()));
-            hipLaunchKernelGGL(k_flag_set, dim3(1), dim3(1), 0, cur(c).stream.get(), &m->shm_dev->done[k][m->rank], gen);
-            HIP_TRY(c, hipGetLastError());
-            HIP_TRY(c, hipEventRecord(m->g1[k], cur(c).stream.get()));
-            HIP_TRY(c, hipEventRecord(m->gathered[k], cur(c).stream.get()));
-        }
-        m->last = k;
-        ++m->frames;
-        return VCT_OK;
+    // that address lies before the allocation).  Interleaved: every world-th tile row from `rank` on, back to back
+    // at the start of the slab.  An empty slab launches nothing.
+    uint16_t* slab = !peer ? m->buf[k].get()
+                           : m->rv.peer_frame[k] + (m->starts.empty() ? (size_t)m->rank * m->slab_halves : (size_t)m->row0 * row_halves(c));
+    const bool il = m->interleaved;
+    PIPE_TRY(vct_launch_trace_rows(c, m->row0, m->row1, il ? slab : slab - (size_t)m->row0 * row_halves(c), il ? m->world : 1, il));
+    // The exchange stream, ordered behind the trace.  (A peer's exchange is one flag store behind its own stores:
+    // always on the context's stream, no `traced` event.)
+    const bool behind_trace = m->same_stream || peer;
+    const hipStream_t cs = behind_trace ? ts : m->comm_stream.get();
+    if (!behind_trace) {
+        HIP_TRY(c, hipEventRecord(m->traced[k].get(), ts));
+        HIP_TRY(c, hipStreamWaitEvent(cs, m->traced[k].get(), 0));
     }
-    uint16_t* out_base = (m->rank == 0 && uneven) ? m->buf[k] : slab - first_row_halves;
-    // interleaved: every world-th tile row from `rank` on, back to back at the start of the slab
-    const int rc = m->interleaved ? vct_launch_trace_rows(c, m->row0, m->row1, slab, m->world, true)
-                                  : vct_launch_trace_rows(c, m->row0, m->row1, out_base);     // an empty slab launches nothing
-    if (rc) return rc;
-    const hipStream_t cs = m->same_stream ? cur(c).stream.get() : m->comm_stream;
-    if (!m->same_stream) {
-        HIP_TRY(c, hipEventRecord(m->traced[k], cur(c).stream.get()));
-        HIP_TRY(c, hipStreamWaitEvent(m->comm_stream, m->traced[k], 0));
-    }
-    Rccl* r = rccl();
-    HIP_TRY(c, hipEventRecord(m->g0[k], cs));
-    if (m->interleaved) {
-        NCCL_TRY(c, m, r->Gather(slab, m->rank == 0 ? m->buf[k] : nullptr, m->slab_halves, ncclFloat16, 0, m->comm,
-                                 cs));
-        if (m->rank == 0) {
-            hipLaunchKernelGGL(k_deinterleave, dim3(2048), dim3(256), 0, cs, (const uint2*)m->buf[k],
-                               (uint2*)m->il_frame[k], c->cfg.width, c->cfg.height, m->world, m->slab_halves / 4);
-            HIP_TRY(c, hipGetLastError());
-        }
-    } else if (!uneven) {
-        // ONE collective per frame.  Root: in place (its slab already sits at offset rank * sendcount = 0).
-        NCCL_TRY(c, m, r->Gather(slab, m->rank == 0 ? m->buf[k] : nullptr, m->slab_halves, ncclFloat16, 0, m->comm, cs));
-    } else {
-        // load-aware slabs differ in size: one fused group of point-to-point transfers, each slab straight to its
-        // rows of the root's frame (what ncclGather is made of inside RCCL, with per-rank counts)
-        const size_t row_halves = (size_t)VCT_TILE * c->cfg.width * 4;
-        NCCL_TRY(c, m, r->GroupStart());
-        ncclResult_t gr = ncclSuccess;
-        if (m->rank == 0) {
-            for (int peer = 1; peer < m->world && gr == ncclSuccess; ++peer) {
-                const size_t n = (size_t)(m->starts[peer + 1] - m->starts[peer]) * row_halves;
-                if (n) gr = r->Recv(m->buf[k] + (size_t)m->starts[peer] * row_halves, n, ncclFloat16, peer, m->comm, cs);
-            }
-        } else {
-            const size_t n = (size_t)(m->row1 - m->row0) * row_halves;
-            if (n) gr = r->Send(slab, n, ncclFloat16, 0, m->comm, cs);
-        }
-        const ncclResult_t ge = r->GroupEnd();
-        if (gr != ncclSuccess) return comm_fail(c, m, "ncclSend/ncclRecv", gr);
-        if (ge != ncclSuccess) return comm_fail(c, m, "ncclGroupEnd", ge);
-    }
-    HIP_TRY(c, hipEventRecord(m->g1[k], cs));
-    HIP_TRY(c, hipEventRecord(m->gathered[k], cs));
+    HIP_TRY(c, hipEventRecord(m->g0[k].get(), cs));
+    PIPE_TRY(!m->direct ? exchange_rccl(c, m, k, cs) : peer ? exchange_direct_peer(c, m, k, cs) : exchange_direct_root(c, m, k, cs));
+    if (il && m->rank == 0)      // the root has every rank's packed slab in buffer k: its rows go to their places in the frame
+        PIPE_TRY(launch_deinterleave(c, cs, m->buf[k].get(), m->il_frame[k].get(), m->world, m->slab_halves / 4));
+    HIP_TRY(c, hipEventRecord(m->g1[k].get(), cs));
+    HIP_TRY(c, hipEventRecord(m->gathered[k].get(), cs));
     m->last = k;
     ++m->frames;
     return VCT_OK;
@@ -681,28 +690,20 @@ int vct_comm_sync(vct_ctx* c) {
     // Compute queued on the context's stream in front of the exchange (several 4K / 1024^3 GI passes, a first-use divisor
     // self-test) is not communication: it gets a deadline of its own -- the last step's "slab traced" event -- and the
     // communication deadline starts when that has fired (advisor, round 4).  Both are bounded: a trace that waits behind
-    // the gather of a dead peer two frames back never fires the event, and the second loop then aborts as before.
-    if (m->last >= 0 && !m->same_stream && !m->direct && m->traced[m->last]) {
-        const auto tc = std::chrono::steady_clock::now();
-        int sp = 0;
-        while (hipEventQuery(m->traced[m->last]) == hipErrorNotReady) {
-            if (std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - tc).count() > m->timeout_ms) break;
-            if (++sp < 2000) std::this_thread::yield();
-            else std::this_thread::sleep_for(std::chrono::microseconds(200));
-        }
-    }
-    const auto t0 = std::chrono::steady_clock::now();
-    int spins = 0;
-    while (true) {
+    // the gather of a dead peer two frames back never fires the event, and the second wait then aborts as before.
+    if (m->last >= 0 && !m->same_stream && !m->direct && m->traced[m->last])
+        (void)wait_until([&] { return hipEventQuery(m->traced[m->last].get()) != hipErrorNotReady; }, m->timeout_ms, true);
+    const int pending = 1;      // (no VCT_* code: those are <= 0)
+    auto poll = [&]() -> int {
         hipError_t qc = hipStreamQuery(cur(c).stream.get());
         if (qc != hipSuccess && qc != hipErrorNotReady) HIP_TRY(c, qc);
         if (qc == hipSuccess && c->frames_in_flight > 1) {      // two frames in flight: the other slot's stream carries steps too
             qc = hipStreamQuery(other(c).stream.get());
             if (qc != hipSuccess && qc != hipErrorNotReady) HIP_TRY(c, qc);
         }
-        const hipError_t q = hipStreamQuery(m->comm_stream);
+        const hipError_t q = hipStreamQuery(m->comm_stream.get());
         if (q == hipSuccess && qc == hipSuccess) {
-            if (m->direct && __atomic_load_n(&m->shm->timed_out, __ATOMIC_ACQUIRE)) {
+            if (m->direct && __atomic_load_n(&m->rv.shm->timed_out, __ATOMIC_ACQUIRE)) {
                 m->broken = true;
                 return vct_fail(c, VCT_ERR_DEVICE, "vct_comm_sync: a rank's flag wait gave up after " + std::to_string(m->timeout_ms) +
                                                    " ms (a peer died or hangs); the frame is incomplete, communicator unusable");
@@ -711,19 +712,17 @@ int vct_comm_sync(vct_ctx* c) {
         }
         if (q != hipSuccess && q != hipErrorNotReady) HIP_TRY(c, q);
         ncclResult_t async = ncclSuccess;
-        if (m->comm && rccl()->CommGetAsyncError && rccl()->CommGetAsyncError(m->comm, &async) == ncclSuccess &&
+        if (m->comm.h && rccl()->CommGetAsyncError && rccl()->CommGetAsyncError(m->comm.h, &async) == ncclSuccess &&
             async != ncclSuccess && async != ncclInProgress)
             return comm_fail(c, m, "vct_comm_sync: asynchronous RCCL error", async);
-        const long long ms = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count();
-        if (ms > m->timeout_ms) {
-            if (m->comm && rccl()->CommAbort) { (void)rccl()->CommAbort(m->comm); m->comm = nullptr; }
-            m->broken = true;
-            return vct_fail(c, VCT_ERR_DEVICE, "vct_comm_sync: the gather did not complete within " + std::to_string(m->timeout_ms) +
-                                               " ms (a peer rank died or hangs); communicator aborted");
-        }
-        if (++spins < 2000) std::this_thread::yield();                         // the common case: done within microseconds
-        else std::this_thread::sleep_for(std::chrono::microseconds(200));
-    }
+        return pending;
+    };
+    int rc = pending;
+    if (wait_until([&] { return (rc = poll()) != pending; }, m->timeout_ms, true)) return rc;      // the common case: done within microseconds
+    m->comm.abort();
+    m->broken = true;
+    return vct_fail(c, VCT_ERR_DEVICE, "vct_comm_sync: the gather did not complete within " + std::to_string(m->timeout_ms) +
+                                       " ms (a peer rank died or hangs); communicator aborted");
 }
 
 // Diagnostics for multi-GPU bench lines: what RCCL itself says about the communicator.
@@ -732,15 +731,15 @@ int vct_comm_info(vct_ctx* c, int32_t out[4]) {
     if (!c || !out) return VCT_ERR_INVALID;
     vct_comm* m = c->comm;
     if (m && m->direct) {        // direct slabs: no RCCL; what the rendezvous block says, version 0
-        out[0] = (int32_t)m->shm->world; out[1] = m->rank; out[2] = c->device; out[3] = 0;
+        out[0] = (int32_t)m->rv.shm->world; out[1] = m->rank; out[2] = c->device; out[3] = 0;
         return VCT_OK;
     }
-    if (!m || !m->comm) return vct_fail(c, VCT_ERR_INVALID, "vct_comm_info: no usable communicator (vct_comm_init)");
+    if (!m || !m->comm.h) return vct_fail(c, VCT_ERR_INVALID, "vct_comm_info: no usable communicator (vct_comm_init)");
     Rccl* r = rccl();
     int v[4] = {-1, -1, -1, -1};
-    if (r->CommCount) (void)r->CommCount(m->comm, &v[0]);
-    if (r->CommUserRank) (void)r->CommUserRank(m->comm, &v[1]);
-    if (r->CommCuDevice) (void)r->CommCuDevice(m->comm, &v[2]);
+    if (r->CommCount) (void)r->CommCount(m->comm.h, &v[0]);
+    if (r->CommUserRank) (void)r->CommUserRank(m->comm.h, &v[1]);
+    if (r->CommCuDevice) (void)r->CommCuDevice(m->comm.h, &v[2]);
     if (r->GetVersion) (void)r->GetVersion(&v[3]);
     for (int i = 0; i < 4; ++i) out[i] = v[i];
     return VCT_OK;
@@ -752,9 +751,8 @@ int vct_comm_last_gather_ms(vct_ctx* c, float* ms) {
     if (!c || !ms) return VCT_ERR_INVALID;
     vct_comm* m = c->comm;
     if (!m || m->last < 0) return vct_fail(c, VCT_ERR_INVALID, "vct_comm_last_gather_ms: no frame stepped yet");
-    const int rc = vct_comm_sync(c);
-    if (rc) return rc;
-    HIP_TRY(c, hipEventElapsedTime(ms, m->g0[m->last], m->g1[m->last]));
+    PIPE_TRY(vct_comm_sync(c));
+    HIP_TRY(c, hipEventElapsedTime(ms, m->g0[m->last].get(), m->g1[m->last].get()));
     return VCT_OK;
 }
 
@@ -763,7 +761,7 @@ int vct_comm_frame(vct_ctx* c, void** dev, size_t* bytes) {
     vct_comm* m = c->comm;
     if (!m || m->last < 0) return vct_fail(c, VCT_ERR_INVALID, "vct_comm_frame: no frame gathered yet");
     if (m->rank != 0) return vct_fail(c, VCT_ERR_INVALID, "vct_comm_frame: only the root (rank 0) holds the frame");
-    *dev = m->interleaved ? m->il_frame[m->last] : m->buf[m->last];
+    *dev = m->interleaved ? m->il_frame[m->last].get() : m->buf[m->last].get();
     if (bytes) *bytes = (size_t)c->cfg.width * c->cfg.height * 8;
     return VCT_OK;
 }
@@ -797,13 +795,10 @@ int vct_selftest_interleaved(vct_ctx* c, int32_t world, uint64_t* mismatches) {
     hipError_t e = hipMemsetAsync(gathered.get(), 0, slab_pixels * world * 8, cur(c).stream.get());
     if (e == hipSuccess) e = hipMemsetAsync(plain.get(), 0, npix * 8, cur(c).stream.get());
     if (e != hipSuccess) return vct_fail(c, VCT_ERR_DEVICE, hipGetErrorString(e));
-    for (int r = 0; r < world; ++r) {
-        const int rc = vct_launch_trace_rows(c, r < ty ? r : ty, ty, (uint16_t*)(gathered.get() + slab_pixels * r), world, true);
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(k_deinterleave, dim3(2048), dim3(256), 0, cur(c).stream.get(), gathered.get(), il.get(), w, h, world, slab_pixels);
-    int rc = vct_launch_trace_rows(c, 0, ty, (uint16_t*)plain.get());
-    if (rc) return rc;
+    for (int r = 0; r < world; ++r)
+        PIPE_TRY(vct_launch_trace_rows(c, r < ty ? r : ty, ty, (uint16_t*)(gathered.get() + slab_pixels * r), world, true));
+    PIPE_TRY(launch_deinterleave(c, cur(c).stream.get(), gathered.get(), il.get(), world, slab_pixels));
+    PIPE_TRY(vct_launch_trace_rows(c, 0, ty, (uint16_t*)plain.get()));
     std::vector<uint2> a(npix), b(npix);
     e = hipStreamSynchronize(cur(c).stream.get());
     if (e == hipSuccess) e = hipMemcpy(a.data(), il.get(), npix * 8, hipMemcpyDeviceToHost);

@@ -273,10 +273,48 @@ struct BlockDesc {
 __device__ __forceinline__ BlockDesc no_block() { return {VCT_NO_BLOCK, {0, 0, 0}}; }
 
 // the trilinear fold of a lane's 8 texels out of a block in LDS; q = the lane's lower corner in the slab
+// NARROW: two texels in flight where there are four -- the same fold in the same order, eight registers fewer at the
+// kernel's widest point (the whole-frame march under the 64-register bound: k_trace_tile_split's MINW)
+template <bool NARROW = false>
 __device__ __forceinline__ F4 gather_block(const float4* q, float a, float b, float c) {
     F4 r;
     const float a0 = 1.0f - a, b0 = 1.0f - b, c0 = 1.0f - c;
     const float ab00 = a0 * b0, ab10 = a * b0, ab01 = a0 * b, ab11 = a * b;
+    if constexpr (NARROW) {
+        {
+            const float4 t0 = q[0], t1 = q[1];
+            const float w0 = ab00 * c0, w1 = ab10 * c0;
+#define VCT_ACC(ch) r.ch = w0 * t0.ch; r.ch = fmaf(w1, t1.ch, r.ch);
+            VCT_ACC(x) VCT_ACC(y) VCT_ACC(z) VCT_ACC(w)
+#undef VCT_ACC
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        {
+            const float4 t2 = q[4], t3 = q[5];
+            const float w2 = ab01 * c0, w3 = ab11 * c0;
+#define VCT_ACC(ch) r.ch = fmaf(w2, t2.ch, r.ch); r.ch = fmaf(w3, t3.ch, r.ch);
+            VCT_ACC(x) VCT_ACC(y) VCT_ACC(z) VCT_ACC(w)
+#undef VCT_ACC
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        {
+            const float4 t4 = q[16], t5 = q[17];
+            const float w4 = ab00 * c, w5 = ab10 * c;
+#define VCT_ACC(ch) r.ch = fmaf(w4, t4.ch, r.ch); r.ch = fmaf(w5, t5.ch, r.ch);
+            VCT_ACC(x) VCT_ACC(y) VCT_ACC(z) VCT_ACC(w)
+#undef VCT_ACC
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        {
+            const float4 t6 = q[20], t7 = q[21];
+            wave_sync();
+            const float w6 = ab01 * c, w7 = ab11 * c;
+#define VCT_ACC(ch) r.ch = fmaf(w6, t6.ch, r.ch); r.ch = fmaf(w7, t7.ch, r.ch);
+            VCT_ACC(x) VCT_ACC(y) VCT_ACC(z) VCT_ACC(w)
+#undef VCT_ACC
+        }
+        return r;
+    }
     {   // lower z plane first, then the upper one: half the texel registers live at a time
         const float4 t0 = q[0], t1 = q[1], t2 = q[4], t3 = q[5];
         const float w0 = ab00 * c0, w1 = ab10 * c0, w2 = ab01 * c0, w3 = ab11 * c0;
@@ -346,7 +384,7 @@ __device__ __forceinline__ void per_lane_census(MarchStats& ms, const Footprint&
 // Over the shared pieces above: the choice between the cooperative block (COOP, every live footprint inside the block
 // at the anchor) and the per-lane gather, the per-lane gather itself (texel loads in phases of 2 + 2 + 4, or one
 // footprint record with CELLS), and where the issue priority (PRIO) is raised and dropped.
-template <bool WRAP, bool COOP, bool LOOSE = false, bool CELLS = false, bool PRIO = false>
+template <bool WRAP, bool COOP, bool LOOSE = false, bool CELLS = false, bool PRIO = false, bool NARROW = false>
 __device__ __forceinline__ F4 sample_level(const uint32_t* __restrict__ chain, const VctLevelRef lv,
                                            float ux, float uy, float uz, bool act, unsigned long long am,
                                            float4* __restrict__ blk, const LaneBlock& lb, MarchStats& ms,
@@ -380,7 +418,7 @@ __device__ __forceinline__ F4 sample_level(const uint32_t* __restrict__ chain, c
         if (any_texel) {     // all 64 texels zero: every footprint sums to exactly +0
             blk[lb.lane] = d;
             wave_sync();
-            r = gather_block(blk + block_slot(act, fit.dx, fit.dy, fit.dz), a, b, c);
+            r = gather_block<NARROW>(blk + block_slot(act, fit.dx, fit.dy, fit.dz), a, b, c);
         }
     } else {
       if (VCT_STATS) per_lane_census(ms, f, act, am, lb.lane);
@@ -435,7 +473,24 @@ __device__ __forceinline__ F4 sample_level(const uint32_t* __restrict__ chain, c
 #undef VCT_ACC
             }
             __builtin_amdgcn_sched_barrier(0);
-            {
+            if constexpr (NARROW) {       // phases of 2 + 2 + 2 + 2
+                {
+                    const float4 f4 = texel_f32(tb, mx0 | my0 | mz1), f5 = texel_f32(tb, mx1 | my0 | mz1);
+                    const float w4 = ab00 * c, w5 = ab10 * c;
+#define VCT_ACC(ch) r.ch = fmaf(w4, f4.ch, r.ch); r.ch = fmaf(w5, f5.ch, r.ch);
+                    VCT_ACC(x) VCT_ACC(y) VCT_ACC(z) VCT_ACC(w)
+#undef VCT_ACC
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                {
+                    const float4 f6 = texel_f32(tb, mx0 | my1 | mz1), f7 = texel_f32(tb, mx1 | my1 | mz1);
+                    if (PRIO) __builtin_amdgcn_s_setprio(0);
+                    const float w6 = ab01 * c, w7 = ab11 * c;
+#define VCT_ACC(ch) r.ch = fmaf(w6, f6.ch, r.ch); r.ch = fmaf(w7, f7.ch, r.ch);
+                    VCT_ACC(x) VCT_ACC(y) VCT_ACC(z) VCT_ACC(w)
+#undef VCT_ACC
+                }
+            } else {
                 const float4 f4 = texel_f32(tb, mx0 | my0 | mz1), f5 = texel_f32(tb, mx1 | my0 | mz1);
                 const float4 f6 = texel_f32(tb, mx0 | my1 | mz1), f7 = texel_f32(tb, mx1 | my1 | mz1);
                 if (PRIO) __builtin_amdgcn_s_setprio(0);
@@ -492,7 +547,7 @@ __device__ __forceinline__ F4 sample_level(const uint32_t* __restrict__ chain, c
 // `held` describes the block in the second one.
 // Over the shared pieces: the fit test runs against the held block first and against a fresh anchor only when that
 // fails, and a fresh block of the second slab becomes the held one.
-template <bool WRAP, bool LOOSE, bool PRIO, int SLAB>
+template <bool WRAP, bool LOOSE, bool PRIO, int SLAB, bool NARROW = false>
 __device__ __forceinline__ F4 sample_level_reuse(const uint32_t* __restrict__ chain, const VctLevelRef lv,
                                                  float ux, float uy, float uz, bool act, unsigned long long am,
                                                  float4* __restrict__ blk, const LaneBlock& lb, MarchStats& ms,
@@ -540,22 +595,22 @@ __device__ __forceinline__ F4 sample_level_reuse(const uint32_t* __restrict__ ch
             }
         }
     }
-    if (mode == 2) return gather_block(blk + at, f.a, f.b, f.c);
+    if (mode == 2) return gather_block<NARROW>(blk + at, f.a, f.b, f.c);
     if (mode == 1) return {0.0f, 0.0f, 0.0f, 0.0f};     // all 64 texels zero: every footprint sums to exactly +0
     // incoherent footprints: the per-lane gather, which leaves the slabs and the descriptor alone
-    return sample_level<WRAP, false, LOOSE, false, PRIO>(chain, lv, ux, uy, uz, act, am, blk, lb, ms);
+    return sample_level<WRAP, false, LOOSE, false, PRIO, NARROW>(chain, lv, ux, uy, uz, act, am, blk, lb, ms);
 }
 
 // level SLAB (0: first, 1: second) of a march step, with or without block reuse; `blk` is the wave's first slab
-template <bool WRAP, bool COOP, bool LOOSE, bool CELLS, bool PRIO, bool REUSE, int SLAB>
+template <bool WRAP, bool COOP, bool LOOSE, bool CELLS, bool PRIO, bool REUSE, int SLAB, bool NARROW = false>
 __device__ __forceinline__ F4 sample_step_level(const VctTraceParams& p, const VctLevelRef lv, float ux, float uy, float uz,
                                                 bool act, unsigned long long am, float4* __restrict__ blk,
                                                 const LaneBlock& lb, MarchStats& ms, BlockDesc& held) {
     if constexpr (REUSE) {
         static_assert(WRAP && COOP && !CELLS, "block reuse: cooperative sampler, GL_REPEAT, no footprint records");
-        return sample_level_reuse<WRAP, LOOSE, PRIO, SLAB>(p.chain, lv, ux, uy, uz, act, am, blk, lb, ms, held);
+        return sample_level_reuse<WRAP, LOOSE, PRIO, SLAB, NARROW>(p.chain, lv, ux, uy, uz, act, am, blk, lb, ms, held);
     } else {
-        return sample_level<WRAP, COOP, LOOSE, CELLS, PRIO>(p.chain, lv, ux, uy, uz, act, am, blk + SLAB * 64, lb, ms, p.cells_biased);
+        return sample_level<WRAP, COOP, LOOSE, CELLS, PRIO, NARROW>(p.chain, lv, ux, uy, uz, act, am, blk + SLAB * 64, lb, ms, p.cells_biased);
     }
 }
 
@@ -674,10 +729,10 @@ __device__ __forceinline__ VctStep load_step(StepTable t, int k) {
         const float uy = fmaf(div_const<FASTDIV>(py, p.half_G_aux, p.half_G_rcp), 0.5f, 0.5f); \
         const float uz = fmaf(div_const<FASTDIV>(pz, p.half_G_aux, p.half_G_rcp), 0.5f, 0.5f); \
         F4 vc = (ANISO && st.level >= 1) ? sample_aniso<WRAP, COOP>(p, st.l1, ux, uy, uz, act, live, blk, lb, ac, ms) \
-                                         : sample_step_level<WRAP, COOP, FASTDIV == 2, CELLS, PRIO, REUSE, 0>(p, st.l1, ux, uy, uz, act, live, blk, lb, ms, held); \
+                                         : sample_step_level<WRAP, COOP, FASTDIV == 2, CELLS, PRIO, REUSE, 0, NARROW>(p, st.l1, ux, uy, uz, act, live, blk, lb, ms, held); \
         if (st.two_levels) { \
             const F4 t2 = ANISO ? sample_aniso<WRAP, COOP>(p, st.l2, ux, uy, uz, act, live, blk + 64, lb, ac, ms) \
-                                : sample_step_level<WRAP, COOP, FASTDIV == 2, CELLS, PRIO, REUSE, 1>(p, st.l2, ux, uy, uz, act, live, blk, lb, ms, held); \
+                                : sample_step_level<WRAP, COOP, FASTDIV == 2, CELLS, PRIO, REUSE, 1, NARROW>(p, st.l2, ux, uy, uz, act, live, blk, lb, ms, held); \
             const float g = st.omf;      /* 1 - frac, from the table */ \
             vc.x = fmaf(st.frac, t2.x, g * vc.x); \
             vc.y = fmaf(st.frac, t2.y, g * vc.y); \
@@ -737,7 +792,7 @@ __device__ __forceinline__ void sky_epilogue(const VctTraceParams& p, bool alive
 #define VCT_SKY_NONE 0
 #define VCT_SKY_INSIDE 1
 #define VCT_SKY_ALPHA 2
-template <bool WRAP, int FASTDIV, bool COOP, bool ANISO, bool CELLS, bool PRIO, bool REUSE, int SKY = VCT_SKY_NONE>
+template <bool WRAP, int FASTDIV, bool COOP, bool ANISO, bool CELLS, bool PRIO, bool REUSE, int SKY = VCT_SKY_NONE, bool NARROW = false>
 __device__ __forceinline__ F4 cone_march(const VctTraceParams& p, bool alive, F3 start, F3 dir,
                                          const VctStep* tab_global, int n,
                                          float4* __restrict__ blk, const LaneBlock& lb,
@@ -1111,9 +1166,10 @@ k_trace_tile(const VctTraceParams p) {
 // for about half of that with ever fewer waves resident (measured: +55..66 us per launch, 7 % of a
 // 1080p frame but 37 % of the 0.15 ms slab an 8-GPU rank traces).  Here a tile is a workgroup of 3
 // waves -- diffuse cones 0-2, diffuse cones 3-5, the specular cone (21 / 21 / 29 steps) -- that
-// leave their raw cone vec4s in LDS and exit; the last one to arrive gathers them in the oracle's
-// order (the weighted sum is an fma chain over cones 0..5) and composites.  Same bits, waves one
-// third as long, no wave ever waits on another.
+// leave their cones in LDS and exit (the first wave the fold of its own, the prefix of the chain;
+// "Cone hand-over" in the kernel); the last one to arrive continues the fold in the oracle's order
+// (the weighted sum is an fma chain over cones 0..5) and composites.  Same bits, waves one third as
+// long, no wave ever waits on another.
 #ifndef VCT_SPLIT
 #define VCT_SPLIT 3               // waves per tile: 3 = {cones 0-2, cones 3-5, specular}, 4 = {0-1, 2-3, 4-5, specular}, 7 = one cone each
 #endif
@@ -1142,6 +1198,25 @@ static_assert(VCT_SPLIT == 3 || VCT_SPLIT == 4 || VCT_SPLIT == 7, "VCT_SPLIT mus
 // SKY: sky light (include/vct.h "sky light"; p.sky): every marched cone adds what its open remainder gathers from the
 // sky -- cone_march<.., VCT_SKY_INSIDE>, or, with GLOSS, one sky_epilogue per lane behind the class loop.  Instantiated
 // with COMP, for the plain, PRIO and HALF forms, each with and without GLOSS.
+// Waves per SIMD of an instantiation (its launch bound): 8, with the two-texel gathers (NARROW), for the whole-frame
+// forms (PRIO) under GL_REPEAT, which fit 64 registers without scratch -- and for the footprint-record forms (CELLS), which
+// ran 8 waves in 64 registers under the bound of 7 until the hand-over took a 65th.  Everything else keeps the bound of 7
+// and the four-texel gathers: clamp mode (66-72 registers), the HALF forms (56-64 registers: 8 waves without being asked),
+// the compaction experiment, and the forms without PRIO -- launches of at most half the frame, the slabs of a multi-GPU
+// frame: an eighth of a frame is 16 tiles per CU, too few for residency to bind, and the 8-wave form's 1.6 % more
+// vector instructions made those launches 0.2 - 1.5 % slower.  Both forms give the same bits.
+// (A cap on the vector registers alone -- amdgpu_num_vgpr(64) under the bound of 7, which keeps six more scalar
+// registers and 30 scalars out of the spill lanes -- does not get the eighth wave: +2.9 % against the parent where the
+// bound of 8 measures -2 %.)  -DVCT_SPLIT_MAX_WAVES=7 builds every form with the bound of 7: kept for A/B builds
+// (tools/build_ab.sh), like VCT_REUSE.  Resource lines: profiles/experiments/r16_occupancy_kernels.txt.
+#ifndef VCT_SPLIT_MAX_WAVES
+#define VCT_SPLIT_MAX_WAVES 8
+#endif
+constexpr int split_min_waves(bool wrap, bool aniso, bool compact, bool cells, bool prio, bool half, bool gloss) {
+    if (aniso) return VCT_ANISO_MIN_WAVES;
+    const bool fits = wrap && !compact && !half && (cells || prio);
+    return fits && VCT_SPLIT_MAX_WAVES >= 8 ? 8 : VCT_TRACE_MIN_WAVES;
+}
 typedef const __attribute__((address_space(4))) VctGlossTable* GlossTable;
 // the lane's class: its byte of the tile's plane under the clamp rule -- never an index before the clamp
 __device__ __forceinline__ int gloss_class_of(const VctTraceParams& p, int tile, int pix, int nclasses) {
@@ -1150,12 +1225,35 @@ __device__ __forceinline__ int gloss_class_of(const VctTraceParams& p, int tile,
 }
 template <bool WRAP, int FASTDIV, bool ANISO, bool COMPACT = false, bool CELLS = false, bool PRIO = false, bool COMP = false,
           bool HALF = false, bool GLOSS = false, bool SKY = false>
-__global__ void __launch_bounds__(64 * VCT_SPLIT, ANISO ? VCT_ANISO_MIN_WAVES : VCT_TRACE_MIN_WAVES)
+__global__ void __launch_bounds__(64 * VCT_SPLIT, split_min_waves(WRAP, ANISO, COMPACT, CELLS, PRIO, HALF, GLOSS))
 k_trace_tile_split(const VctTraceParams p) {
+    constexpr bool NARROW = !ANISO && split_min_waves(WRAP, ANISO, COMPACT, CELLS, PRIO, HALF, GLOSS) >= 8;
     static_assert(!GLOSS || (COMP && !ANISO && !COMPACT && !CELLS), "gloss classes: the default kernel's COMP forms only");
     static_assert(!SKY || (COMP && !ANISO && !COMPACT && !CELLS), "sky light: the default kernel's COMP forms only");
     __shared__ float4 lds_blk[VCT_SPLIT][ANISO ? 4 : 2][64];   // per wave: level-1 slab, level-2 slab (+ their "-axis" slabs)
-    __shared__ float4 lds_cone[7][64];
+    // Cone hand-over.  The workgroup's LDS stays allocated until its last wave ends while the waves that ended free their
+    // slots and registers, so what a tile declares caps how many tiles fill a CU's wave slots: the cones travel in the
+    // slabs, which a wave's marches have finished with, and only a diffuse wave's earlier cones need room of their own.
+    //   first diffuse wave   folds its own cones from +0 -- the prefix of the oracle's chain over cones 0..5, operation
+    //                        for operation -- and leaves that one float4 in its first slab; between its marches the
+    //                        running fold waits in lds_pre (x, y, z) and in the one register a diffuse wave carries
+    //                        across its marches (w; the wave's step count, which has that register in the other waves,
+    //                        waits in lds_steps): registers held across the marches put the kernel into scratch, and a
+    //                        fourth plane of floats puts the tile over 9 KiB
+    //   other diffuse waves  cannot fold without the prefix: raw cones, all but the last in lds_raw, the last in the
+    //                        first slab
+    //   specular wave        its cone in its second slab, E in its first; with GLOSS it marches once per class, and a
+    //                        lane's cone waits in lds_gloss from its own march on (four registers held across the class
+    //                        loop cost the HALF forms their eighth wave and put the clamp-mode ones into scratch): the
+    //                        last arriver reads it there
+    // Every slab is written behind the wave's last march: between two marches nothing writes one (`held` describes the
+    // second slab, and the first is refilled by every sample that reads it).
+    constexpr int RAW_WAVES = VCT_SPLIT - 2, RAW_CONES = VCT_CONES_PER_WAVE - 1;
+    __shared__ float4 lds_raw[RAW_WAVES * RAW_CONES > 0 ? RAW_WAVES * RAW_CONES : 1][64];
+    __shared__ float lds_pre[3][64];
+    __shared__ uint16_t lds_steps[64];
+    __shared__ float4 lds_gloss[GLOSS ? 64 : 1];       // (referenced by the GLOSS forms only: the others declare none of it)
+    static_assert(VCT_CONES_PER_WAVE * VCT_MAX_STEPS < (1 << 16), "a lane's steps over the cones of a wave fit lds_steps");
     // Arrival word: bits 28-31 count the waves that have arrived, bits 0-27 sum their executed steps -- one returning
     // atomic per wave raises both, and the last arriver stores the total.  A tile executes at most 64 lanes x (6 diffuse
     // cones + 8 gloss classes) x VCT_MAX_STEPS steps, and VCT_SPLIT arrivals fit four bits:
@@ -1227,15 +1325,42 @@ k_trace_tile_split(const VctTraceParams p) {
     } else if (wave < VCT_SPLIT - 1) {
         F3 start, k0, k1, k2;
         cone_frame_from_gbuffer(gb, p.vs, start, k0, k1, k2);
+        // (a wave that marches nothing folds or hands over zero cones: a zero prefix stays +0 through the fmas)
+        // `carried` is the one register a diffuse wave holds across its marches.  In the first wave it is the BITS of the
+        // prefix's w until the last cone is folded (the lane's step count waits in lds_steps), in the other waves the
+        // lane's step count; behind the loop it is the lane's step count in every wave, and only then goes into `total`.
+        int carried = 0;
+        const int first = wave * VCT_CONES_PER_WAVE;
+        // (LDS addresses from a fresh copy of the lane id: hoisted out of the loop they live across the marches)
+        auto own_lane = [&]() { int l = lane; asm volatile("" : "+v"(l)); return l; };
 #pragma unroll 1
-        for (int i = wave * VCT_CONES_PER_WAVE; i < wave * VCT_CONES_PER_WAVE + VCT_CONES_PER_WAVE; ++i) {      // :196-199
+        for (int i = first; i < first + VCT_CONES_PER_WAVE; ++i) {      // :196-199
             int st;
-            const F4 c = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO, REUSE, SKY ? VCT_SKY_INSIDE : VCT_SKY_NONE>(p, march_d, start, cone_dir(k0, k1, k2, i),
+            const F4 c = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO, REUSE, SKY ? VCT_SKY_INSIDE : VCT_SKY_NONE, NARROW>(p, march_d, start, cone_dir(k0, k1, k2, i),
                                                                        p.steps_diffuse, n_diffuse, blk, lb, st, ms, held);
-            total += st;
-            lds_cone[i][lane] = make_float4(c.x, c.y, c.z, c.w);
+            const bool last = i - first == RAW_CONES;      // behind the wave's last march: into its first slab
+            const int l = own_lane();
+            F4 out = c;
+            if (wave == 0) {
+                F4 pre = {0.0f, 0.0f, 0.0f, 0.0f};
+                int sum = st;
+                if (i != 0) {
+                    pre = {lds_pre[0][l], lds_pre[1][l], lds_pre[2][l], __int_as_float(carried)};
+                    sum += (int)lds_steps[l];
+                }
+                out = fold_cone(pre, i, c);
+                if (!last) {
+                    lds_pre[0][l] = out.x; lds_pre[1][l] = out.y; lds_pre[2][l] = out.z; carried = __float_as_int(out.w);
+                    lds_steps[l] = (uint16_t)sum;
+                } else carried = sum;
+            } else {
+                carried += st;
+                if (!last) lds_raw[(wave - 1) * RAW_CONES + (i - first)][l] = make_float4(c.x, c.y, c.z, c.w);
+            }
+            if (last) blk[l] = make_float4(out.x, out.y, out.z, out.w);
             store_debug_cone(p, pixel_index, i, c, st, alive, in_frame);
         }
+        total = carried;
     } else {
         // the specular wave is the longest of a tile (29 march steps against 21) and the last ones of a launch are its
         // tail: raised issue priority lets them run ahead of the diffuse waves, which have the slack.  Pays when the
@@ -1245,22 +1370,27 @@ k_trace_tile_split(const VctTraceParams p) {
         if (!PRIO && p.spec_prio) __builtin_amdgcn_s_setprio(1);
         const F3 P = gb_planes3(gb, 0), Nw = gb_planes3(gb, 3), N = gb_planes3(gb, 12);
         const F3 start = cone_start(P, Nw, p.vs);
-        // E is the composite's too: this wave hands it over in its own first slab -- no LDS of its own -- once its marches
-        // are over and nothing reads its slabs again, in every form of this arm, also the 0-step ones of COMP and HALF
+        // E is the composite's too: this wave hands it over in its own first slab and its cone in its second -- no LDS of
+        // their own -- once its marches are over and nothing reads its slabs again, in every form of this arm, also the
+        // 0-step ones of COMP and HALF (GLOSS: the cone is in lds_gloss already)
         const F3 E = eye_dir(P, p.cam);
-        auto hand_over = [&](F3 e) { blk[lane] = make_float4(e.x, e.y, e.z, 0.0f); };
+        auto hand_over_e = [&](F3 e) { blk[lane] = make_float4(e.x, e.y, e.z, 0.0f); };
+        auto hand_over = [&](F4 cone, F3 e) {
+            blk[64 + lane] = make_float4(cone.x, cone.y, cone.z, cone.w);
+            hand_over_e(e);
+        };
         if constexpr (GLOSS) {
             // One march per class present among the live lanes: the class of the first remaining lane, wave-uniform, picks
             // the table and its step count by scalar loads; the lanes of that class march, write their cone and leave the
             // mask.  A lane marches exactly once, so nothing depends on the order of the classes.  `held` stays live across
             // the marches: it describes a block by (level, anchor) alone, every sample tests its own footprints against it,
             // and between two marches nothing writes the wave's slabs (the first slab is refilled by every sample that
-            // reads it, the second only together with the descriptor).
+            // reads it, the second only together with the descriptor) -- so the lane's cone waits in lds_gloss.
             const GlossTable gt = (GlossTable)p.gloss;
             const int cls = gloss_class_of(p, tile, plane_, gt->nclasses);
             const F3 dir = specular_dir(E, N);
             if (!alive) {     // what a lane that marches nothing gets from the one march of the other forms
-                lds_cone[6][lane] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                lds_gloss[lane] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                 if (p.dbg_steps && in_frame) p.dbg_steps[pixel_index() * 7 + 6] = 0;
             }
             [[maybe_unused]] float sky_alpha = 0.0f;       // SKY: what the lane's own march saw last
@@ -1269,10 +1399,10 @@ k_trace_tile_split(const VctTraceParams p) {
                 const bool mine = alive && cls == k;
                 int st;
                 float a = 0.0f;
-                const F4 sc = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO, REUSE, SKY ? VCT_SKY_ALPHA : VCT_SKY_NONE>(
+                const F4 sc = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO, REUSE, SKY ? VCT_SKY_ALPHA : VCT_SKY_NONE, NARROW>(
                     p, mine && march_s, start, dir, &p.gloss->steps[k][0], (groups & 2u) ? gt->nsteps[k] : 0, blk, lb, st, ms, held, &a);
                 total += st;          // (0 for the lanes that did not march)
-                if (mine) lds_cone[6][lane] = make_float4(sc.x, sc.y, sc.z, sc.w);
+                if (mine) lds_gloss[lane] = make_float4(sc.x, sc.y, sc.z, sc.w);
                 if (SKY && mine) sky_alpha = a;
                 store_debug_cone(p, pixel_index, 6, sc, st, mine && !SKY, mine);      // (SKY: the cone is stored below)
                 rest &= ~ballot64(mine);
@@ -1281,30 +1411,29 @@ k_trace_tile_split(const VctTraceParams p) {
                 // the sky once per lane, behind the class loop, from the alpha its own march handed out: inside the march
                 // (as in every other form) the epilogue costs the clamp-mode GLOSS kernels 4 VGPRs -- the 8th wave of the
                 // HALF form -- and the PRIO one 8 B of scratch.  Same chain, same operands, same bits.
-                const float4 v = lds_cone[6][lane];
+                const float4 v = lds_gloss[lane];
                 F4 sc = {v.x, v.y, v.z, v.w};
                 sky_epilogue(p, march_s, dir, sky_alpha, sc.x, sc.y, sc.z);
-                lds_cone[6][lane] = make_float4(sc.x, sc.y, sc.z, sc.w);
+                lds_gloss[lane] = make_float4(sc.x, sc.y, sc.z, sc.w);
                 store_debug_cone(p, pixel_index, 6, sc, 0, alive, false);
             }
             // (E again from planes 0-2, L1 re-reads: live across the class loop it costs the clamp-mode GLOSS kernels 3 VGPRs
             // -- the 8th wave of the HALF forms, 16 B of scratch in the PRIO ones)
-            hand_over(eye_dir(gb_planes3(gbuf_ptr(fresh_lane()), 0), p.cam));
+            hand_over_e(eye_dir(gb_planes3(gbuf_ptr(fresh_lane()), 0), p.cam));
         } else {
         int st6;
-        const F4 sc = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO, REUSE, SKY ? VCT_SKY_INSIDE : VCT_SKY_NONE>(p, march_s, start, specular_dir(E, N),
+        const F4 sc = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO, REUSE, SKY ? VCT_SKY_INSIDE : VCT_SKY_NONE, NARROW>(p, march_s, start, specular_dir(E, N),
                                                                     p.steps_specular, n_specular, blk, lb, st6, ms, held);
         total += st6;
-        lds_cone[6][lane] = make_float4(sc.x, sc.y, sc.z, sc.w);
         store_debug_cone(p, pixel_index, 6, sc, st6, alive, in_frame);
-        hand_over(E);
+        hand_over(sc, E);
         }
     }
     total = wave_sum(total);
     flush_stats(p, ms, lane, wave == VCT_SPLIT - 1);
 
-    // arrival: LDS operations of a wave are performed in order, so the cone values (and E) are in LDS before the
-    // word is raised; whoever raises its count to VCT_SPLIT sees all of them
+    // arrival: LDS operations of a wave are performed in order, so what the wave hands over is in LDS before the
+    // word is raised; whoever raises its count to VCT_SPLIT sees all of it
     __threadfence_block();
     uint32_t before = 0u;
     if (lane == 0) before = atomicAdd(&lds_arrive, (uint32_t)total + (1u << 28));
@@ -1314,7 +1443,7 @@ k_trace_tile_split(const VctTraceParams p) {
     // one plain store per tile: no global atomic, nothing to clear
     if (lane == 0) p.tile_steps[tile0] = (before + (uint32_t)total) & 0x0fffffffu;
 
-    // the last wave gathers the diffuse cones in the oracle's order and composites
+    // the last wave continues the first wave's prefix over the other diffuse cones in the oracle's order and composites
     const float* gb3 = gbuf_ptr(fresh_lane());
     if (in_frame) {
         F4 ind = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -1322,8 +1451,13 @@ k_trace_tile_split(const VctTraceParams p) {
             const float4 v = p.dr_ind[pixel_index()];
             ind = {v.x, v.y, v.z, v.w};
         } else {
+            const float4 pre = lds_blk[0][0][lane];
+            ind = {pre.x, pre.y, pre.z, pre.w};
 #pragma unroll
-            for (int i = 0; i < 6; ++i) ind = fold_cone(ind, i, lds_cone[i][lane]);
+            for (int i = VCT_CONES_PER_WAVE; i < 6; ++i) {
+                const int w = i / VCT_CONES_PER_WAVE, j = i % VCT_CONES_PER_WAVE;
+                ind = fold_cone(ind, i, j < RAW_CONES ? lds_raw[(w - 1) * RAW_CONES + j][lane] : lds_blk[w][0][lane]);
+            }
         }
         float shininess = p.shininess;
         if constexpr (GLOSS) {
@@ -1331,7 +1465,9 @@ k_trace_tile_split(const VctTraceParams p) {
             shininess = p.gloss->shininess[gloss_class_of(p, tile, fresh_lane(), gt->nclasses)];
         }
         const float4 e = lds_blk[VCT_SPLIT - 1][0][lane];
-        composite<COMP>(p, gb3, ind, lds_cone[6][lane], f3(e.x, e.y, e.z), alive, pixel_index,
+        float4 sc;
+        if constexpr (GLOSS) sc = lds_gloss[lane]; else sc = lds_blk[VCT_SPLIT - 1][1][lane];
+        composite<COMP>(p, gb3, ind, sc, f3(e.x, e.y, e.z), alive, pixel_index,
                         [&]() { return (size_t)tile * (VCT_EMIS_NPLANES * VCT_TILE_PIX) + fresh_lane(); }, shininess);
     }
 }

@@ -1,0 +1,652 @@
+"""Two frame slots and the calls that came after tests/test_gpu_pipeline.py was written: the state setters (lights, sky, gloss
+classes and the material gloss map, emission, diffuse rate, lighting components, per-component outputs, footprint records,
+the bounce), the per-slot planes and hand-overs (pixel emission, pixel gloss, the G-buffer import, a host-located vct_trace)
+and the read-backs (G-buffer, planes, outputs, chain, point queries, voxel view).
+
+The method is that file's test_random_call_orders_give_what_a_synchronised_context_gives: the call list is built first, from
+a seeded generator that carries a model of what is attached and what each slot holds (so that it issues only calls
+include/vct.h allows, and reads only memory some call has written), then run twice -- as it stands, and with
+vct_synchronize after every call -- and every read-back must be the same bytes.  Its sizes too: the atrium at 128^3,
+1920 x 1080, because a 1080p trace is still running when the host issues the next call; at the frames of the feature files
+the GPU is idle by then and no ordering can show.  Read-backs are held as BLAKE2b digests of their bytes (a 1080p G-buffer
+is 190 MB), formed 16 MiB at a time on worker threads so that the host's next call is not held up behind them.
+
+What the library's waits are worth, from scratch builds that lack exactly one wait each (never committed); this file alone
+was run on each:
+  * vct_set_pixel_emission without its vct_staging_free, and a build with none of the waits that vct_trace's host-linear
+    hand-over, vct_download_gbuffer and the chain downloads now take: every test here passes.  Every user of c->gb_linear
+    and of c->vol.staging waits for its own stream before it returns, so none of the other slot's work on a staging buffer
+    is ever in flight when a call begins.  Those waits are a guarantee, not an observable.
+  * vct_inject_light without its vct_pipeline_join, lights attached: test_level_0_rewritten_while_the_other_slot_traces
+    fails (the random orders and the staging orders pass: vct_voxelize in front of it, on the same selection, has joined
+    already -- the join shows only where the inject is the selection's first producer, which that test arranges).
+  * vct_refresh_steps (behind vct_set_cone_apertures) without its vct_pipeline_drain, gloss classes attached:
+    test_step_tables_rewritten_while_the_other_slot_traces fails.  (test_gpu_pipeline.py found this drain unobservable with
+    the two tables of a context without classes; the class tables make the upload long enough to land in a running trace.)
+"""
+import hashlib
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import pytest
+
+import components_ref as cr
+import gloss_ref as gr
+import lights_ref as lr
+import sky_ref as sr
+import vctpkg
+from test_gpu_pipeline import cameras, lights as light_dirs, make
+
+pytestmark = pytest.mark.gpu
+
+W, H, V = 1920, 1080, 128
+CAMS, LIGHT_DIRS, ROUNDS = 3, 4, 4
+APERTURES = [(0.577, 0.07), (0.577, 0.2), (0.45, 0.105)]
+MASKS = [cr.SHOW_ALL, cr.SHOW_ALL & ~cr.SHOW_DIFFUSE, cr.SHOW_DIFFUSE | cr.SHOW_INDIRECT_SPECULAR,
+         cr.SHOW_INDIRECT_DIFFUSE | cr.SHOW_AMBIENT_OCCLUSION, cr.SHOW_DIFFUSE | cr.SHOW_SPECULAR]
+ALL_AOV = cr.AOV_INDIRECT_DIFFUSE | cr.AOV_INDIRECT_SPECULAR | cr.AOV_DIRECT
+# what the setters switch between: index 0 detaches
+LIGHT_SETS = [None,
+              [lr.point((-40.0, -5.0, 0.0), (400.0, 300.0, 200.0), 60.0, 2.0),
+               lr.spot((-20.0, 10.0, 5.0), (900.0, 900.0, 500.0), 80.0, 1.5, (-1.0, -0.5, -0.3), 0.9, 0.3)],
+              lr.LIGHTS]
+SKIES = [None, sr.SH, np.ascontiguousarray(sr.SH[:, ::-1] * np.float32(0.5))]
+GLOSS_TABLES = [None, list(gr.CLASSES[:3]), list(gr.CLASSES[1:3])]
+NPOINTS = 64 * 40 + 37
+SEEDS = [1, 2, 3, 4, 5, 6]
+
+
+@pytest.fixture(scope="module")
+def vct():
+    import torch
+    assert torch.cuda.is_available()
+    return vctpkg.load()
+
+
+# ---- the call list ------------------------------------------------------------------------------------------------------
+class CallList:
+    """The calls of one run and the state they leave, as far as legality and defined read-backs need it."""
+
+    def __init__(self, rng):
+        self.rng, self.ops, self.slot = rng, [], 0
+        self.lights = self.sky = self.gloss = 0              # index into LIGHT_SETS / SKIES / GLOSS_TABLES
+        self.matgloss = self.emission = self.bounced = False
+        self.pending = False                # a voxelize pass waits for its inject_light
+        self.rate = 1
+        self.aov = 0
+        self.deck = []
+        self.gb = [False, False]            # the slot has a resident G-buffer
+        self.frame = [False, False]         # some launch has written the slot's whole frame
+        self.marched = [False, False]       # vct_last_step_count has something to report
+        self.emis_user = [False, False]     # the caller's pixel-emission planes
+        self.lit = [False, False]           # a composite launch with lights attached has filled the lit planes
+
+    def pick(self, n):
+        return int(self.rng.integers(n))
+
+    def chance(self, p):
+        return bool(self.rng.random() < p)
+
+    def add(self, *op):
+        self.ops.append(op)
+
+    # -- producers and frames (the eight calls of test_gpu_pipeline.py)
+    def switch(self, slot):
+        self.add("switch", slot)
+        self.slot = slot
+
+    def produce(self):
+        self.add("produce", self.pick(LIGHT_DIRS))
+        self.bounced = self.pending = False
+
+    def revoxelize(self):
+        self.add("revoxelize")
+        self.bounced = self.pending = False
+
+    def voxelize(self):
+        """The first half of a moved light on this selection; inject() on a later one is then the selection's first producer,
+        and its join the only thing between the resolve and the other slot's trace."""
+        self.add("voxelize", self.pick(LIGHT_DIRS))
+        self.pending = True
+
+    def inject(self):
+        self.add("inject")
+        self.bounced = self.pending = False
+
+    def launched(self):
+        s = self.slot
+        self.gb[s] = self.frame[s] = self.marched[s] = True
+        if self.lights:
+            self.lit[s] = True
+
+    def gi(self):
+        self.add("gi", self.pick(LIGHT_DIRS), self.pick(CAMS))
+        self.bounced = self.pending = False
+        self.launched()
+
+    def gbuffer(self):
+        self.add("gbuffer", self.pick(CAMS))
+        self.gb[self.slot] = True
+
+    def trace(self):
+        assert self.gb[self.slot]
+        self.add("trace")
+        self.launched()
+
+    def remesh(self):
+        self.add("remesh", self.pick(2))
+        self.matgloss = self.emission = False        # a new mesh detaches both material tables
+        self.produce()
+
+    # -- hand-overs of a G-buffer other than the raster pass
+    def trace_host(self):
+        self.add("trace_host", self.pick(2))         # a read-back as well: vct_trace returns the frame
+        self.launched()
+
+    def import_gbuffer(self):
+        self.add("import", self.pick(2), self.chance(0.5), self.chance(0.5))       # camera, device inputs, shadow + material ids
+        self.gb[self.slot] = True
+
+    def some_gbuffer(self):
+        r = self.rng.random()
+        if r < 0.5:
+            self.gbuffer()
+        elif r < 0.8:
+            self.import_gbuffer()
+        else:
+            self.trace_host()
+            return
+        self.trace()
+
+    # -- shared state, rewritten while the other slot's trace is in flight
+    def setter(self, r=None):
+        """One kind of shared state rewritten; the kinds come off a shuffled deck, so that a run of a few rounds sees many."""
+        if r is None:
+            if not self.deck:
+                self.deck = [int(x) for x in self.rng.permutation(12)]
+            r = self.deck.pop()
+        if r == 0:
+            self.lights = (self.lights + 1 + self.pick(2)) % 3
+            self.add("lights", self.lights)
+            if not self.lights:
+                self.lit = [False, False]
+            if self.chance(0.5):
+                self.revoxelize()
+            else:
+                self.gi()
+        elif r == 1:
+            self.sky = (self.sky + 1 + self.pick(2)) % 3
+            self.add("sky", self.sky)
+        elif r == 2:
+            self.gloss = (self.gloss + 1 + self.pick(2)) % 3
+            self.add("gloss", self.gloss)
+        elif r == 3:
+            self.matgloss = not self.matgloss
+            self.add("matgloss", self.matgloss)
+        elif r == 4:
+            self.emission = not self.emission
+            self.add("emission", self.emission)
+            self.revoxelize()
+        elif r == 5:
+            self.rate = 3 - self.rate
+            self.add("rate", self.rate)
+        elif r == 6:
+            self.add("components", MASKS[self.pick(len(MASKS))])
+        elif r == 7:
+            sets = [0, ALL_AOV, cr.AOV_INDIRECT_SPECULAR, cr.AOV_DIRECT | cr.AOV_INDIRECT_DIFFUSE]
+            self.aov = sets[(sets.index(self.aov) + 1 + self.pick(3)) % 4]
+            self.add("aov", self.aov)
+        elif r == 8:
+            self.add("apertures", self.pick(len(APERTURES)))
+        elif r == 9:
+            if self.pending:
+                self.inject()              # a bounce is refused between voxelize and inject_light
+            self.add("bounce")
+            self.bounced = True
+            self.marched[self.slot] = True
+            if self.chance(0.5):
+                self.add("read_steps")
+        elif r == 11:
+            self.remesh()                  # buffers the other slot's kernels may still read are freed and re-allocated
+        else:
+            # footprint records are refused beside a sky, gloss classes and rate 2 (and those beside them): whatever bars
+            # them goes first; then on, one frame, off
+            if self.sky:
+                self.sky = 0
+                self.add("sky", 0)
+            if self.gloss:
+                self.gloss = 0
+                self.add("gloss", 0)
+            if self.rate == 2:
+                self.rate = 1
+                self.add("rate", 1)
+            if self.bounced:
+                self.revoxelize()
+            if not self.gb[self.slot]:
+                self.gbuffer()
+            self.add("footprints", True)
+            self.trace()
+            self.read_frame()
+            self.add("footprints", False)
+
+    # -- the slot's own planes
+    def planes(self):
+        r = self.pick(2 if self.gloss else 1)
+        form = ["host", "device", None][self.pick(3)]
+        if r == 0:
+            self.add("pixel_emission", form)
+            self.emis_user[self.slot] = form is not None
+        else:
+            self.add("pixel_gloss", form)
+
+    # -- read-backs: only what some call has written
+    def read_frame(self):
+        if self.frame[self.slot]:
+            self.add("read_frame", self.marched[self.slot])      # (a voxel view writes a frame and marches no cone)
+        else:
+            self.reader()
+
+    def reader(self):
+        s = self.slot
+        can = ["chain", "gather", "gather", "cone", "cone", "voxels"]
+        if self.frame[s]:
+            can.append("read_frame")
+        if self.gb[s]:
+            can.append("read_gbuffer")
+        if self.emission or self.emis_user[s]:
+            can += ["read_pixel_emission"] * 3
+        if self.gloss:
+            can += ["read_pixel_gloss"] * 3
+        if self.lights and self.lit[s]:
+            can += ["read_pixel_lights"] * 3
+        if self.aov:
+            can += ["read_aov"] * 3
+        what = can[self.pick(len(can))]
+        if what == "gather":
+            self.add("gather", self.chance(0.5), self.chance(0.5))                  # device-located, sorted
+        elif what == "cone":
+            nap = 2 + (len(GLOSS_TABLES[self.gloss]) if self.gloss else 0)
+            self.add("cone", self.chance(0.5), self.chance(0.5), self.pick(nap))
+        elif what == "voxels":
+            self.add("voxels", self.pick(4), self.pick(CAMS))
+            self.frame[s] = True
+        elif what == "read_aov":
+            for bit in (1, 2, 4):
+                if self.aov & bit:
+                    self.add("read_aov", bit)
+        elif what == "chain":
+            self.add("read_chain")
+        elif what == "read_frame":
+            self.read_frame()
+        else:
+            self.add(what)
+
+
+def call_list(seed, rounds=ROUNDS):
+    m = CallList(np.random.default_rng(seed))
+    m.add("produce", 0)
+    for r in (0, 1, 2, 4, 7):               # most runs begin with something attached: lights, a sky, gloss classes, emission, outputs
+        if m.chance(0.6):
+            m.setter(r)
+    for _ in range(rounds):
+        s0 = m.pick(2)
+        m.switch(s0)
+        # a frame on slot s0, with or without new shared state in front of it ...
+        r = m.rng.random()
+        if r < 0.15 and m.marched[s0]:
+            m.produce()
+        elif r < 0.3:
+            m.gi()
+        else:
+            if r < 0.45:
+                m.produce()
+            elif r < 0.6:
+                m.planes()
+            m.some_gbuffer()
+        if m.chance(0.4):
+            m.voxelize()
+        # ... and, while its trace is still running, the other slot at once: shared state rewritten, the slot's planes handed
+        # over through the staging both slots share, or a read-back
+        m.switch(1 - s0)
+        m.setter()
+        if m.chance(0.5):
+            m.planes()
+        m.reader()
+        m.setter()
+        if m.gb[m.slot] and m.chance(0.5):
+            m.trace()                      # the resident G-buffer under the new state, at once
+            m.reader()
+        r = m.rng.random()
+        if r < 0.3:
+            m.produce()
+        elif r < 0.45:
+            m.gi()
+        if m.chance(0.6):
+            m.some_gbuffer()
+        if m.chance(0.5):
+            m.reader()
+        m.switch(s0)
+        if m.pending:
+            m.inject()                     # level 0 rewritten at once, while the other slot's frame is in flight
+        m.read_frame()
+        m.reader()
+    return m.ops
+
+
+# ---- inputs, made once for both runs ------------------------------------------------------------------------------------
+class Inputs:
+    def __init__(self, vct, w, h, v):
+        import torch
+        from voxel_cone_tracing_amd import scene as sc
+        self.torch, self.sc, self.w, self.h, self.v = torch, sc, w, h, v
+        npix, tiles = w * h, ((w + 7) // 8) * ((h + 7) // 8)
+        self.meshes = [sc.Scene(sc.ATRIUM, 0.15, 1234), sc.Scene(sc.ATRIUM, 0.2, 99)]
+        self.cams = cameras(sc, w, h, CAMS)
+        self.dirs = light_dirs(LIGHT_DIRS)
+        r = np.random.default_rng(77)
+        # two host-located linear G-buffers, from the raster pass of a context of its own
+        ctx, _ = make(vct, w, h, V=v)
+        ctx.render_shadow_map(sc.light_view_proj(self.dirs[0]))
+        self.host_gb = []
+        for pos, vp in self.cams[:2]:
+            ctx.set_camera_position(pos)
+            ctx.render_gbuffer(vp)
+            self.host_gb.append(ctx.download_gbuffer())
+        ctx.close()
+        # the same two as a renderer's buffers, in host memory and as device tensors
+        self.imp_host, self.imp_dev, self.keep = [], [], []
+        nmat = self.meshes[0].albedo.shape[0]
+        for g in self.host_gb:
+            spec = np.zeros((npix, 4), np.float32)
+            spec[:, :3] = g[19:22].T
+            d = dict(position=np.ascontiguousarray(g[0:3].T), normal=np.ascontiguousarray(g[3:6].T),
+                     albedo=np.ascontiguousarray(g[15:19].T), specular=spec, shadow=np.ascontiguousarray(g[22]),
+                     material=r.integers(0, nmat + 2, npix).astype(np.uint16))
+            self.imp_host.append(d)
+            t = {k: torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).cuda() for k, a in d.items()}
+            self.keep.append(t)
+            self.imp_dev.append({k: x.data_ptr() for k, x in t.items()})
+        # planes of a slot: host linear and device tiled
+        self.emis_host = r.uniform(0.0, 2.0, (3, npix)).astype(np.float32)
+        self.emis_dev = torch.from_numpy(r.uniform(0.0, 2.0, (tiles, 3, 64)).astype(np.float32)).cuda()
+        self.gloss_host = gr.checkerboard(w, h, 3, in_frame_extra=200)
+        self.gloss_dev = torch.from_numpy(r.integers(0, 4, (tiles, 64)).astype(np.uint8)).cuda()
+        # material tables, per mesh
+        self.emission = [(r.uniform(0.0, 1.5, (m.albedo.shape[0], 3)) * (r.random((m.albedo.shape[0], 1)) < 0.5)).astype(np.float32)
+                         for m in self.meshes]
+        for e in self.emission:
+            e[0] = (0.5, 0.25, 1.0)          # never an all-zero table: that would detach
+        self.mat_class = [r.integers(0, 4, m.albedo.shape[0]).astype(np.uint8) for m in self.meshes]
+        # query points: live pixels of the first G-buffer, in an order that is not spatial
+        live = np.flatnonzero(self.host_gb[0][18] >= 0.5)
+        idx = r.permutation(live)[:NPOINTS]
+        self.gather_pts = np.ascontiguousarray(self.host_gb[0][0:12, idx].T, np.float32)
+        dirs = r.normal(size=(idx.size, 3))
+        self.cone_pts = np.ascontiguousarray(np.concatenate(
+            [self.gather_pts[:, 0:6], dirs / np.linalg.norm(dirs, axis=1, keepdims=True)], axis=1), np.float32)
+        n = idx.size
+        self.npts = n
+        self.d_gather, self.d_cone = torch.from_numpy(self.gather_pts).cuda(), torch.from_numpy(self.cone_pts).cuda()
+        self.d_out = torch.zeros((n, 4), dtype=torch.float32, device="cuda")
+        self.d_cones = torch.zeros((n, 6, 4), dtype=torch.float32, device="cuda")
+        self.d_steps = torch.zeros((n, 6), dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+
+
+@pytest.fixture(scope="module")
+def inputs(vct):
+    return Inputs(vct, W, H, V)
+
+
+# ---- one run ------------------------------------------------------------------------------------------------------------
+CHUNK = 16 << 20
+
+
+def digest(chunk):
+    return hashlib.blake2b(chunk, digest_size=16).digest()
+
+
+def digests(pool, a):
+    """One BLAKE2b digest per 16 MiB of the array's bytes, formed on the pool's threads (hashlib releases the GIL)."""
+    b = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+    return [(a.shape, str(a.dtype))] + [pool.submit(digest, b[i:i + CHUNK]) for i in range(0, max(b.size, 1), CHUNK)]
+
+
+def run(vct, inp, ops, sync):
+    """The calls of `ops` on a two-slot context; [(call index, call, digests and values of what it returned)]."""
+    sc = inp.sc
+    c, _ = make(vct, inp.w, inp.h, V=inp.v, voxel_attributes=1)
+    c.set_frames_in_flight(2)
+    mesh = 0
+    records = []
+    pool = ThreadPoolExecutor(max_workers=8)
+
+    def record(k, op, *values):
+        records.append((k, op, [digests(pool, x) if isinstance(x, np.ndarray) else x for x in values]))
+
+    try:
+        for k, op in enumerate(ops):
+            name = op[0]
+            if name == "produce":
+                c.set_light_direction(inp.dirs[op[1]])
+                c.render_shadow_map(sc.light_view_proj(inp.dirs[op[1]]))
+                c.voxelize(); c.inject_light(); c.build_mips()
+            elif name == "revoxelize":
+                c.voxelize(); c.inject_light(); c.build_mips()
+            elif name == "voxelize":
+                c.set_light_direction(inp.dirs[op[1]])
+                c.render_shadow_map(sc.light_view_proj(inp.dirs[op[1]]))
+                c.voxelize()
+            elif name == "inject":
+                c.inject_light(); c.build_mips()
+            elif name == "gi":
+                c.set_light_direction(inp.dirs[op[1]]); c.set_camera_position(inp.cams[op[2]][0])
+                c.gi_pass(sc.light_view_proj(inp.dirs[op[1]]), inp.cams[op[2]][1])
+            elif name == "gbuffer":
+                c.set_camera_position(inp.cams[op[1]][0]); c.render_gbuffer(inp.cams[op[1]][1])
+            elif name == "trace":
+                c.trace_resident()
+            elif name == "switch":
+                c.select_frame_slot(op[1])
+            elif name == "remesh":
+                mesh = op[1]
+                m = inp.meshes[mesh]
+                c.upload_triangles(m.pos, m.material, m.albedo)
+                c.upload_mesh_attributes(*m.frames(), m.specular)
+            elif name == "apertures":
+                c.set_cone_apertures(*APERTURES[op[1]])
+            elif name == "trace_host":
+                c.set_camera_position(inp.cams[op[1]][0])
+                record(k, op, c.trace(inp.host_gb[op[1]]), c.last_step_count())
+            elif name == "import":
+                cam, device, extras = op[1:]
+                src = inp.imp_dev[cam] if device else inp.imp_host[cam]
+                kw = dict(shadow=src["shadow"], material=src["material"]) if extras else {}
+                if device:
+                    kw.update(position_format=vct.IMPORT_POSITION_F32X3, normal_format=vct.IMPORT_NORMAL_F32X3,
+                              albedo_format=vct.IMPORT_COLOR_F32X4, specular_format=vct.IMPORT_COLOR_F32X4)
+                c.set_camera_position(inp.cams[cam][0])
+                c.import_gbuffer(src["position"], src["normal"], src["albedo"], specular=src["specular"], **kw)
+            elif name == "lights":
+                c.set_lights(LIGHT_SETS[op[1]])
+            elif name == "sky":
+                c.set_sky(SKIES[op[1]])
+            elif name == "gloss":
+                c.set_gloss_classes(GLOSS_TABLES[op[1]])
+            elif name == "matgloss":
+                c.upload_material_gloss(inp.mat_class[mesh] if op[1] else None)
+            elif name == "emission":
+                c.upload_emission(inp.emission[mesh] if op[1] else None)
+            elif name == "rate":
+                c.set_diffuse_rate(op[1])
+            elif name == "components":
+                c.set_lighting_components(op[1])
+            elif name == "aov":
+                c.set_aov_outputs(op[1])
+            elif name == "footprints":
+                c.set_footprint_records(op[1])
+            elif name == "bounce":
+                c.bounce()
+            elif name == "pixel_emission":
+                if op[1] == "device":
+                    c.set_pixel_emission(inp.emis_dev.data_ptr(), layout=vct.GB_TILED)
+                else:
+                    c.set_pixel_emission(inp.emis_host if op[1] else None)
+            elif name == "pixel_gloss":
+                if op[1] == "device":
+                    c.set_pixel_gloss(inp.gloss_dev.data_ptr(), layout=vct.GB_TILED)
+                else:
+                    c.set_pixel_gloss(inp.gloss_host if op[1] else None)
+            elif name == "read_frame":
+                record(k, op, c.download_frame(), c.last_step_count() if len(op) < 2 or op[1] else None)
+            elif name == "read_steps":
+                record(k, op, c.last_step_count())
+            elif name == "read_gbuffer":
+                record(k, op, c.download_gbuffer())
+            elif name == "read_pixel_emission":
+                record(k, op, c.download_pixel_emission())
+            elif name == "read_pixel_gloss":
+                record(k, op, c.download_pixel_gloss())
+            elif name == "read_pixel_lights":
+                record(k, op, c.download_pixel_lights())
+            elif name == "read_aov":
+                record(k, op, c.download_aov(op[1]))
+            elif name == "read_chain":
+                record(k, op, c.download_chain())
+            elif name == "gather":
+                device, sort = op[1:]
+                if device:
+                    c.gather_points(inp.d_gather.data_ptr(), n=inp.npts, out_device_ptr=inp.d_out.data_ptr(),
+                                    cones_device_ptr=inp.d_cones.data_ptr(), steps_device_ptr=inp.d_steps.data_ptr(), sort=sort)
+                    last = c.last_point_query()             # waits for the slot's stream, and for nothing else
+                    got = [t.cpu().numpy() for t in (inp.d_out, inp.d_cones, inp.d_steps)]
+                else:
+                    got = list(c.gather_points(inp.gather_pts, want_cones=True, want_steps=True, sort=sort))
+                    last = c.last_point_query()
+                record(k, op, *got, last)
+            elif name == "cone":
+                device, sort, ap = op[1:]
+                if device:
+                    c.cone_points(inp.d_cone.data_ptr(), ap, n=inp.npts, out_device_ptr=inp.d_out.data_ptr(),
+                                  steps_device_ptr=inp.d_steps.data_ptr(), sort=sort)
+                    last = c.last_point_query()
+                    got = [inp.d_out.cpu().numpy(), inp.d_steps.cpu().numpy().reshape(-1)[:inp.npts]]
+                else:
+                    got = list(c.cone_points(inp.cone_pts, ap, want_steps=True, sort=sort))
+                    last = c.last_point_query()
+                record(k, op, *got, last)
+            elif name == "voxels":
+                level = 0 if op[1] >= vct.VOXVIEW_ALBEDO else 1
+                c.render_voxels(sc.invert_matrix(inp.cams[op[2]][1]), op[1], level)
+                record(k, op, c.download_frame())
+            else:
+                raise AssertionError(op)
+            if sync:
+                c.synchronize()
+        c.synchronize()
+    finally:
+        c.close()
+    def settled(v):
+        return [x.result() if hasattr(x, "result") else x for x in v] if isinstance(v, list) else v
+    out = [(k, op, [settled(v) for v in values]) for k, op, values in records]
+    pool.shutdown()
+    return out
+
+
+def assert_same(got, want, ops, what):
+    assert len(got) == len(want), what
+    for (k, op, a), (_, _, b) in zip(got, want):
+        assert a == b, f"{what}: call {k} {op} returned something else without the waits; the calls before it: {ops[max(0, k - 12):k]}"
+
+
+# ---- the tests ----------------------------------------------------------------------------------------------------------
+def test_the_call_lists_reach_every_call():
+    """Not a GPU matter, but the generator is this module's: over the seeds below every kind of call is issued."""
+    seen = {op[0] for seed in SEEDS for op in call_list(seed)}
+    assert seen >= {"produce", "revoxelize", "voxelize", "inject", "gi", "gbuffer", "trace", "switch", "apertures", "trace_host",
+                    "import", "lights",
+                    "sky", "gloss", "matgloss", "emission", "rate", "components", "aov", "bounce", "pixel_emission",
+                    "pixel_gloss", "read_frame", "read_gbuffer", "read_pixel_emission", "read_pixel_gloss", "read_pixel_lights",
+                    "read_aov", "read_chain", "gather", "cone", "voxels", "footprints", "remesh"}, sorted(seen)
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_random_call_orders_give_what_a_synchronised_context_gives(vct, inputs, seed):
+    ops = call_list(seed)
+    got, want = run(vct, inputs, ops, False), run(vct, inputs, ops, True)
+    assert len(want) >= 2 * ROUNDS
+    assert_same(got, want, ops, f"seed {seed}")
+
+
+# (writer on slot 0, what its effect is read back with): each leaves work on slot 0's stream or has just used the staging
+WRITERS = {
+    "trace_host": ([("trace_host", 0)], "read_frame"),
+    "pixel_emission": ([("pixel_emission", "host"), ("trace",)], "read_frame"),
+    "pixel_gloss": ([("pixel_gloss", "host"), ("trace",)], "read_frame"),
+    "read_gbuffer": ([("trace",), ("read_gbuffer",)], "read_gbuffer"),
+    "read_pixel_emission": ([("trace",), ("read_pixel_emission",)], "read_pixel_emission"),
+    "read_pixel_lights": ([("trace",), ("read_pixel_lights",)], "read_pixel_lights"),
+}
+# what slot 1 does at once; the three downloads start with an untile kernel that writes the staging from the GPU, with no
+# host copy in front of it
+USERS = {
+    "trace_host": [("trace_host", 1)],
+    "pixel_emission": [("pixel_emission", "host")],
+    "pixel_gloss": [("pixel_gloss", "host")],
+    "read_gbuffer": [("read_gbuffer",)],
+    "read_pixel_emission": [("read_pixel_emission",)],
+    "read_pixel_lights": [("read_pixel_lights",)],
+}
+
+
+@pytest.mark.parametrize("writer", list(WRITERS))
+def test_directed_orders_on_the_shared_staging(vct, inputs, writer):
+    """For every pair (writer on slot 0, user on slot 1): slot 0's call, the switch, slot 1's call, with nothing in between;
+    then slot 0's frame or plane, and slot 1's frame.  Against the same calls with a vct_synchronize between them.  (One
+    pair of contexts per writer, the six users one after the other: a 1080p context costs more than the calls.)"""
+    first, back = WRITERS[writer]
+    ops = [("produce", 0), ("lights", 1), ("gloss", 1), ("revoxelize",)]
+    for slot in (0, 1):                      # both slots: a G-buffer, planes of their own, a first frame (lit planes)
+        ops += [("switch", slot), ("gbuffer", slot), ("pixel_emission", "device"), ("trace",)]
+    for user in USERS:
+        ops += [("switch", 0)] + first + [("switch", 1)] + USERS[user] + [("switch", 0), (back,), ("switch", 1), ("read_frame",)]
+    got, want = run(vct, inputs, ops, False), run(vct, inputs, ops, True)
+    assert_same(got, want, ops, f"{writer} on slot 0")
+
+
+def two_frames():
+    """Both slots with lights and gloss classes attached, a G-buffer and a first frame each."""
+    ops = [("produce", 0), ("lights", 1), ("gloss", 1), ("revoxelize",)]
+    for slot in (0, 1):
+        ops += [("switch", slot), ("gbuffer", slot), ("pixel_gloss", "host"), ("trace",)]
+    return ops
+
+
+def test_level_0_rewritten_while_the_other_slot_traces(vct, inputs):
+    """With lights attached: slot 0 voxelizes under a moved light, slot 1 queues frames, slot 0 injects at once -- the
+    selection's first producer, so vct_inject_light's own join is all that keeps the resolve and the lights' voxel kernel
+    behind slot 1's traces."""
+    ops = two_frames()
+    for k in (1, 2, 3):
+        ops += [("switch", 0), ("voxelize", k), ("switch", 1), ("trace",), ("trace",), ("trace",), ("switch", 0), ("inject",),
+                ("switch", 1), ("read_frame",), ("trace",), ("read_frame",), ("switch", 0), ("trace",), ("read_frame",)]
+    got, want = run(vct, inputs, ops, False), run(vct, inputs, ops, True)
+    assert_same(got, want, ops, "voxelize, the other slot's traces, inject")
+
+
+def test_step_tables_rewritten_while_the_other_slot_traces(vct, inputs):
+    """With gloss classes attached: new apertures and a trace at once on slot 1 while slot 0's frames are in flight -- the
+    drain of vct_refresh_steps keeps the upload of the tables behind them."""
+    ops = two_frames()
+    for k in (1, 2, 0):
+        ops += [("switch", 0), ("trace",), ("trace",), ("trace",), ("switch", 1), ("apertures", k), ("trace",),
+                ("switch", 0), ("read_frame",), ("switch", 1), ("read_frame",)]
+    got, want = run(vct, inputs, ops, False), run(vct, inputs, ops, True)
+    assert_same(got, want, ops, "traces, new apertures on the other slot")
+
+
+def test_step_count_of_a_bounce_while_the_other_slot_bounces(vct, inputs):
+    """vct_last_step_count after a bounce reads the context's one bank of counters, which the other slot's bounce rewrites."""
+    ops = [("produce", 0), ("bounce",), ("switch", 1), ("bounce",), ("switch", 0), ("read_steps",), ("switch", 1), ("read_steps",)]
+    got, want = run(vct, inputs, ops, False), run(vct, inputs, ops, True)
+    assert_same(got, want, ops, "bounce, bounce")

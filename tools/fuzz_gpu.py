@@ -8,6 +8,8 @@ import numpy as np, synth, vctpkg, raster_oracle
 vct = vctpkg.load()
 from oracle import pyoracle as oracle
 from voxel_cone_tracing_amd import scene as sc
+import gloss_ref as gr, lights_ref as lr, sky_ref as sr
+import test_gpu_feature_combinations as combos      # the combo stage: its context, launch and bars
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
 BIG = len(sys.argv) > 2 and sys.argv[2] == "big"      # larger grids / frames, fewer cases per second
@@ -170,4 +172,36 @@ while time.time() < t_end:
             ctx.select_frame_slot(0)
             if not np.array_equal(ctx.download_gbuffer().view(np.uint32), gref.view(np.uint32)): fail("gbuffer raster (slot 0 behind slot 1)", seed)
         counts["raster"] += 1
+    # ---- combo: the newer features together, drawn at random, against tests/frame_ref.py with the bars of
+    # tests/test_gpu_feature_combinations.py (what its fixed table samples, this sweeps) ----
+    V = int(r.choice([16, 32])); w = int(r.integers(9, 70)); h = int(r.integers(9, 50))
+    planes = combos.floor_gbuffer(w, h) if r.random() < 0.6 and w > 13 and h > 6 else \
+        synth.random_gbuffer(w * h, seed=seed, discard_frac=float(r.uniform(0, 0.3)))
+    cs = dict(V=V, w=w, h=h, ty=(h + 7) // 8, planes=planes, caches={},
+              chain=oracle.build_mips(synth.noise_volume(V, seed=seed, occupancy=float(r.uniform(0.03, 0.4)))))
+    what = dict(rate=int(r.choice([1, 2])), mask=int(r.choice([31, 31, int(r.integers(0, 32))])),
+                aov=int(r.choice([0, 0, int(r.integers(1, 8))])))
+    if r.random() < 0.6:
+        what["sky"] = (sr.SH * r.uniform(-1.0, 1.5, (9, 3))).astype(np.float32)
+    if r.random() < 0.6:
+        ncls = int(r.integers(1, 5))
+        what.update(classes=[gr.CLASSES[i] for i in r.permutation(4)[:ncls]],
+                    gloss_plane=r.integers(0, ncls + 2, w * h).astype(np.uint8))
+    if r.random() < 0.6:
+        what["emission"] = r.uniform(0.0, 2.0, (3, w * h)).astype(np.float32)
+    if r.random() < 0.6:
+        what["lights"] = [combos.ONE_LIGHT, combos.TWO_LIGHTS, lr.LIGHTS, lr.many_lights()][int(r.integers(0, 4))]
+    if what["rate"] == 1 and r.random() < 0.3:
+        r0 = int(r.integers(0, cs["ty"])); what["rows"] = (r0, int(r.integers(r0 + 1, cs["ty"] + 1)))
+    consts = dict(wrap_repeat=int(r.random() < 0.7), max_alpha=float(r.choice([0.95, 0.95, 0.97])))
+    with combos.context(vct, cs, **consts) as ctx:
+        try:
+            full = None
+            if what["rate"] == 2:
+                full = combos.launch_and_check(vct, oracle, ctx, cs, f"combo seed {seed} rate 1", **dict(what, rate=1))[0].copy()
+            combos.launch_and_check(vct, oracle, ctx, cs, f"combo seed {seed}", full=full, **what)
+        except AssertionError as e:
+            shown = {k: v for k, v in what.items() if k not in ("emission", "gloss_plane", "sky")}
+            fail("combo", seed, f"V={V} {w}x{h} {consts} {shown} {str(e)[:400]}")
+    counts["combo"] = counts.get("combo", 0) + 1
 print("fuzz ok:", counts, "seeds", counts["trace"], "last seed", seed)

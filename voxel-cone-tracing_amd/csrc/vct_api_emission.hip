@@ -23,14 +23,6 @@ hipError_t vct_emission_planes(const vct_ctx* c, VctFrameSlot& s) {
     return e;
 }
 
-// c->gb_linear is ONE staging buffer for both frame slots (bind_gbuffer, vct_download_gbuffer and the two calls below use it
-// on the selected slot's stream): before this slot's work overwrites it the host waits for whatever the other slot's stream
-// still has in flight -- that may be a tile kernel reading it.  Only a host-located linear hand-over or a download pays this.
-static int staging_free(vct_ctx* c) {
-    if (c->frames_in_flight > 1) HIP_TRY(c, hipStreamSynchronize(other(c).stream.get()));
-    return VCT_OK;
-}
-
 extern "C" {
 
 int vct_upload_emission(vct_ctx* c, const float* emission) {
@@ -106,7 +98,7 @@ int vct_set_pixel_emission(vct_ctx* c, const float* planes, int32_t layout, int3
     } else {
         const float* src = planes;
         if (location == VCT_MEM_HOST) {
-            PIPE_TRY(staging_free(c));
+            PIPE_TRY(vct_staging_free(c));
             HIP_TRY(c, c->gb_linear.reserve(npix * VCT_GB_NPLANES));
             HIP_TRY(c, hipMemcpyAsync(c->gb_linear.get(), planes, npix * VCT_EMIS_NPLANES * sizeof(float), hipMemcpyHostToDevice, s.stream.get()));
             src = c->gb_linear.get();
@@ -123,7 +115,7 @@ int vct_download_pixel_emission(vct_ctx* c, float* planes) {
     if (!cur(c).emis) return vct_fail(c, VCT_ERR_INVALID, "vct_download_pixel_emission: no pixel-emission planes (vct_upload_emission, vct_set_pixel_emission)");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t npix = (size_t)c->cfg.width * c->cfg.height;
-    PIPE_TRY(staging_free(c));
+    PIPE_TRY(vct_staging_free(c));
     HIP_TRY(c, c->gb_linear.reserve(npix * VCT_GB_NPLANES));
     HIP_TRY(c, vct_launch_untile_emission(cur(c).emis.get(), c->gb_linear.get(), c->cfg.width, c->cfg.height, cur(c).stream.get()));
     HIP_TRY(c, hipMemcpyAsync(planes, c->gb_linear.get(), npix * VCT_EMIS_NPLANES * sizeof(float), hipMemcpyDeviceToHost, cur(c).stream.get()));

@@ -15,12 +15,6 @@ hipError_t vct_gloss_plane(const vct_ctx* c, VctFrameSlot& s) {
 // The caller has made sure nothing in flight reads the map (vct_pipeline_drain + the selected stream).
 void vct_material_gloss_detach(vct_ctx* c) { c->mesh.mat_gloss.reset(); }
 
-// c->gb_linear is ONE staging buffer for both frame slots: see vct_api_emission.hip staging_free
-static int staging_free(vct_ctx* c) {
-    if (c->frames_in_flight > 1) HIP_TRY(c, hipStreamSynchronize(other(c).stream.get()));
-    return VCT_OK;
-}
-
 extern "C" {
 
 int vct_set_gloss_classes(vct_ctx* c, const vct_gloss_class* classes, int32_t nclasses) {
@@ -135,7 +129,7 @@ int vct_set_pixel_gloss(vct_ctx* c, const uint8_t* classes, int32_t layout, int3
     } else {
         const uint8_t* src = classes;
         if (location == VCT_MEM_HOST) {
-            PIPE_TRY(staging_free(c));
+            PIPE_TRY(vct_staging_free(c));
             HIP_TRY(c, c->gb_linear.reserve(npix * VCT_GB_NPLANES));
             HIP_TRY(c, hipMemcpyAsync(c->gb_linear.get(), classes, npix, hipMemcpyHostToDevice, s.stream.get()));
             src = (const uint8_t*)c->gb_linear.get();
@@ -151,7 +145,7 @@ int vct_download_pixel_gloss(vct_ctx* c, uint8_t* out) {
     if (!cur(c).gloss) return vct_fail(c, VCT_ERR_INVALID, "vct_download_pixel_gloss: no pixel-gloss plane (vct_set_gloss_classes)");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t npix = (size_t)c->cfg.width * c->cfg.height;
-    PIPE_TRY(staging_free(c));
+    PIPE_TRY(vct_staging_free(c));
     HIP_TRY(c, c->gb_linear.reserve(npix * VCT_GB_NPLANES));
     HIP_TRY(c, vct_launch_untile_gloss(cur(c).gloss.get(), (uint8_t*)c->gb_linear.get(), c->cfg.width, c->cfg.height, cur(c).stream.get()));
     HIP_TRY(c, hipMemcpyAsync(out, c->gb_linear.get(), npix, hipMemcpyDeviceToHost, cur(c).stream.get()));

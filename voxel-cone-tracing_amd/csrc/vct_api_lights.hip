@@ -101,8 +101,7 @@ int vct_download_pixel_lights(vct_ctx* c, float* planes) {
         return vct_fail(c, VCT_ERR_INVALID, "vct_download_pixel_lights: no composite launch with lights attached has run on this frame slot");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t npix = (size_t)c->cfg.width * c->cfg.height;
-    // the staging buffer is shared by both slots: the other slot's stream may still have a tile kernel reading it
-    if (c->frames_in_flight > 1) HIP_TRY(c, hipStreamSynchronize(other(c).stream.get()));
+    PIPE_TRY(vct_staging_free(c));
     HIP_TRY(c, c->gb_linear.reserve(npix * VCT_GB_NPLANES));
     HIP_TRY(c, vct_launch_untile_emission(s.lit.get(), c->gb_linear.get(), c->cfg.width, c->cfg.height, s.stream.get()));
     HIP_TRY(c, hipMemcpyAsync(planes, c->gb_linear.get(), npix * VCT_EMIS_NPLANES * sizeof(float), hipMemcpyDeviceToHost, s.stream.get()));

@@ -378,6 +378,7 @@ static int bind_gbuffer(vct_ctx* c, const vct_gbuffer* gb) {
     if (gb->layout != VCT_GB_LINEAR) return vct_fail(c, VCT_ERR_INVALID, "vct_trace: unknown G-buffer layout");
     const float* src = gb->planes;
     if (gb->location == VCT_MEM_HOST) {
+        PIPE_TRY(vct_staging_free(c));
         HIP_TRY(c, c->gb_linear.reserve(npix * VCT_GB_NPLANES));
         HIP_TRY(c, hipMemcpyAsync(c->gb_linear.get(), gb->planes, npix * VCT_GB_NPLANES * sizeof(float),
                                   hipMemcpyHostToDevice, cur(c).stream.get()));

@@ -319,6 +319,7 @@ int vct_bounce(vct_ctx* c) {
 
 // One Morton level of N^3 texels -> linear staging -> host, synchronised (the next level reuses the staging buffer).
 static int download_level(vct_ctx* c, const uint32_t* morton, int N, uint8_t* dst) {
+    PIPE_TRY(vct_staging_free(c));
     HIP_TRY(c, c->vol.staging.reserve(c->vol.nvox()));
     HIP_TRY(c, vct_launch_morton_to_linear(morton, c->vol.staging.get(), N, cur(c).stream.get()));
     HIP_TRY(c, hipMemcpyAsync(dst, c->vol.staging.get(), (size_t)N * N * N * 4, hipMemcpyDeviceToHost, cur(c).stream.get()));

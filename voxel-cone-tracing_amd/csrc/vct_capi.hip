@@ -225,6 +225,11 @@ int vct_pipeline_drain(vct_ctx* c) {
     return VCT_OK;
 }
 
+int vct_staging_free(vct_ctx* c) {
+    if (c->frames_in_flight > 1) HIP_TRY(c, hipStreamSynchronize(other(c).stream.get()));
+    return VCT_OK;
+}
+
 hipError_t vct_create_masked_stream(hipStream_t* s, int device, int first_cu, int last_cu) {
     hipDeviceProp_t prop;
     hipError_t e = hipGetDeviceProperties(&prop, device);

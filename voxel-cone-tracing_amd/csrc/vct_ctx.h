@@ -480,6 +480,11 @@ int vct_create_overlapping_stream(vct_ctx* c, hipStream_t base, hipStream_t* out
 int vct_pipeline_join(vct_ctx* c);
 // Uploads free and reallocate buffers the other slot's kernels may still read: the host waits for that slot.
 int vct_pipeline_drain(vct_ctx* c);
+// c->gb_linear and c->vol.staging are ONE staging buffer each for both frame slots, used on the selected slot's stream: before
+// this slot's work overwrites one the host waits for whatever the other slot's stream still has in flight -- that may be a
+// tile kernel reading it.  Only a host-located linear hand-over or a download pays this (a volume upload drains the pipeline
+// anyway); with one slot it does nothing.
+int vct_staging_free(vct_ctx* c);
 // vct_api_scene.hip: textures are used once both the maps and the texture coordinates are there
 VctTextures vct_textures_of(const vct_ctx* c);
 // vct_api_raster.hip: `shadow_ready` not null: the visibility raster is issued at once, only the shading kernel (it reads the shadow map) waits for it

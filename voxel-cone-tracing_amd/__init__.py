@@ -284,6 +284,13 @@ def chain_texels(V):
     return _lib.vct_chain_texels(V)
 
 
+def _plane_elems(cfg, layout, nplanes):
+    """Elements of `nplanes` per-pixel planes of the frame in a layout: linear [nplanes, h*w] or tiled [tiles, nplanes, 64]."""
+    if layout == GB_LINEAR:
+        return nplanes * cfg.width * cfg.height
+    return ((cfg.width + 7) // 8) * ((cfg.height + 7) // 8) * nplanes * 64
+
+
 def _ptr(a):
     if a is None:
         return None
@@ -427,8 +434,7 @@ class Context:
             self._ck(_lib.vct_set_pixel_emission(self._h, _ptr(planes), layout, MEM_DEVICE), "vct_set_pixel_emission")
             return
         planes = np.ascontiguousarray(planes, np.float32)
-        want = 3 * self.cfg.width * self.cfg.height if layout == GB_LINEAR else \
-            ((self.cfg.width + 7) // 8) * ((self.cfg.height + 7) // 8) * 3 * 64
+        want = _plane_elems(self.cfg, layout, 3)
         if planes.size != want:
             raise VctError(f"set_pixel_emission: {planes.size} floats, this layout of the frame has {want}")
         self._ck(_lib.vct_set_pixel_emission(self._h, _ptr(planes), layout, MEM_HOST), "vct_set_pixel_emission")
@@ -482,8 +488,7 @@ class Context:
             self._ck(_lib.vct_set_pixel_gloss(self._h, _ptr(classes), layout, MEM_DEVICE), "vct_set_pixel_gloss")
             return
         classes = np.ascontiguousarray(classes, np.uint8)
-        want = self.cfg.width * self.cfg.height if layout == GB_LINEAR else \
-            ((self.cfg.width + 7) // 8) * ((self.cfg.height + 7) // 8) * 64
+        want = _plane_elems(self.cfg, layout, 1)
         if classes.size != want:
             raise VctError(f"set_pixel_gloss: {classes.size} bytes, this layout of the frame has {want}")
         self._ck(_lib.vct_set_pixel_gloss(self._h, _ptr(classes), layout, MEM_HOST), "vct_set_pixel_gloss")

@@ -14,14 +14,10 @@ void vct_emission_detach(vct_ctx* c) {
         if (!sl.emis_user) sl.emis.reset();
 }
 
-// zeroed planes for a slot that has none, on the slot's stream
-hipError_t vct_emission_planes(const vct_ctx* c, VctFrameSlot& s) {
-    if (s.emis) return hipSuccess;
-    hipError_t e = s.emis.alloc(vct_emis_tiled_floats(c));
-    if (e == hipSuccess) e = hipMemsetAsync(s.emis.get(), 0, vct_emis_tiled_floats(c) * sizeof(float), s.stream.get());
-    if (e != hipSuccess) s.emis.reset();
-    return e;
+hipError_t vct_emission_planes(const vct_ctx* c, VctFrameSlot& s, bool* fresh) {
+    return vct_planes_ensure(s.emis, vct_emis_tiled_floats(c), s.stream.get(), fresh);
 }
+static void emission_planes_drop(VctFrameSlot& s) { s.emis.reset(); }
 
 extern "C" {
 
@@ -37,8 +33,7 @@ int vct_upload_emission(vct_ctx* c, const float* emission) {
                  bad % 3, bad / 3, (double)emission[bad]);
         return vct_fail(c, VCT_ERR_INVALID, msg);
     }
-    if (verdict == VCT_EMISSION_OK && c->cfg.trace_variant != 0)
-        return vct_fail(c, VCT_ERR_INVALID, "vct_upload_emission: config.trace_variant 1 .. 4 has no pixel-emission planes");
+    if (verdict == VCT_EMISSION_OK) PIPE_TRY(vct_refuse_conflict(c, "vct_upload_emission", VCT_FEAT_EMISSION, vct_rules_in_force(c).modes));
     HIP_TRY(c, hipSetDevice(c->device));
     PIPE_TRY(vct_pipeline_drain(c));
     HIP_TRY(c, hipStreamSynchronize(cur(c).stream.get()));
@@ -46,25 +41,15 @@ int vct_upload_emission(vct_ctx* c, const float* emission) {
         vct_emission_detach(c);
         return VCT_OK;
     }
-    // all or nothing: the table and the pool in locals, planes only for slots that have none (released again on a failure)
+    // all or nothing: the table and the pool in locals, planes only for slots that have none
     std::vector<float> padded((size_t)nmat * 4);
     vct_emission_pad(emission, nmat, padded.data());
     VctBuf<float> table;
     VctBuf<uint32_t> pool;
-    bool fresh_planes[2] = {false, false};
     hipError_t e = table.alloc(padded.size());
     if (e == hipSuccess) e = hipMemcpy(table.get(), padded.data(), padded.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess && !c->vox.emis_pool) e = pool.alloc((size_t)(c->vox.nslots ? c->vox.nslots : 1u) * 512);
-    for (int k = 0; k < c->frames_in_flight && e == hipSuccess; ++k) {
-        fresh_planes[k] = !c->slots[k].emis;
-        e = vct_emission_planes(c, c->slots[k]);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->slots[k].stream.get());
-    }
-    if (e != hipSuccess) {
-        for (int k = 0; k < 2; ++k)
-            if (fresh_planes[k]) c->slots[k].emis.reset();
-        return vct_fail(c, e == hipErrorOutOfMemory ? VCT_ERR_NOMEM : VCT_ERR_DEVICE, std::string("vct_upload_emission: ") + hipGetErrorString(e));
-    }
+    PIPE_TRY(vct_planes_attach(c, "vct_upload_emission", vct_emission_planes, emission_planes_drop, e));
     c->mesh.mat_emission = std::move(table);
     if (pool) c->vox.emis_pool = std::move(pool);
     c->vox.emis_dirty = true;       // the next north-star pass rebuilds the pool from this table
@@ -88,25 +73,10 @@ int vct_set_pixel_emission(vct_ctx* c, const float* planes, int32_t layout, int3
     }
     if (layout != VCT_GB_LINEAR && layout != VCT_GB_TILED) return vct_fail(c, VCT_ERR_INVALID, "vct_set_pixel_emission: unknown layout");
     if (location != VCT_MEM_HOST && location != VCT_MEM_DEVICE) return vct_fail(c, VCT_ERR_INVALID, "vct_set_pixel_emission: unknown location");
-    if (c->cfg.trace_variant != 0)
-        return vct_fail(c, VCT_ERR_INVALID, "vct_set_pixel_emission: config.trace_variant 1 .. 4 has no pixel-emission planes");
+    PIPE_TRY(vct_refuse_conflict(c, "vct_set_pixel_emission", VCT_FEAT_EMISSION, vct_rules_in_force(c).modes));
     HIP_TRY(c, vct_emission_planes(c, s));
-    const size_t npix = (size_t)c->cfg.width * c->cfg.height;
-    if (layout == VCT_GB_TILED) {
-        HIP_TRY(c, hipMemcpyAsync(s.emis.get(), planes, vct_emis_tiled_floats(c) * sizeof(float),
-                                  location == VCT_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s.stream.get()));
-    } else {
-        const float* src = planes;
-        if (location == VCT_MEM_HOST) {
-            PIPE_TRY(vct_staging_free(c));
-            HIP_TRY(c, c->gb_linear.reserve(npix * VCT_GB_NPLANES));
-            HIP_TRY(c, hipMemcpyAsync(c->gb_linear.get(), planes, npix * VCT_EMIS_NPLANES * sizeof(float), hipMemcpyHostToDevice, s.stream.get()));
-            src = c->gb_linear.get();
-        }
-        HIP_TRY(c, vct_launch_tile_emission(src, s.emis.get(), c->cfg.width, c->cfg.height, s.stream.get()));
-    }
+    PIPE_TRY(vct_planes_set(c, s.emis.get(), planes, layout, location, VCT_EMIS_NPLANES, sizeof(float)));
     s.emis_user = true;
-    if (location == VCT_MEM_HOST) HIP_TRY(c, hipStreamSynchronize(s.stream.get()));      // the caller's memory is free again
     return VCT_OK;
 }
 
@@ -114,13 +84,7 @@ int vct_download_pixel_emission(vct_ctx* c, float* planes) {
     if (!c || !planes) return VCT_ERR_INVALID;
     if (!cur(c).emis) return vct_fail(c, VCT_ERR_INVALID, "vct_download_pixel_emission: no pixel-emission planes (vct_upload_emission, vct_set_pixel_emission)");
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t npix = (size_t)c->cfg.width * c->cfg.height;
-    PIPE_TRY(vct_staging_free(c));
-    HIP_TRY(c, c->gb_linear.reserve(npix * VCT_GB_NPLANES));
-    HIP_TRY(c, vct_launch_untile_emission(cur(c).emis.get(), c->gb_linear.get(), c->cfg.width, c->cfg.height, cur(c).stream.get()));
-    HIP_TRY(c, hipMemcpyAsync(planes, c->gb_linear.get(), npix * VCT_EMIS_NPLANES * sizeof(float), hipMemcpyDeviceToHost, cur(c).stream.get()));
-    HIP_TRY(c, hipStreamSynchronize(cur(c).stream.get()));
-    return VCT_OK;
+    return vct_planes_download(c, cur(c).emis.get(), planes, VCT_EMIS_NPLANES, sizeof(float));
 }
 
 }  // extern "C"

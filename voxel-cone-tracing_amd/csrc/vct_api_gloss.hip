@@ -3,14 +3,10 @@
 #include "vct_ctx.h"
 #include "vct_gloss_check.h"
 
-// a zeroed plane for a slot that has none, on the slot's stream
-hipError_t vct_gloss_plane(const vct_ctx* c, VctFrameSlot& s) {
-    if (s.gloss) return hipSuccess;
-    hipError_t e = s.gloss.alloc(vct_gloss_tiled_bytes(c));
-    if (e == hipSuccess) e = hipMemsetAsync(s.gloss.get(), 0, vct_gloss_tiled_bytes(c), s.stream.get());
-    if (e != hipSuccess) s.gloss.reset();
-    return e;
+hipError_t vct_gloss_plane(const vct_ctx* c, VctFrameSlot& s, bool* fresh) {
+    return vct_planes_ensure(s.gloss, vct_gloss_tiled_bytes(c), s.stream.get(), fresh);
 }
+static void gloss_plane_drop(VctFrameSlot& s) { s.gloss.reset(); }
 
 // The caller has made sure nothing in flight reads the map (vct_pipeline_drain + the selected stream).
 void vct_material_gloss_detach(vct_ctx* c) { c->mesh.mat_gloss.reset(); }
@@ -33,15 +29,10 @@ int vct_set_gloss_classes(vct_ctx* c, const vct_gloss_class* classes, int32_t nc
         if (!c->gloss.n) return VCT_OK;
         PIPE_TRY(vct_synchronize(c));           // a trace in flight may still read the tables and the planes
         c->gloss = VctGloss();
-        for (VctFrameSlot& sl : c->slots) sl.gloss.reset();
+        for (VctFrameSlot& sl : c->slots) gloss_plane_drop(sl);
         return VCT_OK;
     }
-    if (c->cfg.trace_variant != 0)
-        return vct_fail(c, VCT_ERR_INVALID, "vct_set_gloss_classes: config.trace_variant 1 .. 4 has no gloss classes");
-    if (c->cfg.anisotropic_mips)
-        return vct_fail(c, VCT_ERR_INVALID, "vct_set_gloss_classes: config.anisotropic_mips has no gloss classes");
-    if (c->vol.want_cells)
-        return vct_fail(c, VCT_ERR_INVALID, "vct_set_gloss_classes: footprint records are on (vct_set_footprint_records(ctx, 0) first)");
+    PIPE_TRY(vct_refuse_conflict(c, "vct_set_gloss_classes", VCT_FEAT_GLOSS, vct_rules_in_force(c).modes));
     // every table once on the host: the limits are checked before anything changes
     int nsteps[VCT_GLOSS_CLASSES_MAX] = {};
     for (int k = 0; k < nclasses; ++k) {
@@ -54,20 +45,9 @@ int vct_set_gloss_classes(vct_ctx* c, const vct_gloss_class* classes, int32_t nc
         nsteps[k] = (int)t.size();
     }
     PIPE_TRY(vct_synchronize(c));               // the tables about to be rewritten may still be read
-    // all or nothing: the device table in a local, planes only for slots that have none (released again on a failure)
+    // all or nothing: the device table in a local, planes only for slots that have none
     VctBuf<VctGlossTable> table;
-    bool fresh_plane[2] = {false, false};
-    hipError_t e = c->gloss.table ? hipSuccess : table.alloc(1);
-    for (int k = 0; k < c->frames_in_flight && e == hipSuccess; ++k) {
-        fresh_plane[k] = !c->slots[k].gloss;
-        e = vct_gloss_plane(c, c->slots[k]);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->slots[k].stream.get());
-    }
-    if (e != hipSuccess) {
-        for (int k = 0; k < 2; ++k)
-            if (fresh_plane[k]) c->slots[k].gloss.reset();
-        return vct_fail(c, e == hipErrorOutOfMemory ? VCT_ERR_NOMEM : VCT_ERR_DEVICE, std::string("vct_set_gloss_classes: ") + hipGetErrorString(e));
-    }
+    PIPE_TRY(vct_planes_attach(c, "vct_set_gloss_classes", vct_gloss_plane, gloss_plane_drop, c->gloss.table ? hipSuccess : table.alloc(1)));
     if (table) c->gloss.table = std::move(table);
     c->gloss.n = nclasses;
     for (int k = 0; k < VCT_GLOSS_CLASSES_MAX; ++k) {
@@ -122,35 +102,14 @@ int vct_set_pixel_gloss(vct_ctx* c, const uint8_t* classes, int32_t layout, int3
     }
     if (layout != VCT_GB_LINEAR && layout != VCT_GB_TILED) return vct_fail(c, VCT_ERR_INVALID, "vct_set_pixel_gloss: unknown layout");
     if (location != VCT_MEM_HOST && location != VCT_MEM_DEVICE) return vct_fail(c, VCT_ERR_INVALID, "vct_set_pixel_gloss: unknown location");
-    const size_t npix = (size_t)c->cfg.width * c->cfg.height;
-    if (layout == VCT_GB_TILED) {
-        HIP_TRY(c, hipMemcpyAsync(s.gloss.get(), classes, vct_gloss_tiled_bytes(c),
-                                  location == VCT_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s.stream.get()));
-    } else {
-        const uint8_t* src = classes;
-        if (location == VCT_MEM_HOST) {
-            PIPE_TRY(vct_staging_free(c));
-            HIP_TRY(c, c->gb_linear.reserve(npix * VCT_GB_NPLANES));
-            HIP_TRY(c, hipMemcpyAsync(c->gb_linear.get(), classes, npix, hipMemcpyHostToDevice, s.stream.get()));
-            src = (const uint8_t*)c->gb_linear.get();
-        }
-        HIP_TRY(c, vct_launch_tile_gloss(src, s.gloss.get(), c->cfg.width, c->cfg.height, s.stream.get()));
-    }
-    if (location == VCT_MEM_HOST) HIP_TRY(c, hipStreamSynchronize(s.stream.get()));      // the caller's memory is free again
-    return VCT_OK;
+    return vct_planes_set(c, s.gloss.get(), classes, layout, location, 1, sizeof(uint8_t));
 }
 
 int vct_download_pixel_gloss(vct_ctx* c, uint8_t* out) {
     if (!c || !out) return VCT_ERR_INVALID;
     if (!cur(c).gloss) return vct_fail(c, VCT_ERR_INVALID, "vct_download_pixel_gloss: no pixel-gloss plane (vct_set_gloss_classes)");
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t npix = (size_t)c->cfg.width * c->cfg.height;
-    PIPE_TRY(vct_staging_free(c));
-    HIP_TRY(c, c->gb_linear.reserve(npix * VCT_GB_NPLANES));
-    HIP_TRY(c, vct_launch_untile_gloss(cur(c).gloss.get(), (uint8_t*)c->gb_linear.get(), c->cfg.width, c->cfg.height, cur(c).stream.get()));
-    HIP_TRY(c, hipMemcpyAsync(out, c->gb_linear.get(), npix, hipMemcpyDeviceToHost, cur(c).stream.get()));
-    HIP_TRY(c, hipStreamSynchronize(cur(c).stream.get()));
-    return VCT_OK;
+    return vct_planes_download(c, cur(c).gloss.get(), out, 1, sizeof(uint8_t));
 }
 
 }  // extern "C"

@@ -78,15 +78,9 @@ int vct_import_gbuffer_rows(vct_ctx* c, const vct_gbuffer_import* in, int32_t ro
         HIP_TRY(c, vct_gloss_plane(c, s));
         a.mat_gloss = c->mesh.mat_gloss.get(); a.gloss_tiled = s.gloss.get();
     }
-    if (c->time_traces) {
-        if (!s.gb_import.ev0) HIP_TRY(c, s.gb_import.ev0.create());
-        if (!s.gb_import.ev1) HIP_TRY(c, s.gb_import.ev1.create());
-        HIP_TRY(c, hipEventRecord(s.gb_import.ev0.get(), s.stream.get()));
-    }
+    HIP_TRY(c, s.gb_import.timer.begin(s.stream.get(), c->time_traces));
     HIP_TRY(c, vct_launch_gbuffer_import(a, s.stream.get()));
-    if (c->time_traces) HIP_TRY(c, hipEventRecord(s.gb_import.ev1.get(), s.stream.get()));
-    s.gb_import.have = true;
-    s.gb_import.timed = c->time_traces;
+    HIP_TRY(c, s.gb_import.timer.end(s.stream.get()));
     // the slot's own buffer is the resident G-buffer from here on, also after a zero-copy vct_trace of a caller's
     s.gb_current = s.gb_tiled.get();
     s.last_row0 = row0;
@@ -104,12 +98,8 @@ int vct_import_gbuffer(vct_ctx* c, const vct_gbuffer_import* in) {
 
 int vct_last_gbuffer_import_ms(vct_ctx* c, float* ms) {
     if (!c || !ms) return VCT_ERR_INVALID;
-    if (!cur(c).gb_import.have) return vct_fail(c, VCT_ERR_INVALID, "vct_last_gbuffer_import_ms: no G-buffer import has run on this frame slot");
-    if (!cur(c).gb_import.timed)
-        return vct_fail(c, VCT_ERR_INVALID, "vct_last_gbuffer_import_ms: the last import was issued with timing off (vct_set_trace_timing)");
-    HIP_TRY(c, hipEventSynchronize(cur(c).gb_import.ev1.get()));
-    HIP_TRY(c, hipEventElapsedTime(ms, cur(c).gb_import.ev0.get(), cur(c).gb_import.ev1.get()));
-    return VCT_OK;
+    return vct_timer_ms(c, cur(c).gb_import.timer, ms, "vct_last_gbuffer_import_ms: no G-buffer import has run on this frame slot",
+                        "vct_last_gbuffer_import_ms: the last import was issued with timing off (vct_set_trace_timing)");
 }
 
 }  // extern "C"

@@ -12,15 +12,13 @@ namespace {
 // The buffers of the slot's VctPointQuery a query of these sizes needs.  They only grow; growing frees the old buffer,
 // which an earlier device-located query of this slot may still read or write, so the slot's stream is waited for first.
 int reserve_buffers(vct_ctx* c, VctPointQuery& Q, const VctQuerySizes& sz, bool host, bool sort, size_t n, size_t sort_bytes) {
-    const bool grow = !Q.ctr || !Q.ev0 || !Q.ev1 ||
+    const bool grow = !Q.ctr ||
                       (host && (sz.pts_floats > Q.pts.size() || sz.out_floats > Q.out.size() || sz.cones_floats > Q.out_cones.size() ||
                                 sz.steps_bytes > Q.out_steps.size())) ||
                       (sort && (2 * n > Q.keys.size() || 2 * n > Q.index.size() || sort_bytes > Q.sort_tmp.size()));
     if (!grow) return VCT_OK;
     HIP_TRY(c, hipStreamSynchronize(cur(c).stream.get()));
     if (!Q.ctr) HIP_TRY(c, Q.ctr.alloc(VCT_DR_COUNTERS));
-    if (!Q.ev0) HIP_TRY(c, Q.ev0.create());
-    if (!Q.ev1) HIP_TRY(c, Q.ev1.create());
     if (host) {
         HIP_TRY(c, Q.pts.reserve(sz.pts_floats));
         HIP_TRY(c, Q.out.reserve(sz.out_floats));
@@ -104,12 +102,10 @@ int run_query(vct_ctx* c, const char* who, int kind, const void* pts, int32_t n,
                                                                            VCT_QUERY_KEY_BITS, s)));
         q.index = index + n;
     }
-    if (c->time_traces) HIP_TRY(c, hipEventRecord(Q.ev0.get(), s));      // (vct_set_trace_timing)
+    HIP_TRY(c, Q.timer.begin(s, c->time_traces));
     HIP_TRY(c, vct_launch_query(p, q, kind, s));
-    if (c->time_traces) HIP_TRY(c, hipEventRecord(Q.ev1.get(), s));
+    HIP_TRY(c, Q.timer.end(s));
     c->last_march_form = c->fast_div ? 2 : 1;
-    Q.have = true;
-    Q.timed = c->time_traces;
     Q.sorted = sort;
     Q.n = (uint64_t)n;
     Q.kind = kind;
@@ -139,7 +135,7 @@ int vct_cone_points(vct_ctx* c, const vct_cone_point* pts, int32_t n, int32_t lo
 int vct_last_point_query(vct_ctx* c, uint64_t out[4]) {
     if (!c || !out) return VCT_ERR_INVALID;
     const VctPointQuery& Q = cur(c).query;
-    if (!Q.have) return vct_fail(c, VCT_ERR_INVALID, "vct_last_point_query: no point query has run on this frame slot");
+    if (!Q.timer.have) return vct_fail(c, VCT_ERR_INVALID, "vct_last_point_query: no point query has run on this frame slot");
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(cur(c).stream.get()));
     unsigned long long v[VCT_DR_COUNTERS];
@@ -155,13 +151,8 @@ int vct_last_point_query(vct_ctx* c, uint64_t out[4]) {
 
 int vct_last_point_query_ms(vct_ctx* c, float* ms) {
     if (!c || !ms) return VCT_ERR_INVALID;
-    const VctPointQuery& Q = cur(c).query;
-    if (!Q.have) return vct_fail(c, VCT_ERR_INVALID, "vct_last_point_query_ms: no point query has run on this frame slot");
-    if (!Q.timed)
-        return vct_fail(c, VCT_ERR_INVALID, "vct_last_point_query_ms: the last query was issued with timing off (vct_set_trace_timing)");
-    HIP_TRY(c, hipEventSynchronize(Q.ev1.get()));
-    HIP_TRY(c, hipEventElapsedTime(ms, Q.ev0.get(), Q.ev1.get()));
-    return VCT_OK;
+    return vct_timer_ms(c, cur(c).query.timer, ms, "vct_last_point_query_ms: no point query has run on this frame slot",
+                        "vct_last_point_query_ms: the last query was issued with timing off (vct_set_trace_timing)");
 }
 
 }  // extern "C"

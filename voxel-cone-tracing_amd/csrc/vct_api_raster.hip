@@ -274,13 +274,7 @@ int vct_render_gbuffer(vct_ctx* c, const float view_proj[16]) {
 int vct_download_gbuffer(vct_ctx* c, float* planes) {
     if (!c || !planes) return VCT_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t n = (size_t)c->cfg.width * c->cfg.height * VCT_GB_NPLANES;
-    PIPE_TRY(vct_staging_free(c));
-    HIP_TRY(c, c->gb_linear.reserve(n));
-    HIP_TRY(c, vct_launch_untile_gbuffer(cur(c).gb_current, c->gb_linear.get(), c->cfg.width, c->cfg.height, cur(c).stream.get()));
-    HIP_TRY(c, hipMemcpyAsync(planes, c->gb_linear.get(), n * sizeof(float), hipMemcpyDeviceToHost, cur(c).stream.get()));
-    HIP_TRY(c, hipStreamSynchronize(cur(c).stream.get()));
-    return VCT_OK;
+    return vct_planes_download(c, cur(c).gb_current, planes, VCT_GB_NPLANES, sizeof(float));
 }
 
 }  // extern "C"

@@ -22,12 +22,7 @@ int vct_set_sky(vct_ctx* c, const float sh[9][3]) {
         c->sky = VctSky();
         return VCT_OK;
     }
-    if (c->cfg.trace_variant != 0)
-        return vct_fail(c, VCT_ERR_INVALID, "vct_set_sky: config.trace_variant 1 .. 4 has no sky light");
-    if (c->cfg.anisotropic_mips)
-        return vct_fail(c, VCT_ERR_INVALID, "vct_set_sky: config.anisotropic_mips has no sky light");
-    if (c->vol.want_cells)
-        return vct_fail(c, VCT_ERR_INVALID, "vct_set_sky: footprint records are on (vct_set_footprint_records(ctx, 0) first)");
+    PIPE_TRY(vct_refuse_conflict(c, "vct_set_sky", VCT_FEAT_SKY, vct_rules_in_force(c).modes));
     float poly[VCT_SKY_FLOATS];
     vct_sky_fold(table, poly);
     PIPE_TRY(vct_synchronize(c));             // the coefficients about to be rewritten may still be read

@@ -246,6 +246,9 @@ int vct_launch_trace_rows(vct_ctx* c, int row0, int row1, uint16_t* out_base, in
     p.row_stride = row_stride;
     p.pack_rows = pack_rows ? 1 : 0;
     const int variant = c->cfg.trace_variant;
+    // what is attached against how this context traces (vct_feature_rules.h): the setters keep such a pair from coming about
+    const VctRulesInForce rules = vct_rules_in_force(c);
+    PIPE_TRY(vct_refuse_conflict(c, "trace", rules.features, rules.modes));
     const bool compacting = variant == 4 && !c->cfg.anisotropic_mips;      // variant 4 is in effect (it has no directional form)
     if ((row_stride > 1 || pack_rows) && !vct_variant_takes_row_subsets(variant))
         return vct_fail(c, VCT_ERR_INVALID, "interleaved tile rows need the default trace kernel (config.trace_variant 0 or 3)");
@@ -267,32 +270,23 @@ int vct_launch_trace_rows(vct_ctx* c, int row0, int row1, uint16_t* out_base, in
     bool half_march = false;
     // pixel-emission planes of the slot (include/vct.h "emissive materials"): the composite adds them, in the COMP kernel
     const float* pix_emis = cur(c).emis.get();
-    if (pix_emis && variant != 0)
-        return vct_fail(c, VCT_ERR_INVALID, "pixel-emission planes need the default trace kernel (config.trace_variant 0)");
     // local lights (include/vct.h "local lights"): the slot's lit planes -- filled below, right in front of the launch, with
     // E + Lit -- take the planes' place
     const float* lit = c->lights.n ? cur(c).lit.get() : nullptr;
-    if (lit && variant != 0)
-        return vct_fail(c, VCT_ERR_INVALID, "local lights need the default trace kernel (config.trace_variant 0)");
     const float* slot_emis = pix_emis;
     if (lit) pix_emis = lit;
     p.pix_emis = pix_emis;
     // gloss classes (include/vct.h "per-material gloss"): the slot's plane and the class tables, in the COMP kernel's
     // GLOSS form; config.shininess and the specular table are then not read by this launch
     const uint8_t* pix_gloss = c->gloss.n ? cur(c).gloss.get() : nullptr;
-    if (pix_gloss && (variant != 0 || c->cfg.anisotropic_mips || c->vol.want_cells))
-        return vct_fail(c, VCT_ERR_INVALID, "gloss classes need the default trace kernel (config.trace_variant 0, no anisotropic mips, no footprint records)");
     if (pix_gloss) { p.gloss = c->gloss.table.get(); p.pix_gloss = pix_gloss; }
     // sky light (include/vct.h "sky light"): the context's folded coefficients, in the COMP kernel's SKY form
     const float* sky = c->sky.dev();
-    if (sky && (variant != 0 || c->cfg.anisotropic_mips || c->vol.want_cells))
-        return vct_fail(c, VCT_ERR_INVALID, "sky light needs the default trace kernel (config.trace_variant 0, no anisotropic mips, no footprint records)");
     p.sky = sky;
     if (half) {
         if (row0 != 0 || row1 != vct_tiles_y(c) || row_stride > 1 || pack_rows)
             return vct_fail(c, VCT_ERR_INVALID, "trace: diffuse rate 2 traces whole frames only (no slabs, tile-row ranges or interleaved rows)");
-        if (variant != 0 || c->cfg.anisotropic_mips || c->vol.want_cells || c->comm || !cur(c).dr_ind)
-            return vct_fail(c, VCT_ERR_INVALID, "trace: diffuse rate 2 needs the default trace kernel on a single-GPU context");
+        if (!cur(c).dr_ind) return vct_fail(c, VCT_ERR_INVALID, "trace: diffuse rate 2 on a frame slot without its buffers");
         p.comp = component_word(c->show_mask, aov_which, pix_emis != nullptr);
         p.aov = aov_which ? cur(c).aov.get() : nullptr;
         half_march = ((p.comp >> VCT_COMP_GROUPS_SHIFT) & 1u) != 0u;
@@ -302,8 +296,6 @@ int vct_launch_trace_rows(vct_ctx* c, int row0, int row1, uint16_t* out_base, in
             p.dr_waves = c->diffuse_rate_waves;
         }
     } else if (c->show_mask != VCT_SHOW_ALL || aov_which || pix_emis || pix_gloss || sky) {
-        if (variant != 0)
-            return vct_fail(c, VCT_ERR_INVALID, "lighting components / per-component outputs need the default trace kernel (config.trace_variant 0)");
         p.comp = component_word(c->show_mask, aov_which, pix_emis != nullptr);
         p.aov = aov_which ? cur(c).aov.get() : nullptr;
     }
@@ -330,23 +322,19 @@ int vct_launch_trace_rows(vct_ctx* c, int row0, int row1, uint16_t* out_base, in
         la.nclasses = c->gloss.n;
         for (int k = 0; k < c->gloss.n; ++k) la.class_shininess[k] = c->gloss.cls[k].shininess;
         la.lit = cur(c).lit.get();
-        if (c->time_traces) HIP_TRY(c, hipEventRecord(cur(c).lit_ev0.get(), cur(c).stream.get()));
+        HIP_TRY(c, cur(c).lit_timer.begin(cur(c).stream.get(), c->time_traces));
         HIP_TRY(c, vct_launch_light_pixels(la, cur(c).stream.get()));
-        if (c->time_traces) HIP_TRY(c, hipEventRecord(cur(c).lit_ev1.get(), cur(c).stream.get()));
-        cur(c).have_lit = true;
-        cur(c).lit_timed = c->time_traces;
+        HIP_TRY(c, cur(c).lit_timer.end(cur(c).stream.get()));
     }
-    if (c->time_traces) HIP_TRY(c, hipEventRecord(cur(c).ev0.get(), cur(c).stream.get()));      // (vct_set_trace_timing)
+    HIP_TRY(c, cur(c).march.begin(cur(c).stream.get(), c->time_traces));      // (vct_set_trace_timing)
     const hipEvent_t marks[3] = {cur(c).dr_ev[0].get(), cur(c).dr_ev[1].get(), cur(c).dr_ev[2].get()};
     HIP_TRY(c, vct_launch_trace(p, variant, cur(c).stream.get(), &c->last_march_form,       // an empty row range (a rank without rows) launches nothing
                                 half_march && c->time_traces ? marks : nullptr));
-    if (c->time_traces) HIP_TRY(c, hipEventRecord(cur(c).ev1.get(), cur(c).stream.get()));
-    cur(c).last_trace_timed = c->time_traces;
+    HIP_TRY(c, cur(c).march.end(cur(c).stream.get()));
     cur(c).last_trace_half = half_march;
     cur(c).last_row0 = row0;
     cur(c).last_row1 = row1;
     cur(c).last_row_stride = rstride;
-    cur(c).have_trace = true;
     cur(c).last_was_screen_trace = true;
     cur(c).last_trace_compacted = compacting;
     return VCT_OK;
@@ -364,27 +352,12 @@ static int bind_gbuffer(vct_ctx* c, const vct_gbuffer* gb) {
     if (!gb || !gb->planes) return vct_fail(c, VCT_ERR_INVALID, "vct_trace: null G-buffer");
     if (gb->width != c->cfg.width || gb->height != c->cfg.height)
         return vct_fail(c, VCT_ERR_INVALID, "vct_trace: G-buffer size differs from the context's frame");
-    const size_t npix = (size_t)c->cfg.width * c->cfg.height;
-    if (gb->layout == VCT_GB_TILED) {
-        if (gb->location == VCT_MEM_DEVICE) {
-            cur(c).gb_current = gb->planes;     // zero-copy: trace reads the caller's HBM buffer
-        } else {
-            HIP_TRY(c, hipMemcpyAsync(cur(c).gb_tiled.get(), gb->planes, vct_gb_tiled_floats(c) * sizeof(float),
-                                      hipMemcpyHostToDevice, cur(c).stream.get()));
-            cur(c).gb_current = cur(c).gb_tiled.get();
-        }
+    if (gb->layout != VCT_GB_LINEAR && gb->layout != VCT_GB_TILED) return vct_fail(c, VCT_ERR_INVALID, "vct_trace: unknown G-buffer layout");
+    if (gb->layout == VCT_GB_TILED && gb->location == VCT_MEM_DEVICE) {
+        cur(c).gb_current = gb->planes;     // zero-copy: trace reads the caller's HBM buffer
         return VCT_OK;
     }
-    if (gb->layout != VCT_GB_LINEAR) return vct_fail(c, VCT_ERR_INVALID, "vct_trace: unknown G-buffer layout");
-    const float* src = gb->planes;
-    if (gb->location == VCT_MEM_HOST) {
-        PIPE_TRY(vct_staging_free(c));
-        HIP_TRY(c, c->gb_linear.reserve(npix * VCT_GB_NPLANES));
-        HIP_TRY(c, hipMemcpyAsync(c->gb_linear.get(), gb->planes, npix * VCT_GB_NPLANES * sizeof(float),
-                                  hipMemcpyHostToDevice, cur(c).stream.get()));
-        src = c->gb_linear.get();
-    }
-    HIP_TRY(c, vct_launch_tile_gbuffer(src, cur(c).gb_tiled.get(), c->cfg.width, c->cfg.height, cur(c).stream.get()));
+    PIPE_TRY(vct_planes_set(c, cur(c).gb_tiled.get(), gb->planes, gb->layout, gb->location, VCT_GB_NPLANES, sizeof(float)));
     cur(c).gb_current = cur(c).gb_tiled.get();
     return VCT_OK;
 }
@@ -599,7 +572,7 @@ int vct_get_stage_counts(vct_ctx* c, uint64_t out[8]) {
 
 int vct_last_step_count(vct_ctx* c, uint64_t* steps) {
     if (!c || !steps) return VCT_ERR_INVALID;
-    if (!cur(c).have_trace) return vct_fail(c, VCT_ERR_INVALID, "no trace has run");
+    if (!cur(c).march.have) return vct_fail(c, VCT_ERR_INVALID, "no trace has run");
     HIP_TRY(c, hipSetDevice(c->device));
     uint64_t sum = 0;
     if (cur(c).last_was_screen_trace) {
@@ -623,7 +596,7 @@ int vct_last_step_count(vct_ctx* c, uint64_t* steps) {
 
 int vct_last_row_steps(vct_ctx* c, uint64_t* rows, int32_t nrows) {
     if (!c || !rows) return VCT_ERR_INVALID;
-    if (!cur(c).have_trace || !cur(c).last_was_screen_trace)
+    if (!cur(c).march.have || !cur(c).last_was_screen_trace)
         return vct_fail(c, VCT_ERR_INVALID, "vct_last_row_steps: the last march was not a screen trace");
     if (nrows != vct_tiles_y(c)) return vct_fail(c, VCT_ERR_INVALID, "vct_last_row_steps: nrows must be the frame's tile rows, ceil(height / 8)");
     if (c->diffuse_rate == 2 || cur(c).last_trace_half)
@@ -641,7 +614,7 @@ int vct_last_row_steps(vct_ctx* c, uint64_t* rows, int32_t nrows) {
 int vct_last_trace_stats(vct_ctx* c, uint64_t out[32]) {
     if (!c || !out) return VCT_ERR_INVALID;
 #if defined(VCT_STATS) && VCT_STATS
-    if (!cur(c).have_trace) return vct_fail(c, VCT_ERR_INVALID, "no trace has run");
+    if (!cur(c).march.have) return vct_fail(c, VCT_ERR_INVALID, "no trace has run");
     HIP_TRY(c, hipStreamSynchronize(cur(c).stream.get()));
     HIP_TRY(c, hipMemcpy(out, c->stats.get(), 32 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return VCT_OK;
@@ -653,12 +626,7 @@ int vct_last_trace_stats(vct_ctx* c, uint64_t out[32]) {
 
 int vct_last_trace_ms(vct_ctx* c, float* ms) {
     if (!c || !ms) return VCT_ERR_INVALID;
-    if (!cur(c).have_trace) return vct_fail(c, VCT_ERR_INVALID, "no trace has run");
-    if (!cur(c).last_trace_timed)
-        return vct_fail(c, VCT_ERR_INVALID, "vct_last_trace_ms: the last trace was issued with timing off (vct_set_trace_timing)");
-    HIP_TRY(c, hipEventSynchronize(cur(c).ev1.get()));
-    HIP_TRY(c, hipEventElapsedTime(ms, cur(c).ev0.get(), cur(c).ev1.get()));
-    return VCT_OK;
+    return vct_timer_ms(c, cur(c).march, ms, "no trace has run", "vct_last_trace_ms: the last trace was issued with timing off (vct_set_trace_timing)");
 }
 
 int vct_selftest_const_divide(vct_ctx* c, float d, uint64_t* mismatches) {
@@ -722,10 +690,7 @@ int vct_set_aov_outputs(vct_ctx* c, uint32_t which) {
     if (!c) return VCT_ERR_INVALID;
     if (which & ~(uint32_t)(VCT_AOV_INDIRECT_DIFFUSE | VCT_AOV_INDIRECT_SPECULAR | VCT_AOV_DIRECT))
         return vct_fail(c, VCT_ERR_INVALID, "vct_set_aov_outputs: unknown output bits");
-    if (which && c->cfg.trace_variant != 0)
-        return vct_fail(c, VCT_ERR_INVALID, "vct_set_aov_outputs: config.trace_variant 1 .. 4 has no per-component outputs");
-    if (which && c->comm)
-        return vct_fail(c, VCT_ERR_INVALID, "vct_set_aov_outputs: a rank of a multi-GPU frame (per-component outputs are not gathered)");
+    if (which) PIPE_TRY(vct_refuse_conflict(c, "vct_set_aov_outputs", VCT_FEAT_AOV, vct_rules_in_force(c).modes));
     if (which == c->aov_which) return VCT_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     PIPE_TRY(vct_synchronize(c));            // the buffers being replaced may still be written
@@ -773,16 +738,7 @@ int vct_get_aov_device(vct_ctx* c, uint32_t bit, void** p, size_t* bytes) {
 int vct_set_diffuse_rate(vct_ctx* c, int32_t rate) {
     if (!c) return VCT_ERR_INVALID;
     if (rate != 1 && rate != 2) return vct_fail(c, VCT_ERR_INVALID, "vct_set_diffuse_rate: 1 or 2");
-    if (rate == 2) {
-        if (c->cfg.trace_variant != 0)
-            return vct_fail(c, VCT_ERR_INVALID, "vct_set_diffuse_rate: config.trace_variant 1 .. 4 has no half-rate diffuse gather");
-        if (c->cfg.anisotropic_mips)
-            return vct_fail(c, VCT_ERR_INVALID, "vct_set_diffuse_rate: config.anisotropic_mips has no half-rate diffuse gather");
-        if (c->vol.want_cells)
-            return vct_fail(c, VCT_ERR_INVALID, "vct_set_diffuse_rate: footprint records are on (vct_set_footprint_records(ctx, 0) first)");
-        if (c->comm)
-            return vct_fail(c, VCT_ERR_INVALID, "vct_set_diffuse_rate: a rank of a multi-GPU frame traces slabs (rate 2 traces whole frames only)");
-    }
+    if (rate == 2) PIPE_TRY(vct_refuse_conflict(c, "vct_set_diffuse_rate", VCT_FEAT_RATE2, vct_rules_in_force(c).modes));
     if (rate == c->diffuse_rate) return VCT_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     PIPE_TRY(vct_synchronize(c));            // buffers about to go may still be read
@@ -811,7 +767,7 @@ int vct_get_diffuse_rate(const vct_ctx* c, int32_t* rate, uint64_t* marched_pixe
     if (rate) *rate = c->diffuse_rate;
     if (marched_pixels) {
         *marched_pixels = 0;
-        if (cur(c).have_trace && cur(c).last_trace_half && cur(c).dr_ctr) {
+        if (cur(c).march.have && cur(c).last_trace_half && cur(c).dr_ctr) {
             std::vector<unsigned long long> v(VCT_DR_COUNTERS);
             hipError_t e = hipSetDevice(c->device);
             if (e == hipSuccess) e = hipStreamSynchronize(cur(c).stream.get());
@@ -826,12 +782,12 @@ int vct_get_diffuse_rate(const vct_ctx* c, int32_t* rate, uint64_t* marched_pixe
 
 int vct_last_diffuse_rate_ms(vct_ctx* c, float ms[4]) {
     if (!c || !ms) return VCT_ERR_INVALID;
-    if (!cur(c).have_trace || !cur(c).last_trace_half || !cur(c).last_was_screen_trace)
+    if (!cur(c).march.have || !cur(c).last_trace_half || !cur(c).last_was_screen_trace)
         return vct_fail(c, VCT_ERR_INVALID, "vct_last_diffuse_rate_ms: the last trace was no rate-2 pass that marched the diffuse group");
-    if (!cur(c).last_trace_timed)
+    if (!cur(c).march.timed)
         return vct_fail(c, VCT_ERR_INVALID, "vct_last_diffuse_rate_ms: the last trace was issued with timing off (vct_set_trace_timing)");
-    HIP_TRY(c, hipEventSynchronize(cur(c).ev1.get()));
-    const hipEvent_t ev[5] = {cur(c).ev0.get(), cur(c).dr_ev[0].get(), cur(c).dr_ev[1].get(), cur(c).dr_ev[2].get(), cur(c).ev1.get()};
+    HIP_TRY(c, hipEventSynchronize(cur(c).march.last()));
+    const hipEvent_t ev[5] = {cur(c).march.first(), cur(c).dr_ev[0].get(), cur(c).dr_ev[1].get(), cur(c).dr_ev[2].get(), cur(c).march.last()};
     for (int i = 0; i < 4; ++i) HIP_TRY(c, hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
     return VCT_OK;
 }

@@ -190,11 +190,9 @@ int vct_inject_light(vct_ctx* c) {
         la.V = c->cfg.voxel_dim; la.G = c->cfg.grid_world_size;
         la.level0 = c->vol.chain.get(); la.attr_albedo = v.attr_albedo.get(); la.attr_normal = v.attr_normal.get();
         la.slot_brick = v.slot_brick.get(); la.brick_prev = c->vol.brick_prev.get(); la.nslots = v.nslots;
-        if (c->time_traces) HIP_TRY(c, hipEventRecord(c->lights.ev0.get(), cur(c).stream.get()));      // (vct_set_trace_timing)
+        HIP_TRY(c, c->lights.vox_timer.begin(cur(c).stream.get(), c->time_traces));
         HIP_TRY(c, vct_launch_light_voxels(la, cur(c).stream.get()));
-        if (c->time_traces) HIP_TRY(c, hipEventRecord(c->lights.ev1.get(), cur(c).stream.get()));
-        c->lights.vox_have = true;
-        c->lights.vox_timed = c->time_traces;
+        HIP_TRY(c, c->lights.vox_timer.end(cur(c).stream.get()));
     }
     c->vox.acc_pending = false;
     c->vol.level0_resolved();
@@ -218,12 +216,7 @@ static int build_cells(vct_ctx* c) {
 
 int vct_set_footprint_records(vct_ctx* c, int32_t on) {
     if (!c) return VCT_ERR_INVALID;
-    if (on && c->diffuse_rate == 2)
-        return vct_fail(c, VCT_ERR_INVALID, "vct_set_footprint_records: the half-rate diffuse gather has no footprint-record kernels (vct_set_diffuse_rate(ctx, 1) first)");
-    if (on && c->gloss.n)
-        return vct_fail(c, VCT_ERR_INVALID, "vct_set_footprint_records: gloss classes have no footprint-record kernels (vct_set_gloss_classes(ctx, NULL, 0) first)");
-    if (on && c->sky.attached)
-        return vct_fail(c, VCT_ERR_INVALID, "vct_set_footprint_records: sky light has no footprint-record kernels (vct_set_sky(ctx, NULL) first)");
+    if (on) PIPE_TRY(vct_refuse_conflict(c, "vct_set_footprint_records", vct_rules_in_force(c).features, VCT_MODE_CELLS));
     HIP_TRY(c, hipSetDevice(c->device));
     c->vol.want_cells = on != 0;
     PIPE_TRY(vct_pipeline_drain(c));
@@ -301,10 +294,9 @@ int vct_bounce(vct_ctx* c) {
     p.bounce_list_cap = (uint32_t)(c->bounce_list.size() - 1);
     p.brick_over = c->brick_over.get();
     HIP_TRY(c, hipMemsetAsync(c->step_counter.get(), 0, VCT_STEP_COUNTERS * sizeof(unsigned long long), cur(c).stream.get()));
-    if (c->time_traces) HIP_TRY(c, hipEventRecord(cur(c).ev0.get(), cur(c).stream.get()));
+    HIP_TRY(c, cur(c).march.begin(cur(c).stream.get(), c->time_traces));
     HIP_TRY(c, vct_launch_bounce(p, cur(c).stream.get()));
-    if (c->time_traces) HIP_TRY(c, hipEventRecord(cur(c).ev1.get(), cur(c).stream.get()));
-    cur(c).last_trace_timed = c->time_traces;
+    HIP_TRY(c, cur(c).march.end(cur(c).stream.get()));      // step counter / event pair now describe the bounce launch
     c->last_march_form = c->fast_div ? 2 : 1;
     HIP_TRY(c, vct_launch_build_mips(c->vol.chain_b.get(), c->cfg.voxel_dim, b_sparse ? c->vol.brick_prev.get() : nullptr,
                                      b_sparse ? c->vol.mip_seen_b.get() : nullptr, cur(c).stream.get()));
@@ -312,7 +304,6 @@ int vct_bounce(vct_ctx* c) {
     // from the isotropic bounce-0 chain, like the oracle's vcto_bounce)
     if (c->vol.aniso) HIP_TRY(c, vct_launch_build_mips_aniso(c->vol.chain_b.get(), c->vol.aniso.get(), c->cfg.voxel_dim, cur(c).stream.get()));
     c->vol.bounce_done();
-    cur(c).have_trace = true;      // step counter / event pair now describe the bounce launch
     cur(c).last_was_screen_trace = false;
     return VCT_OK;
 }

@@ -59,26 +59,16 @@ int vct_render_voxels(vct_ctx* c, const float inv_view_proj[16], int32_t source,
             s.vv_gen = c->vol.gen;
         }
     }
-    if (c->time_traces) {
-        if (!s.vv_ev0) HIP_TRY(c, s.vv_ev0.create());
-        if (!s.vv_ev1) HIP_TRY(c, s.vv_ev1.create());
-        HIP_TRY(c, hipEventRecord(s.vv_ev0.get(), s.stream.get()));
-    }
+    HIP_TRY(c, s.vv_timer.begin(s.stream.get(), c->time_traces));
     HIP_TRY(c, vct_launch_voxview(p, skip, s.stream.get()));
-    if (c->time_traces) HIP_TRY(c, hipEventRecord(s.vv_ev1.get(), s.stream.get()));
-    s.have_view = true;
-    s.last_view_timed = c->time_traces;
+    HIP_TRY(c, s.vv_timer.end(s.stream.get()));
     return VCT_OK;
 }
 
 int vct_last_voxel_view_ms(vct_ctx* c, float* ms) {
     if (!c || !ms) return VCT_ERR_INVALID;
-    if (!cur(c).have_view) return vct_fail(c, VCT_ERR_INVALID, "vct_last_voxel_view_ms: no voxel view has run on this frame slot");
-    if (!cur(c).last_view_timed)
-        return vct_fail(c, VCT_ERR_INVALID, "vct_last_voxel_view_ms: the last view was issued with timing off (vct_set_trace_timing)");
-    HIP_TRY(c, hipEventSynchronize(cur(c).vv_ev1.get()));
-    HIP_TRY(c, hipEventElapsedTime(ms, cur(c).vv_ev0.get(), cur(c).vv_ev1.get()));
-    return VCT_OK;
+    return vct_timer_ms(c, cur(c).vv_timer, ms, "vct_last_voxel_view_ms: no voxel view has run on this frame slot",
+                        "vct_last_voxel_view_ms: the last view was issued with timing off (vct_set_trace_timing)");
 }
 
 }  // extern "C"

@@ -50,8 +50,7 @@ hipError_t slot_create(vct_ctx* c, VctFrameSlot& s, hipStream_t stream) {
     const size_t npix = (size_t)c->cfg.width * c->cfg.height, nt = (size_t)vct_tiles_x(c) * vct_tiles_y(c);
     const size_t aov_halves = vct_aov_frames(c->aov_which) * npix * 4;
     s.stream.adopt(stream);
-    hipError_t e = s.ev0.create();
-    if (e == hipSuccess) e = s.ev1.create();
+    hipError_t e = s.march.create();      // (no frame loop allocates them)
     if (e == hipSuccess) e = s.gb_tiled.alloc(vct_gb_tiled_floats(c));
     if (e == hipSuccess) e = s.frame.alloc(npix * 4);
     if (e == hipSuccess) e = s.tile_steps.alloc(nt);
@@ -230,6 +229,48 @@ int vct_staging_free(vct_ctx* c) {
     return VCT_OK;
 }
 
+int vct_timer_ms(vct_ctx* c, const VctTimer& t, float* ms, const char* never, const char* untimed) {
+    hipError_t e = hipSuccess;
+    switch (t.elapsed(ms, &e)) {
+        case VctTimer::NEVER: return vct_fail(c, VCT_ERR_INVALID, never);
+        case VctTimer::UNTIMED: return vct_fail(c, VCT_ERR_INVALID, untimed);
+        case VctTimer::FAILED: return vct_fail(c, VCT_ERR_DEVICE, std::string("timing events: ") + hipGetErrorString(e));
+        default: return VCT_OK;
+    }
+}
+
+VctRulesInForce vct_rules_in_force(const vct_ctx* c) {
+    VctRulesInForce r = {0u, 0u};
+    if (c->show_mask != VCT_SHOW_ALL) r.features |= VCT_FEAT_MASK;
+    if (c->aov_which) r.features |= VCT_FEAT_AOV;
+    if (c->diffuse_rate == 2) r.features |= VCT_FEAT_RATE2;
+    if (c->slots[0].emis || c->slots[1].emis) r.features |= VCT_FEAT_EMISSION;
+    if (c->gloss.n) r.features |= VCT_FEAT_GLOSS;
+    if (c->sky.attached) r.features |= VCT_FEAT_SKY;
+    if (c->lights.n) r.features |= VCT_FEAT_LIGHTS;
+    if (c->frames_in_flight > 1) r.features |= VCT_FEAT_TWO_FRAMES;
+    if (c->cfg.trace_variant != 0) r.modes |= VCT_MODE_VARIANT;
+    if (c->cfg.anisotropic_mips) r.modes |= VCT_MODE_ANISO;
+    if (c->vol.want_cells) r.modes |= VCT_MODE_CELLS;
+    if (c->comm) r.modes |= VCT_MODE_COMM;
+    if (c->cfg.debug_outputs) r.modes |= VCT_MODE_DEBUG;
+    if (c->cfg.trace_variant == 4) r.modes |= VCT_MODE_VARIANT4;
+#if defined(VCT_STATS) && VCT_STATS
+    r.modes |= VCT_MODE_STATS;
+#endif
+    return r;
+}
+
+int vct_refuse_conflict(vct_ctx* c, const char* who, unsigned features, unsigned modes) {
+    const VctConflict hit = vct_rule_conflict(features, modes);
+    if (!hit) return VCT_OK;
+    const VctRuleText& f = kVctFeatureText[vct_rule_bit_index(hit.feature)];
+    const VctRuleText& m = kVctModeText[vct_rule_bit_index(hit.mode)];
+    std::string msg = std::string(who) + ": " + f.name + " and " + m.name + " do not go together (" + f.lift;
+    if (m.lift) msg += std::string(", or ") + m.lift;
+    return vct_fail(c, VCT_ERR_INVALID, msg + " lifts it)");
+}
+
 hipError_t vct_create_masked_stream(hipStream_t* s, int device, int first_cu, int last_cu) {
     hipDeviceProp_t prop;
     hipError_t e = hipGetDeviceProperties(&prop, device);
@@ -343,20 +384,8 @@ int vct_set_cone_apertures(vct_ctx* c, float td, float ts) {
 int vct_set_trace_variant(vct_ctx* c, int32_t variant) {
     if (!c) return VCT_ERR_INVALID;
     if (variant < 0 || variant > 4) return vct_fail(c, VCT_ERR_INVALID, "vct_set_trace_variant: 0 .. 4");
-    if (variant == 4 && c->frames_in_flight > 1)
-        return vct_fail(c, VCT_ERR_INVALID, "vct_set_trace_variant: variant 4 keeps per-context scratch (vct_set_frames_in_flight(ctx, 1) first)");
-    if (variant != 0 && (c->show_mask != VCT_SHOW_ALL || c->aov_which))
-        return vct_fail(c, VCT_ERR_INVALID, "vct_set_trace_variant: variants 1 .. 4 have no lighting components (mask VCT_SHOW_ALL, no outputs first)");
-    if (variant != 0 && c->diffuse_rate == 2)
-        return vct_fail(c, VCT_ERR_INVALID, "vct_set_trace_variant: variants 1 .. 4 have no half-rate diffuse gather (vct_set_diffuse_rate(ctx, 1) first)");
-    if (variant != 0 && (c->slots[0].emis || c->slots[1].emis))
-        return vct_fail(c, VCT_ERR_INVALID, "vct_set_trace_variant: variants 1 .. 4 have no pixel-emission planes (detach the emission first)");
-    if (variant != 0 && c->gloss.n)
-        return vct_fail(c, VCT_ERR_INVALID, "vct_set_trace_variant: variants 1 .. 4 have no gloss classes (vct_set_gloss_classes(ctx, NULL, 0) first)");
-    if (variant != 0 && c->sky.attached)
-        return vct_fail(c, VCT_ERR_INVALID, "vct_set_trace_variant: variants 1 .. 4 have no sky light (vct_set_sky(ctx, NULL) first)");
-    if (variant != 0 && c->lights.n)
-        return vct_fail(c, VCT_ERR_INVALID, "vct_set_trace_variant: variants 1 .. 4 have no local lights (vct_set_lights(ctx, NULL, 0) first)");
+    PIPE_TRY(vct_refuse_conflict(c, "vct_set_trace_variant", vct_rules_in_force(c).features,
+                                 (variant != 0 ? VCT_MODE_VARIANT : 0u) | (variant == 4 ? VCT_MODE_VARIANT4 : 0u)));
     c->cfg.trace_variant = variant;
     return VCT_OK;
 }
@@ -373,13 +402,7 @@ int vct_set_frames_in_flight(vct_ctx* c, int32_t n) {
     if (!c) return VCT_ERR_INVALID;
     if (n != 1 && n != 2) return vct_fail(c, VCT_ERR_INVALID, "vct_set_frames_in_flight: 1 or 2");
     if (n == c->frames_in_flight) return VCT_OK;
-    if (n == 2) {
-        if (c->cfg.debug_outputs || c->cfg.trace_variant == 4)
-            return vct_fail(c, VCT_ERR_INVALID, "vct_set_frames_in_flight: debug_outputs and trace_variant 4 keep per-context scratch: one frame at a time");
-#if defined(VCT_STATS) && VCT_STATS
-        return vct_fail(c, VCT_ERR_INVALID, "vct_set_frames_in_flight: instrumented build (VCT_STATS): one frame at a time");
-#endif
-    }
+    if (n == 2) PIPE_TRY(vct_refuse_conflict(c, "vct_set_frames_in_flight", VCT_FEAT_TWO_FRAMES, vct_rules_in_force(c).modes));
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->comm) PIPE_TRY(vct_comm_sync(c));      // (deadline-bounded: a frame step in flight may wait for a peer)
     PIPE_TRY(vct_synchronize(c));
@@ -446,8 +469,7 @@ int vct_get_stream(vct_ctx* c, void** s) {
 int vct_set_lighting_components(vct_ctx* c, uint32_t mask) {
     if (!c) return VCT_ERR_INVALID;
     if (mask & ~(uint32_t)VCT_SHOW_ALL) return vct_fail(c, VCT_ERR_INVALID, "vct_set_lighting_components: bits above VCT_SHOW_ALL");
-    if (mask != VCT_SHOW_ALL && c->cfg.trace_variant != 0)
-        return vct_fail(c, VCT_ERR_INVALID, "vct_set_lighting_components: config.trace_variant 1 .. 4 has no lighting components");
+    if (mask != VCT_SHOW_ALL) PIPE_TRY(vct_refuse_conflict(c, "vct_set_lighting_components", VCT_FEAT_MASK, vct_rules_in_force(c).modes));
     c->show_mask = mask;
     return VCT_OK;
 }

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/vct.h"
+#include "vct_feature_rules.h"
 #include "vct_internal.h"
 #include "vct_lights_check.h"
 
@@ -94,6 +95,45 @@ public:
 using VctEvent = VctHandle<hipEvent_t, hipEventCreateWithFlags, hipEventDestroy>;
 using VctStream = VctHandle<hipStream_t, hipStreamCreateWithFlags, hipStreamDestroy>;
 
+// The two events around a launch that vct_set_trace_timing decides to time or not, and what the matching vct_last_*_ms
+// may say about them.  begin / end go around the launch on its stream; with timing off they record nothing (an event
+// costs a launch ~7 us of dispatch gaps).  Assigning a fresh VctTimer forgets the result and frees the events.
+struct VctTimer {
+    bool have = false;                  // a launch has run between begin and end
+    bool timed = false;                 // ... the last one with timing on: the events bracket it
+
+    hipError_t create() {               // the events now, so that no later begin allocates
+        hipError_t e = ev0_ ? hipSuccess : ev0_.create();
+        if (e == hipSuccess && !ev1_) e = ev1_.create();
+        return e;
+    }
+    hipError_t begin(hipStream_t s, bool on) {
+        on_ = on;
+        if (!on) return hipSuccess;
+        const hipError_t e = create();
+        return e == hipSuccess ? hipEventRecord(ev0_.get(), s) : e;
+    }
+    hipError_t end(hipStream_t s) {
+        const hipError_t e = on_ ? hipEventRecord(ev1_.get(), s) : hipSuccess;
+        if (e == hipSuccess) { have = true; timed = on_; }
+        return e;
+    }
+    enum Verdict { OK = 0, NEVER, UNTIMED, FAILED };      // FAILED: a HIP error, in *err
+    Verdict elapsed(float* ms, hipError_t* err) const {   // waits for the second event
+        if (!have) return NEVER;
+        if (!timed) return UNTIMED;
+        *err = hipEventSynchronize(ev1_.get());
+        if (*err == hipSuccess) *err = hipEventElapsedTime(ms, ev0_.get(), ev1_.get());
+        return *err == hipSuccess ? OK : FAILED;
+    }
+    hipEvent_t first() const { return ev0_.get(); }       // (vct_last_diffuse_rate_ms reads the marks between them)
+    hipEvent_t last() const { return ev1_.get(); }
+
+private:
+    VctEvent ev0_, ev1_;
+    bool on_ = false;                   // what the pending begin was given
+};
+
 // Scratch of one kind of raster pass (vct_api_raster.hip raster_args).  Between passes every visibility word is all-ones and
 // the counter set of the next pass is zero: the kernels re-establish both themselves (vct_raster.hip run_visibility), so
 // a pass launches no memset.  `dirty` (a launch failed, or nothing is initialised yet) makes the next pass clear
@@ -131,8 +171,8 @@ struct VctPointQuery {
     VctBuf<uint32_t> keys, index;       // VCT_QUERY_SORT_CELLS: two (key, index) buffer pairs of the radix sort, [2][n] each
     VctBuf<char> sort_tmp;              // the device sort's temporary storage
     VctBuf<unsigned long long> ctr;     // [VCT_DR_COUNTERS] executed steps of the last query (zeroed by its launch)
-    VctEvent ev0, ev1;                  // around the march kernel (vct_last_point_query_ms)
-    bool have = false, timed = false, sorted = false;
+    VctTimer timer;                     // around the march kernel (vct_last_point_query_ms)
+    bool sorted = false;
     uint64_t n = 0;
     int kind = 0;
 };
@@ -143,8 +183,7 @@ struct VctPointQuery {
 // returns only when the stream has passed its kernel, so the staging is free again at every entry.
 struct VctGBufferImport {
     VctBuf<char> stage;
-    VctEvent ev0, ev1;                  // around k_gbuffer_import (vct_last_gbuffer_import_ms)
-    bool have = false, timed = false;
+    VctTimer timer;                     // around k_gbuffer_import (vct_last_gbuffer_import_ms)
 };
 
 // Two frames in flight (vct_set_frames_in_flight, round 6).  A whole-frame trace launch pays ~20 us of ramp and drain
@@ -159,7 +198,7 @@ struct VctGBufferImport {
 // other stream wait for that stage.  Slot 0's stream is the context's stream.
 struct VctFrameSlot {
     VctStream stream;
-    VctEvent ev0, ev1;                  // timing events of the march launches (vct_last_trace_ms)
+    VctTimer march;                     // around the march launches, a screen trace's or a bounce's (vct_last_trace_ms); `have`: one has run
     VctBuf<float> gb_tiled;             // [tiles][23][64]
     const float* gb_current = nullptr;  // tiled buffer the next resident trace reads: gb_tiled or the caller's (not owned)
     VctBuf<uint16_t> frame;             // RGBA16F [h][w][4]
@@ -177,8 +216,7 @@ struct VctFrameSlot {
     // lit planes (include/vct.h "local lights"), tiled [tiles][3][64]: present while lights are attached; every composite
     // launch fills the rows it takes (k_light_pixels) and passes them in the place of the pixel-emission planes
     VctBuf<float> lit;
-    VctEvent lit_ev0, lit_ev1;          // around k_light_pixels (vct_last_lights_ms [1])
-    bool have_lit = false, lit_timed = false;      // a launch has filled them; ... bracketed by the timing events
+    VctTimer lit_timer;                 // around k_light_pixels (vct_last_lights_ms [1]); `have`: a launch has filled the planes
     // half-rate diffuse gather (vct_set_diffuse_rate(ctx, 2); vct_internal.h VctTraceParams::dr_*), present at rate 2 only
     VctBuf<float4> dr_ind;              // [h][w]
     VctBuf<float4> dr_coarse;           // [ch][cw]
@@ -189,8 +227,6 @@ struct VctFrameSlot {
     bool last_trace_half = false;       // the last screen trace was a half-rate pass: dr_ctr holds its marches' counts
     int last_row0 = 0, last_row1 = 0;
     int last_row_stride = 1;            // the last screen trace took every last_row_stride-th tile row of [last_row0, last_row1)
-    bool have_trace = false;
-    bool last_trace_timed = false;      // the last march launch was bracketed by the timing events
     bool last_trace_compacted = false;  // ... of trace_variant 4: counts per virtual tile, no per-row histogram
     bool last_was_screen_trace = false; // the step counters hold a screen trace (indexed by tile row), not a bounce
     bool have_gbuffer = false;          // a G-buffer is resident (uploaded by vct_trace or rendered)
@@ -199,8 +235,7 @@ struct VctFrameSlot {
     VctBuf<unsigned long long> vv_occ;
     const uint32_t* vv_texels = nullptr;
     uint64_t vv_gen = 0;
-    VctEvent vv_ev0, vv_ev1;            // timing events of the view's walk (vct_last_voxel_view_ms)
-    bool have_view = false, last_view_timed = false;
+    VctTimer vv_timer;                  // around the view's walk (vct_last_voxel_view_ms)
     VctRasterScratch raster;            // the main draw's
     VctPointQuery query;                // point queries issued on this slot
     VctGBufferImport gb_import;         // G-buffer imports issued on this slot
@@ -403,8 +438,7 @@ struct VctLights {
     int n = 0;
     vct_light given[VCT_LIGHTS_MAX] = {};
     VctBuf<VctLightDev> table;        // [VCT_LIGHTS_MAX]
-    VctEvent ev0, ev1;                // around k_light_voxels (vct_last_lights_ms [0])
-    bool vox_have = false, vox_timed = false;
+    VctTimer vox_timer;               // around k_light_voxels (vct_last_lights_ms [0])
 };
 
 struct vct_ctx {
@@ -485,6 +519,33 @@ int vct_pipeline_drain(vct_ctx* c);
 // tile kernel reading it.  Only a host-located linear hand-over or a download pays this (a volume upload drains the pipeline
 // anyway); with one slot it does nothing.
 int vct_staging_free(vct_ctx* c);
+// *ms of a timer for a vct_last_*_ms getter, or the getter's refusal: `never` / `untimed` are its words for a timer that
+// never ran / whose last launch was issued with timing off
+int vct_timer_ms(vct_ctx* c, const VctTimer& t, float* ms, const char* never, const char* untimed);
+// vct_feature_rules.h on a context: the features and modes in force, gathered in this one place; and the refusal of the
+// first pair of the matrix among `features` x `modes` (VCT_OK: none), in the name of the entry point `who`.  A feature's
+// setter asks with its feature against the modes in force, a mode's setter with the features in force against its mode,
+// a launch with both as they are.
+struct VctRulesInForce { unsigned features, modes; };
+VctRulesInForce vct_rules_in_force(const vct_ctx* c);
+int vct_refuse_conflict(vct_ctx* c, const char* who, unsigned features, unsigned modes);
+// vct_planes.hip -- what the per-pixel side planes of a frame slot (VctFrameSlot::emis, gloss, lit) do the same way.
+// Each kind has a function that gives a slot zeroed planes on its stream if it has none (*fresh, if given, is set when it
+// had none: vct_emission_planes, vct_gloss_plane, vct_lights_planes below) and one that takes them away again.
+typedef hipError_t VctPlanesEnsure(const vct_ctx* c, VctFrameSlot& s, bool* fresh);
+typedef void VctPlanesDrop(VctFrameSlot& s);
+// a zeroed tiled buffer of n elements on stream s for a `b` that is empty; a failure leaves it empty
+template <class T>
+hipError_t vct_planes_ensure(VctBuf<T>& b, size_t n, hipStream_t s, bool* fresh = nullptr);
+// Planes for every live slot, all or nothing, after the caller's own allocations gave `e`: each slot's stream is waited
+// for; a failure drops the planes this call created, sets the error in the name of `who` and returns its code.
+int vct_planes_attach(vct_ctx* c, const char* who, VctPlanesEnsure* ensure, VctPlanesDrop* drop, hipError_t e = hipSuccess);
+// The caller's planes `src` (nplanes of elem-byte elements; layout VCT_GB_LINEAR / _TILED, location VCT_MEM_HOST /
+// _DEVICE, both checked by the caller) into the tiled buffer `tiled` of the selected slot, on its stream; host memory is
+// free again on return.  A linear host array passes through c->gb_linear.
+int vct_planes_set(vct_ctx* c, void* tiled, const void* src, int32_t layout, int32_t location, int nplanes, size_t elem);
+// a tiled buffer of the selected slot as linear planes into host memory, through c->gb_linear; synchronous
+int vct_planes_download(vct_ctx* c, const void* tiled, void* out, int nplanes, size_t elem);
 // vct_api_scene.hip: textures are used once both the maps and the texture coordinates are there
 VctTextures vct_textures_of(const vct_ctx* c);
 // vct_api_raster.hip: `shadow_ready` not null: the visibility raster is issued at once, only the shading kernel (it reads the shadow map) waits for it
@@ -500,14 +561,14 @@ void vct_fill_march_params(const vct_ctx* c, VctTraceParams& p, const uint32_t* 
 // asynchronous, on the slot's stream.  row_stride > 1: only every row_stride-th tile row from row0 on; pack_rows: those rows back to back in out_base (interleaved slabs)
 int vct_launch_trace_rows(vct_ctx* c, int row0, int row1, uint16_t* out_base = nullptr, int row_stride = 1, bool pack_rows = false);
 // vct_api_emission.hip: drops the material emission table, its pool and the planes it attached (a new mesh, a NULL or all-zero
-// table); zeroed pixel-emission planes for a slot that has none, on the slot's stream
+// table); zeroed pixel-emission planes for a slot that has none (vct_planes_ensure)
 void vct_emission_detach(vct_ctx* c);
-hipError_t vct_emission_planes(const vct_ctx* c, VctFrameSlot& s);
-// vct_api_gloss.hip: a zeroed pixel-gloss plane for a slot that has none, on the slot's stream; drops the material map (a new mesh)
-hipError_t vct_gloss_plane(const vct_ctx* c, VctFrameSlot& s);
+hipError_t vct_emission_planes(const vct_ctx* c, VctFrameSlot& s, bool* fresh = nullptr);
+// vct_api_gloss.hip: a zeroed pixel-gloss plane for a slot that has none; drops the material map (a new mesh)
+hipError_t vct_gloss_plane(const vct_ctx* c, VctFrameSlot& s, bool* fresh = nullptr);
 void vct_material_gloss_detach(vct_ctx* c);
-// vct_api_lights.hip: zeroed lit planes and their timing events for a slot that has none, on the slot's stream
-hipError_t vct_lights_planes(const vct_ctx* c, VctFrameSlot& s);
+// vct_api_lights.hip: zeroed lit planes for a slot that has none, the timer around their kernel started over
+hipError_t vct_lights_planes(const vct_ctx* c, VctFrameSlot& s, bool* fresh = nullptr);
 // vct_multi.hip: slab of the attached communicator (false: none attached); its release
 bool vct_comm_rows(const vct_ctx* c, int* row0, int* row1);
 void vct_comm_release(vct_ctx* c);

@@ -511,14 +511,12 @@ hipError_t vct_launch_gbuffer_shade(const VctRasterArgs& a, const float view_pro
 // one level of a texture's mip chain from its parent (pw x ph -> w x h), glGenerateMipmap restated as in the oracle
 hipError_t vct_launch_tri_alpha(const VctRasterArgs& a, int32_t* out, hipStream_t s);
 hipError_t vct_launch_tex_mip(const uint32_t* parent, int pw, int ph, uint32_t* level, int w, int h, hipStream_t s);
-hipError_t vct_launch_untile_gbuffer(const float* tiled, float* planes_linear, int w, int h, hipStream_t s);
-// the same for the three pixel-emission planes: tiled [tile][3][64] <-> linear [3][h*w]
+// vct_planes.hip: linear planes [nplanes][h*w] <-> tiled [tile][nplanes][64] of `elem`-byte elements (pixels outside the
+// frame are tiled as 0), for the kinds of planes a frame slot has: 23 floats (the G-buffer), 3 floats (pixel-emission and
+// lit planes), 1 byte (the pixel-gloss plane); any other kind is hipErrorInvalidValue
 #define VCT_EMIS_NPLANES 3
-hipError_t vct_launch_untile_emission(const float* tiled, float* planes_linear, int w, int h, hipStream_t s);
-hipError_t vct_launch_tile_emission(const float* planes_linear, float* tiled, int w, int h, hipStream_t s);
-// the one-byte pixel-gloss plane: tiled [tile][64] <-> linear [h*w] (pixels outside the frame are tiled as 0)
-hipError_t vct_launch_untile_gloss(const uint8_t* tiled, uint8_t* linear, int w, int h, hipStream_t s);
-hipError_t vct_launch_tile_gloss(const uint8_t* linear, uint8_t* tiled, int w, int h, hipStream_t s);
+hipError_t vct_launch_tile_planes(const void* linear, void* tiled, int nplanes, size_t elem, int w, int h, hipStream_t s);
+hipError_t vct_launch_untile_planes(const void* tiled, void* linear, int nplanes, size_t elem, int w, int h, hipStream_t s);
 // strided (row_stride > 1) and packed tile rows are read by k_trace_tile_split's own tiles only: not by the one-wave
 // kernel (variants 1, 2) nor by the compaction's virtual tiles (4)
 static inline bool vct_variant_takes_row_subsets(int variant) { return variant == 0 || variant == 3; }
@@ -537,8 +535,6 @@ hipError_t vct_launch_build_mips(uint32_t* chain, int V, const uint32_t* bricks_
                                  hipStream_t s);
 hipError_t vct_launch_build_mips_aniso(const uint32_t* level0, uint32_t* aniso, int V, hipStream_t s);
 hipError_t vct_launch_build_cells(const uint32_t* chain, uint4* cells, int V, hipStream_t s);
-hipError_t vct_launch_tile_gbuffer(const float* planes_linear, float* tiled, int w, int h,
-                                   hipStream_t s);
 // fragment list of the conservative voxelizer, built at upload: small triangles (+ the list of the big ones), big
 // triangles, then the counting sort by brick slot
 hipError_t vct_launch_vox_plan(const VctVoxParams& p, uint32_t* plan, uint2* frags,

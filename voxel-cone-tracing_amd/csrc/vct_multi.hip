@@ -420,8 +420,7 @@ int vct_comm_init(vct_ctx* c, const void* id128, int32_t rank, int32_t world) {
     if (!c) return VCT_ERR_INVALID;
     if (!id128 || world <= 0 || rank < 0 || rank >= world) return vct_fail(c, VCT_ERR_INVALID, "vct_comm_init: bad rank / world / id");
     if (c->comm) return vct_fail(c, VCT_ERR_INVALID, "vct_comm_init: already initialised (vct_comm_destroy first)");
-    if (c->aov_which) return vct_fail(c, VCT_ERR_INVALID, "vct_comm_init: per-component outputs are on (they are not gathered)");
-    if (c->diffuse_rate == 2) return vct_fail(c, VCT_ERR_INVALID, "vct_comm_init: diffuse rate 2 traces whole frames only (vct_set_diffuse_rate(ctx, 1) first)");
+    PIPE_TRY(vct_refuse_conflict(c, "vct_comm_init", vct_rules_in_force(c).features, VCT_MODE_COMM));
     const bool direct = direct_mode();
     Rccl* r = direct ? nullptr : rccl();
     if (r && !r->err.empty()) return vct_fail(c, VCT_ERR_DEVICE, r->err);

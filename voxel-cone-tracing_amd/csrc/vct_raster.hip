@@ -1960,23 +1960,6 @@ k_tex_mip(const uint32_t* __restrict__ parent, int pw, int ph, uint32_t* __restr
     }
 }
 
-// tiled [tile][23][64] -> linear planes [23][h*w] (downloads / tests)
-template <int NPLANES>      // 23: the G-buffer; 3: the pixel-emission planes
-__global__ void k_untile_gbuffer(const float* __restrict__ tiled, float* __restrict__ planes, int w, int h,
-                                 int tiles_x) {
-    const size_t npix = (size_t)w * h;
-    const size_t total = npix * NPLANES;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (size_t)gridDim.x * blockDim.x) {
-        const int plane = (int)(i / npix);
-        const size_t pix = i - (size_t)plane * npix;
-        const int y = (int)(pix / w), x = (int)(pix - (size_t)y * w);
-        const size_t tile = (size_t)(y / VCT_TILE) * tiles_x + x / VCT_TILE;
-        const int lane = (y % VCT_TILE) * VCT_TILE + (x % VCT_TILE);
-        planes[i] = tiled[(tile * NPLANES + plane) * VCT_TILE_PIX + lane];
-    }
-}
-
 RasterParams make_raster(const VctRasterArgs& a, const float vp[16], int W, int H, int ys0, int ys1) {
     RasterParams r;
     r.ys0 = ys0 < 0 ? 0 : ys0;
@@ -2201,18 +2184,6 @@ hipError_t vct_launch_tex_mip(const uint32_t* parent, int pw, int ph, uint32_t* 
     const size_t n = (size_t)w * h;
     const unsigned blocks = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
     hipLaunchKernelGGL(k_tex_mip, dim3(blocks ? blocks : 1u), dim3(256), 0, s, parent, pw, ph, level, w, h);
-    return hipGetLastError();
-}
-
-hipError_t vct_launch_untile_gbuffer(const float* tiled, float* planes_linear, int w, int h, hipStream_t s) {
-    const int tx = (w + VCT_TILE - 1) / VCT_TILE;
-    hipLaunchKernelGGL(k_untile_gbuffer<VCT_GB_NPLANES>, dim3(256 * 8), dim3(256), 0, s, tiled, planes_linear, w, h, tx);
-    return hipGetLastError();
-}
-
-hipError_t vct_launch_untile_emission(const float* tiled, float* planes_linear, int w, int h, hipStream_t s) {
-    const int tx = (w + VCT_TILE - 1) / VCT_TILE;
-    hipLaunchKernelGGL(k_untile_gbuffer<VCT_EMIS_NPLANES>, dim3(256 * 8), dim3(256), 0, s, tiled, planes_linear, w, h, tx);
     return hipGetLastError();
 }
 

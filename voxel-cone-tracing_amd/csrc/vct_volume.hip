@@ -165,46 +165,6 @@ k_mip_aniso(const uint32_t* __restrict__ level0, uint32_t* __restrict__ aniso, u
     }
 }
 
-// planes [23][h*w] -> tiled [tile][23][64]; pixels outside the frame are zero (albedo.a = 0).
-template <int NPLANES>      // 23: the G-buffer; 3: the pixel-emission planes
-__global__ void k_tile_gbuffer(const float* __restrict__ planes, float* __restrict__ tiled, int w,
-                               int h, int tiles_x, int tiles_y) {
-    const size_t total = (size_t)tiles_x * tiles_y * NPLANES * VCT_TILE_PIX;
-    const size_t npix = (size_t)w * h;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (size_t)gridDim.x * blockDim.x) {
-        const int lane = (int)(i & 63);
-        const size_t r = i >> 6;
-        const int plane = (int)(r % NPLANES);
-        const size_t tile = r / NPLANES;
-        const int ty = (int)(tile / tiles_x), tx = (int)(tile - (size_t)ty * tiles_x);
-        const int x = tx * VCT_TILE + (lane & 7), y = ty * VCT_TILE + (lane >> 3);
-        float v = 0.0f;
-        if (x < w && y < h) v = planes[(size_t)plane * npix + (size_t)y * w + x];
-        tiled[i] = v;
-    }
-}
-
-// the one-byte pixel-gloss plane (include/vct.h "per-material gloss"): linear [h*w] <-> tiled [tile][64], as above
-__global__ void k_tile_bytes(const uint8_t* __restrict__ linear, uint8_t* __restrict__ tiled, int w, int h, int tiles_x, int tiles_y) {
-    const size_t total = (size_t)tiles_x * tiles_y * VCT_TILE_PIX;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int lane = (int)(i & 63);
-        const size_t tile = i >> 6;
-        const int ty = (int)(tile / tiles_x), tx = (int)(tile - (size_t)ty * tiles_x);
-        const int x = tx * VCT_TILE + (lane & 7), y = ty * VCT_TILE + (lane >> 3);
-        tiled[i] = (x < w && y < h) ? linear[(size_t)y * w + x] : (uint8_t)0;
-    }
-}
-__global__ void k_untile_bytes(const uint8_t* __restrict__ tiled, uint8_t* __restrict__ linear, int w, int h, int tiles_x) {
-    const size_t npix = (size_t)w * h;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (size_t)gridDim.x * blockDim.x) {
-        const int y = (int)(i / w), x = (int)(i - (size_t)y * w);
-        const size_t tile = (size_t)(y / VCT_TILE) * tiles_x + x / VCT_TILE;
-        linear[i] = tiled[tile * VCT_TILE_PIX + (y % VCT_TILE) * VCT_TILE + (x % VCT_TILE)];
-    }
-}
-
 inline int grid_for(size_t n, int threads) {
     size_t b = (n + threads - 1) / threads;
     if (b > 256 * 16) b = 256 * 16;
@@ -283,33 +243,4 @@ hipError_t vct_launch_build_mips_aniso(const uint32_t* level0, uint32_t* aniso, 
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
-}
-
-hipError_t vct_launch_tile_gbuffer(const float* planes_linear, float* tiled, int w, int h,
-                                   hipStream_t s) {
-    const int tx = (w + VCT_TILE - 1) / VCT_TILE, ty = (h + VCT_TILE - 1) / VCT_TILE;
-    const size_t n = (size_t)tx * ty * VCT_GB_NPLANES * VCT_TILE_PIX;
-    hipLaunchKernelGGL(k_tile_gbuffer<VCT_GB_NPLANES>, dim3(grid_for(n, 256)), dim3(256), 0, s, planes_linear, tiled,
-                       w, h, tx, ty);
-    return hipGetLastError();
-}
-
-hipError_t vct_launch_tile_emission(const float* planes_linear, float* tiled, int w, int h, hipStream_t s) {
-    const int tx = (w + VCT_TILE - 1) / VCT_TILE, ty = (h + VCT_TILE - 1) / VCT_TILE;
-    const size_t n = (size_t)tx * ty * VCT_EMIS_NPLANES * VCT_TILE_PIX;
-    hipLaunchKernelGGL(k_tile_gbuffer<VCT_EMIS_NPLANES>, dim3(grid_for(n, 256)), dim3(256), 0, s, planes_linear, tiled,
-                       w, h, tx, ty);
-    return hipGetLastError();
-}
-
-hipError_t vct_launch_tile_gloss(const uint8_t* linear, uint8_t* tiled, int w, int h, hipStream_t s) {
-    const int tx = (w + VCT_TILE - 1) / VCT_TILE, ty = (h + VCT_TILE - 1) / VCT_TILE;
-    hipLaunchKernelGGL(k_tile_bytes, dim3(grid_for((size_t)tx * ty * VCT_TILE_PIX, 256)), dim3(256), 0, s, linear, tiled, w, h, tx, ty);
-    return hipGetLastError();
-}
-
-hipError_t vct_launch_untile_gloss(const uint8_t* tiled, uint8_t* linear, int w, int h, hipStream_t s) {
-    const int tx = (w + VCT_TILE - 1) / VCT_TILE;
-    hipLaunchKernelGGL(k_untile_bytes, dim3(grid_for((size_t)w * h, 256)), dim3(256), 0, s, tiled, linear, w, h, tx);
-    return hipGetLastError();
 }

@@ -938,7 +938,11 @@ int vct_last_trace_stats(vct_ctx* ctx, uint64_t out[32]);
  * [1] conservative fragments of the mesh at this grid size (the voxelizer's brick-sorted list), [2] division form of
  * the last march launch (screen trace, slab, frame step, bounce or point query): 0 none yet, 1 the IEEE divide, 2 the verified
  * two-term product (every divisor of the step tables is in the shipped table or passed the device check, 1 - max_alpha
- * >= 2^-5, every two-level blend fraction in [2^-10, 1 - 2^-10]), 3 trace_variant 3's x * r, [3] brick slots =
+ * >= 2^-5, every two-level blend fraction in [2^-10, 1 - 2^-10]), 3 trace_variant 3's x * r -- in bits 0-7; bits 8-9,
+ * set by screen traces: how the launch's typed loads reached a mip level, 2 through one buffer resource per wave with
+ * the level's byte offset in the load's scalar operand (the default kernel's plain GL_REPEAT forms of a context whose
+ * levels all start below 4 GiB, unless VCT_LEVEL_DESCRIPTORS=1 or the device failed the offset part of the texel
+ * self-test), 1 through a resource per level -- [3] brick slots =
  * 8^3 bricks a fragment of the mesh can land in, [4] bricks level 0 shows after the last resolve, [5] compute
  * units reserved for the communication stream (VCT_COMM_RESERVED_CUS; 0 = none), [6] form of the last main-draw
  * visibility pass (0 none yet, 1 direct, 2 tile-binned: chosen per context by timing), [7] work items
@@ -965,8 +969,11 @@ int vct_selftest_const_divide(vct_ctx* ctx, float d, uint64_t* mismatches);
 /* Round 6: the trace kernels fetch texels through typed-buffer loads (the level as an RGBA8 UNORM texel buffer) and take
  * the four floats the texture path returns instead of decoding the bytes themselves -- valid because that conversion
  * is bit for bit (float)c / 255.0f on gfx950.  This runs every byte value in every channel position through the same
- * load against the library's exact decode: *mismatches = channel values that differ (0 expected).  vct_create runs it
- * once per process and device and fails (VCT_ERR_DEVICE) on a device where the conversion is not exact. */
+ * load against the library's exact decode, and reads the same texels as two levels of a chain through one resource with
+ * their byte offsets in the load's scalar offset operand, against the load without an offset: *mismatches = channel
+ * values that differ in either part (0 expected).  vct_create runs it once per process and device; it fails
+ * (VCT_ERR_DEVICE) on a device where the conversion is not exact, and on one where only the offset reads differ it
+ * traces with a resource per level (vct_get_stage_counts [2], bits 8-9). */
 int vct_selftest_texel_buffer(vct_ctx* ctx, uint64_t* mismatches);
 /* Self-test of the rasteriser's shared-reciprocal division (csrc/vct_raster.hip div_area: the barycentrics' x / area
  * as two FMA corrections of x * RN(1/area), correctly rounded by Markstein's theorem): `count` pseudo-random pairs of

@@ -4,7 +4,8 @@
     tools/valu_model.py  [--write]
 
 Compiles csrc/vct_trace.hip to gfx950 assembly, takes the specular march loop of
-k_trace_tile_split<true,1,false,false,false,true,false,false> (the whole-frame instantiation; the diffuse loop has the
+k_trace_tile_split<true,1,false,false,false,true,..., CHAIN = true> (the whole-frame instantiation of a chain whose
+levels start below 4 GiB: one texel buffer per wave; the diffuse loop has the
 same body), splits it at its labels into basic blocks, tells the blocks of a level sample apart by what they hold
 (coordinates, fit test against the held block, reuse, fresh anchor, fetch, LDS write, gather, zero result, per-lane
 gather: see main) and prices every VALU instruction with the issue cost MEASURED for its class on this GPU
@@ -66,7 +67,7 @@ def main():
                         "-fno-slp-vectorize", "-fPIC", "-Wno-unused-function", "-S", "--cuda-device-only", "-o", out, src],
                        check=True, capture_output=True)
         text = open(out).read()
-    m = re.search(r"^_ZN12_GLOBAL__N_118k_trace_tile_splitILb1ELi1ELb0ELb0ELb0ELb1ELb0ELb0ELb0ELb0EEEv14VctTraceParams:.*?\.end_amdhsa_kernel", text, re.S | re.M)
+    m = re.search(r"^_ZN12_GLOBAL__N_118k_trace_tile_splitILb1ELi1ELb0ELb0ELb0ELb1ELb0ELb0ELb0ELb0ELb1EEEv14VctTraceParams:.*?\.end_amdhsa_kernel", text, re.S | re.M)
     body = m.group(0).split("\n")
     # the specular march = the largest depth-1 inner loop (the diffuse march, inside the cone loop, is depth 2 and has the
     # same body; small depth-1 loops, if any, are prologue code)

@@ -997,8 +997,12 @@ class Context:
     def stage_counts(self):
         v = (C.c_uint64 * 8)()
         self._ck(_lib.vct_get_stage_counts(self._h, v), "vct_get_stage_counts")
-        return dict(zip(("triangles", "vox_candidates", "march_division", "accumulator_bricks", "touched_bricks",
-                         "comm_reserved_cus", "raster_form", "vox_items"), (int(x) for x in v)))
+        d = dict(zip(("triangles", "vox_candidates", "march_division", "accumulator_bricks", "touched_bricks",
+                      "comm_reserved_cus", "raster_form", "vox_items"), (int(x) for x in v)))
+        # word [2]: the division form in bits 0-7; a screen trace's texel-resource form above (1 per level, 2 per wave)
+        d["texel_resource"] = d["march_division"] >> 8
+        d["march_division"] &= 0xff
+        return d
 
     def set_trace_timing(self, on=True):
         """Bracket march launches with the timing events last_trace_ms() reads (default on; ~7 us per launch: include/vct.h)."""

@@ -60,13 +60,14 @@ int vct_build_steps(const vct_config& cfg, float tan_half, std::vector<VctStep>&
 
 namespace {
 
-// The two result words of a self-test kernel (mismatches, one example), through the statistics words as scratch (never the
-// step-counter bank: vct_last_step_count sums that).
-template <class Launch>
-int selftest_words(vct_ctx* c, unsigned long long v[2], Launch launch) {
-    HIP_TRY(c, hipMemsetAsync(c->stats.get(), 0, 2 * sizeof(unsigned long long), cur(c).stream.get()));
+// The result words of a self-test kernel (pairs of mismatches, one example), through the statistics words as scratch
+// (never the step-counter bank: vct_last_step_count sums that).
+template <size_t N, class Launch>
+int selftest_words(vct_ctx* c, unsigned long long (&v)[N], Launch launch) {
+    static_assert(N <= 32, "the statistics words");
+    HIP_TRY(c, hipMemsetAsync(c->stats.get(), 0, N * sizeof(unsigned long long), cur(c).stream.get()));
     HIP_TRY(c, launch(c->stats.get(), cur(c).stream.get()));
-    HIP_TRY(c, hipMemcpyAsync(v, c->stats.get(), 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, cur(c).stream.get()));
+    HIP_TRY(c, hipMemcpyAsync(v, c->stats.get(), N * sizeof(unsigned long long), hipMemcpyDeviceToHost, cur(c).stream.get()));
     HIP_TRY(c, hipStreamSynchronize(cur(c).stream.get()));
     return VCT_OK;
 }
@@ -196,6 +197,7 @@ void vct_fill_march_params(const vct_ctx* c, VctTraceParams& p, const uint32_t* 
     p.max_alpha = c->cfg.max_alpha;
     p.wrap_repeat = c->cfg.wrap_repeat;
     p.spread_lut = c->spread_lut.get();
+    p.chain_form = c->chain_form ? 1 : 0;
     // records of `c->vol.chain` only (the bounce chain has none), biased by the first level's offset
     p.cells_biased = (c->vol.cells_valid && chain == c->vol.chain.get())
                          ? (const char*)c->vol.cells.get() - ((size_t)vct_level_offset(c->cfg.voxel_dim, 1) << 5) : nullptr;
@@ -337,6 +339,39 @@ int vct_launch_trace_rows(vct_ctx* c, int row0, int row1, uint16_t* out_base, in
     cur(c).last_row_stride = rstride;
     cur(c).last_was_screen_trace = true;
     cur(c).last_trace_compacted = compacting;
+    return VCT_OK;
+}
+
+// The trace kernels fetch texels through typed-buffer loads and rely on the texture path converting a UNORM8 channel to
+// exactly (float)c / 255.0f.  Every byte value in every channel position (1,024 texels) through that path against the
+// library's exact decode; *bad_decode = channels that differ (0 on gfx950: tools/unorm_probe.hip).  And the same texels as
+// two levels of a chain, through one resource over the chain with the levels' byte offsets in the loads' scalar offset
+// operand (the CHAIN forms of the default trace kernel, vct_trace.hip ChainRef): *bad_offset = channels whose bits are not the
+// zero-offset load's.
+int vct_texel_buffer_selftest(vct_ctx* c, uint64_t* bad_decode, uint64_t* bad_offset) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint32_t lead = 8u, n = 1024u;                // (a chain's smallest level in front of others holds 8 texels)
+    std::vector<uint32_t> h(lead + 2u * n, 0xdeadbeefu);
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t b = i & 255u, k = i >> 8;       // byte b in channel k, the other channels vary with it
+        const uint32_t o0 = (b * 7u + 3u) & 255u, o1 = 255u - b, o2 = (b * 13u + 5u) & 255u;
+        const uint32_t ch[4] = {o0, o1, o2, b};
+        h[lead + i] = h[lead + n + i] =
+            ch[(0 + 3 - k) & 3] | (ch[(1 + 3 - k) & 3] << 8) | (ch[(2 + 3 - k) & 3] << 16) | (ch[(3 + 3 - k) & 3] << 24);
+    }
+    VctBuf<uint32_t> d;
+    HIP_TRY(c, d.alloc(h.size()));
+    HIP_TRY(c, hipMemcpyAsync(d.get(), h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice, cur(c).stream.get()));
+    unsigned long long v[4] = {0, 0, 0, 0};
+    PIPE_TRY(selftest_words(c, v, [&](unsigned long long* w, hipStream_t st) { return vct_launch_texel_buffer_selftest(d.get(), lead, n, w, st); }));
+    *bad_decode = v[0];
+    *bad_offset = v[2];
+    if (v[0] || v[2]) {
+        char msg[224];
+        snprintf(msg, sizeof(msg), "texel buffer: %llu channel values differ from (float)c / 255.0f, e.g. texel 0x%08llx; %llu differ "
+                 "between a load with a scalar offset and one without, e.g. texel 0x%08llx", v[0], v[1], v[2], v[3]);
+        c->err = msg;
+    }
     return VCT_OK;
 }
 
@@ -552,7 +587,9 @@ int vct_get_stage_counts(vct_ctx* c, uint64_t out[8]) {
     memset(out, 0, 8 * sizeof(uint64_t));
     out[0] = (uint64_t)c->mesh.ntri;
     out[1] = c->vox.n_frags;
-    out[2] = (uint64_t)c->last_march_form;       // division form of the last march launch: 0 none, 1 IEEE, 2 product, 3 x * r
+    // bits 0-7 division form of the last march launch: 0 none, 1 IEEE, 2 product, 3 x * r; bits 8-9 (screen traces) how its
+    // typed loads reached a level: 1 a resource per level, 2 one per wave (include/vct.h)
+    out[2] = (uint64_t)c->last_march_form;
     out[3] = c->vox.nslots;
     out[5] = (uint64_t)c->reserved_cus;          // compute units kept for the communication stream (VCT_COMM_RESERVED_CUS)
     out[6] = (uint64_t)c->raster_form.last_form;      // visibility form of the last main-draw pass: 1 direct, 2 tile-binned
@@ -644,30 +681,12 @@ int vct_selftest_const_divide(vct_ctx* c, float d, uint64_t* mismatches) {
     return VCT_OK;
 }
 
-// The trace kernels fetch texels through typed-buffer loads and rely on the texture path converting a UNORM8 channel to
-// exactly (float)c / 255.0f.  Every byte value in every channel position (1,024 texels) through that path against the
-// library's exact decode; *mismatches = channels that differ (0 on gfx950: tools/unorm_probe.hip).
+// vct_texel_buffer_selftest (above): both of its counts
 int vct_selftest_texel_buffer(vct_ctx* c, uint64_t* mismatches) {
     if (!c || !mismatches) return VCT_ERR_INVALID;
-    HIP_TRY(c, hipSetDevice(c->device));
-    std::vector<uint32_t> h(1024);
-    for (uint32_t i = 0; i < 1024u; ++i) {
-        const uint32_t b = i & 255u, k = i >> 8;       // byte b in channel k, the other channels vary with it
-        const uint32_t o0 = (b * 7u + 3u) & 255u, o1 = 255u - b, o2 = (b * 13u + 5u) & 255u;
-        const uint32_t ch[4] = {o0, o1, o2, b};
-        h[i] = ch[(0 + 3 - k) & 3] | (ch[(1 + 3 - k) & 3] << 8) | (ch[(2 + 3 - k) & 3] << 16) | (ch[(3 + 3 - k) & 3] << 24);
-    }
-    VctBuf<uint32_t> d;
-    HIP_TRY(c, d.alloc(h.size()));
-    HIP_TRY(c, hipMemcpyAsync(d.get(), h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice, cur(c).stream.get()));
-    unsigned long long v[2] = {0, 0};
-    PIPE_TRY(selftest_words(c, v, [&](unsigned long long* w, hipStream_t st) { return vct_launch_texel_buffer_selftest(d.get(), (uint32_t)h.size(), w, st); }));
-    *mismatches = v[0];
-    if (v[0]) {
-        char msg[128];
-        snprintf(msg, sizeof(msg), "texel buffer: %llu channel values differ from (float)c / 255.0f, e.g. texel 0x%08llx", v[0], v[1]);
-        c->err = msg;
-    }
+    uint64_t decode = 0, offset = 0;
+    PIPE_TRY(vct_texel_buffer_selftest(c, &decode, &offset));
+    *mismatches = decode + offset;
     return VCT_OK;
 }
 

@@ -141,18 +141,24 @@ int create_resources(vct_ctx* c) {
     HIP_TRY(c, hipStreamSynchronize(cur(c).stream.get()));
     // once per process and device: the texture path's UNORM8 conversion must be the exact decode the trace kernels count on
     // (it is on gfx950).  No other path is compiled in: a device where it is not fails here, loudly.
+    // The same run checks the loads' scalar offset operand, which the CHAIN forms of the default trace kernel rest on
+    // (vct_trace.hip ChainRef): a device that fails that part traces with a resource per level instead.  So does a chain with a level at
+    // or beyond 4 GiB, and any chain under VCT_LEVEL_DESCRIPTORS=1 (tests: both forms on one small chain; same bits).
     static std::mutex lock;
-    static std::map<int, unsigned long long> verdict;
+    static std::map<int, std::pair<uint64_t, uint64_t>> verdict;      // channel values that differ: decode, offset read
     std::lock_guard<std::mutex> g(lock);
     auto it = verdict.find(c->device);
     if (it == verdict.end()) {
-        uint64_t bad = 0;
-        PIPE_TRY(vct_selftest_texel_buffer(c, &bad));
-        it = verdict.emplace(c->device, bad).first;
+        uint64_t bad = 0, bad_offset = 0;
+        PIPE_TRY(vct_texel_buffer_selftest(c, &bad, &bad_offset));
+        it = verdict.emplace(c->device, std::make_pair(bad, bad_offset)).first;
     }
-    if (it->second)
+    if (it->second.first)
         return vct_fail(c, VCT_ERR_DEVICE, "this device's typed-buffer loads do not convert UNORM8 to exactly c / 255 (" +
-                        std::to_string(it->second) + " of 4096 channel values differ)");
+                        std::to_string(it->second.first) + " of 4096 channel values differ)");
+    const char* ld = getenv("VCT_LEVEL_DESCRIPTORS");
+    c->chain_form = vct_chain_form_fits(cfg->voxel_dim) && it->second.second == 0 && !(ld && ld[0] == '1');
+    c->err.clear();
     return VCT_OK;
 }
 
@@ -312,7 +318,7 @@ int vct_create(const vct_config* cfg, vct_ctx** out) {
     if (!cfg || !out) return vct_fail(nullptr, VCT_ERR_INVALID, "null argument");
     *out = nullptr;
     if (cfg->abi_version != VCT_ABI_VERSION) return vct_fail(nullptr, VCT_ERR_INVALID, "vct_config.abi_version mismatch");
-    if (!is_pow2(cfg->voxel_dim) || cfg->voxel_dim < 8 || cfg->voxel_dim > 1024)
+    if (!is_pow2(cfg->voxel_dim) || cfg->voxel_dim < 8 || cfg->voxel_dim > VCT_MAX_VOXEL_DIM)
         return vct_fail(nullptr, VCT_ERR_INVALID, "voxel_dim must be a power of two in [8,1024]");
     if (cfg->width <= 0 || cfg->height <= 0 || !(cfg->grid_world_size > 0.0f))
         return vct_fail(nullptr, VCT_ERR_INVALID, "bad frame size or grid size");

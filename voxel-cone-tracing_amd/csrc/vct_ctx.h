@@ -468,7 +468,13 @@ struct vct_ctx {
     VctLights lights;
     bool steps_dirty = true;
     bool fast_div = false;            // set by vct_refresh_steps: constant divisors admit the FMA division
-    int last_march_form = 0;          // division of the last march launch: 1 IEEE, 2 verified product, 3 x * r (vct_get_stage_counts [2])
+    // set by vct_create: the default trace kernel runs in its CHAIN form, one texel buffer per wave and the level's byte
+    // offset in the loads' scalar operand (vct_trace.hip ChainRef) -- every level starts below 4 GiB, the device passed the
+    // offset read of the texel self-test, and VCT_LEVEL_DESCRIPTORS=1 does not ask for a resource per level and fetch
+    bool chain_form = false;
+    // division of the last march launch: 1 IEEE, 2 verified product, 3 x * r; a screen trace adds its texel-resource form
+    // in bits 8-9 (vct_trace.hip vct_launch_trace).  vct_get_stage_counts [2].
+    int last_march_form = 0;
     // vct_set_trace_timing: bracket every march launch with the two timing events vct_last_trace_ms reads.  On by default
     // (every entry point keeps working); a frame loop switches it off -- the two events cost a launch ~7 us of dispatch
     // gaps on this GPU (one-stream step 0.549 -> 0.542 ms, a 1/8 slab's 0.12 ms step the same 7 us).
@@ -557,6 +563,8 @@ void vct_glm_voxel_projections(const vct_ctx* c, float proj[48]);
 int vct_refresh_steps(vct_ctx* c);
 // the step sequence of one aperture (trace.fs:90-104); -1: more than VCT_MAX_STEPS steps, or a march that would not end
 int vct_build_steps(const vct_config& cfg, float tan_half, std::vector<VctStep>& out);
+// both verdicts of the texel self-test apart (vct_api_trace.hip): vct_create fails on the first and falls back on the second
+int vct_texel_buffer_selftest(vct_ctx* c, uint64_t* bad_decode, uint64_t* bad_offset);
 void vct_fill_march_params(const vct_ctx* c, VctTraceParams& p, const uint32_t* chain);
 // asynchronous, on the slot's stream.  row_stride > 1: only every row_stride-th tile row from row0 on; pack_rows: those rows back to back in out_base (interleaved slabs)
 int vct_launch_trace_rows(vct_ctx* c, int row0, int row1, uint16_t* out_base = nullptr, int row_stride = 1, bool pack_rows = false);

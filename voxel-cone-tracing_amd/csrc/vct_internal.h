@@ -206,6 +206,11 @@ struct __attribute__((packed, aligned(4))) VctTri9 { float v[9]; };
 // voxels, keep a small bank of atomic counters.
 #define VCT_STEP_COUNTERS 256   // bounce kernels only (power of two)
 
+// One texel buffer per wave serves every level of a chain whose levels all start below 4 GiB: the level's byte offset
+// goes into the load's scalar offset operand (vct_trace.hip ChainRef; the CHAIN forms of the default trace kernel).  A
+// chain with a level at or beyond 4 GiB (1024^3: level 1 starts at byte 2^32) has no such offset.
+static inline bool vct_chain_form_fits(int V) { return vct_level_offset(V, vct_ilog2(V)) < (1ull << 30); }
+
 // One entry per march step of a cone aperture.  The step sequence of trace.fs:90-104 (dist,
 // diameter, lod) does not depend on the pixel, only on (V, G, tanHalfAngle, MAX_DISTANCE): the
 // host evaluates it once with the reference's operation order and the kernel reads it through
@@ -349,6 +354,9 @@ struct VctTraceParams {
     // (all ones: no pixel), vt_count[0] = virtual tiles.  Null: lane = pixel of the launched tile.
     uint32_t* vt_pix;
     uint32_t* vt_count;
+    // 1: every level of `chain` starts below 4 GiB and the context takes the kernels' CHAIN forms (vct_chain_form_fits,
+    // vct_ctx chain_form).  Read by the launch dispatch, by no kernel.
+    int32_t chain_form;
 };
 #define VCT_DR_NO_ANCHOR 0xffu
 #define VCT_DR_COUNTERS 256             // (power of two) a bank, for the reason VCT_STEP_COUNTERS is one
@@ -526,7 +534,8 @@ hipError_t vct_launch_trace(const VctTraceParams& p, int variant, hipStream_t s,
                             const hipEvent_t* marks = nullptr);
 hipError_t vct_launch_divide_selftest(float d, unsigned long long* mismatches, hipStream_t s);
 // typed-buffer texel loads (RGBA8 UNORM -> four floats in the texture path) against the exact decode, n texels
-hipError_t vct_launch_texel_buffer_selftest(const uint32_t* texels, uint32_t n, unsigned long long* out, hipStream_t s);
+// buf: [lead][n][n] texels, out: 4 words (vct_trace.hip k_texel_buffer_selftest)
+hipError_t vct_launch_texel_buffer_selftest(const uint32_t* buf, uint32_t lead, uint32_t n, unsigned long long* out, hipStream_t s);
 hipError_t vct_launch_area_divide_selftest(uint64_t seed, uint64_t count, unsigned long long* out, hipStream_t s);
 hipError_t vct_launch_linear_to_morton(const uint32_t* lin, uint32_t* mor, int N, hipStream_t s);
 hipError_t vct_launch_morton_to_linear(const uint32_t* mor, uint32_t* lin, int N, hipStream_t s);

@@ -21,7 +21,8 @@
 #define VCT_HD inline
 #endif
 
-#define VCT_MAX_LEVELS 11   // V <= 1024
+#define VCT_MAX_VOXEL_DIM 1024
+#define VCT_MAX_LEVELS 11   // V <= VCT_MAX_VOXEL_DIM
 
 // spread the low 10 bits of x so that bit i lands on bit 3*i
 VCT_HD uint32_t vct_spread3(uint32_t x) {

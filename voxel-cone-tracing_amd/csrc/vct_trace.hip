@@ -140,7 +140,12 @@ __device__ __forceinline__ T wave_sum(T v) {
 // per level sample, and the scalar pipe issues one instruction per 4 cycles per SIMD (tools/valu_bench.hip: s_add /
 // s_and / s_mul 4.17 cycles at any occupancy) -- with half as many SALU as VALU instructions it was 68 % busy, and a
 // padding experiment showed the march paying 2.1 us per scalar instruction added to a step against 1.4 us per vector
-// one.  One s_load_dword per axis replaces 13 instructions.  Entry i = spread3(i) << 2 (byte offset of the x axis).
+// one.  (Re-measured on the kernel of 8 waves per SIMD and 0.515 ms: 0.93 us per scalar instruction added to every step,
+// 1.22 us per vector one -- profiles/experiments/README.md, round 17: the price list of the scalar-side changes since.)
+// One s_load_dword per axis replaces 13 instructions.  Entry i = spread3(i) << 2 (byte offset of the x axis).
+// (Round 17: a table per axis with the entries in place and the other bits set takes the two shifts and the three ORs
+// with the masks' complements out of a fetch -- and the allocation that came with it ten more scalars through the spill
+// lanes: 5 us slower than without.  profiles/experiments/README.md.)
 typedef const __attribute__((address_space(4))) uint32_t* SpreadLut;
 // byte offset of x coordinate (a & m) in dilated form; m4 = m << 2.  All 32-bit, so the table entry is one
 // s_load_dword with an SGPR offset.
@@ -149,7 +154,27 @@ __device__ __forceinline__ uint32_t spread_byte(SpreadLut lut, int a, uint32_t m
     return *(SpreadLut)((const __attribute__((address_space(4))) char*)lut + off);
 }
 
+// A chain as the samplers read it (wave-uniform): its first texel and the texel buffer over it, formed once per wave.
+// The samplers' loads take a level's texels in one of two forms (LevelBuf):
+//   CHAIN      the chain's resource and the level's BYTE offset in the load's scalar offset operand: one shift per fetch
+//   otherwise  a resource over the level itself and 0: a shift, a 64-bit add, a mask and the stride word -- six scalar
+//              instructions in front of every fetch, cooperative or per lane
+// Same address, same conversion (k_texel_buffer_selftest), same bits.  A byte offset has 32 bits, so CHAIN serves chains
+// whose levels all start below 4 GiB (vct_internal.h vct_chain_form_fits; the host chooses per context: vct_ctx
+// chain_form, VCT_LEVEL_DESCRIPTORS).  It is a template flag of the default kernel's GL_REPEAT forms (k_trace_tile_split)
+// and nothing else: there the march's scalar stream is what a fetch waits behind, and a flag tested per fetch costs
+// what the flag saves.  Whichever member a form does not read is never formed.
+struct ChainRef { const uint32_t* base; vct_v4i32 tb; };
+__device__ __forceinline__ ChainRef chain_ref(const uint32_t* chain) { return {chain, level_texel_buffer(chain)}; }
+struct LevelBuf { vct_v4i32 tb; uint32_t soffset; };
+template <bool CHAIN>
+__device__ __forceinline__ LevelBuf level_buf(const ChainRef& ch, const VctLevelRef lv) {
+    if constexpr (CHAIN) return {ch.tb, lv.off << 2};
+    else return {level_texel_buffer(ch.base + lv.off), 0u};
+}
+
 struct LaneBlock {      // this lane's texel inside the cooperative 4x4x4 block
+    ChainRef chain;             // (wave-uniform) the launch's chain, p.chain
     SpreadLut lut;              // (wave-uniform) the dilated-coordinate table
     const uint32_t* lut_vec;    // the same table through a plain global pointer (per-lane gather)
     int lane;
@@ -384,8 +409,8 @@ __device__ __forceinline__ void per_lane_census(MarchStats& ms, const Footprint&
 // Over the shared pieces above: the choice between the cooperative block (COOP, every live footprint inside the block
 // at the anchor) and the per-lane gather, the per-lane gather itself (texel loads in phases of 2 + 2 + 4, or one
 // footprint record with CELLS), and where the issue priority (PRIO) is raised and dropped.
-template <bool WRAP, bool COOP, bool LOOSE = false, bool CELLS = false, bool PRIO = false, bool NARROW = false>
-__device__ __forceinline__ F4 sample_level(const uint32_t* __restrict__ chain, const VctLevelRef lv,
+template <bool WRAP, bool COOP, bool LOOSE = false, bool CELLS = false, bool PRIO = false, bool NARROW = false, bool CHAIN = false>
+__device__ __forceinline__ F4 sample_level(const ChainRef& chain, const VctLevelRef lv,
                                            float ux, float uy, float uz, bool act, unsigned long long am,
                                            float4* __restrict__ blk, const LaneBlock& lb, MarchStats& ms,
                                            const char* __restrict__ cells = nullptr) {
@@ -403,15 +428,16 @@ __device__ __forceinline__ F4 sample_level(const uint32_t* __restrict__ chain, c
     const Footprint f = footprint_of(lv, ux, uy, uz);
     const float a = f.a, b = f.b, c = f.c;
     const int i0 = f.i0, j0 = f.j0, k0 = f.k0;
-    const uint32_t* __restrict__ base = chain + lv.off;
     const uint32_t MX = lv.mask_x, MY = MX << 1, MZ = MX << 2;
-    const vct_v4i32 tb = level_texel_buffer(base);
+    const LevelBuf lvb = level_buf<CHAIN>(chain, lv);
+    const vct_v4i32 tb = lvb.tb;
+    const uint32_t so = lvb.soffset;
 
     F4 r = {0.0f, 0.0f, 0.0f, 0.0f};
     const Anchor an = anchor_of(f, anchor_lane(am));          // (without COOP nothing reads these two: compiled away)
     const BlockFit fit = block_fit(f, an, am);
     if (COOP && fit.out == 0ull) {
-        const float4 d = texel_f32(tb, block_texel_index<WRAP>(lv, an, lb));
+        const float4 d = texel_f32(tb, block_texel_index<WRAP>(lv, an, lb), so);
         if (PRIO) __builtin_amdgcn_s_setprio(0);
         const bool any_texel = block_texel_mask(d) != 0ull;
         if (VCT_STATS) { if (any_texel) ++ms.coop_hit; else ++ms.coop_zero; }
@@ -458,7 +484,7 @@ __device__ __forceinline__ F4 sample_level(const uint32_t* __restrict__ chain, c
             const float a0 = 1.0f - a, b0 = 1.0f - b, c0 = 1.0f - c;
             const float ab00 = a0 * b0, ab10 = a * b0, ab01 = a0 * b, ab11 = a * b;
             {
-                const float4 f0 = texel_f32(tb, mx0 | my0 | mz0), f1 = texel_f32(tb, mx1 | my0 | mz0);
+                const float4 f0 = texel_f32(tb, mx0 | my0 | mz0, so), f1 = texel_f32(tb, mx1 | my0 | mz0, so);
                 const float w0 = ab00 * c0, w1 = ab10 * c0;
 #define VCT_ACC(ch) r.ch = w0 * f0.ch; r.ch = fmaf(w1, f1.ch, r.ch);
                 VCT_ACC(x) VCT_ACC(y) VCT_ACC(z) VCT_ACC(w)
@@ -466,7 +492,7 @@ __device__ __forceinline__ F4 sample_level(const uint32_t* __restrict__ chain, c
             }
             __builtin_amdgcn_sched_barrier(0);
             {
-                const float4 f2 = texel_f32(tb, mx0 | my1 | mz0), f3 = texel_f32(tb, mx1 | my1 | mz0);
+                const float4 f2 = texel_f32(tb, mx0 | my1 | mz0, so), f3 = texel_f32(tb, mx1 | my1 | mz0, so);
                 const float w2 = ab01 * c0, w3 = ab11 * c0;
 #define VCT_ACC(ch) r.ch = fmaf(w2, f2.ch, r.ch); r.ch = fmaf(w3, f3.ch, r.ch);
                 VCT_ACC(x) VCT_ACC(y) VCT_ACC(z) VCT_ACC(w)
@@ -475,7 +501,7 @@ __device__ __forceinline__ F4 sample_level(const uint32_t* __restrict__ chain, c
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (NARROW) {       // phases of 2 + 2 + 2 + 2
                 {
-                    const float4 f4 = texel_f32(tb, mx0 | my0 | mz1), f5 = texel_f32(tb, mx1 | my0 | mz1);
+                    const float4 f4 = texel_f32(tb, mx0 | my0 | mz1, so), f5 = texel_f32(tb, mx1 | my0 | mz1, so);
                     const float w4 = ab00 * c, w5 = ab10 * c;
 #define VCT_ACC(ch) r.ch = fmaf(w4, f4.ch, r.ch); r.ch = fmaf(w5, f5.ch, r.ch);
                     VCT_ACC(x) VCT_ACC(y) VCT_ACC(z) VCT_ACC(w)
@@ -483,7 +509,7 @@ __device__ __forceinline__ F4 sample_level(const uint32_t* __restrict__ chain, c
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 {
-                    const float4 f6 = texel_f32(tb, mx0 | my1 | mz1), f7 = texel_f32(tb, mx1 | my1 | mz1);
+                    const float4 f6 = texel_f32(tb, mx0 | my1 | mz1, so), f7 = texel_f32(tb, mx1 | my1 | mz1, so);
                     if (PRIO) __builtin_amdgcn_s_setprio(0);
                     const float w6 = ab01 * c, w7 = ab11 * c;
 #define VCT_ACC(ch) r.ch = fmaf(w6, f6.ch, r.ch); r.ch = fmaf(w7, f7.ch, r.ch);
@@ -491,8 +517,8 @@ __device__ __forceinline__ F4 sample_level(const uint32_t* __restrict__ chain, c
 #undef VCT_ACC
                 }
             } else {
-                const float4 f4 = texel_f32(tb, mx0 | my0 | mz1), f5 = texel_f32(tb, mx1 | my0 | mz1);
-                const float4 f6 = texel_f32(tb, mx0 | my1 | mz1), f7 = texel_f32(tb, mx1 | my1 | mz1);
+                const float4 f4 = texel_f32(tb, mx0 | my0 | mz1, so), f5 = texel_f32(tb, mx1 | my0 | mz1, so);
+                const float4 f6 = texel_f32(tb, mx0 | my1 | mz1, so), f7 = texel_f32(tb, mx1 | my1 | mz1, so);
                 if (PRIO) __builtin_amdgcn_s_setprio(0);
                 const float w4 = ab00 * c, w5 = ab10 * c, w6 = ab01 * c, w7 = ab11 * c;
 #define VCT_ACC(ch) r.ch = fmaf(w4, f4.ch, r.ch); r.ch = fmaf(w5, f5.ch, r.ch); r.ch = fmaf(w6, f6.ch, r.ch); r.ch = fmaf(w7, f7.ch, r.ch);
@@ -506,6 +532,7 @@ __device__ __forceinline__ F4 sample_level(const uint32_t* __restrict__ chain, c
             // scenes: street at 1024^3 / 4K 2.72 -> 2.70 ms, atrium 0.611 -> 0.613 (profiles/experiments/README.md).  Off
             // unless the context asks for it.
             uint32_t t[8];
+            const uint32_t* __restrict__ base = chain.base + lv.off;
             if (WRAP && lv.off != 0u) {     // (CELLS instantiations are launched with records present)
                 // footprint record of the lower corner: the 8 texels as 32 contiguous bytes (levels >= 1; Morton index * 32
                 // = byte offset of the record, < 2^32 for every level but the first of a 2048^3 grid, which has none)
@@ -539,6 +566,8 @@ __device__ __forceinline__ F4 sample_level(const uint32_t* __restrict__ chain, c
         }
       }
     }
+    // (every path above lowers the priority behind its last load -- a new one has to as well; one more s_setprio 0 here
+    // would be a repeat on all of them: profiles/experiments/README.md, round 17)
     return r;
 }
 
@@ -547,8 +576,8 @@ __device__ __forceinline__ F4 sample_level(const uint32_t* __restrict__ chain, c
 // `held` describes the block in the second one.
 // Over the shared pieces: the fit test runs against the held block first and against a fresh anchor only when that
 // fails, and a fresh block of the second slab becomes the held one.
-template <bool WRAP, bool LOOSE, bool PRIO, int SLAB, bool NARROW = false>
-__device__ __forceinline__ F4 sample_level_reuse(const uint32_t* __restrict__ chain, const VctLevelRef lv,
+template <bool WRAP, bool LOOSE, bool PRIO, int SLAB, bool NARROW = false, bool CHAIN = false>
+__device__ __forceinline__ F4 sample_level_reuse(const ChainRef& chain, const VctLevelRef lv,
                                                  float ux, float uy, float uz, bool act, unsigned long long am,
                                                  float4* __restrict__ blk, const LaneBlock& lb, MarchStats& ms,
                                                  BlockDesc& held) {
@@ -582,7 +611,8 @@ __device__ __forceinline__ F4 sample_level_reuse(const uint32_t* __restrict__ ch
         const BlockFit fit = block_fit(f, an, am);
         if (fit.out == 0ull) {
             const uint32_t idx = block_texel_index<true>(lv, an, lb);
-            const float4 d = texel_f32(level_texel_buffer(chain + lv.off), idx);
+            const LevelBuf lvb = level_buf<CHAIN>(chain, lv);
+            const float4 d = texel_f32(lvb.tb, idx, lvb.soffset);
             if (PRIO) __builtin_amdgcn_s_setprio(0);
             const unsigned long long any_texel = block_texel_mask(d);
             if (VCT_STATS) { if (any_texel != 0ull) ++ms.coop_hit; else ++ms.coop_zero; }
@@ -598,19 +628,19 @@ __device__ __forceinline__ F4 sample_level_reuse(const uint32_t* __restrict__ ch
     if (mode == 2) return gather_block<NARROW>(blk + at, f.a, f.b, f.c);
     if (mode == 1) return {0.0f, 0.0f, 0.0f, 0.0f};     // all 64 texels zero: every footprint sums to exactly +0
     // incoherent footprints: the per-lane gather, which leaves the slabs and the descriptor alone
-    return sample_level<WRAP, false, LOOSE, false, PRIO, NARROW>(chain, lv, ux, uy, uz, act, am, blk, lb, ms);
+    return sample_level<WRAP, false, LOOSE, false, PRIO, NARROW, CHAIN>(chain, lv, ux, uy, uz, act, am, blk, lb, ms);
 }
 
 // level SLAB (0: first, 1: second) of a march step, with or without block reuse; `blk` is the wave's first slab
-template <bool WRAP, bool COOP, bool LOOSE, bool CELLS, bool PRIO, bool REUSE, int SLAB, bool NARROW = false>
+template <bool WRAP, bool COOP, bool LOOSE, bool CELLS, bool PRIO, bool REUSE, int SLAB, bool NARROW = false, bool CHAIN = false>
 __device__ __forceinline__ F4 sample_step_level(const VctTraceParams& p, const VctLevelRef lv, float ux, float uy, float uz,
                                                 bool act, unsigned long long am, float4* __restrict__ blk,
                                                 const LaneBlock& lb, MarchStats& ms, BlockDesc& held) {
     if constexpr (REUSE) {
         static_assert(WRAP && COOP && !CELLS, "block reuse: cooperative sampler, GL_REPEAT, no footprint records");
-        return sample_level_reuse<WRAP, LOOSE, PRIO, SLAB, NARROW>(p.chain, lv, ux, uy, uz, act, am, blk, lb, ms, held);
+        return sample_level_reuse<WRAP, LOOSE, PRIO, SLAB, NARROW, CHAIN>(lb.chain, lv, ux, uy, uz, act, am, blk, lb, ms, held);
     } else {
-        return sample_level<WRAP, COOP, LOOSE, CELLS, PRIO, NARROW>(p.chain, lv, ux, uy, uz, act, am, blk + SLAB * 64, lb, ms, p.cells_biased);
+        return sample_level<WRAP, COOP, LOOSE, CELLS, PRIO, NARROW, CHAIN>(lb.chain, lv, ux, uy, uz, act, am, blk + SLAB * 64, lb, ms, p.cells_biased);
     }
 }
 
@@ -682,10 +712,10 @@ __device__ __forceinline__ F4 sample_aniso(const VctTraceParams& p, const VctLev
     if (!done) {
         // per axis: lanes that disagree on the sign are served in two masked passes
         auto axis_sample = [&](int axis, bool neg, unsigned long long mn) -> F4 {
-            if (mn == 0ull) return sample_level<WRAP, COOP>(chain_of(2 * axis), lv, ux, uy, uz, act, m, blk, lb, ms);
-            if (mn == m) return sample_level<WRAP, COOP>(chain_of(2 * axis + 1), lv, ux, uy, uz, act, m, blk, lb, ms);
-            const F4 a = sample_level<WRAP, COOP>(chain_of(2 * axis), lv, ux, uy, uz, act && !neg, m & ~mn, blk, lb, ms);
-            const F4 b = sample_level<WRAP, COOP>(chain_of(2 * axis + 1), lv, ux, uy, uz, act && neg, mn, blk, lb, ms);
+            if (mn == 0ull) return sample_level<WRAP, COOP>(chain_ref(chain_of(2 * axis)), lv, ux, uy, uz, act, m, blk, lb, ms);
+            if (mn == m) return sample_level<WRAP, COOP>(chain_ref(chain_of(2 * axis + 1)), lv, ux, uy, uz, act, m, blk, lb, ms);
+            const F4 a = sample_level<WRAP, COOP>(chain_ref(chain_of(2 * axis)), lv, ux, uy, uz, act && !neg, m & ~mn, blk, lb, ms);
+            const F4 b = sample_level<WRAP, COOP>(chain_ref(chain_of(2 * axis + 1)), lv, ux, uy, uz, act && neg, mn, blk, lb, ms);
             return neg ? b : a;
         };
         tx = axis_sample(0, ac.nx, mx);
@@ -729,10 +759,10 @@ __device__ __forceinline__ VctStep load_step(StepTable t, int k) {
         const float uy = fmaf(div_const<FASTDIV>(py, p.half_G_aux, p.half_G_rcp), 0.5f, 0.5f); \
         const float uz = fmaf(div_const<FASTDIV>(pz, p.half_G_aux, p.half_G_rcp), 0.5f, 0.5f); \
         F4 vc = (ANISO && st.level >= 1) ? sample_aniso<WRAP, COOP>(p, st.l1, ux, uy, uz, act, live, blk, lb, ac, ms) \
-                                         : sample_step_level<WRAP, COOP, FASTDIV == 2, CELLS, PRIO, REUSE, 0, NARROW>(p, st.l1, ux, uy, uz, act, live, blk, lb, ms, held); \
+                                         : sample_step_level<WRAP, COOP, FASTDIV == 2, CELLS, PRIO, REUSE, 0, NARROW, CHAIN>(p, st.l1, ux, uy, uz, act, live, blk, lb, ms, held); \
         if (st.two_levels) { \
             const F4 t2 = ANISO ? sample_aniso<WRAP, COOP>(p, st.l2, ux, uy, uz, act, live, blk + 64, lb, ac, ms) \
-                                : sample_step_level<WRAP, COOP, FASTDIV == 2, CELLS, PRIO, REUSE, 1, NARROW>(p, st.l2, ux, uy, uz, act, live, blk, lb, ms, held); \
+                                : sample_step_level<WRAP, COOP, FASTDIV == 2, CELLS, PRIO, REUSE, 1, NARROW, CHAIN>(p, st.l2, ux, uy, uz, act, live, blk, lb, ms, held); \
             const float g = st.omf;      /* 1 - frac, from the table */ \
             vc.x = fmaf(st.frac, t2.x, g * vc.x); \
             vc.y = fmaf(st.frac, t2.y, g * vc.y); \
@@ -792,7 +822,8 @@ __device__ __forceinline__ void sky_epilogue(const VctTraceParams& p, bool alive
 #define VCT_SKY_NONE 0
 #define VCT_SKY_INSIDE 1
 #define VCT_SKY_ALPHA 2
-template <bool WRAP, int FASTDIV, bool COOP, bool ANISO, bool CELLS, bool PRIO, bool REUSE, int SKY = VCT_SKY_NONE, bool NARROW = false>
+template <bool WRAP, int FASTDIV, bool COOP, bool ANISO, bool CELLS, bool PRIO, bool REUSE, int SKY = VCT_SKY_NONE, bool NARROW = false,
+          bool CHAIN = false>
 __device__ __forceinline__ F4 cone_march(const VctTraceParams& p, bool alive, F3 start, F3 dir,
                                          const VctStep* tab_global, int n,
                                          float4* __restrict__ blk, const LaneBlock& lb,
@@ -910,6 +941,7 @@ __constant__ float kConeWeights[6] = {0.25f, 0.15f, 0.15f, 0.15f, 0.15f, 0.15f};
 __device__ __forceinline__ LaneBlock make_lane_block(const VctTraceParams& p, int lane) {
     LaneBlock lb;
     lb.lane = lane;
+    lb.chain = chain_ref(p.chain);
     lb.lut = (SpreadLut)p.spread_lut; lb.lut_vec = p.spread_lut;
     lb.sbx = vct_spread3((uint32_t)lane & 3u);
     lb.sby = vct_spread3(((uint32_t)lane >> 2) & 3u) << 1;
@@ -1224,12 +1256,13 @@ __device__ __forceinline__ int gloss_class_of(const VctTraceParams& p, int tile,
     return b < nclasses ? b : 0;
 }
 template <bool WRAP, int FASTDIV, bool ANISO, bool COMPACT = false, bool CELLS = false, bool PRIO = false, bool COMP = false,
-          bool HALF = false, bool GLOSS = false, bool SKY = false>
+          bool HALF = false, bool GLOSS = false, bool SKY = false, bool CHAIN = false>
 __global__ void __launch_bounds__(64 * VCT_SPLIT, split_min_waves(WRAP, ANISO, COMPACT, CELLS, PRIO, HALF, GLOSS))
 k_trace_tile_split(const VctTraceParams p) {
     constexpr bool NARROW = !ANISO && split_min_waves(WRAP, ANISO, COMPACT, CELLS, PRIO, HALF, GLOSS) >= 8;
     static_assert(!GLOSS || (COMP && !ANISO && !COMPACT && !CELLS), "gloss classes: the default kernel's COMP forms only");
     static_assert(!SKY || (COMP && !ANISO && !COMPACT && !CELLS), "sky light: the default kernel's COMP forms only");
+    static_assert(!CHAIN || (WRAP && !ANISO && !COMPACT && !CELLS), "one texel buffer per wave (ChainRef): the plain GL_REPEAT forms only");
     __shared__ float4 lds_blk[VCT_SPLIT][ANISO ? 4 : 2][64];   // per wave: level-1 slab, level-2 slab (+ their "-axis" slabs)
     // Cone hand-over.  The workgroup's LDS stays allocated until its last wave ends while the waves that ended free their
     // slots and registers, so what a tile declares caps how many tiles fill a CU's wave slots: the cones travel in the
@@ -1336,7 +1369,7 @@ k_trace_tile_split(const VctTraceParams p) {
 #pragma unroll 1
         for (int i = first; i < first + VCT_CONES_PER_WAVE; ++i) {      // :196-199
             int st;
-            const F4 c = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO, REUSE, SKY ? VCT_SKY_INSIDE : VCT_SKY_NONE, NARROW>(p, march_d, start, cone_dir(k0, k1, k2, i),
+            const F4 c = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO, REUSE, SKY ? VCT_SKY_INSIDE : VCT_SKY_NONE, NARROW, CHAIN>(p, march_d, start, cone_dir(k0, k1, k2, i),
                                                                        p.steps_diffuse, n_diffuse, blk, lb, st, ms, held);
             const bool last = i - first == RAW_CONES;      // behind the wave's last march: into its first slab
             const int l = own_lane();
@@ -1399,7 +1432,7 @@ k_trace_tile_split(const VctTraceParams p) {
                 const bool mine = alive && cls == k;
                 int st;
                 float a = 0.0f;
-                const F4 sc = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO, REUSE, SKY ? VCT_SKY_ALPHA : VCT_SKY_NONE, NARROW>(
+                const F4 sc = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO, REUSE, SKY ? VCT_SKY_ALPHA : VCT_SKY_NONE, NARROW, CHAIN>(
                     p, mine && march_s, start, dir, &p.gloss->steps[k][0], (groups & 2u) ? gt->nsteps[k] : 0, blk, lb, st, ms, held, &a);
                 total += st;          // (0 for the lanes that did not march)
                 if (mine) lds_gloss[lane] = make_float4(sc.x, sc.y, sc.z, sc.w);
@@ -1422,7 +1455,7 @@ k_trace_tile_split(const VctTraceParams p) {
             hand_over_e(eye_dir(gb_planes3(gbuf_ptr(fresh_lane()), 0), p.cam));
         } else {
         int st6;
-        const F4 sc = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO, REUSE, SKY ? VCT_SKY_INSIDE : VCT_SKY_NONE, NARROW>(p, march_s, start, specular_dir(E, N),
+        const F4 sc = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO, REUSE, SKY ? VCT_SKY_INSIDE : VCT_SKY_NONE, NARROW, CHAIN>(p, march_s, start, specular_dir(E, N),
                                                                     p.steps_specular, n_specular, blk, lb, st6, ms, held);
         total += st6;
         store_debug_cone(p, pixel_index, 6, sc, st6, alive, in_frame);
@@ -2030,6 +2063,12 @@ hipError_t launch(const VctTraceParams& p, int blocks, hipStream_t s) {
     return hipGetLastError();
 }
 
+// Does a launch of the default kernel take a CHAIN form (ChainRef)?  The plain forms under GL_REPEAT of a context whose
+// chain admits byte offsets -- what launch_split reaches behind its other branches.
+bool takes_chain_form(const VctTraceParams& p) {
+    return p.chain_form && p.wrap_repeat && !p.sky && !p.pix_gloss && !p.aniso && !p.cells_biased;
+}
+
 // the default kernel's dispatch: anisotropic chains, footprint records, whole-frame issue priority, or plain
 template <bool WRAP, int FASTDIV, bool COMP>
 void launch_split(const VctTraceParams& p, int blocks, hipStream_t s) {
@@ -2061,9 +2100,13 @@ void launch_split(const VctTraceParams& p, int blocks, hipStream_t s) {
             return;
         }
     }
-    if (!p.spec_prio)     // a whole frame (or most of one): issue priority around the samples' loads (sample_level)
-        hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, true, COMP>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, false, COMP>), grid, block, 0, s, p);
+    // the plain forms under GL_REPEAT: with one texel buffer per wave where the chain admits it (p.chain_form; ChainRef)
+    with_flag(WRAP && takes_chain_form(p), [&](auto chain) {
+        constexpr bool CHAIN = WRAP && decltype(chain)::value;
+        if (!p.spec_prio)     // a whole frame (or most of one): issue priority around the samples' loads (sample_level)
+            hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, true, COMP, false, false, false, CHAIN>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, false, COMP, false, false, false, CHAIN>), grid, block, 0, s, p);
+    });
 }
 
 // the four launches of a half-rate pass (p.dr_ind set: whole frame, default kernel, p.comp on); marks: see vct_launch_trace
@@ -2162,10 +2205,15 @@ k_divide_selftest(float d, float r, float aux, unsigned long long* mismatches) {
 
 // The texel buffer's conversion against the exact decode, texel by texel: out[0] = channels that differ, out[1] = the
 // first offending texel word (vct_selftest_texel_buffer; vct_create runs it once per process)
+// ... and the chain form of the samplers' loads: `buf` = [lead][n][n] texels, `lead` texels of anything and the n test
+// texels twice -- two levels of a chain that starts at buf, read through ONE resource over buf with their byte offsets
+// (both non-zero) as the scalar offset operand, the first up to its last texel below the second's start.  out[2] =
+// channels whose bits differ from the zero-offset load's of the same texel, out[3] = an offending texel word.
 __global__ void __launch_bounds__(256)
-k_texel_buffer_selftest(const uint32_t* texels, uint32_t n, unsigned long long* out) {
+k_texel_buffer_selftest(const uint32_t* buf, uint32_t lead, uint32_t n, unsigned long long* out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    const uint32_t* texels = buf + lead;
     const float4 d = texel_f32(level_texel_buffer(texels), i);
     const uint32_t t = texels[i];
     const float want[4] = {vct_unorm8_to_float(t & 0xffu), vct_unorm8_to_float((t >> 8) & 0xffu),
@@ -2173,12 +2221,17 @@ k_texel_buffer_selftest(const uint32_t* texels, uint32_t n, unsigned long long* 
     const float got[4] = {d.x, d.y, d.z, d.w};
     for (int ch = 0; ch < 4; ++ch)
         if (__float_as_uint(got[ch]) != __float_as_uint(want[ch])) { atomicAdd(&out[0], 1ull); out[1] = t; }
+    const vct_v4i32 chain = level_texel_buffer(buf);
+    const float4 o1 = texel_f32(chain, i, lead * 4u), o2 = texel_f32(chain, i, (lead + n) * 4u);
+    const float via[8] = {o1.x, o1.y, o1.z, o1.w, o2.x, o2.y, o2.z, o2.w};
+    for (int k = 0; k < 8; ++k)
+        if (__float_as_uint(via[k]) != __float_as_uint(got[k & 3])) { atomicAdd(&out[2], 1ull); out[3] = t; }
 }
 
 }  // namespace
 
-hipError_t vct_launch_texel_buffer_selftest(const uint32_t* texels, uint32_t n, unsigned long long* out, hipStream_t s) {
-    hipLaunchKernelGGL(k_texel_buffer_selftest, dim3((n + 255u) / 256u), dim3(256), 0, s, texels, n, out);
+hipError_t vct_launch_texel_buffer_selftest(const uint32_t* buf, uint32_t lead, uint32_t n, unsigned long long* out, hipStream_t s) {
+    hipLaunchKernelGGL(k_texel_buffer_selftest, dim3((n + 255u) / 256u), dim3(256), 0, s, buf, lead, n, out);
     return hipGetLastError();
 }
 
@@ -2267,7 +2320,9 @@ hipError_t vct_launch_trace(const VctTraceParams& params, int variant, hipStream
     p.tile_shift = td.shift;
     vct_light_unit(p.light, p.light_unit);
     const bool loose = variant == 3 && !p.aniso;
-    if (march_form) *march_form = loose ? 3 : (p.fast_div ? 2 : 1);
+    // (bits 8-9: how the launch's typed loads reach a level -- 2 one resource per wave, the CHAIN forms; 1 one per level)
+    const bool chain = variant == 0 && !loose && !p.vt_pix && !p.dr_ind && takes_chain_form(p);
+    if (march_form) *march_form = (loose ? 3 : (p.fast_div ? 2 : 1)) | ((chain ? 2 : 1) << 8);
     if (p.ntiles <= 0) return hipSuccess;
     if ((rstride > 1 || p.pack_rows) && !vct_variant_takes_row_subsets(variant)) return hipErrorInvalidValue;
     if (p.pix_gloss && (variant != 0 || p.aniso || p.cells_biased || !p.comp || !p.gloss)) return hipErrorInvalidValue;

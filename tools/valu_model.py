@@ -13,6 +13,11 @@ gather: see main) and prices every VALU instruction with the issue cost MEASURED
 4-cycle ops).  Each block is weighted with the frequency at which the instrumented build executes it
 (profiles/r07_reuse_stats.json: tools/trace_stats.py on the default workload).
 
+Round 18 adds the scalar table: scalar-ALU instructions and branches of every segment and of every route of a level
+sample (held block filled / all zero, fresh block filled / all zero, per lane) x the same frequencies, so that the
+scalar stream per wave-step can be set against SQ_INSTS_SALU per launch route by route.  `--source FILE` prices another
+copy of vct_trace.hip (the parent's, for the predicted difference); nothing is written then.
+
 Output: VALU instructions and issue cycles per wave-step and the mean issue cycles per instruction -- the factor
 bench.py uses for `roofline.valu_pipe_busy_model` (profiles/valu_model.json, keyed by the kernel-source sha).
 The segmentation relies on the block layout the compiler currently emits; the script checks the instruction
@@ -59,12 +64,26 @@ def price(lines):
     return len(ops), sum(COST[classify(o)] for o in ops)
 
 
+NOT_SALU = ("s_waitcnt", "s_nop", "s_setprio", "s_load", "s_buffer_load", "s_barrier", "s_endpgm", "s_sleep")
+
+
+def scalars(lines):
+    """(scalar-ALU instructions, branches) of a block: what the scalar pipe issues, without waits, loads and priority."""
+    ops = [ln.split()[0] for ln in lines if re.match(r"\s+s_", ln)]
+    br = sum(1 for o in ops if o.startswith(("s_cbranch", "s_branch")))
+    return sum(1 for o in ops if not o.startswith(NOT_SALU)) - br, br
+
+
 def main():
     src = os.path.join(ROOT, "voxel-cone-tracing_amd", "csrc", "vct_trace.hip")
+    other = "--source" in sys.argv
+    if other:
+        src = sys.argv[sys.argv.index("--source") + 1]
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.join(tmp, "t.s")
         subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off",
-                        "-fno-slp-vectorize", "-fPIC", "-Wno-unused-function", "-S", "--cuda-device-only", "-o", out, src],
+                        "-fno-slp-vectorize", "-fPIC", "-Wno-unused-function", "-S", "--cuda-device-only",
+                        "-I", os.path.join(ROOT, "voxel-cone-tracing_amd", "csrc"), "-I", os.path.join(ROOT, "include"), "-o", out, src],
                        check=True, capture_output=True)
         text = open(out).read()
     m = re.search(r"^_ZN12_GLOBAL__N_118k_trace_tile_splitILb1ELi1ELb0ELb0ELb0ELb1ELb0ELb0ELb0ELb0ELb1EEEv14VctTraceParams:.*?\.end_amdhsa_kernel", text, re.S | re.M)
@@ -105,7 +124,7 @@ def main():
     f_fetch, f_write = (stats["coop_zero"] + stats["coop_hit"]) / n_s, stats["coop_hit"] / n_s
     f_gather = f_write + (reused - reused_zero) / n_s
     freq = {"coords": 1.0, "cand": f_cand, "hit": f_hit, "anchor": 1.0 - f_hit, "fetch": f_fetch, "write": f_write,
-            "gather": f_gather, "zero": 1.0 - f_gather, "lane": f_lane, "step": 1.0}
+            "gather": f_gather, "zero": 1.0 - f_gather, "lane": f_lane, "route": 1.0, "step": 1.0}
     second = n_s / stats["wave_steps"] - 1.0          # level samples per wave-step: the second level only where two_levels
 
     def kind(b):
@@ -122,6 +141,8 @@ def main():
         if "s_setprio 0" in t: return "hit"
         if "s_setprio 1" in t and nv <= 6: return "lane"      # (the per-lane path's preamble)
         if nv == 4 and all("v_mov_b32" in ln for ln in b if re.match(r"\s+v_", ln)): return "zero"
+        # round 18: a block that only compares and branches on the sampler's routing word (priced per sample in the scalar table)
+        if nv == 0 and "s_cmp" in t and sum(scalars(b)) <= 6 and "s_load" not in t and "s_add" not in t: return "route"
         return "step"
     kinds = [kind(b) for b in blocks]
     # the march is unrolled by two (cone_march): two identical steps per loop body -- model the first
@@ -129,7 +150,8 @@ def main():
     assert len(heads) == 2 and kinds.count("lane") >= 4 and kinds.count("gather") == 4, kinds
     first_step = range(heads[0] - 1 if heads[0] > 0 else 0, heads[1] - 1)
     seg = {}
-    n_step = c_step = 0.0
+    sseg = {1: {}, 2: {}}       # scalar table: level of the step -> segment -> [scalar-ALU instructions, branches]
+    n_step = c_step = s_step = b_step = 0.0
     level = 0
     for i in first_step:
         k = kinds[i]
@@ -138,11 +160,35 @@ def main():
         n, c = price(blocks[i])
         n_step += wgt * n; c_step += wgt * c
         e = seg.setdefault(k, [0, 0.0]); e[0] += n; e[1] = round(e[1] + c, 1)
+        sa, sb = scalars(blocks[i])
+        s_step += wgt * sa; b_step += wgt * sb
+        e = sseg[max(level, 1)].setdefault(k, [0, 0]); e[0] += sa; e[1] += sb
+    # routes of a level sample: the segments a route passes (static counts: every block of a segment, so a route's count
+    # is an upper bound where a segment holds blocks of more than one route -- `route`, the compare-and-branch blocks, is
+    # charged whole to every route) x the route's share of the level samples
+    ROUTES = {"held_filled": ("coords", "cand", "hit", "route", "gather"), "held_zero": ("coords", "cand", "hit", "route", "zero"),
+              "fresh_filled": ("coords", "anchor", "fetch", "write", "route", "gather"),
+              "fresh_zero": ("coords", "anchor", "fetch", "route", "zero"), "per_lane": ("coords", "anchor", "route", "zero", "lane")}
+    f_route = {"held_filled": (reused - reused_zero) / n_s, "held_zero": reused_zero / n_s, "fresh_filled": f_write,
+               "fresh_zero": stats["coop_zero"] / n_s, "per_lane": f_lane}
+    routes = {}
+    for lvl in (1, 2):
+        for r, ks in ROUTES.items():
+            routes[f"level{lvl}_{r}"] = {"scalar_alu": sum(sseg[lvl].get(k, [0, 0])[0] for k in ks),
+                                         "branches": sum(sseg[lvl].get(k, [0, 0])[1] for k in ks),
+                                         "share_of_level_samples": round(f_route[r], 4)}
     res = {"segments": seg, "segment_frequencies": {k: round(v, 4) for k, v in freq.items()},
            "second_level_samples_per_wave_step": round(second, 4),
            "valu_per_wave_step_model": round(n_step, 1), "issue_cycles_per_wave_step_model": round(c_step, 1),
            "model_issue_cycles_per_valu_instr": round(c_step / n_step, 3),
-           "cost_table_cycles": COST}
+           "cost_table_cycles": COST,
+           "scalar_segments": {f"level{l}": v for l, v in sseg.items()}, "scalar_routes": routes,
+           "salu_per_wave_step_model": round(s_step, 1), "branches_per_wave_step_model": round(b_step, 1),
+           "kernel_static": {"scalar": sum(sum(scalars([ln])) for ln in body), "v_readlane_writelane": sum(
+               1 for ln in body if re.match(r"\s+v_(readlane|writelane)", ln))}}
+    if other:
+        print(json.dumps(res, indent=1))
+        return
     import bench
     res["kernel_source_sha16"] = bench.kernel_source_sha()
     tt = os.path.join(ROOT, "profiles", "trace_traffic.json")
@@ -150,6 +196,7 @@ def main():
         t = json.load(open(tt))
         measured = t["wave_instructions_per_launch"]["valu"] / stats["wave_steps"]      # (the r07 statistics' wave steps)
         res["valu_per_wave_step_pmc"] = round(measured, 1)
+        res["salu_per_wave_step_pmc"] = round(t["wave_instructions_per_launch"]["salu"] / stats["wave_steps"], 1)
         res["pipe_busy_model"] = round(t["wave_instructions_per_launch"]["valu"] * res["model_issue_cycles_per_valu_instr"]
                                        / 1024.0 / t["gpu_cycles_per_launch"], 3)
         # the scalar pipe: one instruction per 4 cycles per SIMD (measured), SALU + SMEM instructions of the launch

@@ -586,8 +586,9 @@ __device__ __forceinline__ F4 sample_level_reuse(const ChainRef& chain, const Vc
     const Footprint f = footprint_of(lv, ux, uy, uz);
     // how the sample is served -- an integer, not flags: wave-uniform integers stay in one SGPR, while booleans merged
     // across branches become lane masks.  0: by no block (yet), 1: by an all-zero block, 2: by the block of the wave's
-    // slabs in which this lane's footprint starts at float4 `at`
-    int mode = 0, at = 0;
+    // slabs in which this lane's footprint starts at float4 `at` (set on the routes that gather and read on no other:
+    // a value for the rest is a v_mov on the routes that do not need it)
+    int mode = 0, at;
     // the second slab holds a block of this level: compared on the scalar unit, a sample without one pays nothing more
     if ((held.id & ~1u) == lv.off) {
         const BlockDesc cd = held;
@@ -601,7 +602,7 @@ __device__ __forceinline__ F4 sample_level_reuse(const ChainRef& chain, const Vc
         if (fit.out == 0ull) {
             // every live footprint lies inside it: the block is in LDS already, or known to be all zero -- nothing to fetch
             if (PRIO) __builtin_amdgcn_s_setprio(0);
-            mode = 1 + (int)(cd.id & 1u);
+            mode = 1 + (int)(cd.id - lv.off);       // 1 + the zero bit, as a difference: its range is the compiler's to guess (below)
             at = block_slot(act, fit.dx, fit.dy, fit.dz) + 64;
         }
     }
@@ -616,19 +617,35 @@ __device__ __forceinline__ F4 sample_level_reuse(const ChainRef& chain, const Vc
             if (PRIO) __builtin_amdgcn_s_setprio(0);
             const unsigned long long any_texel = block_texel_mask(d);
             if (VCT_STATS) { if (any_texel != 0ull) ++ms.coop_hit; else ++ms.coop_zero; }
-            mode = any_texel != 0ull ? 2 : 1;
-            if (SLAB == 1) held = {lv.off | (uint32_t)(mode - 1), an};
-            if (mode == 2) {
+            // (the descriptor's zero bit is written as a constant on either side of the ballot's branch: formed from
+            // the ballot, it came back from the vector unit through a v_cndmask and a v_readfirstlane)
+            mode = 1;
+            if (SLAB == 1) held = {lv.off, an};
+            if (any_texel != 0ull) {
+                mode = 2;
+                if (SLAB == 1) held.id = lv.off | 1u;
                 blk[SLAB * 64 + lb.lane] = d;
                 wave_sync();
                 at = block_slot(act, fit.dx, fit.dy, fit.dz) + SLAB * 64;
             }
         }
     }
-    if (mode == 2) return gather_block<NARROW>(blk + at, f.a, f.b, f.c);
-    if (mode == 1) return {0.0f, 0.0f, 0.0f, 0.0f};     // all 64 texels zero: every footprint sums to exactly +0
-    // incoherent footprints: the per-lane gather, which leaves the slabs and the descriptor alone
-    return sample_level<WRAP, false, LOOSE, false, PRIO, NARROW, CHAIN>(chain, lv, ux, uy, uz, act, am, blk, lb, ms);
+    // Round 18: the word is tested by two conditions of which the compiler cannot tell that one is the other's complement
+    // (it does not know that the word stays below 3).  Routes told apart by `if ... else` or by early returns come out of
+    // the compiler's structured control flow with a lane-mask flag -- set to -1 in front of the first side, cleared
+    // behind it, and-not-ed with exec and branched on in front of the second: six scalar instructions of routing around
+    // the gather where these two compares and branches are four, and the four v_mov of a zero result executed on the
+    // per-lane route as well.  (Routes that end in returns or gotos of their own compile to a word like this one, made
+    // by the compiler, or to more such flags; the gather once per route put the kernel into scratch:
+    // profiles/experiments/README.md, round 18.)
+    F4 r;
+    if (mode == 2) r = gather_block<NARROW>(blk + at, f.a, f.b, f.c);
+    if (mode < 2) {
+        r = {0.0f, 0.0f, 0.0f, 0.0f};     // all 64 texels zero: every footprint sums to exactly +0
+        // incoherent footprints: the per-lane gather, which leaves the slabs and the descriptor alone
+        if (mode == 0) r = sample_level<WRAP, false, LOOSE, false, PRIO, NARROW, CHAIN>(chain, lv, ux, uy, uz, act, am, blk, lb, ms);
+    }
+    return r;
 }
 
 // level SLAB (0: first, 1: second) of a march step, with or without block reuse; `blk` is the wave's first slab

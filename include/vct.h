@@ -811,6 +811,69 @@ int vct_get_lights(const vct_ctx* ctx, vct_light out[VCT_LIGHTS_MAX], int32_t* n
 int vct_download_pixel_lights(vct_ctx* ctx, float* planes /* linear [3][h*w] */);
 int vct_last_lights_ms(vct_ctx* ctx, float ms[2]);   /* [0] voxel kernel of the last inject, [1] pixel kernel of the slot's last composite launch */
 
+/* ---- dynamic mesh: moving objects voxelized into the chain per pass ----------------------------------------------------
+ * No reference counterpart (its scene never moves), so the definition is this build's.  Beside the uploaded (static)
+ * mesh a context may hold ONE dynamic mesh: ntri triangles, model-space fp32 positions [ntri][3][3], a material index per
+ * triangle and a flat albedo table [nmat][4] (rgb used), under the same config.model_scale, grid and vertex contract as the
+ * static mesh.  It has NO textures and NO emission.  vct_upload_triangles rebuilds the static plan (allocations, host
+ * sorts, synchronisations); the dynamic mesh has no plan: every pass voxelizes it anew on the stream.
+ *   A pass             vct_voxelize(VCT_VOX_CONSERVATIVE_AVG) + vct_inject_light, or vct_gi_pass, voxelizes the dynamic
+ *                      mesh BY ITSELF exactly as the static one: conservative overlap; per fragment the clamped
+ *                      barycentrics, the 25-tap PCF against the context's shadow map and unorm8(albedo * shadow); per voxel
+ *                      the rounded integer mean; with config.voxel_attributes the mean albedo and the quantised face normal.
+ *                      Bit for bit what the static voxelizer gives for the dynamic mesh alone under the same shadow map.
+ *   Merge              the dynamic mesh wins per voxel.  After the static resolve every voxel the dynamic layer occupies
+ *                      (fragment count > 0) takes the dynamic texel, every other voxel keeps the static result:
+ *                        level0 = D.a > 0 ? D : S
+ *                      Order inside vct_inject_light: static resolve (+ emission pool), the static voxels' local lights,
+ *                      the merge, the local lights over the dynamic layer's own attributes.  With lights the chain is
+ *                      D.a > 0 ? lit(D, Da, Dn) : lit(S', Sa, Sn), S' the static level 0 including emission.
+ *   Everything else    reads the chain and follows unchanged: sparse mip build, directional chains, footprint records,
+ *                      voxel view (radiance sources), point queries, screen trace, a rank's frame step.  The bricks the
+ *                      object left are clean after the next pass, mips included.
+ *   Positions          a pass uses those of the last vct_update_dynamic_positions issued before its vct_voxelize.
+ *   Vertex contract    a triangle with any coordinate v for which !(fabsf(v * model_scale) <= VCT_VERTEX_LIMIT_GRIDS *
+ *                      grid_world_size) -- product in fp32; NaN and the infinities included -- contributes no fragment,
+ *                      disturbs no other triangle and is counted (vct_get_dynamic [6]).  The rule is applied on the device
+ *                      and is the same for host and device positions: a device pointer cannot be checked on the host.
+ *   Capacity           the layer owns max_bricks 8^3 brick slots (26 KiB of device memory each with voxel attributes,
+ *                      10 KiB without).  A pass that touches more leaves the WHOLE dynamic layer out -- that pass is the
+ *                      static chain, deterministically; never "some" bricks -- and reports its need (vct_get_dynamic [3],
+ *                      [7]) so that the caller can attach again with more.  No error is raised.
+ * vct_set_dynamic_mesh attaches (replacing an attached one) or, with pos == NULL or ntri == 0, detaches.  It waits for
+ * work in flight and allocates everything the per-frame path needs.  max_bricks == 0: the library counts the bricks
+ * these positions touch and reserves twice that, at least 64; either way at most the grid's (V/8)^3.  The state survives
+ * vct_upload_triangles of a new static mesh.  After a detach the next pass clears what the object left; detached, every
+ * kernel launched is the one launched without this section.
+ * vct_update_dynamic_positions: new positions for the same triangles, host or device memory (vct_mem), copied into the
+ * context's own buffer on the selected slot's stream; asynchronous; ordered against the other slot like vct_voxelize.
+ * Device memory -- and host memory, to be safe -- must stay valid until the stream has passed the copy.
+ * With a dynamic mesh attached vct_update_dynamic_positions, vct_voxelize, vct_inject_light and vct_gi_pass allocate
+ * nothing, never wait for the stream and copy nothing to the host: the statistics are read by vct_get_dynamic only.
+ * vct_get_dynamic: out[0..2] = ntri, nmat, max_bricks; of the last resolved pass out[3] = bricks needed, [4] = bricks used
+ * (0 if left out), [5] = conservative fragments, [6] = triangles skipped by the vertex contract, [7] = 1 if the layer was
+ * left out for capacity.  Waits for the stream.  Nothing attached: all zero.
+ * vct_download_dynamic_voxels: the dynamic layer of the last resolved pass alone -- radiance before local lights, mean
+ * albedo, mean normal (the last two need config.voxel_attributes) -- dense linear V^3 * 4 bytes each, zero elsewhere; any
+ * pointer may be NULL.
+ * vct_last_dynamic_ms: device time of [0] the dynamic kernels of the last vct_voxelize and [1] the merge of the last
+ * vct_inject_light; needs vct_set_trace_timing on when they were issued (VCT_ERR_INVALID otherwise and before both ran).
+ * VCT_ERR_INVALID, nothing touched: ntri outside 1 .. VCT_DYNAMIC_TRIS_MAX, nmat < 1, max_bricks < 0, a material index
+ * out of range, a NULL table, an unknown location, an update without an attached mesh; and while a dynamic mesh is attached
+ * vct_voxelize(ctx, VCT_VOX_REFERENCE) (as with emission and lights) and vct_bounce -- the bounce walks the static slots'
+ * attributes; carrying the second bounce over the dynamic layer is a follow-up.
+ * Known limits: vct_render_shadow_map and vct_render_gbuffer keep drawing the static mesh only -- the dynamic object
+ * receives the static scene's shadow in the chain, casts none into the map and is invisible to the library's own main
+ * draw: callers with moving objects bring their pixels through vct_import_gbuffer.  The voxel view's albedo / normal
+ * sources and vct_download_voxel_attributes show the static pools. */
+#define VCT_DYNAMIC_TRIS_MAX (1 << 20)
+int vct_set_dynamic_mesh(vct_ctx* ctx, const float* pos, const int32_t* material, int32_t ntri,
+                         const float* albedo, int32_t nmat, int32_t max_bricks);
+int vct_update_dynamic_positions(vct_ctx* ctx, const float* pos, int32_t location);
+int vct_get_dynamic(vct_ctx* ctx, int32_t out[8]);
+int vct_download_dynamic_voxels(vct_ctx* ctx, uint8_t* radiance, uint8_t* albedo, uint8_t* normal);
+int vct_last_dynamic_ms(vct_ctx* ctx, float ms[2]);
+
 /* ---- two frames in flight (round 6) -----------------------------------------------------------------
  * The reference's Render() (VCT.h:146-190) issues GL commands; the driver starts frame k + 1 while frame k
  * drains -- nothing in R/main.cpp:77-94 waits for a frame.  A HIP stream does wait: each whole-frame trace

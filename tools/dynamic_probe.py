@@ -1,0 +1,182 @@
+"""ON THE GPU BOX: what a dynamic mesh costs (include/vct.h "dynamic mesh"), and what the only earlier route cost.
+
+The procedural atrium at 256^3 with its 4096^2 shadow map, one context.  A mover -- a tessellated box of about 1 k, 10 k
+and 100 k triangles, 6 world units across, crossing the hall above the floor, its positions in device memory as a
+renderer has them -- and per mover, medians over ROUNDS rounds:
+  * the two times of vct_last_dynamic_ms (slots + fragments kernels of vct_voxelize; the merge of vct_inject_light);
+  * update + vct_voxelize + vct_inject_light + vct_build_mips: HIP events on the stream, the host time until the four
+    calls have returned, and the wall time until the stream has finished;
+  * the same pass detached (static only), alternating with the attached one;
+  * the route a caller had before: vct_upload_triangles of static + mover concatenated, then the same pass -- wall time.
+    (Only the triangles are uploaded again, not the mesh attributes and textures a renderer would also have to hand
+    over: a lower bound of that route.)
+The chain with the mover differs from the static one (asserted); the detached chain is bit for bit the first one (asserted).
+DETACHED_ONLY=1: only the static pass and the resident step, through entry points every earlier version of the library
+has -- run from a checkout of the parent commit and from this tree alternately (tools/dynamic_probe.sh does).
+Writes dynamic_probe.txt (or dynamic_probe_detached.txt) to $OUT (default: tool_out/)."""
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import vctpkg  # noqa: E402
+
+vct = vctpkg.load()
+from voxel_cone_tracing_amd import scene as sc  # noqa: E402
+
+ROUNDS = int(os.environ.get("ROUNDS", "9"))
+STEPS = int(os.environ.get("STEPS", "40"))
+DETACHED_ONLY = os.environ.get("DETACHED_ONLY", "0") == "1"
+SIDES = [int(x) for x in os.environ.get("SIDES", "9,29,91").split(",")]       # 12 n^2 triangles: 972, 10092, 99372
+light = (0.0, 1.0, 0.25)
+w, h, S, V = 1920, 1080, 4096, 256
+MS = 0.05
+
+
+def ev():
+    return torch.cuda.Event(enable_timing=True)
+
+
+def stats(v):
+    v = np.array(v)
+    return f"{np.median(v):.4f} ms (min {v.min():.4f} max {v.max():.4f})"
+
+
+def box(n, size):
+    """A cube of edge `size` (model units) about the origin, every face n x n quads: [12 n^2, 3, 3] float64."""
+    g = np.linspace(-0.5 * size, 0.5 * size, n + 1)
+    a0, b0 = np.meshgrid(g[:-1], g[:-1], indexing="ij")
+    a1, b1 = np.meshgrid(g[1:], g[1:], indexing="ij")
+    quads = np.stack([np.stack([a0, b0], -1), np.stack([a1, b0], -1), np.stack([a1, b1], -1), np.stack([a0, b1], -1)], 2).reshape(-1, 4, 2)
+    tris = np.concatenate([quads[:, [0, 1, 2]], quads[:, [0, 2, 3]]])
+    faces = []
+    for axis in range(3):
+        for sgn in (-1.0, 1.0):
+            f = np.zeros((tris.shape[0], 3, 3))
+            f[..., (axis + 1) % 3] = tris[..., 0]
+            f[..., (axis + 2) % 3] = tris[..., 1]
+            f[..., axis] = sgn * 0.5 * size
+            faces.append(f)
+    return np.concatenate(faces)
+
+
+scene = sc.Scene(sc.ATRIUM, 1.0, 1234)
+cam = sc.default_camera(position=(-56.0, -9.0, 2.0), yaw=0.0, pitch=8.0)
+vp, lvp = sc.camera_view_proj(cam, w, h), sc.light_view_proj(light)
+ctx = vct.Context(vct.default_config(voxel_dim=V, width=w, height=h, shadow_map_size=S))
+ctx.upload_scene(scene)
+ctx.set_camera_position(tuple(cam.position))
+ctx.set_light_direction(light)
+ctx.render_shadow_map(lvp)
+st = torch.cuda.ExternalStream(ctx.stream())
+
+
+def timed_pass(before=None):
+    """(event ms, host ms of the calls, wall ms to the end of the stream) of [before +] voxelize + inject + mips"""
+    ctx.synchronize()
+    e = [ev(), ev()]
+    t0 = time.perf_counter()
+    with torch.cuda.stream(st):
+        e[0].record()
+        if before:
+            before()
+        ctx.voxelize(); ctx.inject_light(); ctx.build_mips()
+        e[1].record()
+    t1 = time.perf_counter()
+    ctx.synchronize()
+    t2 = time.perf_counter()
+    return e[0].elapsed_time(e[1]), (t1 - t0) * 1e3, (t2 - t0) * 1e3
+
+
+def step_ms():
+    ctx.set_trace_timing(False)
+    e = [ev(), ev()]
+    for _ in range(5):
+        ctx.trace_resident()
+    with torch.cuda.stream(st):
+        e[0].record()
+        for _ in range(STEPS):
+            ctx.trace_resident()
+        e[1].record()
+    ctx.synchronize()
+    ctx.set_trace_timing(True)
+    return e[0].elapsed_time(e[1]) / STEPS
+
+
+for _ in range(3):
+    timed_pass()
+ctx.render_gbuffer(vp)
+ctx.trace_resident()
+ctx.synchronize()
+
+out_dir = os.environ.get("OUT", os.path.join(ROOT, "tool_out"))
+os.makedirs(out_dir, exist_ok=True)
+if DETACHED_ONLY:
+    p = [timed_pass() for _ in range(ROUNDS)]
+    s = [step_ms() for _ in range(ROUNDS)]
+    txt = (f"dynamic_probe detached ({os.environ.get('LABEL', 'this tree')}): atrium {V}^3, {w}x{h}: voxelize + inject + mips "
+           f"{stats([x[0] for x in p])}, wall {stats([x[2] for x in p])}; resident step {stats(s)}")
+    print(txt)
+    with open(os.path.join(out_dir, "dynamic_probe_detached.txt"), "a") as f:
+        f.write(txt + "\n")
+    sys.exit(0)
+
+lines = [f"dynamic_probe: atrium {V}^3 ({scene.pos.shape[0]} static triangles), shadow map {S}^2, {ROUNDS} alternating rounds"]
+chain0 = ctx.download_chain()
+NPOS = 8
+for n in SIDES:
+    tris = box(n, 6.0 / MS)
+    ntri = tris.shape[0]
+    mat = (np.arange(ntri) % 3).astype(np.int32)
+    alb = np.array([[0.9, 0.2, 0.2, 1.0], [0.2, 0.9, 0.2, 1.0], [0.2, 0.2, 0.9, 1.0]], np.float32)
+    path = [np.array([x, -9.0, 1.0]) / MS for x in np.linspace(-30.0, 30.0, NPOS)]
+    host = [np.ascontiguousarray((tris + c[None, None, :]).reshape(-1, 9), np.float32) for c in path]
+    dev = [torch.from_numpy(a).cuda() for a in host]
+    torch.cuda.synchronize()
+    t = {k: [] for k in ("ev0", "host0", "wall0", "ev1", "host1", "wall1", "kvox", "kmerge", "up_wall", "up_ev")}
+    info = None
+    for r in range(ROUNDS):
+        ctx.set_dynamic_mesh(None)
+        timed_pass()
+        a = timed_pass()
+        t["ev0"].append(a[0]); t["host0"].append(a[1]); t["wall0"].append(a[2])
+        if r == 0:
+            assert np.array_equal(ctx.download_chain(), chain0), "detached is not what it was"
+        ctx.set_dynamic_mesh(host[0], mat, alb)
+        timed_pass(lambda: ctx.update_dynamic_positions(dev[1].data_ptr()))
+        k = 2 + r % (NPOS - 2)
+        a = timed_pass(lambda: ctx.update_dynamic_positions(dev[k].data_ptr()))
+        t["ev1"].append(a[0]); t["host1"].append(a[1]); t["wall1"].append(a[2])
+        ms = ctx.last_dynamic_ms()
+        t["kvox"].append(ms[0]); t["kmerge"].append(ms[1])
+        info = ctx.dynamic_info()
+        assert not info["left_out"], info
+        if r == 0:
+            assert not np.array_equal(ctx.download_chain(), chain0), "the mover changed nothing in the chain"
+    ctx.set_dynamic_mesh(None)
+    # the earlier route: the whole scene again, mover included
+    for r in range(ROUNDS):
+        k = 2 + r % (NPOS - 2)
+        pos = np.concatenate([scene.pos.reshape(-1, 9), host[k]])
+        material = np.concatenate([scene.material, mat + scene.albedo.shape[0]]).astype(np.int32)
+        albedo = np.concatenate([scene.albedo.reshape(-1, 4), alb])
+        a = timed_pass(lambda: ctx.upload_triangles(pos, material, albedo))
+        t["up_ev"].append(a[0]); t["up_wall"].append(a[2])
+    ctx.upload_scene(scene)
+    timed_pass()
+    lines += [f"mover of {ntri} triangles: bricks {info['bricks_used']} of {info['max_bricks']} slots, {info['fragments']} fragments",
+              f"  dynamic kernels (vct_voxelize) {stats(t['kvox'])}   merge (vct_inject_light) {stats(t['kmerge'])}",
+              f"  pass detached          events {stats(t['ev0'])}   host {stats(t['host0'])}   wall {stats(t['wall0'])}",
+              f"  update + pass attached events {stats(t['ev1'])}   host {stats(t['host1'])}   wall {stats(t['wall1'])}",
+              f"  re-upload + pass       events {stats(t['up_ev'])}   wall {stats(t['up_wall'])}",
+              f"  attached / re-upload wall: {np.median(t['wall1']) / np.median(t['up_wall']):.3f}"]
+    print("\n".join(lines[-6:]), flush=True)
+ctx.close()
+txt = "\n".join(lines)
+with open(os.path.join(out_dir, "dynamic_probe.txt"), "w") as f:
+    f.write(txt + "\n")

@@ -80,6 +80,8 @@ ABI_SYMBOLS = [
     "vct_set_sky", "vct_get_sky",
     "vct_import_gbuffer", "vct_import_gbuffer_rows", "vct_last_gbuffer_import_ms",
     "vct_set_lights", "vct_get_lights", "vct_download_pixel_lights", "vct_last_lights_ms",
+    "vct_set_dynamic_mesh", "vct_update_dynamic_positions", "vct_get_dynamic", "vct_download_dynamic_voxels",
+    "vct_last_dynamic_ms",
 ]
 
 
@@ -239,6 +241,11 @@ _lib.vct_set_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
 _lib.vct_get_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.vct_download_pixel_lights.argtypes = [C.c_void_p, C.c_void_p]
 _lib.vct_last_lights_ms.argtypes = [C.c_void_p, C.c_void_p]
+_lib.vct_set_dynamic_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]
+_lib.vct_update_dynamic_positions.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+_lib.vct_get_dynamic.argtypes = [C.c_void_p, C.c_void_p]
+_lib.vct_download_dynamic_voxels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.vct_last_dynamic_ms.argtypes = [C.c_void_p, C.c_void_p]
 _lib.vct_upload_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
 
 
@@ -641,6 +648,62 @@ class Context:
         trace timing must have been on for both."""
         v = (C.c_float * 2)()
         self._ck(_lib.vct_last_lights_ms(self._h, v), "vct_last_lights_ms")
+        return v[0], v[1]
+
+    # --- dynamic mesh (include/vct.h "dynamic mesh")
+    def set_dynamic_mesh(self, pos, material=None, albedo=None, max_bricks=0):
+        """Attaches the dynamic mesh: positions [ntri, 9] (model space), a material index per triangle and a flat albedo
+        table [nmat, 4]; pos None detaches.  max_bricks 0: twice the bricks these positions touch, at least 64.  Every
+        following voxelize + inject_light (or gi_pass) voxelizes it and merges it into level 0: it wins per voxel."""
+        if pos is None:
+            self._ck(_lib.vct_set_dynamic_mesh(self._h, None, None, 0, None, 0, 0), "vct_set_dynamic_mesh")
+            self._dyn_ntri = 0
+            return
+        pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 9)
+        material = np.ascontiguousarray(material, np.int32).reshape(-1)
+        albedo = np.ascontiguousarray(albedo, np.float32).reshape(-1, 4)
+        if material.shape[0] != pos.shape[0]:
+            raise VctError(f"set_dynamic_mesh: {material.shape[0]} material indices for {pos.shape[0]} triangles")
+        self._ck(_lib.vct_set_dynamic_mesh(self._h, _ptr(pos), _ptr(material), pos.shape[0], _ptr(albedo), albedo.shape[0],
+                                           int(max_bricks)), "vct_set_dynamic_mesh")
+        self._dyn_ntri = pos.shape[0]
+
+    def update_dynamic_positions(self, pos):
+        """New positions of the attached dynamic mesh's triangles: a float32 array [ntri, 9] or an int device pointer to
+        as many floats.  Asynchronous on the selected slot's stream; the next voxelize uses them."""
+        if isinstance(pos, int):
+            self._ck(_lib.vct_update_dynamic_positions(self._h, _ptr(pos), MEM_DEVICE), "vct_update_dynamic_positions")
+            return
+        pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 9)
+        ntri = getattr(self, "_dyn_ntri", 0)
+        if ntri and pos.shape[0] != ntri:
+            raise VctError(f"update_dynamic_positions: {pos.shape[0]} triangles, the attached mesh has {ntri}")
+        self._dyn_pos = pos          # stays alive until the stream has passed the copy
+        self._ck(_lib.vct_update_dynamic_positions(self._h, _ptr(pos), MEM_HOST), "vct_update_dynamic_positions")
+
+    def dynamic_info(self):
+        """ntri, nmat, max_bricks and, of the last resolved pass: bricks needed / used, fragments, triangles skipped by the
+        vertex contract, and whether the layer was left out for capacity.  Waits for the stream."""
+        v = (C.c_int32 * 8)()
+        self._ck(_lib.vct_get_dynamic(self._h, v), "vct_get_dynamic")
+        keys = ("ntri", "nmat", "max_bricks", "bricks_needed", "bricks_used", "fragments", "skipped", "left_out")
+        return dict(zip(keys, (int(x) for x in v)))
+
+    def download_dynamic_voxels(self):
+        """(radiance, albedo, normal) uint8 [V, V, V, 4]: the dynamic layer of the last resolved pass alone, zero elsewhere
+        (albedo and normal None without voxel_attributes)."""
+        V = self.cfg.voxel_dim
+        rad = np.zeros((V, V, V, 4), np.uint8)
+        alb = nrm = None
+        if self.cfg.voxel_attributes:
+            alb, nrm = np.zeros((V, V, V, 4), np.uint8), np.zeros((V, V, V, 4), np.uint8)
+        self._ck(_lib.vct_download_dynamic_voxels(self._h, _ptr(rad), _ptr(alb), _ptr(nrm)), "vct_download_dynamic_voxels")
+        return rad, alb, nrm
+
+    def last_dynamic_ms(self):
+        """(dynamic kernels of the last voxelize, merge of the last inject_light), device ms; trace timing must have been on."""
+        v = (C.c_float * 2)()
+        self._ck(_lib.vct_last_dynamic_ms(self._h, v), "vct_last_dynamic_ms")
         return v[0], v[1]
 
     def upload_shadow_map(self, depth, light_vp_rowmajor):

@@ -1,0 +1,233 @@
+// vct_api_dynamic.hip -- the C ABI of the dynamic mesh (include/vct.h "dynamic mesh"): a second, small mesh whose
+// positions change every frame, voxelized by itself in every pass and merged into level 0 behind the static resolve.
+// Everything the per-pass path needs is allocated by vct_set_dynamic_mesh; a pass with the mesh attached issues a memset
+// of four words and kernels on the selected slot's stream, nothing else.
+#include "vct_ctx.h"
+#include "vct_dynamic_check.h"
+
+namespace {
+
+// the voxelizer's parameters for the dynamic mesh: its own triangles and table, the context's grid and shadow map, no
+// plan and no textures
+VctVoxParams dyn_vox_params(const vct_ctx* c, const VctDynamic& d) {
+    VctVoxParams p;
+    memset(&p, 0, sizeof(p));
+    p.V = c->cfg.voxel_dim;
+    p.G = c->cfg.grid_world_size;
+    p.model_scale = c->cfg.model_scale;
+    p.pos = d.pos.get();
+    p.material = d.mat.get();
+    p.albedo = d.albedo.get();
+    p.ntri = d.ntri;
+    p.shadow = c->shadow.words.get();
+    p.shadow_tiles = c->shadow.words ? c->shadow.tiles.get() : nullptr;
+    p.shadow_ebase = c->shadow.ebase;
+    p.shadow_size = c->shadow.size;
+    memcpy(p.light_vp, c->shadow.light_vp, 64);
+    return p;
+}
+
+VctDynArgs dyn_args(const vct_ctx* c, const VctDynamic& d) {
+    VctDynArgs a;
+    memset(&a, 0, sizeof(a));
+    a.words = d.words.get();
+    a.brick_slot = d.brick_slot.get();
+    a.slot_brick = d.slot_brick.get();
+    a.big_list = d.big_list.get();
+    a.max_bricks = d.max_bricks;
+    a.vertex_limit = VCT_VERTEX_LIMIT_GRIDS * c->cfg.grid_world_size;
+    a.acc = d.acc.get();
+    a.acc_attr = d.acc_attr.get();
+    return a;
+}
+
+int launch_merge(vct_ctx* c, bool discard) {
+    VctDynamic& d = c->dyn;
+    VctDynMergeArgs a;
+    memset(&a, 0, sizeof(a));
+    a.d = dyn_args(c, d);
+    a.nbricks = (uint32_t)c->vol.nbricks();
+    a.set = 1 - d.set;
+    a.discard = discard ? 1 : 0;
+    a.res_brick = d.res_brick.get();
+    a.pool_rad = d.pool_rad.get(); a.pool_alb = d.pool_alb.get(); a.pool_nrm = d.pool_nrm.get();
+    a.level0 = c->vol.chain.get();
+    a.brick_prev = c->vol.brick_prev.get();
+    HIP_TRY(c, vct_launch_dynamic_merge(a, cur(c).stream.get()));
+    return VCT_OK;
+}
+
+// one pooled volume of the last resolved pass -> dense Morton -> linear staging -> host, synchronised
+int download_pool(vct_ctx* c, const uint32_t* pool, uint32_t* dense, uint8_t* dst) {
+    const VctDynamic& d = c->dyn;
+    hipStream_t s = cur(c).stream.get();
+    HIP_TRY(c, vct_launch_dynamic_unpool(pool, d.res_brick.get(), d.words.get(), d.set, d.max_bricks, (uint32_t)c->vol.nbricks(), dense, s));
+    PIPE_TRY(vct_staging_free(c));
+    HIP_TRY(c, c->vol.staging.reserve(c->vol.nvox()));
+    HIP_TRY(c, vct_launch_morton_to_linear(dense, c->vol.staging.get(), c->vol.V, s));
+    HIP_TRY(c, hipMemcpyAsync(dst, c->vol.staging.get(), c->vol.nvox() * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return VCT_OK;
+}
+
+}  // namespace
+
+int vct_dynamic_voxelize(vct_ctx* c) {
+    VctDynamic& d = c->dyn;
+    if (!d.attached()) return VCT_OK;
+    hipStream_t s = cur(c).stream.get();
+    if (d.pending) PIPE_TRY(launch_merge(c, true));      // a pass that was never resolved: accumulators and table back to empty
+    HIP_TRY(c, d.vox_timer.begin(s, c->time_traces));
+    HIP_TRY(c, hipMemsetAsync(d.words.get(), 0, 4 * sizeof(uint32_t), s));      // need, fragments, skipped, big triangles
+    HIP_TRY(c, vct_launch_dynamic_voxelize(dyn_vox_params(c, d), dyn_args(c, d), false, s));
+    HIP_TRY(c, d.vox_timer.end(s));
+    d.pending = true;
+    return VCT_OK;
+}
+
+int vct_dynamic_merge(vct_ctx* c) {
+    VctDynamic& d = c->dyn;
+    if (!d.attached() || !d.pending) return VCT_OK;
+    hipStream_t s = cur(c).stream.get();
+    HIP_TRY(c, d.merge_timer.begin(s, c->time_traces));
+    PIPE_TRY(launch_merge(c, false));
+    HIP_TRY(c, d.merge_timer.end(s));
+    d.set = 1 - d.set;
+    d.pending = false;
+    // local lights over the layer's own attribute pools: every slot is visited, a slot without a brick has empty pools
+    if (c->lights.n && d.pool_alb) {
+        VctLightVoxArgs la;
+        memset(&la, 0, sizeof(la));
+        la.lights = c->lights.table.get(); la.nlights = c->lights.n;
+        la.V = c->cfg.voxel_dim; la.G = c->cfg.grid_world_size;
+        la.level0 = c->vol.chain.get(); la.attr_albedo = d.pool_alb.get(); la.attr_normal = d.pool_nrm.get();
+        la.slot_brick = d.res_brick.get(); la.brick_prev = c->vol.brick_prev.get(); la.nslots = d.max_bricks;
+        HIP_TRY(c, vct_launch_light_voxels(la, s));
+    }
+    return VCT_OK;
+}
+
+extern "C" {
+
+int vct_set_dynamic_mesh(vct_ctx* c, const float* pos, const int32_t* material, int32_t ntri, const float* albedo,
+                         int32_t nmat, int32_t max_bricks) {
+    if (!c) return VCT_ERR_INVALID;
+    if (!pos || ntri == 0) {      // detach: the next static resolve clears what the object left (brick_prev is raised there)
+        if (!c->dyn.attached()) return VCT_OK;
+        HIP_TRY(c, hipSetDevice(c->device));
+        PIPE_TRY(vct_synchronize(c));         // a kernel in flight may still read the layer
+        c->dyn = VctDynamic();
+        return VCT_OK;
+    }
+    if (const char* why = vct_dynamic_check_args(pos, material, ntri, albedo, nmat, max_bricks))
+        return vct_fail(c, VCT_ERR_INVALID, std::string("vct_set_dynamic_mesh: ") + why);
+    const bool attr = c->cfg.voxel_attributes != 0;
+    const uint32_t nbricks = vct_dynamic_grid_bricks(c->cfg.voxel_dim);
+    HIP_TRY(c, hipSetDevice(c->device));
+    PIPE_TRY(vct_synchronize(c));
+    // all or nothing: a fresh layer in a local; the context keeps what it had until everything below has succeeded
+    VctDynamic d;
+    hipStream_t s = cur(c).stream.get();
+    VctDynamicSizes z = vct_dynamic_sizes(ntri, nmat, 0u, c->cfg.voxel_dim, attr);
+    if (!z.ok) return vct_fail(c, VCT_ERR_INVALID, "vct_set_dynamic_mesh: buffer sizes overflow");
+    HIP_TRY(c, d.pos.alloc((size_t)ntri * 9));
+    HIP_TRY(c, d.mat.alloc((size_t)ntri));
+    HIP_TRY(c, d.albedo.alloc((size_t)nmat * 4));
+    HIP_TRY(c, d.big_list.alloc((size_t)ntri));
+    HIP_TRY(c, d.words.alloc(VCT_DYN_WORDS));
+    HIP_TRY(c, d.brick_slot.alloc(nbricks));
+    HIP_TRY(c, hipMemcpyAsync(d.pos.get(), pos, z.pos, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(d.mat.get(), material, z.material, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(d.albedo.get(), albedo, z.albedo, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemsetAsync(d.words.get(), 0, z.words, s));
+    HIP_TRY(c, hipMemsetAsync(d.brick_slot.get(), 0xff, z.brick_slot, s));
+    d.ntri = ntri; d.nmat = nmat;
+    uint32_t touched = 0u;
+    if (max_bricks == 0) {
+        // the bricks these positions touch: the slots kernels with no slot to hand out, the counter read back
+        HIP_TRY(c, vct_launch_dynamic_voxelize(dyn_vox_params(c, d), dyn_args(c, d), true, s));
+        HIP_TRY(c, hipMemcpyAsync(&touched, d.words.get() + VCT_DYN_W_NEED, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        HIP_TRY(c, hipMemsetAsync(d.words.get(), 0, z.words, s));
+        HIP_TRY(c, hipMemsetAsync(d.brick_slot.get(), 0xff, z.brick_slot, s));
+    }
+    d.max_bricks = vct_dynamic_capacity(max_bricks, touched, nbricks);
+    z = vct_dynamic_sizes(ntri, nmat, d.max_bricks, c->cfg.voxel_dim, attr);
+    if (!z.ok) return vct_fail(c, VCT_ERR_INVALID, "vct_set_dynamic_mesh: buffer sizes overflow");
+    const size_t ns = d.max_bricks;
+    HIP_TRY(c, d.slot_brick.alloc(ns));
+    HIP_TRY(c, d.res_brick.alloc(ns));
+    HIP_TRY(c, d.acc.alloc(ns * 1024));
+    HIP_TRY(c, d.pool_rad.alloc(ns * 512));
+    HIP_TRY(c, hipMemsetAsync(d.slot_brick.get(), 0, z.slot_list, s));
+    HIP_TRY(c, hipMemsetAsync(d.res_brick.get(), 0, z.slot_list, s));
+    HIP_TRY(c, hipMemsetAsync(d.acc.get(), 0, z.acc, s));
+    HIP_TRY(c, hipMemsetAsync(d.pool_rad.get(), 0, z.pool, s));
+    if (attr) {
+        HIP_TRY(c, d.acc_attr.alloc(ns * 1536));
+        HIP_TRY(c, d.pool_alb.alloc(ns * 512));
+        HIP_TRY(c, d.pool_nrm.alloc(ns * 512));
+        HIP_TRY(c, hipMemsetAsync(d.acc_attr.get(), 0, z.acc_attr, s));
+        HIP_TRY(c, hipMemsetAsync(d.pool_alb.get(), 0, z.pool, s));
+        HIP_TRY(c, hipMemsetAsync(d.pool_nrm.get(), 0, z.pool, s));
+    }
+    HIP_TRY(c, d.vox_timer.create());           // the events now, so that no pass allocates
+    HIP_TRY(c, d.merge_timer.create());
+    HIP_TRY(c, hipStreamSynchronize(s));        // the caller's arrays are free again
+    c->dyn = std::move(d);
+    return VCT_OK;
+}
+
+int vct_update_dynamic_positions(vct_ctx* c, const float* pos, int32_t location) {
+    if (!c) return VCT_ERR_INVALID;
+    if (const char* why = vct_dynamic_check_update(c->dyn.attached(), pos, location))
+        return vct_fail(c, VCT_ERR_INVALID, std::string("vct_update_dynamic_positions: ") + why);
+    HIP_TRY(c, hipSetDevice(c->device));
+    PIPE_TRY(vct_pipeline_join(c));       // the buffer is shared: the other slot's pass may still read the previous positions
+    HIP_TRY(c, hipMemcpyAsync(c->dyn.pos.get(), pos, (size_t)c->dyn.ntri * 9 * sizeof(float),
+                              location == VCT_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, cur(c).stream.get()));
+    return VCT_OK;
+}
+
+int vct_get_dynamic(vct_ctx* c, int32_t out[8]) {
+    if (!c || !out) return VCT_ERR_INVALID;
+    memset(out, 0, 8 * sizeof(int32_t));
+    const VctDynamic& d = c->dyn;
+    if (!d.attached()) return VCT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    PIPE_TRY(vct_synchronize(c));         // the last merge may have been issued on the other frame slot's stream
+    uint32_t st[8] = {};
+    HIP_TRY(c, hipMemcpyAsync(st, d.words.get() + VCT_DYN_W_STATS + 8 * d.set, sizeof st, hipMemcpyDeviceToHost, cur(c).stream.get()));
+    HIP_TRY(c, hipStreamSynchronize(cur(c).stream.get()));
+    out[0] = d.ntri; out[1] = d.nmat; out[2] = (int32_t)d.max_bricks;
+    for (int k = 0; k < 5; ++k) out[3 + k] = (int32_t)st[k];
+    return VCT_OK;
+}
+
+int vct_download_dynamic_voxels(vct_ctx* c, uint8_t* radiance, uint8_t* albedo, uint8_t* normal) {
+    if (!c) return VCT_ERR_INVALID;
+    const VctDynamic& d = c->dyn;
+    if (!d.attached()) return vct_fail(c, VCT_ERR_INVALID, "vct_download_dynamic_voxels: no dynamic mesh attached");
+    if ((albedo || normal) && !d.pool_alb)
+        return vct_fail(c, VCT_ERR_INVALID, "vct_download_dynamic_voxels: albedo and normal need config.voxel_attributes = 1");
+    HIP_TRY(c, hipSetDevice(c->device));
+    PIPE_TRY(vct_synchronize(c));         // the pools may still be written on the other frame slot's stream
+    VctBuf<uint32_t> dense;
+    HIP_TRY(c, dense.alloc(c->vol.nvox()));
+    const uint32_t* src[3] = {d.pool_rad.get(), d.pool_alb.get(), d.pool_nrm.get()};
+    uint8_t* dst[3] = {radiance, albedo, normal};
+    for (int k = 0; k < 3; ++k)
+        if (dst[k]) PIPE_TRY(download_pool(c, src[k], dense.get(), dst[k]));
+    return VCT_OK;
+}
+
+int vct_last_dynamic_ms(vct_ctx* c, float ms[2]) {
+    if (!c || !ms) return VCT_ERR_INVALID;
+    const char* never = "vct_last_dynamic_ms: needs a dynamic mesh attached and a vct_voxelize + vct_inject_light since";
+    const char* untimed = "vct_last_dynamic_ms: the last kernels were issued with timing off (vct_set_trace_timing)";
+    if (!c->dyn.attached() || !c->dyn.vox_timer.have || !c->dyn.merge_timer.have) return vct_fail(c, VCT_ERR_INVALID, never);
+    PIPE_TRY(vct_timer_ms(c, c->dyn.vox_timer, &ms[0], never, untimed));
+    return vct_timer_ms(c, c->dyn.merge_timer, &ms[1], never, untimed);
+}
+
+}  // extern "C"

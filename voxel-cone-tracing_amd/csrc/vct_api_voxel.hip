@@ -113,6 +113,9 @@ int vct_voxelize(vct_ctx* c, int32_t mode) {
     if (mode == VCT_VOX_REFERENCE && c->lights.n)
         return vct_fail(c, VCT_ERR_INVALID, "vct_voxelize: VCT_VOX_REFERENCE is the reference's shaders as written and has no local lights "
                                         "(vct_set_lights(ctx, NULL, 0) first)");
+    if (mode == VCT_VOX_REFERENCE && c->dyn.attached())
+        return vct_fail(c, VCT_ERR_INVALID, "vct_voxelize: VCT_VOX_REFERENCE is the reference's shaders as written and has no dynamic mesh "
+                                        "(vct_set_dynamic_mesh(ctx, NULL, ...) first)");
     HIP_TRY(c, hipSetDevice(c->device));
     PIPE_TRY(vct_pipeline_join(c));       // the staging pool is shared: the other slot's resolve may still read the previous pass
     if (!c->vox.brick_slot || !c->vox.stage || (mode == VCT_VOX_REFERENCE && !c->vox.ref_big))
@@ -160,6 +163,7 @@ int vct_voxelize(vct_ctx* c, int32_t mode) {
             p.frag_alb = v.frag_alb.get();
         }
         HIP_TRY(c, vct_launch_voxelize(p, cur(c).stream.get()));      // one workgroup per brick: LDS accumulation + resolve into the staging pool
+        if (c->dyn.attached()) PIPE_TRY(vct_dynamic_voxelize(c));     // the dynamic mesh by itself, into its own accumulators
     }
     v.acc_pending = true;
     c->acc_mode = mode;
@@ -194,6 +198,8 @@ int vct_inject_light(vct_ctx* c) {
         HIP_TRY(c, vct_launch_light_voxels(la, cur(c).stream.get()));
         HIP_TRY(c, c->lights.vox_timer.end(cur(c).stream.get()));
     }
+    // the dynamic mesh wins per voxel (include/vct.h "dynamic mesh"): behind the static resolve and its lights
+    if (c->dyn.pending && c->acc_mode == VCT_VOX_CONSERVATIVE_AVG) PIPE_TRY(vct_dynamic_merge(c));
     c->vox.acc_pending = false;
     c->vol.level0_resolved();
     c->vox.attrs_valid = c->vox.attr_normal && c->acc_mode == VCT_VOX_CONSERVATIVE_AVG;
@@ -250,6 +256,9 @@ int vct_build_mips(vct_ctx* c) {
 
 int vct_bounce(vct_ctx* c) {
     if (!c) return VCT_ERR_INVALID;
+    if (c->dyn.attached())      // the bounce walks the static slots' attributes; carrying it over the dynamic layer is a follow-up
+        return vct_fail(c, VCT_ERR_INVALID, "vct_bounce: a dynamic mesh is attached and the second bounce does not see its voxels "
+                                        "(vct_set_dynamic_mesh(ctx, NULL, ...) first)");
     if (!c->cfg.voxel_attributes || !c->vox.attr_normal)
         return vct_fail(c, VCT_ERR_INVALID, "vct_bounce: needs config.voxel_attributes = 1 and a voxelize + inject pass");
     if (c->vox.acc_pending || !c->vol.mips_valid)

@@ -441,6 +441,30 @@ struct VctLights {
     VctTimer vox_timer;               // around k_light_voxels (vct_last_lights_ms [0])
 };
 
+// The dynamic mesh (include/vct.h "dynamic mesh", vct_api_dynamic.hip): the context's own copy of its triangles and
+// everything the per-pass path needs, allocated by vct_set_dynamic_mesh so that no pass allocates.  ntri == 0: none
+// attached.  Nothing here is indexed by the static mesh's slots: it survives vct_upload_triangles.
+struct VctDynamic {
+    int32_t ntri = 0, nmat = 0;
+    uint32_t max_bricks = 0;            // brick slots of the layer (vct_dynamic_check.h vct_dynamic_capacity)
+    VctBuf<float> pos;                  // [ntri][9] positions of the last update
+    VctBuf<int32_t> mat;                // [ntri]
+    VctBuf<float> albedo;               // [nmat][4]
+    VctBuf<int32_t> big_list;           // [ntri]
+    VctBuf<uint32_t> words;             // [VCT_DYN_WORDS] counters and the two statistics sets (vct_internal.h)
+    VctBuf<uint32_t> brick_slot;        // [V^3 / 512]
+    VctBuf<uint32_t> slot_brick;        // [max_bricks] of the pending pass
+    VctBuf<uint32_t> res_brick;         // [max_bricks] of the last resolved pass
+    VctBuf<unsigned long long> acc;     // [max_bricks][512][2]
+    VctBuf<unsigned long long> acc_attr;   // [max_bricks][512][3] (cfg.voxel_attributes)
+    VctBuf<uint32_t> pool_rad, pool_alb, pool_nrm;      // [max_bricks][512] of the last resolved pass
+    bool pending = false;               // the accumulators hold a pass no merge has resolved
+    int set = 0;                        // the statistics set of the last resolved pass
+    VctTimer vox_timer, merge_timer;    // vct_last_dynamic_ms
+
+    bool attached() const { return ntri > 0; }
+};
+
 struct vct_ctx {
     vct_config cfg;
     int device = 0;
@@ -466,6 +490,7 @@ struct vct_ctx {
     VctGloss gloss;
     VctSky sky;
     VctLights lights;
+    VctDynamic dyn;
     bool steps_dirty = true;
     bool fast_div = false;            // set by vct_refresh_steps: constant divisors admit the FMA division
     // set by vct_create: the default trace kernel runs in its CHAIN form, one texel buffer per wave and the level's byte
@@ -577,6 +602,10 @@ hipError_t vct_gloss_plane(const vct_ctx* c, VctFrameSlot& s, bool* fresh = null
 void vct_material_gloss_detach(vct_ctx* c);
 // vct_api_lights.hip: zeroed lit planes for a slot that has none, the timer around their kernel started over
 hipError_t vct_lights_planes(const vct_ctx* c, VctFrameSlot& s, bool* fresh = nullptr);
+// vct_api_dynamic.hip: the dynamic mesh's part of vct_voxelize (discard of an unresolved pass, slots, fragments) and of
+// vct_inject_light (merge into level 0, its local lights), on the selected slot's stream; nothing attached: nothing issued
+int vct_dynamic_voxelize(vct_ctx* c);
+int vct_dynamic_merge(vct_ctx* c);
 // vct_multi.hip: slab of the attached communicator (false: none attached); its release
 bool vct_comm_rows(const vct_ctx* c, int* row0, int* row1);
 void vct_comm_release(vct_ctx* c);

@@ -1,0 +1,91 @@
+// vct_dynamic_check.h -- argument checks, the default-capacity rule and the buffer-size arithmetic of the dynamic mesh
+// (vct_api_dynamic.hip), free of any HIP call so that a host program can run them under the sanitizers
+// (tests/dynamic_check_main.cpp).
+#ifndef VCT_DYNAMIC_CHECK_H_
+#define VCT_DYNAMIC_CHECK_H_
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/vct.h"
+
+#define VCT_DYNAMIC_MIN_BRICKS 64
+
+// What is wrong with the arguments of an attaching vct_set_dynamic_mesh (pos != NULL and ntri != 0), or null.
+static inline const char* vct_dynamic_check_args(const float* pos, const int32_t* material, int32_t ntri, const float* albedo,
+                                                 int32_t nmat, int32_t max_bricks) {
+    if (!pos) return "null positions";
+    if (ntri < 1 || ntri > VCT_DYNAMIC_TRIS_MAX) return "ntri outside 1 .. VCT_DYNAMIC_TRIS_MAX";
+    if (!material) return "null material indices";
+    if (!albedo) return "null albedo table";
+    if (nmat < 1) return "nmat < 1";
+    if (max_bricks < 0) return "max_bricks < 0";
+    for (int32_t i = 0; i < ntri; ++i)
+        if (material[i] < 0 || material[i] >= nmat) return "material index out of range";
+    return nullptr;
+}
+
+// What is wrong with the arguments of vct_update_dynamic_positions, or null.
+static inline const char* vct_dynamic_check_update(bool attached, const float* pos, int32_t location) {
+    if (!attached) return "no dynamic mesh attached";
+    if (!pos) return "null positions";
+    if (location != VCT_MEM_HOST && location != VCT_MEM_DEVICE) return "location is neither VCT_MEM_HOST nor VCT_MEM_DEVICE";
+    if ((uintptr_t)pos & 3u) return "positions need 4-byte alignment";
+    return nullptr;
+}
+
+// 8^3 bricks of a grid of V^3 voxels (V a power of two, 8 .. 1024: at most 2^21)
+static inline uint32_t vct_dynamic_grid_bricks(int32_t V) {
+    if (V < 8) return 0u;
+    const uint64_t b = (uint64_t)(V / 8);
+    return (uint32_t)(b * b * b);
+}
+
+// Brick slots of the dynamic layer.  asked > 0: as asked; asked == 0: twice the bricks the attached positions touch, at
+// least VCT_DYNAMIC_MIN_BRICKS.  Either way no more than the grid has: more can never be used.
+static inline uint32_t vct_dynamic_capacity(int32_t asked, uint32_t touched, uint32_t grid_bricks) {
+    uint64_t want;
+    if (asked > 0) want = (uint64_t)asked;
+    else {
+        want = 2ull * (uint64_t)touched;
+        if (want < VCT_DYNAMIC_MIN_BRICKS) want = VCT_DYNAMIC_MIN_BRICKS;
+    }
+    if (want > grid_bricks) want = grid_bricks;
+    return (uint32_t)want;
+}
+
+// Byte counts of every buffer of the dynamic layer.  ok == false: a count does not fit size_t (nothing is allocated).
+struct VctDynamicSizes {
+    bool ok;
+    size_t pos, material, albedo;       // [ntri][9] fp32, [ntri] int32, [nmat][4] fp32
+    size_t big_list;                    // [ntri] int32
+    size_t brick_slot;                  // [grid_bricks] uint32
+    size_t slot_list;                   // [slots] uint32 (two of them: claimed, resolved)
+    size_t acc, acc_attr;               // [slots][512][2] / [slots][512][3] uint64 (acc_attr 0 without voxel attributes)
+    size_t pool;                        // [slots][512] uint32 (radiance; with attributes also albedo and normal)
+    size_t words;                       // the counters and the two sets of statistics
+    size_t volume;                      // V^3 * 4: the dense staging of a download
+};
+static inline bool vct_dynamic_mul(size_t a, size_t b, size_t* out) { return !__builtin_mul_overflow(a, b, out); }
+static inline VctDynamicSizes vct_dynamic_sizes(int32_t ntri, int32_t nmat, uint32_t slots, int32_t V, bool attributes) {
+    VctDynamicSizes s = {};
+    if (ntri < 1 || ntri > VCT_DYNAMIC_TRIS_MAX || nmat < 1 || V < 8) return s;
+    const size_t nt = (size_t)ntri, nm = (size_t)nmat, ns = (size_t)slots, nb = (size_t)vct_dynamic_grid_bricks(V);
+    size_t vox = 0;
+    bool ok = vct_dynamic_mul(nt, 9 * sizeof(float), &s.pos);
+    ok = ok && vct_dynamic_mul(nt, sizeof(int32_t), &s.material);
+    ok = ok && vct_dynamic_mul(nm, 4 * sizeof(float), &s.albedo);
+    ok = ok && vct_dynamic_mul(nt, sizeof(int32_t), &s.big_list);
+    ok = ok && vct_dynamic_mul(nb, sizeof(uint32_t), &s.brick_slot);
+    ok = ok && vct_dynamic_mul(ns, sizeof(uint32_t), &s.slot_list);
+    ok = ok && vct_dynamic_mul(ns, (size_t)512 * 2 * sizeof(uint64_t), &s.acc);
+    if (attributes) ok = ok && vct_dynamic_mul(ns, (size_t)512 * 3 * sizeof(uint64_t), &s.acc_attr);
+    ok = ok && vct_dynamic_mul(ns, (size_t)512 * sizeof(uint32_t), &s.pool);
+    ok = ok && vct_dynamic_mul(nb, 512, &vox) && vct_dynamic_mul(vox, sizeof(uint32_t), &s.volume);
+    s.words = 32 * sizeof(uint32_t);
+    s.ok = ok;
+    if (!ok) { const VctDynamicSizes none = {}; return none; }
+    return s;
+}
+
+#endif

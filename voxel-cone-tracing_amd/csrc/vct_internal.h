@@ -567,6 +567,46 @@ hipError_t vct_launch_voxelize_reference(const VctVoxParams& p, int32_t* big_lis
                                          hipStream_t s);
 hipError_t vct_launch_bounce(const VctTraceParams& p, hipStream_t s);
 
+// ---- the dynamic mesh (include/vct.h "dynamic mesh"; k_dyn_* in vct_voxelize.hip) ----
+// Voxelized by itself every pass, with no plan: bricks are claimed in a [V^3/512] table (VCT_NO_SLOT -> VCT_DYN_CLAIMED ->
+// slot number), fragments meet in HBM accumulators [slot][512] laid out like acc2 / acc2_attr, and the merge behind the
+// static resolve turns them into texels.  Device words of the layer (VctDynArgs::words):
+#define VCT_DYN_CLAIMED 0xfffffffeu     // a brick whose winner has not stored its slot yet, or got none (capacity)
+#define VCT_DYN_W_NEED 0                // bricks the pending pass claimed = slot numbers drawn
+#define VCT_DYN_W_FRAGS 1               // its conservative fragments
+#define VCT_DYN_W_SKIPPED 2             // its triangles outside the vertex contract
+#define VCT_DYN_W_NBIG 3                // triangles in big_list
+#define VCT_DYN_W_STATS 8               // two sets of 8 words, written in turn by the merges: need, used, fragments, skipped, left out
+#define VCT_DYN_WORDS 32
+struct VctDynArgs {
+    uint32_t* words;                    // [VCT_DYN_WORDS]
+    uint32_t* brick_slot;               // [V^3 / 512]; all VCT_NO_SLOT between passes
+    uint32_t* slot_brick;               // [max_bricks] slot -> brick of the pending pass
+    int32_t* big_list;                  // [ntri] triangles whose box exceeds VCT_VOX_BIG voxels
+    uint32_t max_bricks;
+    float vertex_limit;                 // VCT_VERTEX_LIMIT_GRIDS * grid_world_size
+    unsigned long long* acc;            // [max_bricks][512][2] sumR | sumG << 32, sumB | count << 32
+    unsigned long long* acc_attr;       // [max_bricks][512][3] or null (config.voxel_attributes)
+};
+// slots (claim) then fragments, small triangles by a thread each, big ones by a workgroup each; p: mesh, grid, shadow map
+hipError_t vct_launch_dynamic_voxelize(const VctVoxParams& p, const VctDynArgs& d, bool slots_only, hipStream_t s);
+struct VctDynMergeArgs {
+    VctDynArgs d;
+    uint32_t nbricks;
+    int32_t set;                        // the statistics set this merge writes (the other holds the last resolved pass)
+    int32_t discard;                    // 1: only re-zero the accumulators and the table (a pass that was never resolved)
+    uint32_t* res_brick;                // [max_bricks] slot -> brick of the last resolved pass; 0 for a slot without one
+    uint32_t* pool_rad;                 // [max_bricks][512] the layer's texels, attributes (null without) of the last resolved pass
+    uint32_t* pool_alb;
+    uint32_t* pool_nrm;
+    uint32_t* level0;                   // [V^3] Morton
+    uint32_t* brick_prev;               // [V^3 / 512]
+};
+hipError_t vct_launch_dynamic_merge(const VctDynMergeArgs& a, hipStream_t s);
+// pooled [slot][512] of the resolved pass of statistics set `set` -> dense Morton volume (zero elsewhere)
+hipError_t vct_launch_dynamic_unpool(const uint32_t* pool, const uint32_t* res_brick, const uint32_t* words, int set,
+                                     uint32_t max_bricks, uint32_t nbricks, uint32_t* dense, hipStream_t s);
+
 // the voxel view (include/vct.h "voxel view", vct_voxview.hip)
 struct VctVoxViewParams {
     const uint32_t* texels;            // the viewed level (Morton), or the pooled attribute [slot][512] when brick_slot is set

@@ -947,6 +947,218 @@ k_unpool(const uint32_t* __restrict__ pooled, const uint32_t* __restrict__ brick
     }
 }
 
+// ---- the dynamic mesh (include/vct.h "dynamic mesh") ----------------------------------------------
+// A small mesh whose positions change every frame is voxelized by itself in every pass, with none of the plan above: no
+// fragment list, no sort, nothing the host reads.  Two launches per triangle class (a thread per triangle; a workgroup
+// per triangle whose box exceeds VCT_VOX_BIG voxels):
+//   slots      every brick an overlapped voxel lies in is claimed in the [V^3/512] table with one atomicCAS; the winner
+//              draws a slot number and stores slot -> brick and brick -> slot.  Nobody waits inside the kernel: a loser
+//              needs nothing of the winner before the next launch.  Slot numbers are racy, nothing indexed by brick is.
+//   fragments  (a launch later: the table is complete) every overlapped voxel's fragment -- frag_bary, frag_eval, the
+//              face normal of k_tri_nrm, operation for operation what the static pass evaluates -- is added to the slot's
+//              accumulators in HBM with 64-bit integer atomics, packed like acc2 / acc2_attr: any order gives the same
+//              sums.  If the pass claimed more bricks than the layer has slots the launch does nothing (a wave-uniform
+//              test of the counter word): the whole layer is left out, never "some" bricks.
+// k_dyn_merge, behind the static resolve, turns the sums into texels with resolve_voxel / resolve_attr.
+__device__ __forceinline__ bool dyn_in_contract(const VctVoxParams& p, const VctDynArgs& d, int t) {
+    const VctTri9 rec = *reinterpret_cast<const VctTri9*>(p.pos + (size_t)t * 9);
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) ok = ok && fabsf(rec.v[k] * p.model_scale) <= d.vertex_limit;      // false for NaN and infinities
+    return ok;
+}
+__device__ __forceinline__ void dyn_claim(const VctDynArgs& d, uint32_t brick) {
+    if (__hip_atomic_load(&d.brick_slot[brick], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != VCT_NO_SLOT) return;
+    if (atomicCAS(&d.brick_slot[brick], VCT_NO_SLOT, VCT_DYN_CLAIMED) != VCT_NO_SLOT) return;
+    const uint32_t s = atomicAdd(&d.words[VCT_DYN_W_NEED], 1u);
+    if (s < d.max_bricks) {       // (beyond the capacity the entry stays VCT_DYN_CLAIMED: the count goes on, k_dyn_merge sweeps the table)
+        d.slot_brick[s] = brick;
+        __hip_atomic_store(&d.brick_slot[brick], s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+// what the fragments of a triangle share: shadow coordinates and colour as setup_pass gives them, the quantised face
+// normal as k_tri_nrm stores it
+template <bool ATTR>
+__device__ __forceinline__ void dyn_pass_tri(const VctVoxParams& p, int t, const TriSetup& r, PassTri& q) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { q.dc[k] = r.dc[k]; q.alb[k] = r.alb[k]; q.nrm[k] = 0u; }
+    if (ATTR) {
+        F3 w[3];
+        load_world_tri(p, t, w);
+        const F3 fn = cross3(sub3(w[1], w[0]), sub3(w[2], w[0]));
+        const float fl = __builtin_sqrtf(dot3(fn, fn));
+        const float fc[3] = {__fdiv_rn(fn.x, fl), __fdiv_rn(fn.y, fl), __fdiv_rn(fn.z, fl)};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) q.nrm[k] = (uint32_t)((int)floorf(fc[k] * 127.0f + 0.5f) + 128);
+    }
+}
+template <bool ATTR>
+__device__ __forceinline__ void dyn_fragment(const VctVoxParams& p, const VctDynArgs& d, const TriSetup& r, const PassTri& q,
+                                             int i, int j, int k) {
+    float b0, b1;
+    frag_bary(r, i, j, k, b0, b1);
+    const FragValue fv = frag_eval(p, q, b0, b1, q.alb);
+    const uint32_t vox = vct_morton3((uint32_t)i, (uint32_t)j, (uint32_t)k);
+    const uint32_t slot = d.brick_slot[vox >> 9];
+    if (slot >= d.max_bricks) return;       // (cannot happen in a pass within capacity; never write outside the pools)
+    const size_t at = (size_t)slot * 512 + (vox & 511u);
+    atomicAdd(&d.acc[2 * at], (unsigned long long)fv.lit.r | ((unsigned long long)fv.lit.g << 32));
+    atomicAdd(&d.acc[2 * at + 1], (unsigned long long)fv.lit.b | (1ull << 32));
+    if (ATTR) {
+        atomicAdd(&d.acc_attr[3 * at], (unsigned long long)fv.alb.r | ((unsigned long long)fv.alb.g << 32));
+        atomicAdd(&d.acc_attr[3 * at + 1], (unsigned long long)fv.alb.b | ((unsigned long long)q.nrm[0] << 32));
+        atomicAdd(&d.acc_attr[3 * at + 2], (unsigned long long)q.nrm[1] | ((unsigned long long)q.nrm[2] << 32));
+    }
+}
+// one add per wave of the lanes' values to a counter word
+__device__ __forceinline__ void dyn_wave_add(uint32_t* word, uint32_t mine) {
+    for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off);
+    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(word, mine);
+}
+
+template <bool FRAGS, bool ATTR>
+__global__ void __launch_bounds__(256)
+k_dyn_tris(const VctVoxParams p, const VctDynArgs d) {
+    if (FRAGS && d.words[VCT_DYN_W_NEED] > d.max_bricks) return;
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t nfrag = 0u, skipped = 0u;
+    if (t < p.ntri) {
+        if (!dyn_in_contract(p, d, t)) skipped = 1u;
+        else {
+            TriSetup r;
+            setup_tri(p, t, r);
+            const long long cnt = tri_candidates(r);
+            if (cnt > VCT_VOX_BIG) {
+                if (!FRAGS) d.big_list[atomicAdd(&d.words[VCT_DYN_W_NBIG], 1u)] = t;      // (capacity ntri)
+            } else if (cnt > 0) {
+                if (!FRAGS) {
+                    uint32_t last = VCT_NO_SLOT;
+                    for_each_overlap(r, [&](int i, int j, int k) {
+                        ++nfrag;
+                        const uint32_t brick = vct_morton3((uint32_t)i, (uint32_t)j, (uint32_t)k) >> 9;
+                        if (brick != last) { dyn_claim(d, brick); last = brick; }
+                    });
+                } else {
+                    PassTri q;
+                    dyn_pass_tri<ATTR>(p, t, r, q);
+                    for_each_overlap(r, [&](int i, int j, int k) { dyn_fragment<ATTR>(p, d, r, q, i, j, k); });
+                }
+            }
+        }
+    }
+    if (!FRAGS) {
+        dyn_wave_add(&d.words[VCT_DYN_W_FRAGS], nfrag);
+        dyn_wave_add(&d.words[VCT_DYN_W_SKIPPED], skipped);
+    }
+}
+
+// the big triangles, a workgroup striding the box of each (as k_vox_plan_big): one huge triangle does not wait on a lane
+template <bool FRAGS, bool ATTR>
+__global__ void __launch_bounds__(256)
+k_dyn_big(const VctVoxParams p, const VctDynArgs d) {
+    if (FRAGS && d.words[VCT_DYN_W_NEED] > d.max_bricks) return;
+    const int n_big = min((int)d.words[VCT_DYN_W_NBIG], p.ntri);
+    for (int b = blockIdx.x; b < n_big; b += gridDim.x) {
+        const int t = d.big_list[b];
+        TriSetup r;
+        setup_tri(p, t, r);
+        PassTri q;
+        if (FRAGS) dyn_pass_tri<ATTR>(p, t, r, q);
+        const int nx = r.hi[0] - r.lo[0] + 1, ny = r.hi[1] - r.lo[1] + 1, nz = r.hi[2] - r.lo[2] + 1;
+        const long long cnt = (long long)nx * ny * nz;
+        uint32_t nfrag = 0u;
+        for (long long v = threadIdx.x; v < cnt; v += blockDim.x) {
+            const int i = r.lo[0] + (int)(v % nx);
+            const int j = r.lo[1] + (int)((v / nx) % ny);
+            const int k = r.lo[2] + (int)(v / ((long long)nx * ny));
+            if (!overlap(r, i, j, k)) continue;
+            if (!FRAGS) {
+                ++nfrag;
+                dyn_claim(d, vct_morton3((uint32_t)i, (uint32_t)j, (uint32_t)k) >> 9);
+            } else dyn_fragment<ATTR>(p, d, r, q, i, j, k);
+        }
+        if (!FRAGS) dyn_wave_add(&d.words[VCT_DYN_W_FRAGS], nfrag);
+    }
+}
+
+// Behind the static resolve (and the static light kernel), one wave per slot of the dynamic layer: the rounded means of
+// the slot's sums; texels with a fragment go into level 0 (the dynamic mesh wins per voxel), the brick's texels and
+// attributes into the layer's own pools (what k_light_voxels and the downloads read); accumulators and table entry go
+// back to zero / VCT_NO_SLOT and brick_prev is raised, so that the next static resolve restores or clears the brick and
+// the sparse mip build reduces it.  A slot that held a brick in the last resolved pass and holds none now gets empty
+// pools and brick 0 in the resolved list: k_light_voxels, launched over every slot, finds no occupied voxel there.
+// A pass beyond the capacity added nothing to the accumulators; its table -- claimed entries without a slot among
+// them -- is swept.  discard: only the accumulators and the table, for a pass that is never resolved.
+template <bool ATTR>
+__global__ void __launch_bounds__(256)
+k_dyn_merge(const VctDynMergeArgs a) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t gtid = blockIdx.x * blockDim.x + threadIdx.x, nthreads = gridDim.x * blockDim.x;
+    const uint32_t need = a.d.words[VCT_DYN_W_NEED];
+    const bool left_out = need > a.d.max_bricks;
+    const uint32_t used = left_out ? 0u : need;
+    const uint32_t* before = a.d.words + VCT_DYN_W_STATS + 8 * (1 - a.set);
+    const uint32_t top = a.discard ? used : max(used, min(before[1], a.d.max_bricks));
+    if (left_out)
+        for (uint32_t b = gtid; b < a.nbricks; b += nthreads) a.d.brick_slot[b] = VCT_NO_SLOT;
+    for (uint32_t sl = gtid >> 6; sl < top; sl += nthreads >> 6) {
+        const size_t pool = (size_t)sl * 512;
+        if (sl >= used) {
+            for (uint32_t v = lane; v < 512u; v += 64) {
+                a.pool_rad[pool + v] = 0u;
+                if (ATTR) { a.pool_alb[pool + v] = 0u; a.pool_nrm[pool + v] = 0u; }
+            }
+            if (lane == 0) a.res_brick[sl] = 0u;
+            continue;
+        }
+        const uint32_t b = a.d.slot_brick[sl];
+        if (b >= a.nbricks) continue;
+        for (uint32_t v = lane; v < 512u; v += 64) {
+            unsigned long long* g = a.d.acc + 2 * (pool + v);
+            const ulonglong2 s = make_ulonglong2(g[0], g[1]);
+            const uint32_t c = (uint32_t)(s.y >> 32);
+            if (c) { g[0] = 0ull; g[1] = 0ull; }
+            if (!a.discard) {
+                const uint32_t texel = resolve_voxel(s);
+                a.pool_rad[pool + v] = texel;
+                if (c) a.level0[(size_t)b * 512 + v] = texel;
+            }
+            if (ATTR) {
+                unsigned long long* ga = a.d.acc_attr + 3 * (pool + v);
+                uint32_t alb = 0u, nrm = 0u;
+                if (c) {
+                    resolve_attr(c, ga[0], ga[1], ga[2], alb, nrm);
+                    ga[0] = 0ull; ga[1] = 0ull; ga[2] = 0ull;
+                }
+                if (!a.discard) { a.pool_alb[pool + v] = alb; a.pool_nrm[pool + v] = nrm; }
+            }
+        }
+        if (lane == 0) {
+            a.d.brick_slot[b] = VCT_NO_SLOT;
+            if (!a.discard) { a.brick_prev[b] = 1u; a.res_brick[sl] = b; }
+        }
+    }
+    if (!a.discard && gtid == 0u) {
+        uint32_t* now = a.d.words + VCT_DYN_W_STATS + 8 * a.set;
+        now[0] = need; now[1] = used; now[2] = a.d.words[VCT_DYN_W_FRAGS]; now[3] = a.d.words[VCT_DYN_W_SKIPPED];
+        now[4] = left_out ? 1u : 0u;
+    }
+}
+
+// the layer's pooled texels or attributes of the last resolved pass into a zeroed dense Morton volume (downloads)
+__global__ void __launch_bounds__(256)
+k_dyn_unpool(const uint32_t* __restrict__ pool, const uint32_t* __restrict__ res_brick, const uint32_t* __restrict__ words,
+             int set, uint32_t max_bricks, uint32_t nbricks, uint32_t* __restrict__ dense) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t used = min(words[VCT_DYN_W_STATS + 8 * set + 1], max_bricks);
+    const uint32_t waves = (gridDim.x * blockDim.x) >> 6;
+    for (uint32_t sl = (blockIdx.x * blockDim.x + threadIdx.x) >> 6; sl < used; sl += waves) {
+        const uint32_t b = res_brick[sl];
+        if (b >= nbricks) continue;
+        for (uint32_t v = lane; v < 512u; v += 64) dense[(size_t)b * 512 + v] = pool[(size_t)sl * 512 + v];
+    }
+}
+
 }  // namespace
 
 // blocks of a grid-stride launch over n units of work: n, at most cap, at least one
@@ -1048,6 +1260,41 @@ hipError_t vct_launch_voxelize(const VctVoxParams& p, hipStream_t s) {
     const unsigned mblocks = capped_grid(p.nmulti, 256 * 16);
     if (p.stage_albedo) hipLaunchKernelGGL(k_vox_resolve_multi<true>, dim3(mblocks), dim3(256), 0, s, p, p.multi_slot, p.nmulti);
     else hipLaunchKernelGGL(k_vox_resolve_multi<false>, dim3(mblocks), dim3(256), 0, s, p, p.multi_slot, p.nmulti);
+    return hipGetLastError();
+}
+
+hipError_t vct_launch_dynamic_voxelize(const VctVoxParams& p, const VctDynArgs& d, bool slots_only, hipStream_t s) {
+    if (p.ntri <= 0) return hipSuccess;
+    const dim3 grid((p.ntri + 255) / 256), big(capped_grid((size_t)p.ntri, 512)), block(256);
+    const bool attr = d.acc_attr != nullptr;
+    // the big list is complete when the first launch has ended; every later one reads its length from the device word
+    hipLaunchKernelGGL((k_dyn_tris<false, false>), grid, block, 0, s, p, d);
+    hipLaunchKernelGGL((k_dyn_big<false, false>), big, block, 0, s, p, d);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || slots_only) return e;
+    if (attr) {
+        hipLaunchKernelGGL((k_dyn_tris<true, true>), grid, block, 0, s, p, d);
+        hipLaunchKernelGGL((k_dyn_big<true, true>), big, block, 0, s, p, d);
+    } else {
+        hipLaunchKernelGGL((k_dyn_tris<true, false>), grid, block, 0, s, p, d);
+        hipLaunchKernelGGL((k_dyn_big<true, false>), big, block, 0, s, p, d);
+    }
+    return hipGetLastError();
+}
+
+hipError_t vct_launch_dynamic_merge(const VctDynMergeArgs& a, hipStream_t s) {
+    const dim3 grid(capped_grid(((size_t)a.d.max_bricks + 3) / 4, 256 * 32)), block(256);      // one wave per slot
+    if (a.d.acc_attr) hipLaunchKernelGGL(k_dyn_merge<true>, grid, block, 0, s, a);
+    else hipLaunchKernelGGL(k_dyn_merge<false>, grid, block, 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t vct_launch_dynamic_unpool(const uint32_t* pool, const uint32_t* res_brick, const uint32_t* words, int set,
+                                     uint32_t max_bricks, uint32_t nbricks, uint32_t* dense, hipStream_t s) {
+    hipError_t e = hipMemsetAsync(dense, 0, (size_t)nbricks * 512 * sizeof(uint32_t), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_dyn_unpool, dim3(capped_grid(((size_t)max_bricks + 3) / 4, 256 * 32)), dim3(256), 0, s, pool, res_brick,
+                       words, set, max_bricks, nbricks, dense);
     return hipGetLastError();
 }
 

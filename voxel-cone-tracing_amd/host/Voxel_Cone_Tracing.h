@@ -374,6 +374,22 @@ struct Voxel_Cone_Tracing {
         return true;
     }
 
+    // The dynamic mesh (vct_set_dynamic_mesh, include/vct.h "dynamic mesh": the reference's scene never moves): a second,
+    // small mesh -- flat colours, no textures -- that every volume pass voxelizes anew and merges into the chain, so that
+    // moving it costs no upload of the scene.  After init.  pos == NULL detaches.  UpdateDynamicMesh hands over new
+    // positions of the same triangles (host memory, or device memory with VCT_MEM_DEVICE); the next volume pass uses
+    // them: every Render() under DynamicLight, DrawVoxelTexture() otherwise.  The library's own main draw does not show
+    // the object: its pixels come in through ImportGBuffer.  Not with Bounces = 2 or ReferenceVoxelization.
+    bool SetDynamicMesh(const float* pos, const int32_t* material, int32_t ntri, const float* albedo, int32_t nmat,
+                        int32_t max_bricks = 0) {
+        if (!ctx) return false;
+        return check(vct_set_dynamic_mesh(ctx, pos, material, ntri, albedo, nmat, max_bricks), "vct_set_dynamic_mesh");
+    }
+    bool UpdateDynamicMesh(const float* pos, int32_t location = VCT_MEM_HOST) {
+        if (!ctx) return false;
+        return check(vct_update_dynamic_positions(ctx, pos, location), "vct_update_dynamic_positions");
+    }
+
     // The sky: coefficients as vct_set_sky takes them (NULL: none), or the three colours of a gradient about `up` (NULL: +y)
     // through vcth_sky_gradient; picked up by the next Render().
     void SetSky(const float sh[9][3]) {

@@ -12,6 +12,13 @@
 //            [--gloss-classes TAN,SHIN[;TAN,SHIN...] --gloss MATERIAL=CLASS[;MATERIAL=CLASS...]]
 //            [--sky-gradient ZR,ZG,ZB;HR,HG,HB;GR,GG,GB[;UX,UY,UZ] | --sky-sh FILE] [--reimport]
 //            [--light X,Y,Z;R,G,B;RADIUS;SRC[;DX,DY,DZ;INNER_DEG;OUTER_DEG]]...
+//            [--dynamic-obj FILE --dynamic-path X0,Y0,Z0;X1,Y1,Z1]
+// --dynamic-obj FILE: a second Wavefront OBJ as the context's dynamic mesh (Voxel_Cone_Tracing::SetDynamicMesh,
+//   vct_set_dynamic_mesh; flat material colours, its textures are not used), translated along the segment of
+//   --dynamic-path (model units, the OBJ's own; default: it stays where it is) over the run's frames.  Every Render()
+//   is then a whole GI pass, as with --dynamic-light, and hands over the frame's positions first.  The main draw does
+//   not show the object (a renderer brings its pixels through the G-buffer import); the voxels do.  Prints the two
+//   kernel times of vct_last_dynamic_ms.  Not with --gpus or --bounces 2.
 //
 // --light SPEC (repeatable, up to 64): a local light (Voxel_Cone_Tracing::SetLights, vct_set_lights) in world units: a point
 //   light at X,Y,Z of colour R,G,B (the factor at distance 1) that reaches RADIUS and whose inverse-square falloff is
@@ -155,6 +162,8 @@ int main(int argc, char** argv) {
     const char* sky_gradient_arg = nullptr;
     const char* sky_sh_arg = nullptr;
     std::vector<const char*> light_args;
+    const char* dynamic_obj = nullptr;
+    const char* dynamic_path = nullptr;
     int cubes[3] = {0, 0, 0};
     bool show_voxels = false;
     int view_source = VCT_VOXVIEW_CURRENT, view_level = 0;
@@ -201,6 +210,8 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--sky-gradient")) sky_gradient_arg = argv[++i];
         else if (!strcmp(argv[i], "--sky-sh")) sky_sh_arg = argv[++i];
         else if (!strcmp(argv[i], "--light") && i + 1 < argc) light_args.push_back(argv[++i]);
+        else if (!strcmp(argv[i], "--dynamic-obj")) dynamic_obj = argv[++i];
+        else if (!strcmp(argv[i], "--dynamic-path")) dynamic_path = argv[++i];
         else if (!strcmp(argv[i], "--ambient-cubes") && i + 2 < argc) {
             if (sscanf(argv[++i], "%d,%d,%d", &cubes[0], &cubes[1], &cubes[2]) != 3 || cubes[0] < 1 || cubes[1] < 1 || cubes[2] < 1 ||
                 (long long)cubes[0] * cubes[1] * cubes[2] * 6 > VCT_POINT_QUERY_MAX) {
@@ -235,6 +246,40 @@ int main(int argc, char** argv) {
             return 1;
         }
         lights.push_back(l);
+    }
+    // --dynamic-obj / --dynamic-path: the file and the segment before a GPU is touched
+    float dyn_path[2][3] = {};
+    std::vector<float> dyn_pos, dyn_albedo;
+    std::vector<int32_t> dyn_material;
+    int32_t dyn_ntri = 0, dyn_nmat = 0;
+    if (dynamic_path && !dynamic_obj) { fprintf(stderr, "--dynamic-path: needs --dynamic-obj\n"); return 1; }
+    if (dynamic_obj) {
+        if (gpus > 0 || bounces >= 2) { fprintf(stderr, "--dynamic-obj: not with --gpus or --bounces 2\n"); return 1; }
+        if (dynamic_path) {
+            int used = 0;
+            float* q = &dyn_path[0][0];
+            if (sscanf(dynamic_path, "%f,%f,%f;%f,%f,%f%n", q, q + 1, q + 2, q + 3, q + 4, q + 5, &used) != 6 || dynamic_path[used]) {
+                fprintf(stderr, "--dynamic-path: X0,Y0,Z0;X1,Y1,Z1 in model units\n");
+                return 1;
+            }
+            for (int k = 0; k < 6; ++k)
+                if (!std::isfinite(q[k])) { fprintf(stderr, "--dynamic-path: finite numbers\n"); return 1; }
+        }
+        char err[256] = "";
+        vcth_scene* obj = vcth_scene_load_obj(dynamic_obj, err);
+        if (!obj) { fprintf(stderr, "--dynamic-obj: cannot load '%s' (%s)\n", dynamic_obj, err); return 1; }
+        dyn_ntri = vcth_scene_num_triangles(obj);
+        dyn_nmat = vcth_scene_num_materials(obj);
+        if (dyn_ntri < 1 || dyn_ntri > VCT_DYNAMIC_TRIS_MAX || dyn_nmat < 1) {
+            fprintf(stderr, "--dynamic-obj: %d triangles, a dynamic mesh takes 1 .. %d\n", (int)dyn_ntri, VCT_DYNAMIC_TRIS_MAX);
+            vcth_scene_destroy(obj);
+            return 1;
+        }
+        dyn_pos.resize((size_t)dyn_ntri * 9); dyn_albedo.resize((size_t)dyn_nmat * 4); dyn_material.resize((size_t)dyn_ntri);
+        std::vector<float> unused_specular((size_t)dyn_nmat * 3);
+        vcth_scene_get(obj, dyn_pos.data(), dyn_material.data(), dyn_albedo.data(), unused_specular.data());
+        vcth_scene_destroy(obj);
+        dynamic_light = true;                               // a whole GI pass per frame: the volume follows the object
     }
     float sky_sh[9][3] = {};                                // --sky-gradient / --sky-sh: before a GPU is touched
     if (sky_gradient_arg && sky_sh_arg) { fprintf(stderr, "--sky-gradient and --sky-sh: one sky per context\n"); return 1; }
@@ -340,7 +385,25 @@ int main(int argc, char** argv) {
     if (sky_gradient_arg || sky_sh_arg) voxel_cone_tracing.SetSky(sky_sh);      // picked up by the first Render()
     if (!lights.empty()) voxel_cone_tracing.SetLights(lights.data(), lights.size());
 
+    // --dynamic-obj: the object's positions for every frame of the run (an update is asynchronous: each frame's array
+    // stays where it is until the run has finished), attached at the first
+    std::vector<std::vector<float>> dyn_frames;
+    if (dynamic_obj) {
+        dyn_frames.resize((size_t)(frames > 1 ? frames : 1));
+        for (size_t f = 0; f < dyn_frames.size(); ++f) {
+            const float t = dyn_frames.size() > 1 ? (float)f / (float)(dyn_frames.size() - 1) : 0.0f;
+            dyn_frames[f] = dyn_pos;
+            for (size_t i = 0; i < dyn_frames[f].size(); ++i)
+                dyn_frames[f][i] += dyn_path[0][i % 3] + t * (dyn_path[1][i % 3] - dyn_path[0][i % 3]);
+        }
+        if (!voxel_cone_tracing.SetDynamicMesh(dyn_frames[0].data(), dyn_material.data(), dyn_ntri, dyn_albedo.data(), dyn_nmat)) return 3;
+    }
+    auto move_dynamic = [&](int f) {                        // frame f's positions, before its Render()
+        return !dynamic_obj || voxel_cone_tracing.UpdateDynamicMesh(dyn_frames[(size_t)f % dyn_frames.size()].data());
+    };
+
     float delta_time = 0.05f;
+    if (!move_dynamic(0)) return 3;
     voxel_cone_tracing.Render();                            // frame 0 pays first-launch costs
     voxel_cone_tracing.Finish();
     if (voxel_cone_tracing.last_status != VCT_OK) return 3;
@@ -348,6 +411,7 @@ int main(int argc, char** argv) {
     auto t0 = std::chrono::steady_clock::now();
     for (int f = 1; f < frames; ++f) {
         camera.ProcessKeyBoard(FORWARD, delta_time);
+        if (!move_dynamic(f)) return 3;
         voxel_cone_tracing.Render();
         if (voxel_cone_tracing.last_status != VCT_OK) return 3;
     }
@@ -360,6 +424,7 @@ int main(int argc, char** argv) {
         const vec3 keep = camera.position;
         auto t1 = std::chrono::steady_clock::now();
         for (int f = 1; f < frames; ++f) {
+            if (!move_dynamic(f)) return 3;
             voxel_cone_tracing.Render();
             if (!voxel_cone_tracing.Frame()) return 3;
         }
@@ -378,6 +443,7 @@ int main(int argc, char** argv) {
     // (single GPU only: a rank's Render() is a collective step, and the other ranks are done)
     if (gpus <= 0) {
         vct_set_trace_timing(voxel_cone_tracing.ctx, 1);
+        if (!move_dynamic(frames > 1 ? frames - 1 : 0)) return 3;
         voxel_cone_tracing.Render();
         if (voxel_cone_tracing.last_status != VCT_OK) return 3;
     }
@@ -396,6 +462,16 @@ int main(int argc, char** argv) {
     }
     printf("frames=%d size=%dx%d voxels=%d cone_steps=%llu trace_ms=%.3f fnv1a=%016llx\n", frames, w, h,
            voxels, (unsigned long long)steps, ms, (unsigned long long)sum);
+    if (dynamic_obj) {                                      // what the last frame's pass made of the object
+        int32_t info[8] = {};
+        float dyn_ms[2] = {0.0f, 0.0f};
+        if (vct_get_dynamic(voxel_cone_tracing.ctx, info) != VCT_OK || vct_last_dynamic_ms(voxel_cone_tracing.ctx, dyn_ms) != VCT_OK) {
+            printf("%s\n", vct_last_error(voxel_cone_tracing.ctx));
+            return 3;
+        }
+        printf("dynamic mesh: triangles=%d bricks=%d of %d fragments=%d skipped=%d left_out=%d voxelize_ms=%.4f merge_ms=%.4f\n",
+               (int)info[0], (int)info[4], (int)info[2], (int)info[5], (int)info[6], (int)info[7], dyn_ms[0], dyn_ms[1]);
+    }
     if (reimport && gpus <= 0 && !show_voxels) {
         // the renderer "that brings its own G-buffer": the rasterised planes, packed as a deferred renderer keeps them
         const size_t npix = (size_t)w * h;

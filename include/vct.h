@@ -844,7 +844,9 @@ int vct_last_lights_ms(vct_ctx* ctx, float ms[2]);   /* [0] voxel kernel of the 
  * work in flight and allocates everything the per-frame path needs.  max_bricks == 0: the library counts the bricks
  * these positions touch and reserves twice that, at least 64; either way at most the grid's (V/8)^3.  The state survives
  * vct_upload_triangles of a new static mesh.  After a detach the next pass clears what the object left; detached, every
- * kernel launched is the one launched without this section.
+ * kernel launched is the one launched without this section.  Attached, replaced or detached between vct_voxelize and
+ * vct_inject_light, the fresh (or no) layer has no pass to resolve: that vct_inject_light gives the static chain, what the
+ * previous layer left is cleared, vct_get_dynamic of the fresh layer reports no resolved pass, and the next full pass merges it.
  * vct_update_dynamic_positions: new positions for the same triangles, host or device memory (vct_mem), copied into the
  * context's own buffer on the selected slot's stream; asynchronous; ordered against the other slot like vct_voxelize.
  * Device memory -- and host memory, to be safe -- must stay valid until the stream has passed the copy.

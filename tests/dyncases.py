@@ -42,6 +42,59 @@ def dynamic_mesh(C, ntri=NTRI):
     return pos, mat, alb
 
 
+def big_triangles(ntri=600, seed=5):
+    """(pos, material, albedo) of an object of large triangles: centres uniform within +-400 model units, vertices normal
+    with sigma 900 around them (the grid spans +-1500).  Nearly every box exceeds VCT_VOX_BIG voxels at 64^3, more of them
+    than k_dyn_big's grid has workgroups; the layer occupies every brick of the grid."""
+    r = np.random.default_rng(seed)
+    c = r.uniform(-400.0, 400.0, (ntri, 1, 3))
+    pos = (c + r.normal(scale=900.0, size=(ntri, 3, 3))).astype(np.float32).reshape(-1, 9)
+    mat, alb = materials(ntri)
+    return pos, mat, alb
+
+
+def crowd(ntri=200_000, seed=91):
+    """(offsets [ntri, 3, 3] float64, material, albedo) of an object of very many small triangles: centres uniform within
+    +-600 model units, vertices normal with sigma 8.  At 128^3 none is big and the object touches a few hundred bricks:
+    long enough on the GPU that the host's next call arrives while k_dyn_tris runs (tests/test_gpu_pipeline_features.py)."""
+    r = np.random.default_rng(seed)
+    off = r.uniform(-600.0, 600.0, (ntri, 1, 3)) + r.normal(scale=8.0, size=(ntri, 3, 3))
+    return (off,) + materials(ntri)
+
+
+def placed(off, C):
+    """Positions [ntri, 9] float32 of the object `off` moved to C."""
+    return (off + np.asarray(C, np.float64)[None, None, :]).astype(np.float32).reshape(-1, 9)
+
+
+VOX_BIG = 4096         # VCT_VOX_BIG (csrc/vct_voxelize.hip)
+
+
+def box_candidates(pos, ms=MS, G=G, V=V):
+    """tri_candidates of csrc/vct_voxelize.hip per triangle, int64 [ntri]: setup_tri's clipped bounding box, operation for
+    operation in fp32 (one rounding per product, quotient and sum: the library is built without contraction) -- 0 for a
+    triangle whose voxel-space normal is zero or NaN or whose box misses the grid, else the voxels of the box.  A triangle
+    goes to k_dyn_big when this exceeds VOX_BIG."""
+    f = np.float32
+    with np.errstate(invalid="ignore", over="ignore"):
+        w = np.asarray(pos, f).reshape(-1, 3, 3) * f(ms)
+        g = (w / f(G) + f(0.5)) * f(V)
+        e0, e1 = g[:, 1] - g[:, 0], g[:, 2] - g[:, 1]
+        n = np.stack([e0[:, 1] * e1[:, 2] - e0[:, 2] * e1[:, 1], e0[:, 2] * e1[:, 0] - e0[:, 0] * e1[:, 2],
+                      e0[:, 0] * e1[:, 1] - e0[:, 1] * e1[:, 0]], 1)
+        valid = ~((n == 0).all(1) | np.isnan(n).any(1))
+        lo = np.maximum(np.floor(g.min(1)).astype(np.int64), 0)
+        hi = np.minimum(np.floor(g.max(1)).astype(np.int64), V - 1)
+    ext = hi - lo + 1
+    return np.where(valid & (ext > 0).all(1), ext.prod(1), 0)
+
+
+def layer_plain(oracle, pos, mat, alb, ms=MS, G=G, V=V, depth=None, vp=None):
+    """Level 0 of a mesh alone from the voxelizer without attributes: the layer of a context with voxel_attributes = 0."""
+    p = oracle.default_params(V, G=G)
+    return oracle.voxelize_conservative(p, oracle.make_scene(pos, mat, alb, ms, shadow_depth=depth, light_vp=vp))
+
+
 def layer(oracle, pos, mat, alb, ms=MS, G=G, V=V, depth=None, vp=None):
     """(level 0, albedo, normal) of a mesh alone: what download_dynamic_voxels returns for it."""
     p = oracle.default_params(V, G=G)

@@ -23,7 +23,26 @@ was run on each:
   * vct_refresh_steps (behind vct_set_cone_apertures) without its vct_pipeline_drain, gloss classes attached:
     test_step_tables_rewritten_while_the_other_slot_traces fails.  (test_gpu_pipeline.py found this drain unobservable with
     the two tables of a context without classes; the class tables make the upload long enough to land in a running trace.)
+
+The dynamic mesh (include/vct.h "dynamic mesh") came after this file: its layer, the two sets of statistics and the one
+position buffer are shared by both slots.  Its four calls -- dyn_attach (two meshes to switch between: dyncases' object of
+150 triangles and dyncases.crowd(), 200 k small ones, so that k_dyn_tris is still running when the host issues the next
+call), dyn_update (host and device positions), dyn_detach, read_dynamic (vct_get_dynamic + vct_download_dynamic_voxels) --
+are drawn only by CallList(dynamic=True): DYN_SEEDS; the lists of SEEDS are, draw for draw, what they were (PARENT_LISTS).
+The model issues a bounce only detached and an update or a layer download only attached.  The directed orders at the end
+of the file are, beyond the comparison of the two runs, held against the CPU oracle: every chain read back is
+build_mips(merge(D, S)) for the mesh and positions resolved_states() says that pass used, every layer read back is D.
+Scratch builds, this file alone on each:
+  * vct_update_dynamic_positions without its vct_pipeline_join: every test passes.  The only readers of the position
+    buffer are the kernels of vct_voxelize / vct_gi_pass, and those calls are producers: vct_select_frame_slot puts the
+    stream selected next behind a producer (VctSlotOrder::produced), so the copy of an update issued on the other slot at
+    once already follows the pass; and a voxelize issued after an update on the other slot joins that slot's stream
+    itself.  The join in the update is a guarantee, not an observable.
+  * the detaching vct_set_dynamic_mesh without its vct_synchronize: every test passes.  The layer's buffers are released
+    with hipFree, which waits for the device itself.  A guarantee, not an observable -- it would become one the day the
+    buffers come from a pool.
 """
+
 import hashlib
 from concurrent.futures import ThreadPoolExecutor
 
@@ -31,6 +50,7 @@ import numpy as np
 import pytest
 
 import components_ref as cr
+import dyncases as dc
 import gloss_ref as gr
 import lights_ref as lr
 import sky_ref as sr
@@ -54,6 +74,12 @@ SKIES = [None, sr.SH, np.ascontiguousarray(sr.SH[:, ::-1] * np.float32(0.5))]
 GLOSS_TABLES = [None, list(gr.CLASSES[:3]), list(gr.CLASSES[1:3])]
 NPOINTS = 64 * 40 + 37
 SEEDS = [1, 2, 3, 4, 5, 6]
+DYN_SEEDS = [7, 8, 9]               # call lists that also draw the dynamic mesh's calls
+DYN_AT = [(0.0, 0.0, 200.0), (500.0, -300.0, 300.0), (-500.0, 200.0, -200.0)]      # where the moving object stands (model units)
+DYN_MESHES = 2                      # 0: dyncases' object of 150 triangles, 1: dyncases.crowd(), 200 k small ones
+# BLAKE2b-128 of repr(call_list(seed)) for SEEDS as the commit before the dynamic calls gave them: what those seeds run stays
+PARENT_LISTS = {1: "7a660e04415f52dafde5dcadd80a686d", 2: "e2f07c84814d189d6ed765f376e623e9", 3: "04d01e65d68d5c8947e75e807342ae87",
+                4: "12652795f3b626c8e5a8a69b0e248c50", 5: "0cd29f76f51ef54a9a66068164995224", 6: "8a095071283f9869ad42359f63b4fac5"}
 
 
 @pytest.fixture(scope="module")
@@ -67,8 +93,10 @@ def vct():
 class CallList:
     """The calls of one run and the state they leave, as far as legality and defined read-backs need it."""
 
-    def __init__(self, rng):
+    def __init__(self, rng, dynamic=False):
         self.rng, self.ops, self.slot = rng, [], 0
+        self.dynamic = dynamic              # draw the dynamic mesh's calls too (off: the lists of SEEDS, draw for draw)
+        self.dyn = None                     # the attached dynamic mesh (index), None: detached
         self.lights = self.sky = self.gloss = 0              # index into LIGHT_SETS / SKIES / GLOSS_TABLES
         self.matgloss = self.emission = self.bounced = False
         self.pending = False                # a voxelize pass waits for its inject_light
@@ -138,6 +166,49 @@ class CallList:
         self.matgloss = self.emission = False        # a new mesh detaches both material tables
         self.produce()
 
+    # -- the dynamic mesh: the layer, its statistics and its one position buffer are shared by both slots
+    def dyn_attach(self, mesh=None):
+        if mesh is None:
+            mesh = self.pick(DYN_MESHES) if self.dyn is None else (self.dyn + 1) % DYN_MESHES
+        self.dyn = mesh
+        self.add("dyn_attach", mesh, self.pick(len(DYN_AT)))
+
+    def dyn_update(self):
+        assert self.dyn is not None         # refused with nothing attached
+        self.add("dyn_update", self.pick(len(DYN_AT)), self.chance(0.5))      # position, device-located
+
+    def dyn_detach(self):
+        self.add("dyn_detach")
+        self.dyn = None
+
+    def read_dynamic(self):
+        assert self.dyn is not None         # the download is refused with nothing attached
+        self.add("read_dynamic")
+
+    def dyn_op(self):
+        """One of the dynamic calls, at once behind whatever the other slot has in flight; a new object or new positions
+        mostly with a pass behind them, so that later frames and read-backs see them."""
+        r = self.rng.random()
+        if self.dyn is None or r < 0.2:
+            self.dyn_attach()
+        elif r < 0.65:
+            self.dyn_update()
+        elif r < 0.8:
+            self.dyn_detach()
+            if self.chance(0.5):
+                self.revoxelize()
+            return
+        else:
+            self.read_dynamic()
+            return
+        r = self.rng.random()
+        if r < 0.4:
+            self.revoxelize()
+        elif r < 0.6:
+            self.gi()
+        if self.chance(0.4):
+            self.read_dynamic()
+
     # -- hand-overs of a G-buffer other than the raster pass
     def trace_host(self):
         self.add("trace_host", self.pick(2))         # a read-back as well: vct_trace returns the frame
@@ -201,6 +272,8 @@ class CallList:
         elif r == 9:
             if self.pending:
                 self.inject()              # a bounce is refused between voxelize and inject_light
+            if self.dyn is not None:
+                self.dyn_detach()          # ... and with a dynamic mesh attached
             self.add("bounce")
             self.bounced = True
             self.marched[self.slot] = True
@@ -261,6 +334,8 @@ class CallList:
             can += ["read_pixel_lights"] * 3
         if self.aov:
             can += ["read_aov"] * 3
+        if self.dyn is not None:
+            can += ["read_dynamic"] * 2
         what = can[self.pick(len(can))]
         if what == "gather":
             self.add("gather", self.chance(0.5), self.chance(0.5))                  # device-located, sorted
@@ -278,16 +353,21 @@ class CallList:
             self.add("read_chain")
         elif what == "read_frame":
             self.read_frame()
+        elif what == "read_dynamic":
+            self.read_dynamic()
         else:
             self.add(what)
 
 
-def call_list(seed, rounds=ROUNDS):
-    m = CallList(np.random.default_rng(seed))
+def call_list(seed, rounds=ROUNDS, dynamic=False):
+    m = CallList(np.random.default_rng(seed), dynamic)
     m.add("produce", 0)
     for r in (0, 1, 2, 4, 7):               # most runs begin with something attached: lights, a sky, gloss classes, emission, outputs
         if m.chance(0.6):
             m.setter(r)
+    if m.dynamic and m.chance(0.7):
+        m.dyn_attach()
+        m.revoxelize()
     for _ in range(rounds):
         s0 = m.pick(2)
         m.switch(s0)
@@ -308,11 +388,15 @@ def call_list(seed, rounds=ROUNDS):
         # ... and, while its trace is still running, the other slot at once: shared state rewritten, the slot's planes handed
         # over through the staging both slots share, or a read-back
         m.switch(1 - s0)
+        if m.dynamic and m.chance(0.7):
+            m.dyn_op()                     # the layer or the positions rewritten under the other slot's pass or frame
         m.setter()
         if m.chance(0.5):
             m.planes()
         m.reader()
         m.setter()
+        if m.dynamic and m.chance(0.5):
+            m.dyn_op()
         if m.gb[m.slot] and m.chance(0.5):
             m.trace()                      # the resident G-buffer under the new state, at once
             m.reader()
@@ -347,6 +431,9 @@ class Inputs:
         # two host-located linear G-buffers, from the raster pass of a context of its own
         ctx, _ = make(vct, w, h, V=v)
         ctx.render_shadow_map(sc.light_view_proj(self.dirs[0]))
+        # the shadow map of light 0 as the oracle takes it: what the directed dynamic orders voxelize under
+        self.shadow0 = ctx.download_shadow_map()
+        self.lvp0 = np.ascontiguousarray(np.asarray(sc.light_view_proj(self.dirs[0]), np.float32).reshape(4, 4).T)
         self.host_gb = []
         for pos, vp in self.cams[:2]:
             ctx.set_camera_position(pos)
@@ -390,6 +477,9 @@ class Inputs:
         self.d_out = torch.zeros((n, 4), dtype=torch.float32, device="cuda")
         self.d_cones = torch.zeros((n, 6, 4), dtype=torch.float32, device="cuda")
         self.d_steps = torch.zeros((n, 6), dtype=torch.uint8, device="cuda")
+        # the dynamic meshes (material, albedo, positions at each of DYN_AT), and the positions as device tensors
+        self.dyn = [(m[1], m[2], [dc.placed(m[0], at) for at in DYN_AT]) for m in ((dc.offsets(),) + dc.materials(), dc.crowd())]
+        self.dyn_dev = [[torch.from_numpy(p).cuda() for p in m[2]] for m in self.dyn]
         torch.cuda.synchronize()
 
 
@@ -418,6 +508,7 @@ def run(vct, inp, ops, sync):
     c, _ = make(vct, inp.w, inp.h, V=inp.v, voxel_attributes=1)
     c.set_frames_in_flight(2)
     mesh = 0
+    dyn = None
     records = []
     pool = ThreadPoolExecutor(max_workers=8)
 
@@ -539,6 +630,17 @@ def run(vct, inp, ops, sync):
                 level = 0 if op[1] >= vct.VOXVIEW_ALBEDO else 1
                 c.render_voxels(sc.invert_matrix(inp.cams[op[2]][1]), op[1], level)
                 record(k, op, c.download_frame())
+            elif name == "dyn_attach":
+                dyn = op[1]
+                mat, alb, at = inp.dyn[dyn]
+                c.set_dynamic_mesh(at[op[2]], mat, alb)
+            elif name == "dyn_update":
+                c.update_dynamic_positions(inp.dyn_dev[dyn][op[1]].data_ptr() if op[2] else inp.dyn[dyn][2][op[1]])
+            elif name == "dyn_detach":
+                dyn = None
+                c.set_dynamic_mesh(None)
+            elif name == "read_dynamic":
+                record(k, op, c.dynamic_info(), *c.download_dynamic_voxels())
             else:
                 raise AssertionError(op)
             if sync:
@@ -568,6 +670,21 @@ def test_the_call_lists_reach_every_call():
                     "sky", "gloss", "matgloss", "emission", "rate", "components", "aov", "bounce", "pixel_emission",
                     "pixel_gloss", "read_frame", "read_gbuffer", "read_pixel_emission", "read_pixel_gloss", "read_pixel_lights",
                     "read_aov", "read_chain", "gather", "cone", "voxels", "footprints", "remesh"}, sorted(seen)
+    assert not seen & {"dyn_attach", "dyn_update", "dyn_detach", "read_dynamic"}
+    for seed in DYN_SEEDS:                  # each of the lists with the dynamic mesh issues all four of its calls
+        ops = call_list(seed, dynamic=True)
+        assert {op[0] for op in ops} >= {"dyn_attach", "dyn_update", "dyn_detach", "read_dynamic", "bounce"}, seed
+        attached = False
+        for op in ops:                      # ... a bounce only detached, an update and a layer download only attached
+            attached = op[0] == "dyn_attach" or (attached and op[0] != "dyn_detach")
+            assert not (op[0] == "bounce" and attached) and not (op[0] in ("dyn_update", "read_dynamic") and not attached), (seed, op)
+
+
+def test_the_call_lists_of_the_earlier_seeds_are_what_they_were():
+    """The dynamic draws sit behind CallList's flag: without it the generator draws what it drew before they existed."""
+    for seed in SEEDS:
+        assert hashlib.blake2b(repr(call_list(seed)).encode(), digest_size=16).hexdigest() == PARENT_LISTS[seed], seed
+        assert call_list(seed, dynamic=True) != call_list(seed)
 
 
 @pytest.mark.parametrize("seed", SEEDS)
@@ -576,6 +693,14 @@ def test_random_call_orders_give_what_a_synchronised_context_gives(vct, inputs, 
     got, want = run(vct, inputs, ops, False), run(vct, inputs, ops, True)
     assert len(want) >= 2 * ROUNDS
     assert_same(got, want, ops, f"seed {seed}")
+
+
+@pytest.mark.parametrize("seed", DYN_SEEDS)
+def test_random_call_orders_with_the_dynamic_mesh(vct, inputs, seed):
+    ops = call_list(seed, dynamic=True)
+    got, want = run(vct, inputs, ops, False), run(vct, inputs, ops, True)
+    assert len(want) >= 2 * ROUNDS
+    assert_same(got, want, ops, f"seed {seed}, dynamic mesh")
 
 
 # (writer on slot 0, what its effect is read back with): each leaves work on slot 0's stream or has just used the staging
@@ -650,3 +775,133 @@ def test_step_count_of_a_bounce_while_the_other_slot_bounces(vct, inputs):
     ops = [("produce", 0), ("bounce",), ("switch", 1), ("bounce",), ("switch", 0), ("read_steps",), ("switch", 1), ("read_steps",)]
     got, want = run(vct, inputs, ops, False), run(vct, inputs, ops, True)
     assert_same(got, want, ops, "bounce, bounce")
+
+
+# ---- the dynamic mesh: directed orders, held against the oracle as well ---------------------------------------------------
+def resolved_states(ops):
+    """The model of a directed list (light 0 throughout; no lights, emission or bounce): call index -> what a read_chain
+    there holds -- None for the static chain, (mesh, position) for merge(D, S) of the layer the last resolved pass voxelized --
+    and what a read_dynamic there downloads -- the same, None for an empty layer.  A pass uses the positions of the last
+    dyn_update issued before its voxelize; a layer replaced or detached between voxelize and inject has no pass to resolve."""
+    mesh = at = pending = level0 = layer0 = None
+    layer, out = 0, {}
+    for k, op in enumerate(ops):
+        name = op[0]
+        if name == "dyn_attach":
+            mesh, at, layer, layer0 = op[1], op[2], layer + 1, None
+        elif name == "dyn_update":
+            at = op[1]
+        elif name == "dyn_detach":
+            mesh, layer, layer0 = None, layer + 1, None
+        elif name in ("produce", "revoxelize", "voxelize", "gi", "inject"):
+            if name != "inject":
+                assert name == "revoxelize" or op[1] == 0, op
+                pending = (layer, None if mesh is None else (mesh, at))
+            if name != "voxelize":
+                level0 = pending[1] if pending[0] == layer else None
+                if pending[0] == layer:
+                    layer0 = level0
+                pending = None
+        elif name == "read_chain":
+            out[k] = level0
+        elif name == "read_dynamic":
+            out[k] = layer0
+        else:
+            assert name in ("switch", "gbuffer", "trace", "read_frame"), op
+    return out
+
+
+_EXPECTED = {}
+
+
+def expected(oracle, inp, state):
+    """(digests of the chain, digests of the dynamic layer, level 0, the layer) the oracle gives for `state`."""
+    def layer(pos, mat, alb):
+        return dc.layer_plain(oracle, pos, mat, alb, V=inp.v, depth=inp.shadow0, vp=inp.lvp0)
+
+    def settled(a):
+        with ThreadPoolExecutor(max_workers=1) as pool:
+            return [x.result() if hasattr(x, "result") else x for x in digests(pool, a)]
+    if state not in _EXPECTED:
+        m = inp.meshes[0]
+        S = _EXPECTED[None][2] if state is not None else layer(m.pos, m.material, m.albedo)
+        D = np.zeros_like(S)
+        if state is not None:
+            mat, alb, at = inp.dyn[state[0]]
+            D = layer(at[state[1]], mat, alb)
+            dc.assert_non_degenerate(D, S)
+        l0 = dc.merge(D, S)
+        _EXPECTED[state] = (settled(oracle.build_mips(l0)), settled(D), l0, D)
+    return _EXPECTED[state]
+
+
+def directed_dynamic(vct, oracle, inp, ops, what, states_wanted):
+    """ops as they stand against ops with a vct_synchronize after every call, and every chain and layer read back against
+    the oracle for the state the model gives; states_wanted: how many different states the chains read back must show."""
+    states = resolved_states(ops)
+    expected(oracle, inp, None)
+    chains = {st: expected(oracle, inp, st)[0] for k, st in states.items() if ops[k][0] == "read_chain"}
+    assert len(chains) >= states_wanted and len({repr(v) for v in chains.values()}) == len(chains), sorted(chains, key=repr)
+    got, want = run(vct, inp, ops, False), run(vct, inp, ops, True)
+    assert_same(got, want, ops, what)
+    for k, op, values in want:
+        if op[0] == "read_chain":
+            assert values[0] == expected(oracle, inp, states[k])[0], f"{what}: call {k}: the chain is not that of {states[k]}"
+        elif op[0] == "read_dynamic":
+            assert values[1] == expected(oracle, inp, states[k])[1], f"{what}: call {k}: the layer is not that of {states[k]}"
+            info = values[0]
+            want_bricks = int(dc.bricks(expected(oracle, inp, states[k])[3][..., 3] > 0).sum())
+            assert (info["bricks_used"], info["left_out"], info["skipped"]) == (want_bricks, 0, 0), (k, info)
+
+
+def dynamic_frames(mesh=1):
+    """The atrium under light 0, the dynamic mesh attached at position 0, a G-buffer and a first frame on both slots."""
+    ops = [("produce", 0), ("dyn_attach", mesh, 0), ("revoxelize",)]
+    for slot in (0, 1):
+        ops += [("switch", slot), ("gbuffer", slot), ("trace",)]
+    return ops
+
+
+@pytest.mark.parametrize("device", [False, True])
+def test_positions_rewritten_while_the_other_slot_voxelizes(vct, oracle, inputs, device):
+    """Slot 0 voxelizes the crowd (shadow map, static pass, k_dyn_tris over 200 k triangles); slot 1 at once issues
+    vct_update_dynamic_positions -- the one position buffer both slots share; slot 0 injects, builds the mips and reads the
+    chain: that of the positions the voxelize was issued under.  Then a whole pass: the new ones."""
+    ops = dynamic_frames()
+    for at in (1, 2, 0):
+        ops += [("switch", 0), ("voxelize", 0), ("switch", 1), ("dyn_update", at, device), ("switch", 0), ("inject",), ("read_chain",),
+                ("read_dynamic",), ("revoxelize",), ("read_chain",)]
+    directed_dynamic(vct, oracle, inputs, ops, f"voxelize, positions on the other slot (device={device})", 3)
+
+
+def test_positions_and_a_pass_while_the_other_slot_traces(vct, oracle, inputs):
+    """Slot 0 queues three frames; slot 1 at once moves the object, runs a pass and reads chain and layer; slot 0's frame is
+    the one traced through the chain before the move."""
+    ops = dynamic_frames()
+    for at in (1, 2, 0):
+        ops += [("switch", 0), ("trace",), ("trace",), ("trace",), ("switch", 1), ("dyn_update", at, at == 2), ("revoxelize",),
+                ("read_chain",), ("read_dynamic",), ("switch", 0), ("read_frame",), ("switch", 1), ("trace",), ("read_frame",)]
+    directed_dynamic(vct, oracle, inputs, ops, "traces, a move and a pass on the other slot", 3)
+
+
+def test_layer_replaced_or_detached_while_the_other_slot_s_pass_is_in_flight(vct, oracle, inputs):
+    """A pass in flight on slot 0 (its kernels write the layer's accumulators, table and pools); slot 1 at once detaches, or
+    attaches the other mesh -- both free the layer -- and runs a pass of its own.  And the same with slot 0's pass only half
+    issued: the inject behind the change resolves the static chain."""
+    ops = dynamic_frames()
+    for change in (("dyn_detach",), ("dyn_attach", 0, 1), ("dyn_attach", 1, 2), ("dyn_detach",), ("dyn_attach", 1, 1)):
+        ops += [("switch", 0), ("revoxelize",), ("trace",), ("switch", 1), change, ("revoxelize",), ("read_chain",), ("switch", 0),
+                ("read_chain",), ("read_frame",)]
+    for change in (("dyn_attach", 0, 2), ("dyn_detach",), ("dyn_attach", 1, 0)):
+        ops += [("switch", 0), ("voxelize", 0), ("switch", 1), change, ("switch", 0), ("inject",), ("read_chain",), ("revoxelize",),
+                ("read_chain",)]
+    directed_dynamic(vct, oracle, inputs, ops, "a pass, the layer replaced on the other slot", 5)
+
+
+def test_layer_read_back_behind_the_other_slot_s_inject(vct, oracle, inputs):
+    """vct_get_dynamic and vct_download_dynamic_voxels from slot 1 directly behind slot 0's vct_inject_light: statistics and
+    pools are written by the merge on slot 0's stream."""
+    ops = dynamic_frames()
+    for at in (1, 2, 0, 1):
+        ops += [("switch", 0), ("dyn_update", at, at == 1), ("voxelize", 0), ("inject",), ("switch", 1), ("read_dynamic",), ("read_chain",)]
+    directed_dynamic(vct, oracle, inputs, ops, "inject, the layer read on the other slot", 3)

@@ -864,17 +864,44 @@ int vct_last_lights_ms(vct_ctx* ctx, float ms[2]);   /* [0] voxel kernel of the 
  * out of range, a NULL table, an unknown location, an update without an attached mesh; and while a dynamic mesh is attached
  * vct_voxelize(ctx, VCT_VOX_REFERENCE) (as with emission and lights) and vct_bounce -- the bounce walks the static slots'
  * attributes; carrying the second bounce over the dynamic layer is a follow-up.
- * Known limits: vct_render_shadow_map and vct_render_gbuffer keep drawing the static mesh only -- the dynamic object
- * receives the static scene's shadow in the chain, casts none into the map and is invisible to the library's own main
- * draw: callers with moving objects bring their pixels through vct_import_gbuffer.  The voxel view's albedo / normal
- * sources and vct_download_voxel_attributes show the static pools. */
+ * Drawing (vct_set_dynamic_draw; off by default): with VCT_DYNAMIC_DRAW_SHADOW vct_render_shadow_map, with
+ * VCT_DYNAMIC_DRAW_GBUFFER vct_render_gbuffer / _rows (and both stages inside vct_gi_pass and a rank's frame step) give,
+ * bit for bit -- shadow-map words, all 23 planes, pixel-emission and pixel-gloss planes -- what they would give for ONE
+ * static mesh that is the static triangles followed by the dynamic triangles, the appended triangles carrying
+ *   positions   those of the last vct_update_dynamic_positions issued before the stage (the rule of a voxelize pass);
+ *   frame       one normal, tangent and bitangent per triangle, the same at all three vertices: with p0, p1, p2 the
+ *               model-space fp32 positions, e1 = p1 - p0, e2 = p2 - p0,
+ *                 n = (e1.y * e2.z - e1.z * e2.y,  e1.z * e2.x - e1.x * e2.z,  e1.x * e2.y - e1.y * e2.x)
+ *               each component a * b - c * d with every product and the difference rounded to fp32 (unfused), then
+ *               (normal, tangent, bitangent) = the (u, t, b) of the G-buffer import's frame construction from n ("G-buffer
+ *               import": u = unit(n), t, b as there).  They are interpolated and inverted like static attributes;
+ *   material    albedo rgb of the dynamic table, alpha plane 1.0 whatever the table's fourth value, no alpha test, the
+ *               specular colour `specular` (NULL: 0, 0, 0) for every triangle, no textures, emission 0, gloss class 0.
+ * Depth ties resolve as in that one mesh: the lower id wins, so the static mesh wins a tie against the dynamic one.  A
+ * triangle outside the vertex contract (the rule above, applied on the device) draws nothing and disturbs nothing.
+ * With VCT_DYNAMIC_DRAW_SHADOW the object casts into the map and every PCF reader sees it: the voxelizer (static mesh and
+ * dynamic layer), the G-buffer shade and the import's PCF -- the dynamic layer then shadows itself under the 0.002 bias
+ * like any static surface.  The flags and the constant are context state: they survive attach, replace and detach of
+ * the mesh and vct_upload_triangles, and do nothing while no mesh is attached.  vct_set_dynamic_draw is ordered like
+ * vct_update_dynamic_positions and waits for nothing; it allocates (four [ntri][9] arrays) when a flag first goes on for
+ * the attached mesh, the stages allocate their scratch for the dynamic triangles in the first pass that draws them (per
+ * frame slot a second visibility buffer, 8 bytes per pixel).  Unknown flag bits or a non-finite specular value:
+ * VCT_ERR_INVALID, nothing touched.  vct_get_dynamic_draw: the state as set.
+ * Known limits: the drawn mesh has no textures, no emission, no gloss class and flat (per-face) normals.  With a flag off
+ * the limit of the stage it names remains: vct_render_shadow_map / vct_render_gbuffer then draw the static mesh only and
+ * every kernel launched is the one launched without this paragraph.  The voxel view's albedo / normal sources and
+ * vct_download_voxel_attributes show the static pools. */
 #define VCT_DYNAMIC_TRIS_MAX (1 << 20)
+#define VCT_DYNAMIC_DRAW_SHADOW  1
+#define VCT_DYNAMIC_DRAW_GBUFFER 2
 int vct_set_dynamic_mesh(vct_ctx* ctx, const float* pos, const int32_t* material, int32_t ntri,
                          const float* albedo, int32_t nmat, int32_t max_bricks);
 int vct_update_dynamic_positions(vct_ctx* ctx, const float* pos, int32_t location);
 int vct_get_dynamic(vct_ctx* ctx, int32_t out[8]);
 int vct_download_dynamic_voxels(vct_ctx* ctx, uint8_t* radiance, uint8_t* albedo, uint8_t* normal);
 int vct_last_dynamic_ms(vct_ctx* ctx, float ms[2]);
+int vct_set_dynamic_draw(vct_ctx* ctx, int32_t flags, const float specular[3] /* NULL: 0,0,0 */);
+int vct_get_dynamic_draw(vct_ctx* ctx, int32_t* flags, float specular[3]);
 
 /* ---- two frames in flight (round 6) -----------------------------------------------------------------
  * The reference's Render() (VCT.h:146-190) issues GL commands; the driver starts frame k + 1 while frame k

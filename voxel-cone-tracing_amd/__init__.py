@@ -81,7 +81,7 @@ ABI_SYMBOLS = [
     "vct_import_gbuffer", "vct_import_gbuffer_rows", "vct_last_gbuffer_import_ms",
     "vct_set_lights", "vct_get_lights", "vct_download_pixel_lights", "vct_last_lights_ms",
     "vct_set_dynamic_mesh", "vct_update_dynamic_positions", "vct_get_dynamic", "vct_download_dynamic_voxels",
-    "vct_last_dynamic_ms",
+    "vct_last_dynamic_ms", "vct_set_dynamic_draw", "vct_get_dynamic_draw",
 ]
 
 
@@ -103,6 +103,7 @@ class GlossClass(C.Structure):
 
 LIGHTS_MAX = 64
 LIGHT_SPOT = 1
+DYNAMIC_DRAW_SHADOW, DYNAMIC_DRAW_GBUFFER = 1, 2      # vct_set_dynamic_draw
 
 
 class Light(C.Structure):
@@ -246,6 +247,8 @@ _lib.vct_update_dynamic_positions.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
 _lib.vct_get_dynamic.argtypes = [C.c_void_p, C.c_void_p]
 _lib.vct_download_dynamic_voxels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.vct_last_dynamic_ms.argtypes = [C.c_void_p, C.c_void_p]
+_lib.vct_set_dynamic_draw.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+_lib.vct_get_dynamic_draw.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.vct_upload_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
 
 
@@ -705,6 +708,19 @@ class Context:
         v = (C.c_float * 2)()
         self._ck(_lib.vct_last_dynamic_ms(self._h, v), "vct_last_dynamic_ms")
         return v[0], v[1]
+
+    def set_dynamic_draw(self, flags, specular=None):
+        """Draws the dynamic mesh in the raster stages: DYNAMIC_DRAW_SHADOW (render_shadow_map) | DYNAMIC_DRAW_GBUFFER
+        (render_gbuffer), with the specular colour `specular` (None: 0, 0, 0) for every dynamic triangle.  Context state:
+        it outlives the mesh and does nothing while none is attached."""
+        sp = None if specular is None else np.ascontiguousarray(specular, np.float32).reshape(3)
+        self._ck(_lib.vct_set_dynamic_draw(self._h, int(flags), _ptr(sp)), "vct_set_dynamic_draw")
+
+    def dynamic_draw(self):
+        """(flags, specular [3]) as set by set_dynamic_draw."""
+        flags, sp = C.c_int32(0), (C.c_float * 3)()
+        self._ck(_lib.vct_get_dynamic_draw(self._h, C.byref(flags), sp), "vct_get_dynamic_draw")
+        return int(flags.value), np.array(list(sp), np.float32)
 
     def upload_shadow_map(self, depth, light_vp_rowmajor):
         if depth is None:

@@ -57,6 +57,21 @@ int launch_merge(vct_ctx* c, bool discard) {
     return VCT_OK;
 }
 
+// The draw copy and the face frames of layer `d` (vct_ctx.h VctDynamic): allocated if the layer has none, rebuilt from its
+// positions on stream s.  Called where the positions change or a draw flag goes on, never from a raster stage.
+int draw_prepare(vct_ctx* c, VctDynamic& d, hipStream_t s) {
+    const size_t n = vct_dynamic_draw_floats(d.ntri);
+    if (!d.draw_pos) {
+        HIP_TRY(c, d.draw_pos.alloc(n));
+        HIP_TRY(c, d.draw_nrm.alloc(n));
+        HIP_TRY(c, d.draw_tan.alloc(n));
+        HIP_TRY(c, d.draw_bit.alloc(n));
+    }
+    HIP_TRY(c, vct_launch_dynamic_draw_prepare(d.pos.get(), d.ntri, c->cfg.model_scale, VCT_VERTEX_LIMIT_GRIDS * c->cfg.grid_world_size,
+                                               d.draw_pos.get(), d.draw_nrm.get(), d.draw_tan.get(), d.draw_bit.get(), s));
+    return VCT_OK;
+}
+
 // one pooled volume of the last resolved pass -> dense Morton -> linear staging -> host, synchronised
 int download_pool(vct_ctx* c, const uint32_t* pool, uint32_t* dense, uint8_t* dst) {
     const VctDynamic& d = c->dyn;
@@ -71,6 +86,12 @@ int download_pool(vct_ctx* c, const uint32_t* pool, uint32_t* dense, uint8_t* ds
 }
 
 }  // namespace
+
+int vct_dynamic_draw_prepare(vct_ctx* c) {
+    VctDynamic& d = c->dyn;
+    if (!d.attached() || !d.draw_flags) return VCT_OK;
+    return draw_prepare(c, d, cur(c).stream.get());
+}
 
 int vct_dynamic_voxelize(vct_ctx* c) {
     VctDynamic& d = c->dyn;
@@ -116,7 +137,9 @@ int vct_set_dynamic_mesh(vct_ctx* c, const float* pos, const int32_t* material, 
         if (!c->dyn.attached()) return VCT_OK;
         HIP_TRY(c, hipSetDevice(c->device));
         PIPE_TRY(vct_synchronize(c));         // a kernel in flight may still read the layer
-        c->dyn = VctDynamic();
+        VctDynamic none;
+        none.keep_draw_state(c->dyn);         // vct_set_dynamic_draw is context state: it outlives the mesh
+        c->dyn = std::move(none);
         return VCT_OK;
     }
     if (const char* why = vct_dynamic_check_args(pos, material, ntri, albedo, nmat, max_bricks))
@@ -173,6 +196,8 @@ int vct_set_dynamic_mesh(vct_ctx* c, const float* pos, const int32_t* material, 
     }
     HIP_TRY(c, d.vox_timer.create());           // the events now, so that no pass allocates
     HIP_TRY(c, d.merge_timer.create());
+    d.keep_draw_state(c->dyn);
+    if (d.draw_flags) PIPE_TRY(draw_prepare(c, d, s));      // drawn: the draw copy and the frames of these positions
     HIP_TRY(c, hipStreamSynchronize(s));        // the caller's arrays are free again
     c->dyn = std::move(d);
     return VCT_OK;
@@ -186,6 +211,30 @@ int vct_update_dynamic_positions(vct_ctx* c, const float* pos, int32_t location)
     PIPE_TRY(vct_pipeline_join(c));       // the buffer is shared: the other slot's pass may still read the previous positions
     HIP_TRY(c, hipMemcpyAsync(c->dyn.pos.get(), pos, (size_t)c->dyn.ntri * 9 * sizeof(float),
                               location == VCT_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, cur(c).stream.get()));
+    return vct_dynamic_draw_prepare(c);   // behind the copy, on its stream: ordered before every stage that draws the mesh
+}
+
+int vct_set_dynamic_draw(vct_ctx* c, int32_t flags, const float specular[3]) {
+    if (!c) return VCT_ERR_INVALID;
+    if (const char* why = vct_dynamic_check_draw(flags, specular))
+        return vct_fail(c, VCT_ERR_INVALID, std::string("vct_set_dynamic_draw: ") + why);
+    VctDynamic& d = c->dyn;
+    const bool goes_on = flags && !d.draw_flags;
+    if (goes_on && d.attached()) {
+        // the draw copy is shared by both slots like the positions: the other slot's pass may still read the previous one
+        HIP_TRY(c, hipSetDevice(c->device));
+        PIPE_TRY(vct_pipeline_join(c));
+        PIPE_TRY(draw_prepare(c, d, cur(c).stream.get()));
+    }
+    d.draw_flags = flags;
+    for (int k = 0; k < 3; ++k) d.draw_specular[k] = specular ? specular[k] : 0.0f;
+    return VCT_OK;
+}
+
+int vct_get_dynamic_draw(vct_ctx* c, int32_t* flags, float specular[3]) {
+    if (!c || !flags || !specular) return VCT_ERR_INVALID;
+    *flags = c->dyn.draw_flags;
+    for (int k = 0; k < 3; ++k) specular[k] = c->dyn.draw_specular[k];
     return VCT_OK;
 }
 

@@ -4,12 +4,13 @@
 static size_t shadow_tile_count(int S) { const size_t nb = ((size_t)S + 7) >> 3; return nb * nb; }
 
 // Scratch `r` of one raster pass on stream `s`: `pixels` 64-bit visibility words (main draw) or 32-bit ones (depth_only,
-// the shadow-map words).
+// the shadow-map words).  `dyn` null: a pass over the static mesh.  Otherwise the dynamic mesh's own pass over its draw
+// copy (include/vct.h "dynamic mesh", drawing): direct form, the triangle count and the records of `dyn`.
 static int raster_args(vct_ctx* c, VctRasterScratch& r, int side_w, int side_h, bool depth_only, bool binned, hipStream_t s,
-                       VctRasterArgs& a) {
+                       VctRasterArgs& a, const VctDynamic* dyn = nullptr) {
     if (!c->mesh.tri_pos) return vct_fail(c, VCT_ERR_INVALID, "no triangles uploaded");
     const size_t pixels = (size_t)side_w * side_h;
-    const VctMesh& m = c->mesh;
+    const int32_t ntri = dyn ? dyn->ntri : c->mesh.ntri;      // what sizes the scratch
     if (!depth_only) HIP_TRY(c, r.vis.reserve(pixels, &r.dirty));
     const uint32_t bins = (uint32_t)(((size_t)side_w + 15) / 16 * (((size_t)side_h + 15) / 16));
     if (binned) {
@@ -19,8 +20,8 @@ static int raster_args(vct_ctx* c, VctRasterScratch& r, int side_w, int side_h, 
         // Bistro-class street at 4K -- plus the bins' counters.  Whatever does not fit takes the huge list or is
         // rasterised in place (k_bin_setup), so these are sizes, not limits.  ~200 B per triangle and pass kind,
         // replicated per rank of a multi-GPU frame.
-        const uint32_t want_recs = (uint32_t)m.ntri + 4096u;
-        const size_t want_ent_sz = (size_t)m.ntri * 4 + (size_t)bins * 4 + 65536;
+        const uint32_t want_recs = (uint32_t)ntri + 4096u;
+        const size_t want_ent_sz = (size_t)ntri * 4 + (size_t)bins * 4 + 65536;
         const uint32_t want_ent = (uint32_t)(want_ent_sz < 0x7fffffffull ? want_ent_sz : 0x7fffffffull);
         HIP_TRY(c, r.bin_recs.reserve((size_t)want_recs * 160));
         HIP_TRY(c, r.bin_entries.reserve((size_t)want_ent + 1));      // + the spare entry k_bin_fill's idle lanes write
@@ -29,8 +30,8 @@ static int raster_args(vct_ctx* c, VctRasterScratch& r, int side_w, int side_h, 
         HIP_TRY(c, r.bin_count.reserve((size_t)bins * 2 * VCT_BIN_CSTRIDE, &r.dirty));
         HIP_TRY(c, r.bin_huge.reserve((size_t)(VCT_BIN_HUGE_CAP + 16 + 32), &r.dirty));
     } else {
-        HIP_TRY(c, r.lists.reserve((size_t)m.ntri * 4));
-        HIP_TRY(c, r.recs.reserve((size_t)m.ntri * 2 * 96));
+        HIP_TRY(c, r.lists.reserve((size_t)ntri * 4));
+        HIP_TRY(c, r.recs.reserve((size_t)ntri * 2 * 96));
         HIP_TRY(c, r.counts.reserve(8, &r.dirty));
         // tile work items: 16x16-pixel pieces of large triangles; pixels/16 entries is ~16x the typical
         // demand (sum of visible bounding boxes ~ a few frames' worth of pixels); overflow is handled
@@ -61,14 +62,22 @@ static int raster_args(vct_ctx* c, VctRasterScratch& r, int side_w, int side_h, 
         a.bin_next_ctr = r.bin_huge.get() + VCT_BIN_HUGE_CAP + 8 * (r.bin_set ^ 1);
         r.bin_set ^= 1;
     }
-    a.pos = m.tri_pos.get();
-    a.nrm = m.tri_nrm.get(); a.tan = m.tri_tan.get(); a.bit = m.tri_bit.get();
-    a.material = m.tri_mat.get();
-    a.albedo = m.mat_albedo.get();
-    a.specular = m.mat_specular.get();
-    a.emission = depth_only ? nullptr : m.mat_emission.get();
-    a.mat_gloss = depth_only ? nullptr : m.mat_gloss.get();
-    a.ntri = m.ntri;
+    if (dyn) {      // no specular table (a constant), no emission, no gloss classes, no textures, no alpha test
+        a.pos = dyn->draw_pos.get();
+        a.nrm = dyn->draw_nrm.get(); a.tan = dyn->draw_tan.get(); a.bit = dyn->draw_bit.get();
+        a.material = dyn->mat.get();
+        a.albedo = dyn->albedo.get();
+    } else {
+        const VctMesh& sm = c->mesh;
+        a.pos = sm.tri_pos.get();
+        a.nrm = sm.tri_nrm.get(); a.tan = sm.tri_tan.get(); a.bit = sm.tri_bit.get();
+        a.material = sm.tri_mat.get();
+        a.albedo = sm.mat_albedo.get();
+        a.specular = sm.mat_specular.get();
+        a.emission = depth_only ? nullptr : sm.mat_emission.get();
+        a.mat_gloss = depth_only ? nullptr : sm.mat_gloss.get();
+    }
+    a.ntri = ntri;
     a.model_scale = c->cfg.model_scale;
     a.vis = r.vis.get();
     a.vis32 = nullptr;          // vct_render_shadow_map points it at the shadow-map words
@@ -80,7 +89,7 @@ static int raster_args(vct_ctx* c, VctRasterScratch& r, int side_w, int side_h, 
         uint32_t* ctr = r.counts.get() + 4 * r.set;
         a.wave_list = r.lists.get();
         a.wave_count = ctr;
-        a.group_list = r.lists.get() + (size_t)m.ntri * 2;
+        a.group_list = r.lists.get() + (size_t)ntri * 2;
         a.group_count = ctr + 1;
         a.item_count = ctr + 2;
         a.next_counts = r.counts.get() + 4 * (r.set ^ 1);
@@ -88,15 +97,17 @@ static int raster_args(vct_ctx* c, VctRasterScratch& r, int side_w, int side_h, 
         r.set ^= 1;
         a.item_capacity = (uint32_t)r.items.size();
     }
+    if (dyn) return VCT_OK;
     a.tex = vct_textures_of(c);
     if (!depth_only) {          // the main draw's alpha-test class per triangle: once per mesh / texture set
-        HIP_TRY(c, c->mesh.tri_alpha.reserve((size_t)m.ntri, &c->mesh.tri_alpha_dirty));
-        if (m.tri_alpha_dirty) {
-            HIP_TRY(c, vct_launch_tri_alpha(a, m.tri_alpha.get(), s));
-            c->mesh.tri_alpha_dirty = false;
+        VctMesh& sm = c->mesh;
+        HIP_TRY(c, sm.tri_alpha.reserve((size_t)ntri, &sm.tri_alpha_dirty));
+        if (sm.tri_alpha_dirty) {
+            HIP_TRY(c, vct_launch_tri_alpha(a, sm.tri_alpha.get(), s));
+            sm.tri_alpha_dirty = false;
             c->xslot.note_producer();      // (shared by both frame slots: the other slot's next pass follows this one)
         }
-        a.tri_alpha = m.tri_alpha.get();
+        a.tri_alpha = sm.tri_alpha.get();
     }
     return VCT_OK;
 }
@@ -104,8 +115,14 @@ static int raster_args(vct_ctx* c, VctRasterScratch& r, int side_w, int side_h, 
 // One shadow pass into the map's words under the next epoch (vct_ctx.h VctShadowMap), then the tile bounds.
 static int shadow_pass(vct_ctx* c, const float light_vp[16], int S) {
     VctShadowMap& sm = c->shadow;
-    VctRasterArgs a;
+    VctRasterArgs a, da;
     PIPE_TRY(raster_args(c, sm.raster, S, S, true, c->raster_form.mode == 2, cur(c).stream.get(), a));
+    // VCT_DYNAMIC_DRAW_SHADOW: the dynamic mesh's draw copy behind the static mesh, into the same words under the same epoch
+    const bool draw_dyn = c->dyn.drawn(VCT_DYNAMIC_DRAW_SHADOW);
+    if (draw_dyn) {      // (a failure here leaves the static scratch's counter sets swapped and unused: cleared by the next pass)
+        const int rc = raster_args(c, sm.dyn_raster, S, S, true, false, cur(c).stream.get(), da, &c->dyn);
+        if (rc) { sm.raster.dirty = true; return rc; }
+    }
     bool memset_due = false;
     const uint32_t epoch = sm.next_epoch(&memset_due);
     if (memset_due) HIP_TRY(c, hipMemsetAsync(sm.words.get(), 0xff, (size_t)S * S * sizeof(uint32_t), cur(c).stream.get()));
@@ -114,6 +131,13 @@ static int shadow_pass(vct_ctx* c, const float light_vp[16], int S) {
     memcpy(sm.light_vp, light_vp, 64);
     const hipError_t e = vct_launch_shadow_raster(a, light_vp, S, cur(c).stream.get());
     if (e != hipSuccess) { sm.raster.dirty = true; HIP_TRY(c, e); }
+    if (draw_dyn) {
+        // direct form: atomicMin lowers whatever the static pass left, the plain stores of its binned form included
+        da.vis32 = sm.words.get();
+        da.vis32_ebase = VCT_SHADOW_EPOCH(epoch);
+        const hipError_t ed = vct_launch_shadow_raster(da, light_vp, S, cur(c).stream.get());
+        if (ed != hipSuccess) { sm.raster.dirty = sm.dyn_raster.dirty = true; HIP_TRY(c, ed); }
+    }
     sm.pass_done(epoch);
     // depth bounds per (dilated) 8 x 8 tile of the new map: the PCF consumers (voxelizer, G-buffer shade) decide most windows on them
     if (sm.tiles) HIP_TRY(c, vct_launch_shadow_minmax(sm.words.get(), sm.ebase, S, sm.tiles.get(), cur(c).stream.get()));
@@ -157,18 +181,35 @@ int vct_render_gbuffer_rows_on(vct_ctx* c, const float view_proj[16], int32_t ro
     VctRasterForm& form = c->raster_form;
     bool binned = false;
     const int slot = form.pick(row0, row1, c->mesh.has_alpha_textures, &binned);      // >= 0: this pass is timed sample `slot`
-    VctRasterArgs a;
+    VctRasterArgs a, da;
     VctRasterScratch& r = cur(c).raster;
+    VctRasterScratch& dr = cur(c).dyn_raster;
     PIPE_TRY(raster_args(c, r, c->cfg.width, c->cfg.height, false, binned, s, a));
+    // VCT_DYNAMIC_DRAW_GBUFFER: the dynamic mesh's draw copy into the slot's second visibility buffer, resolved by the shade kernel
+    const bool draw_dyn = c->dyn.drawn(VCT_DYNAMIC_DRAW_GBUFFER);
+    if (draw_dyn) {      // (a failure here leaves the static scratch's counter sets swapped and unused: cleared by the next pass)
+        const int rc = raster_args(c, dr, c->cfg.width, c->cfg.height, false, false, s, da, &c->dyn);
+        if (rc) { r.dirty = true; return rc; }
+    }
     if (slot >= 0) HIP_TRY(c, hipEventRecord(form.ev[2 * slot].get(), s));
     hipError_t e = vct_launch_gbuffer_visibility(a, view_proj, c->cfg.width, c->cfg.height, row0, row1, s);
     if (slot >= 0 && e == hipSuccess) e = hipEventRecord(form.ev[2 * slot + 1].get(), s);
     if (e == hipSuccess) form.launched();
+    // (behind the timed bracket's end event: the automatic form choice measures the static pass alone)
+    if (e == hipSuccess && draw_dyn) e = vct_launch_dynamic_visibility(da, view_proj, c->cfg.width, c->cfg.height, row0, row1, s);
     if (e == hipSuccess && shadow_ready) e = hipStreamWaitEvent(s, shadow_ready, 0);
+    VctDynShadeArgs ds;
+    if (draw_dyn) {
+        ds.vis = da.vis;
+        ds.pos = da.pos; ds.nrm = da.nrm; ds.tan = da.tan; ds.bit = da.bit;
+        ds.material = da.material; ds.albedo = da.albedo;
+        for (int k = 0; k < 3; ++k) ds.specular[k] = c->dyn.draw_specular[k];
+    }
     if (e == hipSuccess)
         e = vct_launch_gbuffer_shade(a, view_proj, c->cfg.width, c->cfg.height, row0, row1, c->shadow.words.get(), c->shadow.ebase,
-                                     c->shadow.size, c->shadow.tiles.get(), c->shadow.light_vp, cur(c).gb_tiled.get(), cur(c).emis.get(), cur(c).gloss.get(), s);
-    if (e != hipSuccess) { r.dirty = true; HIP_TRY(c, e); }
+                                     c->shadow.size, c->shadow.tiles.get(), c->shadow.light_vp, cur(c).gb_tiled.get(), cur(c).emis.get(), cur(c).gloss.get(), s,
+                                     draw_dyn ? &ds : nullptr);
+    if (e != hipSuccess) { r.dirty = true; if (draw_dyn) dr.dirty = true; HIP_TRY(c, e); }
     cur(c).gb_current = cur(c).gb_tiled.get();
     form.last_form = binned ? 2 : 1;
     cur(c).last_row0 = row0;

@@ -237,6 +237,9 @@ struct VctFrameSlot {
     uint64_t vv_gen = 0;
     VctTimer vv_timer;                  // around the view's walk (vct_last_voxel_view_ms)
     VctRasterScratch raster;            // the main draw's
+    // the dynamic mesh's own direct-form pass of the main draw (include/vct.h "dynamic mesh", VCT_DYNAMIC_DRAW_GBUFFER):
+    // its `vis` is the slot's SECOND visibility buffer, ids from 0; empty until the first pass with the flag on
+    VctRasterScratch dyn_raster;
     VctPointQuery query;                // point queries issued on this slot
     VctGBufferImport gb_import;         // G-buffer imports issued on this slot
 
@@ -362,6 +365,7 @@ struct VctShadowMap {
     VctBuf<uint2> tiles;              // decoded (min, max) per dilated 8 x 8 tile of the current map (vct_launch_shadow_minmax)
     uint32_t passes = 0;              // shadow passes rasterised into `words` since their last memset
     VctRasterScratch raster;          // scratch of the shadow pass (the main draw's is per frame slot)
+    VctRasterScratch dyn_raster;      // ... and of the dynamic mesh's direct-form pass behind it (VCT_DYNAMIC_DRAW_SHADOW)
     float light_vp[16] = {1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f};
 
     void drop() { words.reset(); tiles.reset(); size = 0; }
@@ -461,8 +465,20 @@ struct VctDynamic {
     bool pending = false;               // the accumulators hold a pass no merge has resolved
     int set = 0;                        // the statistics set of the last resolved pass
     VctTimer vox_timer, merge_timer;    // vct_last_dynamic_ms
+    // Drawing the mesh in the raster stages (vct_set_dynamic_draw).  The flags and the specular constant are context
+    // state: they outlive the mesh (keep_draw_state).  The draw copy and the frames exist while a flag is on and a mesh
+    // is attached; k_dyn_draw_prepare rebuilds them behind every copy into `pos`.
+    int32_t draw_flags = 0;             // VCT_DYNAMIC_DRAW_*
+    float draw_specular[3] = {0.0f, 0.0f, 0.0f};
+    VctBuf<float> draw_pos;             // [ntri][9] `pos`, a triangle outside the vertex contract as nine zeros
+    VctBuf<float> draw_nrm, draw_tan, draw_bit;      // [ntri][9] the face frame at all three vertices
 
     bool attached() const { return ntri > 0; }
+    bool drawn(int32_t flag) const { return attached() && (draw_flags & flag) && draw_pos; }
+    void keep_draw_state(const VctDynamic& o) {
+        draw_flags = o.draw_flags;
+        for (int k = 0; k < 3; ++k) draw_specular[k] = o.draw_specular[k];
+    }
 };
 
 struct vct_ctx {
@@ -606,6 +622,8 @@ hipError_t vct_lights_planes(const vct_ctx* c, VctFrameSlot& s, bool* fresh = nu
 // vct_inject_light (merge into level 0, its local lights), on the selected slot's stream; nothing attached: nothing issued
 int vct_dynamic_voxelize(vct_ctx* c);
 int vct_dynamic_merge(vct_ctx* c);
+// k_dyn_draw_prepare over the attached mesh's positions on the selected slot's stream (nothing drawn: nothing issued)
+int vct_dynamic_draw_prepare(vct_ctx* c);
 // vct_multi.hip: slab of the attached communicator (false: none attached); its release
 bool vct_comm_rows(const vct_ctx* c, int* row0, int* row1);
 void vct_comm_release(vct_ctx* c);

@@ -34,6 +34,17 @@ static inline const char* vct_dynamic_check_update(bool attached, const float* p
     return nullptr;
 }
 
+// What is wrong with the arguments of vct_set_dynamic_draw, or null.  specular null: the constant is 0, 0, 0.
+#define VCT_DYNAMIC_DRAW_ALL (VCT_DYNAMIC_DRAW_SHADOW | VCT_DYNAMIC_DRAW_GBUFFER)
+static inline bool vct_dynamic_finite(float v) { return v == v && v - v == 0.0f; }
+static inline const char* vct_dynamic_check_draw(int32_t flags, const float* specular) {
+    if (flags & ~(int32_t)VCT_DYNAMIC_DRAW_ALL) return "unknown flag bits";
+    if (specular)
+        for (int k = 0; k < 3; ++k)
+            if (!vct_dynamic_finite(specular[k])) return "non-finite specular value";
+    return nullptr;
+}
+
 // 8^3 bricks of a grid of V^3 voxels (V a power of two, 8 .. 1024: at most 2^21)
 static inline uint32_t vct_dynamic_grid_bricks(int32_t V) {
     if (V < 8) return 0u;
@@ -85,6 +96,34 @@ static inline VctDynamicSizes vct_dynamic_sizes(int32_t ntri, int32_t nmat, uint
     s.words = 32 * sizeof(uint32_t);
     s.ok = ok;
     if (!ok) { const VctDynamicSizes none = {}; return none; }
+    return s;
+}
+
+// floats of the draw copy and of each of the three frame arrays of a drawn layer, [ntri][9] (ntri <= 2^20: no overflow)
+static inline size_t vct_dynamic_draw_floats(int32_t ntri) { return ntri < 1 ? 0 : (size_t)ntri * 9; }
+
+// Byte counts of what drawing the layer adds: the four [ntri][9] arrays, and per raster target of w x h pixels (a frame
+// slot, or the shadow map with w = h = its size) the direct form's scratch sized by the layer's triangles -- the two
+// lists, the set-up records and the tile work items -- and, for a frame slot, the second visibility buffer.
+struct VctDynamicDrawSizes {
+    bool ok;
+    size_t arrays;                      // draw copy + three frame arrays
+    size_t lists, recs, items;          // [4 * ntri] int32, [2 * ntri] 96-byte records, [pixels / 16 + 4096] 8-byte items
+    size_t vis;                         // [pixels] uint64 (frame slots only)
+};
+static inline VctDynamicDrawSizes vct_dynamic_draw_sizes(int32_t ntri, int32_t w, int32_t h) {
+    VctDynamicDrawSizes s = {};
+    if (ntri < 1 || ntri > VCT_DYNAMIC_TRIS_MAX || w < 1 || h < 1) return s;
+    const size_t nt = (size_t)ntri;
+    size_t pixels = 0, items = 0;
+    bool ok = vct_dynamic_mul((size_t)w, (size_t)h, &pixels);
+    ok = ok && vct_dynamic_mul(vct_dynamic_draw_floats(ntri), 4 * sizeof(float), &s.arrays);
+    ok = ok && vct_dynamic_mul(nt, 4 * sizeof(int32_t), &s.lists);
+    ok = ok && vct_dynamic_mul(nt, (size_t)2 * 96, &s.recs);
+    ok = ok && !__builtin_add_overflow(pixels / 16, (size_t)4096, &items) && vct_dynamic_mul(items, 8, &s.items);
+    ok = ok && vct_dynamic_mul(pixels, sizeof(uint64_t), &s.vis);
+    s.ok = ok;
+    if (!ok) { const VctDynamicDrawSizes none = {}; return none; }
     return s;
 }
 

@@ -513,9 +513,31 @@ hipError_t vct_launch_shadow_minmax(const uint32_t* words, uint32_t ebase, int S
 // (k_gbuffer_shade, the only part that reads the shadow map) are separate calls so that a stream wait can sit between
 hipError_t vct_launch_gbuffer_visibility(const VctRasterArgs& a, const float view_proj[16], int W, int H, int row0, int row1,
                                          hipStream_t s);
+// `dyn` not null: the pass drew the dynamic mesh into a second visibility buffer (vct_launch_dynamic_visibility) and the
+// DYN instantiation of the shade kernel resolves the two words of every pixel (include/vct.h "dynamic mesh", drawing)
+struct VctDynShadeArgs {
+    unsigned long long* vis;     // [H][W] second visibility buffer, ids from 0
+    const float* pos;            // [ntri][9] draw copy of the positions
+    const float* nrm;            // [ntri][9] face frame at all three vertices
+    const float* tan;
+    const float* bit;
+    const int32_t* material;     // [ntri]
+    const float* albedo;         // [nmat][4] (rgb used; the alpha plane is 1)
+    float specular[3];           // the constant of vct_set_dynamic_draw
+};
 hipError_t vct_launch_gbuffer_shade(const VctRasterArgs& a, const float view_proj[16], int W, int H, int row0, int row1,
                                     const uint32_t* shadow, uint32_t shadow_ebase, int shadow_size, const uint2* shadow_tiles,
-                                    const float light_vp[16], float* tiled, float* emis_tiled, uint8_t* gloss_tiled, hipStream_t s);
+                                    const float light_vp[16], float* tiled, float* emis_tiled, uint8_t* gloss_tiled, hipStream_t s,
+                                    const VctDynShadeArgs* dyn = nullptr);
+// The dynamic mesh's own visibility pass of the main draw: the direct form over a.pos (the draw copy) into a.vis (the
+// second buffer) with the scratch in `a`, no material -- no alpha test -- and the scissor rows of the static pass.
+hipError_t vct_launch_dynamic_visibility(const VctRasterArgs& a, const float view_proj[16], int W, int H, int row0, int row1,
+                                         hipStream_t s);
+// k_dyn_draw_prepare, one thread per dynamic triangle: the draw copy of `pos` (a triangle with a coordinate v for which
+// !(fabsf(v * model_scale) <= vertex_limit) becomes nine zeros -- a point, culled by the set-up) and the face frame
+// (u, t, b) = vct_import_frame(cross(p1 - p0, p2 - p0)), written to all three vertices of draw_nrm / _tan / _bit.
+hipError_t vct_launch_dynamic_draw_prepare(const float* pos, int32_t ntri, float model_scale, float vertex_limit, float* draw_pos,
+                                           float* draw_nrm, float* draw_tan, float* draw_bit, hipStream_t s);
 // one level of a texture's mip chain from its parent (pw x ph -> w x h), glGenerateMipmap restated as in the oracle
 hipError_t vct_launch_tri_alpha(const VctRasterArgs& a, int32_t* out, hipStream_t s);
 hipError_t vct_launch_tex_mip(const uint32_t* parent, int pw, int ph, uint32_t* level, int w, int h, hipStream_t s);

@@ -477,12 +477,14 @@ struct RasterParams {
     VctTextures tex;
 };
 
-__device__ __forceinline__ void load_clip_tri(const RasterParams& p, int t, RVert in[3]) {
-    const VctTri9 q = *reinterpret_cast<const VctTri9*>(p.pos + (size_t)t * 9);       // three wide loads, not nine
+// (`pos`: the pass's positions, or the other mesh's where a kernel serves two -- k_gbuffer_shade's DYN instantiation)
+__device__ __forceinline__ void load_clip_tri(const RasterParams& p, const float* pos, int t, RVert in[3]) {
+    const VctTri9 q = *reinterpret_cast<const VctTri9*>(pos + (size_t)t * 9);       // three wide loads, not nine
 #pragma unroll
     for (int k = 0; k < 3; ++k)
         xform4(p.vp, q.v[3 * k] * p.model_scale, q.v[3 * k + 1] * p.model_scale, q.v[3 * k + 2] * p.model_scale, in[k].c);
 }
+__device__ __forceinline__ void load_clip_tri(const RasterParams& p, int t, RVert in[3]) { load_clip_tri(p, p.pos, t, in); }
 
 // Work granularity by bounding-box size (the bench scene: half of the visible triangles cover <= 64
 // pixels, 91-100 % <= 256, the largest ~2k; a Cornell wall covers the whole frame):
@@ -1542,6 +1544,23 @@ struct ShadeParams {
     uint8_t* gloss_tiled;
 };
 
+// The dynamic mesh in the main draw (include/vct.h "dynamic mesh", drawing): its own visibility words and the records the
+// shade kernel selects for a pixel the dynamic mesh owns.  Only the DYN instantiations of k_gbuffer_shade take them: the
+// argument block of the others is ShadeParams as it was.
+struct DynShade {
+    unsigned long long* vis;     // [H][W] second visibility buffer, ids from 0; ~0 = empty
+    const float* pos;            // [ntri][9] draw copy (k_dyn_draw_prepare)
+    const float* nrm;            // [ntri][9] the face frame, the same at all three vertices
+    const float* tan;
+    const float* bit;
+    const int32_t* material;     // [ntri]
+    const float* albedo;         // [nmat][4]
+    float specular[3];
+};
+template <bool DYN> struct ShadeArgs : ShadeParams {};
+template <> struct ShadeArgs<true> : ShadeParams { DynShade d; };
+static_assert(sizeof(ShadeArgs<false>) == sizeof(ShadeParams), "the static instantiations keep their argument block");
+
 // [GL] bilinear clamp-to-edge fetch with the operation order of host/vct_host.cpp shadow_fetch
 __device__ __forceinline__ float shadow_fetch(const uint32_t* __restrict__ words, uint32_t eb, int S, float u, float v) {
     const float x = u * (float)S - 0.5f, y = v * (float)S - 0.5f;
@@ -1668,9 +1687,15 @@ __device__ __forceinline__ float pcf_shadow(const uint32_t* __restrict__ words, 
 #ifndef VCT_SHADE_BLOCK
 #define VCT_SHADE_BLOCK 256        // threads per workgroup = 64 x tiles per workgroup (the kernel has no workgroup-level state)
 #endif
-template <bool TEX>
+// DYN: the pass drew the dynamic mesh into a second visibility buffer.  A pixel reads both words and belongs to the
+// dynamic mesh where that word's depth is STRICTLY smaller -- at equal depth the static mesh wins, the order of the ids
+// of one mesh that is the static triangles followed by the dynamic ones -- and both words go back to "empty".  A dynamic
+// pixel selects the dynamic records (draw positions, face frames, material, table), has no textures, no emission and
+// gloss class 0, alpha 1 and the constant specular colour; everything from the set-up on is the one code below.  The
+// select is per lane: a wave is one 8x8 tile, the divergence stays inside it.
+template <bool TEX, bool DYN>
 __global__ void __launch_bounds__(256, TEX ? VCT_SHADE_TEX_MIN_BLOCKS : VCT_SHADE_MIN_BLOCKS)
-k_gbuffer_shade(const ShadeParams p) {
+k_gbuffer_shade(const ShadeArgs<DYN> p) {
     const int W = p.r.W, H = p.r.H;
     const int tile = p.tile0 + blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -1688,11 +1713,26 @@ k_gbuffer_shade(const ShadeParams p) {
         v = p.r.vis[(size_t)py * W + px];
         p.r.vis[(size_t)py * W + px] = ~0ull;       // consumed: leave the word "empty" for the next pass (no clear launch)
     }
+    bool dyn = false;                       // the pixel shows the dynamic mesh
+    const float *pos_sel = p.r.pos, *nrm_sel = p.nrm, *tan_sel = p.tan, *bit_sel = p.bit, *alb_sel = p.albedo;
+    const int32_t* mat_sel = p.material;
+    if constexpr (DYN) {
+        if (px < W && py < H) {
+            const unsigned long long vd = p.d.vis[(size_t)py * W + px];
+            p.d.vis[(size_t)py * W + px] = ~0ull;
+            dyn = (uint32_t)(vd >> 32) < (uint32_t)(v >> 32);       // (an empty word is the largest depth there is)
+            if (dyn) {
+                v = vd;
+                pos_sel = p.d.pos; nrm_sel = p.d.nrm; tan_sel = p.d.tan; bit_sel = p.d.bit; alb_sel = p.d.albedo;
+                mat_sel = p.d.material;
+            }
+        }
+    }
     if (v != ~0ull) {
         const int id = (int)(uint32_t)v;
         const int t = id >> 1, f = (id & 1) + 1;
         RVert in[3];
-        load_clip_tri(p.r, t, in);
+        load_clip_tri(p.r, pos_sel, t, in);
         // Everything that depends on the triangle index only is requested NOW, ahead of the fp64 set-up: the four
         // per-vertex records (the position once more: the clip-space copy above is consumed by the set-up) and the
         // material index.  The kernel is a chain of dependent round trips (visibility word -> records -> material ->
@@ -1700,27 +1740,37 @@ k_gbuffer_shade(const ShadeParams p) {
         VctTri9 recs4[4];
 #pragma unroll
         for (int arr = 0; arr < 4; ++arr) {
-            const float* src = arr == 0 ? p.r.pos : (arr == 1 ? p.nrm : (arr == 2 ? p.tan : p.bit));
+            const float* src = arr == 0 ? pos_sel : (arr == 1 ? nrm_sel : (arr == 2 ? tan_sel : bit_sel));
             recs4[arr] = *reinterpret_cast<const VctTri9*>(src + (size_t)t * 9);
         }
-        const int m_early = p.material[t];
+        const int m_early = mat_sel[t];
         // ... and the material's colours as soon as the index is there (it arrives with the records), so that they too
         // travel during the set-up
-        const float alb_early[4] = {p.albedo[4 * (size_t)m_early], p.albedo[4 * (size_t)m_early + 1],
-                                    p.albedo[4 * (size_t)m_early + 2], p.albedo[4 * (size_t)m_early + 3]};
-        const float sp_early[3] = {p.specular[3 * (size_t)m_early], p.specular[3 * (size_t)m_early + 1],
-                                   p.specular[3 * (size_t)m_early + 2]};
-        if (p.emis_tiled) {       // (wave-uniform: a kernel argument) ... and its emission, with them
+        float alb_early[4] = {alb_sel[4 * (size_t)m_early], alb_sel[4 * (size_t)m_early + 1],
+                              alb_sel[4 * (size_t)m_early + 2], alb_sel[4 * (size_t)m_early + 3]};
+        float sp_early[3];
+        if (!dyn) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) sp_early[k] = p.specular[3 * (size_t)m_early + k];
+        }
+        if (p.emis_tiled && !dyn) {       // (wave-uniform: a kernel argument) ... and its emission, with them
 #pragma unroll
             for (int k = 0; k < 3; ++k) em[k] = p.emission[4 * (size_t)m_early + k];
         }
-        if (p.gloss_tiled) gloss = p.mat_gloss[m_early];
+        if (p.gloss_tiled && !dyn) gloss = p.mat_gloss[m_early];
+        if constexpr (DYN) {
+            if (dyn) {        // the table's fourth value is not used: the alpha plane is 1; the constant specular colour
+                alb_early[3] = 1.0f;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) sp_early[k] = p.d.specular[k];
+            }
+        }
         // ... and, in a scene with textures, the material's three texture indices and the triangle's texture coordinates
         // (round 4: they used to be asked for after the set-up -- material -> indices -> descriptor -> texels was four
         // dependent round trips behind it, now two)
         int tex_early[3] = {-1, -1, -1};
         float uv_early[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-        if (TEX) {
+        if (TEX && !dyn) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) tex_early[k] = vct_tex_of(p.r.tex, m_early, k);
 #pragma unroll
@@ -1960,6 +2010,39 @@ k_tex_mip(const uint32_t* __restrict__ parent, int pw, int ph, uint32_t* __restr
     }
 }
 
+// ---- the dynamic mesh's draw copy (include/vct.h "dynamic mesh", drawing) ----
+// One thread per dynamic triangle, behind every copy into the layer's positions.  A triangle outside the vertex contract
+// (vct_voxelize.hip dyn_in_contract's rule: NaN and the infinities fail the comparison) is written as nine zeros -- a
+// point, zero area, culled by setup_subtri -- so that no raster set-up ever sees an unbounded coordinate.  The frame is
+// the face's: n = cross(p1 - p0, p2 - p0) on the model-space positions, each component a * b - c * d unfused, then
+// vct_import_frame's unit normal, tangent and bitangent, stored at all three vertices like static attributes.
+__global__ void __launch_bounds__(256)
+k_dyn_draw_prepare(const float* __restrict__ pos, int ntri, float model_scale, float vertex_limit, float* __restrict__ draw_pos,
+                   float* __restrict__ draw_nrm, float* __restrict__ draw_tan, float* __restrict__ draw_bit) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= ntri) return;
+    VctTri9 q = *reinterpret_cast<const VctTri9*>(pos + (size_t)t * 9);
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) ok = ok && fabsf(q.v[k] * model_scale) <= vertex_limit;
+    if (!ok) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) q.v[k] = 0.0f;
+    }
+    const float ax = q.v[3] - q.v[0], ay = q.v[4] - q.v[1], az = q.v[5] - q.v[2];
+    const float bx = q.v[6] - q.v[0], by = q.v[7] - q.v[1], bz = q.v[8] - q.v[2];
+    const float n[3] = {ay * bz - az * by, az * bx - ax * bz, ax * by - ay * bx};
+    float u[3], tg[3], b[3];
+    vct_import_frame(n, u, tg, b);
+    VctTri9 rn, rt, rb;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { rn.v[k] = u[k % 3]; rt.v[k] = tg[k % 3]; rb.v[k] = b[k % 3]; }
+    *reinterpret_cast<VctTri9*>(draw_pos + (size_t)t * 9) = q;
+    *reinterpret_cast<VctTri9*>(draw_nrm + (size_t)t * 9) = rn;
+    *reinterpret_cast<VctTri9*>(draw_tan + (size_t)t * 9) = rt;
+    *reinterpret_cast<VctTri9*>(draw_bit + (size_t)t * 9) = rb;
+}
+
 RasterParams make_raster(const VctRasterArgs& a, const float vp[16], int W, int H, int ys0, int ys1) {
     RasterParams r;
     r.ys0 = ys0 < 0 ? 0 : ys0;
@@ -2115,9 +2198,23 @@ hipError_t vct_launch_gbuffer_visibility(const VctRasterArgs& a, const float vie
     return a.binned ? run_visibility_binned(a, p.r, s) : run_visibility(p.r, s);
 }
 
+hipError_t vct_launch_dynamic_visibility(const VctRasterArgs& a, const float view_proj[16], int W, int H, int row0, int row1,
+                                         hipStream_t s) {
+    return run_visibility(make_raster(a, view_proj, W, H, row0 * VCT_TILE, row1 * VCT_TILE), s);      // no material: no alpha test
+}
+
+hipError_t vct_launch_dynamic_draw_prepare(const float* pos, int32_t ntri, float model_scale, float vertex_limit, float* draw_pos,
+                                           float* draw_nrm, float* draw_tan, float* draw_bit, hipStream_t s) {
+    if (ntri <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_dyn_draw_prepare, dim3((ntri + 255) / 256), dim3(256), 0, s, pos, ntri, model_scale, vertex_limit,
+                       draw_pos, draw_nrm, draw_tan, draw_bit);
+    return hipGetLastError();
+}
+
 hipError_t vct_launch_gbuffer_shade(const VctRasterArgs& a, const float view_proj[16], int W, int H, int row0, int row1,
                                     const uint32_t* shadow, uint32_t shadow_ebase, int shadow_size, const uint2* shadow_tiles,
-                                    const float light_vp[16], float* tiled, float* emis_tiled, uint8_t* gloss_tiled, hipStream_t s) {
+                                    const float light_vp[16], float* tiled, float* emis_tiled, uint8_t* gloss_tiled, hipStream_t s,
+                                    const VctDynShadeArgs* dyn) {
     ShadeParams p = make_shade(a, view_proj, W, H, row0, row1);
     p.shadow_tiles = shadow ? shadow_tiles : nullptr;
     p.nrm = a.nrm; p.tan = a.tan; p.bit = a.bit;
@@ -2135,8 +2232,22 @@ hipError_t vct_launch_gbuffer_shade(const VctRasterArgs& a, const float view_pro
     const int tiles = p.tile1 - p.tile0;
     if (tiles <= 0) return hipSuccess;
     const int per_block = VCT_SHADE_BLOCK / 64;       // tiles (waves) per workgroup
-    if (a.tex.texels) hipLaunchKernelGGL(k_gbuffer_shade<true>, dim3((tiles + per_block - 1) / per_block), dim3(VCT_SHADE_BLOCK), 0, s, p);
-    else hipLaunchKernelGGL(k_gbuffer_shade<false>, dim3((tiles + per_block - 1) / per_block), dim3(VCT_SHADE_BLOCK), 0, s, p);
+    const dim3 grid((tiles + per_block - 1) / per_block), block(VCT_SHADE_BLOCK);
+    if (dyn) {
+        ShadeArgs<true> q;
+        static_cast<ShadeParams&>(q) = p;
+        q.d.vis = dyn->vis;
+        q.d.pos = dyn->pos; q.d.nrm = dyn->nrm; q.d.tan = dyn->tan; q.d.bit = dyn->bit;
+        q.d.material = dyn->material; q.d.albedo = dyn->albedo;
+        for (int k = 0; k < 3; ++k) q.d.specular[k] = dyn->specular[k];
+        if (a.tex.texels) hipLaunchKernelGGL((k_gbuffer_shade<true, true>), grid, block, 0, s, q);
+        else hipLaunchKernelGGL((k_gbuffer_shade<false, true>), grid, block, 0, s, q);
+        return hipGetLastError();
+    }
+    ShadeArgs<false> q;
+    static_cast<ShadeParams&>(q) = p;
+    if (a.tex.texels) hipLaunchKernelGGL((k_gbuffer_shade<true, false>), grid, block, 0, s, q);
+    else hipLaunchKernelGGL((k_gbuffer_shade<false, false>), grid, block, 0, s, q);
     return hipGetLastError();
 }
 

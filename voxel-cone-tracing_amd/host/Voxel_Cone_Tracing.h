@@ -378,8 +378,9 @@ struct Voxel_Cone_Tracing {
     // small mesh -- flat colours, no textures -- that every volume pass voxelizes anew and merges into the chain, so that
     // moving it costs no upload of the scene.  After init.  pos == NULL detaches.  UpdateDynamicMesh hands over new
     // positions of the same triangles (host memory, or device memory with VCT_MEM_DEVICE); the next volume pass uses
-    // them: every Render() under DynamicLight, DrawVoxelTexture() otherwise.  The library's own main draw does not show
-    // the object: its pixels come in through ImportGBuffer.  Not with Bounces = 2 or ReferenceVoxelization.
+    // them: every Render() under DynamicLight, DrawVoxelTexture() otherwise.  The library's own raster stages draw the
+    // object once DrawDynamicMesh says so (below); otherwise its pixels come in through ImportGBuffer.  Not with
+    // Bounces = 2 or ReferenceVoxelization.
     bool SetDynamicMesh(const float* pos, const int32_t* material, int32_t ntri, const float* albedo, int32_t nmat,
                         int32_t max_bricks = 0) {
         if (!ctx) return false;
@@ -388,6 +389,16 @@ struct Voxel_Cone_Tracing {
     bool UpdateDynamicMesh(const float* pos, int32_t location = VCT_MEM_HOST) {
         if (!ctx) return false;
         return check(vct_update_dynamic_positions(ctx, pos, location), "vct_update_dynamic_positions");
+    }
+    // Draws the dynamic mesh in the library's own raster stages (vct_set_dynamic_draw): `shadow` -- it casts into the
+    // shadow map of DrawDepthTexture() and of every whole GI pass, and every PCF reader sees it; `gbuffer` -- the main
+    // draw shows it, with flat per-face normals, its table's colours and the specular colour `specular` (NULL: black).
+    // Render() under DynamicLight then shows and shadows the object.  After init, before or after SetDynamicMesh: the
+    // setting outlives the mesh.
+    bool DrawDynamicMesh(bool shadow, bool gbuffer, const float* specular = nullptr) {
+        if (!ctx) return false;
+        const int32_t flags = (shadow ? VCT_DYNAMIC_DRAW_SHADOW : 0) | (gbuffer ? VCT_DYNAMIC_DRAW_GBUFFER : 0);
+        return check(vct_set_dynamic_draw(ctx, flags, specular), "vct_set_dynamic_draw");
     }
 
     // The sky: coefficients as vct_set_sky takes them (NULL: none), or the three colours of a gradient about `up` (NULL: +y)

@@ -12,13 +12,15 @@
 //            [--gloss-classes TAN,SHIN[;TAN,SHIN...] --gloss MATERIAL=CLASS[;MATERIAL=CLASS...]]
 //            [--sky-gradient ZR,ZG,ZB;HR,HG,HB;GR,GG,GB[;UX,UY,UZ] | --sky-sh FILE] [--reimport]
 //            [--light X,Y,Z;R,G,B;RADIUS;SRC[;DX,DY,DZ;INNER_DEG;OUTER_DEG]]...
-//            [--dynamic-obj FILE --dynamic-path X0,Y0,Z0;X1,Y1,Z1]
+//            [--dynamic-obj FILE --dynamic-path X0,Y0,Z0;X1,Y1,Z1 --dynamic-draw shadow|gbuffer|both]
 // --dynamic-obj FILE: a second Wavefront OBJ as the context's dynamic mesh (Voxel_Cone_Tracing::SetDynamicMesh,
 //   vct_set_dynamic_mesh; flat material colours, its textures are not used), translated along the segment of
 //   --dynamic-path (model units, the OBJ's own; default: it stays where it is) over the run's frames.  Every Render()
-//   is then a whole GI pass, as with --dynamic-light, and hands over the frame's positions first.  The main draw does
-//   not show the object (a renderer brings its pixels through the G-buffer import); the voxels do.  Prints the two
-//   kernel times of vct_last_dynamic_ms.  Not with --gpus or --bounces 2.
+//   is then a whole GI pass, as with --dynamic-light, and hands over the frame's positions first.  The voxels show the
+//   object; the library's own raster stages draw it with --dynamic-draw (Voxel_Cone_Tracing::DrawDynamicMesh,
+//   vct_set_dynamic_draw): `shadow` lets it cast into the shadow map, `gbuffer` shows it in the frame, `both` both.
+//   Without the option a renderer brings its pixels through the G-buffer import.  Prints the two kernel times of
+//   vct_last_dynamic_ms.  Not with --gpus or --bounces 2.
 //
 // --light SPEC (repeatable, up to 64): a local light (Voxel_Cone_Tracing::SetLights, vct_set_lights) in world units: a point
 //   light at X,Y,Z of colour R,G,B (the factor at distance 1) that reaches RADIUS and whose inverse-square falloff is
@@ -164,6 +166,7 @@ int main(int argc, char** argv) {
     std::vector<const char*> light_args;
     const char* dynamic_obj = nullptr;
     const char* dynamic_path = nullptr;
+    const char* dynamic_draw = nullptr;
     int cubes[3] = {0, 0, 0};
     bool show_voxels = false;
     int view_source = VCT_VOXVIEW_CURRENT, view_level = 0;
@@ -192,7 +195,10 @@ int main(int argc, char** argv) {
             }
             continue;
         }
-        if (i + 1 >= argc) break;
+        if (i + 1 >= argc) {
+            if (!strcmp(argv[i], "--dynamic-draw")) { fprintf(stderr, "%s\n", VCT_DEMO_DYNAMIC_DRAW_USAGE); return 1; }
+            break;
+        }
         if (!strcmp(argv[i], "--scene")) scene = argv[++i];
         else if (!strcmp(argv[i], "--voxels")) voxels = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--size")) sscanf(argv[++i], "%dx%d", &w, &h);
@@ -212,6 +218,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--light") && i + 1 < argc) light_args.push_back(argv[++i]);
         else if (!strcmp(argv[i], "--dynamic-obj")) dynamic_obj = argv[++i];
         else if (!strcmp(argv[i], "--dynamic-path")) dynamic_path = argv[++i];
+        else if (!strcmp(argv[i], "--dynamic-draw")) dynamic_draw = argv[++i];
         else if (!strcmp(argv[i], "--ambient-cubes") && i + 2 < argc) {
             if (sscanf(argv[++i], "%d,%d,%d", &cubes[0], &cubes[1], &cubes[2]) != 3 || cubes[0] < 1 || cubes[1] < 1 || cubes[2] < 1 ||
                 (long long)cubes[0] * cubes[1] * cubes[2] * 6 > VCT_POINT_QUERY_MAX) {
@@ -253,6 +260,12 @@ int main(int argc, char** argv) {
     std::vector<int32_t> dyn_material;
     int32_t dyn_ntri = 0, dyn_nmat = 0;
     if (dynamic_path && !dynamic_obj) { fprintf(stderr, "--dynamic-path: needs --dynamic-obj\n"); return 1; }
+    int dyn_draw_flags = 0;
+    if (dynamic_draw) {
+        if (!dynamic_obj) { fprintf(stderr, "--dynamic-draw: needs --dynamic-obj\n"); return 1; }
+        dyn_draw_flags = vct_demo_parse_dynamic_draw(dynamic_draw);
+        if (dyn_draw_flags < 0) { fprintf(stderr, "%s\n", VCT_DEMO_DYNAMIC_DRAW_USAGE); return 1; }
+    }
     if (dynamic_obj) {
         if (gpus > 0 || bounces >= 2) { fprintf(stderr, "--dynamic-obj: not with --gpus or --bounces 2\n"); return 1; }
         if (dynamic_path) {
@@ -397,6 +410,8 @@ int main(int argc, char** argv) {
                 dyn_frames[f][i] += dyn_path[0][i % 3] + t * (dyn_path[1][i % 3] - dyn_path[0][i % 3]);
         }
         if (!voxel_cone_tracing.SetDynamicMesh(dyn_frames[0].data(), dyn_material.data(), dyn_ntri, dyn_albedo.data(), dyn_nmat)) return 3;
+        if (dyn_draw_flags && !voxel_cone_tracing.DrawDynamicMesh((dyn_draw_flags & VCT_DYNAMIC_DRAW_SHADOW) != 0,
+                                                                  (dyn_draw_flags & VCT_DYNAMIC_DRAW_GBUFFER) != 0)) return 3;
     }
     auto move_dynamic = [&](int f) {                        // frame f's positions, before its Render()
         return !dynamic_obj || voxel_cone_tracing.UpdateDynamicMesh(dyn_frames[(size_t)f % dyn_frames.size()].data());

@@ -5,6 +5,7 @@
 
 #include <math.h>
 #include <stdio.h>
+#include <string.h>
 
 #include <utility>
 #include <vector>
@@ -124,6 +125,17 @@ static inline const char* vct_demo_parse_light(const char* text, vct_light& out)
     if (!(out.cos_outer < out.cos_inner)) return text;      // angles too close to tell apart in fp32
     out.flags = VCT_LIGHT_SPOT;
     return nullptr;
+}
+
+// --dynamic-draw shadow|gbuffer|both: the stages that draw the --dynamic-obj mesh (vct_set_dynamic_draw).  Returns the
+// VCT_DYNAMIC_DRAW_* flags, or -1 for any other word.
+#define VCT_DEMO_DYNAMIC_DRAW_USAGE "--dynamic-draw shadow|gbuffer|both (with --dynamic-obj): draw the dynamic mesh into the shadow map, the G-buffer or both"
+static inline int vct_demo_parse_dynamic_draw(const char* word) {
+    if (!word) return -1;
+    if (!strcmp(word, "shadow")) return VCT_DYNAMIC_DRAW_SHADOW;
+    if (!strcmp(word, "gbuffer")) return VCT_DYNAMIC_DRAW_GBUFFER;
+    if (!strcmp(word, "both")) return VCT_DYNAMIC_DRAW_SHADOW | VCT_DYNAMIC_DRAW_GBUFFER;
+    return -1;
 }
 
 #endif

@@ -862,8 +862,26 @@ int vct_last_lights_ms(vct_ctx* ctx, float ms[2]);   /* [0] voxel kernel of the 
  * vct_inject_light; needs vct_set_trace_timing on when they were issued (VCT_ERR_INVALID otherwise and before both ran).
  * VCT_ERR_INVALID, nothing touched: ntri outside 1 .. VCT_DYNAMIC_TRIS_MAX, nmat < 1, max_bricks < 0, a material index
  * out of range, a NULL table, an unknown location, an update without an attached mesh; and while a dynamic mesh is attached
- * vct_voxelize(ctx, VCT_VOX_REFERENCE) (as with emission and lights) and vct_bounce -- the bounce walks the static slots'
- * attributes; carrying the second bounce over the dynamic layer is a follow-up.
+ * vct_voxelize(ctx, VCT_VOX_REFERENCE) (as with emission and lights) and, unless vct_set_dynamic_bounce is on, vct_bounce
+ * -- the plain bounce walks the static slots and their attributes only.
+ * The second bounce (vct_set_dynamic_bounce; off by default).  With the layer's three volumes D, Da, Dn
+ * (vct_download_dynamic_voxels) and the static resolve's S, Sa, Sn, vct_bounce with a mesh attached and the switch on
+ * gives, bit for bit, the oracle's
+ *   vcto_bounce(chain0 = the merged bounce-0 chain the context holds,
+ *               attr_albedo = where(D.a > 0, Da, Sa),  attr_normal = where(D.a > 0, Dn, Sn))
+ * with a mip build of the result behind it as ever.  A voxel the layer occupies -- D.a > 0 in the last resolved pass -- is
+ * shaded with the layer's albedo and normal, every other voxel with the static ones; both kinds gather their six cones
+ * from the merged chain, so static voxels pick up the mover's light and occlusion.  The rule "alpha != 0 and stored normal
+ * != zero" applies to the owner's normal.  level0, the bounce's src, is the lit merged texel (local lights, emission);
+ * ownership is decided by the layer's own radiance, which is stored before lights.  vct_get_stage_counts reports the
+ * oracle's steps.  A pass the layer was left out of (Capacity) bounces as the static chain alone, and so does a pass that
+ * had no layer to resolve (attached, replaced or detached between vct_voxelize and vct_inject_light).  Everything else
+ * vct_bounce does is unchanged: the second chain's sparse mips, the directional chains, and the return to bounce 0 at the
+ * next vct_inject_light.  The switch is context state: it survives attach, replace and detach of the mesh and
+ * vct_upload_triangles, does nothing while no mesh is attached, and waits for nothing; the first bounce that needs it
+ * allocates one word per 8^3 brick of the grid.  Off, the refusal above stands; detached, or on with nothing attached,
+ * every kernel vct_bounce launches, and its argument block, is the one launched without this paragraph.  A value other
+ * than 0 or 1: VCT_ERR_INVALID, nothing touched.  vct_get_dynamic_bounce: the state as set.
  * Drawing (vct_set_dynamic_draw; off by default): with VCT_DYNAMIC_DRAW_SHADOW vct_render_shadow_map, with
  * VCT_DYNAMIC_DRAW_GBUFFER vct_render_gbuffer / _rows (and both stages inside vct_gi_pass and a rank's frame step) give,
  * bit for bit -- shadow-map words, all 23 planes, pixel-emission and pixel-gloss planes -- what they would give for ONE
@@ -902,6 +920,8 @@ int vct_download_dynamic_voxels(vct_ctx* ctx, uint8_t* radiance, uint8_t* albedo
 int vct_last_dynamic_ms(vct_ctx* ctx, float ms[2]);
 int vct_set_dynamic_draw(vct_ctx* ctx, int32_t flags, const float specular[3] /* NULL: 0,0,0 */);
 int vct_get_dynamic_draw(vct_ctx* ctx, int32_t* flags, float specular[3]);
+int vct_set_dynamic_bounce(vct_ctx* ctx, int32_t on);      /* 0 (default) or 1 */
+int vct_get_dynamic_bounce(vct_ctx* ctx, int32_t* on);
 
 /* ---- two frames in flight (round 6) -----------------------------------------------------------------
  * The reference's Render() (VCT.h:146-190) issues GL commands; the driver starts frame k + 1 while frame k

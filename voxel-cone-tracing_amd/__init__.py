@@ -82,6 +82,7 @@ ABI_SYMBOLS = [
     "vct_set_lights", "vct_get_lights", "vct_download_pixel_lights", "vct_last_lights_ms",
     "vct_set_dynamic_mesh", "vct_update_dynamic_positions", "vct_get_dynamic", "vct_download_dynamic_voxels",
     "vct_last_dynamic_ms", "vct_set_dynamic_draw", "vct_get_dynamic_draw",
+    "vct_set_dynamic_bounce", "vct_get_dynamic_bounce",
 ]
 
 
@@ -249,6 +250,8 @@ _lib.vct_download_dynamic_voxels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p,
 _lib.vct_last_dynamic_ms.argtypes = [C.c_void_p, C.c_void_p]
 _lib.vct_set_dynamic_draw.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
 _lib.vct_get_dynamic_draw.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.vct_set_dynamic_bounce.argtypes = [C.c_void_p, C.c_int32]
+_lib.vct_get_dynamic_bounce.argtypes = [C.c_void_p, C.c_void_p]
 _lib.vct_upload_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
 
 
@@ -721,6 +724,19 @@ class Context:
         flags, sp = C.c_int32(0), (C.c_float * 3)()
         self._ck(_lib.vct_get_dynamic_draw(self._h, C.byref(flags), sp), "vct_get_dynamic_draw")
         return int(flags.value), np.array(list(sp), np.float32)
+
+    def set_dynamic_bounce(self, on):
+        """bounce() with a dynamic mesh attached: off (the default) it is refused, on it runs over the merged chain and
+        shades the voxels the dynamic layer occupies with the layer's albedo and normal.  Context state: it outlives the
+        mesh and does nothing while none is attached."""
+        self._ck(_lib.vct_set_dynamic_bounce(self._h, int(on)), "vct_set_dynamic_bounce")
+
+    @property
+    def dynamic_bounce(self):
+        """The switch as set by set_dynamic_bounce."""
+        on = C.c_int32(0)
+        self._ck(_lib.vct_get_dynamic_bounce(self._h, C.byref(on)), "vct_get_dynamic_bounce")
+        return bool(on.value)
 
     def upload_shadow_map(self, depth, light_vp_rowmajor):
         if depth is None:

@@ -139,6 +139,7 @@ int vct_set_dynamic_mesh(vct_ctx* c, const float* pos, const int32_t* material, 
         PIPE_TRY(vct_synchronize(c));         // a kernel in flight may still read the layer
         VctDynamic none;
         none.keep_draw_state(c->dyn);         // vct_set_dynamic_draw is context state: it outlives the mesh
+        none.keep_bounce_state(c->dyn);       // and so is vct_set_dynamic_bounce
         c->dyn = std::move(none);
         return VCT_OK;
     }
@@ -197,6 +198,7 @@ int vct_set_dynamic_mesh(vct_ctx* c, const float* pos, const int32_t* material, 
     HIP_TRY(c, d.vox_timer.create());           // the events now, so that no pass allocates
     HIP_TRY(c, d.merge_timer.create());
     d.keep_draw_state(c->dyn);
+    d.keep_bounce_state(c->dyn);
     if (d.draw_flags) PIPE_TRY(draw_prepare(c, d, s));      // drawn: the draw copy and the frames of these positions
     HIP_TRY(c, hipStreamSynchronize(s));        // the caller's arrays are free again
     c->dyn = std::move(d);
@@ -235,6 +237,20 @@ int vct_get_dynamic_draw(vct_ctx* c, int32_t* flags, float specular[3]) {
     if (!c || !flags || !specular) return VCT_ERR_INVALID;
     *flags = c->dyn.draw_flags;
     for (int k = 0; k < 3; ++k) specular[k] = c->dyn.draw_specular[k];
+    return VCT_OK;
+}
+
+int vct_set_dynamic_bounce(vct_ctx* c, int32_t on) {
+    if (!c) return VCT_ERR_INVALID;
+    if (const char* why = vct_dynamic_check_bounce(on))
+        return vct_fail(c, VCT_ERR_INVALID, std::string("vct_set_dynamic_bounce: ") + why);
+    c->dyn.bounce_on = on;      // read by the next vct_bounce; nothing in flight depends on it
+    return VCT_OK;
+}
+
+int vct_get_dynamic_bounce(vct_ctx* c, int32_t* on) {
+    if (!c || !on) return VCT_ERR_INVALID;
+    *on = c->dyn.bounce_on;
     return VCT_OK;
 }
 

@@ -1,5 +1,6 @@
 // vct_api_voxel.hip -- the C ABI's voxel stages: voxelize, inject, mips, bounce, and the up/downloads of the volume.
 #include "vct_ctx.h"
+#include "vct_dynamic_check.h"
 
 namespace {
 
@@ -199,7 +200,9 @@ int vct_inject_light(vct_ctx* c) {
         HIP_TRY(c, c->lights.vox_timer.end(cur(c).stream.get()));
     }
     // the dynamic mesh wins per voxel (include/vct.h "dynamic mesh"): behind the static resolve and its lights
-    if (c->dyn.pending && c->acc_mode == VCT_VOX_CONSERVATIVE_AVG) PIPE_TRY(vct_dynamic_merge(c));
+    const bool merges = c->dyn.pending && c->acc_mode == VCT_VOX_CONSERVATIVE_AVG;
+    if (merges) PIPE_TRY(vct_dynamic_merge(c));
+    c->dyn.in_chain = merges;       // (vct_bounce: a pass with no layer to merge bounces as the static chain)
     c->vox.acc_pending = false;
     c->vol.level0_resolved();
     c->vox.attrs_valid = c->vox.attr_normal && c->acc_mode == VCT_VOX_CONSERVATIVE_AVG;
@@ -256,7 +259,7 @@ int vct_build_mips(vct_ctx* c) {
 
 int vct_bounce(vct_ctx* c) {
     if (!c) return VCT_ERR_INVALID;
-    if (c->dyn.attached())      // the bounce walks the static slots' attributes; carrying it over the dynamic layer is a follow-up
+    if (c->dyn.attached() && !c->dyn.bounce_on)      // the plain bounce walks the static slots and their attributes only
         return vct_fail(c, VCT_ERR_INVALID, "vct_bounce: a dynamic mesh is attached and the second bounce does not see its voxels "
                                         "(vct_set_dynamic_mesh(ctx, NULL, ...) first)");
     if (!c->cfg.voxel_attributes || !c->vox.attr_normal)
@@ -302,9 +305,26 @@ int vct_bounce(vct_ctx* c) {
     p.bounce_list = c->bounce_list.get() + 1;
     p.bounce_list_cap = (uint32_t)(c->bounce_list.size() - 1);
     p.brick_over = c->brick_over.get();
+    // the dynamic layer in the chain (include/vct.h "dynamic mesh", the second bounce): the DYN kernels and their table
+    const VctDynamic& d = c->dyn;
+    const bool dyn = d.attached() && d.bounce_on && d.in_chain && d.pool_alb;
+    VctBounceDynArgs da;
+    memset(&da, 0, sizeof(da));
+    if (dyn) {
+        const size_t map_bytes = vct_dynamic_bounce_map_bytes(c->cfg.voxel_dim);
+        if (!c->bounce_dyn_map) HIP_TRY(c, c->bounce_dyn_map.alloc(map_bytes / sizeof(uint32_t)));
+        da.res_brick = d.res_brick.get();
+        da.used = d.words.get() + VCT_DYN_W_STATS + 8 * d.set + 1;
+        da.pool_rad = d.pool_rad.get(); da.pool_alb = d.pool_alb.get(); da.pool_nrm = d.pool_nrm.get();
+        da.brick_res = c->bounce_dyn_map.get();
+        da.max_bricks = d.max_bricks;
+        da.list_slots = vct_dynamic_bounce_list_slots(c->vox.nslots, d.max_bricks);
+    }
     HIP_TRY(c, hipMemsetAsync(c->step_counter.get(), 0, VCT_STEP_COUNTERS * sizeof(unsigned long long), cur(c).stream.get()));
     HIP_TRY(c, cur(c).march.begin(cur(c).stream.get(), c->time_traces));
-    HIP_TRY(c, vct_launch_bounce(p, cur(c).stream.get()));
+    // (the table is cleared in front of every bounce that uses it: the layer's bricks of the last one need no undoing)
+    if (dyn) HIP_TRY(c, hipMemsetAsync(da.brick_res, 0xff, vct_dynamic_bounce_map_bytes(c->cfg.voxel_dim), cur(c).stream.get()));
+    HIP_TRY(c, vct_launch_bounce(p, cur(c).stream.get(), dyn ? &da : nullptr));
     HIP_TRY(c, cur(c).march.end(cur(c).stream.get()));      // step counter / event pair now describe the bounce launch
     c->last_march_form = c->fast_div ? 2 : 1;
     HIP_TRY(c, vct_launch_build_mips(c->vol.chain_b.get(), c->cfg.voxel_dim, b_sparse ? c->vol.brick_prev.get() : nullptr,

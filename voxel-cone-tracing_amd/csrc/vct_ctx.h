@@ -472,6 +472,12 @@ struct VctDynamic {
     float draw_specular[3] = {0.0f, 0.0f, 0.0f};
     VctBuf<float> draw_pos;             // [ntri][9] `pos`, a triangle outside the vertex contract as nine zeros
     VctBuf<float> draw_nrm, draw_tan, draw_bit;      // [ntri][9] the face frame at all three vertices
+    // The second bounce over the layer (vct_set_dynamic_bounce).  The switch is context state like the draw flags
+    // (keep_bounce_state).  in_chain: the last vct_inject_light merged THIS layer into level 0 -- false for a fresh layer
+    // (attached or replaced since) and after an inject that had no pass of the layer to merge; a pass the layer was left
+    // out of for capacity keeps it true and shows zero used slots on the device.
+    int32_t bounce_on = 0;
+    bool in_chain = false;
 
     bool attached() const { return ntri > 0; }
     bool drawn(int32_t flag) const { return attached() && (draw_flags & flag) && draw_pos; }
@@ -479,6 +485,7 @@ struct VctDynamic {
         draw_flags = o.draw_flags;
         for (int k = 0; k < 3; ++k) draw_specular[k] = o.draw_specular[k];
     }
+    void keep_bounce_state(const VctDynamic& o) { bounce_on = o.bounce_on; }
 };
 
 struct vct_ctx {
@@ -532,6 +539,7 @@ struct vct_ctx {
     VctBuf<uint32_t> plan;             // [4] device counters used while planning
     VctBuf<uint32_t> bounce_list;      // counter word + occupied-voxel list of the bounce
     VctBuf<uint32_t> brick_over;
+    VctBuf<uint32_t> bounce_dyn_map;   // [nbricks] brick -> resolved slot of the dynamic layer, of one bounce (vct_set_dynamic_bounce)
     int acc_mode = 0;                  // vct_voxelize_mode of the pending (or last resolved) pass
     vct_comm* comm = nullptr;          // multi-GPU slabs + gather (vct_comm_init)
     // frame slots (see VctFrameSlot): slots [0, frames_in_flight) are live, slots[cur_slot] is selected

@@ -52,6 +52,23 @@ static inline uint32_t vct_dynamic_grid_bricks(int32_t V) {
     return (uint32_t)(b * b * b);
 }
 
+// What is wrong with the argument of vct_set_dynamic_bounce, or null.
+static inline const char* vct_dynamic_check_bounce(int32_t on) { return on == 0 || on == 1 ? nullptr : "the switch is 0 or 1"; }
+
+// Bytes of the bounce's brick -> resolved-slot table, [grid bricks] uint32; 0: no grid, or the count does not fit size_t.
+static inline size_t vct_dynamic_bounce_map_bytes(int32_t V) {
+    size_t bytes = 0;
+    if (__builtin_mul_overflow((size_t)vct_dynamic_grid_bricks(V), sizeof(uint32_t), &bytes)) return 0;
+    return bytes;
+}
+
+// Slots the bounce's list kernel is sized for: the static slots and, behind them, the layer's.  Both are at most the
+// grid's bricks (2^21); the sum saturates all the same.
+static inline uint32_t vct_dynamic_bounce_list_slots(uint32_t static_slots, uint32_t max_bricks) {
+    const uint64_t n = (uint64_t)static_slots + (uint64_t)max_bricks;
+    return n > 0xffffffffull ? 0xffffffffu : (uint32_t)n;
+}
+
 // Brick slots of the dynamic layer.  asked > 0: as asked; asked == 0: twice the bricks the attached positions touch, at
 // least VCT_DYNAMIC_MIN_BRICKS.  Either way no more than the grid has: more can never be used.
 static inline uint32_t vct_dynamic_capacity(int32_t asked, uint32_t touched, uint32_t grid_bricks) {

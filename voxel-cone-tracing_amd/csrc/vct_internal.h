@@ -358,6 +358,10 @@ struct VctTraceParams {
     // vct_ctx chain_form).  Read by the launch dispatch, by no kernel.
     int32_t chain_form;
 };
+// What a newer form of a kernel needs beside it rides in a second argument struct (VctQueryArgs, VctBounceDynArgs): this
+// one neither grows nor moves, so the kernels every existing launch takes keep their argument block and their code.
+#define VCT_TRACE_PARAMS_BYTES 424
+static_assert(sizeof(VctTraceParams) == VCT_TRACE_PARAMS_BYTES, "VctTraceParams neither grows nor moves");
 #define VCT_DR_NO_ANCHOR 0xffu
 #define VCT_DR_COUNTERS 256             // (power of two) a bank, for the reason VCT_STEP_COUNTERS is one
 #define VCT_DR_CTR_WORDS (2 * VCT_DR_COUNTERS + 1)
@@ -587,7 +591,20 @@ hipError_t vct_launch_slot_bricks(const uint32_t* slot, uint32_t nbricks, uint32
 hipError_t vct_launch_unpool(const uint32_t* pooled, const uint32_t* brick_slot, uint32_t* dense, uint32_t nbricks, hipStream_t s);
 hipError_t vct_launch_voxelize_reference(const VctVoxParams& p, int32_t* big_list, int32_t* big_count,
                                          hipStream_t s);
-hipError_t vct_launch_bounce(const VctTraceParams& p, hipStream_t s);
+// `dyn` not null: the bounce over a chain the dynamic layer was merged into (include/vct.h "dynamic mesh", the second
+// bounce) -- k_bounce_dyn_map writes brick_res (all VCT_NO_SLOT on entry) from the resolved list, then the DYN
+// instantiations of the three bounce kernels run with these pointers behind VctTraceParams
+struct VctBounceDynArgs {
+    const uint32_t* res_brick;   // [max_bricks] slot -> brick of the last resolved pass
+    const uint32_t* used;        // the statistics word of that pass: slots in use
+    const uint32_t* pool_rad;    // [max_bricks][512] the layer's pools
+    const uint32_t* pool_alb;
+    const uint32_t* pool_nrm;
+    uint32_t* brick_res;         // [nbricks] brick -> resolved slot
+    uint32_t max_bricks;
+    uint32_t list_slots;         // static slots + max_bricks (vct_dynamic_check.h): what the list kernel's grid is sized for
+};
+hipError_t vct_launch_bounce(const VctTraceParams& p, hipStream_t s, const VctBounceDynArgs* dyn = nullptr);
 
 // ---- the dynamic mesh (include/vct.h "dynamic mesh"; k_dyn_* in vct_voxelize.hip) ----
 // Voxelized by itself every pass, with no plan: bricks are claimed in a [V^3/512] table (VCT_NO_SLOT -> VCT_DYN_CLAIMED ->

@@ -1826,8 +1826,39 @@ k_diffuse_resolve(const VctTraceParams p) {
 //                   same cone_march as the screen trace (voxels of a locally flat surface trace
 //                   near-parallel cones, so the cooperative sampler applies);
 //   k_bounce_bricks the same march per brick, only for bricks that did not fit the list.
-template <bool WRAP, int FASTDIV>
-__device__ __forceinline__ void bounce_voxels(const VctTraceParams& p, bool alive, size_t vox, int& total_out,
+// DYN (vct_set_dynamic_bounce, include/vct.h "dynamic mesh"): the bounce over a chain the dynamic layer was merged into.
+// A voxel the layer occupies -- its radiance pool shows alpha != 0 there -- takes albedo and normal from the layer's
+// pools, every other voxel from the static pools as ever; the bricks are the static slots plus the layer's resolved
+// bricks that have no static slot.  The layer's brick -> slot table is empty again behind its merge, so
+// k_bounce_dyn_map writes one for the bounce from the resolved list.  The extra pointers ride behind VctTraceParams in
+// the argument block of the DYN instantiations only.
+struct BounceDyn {
+    const uint32_t* res_brick;   // [max_bricks] slot -> brick of the last resolved pass, meaningful below *used only
+    const uint32_t* used;        // that pass's statistics word: slots in use (capped by max_bricks where it is read)
+    const uint32_t* pool_rad;    // [max_bricks][512] the layer's texels before lights: alpha != 0 = the layer owns the voxel
+    const uint32_t* pool_alb;
+    const uint32_t* pool_nrm;
+    const uint32_t* brick_res;   // [nbricks] brick -> resolved slot, VCT_NO_SLOT elsewhere (k_bounce_dyn_map)
+    uint32_t max_bricks;
+};
+template <bool DYN> struct BounceArgs : VctTraceParams {};
+template <> struct BounceArgs<true> : VctTraceParams { BounceDyn d; };
+static_assert(sizeof(BounceArgs<false>) == sizeof(VctTraceParams), "the static instantiations keep their argument block");
+
+__device__ __forceinline__ uint32_t bounce_dyn_used(const BounceDyn& d) { return min(*d.used, d.max_bricks); }
+
+// brick -> resolved slot of the layer, over a table of VCT_NO_SLOT (the host clears it in front): a thread per used slot
+__global__ void __launch_bounds__(256)
+k_bounce_dyn_map(const BounceDyn d, uint32_t nbricks, uint32_t* __restrict__ brick_res) {
+    const uint32_t used = bounce_dyn_used(d);
+    for (uint32_t sl = blockIdx.x * blockDim.x + threadIdx.x; sl < used; sl += gridDim.x * blockDim.x) {
+        const uint32_t b = d.res_brick[sl];
+        if (b < nbricks) brick_res[b] = sl;
+    }
+}
+
+template <bool WRAP, int FASTDIV, bool DYN>
+__device__ __forceinline__ void bounce_voxels(const BounceArgs<DYN>& p, bool alive, size_t vox, int& total_out,
                                               float4* __restrict__ blk, const LaneBlock& lb, MarchStats& ms) {
     const uint32_t* __restrict__ level0 = p.chain;          // level 0 starts the chain
     const float fV = (float)p.V;
@@ -1835,7 +1866,14 @@ __device__ __forceinline__ void bounce_voxels(const VctTraceParams& p, bool aliv
     // has no slot: they read slot 0 and their result is discarded
     const uint32_t slot = p.brick_slot[vox >> 9];
     const size_t pv = (size_t)(slot == VCT_NO_SLOT ? 0u : slot) * 512 + (vox & 511u);
-    const uint32_t src = level0[vox], nq = p.attr_normal[pv], aq = p.attr_albedo[pv];
+    const uint32_t src = level0[vox];
+    uint32_t nq = p.attr_normal[pv], aq = p.attr_albedo[pv];
+    if constexpr (DYN) {      // the owner's attributes: a lane without a slot of the layer reads its slot 0 and keeps the static ones
+        const uint32_t ds = p.d.brick_res[vox >> 9];
+        const size_t dv = (size_t)(ds == VCT_NO_SLOT ? 0u : ds) * 512 + (vox & 511u);
+        const uint32_t dr = p.d.pool_rad[dv], dn = p.d.pool_nrm[dv], da = p.d.pool_alb[dv];
+        if (ds != VCT_NO_SLOT && (dr >> 24) != 0u) { nq = dn; aq = da; }
+    }
     const uint32_t mi = (uint32_t)vox;
     const int i = (int)vct_compact3(mi), j = (int)vct_compact3(mi >> 1), k = (int)vct_compact3(mi >> 2);
     const F3 P = f3((div_rn((float)i + 0.5f, fV) - 0.5f) * p.G, (div_rn((float)j + 0.5f, fV) - 0.5f) * p.G,
@@ -1871,7 +1909,8 @@ __device__ __forceinline__ void bounce_voxels(const VctTraceParams& p, bool aliv
     MarchStats ms = {};
 
 // compaction of one brick into `list` (LDS); returns the number of occupied voxels
-__device__ __forceinline__ int compact_brick(const VctTraceParams& p, uint32_t b, int lane, uint16_t* list) {
+template <bool DYN>
+__device__ __forceinline__ int compact_brick(const BounceArgs<DYN>& p, uint32_t b, int lane, uint16_t* list) {
     // a brick without a slot holds nothing of the current mesh (the host refuses the bounce when the attributes
     // are stale, vct_capi.hip attrs_valid; this keeps the index in bounds regardless)
     const uint32_t slot = p.brick_slot[b];
@@ -1882,11 +1921,22 @@ __device__ __forceinline__ int compact_brick(const VctTraceParams& p, uint32_t b
     uint32_t t[8], a[8];
 #pragma unroll
     for (int it = 0; it < 8; ++it) { t[it] = src[it * 64]; a[it] = nrm[it * 64]; }
+    if constexpr (DYN) {      // the owner's normal per voxel; a voxel nobody owns counts as one with a zero normal
+        const uint32_t ds = p.d.brick_res[b];
+        const bool dyn = ds != VCT_NO_SLOT;
+        const uint32_t* __restrict__ dr = p.d.pool_rad + (size_t)(dyn ? ds : 0u) * 512 + lane;
+        const uint32_t* __restrict__ dn = p.d.pool_nrm + (size_t)(dyn ? ds : 0u) * 512 + lane;
+        uint32_t r[8], m[8];
+#pragma unroll
+        for (int it = 0; it < 8; ++it) { r[it] = dr[it * 64]; m[it] = dn[it * 64]; }
+#pragma unroll
+        for (int it = 0; it < 8; ++it) a[it] = dyn && (r[it] >> 24) != 0u ? m[it] : (has ? a[it] : 0x808080u);
+    }
     int n = 0;
 #pragma unroll
     for (int it = 0; it < 8; ++it) {
         p.bounce_out[(size_t)b * 512 + it * 64 + lane] = t[it];
-        const bool occ = (t[it] >> 24) != 0u && has && (a[it] & 0xffffffu) != 0x808080u;
+        const bool occ = (t[it] >> 24) != 0u && (DYN || has) && (a[it] & 0xffffffu) != 0x808080u;
         const unsigned long long m = ballot64(occ);
         if (occ) list[n + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)(it * 64 + lane);
         n += __popcll(m);
@@ -1898,8 +1948,9 @@ __device__ __forceinline__ int compact_brick(const VctTraceParams& p, uint32_t b
 // counter.  One atomic per brick meant ~10^4 returning atomics on one address at 512^3, which the L2 executes one after
 // the other (~12 ns each): they, not the bricks, were the 0.12-0.14 ms this kernel took (round 3).
 #define VCT_BLIST_WAVES 16
+template <bool DYN>
 __global__ void __launch_bounds__(64 * VCT_BLIST_WAVES)
-k_bounce_list(const VctTraceParams p) {
+k_bounce_list(const BounceArgs<DYN> p) {
     __shared__ uint16_t lds_list[VCT_BLIST_WAVES][512];
     __shared__ uint32_t lds_n[VCT_BLIST_WAVES];
     __shared__ uint32_t lds_base;
@@ -1919,14 +1970,26 @@ k_bounce_list(const VctTraceParams p) {
         }
     }
     // (2) the touched bricks, one wave each, found through the voxelizer's slot table (every brick level 0 can show
-    // content in has a slot) instead of a scan of the grid
-    for (uint32_t s0 = blockIdx.x * VCT_BLIST_WAVES; s0 < p.nslots; s0 += nwaves) {        // workgroup-uniform trip count
+    // content in has a slot) instead of a scan of the grid.  DYN: behind them the layer's used slots, of which those
+    // whose brick has a static slot are passed over -- every brick once.
+    uint32_t nlist = p.nslots;
+    if constexpr (DYN) nlist += bounce_dyn_used(p.d);
+    for (uint32_t s0 = blockIdx.x * VCT_BLIST_WAVES; s0 < nlist; s0 += nwaves) {        // workgroup-uniform trip count
         const uint32_t sl = s0 + (uint32_t)wave;
         uint32_t b = 0u;
         int n = 0;
         if (sl < p.nslots) {
             b = p.slot_brick[sl];
             if (p.brick_prev[b]) n = compact_brick(p, b, lane, list);
+        }
+        if constexpr (DYN) {
+            if (sl >= p.nslots && sl < nlist) {
+                const uint32_t db = p.d.res_brick[sl - p.nslots];
+                if (db < p.nbricks && p.brick_slot[db] == VCT_NO_SLOT && p.brick_prev[db]) {
+                    b = db;
+                    n = compact_brick(p, b, lane, list);
+                }
+            }
         }
         if (lane == 0) lds_n[wave] = (uint32_t)n;
         __syncthreads();
@@ -1956,9 +2019,9 @@ k_bounce_list(const VctTraceParams p) {
 #define VCT_BOUNCE_MIN_WAVES 5     // the per-voxel frame + attribute state spills under the trace kernel's budget; A/B at 512^3
                                    // (bounce + mips, ms): 4: 0.495, 5: 0.489, 6: 0.500, 7: 0.504
 #endif
-template <bool WRAP, int FASTDIV>
+template <bool WRAP, int FASTDIV, bool DYN>
 __global__ void __launch_bounds__(64 * VCT_WAVES_PER_BLOCK, VCT_BOUNCE_MIN_WAVES)
-k_bounce_march(const VctTraceParams p) {
+k_bounce_march(const BounceArgs<DYN> p) {
     VCT_BOUNCE_SETUP
     const uint32_t n = min(*p.bounce_list_count, p.bounce_list_cap);
     const uint32_t nwaves = gridDim.x * VCT_WAVES_PER_BLOCK;
@@ -1969,27 +2032,36 @@ k_bounce_march(const VctTraceParams p) {
         const uint32_t first = __builtin_amdgcn_readfirstlane(e);
         const size_t vox = alive ? e : (first != 0xffffffffu ? first : 0u);
         int total;
-        bounce_voxels<WRAP, FASTDIV>(p, alive, vox, total, blk, lb, ms);
+        bounce_voxels<WRAP, FASTDIV, DYN>(p, alive, vox, total, blk, lb, ms);
         wave_steps += (unsigned long long)total;
     }
     if (lane == 0 && wave_steps)
         atomicAdd(p.step_counter + ((blockIdx.x * VCT_WAVES_PER_BLOCK + wave) & (VCT_STEP_COUNTERS - 1)), wave_steps);
 }
 
-template <bool WRAP, int FASTDIV>
+template <bool WRAP, int FASTDIV, bool DYN>
 __global__ void __launch_bounds__(64 * VCT_WAVES_PER_BLOCK, VCT_BOUNCE_MIN_WAVES)
-k_bounce_bricks(const VctTraceParams p) {
+k_bounce_bricks(const BounceArgs<DYN> p) {
     VCT_BOUNCE_SETUP
     __shared__ uint16_t lds_list[VCT_WAVES_PER_BLOCK][512];
     uint16_t* list = &lds_list[wave][0];
     unsigned long long wave_steps = 0;
     const uint32_t nwaves = gridDim.x * VCT_WAVES_PER_BLOCK;
     // flags of the slots scanned 64 at a time, one per lane; a served brick's flag is reset for the next pass
-    const uint32_t nchunks = (p.nslots + 63u) >> 6;
+    // DYN: behind them the layer's used slots whose brick has no static slot, as k_bounce_list lists them
+    uint32_t nscan = p.nslots;
+    if constexpr (DYN) nscan += bounce_dyn_used(p.d);
+    const uint32_t nchunks = (nscan + 63u) >> 6;
     for (uint32_t c = blockIdx.x * VCT_WAVES_PER_BLOCK + wave; c < nchunks; c += nwaves) {
         const uint32_t sl = c * 64u + (uint32_t)lane;
-        const uint32_t mine = sl < p.nslots ? p.slot_brick[sl] : 0u;
-        const bool over = sl < p.nslots && p.brick_over[mine] != 0u;
+        uint32_t mine = sl < p.nslots ? p.slot_brick[sl] : 0u;
+        bool over = sl < p.nslots && p.brick_over[mine] != 0u;
+        if constexpr (DYN) {
+            if (sl >= p.nslots && sl < nscan) {
+                const uint32_t db = p.d.res_brick[sl - p.nslots];
+                if (db < p.nbricks && p.brick_slot[db] == VCT_NO_SLOT) { mine = db; over = p.brick_over[db] != 0u; }
+            }
+        }
         if (over) p.brick_over[mine] = 0u;
         for (unsigned long long m = ballot64(over); m != 0ull; m &= m - 1ull) {
             const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)mine, __ffsll((long long)m) - 1);
@@ -1999,7 +2071,7 @@ k_bounce_bricks(const VctTraceParams p) {
                 const bool alive = base + lane < n;
                 const size_t vox = (size_t)b * 512 + (alive ? list[base + lane] : list[base]);
                 int total;
-                bounce_voxels<WRAP, FASTDIV>(p, alive, vox, total, blk, lb, ms);
+                bounce_voxels<WRAP, FASTDIV, DYN>(p, alive, vox, total, blk, lb, ms);
                 wave_steps += (unsigned long long)total;
             }
             wave_sync();
@@ -2293,27 +2365,44 @@ hipError_t vct_launch_query_keys(const VctTraceParams& p, const VctQueryArgs& q,
     return hipGetLastError();
 }
 
-template <bool WRAP, int FASTDIV>
-hipError_t launch_bounce(const VctTraceParams& p, hipStream_t s) {
+template <bool WRAP, int FASTDIV, bool DYN>
+hipError_t launch_bounce(const BounceArgs<DYN>& p, uint32_t list_slots, hipStream_t s) {
     uint32_t blocks = (p.nbricks + VCT_WAVES_PER_BLOCK - 1) / VCT_WAVES_PER_BLOCK;
     if (blocks > 256u * 64u) blocks = 256u * 64u;
     const dim3 block(64 * VCT_WAVES_PER_BLOCK);
-    uint32_t lblocks = (p.nslots + VCT_BLIST_WAVES - 1) / VCT_BLIST_WAVES;               // one wave per touched brick
+    uint32_t lblocks = (list_slots + VCT_BLIST_WAVES - 1) / VCT_BLIST_WAVES;             // one wave per touched brick
     if (lblocks > 256u * 8u) lblocks = 256u * 8u;
     if (lblocks < 64u) lblocks = 64u;
-    hipLaunchKernelGGL(k_bounce_list, dim3(lblocks), dim3(64 * VCT_BLIST_WAVES), 0, s, p);
+    hipLaunchKernelGGL(k_bounce_list<DYN>, dim3(lblocks), dim3(64 * VCT_BLIST_WAVES), 0, s, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_bounce_march<WRAP, FASTDIV>), dim3(256 * 24), block, 0, s, p);
+    hipLaunchKernelGGL((k_bounce_march<WRAP, FASTDIV, DYN>), dim3(256 * 24), block, 0, s, p);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_bounce_bricks<WRAP, FASTDIV>), dim3(blocks), block, 0, s, p);
+    hipLaunchKernelGGL((k_bounce_bricks<WRAP, FASTDIV, DYN>), dim3(blocks), block, 0, s, p);
     return hipGetLastError();
 }
 
-hipError_t vct_launch_bounce(const VctTraceParams& p, hipStream_t s) {
+hipError_t vct_launch_bounce(const VctTraceParams& p, hipStream_t s, const VctBounceDynArgs* dyn) {
     if (p.nbricks == 0) return hipSuccess;
-    return with_march_mode(p, [&](auto wrap, auto fastdiv) { return launch_bounce<decltype(wrap)::value, decltype(fastdiv)::value>(p, s); });
+    if (dyn) {
+        BounceArgs<true> q;
+        static_cast<VctTraceParams&>(q) = p;
+        q.d.res_brick = dyn->res_brick; q.d.used = dyn->used;
+        q.d.pool_rad = dyn->pool_rad; q.d.pool_alb = dyn->pool_alb; q.d.pool_nrm = dyn->pool_nrm;
+        q.d.brick_res = dyn->brick_res; q.d.max_bricks = dyn->max_bricks;
+        hipLaunchKernelGGL(k_bounce_dyn_map, dim3((dyn->max_bricks + 255u) / 256u), dim3(256), 0, s, q.d, p.nbricks, dyn->brick_res);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        return with_march_mode(p, [&](auto wrap, auto fastdiv) {
+            return launch_bounce<decltype(wrap)::value, decltype(fastdiv)::value, true>(q, dyn->list_slots, s);
+        });
+    }
+    BounceArgs<false> q;
+    static_cast<VctTraceParams&>(q) = p;
+    return with_march_mode(p, [&](auto wrap, auto fastdiv) {
+        return launch_bounce<decltype(wrap)::value, decltype(fastdiv)::value, false>(q, p.nslots, s);
+    });
 }
 
 // The screen trace of tile rows [tile_row0, tile_row1) (every row_stride-th of them).  variant = config.trace_variant

@@ -380,10 +380,14 @@ struct Voxel_Cone_Tracing {
     // positions of the same triangles (host memory, or device memory with VCT_MEM_DEVICE); the next volume pass uses
     // them: every Render() under DynamicLight, DrawVoxelTexture() otherwise.  The library's own raster stages draw the
     // object once DrawDynamicMesh says so (below); otherwise its pixels come in through ImportGBuffer.  Not with
-    // Bounces = 2 or ReferenceVoxelization.
+    // ReferenceVoxelization; with Bounces = 2 only under DynamicBounce (vct_set_dynamic_bounce: the second bounce shades
+    // the object's voxels with the object's albedo and normal), which is handed over here and before every bounce of
+    // DrawVoxelTexture() -- with Bounces = 2 that call, not Render(), is the volume pass that follows the object.
+    bool DynamicBounce = false;
     bool SetDynamicMesh(const float* pos, const int32_t* material, int32_t ntri, const float* albedo, int32_t nmat,
                         int32_t max_bricks = 0) {
         if (!ctx) return false;
+        if (!check(vct_set_dynamic_bounce(ctx, DynamicBounce ? 1 : 0), "vct_set_dynamic_bounce")) return false;
         return check(vct_set_dynamic_mesh(ctx, pos, material, ntri, albedo, nmat, max_bricks), "vct_set_dynamic_mesh");
     }
     bool UpdateDynamicMesh(const float* pos, int32_t location = VCT_MEM_HOST) {
@@ -530,6 +534,7 @@ struct Voxel_Cone_Tracing {
         if (!check(vct_voxelize(ctx, ReferenceVoxelization ? VCT_VOX_REFERENCE : VCT_VOX_CONSERVATIVE_AVG), "vct_voxelize")) return;
         if (!check(vct_inject_light(ctx), "vct_inject_light")) return;
         if (!check(vct_build_mips(ctx), "vct_build_mips")) return;          // VCT.h:248
+        if (Bounces >= 2 && !check(vct_set_dynamic_bounce(ctx, DynamicBounce ? 1 : 0), "vct_set_dynamic_bounce")) return;
         if (Bounces >= 2) check(vct_bounce(ctx), "vct_bounce");
     }
 

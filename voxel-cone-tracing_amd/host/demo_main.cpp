@@ -12,7 +12,7 @@
 //            [--gloss-classes TAN,SHIN[;TAN,SHIN...] --gloss MATERIAL=CLASS[;MATERIAL=CLASS...]]
 //            [--sky-gradient ZR,ZG,ZB;HR,HG,HB;GR,GG,GB[;UX,UY,UZ] | --sky-sh FILE] [--reimport]
 //            [--light X,Y,Z;R,G,B;RADIUS;SRC[;DX,DY,DZ;INNER_DEG;OUTER_DEG]]...
-//            [--dynamic-obj FILE --dynamic-path X0,Y0,Z0;X1,Y1,Z1 --dynamic-draw shadow|gbuffer|both]
+//            [--dynamic-obj FILE --dynamic-path X0,Y0,Z0;X1,Y1,Z1 --dynamic-draw shadow|gbuffer|both --dynamic-bounce]
 // --dynamic-obj FILE: a second Wavefront OBJ as the context's dynamic mesh (Voxel_Cone_Tracing::SetDynamicMesh,
 //   vct_set_dynamic_mesh; flat material colours, its textures are not used), translated along the segment of
 //   --dynamic-path (model units, the OBJ's own; default: it stays where it is) over the run's frames.  Every Render()
@@ -20,7 +20,9 @@
 //   object; the library's own raster stages draw it with --dynamic-draw (Voxel_Cone_Tracing::DrawDynamicMesh,
 //   vct_set_dynamic_draw): `shadow` lets it cast into the shadow map, `gbuffer` shows it in the frame, `both` both.
 //   Without the option a renderer brings its pixels through the G-buffer import.  Prints the two kernel times of
-//   vct_last_dynamic_ms.  Not with --gpus or --bounces 2.
+//   vct_last_dynamic_ms.  Not with --gpus; with --bounces 2 only together with --dynamic-bounce
+//   (Voxel_Cone_Tracing::DynamicBounce, vct_set_dynamic_bounce: the second bounce runs over the object's voxels too) --
+//   every frame then rebuilds the shadow map and the volume, second bounce included, before its Render().
 //
 // --light SPEC (repeatable, up to 64): a local light (Voxel_Cone_Tracing::SetLights, vct_set_lights) in world units: a point
 //   light at X,Y,Z of colour R,G,B (the factor at distance 1) that reaches RADIUS and whose inverse-square falloff is
@@ -167,6 +169,7 @@ int main(int argc, char** argv) {
     const char* dynamic_obj = nullptr;
     const char* dynamic_path = nullptr;
     const char* dynamic_draw = nullptr;
+    bool dynamic_bounce = false;
     int cubes[3] = {0, 0, 0};
     bool show_voxels = false;
     int view_source = VCT_VOXVIEW_CURRENT, view_level = 0;
@@ -176,10 +179,11 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--idfile")) idfile = argv[++i];
     }
     if (gpus > 0 && rank < 0) return launch_ranks(gpus, argc, argv);
-    // (options with a value consume it; --dynamic-light has none and may stand anywhere)
+    // (options with a value consume it; --dynamic-light, --reimport and --dynamic-bounce have none and may stand anywhere)
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--dynamic-light")) { dynamic_light = true; continue; }
         if (!strcmp(argv[i], "--reimport")) { reimport = true; continue; }
+        if (!strcmp(argv[i], "--dynamic-bounce")) { dynamic_bounce = true; continue; }
         if (!strcmp(argv[i], "--voxels") && !(i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9')) {
             show_voxels = true;                             // the voxel view: SOURCE[:LEVEL] may follow
             if (i + 1 < argc && strncmp(argv[i + 1], "--", 2)) {
@@ -266,8 +270,9 @@ int main(int argc, char** argv) {
         dyn_draw_flags = vct_demo_parse_dynamic_draw(dynamic_draw);
         if (dyn_draw_flags < 0) { fprintf(stderr, "%s\n", VCT_DEMO_DYNAMIC_DRAW_USAGE); return 1; }
     }
+    if (dynamic_bounce && !dynamic_obj) { fprintf(stderr, "--dynamic-bounce: needs --dynamic-obj\n"); return 1; }
     if (dynamic_obj) {
-        if (gpus > 0 || bounces >= 2) { fprintf(stderr, "--dynamic-obj: not with --gpus or --bounces 2\n"); return 1; }
+        if (gpus > 0 || (bounces >= 2 && !dynamic_bounce)) { fprintf(stderr, "--dynamic-obj: not with --gpus or --bounces 2\n"); return 1; }
         if (dynamic_path) {
             int used = 0;
             float* q = &dyn_path[0][0];
@@ -324,6 +329,7 @@ int main(int argc, char** argv) {
     voxel_cone_tracing.ShadowMapSize = (unsigned)shadow;
     voxel_cone_tracing.model_path = scene;
     voxel_cone_tracing.Bounces = bounces;
+    voxel_cone_tracing.DynamicBounce = dynamic_bounce;
     voxel_cone_tracing.VoxelAttributes = !lights.empty();   // --light: the lights read the voxels' albedo and normal
     voxel_cone_tracing.DynamicLight = dynamic_light;       // every Render() = one whole GI pass (vct_gi_pass)
     voxel_cone_tracing.FramesInFlight = in_flight;
@@ -414,7 +420,13 @@ int main(int argc, char** argv) {
                                                                   (dyn_draw_flags & VCT_DYNAMIC_DRAW_GBUFFER) != 0)) return 3;
     }
     auto move_dynamic = [&](int f) {                        // frame f's positions, before its Render()
-        return !dynamic_obj || voxel_cone_tracing.UpdateDynamicMesh(dyn_frames[(size_t)f % dyn_frames.size()].data());
+        if (!dynamic_obj) return true;
+        if (!voxel_cone_tracing.UpdateDynamicMesh(dyn_frames[(size_t)f % dyn_frames.size()].data())) return false;
+        if (bounces >= 2) {                                 // Render() is no whole pass then: the maps follow the object here
+            voxel_cone_tracing.DrawDepthTexture();
+            voxel_cone_tracing.DrawVoxelTexture();
+        }
+        return voxel_cone_tracing.last_status == VCT_OK;
     };
 
     float delta_time = 0.05f;

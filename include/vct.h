@@ -815,7 +815,8 @@ int vct_last_lights_ms(vct_ctx* ctx, float ms[2]);   /* [0] voxel kernel of the 
  * No reference counterpart (its scene never moves), so the definition is this build's.  Beside the uploaded (static)
  * mesh a context may hold ONE dynamic mesh: ntri triangles, model-space fp32 positions [ntri][3][3], a material index per
  * triangle and a flat albedo table [nmat][4] (rgb used), under the same config.model_scale, grid and vertex contract as the
- * static mesh.  It has NO textures and NO emission.  vct_upload_triangles rebuilds the static plan (allocations, host
+ * static mesh.  It has NO textures and NO emission of its own until vct_set_dynamic_emission attaches a table (below).
+ * vct_upload_triangles rebuilds the static plan (allocations, host
  * sorts, synchronisations); the dynamic mesh has no plan: every pass voxelizes it anew on the stream.
  *   A pass             vct_voxelize(VCT_VOX_CONSERVATIVE_AVG) + vct_inject_light, or vct_gi_pass, voxelizes the dynamic
  *                      mesh BY ITSELF exactly as the static one: conservative overlap; per fragment the clamped
@@ -894,7 +895,8 @@ int vct_last_lights_ms(vct_ctx* ctx, float ms[2]);   /* [0] voxel kernel of the 
  *               (normal, tangent, bitangent) = the (u, t, b) of the G-buffer import's frame construction from n ("G-buffer
  *               import": u = unit(n), t, b as there).  They are interpolated and inverted like static attributes;
  *   material    albedo rgb of the dynamic table, alpha plane 1.0 whatever the table's fourth value, no alpha test, the
- *               specular colour `specular` (NULL: 0, 0, 0) for every triangle, no textures, emission 0, gloss class 0.
+ *               specular colour `specular` (NULL: 0, 0, 0) for every triangle, no textures, gloss class 0, emission 0
+ *               unless vct_set_dynamic_emission attached a table (Emission, below).
  * Depth ties resolve as in that one mesh: the lower id wins, so the static mesh wins a tie against the dynamic one.  A
  * triangle outside the vertex contract (the rule above, applied on the device) draws nothing and disturbs nothing.
  * With VCT_DYNAMIC_DRAW_SHADOW the object casts into the map and every PCF reader sees it: the voxelizer (static mesh and
@@ -905,7 +907,33 @@ int vct_last_lights_ms(vct_ctx* ctx, float ms[2]);   /* [0] voxel kernel of the 
  * the attached mesh, the stages allocate their scratch for the dynamic triangles in the first pass that draws them (per
  * frame slot a second visibility buffer, 8 bytes per pixel).  Unknown flag bits or a non-finite specular value:
  * VCT_ERR_INVALID, nothing touched.  vct_get_dynamic_draw: the state as set.
- * Known limits: the drawn mesh has no textures, no emission, no gloss class and flat (per-face) normals.  With a flag off
+ * Emission (vct_set_dynamic_emission; none by default): fp32 rgb per material of the ATTACHED dynamic mesh, flat
+ * [nmat][3], every value finite and >= 0 (values above 1 saturate in the chain, as with vct_upload_emission).  NULL or an
+ * all-zero table detaches.  The table belongs to the mesh: vct_set_dynamic_mesh drops it on attach, on replace and on
+ * detach; vct_upload_triangles of a new static mesh leaves it alone.
+ *   Level 0    DEm is, per voxel with at least one dynamic fragment, the rounded integer mean over the same fragments of
+ *              unorm8(emission[material] * 1.0f) -- (sum + (c >> 1)) / c per channel, no shadow term: the static emission
+ *              rule applied to the dynamic mesh alone.  With D the layer as above,
+ *                D'.rgb = min(255, D.rgb + DEm.rgb) per byte,  D'.a = D.a,  level0 = D.a > 0 ? D' : S'
+ *              and with local lights D.a > 0 ? lit(D', Da, Dn) : lit(S', Sa, Sn), in the order above.
+ *              vct_download_dynamic_voxels' radiance is D' -- still before local lights, its alpha unchanged, so the
+ *              second bounce's ownership rule is untouched; the bounce's src is the lit merged texel as ever.
+ *   The pass   carries the table that was attached when its vct_voxelize was issued.  Attached or detached between
+ *              vct_voxelize and vct_inject_light, that pass has no dynamic emission; replaced in between, it resolves
+ *              with the table it was voxelized under.  A pass left out for capacity adds nothing.
+ *   Frame      the table attaches zeroed pixel-emission planes to every frame slot as vct_upload_emission does, under the
+ *              same rule (refused with config.trace_variant 1 .. 4; a later second slot gets its own); the planes live
+ *              while either table is attached.  With VCT_DYNAMIC_DRAW_GBUFFER the G-buffer stages write them as for the
+ *              ONE static mesh of "Drawing": the static table (zeros where none is attached) followed by the dynamic
+ *              table, the dynamic material indices offset by the static material count.  With the flag off the planes
+ *              hold the static table's values, or 0.
+ * vct_set_dynamic_emission waits for work in flight and allocates everything (the emission sums, 8 KiB per brick slot),
+ * so that a pass with the table attached still allocates nothing, never waits and copies nothing to the host.  With no
+ * table attached every kernel launched, and its argument block, is the one launched without this paragraph.
+ * VCT_ERR_INVALID, the context keeping what it had: no dynamic mesh attached; a NaN, infinite or negative value (the
+ * message names material and channel); the trace_variant conflict.  vct_get_dynamic_emission: the table as set and its
+ * material count (*nmat = 0: none attached; emission may be NULL).
+ * Known limits: the drawn mesh has no textures, no gloss class and flat (per-face) normals.  With a flag off
  * the limit of the stage it names remains: vct_render_shadow_map / vct_render_gbuffer then draw the static mesh only and
  * every kernel launched is the one launched without this paragraph.  The voxel view's albedo / normal sources and
  * vct_download_voxel_attributes show the static pools. */
@@ -922,6 +950,8 @@ int vct_set_dynamic_draw(vct_ctx* ctx, int32_t flags, const float specular[3] /*
 int vct_get_dynamic_draw(vct_ctx* ctx, int32_t* flags, float specular[3]);
 int vct_set_dynamic_bounce(vct_ctx* ctx, int32_t on);      /* 0 (default) or 1 */
 int vct_get_dynamic_bounce(vct_ctx* ctx, int32_t* on);
+int vct_set_dynamic_emission(vct_ctx* ctx, const float* emission /* [nmat][3] of the ATTACHED dynamic mesh */);
+int vct_get_dynamic_emission(vct_ctx* ctx, float* emission /* [nmat][3], may be NULL */, int32_t* nmat /* 0: none */);
 
 /* ---- two frames in flight (round 6) -----------------------------------------------------------------
  * The reference's Render() (VCT.h:146-190) issues GL commands; the driver starts frame k + 1 while frame k

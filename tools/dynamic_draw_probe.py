@@ -11,7 +11,9 @@ The procedural atrium at 256^3, 1920 x 1080, a 4096^2 shadow map, one context.  
 The drawn G-buffer differs from the static one and the flags-off G-buffer is bit for bit the detached one (asserted).
 COMPAT=1: only the two passes detached and attached with the flags off, through entry points the parent commit has -- run
 from a checkout of the parent and from this tree alternately (tools/dynamic_draw_probe.sh does).
-Writes dynamic_draw_probe.txt (or dynamic_draw_probe_compat.txt) to $OUT (default: tool_out/)."""
+EMISSION_ONLY=1: only vct_render_gbuffer with the 10,092-triangle mover drawn, without and with an emission table on the
+mover (vct_set_dynamic_emission), alternating: what the DYN shade kernel pays for the pixel-emission planes.
+Writes dynamic_draw_probe.txt (or dynamic_draw_probe_compat.txt / dynamic_draw_probe_emission.txt) to $OUT (default: tool_out/)."""
 import os
 import sys
 import time
@@ -135,6 +137,28 @@ if COMPAT:
     sys.exit(0)
 
 BOTH = vct.DYNAMIC_DRAW_SHADOW | vct.DYNAMIC_DRAW_GBUFFER
+if os.environ.get("EMISSION_ONLY", "0") == "1":
+    # vct_render_gbuffer with the mover drawn: without an emission table on the mover, with one (vct_set_dynamic_emission:
+    # the DYN shade kernel also writes the pixel-emission planes), alternating; the 10,092-triangle box
+    host, mat, alb = mover(29)
+    table = np.array([[0.9, 0.35, 0.1], [0.0, 0.0, 0.0], [0.25, 2.0, 0.6]], np.float32)
+    ctx.set_dynamic_mesh(host[0], mat, alb)
+    ctx.set_dynamic_draw(BOTH, (0.2, 0.2, 0.2))
+    t = {k: [] for k in ("plain", "table")}
+    for r in range(ROUNDS):
+        ctx.set_dynamic_emission(None)
+        shadow(); gbuffer()
+        t["plain"].append(timed(gbuffer))
+        ctx.set_dynamic_emission(table)
+        shadow(); gbuffer()
+        t["table"].append(timed(gbuffer))
+    lit = int((ctx.download_pixel_emission() > 0).any(0).sum())
+    txt = (f"dynamic_draw_probe emission: atrium {w}x{h}, mover of {host[0].shape[0]} triangles drawn: vct_render_gbuffer without a table "
+           f"{stats(t['plain'])}   with a table {stats(t['table'])} ({lit} emitting pixels)   +{np.median(t['table']) - np.median(t['plain']):.4f} ms")
+    print(txt)
+    with open(os.path.join(out_dir, "dynamic_draw_probe_emission.txt"), "w") as f:
+        f.write(txt + "\n")
+    sys.exit(0)
 lines = [f"dynamic_draw_probe: atrium {V}^3 ({scene.pos.shape[0]} static triangles), {w}x{h}, shadow map {S}^2, "
          f"{ROUNDS} alternating rounds of {REPS} passes"]
 shadow(); gbuffer()

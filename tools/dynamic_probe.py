@@ -10,6 +10,10 @@ renderer has them -- and per mover, medians over ROUNDS rounds:
   * the route a caller had before: vct_upload_triangles of static + mover concatenated, then the same pass -- wall time.
     (Only the triangles are uploaded again, not the mesh attributes and textures a renderer would also have to hand
     over: a lower bound of that route.)
+  * with an emission table on the mover (vct_set_dynamic_emission), on one of its three materials and on all of them:
+    the two kernel times and the attached pass again, alternating with the plain one; and the earlier route of a glowing
+    mover, vct_upload_triangles + vct_upload_emission of scene plus mover every frame.  (A library without the entry
+    point -- a checkout of the parent commit -- skips these lines; NO_REUPLOAD=1 skips both re-upload routes.)
 The chain with the mover differs from the static one (asserted); the detached chain is bit for bit the first one (asserted).
 DETACHED_ONLY=1: only the static pass and the resident step, through entry points every earlier version of the library
 has -- run from a checkout of the parent commit and from this tree alternately (tools/dynamic_probe.sh does).
@@ -138,7 +142,12 @@ for n in SIDES:
     host = [np.ascontiguousarray((tris + c[None, None, :]).reshape(-1, 9), np.float32) for c in path]
     dev = [torch.from_numpy(a).cuda() for a in host]
     torch.cuda.synchronize()
-    t = {k: [] for k in ("ev0", "host0", "wall0", "ev1", "host1", "wall1", "kvox", "kmerge", "up_wall", "up_ev")}
+    t = {k: [] for k in ("ev0", "host0", "wall0", "ev1", "host1", "wall1", "kvox", "kmerge", "up_wall", "up_ev", "upe_wall", "upe_ev")}
+    tables = {"one material": np.array([[0.0, 0.0, 0.0], [0.0, 0.0, 0.0], [0.25, 2.0, 0.6]], np.float32),
+              "all materials": np.array([[0.9, 0.35, 0.1], [0.5, 0.5, 0.5], [0.25, 2.0, 0.6]], np.float32)}
+    if not hasattr(ctx, "set_dynamic_emission"):
+        tables = {}
+    te = {name: {k: [] for k in ("ev", "wall", "kvox", "kmerge")} for name in tables}
     info = None
     for r in range(ROUNDS):
         ctx.set_dynamic_mesh(None)
@@ -157,25 +166,56 @@ for n in SIDES:
         info = ctx.dynamic_info()
         assert not info["left_out"], info
         if r == 0:
-            assert not np.array_equal(ctx.download_chain(), chain0), "the mover changed nothing in the chain"
+            plain = ctx.download_chain()
+            assert not np.array_equal(plain, chain0), "the mover changed nothing in the chain"
+        for name, table in tables.items():                # the same positions, the table attached
+            ctx.set_dynamic_emission(table)
+            timed_pass(lambda: ctx.update_dynamic_positions(dev[1].data_ptr()))
+            a = timed_pass(lambda: ctx.update_dynamic_positions(dev[k].data_ptr()))
+            ms = ctx.last_dynamic_ms()
+            te[name]["ev"].append(a[0]); te[name]["wall"].append(a[2]); te[name]["kvox"].append(ms[0]); te[name]["kmerge"].append(ms[1])
+            if r == 0:
+                assert not np.array_equal(ctx.download_chain(), plain), "the table changed nothing in the chain"
+        if tables:
+            ctx.set_dynamic_emission(None)
     ctx.set_dynamic_mesh(None)
     # the earlier route: the whole scene again, mover included
-    for r in range(ROUNDS):
+    for r in range(0 if os.environ.get("NO_REUPLOAD", "0") == "1" else ROUNDS):
         k = 2 + r % (NPOS - 2)
         pos = np.concatenate([scene.pos.reshape(-1, 9), host[k]])
         material = np.concatenate([scene.material, mat + scene.albedo.shape[0]]).astype(np.int32)
         albedo = np.concatenate([scene.albedo.reshape(-1, 4), alb])
         a = timed_pass(lambda: ctx.upload_triangles(pos, material, albedo))
         t["up_ev"].append(a[0]); t["up_wall"].append(a[2])
+        if tables:                                        # ... and of a glowing mover: the table of scene plus mover too
+            em = np.concatenate([np.zeros((scene.albedo.reshape(-1, 4).shape[0], 3), np.float32), tables["all materials"]])
+
+            def upload_both():
+                ctx.upload_triangles(pos, material, albedo)
+                ctx.upload_emission(em)
+            a = timed_pass(upload_both)
+            t["upe_ev"].append(a[0]); t["upe_wall"].append(a[2])
     ctx.upload_scene(scene)
     timed_pass()
+    if not t["up_wall"]:
+        t["up_ev"] = t["up_wall"] = t["upe_ev"] = t["upe_wall"] = [float("nan")]
     lines += [f"mover of {ntri} triangles: bricks {info['bricks_used']} of {info['max_bricks']} slots, {info['fragments']} fragments",
               f"  dynamic kernels (vct_voxelize) {stats(t['kvox'])}   merge (vct_inject_light) {stats(t['kmerge'])}",
               f"  pass detached          events {stats(t['ev0'])}   host {stats(t['host0'])}   wall {stats(t['wall0'])}",
               f"  update + pass attached events {stats(t['ev1'])}   host {stats(t['host1'])}   wall {stats(t['wall1'])}",
               f"  re-upload + pass       events {stats(t['up_ev'])}   wall {stats(t['up_wall'])}",
               f"  attached / re-upload wall: {np.median(t['wall1']) / np.median(t['up_wall']):.3f}"]
-    print("\n".join(lines[-6:]), flush=True)
+    nl = 6
+    for name in tables:
+        lines += [f"  table on {name}: dynamic kernels {stats(te[name]['kvox'])}   merge {stats(te[name]['kmerge'])}",
+                  f"  table on {name}: update + pass attached events {stats(te[name]['ev'])}   wall {stats(te[name]['wall'])}"]
+        nl += 2
+    if tables and t["upe_wall"]:
+        lines += [f"  re-upload with vct_upload_emission + pass events {stats(t['upe_ev'])}   wall {stats(t['upe_wall'])}",
+                  f"  attached with a table on all materials / that route, wall: "
+                  f"{np.median(te['all materials']['wall']) / np.median(t['upe_wall']):.3f}"]
+        nl += 2
+    print("\n".join(lines[-nl:]), flush=True)
 ctx.close()
 txt = "\n".join(lines)
 with open(os.path.join(out_dir, "dynamic_probe.txt"), "w") as f:

@@ -82,7 +82,7 @@ ABI_SYMBOLS = [
     "vct_set_lights", "vct_get_lights", "vct_download_pixel_lights", "vct_last_lights_ms",
     "vct_set_dynamic_mesh", "vct_update_dynamic_positions", "vct_get_dynamic", "vct_download_dynamic_voxels",
     "vct_last_dynamic_ms", "vct_set_dynamic_draw", "vct_get_dynamic_draw",
-    "vct_set_dynamic_bounce", "vct_get_dynamic_bounce",
+    "vct_set_dynamic_bounce", "vct_get_dynamic_bounce", "vct_set_dynamic_emission", "vct_get_dynamic_emission",
 ]
 
 
@@ -252,6 +252,8 @@ _lib.vct_set_dynamic_draw.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
 _lib.vct_get_dynamic_draw.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.vct_set_dynamic_bounce.argtypes = [C.c_void_p, C.c_int32]
 _lib.vct_get_dynamic_bounce.argtypes = [C.c_void_p, C.c_void_p]
+_lib.vct_set_dynamic_emission.argtypes = [C.c_void_p, C.c_void_p]
+_lib.vct_get_dynamic_emission.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.vct_upload_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
 
 
@@ -663,7 +665,7 @@ class Context:
         following voxelize + inject_light (or gi_pass) voxelizes it and merges it into level 0: it wins per voxel."""
         if pos is None:
             self._ck(_lib.vct_set_dynamic_mesh(self._h, None, None, 0, None, 0, 0), "vct_set_dynamic_mesh")
-            self._dyn_ntri = 0
+            self._dyn_ntri = self._dyn_nmat = 0
             return
         pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 9)
         material = np.ascontiguousarray(material, np.int32).reshape(-1)
@@ -673,6 +675,7 @@ class Context:
         self._ck(_lib.vct_set_dynamic_mesh(self._h, _ptr(pos), _ptr(material), pos.shape[0], _ptr(albedo), albedo.shape[0],
                                            int(max_bricks)), "vct_set_dynamic_mesh")
         self._dyn_ntri = pos.shape[0]
+        self._dyn_nmat = albedo.shape[0]
 
     def update_dynamic_positions(self, pos):
         """New positions of the attached dynamic mesh's triangles: a float32 array [ntri, 9] or an int device pointer to
@@ -737,6 +740,30 @@ class Context:
         on = C.c_int32(0)
         self._ck(_lib.vct_get_dynamic_bounce(self._h, C.byref(on)), "vct_get_dynamic_bounce")
         return bool(on.value)
+
+    def set_dynamic_emission(self, emission):
+        """Material emission [nmat, 3] (fp32 RGB, finite, >= 0) of the ATTACHED dynamic mesh; None or an all-zero table
+        detaches.  The mesh drops it on attach, replace and detach.  Shows in the chain from the next voxelize +
+        inject_light on, and -- with DYNAMIC_DRAW_GBUFFER -- in the pixel-emission planes of the next G-buffer pass."""
+        if emission is None:
+            self._ck(_lib.vct_set_dynamic_emission(self._h, None), "vct_set_dynamic_emission")
+            return
+        emission = np.ascontiguousarray(emission, np.float32)
+        nmat = getattr(self, "_dyn_nmat", 0)
+        if emission.ndim != 2 or emission.shape[1] != 3 or (nmat and emission.shape[0] != nmat):
+            raise VctError(f"set_dynamic_emission: a table of shape {tuple(emission.shape)}, the attached dynamic mesh has "
+                           f"{nmat} materials: [{nmat}, 3] is expected")
+        self._ck(_lib.vct_set_dynamic_emission(self._h, _ptr(emission)), "vct_set_dynamic_emission")
+
+    def dynamic_emission(self):
+        """The dynamic mesh's emission table as set, float32 [nmat, 3], or None while none is attached."""
+        n = C.c_int32(0)
+        self._ck(_lib.vct_get_dynamic_emission(self._h, None, C.byref(n)), "vct_get_dynamic_emission")
+        if not n.value:
+            return None
+        out = np.zeros((n.value, 3), np.float32)
+        self._ck(_lib.vct_get_dynamic_emission(self._h, _ptr(out), C.byref(n)), "vct_get_dynamic_emission")
+        return out
 
     def upload_shadow_map(self, depth, light_vp_rowmajor):
         if depth is None:

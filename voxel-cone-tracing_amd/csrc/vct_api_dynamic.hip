@@ -1,7 +1,8 @@
 // vct_api_dynamic.hip -- the C ABI of the dynamic mesh (include/vct.h "dynamic mesh"): a second, small mesh whose
 // positions change every frame, voxelized by itself in every pass and merged into level 0 behind the static resolve.
-// Everything the per-pass path needs is allocated by vct_set_dynamic_mesh; a pass with the mesh attached issues a memset
-// of four words and kernels on the selected slot's stream, nothing else.
+// Everything the per-pass path needs is allocated by vct_set_dynamic_mesh (the emission table and its sums by
+// vct_set_dynamic_emission); a pass with the mesh attached issues a memset of four words and kernels on the selected
+// slot's stream, nothing else.
 #include "vct_ctx.h"
 #include "vct_dynamic_check.h"
 
@@ -53,7 +54,8 @@ int launch_merge(vct_ctx* c, bool discard) {
     a.pool_rad = d.pool_rad.get(); a.pool_alb = d.pool_alb.get(); a.pool_nrm = d.pool_nrm.get();
     a.level0 = c->vol.chain.get();
     a.brick_prev = c->vol.brick_prev.get();
-    HIP_TRY(c, vct_launch_dynamic_merge(a, cur(c).stream.get()));
+    // a pass voxelized with the emission table: the EMIS form resolves (or, discarding, only re-zeroes) the sums as well
+    HIP_TRY(c, vct_launch_dynamic_merge(a, cur(c).stream.get(), d.pass_emis ? d.acc_emis.get() : nullptr));
     return VCT_OK;
 }
 
@@ -100,8 +102,10 @@ int vct_dynamic_voxelize(vct_ctx* c) {
     if (d.pending) PIPE_TRY(launch_merge(c, true));      // a pass that was never resolved: accumulators and table back to empty
     HIP_TRY(c, d.vox_timer.begin(s, c->time_traces));
     HIP_TRY(c, hipMemsetAsync(d.words.get(), 0, 4 * sizeof(uint32_t), s));      // need, fragments, skipped, big triangles
-    HIP_TRY(c, vct_launch_dynamic_voxelize(dyn_vox_params(c, d), dyn_args(c, d), false, s));
+    const VctDynEmisArgs ea = {d.emission.get(), d.acc_emis.get()};
+    HIP_TRY(c, vct_launch_dynamic_voxelize(dyn_vox_params(c, d), dyn_args(c, d), false, s, d.emission ? &ea : nullptr));
     HIP_TRY(c, d.vox_timer.end(s));
+    d.pass_emis = (bool)d.emission;       // the pass carries the table it was voxelized under
     d.pending = true;
     return VCT_OK;
 }
@@ -141,6 +145,7 @@ int vct_set_dynamic_mesh(vct_ctx* c, const float* pos, const int32_t* material, 
         none.keep_draw_state(c->dyn);         // vct_set_dynamic_draw is context state: it outlives the mesh
         none.keep_bounce_state(c->dyn);       // and so is vct_set_dynamic_bounce
         c->dyn = std::move(none);
+        vct_emission_planes_release(c);       // the emission table went with the mesh
         return VCT_OK;
     }
     if (const char* why = vct_dynamic_check_args(pos, material, ntri, albedo, nmat, max_bricks))
@@ -202,6 +207,7 @@ int vct_set_dynamic_mesh(vct_ctx* c, const float* pos, const int32_t* material, 
     if (d.draw_flags) PIPE_TRY(draw_prepare(c, d, s));      // drawn: the draw copy and the frames of these positions
     HIP_TRY(c, hipStreamSynchronize(s));        // the caller's arrays are free again
     c->dyn = std::move(d);
+    vct_emission_planes_release(c);             // a replaced mesh's emission table went with it
     return VCT_OK;
 }
 
@@ -251,6 +257,62 @@ int vct_set_dynamic_bounce(vct_ctx* c, int32_t on) {
 int vct_get_dynamic_bounce(vct_ctx* c, int32_t* on) {
     if (!c || !on) return VCT_ERR_INVALID;
     *on = c->dyn.bounce_on;
+    return VCT_OK;
+}
+
+int vct_set_dynamic_emission(vct_ctx* c, const float* emission) {
+    if (!c) return VCT_ERR_INVALID;
+    VctDynamic& d = c->dyn;
+    size_t bad = 0;
+    const char* why = nullptr;
+    const int verdict = vct_dynamic_check_emission(d.attached(), emission, d.nmat, &bad, &why);
+    if (verdict == VCT_EMISSION_BAD) {
+        if (bad == (size_t)-1) return vct_fail(c, VCT_ERR_INVALID, std::string("vct_set_dynamic_emission: ") + why);
+        char msg[160];
+        snprintf(msg, sizeof msg, "vct_set_dynamic_emission: channel %zu of material %zu (%g) is not finite or below 0",
+                 bad % 3, bad / 3, (double)emission[bad]);
+        return vct_fail(c, VCT_ERR_INVALID, msg);
+    }
+    if (verdict == VCT_EMISSION_OK) PIPE_TRY(vct_refuse_conflict(c, "vct_set_dynamic_emission", VCT_FEAT_EMISSION, vct_rules_in_force(c).modes));
+    HIP_TRY(c, hipSetDevice(c->device));
+    PIPE_TRY(vct_synchronize(c));         // a pass in flight may read the table and add to the sums
+    if (verdict == VCT_EMISSION_ZERO) {   // NULL or all zero: detached -- a pending pass resolves without emission
+        d.emission.reset();
+        d.acc_emis.reset();
+        d.pass_emis = false;
+        vct_emission_planes_release(c);
+        return VCT_OK;
+    }
+    // all or nothing: the table and (for a first table) the zeroed sums in locals, planes only for slots that have none.
+    // A replaced table keeps the sums: a pending pass resolves with the table it was voxelized under.
+    const VctDynamicEmissionSizes z = vct_dynamic_emission_sizes(d.nmat, d.max_bricks);
+    if (!z.ok) return vct_fail(c, VCT_ERR_INVALID, "vct_set_dynamic_emission: buffer sizes overflow");
+    std::vector<float> padded((size_t)d.nmat * 4);
+    vct_emission_pad(emission, d.nmat, padded.data());
+    VctBuf<float> table;
+    VctBuf<unsigned long long> sums;
+    hipError_t e = table.alloc(padded.size());
+    if (e == hipSuccess) e = hipMemcpy(table.get(), padded.data(), z.table, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !d.acc_emis) {
+        e = sums.alloc((size_t)d.max_bricks * 1024);
+        if (e == hipSuccess) e = hipMemsetAsync(sums.get(), 0, z.sums, cur(c).stream.get());      // (vct_planes_attach waits for the stream)
+    }
+    PIPE_TRY(vct_planes_attach(c, "vct_set_dynamic_emission", vct_emission_planes, vct_emission_planes_drop, e));
+    if (!d.acc_emis) { d.acc_emis = std::move(sums); d.pass_emis = false; }      // attached behind a vct_voxelize: that pass has none
+    d.emission = std::move(table);
+    return VCT_OK;
+}
+
+int vct_get_dynamic_emission(vct_ctx* c, float* emission, int32_t* nmat) {
+    if (!c || !nmat) return VCT_ERR_INVALID;
+    const VctDynamic& d = c->dyn;
+    *nmat = d.emission ? d.nmat : 0;
+    if (!d.emission || !emission) return VCT_OK;
+    std::vector<float> padded((size_t)d.nmat * 4);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpy(padded.data(), d.emission.get(), padded.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (int32_t m = 0; m < d.nmat; ++m)
+        for (int k = 0; k < 3; ++k) emission[(size_t)m * 3 + k] = padded[(size_t)m * 4 + k];
     return VCT_OK;
 }
 

@@ -10,6 +10,11 @@ void vct_emission_detach(vct_ctx* c) {
     c->vox.emis_pool.reset();
     c->vox.emis_dirty = true;
     c->vox.pass_emis = false;
+    vct_emission_planes_release(c);
+}
+
+void vct_emission_planes_release(vct_ctx* c) {
+    if (vct_emission_table_attached(c)) return;      // the other table still writes them
     for (VctFrameSlot& sl : c->slots)
         if (!sl.emis_user) sl.emis.reset();
 }
@@ -17,7 +22,7 @@ void vct_emission_detach(vct_ctx* c) {
 hipError_t vct_emission_planes(const vct_ctx* c, VctFrameSlot& s, bool* fresh) {
     return vct_planes_ensure(s.emis, vct_emis_tiled_floats(c), s.stream.get(), fresh);
 }
-static void emission_planes_drop(VctFrameSlot& s) { s.emis.reset(); }
+void vct_emission_planes_drop(VctFrameSlot& s) { s.emis.reset(); }
 
 extern "C" {
 
@@ -49,7 +54,7 @@ int vct_upload_emission(vct_ctx* c, const float* emission) {
     hipError_t e = table.alloc(padded.size());
     if (e == hipSuccess) e = hipMemcpy(table.get(), padded.data(), padded.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess && !c->vox.emis_pool) e = pool.alloc((size_t)(c->vox.nslots ? c->vox.nslots : 1u) * 512);
-    PIPE_TRY(vct_planes_attach(c, "vct_upload_emission", vct_emission_planes, emission_planes_drop, e));
+    PIPE_TRY(vct_planes_attach(c, "vct_upload_emission", vct_emission_planes, vct_emission_planes_drop, e));
     c->mesh.mat_emission = std::move(table);
     if (pool) c->vox.emis_pool = std::move(pool);
     c->vox.emis_dirty = true;       // the next north-star pass rebuilds the pool from this table
@@ -63,7 +68,7 @@ int vct_set_pixel_emission(vct_ctx* c, const float* planes, int32_t layout, int3
     if (!planes) {       // detach the caller's planes; with material emission the slot keeps planes, zeroed until the next G-buffer pass
         s.emis_user = false;
         if (!s.emis) return VCT_OK;
-        if (c->mesh.mat_emission) {
+        if (vct_emission_table_attached(c)) {
             HIP_TRY(c, hipMemsetAsync(s.emis.get(), 0, vct_emis_tiled_floats(c) * sizeof(float), s.stream.get()));
         } else {
             HIP_TRY(c, hipStreamSynchronize(s.stream.get()));      // a trace in flight may still read them

@@ -204,6 +204,13 @@ int vct_render_gbuffer_rows_on(vct_ctx* c, const float view_proj[16], int32_t ro
         ds.pos = da.pos; ds.nrm = da.nrm; ds.tan = da.tan; ds.bit = da.bit;
         ds.material = da.material; ds.albedo = da.albedo;
         for (int k = 0; k < 3; ++k) ds.specular[k] = c->dyn.draw_specular[k];
+        ds.emission = c->dyn.emission.get();
+    }
+    // only the dynamic table is attached and this pass does not draw the dynamic mesh: no kernel writes the planes, and
+    // the rows may hold an earlier pass's dynamic pixels -- they show the static table's values, which are 0
+    if (e == hipSuccess && !draw_dyn && c->dyn.emission && !a.emission && cur(c).emis && row1 > row0) {
+        const size_t per_row = (size_t)vct_tiles_x(c) * VCT_EMIS_NPLANES * VCT_TILE_PIX;
+        e = hipMemsetAsync(cur(c).emis.get() + (size_t)row0 * per_row, 0, (size_t)(row1 - row0) * per_row * sizeof(float), s);
     }
     if (e == hipSuccess)
         e = vct_launch_gbuffer_shade(a, view_proj, c->cfg.width, c->cfg.height, row0, row1, c->shadow.words.get(), c->shadow.ebase,

@@ -60,7 +60,7 @@ hipError_t slot_create(vct_ctx* c, VctFrameSlot& s, hipStream_t stream) {
     if (e == hipSuccess && aov_halves) e = s.aov.alloc(aov_halves);
     if (e == hipSuccess && aov_halves) e = hipMemsetAsync(s.aov.get(), 0, aov_halves * 2, stream);
     if (e == hipSuccess && c->diffuse_rate == 2) e = s.alloc_half_rate(c->cfg.width, c->cfg.height);
-    if (e == hipSuccess && c->mesh.mat_emission) e = vct_emission_planes(c, s);      // material emission is attached: every slot has planes
+    if (e == hipSuccess && vct_emission_table_attached(c)) e = vct_emission_planes(c, s);      // material emission is attached (either mesh's): every slot has planes
     if (e == hipSuccess && c->gloss.n) e = vct_gloss_plane(c, s);      // gloss classes are attached: every slot has a plane
     if (e == hipSuccess && c->lights.n) e = vct_lights_planes(c, s);      // local lights are attached: every slot has lit planes
     s.gb_current = s.gb_tiled.get();

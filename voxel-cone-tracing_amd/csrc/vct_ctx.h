@@ -478,6 +478,12 @@ struct VctDynamic {
     // out of for capacity keeps it true and shows zero used slots on the device.
     int32_t bounce_on = 0;
     bool in_chain = false;
+    // Emission of the mesh's materials (vct_set_dynamic_emission): the table and the emission sums beside `acc`, both or
+    // neither.  They belong to the mesh: a fresh layer (attach, replace, detach) has none.  pass_emis: the pending pass
+    // was voxelized with the table, so its merge -- or its discard -- takes the EMIS form and leaves the sums zero.
+    VctBuf<float> emission;             // [nmat][4] (rgb, 0)
+    VctBuf<unsigned long long> acc_emis;   // [max_bricks][512][2]
+    bool pass_emis = false;
 
     bool attached() const { return ntri > 0; }
     bool drawn(int32_t flag) const { return attached() && (draw_flags & flag) && draw_pos; }
@@ -618,9 +624,14 @@ void vct_fill_march_params(const vct_ctx* c, VctTraceParams& p, const uint32_t* 
 // asynchronous, on the slot's stream.  row_stride > 1: only every row_stride-th tile row from row0 on; pack_rows: those rows back to back in out_base (interleaved slabs)
 int vct_launch_trace_rows(vct_ctx* c, int row0, int row1, uint16_t* out_base = nullptr, int row_stride = 1, bool pack_rows = false);
 // vct_api_emission.hip: drops the material emission table, its pool and the planes it attached (a new mesh, a NULL or all-zero
-// table); zeroed pixel-emission planes for a slot that has none (vct_planes_ensure)
+// table); zeroed pixel-emission planes for a slot that has none (vct_planes_ensure).  The planes live while EITHER table
+// is attached -- the static mesh's or the dynamic mesh's: vct_emission_table_attached; vct_emission_planes_release drops
+// them once neither is (the caller's own planes stay), called by whoever has just dropped a table.
 void vct_emission_detach(vct_ctx* c);
+inline bool vct_emission_table_attached(const vct_ctx* c) { return c->mesh.mat_emission || c->dyn.emission; }
+void vct_emission_planes_release(vct_ctx* c);
 hipError_t vct_emission_planes(const vct_ctx* c, VctFrameSlot& s, bool* fresh = nullptr);
+void vct_emission_planes_drop(VctFrameSlot& s);      // ... and takes them away again (the VctPlanesDrop of vct_planes_attach)
 // vct_api_gloss.hip: a zeroed pixel-gloss plane for a slot that has none; drops the material map (a new mesh)
 hipError_t vct_gloss_plane(const vct_ctx* c, VctFrameSlot& s, bool* fresh = nullptr);
 void vct_material_gloss_detach(vct_ctx* c);

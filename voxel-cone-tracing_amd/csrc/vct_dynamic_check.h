@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "../../include/vct.h"
+#include "vct_emission_check.h"
 
 #define VCT_DYNAMIC_MIN_BRICKS 64
 
@@ -67,6 +68,36 @@ static inline size_t vct_dynamic_bounce_map_bytes(int32_t V) {
 static inline uint32_t vct_dynamic_bounce_list_slots(uint32_t static_slots, uint32_t max_bricks) {
     const uint64_t n = (uint64_t)static_slots + (uint64_t)max_bricks;
     return n > 0xffffffffull ? 0xffffffffu : (uint32_t)n;
+}
+
+// What vct_set_dynamic_emission does with a table [nmat][3] for the attached mesh: VCT_EMISSION_OK attaches it,
+// VCT_EMISSION_ZERO (null, or every value zero) detaches, VCT_EMISSION_BAD refuses -- *why says what is wrong, and for a
+// value that is NaN, infinite or below 0 *bad_index is its index (material = index / 3, channel = index % 3), else
+// (size_t)-1.  The table check itself is vct_upload_emission's (vct_emission_check.h).
+static inline int vct_dynamic_check_emission(bool attached, const float* emission, int32_t nmat, size_t* bad_index, const char** why) {
+    *bad_index = (size_t)-1;
+    *why = nullptr;
+    if (!attached || nmat < 1) { *why = "no dynamic mesh attached"; return VCT_EMISSION_BAD; }
+    if (!emission) return VCT_EMISSION_ZERO;
+    const int verdict = vct_emission_check(emission, nmat, bad_index);
+    if (verdict == VCT_EMISSION_BAD) *why = "a value is not finite or below 0";
+    return verdict;
+}
+
+// Byte counts of what the table adds to the layer: the padded table [nmat][4] fp32 and the emission sums
+// [slots][512][2] uint64 -- 8 KiB per brick slot.  ok == false: a count does not fit size_t (nothing is allocated).
+struct VctDynamicEmissionSizes {
+    bool ok;
+    size_t table, sums;
+};
+static inline VctDynamicEmissionSizes vct_dynamic_emission_sizes(int32_t nmat, uint32_t slots) {
+    VctDynamicEmissionSizes s = {};
+    if (nmat < 1) return s;
+    bool ok = !__builtin_mul_overflow((size_t)nmat, 4 * sizeof(float), &s.table);
+    ok = ok && !__builtin_mul_overflow((size_t)slots, (size_t)512 * 2 * sizeof(uint64_t), &s.sums);
+    s.ok = ok;
+    if (!ok) { const VctDynamicEmissionSizes none = {}; return none; }
+    return s;
 }
 
 // Brick slots of the dynamic layer.  asked > 0: as asked; asked == 0: twice the bricks the attached positions touch, at

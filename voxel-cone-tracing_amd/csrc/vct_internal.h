@@ -528,6 +528,7 @@ struct VctDynShadeArgs {
     const int32_t* material;     // [ntri]
     const float* albedo;         // [nmat][4] (rgb used; the alpha plane is 1)
     float specular[3];           // the constant of vct_set_dynamic_draw
+    const float* emission;       // [nmat][4] the table of vct_set_dynamic_emission or null: dynamic pixels emit 0
 };
 hipError_t vct_launch_gbuffer_shade(const VctRasterArgs& a, const float view_proj[16], int W, int H, int row0, int row1,
                                     const uint32_t* shadow, uint32_t shadow_ebase, int shadow_size, const uint2* shadow_tiles,
@@ -628,7 +629,14 @@ struct VctDynArgs {
     unsigned long long* acc_attr;       // [max_bricks][512][3] or null (config.voxel_attributes)
 };
 // slots (claim) then fragments, small triangles by a thread each, big ones by a workgroup each; p: mesh, grid, shadow map
-hipError_t vct_launch_dynamic_voxelize(const VctVoxParams& p, const VctDynArgs& d, bool slots_only, hipStream_t s);
+// `emis` not null (vct_set_dynamic_emission): the EMIS instantiations of the fragment kernels, which also add every
+// fragment's unorm8(emission[material]) to the emission sums
+struct VctDynEmisArgs {
+    const float* emission;              // [nmat][4] (rgb, 0) of the dynamic mesh
+    unsigned long long* acc_emis;       // [max_bricks][512][2]: r | g << 32, b; all zero between passes
+};
+hipError_t vct_launch_dynamic_voxelize(const VctVoxParams& p, const VctDynArgs& d, bool slots_only, hipStream_t s,
+                                       const VctDynEmisArgs* emis = nullptr);
 struct VctDynMergeArgs {
     VctDynArgs d;
     uint32_t nbricks;
@@ -641,7 +649,8 @@ struct VctDynMergeArgs {
     uint32_t* level0;                   // [V^3] Morton
     uint32_t* brick_prev;               // [V^3 / 512]
 };
-hipError_t vct_launch_dynamic_merge(const VctDynMergeArgs& a, hipStream_t s);
+// acc_emis not null: the pass was voxelized with the emission table -- the EMIS instantiation resolves and re-zeroes the sums
+hipError_t vct_launch_dynamic_merge(const VctDynMergeArgs& a, hipStream_t s, unsigned long long* acc_emis = nullptr);
 // pooled [slot][512] of the resolved pass of statistics set `set` -> dense Morton volume (zero elsewhere)
 hipError_t vct_launch_dynamic_unpool(const uint32_t* pool, const uint32_t* res_brick, const uint32_t* words, int set,
                                      uint32_t max_bricks, uint32_t nbricks, uint32_t* dense, hipStream_t s);

@@ -1556,6 +1556,7 @@ struct DynShade {
     const int32_t* material;     // [ntri]
     const float* albedo;         // [nmat][4]
     float specular[3];
+    const float* emission;       // [nmat][4] the dynamic mesh's emission table (vct_set_dynamic_emission) or null: 0
 };
 template <bool DYN> struct ShadeArgs : ShadeParams {};
 template <> struct ShadeArgs<true> : ShadeParams { DynShade d; };
@@ -1690,7 +1691,8 @@ __device__ __forceinline__ float pcf_shadow(const uint32_t* __restrict__ words, 
 // DYN: the pass drew the dynamic mesh into a second visibility buffer.  A pixel reads both words and belongs to the
 // dynamic mesh where that word's depth is STRICTLY smaller -- at equal depth the static mesh wins, the order of the ids
 // of one mesh that is the static triangles followed by the dynamic ones -- and both words go back to "empty".  A dynamic
-// pixel selects the dynamic records (draw positions, face frames, material, table), has no textures, no emission and
+// pixel selects the dynamic records (draw positions, face frames, material, table), has no textures, the emission of the
+// dynamic table (0 without one; the planes are written when either table is attached, a null static table gives 0),
 // gloss class 0, alpha 1 and the constant specular colour; everything from the set-up on is the one code below.  The
 // select is per lane: a wave is one 8x8 tile, the divergence stays inside it.
 template <bool TEX, bool DYN>
@@ -1753,7 +1755,7 @@ k_gbuffer_shade(const ShadeArgs<DYN> p) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) sp_early[k] = p.specular[3 * (size_t)m_early + k];
         }
-        if (p.emis_tiled && !dyn) {       // (wave-uniform: a kernel argument) ... and its emission, with them
+        if (p.emis_tiled && !dyn && (!DYN || p.emission)) {       // (wave-uniform: kernel arguments) ... and its emission, with them
 #pragma unroll
             for (int k = 0; k < 3; ++k) em[k] = p.emission[4 * (size_t)m_early + k];
         }
@@ -1763,6 +1765,10 @@ k_gbuffer_shade(const ShadeArgs<DYN> p) {
                 alb_early[3] = 1.0f;
 #pragma unroll
                 for (int k = 0; k < 3; ++k) sp_early[k] = p.d.specular[k];
+                if (p.emis_tiled && p.d.emission) {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) em[k] = p.d.emission[4 * (size_t)m_early + k];
+                }
             }
         }
         // ... and, in a scene with textures, the material's three texture indices and the triangle's texture coordinates
@@ -2223,7 +2229,7 @@ hipError_t vct_launch_gbuffer_shade(const VctRasterArgs& a, const float view_pro
     for (int i = 0; i < 16; ++i) p.light_vp[i] = light_vp[i];
     p.tiled = tiled;
     p.emission = a.emission;
-    p.emis_tiled = a.emission ? emis_tiled : nullptr;
+    p.emis_tiled = a.emission || (dyn && dyn->emission) ? emis_tiled : nullptr;      // either table: the planes are written
     p.mat_gloss = a.mat_gloss;
     p.gloss_tiled = a.mat_gloss ? gloss_tiled : nullptr;
     p.tiles_x = (W + VCT_TILE - 1) / VCT_TILE;
@@ -2238,7 +2244,7 @@ hipError_t vct_launch_gbuffer_shade(const VctRasterArgs& a, const float view_pro
         static_cast<ShadeParams&>(q) = p;
         q.d.vis = dyn->vis;
         q.d.pos = dyn->pos; q.d.nrm = dyn->nrm; q.d.tan = dyn->tan; q.d.bit = dyn->bit;
-        q.d.material = dyn->material; q.d.albedo = dyn->albedo;
+        q.d.material = dyn->material; q.d.albedo = dyn->albedo; q.d.emission = dyn->emission;
         for (int k = 0; k < 3; ++k) q.d.specular[k] = dyn->specular[k];
         if (a.tex.texels) hipLaunchKernelGGL((k_gbuffer_shade<true, true>), grid, block, 0, s, q);
         else hipLaunchKernelGGL((k_gbuffer_shade<false, true>), grid, block, 0, s, q);

@@ -30,6 +30,8 @@
 //
 // Both modes share the triangle front end (load_world_tri, shadow_coords, dominant_axis), the material (material_colour,
 // load_material, interp_uv, quad_duv, frag_albedo) and the fragment value (shadow_factor, lit_rgb8): DESIGN.md 3.2.
+#include <type_traits>
+
 #include "vct_internal.h"
 
 namespace {
@@ -1010,15 +1012,41 @@ __device__ __forceinline__ void dyn_fragment(const VctVoxParams& p, const VctDyn
         atomicAdd(&d.acc_attr[3 * at + 2], (unsigned long long)q.nrm[1] | ((unsigned long long)q.nrm[2] << 32));
     }
 }
+// Emission of the dynamic mesh (vct_set_dynamic_emission).  Only the EMIS instantiations take the table and the sums: the
+// argument block of the others is VctDynArgs / VctDynMergeArgs as it was.  A triangle's emission is constant, so its
+// three bytes unorm8(emission[material] * 1.0f) -- the static emission pool's fragment value -- are formed once per
+// triangle; a fragment adds them to two words per voxel beside `acc` (r | g << 32, b; the count is acc's: 255 * 2^20
+// fragments stay below 2^32 per channel).  A zero half issues no atomic: adding 0 changes nothing, so a mover with one
+// glowing material pays for that material's fragments alone.
+struct DynEmisArgs : VctDynArgs { VctDynEmisArgs e; };
+struct DynEmisMergeArgs : VctDynMergeArgs { unsigned long long* acc_emis; };
+template <bool EMIS> using DynArgs = std::conditional_t<EMIS, DynEmisArgs, VctDynArgs>;
+template <bool EMIS> using DynMergeArgs = std::conditional_t<EMIS, DynEmisMergeArgs, VctDynMergeArgs>;
+struct DynEmisTri { unsigned long long rg, b; };
+__device__ __forceinline__ DynEmisTri dyn_emis_tri(const VctVoxParams& p, const VctDynEmisArgs& e, int t) {
+    const float* c = e.emission + 4 * (size_t)p.material[t];
+    const float em[3] = {c[0], c[1], c[2]};
+    const Rgb8 v = lit_rgb8(em, 1.0f);
+    return {(unsigned long long)v.r | ((unsigned long long)v.g << 32), (unsigned long long)v.b};
+}
+__device__ __forceinline__ void dyn_emis_fragment(const VctDynArgs& d, const VctDynEmisArgs& e, const DynEmisTri& q, int i, int j, int k) {
+    if (!(q.rg | q.b)) return;
+    const uint32_t vox = vct_morton3((uint32_t)i, (uint32_t)j, (uint32_t)k);
+    const uint32_t slot = d.brick_slot[vox >> 9];
+    if (slot >= d.max_bricks) return;       // (as dyn_fragment: never write outside the sums)
+    const size_t at = (size_t)slot * 512 + (vox & 511u);
+    if (q.rg) atomicAdd(&e.acc_emis[2 * at], q.rg);
+    if (q.b) atomicAdd(&e.acc_emis[2 * at + 1], q.b);
+}
 // one add per wave of the lanes' values to a counter word
 __device__ __forceinline__ void dyn_wave_add(uint32_t* word, uint32_t mine) {
     for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off);
     if ((threadIdx.x & 63) == 0 && mine) atomicAdd(word, mine);
 }
 
-template <bool FRAGS, bool ATTR>
+template <bool FRAGS, bool ATTR, bool EMIS = false>
 __global__ void __launch_bounds__(256)
-k_dyn_tris(const VctVoxParams p, const VctDynArgs d) {
+k_dyn_tris(const VctVoxParams p, const DynArgs<EMIS> d) {
     if (FRAGS && d.words[VCT_DYN_W_NEED] > d.max_bricks) return;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t nfrag = 0u, skipped = 0u;
@@ -1041,7 +1069,15 @@ k_dyn_tris(const VctVoxParams p, const VctDynArgs d) {
                 } else {
                     PassTri q;
                     dyn_pass_tri<ATTR>(p, t, r, q);
-                    for_each_overlap(r, [&](int i, int j, int k) { dyn_fragment<ATTR>(p, d, r, q, i, j, k); });
+                    if constexpr (EMIS) {
+                        const DynEmisTri qe = dyn_emis_tri(p, d.e, t);
+                        for_each_overlap(r, [&](int i, int j, int k) {
+                            dyn_fragment<ATTR>(p, d, r, q, i, j, k);
+                            dyn_emis_fragment(d, d.e, qe, i, j, k);
+                        });
+                    } else {
+                        for_each_overlap(r, [&](int i, int j, int k) { dyn_fragment<ATTR>(p, d, r, q, i, j, k); });
+                    }
                 }
             }
         }
@@ -1053,9 +1089,9 @@ k_dyn_tris(const VctVoxParams p, const VctDynArgs d) {
 }
 
 // the big triangles, a workgroup striding the box of each (as k_vox_plan_big): one huge triangle does not wait on a lane
-template <bool FRAGS, bool ATTR>
+template <bool FRAGS, bool ATTR, bool EMIS = false>
 __global__ void __launch_bounds__(256)
-k_dyn_big(const VctVoxParams p, const VctDynArgs d) {
+k_dyn_big(const VctVoxParams p, const DynArgs<EMIS> d) {
     if (FRAGS && d.words[VCT_DYN_W_NEED] > d.max_bricks) return;
     const int n_big = min((int)d.words[VCT_DYN_W_NBIG], p.ntri);
     for (int b = blockIdx.x; b < n_big; b += gridDim.x) {
@@ -1064,6 +1100,8 @@ k_dyn_big(const VctVoxParams p, const VctDynArgs d) {
         setup_tri(p, t, r);
         PassTri q;
         if (FRAGS) dyn_pass_tri<ATTR>(p, t, r, q);
+        DynEmisTri qe = {0ull, 0ull};
+        if constexpr (EMIS) qe = dyn_emis_tri(p, d.e, t);
         const int nx = r.hi[0] - r.lo[0] + 1, ny = r.hi[1] - r.lo[1] + 1, nz = r.hi[2] - r.lo[2] + 1;
         const long long cnt = (long long)nx * ny * nz;
         uint32_t nfrag = 0u;
@@ -1075,7 +1113,10 @@ k_dyn_big(const VctVoxParams p, const VctDynArgs d) {
             if (!FRAGS) {
                 ++nfrag;
                 dyn_claim(d, vct_morton3((uint32_t)i, (uint32_t)j, (uint32_t)k) >> 9);
-            } else dyn_fragment<ATTR>(p, d, r, q, i, j, k);
+            } else {
+                dyn_fragment<ATTR>(p, d, r, q, i, j, k);
+                if constexpr (EMIS) dyn_emis_fragment(d, d.e, qe, i, j, k);
+            }
         }
         if (!FRAGS) dyn_wave_add(&d.words[VCT_DYN_W_FRAGS], nfrag);
     }
@@ -1089,9 +1130,12 @@ k_dyn_big(const VctVoxParams p, const VctDynArgs d) {
 // pools and brick 0 in the resolved list: k_light_voxels, launched over every slot, finds no occupied voxel there.
 // A pass beyond the capacity added nothing to the accumulators; its table -- claimed entries without a slot among
 // them -- is swept.  discard: only the accumulators and the table, for a pass that is never resolved.
-template <bool ATTR>
+// EMIS (the pass was voxelized with an emission table): the texel is D' = D + DEm per byte with saturation, DEm the
+// rounded mean of the emission sums over acc's count; it goes to level 0 and to pool_rad alike, and the emission words
+// go back to zero wherever acc's do, in the discard form too.
+template <bool ATTR, bool EMIS = false>
 __global__ void __launch_bounds__(256)
-k_dyn_merge(const VctDynMergeArgs a) {
+k_dyn_merge(const DynMergeArgs<EMIS> a) {
     const int lane = threadIdx.x & 63;
     const uint32_t gtid = blockIdx.x * blockDim.x + threadIdx.x, nthreads = gridDim.x * blockDim.x;
     const uint32_t need = a.d.words[VCT_DYN_W_NEED];
@@ -1118,8 +1162,19 @@ k_dyn_merge(const VctDynMergeArgs a) {
             const ulonglong2 s = make_ulonglong2(g[0], g[1]);
             const uint32_t c = (uint32_t)(s.y >> 32);
             if (c) { g[0] = 0ull; g[1] = 0ull; }
+            uint32_t emis = 0u;
+            if constexpr (EMIS) {
+                if (c) {
+                    unsigned long long* ge = a.acc_emis + 2 * (pool + v);
+                    const unsigned long long e0 = ge[0], e1 = ge[1];
+                    if (e0 | e1) {
+                        ge[0] = 0ull; ge[1] = 0ull;
+                        emis = resolve_voxel(make_ulonglong2(e0, (e1 & 0xffffffffull) | ((unsigned long long)c << 32))) & 0x00ffffffu;
+                    }
+                }
+            }
             if (!a.discard) {
-                const uint32_t texel = resolve_voxel(s);
+                const uint32_t texel = EMIS ? add_sat_rgba8(resolve_voxel(s), emis) : resolve_voxel(s);
                 a.pool_rad[pool + v] = texel;
                 if (c) a.level0[(size_t)b * 512 + v] = texel;
             }
@@ -1263,7 +1318,8 @@ hipError_t vct_launch_voxelize(const VctVoxParams& p, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t vct_launch_dynamic_voxelize(const VctVoxParams& p, const VctDynArgs& d, bool slots_only, hipStream_t s) {
+hipError_t vct_launch_dynamic_voxelize(const VctVoxParams& p, const VctDynArgs& d, bool slots_only, hipStream_t s,
+                                       const VctDynEmisArgs* emis) {
     if (p.ntri <= 0) return hipSuccess;
     const dim3 grid((p.ntri + 255) / 256), big(capped_grid((size_t)p.ntri, 512)), block(256);
     const bool attr = d.acc_attr != nullptr;
@@ -1272,6 +1328,19 @@ hipError_t vct_launch_dynamic_voxelize(const VctVoxParams& p, const VctDynArgs& 
     hipLaunchKernelGGL((k_dyn_big<false, false>), big, block, 0, s, p, d);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || slots_only) return e;
+    if (emis) {
+        DynEmisArgs de;
+        static_cast<VctDynArgs&>(de) = d;
+        de.e = *emis;
+        if (attr) {
+            hipLaunchKernelGGL((k_dyn_tris<true, true, true>), grid, block, 0, s, p, de);
+            hipLaunchKernelGGL((k_dyn_big<true, true, true>), big, block, 0, s, p, de);
+        } else {
+            hipLaunchKernelGGL((k_dyn_tris<true, false, true>), grid, block, 0, s, p, de);
+            hipLaunchKernelGGL((k_dyn_big<true, false, true>), big, block, 0, s, p, de);
+        }
+        return hipGetLastError();
+    }
     if (attr) {
         hipLaunchKernelGGL((k_dyn_tris<true, true>), grid, block, 0, s, p, d);
         hipLaunchKernelGGL((k_dyn_big<true, true>), big, block, 0, s, p, d);
@@ -1282,8 +1351,16 @@ hipError_t vct_launch_dynamic_voxelize(const VctVoxParams& p, const VctDynArgs& 
     return hipGetLastError();
 }
 
-hipError_t vct_launch_dynamic_merge(const VctDynMergeArgs& a, hipStream_t s) {
+hipError_t vct_launch_dynamic_merge(const VctDynMergeArgs& a, hipStream_t s, unsigned long long* acc_emis) {
     const dim3 grid(capped_grid(((size_t)a.d.max_bricks + 3) / 4, 256 * 32)), block(256);      // one wave per slot
+    if (acc_emis) {
+        DynEmisMergeArgs ae;
+        static_cast<VctDynMergeArgs&>(ae) = a;
+        ae.acc_emis = acc_emis;
+        if (a.d.acc_attr) hipLaunchKernelGGL((k_dyn_merge<true, true>), grid, block, 0, s, ae);
+        else hipLaunchKernelGGL((k_dyn_merge<false, true>), grid, block, 0, s, ae);
+        return hipGetLastError();
+    }
     if (a.d.acc_attr) hipLaunchKernelGGL(k_dyn_merge<true>, grid, block, 0, s, a);
     else hipLaunchKernelGGL(k_dyn_merge<false>, grid, block, 0, s, a);
     return hipGetLastError();

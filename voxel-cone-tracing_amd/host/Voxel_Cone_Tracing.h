@@ -388,7 +388,26 @@ struct Voxel_Cone_Tracing {
                         int32_t max_bricks = 0) {
         if (!ctx) return false;
         if (!check(vct_set_dynamic_bounce(ctx, DynamicBounce ? 1 : 0), "vct_set_dynamic_bounce")) return false;
-        return check(vct_set_dynamic_mesh(ctx, pos, material, ntri, albedo, nmat, max_bricks), "vct_set_dynamic_mesh");
+        if (!check(vct_set_dynamic_mesh(ctx, pos, material, ntri, albedo, nmat, max_bricks), "vct_set_dynamic_mesh")) return false;
+        // the mesh dropped its emission table: the facade's goes back on if it still fits the materials, else it is forgotten
+        if (!pos || ntri == 0 || DynamicEmission.size() != (size_t)nmat * 3) DynamicEmission.clear();
+        dynamic_nmat = pos && ntri ? (size_t)nmat : 0;
+        if (DynamicEmission.empty()) return true;
+        return check(vct_set_dynamic_emission(ctx, DynamicEmission.data()), "vct_set_dynamic_emission");
+    }
+    // Emission of the dynamic mesh's materials (vct_set_dynamic_emission): fp32 RGB [materials][3], finite and >= 0; NULL
+    // detaches.  The object becomes a moving area light in the volume and, drawn (DrawDynamicMesh), is added to the pixels
+    // that see it.  Before SetDynamicMesh the table is kept for a mesh with as many materials; after it, it is handed over
+    // at once and shows from the next volume pass on.  Not with trace_variant 1 .. 4.
+    std::vector<float> DynamicEmission;              // [materials][3]
+    size_t dynamic_nmat = 0;
+    bool SetDynamicEmission(const float* table, size_t materials) {
+        if (!ctx) return false;
+        if (!table) DynamicEmission.clear();
+        else DynamicEmission.assign(table, table + materials * 3);
+        if (!dynamic_nmat) return true;              // no mesh yet: SetDynamicMesh hands it over
+        if (table && materials != dynamic_nmat) { DynamicEmission.clear(); return false; }
+        return check(vct_set_dynamic_emission(ctx, table ? DynamicEmission.data() : nullptr), "vct_set_dynamic_emission");
     }
     bool UpdateDynamicMesh(const float* pos, int32_t location = VCT_MEM_HOST) {
         if (!ctx) return false;

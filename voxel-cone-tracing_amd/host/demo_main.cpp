@@ -12,7 +12,8 @@
 //            [--gloss-classes TAN,SHIN[;TAN,SHIN...] --gloss MATERIAL=CLASS[;MATERIAL=CLASS...]]
 //            [--sky-gradient ZR,ZG,ZB;HR,HG,HB;GR,GG,GB[;UX,UY,UZ] | --sky-sh FILE] [--reimport]
 //            [--light X,Y,Z;R,G,B;RADIUS;SRC[;DX,DY,DZ;INNER_DEG;OUTER_DEG]]...
-//            [--dynamic-obj FILE --dynamic-path X0,Y0,Z0;X1,Y1,Z1 --dynamic-draw shadow|gbuffer|both --dynamic-bounce]
+//            [--dynamic-obj FILE --dynamic-path X0,Y0,Z0;X1,Y1,Z1 --dynamic-draw shadow|gbuffer|both --dynamic-bounce
+//             --dynamic-emission MATERIAL=R,G,B[;MATERIAL=R,G,B...]]
 // --dynamic-obj FILE: a second Wavefront OBJ as the context's dynamic mesh (Voxel_Cone_Tracing::SetDynamicMesh,
 //   vct_set_dynamic_mesh; flat material colours, its textures are not used), translated along the segment of
 //   --dynamic-path (model units, the OBJ's own; default: it stays where it is) over the run's frames.  Every Render()
@@ -23,6 +24,10 @@
 //   vct_last_dynamic_ms.  Not with --gpus; with --bounces 2 only together with --dynamic-bounce
 //   (Voxel_Cone_Tracing::DynamicBounce, vct_set_dynamic_bounce: the second bounce runs over the object's voxels too) --
 //   every frame then rebuilds the shadow map and the volume, second bounce included, before its Render().
+//   --dynamic-emission LIST: emission (fp32 RGB, finite, >= 0) of the listed materials of the dynamic OBJ, over whatever
+//   its MTL file's Ke gave them (Voxel_Cone_Tracing::SetDynamicEmission, vct_set_dynamic_emission): the object becomes a
+//   moving area light in the volume and, drawn with --dynamic-draw gbuffer|both, is added to the pixels that see it.
+//   Checked before a GPU is touched; without the option the Ke values alone are used.
 //
 // --light SPEC (repeatable, up to 64): a local light (Voxel_Cone_Tracing::SetLights, vct_set_lights) in world units: a point
 //   light at X,Y,Z of colour R,G,B (the factor at distance 1) that reaches RADIUS and whose inverse-square falloff is
@@ -170,6 +175,7 @@ int main(int argc, char** argv) {
     const char* dynamic_path = nullptr;
     const char* dynamic_draw = nullptr;
     bool dynamic_bounce = false;
+    const char* dynamic_emission = nullptr;
     int cubes[3] = {0, 0, 0};
     bool show_voxels = false;
     int view_source = VCT_VOXVIEW_CURRENT, view_level = 0;
@@ -223,6 +229,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--dynamic-obj")) dynamic_obj = argv[++i];
         else if (!strcmp(argv[i], "--dynamic-path")) dynamic_path = argv[++i];
         else if (!strcmp(argv[i], "--dynamic-draw")) dynamic_draw = argv[++i];
+        else if (!strcmp(argv[i], "--dynamic-emission")) dynamic_emission = argv[++i];
         else if (!strcmp(argv[i], "--ambient-cubes") && i + 2 < argc) {
             if (sscanf(argv[++i], "%d,%d,%d", &cubes[0], &cubes[1], &cubes[2]) != 3 || cubes[0] < 1 || cubes[1] < 1 || cubes[2] < 1 ||
                 (long long)cubes[0] * cubes[1] * cubes[2] * 6 > VCT_POINT_QUERY_MAX) {
@@ -271,6 +278,8 @@ int main(int argc, char** argv) {
         if (dyn_draw_flags < 0) { fprintf(stderr, "%s\n", VCT_DEMO_DYNAMIC_DRAW_USAGE); return 1; }
     }
     if (dynamic_bounce && !dynamic_obj) { fprintf(stderr, "--dynamic-bounce: needs --dynamic-obj\n"); return 1; }
+    if (dynamic_emission && !dynamic_obj) { fprintf(stderr, "--dynamic-emission: needs --dynamic-obj\n"); return 1; }
+    std::vector<float> dyn_emission;                        // [dyn_nmat][3]: the OBJ's Ke, then --dynamic-emission over it
     if (dynamic_obj) {
         if (gpus > 0 || (bounces >= 2 && !dynamic_bounce)) { fprintf(stderr, "--dynamic-obj: not with --gpus or --bounces 2\n"); return 1; }
         if (dynamic_path) {
@@ -296,7 +305,14 @@ int main(int argc, char** argv) {
         dyn_pos.resize((size_t)dyn_ntri * 9); dyn_albedo.resize((size_t)dyn_nmat * 4); dyn_material.resize((size_t)dyn_ntri);
         std::vector<float> unused_specular((size_t)dyn_nmat * 3);
         vcth_scene_get(obj, dyn_pos.data(), dyn_material.data(), dyn_albedo.data(), unused_specular.data());
+        dyn_emission.assign((size_t)dyn_nmat * 3, 0.0f);
+        vcth_scene_get_emission(obj, dyn_emission.data());
         vcth_scene_destroy(obj);
+        if (dynamic_emission)
+            if (const char* at = vct_demo_parse_dynamic_emission(dynamic_emission, dyn_nmat, dyn_emission)) {
+                fprintf(stderr, "%s; the OBJ has %d materials (at '%s')\n", VCT_DEMO_DYNAMIC_EMISSION_USAGE, (int)dyn_nmat, at);
+                return 1;
+            }
         dynamic_light = true;                               // a whole GI pass per frame: the volume follows the object
     }
     float sky_sh[9][3] = {};                                // --sky-gradient / --sky-sh: before a GPU is touched
@@ -416,6 +432,8 @@ int main(int argc, char** argv) {
                 dyn_frames[f][i] += dyn_path[0][i % 3] + t * (dyn_path[1][i % 3] - dyn_path[0][i % 3]);
         }
         if (!voxel_cone_tracing.SetDynamicMesh(dyn_frames[0].data(), dyn_material.data(), dyn_ntri, dyn_albedo.data(), dyn_nmat)) return 3;
+        // the OBJ's Ke with --dynamic-emission over it (an all-zero table attaches nothing)
+        if (!voxel_cone_tracing.SetDynamicEmission(dyn_emission.data(), (size_t)dyn_nmat)) return 3;
         if (dyn_draw_flags && !voxel_cone_tracing.DrawDynamicMesh((dyn_draw_flags & VCT_DYNAMIC_DRAW_SHADOW) != 0,
                                                                   (dyn_draw_flags & VCT_DYNAMIC_DRAW_GBUFFER) != 0)) return 3;
     }

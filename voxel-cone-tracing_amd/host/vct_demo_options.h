@@ -138,4 +138,24 @@ static inline int vct_demo_parse_dynamic_draw(const char* word) {
     return -1;
 }
 
+// --dynamic-emission MATERIAL=R,G,B[;MATERIAL=R,G,B...]: emission of the listed materials of the --dynamic-obj mesh, the
+// grammar of --emission, over `table` [nmat][3] (which holds the MTL file's Ke on entry).  Material indices below nmat,
+// values finite and >= 0 (the contract of vct_set_dynamic_emission).  Returns null or the offending place.
+#define VCT_DEMO_DYNAMIC_EMISSION_USAGE "--dynamic-emission MATERIAL=R,G,B[;...] (with --dynamic-obj): finite values >= 0, material indices of the dynamic OBJ"
+static inline const char* vct_demo_parse_dynamic_emission(const char* list, int nmat, std::vector<float>& table) {
+    if (!list || !*list) return list ? list : "";
+    for (const char* q = list; *q;) {
+        int m = -1, used = 0;
+        float v[3] = {0.0f, 0.0f, 0.0f};
+        if (sscanf(q, "%d=%f,%f,%f%n", &m, &v[0], &v[1], &v[2], &used) != 4 || m < 0 || m >= nmat) return q;
+        for (int k = 0; k < 3; ++k)
+            if (!(v[k] >= 0.0f) || isinf(v[k])) return q;
+        for (int k = 0; k < 3; ++k) table[(size_t)m * 3 + k] = v[k];
+        q += used;
+        if (*q == ';') { if (!q[1]) return q; ++q; }
+        else if (*q) return q;
+    }
+    return nullptr;
+}
+
 #endif

@@ -17,7 +17,12 @@ Object at A (OBJECT_TRIS triangles, palette of 3 colours with reds >= 0.6 and fo
     SAIL   a large triangle at y = 8 facing the light: > 4096 texels of the 128^2 shadow map (the camera sees its back)
     NEAR   one vertex behind the near plane: a quad, two fan sub-triangles
     BODY   a cloud of small triangles of either winding
-B is A moved by MOVE."""
+B is A moved by MOVE.
+
+The textured room (tests/test_gpu_dynamic_features.py): the same triangles with texture coordinates (room_uv), four small maps
+(room_textures: wall, an alpha-tested lace, a height map, floor) and their assignment (room_mat_tex) -- the lace on the
+occluder and on TIE opens holes through which the object shows, and hands the tied pixels TIE discards to DUP.  object_lights:
+eight local lights around the object (tests/test_gpu_dynamic_readers.py)."""
 import numpy as np
 
 import gbuffer_import_ref as gi
@@ -177,18 +182,81 @@ def concatenated(static, dyn, specular=SPECULAR, ms=MS, grid=G):
     return pos, mat, alb, spec, frames
 
 
-def mesh_of(oracle, m, ms=MS):
+def mesh_of(oracle, m, ms=MS, tex=None, mipmaps=False):
+    """tex: (uv [ntri, 6], mat_tex [nmat, 3], textures) of the whole mesh m (textured_cat), or None."""
     pos, mat, alb, spec, frames = m
-    return oracle.make_mesh(pos, mat, alb, spec, frames, model_scale=ms)
+    if tex is None:
+        return oracle.make_mesh(pos, mat, alb, spec, frames, model_scale=ms)
+    uv, mat_tex, textures = tex
+    assert uv.shape[0] == pos.shape[0] and mat_tex.shape[0] == alb.shape[0]
+    return oracle.make_mesh(pos, mat, alb, spec, frames, uv=uv, mat_tex=mat_tex, textures=textures, model_scale=ms,
+                            mipmaps=mipmaps)
 
 
-def reference(oracle, m, w, h, vp=None, lvp=None, S=SHADOW, ms=MS, with_shadow=True):
+def reference(oracle, m, w, h, vp=None, lvp=None, S=SHADOW, ms=MS, with_shadow=True, tex=None, mipmaps=False):
     """(depth [S, S], planes [23, h * w]) of mesh tuple m on the CPU checker, the planes under that depth."""
-    mesh = mesh_of(oracle, m, ms)
+    mesh = mesh_of(oracle, m, ms, tex, mipmaps)
     vp = camera(w, h) if vp is None else vp
     lvp = light_vp() if lvp is None else lvp
     depth = oracle.render_shadow_map(mesh, lvp, S)
     return depth, oracle.render_gbuffer(mesh, vp, w, h, depth if with_shadow else None, lvp)
+
+
+# ---- the textured room --------------------------------------------------------------------------------------------------------
+WALL_TEX, LACE_TEX, BUMP_TEX, FLOOR_TEX = 0, 1, 2, 3
+FLOOR_UV, WALL_UV, OCCLUDER_UV, TIE_UV = 12.0, 5.0, 1.5, 1.0
+
+
+def room_textures():
+    """Four power-of-two maps, uint8 [h, w, 4]: 16 x 8 (wall diffuse, TIE specular), the 8 x 8 lace (alpha 0 where
+    (i + j) % 3 == 0, else 255), a 4 x 4 height map, 16 x 16 (floor diffuse, wall specular).  Every red value is below 128,
+    so that owner_is_dynamic still tells the owner of a textured pixel."""
+    rng = np.random.default_rng(3)
+
+    def tex(h, w):
+        t = rng.integers(0, 256, (h, w, 4), dtype=np.uint8)
+        t[..., 0] >>= 1
+        t[..., 3] = 255
+        return t
+    wall, lace, bump, floor = tex(8, 16), tex(8, 8), tex(4, 4), tex(16, 16)
+    lace[..., 3] = np.where((np.add.outer(np.arange(8), np.arange(8)) % 3) == 0, 0, 255)
+    return [wall, lace, bump, floor]
+
+
+def room_uv():
+    """uv [9, 6] f32 of static_mesh's triangles: each quad (a, b, c, d) maps to (0, 0), (s, 0), (s, s), (0, s) with its UV
+    scale s, TIE to (0, 0), (1, 0), (0.5, 1); the LOW patch has none."""
+    def quad(s):
+        return [[0, 0, s, 0, s, s], [0, 0, s, s, 0, s]]
+    uv = quad(FLOOR_UV) + quad(WALL_UV) + quad(OCCLUDER_UV) + [[0, 0, TIE_UV, 0, 0.5 * TIE_UV, TIE_UV]] + quad(0.0)
+    return np.asarray(uv, f32)
+
+
+def room_mat_tex():
+    """mat_tex [9, 3] int32 (diffuse, specular, height) of static_mesh's materials, one per triangle."""
+    floor, wall = [FLOOR_TEX, -1, BUMP_TEX], [WALL_TEX, FLOOR_TEX, -1]
+    occ, tie, low = [LACE_TEX, -1, -1], [LACE_TEX, WALL_TEX, -1], [-1, -1, -1]
+    return np.asarray([floor, floor, wall, wall, occ, occ, tie, low, low], np.int32)
+
+
+def textured_cat(ndyn_tris=0, ndyn_mats=0):
+    """The `tex` argument of mesh_of / reference for the room followed by ndyn_tris dynamic triangles of ndyn_mats
+    materials: dynamic triangles get UV 0 and mat_tex -1 (the definition gives the dynamic mesh no textures)."""
+    uv = np.concatenate([room_uv(), np.zeros((ndyn_tris, 6), f32)])
+    mt = np.concatenate([room_mat_tex(), np.full((ndyn_mats, 3), -1, np.int32)])
+    return uv, mt, room_textures()
+
+
+def object_lights(n=8):
+    """lights_ref.many_lights(n) brought around the object: positions scaled to within +- 8 units of (1, 1, -6), between the
+    camera and the object; radii and colours as they are."""
+    import lights_ref
+    out = []
+    for light in lights_ref.many_lights(n):
+        moved = dict(light)
+        moved["position"] = tuple(float(c + 0.12 * p) for c, p in zip((1.0, 1.0, -6.0), light["position"]))
+        out.append(moved)
+    return out
 
 
 def boxes(pos, vp, w, h, ms=MS, rows=None):

@@ -83,3 +83,40 @@ def test_dense_16(oracle):
     assert occupied >= 3901 > v ** 3 // 8
     assert int(d.sum()) >= 55 and int(dc.bricks(d).sum()) == 8
     assert steps != wrong_steps and int(db.differing(want, wrong).sum()) >= 10
+
+
+# ---- the grids and march forms of tests/test_gpu_dynamic_features.py --------------------------------------------------------------
+@pytest.mark.parametrize("v, differ_min", [(8, 10), (16, 50), (128, 1000)])
+def test_other_grid_sizes(oracle, v, differ_min):
+    """dyncases' world at A on 8^3 / 16^3 / 128^3: 12 / 55 / 1,311 voxels tell whose attributes shade the layer, and the step
+    counts differ at all three sizes.  128^3 has 4,096 bricks: brick indices beyond 9 bits."""
+    p = oracle.default_params(v, G=dc.G)
+    S3, D3 = dc.layer(oracle, *dc.static_scene(), V=v), dc.layer(oracle, *dc.dynamic_mesh(dc.A), V=v)
+    want, steps = db.expected(oracle, D3, S3, p=p)
+    wrong, wrong_steps = db.static_attributes(oracle, D3, S3, p=p)
+    n = int(db.differing(want, wrong).sum())
+    print(v, n, steps, wrong_steps)
+    assert n >= differ_min and steps != wrong_steps
+    assert (v // 8) ** 3 > 512 or v < 64
+
+
+@pytest.mark.parametrize("wrap", [1, 0])
+@pytest.mark.parametrize("scene", ["world64", "dense16"])
+def test_max_alpha_097_shows_in_the_bounce(oracle, layers, scene, wrap):
+    """max_alpha 0.97 (1 - max_alpha < 2^-5: the IEEE-divide march): the bounce differs from the default constants' and
+    still tells whose attributes shade the layer, in both wrap forms."""
+    v = 64 if scene == "world64" else 16
+    if scene == "world64":
+        S3, D3 = layers["S"], layers["A"]
+    else:
+        S3, D3 = dc.layer(oracle, *db.dense16_static(), V=v), dc.layer(oracle, *dc.dynamic_mesh(dc.A), V=v)
+        assert int((dc.merge(D3[0], S3[0])[..., 3] > 0).sum()) > v ** 3 // 8
+    assert np.float32(1.0) - np.float32(0.97) < np.float32(2.0 ** -5)
+    p = oracle.default_params(v, G=dc.G, wrap_repeat=wrap, max_alpha=0.97)
+    want, steps = db.expected(oracle, D3, S3, p=p)
+    wrong, wrong_steps = db.static_attributes(oracle, D3, S3, p=p)
+    default, default_steps = db.expected(oracle, D3, S3, p=oracle.default_params(v, G=dc.G, wrap_repeat=wrap))
+    print(scene, wrap, steps, wrong_steps, int(db.differing(want, wrong).sum()), int(db.differing(want, default).sum()))
+    assert steps != wrong_steps and db.differing(want, wrong).sum() >= (300 if v == 64 else 10)
+    # few cones of the sparse world pass alpha 0.95: the limit shows in the step count and in a handful of voxels
+    assert steps > default_steps and db.differing(want, default).sum() >= 10

@@ -53,3 +53,25 @@ def test_big_triangles_are_not_degenerate_for_the_emission_rule(oracle):
     assert n["same_alpha"] and n["dynamic_voxels"] == 177219, n
     assert n["saturating"] >= 100000 and n["both"] >= 100000 and n["mixed_values"] >= 500, n
     assert (n["saturating"], n["both"], n["mixed_values"]) == (128025, 149506, 586), n
+
+
+# ---- the other grid sizes of tests/test_gpu_dynamic_features.py -----------------------------------------------------------------
+# v: ((D' != D) voxels, D + DEm saturates, the ONE table's D' differs from EM's) at A, the bounds the GPU tests assert
+GRID_FIGURES = {8: (10, 9, 9), 16: (40, 30, 36), 128: (917, 907, 485)}
+
+
+@pytest.mark.parametrize("v", sorted(GRID_FIGURES))
+def test_other_grid_sizes_are_not_degenerate_for_the_emission_rule(oracle, v):
+    """One brick (8^3), eight bricks (16^3) and 128^3: fewer voxels than at 64^3, still saturating ones and a table on one
+    material that shows.  At 128^3 the bounds of assert_non_degenerate hold as they stand."""
+    pos, mat, alb = dc.dynamic_mesh(dc.A)
+    D = dc.layer(oracle, pos, mat, alb, V=v)[0]
+    DEm, one = de.dem(oracle, pos, mat, V=v), de.dem(oracle, pos, mat, de.ONE, V=v)
+    assert D.shape == DEm.shape == (v, v, v, 4)
+    n = de.non_degeneracy(D, DEm)
+    Dp, Dq = de.add(D, DEm), de.add(D, one)
+    figures = (int((Dp != D).any(-1).sum()), n["saturating"], int((Dq != Dp).any(-1).sum()))
+    print(v, figures, n)
+    assert n["same_alpha"] and all(f >= lo for f, lo in zip(figures, GRID_FIGURES[v])), (figures, n)
+    if v == 128:
+        de.assert_non_degenerate(D, DEm)

@@ -41,6 +41,19 @@ Scratch builds, this file alone on each:
   * the detaching vct_set_dynamic_mesh without its vct_synchronize: every test passes.  The layer's buffers are released
     with hipFree, which waits for the device itself.  A guarantee, not an observable -- it would become one the day the
     buffers come from a pool.
+
+The dynamic mesh's three switches came after that: vct_set_dynamic_draw, vct_set_dynamic_emission, vct_set_dynamic_bounce.
+The draw copy with its face frames (k_dyn_draw_prepare), the shadow map's second raster scratch, the emission table with
+its sums and the bounce's brick table are shared by both slots.  CallList(features=True) -- it implies dynamic=True --
+draws dyn_draw(flags), dyn_emission(table | none), dyn_bounce(on) mostly with the stage they switch behind them, and reads
+back the shadow map (read_shadow) and the pixel-emission planes where the model says they exist: FEAT_SEEDS.  The model: a
+bounce is issued attached only while the switch is on (else the mesh is detached first, as before); every
+vct_set_dynamic_mesh -- attach, replace, detach -- drops the table and with it the planes no other owner holds; the table is
+set on an attached mesh only.  A trace variant is refused while planes are attached: no list sets one.  SEEDS and DYN_SEEDS
+generate, draw for draw, what they generated before (PARENT_LISTS holds both).  The directed order at the end of the file
+(positions rewritten behind the other slot's draw) is held against the CPU checker's map and planes as well.
+Times on an MI355X, one run of this file's dynamic tests: DYN_SEEDS 7 / 8 / 9 take 0.21 / 0.15 / 0.13 s, FEAT_SEEDS
+11 / 27 / 42 take 0.17 / 0.27 / 0.24 s -- each within 1.5 times the slowest of the former (0.32 s), so the lists keep ROUNDS.
 """
 
 import hashlib
@@ -51,6 +64,7 @@ import pytest
 
 import components_ref as cr
 import dyncases as dc
+import dynemiscases as de
 import gloss_ref as gr
 import lights_ref as lr
 import sky_ref as sr
@@ -77,9 +91,14 @@ SEEDS = [1, 2, 3, 4, 5, 6]
 DYN_SEEDS = [7, 8, 9]               # call lists that also draw the dynamic mesh's calls
 DYN_AT = [(0.0, 0.0, 200.0), (500.0, -300.0, 300.0), (-500.0, 200.0, -200.0)]      # where the moving object stands (model units)
 DYN_MESHES = 2                      # 0: dyncases' object of 150 triangles, 1: dyncases.crowd(), 200 k small ones
+FEAT_SEEDS = [11, 27, 42]           # call lists that also flip the dynamic mesh's draw, emission and bounce switches
+DYN_TABLES = [None, de.EM, de.ONE]  # vct_set_dynamic_emission: index 0 detaches (both meshes have dyncases' three materials)
+DYN_SPECULAR = (0.3, 0.6, 0.2)
 # BLAKE2b-128 of repr(call_list(seed)) for SEEDS as the commit before the dynamic calls gave them: what those seeds run stays
 PARENT_LISTS = {1: "7a660e04415f52dafde5dcadd80a686d", 2: "e2f07c84814d189d6ed765f376e623e9", 3: "04d01e65d68d5c8947e75e807342ae87",
                 4: "12652795f3b626c8e5a8a69b0e248c50", 5: "0cd29f76f51ef54a9a66068164995224", 6: "8a095071283f9869ad42359f63b4fac5"}
+# ... and of repr(call_list(seed, dynamic=True)) for DYN_SEEDS as the commit before the three switches gave them
+PARENT_LISTS.update({7: "22af0922d6cd95de84bb62137342ee69", 8: "fd5b1d4b0744b8e89b20d5c4fe4dd197", 9: "5a959b8cee900def11044516f65dfa9d"})
 
 
 @pytest.fixture(scope="module")
@@ -93,10 +112,14 @@ def vct():
 class CallList:
     """The calls of one run and the state they leave, as far as legality and defined read-backs need it."""
 
-    def __init__(self, rng, dynamic=False):
+    def __init__(self, rng, dynamic=False, features=False):
         self.rng, self.ops, self.slot = rng, [], 0
-        self.dynamic = dynamic              # draw the dynamic mesh's calls too (off: the lists of SEEDS, draw for draw)
+        self.features = features            # draw the dynamic mesh's three switches too (off: SEEDS and DYN_SEEDS, draw for draw)
+        self.dynamic = dynamic or features  # draw the dynamic mesh's calls too (off: the lists of SEEDS, draw for draw)
         self.dyn = None                     # the attached dynamic mesh (index), None: detached
+        self.dyn_draw_flags = 0             # vct_set_dynamic_draw: context state, outlives the mesh
+        self.dyn_bounce_on = False          # vct_set_dynamic_bounce: context state too
+        self.dyn_emis = 0                   # index into DYN_TABLES, 0: none; vct_set_dynamic_mesh drops the table
         self.lights = self.sky = self.gloss = 0              # index into LIGHT_SETS / SKIES / GLOSS_TABLES
         self.matgloss = self.emission = self.bounced = False
         self.pending = False                # a voxelize pass waits for its inject_light
@@ -171,6 +194,7 @@ class CallList:
         if mesh is None:
             mesh = self.pick(DYN_MESHES) if self.dyn is None else (self.dyn + 1) % DYN_MESHES
         self.dyn = mesh
+        self.dyn_emis = 0                   # vct_set_dynamic_mesh drops the emission table (and the planes it attached)
         self.add("dyn_attach", mesh, self.pick(len(DYN_AT)))
 
     def dyn_update(self):
@@ -180,6 +204,84 @@ class CallList:
     def dyn_detach(self):
         self.add("dyn_detach")
         self.dyn = None
+        self.dyn_emis = 0
+
+    # -- the three switches (CallList(features=True) only): the draw copy with its face frames, the shadow map's second
+    #    raster scratch, the emission table with its sums and the bounce's brick table are shared by both slots
+    def dyn_draw(self, flags=None):
+        if flags is None:
+            flags = (self.dyn_draw_flags + 1 + self.pick(3)) % 4
+        self.dyn_draw_flags = flags
+        self.add("dyn_draw", flags)
+
+    def dyn_emission(self):
+        assert self.dyn is not None         # refused with nothing attached
+        self.dyn_emis = (self.dyn_emis + 1 + self.pick(2)) % 3
+        self.add("dyn_emission", self.dyn_emis)
+
+    def dyn_bounce(self, on):
+        self.dyn_bounce_on = on
+        self.add("dyn_bounce", on)
+
+    def bounce(self):
+        """vct_bounce: refused between voxelize and inject_light, and with a dynamic mesh attached unless the switch is on."""
+        if self.pending:
+            self.inject()
+        if self.dyn is not None:
+            if self.features and (self.dyn_bounce_on or self.chance(0.6)):
+                if not self.dyn_bounce_on:
+                    self.dyn_bounce(True)
+            else:
+                self.dyn_detach()
+        self.add("bounce")
+        self.bounced = True
+        self.marched[self.slot] = True
+        if self.chance(0.5):
+            self.add("read_steps")
+
+    def feat_op(self):
+        """One of the three switches, at once behind whatever the other slot has in flight, mostly with the stage that reads
+        it behind it and a read-back of what that stage wrote."""
+        r = self.rng.random()
+        if self.dyn is None:
+            self.dyn_attach()
+        if r < 0.4:
+            self.dyn_draw()
+            r = self.rng.random()
+            if r < 0.35:
+                self.gi()
+            elif r < 0.85:
+                if r < 0.6:
+                    self.produce()          # the shadow map with (or without) the mover in it
+                self.gbuffer()
+                self.trace()
+            else:
+                return
+            what = self.pick(4)
+            if what == 0:
+                self.add("read_shadow")
+            elif what == 1:
+                self.add("read_gbuffer")
+            elif what == 2 and (self.emission or self.dyn_emis or self.emis_user[self.slot]):
+                self.add("read_pixel_emission")
+            else:
+                self.read_frame()
+        elif r < 0.75:
+            self.dyn_emission()
+            r = self.rng.random()
+            if r < 0.4:
+                self.revoxelize()
+            elif r < 0.7:
+                self.gi()
+            if self.chance(0.5):
+                self.read_dynamic()
+            elif self.dyn_emis:
+                self.add("read_pixel_emission")
+        else:
+            self.dyn_bounce(not self.dyn_bounce_on)
+            if self.dyn_bounce_on and self.chance(0.7):
+                self.bounce()
+                self.add("read_chain")
 
     def read_dynamic(self):
         assert self.dyn is not None         # the download is refused with nothing attached
@@ -270,15 +372,7 @@ class CallList:
         elif r == 8:
             self.add("apertures", self.pick(len(APERTURES)))
         elif r == 9:
-            if self.pending:
-                self.inject()              # a bounce is refused between voxelize and inject_light
-            if self.dyn is not None:
-                self.dyn_detach()          # ... and with a dynamic mesh attached
-            self.add("bounce")
-            self.bounced = True
-            self.marched[self.slot] = True
-            if self.chance(0.5):
-                self.add("read_steps")
+            self.bounce()
         elif r == 11:
             self.remesh()                  # buffers the other slot's kernels may still read are freed and re-allocated
         else:
@@ -326,7 +420,7 @@ class CallList:
             can.append("read_frame")
         if self.gb[s]:
             can.append("read_gbuffer")
-        if self.emission or self.emis_user[s]:
+        if self.emission or self.dyn_emis or self.emis_user[s]:
             can += ["read_pixel_emission"] * 3
         if self.gloss:
             can += ["read_pixel_gloss"] * 3
@@ -336,6 +430,8 @@ class CallList:
             can += ["read_aov"] * 3
         if self.dyn is not None:
             can += ["read_dynamic"] * 2
+        if self.features:
+            can += ["read_shadow"] * 2      # the one shadow map of the context: every list begins with a pass that renders it
         what = can[self.pick(len(can))]
         if what == "gather":
             self.add("gather", self.chance(0.5), self.chance(0.5))                  # device-located, sorted
@@ -359,8 +455,8 @@ class CallList:
             self.add(what)
 
 
-def call_list(seed, rounds=ROUNDS, dynamic=False):
-    m = CallList(np.random.default_rng(seed), dynamic)
+def call_list(seed, rounds=ROUNDS, dynamic=False, features=False):
+    m = CallList(np.random.default_rng(seed), dynamic, features)
     m.add("produce", 0)
     for r in (0, 1, 2, 4, 7):               # most runs begin with something attached: lights, a sky, gloss classes, emission, outputs
         if m.chance(0.6):
@@ -368,6 +464,11 @@ def call_list(seed, rounds=ROUNDS, dynamic=False):
     if m.dynamic and m.chance(0.7):
         m.dyn_attach()
         m.revoxelize()
+    if m.features:                          # most of these runs begin with the mover drawn
+        if m.chance(0.7):
+            m.dyn_draw(1 + m.pick(3))
+        if m.dyn is not None and m.chance(0.5):
+            m.dyn_emission()
     for _ in range(rounds):
         s0 = m.pick(2)
         m.switch(s0)
@@ -390,6 +491,8 @@ def call_list(seed, rounds=ROUNDS, dynamic=False):
         m.switch(1 - s0)
         if m.dynamic and m.chance(0.7):
             m.dyn_op()                     # the layer or the positions rewritten under the other slot's pass or frame
+        if m.features and m.chance(0.8):
+            m.feat_op()                    # a switch flipped, and the stage it switches, under the other slot's pass or frame
         m.setter()
         if m.chance(0.5):
             m.planes()
@@ -397,6 +500,8 @@ def call_list(seed, rounds=ROUNDS, dynamic=False):
         m.setter()
         if m.dynamic and m.chance(0.5):
             m.dyn_op()
+        if m.features and m.chance(0.5):
+            m.feat_op()
         if m.gb[m.slot] and m.chance(0.5):
             m.trace()                      # the resident G-buffer under the new state, at once
             m.reader()
@@ -530,6 +635,9 @@ def run(vct, inp, ops, sync):
                 c.voxelize()
             elif name == "inject":
                 c.inject_light(); c.build_mips()
+            elif name == "shadow":
+                c.set_light_direction(inp.dirs[op[1]])
+                c.render_shadow_map(sc.light_view_proj(inp.dirs[op[1]]))
             elif name == "gi":
                 c.set_light_direction(inp.dirs[op[1]]); c.set_camera_position(inp.cams[op[2]][0])
                 c.gi_pass(sc.light_view_proj(inp.dirs[op[1]]), inp.cams[op[2]][1])
@@ -641,6 +749,14 @@ def run(vct, inp, ops, sync):
                 c.set_dynamic_mesh(None)
             elif name == "read_dynamic":
                 record(k, op, c.dynamic_info(), *c.download_dynamic_voxels())
+            elif name == "dyn_draw":
+                c.set_dynamic_draw(op[1], DYN_SPECULAR)
+            elif name == "dyn_emission":
+                c.set_dynamic_emission(DYN_TABLES[op[1]])
+            elif name == "dyn_bounce":
+                c.set_dynamic_bounce(op[1])
+            elif name == "read_shadow":
+                record(k, op, c.download_shadow_map())
             else:
                 raise AssertionError(op)
             if sync:
@@ -678,6 +794,8 @@ def test_the_call_lists_reach_every_call():
         for op in ops:                      # ... a bounce only detached, an update and a layer download only attached
             attached = op[0] == "dyn_attach" or (attached and op[0] != "dyn_detach")
             assert not (op[0] == "bounce" and attached) and not (op[0] in ("dyn_update", "read_dynamic") and not attached), (seed, op)
+    for seed in FEAT_SEEDS:                 # ... and each of the lists with the switches the three setters and the map read-back
+        assert {op[0] for op in call_list(seed, features=True)} >= FEATURE_CALLS, seed
 
 
 def test_the_call_lists_of_the_earlier_seeds_are_what_they_were():
@@ -685,6 +803,70 @@ def test_the_call_lists_of_the_earlier_seeds_are_what_they_were():
     for seed in SEEDS:
         assert hashlib.blake2b(repr(call_list(seed)).encode(), digest_size=16).hexdigest() == PARENT_LISTS[seed], seed
         assert call_list(seed, dynamic=True) != call_list(seed)
+
+
+def test_the_call_lists_with_the_dynamic_mesh_are_what_they_were():
+    """The three switches sit behind CallList(features=True): without it DYN_SEEDS draw what they drew before."""
+    for seed in DYN_SEEDS:
+        ops = call_list(seed, dynamic=True)
+        assert hashlib.blake2b(repr(ops).encode(), digest_size=16).hexdigest() == PARENT_LISTS[seed], seed
+        assert call_list(seed, features=True) != ops
+        assert not {op[0] for op in ops} & FEATURE_CALLS
+
+
+FEATURE_CALLS = {"dyn_draw", "dyn_emission", "dyn_bounce", "read_shadow"}
+
+
+def test_the_call_lists_with_the_switches_reach_every_new_call_within_the_rules():
+    """Each list of FEAT_SEEDS issues the three setters, the four calls of the dynamic mesh, a bounce with the mesh attached,
+    G-buffer passes that draw the mover and read-backs of the shadow map and of planes the dynamic table attached; and the
+    model holds: a bounce attached only with the switch on, the table only on an attached mesh and gone with every
+    vct_set_dynamic_mesh, pixel emission read only where planes exist.  (No list sets a trace variant: the planes a table
+    attaches would refuse it.)"""
+    for seed in FEAT_SEEDS:
+        ops = call_list(seed, features=True)
+        names = {op[0] for op in ops}
+        assert names >= FEATURE_CALLS | {"dyn_attach", "dyn_update", "dyn_detach", "read_dynamic", "bounce", "read_pixel_emission"}, (seed, sorted(names))
+        assert "variant" not in names
+        attached = switch = pending = False
+        table = static_table = flags = slot = 0
+        user = [False, False]
+        bounces = drawn = table_reads = 0
+        for op in ops:
+            name = op[0]
+            if name == "switch":
+                slot = op[1]
+            elif name in ("dyn_attach", "dyn_detach"):
+                attached, table = name == "dyn_attach", 0
+            elif name == "dyn_bounce":
+                switch = op[1]
+            elif name == "dyn_draw":
+                flags = op[1]
+                assert 0 <= flags <= 3
+            elif name == "dyn_emission":
+                assert attached, (seed, op)
+                table = op[1]
+            elif name == "emission":
+                static_table = op[1]
+            elif name == "remesh":
+                static_table = False
+            elif name == "pixel_emission":
+                user[slot] = op[1] is not None
+            elif name == "voxelize":
+                pending = True
+            elif name in ("inject", "produce", "revoxelize", "gi"):
+                pending = False
+            elif name == "bounce":
+                assert not pending and (switch or not attached), (seed, op)
+                bounces += attached
+            elif name in ("dyn_update", "read_dynamic"):
+                assert attached, (seed, op)
+            elif name == "read_pixel_emission":
+                assert table or static_table or user[slot], (seed, op)
+                table_reads += bool(table) and not static_table and not user[slot]
+            if name in ("gbuffer", "gi") and attached and flags & 2:
+                drawn += 1
+        assert bounces >= 1 and drawn >= 3 and table_reads >= 1, (seed, bounces, drawn, table_reads)
 
 
 @pytest.mark.parametrize("seed", SEEDS)
@@ -701,6 +883,14 @@ def test_random_call_orders_with_the_dynamic_mesh(vct, inputs, seed):
     got, want = run(vct, inputs, ops, False), run(vct, inputs, ops, True)
     assert len(want) >= 2 * ROUNDS
     assert_same(got, want, ops, f"seed {seed}, dynamic mesh")
+
+
+@pytest.mark.parametrize("seed", FEAT_SEEDS)
+def test_random_call_orders_with_the_dynamic_switches(vct, inputs, seed):
+    ops = call_list(seed, features=True)
+    got, want = run(vct, inputs, ops, False), run(vct, inputs, ops, True)
+    assert len(want) >= 2 * ROUNDS
+    assert_same(got, want, ops, f"seed {seed}, dynamic mesh with its switches")
 
 
 # (writer on slot 0, what its effect is read back with): each leaves work on slot 0's stream or has just used the staging
@@ -905,3 +1095,49 @@ def test_layer_read_back_behind_the_other_slot_s_inject(vct, oracle, inputs):
     for at in (1, 2, 0, 1):
         ops += [("switch", 0), ("dyn_update", at, at == 1), ("voxelize", 0), ("inject",), ("switch", 1), ("read_dynamic",), ("read_chain",)]
     directed_dynamic(vct, oracle, inputs, ops, "inject, the layer read on the other slot", 3)
+
+
+# ---- the drawn dynamic mesh: a directed order, held against the CPU checker as well --------------------------------------------
+def test_positions_rewritten_behind_the_other_slot_s_draw(vct, oracle, inputs):
+    """Slot 0 renders the shadow map and the G-buffer with both draw flags on (k_dyn_draw_prepare copies the crowd's 200 k
+    triangles and forms their face frames; both raster passes read the copy); slot 1 at once issues
+    vct_update_dynamic_positions.  Slot 0's map and planes are those of the position they were drawn at; slot 1's next draw
+    shows the new one.  Both against the CPU checker's map and planes of the atrium followed by the crowd."""
+    import dyndrawcases as ddc
+    inp, sc = inputs, inputs.sc
+    m = inp.meshes[0]
+    static = (m.pos, m.material, m.albedo, m.specular, tuple(m.frames()))
+    static_mesh = ddc.mesh_of(oracle, static, 0.05)
+    mat, alb, at = inp.dyn[1]
+    lvp, vp = sc.light_view_proj(inp.dirs[0]), inp.cams[0][1]
+    want = {}
+
+    def settled(a):
+        with ThreadPoolExecutor(max_workers=4) as pool:
+            return [x.result() if hasattr(x, "result") else x for x in digests(pool, a)][1:]
+    depth_static = oracle.render_shadow_map(static_mesh, lvp, 512)
+    for k in range(len(DYN_AT)):
+        cat = ddc.concatenated(static, (at[k], mat, alb), specular=DYN_SPECULAR, ms=0.05, grid=150.0)
+        depth, planes = ddc.reference(oracle, cat, inp.w, inp.h, vp, lvp, S=512, ms=0.05)
+        shown = oracle.render_gbuffer(static_mesh, vp, inp.w, inp.h, depth, lvp)
+        assert (planes.view(np.uint32) != shown.view(np.uint32)).any(0).sum() >= 100_000, k      # the crowd fills much of the frame
+        assert (depth.view(np.uint32) != depth_static.view(np.uint32)).sum() >= 10_000, k
+        want[k] = (settled(depth), settled(planes))
+    assert len({repr(v) for v in want.values()}) == len(DYN_AT)
+    ops = [("produce", 0), ("dyn_attach", 1, 0), ("dyn_draw", 3), ("revoxelize",)]
+    for slot in (0, 1):
+        ops += [("switch", slot), ("gbuffer", 0), ("trace",)]
+    drawn_at, expect = 0, {}
+    for new, device in ((1, False), (2, True), (0, False), (2, True)):
+        ops += [("switch", 0), ("shadow", 0), ("gbuffer", 0), ("switch", 1), ("dyn_update", new, device), ("switch", 0)]
+        expect[len(ops)], expect[len(ops) + 1] = (0, drawn_at), (1, drawn_at)
+        ops += [("read_shadow",), ("read_gbuffer",), ("switch", 1), ("shadow", 0), ("gbuffer", 0)]
+        expect[len(ops)], expect[len(ops) + 1] = (0, new), (1, new)
+        ops += [("read_shadow",), ("read_gbuffer",)]
+        drawn_at = new
+    got, synced = run(vct, inp, ops, False), run(vct, inp, ops, True)
+    assert_same(got, synced, ops, "a draw, new positions on the other slot")
+    assert sorted(k for k, _, _ in synced) == sorted(expect)
+    for k, op, values in synced:
+        which, position = expect[k]
+        assert values[0][1:] == want[position][which], f"call {k} {op}: not the {('map', 'planes')[which]} of position {position}"

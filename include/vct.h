@@ -933,6 +933,50 @@ int vct_last_lights_ms(vct_ctx* ctx, float ms[2]);   /* [0] voxel kernel of the 
  * VCT_ERR_INVALID, the context keeping what it had: no dynamic mesh attached; a NaN, infinite or negative value (the
  * message names material and channel); the trace_variant conflict.  vct_get_dynamic_emission: the table as set and its
  * material count (*nmat = 0: none attached; emission may be NULL).
+ * Parts (vct_set_dynamic_parts; none by default): the attached dynamic mesh may carry part[ntri], one int32 per triangle
+ * in 0 .. nparts-1 with 1 <= nparts <= VCT_DYNAMIC_PARTS_MAX, and is then moved by one 3 x 4 matrix per part -- 48 bytes
+ * per part and frame instead of 36 per triangle.  Parts need not be contiguous in triangle order; a part may own no
+ * triangle.  All arithmetic below is fp32, multiplies and adds in the written order, nothing fused.
+ *   Rest       vct_set_dynamic_parts snapshots the layer's CURRENT positions as the REST positions: what the last
+ *              vct_set_dynamic_mesh, vct_update_dynamic_positions or vct_update_dynamic_transforms issued before it put
+ *              there -- a device-to-device copy on the selected slot's stream, ordered like a position update.  The
+ *              current positions are left as they are.
+ *   Transform  vct_update_dynamic_transforms(ctx, m, location) takes m[nparts][12], the top three rows of each part's
+ *              model matrix, row after row, in host or device memory (vct_mem).  For every vertex (x, y, z) of a rest
+ *              triangle of part k, with M = m[k], it writes into the layer's current positions, for r = 0, 1, 2,
+ *                p'_r = ((M[4r] * x + M[4r+1] * y) + M[4r+2] * z) + M[4r+3]
+ *              Everything downstream follows from these positions exactly as from a vct_update_dynamic_positions of
+ *              the same bits: the per-pass voxelization, the device-side vertex contract and its skipped count, the
+ *              draw copy and the face frames.
+ *   Matrices   ANY fp32 matrix is accepted -- NaN, infinities, singular, mirroring, huge scales: a device pointer cannot
+ *              be checked on the host, and the rule is the same for both locations.  Whatever the product gives goes
+ *              through the vertex contract on the device: a triangle with a coordinate outside it contributes nothing,
+ *              disturbs nothing and is counted.  A mirroring matrix flips the winding; the drawn stages then cull as
+ *              they would for the ONE static mesh of "Drawing".  An identity matrix reproduces the rest bits except
+ *              that -0 becomes +0 (1 * -0 + 0 * y is +0 when 0 * y is).
+ *   Positions  vct_update_dynamic_positions while parts are attached: the given positions become BOTH the rest and the
+ *              current positions -- a deforming mesh whose parts are then moved rigidly.  With no parts attached the
+ *              call does exactly what it did without this paragraph: the same copy, the same kernel.
+ *   Ownership  the parts belong to the mesh: vct_set_dynamic_mesh drops them on attach, replace and detach, as it
+ *              drops the emission table.  vct_set_dynamic_parts(ctx, NULL, 0) detaches: the current positions stay as
+ *              they are, the rest copy is freed.
+ *   Capacity   max_bricks == 0 at attach still counts the bricks of the positions handed to vct_set_dynamic_mesh; a
+ *              caller whose parts spread out passes max_bricks itself.  A pose beyond capacity leaves the layer out
+ *              and reports its need, as above.
+ * vct_set_dynamic_parts waits for work in flight and allocates everything -- the rest copy [ntri][9], the part indices, a
+ * 16-byte-aligned matrix table [nparts][12], a timer pair -- so that vct_update_dynamic_transforms allocates nothing,
+ * never waits for the stream and copies nothing to the host.  It is ordered like vct_update_dynamic_positions (the
+ * positions and the table are shared by both frame slots): it copies the matrices into the context's table on the
+ * selected slot's stream, then runs the kernel.  m needs 4-byte alignment only and must stay valid until the stream has
+ * passed the copy.  With no parts attached every kernel launched, and its argument block, is the one launched without
+ * this paragraph.  vct_get_dynamic_parts: the count (*nparts = 0: none) and, if part is not NULL, the indices as set.
+ * vct_download_dynamic_positions: the layer's current positions [ntri][9], with or without parts; waits for the stream.
+ * vct_last_dynamic_transform_ms: device time of the last transform kernel; needs vct_set_trace_timing on when the update
+ * was issued (VCT_ERR_INVALID otherwise and before any transform has run).
+ * VCT_ERR_INVALID, nothing touched: a NULL context; no dynamic mesh attached; nparts outside 1 ..
+ * VCT_DYNAMIC_PARTS_MAX, or a NULL part with nparts > 0; a part index outside 0 .. nparts-1 (the message names the
+ * triangle); vct_update_dynamic_transforms without parts attached, with NULL m, with an unknown location, or with m not
+ * 4-byte aligned.
  * Known limits: the drawn mesh has no textures, no gloss class and flat (per-face) normals.  With a flag off
  * the limit of the stage it names remains: vct_render_shadow_map / vct_render_gbuffer then draw the static mesh only and
  * every kernel launched is the one launched without this paragraph.  The voxel view's albedo / normal sources and
@@ -952,6 +996,12 @@ int vct_set_dynamic_bounce(vct_ctx* ctx, int32_t on);      /* 0 (default) or 1 *
 int vct_get_dynamic_bounce(vct_ctx* ctx, int32_t* on);
 int vct_set_dynamic_emission(vct_ctx* ctx, const float* emission /* [nmat][3] of the ATTACHED dynamic mesh */);
 int vct_get_dynamic_emission(vct_ctx* ctx, float* emission /* [nmat][3], may be NULL */, int32_t* nmat /* 0: none */);
+#define VCT_DYNAMIC_PARTS_MAX (1 << 16)
+int vct_set_dynamic_parts(vct_ctx* ctx, const int32_t* part /* [ntri], host */, int32_t nparts);
+int vct_get_dynamic_parts(vct_ctx* ctx, int32_t* nparts /* 0: none */, int32_t* part /* [ntri], may be NULL */);
+int vct_update_dynamic_transforms(vct_ctx* ctx, const float* m /* [nparts][12] */, int32_t location);
+int vct_download_dynamic_positions(vct_ctx* ctx, float* pos /* [ntri][9], host */);
+int vct_last_dynamic_transform_ms(vct_ctx* ctx, float* ms);
 
 /* ---- two frames in flight (round 6) -----------------------------------------------------------------
  * The reference's Render() (VCT.h:146-190) issues GL commands; the driver starts frame k + 1 while frame k

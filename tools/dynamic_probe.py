@@ -17,7 +17,10 @@ renderer has them -- and per mover, medians over ROUNDS rounds:
 The chain with the mover differs from the static one (asserted); the detached chain is bit for bit the first one (asserted).
 DETACHED_ONLY=1: only the static pass and the resident step, through entry points every earlier version of the library
 has -- run from a checkout of the parent commit and from this tree alternately (tools/dynamic_probe.sh does).
-Writes dynamic_probe.txt (or dynamic_probe_detached.txt) to $OUT (default: tool_out/)."""
+PARTS=1: only the routes that move the mover -- positions from host and from device memory against
+vct_update_dynamic_transforms with 1 and 64 parts (parts_probe below); a checkout of the parent commit runs the two positions
+routes.  Writes dynamic_probe.txt (or dynamic_probe_detached.txt, or with PARTS=1 $PARTS_FILE, default
+dynamic_parts_probe.txt) to $OUT (default: tool_out/)."""
 import os
 import sys
 import time
@@ -130,9 +133,113 @@ if DETACHED_ONLY:
         f.write(txt + "\n")
     sys.exit(0)
 
+NPOS = 8
+
+
+def parts_probe():
+    """PARTS=1: the routes that move the mover, alternating on one context -- positions from host memory (what a caller
+    without device-side transforms does), positions from device memory, and vct_update_dynamic_transforms with the mover as
+    1 part and as 64 parts (each a 64th of the triangles, the same translation).  Per route update + voxelize + inject +
+    mips as events, host time and wall time; the transform kernel's device time; with both draw flags on, the PARTS form of
+    the prepare kernel against k_dyn_transform followed by the plain prepare (events around the calls); and what NumPy
+    takes to move the vertices on the host.  A library without the entry point (the parent commit) runs the two positions
+    routes only.  Writes dynamic_parts_probe.txt."""
+    have = hasattr(ctx, "update_dynamic_transforms")
+    label = os.environ.get("LABEL", "this tree")
+    out = [f"dynamic_parts_probe ({label}): atrium {V}^3 ({scene.pos.shape[0]} static triangles), shadow map {S}^2, "
+           f"{ROUNDS} alternating rounds, medians (min max)"]
+
+    def bracket(call):
+        ctx.synchronize()
+        e = [ev(), ev()]
+        with torch.cuda.stream(st):
+            e[0].record()
+            call()
+            e[1].record()
+        ctx.synchronize()
+        return e[0].elapsed_time(e[1])
+    for n in SIDES:
+        tris = box(n, 6.0 / MS)
+        ntri = tris.shape[0]
+        mat = (np.arange(ntri) % 3).astype(np.int32)
+        alb = np.array([[0.9, 0.2, 0.2, 1.0], [0.2, 0.9, 0.2, 1.0], [0.2, 0.2, 0.9, 1.0]], np.float32)
+        path = [np.array([x, -9.0, 1.0]) / MS for x in np.linspace(-30.0, 30.0, NPOS)]
+        rest = np.ascontiguousarray(tris.reshape(-1, 9), np.float32)
+        host = [np.ascontiguousarray((tris + c[None, None, :]).reshape(-1, 9), np.float32) for c in path]
+        dev = [torch.from_numpy(a).cuda() for a in host]
+        torch.cuda.synchronize()
+        routes = ["host positions", "device positions"] + (["1 part", "64 parts"] if have else [])
+        t = {r: {k: [] for k in ("ev", "host", "wall", "kernel")} for r in routes}
+        extra = {k: [] for k in ("numpy", "parts_prepare", "transform_then_prepare", "parts_prepare_timer")}
+
+        def matrices(nparts, k):
+            m = np.zeros((nparts, 3, 4), np.float32)
+            m[:, 0, 0] = m[:, 1, 1] = m[:, 2, 2] = 1.0
+            m[:, :, 3] = path[k].astype(np.float32)
+            return m
+        ctx.set_dynamic_mesh(host[0], mat, alb)
+        for r in range(ROUNDS):
+            k = 2 + r % (NPOS - 2)
+            for route in routes:
+                if route == "host positions":
+                    ctx.update_dynamic_positions(rest)
+                    move = [lambda: ctx.update_dynamic_positions(host[1]), lambda: ctx.update_dynamic_positions(host[k])]
+                elif route == "device positions":
+                    move = [lambda: ctx.update_dynamic_positions(dev[1].data_ptr()), lambda: ctx.update_dynamic_positions(dev[k].data_ptr())]
+                else:
+                    nparts = 1 if route == "1 part" else 64
+                    ctx.update_dynamic_positions(rest)
+                    ctx.set_dynamic_parts((np.arange(ntri) * nparts // ntri).astype(np.int32), nparts)
+                    m1, mk = matrices(nparts, 1), matrices(nparts, k)
+                    move = [lambda: ctx.update_dynamic_transforms(m1), lambda: ctx.update_dynamic_transforms(mk)]
+                timed_pass(move[0])
+                a = timed_pass(move[1])
+                t[route]["ev"].append(a[0]); t[route]["host"].append(a[1]); t[route]["wall"].append(a[2])
+                info = ctx.dynamic_info()
+                assert not info["left_out"] and info["bricks_used"] > 0, info
+                if have and route.endswith(("part", "parts")):
+                    t[route]["kernel"].append(ctx.last_dynamic_transform_ms())
+                    if route == "64 parts":           # drawn: one launch against two
+                        ctx.set_dynamic_draw(3)
+                        bracket(lambda: ctx.update_dynamic_transforms(m1))
+                        extra["parts_prepare"].append(bracket(lambda: ctx.update_dynamic_transforms(mk)))
+                        extra["parts_prepare_timer"].append(ctx.last_dynamic_transform_ms())
+                        ctx.set_dynamic_draw(0)
+
+                        def two():
+                            ctx.update_dynamic_transforms(mk)
+                            ctx.set_dynamic_draw(3)
+                        bracket(two)
+                        ctx.set_dynamic_draw(0)
+                        extra["transform_then_prepare"].append(bracket(two))
+                        ctx.set_dynamic_draw(0)
+                    ctx.set_dynamic_parts(None)
+            t0 = time.perf_counter()
+            moved = np.ascontiguousarray((rest.reshape(-1, 3) + path[k].astype(np.float32)).reshape(-1, 9))
+            extra["numpy"].append((time.perf_counter() - t0) * 1e3)
+            assert moved.shape == rest.shape
+        ctx.set_dynamic_mesh(None)
+        out.append(f"mover of {ntri} triangles ({ntri * 36} bytes of positions, 48 or 3072 of matrices):")
+        for route in routes:
+            out.append(f"  {route:17s} update + pass: events {stats(t[route]['ev'])}   host {stats(t[route]['host'])}   "
+                       f"wall {stats(t[route]['wall'])}" + (f"   transform kernel {stats(t[route]['kernel'])}" if t[route]["kernel"] else ""))
+        if have:
+            out.append(f"  drawn, 64 parts: PARTS prepare alone, events around the call {stats(extra['parts_prepare'])} "
+                       f"(its own timer {stats(extra['parts_prepare_timer'])});   k_dyn_transform + plain prepare, events around "
+                       f"both calls {stats(extra['transform_then_prepare'])}")
+        out.append(f"  the host's own loop: NumPy adds one translation to {3 * ntri} vertices in {stats(extra['numpy'])}")
+        print("\n".join(out[-(len(routes) + 3):]), flush=True)
+    with open(os.path.join(out_dir, os.environ.get("PARTS_FILE", "dynamic_parts_probe.txt")), "w") as f:
+        f.write("\n".join(out) + "\n")
+
+
+if os.environ.get("PARTS", "0") == "1":
+    parts_probe()
+    ctx.close()
+    sys.exit(0)
+
 lines = [f"dynamic_probe: atrium {V}^3 ({scene.pos.shape[0]} static triangles), shadow map {S}^2, {ROUNDS} alternating rounds"]
 chain0 = ctx.download_chain()
-NPOS = 8
 for n in SIDES:
     tris = box(n, 6.0 / MS)
     ntri = tris.shape[0]

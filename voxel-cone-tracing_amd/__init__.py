@@ -83,6 +83,8 @@ ABI_SYMBOLS = [
     "vct_set_dynamic_mesh", "vct_update_dynamic_positions", "vct_get_dynamic", "vct_download_dynamic_voxels",
     "vct_last_dynamic_ms", "vct_set_dynamic_draw", "vct_get_dynamic_draw",
     "vct_set_dynamic_bounce", "vct_get_dynamic_bounce", "vct_set_dynamic_emission", "vct_get_dynamic_emission",
+    "vct_set_dynamic_parts", "vct_get_dynamic_parts", "vct_update_dynamic_transforms", "vct_download_dynamic_positions",
+    "vct_last_dynamic_transform_ms",
 ]
 
 
@@ -105,6 +107,7 @@ class GlossClass(C.Structure):
 LIGHTS_MAX = 64
 LIGHT_SPOT = 1
 DYNAMIC_DRAW_SHADOW, DYNAMIC_DRAW_GBUFFER = 1, 2      # vct_set_dynamic_draw
+DYNAMIC_PARTS_MAX = 1 << 16                           # VCT_DYNAMIC_PARTS_MAX (vct_set_dynamic_parts)
 
 
 class Light(C.Structure):
@@ -254,6 +257,11 @@ _lib.vct_set_dynamic_bounce.argtypes = [C.c_void_p, C.c_int32]
 _lib.vct_get_dynamic_bounce.argtypes = [C.c_void_p, C.c_void_p]
 _lib.vct_set_dynamic_emission.argtypes = [C.c_void_p, C.c_void_p]
 _lib.vct_get_dynamic_emission.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.vct_set_dynamic_parts.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+_lib.vct_get_dynamic_parts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.vct_update_dynamic_transforms.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+_lib.vct_download_dynamic_positions.argtypes = [C.c_void_p, C.c_void_p]
+_lib.vct_last_dynamic_transform_ms.argtypes = [C.c_void_p, C.c_void_p]
 _lib.vct_upload_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
 
 
@@ -665,7 +673,7 @@ class Context:
         following voxelize + inject_light (or gi_pass) voxelizes it and merges it into level 0: it wins per voxel."""
         if pos is None:
             self._ck(_lib.vct_set_dynamic_mesh(self._h, None, None, 0, None, 0, 0), "vct_set_dynamic_mesh")
-            self._dyn_ntri = self._dyn_nmat = 0
+            self._dyn_ntri = self._dyn_nmat = self._dyn_nparts = 0
             return
         pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 9)
         material = np.ascontiguousarray(material, np.int32).reshape(-1)
@@ -676,6 +684,7 @@ class Context:
                                            int(max_bricks)), "vct_set_dynamic_mesh")
         self._dyn_ntri = pos.shape[0]
         self._dyn_nmat = albedo.shape[0]
+        self._dyn_nparts = 0         # the parts went with the previous mesh
 
     def update_dynamic_positions(self, pos):
         """New positions of the attached dynamic mesh's triangles: a float32 array [ntri, 9] or an int device pointer to
@@ -764,6 +773,65 @@ class Context:
         out = np.zeros((n.value, 3), np.float32)
         self._ck(_lib.vct_get_dynamic_emission(self._h, _ptr(out), C.byref(n)), "vct_get_dynamic_emission")
         return out
+
+    def set_dynamic_parts(self, part, nparts=None):
+        """Splits the ATTACHED dynamic mesh into rigid parts: `part` is an int32 index per triangle in 0 .. nparts-1
+        (nparts None: the largest index + 1); the layer's current positions become the rest positions that
+        update_dynamic_transforms moves.  None detaches.  The mesh drops its parts on attach, replace and detach."""
+        if part is None:
+            self._ck(_lib.vct_set_dynamic_parts(self._h, None, 0), "vct_set_dynamic_parts")
+            self._dyn_nparts = 0
+            return
+        part = np.ascontiguousarray(part, np.int32)
+        ntri = getattr(self, "_dyn_ntri", 0)
+        if part.ndim != 1 or (ntri and part.shape[0] != ntri):
+            raise VctError(f"set_dynamic_parts: part indices of shape {tuple(part.shape)}, the attached dynamic mesh has "
+                           f"{ntri} triangles: [{ntri}] is expected")
+        if nparts is None:
+            nparts = int(part.max()) + 1 if part.size else 0
+        self._ck(_lib.vct_set_dynamic_parts(self._h, _ptr(part), int(nparts)), "vct_set_dynamic_parts")
+        self._dyn_nparts = int(nparts)
+
+    def dynamic_parts(self):
+        """(nparts, part int32 [ntri]) as set by set_dynamic_parts, or None while no parts are attached."""
+        n = C.c_int32(0)
+        self._ck(_lib.vct_get_dynamic_parts(self._h, C.byref(n), None), "vct_get_dynamic_parts")
+        if not n.value:
+            return None
+        part = np.zeros(self.dynamic_info()["ntri"], np.int32)
+        self._ck(_lib.vct_get_dynamic_parts(self._h, C.byref(n), _ptr(part)), "vct_get_dynamic_parts")
+        return int(n.value), part
+
+    def update_dynamic_transforms(self, m):
+        """One 3 x 4 model matrix per part of the attached dynamic mesh, rows first: a float32 array [nparts, 12] or
+        [nparts, 3, 4], or an int device pointer to as many floats.  The layer's positions become rest x matrix, on the
+        device; asynchronous on the selected slot's stream; the next voxelize uses them."""
+        if isinstance(m, int):
+            self._ck(_lib.vct_update_dynamic_transforms(self._h, _ptr(m), MEM_DEVICE), "vct_update_dynamic_transforms")
+            return
+        m = np.ascontiguousarray(m, np.float32)
+        nparts = getattr(self, "_dyn_nparts", 0)
+        if not ((m.ndim == 2 and m.shape[1] == 12) or (m.ndim == 3 and m.shape[1:] == (3, 4))) or (nparts and m.shape[0] != nparts):
+            raise VctError(f"update_dynamic_transforms: matrices of shape {tuple(m.shape)}, the attached mesh has {nparts} "
+                           f"parts: [{nparts}, 12] or [{nparts}, 3, 4] is expected")
+        self._dyn_m = m              # stays alive until the stream has passed the copy
+        self._ck(_lib.vct_update_dynamic_transforms(self._h, _ptr(m), MEM_HOST), "vct_update_dynamic_transforms")
+
+    def download_dynamic_positions(self):
+        """The dynamic layer's current positions, float32 [ntri, 9]: those of the last update_dynamic_positions or
+        update_dynamic_transforms.  Waits for the stream."""
+        ntri = self.dynamic_info()["ntri"]
+        if not ntri:
+            raise VctError("download_dynamic_positions: no dynamic mesh attached")
+        pos = np.zeros((ntri, 9), np.float32)
+        self._ck(_lib.vct_download_dynamic_positions(self._h, _ptr(pos)), "vct_download_dynamic_positions")
+        return pos
+
+    def last_dynamic_transform_ms(self):
+        """Device ms of the last update_dynamic_transforms' kernel; trace timing must have been on."""
+        v = C.c_float(0.0)
+        self._ck(_lib.vct_last_dynamic_transform_ms(self._h, C.byref(v)), "vct_last_dynamic_transform_ms")
+        return float(v.value)
 
     def upload_shadow_map(self, depth, light_vp_rowmajor):
         if depth is None:

@@ -74,6 +74,19 @@ int draw_prepare(vct_ctx* c, VctDynamic& d, hipStream_t s) {
     return VCT_OK;
 }
 
+// The layer's positions from its rest positions and the matrix table on stream s: k_dyn_transform, or -- drawn -- the PARTS
+// form of the prepare kernel, which goes on to the draw copy and the frames.  The draw arrays exist whenever a flag is on
+// and a mesh is attached (vct_set_dynamic_mesh, vct_set_dynamic_draw), so nothing is allocated here.
+int transform(vct_ctx* c, VctDynamic& d, hipStream_t s) {
+    const VctDynPartsArgs a = {d.rest.get(), d.part.get(), d.part_m.get(), d.pos.get()};
+    if (d.draw_flags && d.draw_pos)
+        HIP_TRY(c, vct_launch_dynamic_transform_prepare(a, d.ntri, c->cfg.model_scale, VCT_VERTEX_LIMIT_GRIDS * c->cfg.grid_world_size,
+                                                        d.draw_pos.get(), d.draw_nrm.get(), d.draw_tan.get(), d.draw_bit.get(), s));
+    else
+        HIP_TRY(c, vct_launch_dynamic_transform(a, d.ntri, s));
+    return VCT_OK;
+}
+
 // one pooled volume of the last resolved pass -> dense Morton -> linear staging -> host, synchronised
 int download_pool(vct_ctx* c, const uint32_t* pool, uint32_t* dense, uint8_t* dst) {
     const VctDynamic& d = c->dyn;
@@ -219,7 +232,102 @@ int vct_update_dynamic_positions(vct_ctx* c, const float* pos, int32_t location)
     PIPE_TRY(vct_pipeline_join(c));       // the buffer is shared: the other slot's pass may still read the previous positions
     HIP_TRY(c, hipMemcpyAsync(c->dyn.pos.get(), pos, (size_t)c->dyn.ntri * 9 * sizeof(float),
                               location == VCT_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, cur(c).stream.get()));
+    if (c->dyn.nparts)                    // parts attached: these positions are the new rest positions as well
+        HIP_TRY(c, hipMemcpyAsync(c->dyn.rest.get(), c->dyn.pos.get(), (size_t)c->dyn.ntri * 9 * sizeof(float),
+                                  hipMemcpyDeviceToDevice, cur(c).stream.get()));
     return vct_dynamic_draw_prepare(c);   // behind the copy, on its stream: ordered before every stage that draws the mesh
+}
+
+int vct_set_dynamic_parts(vct_ctx* c, const int32_t* part, int32_t nparts) {
+    if (!c) return VCT_ERR_INVALID;
+    VctDynamic& d = c->dyn;
+    const bool detach = !part && nparts == 0;
+    if (detach && !d.attached()) return vct_fail(c, VCT_ERR_INVALID, "vct_set_dynamic_parts: no dynamic mesh attached");
+    if (!detach) {
+        int32_t bad = -1;
+        if (const char* why = vct_dynamic_check_parts(d.attached(), part, d.ntri, nparts, &bad)) {
+            if (bad < 0) return vct_fail(c, VCT_ERR_INVALID, std::string("vct_set_dynamic_parts: ") + why);
+            char msg[160];
+            snprintf(msg, sizeof msg, "vct_set_dynamic_parts: part index %d of triangle %d is outside 0 .. %d", (int)part[bad],
+                     (int)bad, (int)nparts - 1);
+            return vct_fail(c, VCT_ERR_INVALID, msg);
+        }
+    }
+    if (detach && !d.nparts) return VCT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    PIPE_TRY(vct_synchronize(c));         // a transform in flight reads all three buffers
+    if (detach) {                         // the current positions stay as they are
+        d.drop_parts();
+        return VCT_OK;
+    }
+    // all or nothing: everything in locals; the context keeps what it had until the last call below has succeeded
+    const VctDynamicPartsSizes z = vct_dynamic_parts_sizes(d.ntri, nparts);
+    if (!z.ok) return vct_fail(c, VCT_ERR_INVALID, "vct_set_dynamic_parts: buffer sizes overflow");
+    hipStream_t s = cur(c).stream.get();
+    VctBuf<float> rest;
+    VctBuf<int32_t> idx;
+    VctBuf<float4> table;
+    VctTimer timer;
+    HIP_TRY(c, rest.alloc((size_t)d.ntri * 9));
+    HIP_TRY(c, idx.alloc((size_t)d.ntri));
+    HIP_TRY(c, table.alloc((size_t)nparts * 3));
+    HIP_TRY(c, timer.create());           // the events now, so that no update allocates
+    // the rest positions: what the last vct_set_dynamic_mesh or vct_update_dynamic_positions -- or transform -- put there
+    HIP_TRY(c, hipMemcpyAsync(rest.get(), d.pos.get(), z.rest, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(idx.get(), part, z.part, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemsetAsync(table.get(), 0, z.table, s));
+    HIP_TRY(c, hipStreamSynchronize(s));  // the caller's array is free again
+    d.rest = std::move(rest);
+    d.part = std::move(idx);
+    d.part_m = std::move(table);
+    d.xform_timer = std::move(timer);
+    d.nparts = nparts;
+    return VCT_OK;
+}
+
+int vct_get_dynamic_parts(vct_ctx* c, int32_t* nparts, int32_t* part) {
+    if (!c || !nparts) return VCT_ERR_INVALID;
+    const VctDynamic& d = c->dyn;
+    *nparts = d.nparts;
+    if (!d.nparts || !part) return VCT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpy(part, d.part.get(), (size_t)d.ntri * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return VCT_OK;
+}
+
+int vct_update_dynamic_transforms(vct_ctx* c, const float* m, int32_t location) {
+    if (!c) return VCT_ERR_INVALID;
+    VctDynamic& d = c->dyn;
+    if (const char* why = vct_dynamic_check_transforms(d.attached(), d.nparts, m, location))
+        return vct_fail(c, VCT_ERR_INVALID, std::string("vct_update_dynamic_transforms: ") + why);
+    HIP_TRY(c, hipSetDevice(c->device));
+    PIPE_TRY(vct_pipeline_join(c));       // positions and table are shared: the other slot's pass may still read the positions
+    hipStream_t s = cur(c).stream.get();
+    HIP_TRY(c, hipMemcpyAsync(d.part_m.get(), m, (size_t)d.nparts * 12 * sizeof(float),
+                              location == VCT_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    HIP_TRY(c, d.xform_timer.begin(s, c->time_traces));
+    PIPE_TRY(transform(c, d, s));
+    HIP_TRY(c, d.xform_timer.end(s));
+    return VCT_OK;
+}
+
+int vct_download_dynamic_positions(vct_ctx* c, float* pos) {
+    if (!c) return VCT_ERR_INVALID;
+    const VctDynamic& d = c->dyn;
+    if (!d.attached()) return vct_fail(c, VCT_ERR_INVALID, "vct_download_dynamic_positions: no dynamic mesh attached");
+    if (!pos) return vct_fail(c, VCT_ERR_INVALID, "vct_download_dynamic_positions: null positions");
+    HIP_TRY(c, hipSetDevice(c->device));
+    PIPE_TRY(vct_synchronize(c));         // the last update may have been issued on the other frame slot's stream
+    HIP_TRY(c, hipMemcpy(pos, d.pos.get(), (size_t)d.ntri * 9 * sizeof(float), hipMemcpyDeviceToHost));
+    return VCT_OK;
+}
+
+int vct_last_dynamic_transform_ms(vct_ctx* c, float* ms) {
+    if (!c || !ms) return VCT_ERR_INVALID;
+    const char* never = "vct_last_dynamic_transform_ms: needs parts attached and a vct_update_dynamic_transforms since";
+    const char* untimed = "vct_last_dynamic_transform_ms: the last transform was issued with timing off (vct_set_trace_timing)";
+    if (!c->dyn.nparts || !c->dyn.xform_timer.have) return vct_fail(c, VCT_ERR_INVALID, never);
+    return vct_timer_ms(c, c->dyn.xform_timer, ms, never, untimed);
 }
 
 int vct_set_dynamic_draw(vct_ctx* c, int32_t flags, const float specular[3]) {

@@ -484,8 +484,22 @@ struct VctDynamic {
     VctBuf<float> emission;             // [nmat][4] (rgb, 0)
     VctBuf<unsigned long long> acc_emis;   // [max_bricks][512][2]
     bool pass_emis = false;
+    // Rigid parts (vct_set_dynamic_parts): a part index per triangle, the rest positions the matrices move, and the
+    // context's own copy of the matrices, all three or none.  They belong to the mesh like the emission table.  While
+    // attached, `pos` is rest x matrices of the last vct_update_dynamic_transforms (or the rest itself behind a
+    // vct_update_dynamic_positions).
+    int32_t nparts = 0;
+    VctBuf<float> rest;                 // [ntri][9]
+    VctBuf<int32_t> part;               // [ntri] in 0 .. nparts-1, checked on the host
+    VctBuf<float4> part_m;              // [nparts][3] rows of the matrices: 16-byte aligned, as the kernels load them
+    VctTimer xform_timer;               // vct_last_dynamic_transform_ms
 
     bool attached() const { return ntri > 0; }
+    void drop_parts() {
+        nparts = 0;
+        rest.reset(); part.reset(); part_m.reset();
+        xform_timer = VctTimer();
+    }
     bool drawn(int32_t flag) const { return attached() && (draw_flags & flag) && draw_pos; }
     void keep_draw_state(const VctDynamic& o) {
         draw_flags = o.draw_flags;

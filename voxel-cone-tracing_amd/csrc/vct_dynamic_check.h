@@ -35,6 +35,46 @@ static inline const char* vct_dynamic_check_update(bool attached, const float* p
     return nullptr;
 }
 
+// What is wrong with the arguments of an attaching vct_set_dynamic_parts (the detaching form is part == NULL with
+// nparts == 0), or null.  A part index outside 0 .. nparts-1: *bad_tri is its triangle, else -1.
+static inline const char* vct_dynamic_check_parts(bool attached, const int32_t* part, int32_t ntri, int32_t nparts, int32_t* bad_tri) {
+    *bad_tri = -1;
+    if (!attached || ntri < 1) return "no dynamic mesh attached";
+    if (nparts < 1 || nparts > VCT_DYNAMIC_PARTS_MAX) return "nparts outside 1 .. VCT_DYNAMIC_PARTS_MAX";
+    if (!part) return "null part indices";
+    for (int32_t i = 0; i < ntri; ++i)
+        if (part[i] < 0 || part[i] >= nparts) { *bad_tri = i; return "part index out of range"; }
+    return nullptr;
+}
+
+// What is wrong with the arguments of vct_update_dynamic_transforms, or null.  The matrices themselves are not looked at:
+// a device pointer cannot be, and the rule is the same for both locations.
+static inline const char* vct_dynamic_check_transforms(bool attached, int32_t nparts, const float* m, int32_t location) {
+    if (!attached) return "no dynamic mesh attached";
+    if (nparts < 1) return "no parts attached (vct_set_dynamic_parts)";
+    if (!m) return "null matrices";
+    if (location != VCT_MEM_HOST && location != VCT_MEM_DEVICE) return "location is neither VCT_MEM_HOST nor VCT_MEM_DEVICE";
+    if ((uintptr_t)m & 3u) return "matrices need 4-byte alignment";
+    return nullptr;
+}
+
+// Byte counts of what the parts add to the layer: the rest copy [ntri][9] fp32, the part indices [ntri] int32 and the
+// matrix table [nparts][12] fp32.  ok == false: an argument out of range, or a count does not fit size_t.
+struct VctDynamicPartsSizes {
+    bool ok;
+    size_t rest, part, table;
+};
+static inline VctDynamicPartsSizes vct_dynamic_parts_sizes(int32_t ntri, int32_t nparts) {
+    VctDynamicPartsSizes s = {};
+    if (ntri < 1 || ntri > VCT_DYNAMIC_TRIS_MAX || nparts < 1 || nparts > VCT_DYNAMIC_PARTS_MAX) return s;
+    bool ok = !__builtin_mul_overflow((size_t)ntri, 9 * sizeof(float), &s.rest);
+    ok = ok && !__builtin_mul_overflow((size_t)ntri, sizeof(int32_t), &s.part);
+    ok = ok && !__builtin_mul_overflow((size_t)nparts, 12 * sizeof(float), &s.table);
+    s.ok = ok;
+    if (!ok) { const VctDynamicPartsSizes none = {}; return none; }
+    return s;
+}
+
 // What is wrong with the arguments of vct_set_dynamic_draw, or null.  specular null: the constant is 0, 0, 0.
 #define VCT_DYNAMIC_DRAW_ALL (VCT_DYNAMIC_DRAW_SHADOW | VCT_DYNAMIC_DRAW_GBUFFER)
 static inline bool vct_dynamic_finite(float v) { return v == v && v - v == 0.0f; }

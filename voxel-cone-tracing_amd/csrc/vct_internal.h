@@ -543,6 +543,19 @@ hipError_t vct_launch_dynamic_visibility(const VctRasterArgs& a, const float vie
 // (u, t, b) = vct_import_frame(cross(p1 - p0, p2 - p0)), written to all three vertices of draw_nrm / _tan / _bit.
 hipError_t vct_launch_dynamic_draw_prepare(const float* pos, int32_t ntri, float model_scale, float vertex_limit, float* draw_pos,
                                            float* draw_nrm, float* draw_tan, float* draw_bit, hipStream_t s);
+// Parts of the dynamic mesh (include/vct.h "dynamic mesh", Parts): pos[t] = the rest triangle t moved by the 3 x 4 matrix
+// table[3 * part[t] ..] -- k_dyn_transform, one thread per triangle -- and, in the _prepare form, the draw copy and the
+// frames of the new positions in the same launch (the PARTS instantiation of k_dyn_draw_prepare).  part[t] was checked
+// on the host; the table is the library's own allocation, so its rows are 16-byte aligned.
+struct VctDynPartsArgs {
+    const float* rest;           // [ntri][9]
+    const int32_t* part;         // [ntri] in 0 .. nparts-1
+    const float4* table;         // [nparts][3] rows of the matrices
+    float* pos;                  // [ntri][9] the layer's current positions
+};
+hipError_t vct_launch_dynamic_transform(const VctDynPartsArgs& a, int32_t ntri, hipStream_t s);
+hipError_t vct_launch_dynamic_transform_prepare(const VctDynPartsArgs& a, int32_t ntri, float model_scale, float vertex_limit,
+                                                float* draw_pos, float* draw_nrm, float* draw_tan, float* draw_bit, hipStream_t s);
 // one level of a texture's mip chain from its parent (pw x ph -> w x h), glGenerateMipmap restated as in the oracle
 hipError_t vct_launch_tri_alpha(const VctRasterArgs& a, int32_t* out, hipStream_t s);
 hipError_t vct_launch_tex_mip(const uint32_t* parent, int pw, int ph, uint32_t* level, int w, int h, hipStream_t s);

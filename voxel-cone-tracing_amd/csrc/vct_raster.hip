@@ -2022,12 +2022,55 @@ k_tex_mip(const uint32_t* __restrict__ parent, int pw, int ph, uint32_t* __restr
 // point, zero area, culled by setup_subtri -- so that no raster set-up ever sees an unbounded coordinate.  The frame is
 // the face's: n = cross(p1 - p0, p2 - p0) on the model-space positions, each component a * b - c * d unfused, then
 // vct_import_frame's unit normal, tangent and bitangent, stored at all three vertices like static attributes.
+//
+// Parts (include/vct.h "dynamic mesh", Parts): dyn_transform_tri is the one place that holds the arithmetic -- per vertex
+// and row r, ((M[4r] * x + M[4r+1] * y) + M[4r+2] * z) + M[4r+3], every product and sum rounded (the build does not
+// contract).  dyn_part_tri reads a rest triangle, its part index -- checked on the host, the array is the library's own --
+// and the part's matrix as three 16-byte loads from the library's aligned table: neighbouring triangles mostly share a
+// part, so the rows come from the cache, not from LDS.  k_dyn_transform is the update with no draw flag on; with one on
+// the PARTS instantiation of k_dyn_draw_prepare does the same, stores the positions and goes on to the draw copy and the
+// frames from the registers: one launch and one read of the positions instead of two.
+__device__ __forceinline__ VctTri9 dyn_transform_tri(const VctTri9& rest, const float (&m)[12]) {
+    VctTri9 out;
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+        const float x = rest.v[3 * v], y = rest.v[3 * v + 1], z = rest.v[3 * v + 2];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) out.v[3 * v + r] = ((m[4 * r] * x + m[4 * r + 1] * y) + m[4 * r + 2] * z) + m[4 * r + 3];
+    }
+    return out;
+}
+
+__device__ __forceinline__ VctTri9 dyn_part_tri(const VctDynPartsArgs& a, int t) {
+    const VctTri9 rest = *reinterpret_cast<const VctTri9*>(a.rest + (size_t)t * 9);
+    const float4* rows = a.table + 3 * (size_t)a.part[t];
+    const float4 r0 = rows[0], r1 = rows[1], r2 = rows[2];
+    const float m[12] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w};
+    return dyn_transform_tri(rest, m);
+}
+
 __global__ void __launch_bounds__(256)
-k_dyn_draw_prepare(const float* __restrict__ pos, int ntri, float model_scale, float vertex_limit, float* __restrict__ draw_pos,
+k_dyn_transform(const VctDynPartsArgs a, int ntri) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= ntri) return;
+    *reinterpret_cast<VctTri9*>(a.pos + (size_t)t * 9) = dyn_part_tri(a, t);
+}
+
+// what k_dyn_draw_prepare reads: the layer's positions, or (PARTS) what dyn_part_tri needs to make and store them
+template <bool PARTS> using DynPrepareSrc = std::conditional_t<PARTS, VctDynPartsArgs, const float* __restrict__>;
+template <bool PARTS = false>
+__global__ void __launch_bounds__(256)
+k_dyn_draw_prepare(const DynPrepareSrc<PARTS> pos, int ntri, float model_scale, float vertex_limit, float* __restrict__ draw_pos,
                    float* __restrict__ draw_nrm, float* __restrict__ draw_tan, float* __restrict__ draw_bit) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= ntri) return;
-    VctTri9 q = *reinterpret_cast<const VctTri9*>(pos + (size_t)t * 9);
+    VctTri9 q;
+    if constexpr (PARTS) {
+        q = dyn_part_tri(pos, t);
+        *reinterpret_cast<VctTri9*>(pos.pos + (size_t)t * 9) = q;
+    } else {
+        q = *reinterpret_cast<const VctTri9*>(pos + (size_t)t * 9);
+    }
     bool ok = true;
 #pragma unroll
     for (int k = 0; k < 9; ++k) ok = ok && fabsf(q.v[k] * model_scale) <= vertex_limit;
@@ -2212,7 +2255,21 @@ hipError_t vct_launch_dynamic_visibility(const VctRasterArgs& a, const float vie
 hipError_t vct_launch_dynamic_draw_prepare(const float* pos, int32_t ntri, float model_scale, float vertex_limit, float* draw_pos,
                                            float* draw_nrm, float* draw_tan, float* draw_bit, hipStream_t s) {
     if (ntri <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_dyn_draw_prepare, dim3((ntri + 255) / 256), dim3(256), 0, s, pos, ntri, model_scale, vertex_limit,
+    hipLaunchKernelGGL(k_dyn_draw_prepare<>, dim3((ntri + 255) / 256), dim3(256), 0, s, pos, ntri, model_scale, vertex_limit,
+                       draw_pos, draw_nrm, draw_tan, draw_bit);
+    return hipGetLastError();
+}
+
+hipError_t vct_launch_dynamic_transform(const VctDynPartsArgs& a, int32_t ntri, hipStream_t s) {
+    if (ntri <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_dyn_transform, dim3((ntri + 255) / 256), dim3(256), 0, s, a, ntri);
+    return hipGetLastError();
+}
+
+hipError_t vct_launch_dynamic_transform_prepare(const VctDynPartsArgs& a, int32_t ntri, float model_scale, float vertex_limit,
+                                                float* draw_pos, float* draw_nrm, float* draw_tan, float* draw_bit, hipStream_t s) {
+    if (ntri <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_dyn_draw_prepare<true>, dim3((ntri + 255) / 256), dim3(256), 0, s, a, ntri, model_scale, vertex_limit,
                        draw_pos, draw_nrm, draw_tan, draw_bit);
     return hipGetLastError();
 }

@@ -413,6 +413,23 @@ struct Voxel_Cone_Tracing {
         if (!ctx) return false;
         return check(vct_update_dynamic_positions(ctx, pos, location), "vct_update_dynamic_positions");
     }
+    // Rigid parts of the dynamic mesh (vct_set_dynamic_parts, include/vct.h "dynamic mesh", Parts): an index per triangle in
+    // 0 .. nparts-1; the mesh's current positions become the rest positions, and UpdateDynamicTransforms then moves every
+    // part by its own 3 x 4 model matrix ([nparts][12] floats, rows first) on the device -- 48 bytes per part and frame
+    // instead of 36 per triangle.  After SetDynamicMesh, which drops the parts as the library does; part == NULL detaches.
+    // DownloadDynamicPositions returns the current positions [ntri][9] (picking, debugging); it waits for the stream.
+    bool SetDynamicParts(const int32_t* part, int32_t nparts) {
+        if (!ctx) return false;
+        return check(vct_set_dynamic_parts(ctx, part, nparts), "vct_set_dynamic_parts");
+    }
+    bool UpdateDynamicTransforms(const float* m3x4, int32_t location = VCT_MEM_HOST) {
+        if (!ctx) return false;
+        return check(vct_update_dynamic_transforms(ctx, m3x4, location), "vct_update_dynamic_transforms");
+    }
+    bool DownloadDynamicPositions(float* pos) {
+        if (!ctx) return false;
+        return check(vct_download_dynamic_positions(ctx, pos), "vct_download_dynamic_positions");
+    }
     // Draws the dynamic mesh in the library's own raster stages (vct_set_dynamic_draw): `shadow` -- it casts into the
     // shadow map of DrawDepthTexture() and of every whole GI pass, and every PCF reader sees it; `gbuffer` -- the main
     // draw shows it, with flat per-face normals, its table's colours and the specular colour `specular` (NULL: black).

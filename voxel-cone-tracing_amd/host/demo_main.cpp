@@ -13,7 +13,7 @@
 //            [--sky-gradient ZR,ZG,ZB;HR,HG,HB;GR,GG,GB[;UX,UY,UZ] | --sky-sh FILE] [--reimport]
 //            [--light X,Y,Z;R,G,B;RADIUS;SRC[;DX,DY,DZ;INNER_DEG;OUTER_DEG]]...
 //            [--dynamic-obj FILE --dynamic-path X0,Y0,Z0;X1,Y1,Z1 --dynamic-draw shadow|gbuffer|both --dynamic-bounce
-//             --dynamic-emission MATERIAL=R,G,B[;MATERIAL=R,G,B...]]
+//             --dynamic-emission MATERIAL=R,G,B[;MATERIAL=R,G,B...] --dynamic-spin AX,AY,AZ;DEG_PER_FRAME]
 // --dynamic-obj FILE: a second Wavefront OBJ as the context's dynamic mesh (Voxel_Cone_Tracing::SetDynamicMesh,
 //   vct_set_dynamic_mesh; flat material colours, its textures are not used), translated along the segment of
 //   --dynamic-path (model units, the OBJ's own; default: it stays where it is) over the run's frames.  Every Render()
@@ -28,6 +28,11 @@
 //   its MTL file's Ke gave them (Voxel_Cone_Tracing::SetDynamicEmission, vct_set_dynamic_emission): the object becomes a
 //   moving area light in the volume and, drawn with --dynamic-draw gbuffer|both, is added to the pixels that see it.
 //   Checked before a GPU is touched; without the option the Ke values alone are used.
+//   --dynamic-spin AX,AY,AZ;DEG_PER_FRAME: the whole OBJ becomes one rigid part (Voxel_Cone_Tracing::SetDynamicParts,
+//   vct_set_dynamic_parts) and frame f hands over one 3 x 4 matrix instead of a position array
+//   (UpdateDynamicTransforms, vct_update_dynamic_transforms): the --dynamic-path translation at f composed with a rotation
+//   by f x DEG about the axis through the object's bounding-box centre, built in double and rounded once.  The per-frame
+//   position arrays are then not built.  Finite numbers and a non-zero axis, checked before a GPU is touched.
 //
 // --light SPEC (repeatable, up to 64): a local light (Voxel_Cone_Tracing::SetLights, vct_set_lights) in world units: a point
 //   light at X,Y,Z of colour R,G,B (the factor at distance 1) that reaches RADIUS and whose inverse-square falloff is
@@ -176,6 +181,7 @@ int main(int argc, char** argv) {
     const char* dynamic_draw = nullptr;
     bool dynamic_bounce = false;
     const char* dynamic_emission = nullptr;
+    const char* dynamic_spin = nullptr;
     int cubes[3] = {0, 0, 0};
     bool show_voxels = false;
     int view_source = VCT_VOXVIEW_CURRENT, view_level = 0;
@@ -230,6 +236,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--dynamic-path")) dynamic_path = argv[++i];
         else if (!strcmp(argv[i], "--dynamic-draw")) dynamic_draw = argv[++i];
         else if (!strcmp(argv[i], "--dynamic-emission")) dynamic_emission = argv[++i];
+        else if (!strcmp(argv[i], "--dynamic-spin")) dynamic_spin = argv[++i];
         else if (!strcmp(argv[i], "--ambient-cubes") && i + 2 < argc) {
             if (sscanf(argv[++i], "%d,%d,%d", &cubes[0], &cubes[1], &cubes[2]) != 3 || cubes[0] < 1 || cubes[1] < 1 || cubes[2] < 1 ||
                 (long long)cubes[0] * cubes[1] * cubes[2] * 6 > VCT_POINT_QUERY_MAX) {
@@ -279,6 +286,11 @@ int main(int argc, char** argv) {
     }
     if (dynamic_bounce && !dynamic_obj) { fprintf(stderr, "--dynamic-bounce: needs --dynamic-obj\n"); return 1; }
     if (dynamic_emission && !dynamic_obj) { fprintf(stderr, "--dynamic-emission: needs --dynamic-obj\n"); return 1; }
+    double spin_axis[3] = {0.0, 0.0, 1.0}, spin_deg = 0.0, spin_centre[3] = {0.0, 0.0, 0.0};
+    if (dynamic_spin) {
+        if (!dynamic_obj) { fprintf(stderr, "--dynamic-spin: needs --dynamic-obj\n"); return 1; }
+        if (!vct_demo_parse_dynamic_spin(dynamic_spin, spin_axis, &spin_deg)) { fprintf(stderr, "%s\n", VCT_DEMO_DYNAMIC_SPIN_USAGE); return 1; }
+    }
     std::vector<float> dyn_emission;                        // [dyn_nmat][3]: the OBJ's Ke, then --dynamic-emission over it
     if (dynamic_obj) {
         if (gpus > 0 || (bounces >= 2 && !dynamic_bounce)) { fprintf(stderr, "--dynamic-obj: not with --gpus or --bounces 2\n"); return 1; }
@@ -313,6 +325,13 @@ int main(int argc, char** argv) {
                 fprintf(stderr, "%s; the OBJ has %d materials (at '%s')\n", VCT_DEMO_DYNAMIC_EMISSION_USAGE, (int)dyn_nmat, at);
                 return 1;
             }
+        if (dynamic_spin) {                                 // the axis goes through the centre of the object's bounding box
+            for (int k = 0; k < 3; ++k) {
+                float lo = dyn_pos[(size_t)k], hi = lo;
+                for (size_t i = (size_t)k; i < dyn_pos.size(); i += 3) { lo = std::min(lo, dyn_pos[i]); hi = std::max(hi, dyn_pos[i]); }
+                spin_centre[k] = 0.5 * ((double)lo + (double)hi);
+            }
+        }
         dynamic_light = true;                               // a whole GI pass per frame: the volume follows the object
     }
     float sky_sh[9][3] = {};                                // --sky-gradient / --sky-sh: before a GPU is touched
@@ -422,16 +441,31 @@ int main(int argc, char** argv) {
 
     // --dynamic-obj: the object's positions for every frame of the run (an update is asynchronous: each frame's array
     // stays where it is until the run has finished), attached at the first
+    // --dynamic-spin: no arrays -- the OBJ's own positions are the rest positions of one part, and a frame is 12 floats
+    // (one matrix per frame of the run, for the same reason)
     std::vector<std::vector<float>> dyn_frames;
+    const size_t dyn_nframes = (size_t)(frames > 1 ? frames : 1);
+    std::vector<float> dyn_matrices(dynamic_spin ? dyn_nframes * 12 : 0);
     if (dynamic_obj) {
-        dyn_frames.resize((size_t)(frames > 1 ? frames : 1));
+        for (size_t f = 0; f * 12 < dyn_matrices.size(); ++f) {
+            const double t = dyn_nframes > 1 ? (double)f / (double)(dyn_nframes - 1) : 0.0;
+            double move[3];
+            for (int k = 0; k < 3; ++k) move[k] = (double)dyn_path[0][k] + t * ((double)dyn_path[1][k] - (double)dyn_path[0][k]);
+            vct_demo_spin_matrix(spin_axis, (double)f * spin_deg, spin_centre, move, &dyn_matrices[f * 12]);
+        }
+        dyn_frames.resize(dynamic_spin ? 0 : dyn_nframes);
         for (size_t f = 0; f < dyn_frames.size(); ++f) {
             const float t = dyn_frames.size() > 1 ? (float)f / (float)(dyn_frames.size() - 1) : 0.0f;
             dyn_frames[f] = dyn_pos;
             for (size_t i = 0; i < dyn_frames[f].size(); ++i)
                 dyn_frames[f][i] += dyn_path[0][i % 3] + t * (dyn_path[1][i % 3] - dyn_path[0][i % 3]);
         }
-        if (!voxel_cone_tracing.SetDynamicMesh(dyn_frames[0].data(), dyn_material.data(), dyn_ntri, dyn_albedo.data(), dyn_nmat)) return 3;
+        const float* first = dynamic_spin ? dyn_pos.data() : dyn_frames[0].data();
+        if (!voxel_cone_tracing.SetDynamicMesh(first, dyn_material.data(), dyn_ntri, dyn_albedo.data(), dyn_nmat)) return 3;
+        if (dynamic_spin) {
+            const std::vector<int32_t> one_part((size_t)dyn_ntri, 0);
+            if (!voxel_cone_tracing.SetDynamicParts(one_part.data(), 1)) return 3;
+        }
         // the OBJ's Ke with --dynamic-emission over it (an all-zero table attaches nothing)
         if (!voxel_cone_tracing.SetDynamicEmission(dyn_emission.data(), (size_t)dyn_nmat)) return 3;
         if (dyn_draw_flags && !voxel_cone_tracing.DrawDynamicMesh((dyn_draw_flags & VCT_DYNAMIC_DRAW_SHADOW) != 0,
@@ -439,7 +473,9 @@ int main(int argc, char** argv) {
     }
     auto move_dynamic = [&](int f) {                        // frame f's positions, before its Render()
         if (!dynamic_obj) return true;
-        if (!voxel_cone_tracing.UpdateDynamicMesh(dyn_frames[(size_t)f % dyn_frames.size()].data())) return false;
+        if (dynamic_spin) {
+            if (!voxel_cone_tracing.UpdateDynamicTransforms(&dyn_matrices[((size_t)f % dyn_nframes) * 12])) return false;
+        } else if (!voxel_cone_tracing.UpdateDynamicMesh(dyn_frames[(size_t)f % dyn_frames.size()].data())) return false;
         if (bounces >= 2) {                                 // Render() is no whole pass then: the maps follow the object here
             voxel_cone_tracing.DrawDepthTexture();
             voxel_cone_tracing.DrawVoxelTexture();

@@ -4,6 +4,7 @@
 #define VCT_DEMO_OPTIONS_H_
 
 #include <math.h>
+#include <cmath>
 #include <stdio.h>
 #include <string.h>
 
@@ -156,6 +157,38 @@ static inline const char* vct_demo_parse_dynamic_emission(const char* list, int 
         else if (*q) return q;
     }
     return nullptr;
+}
+
+// --dynamic-spin AX,AY,AZ;DEG_PER_FRAME: the --dynamic-obj mesh as ONE rigid part (vct_set_dynamic_parts), moved by a
+// 3 x 4 matrix per frame (vct_update_dynamic_transforms) instead of a position array per frame: a rotation about the axis
+// through the object's bounding-box centre.  Finite numbers, the axis not zero.  Returns false for anything else.
+#define VCT_DEMO_DYNAMIC_SPIN_USAGE "--dynamic-spin AX,AY,AZ;DEG_PER_FRAME (with --dynamic-obj): finite numbers, a non-zero axis"
+static inline bool vct_demo_parse_dynamic_spin(const char* text, double axis[3], double* deg_per_frame) {
+    if (!text) return false;
+    int used = 0;
+    if (sscanf(text, "%lf,%lf,%lf;%lf%n", &axis[0], &axis[1], &axis[2], deg_per_frame, &used) != 4 || text[used]) return false;
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(axis[k])) return false;
+    if (!std::isfinite(*deg_per_frame)) return false;
+    const double len = sqrt((axis[0] * axis[0] + axis[1] * axis[1]) + axis[2] * axis[2]);
+    if (!std::isfinite(len) || !(len > 0.0)) return false;
+    for (int k = 0; k < 3; ++k) axis[k] /= len;
+    return true;
+}
+
+// The matrix of one frame, rows first: x -> R (x - centre) + centre + translation, R the rotation by `degrees` about the
+// unit `axis` (Rodrigues), built in double and rounded once.
+static inline void vct_demo_spin_matrix(const double axis[3], double degrees, const double centre[3], const double translation[3],
+                                        float m[12]) {
+    const double t = degrees * 0.017453292519943295, c = cos(t), s = sin(t), u = 1.0 - c;
+    const double x = axis[0], y = axis[1], z = axis[2];
+    const double R[3][3] = {{c + x * x * u, x * y * u - z * s, x * z * u + y * s},
+                            {y * x * u + z * s, c + y * y * u, y * z * u - x * s},
+                            {z * x * u - y * s, z * y * u + x * s, c + z * z * u}};
+    for (int r = 0; r < 3; ++r) {
+        for (int k = 0; k < 3; ++k) m[4 * r + k] = (float)R[r][k];
+        m[4 * r + 3] = (float)(centre[r] - ((R[r][0] * centre[0] + R[r][1] * centre[1]) + R[r][2] * centre[2]) + translation[r]);
+    }
 }
 
 #endif

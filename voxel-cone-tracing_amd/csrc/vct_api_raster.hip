@@ -4,13 +4,26 @@
 static size_t shadow_tile_count(int S) { const size_t nb = ((size_t)S + 7) >> 3; return nb * nb; }
 
 // Scratch `r` of one raster pass on stream `s`: `pixels` 64-bit visibility words (main draw) or 32-bit ones (depth_only,
-// the shadow-map words).  `dyn` null: a pass over the static mesh.  Otherwise the dynamic mesh's own pass over its draw
-// copy (include/vct.h "dynamic mesh", drawing): direct form, the triangle count and the records of `dyn`.
+// the shadow-map words).  `dyn` false: a pass over the static mesh.  Otherwise the dynamic mesh's own pass over its draw
+// copy (include/vct.h "dynamic mesh", drawing): direct form, its triangle count and records (vct_dynamic_raster_mesh).
 static int raster_args(vct_ctx* c, VctRasterScratch& r, int side_w, int side_h, bool depth_only, bool binned, hipStream_t s,
-                       VctRasterArgs& a, const VctDynamic* dyn = nullptr) {
+                       VctRasterArgs& a, bool dyn = false) {
     if (!c->mesh.tri_pos) return vct_fail(c, VCT_ERR_INVALID, "no triangles uploaded");
     const size_t pixels = (size_t)side_w * side_h;
-    const int32_t ntri = dyn ? dyn->ntri : c->mesh.ntri;      // what sizes the scratch
+    memset(&a, 0, sizeof(a));
+    if (dyn) vct_dynamic_raster_mesh(c, a);
+    else {
+        const VctMesh& sm = c->mesh;
+        a.pos = sm.tri_pos.get();
+        a.nrm = sm.tri_nrm.get(); a.tan = sm.tri_tan.get(); a.bit = sm.tri_bit.get();
+        a.material = sm.tri_mat.get();
+        a.albedo = sm.mat_albedo.get();
+        a.specular = sm.mat_specular.get();
+        a.emission = depth_only ? nullptr : sm.mat_emission.get();
+        a.mat_gloss = depth_only ? nullptr : sm.mat_gloss.get();
+        a.ntri = sm.ntri;
+    }
+    const int32_t ntri = a.ntri;      // what sizes the scratch
     if (!depth_only) HIP_TRY(c, r.vis.reserve(pixels, &r.dirty));
     const uint32_t bins = (uint32_t)(((size_t)side_w + 15) / 16 * (((size_t)side_h + 15) / 16));
     if (binned) {
@@ -48,7 +61,6 @@ static int raster_args(vct_ctx* c, VctRasterScratch& r, int side_w, int side_h, 
         }
         r.dirty = false;
     }
-    memset(&a, 0, sizeof(a));
     a.binned = binned ? 1 : 0;
     if (binned) {
         a.bin_recs = r.bin_recs.get(); a.bin_rec_cap = (uint32_t)(r.bin_recs.size() / 160);
@@ -62,22 +74,6 @@ static int raster_args(vct_ctx* c, VctRasterScratch& r, int side_w, int side_h, 
         a.bin_next_ctr = r.bin_huge.get() + VCT_BIN_HUGE_CAP + 8 * (r.bin_set ^ 1);
         r.bin_set ^= 1;
     }
-    if (dyn) {      // no specular table (a constant), no emission, no gloss classes, no textures, no alpha test
-        a.pos = dyn->draw_pos.get();
-        a.nrm = dyn->draw_nrm.get(); a.tan = dyn->draw_tan.get(); a.bit = dyn->draw_bit.get();
-        a.material = dyn->mat.get();
-        a.albedo = dyn->albedo.get();
-    } else {
-        const VctMesh& sm = c->mesh;
-        a.pos = sm.tri_pos.get();
-        a.nrm = sm.tri_nrm.get(); a.tan = sm.tri_tan.get(); a.bit = sm.tri_bit.get();
-        a.material = sm.tri_mat.get();
-        a.albedo = sm.mat_albedo.get();
-        a.specular = sm.mat_specular.get();
-        a.emission = depth_only ? nullptr : sm.mat_emission.get();
-        a.mat_gloss = depth_only ? nullptr : sm.mat_gloss.get();
-    }
-    a.ntri = ntri;
     a.model_scale = c->cfg.model_scale;
     a.vis = r.vis.get();
     a.vis32 = nullptr;          // vct_render_shadow_map points it at the shadow-map words
@@ -118,9 +114,9 @@ static int shadow_pass(vct_ctx* c, const float light_vp[16], int S) {
     VctRasterArgs a, da;
     PIPE_TRY(raster_args(c, sm.raster, S, S, true, c->raster_form.mode == 2, cur(c).stream.get(), a));
     // VCT_DYNAMIC_DRAW_SHADOW: the dynamic mesh's draw copy behind the static mesh, into the same words under the same epoch
-    const bool draw_dyn = c->dyn.drawn(VCT_DYNAMIC_DRAW_SHADOW);
+    const bool draw_dyn = vct_dynamic_drawn(c, VCT_DYNAMIC_DRAW_SHADOW);
     if (draw_dyn) {      // (a failure here leaves the static scratch's counter sets swapped and unused: cleared by the next pass)
-        const int rc = raster_args(c, sm.dyn_raster, S, S, true, false, cur(c).stream.get(), da, &c->dyn);
+        const int rc = raster_args(c, sm.dyn_raster, S, S, true, false, cur(c).stream.get(), da, true);
         if (rc) { sm.raster.dirty = true; return rc; }
     }
     bool memset_due = false;
@@ -186,9 +182,9 @@ int vct_render_gbuffer_rows_on(vct_ctx* c, const float view_proj[16], int32_t ro
     VctRasterScratch& dr = cur(c).dyn_raster;
     PIPE_TRY(raster_args(c, r, c->cfg.width, c->cfg.height, false, binned, s, a));
     // VCT_DYNAMIC_DRAW_GBUFFER: the dynamic mesh's draw copy into the slot's second visibility buffer, resolved by the shade kernel
-    const bool draw_dyn = c->dyn.drawn(VCT_DYNAMIC_DRAW_GBUFFER);
+    const bool draw_dyn = vct_dynamic_drawn(c, VCT_DYNAMIC_DRAW_GBUFFER);
     if (draw_dyn) {      // (a failure here leaves the static scratch's counter sets swapped and unused: cleared by the next pass)
-        const int rc = raster_args(c, dr, c->cfg.width, c->cfg.height, false, false, s, da, &c->dyn);
+        const int rc = raster_args(c, dr, c->cfg.width, c->cfg.height, false, false, s, da, true);
         if (rc) { r.dirty = true; return rc; }
     }
     if (slot >= 0) HIP_TRY(c, hipEventRecord(form.ev[2 * slot].get(), s));
@@ -199,16 +195,10 @@ int vct_render_gbuffer_rows_on(vct_ctx* c, const float view_proj[16], int32_t ro
     if (e == hipSuccess && draw_dyn) e = vct_launch_dynamic_visibility(da, view_proj, c->cfg.width, c->cfg.height, row0, row1, s);
     if (e == hipSuccess && shadow_ready) e = hipStreamWaitEvent(s, shadow_ready, 0);
     VctDynShadeArgs ds;
-    if (draw_dyn) {
-        ds.vis = da.vis;
-        ds.pos = da.pos; ds.nrm = da.nrm; ds.tan = da.tan; ds.bit = da.bit;
-        ds.material = da.material; ds.albedo = da.albedo;
-        for (int k = 0; k < 3; ++k) ds.specular[k] = c->dyn.draw_specular[k];
-        ds.emission = c->dyn.emission.get();
-    }
+    if (draw_dyn) vct_dynamic_shade_args(c, da, ds);
     // only the dynamic table is attached and this pass does not draw the dynamic mesh: no kernel writes the planes, and
     // the rows may hold an earlier pass's dynamic pixels -- they show the static table's values, which are 0
-    if (e == hipSuccess && !draw_dyn && c->dyn.emission && !a.emission && cur(c).emis && row1 > row0) {
+    if (e == hipSuccess && !draw_dyn && vct_dynamic_emission_attached(c) && !a.emission && cur(c).emis && row1 > row0) {
         const size_t per_row = (size_t)vct_tiles_x(c) * VCT_EMIS_NPLANES * VCT_TILE_PIX;
         e = hipMemsetAsync(cur(c).emis.get() + (size_t)row0 * per_row, 0, (size_t)(row1 - row0) * per_row * sizeof(float), s);
     }

@@ -147,7 +147,7 @@ int vct_upload_triangles(vct_ctx* c, const float* pos, const int32_t* material, 
     // leaves the context as it was.  The product is formed in fp32, as every kernel forms it; !(x <= lim) is also
     // true for NaN and the infinities.
     {
-        const float ms = c->cfg.model_scale, lim = VCT_VERTEX_LIMIT_GRIDS * c->cfg.grid_world_size;
+        const float ms = c->cfg.model_scale, lim = vct_vertex_limit(c);
         const size_t nfloat = (size_t)ntri * 9;
         for (size_t i = 0; i < nfloat; ++i)
             if (!(fabsf(pos[i] * ms) <= lim)) {

@@ -1,6 +1,5 @@
 // vct_api_voxel.hip -- the C ABI's voxel stages: voxelize, inject, mips, bounce, and the up/downloads of the volume.
 #include "vct_ctx.h"
-#include "vct_dynamic_check.h"
 
 namespace {
 
@@ -51,21 +50,26 @@ void mat_mul(const float a[16], const float b[16], float o[16]) {      // column
 
 }  // namespace
 
-VctVoxParams vct_vox_params(const vct_ctx* c, const VctVoxelPlan& v) {
+VctVoxParams vct_vox_params_scene(const vct_ctx* c) {
     VctVoxParams p;
     memset(&p, 0, sizeof(p));
     p.V = c->cfg.voxel_dim;
     p.G = c->cfg.grid_world_size;
     p.model_scale = c->cfg.model_scale;
-    p.pos = c->mesh.tri_pos.get();
-    p.material = c->mesh.tri_mat.get();
-    p.albedo = c->mesh.mat_albedo.get();
-    p.ntri = c->mesh.ntri;
     p.shadow = c->shadow.words.get();
     p.shadow_tiles = c->shadow.words ? c->shadow.tiles.get() : nullptr;
     p.shadow_ebase = c->shadow.ebase;
     p.shadow_size = c->shadow.size;
     memcpy(p.light_vp, c->shadow.light_vp, 64);
+    return p;
+}
+
+VctVoxParams vct_vox_params(const vct_ctx* c, const VctVoxelPlan& v) {
+    VctVoxParams p = vct_vox_params_scene(c);
+    p.pos = c->mesh.tri_pos.get();
+    p.material = c->mesh.tri_mat.get();
+    p.albedo = c->mesh.mat_albedo.get();
+    p.ntri = c->mesh.ntri;
     p.acc = v.acc.get();
     p.brick_slot = v.brick_slot.get();
     p.frag_sorted = v.frag_sorted.get();
@@ -100,6 +104,26 @@ void vct_glm_voxel_projections(const vct_ctx* c, float proj[48]) {
         glm_lookat_origin(eye[a], up[a], v);
         mat_mul(o, v, proj + 16 * a);
     }
+}
+
+int vct_light_voxels(vct_ctx* c, const uint32_t* attr_albedo, const uint32_t* attr_normal, const uint32_t* slot_brick, uint32_t nslots) {
+    VctLightVoxArgs la;
+    memset(&la, 0, sizeof(la));
+    la.lights = c->lights.table.get(); la.nlights = c->lights.n;
+    la.V = c->cfg.voxel_dim; la.G = c->cfg.grid_world_size;
+    la.level0 = c->vol.chain.get(); la.attr_albedo = attr_albedo; la.attr_normal = attr_normal;
+    la.slot_brick = slot_brick; la.brick_prev = c->vol.brick_prev.get(); la.nslots = nslots;
+    HIP_TRY(c, vct_launch_light_voxels(la, cur(c).stream.get()));
+    return VCT_OK;
+}
+
+int vct_download_level(vct_ctx* c, const uint32_t* morton, int N, uint8_t* dst) {
+    PIPE_TRY(vct_staging_free(c));
+    HIP_TRY(c, c->vol.staging.reserve(c->vol.nvox()));
+    HIP_TRY(c, vct_launch_morton_to_linear(morton, c->vol.staging.get(), N, cur(c).stream.get()));
+    HIP_TRY(c, hipMemcpyAsync(dst, c->vol.staging.get(), (size_t)N * N * N * 4, hipMemcpyDeviceToHost, cur(c).stream.get()));
+    HIP_TRY(c, hipStreamSynchronize(cur(c).stream.get()));
+    return VCT_OK;
 }
 
 extern "C" {
@@ -164,7 +188,7 @@ int vct_voxelize(vct_ctx* c, int32_t mode) {
             p.frag_alb = v.frag_alb.get();
         }
         HIP_TRY(c, vct_launch_voxelize(p, cur(c).stream.get()));      // one workgroup per brick: LDS accumulation + resolve into the staging pool
-        if (c->dyn.attached()) PIPE_TRY(vct_dynamic_voxelize(c));     // the dynamic mesh by itself, into its own accumulators
+        PIPE_TRY(vct_dynamic_voxelize(c));     // the dynamic mesh, if one is attached, by itself into its own accumulators
     }
     v.acc_pending = true;
     c->acc_mode = mode;
@@ -189,20 +213,12 @@ int vct_inject_light(vct_ctx* c) {
     HIP_TRY(c, vct_launch_resolve(a, c->cfg.voxel_dim, c->vol.level0_dirty, cur(c).stream.get()));
     // local lights (include/vct.h "local lights"): their direct term into the bricks the resolve has just written
     if (c->lights.n && c->acc_mode == VCT_VOX_CONSERVATIVE_AVG && v.attr_albedo) {
-        VctLightVoxArgs la;
-        memset(&la, 0, sizeof(la));
-        la.lights = c->lights.table.get(); la.nlights = c->lights.n;
-        la.V = c->cfg.voxel_dim; la.G = c->cfg.grid_world_size;
-        la.level0 = c->vol.chain.get(); la.attr_albedo = v.attr_albedo.get(); la.attr_normal = v.attr_normal.get();
-        la.slot_brick = v.slot_brick.get(); la.brick_prev = c->vol.brick_prev.get(); la.nslots = v.nslots;
         HIP_TRY(c, c->lights.vox_timer.begin(cur(c).stream.get(), c->time_traces));
-        HIP_TRY(c, vct_launch_light_voxels(la, cur(c).stream.get()));
+        PIPE_TRY(vct_light_voxels(c, v.attr_albedo.get(), v.attr_normal.get(), v.slot_brick.get(), v.nslots));
         HIP_TRY(c, c->lights.vox_timer.end(cur(c).stream.get()));
     }
     // the dynamic mesh wins per voxel (include/vct.h "dynamic mesh"): behind the static resolve and its lights
-    const bool merges = c->dyn.pending && c->acc_mode == VCT_VOX_CONSERVATIVE_AVG;
-    if (merges) PIPE_TRY(vct_dynamic_merge(c));
-    c->dyn.in_chain = merges;       // (vct_bounce: a pass with no layer to merge bounces as the static chain)
+    PIPE_TRY(vct_dynamic_merge(c));
     c->vox.acc_pending = false;
     c->vol.level0_resolved();
     c->vox.attrs_valid = c->vox.attr_normal && c->acc_mode == VCT_VOX_CONSERVATIVE_AVG;
@@ -259,7 +275,7 @@ int vct_build_mips(vct_ctx* c) {
 
 int vct_bounce(vct_ctx* c) {
     if (!c) return VCT_ERR_INVALID;
-    if (c->dyn.attached() && !c->dyn.bounce_on)      // the plain bounce walks the static slots and their attributes only
+    if (vct_dynamic_blocks_bounce(c))      // the plain bounce walks the static slots and their attributes only
         return vct_fail(c, VCT_ERR_INVALID, "vct_bounce: a dynamic mesh is attached and the second bounce does not see its voxels "
                                         "(vct_set_dynamic_mesh(ctx, NULL, ...) first)");
     if (!c->cfg.voxel_attributes || !c->vox.attr_normal)
@@ -305,25 +321,12 @@ int vct_bounce(vct_ctx* c) {
     p.bounce_list = c->bounce_list.get() + 1;
     p.bounce_list_cap = (uint32_t)(c->bounce_list.size() - 1);
     p.brick_over = c->brick_over.get();
-    // the dynamic layer in the chain (include/vct.h "dynamic mesh", the second bounce): the DYN kernels and their table
-    const VctDynamic& d = c->dyn;
-    const bool dyn = d.attached() && d.bounce_on && d.in_chain && d.pool_alb;
-    VctBounceDynArgs da;
-    memset(&da, 0, sizeof(da));
-    if (dyn) {
-        const size_t map_bytes = vct_dynamic_bounce_map_bytes(c->cfg.voxel_dim);
-        if (!c->bounce_dyn_map) HIP_TRY(c, c->bounce_dyn_map.alloc(map_bytes / sizeof(uint32_t)));
-        da.res_brick = d.res_brick.get();
-        da.used = d.words.get() + VCT_DYN_W_STATS + 8 * d.set + 1;
-        da.pool_rad = d.pool_rad.get(); da.pool_alb = d.pool_alb.get(); da.pool_nrm = d.pool_nrm.get();
-        da.brick_res = c->bounce_dyn_map.get();
-        da.max_bricks = d.max_bricks;
-        da.list_slots = vct_dynamic_bounce_list_slots(c->vox.nslots, d.max_bricks);
-    }
     HIP_TRY(c, hipMemsetAsync(c->step_counter.get(), 0, VCT_STEP_COUNTERS * sizeof(unsigned long long), cur(c).stream.get()));
     HIP_TRY(c, cur(c).march.begin(cur(c).stream.get(), c->time_traces));
-    // (the table is cleared in front of every bounce that uses it: the layer's bricks of the last one need no undoing)
-    if (dyn) HIP_TRY(c, hipMemsetAsync(da.brick_res, 0xff, vct_dynamic_bounce_map_bytes(c->cfg.voxel_dim), cur(c).stream.get()));
+    // the dynamic layer in the chain (include/vct.h "dynamic mesh", the second bounce): the DYN kernels and their table
+    VctBounceDynArgs da;
+    bool dyn = false;
+    PIPE_TRY(vct_dynamic_bounce_args(c, da, &dyn));
     HIP_TRY(c, vct_launch_bounce(p, cur(c).stream.get(), dyn ? &da : nullptr));
     HIP_TRY(c, cur(c).march.end(cur(c).stream.get()));      // step counter / event pair now describe the bounce launch
     c->last_march_form = c->fast_div ? 2 : 1;
@@ -337,16 +340,6 @@ int vct_bounce(vct_ctx* c) {
     return VCT_OK;
 }
 
-// One Morton level of N^3 texels -> linear staging -> host, synchronised (the next level reuses the staging buffer).
-static int download_level(vct_ctx* c, const uint32_t* morton, int N, uint8_t* dst) {
-    PIPE_TRY(vct_staging_free(c));
-    HIP_TRY(c, c->vol.staging.reserve(c->vol.nvox()));
-    HIP_TRY(c, vct_launch_morton_to_linear(morton, c->vol.staging.get(), N, cur(c).stream.get()));
-    HIP_TRY(c, hipMemcpyAsync(dst, c->vol.staging.get(), (size_t)N * N * N * 4, hipMemcpyDeviceToHost, cur(c).stream.get()));
-    HIP_TRY(c, hipStreamSynchronize(cur(c).stream.get()));
-    return VCT_OK;
-}
-
 int vct_download_voxel_attributes(vct_ctx* c, uint8_t* albedo, uint8_t* normal) {
     if (!c || !albedo || !normal) return VCT_ERR_INVALID;
     if (!c->vox.attr_albedo) return vct_fail(c, VCT_ERR_INVALID, "no voxel attributes (config.voxel_attributes, vct_voxelize + vct_inject_light)");
@@ -357,7 +350,7 @@ int vct_download_voxel_attributes(vct_ctx* c, uint8_t* albedo, uint8_t* normal) 
     HIP_TRY(c, dense.alloc(c->vol.nvox()));
     for (int k = 0; k < 2; ++k) {
         HIP_TRY(c, vct_launch_unpool(src[k], c->vox.brick_slot.get(), dense.get(), (uint32_t)c->vol.nbricks(), cur(c).stream.get()));
-        PIPE_TRY(download_level(c, dense.get(), c->vol.V, dst[k]));
+        PIPE_TRY(vct_download_level(c, dense.get(), c->vol.V, dst[k]));
     }
     return VCT_OK;
 }
@@ -403,7 +396,7 @@ int vct_download_aniso_rgba8(vct_ctx* c, uint8_t* out) {
     for (int d = 0; d < 6; ++d)
         for (int l = 1; l < c->vol.nlev; ++l) {
             const size_t off = d * stride + (size_t)vct_level_offset(V, l) - c->vol.nvox();
-            PIPE_TRY(download_level(c, c->vol.aniso.get() + off, V >> l, out + off * 4));
+            PIPE_TRY(vct_download_level(c, c->vol.aniso.get() + off, V >> l, out + off * 4));
         }
     return VCT_OK;
 }
@@ -414,7 +407,7 @@ int vct_download_chain_rgba8(vct_ctx* c, uint8_t* chain) {
     HIP_TRY(c, hipSetDevice(c->device));
     for (int l = 0; l < c->vol.nlev; ++l) {
         const size_t off = (size_t)vct_level_offset(c->cfg.voxel_dim, l);
-        PIPE_TRY(download_level(c, c->vol.active() + off, c->cfg.voxel_dim >> l, chain + off * 4));
+        PIPE_TRY(vct_download_level(c, c->vol.active() + off, c->cfg.voxel_dim >> l, chain + off * 4));
     }
     return VCT_OK;
 }

@@ -445,9 +445,19 @@ struct VctLights {
     VctTimer vox_timer;               // around k_light_voxels (vct_last_lights_ms [0])
 };
 
+// What outlives the dynamic mesh (vct_set_dynamic_draw, vct_set_dynamic_bounce): context state BESIDE the layer, so that
+// attaching, replacing or detaching a mesh carries nothing over by hand.
+struct VctDynamicSettings {
+    int32_t draw_flags = 0;             // VCT_DYNAMIC_DRAW_*
+    float draw_specular[3] = {0.0f, 0.0f, 0.0f};
+    int32_t bounce_on = 0;              // the second bounce over the layer; read by the next vct_bounce
+};
+
 // The dynamic mesh (include/vct.h "dynamic mesh", vct_api_dynamic.hip): the context's own copy of its triangles and
 // everything the per-pass path needs, allocated by vct_set_dynamic_mesh so that no pass allocates.  ntri == 0: none
-// attached.  Nothing here is indexed by the static mesh's slots: it survives vct_upload_triangles.
+// attached.  Nothing here is indexed by the static mesh's slots: it survives vct_upload_triangles.  What lives and dies
+// together is one member, and a fresh layer (attach, replace, detach) has a fresh one of each.  Only vct_api_dynamic.hip
+// and the inline helpers of this file name a member; every other file calls what is declared under its name below.
 struct VctDynamic {
     int32_t ntri = 0, nmat = 0;
     uint32_t max_bricks = 0;            // brick slots of the layer (vct_dynamic_check.h vct_dynamic_capacity)
@@ -462,50 +472,41 @@ struct VctDynamic {
     VctBuf<unsigned long long> acc;     // [max_bricks][512][2]
     VctBuf<unsigned long long> acc_attr;   // [max_bricks][512][3] (cfg.voxel_attributes)
     VctBuf<uint32_t> pool_rad, pool_alb, pool_nrm;      // [max_bricks][512] of the last resolved pass
-    bool pending = false;               // the accumulators hold a pass no merge has resolved
-    int set = 0;                        // the statistics set of the last resolved pass
     VctTimer vox_timer, merge_timer;    // vct_last_dynamic_ms
-    // Drawing the mesh in the raster stages (vct_set_dynamic_draw).  The flags and the specular constant are context
-    // state: they outlive the mesh (keep_draw_state).  The draw copy and the frames exist while a flag is on and a mesh
-    // is attached; k_dyn_draw_prepare rebuilds them behind every copy into `pos`.
-    int32_t draw_flags = 0;             // VCT_DYNAMIC_DRAW_*
-    float draw_specular[3] = {0.0f, 0.0f, 0.0f};
-    VctBuf<float> draw_pos;             // [ntri][9] `pos`, a triangle outside the vertex contract as nine zeros
-    VctBuf<float> draw_nrm, draw_tan, draw_bit;      // [ntri][9] the face frame at all three vertices
-    // The second bounce over the layer (vct_set_dynamic_bounce).  The switch is context state like the draw flags
-    // (keep_bounce_state).  in_chain: the last vct_inject_light merged THIS layer into level 0 -- false for a fresh layer
+    // The pass in flight.  in_chain: the last vct_inject_light merged THIS layer into level 0 -- false for a fresh layer
     // (attached or replaced since) and after an inject that had no pass of the layer to merge; a pass the layer was left
-    // out of for capacity keeps it true and shows zero used slots on the device.
-    int32_t bounce_on = 0;
-    bool in_chain = false;
-    // Emission of the mesh's materials (vct_set_dynamic_emission): the table and the emission sums beside `acc`, both or
-    // neither.  They belong to the mesh: a fresh layer (attach, replace, detach) has none.  pass_emis: the pending pass
-    // was voxelized with the table, so its merge -- or its discard -- takes the EMIS form and leaves the sums zero.
-    VctBuf<float> emission;             // [nmat][4] (rgb, 0)
-    VctBuf<unsigned long long> acc_emis;   // [max_bricks][512][2]
-    bool pass_emis = false;
+    // out of for capacity keeps it true and shows zero used slots on the device.  emis: the pending pass was voxelized
+    // with the emission table, so its merge -- or its discard -- takes the EMIS form and leaves the sums zero.
+    struct Pass {
+        bool pending = false;           // the accumulators hold a pass no merge has resolved
+        int set = 0;                    // the statistics set of the last resolved pass
+        bool in_chain = false;
+        bool emis = false;
+    } pass;
+    // Drawing the mesh in the raster stages (vct_set_dynamic_draw): the draw copy and the frames, all four or none, exist
+    // while a flag is on and a mesh is attached; k_dyn_draw_prepare rebuilds them behind every copy into `pos`.
+    struct DrawCopy {
+        VctBuf<float> pos;              // [ntri][9] `pos`, a triangle outside the vertex contract as nine zeros
+        VctBuf<float> nrm, tan, bit;    // [ntri][9] the face frame at all three vertices
+    } draw;
+    // Emission of the mesh's materials (vct_set_dynamic_emission): the table and the sums beside `acc`, both or neither.
+    struct Emission {
+        VctBuf<float> table;            // [nmat][4] (rgb, 0)
+        VctBuf<unsigned long long> acc; // [max_bricks][512][2]
+    } emis;
     // Rigid parts (vct_set_dynamic_parts): a part index per triangle, the rest positions the matrices move, and the
-    // context's own copy of the matrices, all three or none.  They belong to the mesh like the emission table.  While
-    // attached, `pos` is rest x matrices of the last vct_update_dynamic_transforms (or the rest itself behind a
+    // context's own copy of the matrices, all three or none (n == 0).  They belong to the mesh like the emission table.
+    // While attached, `pos` is rest x matrices of the last vct_update_dynamic_transforms (or the rest itself behind a
     // vct_update_dynamic_positions).
-    int32_t nparts = 0;
-    VctBuf<float> rest;                 // [ntri][9]
-    VctBuf<int32_t> part;               // [ntri] in 0 .. nparts-1, checked on the host
-    VctBuf<float4> part_m;              // [nparts][3] rows of the matrices: 16-byte aligned, as the kernels load them
-    VctTimer xform_timer;               // vct_last_dynamic_transform_ms
+    struct Parts {
+        int32_t n = 0;
+        VctBuf<float> rest;             // [ntri][9]
+        VctBuf<int32_t> part;           // [ntri] in 0 .. n-1, checked on the host
+        VctBuf<float4> m;               // [n][3] rows of the matrices: 16-byte aligned, as the kernels load them
+        VctTimer xform_timer;           // vct_last_dynamic_transform_ms
+    } parts;
 
     bool attached() const { return ntri > 0; }
-    void drop_parts() {
-        nparts = 0;
-        rest.reset(); part.reset(); part_m.reset();
-        xform_timer = VctTimer();
-    }
-    bool drawn(int32_t flag) const { return attached() && (draw_flags & flag) && draw_pos; }
-    void keep_draw_state(const VctDynamic& o) {
-        draw_flags = o.draw_flags;
-        for (int k = 0; k < 3; ++k) draw_specular[k] = o.draw_specular[k];
-    }
-    void keep_bounce_state(const VctDynamic& o) { bounce_on = o.bounce_on; }
 };
 
 struct vct_ctx {
@@ -534,6 +535,7 @@ struct vct_ctx {
     VctSky sky;
     VctLights lights;
     VctDynamic dyn;
+    VctDynamicSettings dyn_settings;
     bool steps_dirty = true;
     bool fast_div = false;            // set by vct_refresh_steps: constant divisors admit the FMA division
     // set by vct_create: the default trace kernel runs in its CHAIN form, one texel buffer per wave and the level's byte
@@ -580,6 +582,7 @@ inline bool vct_rows_in_frame(const vct_ctx* c, int row0, int row1) { return row
 inline size_t vct_gb_tiled_floats(const vct_ctx* c) { return (size_t)vct_tiles_x(c) * vct_tiles_y(c) * VCT_GB_NPLANES * VCT_TILE_PIX; }
 inline size_t vct_emis_tiled_floats(const vct_ctx* c) { return (size_t)vct_tiles_x(c) * vct_tiles_y(c) * VCT_EMIS_NPLANES * VCT_TILE_PIX; }
 inline size_t vct_gloss_tiled_bytes(const vct_ctx* c) { return (size_t)vct_tiles_x(c) * vct_tiles_y(c) * VCT_TILE_PIX; }
+inline float vct_vertex_limit(const vct_ctx* c) { return VCT_VERTEX_LIMIT_GRIDS * c->cfg.grid_world_size; }      // the vertex contract's bound (include/vct.h), in fp32 as every kernel compares it
 inline size_t vct_aov_frames(uint32_t which) { return (size_t)__builtin_popcount(which); }      // one frame per VCT_AOV_* bit that is on
 
 // ---- what more than one translation unit needs, by the file that defines it: vct_capi.hip ----
@@ -628,6 +631,13 @@ int vct_render_gbuffer_rows_on(vct_ctx* c, const float view_proj[16], int32_t ro
 // vct_api_voxel.hip: parameters of the voxelizer kernels (the context's mesh and shadow map, the buffers of plan `v`); the reference's ProjX/Y/Z
 VctVoxParams vct_vox_params(const vct_ctx* c, const VctVoxelPlan& v);
 void vct_glm_voxel_projections(const vct_ctx* c, float proj[48]);
+// ... their half that any mesh shares, everything else zero: the grid, the model scale and the shadow map
+VctVoxParams vct_vox_params_scene(const vct_ctx* c);
+// k_light_voxels on the selected slot's stream: the attached lights' direct term into the bricks of `slot_brick` that the
+// last resolve wrote, from the two attribute pools of those slots (vct_inject_light; the dynamic layer's merge)
+int vct_light_voxels(vct_ctx* c, const uint32_t* attr_albedo, const uint32_t* attr_normal, const uint32_t* slot_brick, uint32_t nslots);
+// one Morton level of N^3 texels -> linear staging -> host, synchronised (the next level reuses the staging buffer)
+int vct_download_level(vct_ctx* c, const uint32_t* morton, int N, uint8_t* dst);
 // vct_api_trace.hip: the step tables on the device follow the config; everything the march needs (screen trace and bounce)
 int vct_refresh_steps(vct_ctx* c);
 // the step sequence of one aperture (trace.fs:90-104); -1: more than VCT_MAX_STEPS steps, or a march that would not end
@@ -642,7 +652,8 @@ int vct_launch_trace_rows(vct_ctx* c, int row0, int row1, uint16_t* out_base = n
 // is attached -- the static mesh's or the dynamic mesh's: vct_emission_table_attached; vct_emission_planes_release drops
 // them once neither is (the caller's own planes stay), called by whoever has just dropped a table.
 void vct_emission_detach(vct_ctx* c);
-inline bool vct_emission_table_attached(const vct_ctx* c) { return c->mesh.mat_emission || c->dyn.emission; }
+inline bool vct_dynamic_emission_attached(const vct_ctx* c) { return (bool)c->dyn.emis.table; }
+inline bool vct_emission_table_attached(const vct_ctx* c) { return c->mesh.mat_emission || vct_dynamic_emission_attached(c); }
 void vct_emission_planes_release(vct_ctx* c);
 hipError_t vct_emission_planes(const vct_ctx* c, VctFrameSlot& s, bool* fresh = nullptr);
 void vct_emission_planes_drop(VctFrameSlot& s);      // ... and takes them away again (the VctPlanesDrop of vct_planes_attach)
@@ -652,11 +663,24 @@ void vct_material_gloss_detach(vct_ctx* c);
 // vct_api_lights.hip: zeroed lit planes for a slot that has none, the timer around their kernel started over
 hipError_t vct_lights_planes(const vct_ctx* c, VctFrameSlot& s, bool* fresh = nullptr);
 // vct_api_dynamic.hip: the dynamic mesh's part of vct_voxelize (discard of an unresolved pass, slots, fragments) and of
-// vct_inject_light (merge into level 0, its local lights), on the selected slot's stream; nothing attached: nothing issued
+// vct_inject_light (merge into level 0, its local lights), on the selected slot's stream; nothing attached: nothing issued.
+// The merge decides by itself whether there is a pass of the layer to merge and records it for vct_bounce.
 int vct_dynamic_voxelize(vct_ctx* c);
 int vct_dynamic_merge(vct_ctx* c);
 // k_dyn_draw_prepare over the attached mesh's positions on the selected slot's stream (nothing drawn: nothing issued)
 int vct_dynamic_draw_prepare(vct_ctx* c);
+// a raster stage draws the mesh: attached, `flag` (VCT_DYNAMIC_DRAW_*) on in the settings and the layer's draw copy there
+inline bool vct_dynamic_drawn(const vct_ctx* c, int32_t flag) { return c->dyn.attached() && (c->dyn_settings.draw_flags & flag) && c->dyn.draw.pos; }
+// the mesh half (and ntri) of the dynamic mesh's own raster pass, from the draw copy: no specular table (a constant), no
+// emission, no gloss classes, no textures, no alpha test; and the shade kernel's view of that pass `da`
+void vct_dynamic_raster_mesh(const vct_ctx* c, VctRasterArgs& a);
+void vct_dynamic_shade_args(const vct_ctx* c, const VctRasterArgs& da, VctDynShadeArgs& ds);
+// vct_bounce refuses: a mesh is attached and vct_set_dynamic_bounce is off
+inline bool vct_dynamic_blocks_bounce(const vct_ctx* c) { return c->dyn.attached() && !c->dyn_settings.bounce_on; }
+// The layer's part of a bounce, called in front of the launch: *dyn says whether it takes the DYN form (attached, switched
+// on, the layer in the chain, attribute pools); then `da` is filled and c->bounce_dyn_map, allocated on first use, is
+// cleared on the selected slot's stream -- before every bounce that uses it, so the last one's bricks need no undoing.
+int vct_dynamic_bounce_args(vct_ctx* c, VctBounceDynArgs& da, bool* dyn);
 // vct_multi.hip: slab of the attached communicator (false: none attached); its release
 bool vct_comm_rows(const vct_ctx* c, int* row0, int* row1);
 void vct_comm_release(vct_ctx* c);

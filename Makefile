@@ -27,7 +27,7 @@ $(DEMO): $(PKG)/host/demo_main.cpp $(PKG)/host/Voxel_Cone_Tracing.h $(PKG)/host/
 	g++ -O2 -std=c++17 -Wall -Wextra -o $@ $(PKG)/host/demo_main.cpp -L$(PKG) -lvct_amd -lvct_host \
 	    -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,/opt/rocm/lib
 
-$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/vct_internal.h $(CSRC)/vct_layout.h $(CSRC)/vct_ctx.h $(CSRC)/vct_divisors.h $(CSRC)/vct_texel.h $(CSRC)/vct_tilediv.h $(CSRC)/vct_query_check.h $(CSRC)/vct_emission_check.h $(CSRC)/vct_gloss_check.h $(CSRC)/vct_sky_check.h $(CSRC)/vct_import_check.h $(CSRC)/vct_lights_check.h $(CSRC)/vct_dynamic_check.h $(CSRC)/vct_feature_rules.h include/vct.h
+$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/vct_internal.h $(CSRC)/vct_layout.h $(CSRC)/vct_ctx.h $(CSRC)/vct_divisors.h $(CSRC)/vct_texel.h $(CSRC)/vct_tilediv.h $(CSRC)/vct_query_check.h $(CSRC)/vct_emission_check.h $(CSRC)/vct_gloss_check.h $(CSRC)/vct_sky_check.h $(CSRC)/vct_import_check.h $(CSRC)/vct_lights_check.h $(CSRC)/vct_dynamic_check.h $(CSRC)/vct_feature_rules.h $(CSRC)/vct_trace_forms.h include/vct.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(LIB): $(OBJS)

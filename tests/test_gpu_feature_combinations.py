@@ -16,7 +16,7 @@ outputs as test_gpu_sky and test_gpu_components hold them (the specular cone's h
 
 Accounting, after test_gpu_march_params.py's REACHED / launch_of: every launch records which instantiation of
 k_trace_tile_split's SKY / GLOSS / HALF forms and of k_point_march the dispatch selected for it, and the last test asserts
-that the set reached is the set launch_split, launch_half_rate and launch_point_march can select."""
+that the set reached is the set vct_plan_launch (csrc/vct_trace_forms.h) and launch_point_march can select."""
 import numpy as np
 import pytest
 
@@ -47,14 +47,14 @@ TWO_LIGHTS = [lr.point((10.0, -10.0, -20.0), (400.0, 300.0, 200.0), 45.0, 2.0),
 ONE_LIGHT = TWO_LIGHTS[:1]
 SCENES = {"dense32": (32, 37, 21, 0.3), "thin32": (32, 24, 16, 0.08), "dense16": (16, 24, 16, 0.3), "thin16": (16, 37, 21, 0.08)}
 
-# ---- the instantiations a launch with these features can select (csrc/vct_trace.hip) --------------------------------------
-# k_trace_tile_split<WRAP, FASTDIV, .., PRIO, COMP = true, HALF, GLOSS, SKY>, as (WRAP, division, PRIO, SKY, GLOSS, HALF):
-#   launch_split (2035-2053): rate 1 with a sky (2038-2045: GLOSS and PRIO by with_flag) or with gloss classes alone
-#     (2047-2051); with neither, the ordinary COMP forms, which test_gpu_march_params.py accounts for;
-#   launch_half_rate (2098-2105): the pass's last launch, whole frames only, so PRIO always; every SKY x GLOSS.
-# k_point_march<WRAP, FASTDIV, LISTED, WAVES = 1, SKY>, as (WRAP, division, LISTED, SKY): launch_point_march (2071-2078), once
-#   with LISTED = false and once with true in every half-rate pass (2087-2096).  WAVES = 2 is an A/B switch of the environment
-#   (VCT_DIFFUSE_RATE_WAVES) and not a form a caller can select.
+# ---- the instantiations a launch with these features can select (csrc/vct_trace_forms.h, csrc/vct_trace.hip) --------------
+# k_trace_tile_split<WRAP, FASTDIV, SF_COMP | {SF_PRIO, SF_HALF, SF_GLOSS, SF_SKY}>, as (WRAP, division, PRIO, SKY, GLOSS, HALF):
+#   vct_plan_launch (csrc/vct_trace_forms.h), the rate-1 branches: with a sky (GLOSS by the plane, PRIO by spec_prio) or with
+#     gloss classes alone; with neither, the ordinary COMP forms, which test_gpu_march_params.py accounts for;
+#   vct_plan_launch, the half-rate branch: the pass's last launch, whole frames only, so PRIO always; every SKY x GLOSS.
+# k_point_march<WRAP, FASTDIV, LISTED, WAVES = 1, SKY>, as (WRAP, division, LISTED, SKY): launch_point_march (csrc/vct_trace.hip),
+#   once with LISTED = false and once with true in every half-rate pass (launch_half_rate).  WAVES = 2 is an A/B switch of the
+#   environment (VCT_DIFFUSE_RATE_WAVES) and not a form a caller can select.
 SPLIT_FORMS = ({("k_trace_tile_split", wrap, div, prio, sky, gloss, False) for wrap in (0, 1) for div in (IEEE, PRODUCT)
                 for prio in (False, True) for sky, gloss in ((True, False), (False, True), (True, True))}
                | {("k_trace_tile_split", wrap, div, True, sky, gloss, True) for wrap in (0, 1) for div in (IEEE, PRODUCT)
@@ -65,7 +65,7 @@ REACHED = set()
 
 
 def launch_of(wrap, div, what, ty):
-    """The instantiations vct_launch_trace selects for a launch of `what` (launch_v: 2138-2139)."""
+    """The instantiations vct_launch_trace selects for a launch of `what` (csrc/vct_trace_forms.h vct_plan_launch)."""
     sky, gloss = what["sky"] is not None, what["classes"] is not None
     if what["rate"] == 2 and cr.marched_groups(what["mask"], what["aov"])[0]:
         return {("k_trace_tile_split", wrap, div, True, sky, gloss, True),

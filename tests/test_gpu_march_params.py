@@ -31,7 +31,7 @@ CONSTS = {"grid_world_size": "G", "max_distance": "max_distance", "max_alpha": "
 COMP_MASK = cr.SHOW_ALL & ~cr.SHOW_DIFFUSE    # a non-default mask that still marches both cone groups
 ALL_AOV = cr.AOV_INDIRECT_DIFFUSE | cr.AOV_INDIRECT_SPECULAR | cr.AOV_DIRECT
 
-# the FASTDIV = 0 launches of launch_split / launch_v (csrc/vct_trace.hip): (kernel, WRAP, template choice)
+# the FASTDIV = 0 launches vct_plan_launch can name (csrc/vct_trace_forms.h): (kernel, WRAP, template choice)
 IEEE_TRACE_LAUNCHES = (
     {("k_trace_tile", wrap, coop) for wrap in (0, 1) for coop in (False, True)}
     | {("k_trace_tile_split", wrap, "COMPACT", False) for wrap in (0, 1)}
@@ -113,7 +113,7 @@ def form_of(ctx):
 
 
 def launch_of(variant, wrap, aniso, cells, slab, comp):
-    """Which instantiation vct_launch_trace dispatches to (launch_v / launch_split)."""
+    """Which instantiation vct_launch_trace dispatches to (csrc/vct_trace_forms.h vct_plan_launch), restated by hand."""
     if not aniso and variant in (1, 2):
         return ("k_trace_tile", wrap, variant == 2)
     if not aniso and variant == 4:

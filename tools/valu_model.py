@@ -4,7 +4,7 @@
     tools/valu_model.py  [--write]
 
 Compiles csrc/vct_trace.hip to gfx950 assembly, takes the specular march loop of
-k_trace_tile_split<true,1,false,false,false,true,..., CHAIN = true> (the whole-frame instantiation of a chain whose
+k_trace_tile_split<true, 1, SF_PRIO | SF_CHAIN> (csrc/vct_trace_forms.h; the whole-frame instantiation of a chain whose
 levels start below 4 GiB: one texel buffer per wave; the diffuse loop has the
 same body), splits it at its labels into basic blocks, tells the blocks of a level sample apart by what they hold
 (coordinates, fit test against the held block, reuse, fresh anchor, fetch, LDS write, gather, zero result, per-lane
@@ -74,6 +74,24 @@ def scalars(lines):
     return sum(1 for o in ops if not o.startswith(NOT_SALU)) - br, br
 
 
+def split_kernel_label(asm, wrap, fastdiv, flags):
+    """The assembly label of k_trace_tile_split<wrap, fastdiv, FORM>, FORM = the OR of the named bits of
+    csrc/vct_trace_forms.h (read from the header): found by the demangled name, not by a mangled string."""
+    hdr = open(os.path.join(ROOT, "voxel-cone-tracing_amd", "csrc", "vct_trace_forms.h")).read()
+    bits = {name: 1 << int(sh) for name, sh in re.findall(r"\b(SF_[A-Z]+) = 1u << (\d+)", hdr)}
+    word = sum(bits[f] for f in flags)
+    labels = sorted(set(re.findall(r"^(_Z\w*k_trace_tile_split\w*):", asm, re.M)))
+    names = subprocess.run(["c++filt"], input="\n".join(labels), capture_output=True, text=True, check=True).stdout.split("\n")
+    want = "k_trace_tile_split<%s, %d, (VctSplitForm)%d>(" % ("true" if wrap else "false", fastdiv, word)
+    found = [lb for lb, name in zip(labels, names) if want in name]
+    assert len(found) == 1, (want, found)
+    return found[0]
+
+
+def kernel_text(asm, label):
+    return re.search(r"^" + re.escape(label) + r":.*?\.end_amdhsa_kernel", asm, re.S | re.M).group(0)
+
+
 def main():
     src = os.path.join(ROOT, "voxel-cone-tracing_amd", "csrc", "vct_trace.hip")
     other = "--source" in sys.argv
@@ -86,8 +104,7 @@ def main():
                         "-I", os.path.join(ROOT, "voxel-cone-tracing_amd", "csrc"), "-I", os.path.join(ROOT, "include"), "-o", out, src],
                        check=True, capture_output=True)
         text = open(out).read()
-    m = re.search(r"^_ZN12_GLOBAL__N_118k_trace_tile_splitILb1ELi1ELb0ELb0ELb0ELb1ELb0ELb0ELb0ELb0ELb1EEEv14VctTraceParams:.*?\.end_amdhsa_kernel", text, re.S | re.M)
-    body = m.group(0).split("\n")
+    body = kernel_text(text, split_kernel_label(text, True, 1, ("SF_PRIO", "SF_CHAIN"))).split("\n")
     # the specular march = the largest depth-1 inner loop (the diffuse march, inside the cone loop, is depth 2 and has the
     # same body; small depth-1 loops, if any, are prologue code)
     loops = [i for i, ln in enumerate(body) if "Inner Loop Header: Depth=1" in ln]

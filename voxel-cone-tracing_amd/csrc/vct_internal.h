@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "vct_layout.h"
+#include "vct_trace_forms.h"
 
 #if defined(__HIPCC__)
 // unorm8 -> float, bit-identical to (float)c / 255.0f for every c in [0,255]: c * RN(1/255) misses for
@@ -300,7 +301,7 @@ struct VctTraceParams {
     // flags, output level 0
     // The five of them are read by the bounce kernels only and the dr_* beside them by the screen trace only (half-rate
     // diffuse gather: vct_set_diffuse_rate(ctx, 2), include/vct.h; vct_trace.hip k_point_march / k_diffuse_resolve /
-    // k_trace_tile_split<.., HALF = true>; dr_ind != null in a screen trace's parameters selects it).  They share their
+    // k_trace_tile_split's SF_HALF forms; dr_ind != null in a screen trace's parameters selects it).  They share their
     // slots for the reason bounce_out and aov do.
     union { const uint32_t* attr_albedo;
             float4* dr_ind; };          // [h][w] the gather every pixel's composite takes (anchor, interpolated or fill)
@@ -322,7 +323,7 @@ struct VctTraceParams {
         uint16_t* aov;                  // per-component outputs (below): the frames that are on, back to back in bit order
     };
     uint32_t nbricks;
-    // Lighting components (vct_set_lighting_components / vct_set_aov_outputs; k_trace_tile_split<.., COMP = true>, launched
+    // Lighting components (vct_set_lighting_components / vct_set_aov_outputs; k_trace_tile_split's SF_COMP forms, launched
     // when comp != 0): bits 0-4 the VCT_SHOW_* mask, bits 8-9 the cone groups marched (1: cones 0-5, 2: cone 6), bits
     // 16-18 the VCT_AOV_* outputs written to `aov`, bit 30 VCT_COMP_EMISSION, bit 31 set.  (It fills the padding in front of slot_brick.)
     uint32_t comp;
@@ -338,7 +339,7 @@ struct VctTraceParams {
     uint32_t aniso_stride;
     uint32_t aniso_alt_slab;            // float4 offset from a level's LDS slab to its second ("-axis") slab
     // bounce_list / bounce_list_count are the bounce kernels', gloss / pix_gloss the screen trace's (include/vct.h
-    // "per-material gloss"; k_trace_tile_split<.., GLOSS = true>, launched when pix_gloss != null): they share their slots
+    // "per-material gloss"; k_trace_tile_split's SF_GLOSS forms, launched when pix_gloss != null): they share their slots
     // for the reason bounce_out and aov do
     union { uint32_t* bounce_list;      // global list of occupied voxels (Morton indices), brick by brick
             const VctGlossTable* gloss; };   // the class headers and one step table per class
@@ -565,9 +566,7 @@ hipError_t vct_launch_tex_mip(const uint32_t* parent, int pw, int ph, uint32_t* 
 #define VCT_EMIS_NPLANES 3
 hipError_t vct_launch_tile_planes(const void* linear, void* tiled, int nplanes, size_t elem, int w, int h, hipStream_t s);
 hipError_t vct_launch_untile_planes(const void* tiled, void* linear, int nplanes, size_t elem, int w, int h, hipStream_t s);
-// strided (row_stride > 1) and packed tile rows are read by k_trace_tile_split's own tiles only: not by the one-wave
-// kernel (variants 1, 2) nor by the compaction's virtual tiles (4)
-static inline bool vct_variant_takes_row_subsets(int variant) { return variant == 0 || variant == 3; }
+// (vct_variant_takes_row_subsets, which variants take strided or packed tile rows: vct_trace_forms.h, with the launch plan)
 // sets p.ntiles on its own copy; march_form: the division form dispatched (vct_trace.hip)
 // marks (optional, half-rate passes only): three events recorded between the pass's four launches
 hipError_t vct_launch_trace(const VctTraceParams& p, int variant, hipStream_t s, int* march_form = nullptr,

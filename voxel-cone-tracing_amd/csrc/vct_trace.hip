@@ -46,11 +46,13 @@
 #include <hip/hip_fp16.h>
 
 #include <type_traits>
+#include <utility>
 
 #include "../../include/vct.h"
 #include "vct_internal.h"
 #include "vct_texel.h"
 #include "vct_tilediv.h"
+#include "vct_trace_forms.h"
 
 
 namespace {
@@ -284,10 +286,7 @@ __device__ __forceinline__ unsigned long long block_texel_mask(const float4 d) {
 // The chain does not change during a launch, so the descriptor lives across the cones of a wave; it starts invalid.
 // (A descriptor for each slab would also serve the lower level of a specular step, but its four SGPRs more put the
 // default kernel into scratch and made it slower than without reuse: profiles/experiments/README.md, round 7.)
-// -DVCT_REUSE=0 builds the kernels without the path: kept for A/B builds (tools/build_ab.sh), like VCT_STATS.
-#ifndef VCT_REUSE
-#define VCT_REUSE 1
-#endif
+// -DVCT_REUSE=0 builds the kernels without the path (vct_trace_forms.h, with the rule which forms take it: split_reuse).
 #define VCT_NO_BLOCK 0xfffffff0u     // BlockDesc::id of a slab that holds nothing (no level starts there)
 struct BlockDesc {
     // the level (VctLevelRef::off: a multiple of 8, every level in front of it holds a power of 8 texels >= 8) | 1 when
@@ -409,11 +408,13 @@ __device__ __forceinline__ void per_lane_census(MarchStats& ms, const Footprint&
 // Over the shared pieces above: the choice between the cooperative block (COOP, every live footprint inside the block
 // at the anchor) and the per-lane gather, the per-lane gather itself (texel loads in phases of 2 + 2 + 4, or one
 // footprint record with CELLS), and where the issue priority (PRIO) is raised and dropped.
-template <bool WRAP, bool COOP, bool LOOSE = false, bool CELLS = false, bool PRIO = false, bool NARROW = false, bool CHAIN = false>
+template <bool WRAP, VctLevelForm LEVEL>
 __device__ __forceinline__ F4 sample_level(const ChainRef& chain, const VctLevelRef lv,
                                            float ux, float uy, float uz, bool act, unsigned long long am,
                                            float4* __restrict__ blk, const LaneBlock& lb, MarchStats& ms,
                                            const char* __restrict__ cells = nullptr) {
+    constexpr bool COOP = (LEVEL & LF_COOP) != 0, LOOSE = (LEVEL & LF_LOOSE) != 0, CELLS = (LEVEL & LF_CELLS) != 0;
+    constexpr bool PRIO = (LEVEL & LF_PRIO) != 0, NARROW = (LEVEL & LF_NARROW) != 0, CHAIN = (LEVEL & LF_CHAIN) != 0;
     // `am` is ballot64(act), passed in so that compound predicates are ANDed as lane masks on the
     // scalar unit (a ballot of `x && y` costs a v_cndmask + v_cmp_ne pair to materialise the bool).
     // Issue priority raised from here until the sample's loads are out (round 6): a wave that is forming
@@ -576,11 +577,12 @@ __device__ __forceinline__ F4 sample_level(const ChainRef& chain, const VctLevel
 // `held` describes the block in the second one.
 // Over the shared pieces: the fit test runs against the held block first and against a fresh anchor only when that
 // fails, and a fresh block of the second slab becomes the held one.
-template <bool WRAP, bool LOOSE, bool PRIO, int SLAB, bool NARROW = false, bool CHAIN = false>
+template <bool WRAP, VctLevelForm LEVEL, int SLAB>
 __device__ __forceinline__ F4 sample_level_reuse(const ChainRef& chain, const VctLevelRef lv,
                                                  float ux, float uy, float uz, bool act, unsigned long long am,
                                                  float4* __restrict__ blk, const LaneBlock& lb, MarchStats& ms,
                                                  BlockDesc& held) {
+    constexpr bool PRIO = (LEVEL & LF_PRIO) != 0, NARROW = (LEVEL & LF_NARROW) != 0, CHAIN = (LEVEL & LF_CHAIN) != 0;
     // (GL_REPEAT only: k_trace_tile_split switches the path off in clamp mode)
     if (PRIO) __builtin_amdgcn_s_setprio(1);
     const Footprint f = footprint_of(lv, ux, uy, uz);
@@ -643,21 +645,21 @@ __device__ __forceinline__ F4 sample_level_reuse(const ChainRef& chain, const Vc
     if (mode < 2) {
         r = {0.0f, 0.0f, 0.0f, 0.0f};     // all 64 texels zero: every footprint sums to exactly +0
         // incoherent footprints: the per-lane gather, which leaves the slabs and the descriptor alone
-        if (mode == 0) r = sample_level<WRAP, false, LOOSE, false, PRIO, NARROW, CHAIN>(chain, lv, ux, uy, uz, act, am, blk, lb, ms);
+        if (mode == 0) r = sample_level<WRAP, level_form_without(LEVEL, LF_COOP | LF_REUSE)>(chain, lv, ux, uy, uz, act, am, blk, lb, ms);
     }
     return r;
 }
 
 // level SLAB (0: first, 1: second) of a march step, with or without block reuse; `blk` is the wave's first slab
-template <bool WRAP, bool COOP, bool LOOSE, bool CELLS, bool PRIO, bool REUSE, int SLAB, bool NARROW = false, bool CHAIN = false>
+template <bool WRAP, VctLevelForm LEVEL, int SLAB>
 __device__ __forceinline__ F4 sample_step_level(const VctTraceParams& p, const VctLevelRef lv, float ux, float uy, float uz,
                                                 bool act, unsigned long long am, float4* __restrict__ blk,
                                                 const LaneBlock& lb, MarchStats& ms, BlockDesc& held) {
-    if constexpr (REUSE) {
-        static_assert(WRAP && COOP && !CELLS, "block reuse: cooperative sampler, GL_REPEAT, no footprint records");
-        return sample_level_reuse<WRAP, LOOSE, PRIO, SLAB, NARROW, CHAIN>(lb.chain, lv, ux, uy, uz, act, am, blk, lb, ms, held);
+    if constexpr ((LEVEL & LF_REUSE) != 0) {
+        static_assert(WRAP && (LEVEL & LF_COOP) && !(LEVEL & LF_CELLS), "block reuse: cooperative sampler, GL_REPEAT, no footprint records");
+        return sample_level_reuse<WRAP, LEVEL, SLAB>(lb.chain, lv, ux, uy, uz, act, am, blk, lb, ms, held);
     } else {
-        return sample_level<WRAP, COOP, LOOSE, CELLS, PRIO, NARROW, CHAIN>(lb.chain, lv, ux, uy, uz, act, am, blk + SLAB * 64, lb, ms, p.cells_biased);
+        return sample_level<WRAP, LEVEL>(lb.chain, lv, ux, uy, uz, act, am, blk + SLAB * 64, lb, ms, p.cells_biased);
     }
 }
 
@@ -681,6 +683,7 @@ __device__ __forceinline__ F4 sample_aniso(const VctTraceParams& p, const VctLev
                                            float uy, float uz, bool act, unsigned long long m,
                                            float4* __restrict__ blk, const LaneBlock& lb, const AnisoCone& ac,
                                            MarchStats& ms) {
+    constexpr VctLevelForm LEVEL = level_form(COOP ? LF_COOP : LF_NONE);      // of the samples that go through sample_level
     // chain pointer of direction d such that (pointer + lv.off) is the level's first texel
     auto chain_of = [&](int d) { return p.aniso + (size_t)d * p.aniso_stride - p.level_off[1]; };
     const unsigned long long mx = ballot64(ac.nx) & m, my = ballot64(ac.ny) & m, mz = ballot64(ac.nz) & m;
@@ -729,10 +732,10 @@ __device__ __forceinline__ F4 sample_aniso(const VctTraceParams& p, const VctLev
     if (!done) {
         // per axis: lanes that disagree on the sign are served in two masked passes
         auto axis_sample = [&](int axis, bool neg, unsigned long long mn) -> F4 {
-            if (mn == 0ull) return sample_level<WRAP, COOP>(chain_ref(chain_of(2 * axis)), lv, ux, uy, uz, act, m, blk, lb, ms);
-            if (mn == m) return sample_level<WRAP, COOP>(chain_ref(chain_of(2 * axis + 1)), lv, ux, uy, uz, act, m, blk, lb, ms);
-            const F4 a = sample_level<WRAP, COOP>(chain_ref(chain_of(2 * axis)), lv, ux, uy, uz, act && !neg, m & ~mn, blk, lb, ms);
-            const F4 b = sample_level<WRAP, COOP>(chain_ref(chain_of(2 * axis + 1)), lv, ux, uy, uz, act && neg, mn, blk, lb, ms);
+            if (mn == 0ull) return sample_level<WRAP, LEVEL>(chain_ref(chain_of(2 * axis)), lv, ux, uy, uz, act, m, blk, lb, ms);
+            if (mn == m) return sample_level<WRAP, LEVEL>(chain_ref(chain_of(2 * axis + 1)), lv, ux, uy, uz, act, m, blk, lb, ms);
+            const F4 a = sample_level<WRAP, LEVEL>(chain_ref(chain_of(2 * axis)), lv, ux, uy, uz, act && !neg, m & ~mn, blk, lb, ms);
+            const F4 b = sample_level<WRAP, LEVEL>(chain_ref(chain_of(2 * axis + 1)), lv, ux, uy, uz, act && neg, mn, blk, lb, ms);
             return neg ? b : a;
         };
         tx = axis_sample(0, ac.nx, mx);
@@ -776,10 +779,10 @@ __device__ __forceinline__ VctStep load_step(StepTable t, int k) {
         const float uy = fmaf(div_const<FASTDIV>(py, p.half_G_aux, p.half_G_rcp), 0.5f, 0.5f); \
         const float uz = fmaf(div_const<FASTDIV>(pz, p.half_G_aux, p.half_G_rcp), 0.5f, 0.5f); \
         F4 vc = (ANISO && st.level >= 1) ? sample_aniso<WRAP, COOP>(p, st.l1, ux, uy, uz, act, live, blk, lb, ac, ms) \
-                                         : sample_step_level<WRAP, COOP, FASTDIV == 2, CELLS, PRIO, REUSE, 0, NARROW, CHAIN>(p, st.l1, ux, uy, uz, act, live, blk, lb, ms, held); \
+                                         : sample_step_level<WRAP, LEVEL, 0>(p, st.l1, ux, uy, uz, act, live, blk, lb, ms, held); \
         if (st.two_levels) { \
             const F4 t2 = ANISO ? sample_aniso<WRAP, COOP>(p, st.l2, ux, uy, uz, act, live, blk + 64, lb, ac, ms) \
-                                : sample_step_level<WRAP, COOP, FASTDIV == 2, CELLS, PRIO, REUSE, 1, NARROW, CHAIN>(p, st.l2, ux, uy, uz, act, live, blk, lb, ms, held); \
+                                : sample_step_level<WRAP, LEVEL, 1>(p, st.l2, ux, uy, uz, act, live, blk, lb, ms, held); \
             const float g = st.omf;      /* 1 - frac, from the table */ \
             vc.x = fmaf(st.frac, t2.x, g * vc.x); \
             vc.y = fmaf(st.frac, t2.y, g * vc.y); \
@@ -839,12 +842,13 @@ __device__ __forceinline__ void sky_epilogue(const VctTraceParams& p, bool alive
 #define VCT_SKY_NONE 0
 #define VCT_SKY_INSIDE 1
 #define VCT_SKY_ALPHA 2
-template <bool WRAP, int FASTDIV, bool COOP, bool ANISO, bool CELLS, bool PRIO, bool REUSE, int SKY = VCT_SKY_NONE, bool NARROW = false,
-          bool CHAIN = false>
+template <bool WRAP, int FASTDIV, VctMarchForm MARCH, int SKY = VCT_SKY_NONE>
 __device__ __forceinline__ F4 cone_march(const VctTraceParams& p, bool alive, F3 start, F3 dir,
                                          const VctStep* tab_global, int n,
                                          float4* __restrict__ blk, const LaneBlock& lb,
                                          int& steps_out, MarchStats& ms, BlockDesc& held, float* alpha_out = nullptr) {
+    constexpr bool COOP = (MARCH & MF_COOP) != 0, ANISO = (MARCH & MF_ANISO) != 0;
+    constexpr VctLevelForm LEVEL = march_level_form(MARCH, FASTDIV);
     const StepTable tab = (StepTable)tab_global;
     float cr = 0.0f, cg = 0.0f, cb = 0.0f, occ = 0.0f;
     int steps = 0;
@@ -921,13 +925,14 @@ __device__ __forceinline__ F4 cone_march(const VctTraceParams& p, bool alive, F3
 }
 
 // the march without block reuse
-template <bool WRAP, int FASTDIV, bool COOP, bool ANISO = false, bool CELLS = false, bool PRIO = false, int SKY = VCT_SKY_NONE>
+template <bool WRAP, int FASTDIV, VctMarchForm MARCH, int SKY = VCT_SKY_NONE>
 __device__ __forceinline__ F4 cone_march(const VctTraceParams& p, bool alive, F3 start, F3 dir,
                                          const VctStep* tab_global, int n,
                                          float4* __restrict__ blk, const LaneBlock& lb,
                                          int& steps_out, MarchStats& ms) {
+    static_assert(!(MARCH & MF_REUSE), "a march with block reuse takes the caller's descriptor");
     BlockDesc none = no_block();
-    return cone_march<WRAP, FASTDIV, COOP, ANISO, CELLS, PRIO, false, SKY>(p, alive, start, dir, tab_global, n, blk, lb, steps_out, ms, none);
+    return cone_march<WRAP, FASTDIV, MARCH, SKY>(p, alive, start, dir, tab_global, n, blk, lb, steps_out, ms, none);
 }
 
 // `specular`: the wave marches the specular cone (the reuse counters are kept per kind of wave)
@@ -1048,7 +1053,7 @@ __device__ __forceinline__ float clear_colour(const VctTraceParams& p) { return 
 // order are the same in all three cases.
 // COMP with VCT_COMP_EMISSION in the mask word (wave-uniform): out.rgb = ((A + D) + S) + E, one fp32 add per channel, last,
 // E from the launch's pixel-emission planes at em_offset() = tile * 192 + lane (include/vct.h "emissive materials").
-// `shininess`: the exponent of :213 -- p.shininess, or the lane's gloss class's (k_trace_tile_split<.., GLOSS = true>).
+// `shininess`: the exponent of :213 -- p.shininess, or the lane's gloss class's (the SF_GLOSS forms of k_trace_tile_split).
 template <bool COMP, class V4, class Pixel, class EmOffset>
 __device__ __forceinline__ void composite(const VctTraceParams& p, const float* gb, F4 ind, V4 sc, F3 E,
                                           bool alive, Pixel pixel, EmOffset em_offset, float shininess) {
@@ -1138,17 +1143,14 @@ __device__ __forceinline__ int xcd_remap(int b, int nblocks) {
 #ifndef VCT_WAVES_PER_BLOCK
 #define VCT_WAVES_PER_BLOCK 1
 #endif
-#ifndef VCT_TRACE_MIN_WAVES
-#define VCT_TRACE_MIN_WAVES 7     // waves per SIMD the register allocator must leave room for (<= 72 VGPRs).  A/B on the
-                                  // final round-2 kernel (ms at 256^3/1080p): 4: 0.776, 5: 0.775, 6: 0.7235, 7: 0.695, 8: 0.719
-                                  // (spills); with the two-plane gather 7: 0.683 (69 VGPRs, no scratch), 8: 0.689; gathering texel pairs: 7: 0.685, 8: 0.684
-#endif
+// (VCT_TRACE_MIN_WAVES, the waves per SIMD the register allocator must leave room for: vct_trace_forms.h)
 
 // One wave per tile, lane = pixel, the 7 cones in sequence; VCT_WAVES_PER_BLOCK horizontally
 // adjacent tiles per workgroup, in the tile order of xcd_remap.
 template <bool WRAP, int FASTDIV, bool COOP>
 __global__ void __launch_bounds__(64 * VCT_WAVES_PER_BLOCK, VCT_TRACE_MIN_WAVES)
 k_trace_tile(const VctTraceParams p) {
+    constexpr VctMarchForm MARCH = march_form(COOP ? MF_COOP : MF_NONE);
     __shared__ float4 lds_blk[VCT_WAVES_PER_BLOCK][2][64];
     const int lane = threadIdx.x & 63;
     // wave-uniform by construction; readfirstlane tells the compiler, so tile indices, the tile's
@@ -1190,14 +1192,14 @@ k_trace_tile(const VctTraceParams p) {
 
     int total = 0;
     const F4 ind = gather_six_cones(k0, k1, k2, total,
-        [&](F3 dir, int& st) { return cone_march<WRAP, FASTDIV, COOP>(p, alive, start, dir, p.steps_diffuse, p.n_diffuse, blk, lb, st, ms); },
+        [&](F3 dir, int& st) { return cone_march<WRAP, FASTDIV, MARCH>(p, alive, start, dir, p.steps_diffuse, p.n_diffuse, blk, lb, st, ms); },
         [&](int i, F4 c, int st) { store_debug_cone(p, pixel_index, i, c, st, alive, in_frame); });
 
     // stage 2: the specular cone, from a fresh pointer: re-read instead of keeping planes live
     const float* gb2 = gbuf_ptr(fresh_lane());
     const F3 Rd = specular_dir(eye_dir(gb_planes3(gb2, 0), p.cam), gb_planes3(gb2, 12));
     int st6;
-    const F4 sc = cone_march<WRAP, FASTDIV, COOP>(p, alive, start, Rd, p.steps_specular, p.n_specular, blk, lb, st6, ms);
+    const F4 sc = cone_march<WRAP, FASTDIV, MARCH>(p, alive, start, Rd, p.steps_specular, p.n_specular, blk, lb, st6, ms);
     total += st6;
     store_debug_cone(p, pixel_index, 6, sc, st6, alive, in_frame);
 
@@ -1227,59 +1229,22 @@ k_trace_tile(const VctTraceParams p) {
 // a shorter wave amortises that start-up stall over fewer march steps; 2 waves {0-3, 4-5 + specular} 0.639.
 #define VCT_CONES_PER_WAVE (6 / (VCT_SPLIT - 1))
 static_assert(VCT_SPLIT == 3 || VCT_SPLIT == 4 || VCT_SPLIT == 7, "VCT_SPLIT must be 3, 4 or 7");
-#ifndef VCT_ANISO_MIN_WAVES
-#define VCT_ANISO_MIN_WAVES 5     // A/B (ms, 256^3 1080p): 4: 1.61, 5: 1.47, 6: 1.88 (spills), 7: 1.60
-#endif
-
-// (the anisotropic instantiation carries three samples' worth of state: it gets 128 VGPRs instead of
-// spilling under the 80 of the default kernel)
-// CELLS: the per-lane sampler reads footprint records (p.cells_biased != null; vct_set_footprint_records) -- an
-// instantiation of its own, because the same code behind a run-time test cost the default kernel 2 % (0.608 -> 0.620 ms)
-// COMP: lighting components (p.comp; vct_set_lighting_components, vct_set_aov_outputs) -- a wave whose cone group
-// nothing reads marches nothing, the composite applies the VCT_SHOW_* mask, and the per-component outputs are stored
-// beside the frame.  An instantiation of its own for the same reason as CELLS: the default kernels carry none of it.
-// HALF: the last launch of a half-rate pass (vct_set_diffuse_rate(ctx, 2); "Half-rate diffuse gather" below): the diffuse
-// waves march nothing and leave the debug outputs to the launches in front of this one, and the composite takes the
-// pixel's gather from p.dr_ind instead of the cones in LDS.  Instantiated with COMP and PRIO only (whole frames).
-// GLOSS: gloss classes (include/vct.h "per-material gloss"; p.pix_gloss, p.gloss): the specular wave marches once per class
-// present among its live lanes, each time with that class's step table and the other lanes masked off, and the composite
-// takes the lane's Phong exponent from the class headers.  Instantiated with COMP, for the plain, PRIO and HALF forms.
-// SKY: sky light (include/vct.h "sky light"; p.sky): every marched cone adds what its open remainder gathers from the
-// sky -- cone_march<.., VCT_SKY_INSIDE>, or, with GLOSS, one sky_epilogue per lane behind the class loop.  Instantiated
-// with COMP, for the plain, PRIO and HALF forms, each with and without GLOSS.
-// Waves per SIMD of an instantiation (its launch bound): 8, with the two-texel gathers (NARROW), for the whole-frame
-// forms (PRIO) under GL_REPEAT, which fit 64 registers without scratch -- and for the footprint-record forms (CELLS), which
-// ran 8 waves in 64 registers under the bound of 7 until the hand-over took a 65th.  Everything else keeps the bound of 7
-// and the four-texel gathers: clamp mode (66-72 registers), the HALF forms (56-64 registers: 8 waves without being asked),
-// the compaction experiment, and the forms without PRIO -- launches of at most half the frame, the slabs of a multi-GPU
-// frame: an eighth of a frame is 16 tiles per CU, too few for residency to bind, and the 8-wave form's 1.6 % more
-// vector instructions made those launches 0.2 - 1.5 % slower.  Both forms give the same bits.
-// (A cap on the vector registers alone -- amdgpu_num_vgpr(64) under the bound of 7, which keeps six more scalar
-// registers and 30 scalars out of the spill lanes -- does not get the eighth wave: +2.9 % against the parent where the
-// bound of 8 measures -2 %.)  -DVCT_SPLIT_MAX_WAVES=7 builds every form with the bound of 7: kept for A/B builds
-// (tools/build_ab.sh), like VCT_REUSE.  Resource lines: profiles/experiments/r16_occupancy_kernels.txt.
-#ifndef VCT_SPLIT_MAX_WAVES
-#define VCT_SPLIT_MAX_WAVES 8
-#endif
-constexpr int split_min_waves(bool wrap, bool aniso, bool compact, bool cells, bool prio, bool half, bool gloss) {
-    if (aniso) return VCT_ANISO_MIN_WAVES;
-    const bool fits = wrap && !compact && !half && (cells || prio);
-    return fits && VCT_SPLIT_MAX_WAVES >= 8 ? 8 : VCT_TRACE_MIN_WAVES;
-}
+// The forms of this kernel (ANISO, COMPACT, CELLS, PRIO, COMP, HALF, GLOSS, SKY, CHAIN), which of them exist, the waves per
+// SIMD of each (split_min_waves: its launch bound) and what its marches derive from it (split_march_form: NARROW, REUSE):
+// vct_trace_forms.h.
 typedef const __attribute__((address_space(4))) VctGlossTable* GlossTable;
 // the lane's class: its byte of the tile's plane under the clamp rule -- never an index before the clamp
 __device__ __forceinline__ int gloss_class_of(const VctTraceParams& p, int tile, int pix, int nclasses) {
     const int b = (int)p.pix_gloss[(size_t)tile * VCT_TILE_PIX + pix];
     return b < nclasses ? b : 0;
 }
-template <bool WRAP, int FASTDIV, bool ANISO, bool COMPACT = false, bool CELLS = false, bool PRIO = false, bool COMP = false,
-          bool HALF = false, bool GLOSS = false, bool SKY = false, bool CHAIN = false>
-__global__ void __launch_bounds__(64 * VCT_SPLIT, split_min_waves(WRAP, ANISO, COMPACT, CELLS, PRIO, HALF, GLOSS))
+template <bool WRAP, int FASTDIV, VctSplitForm FORM>
+__global__ void __launch_bounds__(64 * VCT_SPLIT, split_min_waves(WRAP, FORM))
 k_trace_tile_split(const VctTraceParams p) {
-    constexpr bool NARROW = !ANISO && split_min_waves(WRAP, ANISO, COMPACT, CELLS, PRIO, HALF, GLOSS) >= 8;
-    static_assert(!GLOSS || (COMP && !ANISO && !COMPACT && !CELLS), "gloss classes: the default kernel's COMP forms only");
-    static_assert(!SKY || (COMP && !ANISO && !COMPACT && !CELLS), "sky light: the default kernel's COMP forms only");
-    static_assert(!CHAIN || (WRAP && !ANISO && !COMPACT && !CELLS), "one texel buffer per wave (ChainRef): the plain GL_REPEAT forms only");
+    static_assert(VctSplitFormChecked<WRAP, FORM>::value, "a form the kernel has no code for");
+    constexpr bool ANISO = (FORM & SF_ANISO) != 0, COMPACT = (FORM & SF_COMPACT) != 0, PRIO = (FORM & SF_PRIO) != 0;
+    constexpr bool COMP = (FORM & SF_COMP) != 0, HALF = (FORM & SF_HALF) != 0, GLOSS = (FORM & SF_GLOSS) != 0, SKY = (FORM & SF_SKY) != 0;
+    constexpr VctMarchForm MARCH = split_march_form(WRAP, FORM);       // of every march of this kernel
     __shared__ float4 lds_blk[VCT_SPLIT][ANISO ? 4 : 2][64];   // per wave: level-1 slab, level-2 slab (+ their "-axis" slabs)
     // Cone hand-over.  The workgroup's LDS stays allocated until its last wave ends while the waves that ended free their
     // slots and registers, so what a tile declares caps how many tiles fill a CU's wave slots: the cones travel in the
@@ -1332,9 +1297,7 @@ k_trace_tile_split(const VctTraceParams p) {
 
     const LaneBlock lb = make_lane_block(p, lane);
     MarchStats ms = {};
-    // block reuse (BlockDesc): the plain, PRIO, COMP, HALF and loose instantiations under GL_REPEAT; the others -- and
-    // clamp mode, where the descriptor costs the kernel 12 B of scratch per lane -- sample as before
-    constexpr bool REUSE = VCT_REUSE && WRAP && !ANISO && !CELLS && !COMPACT;
+    // block reuse (BlockDesc), in the forms split_reuse names; the others never read the descriptor
     BlockDesc held = no_block();
 
     // (interleaved slabs: traced row j of the launch is tile row row0 + j * stride; the plain launch pays no second division)
@@ -1386,7 +1349,7 @@ k_trace_tile_split(const VctTraceParams p) {
 #pragma unroll 1
         for (int i = first; i < first + VCT_CONES_PER_WAVE; ++i) {      // :196-199
             int st;
-            const F4 c = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO, REUSE, SKY ? VCT_SKY_INSIDE : VCT_SKY_NONE, NARROW, CHAIN>(p, march_d, start, cone_dir(k0, k1, k2, i),
+            const F4 c = cone_march<WRAP, FASTDIV, MARCH, SKY ? VCT_SKY_INSIDE : VCT_SKY_NONE>(p, march_d, start, cone_dir(k0, k1, k2, i),
                                                                        p.steps_diffuse, n_diffuse, blk, lb, st, ms, held);
             const bool last = i - first == RAW_CONES;      // behind the wave's last march: into its first slab
             const int l = own_lane();
@@ -1449,7 +1412,7 @@ k_trace_tile_split(const VctTraceParams p) {
                 const bool mine = alive && cls == k;
                 int st;
                 float a = 0.0f;
-                const F4 sc = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO, REUSE, SKY ? VCT_SKY_ALPHA : VCT_SKY_NONE, NARROW, CHAIN>(
+                const F4 sc = cone_march<WRAP, FASTDIV, MARCH, SKY ? VCT_SKY_ALPHA : VCT_SKY_NONE>(
                     p, mine && march_s, start, dir, &p.gloss->steps[k][0], (groups & 2u) ? gt->nsteps[k] : 0, blk, lb, st, ms, held, &a);
                 total += st;          // (0 for the lanes that did not march)
                 if (mine) lds_gloss[lane] = make_float4(sc.x, sc.y, sc.z, sc.w);
@@ -1472,7 +1435,7 @@ k_trace_tile_split(const VctTraceParams p) {
             hand_over_e(eye_dir(gb_planes3(gbuf_ptr(fresh_lane()), 0), p.cam));
         } else {
         int st6;
-        const F4 sc = cone_march<WRAP, FASTDIV, true, ANISO, CELLS, PRIO, REUSE, SKY ? VCT_SKY_INSIDE : VCT_SKY_NONE, NARROW, CHAIN>(p, march_s, start, specular_dir(E, N),
+        const F4 sc = cone_march<WRAP, FASTDIV, MARCH, SKY ? VCT_SKY_INSIDE : VCT_SKY_NONE>(p, march_s, start, specular_dir(E, N),
                                                                     p.steps_specular, n_specular, blk, lb, st6, ms, held);
         total += st6;
         store_debug_cone(p, pixel_index, 6, sc, st6, alive, in_frame);
@@ -1530,7 +1493,7 @@ k_trace_tile_split(const VctTraceParams p) {
 //   k_point_march<.., LISTED = false>   lane = one quad of an 8x8 block of quads: finds the anchor, marches its cones
 //   k_diffuse_resolve                   lane = one pixel: acceptance test, interpolation, fill list (one append per wave)
 //   k_point_march<.., LISTED = true>    lane = one entry of the fill list, over the list's device-side count
-//   k_trace_tile_split<.., HALF = true> specular cone + composite with the gather of p.dr_ind
+//   k_trace_tile_split<.., SF_HALF ..>  specular cone + composite with the gather of p.dr_ind
 // The marches are cone_march with rate 1's inputs, so cones and gather of a marched pixel are rate 1's, bit for bit.
 __device__ __forceinline__ const float* gb_of_pixel(const VctTraceParams& p, int x, int y) {
     return p.gbuf + (size_t)((y >> 3) * p.tiles_x + (x >> 3)) * (VCT_GB_NPLANES * VCT_TILE_PIX) + (((y & 7) << 3) | (x & 7));
@@ -1600,7 +1563,7 @@ k_point_march(const VctTraceParams p) {
 #pragma unroll 1
         for (int i = first; i < first + 6 / WAVES; ++i) {
             int st;
-            const F4 c = cone_march<WRAP, FASTDIV, true, false, false, false, SKY ? VCT_SKY_INSIDE : VCT_SKY_NONE>(p, alive, start, cone_dir(k0, k1, k2, i), p.steps_diffuse,
+            const F4 c = cone_march<WRAP, FASTDIV, march_form(MF_COOP), SKY ? VCT_SKY_INSIDE : VCT_SKY_NONE>(p, alive, start, cone_dir(k0, k1, k2, i), p.steps_diffuse,
                                                                                    p.n_diffuse, blk, lb, st, ms);
             total += st;
             bool handed = false;
@@ -1685,7 +1648,7 @@ k_query_march(const VctTraceParams p, const VctQueryArgs q) {
 #pragma unroll 1
             for (int c = 0; c < 6; ++c) {
                 int st;
-                const F4 v = cone_march<WRAP, FASTDIV, true, false, false, false, SKY ? VCT_SKY_INSIDE : VCT_SKY_NONE>(p, alive, start, cone_dir(k0, k1, k2, c), p.steps_diffuse,
+                const F4 v = cone_march<WRAP, FASTDIV, march_form(MF_COOP), SKY ? VCT_SKY_INSIDE : VCT_SKY_NONE>(p, alive, start, cone_dir(k0, k1, k2, c), p.steps_diffuse,
                                                                                        p.n_diffuse, blk, lb, st, ms);
                 total += st;
                 ind = fold_cone(ind, c, v);
@@ -1700,7 +1663,7 @@ k_query_march(const VctTraceParams p, const VctQueryArgs q) {
             const F3 start = cone_start(f3(r.v[0], r.v[1], r.v[2]), f3(r.v[3], r.v[4], r.v[5]), p.vs);
             const VctStep* tab = q.specular ? p.steps_specular : p.steps_diffuse;          // (wave-uniform)
             const int nsteps = q.specular ? p.n_specular : p.n_diffuse;
-            const F4 v = cone_march<WRAP, FASTDIV, true, false, false, false, SKY ? VCT_SKY_INSIDE : VCT_SKY_NONE>(p, alive, start, f3(r.v[6], r.v[7], r.v[8]), tab, nsteps, blk, lb,
+            const F4 v = cone_march<WRAP, FASTDIV, march_form(MF_COOP), SKY ? VCT_SKY_INSIDE : VCT_SKY_NONE>(p, alive, start, f3(r.v[6], r.v[7], r.v[8]), tab, nsteps, blk, lb,
                                                                                    total, ms);
             if (alive) {
                 store_vec4(q.out + i * 4, v);
@@ -1886,7 +1849,7 @@ __device__ __forceinline__ void bounce_voxels(const BounceArgs<DYN>& p, bool ali
     const F3 start = cone_start(P, nrm, p.vs);
     int total = 0;
     const F4 ind = gather_six_cones(t, bt, nrm, total,
-        [&](F3 dir, int& st) { return cone_march<WRAP, FASTDIV, true>(p, alive, start, dir, p.steps_diffuse, p.n_diffuse, blk, lb, st, ms); },
+        [&](F3 dir, int& st) { return cone_march<WRAP, FASTDIV, march_form(MF_COOP)>(p, alive, start, dir, p.steps_diffuse, p.n_diffuse, blk, lb, st, ms); },
         [](int, F4, int) {});
     if (alive) {
         const float occlusion = 1.0f - ind.w;
@@ -2152,50 +2115,31 @@ hipError_t launch(const VctTraceParams& p, int blocks, hipStream_t s) {
     return hipGetLastError();
 }
 
-// Does a launch of the default kernel take a CHAIN form (ChainRef)?  The plain forms under GL_REPEAT of a context whose
-// chain admits byte offsets -- what launch_split reaches behind its other branches.
-bool takes_chain_form(const VctTraceParams& p) {
-    return p.chain_form && p.wrap_repeat && !p.sky && !p.pix_gloss && !p.aniso && !p.cells_biased;
+// The default kernel in the form the plan names (vct_trace_forms.h vct_plan_launch): a fold over the table of the forms
+// that exist, which launches the entry that equals `form` -- so the instantiated set is the table, under this WRAP.  A form
+// the table does not hold (under this WRAP) has no kernel: an error, never another kernel.
+template <bool WRAP, int FASTDIV, size_t... I>
+hipError_t launch_split_form(VctSplitForm form, const VctTraceParams& p, int blocks, hipStream_t s, std::index_sequence<I...>) {
+    bool launched = false;
+    auto entry = [&](auto i) {
+        constexpr VctSplitForm FORM = kVctSplitForms[decltype(i)::value];
+        if constexpr (split_form_exists(WRAP, FORM)) {
+            if (FORM == form) {
+                hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, FORM>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
+                launched = true;
+            }
+        }
+    };
+    (entry(std::integral_constant<size_t, I>{}), ...);
+    return launched ? hipGetLastError() : hipErrorInvalidValue;
 }
-
-// the default kernel's dispatch: anisotropic chains, footprint records, whole-frame issue priority, or plain
-template <bool WRAP, int FASTDIV, bool COMP>
-void launch_split(const VctTraceParams& p, int blocks, hipStream_t s) {
-    const dim3 grid(blocks), block(64 * VCT_SPLIT);
-    if constexpr (COMP) {     // sky light and gloss classes (the host launches them with p.comp on, and refuses them beside the two options below)
-        if (p.sky) {
-            with_flag(p.pix_gloss != nullptr, [&](auto gloss) {
-                with_flag(!p.spec_prio, [&](auto prio) {
-                    hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, decltype(prio)::value, true, false,
-                                                           decltype(gloss)::value, true>), grid, block, 0, s, p);
-                });
-            });
-            return;
-        }
-        if (p.pix_gloss) {
-            if (!p.spec_prio)
-                hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, true, true, false, true>), grid, block, 0, s, p);
-            else hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, false, true, false, true>), grid, block, 0, s, p);
-            return;
-        }
+template <bool WRAP, int FASTDIV>
+hipError_t launch_split_kernel(const VctLaunchPlan& plan, const VctTraceParams& p, int blocks, hipStream_t s) {
+    if (plan.fastdiv == 2) {      // variant 3's kernel: one form, on top of the table
+        hipLaunchKernelGGL((k_trace_tile_split<WRAP, 2, split_form(SF_PLAIN)>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
+        return hipGetLastError();
     }
-    if (p.aniso) {
-        hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, true, false, false, false, COMP>), grid, block, 0, s, p);
-        return;
-    }
-    if constexpr (WRAP) {     // the sampler reads footprint records under GL_REPEAT only: clamp mode has no such kernel
-        if (p.cells_biased) {
-            hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, true, false, COMP>), grid, block, 0, s, p);
-            return;
-        }
-    }
-    // the plain forms under GL_REPEAT: with one texel buffer per wave where the chain admits it (p.chain_form; ChainRef)
-    with_flag(WRAP && takes_chain_form(p), [&](auto chain) {
-        constexpr bool CHAIN = WRAP && decltype(chain)::value;
-        if (!p.spec_prio)     // a whole frame (or most of one): issue priority around the samples' loads (sample_level)
-            hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, true, COMP, false, false, false, CHAIN>), grid, block, 0, s, p);
-        else hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, false, COMP, false, false, false, CHAIN>), grid, block, 0, s, p);
-    });
+    return launch_split_form<WRAP, FASTDIV>(plan.form, p, blocks, s, std::make_index_sequence<(size_t)kVctSplitFormCount>{});
 }
 
 // the four launches of a half-rate pass (p.dr_ind set: whole frame, default kernel, p.comp on); marks: see vct_launch_trace
@@ -2210,7 +2154,7 @@ void launch_point_march(const VctTraceParams& p, bool listed, int blocks, hipStr
     else hipLaunchKernelGGL((k_point_march<WRAP, FASTDIV, false, WAVES>), dim3(blocks), dim3(64 * WAVES), 0, s, p);
 }
 template <bool WRAP, int FASTDIV>
-hipError_t launch_half_rate(const VctTraceParams& p, int blocks, hipStream_t s, const hipEvent_t* marks) {
+hipError_t launch_half_rate(const VctLaunchPlan& plan, const VctTraceParams& p, int blocks, hipStream_t s, const hipEvent_t* marks) {
     auto mark = [&](int i) { return marks ? hipEventRecord(marks[i], s) : hipSuccess; };
     hipError_t e = hipMemsetAsync(p.dr_ctr, 0, VCT_DR_CTR_WORDS * sizeof(unsigned long long), s);
     if (e != hipSuccess) return e;
@@ -2227,25 +2171,17 @@ hipError_t launch_half_rate(const VctTraceParams& p, int blocks, hipStream_t s, 
     if (p.dr_waves == 2) launch_point_march<WRAP, FASTDIV, 2>(p, true, listed_blocks, s);
     else launch_point_march<WRAP, FASTDIV, 1>(p, true, listed_blocks, s);
     if ((e = hipGetLastError()) != hipSuccess || (e = mark(2)) != hipSuccess) return e;
-    if (p.sky)
-        with_flag(p.pix_gloss != nullptr, [&](auto gloss) {
-            hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, true, true, true, decltype(gloss)::value, true>),
-                               dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
-        });
-    else if (p.pix_gloss)
-        hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, true, true, true, true>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
-    else hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, false, false, true, true, true>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
-    return hipGetLastError();
+    return launch_split_kernel<WRAP, FASTDIV>(plan, p, blocks, s);
 }
 
-// `loose`: vct_launch_trace's decision to run variant 3's kernel
+// what the plan names, launched
 template <bool WRAP, int FASTDIV>
-hipError_t launch_v(const VctTraceParams& p, int variant, bool loose, hipStream_t s, const hipEvent_t* marks) {
+hipError_t launch_plan(const VctLaunchPlan& plan, const VctTraceParams& p, hipStream_t s, const hipEvent_t* marks) {
     const int ntiles = p.ntiles;
-    if (!p.aniso && (variant == 1 || variant == 2)) {      // the anisotropic option exists in the default kernel only
+    if (plan.family == VCT_FAMILY_TILE) {
         const int nblocks = (ntiles + VCT_WAVES_PER_BLOCK - 1) / VCT_WAVES_PER_BLOCK;
         const int blocks = ((nblocks + 7) / 8) * 8;     // whole rounds of the 8 XCDs
-        return variant == 1 ? launch<WRAP, FASTDIV, false>(p, blocks, s) : launch<WRAP, FASTDIV, true>(p, blocks, s);
+        return with_flag(plan.coop, [&](auto coop) { return launch<WRAP, FASTDIV, decltype(coop)::value>(p, blocks, s); });
     }
     const int blocks = ((ntiles + 7) / 8) * 8;
     if (p.vt_pix) {         // variant 4: compaction pre-pass (the counter was zeroed by the caller)
@@ -2255,21 +2191,8 @@ hipError_t launch_v(const VctTraceParams& p, int variant, bool loose, hipStream_
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    // variant 3: the default kernel with the one-multiply decode and reciprocal-multiply divisions -- never the default,
-    // not bit-exact; it exists to price the exactness (bench.py exactness_tax)
-    if (loose) {
-        hipLaunchKernelGGL((k_trace_tile_split<WRAP, 2, false>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
-        return hipGetLastError();
-    }
-    if (p.vt_pix) {
-        hipLaunchKernelGGL((k_trace_tile_split<WRAP, FASTDIV, false, true>), dim3(blocks), dim3(64 * VCT_SPLIT), 0, s, p);
-        return hipGetLastError();
-    }
-    // lighting components (a mask other than VCT_SHOW_ALL, or per-component outputs): the COMP instantiation of the same
-    // branch; the host refuses them with variants 1 .. 4, so only the branches below need one
-    if (p.dr_ind) return launch_half_rate<WRAP, FASTDIV>(p, blocks, s, marks);
-    with_flag(p.comp != 0, [&](auto comp) { launch_split<WRAP, FASTDIV, decltype(comp)::value>(p, blocks, s); });
-    return hipGetLastError();
+    if (plan.family == VCT_FAMILY_HALF_RATE) return launch_half_rate<WRAP, FASTDIV>(plan, p, blocks, s, marks);
+    return launch_split_kernel<WRAP, FASTDIV>(plan, p, blocks, s);
 }
 
 // every fp32 bit pattern: div_const<true> against the IEEE divide
@@ -2410,8 +2333,11 @@ hipError_t vct_launch_bounce(const VctTraceParams& p, hipStream_t s, const VctBo
 // 2 the cooperative sampler, one wave per tile (k_trace_tile; with anisotropic chains both run the default kernel);
 // 3 the default kernel with reciprocal-multiply divisions and the one-multiply decode, not bit-exact (with anisotropic
 // chains: the default kernel); 4 the default kernel over the live-pixel compaction (p.vt_pix set by the caller).
+// Which kernel that is, and which combinations have none (hipErrorInvalidValue): vct_trace_forms.h vct_plan_launch, from
+// the facts gathered below; this function executes the plan.
 // p.ntiles, p.tile_mul, p.tile_shift and p.light_unit are set here.  *march_form (optional) receives the division form of the launch as vct_get_stage_counts reports
-// it -- 1 IEEE, 2 the verified product, 3 variant 3's x * r -- also for an empty row range, which launches nothing.
+// it -- 1 IEEE, 2 the verified product, 3 variant 3's x * r; bits 8-9: how the launch's typed loads reach a level, 2 one
+// resource per wave (the CHAIN forms), 1 one per level -- also for an empty row range, which launches nothing.
 // p.dr_ind set: a half-rate pass (vct_set_diffuse_rate(ctx, 2)) -- coarse march, resolve, listed march, then the trace
 // kernel that composites; whole frames of the default kernel with p.comp on only.  marks (optional): three events
 // recorded between those four launches.
@@ -2425,18 +2351,21 @@ hipError_t vct_launch_trace(const VctTraceParams& params, int variant, hipStream
     p.tile_mul = td.mul;
     p.tile_shift = td.shift;
     vct_light_unit(p.light, p.light_unit);
-    const bool loose = variant == 3 && !p.aniso;
-    // (bits 8-9: how the launch's typed loads reach a level -- 2 one resource per wave, the CHAIN forms; 1 one per level)
-    const bool chain = variant == 0 && !loose && !p.vt_pix && !p.dr_ind && takes_chain_form(p);
-    if (march_form) *march_form = (loose ? 3 : (p.fast_div ? 2 : 1)) | ((chain ? 2 : 1) << 8);
+    VctLaunchFacts f = {};
+    f.variant = variant;
+    f.wrap = p.wrap_repeat != 0; f.fast_div = p.fast_div != 0;
+    f.aniso = p.aniso != nullptr; f.cells = p.cells_biased != nullptr;
+    f.comp = p.comp != 0; f.sky = p.sky != nullptr;
+    f.gloss_plane = p.pix_gloss != nullptr; f.gloss_table = p.gloss != nullptr;
+    f.half_rate = p.dr_ind != nullptr; f.compact_list = p.vt_pix != nullptr;
+    f.spec_prio = p.spec_prio != 0; f.chain_form = p.chain_form != 0;
+    f.strided = rstride > 1; f.packed = p.pack_rows != 0;
+    f.whole_frame = p.tile_row0 == 0 && p.tile_row1 == p.tiles_y;
+    const VctLaunchPlan plan = vct_plan_launch(f);
+    if (march_form) *march_form = plan.reported_form;
     if (p.ntiles <= 0) return hipSuccess;
-    if ((rstride > 1 || p.pack_rows) && !vct_variant_takes_row_subsets(variant)) return hipErrorInvalidValue;
-    if (p.pix_gloss && (variant != 0 || p.aniso || p.cells_biased || !p.comp || !p.gloss)) return hipErrorInvalidValue;
-    if (p.sky && (variant != 0 || p.aniso || p.cells_biased || !p.comp)) return hipErrorInvalidValue;
-    if (p.dr_ind && (variant != 0 || p.aniso || p.cells_biased || !p.comp || rstride > 1 || p.pack_rows || p.tile_row0 != 0 ||
-                     p.tile_row1 != p.tiles_y))
-        return hipErrorInvalidValue;
+    if (plan.refused) return hipErrorInvalidValue;
     return with_march_mode(p, [&](auto wrap, auto fastdiv) {
-        return launch_v<decltype(wrap)::value, decltype(fastdiv)::value>(p, variant, loose, s, marks);
+        return launch_plan<decltype(wrap)::value, decltype(fastdiv)::value>(plan, p, s, marks);
     });
 }

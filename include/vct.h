@@ -977,6 +977,39 @@ int vct_last_lights_ms(vct_ctx* ctx, float ms[2]);   /* [0] voxel kernel of the 
  * VCT_DYNAMIC_PARTS_MAX, or a NULL part with nparts > 0; a part index outside 0 .. nparts-1 (the message names the
  * triangle); vct_update_dynamic_transforms without parts attached, with NULL m, with an unknown location, or with m not
  * 4-byte aligned.
+ * Skin (vct_set_dynamic_skin; none by default): the attached dynamic mesh may carry, per triangle CORNER, four bone
+ * indices bone[ntri][3][4] in 0 .. nbones-1 and four fp32 weights weight[ntri][3][4], with 1 <= nbones <=
+ * VCT_DYNAMIC_BONES_MAX, and is then moved by one 3 x 4 matrix per BONE: an animated character, cloth on bones, a bending
+ * pipe.  The mesh is a triangle soup, so influences are per corner; corners that share a vertex simply carry the same
+ * values.  The frame call is vct_update_dynamic_transforms(ctx, m, location) with m[nbones][12], the caller's final
+ * skinning matrices (bone x inverse bind): the same table, the same copy, the same ordering, the same 4-byte alignment
+ * rule and the same "ANY fp32 matrix is accepted" rule as for Parts.  All arithmetic is fp32, products and sums in the
+ * written order, nothing fused.  For a corner with rest position (x, y, z), bones b0 .. b3, weights w0 .. w3 and
+ * Mk = m[bk]:
+ *                B[j]  = ((w0 * M0[j] + w1 * M1[j]) + w2 * M2[j]) + w3 * M3[j]        j = 0 .. 11
+ *                p'_r  = ((B[4r] * x + B[4r+1] * y) + B[4r+2] * z) + B[4r+3]          r = 0, 1, 2
+ *   Zero weights  all four terms are ALWAYS evaluated: a weight of 0 does not skip its bone, and 0 * inf is NaN.  A corner
+ *              that names a bone whose matrix is not finite therefore takes its triangle out of the vertex contract
+ *              even where that bone's weight is 0: the triangle contributes nothing and is counted.  Point unused slots
+ *              at a bone that is in use (with weight 0), not at a spare one.
+ *   Weights    are used as given: the library does not normalise them.  Each must be finite (checked on the host at
+ *              attach); negative values and sums other than 1 are accepted.
+ *   Rest, Positions, Ownership, Capacity  as for Parts: vct_set_dynamic_skin snapshots the layer's current positions
+ *              as the rest positions; vct_update_dynamic_positions while a skin is attached sets rest and current
+ *              positions; vct_set_dynamic_mesh drops the skin, vct_set_dynamic_skin(ctx, NULL, NULL, 0) detaches it and
+ *              the current positions stay; max_bricks == 0 counts the bricks of the attached positions only.
+ *   Exclusion  parts and a skin exclude each other: attaching one while the other is attached is VCT_ERR_INVALID with
+ *              nothing touched (detach the other first).  vct_get_dynamic_parts reports 0 while a skin is attached
+ *              and vct_get_dynamic_skin reports 0 while parts are.
+ * vct_set_dynamic_skin waits for work in flight and allocates everything -- the rest copy, the indices (stored packed as
+ * uint16, 24 bytes per triangle: the last admissible index is 65535), the weights, the 16-byte-aligned matrix table
+ * [nbones][12], a timer pair -- so that an update allocates nothing, never waits for the stream and copies nothing to the
+ * host.  vct_last_dynamic_transform_ms then reports the skin kernel.  vct_get_dynamic_skin: the count (*nbones = 0: none)
+ * and, where not NULL, the indices and the weights as set.  With no skin attached every kernel launched, and its argument
+ * block, is the one launched without this paragraph.
+ * VCT_ERR_INVALID, nothing touched: a NULL context; no dynamic mesh attached; nbones outside 1 ..
+ * VCT_DYNAMIC_BONES_MAX; a NULL array (unless both are NULL and nbones is 0); a bone index outside 0 .. nbones-1 or a
+ * weight that is NaN or infinite (the message names triangle, corner and slot); parts attached.
  * Known limits: the drawn mesh has no textures, no gloss class and flat (per-face) normals.  With a flag off
  * the limit of the stage it names remains: vct_render_shadow_map / vct_render_gbuffer then draw the static mesh only and
  * every kernel launched is the one launched without this paragraph.  The voxel view's albedo / normal sources and
@@ -1002,6 +1035,10 @@ int vct_get_dynamic_parts(vct_ctx* ctx, int32_t* nparts /* 0: none */, int32_t* 
 int vct_update_dynamic_transforms(vct_ctx* ctx, const float* m /* [nparts][12] */, int32_t location);
 int vct_download_dynamic_positions(vct_ctx* ctx, float* pos /* [ntri][9], host */);
 int vct_last_dynamic_transform_ms(vct_ctx* ctx, float* ms);
+#define VCT_DYNAMIC_BONES_MAX (1 << 16)
+int vct_set_dynamic_skin(vct_ctx* ctx, const int32_t* bone /* [ntri][3][4], host */, const float* weight /* [ntri][3][4], host */,
+                         int32_t nbones);
+int vct_get_dynamic_skin(vct_ctx* ctx, int32_t* nbones /* 0: none */, int32_t* bone, float* weight /* may be NULL */);
 
 /* ---- two frames in flight (round 6) -----------------------------------------------------------------
  * The reference's Render() (VCT.h:146-190) issues GL commands; the driver starts frame k + 1 while frame k

@@ -84,7 +84,7 @@ ABI_SYMBOLS = [
     "vct_last_dynamic_ms", "vct_set_dynamic_draw", "vct_get_dynamic_draw",
     "vct_set_dynamic_bounce", "vct_get_dynamic_bounce", "vct_set_dynamic_emission", "vct_get_dynamic_emission",
     "vct_set_dynamic_parts", "vct_get_dynamic_parts", "vct_update_dynamic_transforms", "vct_download_dynamic_positions",
-    "vct_last_dynamic_transform_ms",
+    "vct_last_dynamic_transform_ms", "vct_set_dynamic_skin", "vct_get_dynamic_skin",
 ]
 
 
@@ -108,6 +108,7 @@ LIGHTS_MAX = 64
 LIGHT_SPOT = 1
 DYNAMIC_DRAW_SHADOW, DYNAMIC_DRAW_GBUFFER = 1, 2      # vct_set_dynamic_draw
 DYNAMIC_PARTS_MAX = 1 << 16                           # VCT_DYNAMIC_PARTS_MAX (vct_set_dynamic_parts)
+DYNAMIC_BONES_MAX = 1 << 16                           # VCT_DYNAMIC_BONES_MAX (vct_set_dynamic_skin)
 
 
 class Light(C.Structure):
@@ -262,6 +263,8 @@ _lib.vct_get_dynamic_parts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.vct_update_dynamic_transforms.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
 _lib.vct_download_dynamic_positions.argtypes = [C.c_void_p, C.c_void_p]
 _lib.vct_last_dynamic_transform_ms.argtypes = [C.c_void_p, C.c_void_p]
+_lib.vct_set_dynamic_skin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+_lib.vct_get_dynamic_skin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.vct_upload_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
 
 
@@ -673,7 +676,7 @@ class Context:
         following voxelize + inject_light (or gi_pass) voxelizes it and merges it into level 0: it wins per voxel."""
         if pos is None:
             self._ck(_lib.vct_set_dynamic_mesh(self._h, None, None, 0, None, 0, 0), "vct_set_dynamic_mesh")
-            self._dyn_ntri = self._dyn_nmat = self._dyn_nparts = 0
+            self._dyn_ntri = self._dyn_nmat = self._dyn_nparts = self._dyn_nbones = 0
             return
         pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 9)
         material = np.ascontiguousarray(material, np.int32).reshape(-1)
@@ -685,6 +688,7 @@ class Context:
         self._dyn_ntri = pos.shape[0]
         self._dyn_nmat = albedo.shape[0]
         self._dyn_nparts = 0         # the parts went with the previous mesh
+        self._dyn_nbones = 0         # ... and so did the skin
 
     def update_dynamic_positions(self, pos):
         """New positions of the attached dynamic mesh's triangles: a float32 array [ntri, 9] or an int device pointer to
@@ -802,14 +806,59 @@ class Context:
         self._ck(_lib.vct_get_dynamic_parts(self._h, C.byref(n), _ptr(part)), "vct_get_dynamic_parts")
         return int(n.value), part
 
+    def set_dynamic_skin(self, bones, weights, nbones=None):
+        """Skins the ATTACHED dynamic mesh: `bones` int32 and `weights` float32, both [ntri, 3, 4] (or [ntri, 12]) -- four
+        bone indices in 0 .. nbones-1 and four weights per triangle corner (nbones None: the largest index + 1).  The
+        layer's current positions become the rest positions; update_dynamic_transforms then takes one 3 x 4 matrix per
+        bone.  Weights are used as given (not normalised), all four terms always: point unused slots at a bone in use.
+        bones None detaches.  The mesh drops its skin on attach, replace and detach; parts and a skin exclude each other."""
+        if bones is None:
+            self._ck(_lib.vct_set_dynamic_skin(self._h, None, None, 0), "vct_set_dynamic_skin")
+            self._dyn_nbones = 0
+            return
+        bones = np.ascontiguousarray(bones, np.int32)
+        weights = np.ascontiguousarray(weights, np.float32)
+        ntri = getattr(self, "_dyn_ntri", 0)
+        for name, a in (("bone indices", bones), ("weights", weights)):
+            if not ((a.ndim == 3 and a.shape[1:] == (3, 4)) or (a.ndim == 2 and a.shape[1] == 12)) or (ntri and a.shape[0] != ntri):
+                raise VctError(f"set_dynamic_skin: {name} of shape {tuple(a.shape)}, the attached dynamic mesh has "
+                               f"{ntri} triangles: [{ntri}, 3, 4] is expected")
+        if bones.shape[0] != weights.shape[0]:
+            raise VctError(f"set_dynamic_skin: bone indices for {bones.shape[0]} triangles, weights for {weights.shape[0]}")
+        if nbones is None:
+            nbones = int(bones.max()) + 1 if bones.size else 0
+        self._ck(_lib.vct_set_dynamic_skin(self._h, _ptr(bones), _ptr(weights), int(nbones)), "vct_set_dynamic_skin")
+        self._dyn_nbones = int(nbones)
+
+    def dynamic_skin(self):
+        """(nbones, bones int32 [ntri, 3, 4], weights float32 [ntri, 3, 4]) as set by set_dynamic_skin, or None while no
+        skin is attached."""
+        n = C.c_int32(0)
+        self._ck(_lib.vct_get_dynamic_skin(self._h, C.byref(n), None, None), "vct_get_dynamic_skin")
+        if not n.value:
+            return None
+        ntri = self.dynamic_info()["ntri"]
+        bones, weights = np.zeros((ntri, 3, 4), np.int32), np.zeros((ntri, 3, 4), np.float32)
+        self._ck(_lib.vct_get_dynamic_skin(self._h, C.byref(n), _ptr(bones), _ptr(weights)), "vct_get_dynamic_skin")
+        return int(n.value), bones, weights
+
     def update_dynamic_transforms(self, m):
         """One 3 x 4 model matrix per part of the attached dynamic mesh, rows first: a float32 array [nparts, 12] or
         [nparts, 3, 4], or an int device pointer to as many floats.  The layer's positions become rest x matrix, on the
-        device; asynchronous on the selected slot's stream; the next voxelize uses them."""
+        device; asynchronous on the selected slot's stream; the next voxelize uses them.  With a skin attached
+        (set_dynamic_skin) the same call takes one matrix per bone, [nbones, 12] or [nbones, 3, 4]."""
         if isinstance(m, int):
             self._ck(_lib.vct_update_dynamic_transforms(self._h, _ptr(m), MEM_DEVICE), "vct_update_dynamic_transforms")
             return
         m = np.ascontiguousarray(m, np.float32)
+        nbones = getattr(self, "_dyn_nbones", 0)
+        if nbones:
+            if not ((m.ndim == 2 and m.shape[1] == 12) or (m.ndim == 3 and m.shape[1:] == (3, 4))) or m.shape[0] != nbones:
+                raise VctError(f"update_dynamic_transforms: matrices of shape {tuple(m.shape)}, the attached skin has {nbones} "
+                               f"bones: [{nbones}, 12] or [{nbones}, 3, 4] is expected")
+            self._dyn_m = m          # stays alive until the stream has passed the copy
+            self._ck(_lib.vct_update_dynamic_transforms(self._h, _ptr(m), MEM_HOST), "vct_update_dynamic_transforms")
+            return
         nparts = getattr(self, "_dyn_nparts", 0)
         if not ((m.ndim == 2 and m.shape[1] == 12) or (m.ndim == 3 and m.shape[1:] == (3, 4))) or (nparts and m.shape[0] != nparts):
             raise VctError(f"update_dynamic_transforms: matrices of shape {tuple(m.shape)}, the attached mesh has {nparts} "

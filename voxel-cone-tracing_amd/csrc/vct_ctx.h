@@ -494,19 +494,31 @@ struct VctDynamic {
         VctBuf<float> table;            // [nmat][4] (rgb, 0)
         VctBuf<unsigned long long> acc; // [max_bricks][512][2]
     } emis;
-    // Rigid parts (vct_set_dynamic_parts): a part index per triangle, the rest positions the matrices move, and the
-    // context's own copy of the matrices, all three or none (n == 0).  They belong to the mesh like the emission table.
-    // While attached, `pos` is rest x matrices of the last vct_update_dynamic_transforms (or the rest itself behind a
-    // vct_update_dynamic_positions).
+    // Rigid parts (vct_set_dynamic_parts): a part index per triangle and the rest positions the matrices move, both or
+    // none (n == 0).  They belong to the mesh like the emission table.  While attached, `pos` is rest x matrices of the
+    // last vct_update_dynamic_transforms (or the rest itself behind a vct_update_dynamic_positions).
     struct Parts {
         int32_t n = 0;
         VctBuf<float> rest;             // [ntri][9]
         VctBuf<int32_t> part;           // [ntri] in 0 .. n-1, checked on the host
-        VctBuf<float4> m;               // [n][3] rows of the matrices: 16-byte aligned, as the kernels load them
-        VctTimer xform_timer;           // vct_last_dynamic_transform_ms
     } parts;
+    // A skin (vct_set_dynamic_skin): four bone indices and four weights per triangle corner and the rest positions, all
+    // three or none (n == 0: no bones).  Parts and a skin exclude each other (vct_feature_rules.h, movers).
+    struct Skin {
+        int32_t n = 0;
+        VctBuf<float> rest;             // [ntri][9]
+        VctBuf<uint16_t> bone;          // [ntri][3][4] in 0 .. n-1, checked on the host and packed: 24 bytes per triangle
+        VctBuf<float> weight;           // [ntri][3][4] finite, checked on the host
+    } skin;
+    // What the attached mover -- the parts or the skin -- hands to vct_update_dynamic_transforms: the context's own copy of
+    // the matrices, one per part or bone, and the timer of the kernel.  Allocated with the mover, dropped with it.
+    struct Xform {
+        VctBuf<float4> m;               // [n][3] rows of the matrices: 16-byte aligned, as the kernels load them
+        VctTimer timer;                 // vct_last_dynamic_transform_ms
+    } xform;
 
     bool attached() const { return ntri > 0; }
+    int32_t matrices() const { return parts.n ? parts.n : skin.n; }      // what vct_update_dynamic_transforms takes; 0: no mover
 };
 
 struct vct_ctx {

@@ -47,11 +47,12 @@ static inline const char* vct_dynamic_check_parts(bool attached, const int32_t* 
     return nullptr;
 }
 
-// What is wrong with the arguments of vct_update_dynamic_transforms, or null.  The matrices themselves are not looked at:
-// a device pointer cannot be, and the rule is the same for both locations.
+// What is wrong with the arguments of vct_update_dynamic_transforms, or null; nparts is the count of matrices the attached
+// mover takes, its parts or its bones.  The matrices themselves are not looked at: a device pointer cannot be, and the
+// rule is the same for both locations.
 static inline const char* vct_dynamic_check_transforms(bool attached, int32_t nparts, const float* m, int32_t location) {
     if (!attached) return "no dynamic mesh attached";
-    if (nparts < 1) return "no parts attached (vct_set_dynamic_parts)";
+    if (nparts < 1) return "no parts and no skin attached (vct_set_dynamic_parts, vct_set_dynamic_skin)";
     if (!m) return "null matrices";
     if (location != VCT_MEM_HOST && location != VCT_MEM_DEVICE) return "location is neither VCT_MEM_HOST nor VCT_MEM_DEVICE";
     if ((uintptr_t)m & 3u) return "matrices need 4-byte alignment";
@@ -75,9 +76,48 @@ static inline VctDynamicPartsSizes vct_dynamic_parts_sizes(int32_t ntri, int32_t
     return s;
 }
 
+static inline bool vct_dynamic_finite(float v) { return v == v && v - v == 0.0f; }
+
+// What is wrong with the arguments of an attaching vct_set_dynamic_skin (the detaching form is bone == NULL and weight ==
+// NULL with nbones == 0), or null.  bone and weight are [ntri][3][4]: per triangle corner four bone indices in 0 ..
+// nbones-1 and four finite weights.  A bone index out of range or a weight that is NaN or infinite: *bad is its index in
+// the array (triangle = index / 12, corner = index / 4 % 3, slot = index % 4), else (size_t)-1.
+static inline const char* vct_dynamic_check_skin(bool attached, const int32_t* bone, const float* weight, int32_t ntri, int32_t nbones,
+                                                 size_t* bad) {
+    *bad = (size_t)-1;
+    if (!attached || ntri < 1) return "no dynamic mesh attached";
+    if (nbones < 1 || nbones > VCT_DYNAMIC_BONES_MAX) return "nbones outside 1 .. VCT_DYNAMIC_BONES_MAX";
+    if (!bone) return "null bone indices";
+    if (!weight) return "null weights";
+    const size_t n = (size_t)ntri * 12;       // ntri <= 2^20 wherever `attached` is true: no overflow
+    for (size_t i = 0; i < n; ++i)
+        if (bone[i] < 0 || bone[i] >= nbones) { *bad = i; return "bone index out of range"; }
+    for (size_t i = 0; i < n; ++i)
+        if (!vct_dynamic_finite(weight[i])) { *bad = i; return "weight not finite"; }
+    return nullptr;
+}
+
+// Byte counts of what a skin adds to the layer: the rest copy [ntri][9] fp32, the bone indices [ntri][12] packed as
+// uint16 (nbones <= 2^16), the weights [ntri][12] fp32 and the matrix table [nbones][12] fp32.  ok == false: an argument
+// out of range, or a count does not fit size_t.
+struct VctDynamicSkinSizes {
+    bool ok;
+    size_t rest, bone, weight, table;
+};
+static inline VctDynamicSkinSizes vct_dynamic_skin_sizes(int32_t ntri, int32_t nbones) {
+    VctDynamicSkinSizes s = {};
+    if (ntri < 1 || ntri > VCT_DYNAMIC_TRIS_MAX || nbones < 1 || nbones > VCT_DYNAMIC_BONES_MAX) return s;
+    bool ok = !__builtin_mul_overflow((size_t)ntri, 9 * sizeof(float), &s.rest);
+    ok = ok && !__builtin_mul_overflow((size_t)ntri, 12 * sizeof(uint16_t), &s.bone);
+    ok = ok && !__builtin_mul_overflow((size_t)ntri, 12 * sizeof(float), &s.weight);
+    ok = ok && !__builtin_mul_overflow((size_t)nbones, 12 * sizeof(float), &s.table);
+    s.ok = ok;
+    if (!ok) { const VctDynamicSkinSizes none = {}; return none; }
+    return s;
+}
+
 // What is wrong with the arguments of vct_set_dynamic_draw, or null.  specular null: the constant is 0, 0, 0.
 #define VCT_DYNAMIC_DRAW_ALL (VCT_DYNAMIC_DRAW_SHADOW | VCT_DYNAMIC_DRAW_GBUFFER)
-static inline bool vct_dynamic_finite(float v) { return v == v && v - v == 0.0f; }
 static inline const char* vct_dynamic_check_draw(int32_t flags, const float* specular) {
     if (flags & ~(int32_t)VCT_DYNAMIC_DRAW_ALL) return "unknown flag bits";
     if (specular)

@@ -79,4 +79,19 @@ static inline VctConflict vct_rule_conflict(unsigned features, unsigned modes) {
 }
 static inline int vct_rule_bit_index(unsigned bit) { return __builtin_ctz(bit); }
 
+// The MOVERS of the dynamic mesh (include/vct.h "dynamic mesh", Parts and Skin): what turns the matrices of
+// vct_update_dynamic_transforms into positions.  They share the matrix table and the call, so a mesh has at most one:
+// the setter of one is refused while the other is attached.  (Outside the matrix above: no mode is involved.)
+enum VctMover : unsigned { VCT_MOVER_NONE = 0, VCT_MOVER_PARTS = 1, VCT_MOVER_SKIN = 2, VCT_MOVER_COUNT = 3 };
+static const VctRuleText kVctMoverText[VCT_MOVER_COUNT] = {
+    {"no mover", nullptr},
+    {"parts", "vct_set_dynamic_parts(ctx, NULL, 0)"},
+    {"a skin", "vct_set_dynamic_skin(ctx, NULL, NULL, 0)"},
+};
+// The attached mover that refuses attaching `wanted`, or VCT_MOVER_NONE: they go together (nothing attached, or the same
+// kind, which the attach replaces).
+static inline VctMover vct_mover_conflict(VctMover attached, VctMover wanted) {
+    return attached != VCT_MOVER_NONE && wanted != VCT_MOVER_NONE && attached != wanted ? attached : VCT_MOVER_NONE;
+}
+
 #endif

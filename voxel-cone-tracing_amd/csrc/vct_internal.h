@@ -557,6 +557,20 @@ struct VctDynPartsArgs {
 hipError_t vct_launch_dynamic_transform(const VctDynPartsArgs& a, int32_t ntri, hipStream_t s);
 hipError_t vct_launch_dynamic_transform_prepare(const VctDynPartsArgs& a, int32_t ntri, float model_scale, float vertex_limit,
                                                 float* draw_pos, float* draw_nrm, float* draw_tan, float* draw_bit, hipStream_t s);
+// A skin of the dynamic mesh (include/vct.h "dynamic mesh", Skin): pos[t] = the rest triangle t, each corner moved by
+// the blend of four rows of the table with the corner's four weights -- k_dyn_skin, one thread per triangle -- and, in
+// the _prepare form, the draw copy and the frames in the same launch (the skin instantiation of k_dyn_draw_prepare).
+// The indices were checked on the host against the table's rows and packed; all four arrays are the library's own.
+struct VctDynSkinArgs {
+    const float* rest;           // [ntri][9]
+    const uint16_t* bone;        // [ntri][3][4] in 0 .. nbones-1
+    const float* weight;         // [ntri][3][4]
+    const float4* table;         // [nbones][3] rows of the matrices
+    float* pos;                  // [ntri][9] the layer's current positions
+};
+hipError_t vct_launch_dynamic_skin(const VctDynSkinArgs& a, int32_t ntri, hipStream_t s);
+hipError_t vct_launch_dynamic_skin_prepare(const VctDynSkinArgs& a, int32_t ntri, float model_scale, float vertex_limit,
+                                           float* draw_pos, float* draw_nrm, float* draw_tan, float* draw_bit, hipStream_t s);
 // one level of a texture's mip chain from its parent (pw x ph -> w x h), glGenerateMipmap restated as in the oracle
 hipError_t vct_launch_tri_alpha(const VctRasterArgs& a, int32_t* out, hipStream_t s);
 hipError_t vct_launch_tex_mip(const uint32_t* parent, int pw, int ph, uint32_t* level, int w, int h, hipStream_t s);

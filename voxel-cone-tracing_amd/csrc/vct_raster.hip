@@ -2028,8 +2028,16 @@ k_tex_mip(const uint32_t* __restrict__ parent, int pw, int ph, uint32_t* __restr
 // contract).  dyn_part_tri reads a rest triangle, its part index -- checked on the host, the array is the library's own --
 // and the part's matrix as three 16-byte loads from the library's aligned table: neighbouring triangles mostly share a
 // part, so the rows come from the cache, not from LDS.  k_dyn_transform is the update with no draw flag on; with one on
-// the PARTS instantiation of k_dyn_draw_prepare does the same, stores the positions and goes on to the draw copy and the
+// the PARTS (DYN_SRC_PARTS) instantiation of k_dyn_draw_prepare does the same, stores the positions and goes on to the draw copy and the
 // frames from the registers: one launch and one read of the positions instead of two.
+//
+// Skin (include/vct.h "dynamic mesh", Skin): dyn_skin_tri is the one place that holds its arithmetic -- per corner the
+// blend B[j] = ((w0 * M0[j] + w1 * M1[j]) + w2 * M2[j]) + w3 * M3[j] of the four named bones' matrices, all four terms
+// always (a weight of 0 does not skip its bone), then the row expression above on B.  Per corner it reads four packed
+// uint16 indices as one 8-byte load, four weights as one 16-byte load and, per influence, three 16-byte rows of the
+// library's aligned table, served from the cache like a part's.  The indices were checked against the table's rows on the
+// host before they were packed, and 65535 is the last row a full table has.  k_dyn_skin is the update with no draw flag
+// on; with one on the DYN_SRC_SKIN instantiation of k_dyn_draw_prepare goes on to the draw copy and the frames.
 __device__ __forceinline__ VctTri9 dyn_transform_tri(const VctTri9& rest, const float (&m)[12]) {
     VctTri9 out;
 #pragma unroll
@@ -2056,17 +2064,58 @@ k_dyn_transform(const VctDynPartsArgs a, int ntri) {
     *reinterpret_cast<VctTri9*>(a.pos + (size_t)t * 9) = dyn_part_tri(a, t);
 }
 
-// what k_dyn_draw_prepare reads: the layer's positions, or (PARTS) what dyn_part_tri needs to make and store them
-template <bool PARTS> using DynPrepareSrc = std::conditional_t<PARTS, VctDynPartsArgs, const float* __restrict__>;
-template <bool PARTS = false>
+__device__ __forceinline__ VctTri9 dyn_skin_tri(const VctDynSkinArgs& a, int t) {
+    const VctTri9 rest = *reinterpret_cast<const VctTri9*>(a.rest + (size_t)t * 9);
+    VctTri9 out;
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+        const uint2 packed = reinterpret_cast<const uint2*>(a.bone)[(size_t)t * 3 + v];
+        const float4 w4 = reinterpret_cast<const float4*>(a.weight)[(size_t)t * 3 + v];
+        const uint32_t bone[4] = {packed.x & 0xffffu, packed.x >> 16, packed.y & 0xffffu, packed.y >> 16};
+        const float w[4] = {w4.x, w4.y, w4.z, w4.w};
+        float m[4][12];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float4* rows = a.table + 3 * (size_t)bone[i];
+            const float4 r0 = rows[0], r1 = rows[1], r2 = rows[2];
+            const float mi[12] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w};
+#pragma unroll
+            for (int j = 0; j < 12; ++j) m[i][j] = mi[j];
+        }
+        float B[12];
+#pragma unroll
+        for (int j = 0; j < 12; ++j) B[j] = ((w[0] * m[0][j] + w[1] * m[1][j]) + w[2] * m[2][j]) + w[3] * m[3][j];
+        const float x = rest.v[3 * v], y = rest.v[3 * v + 1], z = rest.v[3 * v + 2];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) out.v[3 * v + r] = ((B[4 * r] * x + B[4 * r + 1] * y) + B[4 * r + 2] * z) + B[4 * r + 3];
+    }
+    return out;
+}
+
 __global__ void __launch_bounds__(256)
-k_dyn_draw_prepare(const DynPrepareSrc<PARTS> pos, int ntri, float model_scale, float vertex_limit, float* __restrict__ draw_pos,
+k_dyn_skin(const VctDynSkinArgs a, int ntri) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= ntri) return;
+    *reinterpret_cast<VctTri9*>(a.pos + (size_t)t * 9) = dyn_skin_tri(a, t);
+}
+
+// what k_dyn_draw_prepare reads: the layer's positions, or what dyn_part_tri (DYN_SRC_PARTS) or dyn_skin_tri
+// (DYN_SRC_SKIN) needs to make and store them
+enum DynSrc { DYN_SRC_POS, DYN_SRC_PARTS, DYN_SRC_SKIN };
+template <DynSrc SRC> using DynPrepareSrc =
+    std::conditional_t<SRC == DYN_SRC_PARTS, VctDynPartsArgs, std::conditional_t<SRC == DYN_SRC_SKIN, VctDynSkinArgs, const float* __restrict__>>;
+template <DynSrc SRC = DYN_SRC_POS>
+__global__ void __launch_bounds__(256)
+k_dyn_draw_prepare(const DynPrepareSrc<SRC> pos, int ntri, float model_scale, float vertex_limit, float* __restrict__ draw_pos,
                    float* __restrict__ draw_nrm, float* __restrict__ draw_tan, float* __restrict__ draw_bit) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= ntri) return;
     VctTri9 q;
-    if constexpr (PARTS) {
+    if constexpr (SRC == DYN_SRC_PARTS) {
         q = dyn_part_tri(pos, t);
+        *reinterpret_cast<VctTri9*>(pos.pos + (size_t)t * 9) = q;
+    } else if constexpr (SRC == DYN_SRC_SKIN) {
+        q = dyn_skin_tri(pos, t);
         *reinterpret_cast<VctTri9*>(pos.pos + (size_t)t * 9) = q;
     } else {
         q = *reinterpret_cast<const VctTri9*>(pos + (size_t)t * 9);
@@ -2269,7 +2318,21 @@ hipError_t vct_launch_dynamic_transform(const VctDynPartsArgs& a, int32_t ntri, 
 hipError_t vct_launch_dynamic_transform_prepare(const VctDynPartsArgs& a, int32_t ntri, float model_scale, float vertex_limit,
                                                 float* draw_pos, float* draw_nrm, float* draw_tan, float* draw_bit, hipStream_t s) {
     if (ntri <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_dyn_draw_prepare<true>, dim3((ntri + 255) / 256), dim3(256), 0, s, a, ntri, model_scale, vertex_limit,
+    hipLaunchKernelGGL(k_dyn_draw_prepare<DYN_SRC_PARTS>, dim3((ntri + 255) / 256), dim3(256), 0, s, a, ntri, model_scale, vertex_limit,
+                       draw_pos, draw_nrm, draw_tan, draw_bit);
+    return hipGetLastError();
+}
+
+hipError_t vct_launch_dynamic_skin(const VctDynSkinArgs& a, int32_t ntri, hipStream_t s) {
+    if (ntri <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_dyn_skin, dim3((ntri + 255) / 256), dim3(256), 0, s, a, ntri);
+    return hipGetLastError();
+}
+
+hipError_t vct_launch_dynamic_skin_prepare(const VctDynSkinArgs& a, int32_t ntri, float model_scale, float vertex_limit,
+                                           float* draw_pos, float* draw_nrm, float* draw_tan, float* draw_bit, hipStream_t s) {
+    if (ntri <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_dyn_draw_prepare<DYN_SRC_SKIN>, dim3((ntri + 255) / 256), dim3(256), 0, s, a, ntri, model_scale, vertex_limit,
                        draw_pos, draw_nrm, draw_tan, draw_bit);
     return hipGetLastError();
 }

@@ -422,6 +422,14 @@ struct Voxel_Cone_Tracing {
         if (!ctx) return false;
         return check(vct_set_dynamic_parts(ctx, part, nparts), "vct_set_dynamic_parts");
     }
+    // A skin of the dynamic mesh (vct_set_dynamic_skin, include/vct.h "dynamic mesh", Skin): per triangle corner four bone
+    // indices in 0 .. nbones-1 and four weights ([ntri][3][4] each, used as given); UpdateDynamicTransforms then takes one
+    // 3 x 4 skinning matrix per bone.  After SetDynamicMesh, which drops the skin; not together with SetDynamicParts;
+    // bone == NULL with weight == NULL detaches.
+    bool SetDynamicSkin(const int32_t* bone, const float* weight, int32_t nbones) {
+        if (!ctx) return false;
+        return check(vct_set_dynamic_skin(ctx, bone, weight, nbones), "vct_set_dynamic_skin");
+    }
     bool UpdateDynamicTransforms(const float* m3x4, int32_t location = VCT_MEM_HOST) {
         if (!ctx) return false;
         return check(vct_update_dynamic_transforms(ctx, m3x4, location), "vct_update_dynamic_transforms");

@@ -13,7 +13,7 @@
 //            [--sky-gradient ZR,ZG,ZB;HR,HG,HB;GR,GG,GB[;UX,UY,UZ] | --sky-sh FILE] [--reimport]
 //            [--light X,Y,Z;R,G,B;RADIUS;SRC[;DX,DY,DZ;INNER_DEG;OUTER_DEG]]...
 //            [--dynamic-obj FILE --dynamic-path X0,Y0,Z0;X1,Y1,Z1 --dynamic-draw shadow|gbuffer|both --dynamic-bounce
-//             --dynamic-emission MATERIAL=R,G,B[;MATERIAL=R,G,B...] --dynamic-spin AX,AY,AZ;DEG_PER_FRAME]
+//             --dynamic-emission MATERIAL=R,G,B[;MATERIAL=R,G,B...] --dynamic-spin AX,AY,AZ;DEG_PER_FRAME | --dynamic-bend AX,AY,AZ;DEG_PER_FRAME]
 // --dynamic-obj FILE: a second Wavefront OBJ as the context's dynamic mesh (Voxel_Cone_Tracing::SetDynamicMesh,
 //   vct_set_dynamic_mesh; flat material colours, its textures are not used), translated along the segment of
 //   --dynamic-path (model units, the OBJ's own; default: it stays where it is) over the run's frames.  Every Render()
@@ -33,6 +33,11 @@
 //   (UpdateDynamicTransforms, vct_update_dynamic_transforms): the --dynamic-path translation at f composed with a rotation
 //   by f x DEG about the axis through the object's bounding-box centre, built in double and rounded once.  The per-frame
 //   position arrays are then not built.  Finite numbers and a non-zero axis, checked before a GPU is touched.
+//   --dynamic-bend AX,AY,AZ;DEG_PER_FRAME: the OBJ is skinned to two bones (Voxel_Cone_Tracing::SetDynamicSkin,
+//   vct_set_dynamic_skin) and frame f hands over two matrices: bone 0 the --dynamic-path translation alone, bone 1 that
+//   composed with a rotation by f x DEG about the axis through the object's bounding-box centre.  A corner's weight of
+//   bone 1 is clamp((c - lo) / (hi - lo), 0, 1) along the longest axis of the bounding box, bone 0 has the rest: the
+//   object bends.  Not with --dynamic-spin; checked like it.
 //
 // --light SPEC (repeatable, up to 64): a local light (Voxel_Cone_Tracing::SetLights, vct_set_lights) in world units: a point
 //   light at X,Y,Z of colour R,G,B (the factor at distance 1) that reaches RADIUS and whose inverse-square falloff is
@@ -182,6 +187,7 @@ int main(int argc, char** argv) {
     bool dynamic_bounce = false;
     const char* dynamic_emission = nullptr;
     const char* dynamic_spin = nullptr;
+    const char* dynamic_bend = nullptr;
     int cubes[3] = {0, 0, 0};
     bool show_voxels = false;
     int view_source = VCT_VOXVIEW_CURRENT, view_level = 0;
@@ -237,6 +243,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--dynamic-draw")) dynamic_draw = argv[++i];
         else if (!strcmp(argv[i], "--dynamic-emission")) dynamic_emission = argv[++i];
         else if (!strcmp(argv[i], "--dynamic-spin")) dynamic_spin = argv[++i];
+        else if (!strcmp(argv[i], "--dynamic-bend")) dynamic_bend = argv[++i];
         else if (!strcmp(argv[i], "--ambient-cubes") && i + 2 < argc) {
             if (sscanf(argv[++i], "%d,%d,%d", &cubes[0], &cubes[1], &cubes[2]) != 3 || cubes[0] < 1 || cubes[1] < 1 || cubes[2] < 1 ||
                 (long long)cubes[0] * cubes[1] * cubes[2] * 6 > VCT_POINT_QUERY_MAX) {
@@ -291,6 +298,14 @@ int main(int argc, char** argv) {
         if (!dynamic_obj) { fprintf(stderr, "--dynamic-spin: needs --dynamic-obj\n"); return 1; }
         if (!vct_demo_parse_dynamic_spin(dynamic_spin, spin_axis, &spin_deg)) { fprintf(stderr, "%s\n", VCT_DEMO_DYNAMIC_SPIN_USAGE); return 1; }
     }
+    if (dynamic_bend) {                                     // the spin's axis, angle and centre serve the bend's second bone
+        if (!dynamic_obj) { fprintf(stderr, "--dynamic-bend: needs --dynamic-obj\n"); return 1; }
+        if (dynamic_spin) { fprintf(stderr, "--dynamic-bend: not with --dynamic-spin (parts and a skin exclude each other)\n"); return 1; }
+        if (!vct_demo_parse_dynamic_bend(dynamic_bend, spin_axis, &spin_deg)) { fprintf(stderr, "%s\n", VCT_DEMO_DYNAMIC_BEND_USAGE); return 1; }
+    }
+    const bool dyn_by_matrix = dynamic_spin || dynamic_bend;      // a frame hands over matrices, not positions
+    const size_t dyn_nmatrices = dynamic_bend ? 2 : 1;
+    float dyn_lo[3] = {0.0f, 0.0f, 0.0f}, dyn_hi[3] = {0.0f, 0.0f, 0.0f};
     std::vector<float> dyn_emission;                        // [dyn_nmat][3]: the OBJ's Ke, then --dynamic-emission over it
     if (dynamic_obj) {
         if (gpus > 0 || (bounces >= 2 && !dynamic_bounce)) { fprintf(stderr, "--dynamic-obj: not with --gpus or --bounces 2\n"); return 1; }
@@ -325,11 +340,12 @@ int main(int argc, char** argv) {
                 fprintf(stderr, "%s; the OBJ has %d materials (at '%s')\n", VCT_DEMO_DYNAMIC_EMISSION_USAGE, (int)dyn_nmat, at);
                 return 1;
             }
-        if (dynamic_spin) {                                 // the axis goes through the centre of the object's bounding box
+        if (dyn_by_matrix) {                                // the axis goes through the centre of the object's bounding box
             for (int k = 0; k < 3; ++k) {
                 float lo = dyn_pos[(size_t)k], hi = lo;
                 for (size_t i = (size_t)k; i < dyn_pos.size(); i += 3) { lo = std::min(lo, dyn_pos[i]); hi = std::max(hi, dyn_pos[i]); }
                 spin_centre[k] = 0.5 * ((double)lo + (double)hi);
+                dyn_lo[k] = lo; dyn_hi[k] = hi;
             }
         }
         dynamic_light = true;                               // a whole GI pass per frame: the volume follows the object
@@ -442,29 +458,38 @@ int main(int argc, char** argv) {
     // --dynamic-obj: the object's positions for every frame of the run (an update is asynchronous: each frame's array
     // stays where it is until the run has finished), attached at the first
     // --dynamic-spin: no arrays -- the OBJ's own positions are the rest positions of one part, and a frame is 12 floats
-    // (one matrix per frame of the run, for the same reason)
+    // (one matrix per frame of the run, for the same reason); --dynamic-bend: the same with two matrices per frame
     std::vector<std::vector<float>> dyn_frames;
     const size_t dyn_nframes = (size_t)(frames > 1 ? frames : 1);
-    std::vector<float> dyn_matrices(dynamic_spin ? dyn_nframes * 12 : 0);
+    const size_t dyn_stride = dyn_nmatrices * 12;
+    std::vector<float> dyn_matrices(dyn_by_matrix ? dyn_nframes * dyn_stride : 0);
     if (dynamic_obj) {
-        for (size_t f = 0; f * 12 < dyn_matrices.size(); ++f) {
+        for (size_t f = 0; f * dyn_stride < dyn_matrices.size(); ++f) {
             const double t = dyn_nframes > 1 ? (double)f / (double)(dyn_nframes - 1) : 0.0;
             double move[3];
             for (int k = 0; k < 3; ++k) move[k] = (double)dyn_path[0][k] + t * ((double)dyn_path[1][k] - (double)dyn_path[0][k]);
-            vct_demo_spin_matrix(spin_axis, (double)f * spin_deg, spin_centre, move, &dyn_matrices[f * 12]);
+            float* m = &dyn_matrices[f * dyn_stride];
+            if (dynamic_bend) { vct_demo_spin_matrix(spin_axis, 0.0, spin_centre, move, m); m += 12; }      // bone 0 does not turn
+            vct_demo_spin_matrix(spin_axis, (double)f * spin_deg, spin_centre, move, m);
         }
-        dyn_frames.resize(dynamic_spin ? 0 : dyn_nframes);
+        dyn_frames.resize(dyn_by_matrix ? 0 : dyn_nframes);
         for (size_t f = 0; f < dyn_frames.size(); ++f) {
             const float t = dyn_frames.size() > 1 ? (float)f / (float)(dyn_frames.size() - 1) : 0.0f;
             dyn_frames[f] = dyn_pos;
             for (size_t i = 0; i < dyn_frames[f].size(); ++i)
                 dyn_frames[f][i] += dyn_path[0][i % 3] + t * (dyn_path[1][i % 3] - dyn_path[0][i % 3]);
         }
-        const float* first = dynamic_spin ? dyn_pos.data() : dyn_frames[0].data();
+        const float* first = dyn_by_matrix ? dyn_pos.data() : dyn_frames[0].data();
         if (!voxel_cone_tracing.SetDynamicMesh(first, dyn_material.data(), dyn_ntri, dyn_albedo.data(), dyn_nmat)) return 3;
         if (dynamic_spin) {
             const std::vector<int32_t> one_part((size_t)dyn_ntri, 0);
             if (!voxel_cone_tracing.SetDynamicParts(one_part.data(), 1)) return 3;
+        }
+        if (dynamic_bend) {
+            std::vector<int32_t> bone;
+            std::vector<float> weight;
+            vct_demo_bend_influences(dyn_pos.data(), (size_t)dyn_ntri, dyn_lo, dyn_hi, bone, weight);
+            if (!voxel_cone_tracing.SetDynamicSkin(bone.data(), weight.data(), 2)) return 3;
         }
         // the OBJ's Ke with --dynamic-emission over it (an all-zero table attaches nothing)
         if (!voxel_cone_tracing.SetDynamicEmission(dyn_emission.data(), (size_t)dyn_nmat)) return 3;
@@ -473,8 +498,8 @@ int main(int argc, char** argv) {
     }
     auto move_dynamic = [&](int f) {                        // frame f's positions, before its Render()
         if (!dynamic_obj) return true;
-        if (dynamic_spin) {
-            if (!voxel_cone_tracing.UpdateDynamicTransforms(&dyn_matrices[((size_t)f % dyn_nframes) * 12])) return false;
+        if (dyn_by_matrix) {
+            if (!voxel_cone_tracing.UpdateDynamicTransforms(&dyn_matrices[((size_t)f % dyn_nframes) * dyn_stride])) return false;
         } else if (!voxel_cone_tracing.UpdateDynamicMesh(dyn_frames[(size_t)f % dyn_frames.size()].data())) return false;
         if (bounces >= 2) {                                 // Render() is no whole pass then: the maps follow the object here
             voxel_cone_tracing.DrawDepthTexture();

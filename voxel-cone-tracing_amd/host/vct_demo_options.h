@@ -191,4 +191,33 @@ static inline void vct_demo_spin_matrix(const double axis[3], double degrees, co
     }
 }
 
+// --dynamic-bend AX,AY,AZ;DEG_PER_FRAME: the --dynamic-obj mesh skinned to TWO bones (vct_set_dynamic_skin) -- bone 0 the
+// identity, bone 1 a rotation about the axis through the object's bounding-box centre that grows by DEG_PER_FRAME per
+// frame -- so that the object bends along its longest axis.  The grammar and the checks are the spin's; the two exclude
+// each other.
+#define VCT_DEMO_DYNAMIC_BEND_USAGE "--dynamic-bend AX,AY,AZ;DEG_PER_FRAME (with --dynamic-obj, not with --dynamic-spin): finite numbers, a non-zero axis"
+static inline bool vct_demo_parse_dynamic_bend(const char* text, double axis[3], double* deg_per_frame) {
+    return vct_demo_parse_dynamic_spin(text, axis, deg_per_frame);
+}
+
+// The influences of the bend for positions [ntri][9] with bounding box lo .. hi: per corner bones (0, 1, 0, 0) and weights
+// (w0, w1, 0, 0) with w1 = clamp((c - lo) / (hi - lo), 0, 1) along the box's longest axis (c the corner's coordinate) and
+// w0 = 1 - w1.  The unused slots point at bone 0, which is in use.  A box without extent: w1 = 0.
+static inline void vct_demo_bend_influences(const float* pos, size_t ntri, const float lo[3], const float hi[3],
+                                            std::vector<int32_t>& bone, std::vector<float>& weight) {
+    int axis = 0;
+    for (int k = 1; k < 3; ++k)
+        if (hi[k] - lo[k] > hi[axis] - lo[axis]) axis = k;
+    const float extent = hi[axis] - lo[axis];
+    bone.assign(ntri * 12, 0);
+    weight.assign(ntri * 12, 0.0f);
+    for (size_t v = 0; v < ntri * 3; ++v) {
+        float w1 = extent > 0.0f ? (pos[3 * v + axis] - lo[axis]) / extent : 0.0f;
+        w1 = w1 < 0.0f ? 0.0f : (w1 > 1.0f ? 1.0f : w1);
+        bone[4 * v + 1] = 1;
+        weight[4 * v] = 1.0f - w1;
+        weight[4 * v + 1] = w1;
+    }
+}
+
 #endif

@@ -320,7 +320,7 @@ def test_draw_going_on_after_a_transform_draws_the_transformed_positions(vct, wo
             ctx.render_shadow_map(lvp)
             ctx.render_gbuffer(vp)
             return u32(ctx.download_shadow_map()), u32(ctx.download_gbuffer())
-        ctx.update_dynamic_transforms(dp.pose("P1"))      # flags off: k_dyn_transform, no draw copy yet
+        ctx.update_dynamic_transforms(dp.pose("P1"))      # flags off: k_dyn_move, no draw copy yet
         ctx.set_dynamic_draw(3)
         a = drawn()
         ctx.update_dynamic_positions(world["P1"])

@@ -339,6 +339,40 @@ def test_parts_and_skin_refuse_each_other(vct, world):
         assert ctx.dynamic_parts()[0] == dp.NPARTS
 
 
+@pytest.mark.parametrize("draw", [0, 3], ids=["plain", "prepare"])
+def test_table_and_timer_are_fresh_across_a_change_of_kind(vct, world, draw):
+    """The movers share one rest buffer, one matrix table and one timer: every attach -- of the other kind behind a detach,
+    or of the same kind again -- starts with a fresh rest snapshot and a timer that has not run."""
+    pos, mat, alb = world["mesh"]
+    bone, weight = world["bone"], world["weight"]
+    part = dp.parts(150)
+    with vct.Context(dc.config(vct)) as ctx:
+        ctx.set_trace_timing(True)
+        ctx.set_dynamic_draw(draw)
+        ctx.set_dynamic_mesh(pos, mat, alb, max_bricks=ds.MAX_BRICKS)
+        ctx.set_dynamic_skin(bone, weight, ds.NBONES)
+        ctx.update_dynamic_transforms(ds.pose("P1"))
+        assert ctx.last_dynamic_transform_ms() > 0.0
+        ctx.set_dynamic_skin(None, None)
+        refused(vct, ctx.last_dynamic_transform_ms)
+        ctx.update_dynamic_positions(pos)
+        ctx.set_dynamic_parts(part, dp.NPARTS)
+        refused(vct, ctx.last_dynamic_transform_ms)              # the skin's timer did not carry over
+        ctx.update_dynamic_transforms(dp.pose("P1"))
+        moved = dp.transform_ref(pos, part, dp.pose("P1"))
+        assert_positions(ctx, moved, "parts behind a skin")      # ... and neither did its table or its rest positions
+        assert ctx.last_dynamic_transform_ms() > 0.0
+        ctx.set_dynamic_parts(part, dp.NPARTS)                   # the same kind again: the moved positions are the rest
+        refused(vct, ctx.last_dynamic_transform_ms)
+        ctx.update_dynamic_transforms(dp.pose("P1"))
+        moved = dp.transform_ref(moved, part, dp.pose("P1"))
+        assert_positions(ctx, moved, "parts re-attached")
+        ctx.set_dynamic_parts(None)
+        ctx.set_dynamic_skin(bone, weight, ds.NBONES)
+        ctx.update_dynamic_transforms(ds.pose("P2"))
+        assert_positions(ctx, ds.skin_ref(moved, bone, weight, ds.pose("P2")), "a skin behind parts")
+
+
 def test_refusals_leave_everything_as_it_was(vct, world):
     pos, mat, alb = world["mesh"]
     bone, weight = world["bone"], world["weight"]

@@ -141,7 +141,8 @@ def parts_probe():
     without device-side transforms does), positions from device memory, and vct_update_dynamic_transforms with the mover as
     1 part and as 64 parts (each a 64th of the triangles, the same translation).  Per route update + voxelize + inject +
     mips as events, host time and wall time; the transform kernel's device time; with both draw flags on, the PARTS form of
-    the prepare kernel against k_dyn_transform followed by the plain prepare (events around the calls); and what NumPy
+    the prepare kernel against k_dyn_transform (k_dyn_move<DYN_SRC_PARTS> now; the printed label keeps the old name)
+    followed by the plain prepare (events around the calls); and what NumPy
     takes to move the vertices on the host.  A library without the entry point (the parent commit) runs the two positions
     routes only.  Writes dynamic_parts_probe.txt."""
     have = hasattr(ctx, "update_dynamic_transforms")

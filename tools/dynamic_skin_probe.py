@@ -8,7 +8,8 @@ point at the first with weight 0); bone b's matrix is the frame's translation an
 box twists.  Per mover, ROUNDS alternating rounds, medians with min and max:
   * the kernels, by vct_last_dynamic_transform_ms: k_dyn_skin (NB = 2, 64, 4096) and the skin form of the prepare kernel
     (both draw flags on) against k_dyn_transform and the PARTS prepare with 64 parts -- the arms alternate on the context,
-    each attaching its mover in turn;
+    each attaching its mover in turn (the kernels are k_dyn_move<DYN_SRC_SKIN> and k_dyn_move<DYN_SRC_PARTS> now; the
+    printed labels keep the old names so that new lines compare with the logged ones);
   * update + vct_voxelize + vct_inject_light + vct_build_mips as events, the host's time inside the calls, and the wall
     time to the end of the stream: matrices (NB = 64) against positions skinned by NumPy on the host (its time apart and
     included) against positions that are already in host memory.

@@ -851,18 +851,13 @@ class Context:
             self._ck(_lib.vct_update_dynamic_transforms(self._h, _ptr(m), MEM_DEVICE), "vct_update_dynamic_transforms")
             return
         m = np.ascontiguousarray(m, np.float32)
-        nbones = getattr(self, "_dyn_nbones", 0)
-        if nbones:
-            if not ((m.ndim == 2 and m.shape[1] == 12) or (m.ndim == 3 and m.shape[1:] == (3, 4))) or m.shape[0] != nbones:
-                raise VctError(f"update_dynamic_transforms: matrices of shape {tuple(m.shape)}, the attached skin has {nbones} "
-                               f"bones: [{nbones}, 12] or [{nbones}, 3, 4] is expected")
-            self._dyn_m = m          # stays alive until the stream has passed the copy
-            self._ck(_lib.vct_update_dynamic_transforms(self._h, _ptr(m), MEM_HOST), "vct_update_dynamic_transforms")
-            return
-        nparts = getattr(self, "_dyn_nparts", 0)
-        if not ((m.ndim == 2 and m.shape[1] == 12) or (m.ndim == 3 and m.shape[1:] == (3, 4))) or (nparts and m.shape[0] != nparts):
-            raise VctError(f"update_dynamic_transforms: matrices of shape {tuple(m.shape)}, the attached mesh has {nparts} "
-                           f"parts: [{nparts}, 12] or [{nparts}, 3, 4] is expected")
+        # a skin's bone count is always known here; a parts count of 0 is unknown to the binding: the library decides
+        n, owner, noun = getattr(self, "_dyn_nbones", 0), "skin", "bones"
+        if not n:
+            n, owner, noun = getattr(self, "_dyn_nparts", 0), "mesh", "parts"
+        if not ((m.ndim == 2 and m.shape[1] == 12) or (m.ndim == 3 and m.shape[1:] == (3, 4))) or (n and m.shape[0] != n):
+            raise VctError(f"update_dynamic_transforms: matrices of shape {tuple(m.shape)}, the attached {owner} has {n} "
+                           f"{noun}: [{n}, 12] or [{n}, 3, 4] is expected")
         self._dyn_m = m              # stays alive until the stream has passed the copy
         self._ck(_lib.vct_update_dynamic_transforms(self._h, _ptr(m), MEM_HOST), "vct_update_dynamic_transforms")
 

@@ -63,47 +63,85 @@ int launch_merge(vct_ctx* c, bool discard) {
     return VCT_OK;
 }
 
+// what the prepare kernels take beside the positions: the vertex contract and the draw arrays of layer `d`
+VctDynPrepare prepare_args(const vct_ctx* c, const VctDynamic& d) {
+    return {c->cfg.model_scale, vct_vertex_limit(c), d.draw.pos.get(), d.draw.nrm.get(), d.draw.tan.get(), d.draw.bit.get()};
+}
+
 // The draw copy and the face frames of layer `d` (vct_ctx.h VctDynamic): allocated if the layer has none, rebuilt from its
 // positions on stream s.  Called where the positions change or a draw flag goes on, never from a raster stage.
 int draw_prepare(vct_ctx* c, VctDynamic& d, hipStream_t s) {
     const size_t n = vct_dynamic_draw_floats(d.ntri);
     if (!d.draw.pos)
         for (VctBuf<float>* b : {&d.draw.nrm, &d.draw.tan, &d.draw.bit, &d.draw.pos}) HIP_TRY(c, b->alloc(n));      // (pos last: it says "all four")
-    HIP_TRY(c, vct_launch_dynamic_draw_prepare(d.pos.get(), d.ntri, c->cfg.model_scale, vct_vertex_limit(c),
-                                               d.draw.pos.get(), d.draw.nrm.get(), d.draw.tan.get(), d.draw.bit.get(), s));
+    HIP_TRY(c, vct_launch_dynamic_draw_prepare(d.pos.get(), d.ntri, prepare_args(c, d), s));
     return VCT_OK;
 }
 
-// The layer's positions from its rest positions and the matrix table on stream s: k_dyn_transform, or -- drawn -- the PARTS
-// form of the prepare kernel, which goes on to the draw copy and the frames.  The draw arrays exist whenever a flag is on
-// and a mesh is attached (vct_set_dynamic_mesh, vct_set_dynamic_draw), so nothing is allocated here.
-// With a skin attached instead of parts: k_dyn_skin and the skin form of the prepare kernel.
+// The layer's positions from the mover's rest positions and matrix table on stream s: the plain kernel, or -- drawn -- the
+// mover's form of the prepare kernel, which goes on to the draw copy and the frames.  The draw arrays exist whenever a
+// flag is on and a mesh is attached (vct_set_dynamic_mesh, vct_set_dynamic_draw), so nothing is allocated here.
 int transform(vct_ctx* c, VctDynamic& d, hipStream_t s) {
-    if (d.skin.n) {
-        const VctDynSkinArgs k = {d.skin.rest.get(), d.skin.bone.get(), d.skin.weight.get(), d.xform.m.get(), d.pos.get()};
-        if (c->dyn_settings.draw_flags && d.draw.pos)
-            HIP_TRY(c, vct_launch_dynamic_skin_prepare(k, d.ntri, c->cfg.model_scale, vct_vertex_limit(c),
-                                                       d.draw.pos.get(), d.draw.nrm.get(), d.draw.tan.get(), d.draw.bit.get(), s));
-        else
-            HIP_TRY(c, vct_launch_dynamic_skin(k, d.ntri, s));
-        return VCT_OK;
-    }
-    const VctDynPartsArgs a = {d.parts.rest.get(), d.parts.part.get(), d.xform.m.get(), d.pos.get()};
-    if (c->dyn_settings.draw_flags && d.draw.pos)
-        HIP_TRY(c, vct_launch_dynamic_transform_prepare(a, d.ntri, c->cfg.model_scale, vct_vertex_limit(c),
-                                                        d.draw.pos.get(), d.draw.nrm.get(), d.draw.tan.get(), d.draw.bit.get(), s));
-    else
-        HIP_TRY(c, vct_launch_dynamic_transform(a, d.ntri, s));
+    const VctDynamic::Mover& v = d.mover;
+    VctDynMoverArgs a = {};
+    a.is_skin = v.kind == VCT_MOVER_SKIN;
+    if (a.is_skin) a.skin = {v.rest.get(), v.bone.get(), v.weight.get(), v.m.get(), d.pos.get()};
+    else a.parts = {v.rest.get(), v.part.get(), v.m.get(), d.pos.get()};
+    const VctDynPrepare p = prepare_args(c, d);
+    HIP_TRY(c, vct_launch_dynamic_move(a, d.ntri, c->dyn_settings.draw_flags && d.draw.pos ? &p : nullptr, s));
     return VCT_OK;
 }
 
-// The movers' rule (vct_feature_rules.h): attaching `wanted` while the other mover is attached is refused.
-int refuse_other_mover(vct_ctx* c, const char* who, VctMover wanted) {
-    const VctDynamic& d = c->dyn;
-    const VctMover hit = vct_mover_conflict(d.parts.n ? VCT_MOVER_PARTS : d.skin.n ? VCT_MOVER_SKIN : VCT_MOVER_NONE, wanted);
-    if (hit == VCT_MOVER_NONE) return VCT_OK;
-    return vct_fail(c, VCT_ERR_INVALID, std::string(who) + ": " + kVctMoverText[wanted].name + " and " + kVctMoverText[hit].name +
-                                            " do not go together on one mesh (" + kVctMoverText[hit].lift + " lifts it)");
+// What an attach needs beside the kind's own arrays: byte counts of vct_dynamic_parts_sizes / vct_dynamic_skin_sizes.
+struct MoverSizes {
+    bool ok;
+    size_t rest, table;
+};
+
+// Attaches a mover of `kind` with n matrices to the attached mesh, in place of one of the same kind; the other kind attached
+// is refused (vct_feature_rules.h).  fill(mover, stream) allocates and copies the kind's own arrays.  All or nothing:
+// everything in a local; the context keeps what it had until the last call below has succeeded.
+template <class Fill>
+int attach_mover(vct_ctx* c, const char* who, VctMover kind, int32_t n, const MoverSizes& z, Fill fill) {
+    VctDynamic& d = c->dyn;
+    const VctMover hit = vct_mover_conflict(d.mover.kind, kind);
+    if (hit != VCT_MOVER_NONE)
+        return vct_fail(c, VCT_ERR_INVALID, std::string(who) + ": " + kVctMoverText[kind].name + " and " + kVctMoverText[hit].name +
+                                                " do not go together on one mesh (" + kVctMoverText[hit].lift + " lifts it)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    PIPE_TRY(vct_synchronize(c));         // an update in flight reads all of the previous mover's buffers
+    if (!z.ok) return vct_fail(c, VCT_ERR_INVALID, std::string(who) + ": buffer sizes overflow");
+    hipStream_t s = cur(c).stream.get();
+    VctDynamic::Mover v;
+    HIP_TRY(c, alloc_bytes(v.rest, z.rest));
+    HIP_TRY(c, v.timer.create());         // the events now, so that no update allocates
+    // the rest positions: what the last vct_set_dynamic_mesh or vct_update_dynamic_positions -- or transform -- put there
+    HIP_TRY(c, hipMemcpyAsync(v.rest.get(), d.pos.get(), z.rest, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(c, fill(v, s));
+    HIP_TRY(c, alloc_filled(v.m, z.table, 0, s));
+    HIP_TRY(c, hipStreamSynchronize(s));  // the caller's arrays are free again
+    v.kind = kind;
+    v.n = n;
+    d.mover = std::move(v);
+    return VCT_OK;
+}
+
+// Detaches the mover if it is of `kind` -- the other kind, or none, attached: nothing to do.  The current positions stay.
+int detach_mover(vct_ctx* c, const char* who, VctMover kind) {
+    VctDynamic& d = c->dyn;
+    if (!d.attached()) return vct_fail(c, VCT_ERR_INVALID, std::string(who) + ": no dynamic mesh attached");
+    if (d.mover.kind != kind) return VCT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    PIPE_TRY(vct_synchronize(c));         // an update in flight reads all of its buffers
+    d.mover = VctDynamic::Mover();
+    return VCT_OK;
+}
+
+// `bytes` bytes of a caller's array into a fresh allocation of `b` on stream s
+template <class T>
+hipError_t alloc_copied(VctBuf<T>& b, const void* src, size_t bytes, hipStream_t s) {
+    const hipError_t e = alloc_bytes(b, bytes);
+    return e == hipSuccess ? hipMemcpyAsync(b.get(), src, bytes, hipMemcpyHostToDevice, s) : e;
 }
 
 }  // namespace
@@ -252,131 +290,78 @@ int vct_update_dynamic_positions(vct_ctx* c, const float* pos, int32_t location)
     HIP_TRY(c, hipMemcpyAsync(c->dyn.pos.get(), pos, (size_t)c->dyn.ntri * 9 * sizeof(float),
                               location == VCT_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, cur(c).stream.get()));
     if (c->dyn.matrices())                // parts or a skin attached: these positions are the new rest positions as well
-        HIP_TRY(c, hipMemcpyAsync(c->dyn.parts.n ? c->dyn.parts.rest.get() : c->dyn.skin.rest.get(), c->dyn.pos.get(),
-                                  (size_t)c->dyn.ntri * 9 * sizeof(float), hipMemcpyDeviceToDevice, cur(c).stream.get()));
+        HIP_TRY(c, hipMemcpyAsync(c->dyn.mover.rest.get(), c->dyn.pos.get(), (size_t)c->dyn.ntri * 9 * sizeof(float),
+                                  hipMemcpyDeviceToDevice, cur(c).stream.get()));
     return vct_dynamic_draw_prepare(c);   // behind the copy, on its stream: ordered before every stage that draws the mesh
 }
 
 int vct_set_dynamic_parts(vct_ctx* c, const int32_t* part, int32_t nparts) {
     if (!c) return VCT_ERR_INVALID;
-    VctDynamic& d = c->dyn;
-    const bool detach = !part && nparts == 0;
-    if (detach && !d.attached()) return vct_fail(c, VCT_ERR_INVALID, "vct_set_dynamic_parts: no dynamic mesh attached");
-    if (!detach) {
-        int32_t bad = -1;
-        if (const char* why = vct_dynamic_check_parts(d.attached(), part, d.ntri, nparts, &bad)) {
-            if (bad < 0) return vct_fail(c, VCT_ERR_INVALID, std::string("vct_set_dynamic_parts: ") + why);
-            char msg[160];
-            snprintf(msg, sizeof msg, "vct_set_dynamic_parts: part index %d of triangle %d is outside 0 .. %d", (int)part[bad],
-                     (int)bad, (int)nparts - 1);
-            return vct_fail(c, VCT_ERR_INVALID, msg);
-        }
-        PIPE_TRY(refuse_other_mover(c, "vct_set_dynamic_parts", VCT_MOVER_PARTS));
+    const VctDynamic& d = c->dyn;
+    if (!part && nparts == 0) return detach_mover(c, "vct_set_dynamic_parts", VCT_MOVER_PARTS);
+    int32_t bad = -1;
+    if (const char* why = vct_dynamic_check_parts(d.attached(), part, d.ntri, nparts, &bad)) {
+        if (bad < 0) return vct_fail(c, VCT_ERR_INVALID, std::string("vct_set_dynamic_parts: ") + why);
+        char msg[160];
+        snprintf(msg, sizeof msg, "vct_set_dynamic_parts: part index %d of triangle %d is outside 0 .. %d", (int)part[bad],
+                 (int)bad, (int)nparts - 1);
+        return vct_fail(c, VCT_ERR_INVALID, msg);
     }
-    if (detach && !d.parts.n) return VCT_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    PIPE_TRY(vct_synchronize(c));         // a transform in flight reads all three buffers
-    if (detach) {                         // the current positions stay as they are
-        d.parts = VctDynamic::Parts();
-        d.xform = VctDynamic::Xform();
-        return VCT_OK;
-    }
-    // all or nothing: everything in locals; the context keeps what it had until the last call below has succeeded
     const VctDynamicPartsSizes z = vct_dynamic_parts_sizes(d.ntri, nparts);
-    if (!z.ok) return vct_fail(c, VCT_ERR_INVALID, "vct_set_dynamic_parts: buffer sizes overflow");
-    hipStream_t s = cur(c).stream.get();
-    VctDynamic::Parts p;
-    VctDynamic::Xform x;
-    HIP_TRY(c, alloc_bytes(p.rest, z.rest));
-    HIP_TRY(c, alloc_bytes(p.part, z.part));
-    HIP_TRY(c, x.timer.create());         // the events now, so that no update allocates
-    // the rest positions: what the last vct_set_dynamic_mesh or vct_update_dynamic_positions -- or transform -- put there
-    HIP_TRY(c, hipMemcpyAsync(p.rest.get(), d.pos.get(), z.rest, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(p.part.get(), part, z.part, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, alloc_filled(x.m, z.table, 0, s));
-    HIP_TRY(c, hipStreamSynchronize(s));  // the caller's array is free again
-    p.n = nparts;
-    d.parts = std::move(p);
-    d.xform = std::move(x);
-    return VCT_OK;
+    return attach_mover(c, "vct_set_dynamic_parts", VCT_MOVER_PARTS, nparts, {z.ok, z.rest, z.table},
+                        [&](VctDynamic::Mover& v, hipStream_t s) { return alloc_copied(v.part, part, z.part, s); });
 }
 
 int vct_get_dynamic_parts(vct_ctx* c, int32_t* nparts, int32_t* part) {
     if (!c || !nparts) return VCT_ERR_INVALID;
     const VctDynamic& d = c->dyn;
-    *nparts = d.parts.n;
-    if (!d.parts.n || !part) return VCT_OK;
+    *nparts = d.mover.kind == VCT_MOVER_PARTS ? d.mover.n : 0;
+    if (!*nparts || !part) return VCT_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpy(part, d.parts.part.get(), (size_t)d.ntri * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(part, d.mover.part.get(), (size_t)d.ntri * sizeof(int32_t), hipMemcpyDeviceToHost));
     return VCT_OK;
 }
 
 int vct_set_dynamic_skin(vct_ctx* c, const int32_t* bone, const float* weight, int32_t nbones) {
     if (!c) return VCT_ERR_INVALID;
-    VctDynamic& d = c->dyn;
-    const bool detach = !bone && !weight && nbones == 0;
-    if (detach && !d.attached()) return vct_fail(c, VCT_ERR_INVALID, "vct_set_dynamic_skin: no dynamic mesh attached");
-    if (!detach) {
-        size_t bad = 0;
-        if (const char* why = vct_dynamic_check_skin(d.attached(), bone, weight, d.ntri, nbones, &bad)) {
-            if (bad == (size_t)-1) return vct_fail(c, VCT_ERR_INVALID, std::string("vct_set_dynamic_skin: ") + why);
-            char msg[200];
-            const int tri = (int)(bad / 12), corner = (int)(bad / 4 % 3), slot = (int)(bad % 4);
-            if (bone[bad] < 0 || bone[bad] >= nbones)
-                snprintf(msg, sizeof msg, "vct_set_dynamic_skin: bone index %d of triangle %d, corner %d, slot %d is outside 0 .. %d",
-                         (int)bone[bad], tri, corner, slot, (int)nbones - 1);
-            else
-                snprintf(msg, sizeof msg, "vct_set_dynamic_skin: weight %g of triangle %d, corner %d, slot %d is not finite",
-                         (double)weight[bad], tri, corner, slot);
-            return vct_fail(c, VCT_ERR_INVALID, msg);
-        }
-        PIPE_TRY(refuse_other_mover(c, "vct_set_dynamic_skin", VCT_MOVER_SKIN));
+    const VctDynamic& d = c->dyn;
+    if (!bone && !weight && nbones == 0) return detach_mover(c, "vct_set_dynamic_skin", VCT_MOVER_SKIN);
+    size_t bad = 0;
+    if (const char* why = vct_dynamic_check_skin(d.attached(), bone, weight, d.ntri, nbones, &bad)) {
+        if (bad == (size_t)-1) return vct_fail(c, VCT_ERR_INVALID, std::string("vct_set_dynamic_skin: ") + why);
+        char msg[200];
+        const int tri = (int)(bad / 12), corner = (int)(bad / 4 % 3), slot = (int)(bad % 4);
+        if (bone[bad] < 0 || bone[bad] >= nbones)
+            snprintf(msg, sizeof msg, "vct_set_dynamic_skin: bone index %d of triangle %d, corner %d, slot %d is outside 0 .. %d",
+                     (int)bone[bad], tri, corner, slot, (int)nbones - 1);
+        else
+            snprintf(msg, sizeof msg, "vct_set_dynamic_skin: weight %g of triangle %d, corner %d, slot %d is not finite",
+                     (double)weight[bad], tri, corner, slot);
+        return vct_fail(c, VCT_ERR_INVALID, msg);
     }
-    if (detach && !d.skin.n) return VCT_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    PIPE_TRY(vct_synchronize(c));         // a skin kernel in flight reads all four buffers
-    if (detach) {                         // the current positions stay as they are
-        d.skin = VctDynamic::Skin();
-        d.xform = VctDynamic::Xform();
-        return VCT_OK;
-    }
-    // all or nothing: everything in locals; the context keeps what it had until the last call below has succeeded
     const VctDynamicSkinSizes z = vct_dynamic_skin_sizes(d.ntri, nbones);
-    if (!z.ok) return vct_fail(c, VCT_ERR_INVALID, "vct_set_dynamic_skin: buffer sizes overflow");
     std::vector<uint16_t> packed((size_t)d.ntri * 12);      // checked above: every index is below nbones <= 2^16
     for (size_t i = 0; i < packed.size(); ++i) packed[i] = (uint16_t)bone[i];
-    hipStream_t s = cur(c).stream.get();
-    VctDynamic::Skin k;
-    VctDynamic::Xform x;
-    HIP_TRY(c, alloc_bytes(k.rest, z.rest));
-    HIP_TRY(c, alloc_bytes(k.bone, z.bone));
-    HIP_TRY(c, alloc_bytes(k.weight, z.weight));
-    HIP_TRY(c, x.timer.create());         // the events now, so that no update allocates
-    // the rest positions: what the last vct_set_dynamic_mesh or vct_update_dynamic_positions -- or transform -- put there
-    HIP_TRY(c, hipMemcpyAsync(k.rest.get(), d.pos.get(), z.rest, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(k.bone.get(), packed.data(), z.bone, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(k.weight.get(), weight, z.weight, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, alloc_filled(x.m, z.table, 0, s));
-    HIP_TRY(c, hipStreamSynchronize(s));  // the caller's arrays and the packed copy are free again
-    k.n = nbones;
-    d.skin = std::move(k);
-    d.xform = std::move(x);
-    return VCT_OK;
+    return attach_mover(c, "vct_set_dynamic_skin", VCT_MOVER_SKIN, nbones, {z.ok, z.rest, z.table},
+                        [&](VctDynamic::Mover& v, hipStream_t s) {      // (the attach waits for the stream: `packed` outlives the copy)
+                            const hipError_t e = alloc_copied(v.bone, packed.data(), z.bone, s);
+                            return e == hipSuccess ? alloc_copied(v.weight, weight, z.weight, s) : e;
+                        });
 }
 
 int vct_get_dynamic_skin(vct_ctx* c, int32_t* nbones, int32_t* bone, float* weight) {
     if (!c || !nbones) return VCT_ERR_INVALID;
     const VctDynamic& d = c->dyn;
-    *nbones = d.skin.n;
-    if (!d.skin.n) return VCT_OK;
+    *nbones = d.mover.kind == VCT_MOVER_SKIN ? d.mover.n : 0;
+    if (!*nbones) return VCT_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t n = (size_t)d.ntri * 12;
     if (bone) {
         std::vector<uint16_t> packed(n);
-        HIP_TRY(c, hipMemcpy(packed.data(), d.skin.bone.get(), n * sizeof(uint16_t), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(packed.data(), d.mover.bone.get(), n * sizeof(uint16_t), hipMemcpyDeviceToHost));
         for (size_t i = 0; i < n; ++i) bone[i] = (int32_t)packed[i];
     }
-    if (weight) HIP_TRY(c, hipMemcpy(weight, d.skin.weight.get(), n * sizeof(float), hipMemcpyDeviceToHost));
+    if (weight) HIP_TRY(c, hipMemcpy(weight, d.mover.weight.get(), n * sizeof(float), hipMemcpyDeviceToHost));
     return VCT_OK;
 }
 
@@ -388,11 +373,11 @@ int vct_update_dynamic_transforms(vct_ctx* c, const float* m, int32_t location) 
     HIP_TRY(c, hipSetDevice(c->device));
     PIPE_TRY(vct_pipeline_join(c));       // positions and table are shared: the other slot's pass may still read the positions
     hipStream_t s = cur(c).stream.get();
-    HIP_TRY(c, hipMemcpyAsync(d.xform.m.get(), m, (size_t)d.matrices() * 12 * sizeof(float),
+    HIP_TRY(c, hipMemcpyAsync(d.mover.m.get(), m, (size_t)d.matrices() * 12 * sizeof(float),
                               location == VCT_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-    HIP_TRY(c, d.xform.timer.begin(s, c->time_traces));
+    HIP_TRY(c, d.mover.timer.begin(s, c->time_traces));
     PIPE_TRY(transform(c, d, s));
-    HIP_TRY(c, d.xform.timer.end(s));
+    HIP_TRY(c, d.mover.timer.end(s));
     return VCT_OK;
 }
 
@@ -411,8 +396,8 @@ int vct_last_dynamic_transform_ms(vct_ctx* c, float* ms) {
     if (!c || !ms) return VCT_ERR_INVALID;
     const char* never = "vct_last_dynamic_transform_ms: needs parts or a skin attached and a vct_update_dynamic_transforms since";
     const char* untimed = "vct_last_dynamic_transform_ms: the last transform was issued with timing off (vct_set_trace_timing)";
-    if (!c->dyn.matrices() || !c->dyn.xform.timer.have) return vct_fail(c, VCT_ERR_INVALID, never);
-    return vct_timer_ms(c, c->dyn.xform.timer, ms, never, untimed);
+    if (!c->dyn.matrices() || !c->dyn.mover.timer.have) return vct_fail(c, VCT_ERR_INVALID, never);
+    return vct_timer_ms(c, c->dyn.mover.timer, ms, never, untimed);
 }
 
 int vct_set_dynamic_draw(vct_ctx* c, int32_t flags, const float specular[3]) {

@@ -494,31 +494,24 @@ struct VctDynamic {
         VctBuf<float> table;            // [nmat][4] (rgb, 0)
         VctBuf<unsigned long long> acc; // [max_bricks][512][2]
     } emis;
-    // Rigid parts (vct_set_dynamic_parts): a part index per triangle and the rest positions the matrices move, both or
-    // none (n == 0).  They belong to the mesh like the emission table.  While attached, `pos` is rest x matrices of the
-    // last vct_update_dynamic_transforms (or the rest itself behind a vct_update_dynamic_positions).
-    struct Parts {
-        int32_t n = 0;
-        VctBuf<float> rest;             // [ntri][9]
-        VctBuf<int32_t> part;           // [ntri] in 0 .. n-1, checked on the host
-    } parts;
-    // A skin (vct_set_dynamic_skin): four bone indices and four weights per triangle corner and the rest positions, all
-    // three or none (n == 0: no bones).  Parts and a skin exclude each other (vct_feature_rules.h, movers).
-    struct Skin {
-        int32_t n = 0;
-        VctBuf<float> rest;             // [ntri][9]
-        VctBuf<uint16_t> bone;          // [ntri][3][4] in 0 .. n-1, checked on the host and packed: 24 bytes per triangle
-        VctBuf<float> weight;           // [ntri][3][4] finite, checked on the host
-    } skin;
-    // What the attached mover -- the parts or the skin -- hands to vct_update_dynamic_transforms: the context's own copy of
-    // the matrices, one per part or bone, and the timer of the kernel.  Allocated with the mover, dropped with it.
-    struct Xform {
-        VctBuf<float4> m;               // [n][3] rows of the matrices: 16-byte aligned, as the kernels load them
+    // The mover (vct_feature_rules.h): rigid parts (vct_set_dynamic_parts) or a skin (vct_set_dynamic_skin), one at a time.
+    // All of it or none (VCT_MOVER_NONE, n == 0): it belongs to the mesh like the emission table and is dropped on attach,
+    // replace and detach of the mesh.  While attached, `pos` is `rest` moved by the matrices of the last
+    // vct_update_dynamic_transforms (or the rest itself behind a vct_update_dynamic_positions).
+    struct Mover {
+        VctMover kind = VCT_MOVER_NONE;
+        int32_t n = 0;                  // parts or bones: the matrices vct_update_dynamic_transforms takes
+        VctBuf<float> rest;             // [ntri][9] the positions at the attach or of the last vct_update_dynamic_positions
+        VctBuf<float4> m;               // [n][3] rows of the matrices, the context's own copy: 16-byte aligned, as the kernels load them
         VctTimer timer;                 // vct_last_dynamic_transform_ms
-    } xform;
+        // the kind's own arrays, checked on the host; those of the other kind stay empty
+        VctBuf<int32_t> part;           // parts: [ntri] in 0 .. n-1
+        VctBuf<uint16_t> bone;          // skin: [ntri][3][4] in 0 .. n-1, packed: 24 bytes per triangle
+        VctBuf<float> weight;           // skin: [ntri][3][4] finite
+    } mover;
 
     bool attached() const { return ntri > 0; }
-    int32_t matrices() const { return parts.n ? parts.n : skin.n; }      // what vct_update_dynamic_transforms takes; 0: no mover
+    int32_t matrices() const { return mover.n; }      // what vct_update_dynamic_transforms takes; 0: no mover
 };
 
 struct vct_ctx {

@@ -542,25 +542,23 @@ hipError_t vct_launch_dynamic_visibility(const VctRasterArgs& a, const float vie
 // k_dyn_draw_prepare, one thread per dynamic triangle: the draw copy of `pos` (a triangle with a coordinate v for which
 // !(fabsf(v * model_scale) <= vertex_limit) becomes nine zeros -- a point, culled by the set-up) and the face frame
 // (u, t, b) = vct_import_frame(cross(p1 - p0, p2 - p0)), written to all three vertices of draw_nrm / _tan / _bit.
-hipError_t vct_launch_dynamic_draw_prepare(const float* pos, int32_t ntri, float model_scale, float vertex_limit, float* draw_pos,
-                                           float* draw_nrm, float* draw_tan, float* draw_bit, hipStream_t s);
+struct VctDynPrepare {
+    float model_scale, vertex_limit;
+    float *draw_pos, *draw_nrm, *draw_tan, *draw_bit;      // [ntri][9] each
+};
+hipError_t vct_launch_dynamic_draw_prepare(const float* pos, int32_t ntri, const VctDynPrepare& prepare, hipStream_t s);
 // Parts of the dynamic mesh (include/vct.h "dynamic mesh", Parts): pos[t] = the rest triangle t moved by the 3 x 4 matrix
-// table[3 * part[t] ..] -- k_dyn_transform, one thread per triangle -- and, in the _prepare form, the draw copy and the
-// frames of the new positions in the same launch (the PARTS instantiation of k_dyn_draw_prepare).  part[t] was checked
-// on the host; the table is the library's own allocation, so its rows are 16-byte aligned.
+// table[3 * part[t] ..].  part[t] was checked on the host; the table is the library's own allocation, so its rows are
+// 16-byte aligned.  (This struct and the skin's are kernel arguments: their layout is the kernels' scalar loads.)
 struct VctDynPartsArgs {
     const float* rest;           // [ntri][9]
     const int32_t* part;         // [ntri] in 0 .. nparts-1
     const float4* table;         // [nparts][3] rows of the matrices
     float* pos;                  // [ntri][9] the layer's current positions
 };
-hipError_t vct_launch_dynamic_transform(const VctDynPartsArgs& a, int32_t ntri, hipStream_t s);
-hipError_t vct_launch_dynamic_transform_prepare(const VctDynPartsArgs& a, int32_t ntri, float model_scale, float vertex_limit,
-                                                float* draw_pos, float* draw_nrm, float* draw_tan, float* draw_bit, hipStream_t s);
 // A skin of the dynamic mesh (include/vct.h "dynamic mesh", Skin): pos[t] = the rest triangle t, each corner moved by
-// the blend of four rows of the table with the corner's four weights -- k_dyn_skin, one thread per triangle -- and, in
-// the _prepare form, the draw copy and the frames in the same launch (the skin instantiation of k_dyn_draw_prepare).
-// The indices were checked on the host against the table's rows and packed; all four arrays are the library's own.
+// the blend of four rows of the table with the corner's four weights.  The indices were checked on the host against the
+// table's rows and packed; all four arrays are the library's own.
 struct VctDynSkinArgs {
     const float* rest;           // [ntri][9]
     const uint16_t* bone;        // [ntri][3][4] in 0 .. nbones-1
@@ -568,9 +566,15 @@ struct VctDynSkinArgs {
     const float4* table;         // [nbones][3] rows of the matrices
     float* pos;                  // [ntri][9] the layer's current positions
 };
-hipError_t vct_launch_dynamic_skin(const VctDynSkinArgs& a, int32_t ntri, hipStream_t s);
-hipError_t vct_launch_dynamic_skin_prepare(const VctDynSkinArgs& a, int32_t ntri, float model_scale, float vertex_limit,
-                                           float* draw_pos, float* draw_nrm, float* draw_tan, float* draw_bit, hipStream_t s);
+// The attached mover's update, one thread per triangle: the arguments of its kind (host side only; a kernel takes the
+// one that is in use) into k_dyn_move, or -- `prepare` not null -- into the kind's instantiation of k_dyn_draw_prepare,
+// which stores the positions and goes on to the draw copy and the frames in the same launch.
+struct VctDynMoverArgs {
+    bool is_skin;
+    VctDynPartsArgs parts;       // !is_skin
+    VctDynSkinArgs skin;         // is_skin
+};
+hipError_t vct_launch_dynamic_move(const VctDynMoverArgs& a, int32_t ntri, const VctDynPrepare* prepare, hipStream_t s);
 // one level of a texture's mip chain from its parent (pw x ph -> w x h), glGenerateMipmap restated as in the oracle
 hipError_t vct_launch_tri_alpha(const VctRasterArgs& a, int32_t* out, hipStream_t s);
 hipError_t vct_launch_tex_mip(const uint32_t* parent, int pw, int ph, uint32_t* level, int w, int h, hipStream_t s);

@@ -2025,19 +2025,20 @@ k_tex_mip(const uint32_t* __restrict__ parent, int pw, int ph, uint32_t* __restr
 //
 // Parts (include/vct.h "dynamic mesh", Parts): dyn_transform_tri is the one place that holds the arithmetic -- per vertex
 // and row r, ((M[4r] * x + M[4r+1] * y) + M[4r+2] * z) + M[4r+3], every product and sum rounded (the build does not
-// contract).  dyn_part_tri reads a rest triangle, its part index -- checked on the host, the array is the library's own --
-// and the part's matrix as three 16-byte loads from the library's aligned table: neighbouring triangles mostly share a
-// part, so the rows come from the cache, not from LDS.  k_dyn_transform is the update with no draw flag on; with one on
-// the PARTS (DYN_SRC_PARTS) instantiation of k_dyn_draw_prepare does the same, stores the positions and goes on to the draw copy and the
-// frames from the registers: one launch and one read of the positions instead of two.
+// contract).  dyn_moved_tri of the parts reads a rest triangle, its part index -- checked on the host, the array is the
+// library's own -- and the part's matrix as three 16-byte loads from the library's aligned table: neighbouring triangles
+// mostly share a part, so the rows come from the cache, not from LDS.
 //
-// Skin (include/vct.h "dynamic mesh", Skin): dyn_skin_tri is the one place that holds its arithmetic -- per corner the
+// Skin (include/vct.h "dynamic mesh", Skin): dyn_moved_tri of the skin is the one place that holds its arithmetic -- per corner the
 // blend B[j] = ((w0 * M0[j] + w1 * M1[j]) + w2 * M2[j]) + w3 * M3[j] of the four named bones' matrices, all four terms
 // always (a weight of 0 does not skip its bone), then the row expression above on B.  Per corner it reads four packed
 // uint16 indices as one 8-byte load, four weights as one 16-byte load and, per influence, three 16-byte rows of the
 // library's aligned table, served from the cache like a part's.  The indices were checked against the table's rows on the
-// host before they were packed, and 65535 is the last row a full table has.  k_dyn_skin is the update with no draw flag
-// on; with one on the DYN_SRC_SKIN instantiation of k_dyn_draw_prepare goes on to the draw copy and the frames.
+// host before they were packed, and 65535 is the last row a full table has.
+//
+// k_dyn_move<DYN_SRC_PARTS or _SKIN> is the mover's update with no draw flag on; with one on the same instantiation of
+// k_dyn_draw_prepare makes the triangle, stores the positions and goes on to the draw copy and the frames from the
+// registers: one launch and one read of the positions instead of two.
 __device__ __forceinline__ VctTri9 dyn_transform_tri(const VctTri9& rest, const float (&m)[12]) {
     VctTri9 out;
 #pragma unroll
@@ -2049,7 +2050,7 @@ __device__ __forceinline__ VctTri9 dyn_transform_tri(const VctTri9& rest, const 
     return out;
 }
 
-__device__ __forceinline__ VctTri9 dyn_part_tri(const VctDynPartsArgs& a, int t) {
+__device__ __forceinline__ VctTri9 dyn_moved_tri(const VctDynPartsArgs& a, int t) {
     const VctTri9 rest = *reinterpret_cast<const VctTri9*>(a.rest + (size_t)t * 9);
     const float4* rows = a.table + 3 * (size_t)a.part[t];
     const float4 r0 = rows[0], r1 = rows[1], r2 = rows[2];
@@ -2057,14 +2058,7 @@ __device__ __forceinline__ VctTri9 dyn_part_tri(const VctDynPartsArgs& a, int t)
     return dyn_transform_tri(rest, m);
 }
 
-__global__ void __launch_bounds__(256)
-k_dyn_transform(const VctDynPartsArgs a, int ntri) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= ntri) return;
-    *reinterpret_cast<VctTri9*>(a.pos + (size_t)t * 9) = dyn_part_tri(a, t);
-}
-
-__device__ __forceinline__ VctTri9 dyn_skin_tri(const VctDynSkinArgs& a, int t) {
+__device__ __forceinline__ VctTri9 dyn_moved_tri(const VctDynSkinArgs& a, int t) {
     const VctTri9 rest = *reinterpret_cast<const VctTri9*>(a.rest + (size_t)t * 9);
     VctTri9 out;
 #pragma unroll
@@ -2092,30 +2086,29 @@ __device__ __forceinline__ VctTri9 dyn_skin_tri(const VctDynSkinArgs& a, int t) 
     return out;
 }
 
+// where a triangle's positions come from: the layer's positions as they are, or what dyn_moved_tri needs to make -- and
+// the kernel to store -- them
+enum DynSrc { DYN_SRC_POS, DYN_SRC_PARTS, DYN_SRC_SKIN };
+template <DynSrc SRC> using DynSrcArgs =
+    std::conditional_t<SRC == DYN_SRC_PARTS, VctDynPartsArgs, std::conditional_t<SRC == DYN_SRC_SKIN, VctDynSkinArgs, const float* __restrict__>>;
+
+template <DynSrc SRC>
 __global__ void __launch_bounds__(256)
-k_dyn_skin(const VctDynSkinArgs a, int ntri) {
+k_dyn_move(const DynSrcArgs<SRC> a, int ntri) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= ntri) return;
-    *reinterpret_cast<VctTri9*>(a.pos + (size_t)t * 9) = dyn_skin_tri(a, t);
+    *reinterpret_cast<VctTri9*>(a.pos + (size_t)t * 9) = dyn_moved_tri(a, t);
 }
 
-// what k_dyn_draw_prepare reads: the layer's positions, or what dyn_part_tri (DYN_SRC_PARTS) or dyn_skin_tri
-// (DYN_SRC_SKIN) needs to make and store them
-enum DynSrc { DYN_SRC_POS, DYN_SRC_PARTS, DYN_SRC_SKIN };
-template <DynSrc SRC> using DynPrepareSrc =
-    std::conditional_t<SRC == DYN_SRC_PARTS, VctDynPartsArgs, std::conditional_t<SRC == DYN_SRC_SKIN, VctDynSkinArgs, const float* __restrict__>>;
 template <DynSrc SRC = DYN_SRC_POS>
 __global__ void __launch_bounds__(256)
-k_dyn_draw_prepare(const DynPrepareSrc<SRC> pos, int ntri, float model_scale, float vertex_limit, float* __restrict__ draw_pos,
+k_dyn_draw_prepare(const DynSrcArgs<SRC> pos, int ntri, float model_scale, float vertex_limit, float* __restrict__ draw_pos,
                    float* __restrict__ draw_nrm, float* __restrict__ draw_tan, float* __restrict__ draw_bit) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= ntri) return;
     VctTri9 q;
-    if constexpr (SRC == DYN_SRC_PARTS) {
-        q = dyn_part_tri(pos, t);
-        *reinterpret_cast<VctTri9*>(pos.pos + (size_t)t * 9) = q;
-    } else if constexpr (SRC == DYN_SRC_SKIN) {
-        q = dyn_skin_tri(pos, t);
+    if constexpr (SRC != DYN_SRC_POS) {      // a mover's: make the triangle, store it
+        q = dyn_moved_tri(pos, t);
         *reinterpret_cast<VctTri9*>(pos.pos + (size_t)t * 9) = q;
     } else {
         q = *reinterpret_cast<const VctTri9*>(pos + (size_t)t * 9);
@@ -2301,40 +2294,26 @@ hipError_t vct_launch_dynamic_visibility(const VctRasterArgs& a, const float vie
     return run_visibility(make_raster(a, view_proj, W, H, row0 * VCT_TILE, row1 * VCT_TILE), s);      // no material: no alpha test
 }
 
-hipError_t vct_launch_dynamic_draw_prepare(const float* pos, int32_t ntri, float model_scale, float vertex_limit, float* draw_pos,
-                                           float* draw_nrm, float* draw_tan, float* draw_bit, hipStream_t s) {
+// one thread per dynamic triangle from source `src`: k_dyn_draw_prepare with the draw copy of `prepare`, or -- null, a
+// mover's source only -- k_dyn_move
+template <DynSrc SRC>
+static hipError_t launch_dyn_tris(const DynSrcArgs<SRC>& src, int32_t ntri, const VctDynPrepare* prepare, hipStream_t s) {
     if (ntri <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_dyn_draw_prepare<>, dim3((ntri + 255) / 256), dim3(256), 0, s, pos, ntri, model_scale, vertex_limit,
-                       draw_pos, draw_nrm, draw_tan, draw_bit);
+    const dim3 grid((ntri + 255) / 256), block(256);
+    if (prepare)
+        hipLaunchKernelGGL(k_dyn_draw_prepare<SRC>, grid, block, 0, s, src, ntri, prepare->model_scale, prepare->vertex_limit,
+                           prepare->draw_pos, prepare->draw_nrm, prepare->draw_tan, prepare->draw_bit);
+    else if constexpr (SRC != DYN_SRC_POS)
+        hipLaunchKernelGGL(k_dyn_move<SRC>, grid, block, 0, s, src, ntri);
     return hipGetLastError();
 }
 
-hipError_t vct_launch_dynamic_transform(const VctDynPartsArgs& a, int32_t ntri, hipStream_t s) {
-    if (ntri <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_dyn_transform, dim3((ntri + 255) / 256), dim3(256), 0, s, a, ntri);
-    return hipGetLastError();
+hipError_t vct_launch_dynamic_draw_prepare(const float* pos, int32_t ntri, const VctDynPrepare& prepare, hipStream_t s) {
+    return launch_dyn_tris<DYN_SRC_POS>(pos, ntri, &prepare, s);
 }
 
-hipError_t vct_launch_dynamic_transform_prepare(const VctDynPartsArgs& a, int32_t ntri, float model_scale, float vertex_limit,
-                                                float* draw_pos, float* draw_nrm, float* draw_tan, float* draw_bit, hipStream_t s) {
-    if (ntri <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_dyn_draw_prepare<DYN_SRC_PARTS>, dim3((ntri + 255) / 256), dim3(256), 0, s, a, ntri, model_scale, vertex_limit,
-                       draw_pos, draw_nrm, draw_tan, draw_bit);
-    return hipGetLastError();
-}
-
-hipError_t vct_launch_dynamic_skin(const VctDynSkinArgs& a, int32_t ntri, hipStream_t s) {
-    if (ntri <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_dyn_skin, dim3((ntri + 255) / 256), dim3(256), 0, s, a, ntri);
-    return hipGetLastError();
-}
-
-hipError_t vct_launch_dynamic_skin_prepare(const VctDynSkinArgs& a, int32_t ntri, float model_scale, float vertex_limit,
-                                           float* draw_pos, float* draw_nrm, float* draw_tan, float* draw_bit, hipStream_t s) {
-    if (ntri <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_dyn_draw_prepare<DYN_SRC_SKIN>, dim3((ntri + 255) / 256), dim3(256), 0, s, a, ntri, model_scale, vertex_limit,
-                       draw_pos, draw_nrm, draw_tan, draw_bit);
-    return hipGetLastError();
+hipError_t vct_launch_dynamic_move(const VctDynMoverArgs& a, int32_t ntri, const VctDynPrepare* prepare, hipStream_t s) {
+    return a.is_skin ? launch_dyn_tris<DYN_SRC_SKIN>(a.skin, ntri, prepare, s) : launch_dyn_tris<DYN_SRC_PARTS>(a.parts, ntri, prepare, s);
 }
 
 hipError_t vct_launch_gbuffer_shade(const VctRasterArgs& a, const float view_proj[16], int W, int H, int row0, int row1,

@@ -1010,7 +1010,58 @@ int vct_last_lights_ms(vct_ctx* ctx, float ms[2]);   /* [0] voxel kernel of the 
  * VCT_ERR_INVALID, nothing touched: a NULL context; no dynamic mesh attached; nbones outside 1 ..
  * VCT_DYNAMIC_BONES_MAX; a NULL array (unless both are NULL and nbones is 0); a bone index outside 0 .. nbones-1 or a
  * weight that is NaN or infinite (the message names triangle, corner and slot); parts attached.
- * Known limits: the drawn mesh has no textures, no gloss class and flat (per-face) normals.  With a flag off
+ * Normals (vct_set_dynamic_normals; none by default): the attached dynamic mesh may carry one fp32 normal per triangle
+ * CORNER, nrm[ntri][3][3]; the mesh is a triangle soup, so corners that share a vertex simply carry the same values.  The
+ * drawn mesh then shades smooth: each corner gets a frame of its own in place of the face frame of "Drawing".  All
+ * arithmetic below is fp32, operations in the written order, nothing fused.
+ *   Moved normal  of a corner with given normal n.  No mover attached: n' = n.  Parts: with M the triangle's part matrix
+ *              and A_r = (M[4r], M[4r+1], M[4r+2]) its rows,
+ *                C_0 = A_1 x A_2,  C_1 = A_2 x A_0,  C_2 = A_0 x A_1
+ *              each component a * b - c * d in the component order of the face normal n of "Drawing", and
+ *                n'_r = ((C_r.x * n.x + C_r.y * n.y) + C_r.z * n.z)                    r = 0, 1, 2
+ *              C is the cofactor matrix, not an inverse: cross(A a, A b) = C cross(a, b), so the moved corner normal
+ *              stays on the side of the face normal of the moved positions under ANY matrix, mirrors and non-uniform
+ *              scales included, with no division and no determinant test.  Skin: the same with the corner's blended B
+ *              (Skin, above) in place of M.  A mover whose rest positions have not been moved yet -- between
+ *              vct_set_dynamic_parts / _skin or a vct_update_dynamic_positions and the next
+ *              vct_update_dynamic_transforms, while the current positions ARE the rest positions -- moves nothing: n' = n.
+ *   Frame      of a corner.  (u_f, t_f, b_f) is the face frame exactly as in "Drawing": the face normal of the draw-copy
+ *              positions, then the import's frame construction.  With unit() that construction's unit,
+ *                u_c = unit(n');   d_f = (u_c.x * u_f.x + u_c.y * u_f.y) + u_c.z * u_f.z
+ *              if !(d_f > 0) the corner takes the face frame (u_f, t_f, b_f): NaN, zero, a length that overflows, a
+ *              normal 90 degrees or more from its face and anything else that is not a usable normal.  Nothing is an
+ *              error.  Otherwise
+ *                d = (u_c.x * t_f.x + u_c.y * t_f.y) + u_c.z * t_f.z;   k_i = t_f_i - u_c_i * d;   t_c = unit(k)
+ *              and if t_c is all zero the corner takes the face frame; else
+ *                b_c = (u_c.y * t_c.z - u_c.z * t_c.y,  u_c.z * t_c.x - u_c.x * t_c.z,  u_c.x * t_c.y - u_c.y * t_c.x)
+ *              and the corner's frame is (u_c, t_c, b_c).  The tangent is the FACE's, re-orthogonalised per corner, not a
+ *              fresh frame construction per corner: that one chooses its axis on the largest component, the three
+ *              corners of a triangle can choose differently, and the shade kernel's (T x B) / det over the interpolated
+ *              vectors would pass through det = 0 inside the triangle.  A triangle outside the vertex contract keeps
+ *              nine zero positions and the frames the face rule gives for them.
+ *   Stages     "Drawing" holds unchanged: the stages equal, bit for bit, the ONE static mesh whose appended triangles
+ *              carry these per-corner frames.  Normals have no effect on the shadow map, on any pass with
+ *              VCT_DYNAMIC_DRAW_GBUFFER off, or on the voxel layer: Dn stays the quantised face normal, as for the
+ *              static voxelizer.
+ *   Ownership  the normals belong to the mesh: vct_set_dynamic_mesh drops them on attach, replace and detach.  They
+ *              survive attaching, replacing and detaching a mover; they are in the space of the rest positions while a
+ *              mover is attached and are used as given while none is -- a caller who detaches a mover in a moved pose
+ *              hands over new normals itself.  vct_set_dynamic_normals(ctx, NULL) detaches: the face frames return.
+ * vct_set_dynamic_normals waits for work in flight and allocates everything (one [ntri][9] array), so that an update
+ * allocates nothing, never waits for the stream and copies nothing to the host.  vct_update_dynamic_normals is for
+ * deforming meshes: ordered, and copied on the selected slot's stream, like vct_update_dynamic_positions, with the same
+ * 4-byte alignment and pointer-lifetime rules (vct_mem location).  With a draw flag on, the frames are rebuilt behind
+ * either call, behind every position or transform update, an attach and a flag going on -- in the launch that makes the
+ * draw copy; with no flag on the normals are stored and nothing is launched.  ANY fp32 value is accepted as a normal, host
+ * or device: the accept test on the device decides, the stance of "ANY fp32 matrix is accepted".  With no normals
+ * attached every kernel launched, and its argument block, is the one launched without this paragraph.
+ * vct_get_dynamic_normals: *attached (0: none) and, where nrm is not NULL, the normals as last given.
+ * vct_download_dynamic_frames: the draw frames [ntri][9] each as the shade kernel will read them, with or without
+ * normals attached; waits for the stream; VCT_ERR_INVALID while no draw flag is on for an attached mesh (the arrays do not
+ * exist then).  VCT_ERR_INVALID, nothing touched: a NULL context; no dynamic mesh attached; an update with no normals
+ * attached, a NULL pointer, an unknown location or a pointer that is not 4-byte aligned.
+ * Known limits: the drawn mesh has no textures, no gloss class and flat (per-face) normals unless
+ * vct_set_dynamic_normals attached corner normals (Normals, above).  With a flag off
  * the limit of the stage it names remains: vct_render_shadow_map / vct_render_gbuffer then draw the static mesh only and
  * every kernel launched is the one launched without this paragraph.  The voxel view's albedo / normal sources and
  * vct_download_voxel_attributes show the static pools. */
@@ -1039,6 +1090,10 @@ int vct_last_dynamic_transform_ms(vct_ctx* ctx, float* ms);
 int vct_set_dynamic_skin(vct_ctx* ctx, const int32_t* bone /* [ntri][3][4], host */, const float* weight /* [ntri][3][4], host */,
                          int32_t nbones);
 int vct_get_dynamic_skin(vct_ctx* ctx, int32_t* nbones /* 0: none */, int32_t* bone, float* weight /* may be NULL */);
+int vct_set_dynamic_normals(vct_ctx* ctx, const float* nrm /* [ntri][3][3], host; NULL detaches */);
+int vct_update_dynamic_normals(vct_ctx* ctx, const float* nrm, int32_t location);  /* vct_mem */
+int vct_get_dynamic_normals(vct_ctx* ctx, int32_t* attached, float* nrm /* may be NULL */);
+int vct_download_dynamic_frames(vct_ctx* ctx, float* nrm, float* tan, float* bit /* [ntri][9] each, any may be NULL */);
 
 /* ---- two frames in flight (round 6) -----------------------------------------------------------------
  * The reference's Render() (VCT.h:146-190) issues GL commands; the driver starts frame k + 1 while frame k

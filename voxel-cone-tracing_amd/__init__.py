@@ -85,6 +85,7 @@ ABI_SYMBOLS = [
     "vct_set_dynamic_bounce", "vct_get_dynamic_bounce", "vct_set_dynamic_emission", "vct_get_dynamic_emission",
     "vct_set_dynamic_parts", "vct_get_dynamic_parts", "vct_update_dynamic_transforms", "vct_download_dynamic_positions",
     "vct_last_dynamic_transform_ms", "vct_set_dynamic_skin", "vct_get_dynamic_skin",
+    "vct_set_dynamic_normals", "vct_update_dynamic_normals", "vct_get_dynamic_normals", "vct_download_dynamic_frames",
 ]
 
 
@@ -265,6 +266,10 @@ _lib.vct_download_dynamic_positions.argtypes = [C.c_void_p, C.c_void_p]
 _lib.vct_last_dynamic_transform_ms.argtypes = [C.c_void_p, C.c_void_p]
 _lib.vct_set_dynamic_skin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
 _lib.vct_get_dynamic_skin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.vct_set_dynamic_normals.argtypes = [C.c_void_p, C.c_void_p]
+_lib.vct_update_dynamic_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+_lib.vct_get_dynamic_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.vct_download_dynamic_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.vct_upload_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
 
 
@@ -323,6 +328,17 @@ def _ptr(a):
     if isinstance(a, int):
         return C.c_void_p(a)
     return a.ctypes.data_as(C.c_void_p)
+
+
+def _dynamic_normals_array(self, who, nrm):
+    """nrm as float32 [ntri, 3, 3] (or [ntri, 9]) of the attached mesh, checked before any pointer is handed over"""
+    nrm = np.ascontiguousarray(nrm, np.float32)
+    ntri = getattr(self, "_dyn_ntri", 0)
+    shaped = (nrm.ndim == 3 and nrm.shape[1:] == (3, 3)) or (nrm.ndim == 2 and nrm.shape[1] == 9)
+    if not shaped or (ntri and nrm.shape[0] != ntri):          # (no mesh attached: the library refuses)
+        raise VctError(f"{who}: normals of shape {tuple(nrm.shape)}, the attached dynamic mesh has {ntri} triangles: "
+                       f"[{ntri}, 3, 3] is expected")
+    return nrm
 
 
 class Context:
@@ -870,6 +886,48 @@ class Context:
         pos = np.zeros((ntri, 9), np.float32)
         self._ck(_lib.vct_download_dynamic_positions(self._h, _ptr(pos)), "vct_download_dynamic_positions")
         return pos
+
+    def set_dynamic_normals(self, nrm):
+        """Corner normals of the ATTACHED dynamic mesh, float32 [ntri, 3, 3] (or [ntri, 9]): the drawn mesh then shades
+        smooth -- a frame per corner in place of the face frame.  In the space of the rest positions while parts or a skin
+        are attached (moved by the cofactor matrix on the device), used as given while none is.  Any value is accepted: a
+        corner whose normal is not usable (NaN, zero, 90 degrees or more from its face) takes the face frame.  None
+        detaches.  The mesh drops its normals on attach, replace and detach; a mover attached or detached leaves them."""
+        if nrm is None:
+            self._ck(_lib.vct_set_dynamic_normals(self._h, None), "vct_set_dynamic_normals")
+            return
+        nrm = _dynamic_normals_array(self, "set_dynamic_normals", nrm)
+        self._ck(_lib.vct_set_dynamic_normals(self._h, _ptr(nrm)), "vct_set_dynamic_normals")
+
+    def update_dynamic_normals(self, nrm):
+        """New corner normals of a deforming mesh: a float32 array [ntri, 3, 3] (or [ntri, 9]) or an int device pointer to
+        as many floats.  Asynchronous on the selected slot's stream, ordered like update_dynamic_positions."""
+        if isinstance(nrm, int):
+            self._ck(_lib.vct_update_dynamic_normals(self._h, _ptr(nrm), MEM_DEVICE), "vct_update_dynamic_normals")
+            return
+        nrm = _dynamic_normals_array(self, "update_dynamic_normals", nrm)
+        self._dyn_nrm = nrm          # stays alive until the stream has passed the copy
+        self._ck(_lib.vct_update_dynamic_normals(self._h, _ptr(nrm), MEM_HOST), "vct_update_dynamic_normals")
+
+    def dynamic_normals(self):
+        """The corner normals as last given, float32 [ntri, 3, 3], or None while none are attached."""
+        on = C.c_int32(0)
+        self._ck(_lib.vct_get_dynamic_normals(self._h, C.byref(on), None), "vct_get_dynamic_normals")
+        if not on.value:
+            return None
+        nrm = np.zeros((self.dynamic_info()["ntri"], 3, 3), np.float32)
+        self._ck(_lib.vct_get_dynamic_normals(self._h, C.byref(on), _ptr(nrm)), "vct_get_dynamic_normals")
+        return nrm
+
+    def download_dynamic_frames(self):
+        """(normal, tangent, bitangent) float32 [ntri, 9] each: the drawn mesh's frames as the shade kernel will read them
+        -- the face frames, or the corner frames of set_dynamic_normals.  Needs a draw flag on.  Waits for the stream."""
+        ntri = getattr(self, "_dyn_ntri", 0)
+        if not ntri:
+            raise VctError("download_dynamic_frames: no dynamic mesh attached")
+        out = [np.zeros((ntri, 9), np.float32) for _ in range(3)]
+        self._ck(_lib.vct_download_dynamic_frames(self._h, _ptr(out[0]), _ptr(out[1]), _ptr(out[2])), "vct_download_dynamic_frames")
+        return tuple(out)
 
     def last_dynamic_transform_ms(self):
         """Device ms of the last update_dynamic_transforms' kernel; trace timing must have been on."""

@@ -65,30 +65,34 @@ int launch_merge(vct_ctx* c, bool discard) {
 
 // what the prepare kernels take beside the positions: the vertex contract and the draw arrays of layer `d`
 VctDynPrepare prepare_args(const vct_ctx* c, const VctDynamic& d) {
-    return {c->cfg.model_scale, vct_vertex_limit(c), d.draw.pos.get(), d.draw.nrm.get(), d.draw.tan.get(), d.draw.bit.get()};
-}
-
-// The draw copy and the face frames of layer `d` (vct_ctx.h VctDynamic): allocated if the layer has none, rebuilt from its
-// positions on stream s.  Called where the positions change or a draw flag goes on, never from a raster stage.
-int draw_prepare(vct_ctx* c, VctDynamic& d, hipStream_t s) {
-    const size_t n = vct_dynamic_draw_floats(d.ntri);
-    if (!d.draw.pos)
-        for (VctBuf<float>* b : {&d.draw.nrm, &d.draw.tan, &d.draw.bit, &d.draw.pos}) HIP_TRY(c, b->alloc(n));      // (pos last: it says "all four")
-    HIP_TRY(c, vct_launch_dynamic_draw_prepare(d.pos.get(), d.ntri, prepare_args(c, d), s));
-    return VCT_OK;
+    return {c->cfg.model_scale, vct_vertex_limit(c), d.draw.pos.get(), d.draw.nrm.get(), d.draw.tan.get(), d.draw.bit.get(),
+            d.corner_nrm.get()};
 }
 
 // The layer's positions from the mover's rest positions and matrix table on stream s: the plain kernel, or -- drawn -- the
 // mover's form of the prepare kernel, which goes on to the draw copy and the frames.  The draw arrays exist whenever a
 // flag is on and a mesh is attached (vct_set_dynamic_mesh, vct_set_dynamic_draw), so nothing is allocated here.
-int transform(vct_ctx* c, VctDynamic& d, hipStream_t s) {
+int transform(vct_ctx* c, VctDynamic& d, hipStream_t s, bool drawn) {
     const VctDynamic::Mover& v = d.mover;
     VctDynMoverArgs a = {};
     a.is_skin = v.kind == VCT_MOVER_SKIN;
     if (a.is_skin) a.skin = {v.rest.get(), v.bone.get(), v.weight.get(), v.m.get(), d.pos.get()};
     else a.parts = {v.rest.get(), v.part.get(), v.m.get(), d.pos.get()};
     const VctDynPrepare p = prepare_args(c, d);
-    HIP_TRY(c, vct_launch_dynamic_move(a, d.ntri, c->dyn_settings.draw_flags && d.draw.pos ? &p : nullptr, s));
+    HIP_TRY(c, vct_launch_dynamic_move(a, d.ntri, drawn ? &p : nullptr, s));
+    return VCT_OK;
+}
+
+// The draw copy and the frames of layer `d` (vct_ctx.h VctDynamic): allocated if the layer has none, rebuilt from its
+// positions on stream s.  Called where the positions change or a draw flag goes on, never from a raster stage.  With
+// corner normals AND a mover attached the frames need the mover's matrices (the normals are in rest space), so the
+// mover's own kernel runs again over the rest positions and the table: it rewrites the same positions on the way.
+int draw_prepare(vct_ctx* c, VctDynamic& d, hipStream_t s) {
+    const size_t n = vct_dynamic_draw_floats(d.ntri);
+    if (!d.draw.pos)
+        for (VctBuf<float>* b : {&d.draw.nrm, &d.draw.tan, &d.draw.bit, &d.draw.pos}) HIP_TRY(c, b->alloc(n));      // (pos last: it says "all four")
+    if (d.corner_nrm && d.matrices() && d.mover.moved) return transform(c, d, s, true);
+    HIP_TRY(c, vct_launch_dynamic_draw_prepare(d.pos.get(), d.ntri, prepare_args(c, d), s));
     return VCT_OK;
 }
 
@@ -122,8 +126,13 @@ int attach_mover(vct_ctx* c, const char* who, VctMover kind, int32_t n, const Mo
     HIP_TRY(c, hipStreamSynchronize(s));  // the caller's arrays are free again
     v.kind = kind;
     v.n = n;
-    d.mover = std::move(v);
-    return VCT_OK;
+    std::swap(d.mover, v);
+    if (!d.corner_nrm) return VCT_OK;
+    // corner normals are read in the space of the new rest positions from here on: the frames of a replaced mover's pose
+    // go.  Still all or nothing: a launch that fails puts the previous mover back.
+    const int rc = vct_dynamic_draw_prepare(c);
+    if (rc != VCT_OK) std::swap(d.mover, v);
+    return rc;
 }
 
 // Detaches the mover if it is of `kind` -- the other kind, or none, attached: nothing to do.  The current positions stay.
@@ -133,8 +142,12 @@ int detach_mover(vct_ctx* c, const char* who, VctMover kind) {
     if (d.mover.kind != kind) return VCT_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     PIPE_TRY(vct_synchronize(c));         // an update in flight reads all of its buffers
-    d.mover = VctDynamic::Mover();
-    return VCT_OK;
+    VctDynamic::Mover none;
+    std::swap(d.mover, none);
+    if (!d.corner_nrm) return VCT_OK;
+    const int rc = vct_dynamic_draw_prepare(c);      // corner normals are used as given from here on
+    if (rc != VCT_OK) std::swap(d.mover, none);      // (a launch that fails leaves the mover attached)
+    return rc;
 }
 
 // `bytes` bytes of a caller's array into a fresh allocation of `b` on stream s
@@ -289,9 +302,11 @@ int vct_update_dynamic_positions(vct_ctx* c, const float* pos, int32_t location)
     PIPE_TRY(vct_pipeline_join(c));       // the buffer is shared: the other slot's pass may still read the previous positions
     HIP_TRY(c, hipMemcpyAsync(c->dyn.pos.get(), pos, (size_t)c->dyn.ntri * 9 * sizeof(float),
                               location == VCT_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, cur(c).stream.get()));
-    if (c->dyn.matrices())                // parts or a skin attached: these positions are the new rest positions as well
+    if (c->dyn.matrices()) {              // parts or a skin attached: these positions are the new rest positions as well
         HIP_TRY(c, hipMemcpyAsync(c->dyn.mover.rest.get(), c->dyn.pos.get(), (size_t)c->dyn.ntri * 9 * sizeof(float),
                                   hipMemcpyDeviceToDevice, cur(c).stream.get()));
+        c->dyn.mover.moved = false;
+    }
     return vct_dynamic_draw_prepare(c);   // behind the copy, on its stream: ordered before every stage that draws the mesh
 }
 
@@ -375,8 +390,9 @@ int vct_update_dynamic_transforms(vct_ctx* c, const float* m, int32_t location) 
     hipStream_t s = cur(c).stream.get();
     HIP_TRY(c, hipMemcpyAsync(d.mover.m.get(), m, (size_t)d.matrices() * 12 * sizeof(float),
                               location == VCT_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    d.mover.moved = true;
     HIP_TRY(c, d.mover.timer.begin(s, c->time_traces));
-    PIPE_TRY(transform(c, d, s));
+    PIPE_TRY(transform(c, d, s, c->dyn_settings.draw_flags && d.draw.pos));
     HIP_TRY(c, d.mover.timer.end(s));
     return VCT_OK;
 }
@@ -389,6 +405,69 @@ int vct_download_dynamic_positions(vct_ctx* c, float* pos) {
     HIP_TRY(c, hipSetDevice(c->device));
     PIPE_TRY(vct_synchronize(c));         // the last update may have been issued on the other frame slot's stream
     HIP_TRY(c, hipMemcpy(pos, d.pos.get(), (size_t)d.ntri * 9 * sizeof(float), hipMemcpyDeviceToHost));
+    return VCT_OK;
+}
+
+int vct_set_dynamic_normals(vct_ctx* c, const float* nrm) {
+    if (!c) return VCT_ERR_INVALID;
+    VctDynamic& d = c->dyn;
+    if (const char* why = vct_dynamic_check_normals(d.attached(), d.ntri))
+        return vct_fail(c, VCT_ERR_INVALID, std::string("vct_set_dynamic_normals: ") + why);
+    if (!nrm && !d.corner_nrm) return VCT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    PIPE_TRY(vct_synchronize(c));         // a prepare kernel in flight reads the previous array
+    hipStream_t s = cur(c).stream.get();
+    VctBuf<float> n;                      // all or nothing: the new array (none: detach) in a local until everything has succeeded
+    if (nrm) {
+        const size_t bytes = vct_dynamic_normals_bytes(d.ntri);
+        HIP_TRY(c, alloc_bytes(n, bytes));
+        HIP_TRY(c, hipMemcpyAsync(n.get(), nrm, bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipStreamSynchronize(s));      // the caller's array is free again
+    }
+    std::swap(d.corner_nrm, n);
+    // drawn: the frames of these normals, or the face frames again.  (Under a moved mover this is the mover's own kernel,
+    // which also rewrites the layer's positions with the values they have: everything in flight was waited for above.)
+    const int rc = vct_dynamic_draw_prepare(c);
+    if (rc != VCT_OK) std::swap(d.corner_nrm, n);
+    return rc;
+}
+
+int vct_update_dynamic_normals(vct_ctx* c, const float* nrm, int32_t location) {
+    if (!c) return VCT_ERR_INVALID;
+    VctDynamic& d = c->dyn;
+    if (const char* why = vct_dynamic_check_normals_update(d.attached(), (bool)d.corner_nrm, nrm, location))
+        return vct_fail(c, VCT_ERR_INVALID, std::string("vct_update_dynamic_normals: ") + why);
+    HIP_TRY(c, hipSetDevice(c->device));
+    PIPE_TRY(vct_pipeline_join(c));       // the array is shared: the other slot's prepare kernel may still read the previous normals
+    HIP_TRY(c, hipMemcpyAsync(d.corner_nrm.get(), nrm, vct_dynamic_normals_bytes(d.ntri),
+                              location == VCT_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, cur(c).stream.get()));
+    // behind the copy, on its stream.  (Under a moved mover the prepare is the mover's own kernel, which also rewrites the
+    // layer's positions with the values they have; the join above has waited for the other slot's readers.)
+    return vct_dynamic_draw_prepare(c);
+}
+
+int vct_get_dynamic_normals(vct_ctx* c, int32_t* attached, float* nrm) {
+    if (!c || !attached) return VCT_ERR_INVALID;
+    const VctDynamic& d = c->dyn;
+    *attached = d.corner_nrm ? 1 : 0;
+    if (!*attached || !nrm) return VCT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    PIPE_TRY(vct_synchronize(c));         // the last update may have been issued on the other frame slot's stream
+    HIP_TRY(c, hipMemcpy(nrm, d.corner_nrm.get(), vct_dynamic_normals_bytes(d.ntri), hipMemcpyDeviceToHost));
+    return VCT_OK;
+}
+
+int vct_download_dynamic_frames(vct_ctx* c, float* nrm, float* tan, float* bit) {
+    if (!c) return VCT_ERR_INVALID;
+    const VctDynamic& d = c->dyn;
+    if (const char* why = vct_dynamic_check_frames(d.attached(), c->dyn_settings.draw_flags, (bool)d.draw.pos))
+        return vct_fail(c, VCT_ERR_INVALID, std::string("vct_download_dynamic_frames: ") + why);
+    HIP_TRY(c, hipSetDevice(c->device));
+    PIPE_TRY(vct_synchronize(c));         // the last prepare kernel may have been issued on the other frame slot's stream
+    const float* src[3] = {d.draw.nrm.get(), d.draw.tan.get(), d.draw.bit.get()};
+    float* dst[3] = {nrm, tan, bit};
+    for (int k = 0; k < 3; ++k)
+        if (dst[k]) HIP_TRY(c, hipMemcpy(dst[k], src[k], vct_dynamic_draw_floats(d.ntri) * sizeof(float), hipMemcpyDeviceToHost));
     return VCT_OK;
 }
 
@@ -410,6 +489,7 @@ int vct_set_dynamic_draw(vct_ctx* c, int32_t flags, const float specular[3]) {
         // the draw copy is shared by both slots like the positions: the other slot's pass may still read the previous one
         HIP_TRY(c, hipSetDevice(c->device));
         PIPE_TRY(vct_pipeline_join(c));
+        // (with corner normals under a moved mover this is the mover's own kernel: it rewrites the positions as they are)
         PIPE_TRY(draw_prepare(c, c->dyn, cur(c).stream.get()));
     }
     k.draw_flags = flags;

@@ -487,8 +487,11 @@ struct VctDynamic {
     // while a flag is on and a mesh is attached; k_dyn_draw_prepare rebuilds them behind every copy into `pos`.
     struct DrawCopy {
         VctBuf<float> pos;              // [ntri][9] `pos`, a triangle outside the vertex contract as nine zeros
-        VctBuf<float> nrm, tan, bit;    // [ntri][9] the face frame at all three vertices
+        VctBuf<float> nrm, tan, bit;    // [ntri][9] the face frame at all three vertices, or the corner frames of `corner_nrm`
     } draw;
+    // Corner normals (vct_set_dynamic_normals), empty: none -- the frames are the faces'.  They belong to the mesh like the
+    // emission table, are in the space of the mover's rest positions, and outlive a mover attached, replaced or detached.
+    VctBuf<float> corner_nrm;           // [ntri][3][3] as given
     // Emission of the mesh's materials (vct_set_dynamic_emission): the table and the sums beside `acc`, both or neither.
     struct Emission {
         VctBuf<float> table;            // [nmat][4] (rgb, 0)
@@ -504,6 +507,7 @@ struct VctDynamic {
         VctBuf<float> rest;             // [ntri][9] the positions at the attach or of the last vct_update_dynamic_positions
         VctBuf<float4> m;               // [n][3] rows of the matrices, the context's own copy: 16-byte aligned, as the kernels load them
         VctTimer timer;                 // vct_last_dynamic_transform_ms
+        bool moved = false;             // `pos` is `rest` moved by `m` (a vct_update_dynamic_transforms since the rest was set), not `rest` itself
         // the kind's own arrays, checked on the host; those of the other kind stay empty
         VctBuf<int32_t> part;           // parts: [ntri] in 0 .. n-1
         VctBuf<uint16_t> bone;          // skin: [ntri][3][4] in 0 .. n-1, packed: 24 bytes per triangle

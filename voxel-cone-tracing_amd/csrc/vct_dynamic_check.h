@@ -116,6 +116,36 @@ static inline VctDynamicSkinSizes vct_dynamic_skin_sizes(int32_t ntri, int32_t n
     return s;
 }
 
+// What is wrong with the arguments of an attaching vct_set_dynamic_normals (nrm == NULL detaches), or null.  The values
+// are not looked at: any fp32 value is accepted, and the accept test on the device decides corner by corner.
+static inline const char* vct_dynamic_check_normals(bool attached, int32_t ntri) {
+    if (!attached || ntri < 1) return "no dynamic mesh attached";
+    return nullptr;
+}
+
+// What is wrong with the arguments of vct_update_dynamic_normals, or null.
+static inline const char* vct_dynamic_check_normals_update(bool attached, bool normals, const float* nrm, int32_t location) {
+    if (!attached) return "no dynamic mesh attached";
+    if (!normals) return "no normals attached (vct_set_dynamic_normals)";
+    if (!nrm) return "null normals";
+    if (location != VCT_MEM_HOST && location != VCT_MEM_DEVICE) return "location is neither VCT_MEM_HOST nor VCT_MEM_DEVICE";
+    if ((uintptr_t)nrm & 3u) return "normals need 4-byte alignment";
+    return nullptr;
+}
+
+// What is wrong with a vct_download_dynamic_frames, or null: the frame arrays exist while a draw flag is on for an
+// attached mesh.
+static inline const char* vct_dynamic_check_frames(bool attached, int32_t draw_flags, bool arrays) {
+    if (!attached) return "no dynamic mesh attached";
+    if (!draw_flags || !arrays) return "no draw flag is on (vct_set_dynamic_draw): the frame arrays do not exist";
+    return nullptr;
+}
+
+// Bytes of the corner normals [ntri][3][3] fp32; 0: ntri out of range (ntri <= 2^20: no overflow).
+static inline size_t vct_dynamic_normals_bytes(int32_t ntri) {
+    return ntri < 1 || ntri > VCT_DYNAMIC_TRIS_MAX ? 0 : (size_t)ntri * 9 * sizeof(float);
+}
+
 // What is wrong with the arguments of vct_set_dynamic_draw, or null.  specular null: the constant is 0, 0, 0.
 #define VCT_DYNAMIC_DRAW_ALL (VCT_DYNAMIC_DRAW_SHADOW | VCT_DYNAMIC_DRAW_GBUFFER)
 static inline const char* vct_dynamic_check_draw(int32_t flags, const float* specular) {

@@ -145,6 +145,43 @@ VCT_IMPORT_FN void vct_import_frame(const float n[3], float u[3], float t[3], fl
     b[2] = u[0] * t[1] - u[1] * t[0];
 }
 
+// ---- corner normals of the dynamic mesh (include/vct.h "dynamic mesh", Normals) ----
+// n' = C n with C the cofactor matrix of the top-left 3 x 3 of the row-major 3 x 4 matrix m: with A_r its rows,
+// C_0 = A_1 x A_2, C_1 = A_2 x A_0, C_2 = A_0 x A_1, each component a * b - c * d in the face normal's component order,
+// then n'_r = ((C_r.x * n.x + C_r.y * n.y) + C_r.z * n.z).  No division: cross(A a, A b) = C cross(a, b) for any A.
+VCT_IMPORT_FN void vct_import_cofactor(const float m[12], float c[9]) {
+    for (int r = 0; r < 3; ++r) {
+        const float* a = m + 4 * ((r + 1) % 3);
+        const float* b = m + 4 * ((r + 2) % 3);
+        c[3 * r] = a[1] * b[2] - a[2] * b[1];
+        c[3 * r + 1] = a[2] * b[0] - a[0] * b[2];
+        c[3 * r + 2] = a[0] * b[1] - a[1] * b[0];
+    }
+}
+VCT_IMPORT_FN void vct_import_cofactor_normal(const float c[9], const float n[3], float out[3]) {
+    for (int r = 0; r < 3; ++r) out[r] = (c[3 * r] * n[0] + c[3 * r + 1] * n[1]) + c[3 * r + 2] * n[2];
+}
+
+// The frame of a corner with moved normal n' on a face with frame (uf, tf, bf): u = unit(n'), accepted where
+// uf . u > 0 (NaN, zero, an overflowing length and a normal 90 degrees or more from the face all fail that one test);
+// t = unit(tf - u * (u . tf)), the face's tangent re-orthogonalised, never a fresh axis choice per corner; b = u x t.
+// Returns whether the corner took a frame of its own; false: (u, t, b) is the face frame.
+VCT_IMPORT_FN bool vct_import_corner_frame(const float n[3], const float uf[3], const float tf[3], const float bf[3], float u[3],
+                                           float t[3], float b[3]) {
+    float uc[3], k[3], tc[3];
+    vct_import_unit(n, uc);
+    const float df = (uc[0] * uf[0] + uc[1] * uf[1]) + uc[2] * uf[2];
+    bool own = df > 0.0f;
+    const float d = (uc[0] * tf[0] + uc[1] * tf[1]) + uc[2] * tf[2];
+    for (int i = 0; i < 3; ++i) k[i] = tf[i] - uc[i] * d;
+    vct_import_unit(k, tc);
+    own = own && !(tc[0] == 0.0f && tc[1] == 0.0f && tc[2] == 0.0f);
+    for (int i = 0; i < 3; ++i) { u[i] = own ? uc[i] : uf[i]; t[i] = own ? tc[i] : tf[i]; }
+    const float cb[3] = {uc[1] * tc[2] - uc[2] * tc[1], uc[2] * tc[0] - uc[0] * tc[2], uc[0] * tc[1] - uc[1] * tc[0]};
+    for (int i = 0; i < 3; ++i) b[i] = own ? cb[i] : bf[i];
+    return own;
+}
+
 // The 23 planes of frame pixel (x, y), row 0 at the bottom, of a w x h frame.  Returns whether the pixel has a surface
 // (none: every plane is +0).  Plane 22 is the given shadow value, or 25 * 0.111f where the descriptor has none -- the
 // kernel with a shadow map replaces that by the PCF value.

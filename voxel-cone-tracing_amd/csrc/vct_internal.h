@@ -542,9 +542,13 @@ hipError_t vct_launch_dynamic_visibility(const VctRasterArgs& a, const float vie
 // k_dyn_draw_prepare, one thread per dynamic triangle: the draw copy of `pos` (a triangle with a coordinate v for which
 // !(fabsf(v * model_scale) <= vertex_limit) becomes nine zeros -- a point, culled by the set-up) and the face frame
 // (u, t, b) = vct_import_frame(cross(p1 - p0, p2 - p0)), written to all three vertices of draw_nrm / _tan / _bit.
+// corner_nrm not null (include/vct.h "dynamic mesh", Normals): the NRM instantiation of the same kernel, which reads the
+// triangle's corner normals, moves them with a mover's matrices and writes vct_import_corner_frame per corner.  (Host
+// side only: the kernels take the members one by one, and the forms without normals take what they always took.)
 struct VctDynPrepare {
     float model_scale, vertex_limit;
     float *draw_pos, *draw_nrm, *draw_tan, *draw_bit;      // [ntri][9] each
+    const float* corner_nrm;                               // [ntri][3][3], or null: face frames
 };
 hipError_t vct_launch_dynamic_draw_prepare(const float* pos, int32_t ntri, const VctDynPrepare& prepare, hipStream_t s);
 // Parts of the dynamic mesh (include/vct.h "dynamic mesh", Parts): pos[t] = the rest triangle t moved by the 3 x 4 matrix

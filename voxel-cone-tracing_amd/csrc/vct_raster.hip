@@ -2050,15 +2050,29 @@ __device__ __forceinline__ VctTri9 dyn_transform_tri(const VctTri9& rest, const 
     return out;
 }
 
-__device__ __forceinline__ VctTri9 dyn_moved_tri(const VctDynPartsArgs& a, int t) {
+// NRM (include/vct.h "dynamic mesh", Normals): *nrm holds the triangle's three corner normals in rest space and leaves as
+// the moved normals C n, C the cofactor matrix (vct_import_cofactor) of the matrix that moves the corner's position -- the
+// part's, formed once per triangle, or the skin's blend B of the corner, formed from the B the position arithmetic holds.
+template <bool NRM = false>
+__device__ __forceinline__ VctTri9 dyn_moved_tri(const VctDynPartsArgs& a, int t, VctTri9* nrm = nullptr) {
     const VctTri9 rest = *reinterpret_cast<const VctTri9*>(a.rest + (size_t)t * 9);
     const float4* rows = a.table + 3 * (size_t)a.part[t];
     const float4 r0 = rows[0], r1 = rows[1], r2 = rows[2];
     const float m[12] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, r2.y, r2.z, r2.w};
+    if constexpr (NRM) {
+        float c[9];
+        vct_import_cofactor(m, c);
+#pragma unroll
+        for (int v = 0; v < 3; ++v) {
+            const float n[3] = {nrm->v[3 * v], nrm->v[3 * v + 1], nrm->v[3 * v + 2]};
+            vct_import_cofactor_normal(c, n, &nrm->v[3 * v]);
+        }
+    }
     return dyn_transform_tri(rest, m);
 }
 
-__device__ __forceinline__ VctTri9 dyn_moved_tri(const VctDynSkinArgs& a, int t) {
+template <bool NRM = false>
+__device__ __forceinline__ VctTri9 dyn_moved_tri(const VctDynSkinArgs& a, int t, VctTri9* nrm = nullptr) {
     const VctTri9 rest = *reinterpret_cast<const VctTri9*>(a.rest + (size_t)t * 9);
     VctTri9 out;
 #pragma unroll
@@ -2082,6 +2096,12 @@ __device__ __forceinline__ VctTri9 dyn_moved_tri(const VctDynSkinArgs& a, int t)
         const float x = rest.v[3 * v], y = rest.v[3 * v + 1], z = rest.v[3 * v + 2];
 #pragma unroll
         for (int r = 0; r < 3; ++r) out.v[3 * v + r] = ((B[4 * r] * x + B[4 * r + 1] * y) + B[4 * r + 2] * z) + B[4 * r + 3];
+        if constexpr (NRM) {
+            float c[9];
+            vct_import_cofactor(B, c);
+            const float n[3] = {nrm->v[3 * v], nrm->v[3 * v + 1], nrm->v[3 * v + 2]};
+            vct_import_cofactor_normal(c, n, &nrm->v[3 * v]);
+        }
     }
     return out;
 }
@@ -2100,18 +2120,32 @@ k_dyn_move(const DynSrcArgs<SRC> a, int ntri) {
     *reinterpret_cast<VctTri9*>(a.pos + (size_t)t * 9) = dyn_moved_tri(a, t);
 }
 
-template <DynSrc SRC = DYN_SRC_POS>
+// With corner normals attached (NRM) the source travels with their array: the kernel argument of the NRM = false forms is
+// the source alone, as it was before there were normals.
+template <DynSrc SRC> struct DynNrmSrc {
+    DynSrcArgs<SRC> src;
+    const float* __restrict__ nrm;      // [ntri][3][3] corner normals, rest space under a mover
+};
+template <DynSrc SRC, bool NRM> using DynPrepareSrc = std::conditional_t<NRM, DynNrmSrc<SRC>, DynSrcArgs<SRC>>;
+template <DynSrc SRC> __device__ __forceinline__ const DynSrcArgs<SRC>& dyn_src(const DynSrcArgs<SRC>& a) { return a; }
+template <DynSrc SRC> __device__ __forceinline__ const DynSrcArgs<SRC>& dyn_src(const DynNrmSrc<SRC>& a) { return a.src; }
+
+// NRM: the triangle's corner normals are read as one VctTri9, moved with the positions (dyn_moved_tri) and each corner takes
+// vct_import_corner_frame of its moved normal on the face frame -- the face frame itself where the normal is not usable.
+template <DynSrc SRC = DYN_SRC_POS, bool NRM = false>
 __global__ void __launch_bounds__(256)
-k_dyn_draw_prepare(const DynSrcArgs<SRC> pos, int ntri, float model_scale, float vertex_limit, float* __restrict__ draw_pos,
+k_dyn_draw_prepare(const DynPrepareSrc<SRC, NRM> pos, int ntri, float model_scale, float vertex_limit, float* __restrict__ draw_pos,
                    float* __restrict__ draw_nrm, float* __restrict__ draw_tan, float* __restrict__ draw_bit) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= ntri) return;
-    VctTri9 q;
+    const DynSrcArgs<SRC>& src = dyn_src<SRC>(pos);
+    VctTri9 q, cn;
+    if constexpr (NRM) cn = *reinterpret_cast<const VctTri9*>(pos.nrm + (size_t)t * 9);
     if constexpr (SRC != DYN_SRC_POS) {      // a mover's: make the triangle, store it
-        q = dyn_moved_tri(pos, t);
-        *reinterpret_cast<VctTri9*>(pos.pos + (size_t)t * 9) = q;
+        q = dyn_moved_tri<NRM>(src, t, &cn);
+        *reinterpret_cast<VctTri9*>(src.pos + (size_t)t * 9) = q;
     } else {
-        q = *reinterpret_cast<const VctTri9*>(pos + (size_t)t * 9);
+        q = *reinterpret_cast<const VctTri9*>(src + (size_t)t * 9);
     }
     bool ok = true;
 #pragma unroll
@@ -2126,8 +2160,16 @@ k_dyn_draw_prepare(const DynSrcArgs<SRC> pos, int ntri, float model_scale, float
     float u[3], tg[3], b[3];
     vct_import_frame(n, u, tg, b);
     VctTri9 rn, rt, rb;
+    if constexpr (NRM) {
 #pragma unroll
-    for (int k = 0; k < 9; ++k) { rn.v[k] = u[k % 3]; rt.v[k] = tg[k % 3]; rb.v[k] = b[k % 3]; }
+        for (int v = 0; v < 3; ++v) {
+            const float c[3] = {cn.v[3 * v], cn.v[3 * v + 1], cn.v[3 * v + 2]};
+            vct_import_corner_frame(c, u, tg, b, &rn.v[3 * v], &rt.v[3 * v], &rb.v[3 * v]);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) { rn.v[k] = u[k % 3]; rt.v[k] = tg[k % 3]; rb.v[k] = b[k % 3]; }
+    }
     *reinterpret_cast<VctTri9*>(draw_pos + (size_t)t * 9) = q;
     *reinterpret_cast<VctTri9*>(draw_nrm + (size_t)t * 9) = rn;
     *reinterpret_cast<VctTri9*>(draw_tan + (size_t)t * 9) = rt;
@@ -2300,7 +2342,11 @@ template <DynSrc SRC>
 static hipError_t launch_dyn_tris(const DynSrcArgs<SRC>& src, int32_t ntri, const VctDynPrepare* prepare, hipStream_t s) {
     if (ntri <= 0) return hipSuccess;
     const dim3 grid((ntri + 255) / 256), block(256);
-    if (prepare)
+    if (prepare && prepare->corner_nrm)       // corner normals attached: the NRM form, the source with their array
+        hipLaunchKernelGGL((k_dyn_draw_prepare<SRC, true>), grid, block, 0, s, DynNrmSrc<SRC>{src, prepare->corner_nrm}, ntri,
+                           prepare->model_scale, prepare->vertex_limit, prepare->draw_pos, prepare->draw_nrm, prepare->draw_tan,
+                           prepare->draw_bit);
+    else if (prepare)
         hipLaunchKernelGGL(k_dyn_draw_prepare<SRC>, grid, block, 0, s, src, ntri, prepare->model_scale, prepare->vertex_limit,
                            prepare->draw_pos, prepare->draw_nrm, prepare->draw_tan, prepare->draw_bit);
     else if constexpr (SRC != DYN_SRC_POS)

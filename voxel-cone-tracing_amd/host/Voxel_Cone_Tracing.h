@@ -438,9 +438,28 @@ struct Voxel_Cone_Tracing {
         if (!ctx) return false;
         return check(vct_download_dynamic_positions(ctx, pos), "vct_download_dynamic_positions");
     }
+    // Corner normals of the dynamic mesh (vct_set_dynamic_normals, include/vct.h "dynamic mesh", Normals): one fp32 normal
+    // per triangle corner, [ntri][3][3]; the drawn mesh (DrawDynamicMesh with `gbuffer`) then shades smooth instead of
+    // faceted.  In the space of the rest positions while parts or a skin are attached -- the library moves them with the
+    // positions -- and used as given while none is.  After SetDynamicMesh, which drops them; NULL detaches.
+    // UpdateDynamicNormals hands over new ones for a deforming mesh (asynchronous, like UpdateDynamicMesh);
+    // DownloadDynamicFrames returns the drawn frames [ntri][9] each (any may be NULL) and waits for the stream.
+    bool SetDynamicNormals(const float* nrm) {
+        if (!ctx) return false;
+        return check(vct_set_dynamic_normals(ctx, nrm), "vct_set_dynamic_normals");
+    }
+    bool UpdateDynamicNormals(const float* nrm, int32_t location = VCT_MEM_HOST) {
+        if (!ctx) return false;
+        return check(vct_update_dynamic_normals(ctx, nrm, location), "vct_update_dynamic_normals");
+    }
+    bool DownloadDynamicFrames(float* nrm, float* tan, float* bit) {
+        if (!ctx) return false;
+        return check(vct_download_dynamic_frames(ctx, nrm, tan, bit), "vct_download_dynamic_frames");
+    }
     // Draws the dynamic mesh in the library's own raster stages (vct_set_dynamic_draw): `shadow` -- it casts into the
     // shadow map of DrawDepthTexture() and of every whole GI pass, and every PCF reader sees it; `gbuffer` -- the main
-    // draw shows it, with flat per-face normals, its table's colours and the specular colour `specular` (NULL: black).
+    // draw shows it, with flat per-face normals (or SetDynamicNormals' corner normals), its table's colours and the
+    // specular colour `specular` (NULL: black).
     // Render() under DynamicLight then shows and shadows the object.  After init, before or after SetDynamicMesh: the
     // setting outlives the mesh.
     bool DrawDynamicMesh(bool shadow, bool gbuffer, const float* specular = nullptr) {

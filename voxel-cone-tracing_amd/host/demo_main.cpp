@@ -13,7 +13,8 @@
 //            [--sky-gradient ZR,ZG,ZB;HR,HG,HB;GR,GG,GB[;UX,UY,UZ] | --sky-sh FILE] [--reimport]
 //            [--light X,Y,Z;R,G,B;RADIUS;SRC[;DX,DY,DZ;INNER_DEG;OUTER_DEG]]...
 //            [--dynamic-obj FILE --dynamic-path X0,Y0,Z0;X1,Y1,Z1 --dynamic-draw shadow|gbuffer|both --dynamic-bounce
-//             --dynamic-emission MATERIAL=R,G,B[;MATERIAL=R,G,B...] --dynamic-spin AX,AY,AZ;DEG_PER_FRAME | --dynamic-bend AX,AY,AZ;DEG_PER_FRAME]
+//             --dynamic-emission MATERIAL=R,G,B[;MATERIAL=R,G,B...] --dynamic-spin AX,AY,AZ;DEG_PER_FRAME | --dynamic-bend AX,AY,AZ;DEG_PER_FRAME
+//             --dynamic-smooth]
 // --dynamic-obj FILE: a second Wavefront OBJ as the context's dynamic mesh (Voxel_Cone_Tracing::SetDynamicMesh,
 //   vct_set_dynamic_mesh; flat material colours, its textures are not used), translated along the segment of
 //   --dynamic-path (model units, the OBJ's own; default: it stays where it is) over the run's frames.  Every Render()
@@ -38,6 +39,10 @@
 //   composed with a rotation by f x DEG about the axis through the object's bounding-box centre.  A corner's weight of
 //   bone 1 is clamp((c - lo) / (hi - lo), 0, 1) along the longest axis of the bounding box, bone 0 has the rest: the
 //   object bends.  Not with --dynamic-spin; checked like it.
+//   --dynamic-smooth: the drawn object shades with the OBJ's vertex normals (its vn records, or the reader's area-weighted
+//   ones) instead of face normals (Voxel_Cone_Tracing::SetDynamicNormals, vct_set_dynamic_normals); alone, or with
+//   --dynamic-path, --dynamic-spin or --dynamic-bend: the library moves the normals with the parts or the skin.  Needs
+//   --dynamic-draw gbuffer|both; checked before a GPU is touched.
 //
 // --light SPEC (repeatable, up to 64): a local light (Voxel_Cone_Tracing::SetLights, vct_set_lights) in world units: a point
 //   light at X,Y,Z of colour R,G,B (the factor at distance 1) that reaches RADIUS and whose inverse-square falloff is
@@ -188,6 +193,7 @@ int main(int argc, char** argv) {
     const char* dynamic_emission = nullptr;
     const char* dynamic_spin = nullptr;
     const char* dynamic_bend = nullptr;
+    bool dynamic_smooth = false;
     int cubes[3] = {0, 0, 0};
     bool show_voxels = false;
     int view_source = VCT_VOXVIEW_CURRENT, view_level = 0;
@@ -202,6 +208,7 @@ int main(int argc, char** argv) {
         if (!strcmp(argv[i], "--dynamic-light")) { dynamic_light = true; continue; }
         if (!strcmp(argv[i], "--reimport")) { reimport = true; continue; }
         if (!strcmp(argv[i], "--dynamic-bounce")) { dynamic_bounce = true; continue; }
+        if (!strcmp(argv[i], "--dynamic-smooth")) { dynamic_smooth = true; continue; }
         if (!strcmp(argv[i], "--voxels") && !(i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9')) {
             show_voxels = true;                             // the voxel view: SOURCE[:LEVEL] may follow
             if (i + 1 < argc && strncmp(argv[i + 1], "--", 2)) {
@@ -281,7 +288,7 @@ int main(int argc, char** argv) {
     }
     // --dynamic-obj / --dynamic-path: the file and the segment before a GPU is touched
     float dyn_path[2][3] = {};
-    std::vector<float> dyn_pos, dyn_albedo;
+    std::vector<float> dyn_pos, dyn_albedo, dyn_normals;
     std::vector<int32_t> dyn_material;
     int32_t dyn_ntri = 0, dyn_nmat = 0;
     if (dynamic_path && !dynamic_obj) { fprintf(stderr, "--dynamic-path: needs --dynamic-obj\n"); return 1; }
@@ -292,6 +299,11 @@ int main(int argc, char** argv) {
         if (dyn_draw_flags < 0) { fprintf(stderr, "%s\n", VCT_DEMO_DYNAMIC_DRAW_USAGE); return 1; }
     }
     if (dynamic_bounce && !dynamic_obj) { fprintf(stderr, "--dynamic-bounce: needs --dynamic-obj\n"); return 1; }
+    if (dynamic_smooth)
+        if (const char* why = vct_demo_check_dynamic_smooth(dynamic_obj != nullptr, dyn_draw_flags)) {
+            fprintf(stderr, "%s\n%s\n", why, VCT_DEMO_DYNAMIC_SMOOTH_USAGE);
+            return 1;
+        }
     if (dynamic_emission && !dynamic_obj) { fprintf(stderr, "--dynamic-emission: needs --dynamic-obj\n"); return 1; }
     double spin_axis[3] = {0.0, 0.0, 1.0}, spin_deg = 0.0, spin_centre[3] = {0.0, 0.0, 0.0};
     if (dynamic_spin) {
@@ -334,6 +346,10 @@ int main(int argc, char** argv) {
         vcth_scene_get(obj, dyn_pos.data(), dyn_material.data(), dyn_albedo.data(), unused_specular.data());
         dyn_emission.assign((size_t)dyn_nmat * 3, 0.0f);
         vcth_scene_get_emission(obj, dyn_emission.data());
+        if (dynamic_smooth) {                               // the file's vn, or the reader's area-weighted normals
+            dyn_normals.resize((size_t)dyn_ntri * 9);
+            vcth_scene_get_frames(obj, dyn_normals.data(), nullptr, nullptr);
+        }
         vcth_scene_destroy(obj);
         if (dynamic_emission)
             if (const char* at = vct_demo_parse_dynamic_emission(dynamic_emission, dyn_nmat, dyn_emission)) {
@@ -491,6 +507,8 @@ int main(int argc, char** argv) {
             vct_demo_bend_influences(dyn_pos.data(), (size_t)dyn_ntri, dyn_lo, dyn_hi, bone, weight);
             if (!voxel_cone_tracing.SetDynamicSkin(bone.data(), weight.data(), 2)) return 3;
         }
+        // in the space of the positions just attached -- the rest positions of the part or the skin
+        if (dynamic_smooth && !voxel_cone_tracing.SetDynamicNormals(dyn_normals.data())) return 3;
         // the OBJ's Ke with --dynamic-emission over it (an all-zero table attaches nothing)
         if (!voxel_cone_tracing.SetDynamicEmission(dyn_emission.data(), (size_t)dyn_nmat)) return 3;
         if (dyn_draw_flags && !voxel_cone_tracing.DrawDynamicMesh((dyn_draw_flags & VCT_DYNAMIC_DRAW_SHADOW) != 0,

@@ -159,6 +159,16 @@ static inline const char* vct_demo_parse_dynamic_emission(const char* list, int 
     return nullptr;
 }
 
+// --dynamic-smooth: the --dynamic-obj mesh drawn with the corner normals of its file (vct_set_dynamic_normals) instead of
+// face normals.  Only a mesh that is drawn into the G-buffer shows them, so anything else is a usage error.  Returns
+// what is wrong, or null.
+#define VCT_DEMO_DYNAMIC_SMOOTH_USAGE "--dynamic-smooth (with --dynamic-obj and --dynamic-draw gbuffer|both): the OBJ's vertex normals on the drawn mesh"
+static inline const char* vct_demo_check_dynamic_smooth(bool have_obj, int draw_flags) {
+    if (!have_obj) return "--dynamic-smooth: needs --dynamic-obj";
+    if (draw_flags < 0 || !(draw_flags & VCT_DYNAMIC_DRAW_GBUFFER)) return "--dynamic-smooth: needs --dynamic-draw gbuffer|both";
+    return nullptr;
+}
+
 // --dynamic-spin AX,AY,AZ;DEG_PER_FRAME: the --dynamic-obj mesh as ONE rigid part (vct_set_dynamic_parts), moved by a
 // 3 x 4 matrix per frame (vct_update_dynamic_transforms) instead of a position array per frame: a rotation about the axis
 // through the object's bounding-box centre.  Finite numbers, the axis not zero.  Returns false for anything else.
